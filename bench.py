@@ -5,23 +5,30 @@ One "step" = one pass of the encode hot path (MS, pre-emphasis, LPC analysis + l
 quantisation, int32 FIR cascade: LINNEAmd_EncodeFramesDevice) over one batch of synthetic PCM that is already
 resident in HBM.  At N=1 the batch is BASELINE.json configs[1]: 60 min of 44.1 kHz int16 stereo = 15 504 frames of
 10 240 samples (the last one a 9 280-sample tail).  With N > 1 every rank encodes its own 60-minute track (frames
-shard with no data-path collective): "scaling": "weak".  The decode hot path (configs[2]) is timed right after on
-the encode's own output and reported as decode_frames_per_s; it must reproduce the PCM bit for bit.
+shard with no data-path collective): "scaling": "weak".  With --full the decode hot path (configs[2]) is timed right after
+on the encode's own output and reported as decode_frames_per_s; it must reproduce the PCM bit for bit.
 
 Starting it.  `python bench.py --gpus N` alone starts the N ranks itself (N child processes, one per GPU, from a parent
 that never touches the GPU; rank 0's line is the output; any child's failure is the exit code).  Under a launcher
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`) WORLD_SIZE is set and must equal --gpus.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant encode kernel against HBM as BASELINE.json asks (the path is
-FP64-VALU / dependent-chain bound, see DESIGN.md; `valu_f64` gives that view), `roofline_decode` the dominant decode kernel;
-`cpu_baseline` / `cpu_baseline_decode` time the reference CPU encoder / decoder (oracle/_ref, or the oracle port if absent) on a
-bounded sample of the same workload; `block_at_a_time` is the per-call latency of the unchanged 13-symbol API.
+Prints ONE JSON line (rank 0).  With --full, `roofline` prices the dominant encode kernel against HBM as BASELINE.json asks
+(the path is FP64-VALU / dependent-chain bound; `valu_f64` gives that view), `roofline_decode` the dominant
+decode kernel; `cpu_baseline` / `cpu_baseline_decode` time the reference CPU encoder / decoder (oracle/_ref, or the oracle port
+if absent) on a bounded sample of the same workload; `block_at_a_time` is the per-call latency of the unchanged 13-symbol API.
 
-Everything behind the timed regions is an optional LEG with a deadline of its own (sample parity, CPU baselines, block-at-a-time
-calls, the end-to-end API, the transports).  A leg that raises becomes {"error": ...}; a leg that HANGS is cut off by a watchdog
-thread, which prints the line with what there is and ends the process: the headline is never lost to a sick link.  Control
-traffic at N > 1 (barriers, the MAX of the times, agreement flags) runs on a gloo group; RCCL carries only what north_star gives
-it, the scatter of frame batches and the gather of residuals (transports.rccl_scatter_gather), on a group of its own.
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, warms up, times the K encode steps
+and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed encode step).
+`--full` adds everything else: per-kernel HIP-event times, the extra one-stream step and the rooflines, the timed decode
+steps and their bit-exactness, and the optional legs below.  `--dump-outputs DIR` writes what the last timed step computed
+(a fixed sample of its frames, float64 .npy; see dump_outputs) so that two builds can be compared output for output.
+
+With --full, everything behind the timed regions is an optional LEG with a deadline of its own (sample parity, CPU baselines,
+block-at-a-time calls, the end-to-end API, the transports).  A leg that raises becomes {"error": ...}; a leg that HANGS is cut
+off by a watchdog thread, which prints the line with what there is and ends the process: the headline is never lost to a sick
+link.  Control traffic at N > 1 (barriers, the MAX of the times, agreement flags) runs on a gloo group; RCCL carries only what
+north_star gives it, the scatter of frame batches and the gather of residuals (transports.rccl_scatter_gather), on a group of
+its own.
 """
 import argparse
 import json
@@ -193,6 +200,31 @@ def sample_parity(frames, nsm, res, prm, st, shape, bits, block, preset, ms, ned
     return {"ok": not bad, "frames_compared": len(idx), "mismatching_frames": bad[:16], "checker": "reference" if use_ref else "port",
             "what": "LINNEAmd_PackFrames(GPU params/residual/stats) == CPU EncodeBlock bytes, per frame, fresh handle each",
             "seconds": time.perf_counter() - t0}
+
+
+DUMP_BYTES = 60_000_000             # --dump-outputs: payload of all the .npy files together
+
+
+def dump_outputs(dirname, res, prm, st, nsm, seed=0x4C4E4E):
+    """--dump-outputs: what a caller of the timed path (LINNEAmd_EncodeFramesDevice) receives -- residual [F][C][S], parameters
+    [F][C][PARAM_WORDS], statistics [F][C][STAT_WORDS] -- for a fixed, seeded sample of the batch's frames that fits DUMP_BYTES
+    (always the first frame and the last, ragged one), as float64 (exact for the int32 words).  frame_index.npy and
+    num_samples.npy say which frames they are and how many samples each holds.  The same arguments give the same files."""
+    F, nch, S = res.shape
+    per_frame = 8 * (nch * (S + prm.shape[2] + st.shape[2]) + 2)
+    n = max(1, min(F, DUMP_BYTES // per_frame))
+    if n >= F:
+        idx = np.arange(F)
+    else:
+        rng = np.random.default_rng(seed)
+        mid = rng.choice(np.arange(1, F - 1), size=max(0, n - 2), replace=False) if F > 2 else np.array([], dtype=np.int64)
+        idx = np.unique(np.concatenate([[0, F - 1], mid]).astype(np.int64))
+    sel = torch.as_tensor(idx, device=res.device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in (("residual", res), ("params", prm), ("stats", st)):
+        np.save(os.path.join(dirname, name + ".npy"), t.index_select(0, sel).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "frame_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "num_samples.npy"), np.asarray(nsm)[idx].astype(np.float64))
 
 
 def _run_threads(work, n):
@@ -590,6 +622,11 @@ def parse_args(argv):
     ap.add_argument("--tracks", type=int, default=1, help="tracks per GPU in ONE batch, each --minutes long with its own ragged tail "
                     "(BASELINE configs[3]: --tracks 1024 --minutes 3 on 8 GPUs = 128 per GPU)")
     ap.add_argument("--leg-seconds", type=float, default=60.0, help="deadline of an optional leg (the CPU baselines and the end-to-end leg get twice as long)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel times and the rooflines, the decode step, "
+                    "the sampled parity check, the CPU baselines, the block-at-a-time and end-to-end API legs, the transports "
+                    "(without it a run sets up, warms up, times the encode steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (residual, "
+                    "parameters, statistics of a fixed sample of frames) as DIR/<name>.npy, float64")
     return ap.parse_args(argv)
 
 
@@ -654,7 +691,7 @@ def worker(args):
     res = torch.empty_like(frames)
     prm = torch.zeros((F, nch, linne_amd.PARAM_WORDS), dtype=torch.int32, device=dev)
     st = torch.zeros((F, nch, linne_amd.STAT_WORDS), dtype=torch.float64, device=dev)
-    work = torch.empty_like(frames)
+    work = torch.empty_like(frames) if args.full else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -690,24 +727,59 @@ def worker(args):
             buf.copy_(res)
         ctx.decode_frames(shape, buf, prm, nsm)
 
+    def finish():
+        guard.emit()
+        ctx.close()
+        if world > 1:
+            # leave together; the process groups are not torn down collectively (a communicator that has seen a failed leg may hang in
+            # its destructor) -- the line is out, the processes just end
+            guard.run("final_barrier", 30, lambda: dist.barrier() or {})
+            sys.stdout.flush(); sys.stderr.flush()
+            os._exit(guard.exit_code)
+        if guard.exit_code:
+            sys.exit(guard.exit_code)
+
     for _ in range(args.warmup):
         encode_step()
     barrier()
-    ctx.enable_timing(True)
+    ctx.enable_timing(args.full)            # per-kernel HIP events: --full only
     kern_ms = {k: 0.0 for k in KERNEL_KINDS}
     kern_launches = {k: 0 for k in KERNEL_KINDS}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         encode_step()
-        torch.cuda.synchronize()            # per-step sync so the per-kernel events of this step can be read
-        for k in ENCODE_KINDS:
-            m = ctx.last_ms(k)
-            if m > 0:
-                kern_ms[k] += m
-                kern_launches[k] += ctx.last_launches(k)
+        torch.cuda.synchronize()            # per-step sync (so the per-kernel events of this step can be read)
+        if args.full:
+            for k in ENCODE_KINDS:
+                m = ctx.last_ms(k)
+                if m > 0:
+                    kern_ms[k] += m
+                    kern_launches[k] += ctx.last_launches(k)
     barrier()
     enc_s = red_max(time.perf_counter() - t0)
     ctx.enable_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, prm, st, nsm)
+
+    # ---- the headline: what every run prints
+    if rank == 0:
+        enc_fps = F * world * args.steps / enc_s
+        guard.line = {
+            "metric": "frames/sec encode (-m 7) + decode, 44.1 kHz stereo, bit-exact; 1/2/4/8 GPU",
+            "value": enc_fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": enc_s / args.steps * 1e3, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"encode -m {args.preset}: {args.tracks} x {args.minutes:g} min {rate / 1000:g} kHz int{bits} {nch}-channel per GPU = {F} frames of {block} samples "
+                                   f"(tail {int(nsm[-1])}), MS {'on' if ms else 'off'}, PCM resident in HBM; decode = inverse hot path on the encode output",
+                       "frames_per_gpu": F, "channels": nch, "preset": args.preset, "tracks_per_gpu": args.tracks, "sharding": f"{world * args.tracks} independent track(s), {args.tracks} per GPU"},
+            "ranks": world, "control_backend": "gloo" if world > 1 else None, "transfer_backend": (backend if world > 1 else None),
+            "full": args.full,
+        }
+    if not args.full:
+        if rank == 0:
+            guard.line["full_note"] = "the headline only: the decode step, per-kernel figures, parity, CPU baselines, API and transport legs come with --full"
+        finish()
+        return
 
     # One more step, UNTIMED, on ONE compute stream: with the default two streams a kernel's HIP-event span includes what the other
     # half's kernels took of the GPU beside it, so the spans of the timed steps overlap and add up to ~2x the step.  This step's
@@ -847,15 +919,7 @@ def worker(args):
                         "sustains 32.4 TFLOP/s of unfused FP64 mul+add on this GPU (profiles/r01_dp_rate.txt), 63 with FMA; the multiply-add "
                         "count per channel-frame is DESIGN.md's figure for -m 7 (a constant, not a counter)"} if args.preset == 7 else None
         breakdown = {KERNEL_KINDS[k]: round(kern_ms[k] / args.steps, 3) for k in KERNEL_KINDS if kern_ms[k] > 0}
-        guard.line = {
-            "metric": "frames/sec encode (-m 7) + decode, 44.1 kHz stereo, bit-exact; 1/2/4/8 GPU",
-            "value": enc_fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": enc_s / args.steps * 1e3, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"encode -m {args.preset}: {args.tracks} x {args.minutes:g} min {rate / 1000:g} kHz int{bits} {nch}-channel per GPU = {F} frames of {block} samples "
-                                   f"(tail {int(nsm[-1])}), MS {'on' if ms else 'off'}, PCM resident in HBM; decode = inverse hot path on the encode output",
-                       "frames_per_gpu": F, "channels": nch, "preset": args.preset, "tracks_per_gpu": args.tracks, "sharding": f"{world * args.tracks} independent track(s), {args.tracks} per GPU"},
-            "ranks": world, "control_backend": "gloo" if world > 1 else None, "transfer_backend": (backend if world > 1 else None),
+        guard.line.update({
             "decode_frames_per_s": dec_fps, "decode_ms_per_step": dec_s / args.steps * 1e3, "decode_bit_exact": ok,
             "decode_input": f"the decode is in place: each of the first {DECODE_COPIES} timed steps decodes a resident copy of the residual made before the timed region (later steps restore theirs inside it); every step's output is compared with the PCM",
             "encode_sample_parity": None, "encode_sample_parity_detail": None,
@@ -870,7 +934,7 @@ def worker(args):
             "transports_note": "value = the hot path with every rank's shard resident in its own HBM (contract: inputs resident when the timed "
                                "region starts); transports = the same work with the data starting elsewhere: in pinned host memory of each rank "
                                "(direct_h2d) or in rank 0's HBM (rccl_scatter_gather, N > 1), transfers inside the timed region",
-        }
+        })
     line = guard.line
 
     # ---- leg: sampled parity against the CPU reference, on EVERY rank's own shard
@@ -1000,16 +1064,7 @@ def worker(args):
             if e2e and e2e.get("decode_whole_frames_per_s"):
                 line["speedup_decode_end_to_end_vs_cpu_baseline"] = e2e["decode_whole_frames_per_s"] / cpud["value"]
             line["decode_hot_path_resident_over_cpu_decodeblock"] = line["decode_frames_per_s"] / cpud["value"]
-    guard.emit()
-    ctx.close()
-    if world > 1:
-        # leave together; the process groups are not torn down collectively (a communicator that has seen a failed leg may hang in
-        # its destructor) -- the line is out, the processes just end
-        guard.run("final_barrier", 30, lambda: dist.barrier() or {})
-        sys.stdout.flush(); sys.stderr.flush()
-        os._exit(guard.exit_code)
-    if guard.exit_code:
-        sys.exit(guard.exit_code)
+    finish()
 
 
 if __name__ == "__main__":

@@ -24,11 +24,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """the real reference library, when oracle/_ref was built (it is prebuilt for the GPU box)"""
-    from refs import Reference, reference_available
-    if not reference_available():
-        pytest.skip("oracle/_ref/liblinne_ref.so not built")
-    return Reference()
+    """the real reference's answers for the tests' inputs (encode_whole, decode_whole, its CLI's output files), recorded from
+    oracle/_ref by tests/golden/make_reference_golden.py: no build of the reference is needed to run the tests"""
+    from refs import RecordedReference
+    return RecordedReference()
 
 
 @pytest.fixture(scope="session")

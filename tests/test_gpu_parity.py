@@ -106,7 +106,7 @@ def test_lnn_bytes_music_with_tail(product, oracle, reference):
     ret, dec = product.decode_whole(mine)
     assert ret == 0 and np.array_equal(dec, x)
     ret, dec = reference.decode_whole(mine)
-    assert ret == 0 and np.array_equal(dec, x)
+    assert ret == 0 and dec == x
 
 
 def test_decode_errors(product, oracle):
@@ -251,43 +251,38 @@ def test_device_rice_plan_equals_host_search(ctx, nch, bits, block, preset, tail
     assert a == c
 
 
-def test_own_cli_matches_the_reference_cli(tmp_path):
+def test_own_cli_matches_the_reference_cli(tmp_path, reference):
     """tools/cli (own WAV reader/writer, own option parsing) on liblinne_amd.so: the .lnn it writes -- whole-stream and
     block-at-a-time -- equals the reference CLI's byte for byte, decoding gives the reference's WAV, and --batch runs
-    several files through one handle (BASELINE config 4's many-track use)"""
+    several files through one handle (BASELINE config 4's many-track use).  What the reference CLI writes for these files is
+    recorded in tests/golden/reference_answers.json (tests/golden/make_reference_golden.py ran oracle/_ref/linne_ref)"""
     import os
     import shutil
     import subprocess
     from refs import ROOT
-    cli, refcli = os.path.join(ROOT, "linne_amd", "linne_amd_cli"), os.path.join(ROOT, "oracle", "_ref", "linne_ref")
-    if not (os.path.exists(cli) and os.path.exists(refcli)):
-        pytest.skip("CLI binaries not built")
+    cli = os.path.join(ROOT, "linne_amd", "linne_amd_cli")
+    if not os.path.exists(cli):
+        pytest.skip("CLI binary not built")
     wav = os.path.join(ROOT, "tests", "golden", "ref_16bit_2ch.wav")
     wav2 = os.path.join(ROOT, "tests", "golden", "ref_a.wav")
-    ref_lnn, mine, mine_b = str(tmp_path / "ref.lnn"), str(tmp_path / "mine.lnn"), str(tmp_path / "mine_b.lnn")
-    subprocess.run([refcli, "-e", "-m", "7", wav, ref_lnn], check=True, stdout=subprocess.DEVNULL)
+    mine, mine_b = str(tmp_path / "mine.lnn"), str(tmp_path / "mine_b.lnn")
     subprocess.run([cli, "-e", "-m", "7", wav, mine], check=True, stdout=subprocess.DEVNULL)
     subprocess.run([cli, "-e", "--mode=7", "-B", "-q", wav, mine_b], check=True, stdout=subprocess.DEVNULL)
-    want = open(ref_lnn, "rb").read()
+    want = reference.cli(["-e", "-m", "7"], open(wav, "rb").read())
     assert open(mine, "rb").read() == want and open(mine_b, "rb").read() == want
-    ref_wav, my_wav = str(tmp_path / "ref.wav"), str(tmp_path / "mine.wav")
-    subprocess.run([refcli, "-d", ref_lnn, ref_wav], check=True, stdout=subprocess.DEVNULL)
+    my_wav = str(tmp_path / "mine.wav")
     subprocess.run([cli, "-d", mine, my_wav], check=True, stdout=subprocess.DEVNULL)
-    assert open(my_wav, "rb").read() == open(ref_wav, "rb").read()
+    assert open(my_wav, "rb").read() == reference.cli(["-d"], open(mine, "rb").read())
     # batch: two different files (different formats) through one encoder handle, then one decoder handle
     out = tmp_path / "batch"; out.mkdir()
     shutil.copy(wav, tmp_path / "one.wav"); shutil.copy(wav2, tmp_path / "two.wav")
     subprocess.run([cli, "-e", "-m", "5", "-q", "--batch", str(out), str(tmp_path / "one.wav"), str(tmp_path / "two.wav")], check=True)
     for name, src in (("one", wav), ("two", wav2)):
-        r = str(tmp_path / (name + "_ref.lnn"))
-        subprocess.run([refcli, "-e", "-m", "5", src, r], check=True, stdout=subprocess.DEVNULL)
-        assert (out / (name + ".lnn")).read_bytes() == open(r, "rb").read(), name
+        assert (out / (name + ".lnn")).read_bytes() == reference.cli(["-e", "-m", "5"], open(src, "rb").read()), name
     back = tmp_path / "back"; back.mkdir()
     subprocess.run([cli, "-d", "-q", "--batch", str(back), str(out / "one.lnn"), str(out / "two.lnn")], check=True)
     for name in ("one", "two"):
-        r = str(tmp_path / (name + "_ref.wav"))
-        subprocess.run([refcli, "-d", str(out / (name + ".lnn")), r], check=True, stdout=subprocess.DEVNULL)
-        assert (back / (name + ".wav")).read_bytes() == open(r, "rb").read(), name
+        assert (back / (name + ".wav")).read_bytes() == reference.cli(["-d"], (out / (name + ".lnn")).read_bytes()), name
 
 
 def _params_from_tap(tap, preset, nch):
@@ -553,31 +548,42 @@ def test_batch_with_more_length_runs_than_the_run_table_holds(ctx, oracle, monke
         assert np.array_equal(dec[f][:, :n], frames[f][:, :n])
 
 
-def test_decode_whole_of_a_stream_with_many_distinct_block_lengths(product, reference):
-    """a valid .lnn written by EncodeBlock calls of varying num_samples (linne_encoder.c:774-862 accepts any length up to the
-    block size): 48 distinct block lengths in one DecodeWhole group.  The decoder takes the lengths from the stream
-    (linne_decoder.c:671-742) and must not care how many different ones there are"""
+def many_block_lengths():
+    """(x, lens): 48 distinct block lengths of one stereo stream, blocks of up to 4096 samples"""
+    lens = [4096 - 8 * i - (i % 3) for i in range(48)]
+    return music(2, sum(lens), 16, seed=123), lens
+
+
+def stream_of_blocks(api, x, bits, rate, block, preset, ms, lens):
+    """header + one LINNEEncoder_EncodeBlock call per entry of `lens`, through the public API of `api` (a LinneApi)"""
     import ctypes as C
     from refs import _planar_ptrs, _RefHeader
-    nch, bits, block, preset = 2, 16, 4096, 7
-    lens = [4096 - 8 * i - (i % 3) for i in range(48)]
-    total = sum(lens)
-    x = music(nch, total, bits, seed=123)
-    enc = reference.new_encoder(nch, bits, 44100, block, preset, True)
-    hdr = _RefHeader(1, 2, nch, total, 44100, bits, block, preset, 1)
+    nch, total = x.shape[0], sum(lens)
+    enc = api.new_encoder(nch, bits, rate, block, preset, ms)
+    hdr = _RefHeader(1, 2, nch, total, rate, bits, block, preset, int(ms))
     out = np.zeros(total * nch * 8 + 65536, dtype=np.uint8)
-    assert reference.L.LINNEEncoder_EncodeHeader(C.byref(hdr), out.ctypes.data, out.size) == 0
+    assert api.L.LINNEEncoder_EncodeHeader(C.byref(hdr), out.ctypes.data, out.size) == 0
     off, prog = 30, 0
     for n in lens:
         ptrs, keep = _planar_ptrs(x[:, prog:prog + n])
         osz = C.c_uint32(0)
-        assert reference.L.LINNEEncoder_EncodeBlock(enc, ptrs, n, out.ctypes.data + off, out.size - off, C.byref(osz)) == 0
+        assert api.L.LINNEEncoder_EncodeBlock(enc, ptrs, n, out.ctypes.data + off, out.size - off, C.byref(osz)) == 0
         off += osz.value
         prog += n
-    reference.L.LINNEEncoder_Destroy(enc)
-    stream = out[:off].tobytes()
+    api.L.LINNEEncoder_Destroy(enc)
+    return out[:off].tobytes()
+
+
+def test_decode_whole_of_a_stream_with_many_distinct_block_lengths(product, reference):
+    """a valid .lnn written by EncodeBlock calls of varying num_samples (linne_encoder.c:774-862 accepts any length up to the
+    block size): 48 distinct block lengths in one DecodeWhole group.  The decoder takes the lengths from the stream
+    (linne_decoder.c:671-742) and must not care how many different ones there are.  The stream is the reference's: written
+    here through this library's EncodeBlock, it must equal what the reference's EncodeBlock calls wrote"""
+    x, lens = many_block_lengths()
+    stream = stream_of_blocks(product, x, 16, 44100, 4096, 7, True, lens)
+    assert stream == reference.encode_block_lengths(x, 16, 44100, 4096, 7, True, lens)
     ret, want = reference.decode_whole(stream)
-    assert ret == 0 and np.array_equal(want, x)
+    assert ret == 0 and want == x
     ret, got = product.decode_whole(stream)
     assert ret == 0 and np.array_equal(got, x)
 
@@ -654,6 +660,12 @@ def test_device_rice_emission_equals_the_host_coder(ctx, monkeypatch, nch, bits,
         assert int(off[-1]) == int(((nbits.astype(np.uint64) + 63) // 64 * 8).sum())
 
 
+def emission_input(block):
+    parts = [music(2, 7 * block, 16, seed=41), np.zeros((2, block), dtype=np.int32), waveform("white_noise", 2, 2 * block, 16, seed=6),
+             music(2, 3 * block + 1500, 16, seed=42)]
+    return np.concatenate(parts, axis=1)
+
+
 @pytest.mark.parametrize("emit", ["0", "1"])
 def test_whole_stream_with_and_without_device_emission(product, oracle, reference, monkeypatch, emit):
     """LINNEEncoder_EncodeWhole stages 16-bit PCM as int16 and lets the device write the Rice codes (LINNE_AMD_EMIT, default 1);
@@ -661,9 +673,7 @@ def test_whole_stream_with_and_without_device_emission(product, oracle, referenc
     monkeypatch.setenv("LINNE_AMD_EMIT", emit)
     monkeypatch.setenv("LINNE_AMD_GROUP", "3")
     block = 4096
-    parts = [music(2, 7 * block, 16, seed=41), np.zeros((2, block), dtype=np.int32), waveform("white_noise", 2, 2 * block, 16, seed=6),
-             music(2, 3 * block + 1500, 16, seed=42)]
-    x = np.concatenate(parts, axis=1)
+    x = emission_input(block)
     mine = product.encode_whole(x, 16, 44100, block, 7, True)
     assert mine == reference.encode_whole(x, 16, 44100, block, 7, True)
     x24 = music(3, 5 * 2048 + 99, 24, seed=43)

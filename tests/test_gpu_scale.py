@@ -496,7 +496,7 @@ def test_the_default_split_at_the_real_frame_size_against_the_oracle(oracle):
 
 
 def test_bench_two_rank_rehearsal_line_is_complete(tmp_path):
-    """`python bench.py --gpus 2` on the one-GPU box (both ranks on device 0, transfers over gloo: BENCH_BACKEND=gloo -- a rehearsal of
+    """`python bench.py --full --gpus 2` on the one-GPU box (both ranks on device 0, transfers over gloo: BENCH_BACKEND=gloo -- a rehearsal of
     the N > 1 path, not an RCCL measurement).  The line an 8-GPU run would be judged by must be complete: the reference's CPU encoder
     and decoder timed in the SAME run (north_star; libs/linne_encoder/src/linne_encoder.c:774-862, libs/linne_decoder/src/linne_decoder.c:564-668),
     parity on every rank, the N = 1 figures of the transport legs and the ratios over them."""
@@ -506,7 +506,7 @@ def test_bench_two_rank_rehearsal_line_is_complete(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--minutes", "4", "--steps", "2", "--cpu-frames-per-thread", "8", "--scratch-gib", "8"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--minutes", "4", "--steps", "2", "--cpu-frames-per-thread", "8", "--scratch-gib", "8"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
