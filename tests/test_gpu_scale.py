@@ -387,11 +387,14 @@ def test_whole_stream_api_over_several_devices(product, oracle, monkeypatch, dev
 
 
 @pytest.mark.parametrize("preset,nch,bits", [(0, 2, 16), (2, 1, 16), (4, 2, 24), (5, 8, 16), (7, 2, 16)])
-def test_decode_throughput_forms_at_the_batch_sizes_that_pick_them(preset, nch, bits):
+def test_decode_throughput_forms_at_the_batch_sizes_that_pick_them(oracle, preset, nch, bits):
     """DecodeFramesDevice with nothing forced on batches of > 20 480 channel-frames (short blocks keep them cheap): k_synth_rows for
     the long layer of every preset family (32 / 64 / 128 taps), k_synth_rows8 for the layers of <= 16 taps, k_deemph_lr with and without
     the fused MS -> LR (1, 2 and 8 channels), several rounds of waves per SIMD, frames of a dozen lengths in the batch.  decode(encode(x))
-    must be x, and what lies behind a frame's end must stay."""
+    must be x, and what lies behind a frame's end must stay.  Before that, each side against the oracle on every frame: the product's
+    encode output, and the decode of the oracle's own residual and parameters against the oracle's synthesis (a wrong but
+    self-consistent residual and parameter pair passes the round trip alone)."""
+    from test_gpu_batch_forms import OracleBatch, check_decode, check_encode, marked as with_sentinel
     for v in ("LINNE_AMD_DECODE_KERNEL", "LINNE_AMD_DECODE_ROWS8"):
         assert v not in os.environ
     block = 1024
@@ -406,10 +409,16 @@ def test_decode_throughput_forms_at_the_batch_sizes_that_pick_them(preset, nch, 
     ns[-1] = 777
     for f in np.flatnonzero(ns < block):
         frames[f, :, int(ns[f]):] = 0
+    batch = {"bases": base, "bmap": np.arange(F) % 64, "ns": ns, "nch": nch, "bits": bits, "block": block, "preset": preset}
+    ob = OracleBatch(oracle, batch, nch >= 2)
     c = linne_amd.Context(0)
     try:
         shape = c.shape(nch, bits, block, preset, nch >= 2)
         res, prm, st = c.encode_frames_host(shape, frames, ns)
+        check_encode(ob, batch, res, prm, st, "encode side: the product's encode output against the oracle")
+        want = with_sentinel(ob.dec[ob.key], ns, block)
+        dec_o = c.decode_frames_host(shape, with_sentinel(ob.res[ob.key], ns, block), ob.prm[ob.key], ns)
+        check_decode(dec_o, want, ns, block, "decode side: the decode of the oracle's residual and parameters against the oracle's synthesis")
         marked = res.copy()
         for f in np.flatnonzero(ns < block):
             marked[f, :, int(ns[f]):] = -123456
