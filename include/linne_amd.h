@@ -269,7 +269,11 @@ int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
  * the long layer (k_synth_big) / of the short layers and the de-emphasis (k_synth_small); 11 is then the one-launch form
  * (k_synthesize), 32 the pipelined latency form (k_synth_pipe: small batches), 33 the throughput form of a layer (k_synth_rows / k_synth_rows8: four
  * or eight channel-frames per wave, what large batches take), 34 the de-emphasis behind it (k_deemph_lr; it includes MS->LR when whole frames
- * lie in a block of 64 rows: no kind 12 then). */
+ * lie in a block of 64 rows: no kind 12 then).  The stream decoder (LINNEAmd_StreamIndexCreate / LINNEAmd_DecodeStreamDevice, each a
+ * call of its own): 37 / 38 counting / writing the block candidates (k_sx_count / k_sx_write), 39 prefix sums (k_sx_scan), 40 successors
+ * (k_sx_succ), 41 pointer doubling (k_sx_jump, a launch per level), 42 / 43 the chain's length / its blocks (k_sx_chain_len / k_sx_chain),
+ * 44 CRC16 and block checks (k_sx_check), 45 parameter records (k_sx_params), 46 the Rice decoder's consumption check (k_sx_rice_check),
+ * 47 placing the range into planar output (k_sx_place); the Rice decoding and the synthesis of a range report as 28 and 11-12, 30-36. */
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_EnableTiming(struct LINNEAmdContext *ctx, int enable);
@@ -304,6 +308,34 @@ int LINNEAmd_PackFramesEmitted(const struct LINNEAmdShape *shape, const int32_t 
         const uint32_t *num_samples, uint32_t num_frames, const int32_t *params, const double *stats, const uint8_t *rice_plan,
         const uint8_t *packed, const uint32_t *offsets, int (*fetch)(void *arg, uint32_t frame, int32_t *dst), void *fetch_arg,
         uint8_t *blocks_out, uint64_t blocks_capacity, uint32_t *block_sizes, double *parcor_state, uint32_t num_threads);
+
+/* ---- .lnn streams held in device memory: a block index built once, then decodes of sample ranges ----
+ * LINNEAmd_StreamIndexCreate reads the 30-byte header through LINNEDecoder_DecodeHeader (the header errors of
+ * LINNEDecoder_DecodeWhole), finds the chain of blocks, checks every block's CRC16 and the checks lnn's block parser makes
+ * after it, all on the device.  d_stream: the device bytes of a whole stream, at any alignment.  Synchronous; returns NULL and
+ * *result = LINNEApiResult when it fails.  The index holds O(blocks) device memory; the stream's bytes stay the caller's and must
+ * be passed again, unchanged, to every decode.
+ *
+ * LINNEAmd_DecodeStreamDevice writes samples [first_sample, first_sample + num_samples) of every channel ch to
+ * d_pcm[ch * pcm_stride + i], int32.  Enqueued on the context's stream and synchronous.  The result:
+ *   - whole range [0, header.num_samples): the LINNEApiResult of LINNEDecoder_DecodeWhole with the CRC check on and a buffer of
+ *     exactly num_samples per channel, and when that is OK the same PCM (samples the stream's blocks do not reach are 0).  The one
+ *     exception: a CRC-valid block no encoder writes (a payload other than its size field says, Rice codes that do not end
+ *     where the block does) may give LINNE_APIRESULT_NG instead; GetLastError names the block.
+ *   - any range: the first failure among blocks 0 .. the last block the range overlaps (damage behind the range does not matter,
+ *     damage before it does: earlier blocks fix where later samples sit); otherwise OK and that slice of the whole decode.  The
+ *     Rice decoder's consumption is checked on the blocks the range decodes.
+ *   - a range beyond num_samples: LINNE_APIRESULT_INVALID_ARGUMENT.
+ * The CRC is always checked.  Scratch (kept by the context) grows with the blocks of the range. */
+struct LINNEAmdStreamIndex;
+struct LINNEHeader;
+struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAmdContext *ctx, const uint8_t *d_stream,
+        uint64_t stream_bytes, int *result);
+void     LINNEAmd_StreamIndexDestroy(struct LINNEAmdStreamIndex *index);
+int      LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, struct LINNEHeader *header);
+uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index);   /* the blocks a whole decode walks */
+int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *index,
+        const uint8_t *d_stream, uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride);
 
 #ifdef __cplusplus
 }

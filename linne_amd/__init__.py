@@ -46,12 +46,21 @@ AMD_SYMBOLS = [
     "LINNEAmd_SlotCapacity", "LINNEAmd_SlotRicePlan", "LINNEAmd_SlotCreateEx", "LINNEAmd_SlotFlags", "LINNEAmd_SlotPcm16", "LINNEAmd_SlotPacked", "LINNEAmd_SlotOffsets",
     "LINNEAmd_SlotFetchResidual", "LINNEAmd_SlotStream", "LINNEAmd_SlotStreamCapacity", "LINNEAmd_SlotBitPos", "LINNEAmd_SlotEndBits", "LINNEAmd_SlotPcm16Valid",
     "LINNEAmd_SlotPcmWidth", "LINNEAmd_SlotDecodeStreamSubmit", "LINNEAmd_SlotFetchPcm32", "LINNEAmd_RiceDecodeDevice", "LINNEAmd_SlotBitEnd", "LINNEAmd_LastDecodeWholeMode", "LINNEAmd_RiceEmitDevice", "LINNEAmd_PackFramesEmitted", "LINNEAmd_RicePlanDevice", "LINNEAmd_PackFramesPlanned", "LINNEAmd_SlotEncodeSubmit", "LINNEAmd_SlotDecodeSubmit", "LINNEAmd_SlotWait",
+    "LINNEAmd_StreamIndexCreate", "LINNEAmd_StreamIndexDestroy", "LINNEAmd_StreamIndexHeader", "LINNEAmd_StreamIndexNumBlocks",
+    "LINNEAmd_DecodeStreamDevice",
 ]
 
 
 class Shape(C.Structure):
     _fields_ = [("num_channels", C.c_uint32), ("bits_per_sample", C.c_uint32), ("num_samples_per_block", C.c_uint32),
                 ("preset", C.c_uint32), ("ch_process_method", C.c_uint32)]
+
+
+class Header(C.Structure):
+    """struct LINNEHeader (include/linne.h)"""
+    _fields_ = [("format_version", C.c_uint32), ("codec_version", C.c_uint32), ("num_channels", C.c_uint16),
+                ("num_samples", C.c_uint32), ("sampling_rate", C.c_uint32), ("bits_per_sample", C.c_uint16),
+                ("num_samples_per_block", C.c_uint32), ("preset", C.c_uint8), ("ch_process_method", C.c_int)]
 
 
 def _load():
@@ -104,6 +113,13 @@ def _load():
     L.LINNEAmd_PackFramesEmitted.argtypes = [C.POINTER(Shape), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                              C.POINTER(C.c_double), C.c_uint32]
+    L.LINNEAmd_StreamIndexCreate.restype = C.c_void_p
+    L.LINNEAmd_StreamIndexCreate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int)]
+    L.LINNEAmd_StreamIndexDestroy.argtypes = [C.c_void_p]
+    L.LINNEAmd_StreamIndexHeader.argtypes = [C.c_void_p, C.POINTER(Header)]
+    L.LINNEAmd_StreamIndexNumBlocks.restype = C.c_uint32
+    L.LINNEAmd_StreamIndexNumBlocks.argtypes = [C.c_void_p]
+    L.LINNEAmd_DecodeStreamDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
     L.LINNEAmd_MultiCreate.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.LINNEAmd_MultiDestroy.argtypes = [C.c_void_p]
@@ -128,7 +144,29 @@ def device_count():
 
 
 class LinneAmdError(RuntimeError):
-    pass
+    """code: the LINNEApiResult of the failing call, where one is known"""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+class StreamIndex:
+    """the block index of one .lnn stream in device memory (Context.index_stream; include/linne_amd.h LINNEAmd_StreamIndexCreate)"""
+
+    def __init__(self, handle, header, num_blocks, nbytes):
+        self.h = handle
+        self.header = header
+        self.num_blocks = num_blocks
+        self.nbytes = nbytes
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.LINNEAmd_StreamIndexDestroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 class Context:
@@ -256,6 +294,57 @@ class Context:
         self._check(lib.LINNEAmd_DecodeFramesDevice(self.h, C.byref(shape), data.data_ptr(), ns.ctypes.data if ns is not None else None,
                                                     F, params.data_ptr()), "DecodeFramesDevice")
         return data
+
+    def _stream_bytes(self, data):
+        """a .lnn stream as a 1-D uint8 CUDA tensor on the context's device: tensors are taken as they are (any offset),
+        bytes / numpy arrays are copied there"""
+        import torch
+        if isinstance(data, torch.Tensor):
+            assert data.dtype == torch.uint8 and data.is_cuda and data.dim() == 1 and data.is_contiguous(), \
+                "a stream tensor is a contiguous 1-D uint8 CUDA tensor"
+            assert data.device.index == self.device, f"the stream is on {data.device}, the context on cuda:{self.device}"
+            return data
+        arr = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        return torch.from_numpy(arr.copy()).to(f"cuda:{self.device}")
+
+    def index_stream(self, data):
+        """block index of a whole .lnn stream (uint8 CUDA tensor, bytes or numpy) -> StreamIndex; raises LinneAmdError (.code =
+        the LINNEApiResult, the header's errors are DecodeWhole's) when the header is unusable"""
+        t = self._stream_bytes(data)
+        self._fence()
+        res = C.c_int(0)
+        h = lib.LINNEAmd_StreamIndexCreate(self.h, C.c_void_p(t.data_ptr()), t.numel(), C.byref(res))
+        if not h:
+            raise LinneAmdError(f"StreamIndexCreate -> {res.value}: {lib.LINNEAmd_GetLastError(self.h).decode()}", res.value)
+        hd = Header()
+        lib.LINNEAmd_StreamIndexHeader(h, C.byref(hd))
+        header = {k: int(getattr(hd, k)) for k, _ in Header._fields_}
+        return StreamIndex(h, header, int(lib.LINNEAmd_StreamIndexNumBlocks(h)), t.numel())
+
+    def decode_stream(self, data, first_sample=0, num_samples=None, index=None):
+        """samples [first_sample, first_sample + num_samples) of a .lnn stream in device memory -> int32 CUDA tensor (C, n), decoded
+        on the device (include/linne_amd.h LINNEAmd_DecodeStreamDevice states the result contract).  Without an index a temporary
+        one is built.  Raises LinneAmdError with .code = the LINNEApiResult"""
+        import torch
+        t = self._stream_bytes(data)
+        own = index is None
+        if own:
+            index = self.index_stream(t)
+        try:
+            assert index.nbytes == t.numel(), "the index was built for a stream of another length"
+            total = index.header["num_samples"]
+            n = total - int(first_sample) if num_samples is None else int(num_samples)
+            nch = index.header["num_channels"]
+            out = torch.empty((nch, max(n, 0)), dtype=torch.int32, device=t.device)
+            self._fence()
+            ret = lib.LINNEAmd_DecodeStreamDevice(self.h, index.h, C.c_void_p(t.data_ptr()), int(first_sample), max(n, 0) if n >= 0 else (1 << 64) - 1,
+                                                  C.c_void_p(out.data_ptr()), out.shape[1])
+            if ret != 0:
+                raise LinneAmdError(f"DecodeStreamDevice -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
+            return out
+        finally:
+            if own:
+                index.close()
 
     def encode_frames_host(self, shape, pcm, num_samples=None):
         """numpy int32 [F][C][S] -> numpy (residual, params, stats)"""

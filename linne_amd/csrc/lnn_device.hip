@@ -23,6 +23,8 @@
 
 #include "linne_amd.h"
 #include "lnn_common.h"
+#include "lnn_host.h"
+#include "linne_decoder.h"
 
 /* the kernels, in pipeline order */
 #include "lnn_dev_common.h"
@@ -42,6 +44,7 @@
 #include "lnn_k_decode_fused.h"
 #include "lnn_k_finalize.h"
 #include "lnn_k_rice.h"
+#include "lnn_k_stream.h"
 
 /* ================================================================================================
  * host side of this TU: context, scratch arena, launch sequences, C-ABI
@@ -89,6 +92,7 @@ struct LINNEAmdContext {
     int pcm16_next;                     /* the next EncodeFramesDevice call reads narrow samples: 1 int16, 2 packed 3-byte (set by the staging slots, cleared by the call) */
     int force_exact;                    /* LINNE_AMD_EXACT=1: every unit-count search runs the exact ordered chains (diff against the certified search) */
     int fir_spec;                       /* LINNE_AMD_SPECULATE (default 1): fuse the one-unit forward into the search of layers 0 .. L-2 */
+    void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
     /* debug / test knobs that select a kernel form per CALL (read_call_knobs: once at the top of an encode / decode call, never
      * inside the chunk loop; production never sets them and gets the batch-size rules) */
@@ -217,6 +221,7 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->d_nsmp) hipFree(ctx->d_nsmp);
     if (ctx->d_plan_nsmp) hipFree(ctx->d_plan_nsmp);
     if (ctx->hstage) hipFree(ctx->hstage);
+    if (ctx->sdec) hipFree(ctx->sdec);
     if (ctx->af_h) hipHostFree(ctx->af_h);
     for (int i = 0; i < LNN_META; i++) { if (ctx->meta_h[i]) hipHostFree(ctx->meta_h[i]); if (ctx->meta_ev[i]) hipEventDestroy(ctx->meta_ev[i]); }
     for (int i = 0; i < ctx->n_rice_pool; i++) { hipStreamSynchronize(ctx->rice_pool[i]); hipStreamDestroy(ctx->rice_pool[i]); }
@@ -1085,26 +1090,16 @@ static int params_in_range(LINNEAmdContext *ctx, const HostShape *hs, uint32_t C
     return LNN_OK;
 }
 
-extern "C" int LINNEAmd_DecodeFramesDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdShape *shape,
-        int32_t *d_data, const uint32_t *h_num_samples, uint32_t num_frames, const int32_t *d_params)
+/* the synthesis of num_frames frames whose lengths are in device memory (d_nsmp): enqueued on the context's stream behind what is
+ * there; records the call's end event when timing is on.  The caller has read the call's knobs and started its spans. */
+static int decode_frames_dev(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape, const HostShape &hs,
+        int32_t *d_data, const uint32_t *d_nsmp, uint32_t num_frames, const int32_t *d_params)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (!shape || !d_data || !d_params) { snprintf(ctx->err, sizeof(ctx->err), "null argument"); return LNN_INVALID_ARGUMENT; }
-    if (num_frames == 0) return LNN_OK;
-    HostShape hs;
-    int ret = shape_info(shape, &hs);
-    if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid shape"); return ret; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    read_call_knobs(ctx);
-    if ((ret = upload_lengths(ctx, shape, h_num_samples, num_frames)) != LNN_OK) return ret;
     DecPlan p; memset(&p, 0, sizeof(p));
     p.C = shape->num_channels; p.S = shape->num_samples_per_block; p.L = hs.L; p.ms = shape->ch_process_method; p.F = num_frames;
     for (uint32_t l = 0; l < hs.L; l++) { p.P[l] = hs.P[l]; p.coef_off[l] = hs.coef_off[l]; }
-    p.data = d_data; p.prm = d_params; p.nsmp = ctx->d_nsmp;
-    ctx->nspans = 0;
+    p.data = d_data; p.prm = d_params; p.nsmp = d_nsmp;
     bool ms_done = false;
-    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
     {   /* layers in reverse order (linne_decoder.c:503-509): long layers one wave per channel-frame, short ones (order <= 16)
          * with lanes = channel-frames; the de-emphasis rides on layer 0's pass */
         const uint32_t CF = num_frames * p.C, gsmall = (CF + 63) / 64;
@@ -1179,6 +1174,24 @@ extern "C" int LINNEAmd_DecodeFramesDevice(struct LINNEAmdContext *ctx, const st
     HIPCHK(ctx, hipGetLastError());
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     return LNN_OK;
+}
+
+extern "C" int LINNEAmd_DecodeFramesDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdShape *shape,
+        int32_t *d_data, const uint32_t *h_num_samples, uint32_t num_frames, const int32_t *d_params)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (!shape || !d_data || !d_params) { snprintf(ctx->err, sizeof(ctx->err), "null argument"); return LNN_INVALID_ARGUMENT; }
+    if (num_frames == 0) return LNN_OK;
+    HostShape hs;
+    int ret = shape_info(shape, &hs);
+    if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid shape"); return ret; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    read_call_knobs(ctx);
+    if ((ret = upload_lengths(ctx, shape, h_num_samples, num_frames)) != LNN_OK) return ret;
+    ctx->nspans = 0;
+    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
+    return decode_frames_dev(ctx, shape, hs, d_data, ctx->d_nsmp, num_frames, d_params);
 }
 
 /* device staging of the host-buffer forms: one allocation kept between calls (a block-at-a-time caller pays no hipMalloc /
@@ -1717,5 +1730,341 @@ extern "C" int LINNEAmd_SlotFetchPcm32(struct LINNEAmdSlot *s, uint32_t num_fram
     if (hipSetDevice(s->ctx->device) != hipSuccess) return LNN_NG;
     if (!s->h_data && hipHostMalloc((void **)&s->h_data, sizeof(int32_t) * (uint64_t)s->shape.num_channels * s->shape.num_samples_per_block * s->max_frames, hipHostMallocDefault) != hipSuccess) { s->h_data = NULL; return LNN_NG; }
     if (hipMemcpy(s->h_data, s->d_data, nb, hipMemcpyDeviceToHost) != hipSuccess) return LNN_NG;
+    return LNN_OK;
+}
+
+/* ================================================================================================
+ * .lnn streams in device memory (lnn_k_stream.h): a block index built once, then decodes of sample ranges
+ * ============================================================================================== */
+struct LINNEAmdStreamIndex {
+    int device;
+    struct LINNEHeader header; struct LINNEAmdShape shape;
+    uint64_t stream_bytes;
+    uint32_t nb;                        /* the blocks a whole decode walks: up to the one that reaches num_samples */
+    uint64_t covered;                   /* the samples they hold (first sample of block nb) */
+    int64_t fail_block;                 /* lowest failing block (nb: the place behind the last one), -1: none */
+    int fail_code; uint64_t fail_off;
+    uint64_t *h_off, *h_first; uint32_t *h_size, *h_type, *h_nsmp;           /* host copies */
+    uint64_t *d_off, *d_first; uint32_t *d_size, *d_type, *d_nsmp; int32_t *d_status; SxTables *d_tab;
+};
+
+extern "C" void LINNEAmd_StreamIndexDestroy(struct LINNEAmdStreamIndex *x)
+{
+    if (!x) return;
+    (void)hipSetDevice(x->device);
+    void *dev[] = { x->d_off, x->d_first, x->d_size, x->d_type, x->d_nsmp, x->d_status, x->d_tab };
+    for (void *p : dev) if (p) (void)hipFree(p);
+    free(x->h_off); free(x->h_first); free(x->h_size); free(x->h_type); free(x->h_nsmp);
+    free(x);
+}
+
+/* device allocations of one index build, freed when it returns (the stream is synchronised by then) */
+struct SxTemp {
+    void *p[8]; int n = 0;
+    ~SxTemp() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
+};
+static int sx_malloc(LINNEAmdContext *ctx, void **out, uint64_t bytes)
+{
+    *out = NULL;
+    HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 8u));
+    return LNN_OK;
+}
+static int sx_temp(LINNEAmdContext *ctx, SxTemp &t, void **out, uint64_t bytes)
+{
+    const int r = sx_malloc(ctx, out, bytes);
+    if (r == LNN_OK) t.p[t.n++] = *out;
+    return r;
+}
+/* device -> host, synchronous, behind the context's stream */
+static int sx_fetch(LINNEAmdContext *ctx, void *dst, const void *src, uint64_t bytes)
+{
+    if (!bytes) return LNN_OK;
+    HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LNN_OK;
+}
+#define SX_TRY(call) do { const int r_ = (call); if (r_ != LNN_OK) return r_; } while (0)
+#define SX_LAUNCH(kind, ...) do { const int sp_ = span_begin(ctx, (kind), ctx->stream); hipLaunchKernelGGL(__VA_ARGS__); span_end(ctx, sp_, ctx->stream); HIPCHK(ctx, hipGetLastError()); } while (0)
+
+static void sx_tables(SxTables *t)
+{
+    lnn_stream_tables(t->crc, &t->root, t->child);
+    /* feeding one zero byte to the CRC state c: (c >> 8) ^ crc[c & 0xFF], a linear map; level k + 1 = level k applied twice */
+    for (uint32_t j = 0; j < 16u; j++) { const uint32_t c = 1u << j; t->shift[0][j] = (uint16_t)((c >> 8) ^ t->crc[c & 0xFFu]); }
+    for (uint32_t k = 1; k < SX_CRC_LEVELS; k++)
+        for (uint32_t j = 0; j < 16u; j++) {
+            uint32_t v = t->shift[k - 1][j], r = 0;
+            for (uint32_t i = 0; i < 16u; i++) if ((v >> i) & 1u) r ^= t->shift[k - 1][i];
+            t->shift[k][j] = (uint16_t)r;
+        }
+}
+
+/* the checks of lnn_parse_block_head before the CRC, for the place behind the chain's last block (no candidate is there) */
+static int sx_head_code(LINNEAmdContext *ctx, const uint8_t *d_stream, uint64_t N, uint64_t q)
+{
+    uint8_t h[6];
+    if (N - q < 11u) return LNN_INSUFFICIENT_DATA;
+    SX_TRY(sx_fetch(ctx, h, d_stream + q, 6));
+    if (h[0] != 0xFFu || h[1] != 0xFFu) return LNN_INVALID_FORMAT;
+    const uint32_t bsize = ((uint32_t)h[2] << 24) | ((uint32_t)h[3] << 16) | ((uint32_t)h[4] << 8) | h[5];
+    if ((uint64_t)bsize + 6u > N - q) return LNN_INSUFFICIENT_DATA;
+    if (bsize < 5u) return LNN_INVALID_FORMAT;
+    snprintf(ctx->err, sizeof(ctx->err), "internal: a block head at byte %llu the index did not find", (unsigned long long)q);
+    return LNN_NG;
+}
+
+static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t *b)
+{
+    const uint64_t N = x->stream_bytes, ns = x->header.num_samples;
+    SxTemp tmp;
+    SxTables h_tab;
+    sx_tables(&h_tab);
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_tab, sizeof(SxTables)));
+    HIPCHK(ctx, hipMemcpyAsync(x->d_tab, &h_tab, sizeof(SxTables), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));             /* (h_tab lives on this frame) */
+    /* candidates, in stream order */
+    uint64_t M = 0, *cand = NULL;
+    if (N > SX_FIRST_BLOCK) {
+        const uint64_t nw = (N - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
+        uint32_t *counts; uint64_t *cofs;
+        SX_TRY(sx_temp(ctx, tmp, (void **)&counts, sizeof(uint32_t) * nw));
+        SX_TRY(sx_temp(ctx, tmp, (void **)&cofs, sizeof(uint64_t) * (nw + 1u)));
+        SX_LAUNCH(37, k_sx_count, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, counts);
+        SX_LAUNCH(39, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nw, cofs);
+        SX_TRY(sx_fetch(ctx, &M, cofs + nw, sizeof(M)));
+        if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
+        if (M) {
+            SX_TRY(sx_temp(ctx, tmp, (void **)&cand, sizeof(uint64_t) * M));
+            SX_LAUNCH(38, k_sx_write, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, (const uint64_t *)cofs, cand);
+        }
+    }
+    uint64_t head = 0, nchain = 0;
+    if (M) SX_TRY(sx_fetch(ctx, &head, cand, sizeof(head)));
+    uint32_t K = 1, *jump = NULL;
+    if (M && head == SX_FIRST_BLOCK) {
+        /* the head's chain: successors, pointer doubling (2^K > M: K levels cover any chain), its length */
+        const uint32_t M32 = (uint32_t)M, g = (uint32_t)((M + 1u + 255u) / 256u);
+        while ((1ull << K) <= M) K++;
+        SX_TRY(sx_temp(ctx, tmp, (void **)&jump, sizeof(uint32_t) * (uint64_t)K * (M + 1u)));
+        SX_LAUNCH(40, k_sx_succ, dim3(g), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, M32, jump);
+        for (uint32_t k = 1; k < K; k++)
+            SX_LAUNCH(41, k_sx_jump, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
+        uint64_t *d_len;
+        SX_TRY(sx_temp(ctx, tmp, (void **)&d_len, sizeof(uint64_t)));
+        SX_LAUNCH(42, k_sx_chain_len, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t *)jump, K, M32, d_len);
+        SX_TRY(sx_fetch(ctx, &nchain, d_len, sizeof(nchain)));
+        nchain++;
+    }
+    /* the chain's blocks and their first samples */
+    const uint64_t nc1 = nchain ? nchain : 1u;
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_off, sizeof(uint64_t) * nc1));
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_first, sizeof(uint64_t) * (nchain + 1u)));
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_size, sizeof(uint32_t) * nc1));
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_type, sizeof(uint32_t) * nc1));
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_nsmp, sizeof(uint32_t) * nc1));
+    SX_TRY(sx_malloc(ctx, (void **)&x->d_status, sizeof(int32_t) * nc1));
+    x->h_off = (uint64_t *)malloc(sizeof(uint64_t) * nc1); x->h_first = (uint64_t *)malloc(sizeof(uint64_t) * (nchain + 1u));
+    x->h_size = (uint32_t *)malloc(sizeof(uint32_t) * nc1); x->h_type = (uint32_t *)malloc(sizeof(uint32_t) * nc1); x->h_nsmp = (uint32_t *)malloc(sizeof(uint32_t) * nc1);
+    if (!x->h_off || !x->h_first || !x->h_size || !x->h_type || !x->h_nsmp) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+    x->h_first[0] = 0;
+    if (nchain) {
+        SX_LAUNCH(43, k_sx_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, (const uint32_t *)jump, K, (uint32_t)M,
+                (uint32_t)nchain, x->d_off, x->d_size, x->d_type, x->d_nsmp);
+        SX_LAUNCH(39, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)x->d_nsmp, nchain, x->d_first);
+        HIPCHK(ctx, hipMemcpyAsync(x->h_off, x->d_off, sizeof(uint64_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(x->h_size, x->d_size, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(x->h_type, x->d_type, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(x->h_nsmp, x->d_nsmp, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
+        SX_TRY(sx_fetch(ctx, x->h_first, x->d_first, sizeof(uint64_t) * (nchain + 1u)));
+    } else
+        HIPCHK(ctx, hipMemcpyAsync(x->d_first, x->h_first, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    /* DecodeWhole's loop ends once the samples reach the header's count (lnn_api.c:772) */
+    uint64_t nb = 0;
+    while (nb < nchain && x->h_first[nb] < ns) nb++;
+    x->nb = (uint32_t)nb; x->covered = x->h_first[nb];
+    x->fail_block = -1; x->fail_code = LNN_OK;
+    if (nb) {
+        SxCheckArgs a;
+        a.b = b; a.N = N; a.off = x->d_off; a.first = x->d_first; a.size = x->d_size; a.type = x->d_type; a.nsmp = x->d_nsmp;
+        a.nb = (uint32_t)nb; a.C = x->shape.num_channels; a.S = x->shape.num_samples_per_block; a.bits = x->shape.bits_per_sample; a.num_samples = ns;
+        a.tab = x->d_tab; a.status = x->d_status;
+        SX_LAUNCH(44, k_sx_check, dim3((uint32_t)((nb + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
+        int32_t *st = (int32_t *)malloc(sizeof(int32_t) * nb);
+        if (!st) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+        const int r = sx_fetch(ctx, st, x->d_status, sizeof(int32_t) * nb);
+        for (uint64_t i = 0; r == LNN_OK && i < nb; i++) if (st[i] != LNN_OK) { x->fail_block = (int64_t)i; x->fail_code = st[i]; x->fail_off = x->h_off[i]; break; }
+        free(st);
+        if (r != LNN_OK) return r;
+    }
+    if (x->fail_block < 0 && nb == nchain && x->covered < ns) {
+        /* the chain ends before the header's sample count: behind its last block lies the end of the stream (DecodeWhole stops
+         * there, the rest of its buffer untouched) or something that is no block head (DecodeWhole fails on it) */
+        const uint64_t q = nb ? x->h_off[nb - 1] + x->h_size[nb - 1] + 6u : SX_FIRST_BLOCK;
+        if (q < N) {
+            const int code = sx_head_code(ctx, b, N, q);
+            if (code == LNN_NG) return code;
+            x->fail_block = (int64_t)nb; x->fail_code = code; x->fail_off = q;
+        }
+    }
+    return LNN_OK;
+}
+
+extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAmdContext *ctx, const uint8_t *d_stream,
+        uint64_t stream_bytes, int *result)
+{
+    int dummy;
+    if (!result) result = &dummy;
+    if (!ctx || !d_stream) { *result = LNN_INVALID_ARGUMENT; return NULL; }
+    ctx->err[0] = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "hipSetDevice(%d) failed", ctx->device); *result = LNN_NG; return NULL; }
+    /* the header as DecodeWhole reads it: LINNEDecoder_DecodeHeader, then SetHeader's checks on a decoder with room for it */
+    uint8_t hb[LINNE_HEADER_SIZE];
+    struct LINNEHeader h;
+    const uint64_t hn = stream_bytes < LINNE_HEADER_SIZE ? stream_bytes : LINNE_HEADER_SIZE;
+    int ret = sx_fetch(ctx, hb, d_stream, hn);
+    if (ret != LNN_OK) { *result = ret; return NULL; }
+    if ((ret = (int)LINNEDecoder_DecodeHeader(hb, (uint32_t)hn, &h)) != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "stream header: LINNEDecoder_DecodeHeader -> %d", ret); *result = ret; return NULL; }
+    {
+        struct LINNEDecoderConfig cfg;
+        memset(&cfg, 0, sizeof(cfg));
+        cfg.max_num_channels = h.num_channels ? h.num_channels : 1u; cfg.max_num_layers = LINNE_AMD_MAX_LAYERS; cfg.max_num_parameters_per_layer = 128; cfg.check_crc = 1;
+        struct LINNEDecoder *dec = LINNEDecoder_Create(&cfg, NULL, 0);
+        if (!dec) { snprintf(ctx->err, sizeof(ctx->err), "LINNEDecoder_Create failed"); *result = LNN_NG; return NULL; }
+        ret = (int)LINNEDecoder_SetHeader(dec, &h);
+        LINNEDecoder_Destroy(dec);
+        if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "stream header: LINNEDecoder_SetHeader -> %d", ret); *result = ret; return NULL; }
+    }
+    LINNEAmdStreamIndex *x = (LINNEAmdStreamIndex *)calloc(1, sizeof(LINNEAmdStreamIndex));
+    if (!x) { *result = LNN_NG; return NULL; }
+    x->device = ctx->device; x->header = h; x->stream_bytes = stream_bytes;
+    x->shape.num_channels = h.num_channels; x->shape.bits_per_sample = h.bits_per_sample; x->shape.num_samples_per_block = h.num_samples_per_block;
+    x->shape.preset = h.preset; x->shape.ch_process_method = (uint32_t)h.ch_process_method;
+    HostShape hs;
+    if (shape_info(&x->shape, &hs) != LNN_OK) {
+        snprintf(ctx->err, sizeof(ctx->err), "stream header: a shape the device decoder does not take (%u bits, %u samples per block)", h.bits_per_sample, h.num_samples_per_block);
+        LINNEAmd_StreamIndexDestroy(x); *result = LNN_INVALID_FORMAT; return NULL;
+    }
+    ctx->nspans = 0;
+    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
+    ret = sx_build(ctx, x, d_stream);
+    if (ret == LNN_OK && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    if (ret == LNN_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "index build: hipStreamSynchronize failed"); ret = LNN_NG; }
+    if (ret != LNN_OK) { (void)hipStreamSynchronize(ctx->stream); LINNEAmd_StreamIndexDestroy(x); *result = ret; return NULL; }
+    *result = LNN_OK;
+    return x;
+}
+
+extern "C" int LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, struct LINNEHeader *header)
+{
+    if (!index || !header) return LNN_INVALID_ARGUMENT;
+    *header = index->header;
+    return LNN_OK;
+}
+extern "C" uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index) { return index ? index->nb : 0u; }
+
+/* the block holding sample s (s < covered): the last r < nb with first[r] <= s */
+static uint64_t sx_block_of(const LINNEAmdStreamIndex *x, uint64_t s)
+{
+    uint64_t lo = 0, hi = x->nb;
+    while (hi - lo > 1u) { const uint64_t mid = lo + ((hi - lo) >> 1); if (x->h_first[mid] <= s) lo = mid; else hi = mid; }
+    return lo;
+}
+
+extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *x, const uint8_t *d_stream,
+        uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (!x || !d_stream || (!d_pcm && num_samples)) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if (x->device != ctx->device) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
+    const uint64_t total = x->header.num_samples;
+    const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
+    if (first_sample > total || num_samples > total - first_sample) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)first_sample, (unsigned long long)(first_sample + num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
+    if (C > 1u && pcm_stride < num_samples) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)pcm_stride, (unsigned long long)num_samples); return LNN_INVALID_ARGUMENT; }
+    if (num_samples == 0) return LNN_OK;
+    const uint64_t lo = first_sample, hi = first_sample + num_samples;
+    /* blocks 0 .. r1 decide the range (r1 = nb: it reaches behind the last block) */
+    const uint64_t r1 = (hi - 1u < x->covered) ? sx_block_of(x, hi - 1u) : x->nb;
+    if (x->fail_block >= 0 && (uint64_t)x->fail_block <= r1) {
+        snprintf(ctx->err, sizeof(ctx->err), "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
+                x->fail_code == LNN_NG ? "a block no encoder writes" : "damaged or truncated stream");
+        return x->fail_code;
+    }
+    HostShape hs;
+    SX_TRY(shape_info(&x->shape, &hs));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    read_call_knobs(ctx);
+    const uint64_t r0 = (lo < x->covered) ? sx_block_of(x, lo) : x->nb;
+    const uint64_t nr = (r0 < x->nb) ? ((r1 < x->nb ? r1 : x->nb - 1u) - r0 + 1u) : 0u;
+    /* the range's COMPRESS blocks, compacted */
+    uint32_t *h_list = (uint32_t *)malloc(sizeof(uint32_t) * (2u * nr + 1u));
+    if (!h_list) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+    uint32_t *h_comp = h_list, *h_cidx = h_list + nr, ncomp = 0;
+    for (uint64_t y = 0; y < nr; y++) {
+        const uint64_t r = r0 + y;
+        if (x->h_type[r] == SX_COMPRESS) { h_cidx[y] = ncomp; h_comp[ncomp++] = (uint32_t)r; } else h_cidx[y] = 0xFFFFFFFFu;
+    }
+    const uint64_t seg_first = ncomp ? x->h_off[h_comp[0]] : 0u;
+    const uint64_t seg_bytes = ncomp ? x->h_off[h_comp[ncomp - 1]] + x->h_size[h_comp[ncomp - 1]] + 6u - seg_first : 0u;
+    /* scratch: fail word, lists, per-frame words, parameter records, residual / PCM, the Rice decoder's copy of the segment */
+    const uint64_t CS = (uint64_t)C * S;
+    uint64_t at = 0;
+    const uint64_t o_fail = at; at = align_up(at + sizeof(uint32_t));
+    const uint64_t o_comp = at; at = align_up(at + sizeof(uint32_t) * (ncomp + 1u));
+    const uint64_t o_cidx = at; at = align_up(at + sizeof(uint32_t) * (nr + 1u));
+    const uint64_t o_nsmp = at; at = align_up(at + sizeof(uint32_t) * (ncomp + 1u));
+    const uint64_t o_bpos = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
+    const uint64_t o_bend = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
+    const uint64_t o_eb = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
+    const uint64_t o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * (uint64_t)ncomp);
+    const uint64_t o_data = at; at = align_up(at + sizeof(int32_t) * CS * ncomp);
+    const uint64_t o_seg = at; at = align_up(at + seg_bytes + 16u);
+    int ret = ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, at);
+    if (ret != LNN_OK) { free(h_list); return ret; }
+    uint8_t *sd = (uint8_t *)ctx->sdec;
+    uint32_t *d_fail = (uint32_t *)(sd + o_fail), *d_comp = (uint32_t *)(sd + o_comp), *d_cidx = (uint32_t *)(sd + o_cidx), *d_nsmp = (uint32_t *)(sd + o_nsmp);
+    uint64_t *d_bpos = (uint64_t *)(sd + o_bpos), *d_bend = (uint64_t *)(sd + o_bend), *d_eb = (uint64_t *)(sd + o_eb);
+    int32_t *d_prm = (int32_t *)(sd + o_prm), *d_data = (int32_t *)(sd + o_data);
+    uint8_t *d_seg = sd + o_seg;
+    ctx->nspans = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (ncomp) HIPCHK(ctx, hipMemcpyAsync(d_comp, h_comp, sizeof(uint32_t) * ncomp, hipMemcpyHostToDevice, ctx->stream));
+    if (nr) HIPCHK(ctx, hipMemcpyAsync(d_cidx, h_cidx, sizeof(uint32_t) * nr, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));             /* (the host lists are freed next) */
+    free(h_list);
+    if (ncomp) {
+        /* the Rice decoder reads 4-byte words of a zero-padded segment: the bytes of the range's COMPRESS blocks, copied */
+        HIPCHK(ctx, hipMemcpyAsync(d_seg, d_stream + seg_first, seg_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_seg + seg_bytes, 0, 16u, ctx->stream));
+        SxParamArgs pa; memset(&pa, 0, sizeof(pa));
+        pa.b = d_stream; pa.N = x->stream_bytes; pa.off = x->d_off; pa.size = x->d_size; pa.nsmp = x->d_nsmp; pa.comp = d_comp;
+        pa.ncomp = ncomp; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
+        for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
+        pa.seg_first = seg_first; pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
+        SX_LAUNCH(45, k_sx_params, dim3((ncomp + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
+        RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
+        ra.words = (const uint32_t *)d_seg; ra.nbytes = seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
+        ra.resid = d_data; ra.endbit = d_eb; ra.F = ncomp; ra.C = C; ra.S = S;
+        SX_LAUNCH(28, k_rice_decode, dim3((ncomp + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
+        HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
+        SX_LAUNCH(46, k_sx_rice_check, dim3((ncomp + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, (const uint32_t *)d_comp, (const uint64_t *)x->d_off,
+                (const uint32_t *)x->d_size, ncomp, seg_first, d_fail);
+        SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, ncomp, d_prm));
+        uint32_t fail = 0;
+        SX_TRY(sx_fetch(ctx, &fail, d_fail, sizeof(fail)));
+        if (fail != 0xFFFFFFFFu) {
+            snprintf(ctx->err, sizeof(ctx->err), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
+                    fail, (unsigned long long)x->h_off[fail]);
+            return LNN_NG;
+        }
+    }
+    SxPlaceArgs la; memset(&la, 0, sizeof(la));
+    la.b = d_stream; la.N = x->stream_bytes; la.off = x->d_off; la.first = x->d_first; la.type = x->d_type; la.nsmp = x->d_nsmp; la.cidx = d_cidx;
+    la.r0 = (uint32_t)r0; la.nr = (uint32_t)nr; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
+    la.lo = lo; la.hi = hi; la.covered = x->covered; la.out = d_pcm; la.stride = pcm_stride;
+    la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
+    SX_LAUNCH(47, k_sx_place, dim3((uint32_t)((nr + 1u) * la.xch)), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return LNN_OK;
 }

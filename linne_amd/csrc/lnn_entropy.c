@@ -246,6 +246,14 @@ static pthread_once_t g_once = PTHREAD_ONCE_INIT;
 static void rice_k2_init(void);
 static void tables_init(void) { crc_init(); huff_init(); rice_k2_init(); }
 void lnn_tables_init(void) { pthread_once(&g_once, tables_init); }
+void lnn_stream_tables(uint16_t crc[256], uint32_t *huff_root, uint16_t huff_child[512][2])
+{
+    uint32_t i;
+    lnn_tables_init();
+    for (i = 0; i < 256; i++) crc[i] = g_crc[0][i];
+    *huff_root = g_huff.root;
+    memcpy(huff_child, g_huff.child, sizeof(g_huff.child));
+}
 
 /* ------------------------------------------------------------------------------------------------ Rice */
 #define RICE_LOG2_PARTS 10u

@@ -6,6 +6,10 @@
 #include "linne_amd.h"
 #include "lnn_common.h"
 
+#ifdef __cplusplus
+extern "C" {
+#endif
+
 /* block types (libs/linne_internal/include/linne_internal.h:47-52) */
 #define LNN_BLOCK_COMPRESS 0u
 #define LNN_BLOCK_SILENT   1u
@@ -33,5 +37,13 @@ int lnn_parse_block(const struct LINNEAmdShape *shape, const struct lnn_layers *
 int lnn_parse_block_head(const struct LINNEAmdShape *shape, const struct lnn_layers *ly, const uint8_t *data, uint64_t avail,
         int check_crc, uint32_t max_samples, uint32_t *type_out, uint32_t *n_out, uint32_t *consumed_out,
         int32_t *samples, int32_t *params, uint64_t *rice_bit_out);
+
+/* the tables of the stream decoder on the device (LINNEAmd_StreamIndexCreate): the byte table of lnn_crc16 (CRC-16/ARC) and the
+ * static Huffman tree of the coefficients as huff_init builds it (nodes below 256 are symbols) */
+void lnn_stream_tables(uint16_t crc[256], uint32_t *huff_root, uint16_t huff_child[512][2]);
+
+#ifdef __cplusplus
+}
+#endif
 
 #endif
