@@ -273,7 +273,11 @@ int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
  * call of its own): 37 / 38 counting / writing the block candidates (k_sx_count / k_sx_write), 39 prefix sums (k_sx_scan), 40 successors
  * (k_sx_succ), 41 pointer doubling (k_sx_jump, a launch per level), 42 / 43 the chain's length / its blocks (k_sx_chain_len / k_sx_chain),
  * 44 CRC16 and block checks (k_sx_check), 45 parameter records (k_sx_params), 46 the Rice decoder's consumption check (k_sx_rice_check),
- * 47 placing the range into planar output (k_sx_place); the Rice decoding and the synthesis of a range report as 28 and 11-12, 30-36. */
+ * 47 placing the range into planar output (k_sx_place); the Rice decoding and the synthesis of a range report as 28 and 11-12, 30-36.
+ * The stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above): 48 gathering
+ * the planar input into frames (k_se_gather), 49 compacting the Rice plans for the host step (k_se_compact), 50 block sizes
+ * (k_se_size), 51 their offsets (k_sx_scan), 52 parameter bits (k_se_params), 53 Rice codes (k_se_rice), 54 RAW payloads (k_se_raw),
+ * 55 CRC16 and block headers (k_se_crc); a launch of each per pass. */
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_EnableTiming(struct LINNEAmdContext *ctx, int enable);
@@ -336,6 +340,35 @@ int      LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, str
 uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index);   /* the blocks a whole decode walks */
 int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *index,
         const uint8_t *d_stream, uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride);
+
+/* ---- planar PCM held in device memory -> a .lnn stream in device memory ----
+ * LINNEAmd_EncodeStreamDevice encodes header->num_samples samples of every channel ch, read from d_pcm + ch * pcm_stride (int32,
+ * right-justified; any element offset), into d_out[0, *out_bytes).  header's num_channels, num_samples, sampling_rate,
+ * bits_per_sample, num_samples_per_block, preset and ch_process_method are used (the version fields are not); -a / -l come from
+ * the context (LINNEAmd_SetAfIterations / SetLearning).  The result is the LINNEApiResult LINNEEncoder_EncodeWhole returns on a fresh
+ * encoder (room for the header) given the same fields and settings and a buffer of `capacity` bytes, and when that is OK
+ * d_out[0, *out_bytes) holds exactly its bytes:
+ *   - the header checks of SetEncodeParameter, then EncodeHeader's (a capacity under 30 bytes, then the fields), with their codes;
+ *   - LINNE_APIRESULT_INVALID_FORMAT when a block comes out RAW at a width other than 8, 16 or 24 bits, INSUFFICIENT_BUFFER when a
+ *     block is over the host stitcher's 64 + C * S * 8 bytes -- the first such block in stream order; such a block takes precedence
+ *     over a stream that does not fit (EncodeWhole meets the two in the order of its groups; with one group, in this order);
+ *   - LINNE_APIRESULT_INSUFFICIENT_BUFFER when the stream is longer than `capacity` (or than 2^32 - 1 bytes): nothing is written at
+ *     or beyond `capacity`, and *out_bytes is the size the stream needs (0 after a header or block error).
+ * *parcor_state (may be NULL: start from 0.0 like a fresh encoder) is read, and on OK replaced by the value the host stitcher would
+ * carry to the next call (oracle quirk Q2): two calls that thread it give the blocks of two EncodeWhole calls on one encoder.
+ * group_frames bounds the frames of one analysis pass (device memory ~ 8 * C * S bytes per frame of a pass); 0 = the whole stream in
+ * one pass.  It never changes the bytes.  d_out must be 4-byte aligned (INVALID_ARGUMENT otherwise): the bit fields are ORed into
+ * 32-bit words, and the last word of the stream may be touched by an OR that leaves the bytes behind it as they are.  Enqueued on
+ * the context's stream and synchronous: every pass has one host step (block types with the host's libm, Rice plans the device
+ * left to the host).  The environment variable LINNE_AMD_RICE_GUARD (a test knob; default 1e-9) widens the device's guard band for
+ * this entry point, sending more plans to the host; the bytes do not change. */
+uint64_t LINNEAmd_EncodeStreamBound(const struct LINNEHeader *header);      /* 30 + blocks * (64 + C * S * 8): always enough */
+int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state);
+/* how the last EncodeStreamDevice call of this context went: which 0 / 1 / 2 = its COMPRESS / SILENT / RAW blocks, 3 = the
+ * channel-frames whose Rice plan the host settled (a mean in a guard band); -1 for a NULL context or another `which` */
+int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx, int which);
 
 #ifdef __cplusplus
 }

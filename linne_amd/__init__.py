@@ -47,7 +47,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_SlotFetchResidual", "LINNEAmd_SlotStream", "LINNEAmd_SlotStreamCapacity", "LINNEAmd_SlotBitPos", "LINNEAmd_SlotEndBits", "LINNEAmd_SlotPcm16Valid",
     "LINNEAmd_SlotPcmWidth", "LINNEAmd_SlotDecodeStreamSubmit", "LINNEAmd_SlotFetchPcm32", "LINNEAmd_RiceDecodeDevice", "LINNEAmd_SlotBitEnd", "LINNEAmd_LastDecodeWholeMode", "LINNEAmd_RiceEmitDevice", "LINNEAmd_PackFramesEmitted", "LINNEAmd_RicePlanDevice", "LINNEAmd_PackFramesPlanned", "LINNEAmd_SlotEncodeSubmit", "LINNEAmd_SlotDecodeSubmit", "LINNEAmd_SlotWait",
     "LINNEAmd_StreamIndexCreate", "LINNEAmd_StreamIndexDestroy", "LINNEAmd_StreamIndexHeader", "LINNEAmd_StreamIndexNumBlocks",
-    "LINNEAmd_DecodeStreamDevice",
+    "LINNEAmd_DecodeStreamDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
 ]
 
 
@@ -120,6 +120,12 @@ def _load():
     L.LINNEAmd_StreamIndexNumBlocks.restype = C.c_uint32
     L.LINNEAmd_StreamIndexNumBlocks.argtypes = [C.c_void_p]
     L.LINNEAmd_DecodeStreamDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    L.LINNEAmd_EncodeStreamBound.restype = C.c_uint64
+    L.LINNEAmd_EncodeStreamBound.argtypes = [C.POINTER(Header)]
+    L.LINNEAmd_EncodeStreamDevice.argtypes = [C.c_void_p, C.POINTER(Header), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    L.LINNEAmd_GetLastStreamEncodeCount.restype = C.c_int64
+    L.LINNEAmd_GetLastStreamEncodeCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
     L.LINNEAmd_MultiCreate.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.LINNEAmd_MultiDestroy.argtypes = [C.c_void_p]
@@ -345,6 +351,47 @@ class Context:
         finally:
             if own:
                 index.close()
+
+    def encode_stream(self, pcm, bits, rate, block, preset, ms, group_frames=0, parcor_state=None, out=None):
+        """planar PCM (int32 CUDA tensor (C, N), any row stride, or numpy: copied to the device) -> a .lnn stream encoded on the device,
+        as a 1-D uint8 CUDA tensor (a view of `out` when one is given); with parcor_state (a float, the quirk-Q2 state) not None, the
+        pair (stream, new state).  include/linne_amd.h LINNEAmd_EncodeStreamDevice states the result contract.  The default buffer is
+        what the reference's command line tool allocates (twice the PCM's bytes at `bits` width, plus the header); a stream that does not
+        fit is encoded again into a buffer of its exact size.  Raises LinneAmdError with .code = the LINNEApiResult"""
+        import torch
+        if not isinstance(pcm, torch.Tensor):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int32)).to(f"cuda:{self.device}")
+        assert pcm.dtype == torch.int32 and pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1, \
+            "pcm is an int32 CUDA tensor (C, N) whose rows are contiguous"
+        assert pcm.device.index == self.device, f"the PCM is on {pcm.device}, the context on cuda:{self.device}"
+        nch, ns = pcm.shape
+        hd = Header(1, 2, nch, ns, rate, bits, block, preset, int(bool(ms)))
+        state = C.c_double(0.0 if parcor_state is None else float(parcor_state))
+        nbytes = C.c_uint64(0)
+
+        def run(buf):
+            state.value = 0.0 if parcor_state is None else float(parcor_state)
+            self._fence()
+            return lib.LINNEAmd_EncodeStreamDevice(self.h, C.byref(hd), C.c_void_p(pcm.data_ptr()), pcm.stride(0) if nch > 1 else ns,
+                                                   int(group_frames), C.c_void_p(buf.data_ptr()), buf.numel(), C.byref(nbytes),
+                                                   C.byref(state))
+        if out is not None:
+            assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.is_contiguous()
+            buf = out
+        else:
+            buf = torch.empty(2 * nch * ns * ((bits + 7) // 8) + 30, dtype=torch.uint8, device=pcm.device)
+        ret = run(buf)
+        if ret == 3 and out is None and nbytes.value > 0:             # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
+            buf = torch.empty(nbytes.value, dtype=torch.uint8, device=pcm.device)
+            ret = run(buf)
+        if ret != 0:
+            raise LinneAmdError(f"EncodeStreamDevice -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
+        stream = buf[:nbytes.value]
+        return stream if parcor_state is None else (stream, state.value)
+
+    def last_stream_encode_count(self, which):
+        """the last encode_stream call: 0 / 1 / 2 its COMPRESS / SILENT / RAW blocks, 3 the channel-frames whose Rice plan the host settled"""
+        return int(lib.LINNEAmd_GetLastStreamEncodeCount(self.h, int(which)))
 
     def encode_frames_host(self, shape, pcm, num_samples=None):
         """numpy int32 [F][C][S] -> numpy (residual, params, stats)"""

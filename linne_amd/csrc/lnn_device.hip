@@ -25,6 +25,7 @@
 #include "lnn_common.h"
 #include "lnn_host.h"
 #include "linne_decoder.h"
+#include "linne_encoder.h"
 
 /* the kernels, in pipeline order */
 #include "lnn_dev_common.h"
@@ -45,6 +46,7 @@
 #include "lnn_k_finalize.h"
 #include "lnn_k_rice.h"
 #include "lnn_k_stream.h"
+#include "lnn_k_stream_enc.h"
 
 /* ================================================================================================
  * host side of this TU: context, scratch arena, launch sequences, C-ABI
@@ -93,6 +95,10 @@ struct LINNEAmdContext {
     int force_exact;                    /* LINNE_AMD_EXACT=1: every unit-count search runs the exact ordered chains (diff against the certified search) */
     int fir_spec;                       /* LINNE_AMD_SPECULATE (default 1): fuse the one-unit forward into the search of layers 0 .. L-2 */
     void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
+    void *senc; uint64_t senc_cap;      /* scratch of EncodeStreamDevice: the buffers of one pass */
+    int64_t senc_count[4];              /* the last EncodeStreamDevice call: COMPRESS, SILENT, RAW blocks, host-settled Rice plans */
+    int span_keep;                      /* EncodeFramesDevice inside EncodeStreamDevice: keep the call's spans and start event */
+    double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
     /* debug / test knobs that select a kernel form per CALL (read_call_knobs: once at the top of an encode / decode call, never
      * inside the chunk loop; production never sets them and gets the batch-size rules) */
@@ -222,6 +228,7 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->d_plan_nsmp) hipFree(ctx->d_plan_nsmp);
     if (ctx->hstage) hipFree(ctx->hstage);
     if (ctx->sdec) hipFree(ctx->sdec);
+    if (ctx->senc) hipFree(ctx->senc);
     if (ctx->af_h) hipHostFree(ctx->af_h);
     for (int i = 0; i < LNN_META; i++) { if (ctx->meta_h[i]) hipHostFree(ctx->meta_h[i]); if (ctx->meta_ev[i]) hipEventDestroy(ctx->meta_ev[i]); }
     for (int i = 0; i < ctx->n_rice_pool; i++) { hipStreamSynchronize(ctx->rice_pool[i]); hipStreamDestroy(ctx->rice_pool[i]); }
@@ -718,10 +725,10 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
         nchunks = ((nchunks + nsub - 1) / nsub) * nsub;
         chunk = (num_frames + nchunks - 1) / nchunks;
     }
-    ctx->nspans = 0;
+    if (!ctx->span_keep) ctx->nspans = 0;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount, 0, sizeof(uint32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount + 2, 0x7F, 2 * sizeof(uint32_t), ctx->stream));      /* min margin: a huge double (0x7F7F...) */
-    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
+    if (ctx->timing && !ctx->span_keep) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
     const bool use_sub = ctx->nsub > 0 && (nsub > 1 || (streams_forced && ctx->knob.streams != 1));
     if (use_sub || ctx->has_side) HIPCHK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     if (use_sub) for (uint32_t i = 0; i < nsub; i++) HIPCHK(ctx, hipStreamWaitEvent(ctx->sub[i], ctx->ev_start, 0));
@@ -1317,6 +1324,7 @@ extern "C" int LINNEAmd_RicePlanDevice(struct LINNEAmdContext *ctx, const struct
     a.resid = d_residual; a.nsmp = ctx->d_plan_nsmp; a.plan = d_plan; a.C = shape->num_channels; a.S = shape->num_samples_per_block;
     a.nsteps = ctx->rice_nsteps;
     for (uint32_t i = 0; i < 32; i++) a.steps[i] = ctx->rice_steps[i];
+    a.guard = ctx->rice_guard > 0.0 ? ctx->rice_guard : LNN_RICE_GUARD;
     const uint64_t CF = (uint64_t)num_frames * shape->num_channels;
     for (uint64_t c0 = 0; c0 < CF; ) {        /* grid.x limit: split very large batches on frame boundaries */
         uint64_t cnt = CF - c0;
@@ -2067,4 +2075,233 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return LNN_OK;
+}
+
+
+/* ================================================================================================
+ * planar PCM in device memory -> a .lnn stream in device memory (lnn_k_stream_enc.h)
+ * ============================================================================================== */
+extern "C" uint64_t LINNEAmd_EncodeStreamBound(const struct LINNEHeader *header)
+{
+    if (!header || header->num_samples_per_block == 0) return 0;
+    const uint64_t S = header->num_samples_per_block, blocks = ((uint64_t)header->num_samples + S - 1u) / S;
+    return LINNE_HEADER_SIZE + blocks * (64u + (uint64_t)header->num_channels * S * 8u);
+}
+
+extern "C" int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx, int which)
+{
+    if (!ctx || which < 0 || which > 3) return -1;
+    return ctx->senc_count[which];
+}
+
+/* LINNEEncoder_SetEncodeParameter's checks (lnn_api.c), in its order, on an encoder with room for the header */
+static int se_parameter_code(const struct LINNEHeader *h)
+{
+    struct LINNEAmdShape shape;
+    struct lnn_layers ly;
+    if (h->num_channels == 0 || h->bits_per_sample == 0 || h->sampling_rate == 0 || h->num_samples_per_block == 0
+            || h->preset >= LINNE_NUM_PARAMETER_PRESETS || (int)h->ch_process_method >= (int)LINNE_CH_PROCESS_METHOD_INVALID
+            || (int)h->ch_process_method < 0) return LNN_INVALID_FORMAT;
+    shape.num_channels = h->num_channels; shape.bits_per_sample = h->bits_per_sample; shape.num_samples_per_block = h->num_samples_per_block;
+    shape.preset = h->preset; shape.ch_process_method = (uint32_t)h->ch_process_method;
+    if (lnn_shape_layers(&shape, &ly) != 0) return LNN_INVALID_FORMAT;
+    for (uint32_t l = 0; l < ly.num_layers; l++) if (h->num_samples_per_block <= ly.size[l]) return LNN_INVALID_FORMAT;
+    if (h->num_channels > LINNE_MAX_NUM_CHANNELS) return LNN_INSUFFICIENT_BUFFER;
+    return LNN_OK;
+}
+
+/* host buffers of one call */
+struct SeHost {
+    uint2 *cmp = NULL; double *st = NULL; uint32_t *nz32 = NULL, *nsmp = NULL, *settle = NULL, *settle_n = NULL; uint8_t *nz8 = NULL, *types = NULL;
+    int32_t *res = NULL; uint8_t *plans = NULL; uint64_t res_cap = 0;
+    ~SeHost() { free(cmp); free(st); free(nz32); free(nsmp); free(settle); free(settle_n); free(nz8); free(types); free(res); free(plans); }
+};
+
+static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const struct LINNEAmdShape &shape, const HostShape &hs,
+        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes,
+        double *parcor_state)
+{
+    const uint32_t C = shape.num_channels, S = shape.num_samples_per_block;
+    const uint64_t N = header->num_samples, F = (N + S - 1u) / S, CS = (uint64_t)C * S;
+    uint64_t G = group_frames ? (group_frames < F ? group_frames : F) : F;
+    if (G * C > 0x7FFFFFFFull) G = 0x7FFFFFFFull / C;              /* grid.x of the channel-frame kernels */
+    /* scratch of one pass */
+    uint64_t at = 0;
+    const uint64_t o_frames = at; at = align_up(at + sizeof(int32_t) * CS * G);
+    const uint64_t o_resid = at; at = align_up(at + sizeof(int32_t) * CS * G);
+    const uint64_t o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * G);
+    const uint64_t o_st = at; at = align_up(at + sizeof(double) * LINNE_AMD_STAT_WORDS * C * G);
+    const uint64_t o_plan = at; at = align_up(at + (uint64_t)LINNE_AMD_RICE_PLAN_BYTES * C * G);
+    const uint64_t o_nz = at; at = align_up(at + sizeof(uint32_t) * G);
+    const uint64_t o_cmp = at; at = align_up(at + sizeof(uint2) * C * G);
+    const uint64_t o_types = at; at = align_up(at + G);
+    const uint64_t o_size = at; at = align_up(at + sizeof(uint32_t) * G);
+    const uint64_t o_status = at; at = align_up(at + sizeof(int32_t) * G);
+    const uint64_t o_off = at; at = align_up(at + sizeof(uint64_t) * (G + 1u));
+    const uint64_t o_cfbit = at; at = align_up(at + sizeof(uint64_t) * C * G);
+    const uint64_t o_fail = at; at = align_up(at + 2u * sizeof(uint32_t));
+    const uint64_t o_tab = at; at = align_up(at + sizeof(SeTables));
+    SX_TRY(ensure_buf(ctx, &ctx->senc, &ctx->senc_cap, at));
+    uint8_t *sd = (uint8_t *)ctx->senc;
+    int32_t *d_frames = (int32_t *)(sd + o_frames), *d_resid = (int32_t *)(sd + o_resid), *d_prm = (int32_t *)(sd + o_prm), *d_status = (int32_t *)(sd + o_status);
+    double *d_st = (double *)(sd + o_st);
+    uint8_t *d_plan = sd + o_plan, *d_types = sd + o_types;
+    uint32_t *d_nz = (uint32_t *)(sd + o_nz), *d_size = (uint32_t *)(sd + o_size), *d_fail = (uint32_t *)(sd + o_fail);
+    uint2 *d_cmp = (uint2 *)(sd + o_cmp);
+    uint64_t *d_off = (uint64_t *)(sd + o_off), *d_cfbit = (uint64_t *)(sd + o_cfbit);
+    SeTables *d_tab = (SeTables *)(sd + o_tab);
+    SeHost h;
+    h.cmp = (uint2 *)malloc(sizeof(uint2) * C * G); h.st = (double *)malloc(sizeof(double) * LINNE_AMD_STAT_WORDS * C * G);
+    h.nz32 = (uint32_t *)malloc(sizeof(uint32_t) * G); h.nsmp = (uint32_t *)malloc(sizeof(uint32_t) * G);
+    h.settle = (uint32_t *)malloc(sizeof(uint32_t) * C * G); h.settle_n = (uint32_t *)malloc(sizeof(uint32_t) * C * G);
+    h.nz8 = (uint8_t *)malloc(G); h.types = (uint8_t *)malloc(G);
+    if (!h.cmp || !h.st || !h.nz32 || !h.nsmp || !h.settle || !h.settle_n || !h.nz8 || !h.types) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+    {
+        SeTables t;
+        sx_tables(&t.sx);
+        lnn_huff_code_table(t.code, t.len);
+        HIPCHK(ctx, hipMemcpyAsync(d_tab, &t, sizeof(t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_fail + 1, 0, sizeof(uint32_t), ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (t lives on this frame) */
+    }
+    double state = parcor_state ? *parcor_state : 0.0;
+    const uint64_t room = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;     /* EncodeWhole's buffer size is a uint32 */
+    bool writing = capacity >= LINNE_HEADER_SIZE;
+    uint64_t pos = LINNE_HEADER_SIZE;
+    for (uint64_t f0 = 0; f0 < F; f0 += G) {
+        const uint32_t Fp = (uint32_t)((F - f0 < G) ? F - f0 : G);
+        for (uint32_t f = 0; f < Fp; f++) { const uint64_t s0 = (f0 + f) * S; h.nsmp[f] = (N - s0 < S) ? (uint32_t)(N - s0) : S; }
+        /* 1. gather */
+        HIPCHK(ctx, hipMemsetAsync(d_nz, 0, sizeof(uint32_t) * Fp, ctx->stream));
+        {
+            SeGatherArgs g; g.pcm = d_pcm; g.stride = pcm_stride; g.first = f0 * S; g.total = N; g.frames = d_frames; g.nonzero = d_nz;
+            g.F = Fp; g.C = C; g.S = S;
+            SX_LAUNCH(48, k_se_gather, dim3(Fp * C), dim3(SE_THREADS), 0, ctx->stream, g);
+        }
+        /* 2. analysis and Rice plan, unchanged */
+        SX_TRY(LINNEAmd_EncodeFramesDevice(ctx, &shape, d_frames, h.nsmp, Fp, d_resid, d_prm, d_st));
+        SX_TRY(LINNEAmd_RicePlanDevice(ctx, &shape, d_resid, h.nsmp, Fp, d_plan));
+        const uint32_t *d_nsmp = ctx->d_plan_nsmp;                 /* (RicePlanDevice's copy of this pass's lengths) */
+        const uint32_t CF = Fp * C;
+        SX_LAUNCH(49, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
+        /* 3. the host step: block types in stream order (quirk Q2, host libm), the plans the device could not settle */
+        HIPCHK(ctx, hipMemcpyAsync(h.cmp, d_cmp, sizeof(uint2) * CF, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h.st, d_st, sizeof(double) * LINNE_AMD_STAT_WORDS * CF, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h.nz32, d_nz, sizeof(uint32_t) * Fp, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t f = 0; f < Fp; f++) h.nz8[f] = h.nz32[f] ? 1u : 0u;
+        if (lnn_decide_block_types(&shape, h.nsmp, Fp, h.st, h.nz8, h.types, &state) != 0) { snprintf(ctx->err, sizeof(ctx->err), "block types: invalid shape"); return LNN_INVALID_FORMAT; }
+        uint32_t nsettle = 0;
+        for (uint32_t f = 0; f < Fp; f++) {
+            ctx->senc_count[h.types[f] == LNN_BLOCK_COMPRESS ? 0 : (h.types[f] == LNN_BLOCK_SILENT ? 1 : 2)]++;
+            if (h.types[f] != LNN_BLOCK_COMPRESS) continue;
+            for (uint32_t ch = 0; ch < C; ch++) {
+                const uint2 r = h.cmp[f * C + ch];
+                const uint32_t order = r.x & 0xFFu, flag = (r.x >> 8) & 0xFFu;
+                if (flag || order > 10u || (h.nsmp[f] % (1u << order)) != 0u) { h.settle[nsettle] = f * C + ch; h.settle_n[nsettle] = h.nsmp[f]; nsettle++; }
+            }
+        }
+        ctx->senc_count[3] += nsettle;
+        if (nsettle) {
+            if (h.res_cap < (uint64_t)nsettle * S) {
+                free(h.res); free(h.plans); h.res_cap = 0;
+                h.res = (int32_t *)malloc(sizeof(int32_t) * (uint64_t)nsettle * S); h.plans = (uint8_t *)malloc((uint64_t)LINNE_AMD_RICE_PLAN_BYTES * nsettle);
+                if (!h.res || !h.plans) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+                h.res_cap = (uint64_t)nsettle * S;
+            }
+            for (uint32_t k = 0; k < nsettle; k++)
+                HIPCHK(ctx, hipMemcpyAsync(h.res + (uint64_t)k * S, d_resid + (uint64_t)h.settle[k] * S, sizeof(int32_t) * h.settle_n[k], hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            if (lnn_rice_plan_host(h.res, S, h.settle_n, nsettle, h.plans) != 0) { snprintf(ctx->err, sizeof(ctx->err), "host Rice search failed"); return LNN_NG; }
+            for (uint32_t k = 0; k < nsettle; k++) {
+                const uint8_t *rec = h.plans + (uint64_t)k * LINNE_AMD_RICE_PLAN_BYTES;
+                HIPCHK(ctx, hipMemcpyAsync(d_plan + (uint64_t)h.settle[k] * LINNE_AMD_RICE_PLAN_BYTES, rec, LINNE_AMD_RICE_PLAN_K2 + (1u << rec[0]), hipMemcpyHostToDevice, ctx->stream));
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(d_types, h.types, Fp, hipMemcpyHostToDevice, ctx->stream));
+        /* 4. sizes and offsets */
+        SeBlockArgs a; memset(&a, 0, sizeof(a));
+        a.types = d_types; a.nsmp = d_nsmp; a.prm = d_prm; a.plan = d_plan; a.resid = d_resid; a.tab = d_tab;
+        a.F = Fp; a.C = C; a.S = S; a.bits = shape.bits_per_sample; a.L = hs.L;
+        for (uint32_t l = 0; l < hs.L; l++) { a.P[l] = hs.P[l]; a.coef_off[l] = hs.coef_off[l]; }
+        a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.out = d_out; a.base = pos;
+        a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
+        HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
+        SX_LAUNCH(50, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(51, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
+        uint64_t pass_bytes = 0;
+        uint32_t fail = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&fail, d_fail, sizeof(fail), hipMemcpyDeviceToHost, ctx->stream));
+        SX_TRY(sx_fetch(ctx, &pass_bytes, d_off + Fp, sizeof(pass_bytes)));
+        if (fail != 0xFFFFFFFFu) {
+            /* a block the host stitcher refuses: its code, as EncodeWhole returns it (after the header's: a buffer under 30 bytes) */
+            int32_t st = LNN_NG;
+            SX_TRY(sx_fetch(ctx, &st, d_status + fail, sizeof(st)));
+            snprintf(ctx->err, sizeof(ctx->err), "block %llu: %s", (unsigned long long)(f0 + fail),
+                    st == LNN_INVALID_FORMAT ? "a RAW block at a width other than 8, 16 or 24 bits" : "longer than the host stitcher's 64 + C * S * 8 bytes");
+            *out_bytes = 0;
+            return capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : st;
+        }
+        /* 5. 6. the writers and the CRC, into the zeroed region of this pass -- unless the stream does not fit */
+        if (writing && pos + pass_bytes > room) writing = false;
+        if (writing) {
+            HIPCHK(ctx, hipMemsetAsync(d_out + pos, 0, pass_bytes, ctx->stream));
+            SX_LAUNCH(52, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(53, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(53, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(54, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(55, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+        }
+        pos += pass_bytes;
+    }
+    *out_bytes = pos;
+    if (!writing || pos > room) {
+        snprintf(ctx->err, sizeof(ctx->err), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)pos, (unsigned long long)capacity);
+        return LNN_INSUFFICIENT_BUFFER;
+    }
+    uint32_t bad_length = 0;
+    SX_TRY(sx_fetch(ctx, &bad_length, d_fail + 1, sizeof(bad_length)));
+    if (bad_length) { snprintf(ctx->err, sizeof(ctx->err), "a Rice code's length is not its plan's (a wrapped 32-bit length count)"); return LNN_NG; }
+    /* 7. the stream header (LINNEEncoder_EncodeHeader, host) */
+    uint8_t hb[LINNE_HEADER_SIZE];
+    SX_TRY((int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE));
+    HIPCHK(ctx, hipMemcpyAsync(d_out, hb, LINNE_HEADER_SIZE, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (parcor_state) *parcor_state = state;
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    for (int i = 0; i < 4; i++) ctx->senc_count[i] = 0;
+    if (!header || !d_pcm || !d_out || !out_bytes) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if ((uintptr_t)d_out & 3u) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: d_out is not 4-byte aligned"); return LNN_INVALID_ARGUMENT; }
+    *out_bytes = 0;
+    /* the header as SetEncodeParameter, then EncodeHeader see it (a buffer under 30 bytes is EncodeHeader's first complaint) */
+    int ret = se_parameter_code(header);
+    if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: header refused by SetEncodeParameter's checks"); return ret; }
+    {
+        uint8_t hb[LINNE_HEADER_SIZE];
+        ret = (int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE);
+        if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: header refused by EncodeHeader"); return capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : ret; }
+    }
+    struct LINNEAmdShape shape;
+    shape.num_channels = header->num_channels; shape.bits_per_sample = header->bits_per_sample; shape.num_samples_per_block = header->num_samples_per_block;
+    shape.preset = header->preset; shape.ch_process_method = (uint32_t)header->ch_process_method;
+    HostShape hs;
+    if ((ret = shape_info(&shape, &hs)) != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: a shape the device path does not take"); return ret; }
+    if (shape.num_channels > 1u && pcm_stride < header->num_samples) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob: wider guard band, more plans for the host */
+    ctx->nspans = 0; ctx->span_keep = 1;
+    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
+    ret = se_run(ctx, header, shape, hs, d_pcm, pcm_stride, group_frames, d_out, capacity, out_bytes, parcor_state);
+    ctx->span_keep = 0; ctx->rice_guard = 0.0;
+    if (ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
+    return ret;
 }

@@ -254,6 +254,12 @@ void lnn_stream_tables(uint16_t crc[256], uint32_t *huff_root, uint16_t huff_chi
     *huff_root = g_huff.root;
     memcpy(huff_child, g_huff.child, sizeof(g_huff.child));
 }
+void lnn_huff_code_table(uint32_t code[256], uint8_t len[256])
+{
+    lnn_tables_init();
+    memcpy(code, g_huff.code, sizeof(g_huff.code));
+    memcpy(len, g_huff.len, sizeof(g_huff.len));
+}
 
 /* ------------------------------------------------------------------------------------------------ Rice */
 #define RICE_LOG2_PARTS 10u
@@ -406,7 +412,9 @@ static uint64_t g_prof[8];
 #define PROF(i) do { } while (0)
 #define PROF_BEGIN do { } while (0)
 #endif
-static int rice_encode(struct bitw *w, const int32_t *data, uint32_t n, struct rice_scratch *sc)
+/* the search half of rice_encode (linne_coder.c:217-279): the partition order of the shortest code, its length in bits without the
+ * 10-bit order field (uint32 with wrap-around, as the reference counts it) and, in sc->k2[order], the parameters of every order */
+static int rice_search(const int32_t *data, uint32_t n, struct rice_scratch *sc, uint32_t *best_out, uint32_t *bits_out)
 {
     uint32_t max_order = 1, parts, order, part, s, best = 0, min_bits = 0xFFFFFFFFu;
     int32_t i;
@@ -480,9 +488,43 @@ static int rice_encode(struct bitw *w, const int32_t *data, uint32_t n, struct r
         }
     }
     PROF(2);
-    rice_emit(w, data, n, best, sc->k2[best]);
-    PROF(3);
+    *best_out = best; *bits_out = min_bits;
     return 0;
+}
+static int rice_encode(struct bitw *w, const int32_t *data, uint32_t n, struct rice_scratch *sc)
+{
+    uint32_t best, bits;
+    if (rice_search(data, n, sc, &best, &bits) != 0) return -1;
+    {
+        PROF_BEGIN;
+        rice_emit(w, data, n, best, sc->k2[best]);
+        PROF(3);
+    }
+    return 0;
+}
+
+/* The host's plan of `count` channel-frames (row r: residual + r * stride, num_samples[r] samples) in the record layout of
+ * k_rice_plan (LINNE_AMD_RICE_PLAN_BYTES apart): order, flag 0, the code's bit length, the parameters of the order.  What a flagged
+ * device plan is replaced by: rice_encode's own search, whose parameters come from the libm expression wherever it matters. */
+int lnn_rice_plan_host(const int32_t *residual, uint64_t stride, const uint32_t *num_samples, uint32_t count, uint8_t *plans)
+{
+    struct rice_scratch *sc;
+    uint32_t r, p;
+    int ret = 0;
+    lnn_tables_init();
+    if (!(sc = calloc(1, sizeof(*sc)))) return -1;
+    for (r = 0; r < count && ret == 0; r++) {
+        uint8_t *rec = plans + (size_t)r * LINNE_AMD_RICE_PLAN_BYTES;
+        uint32_t best = 0, bits = 0, nbits;
+        if (num_samples[r] == 0 || (ret = rice_search(residual + r * stride, num_samples[r], sc, &best, &bits)) != 0) { ret = -1; break; }
+        nbits = 10u + bits;
+        memset(rec, 0, LINNE_AMD_RICE_PLAN_K2);
+        rec[0] = (uint8_t)best;
+        memcpy(rec + LINNE_AMD_RICE_PLAN_NBITS, &nbits, 4);
+        for (p = 0; p < (1u << best); p++) rec[LINNE_AMD_RICE_PLAN_K2 + p] = sc->k2[best][p];
+    }
+    free(sc->u); free(sc->t); free(sc->fetched); free(sc);
+    return ret;
 }
 
 /* returns 0, or -1 where the reference's own behaviour is undefined (a partition order of 32 or more: `1 << order`,
@@ -557,7 +599,8 @@ int lnn_shape_layers(const struct LINNEAmdShape *shape, struct lnn_layers *out)
  * reference's calculator holds in parcor[order] (oracle quirk Q2). */
 /* where a frame's PCM lives: a frames array [F][C][S] (frame f, channel ch at frames + (f * C + ch) * S) or the caller's planes
  * (channel ch of frame f at planes[ch] + first_sample + f * S) */
-struct pcm_view { const int32_t *frames; const int32_t *const *planes; uint64_t first_sample; };
+struct pcm_view { const int32_t *frames; const int32_t *const *planes; uint64_t first_sample;
+                  const uint8_t *nonzero;  /* or, instead of PCM for the SILENT test: per frame, 1 if some sample of its n is not 0 */ };
 static inline const int32_t *pcm_channel(const struct pcm_view *v, const struct LINNEAmdShape *shape, uint64_t f, uint32_t ch)
 {
     const uint64_t S = shape->num_samples_per_block;
@@ -570,7 +613,7 @@ static uint32_t decide_block_type_view(const struct LINNEAmdShape *shape, const 
 uint32_t lnn_decide_block_type(const struct LINNEAmdShape *shape, const struct lnn_layers *ly, uint32_t n,
         const int32_t *pcm_frame, const double *stats_frame, double *state)
 {
-    struct pcm_view pv; pv.frames = pcm_frame; pv.planes = NULL; pv.first_sample = 0;
+    struct pcm_view pv; pv.frames = pcm_frame; pv.planes = NULL; pv.first_sample = 0; pv.nonzero = NULL;
     return decide_block_type_view(shape, ly, n, &pv, 0, stats_frame, state);
 }
 
@@ -601,6 +644,7 @@ static uint32_t decide_block_type_view(const struct LINNEAmdShape *shape, const 
     mean /= C;
     mean /= bits;
     if (mean >= 0.95f) return LNN_BLOCK_RAW;
+    if (pv->nonzero) return pv->nonzero[f] ? LNN_BLOCK_COMPRESS : LNN_BLOCK_SILENT;
     for (ch = 0; ch < C; ch++) {
         const int32_t *x = pcm_channel(pv, shape, f, ch);
         for (s = 0; s < n; s++) if (x[s] != 0) return LNN_BLOCK_COMPRESS;
@@ -785,12 +829,39 @@ static int pack_frames_core(const struct LINNEAmdShape *shape, const struct pcm_
         const uint8_t *packed, const uint32_t *offsets, int (*fetch)(void *, uint32_t, int32_t *), void *fetch_arg,
         uint8_t *blocks_out, uint64_t blocks_capacity, uint32_t *block_sizes, double *parcor_state, uint32_t num_threads);
 
+/* the block types of a batch in stream order; *state carries quirk Q2 from frame to frame */
+static void decide_types(const struct LINNEAmdShape *shape, const struct lnn_layers *ly, const struct pcm_view *pv,
+        const uint32_t *num_samples, uint32_t num_frames, const double *stats, uint8_t *types, double *state)
+{
+    const uint32_t C = shape->num_channels;
+    uint32_t f;
+    for (f = 0; f < num_frames; f++) {
+        const uint32_t n = num_samples ? num_samples[f] : shape->num_samples_per_block;
+        const double *st = stats + (size_t)f * C * LINNE_AMD_STAT_WORDS;
+        types[f] = (uint8_t)decide_block_type_view(shape, ly, n, pv, f, st, state);
+        if (types[f] == LNN_BLOCK_COMPRESS) *state = st[(size_t)(C - 1) * LINNE_AMD_STAT_WORDS + LINNE_AMD_ST_TAIL];
+    }
+}
+
+/* The same decision from per-frame silence flags instead of PCM (the stream encoder on the device: nonzero[f] = 1 if some sample of
+ * frame f is not 0).  Returns -1 for a shape without a preset. */
+int lnn_decide_block_types(const struct LINNEAmdShape *shape, const uint32_t *num_samples, uint32_t num_frames, const double *stats,
+        const uint8_t *nonzero, uint8_t *types, double *state)
+{
+    struct lnn_layers ly;
+    struct pcm_view pv; pv.frames = NULL; pv.planes = NULL; pv.first_sample = 0; pv.nonzero = nonzero;
+    if (!shape || !nonzero || lnn_shape_layers(shape, &ly) != 0) return -1;
+    lnn_tables_init();
+    decide_types(shape, &ly, &pv, num_samples, num_frames, stats, types, state);
+    return 0;
+}
+
 int LINNEAmd_PackFramesPlanned(const struct LINNEAmdShape *shape, const int32_t *pcm, const uint32_t *num_samples,
         uint32_t num_frames, const int32_t *residual, const int32_t *params, const double *stats, const uint8_t *rice_plan,
         uint8_t *blocks_out, uint64_t blocks_capacity, uint32_t *block_sizes, double *parcor_state,
         uint32_t num_threads)
 {
-    struct pcm_view pv; pv.frames = pcm; pv.planes = NULL; pv.first_sample = 0;
+    struct pcm_view pv; pv.frames = pcm; pv.planes = NULL; pv.first_sample = 0; pv.nonzero = NULL;
     if (!pcm || !residual) return LNN_INVALID_ARGUMENT;
     return pack_frames_core(shape, &pv, num_samples, num_frames, residual, params, stats, rice_plan, NULL, NULL, NULL, NULL,
             blocks_out, blocks_capacity, block_sizes, parcor_state, num_threads);
@@ -807,7 +878,7 @@ int LINNEAmd_PackFramesEmitted(const struct LINNEAmdShape *shape, const int32_t 
         const uint8_t *packed, const uint32_t *offsets, int (*fetch)(void *arg, uint32_t frame, int32_t *dst), void *fetch_arg,
         uint8_t *blocks_out, uint64_t blocks_capacity, uint32_t *block_sizes, double *parcor_state, uint32_t num_threads)
 {
-    struct pcm_view pv; pv.frames = NULL; pv.planes = planes; pv.first_sample = first_sample;
+    struct pcm_view pv; pv.frames = NULL; pv.planes = planes; pv.first_sample = first_sample; pv.nonzero = NULL;
     if (!planes || !rice_plan || !packed || !offsets) return LNN_INVALID_ARGUMENT;
     return pack_frames_core(shape, &pv, num_samples, num_frames, NULL, params, stats, rice_plan, packed, offsets, fetch, fetch_arg,
             blocks_out, blocks_capacity, block_sizes, parcor_state, num_threads);
@@ -835,12 +906,7 @@ static int pack_frames_core(const struct LINNEAmdShape *shape, const struct pcm_
     rets = malloc(sizeof(int) * num_frames);
     if (!types || !rets) { ret = LNN_NG; goto done; }
     /* sequential pass: block types (the only cross-frame dependency, quirk Q2) */
-    for (f = 0; f < num_frames; f++) {
-        const uint32_t n = num_samples ? num_samples[f] : shape->num_samples_per_block;
-        const double *st = stats + (size_t)f * C * LINNE_AMD_STAT_WORDS;
-        types[f] = (uint8_t)decide_block_type_view(shape, &ly, n, pv, f, st, &state);
-        if (types[f] == LNN_BLOCK_COMPRESS) state = st[(size_t)(C - 1) * LINNE_AMD_STAT_WORDS + LINNE_AMD_ST_TAIL];
-    }
+    decide_types(shape, &ly, pv, num_samples, num_frames, stats, types, &state);
     if (parcor_state) *parcor_state = state;
     /* parallel pass: serialise into per-worker regions, then copy the regions into place */
     per_slot = 64 + CS * 8;

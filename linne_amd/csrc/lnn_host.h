@@ -41,6 +41,14 @@ int lnn_parse_block_head(const struct LINNEAmdShape *shape, const struct lnn_lay
 /* the tables of the stream decoder on the device (LINNEAmd_StreamIndexCreate): the byte table of lnn_crc16 (CRC-16/ARC) and the
  * static Huffman tree of the coefficients as huff_init builds it (nodes below 256 are symbols) */
 void lnn_stream_tables(uint16_t crc[256], uint32_t *huff_root, uint16_t huff_child[512][2]);
+/* the encoder's side of that Huffman code: each symbol's code word (its low len[sym] bits, MSB first) and length */
+void lnn_huff_code_table(uint32_t code[256], uint8_t len[256]);
+
+/* the stream encoder on the device (LINNEAmd_EncodeStreamDevice): block types from per-frame silence flags, and the host's Rice plan
+ * of the channel-frames the device could not settle (lnn_entropy.c) */
+int lnn_decide_block_types(const struct LINNEAmdShape *shape, const uint32_t *num_samples, uint32_t num_frames, const double *stats,
+        const uint8_t *nonzero, uint8_t *types, double *state);
+int lnn_rice_plan_host(const int32_t *residual, uint64_t stride, const uint32_t *num_samples, uint32_t count, uint8_t *plans);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 struct RicePlanArgs {
     const int32_t *resid; const uint32_t *nsmp; uint8_t *plan; uint32_t C, S, nsteps;
     double steps[32];
+    double guard;                       /* relative width of the guard band around each step (LNN_RICE_GUARD) */
 };
 __device__ __forceinline__ uint32_t rp_zz(int32_t v) { const uint32_t d = (uint32_t)v << 1; return (v < 0) ? ((0u - d) - 1u) : d; }
 __device__ __forceinline__ uint32_t rp_wave_sum(uint32_t v) { for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64); return v; }    /* every lane gets the wave's total */
@@ -60,8 +61,8 @@ template <bool LDS> __global__ __launch_bounds__(RICE_THREADS) void k_rice_plan(
         uint32_t k = 0;
         for (uint32_t i = 0; i < a.nsteps; i++) k += (m >= a.steps[i]) ? 1u : 0u;
         bool guard = !(m >= 0.0);
-        if (k < a.nsteps && m >= a.steps[k] * (1.0 - LNN_RICE_GUARD)) guard = true;
-        if (k > 0 && m <= a.steps[k - 1] * (1.0 + LNN_RICE_GUARD)) guard = true;
+        if (k < a.nsteps && m >= a.steps[k] * (1.0 - a.guard)) guard = true;
+        if (k > 0 && m <= a.steps[k - 1] * (1.0 + a.guard)) guard = true;
         if (guard) atomicOr(&flag, 1u);
         kk[e] = (uint8_t)(k & 31u);
     }
