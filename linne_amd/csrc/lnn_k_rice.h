@@ -448,14 +448,18 @@ __global__ __launch_bounds__(RDEC_THREADS) void k_rice_decode(RiceDecodeArgs a)
                     uint32_t quot = (uint32_t)__clz((int)t), low;
                     const uint32_t kk = (quot == 0u) ? k1 : k2, used = quot + 1u + kk;
                     const bool usual = (t >> 7) != 0u && used <= 32u && r.widx < r.hi;
+                    /* the binary part of a usual sample (quot + 1 <= 25, 1 <= 32 - kk <= 31; kk = 0: none).  Every lane computes it,
+                     * usual or not, so both shift counts are kept below 32 (t = 0 gives quot = 32) and kk = 0 is a mask */
+                    const uint32_t qs = (quot < 31u) ? quot + 1u : 31u;
+                    const uint32_t low_usual = ((t << qs) >> ((32u - kk) & 31u)) & ((kk != 0u) ? ~0u : 0u);
                     if (__all(usual || !go)) {
-                        low = (kk != 0u) ? ((t << (quot + 1u)) >> (32u - kk)) : 0u;          /* (quot + 1 <= 25, 1 <= 32 - kk <= 31) */
+                        low = low_usual;
                         r.skip_staged(go ? used : 0u);
                         const uint32_t v = (quot == 0u) ? low : (low + k1pow + ((quot - 1u) << k2));
                         val = go ? ((int32_t)(v >> 1) ^ -(int32_t)(v & 1u)) : 0;
                     } else if (go) {
                         if (usual) {
-                            low = (kk != 0u) ? ((t << (quot + 1u)) >> (32u - kk)) : 0u;
+                            low = low_usual;
                             r.skip_staged(used);
                         } else {
                             if (t >> 7) r.skip(quot + 1u);

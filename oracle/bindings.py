@@ -74,6 +74,10 @@ class Oracle:
         L.oracle_crc16.argtypes = [C.c_void_p, C.c_uint64]
         L.oracle_rice_encode.restype = C.c_uint32
         L.oracle_rice_encode.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.oracle_rice_encode_bits.restype = C.c_uint32
+        L.oracle_rice_encode_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.oracle_rice_encode_given.restype = C.c_uint32
+        L.oracle_rice_encode_given.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.oracle_rice_decode.restype = C.c_uint32
         L.oracle_rice_decode.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.oracle_huffman_code.restype = C.c_uint32
@@ -101,6 +105,32 @@ class Oracle:
         self.L.oracle_encoder_destroy(enc)
         assert ret == 0, f"oracle_encode_whole -> {ret}"
         return out[:osz.value].tobytes()
+
+    def rice_encode(self, x, k2=None):
+        """one channel's Rice code -> (bytes, length in bits): the oracle's own search (linne_coder.c), or with k2 = a list of
+        1 << porder parameters the code of that partition order and those parameters (any decoder reads it)"""
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        n = len(x)
+        zz = (np.abs(x.astype(np.int64)) * 2).sum()                            # (>= the zig-zag values' sum minus n)
+        cap = n * 8 + 4096 + (0 if k2 is None else (int(zz) + n) // (8 << int(min(k2))) + 128 * len(k2))
+        out = np.zeros(cap, dtype=np.uint8)
+        nbits = C.c_uint64(0)
+        if k2 is None:
+            nb = self.L.oracle_rice_encode_bits(x.ctypes.data, n, out.ctypes.data, cap, C.byref(nbits))
+        else:
+            ks = np.ascontiguousarray(k2, dtype=np.uint32)
+            porder = len(ks).bit_length() - 1
+            assert len(ks) == 1 << porder and n % len(ks) == 0 and porder <= 10
+            nb = self.L.oracle_rice_encode_given(x.ctypes.data, n, porder, ks.ctypes.data, out.ctypes.data, cap, C.byref(nbits))
+        assert nb and nb == (nbits.value + 7) // 8, "oracle Rice coder: output buffer too small"
+        return out[:nb].tobytes(), nbits.value
+
+    def rice_decode(self, data, n):
+        """(samples, bytes consumed) of oracle_rice_decode"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = np.zeros(n, dtype=np.int32)
+        used = self.L.oracle_rice_decode(buf.ctypes.data, len(buf), out.ctypes.data, n)
+        return out, used
 
     def decode_whole(self, data, check_crc=1):
         buf = np.frombuffer(data, dtype=np.uint8)

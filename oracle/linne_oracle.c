@@ -284,6 +284,36 @@ uint32_t oracle_rice_encode(const int32_t *data, uint32_t num_samples, uint8_t *
     free(pm);
     return w.overflow ? 0 : bw_tell(&w);
 }
+uint32_t oracle_rice_encode_bits(const int32_t *data, uint32_t num_samples, uint8_t *out, uint32_t out_size, uint64_t *nbits)
+{
+    struct BitW w;
+    double (*pm)[RICE_MAX_PARTS] = malloc(sizeof(double) * (RICE_LOG2_MAX_PARTS + 1) * RICE_MAX_PARTS);
+    bw_open(&w, out, out_size);
+    rice_encode_core(&w, data, num_samples, pm);
+    *nbits = (uint64_t)bw_tell(&w) * 8u + w.n;
+    bw_flush(&w);
+    free(pm);
+    return w.overflow ? 0 : bw_tell(&w);
+}
+uint32_t oracle_rice_encode_given(const int32_t *data, uint32_t num_samples, uint32_t porder, const uint32_t *k2s,
+                                  uint8_t *out, uint32_t out_size, uint64_t *nbits)
+{
+    struct BitW w;
+    const uint32_t ns = num_samples >> porder;
+    uint32_t part, smpl, prevk2 = 0;
+    bw_open(&w, out, out_size);
+    bw_put(&w, porder, RICE_LOG2_MAX_PARTS);
+    for (part = 0; part < (1u << porder); part++) {
+        const uint32_t k2 = k2s[part];
+        if (part == 0) bw_put(&w, k2, RICE_PARAM_BITS);
+        else gamma_put(&w, zigzag((int32_t)k2 - (int32_t)prevk2));
+        prevk2 = k2;
+        for (smpl = 0; smpl < ns; smpl++) rice_put(&w, k2 + 1u, k2, zigzag(data[part * ns + smpl]));
+    }
+    *nbits = (uint64_t)bw_tell(&w) * 8u + w.n;
+    bw_flush(&w);
+    return w.overflow ? 0 : bw_tell(&w);
+}
 uint32_t oracle_rice_decode(const uint8_t *in, uint32_t in_size, int32_t *data, uint32_t num_samples)
 {
     struct BitR r;

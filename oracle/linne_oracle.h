@@ -108,6 +108,12 @@ int oracle_decode_frame_hotpath(const struct OracleEncodeParameter *param, const
 uint16_t oracle_crc16(const uint8_t *data, uint64_t size);
 /* partitioned recursive Rice coder: returns bytes written (flushed to a byte boundary) */
 uint32_t oracle_rice_encode(const int32_t *data, uint32_t num_samples, uint8_t *out, uint32_t out_size);
+/* oracle_rice_encode, and the code's length in bits in front of the padding of its last byte */
+uint32_t oracle_rice_encode_bits(const int32_t *data, uint32_t num_samples, uint8_t *out, uint32_t out_size, uint64_t *nbits);
+/* a code with the CALLER's partition order and parameters k2s[1 << porder], laid out as oracle_rice_encode lays out its own: any
+ * decoder must read it, whichever parameters an encoder's search would pick (k2s[p] <= 30; 1 << porder must divide num_samples) */
+uint32_t oracle_rice_encode_given(const int32_t *data, uint32_t num_samples, uint32_t porder, const uint32_t *k2s,
+                                  uint8_t *out, uint32_t out_size, uint64_t *nbits);
 uint32_t oracle_rice_decode(const uint8_t *in, uint32_t in_size, int32_t *data, uint32_t num_samples);
 /* static Huffman code of symbol sym: returns bit length, *code receives the code word */
 uint32_t oracle_huffman_code(uint32_t sym, uint32_t *code);

@@ -17,7 +17,7 @@ sys.path[:0] = [ROOT, TESTS]
 import test_gpu_parity as gp  # noqa: E402
 import test_oracle_cpu as oc  # noqa: E402
 from refs import ANSWERS, REF_SO, Reference, blocks_key, cli_key, decode_key, digest, encode_key, reference_available  # noqa: E402
-from signals import WAVEFORMS, music, waveform  # noqa: E402
+from signals import LONG_STREAMS, WAVEFORMS, long_stream_args, music, waveform  # noqa: E402
 
 REF_CLI = os.path.join(ROOT, "oracle", "_ref", "linne_ref")
 
@@ -70,6 +70,10 @@ def main():
         encode(music(nch, total, bits, seed=block + af), bits, 44100, block, preset, nch >= 2, af_iters=af, learning=1)
     for kind in params(gp.test_network_trainer_on_degenerate_signals):
         encode(waveform(kind, 1, 1024, 16, seed=1), 16, 44100, 512, 4, False, learning=1)
+
+    # test_gpu_rice_oracle.py test_long_block_streams, test_oracle_cpu.py test_oracle_equals_reference_at_long_blocks
+    for cfg in LONG_STREAMS:
+        decode(encode(*long_stream_args(*cfg)))
 
     # test_own_cli_matches_the_reference_cli: the reference CLI's .lnn of each WAV, and its WAV of each such .lnn
     with tempfile.TemporaryDirectory() as tmp:

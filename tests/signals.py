@@ -69,3 +69,23 @@ def music_frames(num_frames, nch, block, bits, seed=0):
     """[frame][ch][block] int32 of independent 'music' frames (each frame its own seed)"""
     x = music(nch, num_frames * block, bits, seed)
     return np.ascontiguousarray(x.reshape(nch, num_frames, block).transpose(1, 0, 2))
+
+
+def long_block_input(nch, bits, block, tail, click, seed):
+    """two blocks of music and a tail; with click, the tail is a quiet passage holding one loud sample (odd tails: partition order 0,
+    so the click shares its partition's parameter with the quiet samples and its code has a long zero run)"""
+    x = music(nch, 2 * block + tail, bits, seed=seed)
+    if click:
+        x[:, 2 * block:] //= 512
+        x[0, 2 * block + tail // 3] = (1 << (bits - 1)) - 7
+    return x
+
+
+# (nch, bits, block, preset, tail, click): presets 0 / 4 / 7, 16 and 24 bits, mono and stereo MS
+LONG_STREAMS = [(1, 16, 12289, 0, 5001, True), (2, 24, 16384, 4, 3000, False), (2, 16, 32768, 7, 12345, True),
+                (2, 24, 65535, 7, 777, True), (1, 16, 65535, 0, 20000, False), (1, 24, 16384, 7, 16383, True),
+                (2, 16, 10240, 7, 1001, True)]
+
+
+def long_stream_args(nch, bits, block, preset, tail, click):
+    return long_block_input(nch, bits, block, tail, click, seed=block + tail), bits, 44100, block, preset, nch >= 2
