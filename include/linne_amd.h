@@ -274,6 +274,9 @@ int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
  * (k_sx_succ), 41 pointer doubling (k_sx_jump, a launch per level), 42 / 43 the chain's length / its blocks (k_sx_chain_len / k_sx_chain),
  * 44 CRC16 and block checks (k_sx_check), 45 parameter records (k_sx_params), 46 the Rice decoder's consumption check (k_sx_rice_check),
  * 47 placing the range into planar output (k_sx_place); the Rice decoding and the synthesis of a range report as 28 and 11-12, 30-36.
+ * Many windows in one call (LINNEAmd_DecodeWindowsDevice; a launch of each per pass, with 28 and the synthesis' kinds between them):
+ * 56 gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather), 57 parameter records (k_wx_params), 58 the consumption
+ * check per window (k_wx_rice_check), 59 placing every window's samples (k_wx_place).
  * The stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above): 48 gathering
  * the planar input into frames (k_se_gather), 49 compacting the Rice plans for the host step (k_se_compact), 50 block sizes
  * (k_se_size), 51 their offsets (k_sx_scan), 52 parameter bits (k_se_params), 53 Rice codes (k_se_rice), 54 RAW payloads (k_se_raw),
@@ -340,6 +343,31 @@ int      LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, str
 uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index);   /* the blocks a whole decode walks */
 int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *index,
         const uint8_t *d_stream, uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride);
+
+/* ---- many sample windows of resident streams in one call ----
+ * LINNEAmd_DecodeWindowsDevice decodes num_windows windows, each a sample range of some stream with a built index; streams of
+ * different shapes (channels, bits, block size, preset, MS) may be mixed, windows may overlap, repeat and name the same stream (a
+ * block two windows share is decoded twice).  Every window's `result` and PCM are what LINNEAmd_DecodeStreamDevice(ctx, index,
+ * d_stream, first_sample, num_samples, d_pcm, pcm_stride) returns and writes for it alone -- its argument checks, the index's
+ * failing block at or before the range, the Rice consumption check -- except that a failing window's d_pcm is never written, and a
+ * failing window does not disturb the others.  Returns LINNE_APIRESULT_OK when every window is OK, otherwise the result of the
+ * lowest-numbered failing window; GetLastError then reads "window <i>: " and the single call's text.  A HIP error or running out of
+ * memory fails the whole call: LINNE_APIRESULT_NG, in every `result` too.  num_windows == 0 is OK; a NULL ctx, or NULL windows with
+ * num_windows > 0, INVALID_ARGUMENT.
+ * The windows of one shape are decoded together: the number of kernel launches, copies and host synchronisations does not depend
+ * on num_windows.  group_frames bounds the COMPRESS blocks of one pass (scratch, kept by the context: about 8 + 4 * C * S bytes per
+ * block plus its stream bytes); 0 = one pass per shape.  It never changes a result: windows are kept whole in a pass where they
+ * fit, and a window of more COMPRESS blocks than group_frames has its Rice codes checked in passes of their own before any of its
+ * samples is placed.  Enqueued on the context's stream and synchronous. */
+struct LINNEAmdWindow {
+    const struct LINNEAmdStreamIndex *index;   /* of the stream below, same device as the context */
+    const uint8_t *d_stream;                   /* the stream's device bytes, any alignment */
+    uint64_t first_sample, num_samples;
+    int32_t *d_pcm; uint64_t pcm_stride;       /* channel ch, sample i -> d_pcm[ch * pcm_stride + i] */
+    int32_t result;                            /* out: the LINNEApiResult of this window */
+};
+int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        uint32_t num_windows, uint32_t group_frames);
 
 /* ---- planar PCM held in device memory -> a .lnn stream in device memory ----
  * LINNEAmd_EncodeStreamDevice encodes header->num_samples samples of every channel ch, read from d_pcm + ch * pcm_stride (int32,

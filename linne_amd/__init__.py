@@ -47,7 +47,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_SlotFetchResidual", "LINNEAmd_SlotStream", "LINNEAmd_SlotStreamCapacity", "LINNEAmd_SlotBitPos", "LINNEAmd_SlotEndBits", "LINNEAmd_SlotPcm16Valid",
     "LINNEAmd_SlotPcmWidth", "LINNEAmd_SlotDecodeStreamSubmit", "LINNEAmd_SlotFetchPcm32", "LINNEAmd_RiceDecodeDevice", "LINNEAmd_SlotBitEnd", "LINNEAmd_LastDecodeWholeMode", "LINNEAmd_RiceEmitDevice", "LINNEAmd_PackFramesEmitted", "LINNEAmd_RicePlanDevice", "LINNEAmd_PackFramesPlanned", "LINNEAmd_SlotEncodeSubmit", "LINNEAmd_SlotDecodeSubmit", "LINNEAmd_SlotWait",
     "LINNEAmd_StreamIndexCreate", "LINNEAmd_StreamIndexDestroy", "LINNEAmd_StreamIndexHeader", "LINNEAmd_StreamIndexNumBlocks",
-    "LINNEAmd_DecodeStreamDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
+    "LINNEAmd_DecodeStreamDevice", "LINNEAmd_DecodeWindowsDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
 ]
 
 
@@ -61,6 +61,12 @@ class Header(C.Structure):
     _fields_ = [("format_version", C.c_uint32), ("codec_version", C.c_uint32), ("num_channels", C.c_uint16),
                 ("num_samples", C.c_uint32), ("sampling_rate", C.c_uint32), ("bits_per_sample", C.c_uint16),
                 ("num_samples_per_block", C.c_uint32), ("preset", C.c_uint8), ("ch_process_method", C.c_int)]
+
+
+class Window(C.Structure):
+    """struct LINNEAmdWindow (include/linne_amd.h)"""
+    _fields_ = [("index", C.c_void_p), ("d_stream", C.c_void_p), ("first_sample", C.c_uint64), ("num_samples", C.c_uint64),
+                ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("result", C.c_int32)]
 
 
 def _load():
@@ -120,6 +126,7 @@ def _load():
     L.LINNEAmd_StreamIndexNumBlocks.restype = C.c_uint32
     L.LINNEAmd_StreamIndexNumBlocks.argtypes = [C.c_void_p]
     L.LINNEAmd_DecodeStreamDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    L.LINNEAmd_DecodeWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.c_uint32, C.c_uint32]
     L.LINNEAmd_EncodeStreamBound.restype = C.c_uint64
     L.LINNEAmd_EncodeStreamBound.argtypes = [C.POINTER(Header)]
     L.LINNEAmd_EncodeStreamDevice.argtypes = [C.c_void_p, C.POINTER(Header), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
@@ -150,11 +157,12 @@ def device_count():
 
 
 class LinneAmdError(RuntimeError):
-    """code: the LINNEApiResult of the failing call, where one is known"""
+    """code: the LINNEApiResult of the failing call, where one is known; codes: those of a batch's members (decode_windows)"""
 
-    def __init__(self, msg, code=None):
+    def __init__(self, msg, code=None, codes=None):
         super().__init__(msg)
         self.code = code
+        self.codes = codes
 
 
 class StreamIndex:
@@ -351,6 +359,54 @@ class Context:
         finally:
             if own:
                 index.close()
+
+    def decode_windows(self, windows, out=None, group_frames=0, return_codes=False):
+        """many sample windows of resident .lnn streams in one call (include/linne_amd.h LINNEAmd_DecodeWindowsDevice).  windows: a
+        sequence of (stream, index, first_sample, num_samples): a 1-D uint8 CUDA tensor, its StreamIndex, and the range (num_samples
+        None: to the stream's end).  Without `out` -> a list of int32 CUDA tensors (C_w, n_w), views of one allocation; with `out`, an
+        int32 CUDA tensor (W, C, n) whose last dimension is contiguous, every window must have that C and n, and `out` is returned
+        (the form of a training batch).  Every window's PCM is what decode_stream gives for it alone; a failing window's is not
+        written.  Raises LinneAmdError with .code = the call's result and .codes = the per-window LINNEApiResults when a window
+        fails; with return_codes -> (pcm, codes), and only a failure of the whole call raises.  group_frames bounds the COMPRESS
+        blocks decoded per pass (0: one pass per stream shape) and never changes the result"""
+        import torch
+        W = len(windows)
+        arr = (Window * max(W, 1))()
+        keep, shapes = [], []
+        for i, (stream, index, first, n) in enumerate(windows):
+            t = self._stream_bytes(stream)
+            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            keep.append(t)
+            shapes.append((index.header["num_channels"], max(n, 0)))
+            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
+            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+        dev = f"cuda:{self.device}"
+        if out is not None:
+            assert out.dtype == torch.int32 and out.is_cuda and out.dim() == 3 and out.shape[0] == W and (out.stride(2) == 1 or out.shape[2] <= 1), \
+                "out is an int32 CUDA tensor (W, C, n), contiguous in its last dimension"
+            assert out.device.index == self.device, f"out is on {out.device}, the context on cuda:{self.device}"
+            for i, (c, n) in enumerate(shapes):
+                assert (c, n) == (out.shape[1], out.shape[2]), f"window {i} is {(c, n)}, out holds {tuple(out.shape[1:])} per window"
+                arr[i].d_pcm, arr[i].pcm_stride = out.data_ptr() + 4 * i * out.stride(0), out.stride(1) if c > 1 else n
+            pcm = out
+        else:
+            flat = torch.empty(sum(c * n for c, n in shapes), dtype=torch.int32, device=dev)
+            pcm, at = [], 0
+            for i, (c, n) in enumerate(shapes):
+                v = flat[at:at + c * n].view(c, n)
+                at += c * n
+                pcm.append(v)
+                arr[i].d_pcm, arr[i].pcm_stride = v.data_ptr(), n
+        self._fence()
+        ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
+        codes = [int(arr[i].result) for i in range(W)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
+                raise LinneAmdError(f"DecodeWindowsDevice -> {ret}: {msg}", ret, codes)
+        return (pcm, codes) if return_codes else pcm
 
     def encode_stream(self, pcm, bits, rate, block, preset, ms, group_frames=0, parcor_state=None, out=None):
         """planar PCM (int32 CUDA tensor (C, N), any row stride, or numpy: copied to the device) -> a .lnn stream encoded on the device,

@@ -20,6 +20,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <new>
+#include <vector>
 
 #include "linne_amd.h"
 #include "lnn_common.h"
@@ -46,6 +48,7 @@
 #include "lnn_k_finalize.h"
 #include "lnn_k_rice.h"
 #include "lnn_k_stream.h"
+#include "lnn_k_windows.h"
 #include "lnn_k_stream_enc.h"
 
 /* ================================================================================================
@@ -96,6 +99,8 @@ struct LINNEAmdContext {
     int fir_spec;                       /* LINNE_AMD_SPECULATE (default 1): fuse the one-unit forward into the search of layers 0 .. L-2 */
     void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
     void *senc; uint64_t senc_cap;      /* scratch of EncodeStreamDevice: the buffers of one pass */
+    void *wdec; uint64_t wdec_cap;      /* DecodeWindowsDevice: fail words, window and block records of one call (its passes' buffers are sdec) */
+    void *wstage; uint64_t wstage_cap;  /* pinned: the same lists on the host, uploaded in one copy; the fail words come back into it */
     int64_t senc_count[4];              /* the last EncodeStreamDevice call: COMPRESS, SILENT, RAW blocks, host-settled Rice plans */
     int span_keep;                      /* EncodeFramesDevice inside EncodeStreamDevice: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
@@ -229,6 +234,8 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->hstage) hipFree(ctx->hstage);
     if (ctx->sdec) hipFree(ctx->sdec);
     if (ctx->senc) hipFree(ctx->senc);
+    if (ctx->wdec) hipFree(ctx->wdec);
+    if (ctx->wstage) hipHostFree(ctx->wstage);
     if (ctx->af_h) hipHostFree(ctx->af_h);
     for (int i = 0; i < LNN_META; i++) { if (ctx->meta_h[i]) hipHostFree(ctx->meta_h[i]); if (ctx->meta_ev[i]) hipEventDestroy(ctx->meta_ev[i]); }
     for (int i = 0; i < ctx->n_rice_pool; i++) { hipStreamSynchronize(ctx->rice_pool[i]); hipStreamDestroy(ctx->rice_pool[i]); }
@@ -2075,6 +2082,249 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return LNN_OK;
+}
+
+
+/* ================================================================================================
+ * many sample windows of many resident streams in one call (lnn_k_windows.h)
+ * ============================================================================================== */
+/* the argument and index checks of LINNEAmd_DecodeStreamDevice on one window, with its codes and texts, in its order.  *r1 = the last
+ * block the window overlaps (nb: it reaches behind the last block); not set for a window of 0 samples */
+static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, char *err, size_t cap, uint64_t *r1)
+{
+    const LINNEAmdStreamIndex *x = w->index;
+    err[0] = 0;
+    if (!x || !w->d_stream || (!w->d_pcm && w->num_samples)) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
+    const uint64_t total = x->header.num_samples;
+    if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
+    if (x->shape.num_channels > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
+    if (w->num_samples == 0) return LNN_OK;
+    const uint64_t hi = w->first_sample + w->num_samples;
+    *r1 = (hi - 1u < x->covered) ? sx_block_of(x, hi - 1u) : x->nb;
+    if (x->fail_block >= 0 && (uint64_t)x->fail_block <= *r1) {
+        snprintf(err, cap, "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
+                x->fail_code == LNN_NG ? "a block no encoder writes" : "damaged or truncated stream");
+        return x->fail_code;
+    }
+    return LNN_OK;
+}
+
+struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
+struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
+/* the buffers of one pass in ctx->sdec */
+struct WxScratch { uint64_t o_nsmp, o_bpos, o_bend, o_eb, o_prm, o_data, o_seg, bytes; };
+static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_bytes)
+{
+    WxScratch s; uint64_t at = 0;
+    s.o_nsmp = at; at = align_up(at + sizeof(uint32_t) * (nc + 1u));
+    s.o_bpos = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_bend = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_eb = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * (uint64_t)nc);
+    s.o_data = at; at = align_up(at + sizeof(int32_t) * (uint64_t)C * S * nc);
+    s.o_seg = at; at = align_up(at + seg_bytes + 16u);
+    s.bytes = at;
+    return s;
+}
+#define WX_MAXGROUPS 64
+
+/* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call */
+static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, WxPlan *plan, const uint32_t **fail_out)
+{
+    const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
+    char text[sizeof(ctx->err)];
+    /* 1. the checks per window; the live ones get their blocks and the group of their shape */
+    uint64_t nlive = 0, total_rec = 0, total_crec = 0;
+    for (uint32_t i = 0; i < W; i++) {
+        uint64_t r1 = 0;
+        plan[i].group = -1; plan[i].r0 = plan[i].nr = plan[i].ncomp = 0;
+        win[i].result = wx_check_window(ctx, &win[i], text, sizeof(text), &r1);
+        if (win[i].result != LNN_OK || win[i].num_samples == 0) continue;
+        const LINNEAmdStreamIndex *x = win[i].index;
+        const uint64_t lo = win[i].first_sample;
+        const uint64_t r0 = (lo < x->covered) ? sx_block_of(x, lo) : x->nb;
+        const uint64_t nr = (r0 < x->nb) ? ((r1 < x->nb ? r1 : x->nb - 1u) - r0 + 1u) : 0u;
+        uint32_t nc = 0;
+        for (uint64_t y = 0; y < nr; y++) nc += (x->h_type[r0 + y] == SX_COMPRESS);
+        uint32_t g = 0;
+        while (g < ngroups && memcmp(&gx[g]->shape, &x->shape, sizeof(x->shape)) != 0) g++;
+        if (g == ngroups) {
+            if (ngroups == WX_MAXGROUPS) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: more than %d stream shapes in one call", WX_MAXGROUPS); return LNN_NG; }
+            gx[ngroups++] = x;
+        }
+        plan[i].r0 = (uint32_t)r0; plan[i].nr = (uint32_t)nr; plan[i].ncomp = nc; plan[i].group = (int32_t)g;
+        const bool big = group_frames && nc > group_frames;
+        nlive++; total_rec += nr + 1u + (big ? nc : 0u); total_crec += (uint64_t)nc * (big ? 2u : 1u);
+    }
+    *fail_out = NULL;
+    if (!nlive) return LNN_OK;
+    if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: %llu blocks in one call: too many", (unsigned long long)total_rec); return LNN_NG; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    read_call_knobs(ctx);
+    /* 2. the lists, in pinned memory: fail words | window records | block records | the passes' COMPRESS records */
+    const uint64_t o_fail = 0, o_win = align_up(sizeof(uint32_t) * (uint64_t)W), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
+            o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
+    if (ctx->wstage_cap < list_bytes) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->wstage) HIPCHK(ctx, hipHostFree(ctx->wstage));
+        ctx->wstage = NULL; ctx->wstage_cap = 0;
+        HIPCHK(ctx, hipHostMalloc(&ctx->wstage, list_bytes, hipHostMallocDefault));
+        ctx->wstage_cap = list_bytes;
+    }
+    uint8_t *hs_ = (uint8_t *)ctx->wstage;
+    uint32_t *h_fail = (uint32_t *)(hs_ + o_fail), *h_crec = (uint32_t *)(hs_ + o_crec);
+    WxWindow *h_win = (WxWindow *)(hs_ + o_win);
+    WxBlock *h_rec = (WxBlock *)(hs_ + o_rec);
+    for (uint32_t i = 0; i < W; i++) h_fail[i] = WX_NOFAIL;
+    std::vector<WxPass> passes;
+    uint32_t nrec = 0, ncrec = 0, nwin = 0;
+    uint64_t scratch_bytes = 0;
+    for (uint32_t g = 0; g < ngroups; g++) {
+        WxPass cur;
+        auto fresh = [&](int check_only) { cur.group = g; cur.rec0 = nrec; cur.nrec = 0; cur.c0 = ncrec; cur.nc = 0; cur.seg_bytes = 0; cur.check_only = check_only; };
+        auto close = [&](int check_only) {
+            if (cur.nrec) {
+                const WxScratch sc = wx_scratch(cur.nc, gx[g]->shape.num_channels, gx[g]->shape.num_samples_per_block, cur.seg_bytes);
+                if (sc.bytes > scratch_bytes) scratch_bytes = sc.bytes;
+                passes.push_back(cur);
+            }
+            fresh(check_only);
+        };
+        auto add = [&](const struct LINNEAmdWindow &w, uint32_t wi, uint32_t type, uint32_t r) {
+            const LINNEAmdStreamIndex *x = w.index;
+            WxBlock &rc = h_rec[nrec++];
+            memset(&rc, 0, sizeof(rc));
+            rc.b = w.d_stream; rc.N = x->stream_bytes; rc.type = type; rc.win = wi; rc.cidx = 0xFFFFFFFFu; rc.blk = r;
+            if (type != WX_TAIL) { rc.off = x->h_off[r]; rc.first = x->h_first[r]; rc.size = x->h_size[r]; rc.nsmp = x->h_nsmp[r]; }
+            if (type == SX_COMPRESS) {
+                /* the block's slot in the packed segment: whole 16-byte groups, the block at its source's address modulo 16 */
+                rc.dst = cur.seg_bytes + ((uintptr_t)(w.d_stream + rc.off) & 15u);
+                cur.seg_bytes = (rc.dst + (uint64_t)rc.size + 6u + 15u) & ~(uint64_t)15u;
+                rc.cidx = cur.nc++;
+                h_crec[ncrec++] = cur.nrec;
+            }
+            cur.nrec++;
+        };
+        fresh(0);
+        for (uint32_t i = 0; i < W; i++) {
+            if (plan[i].group != (int32_t)g) continue;
+            const LINNEAmdStreamIndex *x = win[i].index;
+            const uint32_t wi = nwin++;
+            WxWindow &ww = h_win[wi];
+            ww.lo = win[i].first_sample; ww.hi = ww.lo + win[i].num_samples; ww.covered = x->covered; ww.out = win[i].d_pcm; ww.stride = win[i].pcm_stride; ww.fidx = i; ww.pad = 0;
+            const bool big = group_frames && plan[i].ncomp > group_frames;
+            if (big) {
+                /* a window of more COMPRESS blocks than a pass takes: its Rice codes are checked first, in passes that place
+                 * nothing, so that no sample of it is written before all its fail word can say is known */
+                close(1);
+                for (uint32_t y = 0; y < plan[i].nr; y++) {
+                    const uint32_t r = plan[i].r0 + y;
+                    if (x->h_type[r] != SX_COMPRESS) continue;
+                    if (cur.nc == group_frames) close(1);
+                    add(win[i], wi, SX_COMPRESS, r);
+                }
+                close(0);
+            } else if (group_frames && cur.nc + plan[i].ncomp > group_frames) close(0);
+            if (ww.hi > ww.covered) add(win[i], wi, WX_TAIL, 0);
+            for (uint32_t y = 0; y < plan[i].nr; y++) {
+                const uint32_t r = plan[i].r0 + y, type = x->h_type[r];
+                if (type == SX_COMPRESS && group_frames && cur.nc == group_frames) close(0);
+                add(win[i], wi, type, r);
+            }
+            if (big) close(0);
+        }
+        close(0);
+    }
+    for (const WxPass &p : passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: a pass of %llu stream bytes: give group_frames", (unsigned long long)p.seg_bytes); return LNN_NG; }
+    /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
+    SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, scratch_bytes));
+    uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
+    uint32_t *d_fail = (uint32_t *)(wd + o_fail);
+    const WxWindow *d_win = (const WxWindow *)(wd + o_win);
+    ctx->nspans = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(wd, hs_, list_bytes, hipMemcpyHostToDevice, ctx->stream));
+    /* 4. the passes */
+    for (const WxPass &p : passes) {
+        const LINNEAmdStreamIndex *x = gx[p.group];
+        const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
+        HostShape hs;
+        SX_TRY(shape_info(&x->shape, &hs));
+        const WxScratch sc = wx_scratch(p.nc, C, S, p.seg_bytes);
+        const WxBlock *d_rec = (const WxBlock *)(wd + o_rec) + p.rec0;
+        const uint32_t *d_crec = (const uint32_t *)(wd + o_crec) + p.c0;
+        uint32_t *d_nsmp = (uint32_t *)(sd + sc.o_nsmp);
+        uint64_t *d_bpos = (uint64_t *)(sd + sc.o_bpos), *d_bend = (uint64_t *)(sd + sc.o_bend), *d_eb = (uint64_t *)(sd + sc.o_eb);
+        int32_t *d_prm = (int32_t *)(sd + sc.o_prm), *d_data = (int32_t *)(sd + sc.o_data);
+        uint8_t *d_seg = sd + sc.o_seg;
+        if (p.nc) {
+            SX_LAUNCH(56, k_wx_gather, dim3(p.nc), dim3(WX_GATHER_THREADS), 0, ctx->stream, d_rec, d_crec, p.nc, d_seg);
+            WxParamArgs pa; memset(&pa, 0, sizeof(pa));
+            pa.recs = d_rec; pa.crec = d_crec; pa.ncomp = p.nc; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
+            for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
+            pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
+            SX_LAUNCH(57, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
+            RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
+            ra.words = (const uint32_t *)d_seg; ra.nbytes = p.seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
+            ra.resid = d_data; ra.endbit = d_eb; ra.F = p.nc; ra.C = C; ra.S = S;
+            SX_LAUNCH(28, k_rice_decode, dim3((p.nc + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
+            SX_LAUNCH(58, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
+            if (!p.check_only) SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, p.nc, d_prm));
+        }
+        if (p.check_only) continue;
+        WxPlaceArgs la; memset(&la, 0, sizeof(la));
+        la.recs = d_rec; la.nrec = p.nrec; la.wins = d_win; la.fail = d_fail; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
+        la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
+        if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: a pass of %u blocks: give group_frames", p.nrec); return LNN_NG; }
+        SX_LAUNCH(59, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+    }
+    /* 5. the fail words, with the call's one wait */
+    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, sizeof(uint32_t) * (uint64_t)W, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < W; i++) if (plan[i].group >= 0 && h_fail[i] != WX_NOFAIL) win[i].result = LNN_NG;
+    *fail_out = h_fail;
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (num_windows == 0) return LNN_OK;
+    if (!windows) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    const uint32_t *fail = NULL;
+    int ret;
+    WxPlan *plan = (WxPlan *)malloc(sizeof(WxPlan) * (size_t)num_windows);
+    if (!plan) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    else {
+        try { ret = wx_decode(ctx, windows, num_windows, group_frames, plan, &fail); }
+        catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    }
+    if (ret != LNN_OK) {
+        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
+        (void)hipStreamSynchronize(ctx->stream);
+        for (uint32_t i = 0; i < num_windows; i++) windows[i].result = LNN_NG;
+        free(plan);
+        return LNN_NG;
+    }
+    /* the lowest-numbered failing window's code, and its text behind its number */
+    ret = LNN_OK;
+    for (uint32_t i = 0; i < num_windows; i++) {
+        if (windows[i].result == LNN_OK) continue;
+        char text[sizeof(ctx->err)]; uint64_t r1;
+        ret = windows[i].result;
+        if (plan[i].group >= 0 && fail)
+            snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
+                    fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
+        else (void)wx_check_window(ctx, &windows[i], text, sizeof(text), &r1);
+        snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
+        break;
+    }
+    free(plan);
+    return ret;
 }
 
 

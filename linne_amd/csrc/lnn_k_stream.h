@@ -242,7 +242,33 @@ struct SxParamArgs {
     uint64_t *bitpos, *bitend;          /* [ncomp], bits from seg_first */
     uint32_t *out_nsmp;                 /* [ncomp] */
 };
-/* lnn_parse_block_head's parameter part (lnn_entropy.c:912-932), a lane per block: the records are serial within a block */
+/* lnn_parse_block_head's parameter part (lnn_entropy.c:912-932) of one block, read from r into base[C][LINNE_AMD_PARAM_WORDS]:
+ * the records are serial within a block.  child: the Huffman tree (in LDS) */
+__device__ __forceinline__ void sx_parse_params(SxBits &r, const uint16_t (*child)[2], uint32_t root, uint32_t C, uint32_t bits, uint32_t L,
+        const uint32_t *P, const uint32_t *coef_off, int32_t *base)
+{
+    for (uint32_t ch = 0; ch < C; ch++) {
+        int32_t *rec = base + (uint64_t)ch * LINNE_AMD_PARAM_WORDS;
+        for (uint32_t w = 0; w < LINNE_AMD_PARAM_WORDS; w++) rec[w] = 0;
+        for (uint32_t l = 0; l < 2u; l++) {
+            rec[LINNE_AMD_PRM_PREV + l] = sx_unzz(r.get(bits + 1u));
+            rec[LINNE_AMD_PRM_PCOEF + l] = (int32_t)r.get(4);
+        }
+    }
+    for (uint32_t ch = 0; ch < C; ch++) {
+        int32_t *rec = base + (uint64_t)ch * LINNE_AMD_PARAM_WORDS;
+        for (uint32_t l = 0; l < L; l++) {
+            rec[LINNE_AMD_PRM_UNITS + l] = (int32_t)(1u << r.get(3));
+            rec[LINNE_AMD_PRM_RSHIFT + l] = (int32_t)r.get(4);
+            for (uint32_t i = 0; i < P[l]; i++) {
+                uint32_t node = root;
+                do { node = child[node][r.get(1)]; } while (node >= 256u);
+                rec[LINNE_AMD_PRM_COEF + coef_off[l] + i] = sx_unzz(node);
+            }
+        }
+    }
+}
+/* a lane per COMPRESS block of the range */
 __global__ __launch_bounds__(64) void k_sx_params(SxParamArgs a)
 {
     __shared__ uint16_t child[512][2];
@@ -250,30 +276,10 @@ __global__ __launch_bounds__(64) void k_sx_params(SxParamArgs a)
     __syncthreads();
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     if (k >= a.ncomp) return;
-    const uint32_t blk = a.comp[k], root = a.tab->root;
+    const uint32_t blk = a.comp[k];
     const uint64_t p = a.off[blk];
     SxBits r; r.open(a.b, a.N, p + 11u);
-    int32_t *base = a.prm + (uint64_t)k * a.C * LINNE_AMD_PARAM_WORDS;
-    for (uint32_t ch = 0; ch < a.C; ch++) {
-        int32_t *rec = base + (uint64_t)ch * LINNE_AMD_PARAM_WORDS;
-        for (uint32_t w = 0; w < LINNE_AMD_PARAM_WORDS; w++) rec[w] = 0;
-        for (uint32_t l = 0; l < 2u; l++) {
-            rec[LINNE_AMD_PRM_PREV + l] = sx_unzz(r.get(a.bits + 1u));
-            rec[LINNE_AMD_PRM_PCOEF + l] = (int32_t)r.get(4);
-        }
-    }
-    for (uint32_t ch = 0; ch < a.C; ch++) {
-        int32_t *rec = base + (uint64_t)ch * LINNE_AMD_PARAM_WORDS;
-        for (uint32_t l = 0; l < a.L; l++) {
-            rec[LINNE_AMD_PRM_UNITS + l] = (int32_t)(1u << r.get(3));
-            rec[LINNE_AMD_PRM_RSHIFT + l] = (int32_t)r.get(4);
-            for (uint32_t i = 0; i < a.P[l]; i++) {
-                uint32_t node = root;
-                do { node = child[node][r.get(1)]; } while (node >= 256u);
-                rec[LINNE_AMD_PRM_COEF + a.coef_off[l] + i] = sx_unzz(node);
-            }
-        }
-    }
+    sx_parse_params(r, child, a.tab->root, a.C, a.bits, a.L, a.P, a.coef_off, a.prm + (uint64_t)k * a.C * LINNE_AMD_PARAM_WORDS);
     a.bitpos[k] = (p - a.seg_first) * 8u + 88u + r.consumed;
     a.bitend[k] = (p - a.seg_first + (uint64_t)a.size[blk] + 6u) * 8u;
     a.out_nsmp[k] = a.nsmp[blk];
