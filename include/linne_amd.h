@@ -283,6 +283,10 @@ int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
  * 55 CRC16 and block headers (k_se_crc); a launch of each per pass. */
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
+/* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
+ * per job that walks the job's tiles (chosen by the launch's job count; LINNE_AMD_SEARCH_JOB=0 / 1 forces either), -1 if the call
+ * did not launch the kernel. */
+int LINNEAmd_GetLastSearchLongForm(struct LINNEAmdContext *ctx);
 int LINNEAmd_EnableTiming(struct LINNEAmdContext *ctx, int enable);
 
 /* Host entropy stage, batch form (thread pool over frames): serialises analysed frames to .lnn blocks exactly

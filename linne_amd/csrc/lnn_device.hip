@@ -81,6 +81,8 @@ struct LINNEAmdContext {
     int lev_ride;                       /* short Levinson trials ride along with the one-unit trial (LINNE_AMD_LEV_RIDE, default 1) */
     int lev_wave;                       /* batches of <= 64 jobs: a wave per Levinson problem (LINNE_AMD_LEV_WAVE, default 1) */
     int search_two;                     /* k_search_long in two passes over the window, five waves per SIMD (LINNE_AMD_SEARCH_TWO) */
+    int search_job;                     /* k_search_long with one block per job that walks the job's tiles: 1 always, 0 never ((jobs, tiles) blocks), -1 by the size of the batch (LINNE_AMD_SEARCH_JOB, default -1) */
+    int last_search_form;               /* the form of the call's last k_search_long launch: 0 (jobs, tiles), 1 per job, -1 none (LINNEAmd_GetLastSearchLongForm) */
     const uint32_t *cur_idx;            /* class index per frame of the call being enqueued (host copy, in the meta ring) */
     uint32_t *meta_h[LNN_META]; uint64_t meta_cap[LNN_META]; hipEvent_t meta_ev[LNN_META]; int meta_used[LNN_META]; int meta_next;
     /* copy streams of the staging slots (H2D of the next group and D2H of the previous one overlap the kernels) */
@@ -206,6 +208,7 @@ extern "C" struct LINNEAmdContext *LINNEAmd_ContextCreate(int device, uint64_t s
     { const char *lr = getenv("LINNE_AMD_LEV_RIDE"); ctx->lev_ride = lr ? atoi(lr) : 1; }
     { const char *lw = getenv("LINNE_AMD_LEV_WAVE"); ctx->lev_wave = lw ? atoi(lw) : 1; }
     { const char *st_ = getenv("LINNE_AMD_SEARCH_TWO"); ctx->search_two = st_ ? atoi(st_) : 1; }
+    { const char *sj_ = getenv("LINNE_AMD_SEARCH_JOB"); ctx->search_job = sj_ ? atoi(sj_) : -1; ctx->last_search_form = -1; }
     { const char *fl = getenv("LINNE_AMD_FWD_LOSS"); ctx->fwd_loss = fl ? atoi(fl) : -1; }
     { const char *sp = getenv("LINNE_AMD_FIR_SMALL"); ctx->fir_small = sp ? atoi(sp) : 1; }
     (void)hipFuncSetAttribute((const void *)k_levinson_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LEV_LDS_BUDGET);
@@ -378,6 +381,7 @@ extern "C" double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int whic
     }
     return cnt ? sum : -1.0;
 }
+extern "C" int LINNEAmd_GetLastSearchLongForm(struct LINNEAmdContext *ctx) { return ctx ? ctx->last_search_form : -1; }
 extern "C" int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which)
 {
     if (!ctx) return 0;
@@ -733,6 +737,7 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
         chunk = (num_frames + nchunks - 1) / nchunks;
     }
     if (!ctx->span_keep) ctx->nspans = 0;
+    ctx->last_search_form = -1;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount, 0, sizeof(uint32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount + 2, 0x7F, 2 * sizeof(uint32_t), ctx->stream));      /* min margin: a huge double (0x7F7F...) */
     if (ctx->timing && !ctx->span_keep) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
@@ -952,8 +957,14 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
                 if (long_any) {
                     const int sp_ = span_begin(ctx, 25, st);
                     const dim3 grid((uint32_t)Jq, (S + FIR_TILE - 1) / FIR_TILE), blk(FIR_THREADS);
-                    if (ctx->search_two) { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, true>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, true>), grid, blk, 0, st, q, l, cur); }
-                    else { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, false>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, false>), grid, blk, 0, st, q, l, cur); }
+                    /* one block per job that walks its tiles (coefficients, bookkeeping and reductions once per job) where the jobs alone
+                     * are at least SEARCH_JOB_MIN; (jobs, tiles) blocks below that.  The one-pass kernel has the latter form only. */
+                    const bool per_job = ctx->search_two && (ctx->search_job < 0 ? Jq >= SEARCH_JOB_MIN : ctx->search_job != 0);
+                    const dim3 gjob((uint32_t)Jq, 1);
+                    ctx->last_search_form = per_job ? 1 : 0;
+                    if (per_job) { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, true, true>), gjob, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, true, true>), gjob, blk, 0, st, q, l, cur); }
+                    else if (ctx->search_two) { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, true, false>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, true, false>), grid, blk, 0, st, q, l, cur); }
+                    else { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, false, false>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, false, false>), grid, blk, 0, st, q, l, cur); }
                     span_end(ctx, sp_, st);
                 }
                 if (!(long_any && long_all)) {
