@@ -250,6 +250,25 @@ int64_t LINNEAmd_GetLastFallbackCount(struct LINNEAmdContext *ctx);
  * the environment of ContextCreate makes every search take the exact ordered chains instead (for diffing the two paths). */
 double LINNEAmd_GetLastMinMargin(struct LINNEAmdContext *ctx);
 
+/* Test instrument of the certified search (off by default; nothing in production enables it): what the selection kernels decided
+ * every unit-count search FROM.  After SetSearchCapture(ctx, 1) every EncodeFramesDevice call leaves LINNE_AMD_CAPTURE_WORDS doubles
+ * per trial slot, indexed [frame][channel][regulariser pass][layer][LINNE_AMD_CAPTURE_TRIALS] with the frames in the CALLER's order
+ * (whatever chunks, streams and class-sorted rows the call was cut into), trial t of a layer of P coefficients being the one with
+ * 2^t units:
+ *   [0] the mean of the order-free sum exactly as the certificate compared it    [1] its slack   [2] rel   [3] max |input|
+ *   [4] the largest L1 norm of a unit's coefficients   [5] how the search was decided: 0 by the certificate, 1 by the exact
+ *   ordered chains after the certificate refused (or LINNE_AMD_EXACT=1), 2 by k_last_layer's exact chains (then [0]..[4] were
+ *   never computed)   [6] the ordered mean, where the exact chains ran   [7] the trial's unit count.
+ * A word that was not computed, and every word of a slot without a trial, is NaN (all bits set).  The searches inside the real final
+ * pass of -a N are not recorded.  Enabled or not, the call's results, telemetry and kernel choices are the same; disabled, the
+ * kernels see a null pointer and write nothing.
+ * GetLastSearchCapture synchronises, copies min(records, capacity_records) records (LINNE_AMD_CAPTURE_WORDS doubles each) of the
+ * last encode call to host and returns the number of records that call left (0: capture was off; -1 on error). */
+#define LINNE_AMD_CAPTURE_WORDS   8
+#define LINNE_AMD_CAPTURE_TRIALS  8
+int LINNEAmd_SetSearchCapture(struct LINNEAmdContext *ctx, int enable);
+int64_t LINNEAmd_GetLastSearchCapture(struct LINNEAmdContext *ctx, double *host, uint64_t capacity_records);
+
 /* blocks until everything enqueued on the context's stream has finished */
 int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
 

@@ -27,6 +27,8 @@ PRM_PREV, PRM_PCOEF, PRM_UNITS, PRM_RSHIFT, PRM_COEF = 0, 2, 4, 7, 10
 ST_R0, ST_K1, ST_ZERO, ST_TAIL, ST_BEST, ST_LOSS = 0, 1, 4, 5, 6, 7
 PRESET_LAYERS = {0: (2, 32), 1: (2, 32), 2: (4, 64, 8), 3: (4, 64, 8), 4: (4, 64, 8),
                  5: (4, 128, 16), 6: (4, 128, 16), 7: (4, 128, 16)}
+CAPTURE_WORDS, CAPTURE_TRIALS = 8, 8      # include/linne_amd.h LINNEAmd_GetLastSearchCapture
+CAP_MEAN, CAP_SLACK, CAP_REL, CAP_XMAX, CAP_HSUM, CAP_HOW, CAP_ORDERED, CAP_UNITS = range(8)
 PRESET_NUM_REGULARS = {0: 1, 1: 2, 2: 1, 3: 2, 4: 4, 5: 1, 6: 2, 7: 4}
 
 # symbols include/*.h declare (checked by tests/test_abi.py)
@@ -41,7 +43,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_ReserveScratch", "LINNEAmd_ScratchBytesPerFrame", "LINNEAmd_SetStream", "LINNEAmd_EncodeFramesDevice", "LINNEAmd_DecodeFramesDevice",
     "LINNEAmd_EncodeFramesHost", "LINNEAmd_DecodeFramesHost", "LINNEAmd_Synchronize", "LINNEAmd_GetLastFallbackCount", "LINNEAmd_GetLastTimingMs",
     "LINNEAmd_GetLastTimingLaunches", "LINNEAmd_GetLastSearchLongForm", "LINNEAmd_EnableTiming", "LINNEAmd_PackFrames",
-    "LINNEAmd_GetLastMinMargin", "LINNEAmd_SetAfIterations", "LINNEAmd_SetLearning", "LINNEAmd_MultiCreate", "LINNEAmd_MultiDestroy", "LINNEAmd_MultiNumDevices", "LINNEAmd_MultiDevice",
+    "LINNEAmd_GetLastMinMargin", "LINNEAmd_SetSearchCapture", "LINNEAmd_GetLastSearchCapture", "LINNEAmd_SetAfIterations", "LINNEAmd_SetLearning", "LINNEAmd_MultiCreate", "LINNEAmd_MultiDestroy", "LINNEAmd_MultiNumDevices", "LINNEAmd_MultiDevice",
     "LINNEAmd_MultiContext", "LINNEAmd_MultiGetLastError", "LINNEAmd_MultiEncodeFramesHost", "LINNEAmd_MultiDecodeFramesHost", "LINNEAmd_SlotCreate", "LINNEAmd_SlotDestroy", "LINNEAmd_SlotPcm", "LINNEAmd_SlotData", "LINNEAmd_SlotParams", "LINNEAmd_SlotStats",
     "LINNEAmd_SlotCapacity", "LINNEAmd_SlotRicePlan", "LINNEAmd_SlotCreateEx", "LINNEAmd_SlotFlags", "LINNEAmd_SlotPcm16", "LINNEAmd_SlotPacked", "LINNEAmd_SlotOffsets",
     "LINNEAmd_SlotFetchResidual", "LINNEAmd_SlotStream", "LINNEAmd_SlotStreamCapacity", "LINNEAmd_SlotBitPos", "LINNEAmd_SlotEndBits", "LINNEAmd_SlotPcm16Valid",
@@ -105,6 +107,9 @@ def _load():
     L.LINNEAmd_SetLearning.argtypes = [C.c_void_p, C.c_uint32]
     L.LINNEAmd_GetLastMinMargin.restype = C.c_double
     L.LINNEAmd_GetLastMinMargin.argtypes = [C.c_void_p]
+    L.LINNEAmd_SetSearchCapture.argtypes = [C.c_void_p, C.c_int]
+    L.LINNEAmd_GetLastSearchCapture.restype = C.c_int64
+    L.LINNEAmd_GetLastSearchCapture.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.LINNEAmd_GetLastTimingMs.restype = C.c_double
     L.LINNEAmd_GetLastTimingMs.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_EnableTiming.argtypes = [C.c_void_p, C.c_int]
@@ -246,6 +251,20 @@ class Context:
 
     def last_min_margin(self):
         return float(lib.LINNEAmd_GetLastMinMargin(self.h))
+
+    def set_search_capture(self, on=True):
+        """test instrument (include/linne_amd.h LINNEAmd_SetSearchCapture): the encode calls record what every unit-count search was decided from"""
+        self._check(lib.LINNEAmd_SetSearchCapture(self.h, int(bool(on))), "SetSearchCapture")
+
+    def last_search_capture(self, shape, num_frames):
+        """the last encode call's records as float64 [F][C][R][L][CAPTURE_TRIALS][CAPTURE_WORDS] (words: CAP_*; NaN = not computed / no such trial)"""
+        R, nl = PRESET_NUM_REGULARS[shape.preset], len(PRESET_LAYERS[shape.preset])
+        out = np.full((int(num_frames), shape.num_channels, R, nl, CAPTURE_TRIALS, CAPTURE_WORDS), np.nan)
+        n = int(lib.LINNEAmd_GetLastSearchCapture(self.h, out.ctypes.data, out.size // CAPTURE_WORDS))
+        if n != out.size // CAPTURE_WORDS:
+            raise LinneAmdError(f"GetLastSearchCapture -> {n} records, {out.size // CAPTURE_WORDS} expected "
+                                f"(capture off, or another shape?): {lib.LINNEAmd_GetLastError(self.h).decode()}")
+        return out
 
     def synchronize(self):
         self._check(lib.LINNEAmd_Synchronize(self.h), "Synchronize")

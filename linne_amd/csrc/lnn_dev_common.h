@@ -94,7 +94,11 @@ struct Plan {
     uint32_t *af_state;                 /* [J][MAXU]   0 iterating, 1 converged, 2 zero problem, 3 singular                    */
     uint32_t *af_prob, *af_nprob;       /* compact list of the (job, unit) problems of the layer (job * MAXU + unit), its length */
     double *af_pivot;                   /* [problems]  pivot sums out / pow(sum, -0.5) in (host libm), per Cholesky step       */
+    /* LINNEAmd_SetSearchCapture (tests): what k_select decided every unit-count search from, LNN_CAP_WORDS doubles per trial at
+     * [caller's frame][channel][regulariser pass][layer][LNN_MAXT]; NULL (always, outside a test): nothing is written */
+    double *capture;
 };
+#define LNN_CAP_WORDS   8       /* include/linne_amd.h LINNE_AMD_CAPTURE_WORDS: mean, slack, rel, xmax, thsum, how, ordered mean, units */
 
 typedef const double __attribute__((address_space(4))) *lnn_cdp;    /* constant address space: wave-uniform loads become scalar loads */
 #define LNN_FIR_TILE 2048u               /* samples per block of the search / forward kernels (lnn_k_fir.h FIR_TILE) */

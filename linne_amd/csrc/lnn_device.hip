@@ -98,6 +98,8 @@ struct LINNEAmdContext {
     double *af_h; uint32_t af_h_cap;    /* pinned: a Cholesky step's pivots on their way through the host's pow() */
     int pcm16_next;                     /* the next EncodeFramesDevice call reads narrow samples: 1 int16, 2 packed 3-byte (set by the staging slots, cleared by the call) */
     int force_exact;                    /* LINNE_AMD_EXACT=1: every unit-count search runs the exact ordered chains (diff against the certified search) */
+    int capture_on;                     /* LINNEAmd_SetSearchCapture: the encode calls leave what k_select decided from (tests; off: Plan.capture is NULL) */
+    double *d_capture; uint64_t capture_cap, capture_n;      /* its records on the device: capacity, and those of the last call */
     int fir_spec;                       /* LINNE_AMD_SPECULATE (default 1): fuse the one-unit forward into the search of layers 0 .. L-2 */
     void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
     void *senc; uint64_t senc_cap;      /* scratch of EncodeStreamDevice: the buffers of one pass */
@@ -226,6 +228,7 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->d_cls) hipFree(ctx->d_cls);
     if (ctx->d_ucount) hipFree(ctx->d_ucount);
+    if (ctx->d_capture) hipFree(ctx->d_capture);
     for (int i = 0; i < ctx->nsub; i++) { hipStreamSynchronize(ctx->sub[i]); hipStreamDestroy(ctx->sub[i]); hipEventDestroy(ctx->sub_done[i]); }
     if (ctx->ev_start) hipEventDestroy(ctx->ev_start);
     if (ctx->has_side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); hipEventDestroy(ctx->side_done); hipEventDestroy(ctx->fork_ev); hipEventDestroy(ctx->join_ev); }
@@ -291,6 +294,22 @@ extern "C" double LINNEAmd_GetLastMinMargin(struct LINNEAmdContext *ctx)
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess
             || hipMemcpy(&v, ctx->d_ucount + 2, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
     return v;
+}
+
+extern "C" int LINNEAmd_SetSearchCapture(struct LINNEAmdContext *ctx, int enable)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->capture_on = enable ? 1 : 0;
+    return LNN_OK;
+}
+
+extern "C" int64_t LINNEAmd_GetLastSearchCapture(struct LINNEAmdContext *ctx, double *host, uint64_t capacity_records)
+{
+    if (!ctx) return -1;
+    const uint64_t n = ctx->capture_n < capacity_records ? ctx->capture_n : capacity_records;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
+    if (n && (!host || hipMemcpy(host, ctx->d_capture, n * LNN_CAP_WORDS * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) return -1;
+    return (int64_t)ctx->capture_n;
 }
 
 extern "C" int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx)
@@ -738,6 +757,19 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
     }
     if (!ctx->span_keep) ctx->nspans = 0;
     ctx->last_search_form = -1;
+    ctx->capture_n = 0;
+    if (ctx->capture_on) {          /* one record per (frame, channel, pass, layer, trial slot) in the caller's order; slots no search fills stay NaN */
+        const uint64_t nrec = (uint64_t)num_frames * C * hs.R * hs.L * LNN_MAXT;
+        if (ctx->capture_cap < nrec) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_capture) HIPCHK(ctx, hipFree(ctx->d_capture));
+            ctx->d_capture = NULL; ctx->capture_cap = 0;
+            HIPCHK(ctx, hipMalloc((void **)&ctx->d_capture, nrec * LNN_CAP_WORDS * sizeof(double)));
+            ctx->capture_cap = nrec;
+        }
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_capture, 0xFF, nrec * LNN_CAP_WORDS * sizeof(double), ctx->stream));
+        ctx->capture_n = nrec;
+    }
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount, 0, sizeof(uint32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount + 2, 0x7F, 2 * sizeof(uint32_t), ctx->stream));      /* min margin: a huge double (0x7F7F...) */
     if (ctx->timing && !ctx->span_keep) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
@@ -818,6 +850,7 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
             }
         }
         p.cls_of_frame = ctx->d_clsidx + f0; p.frame_map = ctx->d_map + f0; p.cls = ctx->d_cls; p.sintab = ctx->d_sin; p.wtab = ctx->d_wt; p.ucount = ctx->d_ucount; p.min_margin = (unsigned long long *)(ctx->d_ucount + 2); p.force_exact = ctx->force_exact ? 1u : 0u; p.dbg_maxtr = ctx->knob.dbg_maxtr;
+        p.capture = ctx->capture_n ? ctx->d_capture : NULL;
         uint8_t *const abase = (uint8_t *)ctx->arena + (size_t)slot * part_bytes;
         uint8_t *a = abase;
 #define TAKE(ptr, type, count) do { ptr = (type *)a; a += align_up(sizeof(type) * (uint64_t)(count)); } while (0)
@@ -1067,6 +1100,7 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
             Plan q = p;
             q.R = 1; q.J = (uint32_t)CF; q.regs[0] = 0.0;
             q.hist = 0; q.fused_last = 0; q.search_long = 0;
+            q.capture = NULL;                                       /* the final pass does not search: it refines the winner */
             build_runs(&q.runs[1], ctx->cur_idx + f0, Fc, C);
             q.job_reg = af_reg; q.af_best = af_best; q.af_loss = af_loss;
             hipLaunchKernelGGL(k_af_best, dim3(((uint32_t)CF + 255) / 256), dim3(256), 0, st, p, af_best, af_loss, af_reg);

@@ -547,6 +547,14 @@ __global__ __launch_bounds__(64) void k_chain_sum_wave(Plan p, uint32_t layer, u
     if (lane == 0) { if (MODE == 0) p.tloss[myrow] = sum / (double)na; else p.jloss[myrow] = sum / (double)na; }
 }
 
+/* the capture records of (job, layer): rows of the class-sorted chunk lead back to the caller's frames through frame_map */
+__device__ __forceinline__ double *capture_rec(const Plan &p, uint32_t job, uint32_t layer)
+{
+    const uint32_t cf = job / p.R;
+    const size_t ocf = (size_t)p.frame_map[cf / p.C] * p.C + cf % p.C;
+    return p.capture + ((ocf * p.R + job % p.R) * p.L + layer) * (size_t)(LNN_MAXT * LNN_CAP_WORDS);
+}
+
 /* strict-< argmin over the trials (linne_network.c:338-341), keep its coefficients (== SetParameter,
  * :350-376, which recomputes the same values) and, for the last layer, the value the layer leaves in
  * parcor[P0] (Q2): the last call in reference order -- trials in order, then SetParameter's units -- that
@@ -565,6 +573,13 @@ __global__ void k_select(Plan p, uint32_t layer, uint32_t exact)
             const double l = p.tloss[(size_t)job * LNN_MAXT + t];
             if (l < min_loss) { min_loss = l; best = t; }
         }
+        if (p.capture) {                                        /* the ordered means this decision was taken from */
+            double *rec = capture_rec(p, job, layer);
+            for (uint32_t t = 0; t < nt; t++) {
+                rec[t * LNN_CAP_WORDS + 6] = p.tloss[(size_t)job * LNN_MAXT + t];
+                if (exact == 2u) { rec[t * LNN_CAP_WORDS + 5] = 2.0; rec[t * LNN_CAP_WORDS + 7] = (double)c.trial_u[layer][t]; }
+            }
+        }
     } else {
         /* Certified search.  m_t below is the mean of an order-free sum of the same non-negative terms the reference
          * adds sequentially; both sums are within gamma_n * S of the exact sum S, so they differ by at most
@@ -580,10 +595,10 @@ __global__ void k_select(Plan p, uint32_t layer, uint32_t exact)
          * gamma_(np+1) (|x| + sum |h_k x_k|) of the exact value: a term is off the reference's by at most
          * 2 gamma_(np+1) max|x| (1 + sum |h_k|) (taken with a factor 4 and np + 2 here), and so is the mean. */
         double slack[LNN_MAXT];
+        double xmax = 0.0;
         {
             const uint32_t np_used = ((c.na + FIR_TILE - 1) / FIR_TILE) * (FIR_THREADS / 64);
             const double *px = p.txmax + (size_t)job * p.npart;
-            double xmax = 0.0;
             for (uint32_t i = 0; i < np_used; i++) xmax = fmax(xmax, px[i]);
             for (uint32_t t = 0; t < nt; t++) {
                 const double npt = (double)(p.P[layer] / c.trial_u[layer][t]);
@@ -615,6 +630,14 @@ __global__ void k_select(Plan p, uint32_t layer, uint32_t exact)
         if (p.force_exact) ok = 0;                              /* LINNE_AMD_EXACT=1: every search takes the ordered chains */
         p.uncertain[job] = ok ? 0 : 1;
         if (!ok) atomicAdd(p.ucount, 1u);
+        if (p.capture) {                                        /* what the certificate saw, and whether it decided */
+            double *rec = capture_rec(p, job, layer);
+            for (uint32_t t = 0; t < nt; t++) {
+                double *r = rec + t * LNN_CAP_WORDS;
+                r[0] = m[t]; r[1] = slack[t]; r[2] = rel; r[3] = xmax; r[4] = p.thsum[(size_t)job * LNN_MAXT + t];
+                r[5] = ok ? 0.0 : 1.0; r[7] = (double)c.trial_u[layer][t];
+            }
+        }
     }
     const uint32_t P = p.P[layer];
     if (exact == 2u) p.jloss[job] = p.tsum[((size_t)job * LNN_MAXT + best) * p.npart];      /* the winner's forward loss, as k_last_layer left it */
@@ -664,6 +687,10 @@ __global__ __launch_bounds__(64) void k_select_wave(Plan p, uint32_t layer, uint
         uint32_t best = 0;
         if (exact) {
             for (uint32_t t = 0; t < nt; t++) { const double l = s_loss[t]; if (l < min_loss) { min_loss = l; best = t; } }
+            if (p.capture) {
+                double *rec = capture_rec(p, job, layer);
+                for (uint32_t t = 0; t < nt; t++) rec[t * LNN_CAP_WORDS + 6] = s_loss[t];
+            }
         } else {        /* (k_select's certificate, statement for statement) */
             double m[LNN_MAXT], slack[LNN_MAXT];
             const double rel = (2.0 * (double)c.na + 8.0) * 1.1102230246251565e-16;
@@ -693,6 +720,14 @@ __global__ __launch_bounds__(64) void k_select_wave(Plan p, uint32_t layer, uint
             if (p.force_exact) ok = 0;
             p.uncertain[job] = ok ? 0 : 1;
             if (!ok) atomicAdd(p.ucount, 1u);
+            if (p.capture) {
+                double *rec = capture_rec(p, job, layer);
+                for (uint32_t t = 0; t < nt; t++) {
+                    double *r = rec + t * LNN_CAP_WORDS;
+                    r[0] = m[t]; r[1] = slack[t]; r[2] = rel; r[3] = xmax; r[4] = s_hsum[t];
+                    r[5] = ok ? 0.0 : 1.0; r[7] = (double)c.trial_u[layer][t];
+                }
+            }
         }
         s_best = best;
         p.lunits[(size_t)job * LNN_MAXL + layer] = c.trial_u[layer][best];

@@ -23,6 +23,7 @@ REF_SO = os.path.join(ROOT, "oracle", "_ref", "liblinne_ref.so")
 MAX_CH, MAX_LAYERS, MAX_PARAMS = 8, 3, 128
 PRESET_LAYERS = {0: (2, 32), 1: (2, 32), 2: (4, 64, 8), 3: (4, 64, 8), 4: (4, 64, 8),
                  5: (4, 128, 16), 6: (4, 128, 16), 7: (4, 128, 16)}
+PRESET_NUM_REGULARS = {0: 1, 1: 2, 2: 1, 3: 2, 4: 4, 5: 1, 6: 2, 7: 4}
 
 
 from linne_amd.api import _planar_ptrs  # noqa: E402
@@ -84,6 +85,12 @@ class Oracle:
         L.oracle_huffman_code.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.oracle_bench_encode.restype = C.c_double
         L.oracle_bench_encode.argtypes = [C.POINTER(EncodeParameter), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.oracle_set_trial_tap.argtypes = [C.c_void_p, C.c_uint32]
+        L.oracle_set_trial_tap.restype = None
+        L.oracle_trial_tap_count.restype = C.c_uint32
+        L.oracle_set_trial_data_tap.argtypes = [C.c_void_p, C.c_uint64]
+        L.oracle_set_trial_data_tap.restype = None
+        L.oracle_trial_data_tap_count.restype = C.c_uint64
         self.L = L
 
     @staticmethod
@@ -182,6 +189,71 @@ class Oracle:
             ret = self.o.L.oracle_encode_frame_hotpath(self.h, x.ctypes.data, n, n, C.byref(tap), res.ctypes.data)
             assert ret == 0, ret
             return tap, res
+
+        def hotpath_trials(self, x, with_data=False):
+            """hotpath(x) with the trial tap set -> (tap, residual, searches): what every unit-count search of this frame's hot-path
+            call compared (linne_network.c:318-341).  searches[ch][pass][layer] is a dict of arrays over the layer's trials in the
+            reference's order: "units", "mean" (the ordered mean the reference's strict-< argmin ran on), "hmax" (largest L1 norm of a
+            unit's coefficients), "xmax" (max |layer input|), and the scalars "P", "n"; with_data adds "coef" [trial][P] (filter
+            order, units back to back) and "input" [n], from which a test can recompute the means on its own.  pass = the regulariser
+            passes of linne_network.c:605-627; the final pass (:628-629), which repeats the winning pass's searches bit for bit, is
+            checked against it and dropped.
+            The taps are THREAD-LOCAL in the oracle: they are set, filled and read inside this one call, on the calling thread.  A
+            pooled run calls this method on the worker's own thread; a tap set on one thread sees nothing of another's encode."""
+            x = np.ascontiguousarray(x, dtype=np.int32)
+            nch, n = x.shape
+            nl, R = len(PRESET_LAYERS[self.p.preset]), PRESET_NUM_REGULARS[self.p.preset]
+            nsearch = nch * (R + 1) * nl
+            buf = np.zeros((nsearch * 8, 5))
+            data = np.zeros(nsearch * (self.block + 8 * (MAX_PARAMS + 3)) if with_data else 1)
+            L = self.o.L
+            L.oracle_set_trial_tap(buf.ctypes.data, len(buf))
+            if with_data:
+                L.oracle_set_trial_data_tap(data.ctypes.data, len(data))
+            try:
+                tap, res = self.hotpath(x)
+                nrec, ndata = int(L.oracle_trial_tap_count()), int(L.oracle_trial_data_tap_count())
+            finally:
+                L.oracle_set_trial_tap(None, 0)
+                L.oracle_set_trial_data_tap(None, 0)
+            flat, cur, at = [], None, 0
+            for r in buf[:nrec]:
+                if r[1] == 1:                                       # (one unit divides everything: every search opens with it)
+                    cur = {"P": int(r[0]), "units": [], "mean": [], "hmax": [], "xmax": [], "coef": [], "input": None}
+                    flat.append(cur)
+                assert cur is not None and cur["P"] == int(r[0])
+                for k, v in zip(("units", "mean", "hmax", "xmax"), (int(r[1]), r[2], r[3], r[4])):
+                    cur[k].append(v)
+                if with_data:
+                    P, u, nn = (int(v) for v in data[at:at + 3])
+                    assert (P, u) == (int(r[0]), int(r[1]))
+                    cur["coef"].append(data[at + 3:at + 3 + P].copy())
+                    at += 3 + P
+                    if u == 1:
+                        cur["input"] = data[at:at + nn].copy()
+                        at += nn
+            assert len(flat) == nsearch and (not with_data or at == ndata), f"{len(flat)} searches tapped, {nsearch} expected"
+            out = []
+            for ch in range(nch):
+                passes = []
+                for ps in range(R + 1):
+                    layers = []
+                    for l in range(nl):
+                        s = flat[(ch * (R + 1) + ps) * nl + l]
+                        assert s["P"] == PRESET_LAYERS[self.p.preset][l]
+                        d = {"P": s["P"], "n": int(tap.num_analyze_samples), "units": np.array(s["units"], dtype=np.uint32)}
+                        for k in ("mean", "hmax", "xmax"):
+                            d[k] = np.array(s[k], dtype=np.float64)
+                        if with_data:
+                            d["coef"], d["input"] = np.array(s["coef"]), s["input"]
+                            assert len(d["input"]) == d["n"]
+                        layers.append(d)
+                    passes.append(layers)
+                best = int(tap.ch[ch].best_pass)
+                for l in range(nl):                                  # linne_network.c:628-629: the winning pass once more
+                    assert np.array_equal(passes[R][l]["mean"], passes[best][l]["mean"])
+                out.append(passes[:R])
+            return tap, res, out
 
     def encoder(self, nch, bits, rate, block, preset, ms, af_iters=0):
         return Oracle.Encoder(self, nch, bits, rate, block, preset, ms, af_iters)

@@ -584,6 +584,14 @@ static __thread double *g_trial_tap = NULL;
 static __thread uint32_t g_trial_tap_cap = 0, g_trial_tap_n = 0;
 void oracle_set_trial_tap(double *buf, uint32_t cap_records) { g_trial_tap = buf; g_trial_tap_cap = cap_records; g_trial_tap_n = 0; }
 uint32_t oracle_trial_tap_count(void) { return g_trial_tap_n; }
+/* TEST TAP beside it (tests/test_search_means_cpu.py): what the trials were computed FROM, so that a test can recompute every mean on its
+ * own.  When set, every trial appends { num_params, nunits, n }, its num_params coefficients in filter order (all units, as the
+ * residual loop above reads them) and -- for the first trial of a search, nunits = 1 -- the layer's n input samples.  A trial that
+ * does not fit stops the tap (the count stays at what is complete). */
+static __thread double *g_trial_data = NULL;
+static __thread uint64_t g_trial_data_cap = 0, g_trial_data_n = 0;
+void oracle_set_trial_data_tap(double *buf, uint64_t cap_doubles) { g_trial_data = buf; g_trial_data_cap = cap_doubles; g_trial_data_n = 0; }
+uint64_t oracle_trial_data_tap_count(void) { return g_trial_data_n; }
 /* linne_network.c:268-347 */
 static uint32_t layer_search_units(struct Layer *L, struct Lpc *c, const double *input, uint32_t n, uint32_t max_units, double reg)
 {
@@ -621,6 +629,17 @@ static uint32_t layer_search_units(struct Layer *L, struct Lpc *c, const double 
             for (unit = 0; unit < nunits; unit++) { double a = 0.0; for (k = 0; k < np; k++) a += fabs(L->params[unit * np + k]); if (a > hmax) hmax = a; }
             for (k = 0; k < n; k++) if (fabs(input[k]) > xmax) xmax = fabs(input[k]);
             rec[0] = L->num_params; rec[1] = nunits; rec[2] = mean_loss; rec[3] = hmax; rec[4] = xmax;
+        }
+        if (g_trial_data) {
+            const uint64_t need = 3u + L->num_params + (nunits == 1 ? n : 0u);
+            if (g_trial_data_n + need > g_trial_data_cap) g_trial_data = NULL;
+            else {
+                double *d = g_trial_data + g_trial_data_n;
+                d[0] = L->num_params; d[1] = nunits; d[2] = n;
+                memcpy(d + 3, L->params, sizeof(double) * L->num_params);
+                if (nunits == 1) memcpy(d + 3 + L->num_params, input, sizeof(double) * n);
+                g_trial_data_n += need;
+            }
         }
         if (mean_loss < min_loss) { min_loss = mean_loss; best = nunits; }
     }

@@ -120,9 +120,14 @@ uint32_t oracle_huffman_code(uint32_t sym, uint32_t *code);
 
 /* multi-threaded throughput helper for bench.py's cpu_baseline leg ("port"): encodes num_frames frames
  * (planar [frame][ch][block]) with num_threads handles over disjoint frames; returns seconds. */
-/* measurement tap (tools/search_margins.py): records of 5 doubles per trial of every unit-count search of THIS thread from now on */
+/* measurement / test tap: records of 5 doubles { num_params, nunits, mean, largest L1 norm of a unit's coefficients, max |input| } per
+ * trial of every unit-count search of THIS thread from now on (thread-local: set it, encode and read it on one thread) */
 void oracle_set_trial_tap(double *buf, uint32_t cap_records);
 uint32_t oracle_trial_tap_count(void);
+/* test tap beside it, thread-local too: per trial { num_params, nunits, n }, the trial's num_params coefficients in filter order and,
+ * for the one-unit trial that opens a search, the layer's n input samples (oracle_trial_data_tap_count: doubles written) */
+void oracle_set_trial_data_tap(double *buf, uint64_t cap_doubles);
+uint64_t oracle_trial_data_tap_count(void);
 double oracle_bench_encode(const struct OracleEncodeParameter *param, const int32_t *frames, uint32_t num_frames,
         uint32_t num_threads, uint64_t *total_bytes);
 

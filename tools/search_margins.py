@@ -7,7 +7,7 @@ An fp32 evaluation (inputs rounded to fp32, fp32 fused multiply-adds, products s
 lies within  (np + 4) 2^-24 (|x| + sum |h_k x_k|)  of the exact value; the trial's mean then carries the slack
 (np + 4) 2^-24 max|x| (1 + max_unit sum|h_k|).  The one-unit trial stays exact (its chain is the forward pass).
 usage: python3 tools/search_margins.py [frames] [out.json]"""
-import ctypes as C, json, os, sys
+import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np
@@ -17,28 +17,20 @@ from signals import music
 nframes = int(sys.argv[1]) if len(sys.argv) > 1 else 48
 block, nch, bits, preset = 10240, 2, 16, 7
 o = Oracle()
-o.L.oracle_set_trial_tap.argtypes = [C.c_void_p, C.c_uint32]
-o.L.oracle_trial_tap_count.restype = C.c_uint32
 x = music(nch, nframes * block, bits, seed=1)
 frames = x.reshape(nch, nframes, block).transpose(1, 0, 2)
-cap = nframes * nch * 4 * 32 * 2
-buf = np.zeros((cap, 5))
-o.L.oracle_set_trial_tap(buf.ctypes.data, cap)
+# a search = the records of one layer's trials (nunits 1, 2, 4, ...) as [num_params, nunits, mean, hmax, xmax]; every pass counts,
+# the final one (a repeat of the winner) as in the reference's run
+searches = []
 for f in range(nframes):
     enc = o.encoder(nch, bits, 44100, block, preset, True)
-    enc.hotpath(np.ascontiguousarray(frames[f]))
+    tap, _, tr = enc.hotpath_trials(np.ascontiguousarray(frames[f]))
     enc.close()
-n = o.L.oracle_trial_tap_count()
-o.L.oracle_set_trial_tap(None, 0)
-rec = buf[:n]
-# group the records into searches: a search = consecutive records of one num_params with nunits 1, 2, 4, ...
-searches, cur = [], []
-for r in rec:
-    if r[1] == 1 and cur:
-        searches.append(cur); cur = []
-    cur.append(r)
-if cur:
-    searches.append(cur)
+    for ch in range(nch):
+        for passes in (tr[ch], [tr[ch][int(tap.ch[ch].best_pass)]]):
+            for layers in passes:
+                for s in layers:
+                    searches.append([(s["P"], float(u), m, h, xm) for u, m, h, xm in zip(s["units"], s["mean"], s["hmax"], s["xmax"])])
 out = {}
 for P in (128, 16, 4):
     S = [s for s in searches if s[0][0] == P]
