@@ -216,7 +216,7 @@ class Context:
 
     def _check(self, ret, what):
         if ret != 0:
-            raise LinneAmdError(f"{what} -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}")
+            raise LinneAmdError(f"{what} -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
 
     def _fence(self):
         """own stream: everything torch has enqueued so far (allocations' fills, clones, H2D copies) is done before the library runs"""

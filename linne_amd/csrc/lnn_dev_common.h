@@ -88,7 +88,8 @@ struct Plan {
     const uint32_t *af_best; const double *af_loss;   /* [J] winner of the search passes and its loss, for the stats record (NULL: from jloss) */
     double *af_a;                       /* [J][MAXP]   coefficients in LPC order, units back to back                           */
     double *af_inv;                     /* [J][S]      1 / max(|residual|, 1e-6) per sample                                    */
-    double *af_R;                       /* [J][MAXP*MAXP] normal matrices, unit un of order np at un * np * np, row-major      */
+    double *af_R;                       /* [J][af_Rstride] normal matrices, unit un of order np at un * np * np, row-major     */
+    uint32_t af_Rstride;                /* the square of the preset's largest layer order (u units of order P / u fill u * (P / u)^2 <= P^2) */
     double *af_rv, *af_invd;            /* [J][MAXP]   right-hand sides / inverse diagonals, units back to back               */
     double *af_obj, *af_prev;           /* [J][MAXU]   objective of this / the previous iteration per unit                     */
     uint32_t *af_state;                 /* [J][MAXU]   0 iterating, 1 converged, 2 zero problem, 3 singular                    */

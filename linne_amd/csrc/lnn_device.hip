@@ -869,7 +869,7 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
             TAKE(tr.loss, double, CF); TAKE(tr.prev, double, CF); TAKE(tr.active, uint32_t, CF); TAKE(tr.nactive, uint32_t, 64);
         }
         if (ctx->af_iters) {      /* the final pass works on CF jobs */
-            TAKE(p.af_a, double, CF * LNN_MAXP); TAKE(p.af_inv, double, CF * S); TAKE(p.af_R, double, CF * hs.maxP * hs.maxP);
+            TAKE(p.af_a, double, CF * LNN_MAXP); TAKE(p.af_inv, double, CF * S); p.af_Rstride = hs.maxP * hs.maxP; TAKE(p.af_R, double, CF * p.af_Rstride);
             TAKE(p.af_rv, double, CF * LNN_MAXP); TAKE(p.af_invd, double, CF * LNN_MAXP);
             TAKE(p.af_obj, double, CF * LNN_MAXU); TAKE(p.af_prev, double, CF * LNN_MAXU); TAKE(p.af_state, uint32_t, CF * LNN_MAXU);
             TAKE(p.af_prob, uint32_t, CF * LNN_MAXU); TAKE(p.af_nprob, uint32_t, 64); TAKE(p.af_pivot, double, CF * LNN_MAXU);

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(AFM_THREADS) void k_af_matrix(Plan p, uint32_t laye
     }
     if (!valid) return;
     if (vec) p.af_rv[(size_t)job * LNN_MAXP + un * np + i] = acc;
-    else p.af_R[(size_t)job * LNN_MAXP * LNN_MAXP + (size_t)un * np * np + (size_t)i * np + j] = acc;
+    else p.af_R[(size_t)job * p.af_Rstride + (size_t)un * np * np + (size_t)i * np + j] = acc;
 }
 
 /* Cholesky step i, first half: the pivot sum of every live problem of order > i (lpc.c:416-420) */
@@ -170,7 +170,7 @@ __global__ void k_af_pivot(Plan p, uint32_t layer, uint32_t i)
     const uint32_t job = p.af_prob[k] / LNN_MAXU, un = p.af_prob[k] % LNN_MAXU;
     const uint32_t u = p.lunits[(size_t)job * LNN_MAXL + layer], np = p.P[layer] / u;
     if (p.af_state[(size_t)job * LNN_MAXU + un] != 0u || i >= np) { p.af_pivot[k] = 1.0; return; }
-    const double *A = p.af_R + (size_t)job * LNN_MAXP * LNN_MAXP + (size_t)un * np * np;
+    const double *A = p.af_R + (size_t)job * p.af_Rstride + (size_t)un * np * np;
     double sum = A[(size_t)i * np + i];
     for (int32_t kk = (int32_t)i - 1; kk >= 0; kk--) sum -= A[(size_t)i * np + kk] * A[(size_t)i * np + kk];
     p.af_pivot[k] = sum;
@@ -186,7 +186,7 @@ __global__ void k_af_column(Plan p, uint32_t layer, uint32_t i)
     if (p.af_state[(size_t)job * LNN_MAXU + un] != 0u || i >= np) return;
     const double invd = p.af_pivot[k];
     if (invd < 0.0) { __syncthreads(); if (tid == 0) p.af_state[(size_t)job * LNN_MAXU + un] = 3u; return; }
-    double *A = p.af_R + (size_t)job * LNN_MAXP * LNN_MAXP + (size_t)un * np * np;
+    double *A = p.af_R + (size_t)job * p.af_Rstride + (size_t)un * np * np;
     if (tid == 0) p.af_invd[(size_t)job * LNN_MAXP + un * np + i] = invd;
     for (uint32_t j = i + 1 + tid; j < np; j += blockDim.x) {
         double sum = A[(size_t)i * np + j];
@@ -204,7 +204,7 @@ __global__ void k_af_solve(Plan p, uint32_t layer)
     const size_t pi = (size_t)job * LNN_MAXU + un;
     if (p.af_state[pi] != 0u) return;
     const uint32_t u = p.lunits[(size_t)job * LNN_MAXL + layer], np = p.P[layer] / u;
-    const double *A = p.af_R + (size_t)job * LNN_MAXP * LNN_MAXP + (size_t)un * np * np;
+    const double *A = p.af_R + (size_t)job * p.af_Rstride + (size_t)un * np * np;
     const double *b = p.af_rv + (size_t)job * LNN_MAXP + un * np, *invd = p.af_invd + (size_t)job * LNN_MAXP + un * np;
     double *x = p.af_a + (size_t)job * LNN_MAXP + un * np;
     for (int32_t i = 0; i < (int32_t)np; i++) {

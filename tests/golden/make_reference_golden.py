@@ -14,6 +14,7 @@ TESTS = os.path.dirname(HERE)
 ROOT = os.path.dirname(TESTS)
 sys.path[:0] = [ROOT, TESTS]
 
+import call_history as ch  # noqa: E402
 import test_gpu_parity as gp  # noqa: E402
 import test_oracle_cpu as oc  # noqa: E402
 from refs import ANSWERS, REF_SO, Reference, blocks_key, cli_key, decode_key, digest, encode_key, reference_available  # noqa: E402
@@ -74,6 +75,14 @@ def main():
     # test_gpu_rice_oracle.py test_long_block_streams, test_oracle_cpu.py test_oracle_equals_reference_at_long_blocks
     for cfg in LONG_STREAMS:
         decode(encode(*long_stream_args(*cfg)))
+
+    # test_gpu_call_history.py test_one_handle_many_streams: the four streams ONE encoder handle of the reference writes in turn
+    # (call_history.handle_sequence), and its own decoder handle's round trip of them
+    xs, streams = ch.handle_inputs(), ch.handle_sequence(ref)
+    for i, (x, stream) in enumerate(zip(xs, streams)):
+        answers[ch.handle_key(i, x)] = dict(digest(stream), block_types=ch.block_types(stream))
+    for i, (ret, pcm) in zip(ch.DECODE_ORDER9, ch.decode_through_one_handle(ref, streams)):
+        assert ret == 0 and (pcm == xs[i]).all(), f"the reference's own round trip of stream {i}"
 
     # test_own_cli_matches_the_reference_cli: the reference CLI's .lnn of each WAV, and its WAV of each such .lnn
     with tempfile.TemporaryDirectory() as tmp:

@@ -17,6 +17,7 @@ the unit counts and best regularisers differ between the lanes of a wave; about 
 lengths from a small pool.  The oracle runs once per distinct (base, length).  Frame counts are chosen so that the channel-frame
 count is not a multiple of 64 (and of 8 or 4 where the channel count allows): the last block of every row kernel is partial.
 """
+import hashlib
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -130,7 +131,9 @@ class OracleBatch:
     """the oracle's hot path for every distinct (base, length) of a batch, and its own synthesis of its output; .key[f] indexes
     the per-key arrays for frame f"""
 
-    def __init__(self, oracle, batch, ms):
+    def __init__(self, oracle, batch, ms, cache=None, af=0, learn=0):
+        """cache: a dict that keeps the oracle's answers by (shape, settings, length, content) over many batches; af, learn: the
+        oracle's -a N / -l settings"""
         nch, bits, block, preset = batch["nch"], batch["bits"], batch["block"], batch["preset"]
         pairs = np.stack([batch["bmap"], batch["ns"].astype(np.int64)], axis=1)
         keys, self.key = np.unique(pairs, axis=0, return_inverse=True)
@@ -146,11 +149,17 @@ class OracleBatch:
         def one(k):
             b, n = int(keys[k][0]), int(keys[k][1])
             x = batch["bases"][b][:, :n]
-            enc = oracle.encoder(nch, bits, 44100, block, preset, ms)
+            ck = (nch, bits, block, preset, bool(ms), af, learn, n, hashlib.sha1(np.ascontiguousarray(x).tobytes()).hexdigest())
+            if cache is not None and ck in cache:
+                return (k, n) + cache[ck]
+            enc = oracle.encoder(nch, bits, 44100, block, preset, ms, af_iters=af)
+            oracle.L.oracle_encoder_set_learning(enc.h, learn)
             tap, r = enc.hotpath(x)
             enc.close()
             d = oracle.decode_hotpath([tap.ch[ch] for ch in range(nch)], r, bits, block, preset, ms)
             assert np.array_equal(d, x), f"base {b}, n = {n}: the oracle's own round trip"
+            if cache is not None:
+                cache[ck] = (tap, r, d)
             return k, n, tap, r, d
 
         with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
