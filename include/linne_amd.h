@@ -275,31 +275,73 @@ int LINNEAmd_Synchronize(struct LINNEAmdContext *ctx);
 /* Per-kernel timing of the last Encode/DecodeFramesDevice call, measured with HIP events recorded on the
  * context's stream around each launch (only while timing is enabled).  GetLastTimingMs returns the summed
  * milliseconds of all launches of one kernel kind (negative if none was recorded), GetLastTimingLaunches their
- * count.  which: 0 whole call, 1 prep, 2 window, 3 autocorrelation, 4 levinson, 5 trial residual, 6 loss sum,
- * 7 select, 8 forward, 9 final loss, 10 finalize (quantise + FIR cascade), 11 synthesis, 12 MS->LR,
- * 13 block-type statistics (runs on a side stream beside the analysis), 14 autocorrelation of the short layers
- * (kind 3 is the long layer's kernel), 15 / 16 trial residual / forward of layer 0 (int32 input; kinds 5 / 8 are the
- * double-input instantiations used by the other layers; when those layers run without the fused one-unit forward --
- * the last layer, or LINNE_AMD_SPECULATE=0 -- they are different kernels and report as kinds 18 / 19), 20 the last layer's
- * forward pass fused with its loss (k_fwd_loss; replaces 19 + 9 for the frames it takes), 21 / 22 / 23 the long layer's
- * autocorrelation with lanes = jobs (k_autocorr_hist for the trials of order P and P/2, k_autocorr_sub for the shorter ones;
- * replace 3 for the frames they take), 24 Rice scan + emission, 25 the long layer's search in one window pass (k_search_long;
- * replaces 5 for the frames it takes), 26 the real final pass of -a N, 27 the -l trainer, 28 Rice decoding, 30 / 31 the synthesis of
- * the long layer (k_synth_big) / of the short layers and the de-emphasis (k_synth_small); 11 is then the one-launch form
- * (k_synthesize), 32 the pipelined latency form (k_synth_pipe: small batches), 33 the throughput form of a layer (k_synth_rows / k_synth_rows8: four
- * or eight channel-frames per wave, what large batches take), 34 the de-emphasis behind it (k_deemph_lr; it includes MS->LR when whole frames
- * lie in a block of 64 rows: no kind 12 then).  The stream decoder (LINNEAmd_StreamIndexCreate / LINNEAmd_DecodeStreamDevice, each a
- * call of its own): 37 / 38 counting / writing the block candidates (k_sx_count / k_sx_write), 39 prefix sums (k_sx_scan), 40 successors
- * (k_sx_succ), 41 pointer doubling (k_sx_jump, a launch per level), 42 / 43 the chain's length / its blocks (k_sx_chain_len / k_sx_chain),
- * 44 CRC16 and block checks (k_sx_check), 45 parameter records (k_sx_params), 46 the Rice decoder's consumption check (k_sx_rice_check),
- * 47 placing the range into planar output (k_sx_place); the Rice decoding and the synthesis of a range report as 28 and 11-12, 30-36.
- * Many windows in one call (LINNEAmd_DecodeWindowsDevice; a launch of each per pass, with 28 and the synthesis' kinds between them):
- * 56 gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather), 57 parameter records (k_wx_params), 58 the consumption
- * check per window (k_wx_rice_check), 59 placing every window's samples (k_wx_place).
- * The stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above): 48 gathering
- * the planar input into frames (k_se_gather), 49 compacting the Rice plans for the host step (k_se_compact), 50 block sizes
- * (k_se_size), 51 their offsets (k_sx_scan), 52 parameter bits (k_se_params), 53 Rice codes (k_se_rice), 54 RAW payloads (k_se_raw),
- * 55 CRC16 and block headers (k_se_crc); a launch of each per pass. */
+ * count.  `which` is one of the kinds below; the numbers are ABI (callers pass them as plain integers). */
+enum LINNEAmdTimingKind {
+    LINNE_AMD_T_CALL = 0,               /* the whole call */
+    LINNE_AMD_T_PREP = 1,               /* prep (k_prep, and k_prep_slow behind it) */
+    LINNE_AMD_T_WINDOW = 2,             /* window */
+    LINNE_AMD_T_AUTOCORR = 3,           /* autocorrelation: the long layer's kernel */
+    LINNE_AMD_T_LEVINSON = 4,           /* levinson */
+    LINNE_AMD_T_SEARCH = 5,             /* trial residual (the double-input instantiation with the fused one-unit forward: layers behind layer 0) */
+    LINNE_AMD_T_EXACT = 6,              /* loss sum: the exact ordered chains and the selection after them */
+    LINNE_AMD_T_SELECT = 7,             /* select */
+    LINNE_AMD_T_FORWARD = 8,            /* forward (double input, behind a search with the fused one-unit forward) */
+    LINNE_AMD_T_FINAL_LOSS = 9,         /* final loss */
+    LINNE_AMD_T_FINALIZE = 10,          /* finalize (quantise + FIR cascade) */
+    LINNE_AMD_T_SYNTH = 11,             /* synthesis: the one-launch form (k_synthesize) */
+    LINNE_AMD_T_MS_TO_LR = 12,          /* MS->LR */
+    LINNE_AMD_T_STATS = 13,             /* block-type statistics (runs on a side stream beside the analysis) */
+    LINNE_AMD_T_AUTOCORR_SHORT = 14,    /* autocorrelation of the short layers */
+    LINNE_AMD_T_SEARCH_L0 = 15,         /* trial residual of layer 0 (int32 input) */
+    LINNE_AMD_T_FORWARD_L0 = 16,        /* forward of layer 0 (int32 input) */
+    LINNE_AMD_T_RICE_PLAN = 17,         /* Rice plan */
+    LINNE_AMD_T_SEARCH_PLAIN = 18,      /* trial residual without the fused one-unit forward (the last layer, or LINNE_AMD_SPECULATE=0): a different kernel from 5 */
+    LINNE_AMD_T_FORWARD_PLAIN = 19,     /* forward behind such a search: a different kernel from 8 */
+    LINNE_AMD_T_FWD_LOSS = 20,          /* the last layer's forward pass fused with its loss (k_fwd_loss, k_fwd_loss_mw, k_last_layer; replaces 19 + 9 for the frames it takes) */
+    LINNE_AMD_T_HIST_P = 21,            /* the long layer's autocorrelation with lanes = jobs: k_autocorr_hist for the trials of order P ... */
+    LINNE_AMD_T_HIST_P2 = 22,           /* ... and P/2 ... */
+    LINNE_AMD_T_HIST_SUB = 23,          /* ... k_autocorr_sub for the shorter ones (21-23 replace 3 for the frames they take) */
+    LINNE_AMD_T_RICE_EMIT = 24,         /* Rice scan + emission */
+    LINNE_AMD_T_SEARCH_LONG = 25,       /* the long layer's search in one window pass (k_search_long; replaces 5 for the frames it takes) */
+    LINNE_AMD_T_AF_PASS = 26,           /* the real final pass of -a N */
+    LINNE_AMD_T_TRAIN = 27,             /* the -l trainer */
+    LINNE_AMD_T_RICE_DECODE = 28,       /* Rice decoding */
+    LINNE_AMD_T_SYNTH_BIG = 30,         /* the synthesis of the long layer (k_synth_big) */
+    LINNE_AMD_T_SYNTH_SMALL = 31,       /* ... of the short layers and the de-emphasis (k_synth_small) */
+    LINNE_AMD_T_SYNTH_PIPE = 32,        /* the pipelined latency form (k_synth_pipe: small batches) */
+    LINNE_AMD_T_SYNTH_ROWS = 33,        /* the throughput form of a long layer (k_synth_rows<NCH > 0>: four channel-frames per wave, what large batches take) */
+    LINNE_AMD_T_DEEMPH_LR = 34,         /* the de-emphasis behind it (k_deemph_lr; it includes MS->LR when whole frames lie in a block of 64 rows: no kind 12 then) */
+    LINNE_AMD_T_SYNTH_L0_DE = 35,       /* layer 0 + de-emphasis + MS->LR in one launch (k_synth_l0_de) */
+    LINNE_AMD_T_SYNTH_ROWS_SHORT = 36,  /* the throughput form of a short layer (k_synth_rows<0> / k_synth_rows8: four or eight channel-frames per wave) */
+    /* the stream decoder (LINNEAmd_StreamIndexCreate / LINNEAmd_DecodeStreamDevice, each a call of its own); the Rice decoding and the
+     * synthesis of a range report as 28 and 11-12, 30-36 */
+    LINNE_AMD_T_SX_COUNT = 37,          /* counting the block candidates (k_sx_count) */
+    LINNE_AMD_T_SX_WRITE = 38,          /* writing them (k_sx_write) */
+    LINNE_AMD_T_SX_SCAN = 39,           /* prefix sums (k_sx_scan) */
+    LINNE_AMD_T_SX_SUCC = 40,           /* successors (k_sx_succ) */
+    LINNE_AMD_T_SX_JUMP = 41,           /* pointer doubling (k_sx_jump, a launch per level) */
+    LINNE_AMD_T_SX_CHAIN_LEN = 42,      /* the chain's length (k_sx_chain_len) */
+    LINNE_AMD_T_SX_CHAIN = 43,          /* its blocks (k_sx_chain) */
+    LINNE_AMD_T_SX_CHECK = 44,          /* CRC16 and block checks (k_sx_check) */
+    LINNE_AMD_T_SX_PARAMS = 45,         /* parameter records (k_sx_params) */
+    LINNE_AMD_T_SX_RICE_CHECK = 46,     /* the Rice decoder's consumption check (k_sx_rice_check) */
+    LINNE_AMD_T_SX_PLACE = 47,          /* placing the range into planar output (k_sx_place) */
+    /* the stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above); a
+     * launch of each per pass */
+    LINNE_AMD_T_SE_GATHER = 48,         /* gathering the planar input into frames (k_se_gather) */
+    LINNE_AMD_T_SE_COMPACT = 49,        /* compacting the Rice plans for the host step (k_se_compact) */
+    LINNE_AMD_T_SE_SIZE = 50,           /* block sizes (k_se_size) */
+    LINNE_AMD_T_SE_SCAN = 51,           /* their offsets (k_sx_scan) */
+    LINNE_AMD_T_SE_PARAMS = 52,         /* parameter bits (k_se_params) */
+    LINNE_AMD_T_SE_RICE = 53,           /* Rice codes (k_se_rice) */
+    LINNE_AMD_T_SE_RAW = 54,            /* RAW payloads (k_se_raw) */
+    LINNE_AMD_T_SE_CRC = 55,            /* CRC16 and block headers (k_se_crc) */
+    /* many windows in one call (LINNEAmd_DecodeWindowsDevice; a launch of each per pass, with 28 and the synthesis' kinds between them) */
+    LINNE_AMD_T_WX_GATHER = 56,         /* gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather) */
+    LINNE_AMD_T_WX_PARAMS = 57,         /* parameter records (k_wx_params) */
+    LINNE_AMD_T_WX_RICE_CHECK = 58,     /* the consumption check per window (k_wx_rice_check) */
+    LINNE_AMD_T_WX_PLACE = 59           /* placing every window's samples (k_wx_place) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block

@@ -4,39 +4,9 @@
 #define LNN_DEV_COMMON_H_INCLUDED
 
 
-#define LNN_MAXT        8       /* unit-count trials per layer: u = 1,2,...,128 */
-#define LNN_MAXU        128
-#define LNN_MAXP        128
-#define LNN_MAXL        3
-#define LNN_MAXR        4
-#define LNN_MAXCLS      16
-#define LNN_MAXCH       8
-#define LNN_ACW         256     /* autocorrelation words per (job, trial): P + u <= 256 */
-#define LNN_MAXSUB      8
-#define LNN_META        8
+#include "lnn_forms.h"                /* the LNN_MAX* constants, DevClass, RowRuns and the class predicates: one definition for host and device */
 typedef double lnn_d2 __attribute__((ext_vector_type(2)));
 typedef int lnn_v4i __attribute__((ext_vector_type(4)));
-
-/* one distinct frame length of a batch (full frames, the ragged tail, ...) */
-struct DevClass {
-    uint32_t n;                         /* valid samples                                             */
-    uint32_t na;                        /* analysis length (linne_encoder.c:644-655)                 */
-    uint32_t sin_off;                   /* offset of this class's SIN window table                   */
-    uint32_t pad;
-    uint32_t ntrials[LNN_MAXL];
-    uint32_t trial_u[LNN_MAXL][LNN_MAXT];
-    double   trial_div[LNN_MAXL][LNN_MAXT];   /* 4*pow(na/u - 1, -2) from the host libm (lpc.c:199)  */
-    uint32_t wt_off[LNN_MAXL][LNN_MAXT];      /* offset of the trial's Welch weight table (padded unit: n + max(p,4) entries) */
-};
-
-/* Rows of a chunk (channel-frames, or jobs) cut into runs of one length class, so that the kernels that put 64 rows on
- * the lanes of a wave see blocks of one class and may take their wave-uniform fast paths; a ragged last frame gets a
- * block of its own.  Run i = rows [row_begin[i], row_begin[i+1]) = blocks [blk_begin[i], blk_begin[i+1]) of 64 rows.
- * The host hands the frames of a call to the kernels sorted by class (Plan.frame_map leads back to the caller's order), so a
- * chunk never has more runs than there are classes.  Only with the sort switched off (LINNE_AMD_SORT=0, a test knob) can a
- * chunk exceed LNN_MAXRUN runs: then one run covers everything (blocks may mix classes: slower, same results). */
-#define LNN_MAXRUN LNN_MAXCLS
-struct RowRuns { uint32_t n; uint32_t mixed; uint32_t row_begin[LNN_MAXRUN + 1]; uint32_t blk_begin[LNN_MAXRUN + 1]; };   /* mixed: the one-run fallback */
 
 /* timing experiments (never in a release build): LNN_DBG_IS(p, v) is a compile-time false unless the library was built with
  * make EXPERIMENTS=1 */
@@ -102,16 +72,7 @@ struct Plan {
 #define LNN_CAP_WORDS   8       /* include/linne_amd.h LINNE_AMD_CAPTURE_WORDS: mean, slack, rel, xmax, thsum, how, ordered mean, units */
 
 typedef const double __attribute__((address_space(4))) *lnn_cdp;    /* constant address space: wave-uniform loads become scalar loads */
-#define LNN_FIR_TILE 2048u               /* samples per block of the search / forward kernels (lnn_k_fir.h FIR_TILE) */
-/* does k_search_long (lnn_k_search.h) produce this job's unit-count search of `layer`?  The long layer (64 / 128 taps) of a preset
- * with a layer behind it, every trial present, the analysis length whole 2048-sample tiles (all full 10240-sample frames);
- * k_fir2<2> keeps the other frames */
-__device__ __host__ __forceinline__ bool search_long_takes(const Plan &p, uint32_t layer, const DevClass &c)
-{
-    const uint32_t P = p.P[layer];
-    uint32_t nt = 0; for (uint32_t u = 1; u <= P && u <= (uint32_t)LNN_MAXU; u <<= 1) nt++;
-    return p.search_long && layer > 0 && layer + 1 < p.L && (P == 128u || P == 64u) && c.ntrials[layer] == nt && (c.na % LNN_FIR_TILE) == 0;
-}
+/* search_long_takes, fwd_loss_takes, hist_takes -- which frames the lanes = jobs kernels take -- are lnn_forms.h's: host and device share them */
 
 /* input sample i of the caller's PCM array */
 __device__ __forceinline__ int32_t pcm24_at(const void *base, size_t i)
@@ -120,19 +81,6 @@ __device__ __forceinline__ int32_t pcm24_at(const void *base, size_t i)
     return (int32_t)((uint32_t)b[0] | ((uint32_t)b[1] << 8)) | ((int32_t)(int8_t)b[2] << 16);
 }
 __device__ __forceinline__ int32_t pcm_at(const Plan &p, size_t i) { return p.pcm16 == 1u ? (int32_t)((const int16_t *)p.pcm)[i] : (p.pcm16 == 2u ? pcm24_at(p.pcm, i) : p.pcm[i]); }
-
-/* does k_fwd_loss (lnn_k_fwdloss.h) produce this job's last-layer loss?  (na: the job's analysis length) */
-__device__ __forceinline__ bool fwd_loss_takes(const Plan &p, uint32_t layer, uint32_t na) { return p.fused_last && layer + 1 == p.L && (na % (4u * p.P[layer])) == 0; }
-
-/* Which frames k_autocorr_hist / k_autocorr_sub (lnn_k_autocorr_hist.h) take (the others stay with k_autocorr2, which skips
- * the ones taken there): every trial present,
- * every unit a whole number of 16-sample tiles, the finest unit at least one weight tile long, rows 16-byte aligned. */
-__device__ __forceinline__ bool hist_takes(const Plan &p, uint32_t layer, const DevClass &c)
-{
-    const uint32_t P = p.P[layer];
-    uint32_t nt = 0; for (uint32_t u = 1; u <= P && u <= (uint32_t)LNN_MAXU; u <<= 1) nt++;
-    return p.hist && P >= 64u && c.ntrials[layer] == nt && (c.na % (16u << (nt - 1))) == 0 && (c.na >> (nt - 1)) >= 32u && (p.S & 3u) == 0;
-}
 
 /* ------------------------------------------------------------------------------------------------
  * small device helpers

@@ -30,9 +30,7 @@
 #include "linne_encoder.h"
 
 /* the kernels, in pipeline order */
-#include "lnn_dev_common.h"
-#define LEV_LDS(np_) (sizeof(double) * 64 * (size_t)(2 * (np_) + 3))       /* LDS columns of one Levinson problem set of order np_ */
-#define LEV_LDS_BUDGET ((size_t)160 * 1024)                                   /* LDS of a CU */
+#include "lnn_dev_common.h"             /* (brings lnn_forms.h: the shared structs, and which kernel form a call, a chunk, a layer gets) */
 #include "lnn_k_prep.h"
 #include "lnn_k_autocorr.h"
 #include "lnn_k_levinson.h"
@@ -50,6 +48,8 @@
 #include "lnn_k_stream.h"
 #include "lnn_k_windows.h"
 #include "lnn_k_stream_enc.h"
+/* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
+static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
  * host side of this TU: context, scratch arena, launch sequences, C-ABI
@@ -75,13 +75,8 @@ struct LINNEAmdContext {
     hipEvent_t fork_ev, join_ev;        /* side stream: the general autocorrelation kernel for the few frames the lanes = jobs kernels do not take */
     DevClass *d_cls; double *d_sin; uint64_t sin_cap; double *d_wt; uint64_t wt_cap; uint32_t *d_clsidx; uint64_t clsidx_cap; uint32_t *d_map;   /* class index per sorted row, then the sorted row's frame (same buffer) */ uint32_t *d_nsmp; uint64_t nsmp_cap;
     /* what the resident class tables were built for: a call with the same shape and frame lengths re-uses them */
-    DevClass sig_cls[LNN_MAXCLS]; struct LINNEAmdShape sig_shape; int sig_valid; uint32_t sig_ncls; uint64_t sig_sin_total, sig_wt_total;
+    LnnClassTable tab;
     /* pinned ring for the per-call frame metadata (class index, length), so that a call enqueues without a host sync */
-    int fwd_loss;                       /* LINNE_AMD_FWD_LOSS: last layer's forward pass and loss in one kernel (k_fwd_loss); -1 = by batch size */
-    int lev_ride;                       /* short Levinson trials ride along with the one-unit trial (LINNE_AMD_LEV_RIDE, default 1) */
-    int lev_wave;                       /* batches of <= 64 jobs: a wave per Levinson problem (LINNE_AMD_LEV_WAVE, default 1) */
-    int search_two;                     /* k_search_long in two passes over the window, five waves per SIMD (LINNE_AMD_SEARCH_TWO) */
-    int search_job;                     /* k_search_long with one block per job that walks the job's tiles: 1 always, 0 never ((jobs, tiles) blocks), -1 by the size of the batch (LINNE_AMD_SEARCH_JOB, default -1) */
     int last_search_form;               /* the form of the call's last k_search_long launch: 0 (jobs, tiles), 1 per job, -1 none (LINNEAmd_GetLastSearchLongForm) */
     const uint32_t *cur_idx;            /* class index per frame of the call being enqueued (host copy, in the meta ring) */
     uint32_t *meta_h[LNN_META]; uint64_t meta_cap[LNN_META]; hipEvent_t meta_ev[LNN_META]; int meta_used[LNN_META]; int meta_next;
@@ -92,15 +87,12 @@ struct LINNEAmdContext {
     hipStream_t rice_pool[LNN_RICE_STREAMS]; int n_rice_pool, rice_next;
     uint32_t *d_plan_nsmp; uint64_t plan_nsmp_cap; double rice_steps[32]; uint32_t rice_nsteps;
     int prod_ok;                        /* set per batch by build_classes, bit l: in layer l every class has all its trials and even unit lengths (k_autocorr_prod) */
-    int fir_small;                      /* LINNE_AMD_FIR_SMALL (default 1): register-window search kernel for layers of <= 16 taps */
     uint32_t learning;                  /* -l: the SGD trainer after the analysis (LINNEAmd_SetLearning), 0 = off */
     uint32_t af_iters;                  /* -a N: auxiliary-function iterations of the final pass (LINNEAmd_SetAfIterations), 0 = off */
     double *af_h; uint32_t af_h_cap;    /* pinned: a Cholesky step's pivots on their way through the host's pow() */
     int pcm16_next;                     /* the next EncodeFramesDevice call reads narrow samples: 1 int16, 2 packed 3-byte (set by the staging slots, cleared by the call) */
-    int force_exact;                    /* LINNE_AMD_EXACT=1: every unit-count search runs the exact ordered chains (diff against the certified search) */
     int capture_on;                     /* LINNEAmd_SetSearchCapture: the encode calls leave what k_select decided from (tests; off: Plan.capture is NULL) */
     double *d_capture; uint64_t capture_cap, capture_n;      /* its records on the device: capacity, and those of the last call */
-    int fir_spec;                       /* LINNE_AMD_SPECULATE (default 1): fuse the one-unit forward into the search of layers 0 .. L-2 */
     void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
     void *senc; uint64_t senc_cap;      /* scratch of EncodeStreamDevice: the buffers of one pass */
     void *wdec; uint64_t wdec_cap;      /* DecodeWindowsDevice: fail words, window and block records of one call (its passes' buffers are sdec) */
@@ -109,9 +101,7 @@ struct LINNEAmdContext {
     int span_keep;                      /* EncodeFramesDevice inside EncodeStreamDevice: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
-    /* debug / test knobs that select a kernel form per CALL (read_call_knobs: once at the top of an encode / decode call, never
-     * inside the chunk loop; production never sets them and gets the batch-size rules) */
-    struct { int sort, l0_products, wide, search_long, rows16, prep_general, stats_rows /* -1 = by batch size */, hist /* -1 = by batch size */, decode_kernel /* 0 = by batch size, 1 = wave, 2 = lanes, 3 = pipe, 4 = rows */, rows8, streams /* LINNE_AMD_STREAMS of this call, 0 = not given */, nostats, fwd_loss_mw /* LINNE_AMD_FWD_LOSS_MW (default 1): chunks below 65 536 jobs take the five-wave form of k_fwd_loss */, prep_defer /* LINNE_AMD_PREP_DEFER (default 1): inexact pre-emphasis sums go to k_prep_slow */, last_layer /* LINNE_AMD_LAST_LAYER (default 1): the last layer's search, forward pass and loss in one launch (k_last_layer) where it takes the chunk */, decode_fused /* LINNE_AMD_DECODE_FUSED (default 1): layer 0 + de-emphasis + MS -> LR in one launch */; uint32_t dbg_maxtr; } knob;
+    LnnKnobs knob;                      /* every form-selecting knob (lnn_forms.h): some read when the context is created, the others at the top of each call */
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf((ctx)->err, sizeof((ctx)->err), "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); return LNN_NG; } } while (0)
@@ -164,16 +154,14 @@ static int ctx_encode_streams(LINNEAmdContext *ctx)
     if (ctx->enc_streams_done) return LNN_OK;
     ctx->enc_streams_done = 1;
     {
-        const char *env = getenv("LINNE_AMD_STREAMS");
-        int ns = env ? atoi(env) : 2;                /* (two by default since round 3: see the rule at the chunk loop) */
-        ctx->nsub_forced = env != NULL;
-        if (ns < 1) ns = 1;
-        if (ns > LNN_MAXSUB) ns = LNN_MAXSUB;
+        int forced = 0;
+        const int ns = lnn_context_streams(&forced);     /* (two by default since round 3: see lnn_call_split) */
+        ctx->nsub_forced = forced;
         /* One stream of a process maps onto one of a few hardware queues (four by default); streams that share a queue run in
          * order whatever their events say.  A context therefore creates as few streams as it needs: two compute sub-streams
          * (LINNE_AMD_STREAMS=1: none -- the analysis then always runs on the context's own stream, as small batches do anyway). */
         ctx->nsub = 0;
-        for (int i = 0; i < ns && ns >= 2; i++) {
+        for (int i = 0; i < ns; i++) {
             if (hipStreamCreateWithFlags(&ctx->sub[i], hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->sub_done[i], hipEventDisableTiming) != hipSuccess) break;
             ctx->nsub++;
         }
@@ -205,14 +193,7 @@ extern "C" struct LINNEAmdContext *LINNEAmd_ContextCreate(int device, uint64_t s
     ctx->arena_bytes = scratch_bytes;
     if ((e = hipMalloc((void **)&ctx->d_cls, sizeof(DevClass) * LNN_MAXCLS)) != hipSuccess) { CC_FAIL("hipMalloc(classes)"); hipFree(ctx->arena); hipStreamDestroy(ctx->stream); free(ctx); return NULL; }
     if ((e = hipMalloc((void **)&ctx->d_ucount, 4 * sizeof(uint32_t))) != hipSuccess) { CC_FAIL("hipMalloc(counter)"); }
-    { const char *ex = getenv("LINNE_AMD_EXACT"); ctx->force_exact = ex ? atoi(ex) : 0; }
-    { const char *sp = getenv("LINNE_AMD_SPECULATE"); ctx->fir_spec = sp ? atoi(sp) : 1; }
-    { const char *lr = getenv("LINNE_AMD_LEV_RIDE"); ctx->lev_ride = lr ? atoi(lr) : 1; }
-    { const char *lw = getenv("LINNE_AMD_LEV_WAVE"); ctx->lev_wave = lw ? atoi(lw) : 1; }
-    { const char *st_ = getenv("LINNE_AMD_SEARCH_TWO"); ctx->search_two = st_ ? atoi(st_) : 1; }
-    { const char *sj_ = getenv("LINNE_AMD_SEARCH_JOB"); ctx->search_job = sj_ ? atoi(sj_) : -1; ctx->last_search_form = -1; }
-    { const char *fl = getenv("LINNE_AMD_FWD_LOSS"); ctx->fwd_loss = fl ? atoi(fl) : -1; }
-    { const char *sp = getenv("LINNE_AMD_FIR_SMALL"); ctx->fir_small = sp ? atoi(sp) : 1; }
+    lnn_knobs_read_context(&ctx->knob); ctx->last_search_form = -1;
     (void)hipFuncSetAttribute((const void *)k_levinson_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LEV_LDS_BUDGET);
     (void)hipFuncSetAttribute((const void *)k_synth_pipe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LEV_LDS_BUDGET);
     if ((e = hipEventCreate(&ctx->ev[0])) != hipSuccess || (e = hipEventCreate(&ctx->ev[1])) != hipSuccess) { CC_FAIL("hipEventCreate"); }
@@ -333,34 +314,6 @@ extern "C" int LINNEAmd_SetAfIterations(struct LINNEAmdContext *ctx, uint32_t it
     return LNN_OK;
 }
 extern "C" int LINNEAmd_EnableTiming(struct LINNEAmdContext *ctx, int enable) { if (!ctx) return LNN_INVALID_ARGUMENT; ctx->timing = enable; return LNN_OK; }
-static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-static void read_call_knobs(LINNEAmdContext *ctx)
-{
-    ctx->knob.sort = env_int("LINNE_AMD_SORT", 1);
-    ctx->knob.l0_products = env_int("LINNE_AMD_L0_PRODUCTS", 1);
-    ctx->knob.wide = env_int("LINNE_AMD_WIDE", 1);
-    ctx->knob.search_long = env_int("LINNE_AMD_SEARCH_LONG", 1);
-    ctx->knob.rows16 = env_int("LINNE_AMD_ROWS16", 1);
-    ctx->knob.prep_general = env_int("LINNE_AMD_PREP_GENERAL", 0);
-    ctx->knob.prep_defer = env_int("LINNE_AMD_PREP_DEFER", 1);
-    ctx->knob.fwd_loss_mw = env_int("LINNE_AMD_FWD_LOSS_MW", 1);
-    ctx->knob.last_layer = env_int("LINNE_AMD_LAST_LAYER", 1);
-    ctx->knob.stats_rows = env_int("LINNE_AMD_STATS_ROWS", -1);
-    { const char *e = getenv("LINNE_AMD_HIST"); ctx->knob.hist = e ? (atoi(e) != 0) : -1; }
-    ctx->knob.rows8 = env_int("LINNE_AMD_DECODE_ROWS8", -1);
-    ctx->knob.decode_fused = env_int("LINNE_AMD_DECODE_FUSED", 1);
-    { const char *e = getenv("LINNE_AMD_DECODE_KERNEL"); ctx->knob.decode_kernel = !e ? 0 : (strcmp(e, "wave") == 0 ? 1 : (strcmp(e, "pipe") == 0 ? 3 : (strcmp(e, "rows") == 0 ? 4 : 2))); }
-    /* LINNE_AMD_STREAMS per call: a call may use fewer compute sub-streams than the context created (bench.py times one step on
-     * one stream so that its per-kernel spans do not overlap); it cannot use more */
-    ctx->knob.streams = env_int("LINNE_AMD_STREAMS", 0);
-    if (ctx->knob.streams < 0) ctx->knob.streams = 0;
-#ifdef LNN_TIMING_EXPERIMENTS       /* builds for timing experiments only (make EXPERIMENTS=1): with these set the results are WRONG */
-    ctx->knob.dbg_maxtr = (uint32_t)env_int("LINNE_AMD_DBG_MAXTR", 0);
-    ctx->knob.nostats = env_int("LINNE_AMD_DBG_NOSTATS", 0);
-#else
-    ctx->knob.dbg_maxtr = 0; ctx->knob.nostats = 0;
-#endif
-}
 /* span bookkeeping: span_begin/span_end bracket one kernel launch with events when timing is on */
 static int span_begin(LINNEAmdContext *ctx, int kind, hipStream_t st)
 {
@@ -420,7 +373,6 @@ static int ensure_buf(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t 
     return LNN_OK;
 }
 
-struct HostShape { uint32_t L, R, P[LNN_MAXL], coef_off[LNN_MAXL], maxP; double regs[LNN_MAXR]; };
 static int shape_info(const struct LINNEAmdShape *s, HostShape *h)
 {
     if (!s || s->preset >= 8 || s->num_channels == 0 || s->num_channels > LNN_MAXCH || s->bits_per_sample == 0 || s->bits_per_sample > 32
@@ -473,102 +425,38 @@ static int upload_lengths(LINNEAmdContext *ctx, const struct LINNEAmdShape *shap
 /* The libm values of the path, behind names of their own so that a test can compare the box's libm with the committed
  * values of the build container (tests/golden/libm_values.json): were they ever to differ, the test names the cause where the
  * parity tests would only show hashes that do not match. */
-extern "C" double lnn_welch_divisor(uint32_t unit_samples) { return 4.0 * pow((double)(unit_samples - 1u), -2.0); }                        /* lpc.c:199 */
+extern "C" double lnn_welch_divisor(uint32_t unit_samples) { return lnn_welch_div(unit_samples); }                        /* lpc.c:199 */
 extern "C" double lnn_sin_window(uint32_t s, uint32_t n) { return sin((3.1415926535897932384626433832795029 * s) / (n - 1)); }            /* lpc.c:192 */
 extern "C" double lnn_cholesky_pivot(double sum) { return pow(sum, -0.5); }                                                                /* lpc.c:421 */
 
-/* one length class: analysis length, the unit counts each layer may try, their Welch divisors (host libm, lpc.c:199) and
- * the offsets of its tables; returns LNN_INVALID_FORMAT for a length the device path does not take */
-static int make_class(LINNEAmdContext *ctx, const HostShape *hs, uint32_t S, uint32_t n, uint64_t *sin_total, uint64_t *wt_total, DevClass *out)
-{
-    DevClass c; memset(&c, 0, sizeof(c));
-    c.n = n;
-    uint32_t na = ((n + 7u) / 8u) * 8u;             /* linne_encoder.c:652-654 */
-    if (na < hs->maxP) na = hs->maxP;
-    if (na > S) na = S;
-    c.na = na;
-    c.sin_off = (uint32_t)*sin_total; *sin_total += n;
-    for (uint32_t l = 0; l < hs->L; l++) {
-        const uint32_t maxu = hs->P[l] < 128u ? hs->P[l] : 128u;    /* linne_network.c:586,594 */
-        uint32_t nt = 0;
-        for (uint32_t u = 1; u <= maxu; u <<= 1) {
-            if ((hs->P[l] % u) != 0 || (na % u) != 0) continue;      /* linne_network.c:291-294 */
-            c.trial_u[l][nt] = u;
-            c.trial_div[l][nt] = lnn_welch_divisor(na / u);               /* lpc.c:199 */
-            c.wt_off[l][nt] = (uint32_t)*wt_total;
-            { const uint32_t pu = hs->P[l] / u; *wt_total += na / u + (pu > 4 ? pu : 4); *wt_total = (*wt_total + 3u) & ~(uint64_t)3u; }   /* tables start 32-byte aligned */
-            nt++;
-        }
-        c.ntrials[l] = nt;
-    }
-    *out = c;
-    return LNN_OK;
-}
-
-/* Builds the per-length classes of an encode batch (tables are host libm values) and the class-sorted
- * order the kernels work in: sorted row i is the caller's frame map[i]; rows of one class are contiguous (stable: the
- * caller's order inside a class), so that whatever the order of lengths in the batch -- many tracks back to back, each
- * with its ragged tail -- a chunk has at most one run per class and the lanes = rows kernels see class-homogeneous
- * blocks.  The class tables are CUMULATIVE: a length seen in an earlier call of the same shape keeps its slot, so a caller
- * that alternates between batches with and without a ragged tail (a pipelined stream, chunk after chunk) uploads tables
- * once per new length and never again; only then does the call synchronise the host.  The per-frame class index and the
- * map go through a pinned ring. */
+/* Builds the per-length classes of an encode batch and the class-sorted order the kernels work in (lnn_call_classes has the
+ * bookkeeping), fills the tables of new classes (host libm values) and uploads them: only a call with a new length
+ * synchronises the host.  The per-frame class index and the map go through a pinned ring. */
 static int build_classes(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape, const HostShape *hs,
         const uint32_t *h_num_samples, uint32_t F)
 {
-    uint32_t count[LNN_MAXCLS + 1];
-    uint32_t lens[LNN_MAXCLS], slot_of[LNN_MAXCLS], nlen = 0;
-    const uint32_t S = shape->num_samples_per_block;
     int m, ret;
     { const int r_ = meta_acquire(ctx, F, &m); if (r_ != LNN_OK) return r_; }
     uint32_t *idx = ctx->meta_h[m], *map = ctx->meta_h[m] + F, *raw = ctx->meta_h[m] + 2 * (size_t)F;
     ctx->cur_idx = idx;
-    /* pass 1: the distinct lengths of this call (raw[f] = index into lens[]) */
-    {
-        uint32_t last_n = 0, last_k = 0;
-        for (uint32_t f = 0; f < F; f++) {
-            const uint32_t n = h_num_samples ? h_num_samples[f] : S;
-            if (n == 0 || n > S) { snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", f, n); return LNN_INVALID_ARGUMENT; }
-            uint32_t k = last_k;
-            if (n != last_n || nlen == 0) {
-                for (k = 0; k < nlen; k++) if (lens[k] == n) break;
-                if (k == nlen) {
-                    if (nlen == LNN_MAXCLS) { snprintf(ctx->err, sizeof(ctx->err), "more than %d distinct frame lengths in one batch", LNN_MAXCLS); return LNN_INVALID_ARGUMENT; }
-                    lens[nlen++] = n;
-                }
-                last_n = n; last_k = k;
-            }
-            raw[f] = k;
-        }
+    LnnClassTable &tab = ctx->tab;
+    LnnCallClasses cc;
+    switch (lnn_call_classes(&tab, shape, hs, &ctx->knob, h_num_samples, F, idx, map, raw, &cc)) {
+    case LNN_CLS_BAD_LENGTH: snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", cc.error_frame, h_num_samples[cc.error_frame]); return LNN_INVALID_ARGUMENT;
+    case LNN_CLS_TOO_MANY: snprintf(ctx->err, sizeof(ctx->err), "more than %d distinct frame lengths in one batch", LNN_MAXCLS); return LNN_INVALID_ARGUMENT;
+    default: break;
     }
-    /* the resident table: keep it if it has (room for) every length of this call, else start over with this call's lengths */
-    const bool same_shape = ctx->sig_valid && memcmp(&ctx->sig_shape, shape, sizeof(*shape)) == 0;
-    uint32_t missing = 0;
-    for (uint32_t k = 0; k < nlen; k++) {
-        uint32_t j = 0;
-        if (same_shape) for (; j < ctx->sig_ncls; j++) if (ctx->sig_cls[j].n == lens[k]) break;
-        slot_of[k] = (same_shape && j < ctx->sig_ncls) ? j : 0xFFFFFFFFu;
-        if (slot_of[k] == 0xFFFFFFFFu) missing++;
-    }
-    if (missing) {
-        if (!same_shape || ctx->sig_ncls + missing > LNN_MAXCLS) {
-            ctx->sig_valid = 0; ctx->sig_ncls = 0; ctx->sig_sin_total = 0; ctx->sig_wt_total = 0;
-            memset(ctx->sig_cls, 0, sizeof(ctx->sig_cls));
-            for (uint32_t k = 0; k < nlen; k++) slot_of[k] = 0xFFFFFFFFu;
-        }
-        for (uint32_t k = 0; k < nlen; k++) if (slot_of[k] == 0xFFFFFFFFu) {
-            if ((ret = make_class(ctx, hs, S, lens[k], &ctx->sig_sin_total, &ctx->sig_wt_total, &ctx->sig_cls[ctx->sig_ncls])) != LNN_OK) { ctx->sig_valid = 0; ctx->sig_ncls = 0; return ret; }
-            slot_of[k] = ctx->sig_ncls++;
-        }
+    ctx->na_max = cc.na_max; ctx->prod_ok = cc.prod_ok;
+    if (cc.branch != LNN_CLS_REUSE) {
         /* (re)build and upload the tables of every resident class */
-        const uint64_t sin_total = ctx->sig_sin_total, wt_total = ctx->sig_wt_total;
-        double *tab = (double *)malloc(sizeof(double) * (sin_total ? sin_total : 1));
+        const uint64_t sin_total = tab.sin_total, wt_total = tab.wt_total;
+        double *sintab = (double *)malloc(sizeof(double) * (sin_total ? sin_total : 1));
         double *wt = (double *)calloc(wt_total ? wt_total : 1, sizeof(double));
-        if (!tab || !wt) { free(tab); free(wt); ctx->sig_valid = 0; ctx->sig_ncls = 0; snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-        for (uint32_t k = 0; k < ctx->sig_ncls; k++) {
-            const DevClass &c = ctx->sig_cls[k];
+        if (!sintab || !wt) { free(sintab); free(wt); tab.valid = 0; tab.ncls = 0; snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+        for (uint32_t k = 0; k < tab.ncls; k++) {
+            const DevClass &c = tab.cls[k];
             const uint32_t n = c.n;
-            for (uint32_t s = 0; s < n; s++) tab[c.sin_off + s] = lnn_sin_window(s, n);   /* lpc.c:192 */
+            for (uint32_t s = 0; s < n; s++) sintab[c.sin_off + s] = lnn_sin_window(s, n);   /* lpc.c:192 */
             /* Welch weights per trial over one padded unit (lpc.c:199-204): w[loc] = (div * h) * (n-1-h), h = min(loc, n-1-loc);
              * zero in the zero zone; the (never written) middle of an odd unit is handled on the device (Q1) */
             for (uint32_t l = 0; l < hs->L; l++)
@@ -586,44 +474,13 @@ static int build_classes(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape
         hipError_t e = hipDeviceSynchronize();
         ret = (e == hipSuccess) ? ensure_buf(ctx, (void **)&ctx->d_sin, &ctx->sin_cap, sizeof(double) * (sin_total ? sin_total : 1)) : LNN_NG;
         if (ret == LNN_OK) ret = ensure_buf(ctx, (void **)&ctx->d_wt, &ctx->wt_cap, sizeof(double) * (wt_total ? wt_total : 1));
-        if (ret != LNN_OK) { free(tab); free(wt); ctx->sig_valid = 0; ctx->sig_ncls = 0; return ret; }
-        e = hipMemcpyAsync(ctx->d_sin, tab, sizeof(double) * sin_total, hipMemcpyHostToDevice, ctx->stream);
+        if (ret != LNN_OK) { free(sintab); free(wt); tab.valid = 0; tab.ncls = 0; return ret; }
+        e = hipMemcpyAsync(ctx->d_sin, sintab, sizeof(double) * sin_total, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_wt, wt, sizeof(double) * wt_total, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_cls, ctx->sig_cls, sizeof(DevClass) * LNN_MAXCLS, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          /* tab / wt are freed here */
-        free(tab); free(wt);
-        if (e != hipSuccess) { ctx->sig_valid = 0; ctx->sig_ncls = 0; snprintf(ctx->err, sizeof(ctx->err), "class table upload: %s", hipGetErrorString(e)); return LNN_NG; }
-        ctx->sig_shape = *shape; ctx->sig_valid = 1;
-    }
-    /* pass 2: class slots in order of first appearance in this call, stable counting sort by class
-     * (LINNE_AMD_SORT=0: the caller's order, for tests of the mixed-run fallback) */
-    memset(count, 0, sizeof(count));
-    ctx->na_max = 0;
-    for (uint32_t k = 0; k < nlen; k++) if (ctx->sig_cls[slot_of[k]].na > ctx->na_max) ctx->na_max = ctx->sig_cls[slot_of[k]].na;
-    {
-        if (ctx->knob.sort == 0) { for (uint32_t f = 0; f < F; f++) { idx[f] = slot_of[raw[f]]; map[f] = f; } }
-        else {
-            for (uint32_t f = 0; f < F; f++) count[raw[f] + 1]++;
-            for (uint32_t k = 0; k < nlen; k++) count[k + 1] += count[k];
-            for (uint32_t f = 0; f < F; f++) { const uint32_t pos = count[raw[f]]++; idx[pos] = slot_of[raw[f]]; map[pos] = f; }
-        }
-    }
-    {       /* short layers by products (k_autocorr_prod): all trials present and every unit length even, in every class of this call */
-        ctx->prod_ok = 0;
-        for (uint32_t l = 0; l < hs->L; l++) {
-            if (hs->P[l] > 16u || !ctx->knob.l0_products) continue;
-            uint32_t nt = 0; for (uint32_t u = 1; u <= hs->P[l]; u <<= 1) nt++;
-            int ok = 1;
-            for (uint32_t k = 0; k < nlen; k++) { const DevClass &c = ctx->sig_cls[slot_of[k]]; if (c.ntrials[l] != nt || (c.na % (1u << nt)) != 0) ok = 0; }
-            if (ok) ctx->prod_ok |= 1 << l;
-        }
-        /* long layers by lanes = lags (k_autocorr_wide): a small batch, and every unit length of every trial a class has even */
-        for (uint32_t l = 0; l < hs->L; l++) {
-            if (hs->P[l] < 32u || hs->P[l] > 128u || !ctx->knob.wide || (uint64_t)F * shape->num_channels * (l == 0 ? 1u : hs->R) > 64u) continue;
-            int ok = 1;
-            for (uint32_t k = 0; k < nlen; k++) { const DevClass &c = ctx->sig_cls[slot_of[k]]; if (c.ntrials[l] == 0 || (c.na % (1u << c.ntrials[l])) != 0) ok = 0; }
-            if (ok) ctx->prod_ok |= 1 << l;
-        }
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_cls, tab.cls, sizeof(DevClass) * LNN_MAXCLS, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          /* sintab / wt are freed here */
+        free(sintab); free(wt);
+        if (e != hipSuccess) { tab.valid = 0; tab.ncls = 0; snprintf(ctx->err, sizeof(ctx->err), "class table upload: %s", hipGetErrorString(e)); return LNN_NG; }
     }
     if ((ret = ensure_buf(ctx, (void **)&ctx->d_clsidx, &ctx->clsidx_cap, sizeof(uint32_t) * 2 * (uint64_t)(F ? F : 1))) != LNN_OK) return ret;
     ctx->d_map = ctx->d_clsidx + F;
@@ -634,24 +491,6 @@ static int build_classes(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape
 }
 
 static uint64_t align_up(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
-/* RowRuns of a chunk of frames whose rows are `rpf` per frame (see lnn_dev_common.h) */
-static void build_runs(RowRuns *rr, const uint32_t *idx, uint32_t F, uint32_t rpf)
-{
-    uint32_t n = 0, f = 0;
-    rr->row_begin[0] = 0; rr->blk_begin[0] = 0;
-    while (f < F) {
-        uint32_t g = f + 1;
-        while (g < F && idx[g] == idx[f]) g++;
-        if (n == LNN_MAXRUN) { n = 0; break; }                  /* too many runs: one run over everything */
-        rr->row_begin[n + 1] = g * rpf;
-        rr->blk_begin[n + 1] = rr->blk_begin[n] + ((g - f) * rpf + 63u) / 64u;
-        n++; f = g;
-    }
-    rr->mixed = 0;
-    if (n == 0) { n = 1; rr->mixed = 1; rr->row_begin[1] = F * rpf; rr->blk_begin[1] = (F * rpf + 63u) / 64u; }
-    rr->n = n;
-}
 
 /* bytes of scratch one frame needs (C channel-frames, R passes each) */
 static uint64_t frame_scratch_bytes(const struct LINNEAmdShape *shape, const HostShape *hs, uint32_t af_iters = 0, uint32_t learning = 0)
@@ -685,81 +524,473 @@ extern "C" uint64_t LINNEAmd_ScratchBytesPerFrame(const struct LINNEAmdShape *sh
     return frame_scratch_bytes(shape, &hs);
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * dispatch helpers: one per kernel family, from run-time orders and flags to the template instantiation
+ * ---------------------------------------------------------------------------------------------- */
+/* a kernel template over the order of a short layer (2 / 4 / 8 / 16 taps) */
+#define LNN_BY_ORDER(P_, LAUNCH_) do { switch (P_) { case 2: LAUNCH_(2); break; case 4: LAUNCH_(4); break; case 8: LAUNCH_(8); break; default: LAUNCH_(16); break; } } while (0)
+/* a kernel template over <layer 0 reads the int32 channel, the search writes / the forward skips the one-unit trial> */
+#define LNN_BY_L0_SPEC(l0_, spec_, LAUNCH_) do { if (l0_) { if (spec_) LAUNCH_(true, true); else LAUNCH_(true, false); } else { if (spec_) LAUNCH_(false, true); else LAUNCH_(false, false); } } while (0)
+
 /* k_fir2 launcher: layer 0 reads the int32 channel (L0); `spec` = the search also writes the one-unit trial's forward output
  * (MODE 2) / the forward pass skips the jobs that chose one unit (MODE 1) */
-template <int MODE> static void launch_fir(hipStream_t st, const Plan &p, uint32_t l, uint32_t cur, uint32_t J, uint32_t tiles, bool spec)
+template <int MODE> static void launch_fir(hipStream_t st, const Plan &p, uint32_t l, uint32_t cur, uint32_t J, uint32_t grid_y, bool spec)
 {
-    const dim3 grid(J, (MODE == 1 && spec && J >= 4096u) ? 1u : tiles), blk(FIR_THREADS);      /* forward pass in batches: a block per job walks the tiles (few jobs have any work) */
-    if (l == 0) { if (spec) hipLaunchKernelGGL((k_fir2<MODE, true, true>), grid, blk, 0, st, p, l, cur); else hipLaunchKernelGGL((k_fir2<MODE, true, false>), grid, blk, 0, st, p, l, cur); }
-    else        { if (spec) hipLaunchKernelGGL((k_fir2<MODE, false, true>), grid, blk, 0, st, p, l, cur); else hipLaunchKernelGGL((k_fir2<MODE, false, false>), grid, blk, 0, st, p, l, cur); }
+    const dim3 grid(J, grid_y), blk(FIR_THREADS);
+#define LNN_F2(L0_, SPEC_) hipLaunchKernelGGL((k_fir2<MODE, L0_, SPEC_>), grid, blk, 0, st, p, l, cur)
+    LNN_BY_L0_SPEC(l == 0, spec, LNN_F2);
+#undef LNN_F2
 }
 
 /* search of a short layer (P <= 16): register-window kernel */
+template <int PP> static void launch_fir_small_p(hipStream_t st, const Plan &p, uint32_t l, uint32_t cur, const dim3 grid, bool spec)
+{
+#define LNN_FS(L0_, SPEC_) hipLaunchKernelGGL((k_fir_small<PP, L0_, SPEC_>), grid, dim3(FIR_THREADS), 0, st, p, l, cur)
+    LNN_BY_L0_SPEC(l == 0, spec, LNN_FS);
+#undef LNN_FS
+}
 static void launch_fir_small_search(hipStream_t st, const Plan &p, uint32_t l, uint32_t cur, uint32_t J, uint32_t tiles, bool spec, uint32_t P)
 {
-    const dim3 grid(l == 0 ? J / p.R : J, tiles), blk(FIR_THREADS);      /* layer 0: one block serves the R jobs of a channel-frame */
-#define LNN_FS(PP) do { \
-        if (l == 0) { if (spec) hipLaunchKernelGGL((k_fir_small<PP, true, true>), grid, blk, 0, st, p, l, cur); else hipLaunchKernelGGL((k_fir_small<PP, true, false>), grid, blk, 0, st, p, l, cur); } \
-        else        { if (spec) hipLaunchKernelGGL((k_fir_small<PP, false, true>), grid, blk, 0, st, p, l, cur); else hipLaunchKernelGGL((k_fir_small<PP, false, false>), grid, blk, 0, st, p, l, cur); } } while (0)
-    switch (P) { case 2: LNN_FS(2); break; case 4: LNN_FS(4); break; case 8: LNN_FS(8); break; default: LNN_FS(16); break; }
-#undef LNN_FS
+    const dim3 grid(l == 0 ? J / p.R : J, tiles);      /* layer 0: one block serves the R jobs of a channel-frame */
+#define LNN_FSP(PP_) launch_fir_small_p<PP_>(st, p, l, cur, grid, spec)
+    LNN_BY_ORDER(P, LNN_FSP);
+#undef LNN_FSP
+}
+
+static void launch_last_layer(hipStream_t st, const Plan &q, uint32_t l, uint32_t cur, uint32_t J)
+{
+#define LNN_LL(PP_) hipLaunchKernelGGL(k_last_layer<PP_>, dim3((J + 63) / 64), dim3(64), 0, st, q, l, cur)
+    LNN_BY_ORDER(q.P[l], LNN_LL);
+#undef LNN_LL
+}
+
+/* k_fwd_loss: a wave per 64 jobs; mw: its five-wave form */
+static void launch_fwd_loss(hipStream_t st, const Plan &q, uint32_t l, uint32_t cur, uint32_t J, bool mw)
+{
+    const dim3 g((J + 63) / 64);
+#define LNN_FLM(PP_) hipLaunchKernelGGL(k_fwd_loss_mw<PP_>, g, dim3(320), 0, st, q, l, cur)
+#define LNN_FL(PP_) hipLaunchKernelGGL(k_fwd_loss<PP_>, g, dim3(64), 0, st, q, l, cur)
+    if (mw) LNN_BY_ORDER(q.P[l], LNN_FLM); else LNN_BY_ORDER(q.P[l], LNN_FL);
+#undef LNN_FLM
+#undef LNN_FL
+}
+
+/* k_search_long<P, two passes, one block per job>; form: LnnLayerForms.search_form */
+static void launch_search_long(hipStream_t st, const Plan &q, uint32_t l, uint32_t cur, uint32_t J, uint32_t tiles, int form)
+{
+    const dim3 grid(J, form == 2 ? 1u : tiles), blk(FIR_THREADS);
+#define LNN_SL(TWO_, JOB_) do { if (q.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, TWO_, JOB_>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, TWO_, JOB_>), grid, blk, 0, st, q, l, cur); } while (0)
+    if (form == 2) LNN_SL(true, true); else if (form == 1) LNN_SL(true, false); else LNN_SL(false, false);
+#undef LNN_SL
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * the encode call: what its launchers share, and the launchers in pipeline order
+ * ---------------------------------------------------------------------------------------------- */
+struct EncodeCall {             /* one LINNEAmd_EncodeFramesDevice call */
+    const struct LINNEAmdShape *shape; HostShape hs; uint32_t C, S, num_frames, pcm16;
+    const int32_t *d_pcm; int32_t *d_residual, *d_params; double *d_stats;
+    LnnSplit split;
+};
+struct Chunk {                  /* one chunk of it on its stream */
+    LINNEAmdContext *ctx; hipStream_t st; const HostShape *hs;
+    uint32_t C, S, f0, Fc; uint64_t CF, J;
+    const uint32_t *idx;        /* class slot of each of its frames (host copy) */
+    Plan p; LnnChunkForms forms;
+    uint8_t *abase; uint64_t part_bytes;                /* its slice of the arena */
+    uint32_t *af_best; double *af_loss, *af_reg; TrainArgs tr;
+};
+struct Pass {                   /* the layers of one pass over the jobs of plan q: the R search passes, or the real final pass of -a N */
+    const Plan *q; const LnnChunkForms *forms; uint32_t J, af_iters;
+    uint32_t cur;               /* which half of `sig` holds the current layer's input */
+};
+
+static void fill_plan(Plan &p, const EncodeCall &e, uint32_t F)
+{
+    memset(&p, 0, sizeof(p));
+    p.C = e.C; p.S = e.S; p.bits = e.shape->bits_per_sample; p.L = e.hs.L; p.R = e.hs.R; p.F = F;
+    for (uint32_t l = 0; l < e.hs.L; l++) p.P[l] = e.hs.P[l];
+    p.scale = ldexp(1.0, -(int)(e.shape->bits_per_sample - 1));
+    p.pcm = e.d_pcm; p.pcm16 = e.pcm16; p.stats = e.d_stats;
+}
+
+/* statistics of every frame of the call: one launch beside the analysis */
+static int launch_stats(LINNEAmdContext *ctx, const EncodeCall &e)
+{
+    Plan ps; fill_plan(ps, e, e.num_frames);
+    ps.cls_of_frame = ctx->d_clsidx; ps.frame_map = ctx->d_map; ps.cls = ctx->d_cls; ps.sintab = ctx->d_sin;
+    hipStream_t ss = ctx->stream;
+    if (ctx->has_side) { ss = ctx->side; HIPCHK(ctx, hipStreamWaitEvent(ss, ctx->ev_start, 0)); }
+    if (!ctx->knob.nostats) {      /* (always, except in a build for timing experiments: without the statistics the block types are wrong) */
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_STATS, ss);
+        if (lnn_stats_rows_form(&ctx->knob, e.num_frames, e.C, e.S, e.hs.P[0])) {
+            const dim3 g((e.num_frames * e.C + 63u) / 64u);
+#define LNN_SR(W_, T_) do { if (e.pcm16 == 1u) hipLaunchKernelGGL((k_stats_rows<W_, 1>), g, dim3(T_), 0, ss, ps); else if (e.pcm16 == 2u) hipLaunchKernelGGL((k_stats_rows<W_, 2>), g, dim3(T_), 0, ss, ps); else hipLaunchKernelGGL((k_stats_rows<W_, 0>), g, dim3(T_), 0, ss, ps); } while (0)
+            if (e.hs.P[0] == 4u) LNN_SR(5, 320); else LNN_SR(3, 192);
+#undef LNN_SR
+        }
+        else hipLaunchKernelGGL(k_stats, dim3(e.num_frames, e.C), dim3(STAT_THREADS), 0, ss, ps);
+        span_end(ctx, sp_, ss);
+    }
+    if (ss != ctx->stream) HIPCHK(ctx, hipEventRecord(ctx->side_done, ss));
+    return LNN_OK;
+}
+
+/* the chunk's plan, its forms and the carve-up of its slice of the arena */
+static int chunk_setup(Chunk &k, LINNEAmdContext *ctx, const EncodeCall &e, uint32_t f0, uint32_t slot)
+{
+    const uint32_t S = e.S;
+    k.ctx = ctx; k.hs = &e.hs; k.C = e.C; k.S = S; k.f0 = f0;
+    k.st = e.split.use_sub ? ctx->sub[slot] : ctx->stream;
+    k.Fc = (e.num_frames - f0 < e.split.chunk) ? (e.num_frames - f0) : (uint32_t)e.split.chunk;
+    k.CF = (uint64_t)k.Fc * e.C; k.J = k.CF * e.hs.R;
+    k.idx = ctx->cur_idx + f0;
+    const uint64_t CF = k.CF, J = k.J;
+    const LnnChunkIn in = { &e.hs, e.C, S, k.Fc, ctx->tab.cls, k.idx, &ctx->knob, e.split.use_sub, ctx->has_side != 0, ctx->af_iters, ctx->learning, false };
+    lnn_chunk_forms(&in, &k.forms);
+    Plan &p = k.p;
+    fill_plan(p, e, k.Fc);
+    p.ms = e.shape->ch_process_method; p.J = (uint32_t)J;
+    for (uint32_t l = 0; l < e.hs.L; l++) p.coef_off[l] = e.hs.coef_off[l];
+    for (uint32_t r = 0; r < e.hs.R; r++) p.regs[r] = e.hs.regs[r];
+    p.resid = e.d_residual; p.prm = e.d_params;      /* the caller's arrays: rows of the class-sorted chunk reach them through frame_map */
+    p.fused_last = k.forms.fuse_cfg ? 1u : 0u;
+    p.search_long = ctx->knob.search_long ? 1u : 0u;
+    p.rows16 = ctx->knob.rows16 ? 1u : 0u;
+    p.prep_general = ctx->knob.prep_general ? 1u : 0u;
+    p.prep_defer = k.forms.prep_defer ? 1u : 0u;
+    lnn_build_runs(&p.runs[0], k.idx, k.Fc, e.C); lnn_build_runs(&p.runs[1], k.idx, k.Fc, e.C * e.hs.R);
+    p.hist = k.forms.hist ? 1u : 0u;
+    p.cls_of_frame = ctx->d_clsidx + f0; p.frame_map = ctx->d_map + f0; p.cls = ctx->d_cls; p.sintab = ctx->d_sin; p.wtab = ctx->d_wt; p.ucount = ctx->d_ucount; p.min_margin = (unsigned long long *)(ctx->d_ucount + 2); p.force_exact = ctx->knob.force_exact ? 1u : 0u; p.dbg_maxtr = ctx->knob.dbg_maxtr;
+    p.capture = ctx->capture_n ? ctx->d_capture : NULL;
+    k.part_bytes = e.split.part_bytes;
+    k.abase = (uint8_t *)ctx->arena + (size_t)slot * k.part_bytes;
+    uint8_t *a = k.abase;
+#define TAKE(ptr, type, count) do { ptr = (type *)a; a += align_up(sizeof(type) * (uint64_t)(count)); } while (0)
+    TAKE(p.xint, int32_t, CF * S); TAKE(p.xtmp, int32_t, CF * S);
+    TAKE(p.sig, double, J * 2 * S);
+    TAKE(p.acorr, double, J * LNN_MAXT * LNN_ACW); TAKE(p.tcoef, double, J * LNN_MAXT * LNN_MAXP);
+    TAKE(p.ptail, double, J * LNN_MAXT * LNN_MAXU); TAKE(p.ptail_set, uint8_t, J * LNN_MAXT * LNN_MAXU);
+    TAKE(p.tloss, double, J * LNN_MAXT); p.npart = ((S + FIR_TILE - 1) / FIR_TILE) * (FIR_THREADS / 64); TAKE(p.tsum, double, J * LNN_MAXT * p.npart); TAKE(p.txmax, double, J * p.npart); TAKE(p.thsum, double, J * LNN_MAXT); TAKE(p.uncertain, uint8_t, J); TAKE(p.lparams, double, J * LNN_MAXL * LNN_MAXP);
+    TAKE(p.lunits, uint32_t, J * LNN_MAXL); TAKE(p.jloss, double, J); TAKE(p.jtail, double, J);
+    TAKE(p.prep_slow_n, uint32_t, 64); TAKE(p.prep_slow_rows, uint32_t, CF);
+    k.af_best = NULL; k.af_loss = NULL; k.af_reg = NULL;
+    memset(&k.tr, 0, sizeof(k.tr));
+    TrainArgs &tr = k.tr;
+    if (ctx->af_iters || ctx->learning) { TAKE(k.af_best, uint32_t, CF); TAKE(k.af_loss, double, CF); TAKE(k.af_reg, double, CF); }
+    if (ctx->learning) {
+        TAKE(tr.buf, double, CF * TR_NBUF * S); TAKE(tr.dparams, double, CF * LNN_MAXL * LNN_MAXP); TAKE(tr.momentum, double, CF * LNN_MAXL * LNN_MAXP);
+        TAKE(tr.loss, double, CF); TAKE(tr.prev, double, CF); TAKE(tr.active, uint32_t, CF); TAKE(tr.nactive, uint32_t, 64);
+    }
+    if (ctx->af_iters) {      /* the final pass works on CF jobs */
+        TAKE(p.af_a, double, CF * LNN_MAXP); TAKE(p.af_inv, double, CF * S); p.af_Rstride = e.hs.maxP * e.hs.maxP; TAKE(p.af_R, double, CF * p.af_Rstride);
+        TAKE(p.af_rv, double, CF * LNN_MAXP); TAKE(p.af_invd, double, CF * LNN_MAXP);
+        TAKE(p.af_obj, double, CF * LNN_MAXU); TAKE(p.af_prev, double, CF * LNN_MAXU); TAKE(p.af_state, uint32_t, CF * LNN_MAXU);
+        TAKE(p.af_prob, uint32_t, CF * LNN_MAXU); TAKE(p.af_nprob, uint32_t, 64); TAKE(p.af_pivot, double, CF * LNN_MAXU);
+    }
+#undef TAKE
+    if ((uint64_t)(a - k.abase) > k.part_bytes) { snprintf(ctx->err, sizeof(ctx->err), "internal: arena overflow"); return LNN_NG; }
+    return LNN_OK;
+}
+
+/* k_prep, and behind it k_prep_slow for the channel-frames it listed (none for 16-bit material: its blocks leave at once) */
+static int launch_prep(Chunk &k)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &p = k.p;
+    if (p.prep_defer) HIPCHK(ctx, hipMemsetAsync(p.prep_slow_n, 0, sizeof(uint32_t), st));
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_PREP, st);
+    hipLaunchKernelGGL(k_prep, dim3(k.Fc, k.C), dim3(PREP_THREADS), 0, st, p);
+    if (p.prep_defer) hipLaunchKernelGGL(k_prep_slow, dim3((uint32_t)((k.CF + 63) / 64)), dim3(256), 0, st, p);
+    span_end(ctx, sp_, st);
+    return LNN_OK;
+}
+
+/* lags of layer l: the lanes = jobs kernels for the frames they take (hist_takes), the general kernels for the others */
+static int launch_lags(Chunk &k, const Pass &ps, uint32_t l)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
+    const uint32_t P = k.hs->P[l];
+    if (lf.beside) {
+        HIPCHK(ctx, hipEventRecord(ctx->fork_ev, st)); HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->fork_ev, 0));
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_AUTOCORR, ctx->side); dispatch_autocorr2(ctx->side, q, l, ps.cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, ctx->side);
+        HIPCHK(ctx, hipEventRecord(ctx->join_ev, ctx->side));
+    }
+    if (lf.hist_layer) {
+        for (int w = 0; w < 3; w++) {
+            if (P == 64u && w == 1) continue;
+            const int sp_ = span_begin(ctx, LINNE_AMD_T_HIST_P + w, st); (void)launch_autocorr_hist(st, q, l, ps.cur, w); span_end(ctx, sp_, st);
+        }
+    }
+    if (lf.beside) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join_ev, 0));
+    else if (!lf.hist_all) {
+        const int sp_ = span_begin(ctx, (P >= 32u) ? LINNE_AMD_T_AUTOCORR : LINNE_AMD_T_AUTOCORR_SHORT, st); dispatch_autocorr2(st, q, l, ps.cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, st);
+    }
+    return LNN_OK;
+}
+
+static void launch_levinson(Chunk &k, const Pass &ps, uint32_t l)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
+    const uint32_t P = k.hs->P[l], maxu = P < 128u ? P : 128u;
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_LEVINSON, st);
+    if (lf.lev_wave) hipLaunchKernelGGL(k_levinson_wave, dim3(ps.J, 2u * maxu - 1u), dim3(64), 0, st, q, l);
+    else for (uint32_t i = 0; i < lf.nlev; i++) {
+        const LnnLevLaunch &v = lf.lev[i];
+        hipLaunchKernelGGL(k_levinson_lds, dim3((ps.J + 63) / 64, v.u), dim3(v.threads), v.lds, st, q, l, v.t, v.ride);
+    }
+    span_end(ctx, sp_, st);
+}
+
+/* unit-count search of layer l: k_search_long for the frames it takes, the register-window kernel / k_fir2<2> for the others */
+static void launch_search(Chunk &k, const Pass &ps, uint32_t l)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
+    const uint32_t tiles = (k.S + FIR_TILE - 1) / FIR_TILE;
+    if (lf.long_any) {
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_SEARCH_LONG, st);
+        ctx->last_search_form = lf.search_form == 2 ? 1 : 0;
+        launch_search_long(st, q, l, ps.cur, ps.J, tiles, lf.search_form);
+        span_end(ctx, sp_, st);
+    }
+    if (lf.long_any && lf.long_all) return;
+    const int sp_ = span_begin(ctx, (l == 0) ? LINNE_AMD_T_SEARCH_L0 : (lf.fir_spec ? LINNE_AMD_T_SEARCH : LINNE_AMD_T_SEARCH_PLAIN), st);
+    if (lf.fir_small) launch_fir_small_search(st, q, l, ps.cur, ps.J, tiles, lf.fir_spec, k.hs->P[l]);
+    else if (lf.long_any) {
+        /* a launch per run of frames k_search_long leaves, not 620 k blocks of which all but a handful look up their job and go (0.7 ms) */
+        const uint32_t rpf = ps.J / k.Fc;
+        for (uint32_t f = 0, g = 0; lnn_next_left_run(&lf, k.idx, k.Fc, g, &f, &g); ) {
+            Plan qq = q; qq.job_off = f * rpf;
+            launch_fir<2>(st, qq, l, ps.cur, (g - f) * rpf, tiles, lf.fir_spec);
+        }
+    }
+    else launch_fir<2>(st, q, l, ps.cur, ps.J, tiles, lf.fir_spec);
+    span_end(ctx, sp_, st);
+}
+
+/* the selection, then the exact ordered chains for the (rare) jobs the certified search flagged (everything else exits at once) and
+ * the selection among those */
+static void launch_select(Chunk &k, const Pass &ps, uint32_t l)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
+    for (uint32_t exact = 0; exact < 2; exact++) {
+        const int sp_ = span_begin(ctx, exact ? LINNE_AMD_T_EXACT : LINNE_AMD_T_SELECT, st);
+        if (exact) { if (l == 0) hipLaunchKernelGGL((k_fir2<0, true, false>), dim3(ps.J, 1), dim3(FIR_THREADS), 0, st, q, l, ps.cur); else hipLaunchKernelGGL((k_fir2<0, false, false>), dim3(ps.J, 1), dim3(FIR_THREADS), 0, st, q, l, ps.cur); }
+        if (lf.sel_wave) hipLaunchKernelGGL(k_select_wave, dim3(ps.J), dim3(64), 0, st, q, l, exact);
+        else hipLaunchKernelGGL(k_select, dim3((ps.J + 63) / 64), dim3(64), 0, st, q, l, exact);
+        span_end(ctx, sp_, st);
+    }
+}
+
+/* -a N: the auxiliary-function iterations on the coefficients k_select kept for layer l (lnn_k_af.h); synchronous: every
+ * Cholesky pivot goes through the host's pow() */
+static int run_af(Chunk &k, const Pass &ps, uint32_t l)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q;
+    const uint32_t P = k.hs->P[l], S = k.S, Jq = ps.J, cur = ps.cur;
+    HIPCHK(ctx, hipMemsetAsync(q.af_nprob, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_af_init, dim3((Jq + 255) / 256), dim3(256), 0, st, q, l);
+    uint32_t nprob = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&nprob, q.af_nprob, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (nprob == 0) return LNN_OK;
+    if (ctx->af_h_cap < nprob) {
+        if (ctx->af_h) HIPCHK(ctx, hipHostFree(ctx->af_h));
+        ctx->af_h = NULL; ctx->af_h_cap = 0;
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->af_h, sizeof(double) * (size_t)nprob, hipHostMallocDefault));
+        ctx->af_h_cap = nprob;
+    }
+    uint32_t mblocks = 0;                                                      /* k_af_matrix: blocks per job, whatever unit count it chose */
+    for (uint32_t uu = 1; uu <= P; uu <<= 1) { const uint32_t b_ = uu * afm_blocks_per_unit(P / uu); if (b_ > mblocks) mblocks = b_; }
+    for (uint32_t it = 0; it < ps.af_iters; it++) {
+        hipLaunchKernelGGL(k_af_resid, dim3(Jq, (S + AFR_THREADS * 4 - 1) / (AFR_THREADS * 4)), dim3(AFR_THREADS), 0, st, q, l, cur);
+        hipLaunchKernelGGL(k_af_obj, dim3(nprob), dim3(64), 0, st, q, l, cur);
+        hipLaunchKernelGGL(k_af_matrix, dim3(Jq, mblocks), dim3(AFM_THREADS), 0, st, q, l, cur);
+        for (uint32_t i = 0; i < P; i++) {
+            hipLaunchKernelGGL(k_af_pivot, dim3((nprob + 63) / 64), dim3(64), 0, st, q, l, i);
+            HIPCHK(ctx, hipMemcpyAsync(ctx->af_h, q.af_pivot, sizeof(double) * (size_t)nprob, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            for (uint32_t j = 0; j < nprob; j++) { const double v = ctx->af_h[j]; ctx->af_h[j] = (v <= 0.0) ? -1.0 : lnn_cholesky_pivot(v); }      /* lpc.c:418-421, host libm */
+            HIPCHK(ctx, hipMemcpyAsync(q.af_pivot, ctx->af_h, sizeof(double) * (size_t)nprob, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_af_column, dim3(nprob), dim3(128), 0, st, q, l, i);
+        }
+        hipLaunchKernelGGL(k_af_solve, dim3((nprob + 63) / 64), dim3(64), 0, st, q, l);
+    }
+    hipLaunchKernelGGL(k_af_finish, dim3((Jq + 255) / 256), dim3(256), 0, st, q, l);
+    HIPCHK(ctx, hipGetLastError());
+    return LNN_OK;
+}
+
+/* the layers of one pass (linne_network.c:582-602): lags, Levinson-Durbin, the unit-count search, [the auxiliary-function refinement
+ * of the chosen coefficients], the forward pass.  Returns LNN_*; ps.cur = which half of `sig` holds the last layer's output */
+static int run_layers(Chunk &k, Pass &ps)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q;
+    const uint32_t L = k.hs->L, tiles = (k.S + FIR_TILE - 1) / FIR_TILE;
+    int ret;
+    ps.cur = 0;
+    for (uint32_t l = 0; l < L; l++) {
+        const LnnLayerForms &lf = ps.forms->layer[l];
+        if ((ret = launch_lags(k, ps, l)) != LNN_OK) return ret;
+        launch_levinson(k, ps, l);
+        if (lf.last_layer) {        /* search, selection, forward pass and loss from one pass over the input */
+            { const int sp_ = span_begin(ctx, LINNE_AMD_T_FWD_LOSS, st); launch_last_layer(st, q, l, ps.cur, ps.J); span_end(ctx, sp_, st); }
+            { const int sp_ = span_begin(ctx, LINNE_AMD_T_SELECT, st); hipLaunchKernelGGL(k_select, dim3((ps.J + 63) / 64), dim3(64), 0, st, q, l, 2u); span_end(ctx, sp_, st); }
+        } else {
+            launch_search(k, ps, l);
+            launch_select(k, ps, l);
+            if (lf.fwd_loss) { const int sp_ = span_begin(ctx, LINNE_AMD_T_FWD_LOSS, st); launch_fwd_loss(st, q, l, ps.cur, ps.J, lf.fwd_loss_mw); span_end(ctx, sp_, st); }
+        }
+        if (ps.af_iters && (ret = run_af(k, ps, l)) != LNN_OK) return ret;
+        if (lf.forward) {
+            const int sp_ = span_begin(ctx, (l == 0) ? LINNE_AMD_T_FORWARD_L0 : (lf.fir_spec ? LINNE_AMD_T_FORWARD : LINNE_AMD_T_FORWARD_PLAIN), st);
+            launch_fir<1>(st, q, l, ps.cur, ps.J, lf.forward_walk ? 1u : tiles, lf.fir_spec);
+            span_end(ctx, sp_, st);
+        }
+        ps.cur ^= 1u;
+    }
+    return LNN_OK;
+}
+
+/* -l: LINNENetworkTrainer_Train on the parameters the analysis left (lnn_k_train.h); synchronous: the host reads after every
+ * step how many channel-frames go on */
+static int run_train(Chunk &k, const Plan &q, const uint32_t *best)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; TrainArgs &tr = k.tr;
+    const uint32_t CF = (uint32_t)k.CF, L = k.hs->L;
+    tr.p = q; tr.best = best; tr.CF = CF;
+    const uint32_t tiles = (k.S + TR_TILE - 1) / TR_TILE;
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_TRAIN, st);
+    hipLaunchKernelGGL(k_tr_init, dim3((CF + 255) / 256), dim3(256), 0, st, tr);
+    for (uint32_t it = 0; it < 2000u; it++) {                      /* LINNE_TRAINING_PARAMETER_MAX_NUM_ITRATION, linne_internal.h:29 */
+        HIPCHK(ctx, hipMemsetAsync(tr.nactive, 0, sizeof(uint32_t), st));
+        for (uint32_t l = 0; l < L; l++) hipLaunchKernelGGL(k_tr_forward, dim3(CF, tiles), dim3(TR_THREADS), 0, st, tr, l);
+        hipLaunchKernelGGL(k_tr_loss, dim3(CF), dim3(64), 0, st, tr);                                   /* the loss and, in place, its gradient */
+        for (uint32_t l = L - 1; l >= 1; l--) hipLaunchKernelGGL(k_tr_back, dim3(CF, tiles), dim3(TR_THREADS), 0, st, tr, l);
+        hipLaunchKernelGGL(k_tr_gradp, dim3(CF, L), dim3(128), 0, st, tr);
+        hipLaunchKernelGGL(k_tr_update, dim3(CF), dim3(128), 0, st, tr, (double)0.8f, (double)0.1f, 1.0e-7);     /* linne_network.c:829, linne_internal.h:31-33 */
+        uint32_t left = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&left, tr.nactive, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        if (left == 0) break;
+    }
+    span_end(ctx, sp_, st);
+    HIPCHK(ctx, hipGetLastError());
+    return LNN_OK;
+}
+
+/* quantise + cascade: the parameter records and the residual */
+static void launch_finish(Chunk &k, const Plan &q)
+{
+    const uint32_t CF = (uint32_t)k.CF;
+    const int sp_ = span_begin(k.ctx, LINNE_AMD_T_FINALIZE, k.st);
+    hipLaunchKernelGGL(k_quantize, dim3(CF), dim3(64), 0, k.st, q);
+    hipLaunchKernelGGL(k_fir_cascade, dim3(CF, k.forms.cascade_walk ? 1u : (k.S + FIN_TILE - 1) / FIN_TILE), dim3(FIN_THREADS), 0, k.st, q);
+    span_end(k.ctx, sp_, k.st);
+}
+
+/* -a N: the final pass is real -- the winner's regulariser, the refinement after every layer's search, and therefore new inputs (and
+ * possibly new unit counts) for the layers behind it.  One job per channel-frame, general kernels: the same rules, asked with R = 1. */
+static int run_final_pass(Chunk &k)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &p = k.p;
+    const uint32_t CF = (uint32_t)k.CF;
+    int ret;
+    Plan q = p;
+    q.R = 1; q.J = CF; q.regs[0] = 0.0;
+    q.hist = 0; q.fused_last = 0; q.search_long = 0;
+    q.capture = NULL;                                       /* the final pass does not search: it refines the winner */
+    lnn_build_runs(&q.runs[1], k.idx, k.Fc, k.C);
+    q.job_reg = k.af_reg; q.af_best = k.af_best; q.af_loss = k.af_loss;
+    hipLaunchKernelGGL(k_af_best, dim3((CF + 255) / 256), dim3(256), 0, st, p, k.af_best, k.af_loss, k.af_reg);
+    const LnnChunkIn in = { k.hs, k.C, k.S, k.Fc, ctx->tab.cls, k.idx, &ctx->knob, false, ctx->has_side != 0, ctx->af_iters, ctx->learning, true };
+    LnnChunkForms ff;
+    lnn_chunk_forms(&in, &ff);
+    Pass fp = { &q, &ff, CF, ctx->af_iters, 0 };
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_AF_PASS, st);
+    if ((ret = run_layers(k, fp)) != LNN_OK) return ret;
+    span_end(ctx, sp_, st);
+    if (ctx->learning && (ret = run_train(k, q, NULL)) != LNN_OK) return ret;
+    launch_finish(k, q);
+    return LNN_OK;
+}
+
+/* everything of one chunk, on its stream */
+static int enqueue_chunk(Chunk &k)
+{
+    LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &p = k.p;
+    int ret;
+    if ((ret = launch_prep(k)) != LNN_OK) return ret;
+    Pass sp = { &p, &k.forms, (uint32_t)k.J, 0u, 0 };
+    if ((ret = run_layers(k, sp)) != LNN_OK) return ret;
+    if (k.forms.chain_sum) {
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_FINAL_LOSS, st);
+        if (k.forms.chain_sum_wave) hipLaunchKernelGGL(k_chain_sum_wave<1>, dim3((uint32_t)k.J), dim3(64), 0, st, p, 0u, sp.cur);
+        else hipLaunchKernelGGL(k_chain_sum<1>, dim3(((uint32_t)k.J + 63) / 64), dim3(SUM_THREADS), 0, st, p, 0u, sp.cur);
+        span_end(ctx, sp_, st);
+    }
+    if (ctx->af_iters) { if ((ret = run_final_pass(k)) != LNN_OK) return ret; }
+    else {                      /* the final pass of linne_network.c:628-629 repeats the winning pass bit for bit: skipped */
+        if (ctx->learning) {
+            hipLaunchKernelGGL(k_af_best, dim3(((uint32_t)k.CF + 255) / 256), dim3(256), 0, st, p, k.af_best, k.af_loss, k.af_reg);
+            if ((ret = run_train(k, p, k.af_best)) != LNN_OK) return ret;
+        }
+        launch_finish(k, p);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return LNN_OK;
+}
+
+/* the chunks are enqueued inside one function so that EVERY way out of the loop -- a failing HIP call, a failing layer pass --
+ * comes by the join in LINNEAmd_EncodeFramesDevice: with sub-streams forked off, the caller may only reuse its buffers once they
+ * have drained */
+static int enqueue_chunks(LINNEAmdContext *ctx, const EncodeCall &e)
+{
+    uint32_t chunk_index = 0;
+    for (uint32_t f0 = 0; f0 < e.num_frames; f0 += (uint32_t)e.split.chunk, chunk_index++) {
+        Chunk k;
+        int ret = chunk_setup(k, ctx, e, f0, chunk_index % e.split.nsub);
+        if (ret == LNN_OK) ret = enqueue_chunk(k);
+        if (ret != LNN_OK) return ret;
+    }
+    return LNN_OK;
 }
 
 extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdShape *shape,
         const int32_t *d_pcm, const uint32_t *h_num_samples, uint32_t num_frames,
         int32_t *d_residual, int32_t *d_params, double *d_stats)
 {
+    /* validate */
     if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
-    const uint32_t pcm16 = (uint32_t)ctx->pcm16_next;        /* 0 int32, 1 int16, 2 packed 3-byte samples (set by the staging slots) */
+    EncodeCall e;
+    e.pcm16 = (uint32_t)ctx->pcm16_next;        /* 0 int32, 1 int16, 2 packed 3-byte samples (set by the staging slots) */
     ctx->pcm16_next = 0;
     if (!shape || !d_pcm || !d_residual || !d_params || !d_stats) { snprintf(ctx->err, sizeof(ctx->err), "null argument"); return LNN_INVALID_ARGUMENT; }
     if (num_frames == 0) return LNN_OK;
-    HostShape hs;
-    int ret = shape_info(shape, &hs);
+    int ret = shape_info(shape, &e.hs);
     if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid shape"); return ret; }
+    e.shape = shape; e.C = shape->num_channels; e.S = shape->num_samples_per_block; e.num_frames = num_frames;
+    e.d_pcm = d_pcm; e.d_residual = d_residual; e.d_params = d_params; e.d_stats = d_stats;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((ret = ctx_encode_streams(ctx)) != LNN_OK) return ret;
-    read_call_knobs(ctx);
-    if ((ret = build_classes(ctx, shape, &hs, h_num_samples, num_frames)) != LNN_OK) return ret;
-
-    const uint32_t C = shape->num_channels, S = shape->num_samples_per_block;
-    const uint64_t per_frame = frame_scratch_bytes(shape, &hs, ctx->af_iters, ctx->learning);
+    lnn_knobs_read_call(&ctx->knob);
+    /* classes */
+    if ((ret = build_classes(ctx, shape, &e.hs, h_num_samples, num_frames)) != LNN_OK) return ret;
+    /* split */
+    const uint64_t per_frame = frame_scratch_bytes(shape, &e.hs, ctx->af_iters, ctx->learning);
     if (ctx->arena_bytes < per_frame * 4 + 65536) {       /* grow the arena to hold at least a few frames */
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipFree(ctx->arena)); ctx->arena = NULL; ctx->arena_bytes = 0;
         HIPCHK(ctx, hipMalloc(&ctx->arena, per_frame * 4 + 65536));
         ctx->arena_bytes = per_frame * 4 + 65536;
     }
-    /* frame groups ("chunks") rotate over nsub streams, each with its own slice of the arena */
-    uint32_t nsub = ctx->nsub > 0 ? (uint32_t)ctx->nsub : 1u;
-    const bool streams_forced = ctx->nsub_forced || ctx->knob.streams > 0;
-    if (ctx->knob.streams > 0 && (uint32_t)ctx->knob.streams < nsub) nsub = (uint32_t)ctx->knob.streams;
-    while (nsub > 1 && ((ctx->arena_bytes - 65536) / nsub < per_frame * 2 || num_frames < nsub * 512u)) nsub--;
-    /* By default a call is cut in two only if each half still fills the chip and keeps every large-batch kernel form (the rules below
-     * go by the jobs of a chunk: k_fwd_loss from 24 576): the halves' latency-bound kernels (Levinson-Durbin, the short layers' search,
-     * the selections) then run beside the other half's vector-unit-bound ones -- 83.1 -> 80.1 ms per step on the 60-minute batch
-     * (tools/streams_ab.sh).  Smaller batches keep one stream and the context's own (no fork / join around a block-at-a-time call). */
-    if (!streams_forced) while (nsub > 1 && (uint64_t)(num_frames / nsub) * C * hs.R < 32768u) nsub--;
-    const uint64_t part_bytes = ((ctx->arena_bytes - 65536) / nsub) & ~(uint64_t)255;
-    uint64_t chunk = part_bytes / per_frame;
-    if (chunk == 0) chunk = 1;
-    {   /* even split over the streams; every kernel carries the job index in grid.x: J = chunk * C * R is kept below 2^22 */
-        const uint64_t even = (num_frames + nsub - 1) / nsub;
-        if (chunk > even) chunk = even;
-        const uint64_t lim = 4194304u / ((uint64_t)C * hs.R);
-        if (chunk > lim) chunk = lim;
-        /* chunks of equal size (a multiple of the stream count): a small last chunk would run the latency-bound kernels
-         * nearly empty */
-        uint64_t nchunks = (num_frames + chunk - 1) / chunk;
-        nchunks = ((nchunks + nsub - 1) / nsub) * nsub;
-        chunk = (num_frames + nchunks - 1) / nchunks;
-    }
+    e.split = lnn_call_split(ctx->arena_bytes, per_frame, num_frames, e.C, e.hs.R, ctx->nsub, ctx->nsub_forced != 0, &ctx->knob);
+    const LnnSplit &sp = e.split;
     if (!ctx->span_keep) ctx->nspans = 0;
     ctx->last_search_form = -1;
     ctx->capture_n = 0;
     if (ctx->capture_on) {          /* one record per (frame, channel, pass, layer, trial slot) in the caller's order; slots no search fills stay NaN */
-        const uint64_t nrec = (uint64_t)num_frames * C * hs.R * hs.L * LNN_MAXT;
+        const uint64_t nrec = (uint64_t)num_frames * e.C * e.hs.R * e.hs.L * LNN_MAXT;
         if (ctx->capture_cap < nrec) {
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             if (ctx->d_capture) HIPCHK(ctx, hipFree(ctx->d_capture));
@@ -773,357 +1004,20 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount, 0, sizeof(uint32_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ucount + 2, 0x7F, 2 * sizeof(uint32_t), ctx->stream));      /* min margin: a huge double (0x7F7F...) */
     if (ctx->timing && !ctx->span_keep) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
-    const bool use_sub = ctx->nsub > 0 && (nsub > 1 || (streams_forced && ctx->knob.streams != 1));
-    if (use_sub || ctx->has_side) HIPCHK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    if (use_sub) for (uint32_t i = 0; i < nsub; i++) HIPCHK(ctx, hipStreamWaitEvent(ctx->sub[i], ctx->ev_start, 0));
-    {   /* statistics of every frame of the call: one launch beside the analysis */
-        Plan ps; memset(&ps, 0, sizeof(ps));
-        ps.C = C; ps.S = S; ps.bits = shape->bits_per_sample; ps.L = hs.L; ps.R = hs.R; ps.F = num_frames;
-        for (uint32_t l = 0; l < hs.L; l++) ps.P[l] = hs.P[l];
-        ps.scale = ldexp(1.0, -(int)(shape->bits_per_sample - 1));
-        ps.pcm = d_pcm; ps.pcm16 = pcm16; ps.stats = d_stats; ps.cls_of_frame = ctx->d_clsidx; ps.frame_map = ctx->d_map; ps.cls = ctx->d_cls; ps.sintab = ctx->d_sin;
-        hipStream_t ss = ctx->stream;
-        if (ctx->has_side) { ss = ctx->side; HIPCHK(ctx, hipStreamWaitEvent(ss, ctx->ev_start, 0)); }
-        if (!ctx->knob.nostats) {      /* (always, except in a build for timing experiments: without the statistics the block types are wrong) */
-        const int sp_ = span_begin(ctx, 13, ss);
-        /* batches: lanes = channel-frames (k_stats_rows); a few channel-frames: a block each (k_stats finishes one block sooner).  LINNE_AMD_STATS_ROWS forces either */
-        const bool rows_form = ctx->knob.stats_rows >= 0 ? (ctx->knob.stats_rows != 0) : ((uint64_t)num_frames * C >= 1024u);
-        if (rows_form && (S & 3u) == 0 && (hs.P[0] == 2u || hs.P[0] == 4u)) {
-            const dim3 g((num_frames * C + 63u) / 64u);
-            if (hs.P[0] == 4u) { if (pcm16 == 1u) hipLaunchKernelGGL((k_stats_rows<5, 1>), g, dim3(320), 0, ss, ps); else if (pcm16 == 2u) hipLaunchKernelGGL((k_stats_rows<5, 2>), g, dim3(320), 0, ss, ps); else hipLaunchKernelGGL((k_stats_rows<5, 0>), g, dim3(320), 0, ss, ps); }
-            else               { if (pcm16 == 1u) hipLaunchKernelGGL((k_stats_rows<3, 1>), g, dim3(192), 0, ss, ps); else if (pcm16 == 2u) hipLaunchKernelGGL((k_stats_rows<3, 2>), g, dim3(192), 0, ss, ps); else hipLaunchKernelGGL((k_stats_rows<3, 0>), g, dim3(192), 0, ss, ps); }
-        }
-        else hipLaunchKernelGGL(k_stats, dim3(num_frames, C), dim3(STAT_THREADS), 0, ss, ps);
-        span_end(ctx, sp_, ss); }
-        if (ss != ctx->stream) HIPCHK(ctx, hipEventRecord(ctx->side_done, ss));
-    }
-    /* the chunks are enqueued inside one function so that EVERY way out of the loop -- a failing HIP call, a failing layer pass --
-     * comes by the join below: with sub-streams forked off, the caller may only reuse its buffers once they have drained */
-    auto enqueue_chunks = [&]() -> int {
-    uint32_t chunk_index = 0;
-    for (uint32_t f0 = 0; f0 < num_frames; f0 += (uint32_t)chunk, chunk_index++) {
-        const uint32_t slot = chunk_index % nsub;
-        hipStream_t st = use_sub ? ctx->sub[slot] : ctx->stream;
-        const uint32_t Fc = (num_frames - f0 < chunk) ? (num_frames - f0) : (uint32_t)chunk;
-        const uint64_t CF = (uint64_t)Fc * C, J = CF * hs.R;
-        Plan p; memset(&p, 0, sizeof(p));
-        p.C = C; p.S = S; p.bits = shape->bits_per_sample; p.L = hs.L; p.R = hs.R; p.ms = shape->ch_process_method; p.F = Fc; p.J = (uint32_t)J;
-        for (uint32_t l = 0; l < hs.L; l++) { p.P[l] = hs.P[l]; p.coef_off[l] = hs.coef_off[l]; }
-        for (uint32_t r = 0; r < hs.R; r++) p.regs[r] = hs.regs[r];
-        p.scale = ldexp(1.0, -(int)(shape->bits_per_sample - 1));
-        p.pcm = d_pcm; p.pcm16 = pcm16; p.resid = d_residual; p.prm = d_params; p.stats = d_stats;      /* the caller's arrays: rows of the class-sorted chunk reach them through frame_map */
-        /* last layer: forward pass + loss in one kernel for the jobs it takes (fwd_loss_takes); the two-kernel form runs only
-         * when the chunk holds frames it does not take */
-        const uint32_t Plast = hs.P[hs.L - 1];
-        /* The lanes = jobs kernels need a batch that fills the chip with 64-job waves: below ~24 k jobs (k_fwd_loss: one wave per
-         * 64 jobs) / ~12 k jobs (k_autocorr_hist: one block per 64 jobs and trial) the block-per-job kernels finish sooner --
-         * a single stereo frame takes 2.6 ms with them, 6.2 ms without this rule.  The environment forces either form. */
-        const bool fwd_loss_on = (ctx->fwd_loss < 0) ? (J >= 24576u) : (ctx->fwd_loss != 0);
-        const bool fuse_cfg = fwd_loss_on && hs.L > 1 && (Plast == 2u || Plast == 4u || Plast == 8u || Plast == 16u);
-        bool fuse_all = fuse_cfg;
-        for (uint32_t f = f0; f < f0 + Fc && fuse_all; f++) if ((ctx->sig_cls[ctx->cur_idx[f]].na % (4u * Plast)) != 0) fuse_all = false;
-        p.fused_last = fuse_cfg ? 1u : 0u;
-        /* k_last_layer (search + forward pass + loss of the last layer in one launch) takes a chunk whole or not at all: every frame
-         * k_fwd_loss's and with every trial (LINNE_AMD_EXACT keeps the certified search's exact fallback in use: that knob compares the two) */
-        /* (from 49 152 jobs on, or when LINNE_AMD_LAST_LAYER=2 says always: with lanes = jobs and a wave per 64 of them a chunk of J jobs is
-         * J / 64 waves on 1024 SIMDs, and a lone wave walks its frames in 4.1 ms however few they are -- the 31 008 jobs of a group of
-         * EncodeWhole took 4.1 ms here and 1.8 in the three kernels: 108 -> 110.5 ms per 60-minute stream) */
-        bool last_layer_all = fuse_all && ctx->knob.last_layer && !ctx->force_exact && !ctx->af_iters && !ctx->learning && (J >= (use_sub ? 49152u : 81920u) || (ctx->knob.last_layer == 2 && J > 256u));      /* (a chunk alone on the GPU has nothing beside its lone waves: it pays from ~78 k jobs on -- 124 k x 4.1 / 6.6) */
-        if (last_layer_all) {
-            uint32_t nt = 0; for (uint32_t u = 1; u <= Plast && u <= (uint32_t)LNN_MAXU; u <<= 1) nt++;
-            for (uint32_t f = f0; f < f0 + Fc && last_layer_all; f++) if (ctx->sig_cls[ctx->cur_idx[f]].ntrials[hs.L - 1] != nt) last_layer_all = false;
-        }
-        p.search_long = ctx->knob.search_long ? 1u : 0u;
-        p.rows16 = ctx->knob.rows16 ? 1u : 0u;
-        p.prep_general = ctx->knob.prep_general ? 1u : 0u;
-        p.prep_defer = (ctx->knob.prep_defer && !ctx->knob.prep_general && (S & 3u) == 0 && CF * S * sizeof(int32_t) <= 0xFFFFFFFFull) ? 1u : 0u;      /* (k_prep_slow addresses xtmp with 32-bit byte offsets) */
-        build_runs(&p.runs[0], ctx->cur_idx + f0, Fc, C); build_runs(&p.runs[1], ctx->cur_idx + f0, Fc, C * hs.R);
-        p.hist = (ctx->knob.hist >= 0 ? (ctx->knob.hist != 0) : (J >= 12288u)) ? 1u : 0u;
-        if (p.runs[1].mixed) p.hist = 0;                        /* more class runs than RowRuns holds: blocks may mix classes, which only the general kernels serve */
-        bool hist_all[LNN_MAXL];                                /* per layer: every frame of the chunk is k_autocorr_hist's (host copy of hist_takes) */
-        for (uint32_t l = 0; l < hs.L; l++) {
-            uint32_t nt = 0; for (uint32_t u = 1; u <= hs.P[l] && u <= (uint32_t)LNN_MAXU; u <<= 1) nt++;
-            hist_all[l] = p.hist && hs.P[l] >= 64u && (S & 3u) == 0;
-            for (uint32_t f = f0; f < f0 + Fc && hist_all[l]; f++) {
-                const DevClass &c = ctx->sig_cls[ctx->cur_idx[f]];
-                if (!(c.ntrials[l] == nt && (c.na % (16u << (nt - 1))) == 0 && (c.na >> (nt - 1)) >= 32u)) hist_all[l] = false;
-            }
-        }
-        p.cls_of_frame = ctx->d_clsidx + f0; p.frame_map = ctx->d_map + f0; p.cls = ctx->d_cls; p.sintab = ctx->d_sin; p.wtab = ctx->d_wt; p.ucount = ctx->d_ucount; p.min_margin = (unsigned long long *)(ctx->d_ucount + 2); p.force_exact = ctx->force_exact ? 1u : 0u; p.dbg_maxtr = ctx->knob.dbg_maxtr;
-        p.capture = ctx->capture_n ? ctx->d_capture : NULL;
-        uint8_t *const abase = (uint8_t *)ctx->arena + (size_t)slot * part_bytes;
-        uint8_t *a = abase;
-#define TAKE(ptr, type, count) do { ptr = (type *)a; a += align_up(sizeof(type) * (uint64_t)(count)); } while (0)
-        TAKE(p.xint, int32_t, CF * S); TAKE(p.xtmp, int32_t, CF * S);
-        TAKE(p.sig, double, J * 2 * S);
-        TAKE(p.acorr, double, J * LNN_MAXT * LNN_ACW); TAKE(p.tcoef, double, J * LNN_MAXT * LNN_MAXP);
-        TAKE(p.ptail, double, J * LNN_MAXT * LNN_MAXU); TAKE(p.ptail_set, uint8_t, J * LNN_MAXT * LNN_MAXU);
-        TAKE(p.tloss, double, J * LNN_MAXT); p.npart = ((S + FIR_TILE - 1) / FIR_TILE) * (FIR_THREADS / 64); TAKE(p.tsum, double, J * LNN_MAXT * p.npart); TAKE(p.txmax, double, J * p.npart); TAKE(p.thsum, double, J * LNN_MAXT); TAKE(p.uncertain, uint8_t, J); TAKE(p.lparams, double, J * LNN_MAXL * LNN_MAXP);
-        TAKE(p.lunits, uint32_t, J * LNN_MAXL); TAKE(p.jloss, double, J); TAKE(p.jtail, double, J);
-        TAKE(p.prep_slow_n, uint32_t, 64); TAKE(p.prep_slow_rows, uint32_t, CF);
-        uint32_t *af_best = NULL; double *af_loss = NULL, *af_reg = NULL;
-        TrainArgs tr; memset(&tr, 0, sizeof(tr));
-        if (ctx->af_iters || ctx->learning) { TAKE(af_best, uint32_t, CF); TAKE(af_loss, double, CF); TAKE(af_reg, double, CF); }
-        if (ctx->learning) {
-            TAKE(tr.buf, double, CF * TR_NBUF * S); TAKE(tr.dparams, double, CF * LNN_MAXL * LNN_MAXP); TAKE(tr.momentum, double, CF * LNN_MAXL * LNN_MAXP);
-            TAKE(tr.loss, double, CF); TAKE(tr.prev, double, CF); TAKE(tr.active, uint32_t, CF); TAKE(tr.nactive, uint32_t, 64);
-        }
-        if (ctx->af_iters) {      /* the final pass works on CF jobs */
-            TAKE(p.af_a, double, CF * LNN_MAXP); TAKE(p.af_inv, double, CF * S); p.af_Rstride = hs.maxP * hs.maxP; TAKE(p.af_R, double, CF * p.af_Rstride);
-            TAKE(p.af_rv, double, CF * LNN_MAXP); TAKE(p.af_invd, double, CF * LNN_MAXP);
-            TAKE(p.af_obj, double, CF * LNN_MAXU); TAKE(p.af_prev, double, CF * LNN_MAXU); TAKE(p.af_state, uint32_t, CF * LNN_MAXU);
-            TAKE(p.af_prob, uint32_t, CF * LNN_MAXU); TAKE(p.af_nprob, uint32_t, 64); TAKE(p.af_pivot, double, CF * LNN_MAXU);
-        }
-#undef TAKE
-        if ((uint64_t)(a - abase) > part_bytes) { snprintf(ctx->err, sizeof(ctx->err), "internal: arena overflow"); return LNN_NG; }
-        const uint32_t sblocks = (S + 255) / 256;
-        if (p.prep_defer) HIPCHK(ctx, hipMemsetAsync(p.prep_slow_n, 0, sizeof(uint32_t), st));
-        {   /* k_prep, and behind it k_prep_slow for the channel-frames it listed (none for 16-bit material: its blocks leave at once) */
-            const int sp_ = span_begin(ctx, 1, st);
-            hipLaunchKernelGGL(k_prep, dim3(Fc, C), dim3(PREP_THREADS), 0, st, p);
-            if (p.prep_defer) hipLaunchKernelGGL(k_prep_slow, dim3((uint32_t)((CF + 63) / 64)), dim3(256), 0, st, p);
-            span_end(ctx, sp_, st);
-        }
-        /* -a N: the auxiliary-function iterations on the coefficients k_select kept for layer l (lnn_k_af.h); synchronous: every
-         * Cholesky pivot goes through the host's pow() */
-        auto run_af = [&](const Plan &q, uint64_t Jq, uint32_t l, uint32_t cur, uint32_t iters) -> int {
-            const uint32_t P = hs.P[l];
-            HIPCHK(ctx, hipMemsetAsync(q.af_nprob, 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(k_af_init, dim3(((uint32_t)Jq + 255) / 256), dim3(256), 0, st, q, l);
-            uint32_t nprob = 0;
-            HIPCHK(ctx, hipMemcpyAsync(&nprob, q.af_nprob, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            if (nprob == 0) return LNN_OK;
-            if (ctx->af_h_cap < nprob) {
-                if (ctx->af_h) HIPCHK(ctx, hipHostFree(ctx->af_h));
-                ctx->af_h = NULL; ctx->af_h_cap = 0;
-                HIPCHK(ctx, hipHostMalloc((void **)&ctx->af_h, sizeof(double) * (size_t)nprob, hipHostMallocDefault));
-                ctx->af_h_cap = nprob;
-            }
-            uint32_t mblocks = 0;                                                      /* k_af_matrix: blocks per job, whatever unit count it chose */
-            for (uint32_t uu = 1; uu <= P; uu <<= 1) { const uint32_t b_ = uu * afm_blocks_per_unit(P / uu); if (b_ > mblocks) mblocks = b_; }
-            for (uint32_t it = 0; it < iters; it++) {
-                hipLaunchKernelGGL(k_af_resid, dim3((uint32_t)Jq, (S + AFR_THREADS * 4 - 1) / (AFR_THREADS * 4)), dim3(AFR_THREADS), 0, st, q, l, cur);
-                hipLaunchKernelGGL(k_af_obj, dim3(nprob), dim3(64), 0, st, q, l, cur);
-                hipLaunchKernelGGL(k_af_matrix, dim3((uint32_t)Jq, mblocks), dim3(AFM_THREADS), 0, st, q, l, cur);
-                for (uint32_t i = 0; i < P; i++) {
-                    hipLaunchKernelGGL(k_af_pivot, dim3((nprob + 63) / 64), dim3(64), 0, st, q, l, i);
-                    HIPCHK(ctx, hipMemcpyAsync(ctx->af_h, q.af_pivot, sizeof(double) * (size_t)nprob, hipMemcpyDeviceToHost, st));
-                    HIPCHK(ctx, hipStreamSynchronize(st));
-                    for (uint32_t k = 0; k < nprob; k++) { const double v = ctx->af_h[k]; ctx->af_h[k] = (v <= 0.0) ? -1.0 : lnn_cholesky_pivot(v); }      /* lpc.c:418-421, host libm */
-                    HIPCHK(ctx, hipMemcpyAsync(q.af_pivot, ctx->af_h, sizeof(double) * (size_t)nprob, hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(k_af_column, dim3(nprob), dim3(128), 0, st, q, l, i);
-                }
-                hipLaunchKernelGGL(k_af_solve, dim3((nprob + 63) / 64), dim3(64), 0, st, q, l);
-            }
-            hipLaunchKernelGGL(k_af_finish, dim3(((uint32_t)Jq + 255) / 256), dim3(256), 0, st, q, l);
-            HIPCHK(ctx, hipGetLastError());
-            return LNN_OK;
-        };
-        /* the layers of one pass over the jobs of plan q (linne_network.c:582-602): lags, Levinson-Durbin, the unit-count search,
-         * [the auxiliary-function refinement of the chosen coefficients], the forward pass.  Returns LNN_*; cur_out = which half of
-         * `sig` holds the last layer's output */
-        uint32_t cur_final = 0;
-        auto run_layers = [&](const Plan &q, uint64_t Jq, bool spec_ok, const bool *hall, bool fcfg, bool fall, uint32_t af_iters, bool final_pass) -> int {
-            int ret = LNN_OK;
-            uint32_t cur = 0;
-        for (uint32_t l = 0; l < hs.L; l++) {
-            const uint32_t maxu = hs.P[l] < 128u ? hs.P[l] : 128u;
-            /* the first two layers nearly always keep one unit: their search pass also writes that trial's forward output */
-            const uint32_t fir_spec = (spec_ok && ctx->fir_spec && l + 1 < hs.L) ? 1u : 0u;
-            {
-                const bool hist_layer = q.hist && hs.P[l] >= 64u;
-                /* the general kernels serve what the lanes = jobs kernels do not take -- usually one ragged frame, a launch that is
-                 * all latency: it runs beside them on the side stream */
-                const bool beside = hist_layer && !hall[l] && ctx->has_side;
-                if (beside) {
-                    HIPCHK(ctx, hipEventRecord(ctx->fork_ev, st)); HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->fork_ev, 0));
-                    const int sp_ = span_begin(ctx, 3, ctx->side); dispatch_autocorr2(ctx->side, q, l, cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, ctx->side);
-                    HIPCHK(ctx, hipEventRecord(ctx->join_ev, ctx->side));
-                }
-                if (hist_layer) {                               /* long layer: lanes = jobs kernels for the frames they take (hist_takes) */
-                    for (int w = 0; w < 3; w++) {
-                        if (hs.P[l] == 64u && w == 1) continue;
-                        const int sp_ = span_begin(ctx, 21 + w, st); (void)launch_autocorr_hist(st, q, l, cur, w); span_end(ctx, sp_, st);
-                    }
-                }
-                if (beside) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join_ev, 0));
-                else if (!hall[l]) {
-                    const int sp_ = span_begin(ctx, (hs.P[l] >= 32u) ? 3 : 14, st); dispatch_autocorr2(st, q, l, cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, st);
-                }
-            }
-            { const int sp_ = span_begin(ctx, 4, st);
-              /* one launch per trial, every order on LDS columns -- except that the short trials whose columns fit beside the
-               * one-unit trial's ride along with it on a second wave (k_levinson_lds) */
-              uint32_t ride = LNN_MAXT;
-              if (Jq <= 64u && ctx->lev_wave) {       /* a handful of jobs: a wave per problem, all trials in one launch */
-                  hipLaunchKernelGGL(k_levinson_wave, dim3((uint32_t)Jq, 2u * maxu - 1u), dim3(64), 0, st, q, l);
-              } else {
-              for (uint32_t t = 1, u = 2; u <= maxu && ctx->lev_ride; u <<= 1, t++)
-                  if (LEV_LDS(hs.P[l]) + LEV_MAXRIDE * LEV_LDS(hs.P[l] / u) <= LEV_LDS_BUDGET) { ride = t; break; }
-              for (uint32_t t = 0, u = 1; u <= maxu && t < (ride < LNN_MAXT ? ride : LNN_MAXT); u <<= 1, t++) {
-                  const uint32_t np = hs.P[l] / u;
-                  const bool carry = (t == 0 && ride < LNN_MAXT);
-                  const size_t lds = LEV_LDS(np) + (carry ? LEV_MAXRIDE * LEV_LDS(hs.P[l] >> ride) : 0);
-                  hipLaunchKernelGGL(k_levinson_lds, dim3(((uint32_t)Jq + 63) / 64, u), dim3(carry ? 64 * (1 + LEV_MAXRIDE) : 64), lds, st, q, l, t, carry ? ride : (uint32_t)LNN_MAXT);
-              }
-              }
-              span_end(ctx, sp_, st); }
-            /* the last layer of a chunk k_last_layer takes: search, selection, forward pass and loss from one pass over the input */
-            const bool ll = last_layer_all && l + 1 == hs.L && fcfg && fall && !final_pass && spec_ok;
-            if (ll) {
-                { const int sp_ = span_begin(ctx, 20, st);
-                  const dim3 g(((uint32_t)Jq + 63) / 64), b(64);
-                  switch (hs.P[l]) {
-                  case 2: hipLaunchKernelGGL(k_last_layer<2>, g, b, 0, st, q, l, cur); break;
-                  case 4: hipLaunchKernelGGL(k_last_layer<4>, g, b, 0, st, q, l, cur); break;
-                  case 8: hipLaunchKernelGGL(k_last_layer<8>, g, b, 0, st, q, l, cur); break;
-                  default: hipLaunchKernelGGL(k_last_layer<16>, g, b, 0, st, q, l, cur); break;
-                  }
-                  span_end(ctx, sp_, st); }
-                { const int sp_ = span_begin(ctx, 7, st); hipLaunchKernelGGL(k_select, dim3(((uint32_t)Jq + 63) / 64), dim3(64), 0, st, q, l, 2u); span_end(ctx, sp_, st); }
-            } else {
-            {   /* unit-count search.  Short layers: the register-window kernel.  The long layer: k_search_long for the frames it takes
-                 * (search_long_takes), k_fir2<2> for the others (it returns at once for the jobs taken there) */
-                bool long_any = false, long_all = true;
-                for (uint32_t f = f0; f < f0 + Fc; f++) { const bool t_ = fir_spec && search_long_takes(q, l, ctx->sig_cls[ctx->cur_idx[f]]); long_any |= t_; long_all &= t_; }
-                if (long_any) {
-                    const int sp_ = span_begin(ctx, 25, st);
-                    const dim3 grid((uint32_t)Jq, (S + FIR_TILE - 1) / FIR_TILE), blk(FIR_THREADS);
-                    /* one block per job that walks its tiles (coefficients, bookkeeping and reductions once per job) where the jobs alone
-                     * are at least SEARCH_JOB_MIN; (jobs, tiles) blocks below that.  The one-pass kernel has the latter form only. */
-                    const bool per_job = ctx->search_two && (ctx->search_job < 0 ? Jq >= SEARCH_JOB_MIN : ctx->search_job != 0);
-                    const dim3 gjob((uint32_t)Jq, 1);
-                    ctx->last_search_form = per_job ? 1 : 0;
-                    if (per_job) { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, true, true>), gjob, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, true, true>), gjob, blk, 0, st, q, l, cur); }
-                    else if (ctx->search_two) { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, true, false>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, true, false>), grid, blk, 0, st, q, l, cur); }
-                    else { if (hs.P[l] == 128u) hipLaunchKernelGGL((k_search_long<128, false, false>), grid, blk, 0, st, q, l, cur); else hipLaunchKernelGGL((k_search_long<64, false, false>), grid, blk, 0, st, q, l, cur); }
-                    span_end(ctx, sp_, st);
-                }
-                if (!(long_any && long_all)) {
-                    const int sp_ = span_begin(ctx, (l == 0) ? 15 : (fir_spec ? 5 : 18), st);
-                    if (hs.P[l] <= 16u && ctx->fir_small) launch_fir_small_search(st, q, l, cur, (uint32_t)Jq, (S + FIR_TILE - 1) / FIR_TILE, fir_spec != 0, hs.P[l]);
-                    else if (long_any) {
-                        /* the frames k_search_long leaves -- usually the one ragged tail -- are runs of consecutive rows (the chunk is sorted by
-                         * class): a launch per run, not 620 k blocks of which all but a handful look up their job and go (0.7 ms) */
-                        const uint32_t rpf = (uint32_t)(Jq / Fc);
-                        for (uint32_t f = f0; f < f0 + Fc; ) {
-                            if (search_long_takes(q, l, ctx->sig_cls[ctx->cur_idx[f]])) { f++; continue; }
-                            uint32_t g = f + 1;
-                            while (g < f0 + Fc && !search_long_takes(q, l, ctx->sig_cls[ctx->cur_idx[g]])) g++;
-                            Plan qq = q; qq.job_off = (f - f0) * rpf;
-                            launch_fir<2>(st, qq, l, cur, (g - f) * rpf, (S + FIR_TILE - 1) / FIR_TILE, fir_spec != 0);
-                            f = g;
-                        }
-                    }
-                    else launch_fir<2>(st, q, l, cur, (uint32_t)Jq, (S + FIR_TILE - 1) / FIR_TILE, fir_spec != 0);
-                    span_end(ctx, sp_, st);
-                }
-            }
-            const bool sel_wave = Jq <= 256u && (uint64_t)((S + FIR_TILE - 1) / FIR_TILE) * (FIR_THREADS / 64) <= SELW_MAXPART;       /* a handful of jobs: a wave per job */
-            { const int sp_ = span_begin(ctx, 7, st);
-              if (sel_wave) hipLaunchKernelGGL(k_select_wave, dim3((uint32_t)Jq), dim3(64), 0, st, q, l, 0u);
-              else hipLaunchKernelGGL(k_select, dim3(((uint32_t)Jq + 63) / 64), dim3(64), 0, st, q, l, 0u);
-              span_end(ctx, sp_, st); }
-            /* exact ordered chains for the (rare) jobs the certified search flagged; everything else exits at once */
-            { const int sp_ = span_begin(ctx, 6, st); if (l == 0) hipLaunchKernelGGL((k_fir2<0, true, false>), dim3((uint32_t)Jq, 1), dim3(FIR_THREADS), 0, st, q, l, cur); else hipLaunchKernelGGL((k_fir2<0, false, false>), dim3((uint32_t)Jq, 1), dim3(FIR_THREADS), 0, st, q, l, cur);
-              if (sel_wave) hipLaunchKernelGGL(k_select_wave, dim3((uint32_t)Jq), dim3(64), 0, st, q, l, 1u);
-              else hipLaunchKernelGGL(k_select, dim3(((uint32_t)Jq + 63) / 64), dim3(64), 0, st, q, l, 1u);
-              span_end(ctx, sp_, st); }
-            /* the last layer's output is only ever summed: layers of <= 16 taps do the forward pass and the ordered loss in one
-             * kernel and write nothing else */
-            if (l + 1 == hs.L && fcfg && !final_pass) {
-                const int sp_ = span_begin(ctx, 20, st);
-                const dim3 g(((uint32_t)Jq + 63) / 64), b(64), b5(320);
-                /* fewer than 1024 waves of 64 jobs: each would be alone on its SIMD (1.4 ms per launch however few) -- five waves per 64 jobs then (k_fwd_loss_mw) */
-                if (Jq < 65536u && ctx->knob.fwd_loss_mw) switch (hs.P[l]) {
-                case 2: hipLaunchKernelGGL(k_fwd_loss_mw<2>, g, b5, 0, st, q, l, cur); break;
-                case 4: hipLaunchKernelGGL(k_fwd_loss_mw<4>, g, b5, 0, st, q, l, cur); break;
-                case 8: hipLaunchKernelGGL(k_fwd_loss_mw<8>, g, b5, 0, st, q, l, cur); break;
-                default: hipLaunchKernelGGL(k_fwd_loss_mw<16>, g, b5, 0, st, q, l, cur); break;
-                }
-                else switch (hs.P[l]) {
-                case 2: hipLaunchKernelGGL(k_fwd_loss<2>, g, b, 0, st, q, l, cur); break;
-                case 4: hipLaunchKernelGGL(k_fwd_loss<4>, g, b, 0, st, q, l, cur); break;
-                case 8: hipLaunchKernelGGL(k_fwd_loss<8>, g, b, 0, st, q, l, cur); break;
-                default: hipLaunchKernelGGL(k_fwd_loss<16>, g, b, 0, st, q, l, cur); break;
-                }
-                span_end(ctx, sp_, st);
-            }
-            }       /* (not k_last_layer's) */
-            if (af_iters && (ret = run_af(q, Jq, l, cur, af_iters)) != LNN_OK) return ret;
-            if (final_pass && l + 1 == hs.L) { cur ^= 1u; continue; }       /* the final pass needs no output of the last layer: only its parameters */
-            if (!(l + 1 == hs.L && fall)) { const int sp_ = span_begin(ctx, (l == 0) ? 16 : (fir_spec ? 8 : 19), st); launch_fir<1>(st, q, l, cur, (uint32_t)Jq, (S + FIR_TILE - 1) / FIR_TILE, fir_spec != 0); span_end(ctx, sp_, st); }
-            cur ^= 1u;
-        }
-            cur_final = cur;
-            return ret;
-        };
-        /* -l: LINNENetworkTrainer_Train on the parameters the analysis left (lnn_k_train.h); synchronous: the host reads after every
-         * step how many channel-frames go on */
-        auto run_train = [&](const Plan &q, const uint32_t *best) -> int {
-            tr.p = q; tr.best = best; tr.CF = (uint32_t)CF;
-            const uint32_t tiles = (S + TR_TILE - 1) / TR_TILE;
-            const int sp_ = span_begin(ctx, 27, st);
-            hipLaunchKernelGGL(k_tr_init, dim3(((uint32_t)CF + 255) / 256), dim3(256), 0, st, tr);
-            for (uint32_t it = 0; it < 2000u; it++) {                      /* LINNE_TRAINING_PARAMETER_MAX_NUM_ITRATION, linne_internal.h:29 */
-                HIPCHK(ctx, hipMemsetAsync(tr.nactive, 0, sizeof(uint32_t), st));
-                for (uint32_t l = 0; l < hs.L; l++) hipLaunchKernelGGL(k_tr_forward, dim3((uint32_t)CF, tiles), dim3(TR_THREADS), 0, st, tr, l);
-                hipLaunchKernelGGL(k_tr_loss, dim3((uint32_t)CF), dim3(64), 0, st, tr);                                   /* the loss and, in place, its gradient */
-                for (uint32_t l = hs.L - 1; l >= 1; l--) hipLaunchKernelGGL(k_tr_back, dim3((uint32_t)CF, tiles), dim3(TR_THREADS), 0, st, tr, l);
-                hipLaunchKernelGGL(k_tr_gradp, dim3((uint32_t)CF, hs.L), dim3(128), 0, st, tr);
-                hipLaunchKernelGGL(k_tr_update, dim3((uint32_t)CF), dim3(128), 0, st, tr, (double)0.8f, (double)0.1f, 1.0e-7);     /* linne_network.c:829, linne_internal.h:31-33 */
-                uint32_t left = 0;
-                HIPCHK(ctx, hipMemcpyAsync(&left, tr.nactive, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipStreamSynchronize(st));
-                if (left == 0) break;
-            }
-            span_end(ctx, sp_, st);
-            HIPCHK(ctx, hipGetLastError());
-            return LNN_OK;
-        };
-        const uint32_t af_iters = ctx->af_iters;
-        if ((ret = run_layers(p, J, true, hist_all, fuse_cfg, fuse_all, 0u, false)) != LNN_OK) return ret;
-        uint32_t cur = cur_final;
-        if (!fuse_all) { const int sp_ = span_begin(ctx, 9, st); if (J <= 1024u) hipLaunchKernelGGL(k_chain_sum_wave<1>, dim3((uint32_t)J), dim3(64), 0, st, p, 0u, cur);       /* few rows: a wave per row */
-            else hipLaunchKernelGGL(k_chain_sum<1>, dim3(((uint32_t)J + 63) / 64), dim3(SUM_THREADS), 0, st, p, 0u, cur);
-            span_end(ctx, sp_, st); }
-        if (af_iters == 0) {        /* the final pass of linne_network.c:628-629 repeats the winning pass bit for bit: skipped */
-            if (ctx->learning) {
-                hipLaunchKernelGGL(k_af_best, dim3(((uint32_t)CF + 255) / 256), dim3(256), 0, st, p, af_best, af_loss, af_reg);
-                if ((ret = run_train(p, af_best)) != LNN_OK) return ret;
-            }
-            const int sp_ = span_begin(ctx, 10, st); hipLaunchKernelGGL(k_quantize, dim3((uint32_t)CF), dim3(64), 0, st, p); hipLaunchKernelGGL(k_fir_cascade, dim3((uint32_t)CF, CF >= 1024u ? 1u : (S + FIN_TILE - 1) / FIN_TILE), dim3(FIN_THREADS), 0, st, p); span_end(ctx, sp_, st);
-        } else {
-            /* -a N: the final pass is real -- the winner's regulariser, the refinement after every layer's search, and therefore
-             * new inputs (and possibly new unit counts) for the layers behind it.  One job per channel-frame, general kernels. */
-            Plan q = p;
-            q.R = 1; q.J = (uint32_t)CF; q.regs[0] = 0.0;
-            q.hist = 0; q.fused_last = 0; q.search_long = 0;
-            q.capture = NULL;                                       /* the final pass does not search: it refines the winner */
-            build_runs(&q.runs[1], ctx->cur_idx + f0, Fc, C);
-            q.job_reg = af_reg; q.af_best = af_best; q.af_loss = af_loss;
-            hipLaunchKernelGGL(k_af_best, dim3(((uint32_t)CF + 255) / 256), dim3(256), 0, st, p, af_best, af_loss, af_reg);
-            const bool none[LNN_MAXL] = { false, false, false };
-            const int sp_ = span_begin(ctx, 26, st);
-            if ((ret = run_layers(q, CF, false, none, false, false, af_iters, true)) != LNN_OK) return ret;
-            span_end(ctx, sp_, st);
-            if (ctx->learning && (ret = run_train(q, NULL)) != LNN_OK) return ret;
-            { const int sp2_ = span_begin(ctx, 10, st); hipLaunchKernelGGL(k_quantize, dim3((uint32_t)CF), dim3(64), 0, st, q); hipLaunchKernelGGL(k_fir_cascade, dim3((uint32_t)CF, CF >= 1024u ? 1u : (S + FIN_TILE - 1) / FIN_TILE), dim3(FIN_THREADS), 0, st, q); span_end(ctx, sp2_, st); }
-        }
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return LNN_OK;
-    };
-    const int loop_ret = enqueue_chunks();
+    if (sp.use_sub || ctx->has_side) HIPCHK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (sp.use_sub) for (uint32_t i = 0; i < sp.nsub; i++) HIPCHK(ctx, hipStreamWaitEvent(ctx->sub[i], ctx->ev_start, 0));
+    /* statistics launch, loop over chunks */
+    if ((ret = launch_stats(ctx, e)) != LNN_OK) return ret;
+    const int loop_ret = enqueue_chunks(ctx, e);
+    /* join */
     if (loop_ret != LNN_OK) {       /* what was forked is waited for before the error goes back (the callers synchronise ctx->stream only) */
-        if (use_sub) for (uint32_t i = 0; i < nsub; i++) (void)hipStreamSynchronize(ctx->sub[i]);
+        if (sp.use_sub) for (uint32_t i = 0; i < sp.nsub; i++) (void)hipStreamSynchronize(ctx->sub[i]);
         if (ctx->has_side) (void)hipStreamSynchronize(ctx->side);
         return loop_ret;
     }
     if (ctx->has_side) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
-    if (use_sub) {
-        for (uint32_t i = 0; i < nsub; i++) { HIPCHK(ctx, hipEventRecord(ctx->sub_done[i], ctx->sub[i])); HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->sub_done[i], 0)); }
+    if (sp.use_sub) {
+        for (uint32_t i = 0; i < sp.nsub; i++) { HIPCHK(ctx, hipEventRecord(ctx->sub_done[i], ctx->sub[i])); HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->sub_done[i], 0)); }
     }
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     return LNN_OK;
@@ -1149,8 +1043,43 @@ static int params_in_range(LINNEAmdContext *ctx, const HostShape *hs, uint32_t C
     return LNN_OK;
 }
 
+/* dispatch helpers of the synthesis kernels */
+static void launch_synth_rows(hipStream_t st, const DecPlan &p, uint32_t l, const LnnDecLayer &d, uint32_t CF)
+{
+    const dim3 grows((CF + 3) / 4), grows8((CF + 7) / 8), b(64);
+    if (d.form == LNN_DL_ROWS8) switch (d.pb) {
+    case 4: hipLaunchKernelGGL((k_synth_rows8<4>), grows8, b, 0, st, p, l); break;
+    case 8: hipLaunchKernelGGL((k_synth_rows8<8>), grows8, b, 0, st, p, l); break;
+    default: hipLaunchKernelGGL((k_synth_rows8<16>), grows8, b, 0, st, p, l); break;
+    }
+    else switch (d.nch) {
+    case 0: if (d.pb == 4u) hipLaunchKernelGGL((k_synth_rows<0, 4>), grows, b, 0, st, p, l); else hipLaunchKernelGGL((k_synth_rows<0>), grows, b, 0, st, p, l); break;
+    case 1: hipLaunchKernelGGL((k_synth_rows<1>), grows, b, 0, st, p, l); break;
+    case 3: hipLaunchKernelGGL((k_synth_rows<3>), grows, b, 0, st, p, l); break;
+    default: hipLaunchKernelGGL((k_synth_rows<7>), grows, b, 0, st, p, l); break;
+    }
+}
+template <int PP> static void launch_synth_small_p(hipStream_t st, const DecPlan &p, uint32_t l, bool de, uint32_t CF)
+{
+    if (de) hipLaunchKernelGGL((k_synth_small<PP, true>), dim3((CF + 63) / 64), dim3(64), 0, st, p, l); else hipLaunchKernelGGL((k_synth_small<PP, false>), dim3((CF + 63) / 64), dim3(64), 0, st, p, l);
+}
+/* the lanes forms: short layers with lanes = channel-frames (and the de-emphasis on layer 0's pass), long ones a wave per 16 */
+static void launch_synth_lanes(hipStream_t st, const DecPlan &p, uint32_t l, const LnnDecLayer &d, uint32_t CF)
+{
+#define LNN_SS(PP_) launch_synth_small_p<PP_>(st, p, l, d.de, CF)
+    if (d.form == LNN_DL_SMALL) LNN_BY_ORDER(d.pb, LNN_SS);
+#undef LNN_SS
+    else if (d.form == LNN_DL_BIG) switch (d.pb) {
+    case 32:  hipLaunchKernelGGL((k_synth_big<32>), dim3((CF + 15) / 16), dim3(64), 0, st, p, l); break;
+    case 64:  hipLaunchKernelGGL((k_synth_big<64>), dim3((CF + 15) / 16), dim3(64), 0, st, p, l); break;
+    default: hipLaunchKernelGGL((k_synth_big<128>), dim3((CF + 15) / 16), dim3(64), 0, st, p, l); break;
+    }
+    else hipLaunchKernelGGL(k_synthesize, dim3(CF), dim3(64), 0, st, p, l, 0u);      /* not a preset size */
+}
+
 /* the synthesis of num_frames frames whose lengths are in device memory (d_nsmp): enqueued on the context's stream behind what is
- * there; records the call's end event when timing is on.  The caller has read the call's knobs and started its spans. */
+ * there; records the call's end event when timing is on.  The caller has read the call's knobs and started its spans.  Layers in
+ * reverse order (linne_decoder.c:503-509); which form each takes: lnn_decode_forms */
 static int decode_frames_dev(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape, const HostShape &hs,
         int32_t *d_data, const uint32_t *d_nsmp, uint32_t num_frames, const int32_t *d_params)
 {
@@ -1158,78 +1087,37 @@ static int decode_frames_dev(LINNEAmdContext *ctx, const struct LINNEAmdShape *s
     p.C = shape->num_channels; p.S = shape->num_samples_per_block; p.L = hs.L; p.ms = shape->ch_process_method; p.F = num_frames;
     for (uint32_t l = 0; l < hs.L; l++) { p.P[l] = hs.P[l]; p.coef_off[l] = hs.coef_off[l]; }
     p.data = d_data; p.prm = d_params; p.nsmp = d_nsmp;
-    bool ms_done = false;
-    {   /* layers in reverse order (linne_decoder.c:503-509): long layers one wave per channel-frame, short ones (order <= 16)
-         * with lanes = channel-frames; the de-emphasis rides on layer 0's pass */
-        const uint32_t CF = num_frames * p.C, gsmall = (CF + 63) / 64;
-        if (hs.P[0] > 16) { snprintf(ctx->err, sizeof(ctx->err), "internal: layer 0 of order %u", hs.P[0]); return LNN_NG; }
-        /* The lanes = channel-frames kernels have few, long-running waves: a pass over a short layer takes the time of one
-         * wave's 10240-step recurrence however small the batch.  Below a few thousand channel-frames the one-wave-per-
-         * channel-frame kernel (all layers and the de-emphasis in one launch) finishes sooner. */
-        /* LINNE_AMD_DECODE_KERNEL = "wave" / "lanes" / "pipe": for tests and measurements.  Small batches -- block-at-a-time calls
-         * above all -- take the pipelined latency form (k_synth_pipe: a wave per stage of the cascade, 16-sample blocks) when the
-         * frame fits its LDS image; k_synthesize is its fallback for longer frames */
-        const bool pipe_fits = SP_LDS_BYTES(p.S) <= LEV_LDS_BUDGET;
-        /* (tools/decode_crossover.py: the pipelined form costs 0.85 ms per 1024 channel-frames, the throughput form 1.25 ms up to ~4000 and
-         * 0.12 per 1024 beyond: they cross at 1536; the lanes form the throughput form falls back to, 5.1 ms whatever the batch: at 6144) */
-        const bool rows_fit = (p.S & 3u) == 0u && ((uintptr_t)d_data & 15u) == 0u;
-        const int form = ctx->knob.decode_kernel ? ctx->knob.decode_kernel : (CF < (rows_fit ? 1536u : 6144u) ? 3 : 0);
-        const bool use_pipe = (form == 3) && pipe_fits, use_wave = (form == 1) || (form == 3 && !pipe_fits);
-        /* timing kinds: 11 = k_synthesize (all layers in one launch), 30 = k_synth_big, 31 = k_synth_small, 32 = k_synth_pipe, 33 = k_synth_rows<NCH > 0> (a long layer), 36 = k_synth_rows<0> / k_synth_rows8 (a short layer), 34 = k_deemph_lr, 35 = k_synth_l0_de (layer 0 + de-emphasis + MS -> LR) */
-        if (use_pipe) { const int sp_ = span_begin(ctx, 32, ctx->stream); hipLaunchKernelGGL(k_synth_pipe, dim3(CF), dim3(64 * (hs.L + 1)), SP_LDS_BYTES(p.S), ctx->stream, p); span_end(ctx, sp_, ctx->stream); }
-        else if (use_wave) { const int sp_ = span_begin(ctx, 11, ctx->stream); hipLaunchKernelGGL(k_synthesize, dim3(CF), dim3(64), 0, ctx->stream, p, 0xFFFFFFFFu, 1u); span_end(ctx, sp_, ctx->stream); }
-        else for (int32_t l = (int32_t)hs.L - 1; l >= 0; l--) {
-            const bool de = (l == 0);
-            /* k_synth_rows (four channel-frames per wave, the old taps on the matrix unit) takes the layers without de-emphasis whose
-             * order is a preset's, when the samples can travel as 16-byte groups (LINNE_AMD_DECODE_KERNEL=lanes: none) */
-            const int nch = hs.P[l] <= 16u ? 0 : (hs.P[l] == 32u ? 1 : (hs.P[l] == 64u ? 3 : (hs.P[l] == 128u ? 7 : -1)));
-            if (de && nch == 0 && form != 2 && rows_fit && hs.P[l] <= 4u && ctx->knob.decode_fused) {
-                /* the end of the cascade in ONE launch: layer 0, the de-emphasis and MS -> LR on tiles in LDS (lnn_k_decode_fused.h) */
-                const int sp_ = span_begin(ctx, 35, ctx->stream);
-                if (p.ms && p.C >= 2u && p.C <= 64u && (p.C & (p.C - 1u)) == 0u) { hipLaunchKernelGGL((k_synth_l0_de<true>), dim3(gsmall), dim3(64 * SF_WAVES), 0, ctx->stream, p); ms_done = true; }
-                else hipLaunchKernelGGL((k_synth_l0_de<false>), dim3(gsmall), dim3(64 * SF_WAVES), 0, ctx->stream, p);
-                span_end(ctx, sp_, ctx->stream);
-                continue;
+    hipStream_t st = ctx->stream;
+    const uint32_t CF = num_frames * p.C, gsmall = (CF + 63) / 64;
+    if (hs.P[0] > 16) { snprintf(ctx->err, sizeof(ctx->err), "internal: layer 0 of order %u", hs.P[0]); return LNN_NG; }
+    LnnDecodeForms df;
+    lnn_decode_forms(&hs, p.C, p.S, p.ms, num_frames, ((uintptr_t)d_data & 15u) == 0u, SP_LDS_BYTES(p.S) <= LEV_LDS_BUDGET, &ctx->knob, &df);
+    if (df.call == LNN_DEC_PIPE) { const int sp_ = span_begin(ctx, LINNE_AMD_T_SYNTH_PIPE, st); hipLaunchKernelGGL(k_synth_pipe, dim3(CF), dim3(64 * (hs.L + 1)), SP_LDS_BYTES(p.S), st, p); span_end(ctx, sp_, st); }
+    else if (df.call == LNN_DEC_WAVE) { const int sp_ = span_begin(ctx, LINNE_AMD_T_SYNTH, st); hipLaunchKernelGGL(k_synthesize, dim3(CF), dim3(64), 0, st, p, 0xFFFFFFFFu, 1u); span_end(ctx, sp_, st); }
+    else for (int32_t li = (int32_t)hs.L - 1; li >= 0; li--) {
+        const uint32_t l = (uint32_t)li;
+        const LnnDecLayer &d = df.layer[l];
+        if (d.form == LNN_DL_FUSED_L0) {
+            const int sp_ = span_begin(ctx, LINNE_AMD_T_SYNTH_L0_DE, st);
+            if (d.ms_fold) hipLaunchKernelGGL((k_synth_l0_de<true>), dim3(gsmall), dim3(64 * SF_WAVES), 0, st, p); else hipLaunchKernelGGL((k_synth_l0_de<false>), dim3(gsmall), dim3(64 * SF_WAVES), 0, st, p);
+            span_end(ctx, sp_, st);
+        } else if (d.form == LNN_DL_ROWS || d.form == LNN_DL_ROWS8) {
+            const int sp_ = span_begin(ctx, d.nch > 0 ? LINNE_AMD_T_SYNTH_ROWS : LINNE_AMD_T_SYNTH_ROWS_SHORT, st);
+            launch_synth_rows(st, p, l, d, CF);
+            span_end(ctx, sp_, st);
+            if (d.de) {
+                const int sd_ = span_begin(ctx, LINNE_AMD_T_DEEMPH_LR, st);
+                if (d.ms_fold) hipLaunchKernelGGL((k_deemph_lr<true>), dim3(gsmall), dim3(64 * (2 + DL_STORERS)), 0, st, p); else hipLaunchKernelGGL((k_deemph_lr<false>), dim3(gsmall), dim3(64 * (2 + DL_STORERS)), 0, st, p);
+                span_end(ctx, sd_, st);
             }
-            if (nch >= 0 && form != 2 && rows_fit) {
-                const int sp_ = span_begin(ctx, nch > 0 ? 33 : 36, ctx->stream);
-                const dim3 grows((CF + 3) / 4);
-                switch (nch) {
-                case 0:     /* (LINNE_AMD_DECODE_ROWS8=0 / 1: the four- / eight-channel-frame form whatever the batch) */
-                        if (!(ctx->knob.rows8 < 0 ? CF >= 20480u : ctx->knob.rows8 != 0)) {     /* (eight per wave are twice the blocks per wave: they pay once the four-per-wave form fills the SIMDs, tools/decode_crossover.py) */ if (hs.P[l] <= 4u) hipLaunchKernelGGL((k_synth_rows<0, 4>), grows, dim3(64), 0, ctx->stream, p, (uint32_t)l); else hipLaunchKernelGGL((k_synth_rows<0>), grows, dim3(64), 0, ctx->stream, p, (uint32_t)l); }
-                        else if (hs.P[l] <= 4u) hipLaunchKernelGGL((k_synth_rows8<4>), dim3((CF + 7) / 8), dim3(64), 0, ctx->stream, p, (uint32_t)l);
-                        else if (hs.P[l] <= 8u) hipLaunchKernelGGL((k_synth_rows8<8>), dim3((CF + 7) / 8), dim3(64), 0, ctx->stream, p, (uint32_t)l);
-                        else hipLaunchKernelGGL((k_synth_rows8<16>), dim3((CF + 7) / 8), dim3(64), 0, ctx->stream, p, (uint32_t)l);
-                        break;
-                case 1: hipLaunchKernelGGL((k_synth_rows<1>), grows, dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-                case 3: hipLaunchKernelGGL((k_synth_rows<3>), grows, dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-                default: hipLaunchKernelGGL((k_synth_rows<7>), grows, dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-                }
-                span_end(ctx, sp_, ctx->stream);
-                if (de) {       /* the de-emphasis behind layer 0 (lanes = channel-frames), MS -> LR on its way out when a block of 64 rows holds whole frames */
-                    const int sd_ = span_begin(ctx, 34, ctx->stream);
-                    if (p.ms && p.C >= 2u && p.C <= 64u && (p.C & (p.C - 1u)) == 0u) { hipLaunchKernelGGL((k_deemph_lr<true>), dim3(gsmall), dim3(64 * (2 + DL_STORERS)), 0, ctx->stream, p); ms_done = true; }
-                    else hipLaunchKernelGGL((k_deemph_lr<false>), dim3(gsmall), dim3(64 * (2 + DL_STORERS)), 0, ctx->stream, p);
-                    span_end(ctx, sd_, ctx->stream);
-                }
-                continue;
-            }
-            const int sp_ = span_begin(ctx, hs.P[l] <= 16u ? 31 : (hs.P[l] <= 128u && (hs.P[l] & (hs.P[l] - 1u)) == 0 ? 30 : 11), ctx->stream);
-            switch (hs.P[l]) {
-            case 2:  if (de) hipLaunchKernelGGL((k_synth_small<2, true>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); else hipLaunchKernelGGL((k_synth_small<2, false>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 4:  if (de) hipLaunchKernelGGL((k_synth_small<4, true>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); else hipLaunchKernelGGL((k_synth_small<4, false>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 8:  if (de) hipLaunchKernelGGL((k_synth_small<8, true>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); else hipLaunchKernelGGL((k_synth_small<8, false>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 16: if (de) hipLaunchKernelGGL((k_synth_small<16, true>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); else hipLaunchKernelGGL((k_synth_small<16, false>), dim3(gsmall), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 32:  hipLaunchKernelGGL((k_synth_big<32>), dim3((CF + 15) / 16), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 64:  hipLaunchKernelGGL((k_synth_big<64>), dim3((CF + 15) / 16), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            case 128: hipLaunchKernelGGL((k_synth_big<128>), dim3((CF + 15) / 16), dim3(64), 0, ctx->stream, p, (uint32_t)l); break;
-            default: hipLaunchKernelGGL(k_synthesize, dim3(CF), dim3(64), 0, ctx->stream, p, (uint32_t)l, 0u); break;      /* not a preset size */
-            }
-            span_end(ctx, sp_, ctx->stream);
+        } else {
+            const int sp_ = span_begin(ctx, d.form == LNN_DL_SMALL ? LINNE_AMD_T_SYNTH_SMALL : (d.form == LNN_DL_BIG ? LINNE_AMD_T_SYNTH_BIG : LINNE_AMD_T_SYNTH), st);
+            launch_synth_lanes(st, p, l, d, CF);
+            span_end(ctx, sp_, st);
         }
     }
-    if (p.ms && !ms_done)
-        { const int sp_ = span_begin(ctx, 12, ctx->stream); hipLaunchKernelGGL(k_ms_to_lr, dim3(num_frames, (p.S + 255) / 256), dim3(256), 0, ctx->stream, p); span_end(ctx, sp_, ctx->stream); }
+    if (df.ms_separate)
+        { const int sp_ = span_begin(ctx, LINNE_AMD_T_MS_TO_LR, st); hipLaunchKernelGGL(k_ms_to_lr, dim3(num_frames, (p.S + 255) / 256), dim3(256), 0, st, p); span_end(ctx, sp_, st); }
     HIPCHK(ctx, hipGetLastError());
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     return LNN_OK;
@@ -1246,7 +1134,7 @@ extern "C" int LINNEAmd_DecodeFramesDevice(struct LINNEAmdContext *ctx, const st
     int ret = shape_info(shape, &hs);
     if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid shape"); return ret; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    read_call_knobs(ctx);
+    lnn_knobs_read_call(&ctx->knob);
     if ((ret = upload_lengths(ctx, shape, h_num_samples, num_frames)) != LNN_OK) return ret;
     ctx->nspans = 0;
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream)); }
@@ -1384,7 +1272,7 @@ extern "C" int LINNEAmd_RicePlanDevice(struct LINNEAmdContext *ctx, const struct
         if (cnt > lim) cnt = lim;
         RicePlanArgs b = a;
         b.resid = d_residual + c0 * a.S; b.plan = d_plan + c0 * LINNE_AMD_RICE_PLAN_BYTES; b.nsmp = ctx->d_plan_nsmp + c0 / a.C;
-        const int sp_ = span_begin(ctx, 17, ctx->stream);
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_PLAN, ctx->stream);
         if (b.S <= REMIT_LDS_SAMPLES) hipLaunchKernelGGL(k_rice_plan<true>, dim3((uint32_t)cnt), dim3(RICE_THREADS), sizeof(uint32_t) * (b.S + 1025u), ctx->stream, b);
         else hipLaunchKernelGGL(k_rice_plan<false>, dim3((uint32_t)cnt), dim3(RICE_THREADS), 0, ctx->stream, b);
         span_end(ctx, sp_, ctx->stream);
@@ -1412,7 +1300,7 @@ extern "C" int LINNEAmd_RiceEmitDevice(struct LINNEAmdContext *ctx, const struct
     a.packed_cap = packed_capacity & ~(uint64_t)15; a.C = shape->num_channels; a.S = shape->num_samples_per_block; a.CF = (uint32_t)CF;
     a.cap_bytes = shape->num_samples_per_block * 4u;
     { const char *e_ = getenv("LINNE_AMD_RICE_EMIT_CAP"); if (e_) a.cap_bytes = (uint32_t)atol(e_); }      /* test knob: forces the host fallback */
-    { const int sp_ = span_begin(ctx, 24, ctx->stream);
+    { const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_EMIT, ctx->stream);
       hipLaunchKernelGGL(k_rice_scan, dim3(1), dim3(RSCAN_THREADS), 0, ctx->stream, a);
       if (a.S <= REMIT_LDS_SAMPLES) hipLaunchKernelGGL(k_rice_emit<true>, dim3((uint32_t)CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (a.S + REMIT_THREADS + 1u), ctx->stream, a);
       else hipLaunchKernelGGL(k_rice_emit<false>, dim3((uint32_t)CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
@@ -1439,7 +1327,7 @@ extern "C" int LINNEAmd_RiceDecodeDevice(struct LINNEAmdContext *ctx, const stru
     RiceDecodeArgs a; memset(&a, 0, sizeof(a));
     a.words = (const uint32_t *)d_stream; a.nbytes = stream_bytes; a.bitpos = d_bitpos; a.nsmp = ctx->d_nsmp; a.resid = d_residual; a.endbit = d_endbit;
     a.F = num_frames; a.C = shape->num_channels; a.S = shape->num_samples_per_block;
-    const int sp_ = span_begin(ctx, 28, ctx->stream);
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_DECODE, ctx->stream);
     hipLaunchKernelGGL(k_rice_decode, dim3((num_frames + RDEC_THREADS - 1) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, a);
     span_end(ctx, sp_, ctx->stream);
     HIPCHK(ctx, hipGetLastError());
@@ -1753,7 +1641,7 @@ extern "C" int LINNEAmd_SlotDecodeStreamSubmit(struct LINNEAmdSlot *s, uint64_t 
         a.words = (const uint32_t *)s->d_stream; a.nbytes = stream_bytes; a.bitpos = s->d_bitpos; a.nsmp = (const uint32_t *)(s->d_bitpos + 2 * (size_t)s->max_frames); a.bitend = s->d_bitpos + s->max_frames;
         a.resid = s->d_data; a.endbit = s->d_endbit; a.F = num_frames; a.C = s->shape.num_channels; a.S = s->shape.num_samples_per_block;
         if (rst != cin) { HIPCHK(ctx, hipEventRecord(s->ev_in, cin)); HIPCHK(ctx, hipStreamWaitEvent(rst, s->ev_in, 0)); }
-        const int sp_ = span_begin(ctx, 28, rst);
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_DECODE, rst);
         hipLaunchKernelGGL(k_rice_decode, dim3((num_frames + RDEC_THREADS - 1) / RDEC_THREADS), dim3(RDEC_THREADS), 0, rst, a);
         span_end(ctx, sp_, rst);
     }
@@ -1889,13 +1777,13 @@ static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t 
         uint32_t *counts; uint64_t *cofs;
         SX_TRY(sx_temp(ctx, tmp, (void **)&counts, sizeof(uint32_t) * nw));
         SX_TRY(sx_temp(ctx, tmp, (void **)&cofs, sizeof(uint64_t) * (nw + 1u)));
-        SX_LAUNCH(37, k_sx_count, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, counts);
-        SX_LAUNCH(39, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nw, cofs);
+        SX_LAUNCH(LINNE_AMD_T_SX_COUNT, k_sx_count, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, counts);
+        SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nw, cofs);
         SX_TRY(sx_fetch(ctx, &M, cofs + nw, sizeof(M)));
         if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
         if (M) {
             SX_TRY(sx_temp(ctx, tmp, (void **)&cand, sizeof(uint64_t) * M));
-            SX_LAUNCH(38, k_sx_write, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, (const uint64_t *)cofs, cand);
+            SX_LAUNCH(LINNE_AMD_T_SX_WRITE, k_sx_write, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, (const uint64_t *)cofs, cand);
         }
     }
     uint64_t head = 0, nchain = 0;
@@ -1906,12 +1794,12 @@ static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t 
         const uint32_t M32 = (uint32_t)M, g = (uint32_t)((M + 1u + 255u) / 256u);
         while ((1ull << K) <= M) K++;
         SX_TRY(sx_temp(ctx, tmp, (void **)&jump, sizeof(uint32_t) * (uint64_t)K * (M + 1u)));
-        SX_LAUNCH(40, k_sx_succ, dim3(g), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, M32, jump);
+        SX_LAUNCH(LINNE_AMD_T_SX_SUCC, k_sx_succ, dim3(g), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, M32, jump);
         for (uint32_t k = 1; k < K; k++)
-            SX_LAUNCH(41, k_sx_jump, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
+            SX_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
         uint64_t *d_len;
         SX_TRY(sx_temp(ctx, tmp, (void **)&d_len, sizeof(uint64_t)));
-        SX_LAUNCH(42, k_sx_chain_len, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t *)jump, K, M32, d_len);
+        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN_LEN, k_sx_chain_len, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t *)jump, K, M32, d_len);
         SX_TRY(sx_fetch(ctx, &nchain, d_len, sizeof(nchain)));
         nchain++;
     }
@@ -1928,9 +1816,9 @@ static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t 
     if (!x->h_off || !x->h_first || !x->h_size || !x->h_type || !x->h_nsmp) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
     x->h_first[0] = 0;
     if (nchain) {
-        SX_LAUNCH(43, k_sx_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, (const uint32_t *)jump, K, (uint32_t)M,
+        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_sx_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, (const uint32_t *)jump, K, (uint32_t)M,
                 (uint32_t)nchain, x->d_off, x->d_size, x->d_type, x->d_nsmp);
-        SX_LAUNCH(39, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)x->d_nsmp, nchain, x->d_first);
+        SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)x->d_nsmp, nchain, x->d_first);
         HIPCHK(ctx, hipMemcpyAsync(x->h_off, x->d_off, sizeof(uint64_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(x->h_size, x->d_size, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(x->h_type, x->d_type, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
@@ -1948,7 +1836,7 @@ static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t 
         a.b = b; a.N = N; a.off = x->d_off; a.first = x->d_first; a.size = x->d_size; a.type = x->d_type; a.nsmp = x->d_nsmp;
         a.nb = (uint32_t)nb; a.C = x->shape.num_channels; a.S = x->shape.num_samples_per_block; a.bits = x->shape.bits_per_sample; a.num_samples = ns;
         a.tab = x->d_tab; a.status = x->d_status;
-        SX_LAUNCH(44, k_sx_check, dim3((uint32_t)((nb + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
+        SX_LAUNCH(LINNE_AMD_T_SX_CHECK, k_sx_check, dim3((uint32_t)((nb + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
         int32_t *st = (int32_t *)malloc(sizeof(int32_t) * nb);
         if (!st) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
         const int r = sx_fetch(ctx, st, x->d_status, sizeof(int32_t) * nb);
@@ -2053,7 +1941,7 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     HostShape hs;
     SX_TRY(shape_info(&x->shape, &hs));
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    read_call_knobs(ctx);
+    lnn_knobs_read_call(&ctx->knob);
     const uint64_t r0 = (lo < x->covered) ? sx_block_of(x, lo) : x->nb;
     const uint64_t nr = (r0 < x->nb) ? ((r1 < x->nb ? r1 : x->nb - 1u) - r0 + 1u) : 0u;
     /* the range's COMPRESS blocks, compacted */
@@ -2101,13 +1989,13 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
         pa.ncomp = ncomp; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
         for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
         pa.seg_first = seg_first; pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
-        SX_LAUNCH(45, k_sx_params, dim3((ncomp + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
+        SX_LAUNCH(LINNE_AMD_T_SX_PARAMS, k_sx_params, dim3((ncomp + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
         RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
         ra.words = (const uint32_t *)d_seg; ra.nbytes = seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
         ra.resid = d_data; ra.endbit = d_eb; ra.F = ncomp; ra.C = C; ra.S = S;
-        SX_LAUNCH(28, k_rice_decode, dim3((ncomp + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
+        SX_LAUNCH(LINNE_AMD_T_RICE_DECODE, k_rice_decode, dim3((ncomp + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
         HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
-        SX_LAUNCH(46, k_sx_rice_check, dim3((ncomp + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, (const uint32_t *)d_comp, (const uint64_t *)x->d_off,
+        SX_LAUNCH(LINNE_AMD_T_SX_RICE_CHECK, k_sx_rice_check, dim3((ncomp + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, (const uint32_t *)d_comp, (const uint64_t *)x->d_off,
                 (const uint32_t *)x->d_size, ncomp, seg_first, d_fail);
         SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, ncomp, d_prm));
         uint32_t fail = 0;
@@ -2123,7 +2011,7 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     la.r0 = (uint32_t)r0; la.nr = (uint32_t)nr; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
     la.lo = lo; la.hi = hi; la.covered = x->covered; la.out = d_pcm; la.stride = pcm_stride;
     la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
-    SX_LAUNCH(47, k_sx_place, dim3((uint32_t)((nr + 1u) * la.xch)), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+    SX_LAUNCH(LINNE_AMD_T_SX_PLACE, k_sx_place, dim3((uint32_t)((nr + 1u) * la.xch)), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return LNN_OK;
@@ -2206,7 +2094,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     if (!nlive) return LNN_OK;
     if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: %llu blocks in one call: too many", (unsigned long long)total_rec); return LNN_NG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    read_call_knobs(ctx);
+    lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory: fail words | window records | block records | the passes' COMPRESS records */
     const uint64_t o_fail = 0, o_win = align_up(sizeof(uint32_t) * (uint64_t)W), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
             o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
@@ -2305,17 +2193,17 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         int32_t *d_prm = (int32_t *)(sd + sc.o_prm), *d_data = (int32_t *)(sd + sc.o_data);
         uint8_t *d_seg = sd + sc.o_seg;
         if (p.nc) {
-            SX_LAUNCH(56, k_wx_gather, dim3(p.nc), dim3(WX_GATHER_THREADS), 0, ctx->stream, d_rec, d_crec, p.nc, d_seg);
+            SX_LAUNCH(LINNE_AMD_T_WX_GATHER, k_wx_gather, dim3(p.nc), dim3(WX_GATHER_THREADS), 0, ctx->stream, d_rec, d_crec, p.nc, d_seg);
             WxParamArgs pa; memset(&pa, 0, sizeof(pa));
             pa.recs = d_rec; pa.crec = d_crec; pa.ncomp = p.nc; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
             for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
             pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
-            SX_LAUNCH(57, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
+            SX_LAUNCH(LINNE_AMD_T_WX_PARAMS, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
             RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
             ra.words = (const uint32_t *)d_seg; ra.nbytes = p.seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
             ra.resid = d_data; ra.endbit = d_eb; ra.F = p.nc; ra.C = C; ra.S = S;
-            SX_LAUNCH(28, k_rice_decode, dim3((p.nc + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
-            SX_LAUNCH(58, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
+            SX_LAUNCH(LINNE_AMD_T_RICE_DECODE, k_rice_decode, dim3((p.nc + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
+            SX_LAUNCH(LINNE_AMD_T_WX_RICE_CHECK, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
             if (!p.check_only) SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, p.nc, d_prm));
         }
         if (p.check_only) continue;
@@ -2323,7 +2211,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         la.recs = d_rec; la.nrec = p.nrec; la.wins = d_win; la.fail = d_fail; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
         if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: a pass of %u blocks: give group_frames", p.nrec); return LNN_NG; }
-        SX_LAUNCH(59, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+        SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
     /* 5. the fail words, with the call's one wait */
     HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, sizeof(uint32_t) * (uint64_t)W, hipMemcpyDeviceToHost, ctx->stream));
@@ -2471,14 +2359,14 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         {
             SeGatherArgs g; g.pcm = d_pcm; g.stride = pcm_stride; g.first = f0 * S; g.total = N; g.frames = d_frames; g.nonzero = d_nz;
             g.F = Fp; g.C = C; g.S = S;
-            SX_LAUNCH(48, k_se_gather, dim3(Fp * C), dim3(SE_THREADS), 0, ctx->stream, g);
+            SX_LAUNCH(LINNE_AMD_T_SE_GATHER, k_se_gather, dim3(Fp * C), dim3(SE_THREADS), 0, ctx->stream, g);
         }
         /* 2. analysis and Rice plan, unchanged */
         SX_TRY(LINNEAmd_EncodeFramesDevice(ctx, &shape, d_frames, h.nsmp, Fp, d_resid, d_prm, d_st));
         SX_TRY(LINNEAmd_RicePlanDevice(ctx, &shape, d_resid, h.nsmp, Fp, d_plan));
         const uint32_t *d_nsmp = ctx->d_plan_nsmp;                 /* (RicePlanDevice's copy of this pass's lengths) */
         const uint32_t CF = Fp * C;
-        SX_LAUNCH(49, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
+        SX_LAUNCH(LINNE_AMD_T_SE_COMPACT, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
         /* 3. the host step: block types in stream order (quirk Q2, host libm), the plans the device could not settle */
         HIPCHK(ctx, hipMemcpyAsync(h.cmp, d_cmp, sizeof(uint2) * CF, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(h.st, d_st, sizeof(double) * LINNE_AMD_STAT_WORDS * CF, hipMemcpyDeviceToHost, ctx->stream));
@@ -2522,8 +2410,8 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.out = d_out; a.base = pos;
         a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
         HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
-        SX_LAUNCH(50, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
-        SX_LAUNCH(51, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
+        SX_LAUNCH(LINNE_AMD_T_SE_SIZE, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
         uint64_t pass_bytes = 0;
         uint32_t fail = 0;
         HIPCHK(ctx, hipMemcpyAsync(&fail, d_fail, sizeof(fail), hipMemcpyDeviceToHost, ctx->stream));
@@ -2541,11 +2429,11 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         if (writing && pos + pass_bytes > room) writing = false;
         if (writing) {
             HIPCHK(ctx, hipMemsetAsync(d_out + pos, 0, pass_bytes, ctx->stream));
-            SX_LAUNCH(52, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
-            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(53, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
-            else SX_LAUNCH(53, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
-            SX_LAUNCH(54, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
-            SX_LAUNCH(55, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SE_PARAMS, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SE_RICE, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(LINNE_AMD_T_SE_RICE, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SE_RAW, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(LINNE_AMD_T_SE_CRC, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
         }
         pos += pass_bytes;
     }
@@ -2599,4 +2487,100 @@ extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
     return ret;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * test infrastructure (like lnn_preset_info: exported, not in include/): what the rules of lnn_forms.h say for a call, without a GPU
+ * ---------------------------------------------------------------------------------------------- */
+#define LNN_Q_HEADER 48         /* words of the call record */
+#define LNN_Q_CHUNK 16          /* words of a chunk record; LNN_Q_LAYER words per layer follow it */
+#define LNN_Q_LAYER 24
+/* mode 0: an encode call -- class bookkeeping, split and the forms of every chunk, as a fresh context would decide them with the
+ * knobs of the environment.  ctx_streams: the compute sub-streams of the context (-1: what LINNE_AMD_STREAMS makes it create);
+ * arena_bytes 0: the default arena.  out: the call record (layout: tests/test_forms_cpu.py CALL_FIELDS), then per chunk a chunk
+ * record and hs.L layer records (CHUNK_FIELDS, LAYER_FIELDS); with -a N a second such group per chunk, the final pass's.
+ * mode 1: a decode call of num_frames frames (data_aligned: the samples lie 16-byte aligned): out = call form, ms_separate, then per
+ * layer form, nch, pb, de, ms_fold.  Returns the words written, -1 on a bad argument or too small a buffer. */
+extern "C" int64_t lnn_forms_query(int mode, const struct LINNEAmdShape *shape, const uint32_t *num_samples, uint32_t num_frames,
+        uint64_t arena_bytes, int ctx_streams, int has_side, uint32_t af_iters, uint32_t learning, int data_aligned, int64_t *out, uint64_t cap)
+{
+    HostShape hs;
+    if (!out || num_frames == 0 || shape_info(shape, &hs) != LNN_OK) return -1;
+    LnnKnobs knob; memset(&knob, 0, sizeof(knob));
+    lnn_knobs_read_context(&knob); lnn_knobs_read_call(&knob);
+    const uint32_t C = shape->num_channels, S = shape->num_samples_per_block;
+    uint64_t n = 0;
+    uint32_t *meta = NULL; LnnClassTable *tab = NULL;
+#define PUT(v) do { if (n >= cap) { free(meta); free(tab); return -1; } out[n++] = (int64_t)(v); } while (0)
+    if (mode == 1) {
+        LnnDecodeForms df;
+        lnn_decode_forms(&hs, C, S, shape->ch_process_method, num_frames, data_aligned != 0, SP_LDS_BYTES(S) <= LEV_LDS_BUDGET, &knob, &df);
+        PUT(df.call); PUT(df.ms_separate);
+        for (uint32_t l = 0; l < hs.L; l++) { const LnnDecLayer &d = df.layer[l]; PUT(d.form); PUT(d.nch); PUT(d.pb); PUT(d.de); PUT(d.ms_fold); }
+        return (int64_t)n;
+    }
+    int forced = 0;
+    if (ctx_streams < 0) ctx_streams = lnn_context_streams(&forced);
+    meta = (uint32_t *)malloc(sizeof(uint32_t) * 3 * (size_t)num_frames);
+    tab = (LnnClassTable *)calloc(1, sizeof(LnnClassTable));
+    LnnCallClasses cc;
+    if (!meta || !tab || lnn_call_classes(tab, shape, &hs, &knob, num_samples, num_frames, meta, meta + num_frames, meta + 2 * (size_t)num_frames, &cc) != LNN_CLS_OK) { free(meta); free(tab); return -1; }
+    const uint64_t per_frame = frame_scratch_bytes(shape, &hs, af_iters, learning);
+    if (arena_bytes == 0) arena_bytes = 6ull << 30;
+    if (arena_bytes < per_frame * 4 + 65536) arena_bytes = per_frame * 4 + 65536;
+    const LnnSplit sp = lnn_call_split(arena_bytes, per_frame, num_frames, C, hs.R, ctx_streams, forced != 0, &knob);
+    PUT(cc.branch); PUT(cc.nlen); PUT(cc.na_max); PUT(cc.prod_ok); PUT(sp.nsub); PUT(sp.use_sub); PUT(sp.chunk); PUT(sp.part_bytes);
+    PUT((num_frames + sp.chunk - 1) / sp.chunk); PUT(lnn_stats_rows_form(&knob, num_frames, C, S, hs.P[0])); PUT(per_frame); PUT(hs.L);
+    PUT(sp.streams_forced); PUT(0); PUT(0); PUT(0);
+    for (uint32_t i = 0; i < LNN_MAXCLS; i++) PUT(i < cc.nlen ? cc.lens[i] : 0);
+    for (uint32_t i = 0; i < LNN_MAXCLS; i++) PUT(i < cc.nlen ? cc.slot_of[i] : 0);
+    for (uint32_t f0 = 0; f0 < num_frames; f0 += (uint32_t)sp.chunk) {
+        const uint32_t Fc = (num_frames - f0 < sp.chunk) ? (num_frames - f0) : (uint32_t)sp.chunk;
+        for (int fin = 0; fin < (af_iters ? 2 : 1); fin++) {
+            const LnnChunkIn in = { &hs, C, S, Fc, tab->cls, meta + f0, &knob, sp.use_sub, has_side != 0, af_iters, learning, fin != 0 };
+            LnnChunkForms cf;
+            lnn_chunk_forms(&in, &cf);
+            RowRuns rr; lnn_build_runs(&rr, meta + f0, Fc, C * hs.R);
+            PUT(f0); PUT(Fc); PUT((uint64_t)Fc * C * (fin ? 1u : hs.R)); PUT(fin); PUT(cf.fwd_loss_on); PUT(cf.fuse_cfg); PUT(cf.fuse_all); PUT(cf.last_layer_all);
+            PUT(cf.prep_defer); PUT(cf.hist); PUT(cf.chain_sum); PUT(cf.chain_sum_wave); PUT(cf.cascade_walk); PUT(rr.mixed); PUT(rr.n); PUT(cf.present);
+            for (uint32_t l = 0; l < hs.L; l++) {
+                const LnnLayerForms &lf = cf.layer[l];
+                uint32_t nleft = 0, left_first = 0, left_frames = 0;
+                if (lf.long_any && !lf.long_all && !lf.fir_small)
+                    for (uint32_t f = 0, g = 0; lnn_next_left_run(&lf, meta + f0, Fc, g, &f, &g); nleft++) { if (!nleft) left_first = f; left_frames += g - f; }
+                PUT(lf.fir_spec); PUT(lf.hist_layer); PUT(lf.hist_all); PUT(lf.beside); PUT(lf.lev_wave); PUT(lf.nlev); PUT(lf.nlev ? lf.lev[0].ride : 0); PUT(lf.last_layer);
+                PUT(lf.long_any); PUT(lf.long_all); PUT(lf.search_form); PUT(lf.fir_small); PUT(lf.sel_wave); PUT(lf.fwd_loss); PUT(lf.fwd_loss_mw); PUT(lf.forward);
+                PUT(lf.forward_walk); PUT(nleft); PUT(left_first); PUT(left_frames); PUT(lf.long_mask); PUT(0); PUT(0); PUT(0);
+            }
+        }
+    }
+    free(meta); free(tab);
+    return (int64_t)n;
+#undef PUT
+}
+
+/* the class bookkeeping of a LIST of encode calls on one context: call i has shape shapes[i] and the counts[i] next lengths of
+ * `lengths`.  out: per call 2 + LNN_MAXCLS words -- the branch taken (LNN_CLS_*), the resident classes after it, their lengths in
+ * slot order.  Returns the words written, -1 on a bad argument or a call the encoder would refuse. */
+extern "C" int64_t lnn_classes_replay(const struct LINNEAmdShape *shapes, const uint32_t *lengths, const uint32_t *counts, uint32_t num_calls, int64_t *out, uint64_t cap)
+{
+    if (!shapes || !lengths || !counts || !out || cap < (uint64_t)num_calls * (2 + LNN_MAXCLS)) return -1;
+    LnnKnobs knob; memset(&knob, 0, sizeof(knob));
+    lnn_knobs_read_context(&knob); lnn_knobs_read_call(&knob);
+    LnnClassTable *tab = (LnnClassTable *)calloc(1, sizeof(LnnClassTable));
+    if (!tab) return -1;
+    uint64_t n = 0;
+    for (uint32_t i = 0; i < num_calls; i++) {
+        HostShape hs; LnnCallClasses cc;
+        uint32_t *meta = (uint32_t *)malloc(sizeof(uint32_t) * 3 * (size_t)(counts[i] ? counts[i] : 1));
+        const bool ok = meta && shape_info(&shapes[i], &hs) == LNN_OK
+                && lnn_call_classes(tab, &shapes[i], &hs, &knob, lengths, counts[i], meta, meta + counts[i], meta + 2 * (size_t)counts[i], &cc) == LNN_CLS_OK;
+        free(meta);
+        if (!ok) { free(tab); return -1; }
+        out[n++] = cc.branch; out[n++] = tab->ncls;
+        for (uint32_t s = 0; s < LNN_MAXCLS; s++) out[n++] = s < tab->ncls ? tab->cls[s].n : 0;
+        lengths += counts[i];
+    }
+    free(tab);
+    return (int64_t)n;
 }
