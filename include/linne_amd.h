@@ -313,8 +313,7 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_DEEMPH_LR = 34,         /* the de-emphasis behind it (k_deemph_lr; it includes MS->LR when whole frames lie in a block of 64 rows: no kind 12 then) */
     LINNE_AMD_T_SYNTH_L0_DE = 35,       /* layer 0 + de-emphasis + MS->LR in one launch (k_synth_l0_de) */
     LINNE_AMD_T_SYNTH_ROWS_SHORT = 36,  /* the throughput form of a short layer (k_synth_rows<0> / k_synth_rows8: four or eight channel-frames per wave) */
-    /* the stream decoder (LINNEAmd_StreamIndexCreate / LINNEAmd_DecodeStreamDevice, each a call of its own); the Rice decoding and the
-     * synthesis of a range report as 28 and 11-12, 30-36 */
+    /* the stream index (LINNEAmd_StreamIndexCreate, a call of its own) */
     LINNE_AMD_T_SX_COUNT = 37,          /* counting the block candidates (k_sx_count) */
     LINNE_AMD_T_SX_WRITE = 38,          /* writing them (k_sx_write) */
     LINNE_AMD_T_SX_SCAN = 39,           /* prefix sums (k_sx_scan) */
@@ -323,9 +322,8 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_SX_CHAIN_LEN = 42,      /* the chain's length (k_sx_chain_len) */
     LINNE_AMD_T_SX_CHAIN = 43,          /* its blocks (k_sx_chain) */
     LINNE_AMD_T_SX_CHECK = 44,          /* CRC16 and block checks (k_sx_check) */
-    LINNE_AMD_T_SX_PARAMS = 45,         /* parameter records (k_sx_params) */
-    LINNE_AMD_T_SX_RICE_CHECK = 46,     /* the Rice decoder's consumption check (k_sx_rice_check) */
-    LINNE_AMD_T_SX_PLACE = 47,          /* placing the range into planar output (k_sx_place) */
+    /* 45-47 were the kinds of LINNEAmd_DecodeStreamDevice's own kernels, which are gone (it reports 56-59 now); the numbers are not
+     * reused, so that recorded profiles stay readable */
     /* the stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above); a
      * launch of each per pass */
     LINNE_AMD_T_SE_GATHER = 48,         /* gathering the planar input into frames (k_se_gather) */
@@ -336,7 +334,8 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_SE_RICE = 53,           /* Rice codes (k_se_rice) */
     LINNE_AMD_T_SE_RAW = 54,            /* RAW payloads (k_se_raw) */
     LINNE_AMD_T_SE_CRC = 55,            /* CRC16 and block headers (k_se_crc) */
-    /* many windows in one call (LINNEAmd_DecodeWindowsDevice; a launch of each per pass, with 28 and the synthesis' kinds between them) */
+    /* sample windows of indexed streams (LINNEAmd_DecodeWindowsDevice, and LINNEAmd_DecodeStreamDevice as its one-window case; a
+     * launch of each per pass, with 28 and the synthesis' kinds 11-12, 30-36 between them) */
     LINNE_AMD_T_WX_GATHER = 56,         /* gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather) */
     LINNE_AMD_T_WX_PARAMS = 57,         /* parameter records (k_wx_params) */
     LINNE_AMD_T_WX_RICE_CHECK = 58,     /* the consumption check per window (k_wx_rice_check) */
@@ -398,7 +397,9 @@ int LINNEAmd_PackFramesEmitted(const struct LINNEAmdShape *shape, const int32_t 
  *     damage before it does: earlier blocks fix where later samples sit); otherwise OK and that slice of the whole decode.  The
  *     Rice decoder's consumption is checked on the blocks the range decodes.
  *   - a range beyond num_samples: LINNE_APIRESULT_INVALID_ARGUMENT.
- * The CRC is always checked.  Scratch (kept by the context) grows with the blocks of the range. */
+ * The CRC is always checked.  The call is the one-window case of LINNEAmd_DecodeWindowsDevice below (group_frames 0), run by the same
+ * code: scratch (kept by the context) is as described there, and a range whose COMPRESS blocks hold 2^33 bytes or more is refused
+ * with LINNE_APIRESULT_NG (decode it in parts).  Neither call writes any of d_pcm when the result is a block's failure. */
 struct LINNEAmdStreamIndex;
 struct LINNEHeader;
 struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAmdContext *ctx, const uint8_t *d_stream,
@@ -414,14 +415,15 @@ int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEA
  * different shapes (channels, bits, block size, preset, MS) may be mixed, windows may overlap, repeat and name the same stream (a
  * block two windows share is decoded twice).  Every window's `result` and PCM are what LINNEAmd_DecodeStreamDevice(ctx, index,
  * d_stream, first_sample, num_samples, d_pcm, pcm_stride) returns and writes for it alone -- its argument checks, the index's
- * failing block at or before the range, the Rice consumption check -- except that a failing window's d_pcm is never written, and a
- * failing window does not disturb the others.  Returns LINNE_APIRESULT_OK when every window is OK, otherwise the result of the
+ * failing block at or before the range, the Rice consumption check; a failing window's d_pcm is never written, as in the single
+ * call -- and a failing window does not disturb the others.  Returns LINNE_APIRESULT_OK when every window is OK, otherwise the result of the
  * lowest-numbered failing window; GetLastError then reads "window <i>: " and the single call's text.  A HIP error or running out of
  * memory fails the whole call: LINNE_APIRESULT_NG, in every `result` too.  num_windows == 0 is OK; a NULL ctx, or NULL windows with
  * num_windows > 0, INVALID_ARGUMENT.
  * The windows of one shape are decoded together: the number of kernel launches, copies and host synchronisations does not depend
  * on num_windows.  group_frames bounds the COMPRESS blocks of one pass (scratch, kept by the context: about 8 + 4 * C * S bytes per
- * block plus its stream bytes); 0 = one pass per shape.  It never changes a result: windows are kept whole in a pass where they
+ * COMPRESS block of the pass plus its stream bytes, and 64 bytes per block of the call in a pinned host buffer and its device copy);
+ * 0 = one pass per shape, which is refused with LINNE_APIRESULT_NG when its COMPRESS blocks hold 2^33 bytes or more.  It never changes a result: windows are kept whole in a pass where they
  * fit, and a window of more COMPRESS blocks than group_frames has its Rice codes checked in passes of their own before any of its
  * samples is placed.  Enqueued on the context's stream and synchronous. */
 struct LINNEAmdWindow {

@@ -401,20 +401,27 @@ static int meta_acquire(LINNEAmdContext *ctx, uint32_t F, int *m_out)
     return LNN_OK;
 }
 
+/* a call's per-frame lengths into dst[F] (NULL: every frame is a whole block); a length of 0 or beyond the block size is refused */
+static int copy_lengths(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape, const uint32_t *h_num_samples, uint32_t F, uint32_t *dst)
+{
+    const uint32_t S = shape->num_samples_per_block;
+    for (uint32_t f = 0; f < F; f++) {
+        const uint32_t n = h_num_samples ? h_num_samples[f] : S;
+        if (n == 0 || n > S) { snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", f, n); return LNN_INVALID_ARGUMENT; }
+        dst[f] = n;
+    }
+    return LNN_OK;
+}
+
 /* frame lengths of a decode call: the synthesis kernels need nothing but each frame's length (any number of distinct
  * lengths: a stream written by EncodeBlock calls of varying num_samples, linne_decoder.c:671-742), so no class tables
  * are built and the encode side's resident tables stay valid */
 static int upload_lengths(LINNEAmdContext *ctx, const struct LINNEAmdShape *shape, const uint32_t *h_num_samples, uint32_t F)
 {
-    const uint32_t S = shape->num_samples_per_block;
     int m, ret;
     if ((ret = meta_acquire(ctx, F, &m)) != LNN_OK) return ret;
     uint32_t *nsm = ctx->meta_h[m];
-    for (uint32_t f = 0; f < F; f++) {
-        const uint32_t n = h_num_samples ? h_num_samples[f] : S;
-        if (n == 0 || n > S) { snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", f, n); return LNN_INVALID_ARGUMENT; }
-        nsm[f] = n;
-    }
+    if ((ret = copy_lengths(ctx, shape, h_num_samples, F, nsm)) != LNN_OK) return ret;
     if ((ret = ensure_buf(ctx, (void **)&ctx->d_nsmp, &ctx->nsmp_cap, sizeof(uint32_t) * (uint64_t)(F ? F : 1))) != LNN_OK) return ret;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_nsmp, nsm, sizeof(uint32_t) * F, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->meta_ev[m], ctx->stream));
@@ -1251,11 +1258,7 @@ extern "C" int LINNEAmd_RicePlanDevice(struct LINNEAmdContext *ctx, const struct
     int m;
     if ((ret = meta_acquire(ctx, num_frames, &m)) != LNN_OK) return ret;
     uint32_t *nsm = ctx->meta_h[m];
-    for (uint32_t f = 0; f < num_frames; f++) {
-        const uint32_t n = h_num_samples ? h_num_samples[f] : shape->num_samples_per_block;
-        if (n == 0 || n > shape->num_samples_per_block) { snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", f, n); return LNN_INVALID_ARGUMENT; }
-        nsm[f] = n;
-    }
+    if ((ret = copy_lengths(ctx, shape, h_num_samples, num_frames, nsm)) != LNN_OK) return ret;
     if ((ret = ensure_buf(ctx, (void **)&ctx->d_plan_nsmp, &ctx->plan_nsmp_cap, sizeof(uint32_t) * (uint64_t)num_frames)) != LNN_OK) return ret;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_plan_nsmp, nsm, sizeof(uint32_t) * num_frames, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->meta_ev[m], ctx->stream));
@@ -1309,6 +1312,21 @@ extern "C" int LINNEAmd_RiceEmitDevice(struct LINNEAmdContext *ctx, const struct
     return LNN_OK;
 }
 
+/* k_rice_decode over the F frames of one segment (seg: 4-byte aligned, nbytes of it valid, zero padded to 8 bytes), under its span,
+ * on st.  bitend may be NULL: the codes may run to the segment's end */
+static int rice_decode_launch(LINNEAmdContext *ctx, hipStream_t st, const struct LINNEAmdShape *shape, const uint8_t *seg, uint64_t nbytes,
+        const uint64_t *bitpos, const uint64_t *bitend, const uint32_t *nsmp, uint32_t F, int32_t *resid, uint64_t *endbit)
+{
+    RiceDecodeArgs a; memset(&a, 0, sizeof(a));
+    a.words = (const uint32_t *)seg; a.nbytes = nbytes; a.bitpos = bitpos; a.bitend = bitend; a.nsmp = nsmp; a.resid = resid; a.endbit = endbit;
+    a.F = F; a.C = shape->num_channels; a.S = shape->num_samples_per_block;
+    const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_DECODE, st);
+    hipLaunchKernelGGL(k_rice_decode, dim3((F + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, st, a);
+    span_end(ctx, sp_, st);
+    HIPCHK(ctx, hipGetLastError());
+    return LNN_OK;
+}
+
 /* Rice decoding on the device: see lnn_k_rice.h.  d_stream: the bytes of a group of blocks (4-byte aligned; stream_bytes of it
  * valid, readable up to the next multiple of 8); d_bitpos[f]: where frame f's first channel's code starts (~0: skip the frame);
  * d_endbit[f] receives the bit position behind its last channel's code (~0: the stream held something no encoder writes: the host
@@ -1324,14 +1342,7 @@ extern "C" int LINNEAmd_RiceDecodeDevice(struct LINNEAmdContext *ctx, const stru
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int ret = upload_lengths(ctx, shape, h_num_samples, num_frames);
     if (ret != LNN_OK) return ret;
-    RiceDecodeArgs a; memset(&a, 0, sizeof(a));
-    a.words = (const uint32_t *)d_stream; a.nbytes = stream_bytes; a.bitpos = d_bitpos; a.nsmp = ctx->d_nsmp; a.resid = d_residual; a.endbit = d_endbit;
-    a.F = num_frames; a.C = shape->num_channels; a.S = shape->num_samples_per_block;
-    const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_DECODE, ctx->stream);
-    hipLaunchKernelGGL(k_rice_decode, dim3((num_frames + RDEC_THREADS - 1) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, a);
-    span_end(ctx, sp_, ctx->stream);
-    HIPCHK(ctx, hipGetLastError());
-    return LNN_OK;
+    return rice_decode_launch(ctx, ctx->stream, shape, d_stream, stream_bytes, d_bitpos, NULL, ctx->d_nsmp, num_frames, d_residual, d_endbit);
 }
 
 /* ================================================================================================
@@ -1624,27 +1635,14 @@ extern "C" int LINNEAmd_SlotDecodeStreamSubmit(struct LINNEAmdSlot *s, uint64_t 
     const uint64_t nb = sizeof(int32_t) * CS * num_frames, pb = sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * num_frames;
     memset(s->h_stream + stream_bytes, 0, 16);                 /* the reader loads whole 8-byte words */
     HIPCHK(ctx, hipMemcpyAsync(s->d_stream, s->h_stream, (stream_bytes + 15u) & ~(uint64_t)7u, hipMemcpyHostToDevice, cin));
-    {   /* the frames' lengths travel with the bit positions: the Rice decoder runs on the copy-in stream, beside the synthesis of
-         * the group before (k_rice_decode has a wave per 64 frames -- a few dozen waves -- and leaves the chip to it) */
-        uint32_t *h_nsm = (uint32_t *)(s->h_bitpos + 2 * (size_t)s->max_frames);
-        const uint32_t S_ = s->shape.num_samples_per_block;
-        for (uint32_t f = 0; f < num_frames; f++) {
-            const uint32_t n_ = num_samples ? num_samples[f] : S_;
-            if (n_ == 0 || n_ > S_) { snprintf(ctx->err, sizeof(ctx->err), "frame %u: num_samples %u out of range", f, n_); return LNN_INVALID_ARGUMENT; }
-            h_nsm[f] = n_;
-        }
-    }
+    /* the frames' lengths travel with the bit positions: the Rice decoder runs on the copy-in stream, beside the synthesis of the
+     * group before (k_rice_decode has a wave per 64 frames -- a few dozen waves -- and leaves the chip to it) */
+    if ((ret = copy_lengths(ctx, &s->shape, num_samples, num_frames, (uint32_t *)(s->h_bitpos + 2 * (size_t)s->max_frames))) != LNN_OK) return ret;
     HIPCHK(ctx, hipMemcpyAsync(s->d_bitpos, s->h_bitpos, 2 * sizeof(uint64_t) * s->max_frames + sizeof(uint32_t) * num_frames, hipMemcpyHostToDevice, cin));
     HIPCHK(ctx, hipMemcpyAsync(s->d_prm, s->h_prm, pb, hipMemcpyHostToDevice, cin));
-    {
-        RiceDecodeArgs a; memset(&a, 0, sizeof(a));
-        a.words = (const uint32_t *)s->d_stream; a.nbytes = stream_bytes; a.bitpos = s->d_bitpos; a.nsmp = (const uint32_t *)(s->d_bitpos + 2 * (size_t)s->max_frames); a.bitend = s->d_bitpos + s->max_frames;
-        a.resid = s->d_data; a.endbit = s->d_endbit; a.F = num_frames; a.C = s->shape.num_channels; a.S = s->shape.num_samples_per_block;
-        if (rst != cin) { HIPCHK(ctx, hipEventRecord(s->ev_in, cin)); HIPCHK(ctx, hipStreamWaitEvent(rst, s->ev_in, 0)); }
-        const int sp_ = span_begin(ctx, LINNE_AMD_T_RICE_DECODE, rst);
-        hipLaunchKernelGGL(k_rice_decode, dim3((num_frames + RDEC_THREADS - 1) / RDEC_THREADS), dim3(RDEC_THREADS), 0, rst, a);
-        span_end(ctx, sp_, rst);
-    }
+    if (rst != cin) { HIPCHK(ctx, hipEventRecord(s->ev_in, cin)); HIPCHK(ctx, hipStreamWaitEvent(rst, s->ev_in, 0)); }
+    if ((ret = rice_decode_launch(ctx, rst, &s->shape, s->d_stream, stream_bytes, s->d_bitpos, s->d_bitpos + s->max_frames,
+            (const uint32_t *)(s->d_bitpos + 2 * (size_t)s->max_frames), num_frames, s->d_data, s->d_endbit)) != LNN_OK) return ret;
     HIPCHK(ctx, hipEventRecord(s->ev_in, rst));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s->ev_in, 0));
     if ((ret = LINNEAmd_DecodeFramesDevice(ctx, &s->shape, s->d_data, num_samples, num_frames, s->d_prm)) != LNN_OK) return ret;
@@ -1918,111 +1916,12 @@ static uint64_t sx_block_of(const LINNEAmdStreamIndex *x, uint64_t s)
     return lo;
 }
 
-extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *x, const uint8_t *d_stream,
-        uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride)
-{
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (!x || !d_stream || (!d_pcm && num_samples)) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    if (x->device != ctx->device) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
-    const uint64_t total = x->header.num_samples;
-    const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
-    if (first_sample > total || num_samples > total - first_sample) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)first_sample, (unsigned long long)(first_sample + num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
-    if (C > 1u && pcm_stride < num_samples) { snprintf(ctx->err, sizeof(ctx->err), "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)pcm_stride, (unsigned long long)num_samples); return LNN_INVALID_ARGUMENT; }
-    if (num_samples == 0) return LNN_OK;
-    const uint64_t lo = first_sample, hi = first_sample + num_samples;
-    /* blocks 0 .. r1 decide the range (r1 = nb: it reaches behind the last block) */
-    const uint64_t r1 = (hi - 1u < x->covered) ? sx_block_of(x, hi - 1u) : x->nb;
-    if (x->fail_block >= 0 && (uint64_t)x->fail_block <= r1) {
-        snprintf(ctx->err, sizeof(ctx->err), "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
-                x->fail_code == LNN_NG ? "a block no encoder writes" : "damaged or truncated stream");
-        return x->fail_code;
-    }
-    HostShape hs;
-    SX_TRY(shape_info(&x->shape, &hs));
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    lnn_knobs_read_call(&ctx->knob);
-    const uint64_t r0 = (lo < x->covered) ? sx_block_of(x, lo) : x->nb;
-    const uint64_t nr = (r0 < x->nb) ? ((r1 < x->nb ? r1 : x->nb - 1u) - r0 + 1u) : 0u;
-    /* the range's COMPRESS blocks, compacted */
-    uint32_t *h_list = (uint32_t *)malloc(sizeof(uint32_t) * (2u * nr + 1u));
-    if (!h_list) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-    uint32_t *h_comp = h_list, *h_cidx = h_list + nr, ncomp = 0;
-    for (uint64_t y = 0; y < nr; y++) {
-        const uint64_t r = r0 + y;
-        if (x->h_type[r] == SX_COMPRESS) { h_cidx[y] = ncomp; h_comp[ncomp++] = (uint32_t)r; } else h_cidx[y] = 0xFFFFFFFFu;
-    }
-    const uint64_t seg_first = ncomp ? x->h_off[h_comp[0]] : 0u;
-    const uint64_t seg_bytes = ncomp ? x->h_off[h_comp[ncomp - 1]] + x->h_size[h_comp[ncomp - 1]] + 6u - seg_first : 0u;
-    /* scratch: fail word, lists, per-frame words, parameter records, residual / PCM, the Rice decoder's copy of the segment */
-    const uint64_t CS = (uint64_t)C * S;
-    uint64_t at = 0;
-    const uint64_t o_fail = at; at = align_up(at + sizeof(uint32_t));
-    const uint64_t o_comp = at; at = align_up(at + sizeof(uint32_t) * (ncomp + 1u));
-    const uint64_t o_cidx = at; at = align_up(at + sizeof(uint32_t) * (nr + 1u));
-    const uint64_t o_nsmp = at; at = align_up(at + sizeof(uint32_t) * (ncomp + 1u));
-    const uint64_t o_bpos = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
-    const uint64_t o_bend = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
-    const uint64_t o_eb = at; at = align_up(at + sizeof(uint64_t) * (ncomp + 1u));
-    const uint64_t o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * (uint64_t)ncomp);
-    const uint64_t o_data = at; at = align_up(at + sizeof(int32_t) * CS * ncomp);
-    const uint64_t o_seg = at; at = align_up(at + seg_bytes + 16u);
-    int ret = ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, at);
-    if (ret != LNN_OK) { free(h_list); return ret; }
-    uint8_t *sd = (uint8_t *)ctx->sdec;
-    uint32_t *d_fail = (uint32_t *)(sd + o_fail), *d_comp = (uint32_t *)(sd + o_comp), *d_cidx = (uint32_t *)(sd + o_cidx), *d_nsmp = (uint32_t *)(sd + o_nsmp);
-    uint64_t *d_bpos = (uint64_t *)(sd + o_bpos), *d_bend = (uint64_t *)(sd + o_bend), *d_eb = (uint64_t *)(sd + o_eb);
-    int32_t *d_prm = (int32_t *)(sd + o_prm), *d_data = (int32_t *)(sd + o_data);
-    uint8_t *d_seg = sd + o_seg;
-    ctx->nspans = 0;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (ncomp) HIPCHK(ctx, hipMemcpyAsync(d_comp, h_comp, sizeof(uint32_t) * ncomp, hipMemcpyHostToDevice, ctx->stream));
-    if (nr) HIPCHK(ctx, hipMemcpyAsync(d_cidx, h_cidx, sizeof(uint32_t) * nr, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));             /* (the host lists are freed next) */
-    free(h_list);
-    if (ncomp) {
-        /* the Rice decoder reads 4-byte words of a zero-padded segment: the bytes of the range's COMPRESS blocks, copied */
-        HIPCHK(ctx, hipMemcpyAsync(d_seg, d_stream + seg_first, seg_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_seg + seg_bytes, 0, 16u, ctx->stream));
-        SxParamArgs pa; memset(&pa, 0, sizeof(pa));
-        pa.b = d_stream; pa.N = x->stream_bytes; pa.off = x->d_off; pa.size = x->d_size; pa.nsmp = x->d_nsmp; pa.comp = d_comp;
-        pa.ncomp = ncomp; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
-        for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
-        pa.seg_first = seg_first; pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
-        SX_LAUNCH(LINNE_AMD_T_SX_PARAMS, k_sx_params, dim3((ncomp + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
-        RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
-        ra.words = (const uint32_t *)d_seg; ra.nbytes = seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
-        ra.resid = d_data; ra.endbit = d_eb; ra.F = ncomp; ra.C = C; ra.S = S;
-        SX_LAUNCH(LINNE_AMD_T_RICE_DECODE, k_rice_decode, dim3((ncomp + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
-        HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
-        SX_LAUNCH(LINNE_AMD_T_SX_RICE_CHECK, k_sx_rice_check, dim3((ncomp + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, (const uint32_t *)d_comp, (const uint64_t *)x->d_off,
-                (const uint32_t *)x->d_size, ncomp, seg_first, d_fail);
-        SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, ncomp, d_prm));
-        uint32_t fail = 0;
-        SX_TRY(sx_fetch(ctx, &fail, d_fail, sizeof(fail)));
-        if (fail != 0xFFFFFFFFu) {
-            snprintf(ctx->err, sizeof(ctx->err), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
-                    fail, (unsigned long long)x->h_off[fail]);
-            return LNN_NG;
-        }
-    }
-    SxPlaceArgs la; memset(&la, 0, sizeof(la));
-    la.b = d_stream; la.N = x->stream_bytes; la.off = x->d_off; la.first = x->d_first; la.type = x->d_type; la.nsmp = x->d_nsmp; la.cidx = d_cidx;
-    la.r0 = (uint32_t)r0; la.nr = (uint32_t)nr; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
-    la.lo = lo; la.hi = hi; la.covered = x->covered; la.out = d_pcm; la.stride = pcm_stride;
-    la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
-    SX_LAUNCH(LINNE_AMD_T_SX_PLACE, k_sx_place, dim3((uint32_t)((nr + 1u) * la.xch)), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
-    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LNN_OK;
-}
-
-
 /* ================================================================================================
- * many sample windows of many resident streams in one call (lnn_k_windows.h)
+ * sample windows of resident streams: many in one call, or one (lnn_k_windows.h)
  * ============================================================================================== */
-/* the argument and index checks of LINNEAmd_DecodeStreamDevice on one window, with its codes and texts, in its order.  *r1 = the last
- * block the window overlaps (nb: it reaches behind the last block); not set for a window of 0 samples */
+/* the argument and index checks on one window, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
+ * window's fields are).  *r1 = the last block the window overlaps (nb: it reaches behind the last block); not set for a window of 0
+ * samples */
 static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, char *err, size_t cap, uint64_t *r1)
 {
     const LINNEAmdStreamIndex *x = w->index;
@@ -2062,10 +1961,12 @@ static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_by
 }
 #define WX_MAXGROUPS 64
 
-/* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call */
-static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, WxPlan *plan, const uint32_t **fail_out)
+/* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call.  single: the call
+ * is LINNEAmd_DecodeStreamDevice, which its texts then name */
+static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, bool single, WxPlan *plan, const uint32_t **fail_out)
 {
     const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
+    const char *who = single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
     char text[sizeof(ctx->err)];
     /* 1. the checks per window; the live ones get their blocks and the group of their shape */
     uint64_t nlive = 0, total_rec = 0, total_crec = 0;
@@ -2083,7 +1984,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         uint32_t g = 0;
         while (g < ngroups && memcmp(&gx[g]->shape, &x->shape, sizeof(x->shape)) != 0) g++;
         if (g == ngroups) {
-            if (ngroups == WX_MAXGROUPS) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: more than %d stream shapes in one call", WX_MAXGROUPS); return LNN_NG; }
+            if (ngroups == WX_MAXGROUPS) { snprintf(ctx->err, sizeof(ctx->err), "%s: more than %d stream shapes in one call", who, WX_MAXGROUPS); return LNN_NG; }
             gx[ngroups++] = x;
         }
         plan[i].r0 = (uint32_t)r0; plan[i].nr = (uint32_t)nr; plan[i].ncomp = nc; plan[i].group = (int32_t)g;
@@ -2092,7 +1993,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     }
     *fail_out = NULL;
     if (!nlive) return LNN_OK;
-    if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: %llu blocks in one call: too many", (unsigned long long)total_rec); return LNN_NG; }
+    if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu blocks in one call: too many", who, (unsigned long long)total_rec); return LNN_NG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory: fail words | window records | block records | the passes' COMPRESS records */
@@ -2169,7 +2070,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         }
         close(0);
     }
-    for (const WxPass &p : passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: a pass of %llu stream bytes: give group_frames", (unsigned long long)p.seg_bytes); return LNN_NG; }
+    for (const WxPass &p : passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
     SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, scratch_bytes));
@@ -2199,10 +2100,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
             for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
             pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
             SX_LAUNCH(LINNE_AMD_T_WX_PARAMS, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
-            RiceDecodeArgs ra; memset(&ra, 0, sizeof(ra));
-            ra.words = (const uint32_t *)d_seg; ra.nbytes = p.seg_bytes; ra.bitpos = d_bpos; ra.bitend = d_bend; ra.nsmp = d_nsmp;
-            ra.resid = d_data; ra.endbit = d_eb; ra.F = p.nc; ra.C = C; ra.S = S;
-            SX_LAUNCH(LINNE_AMD_T_RICE_DECODE, k_rice_decode, dim3((p.nc + RDEC_THREADS - 1u) / RDEC_THREADS), dim3(RDEC_THREADS), 0, ctx->stream, ra);
+            SX_TRY(rice_decode_launch(ctx, ctx->stream, &x->shape, d_seg, p.seg_bytes, d_bpos, d_bend, d_nsmp, p.nc, d_data, d_eb));
             SX_LAUNCH(LINNE_AMD_T_WX_RICE_CHECK, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
             if (!p.check_only) SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, p.nc, d_prm));
         }
@@ -2210,7 +2108,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         WxPlaceArgs la; memset(&la, 0, sizeof(la));
         la.recs = d_rec; la.nrec = p.nrec; la.wins = d_win; la.fail = d_fail; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
-        if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: a pass of %u blocks: give group_frames", p.nrec); return LNN_NG; }
+        if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
         SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
     /* 5. the fail words, with the call's one wait */
@@ -2222,42 +2120,53 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     return LNN_OK;
 }
 
+/* Both entry points behind their argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
+ * with its text in ctx->err (behind the window's number unless the call is the single one) */
+static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames, bool single)
+{
+    ctx->err[0] = 0;
+    const uint32_t *fail = NULL;
+    std::vector<WxPlan> plan;
+    int ret;
+    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, num_windows, group_frames, single, plan.data(), &fail); }
+    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    if (ret != LNN_OK) {
+        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
+        (void)hipStreamSynchronize(ctx->stream);
+        for (uint32_t i = 0; i < num_windows; i++) windows[i].result = LNN_NG;
+        return LNN_NG;
+    }
+    for (uint32_t i = 0; i < num_windows; i++) {
+        if (windows[i].result == LNN_OK) continue;
+        char text[sizeof(ctx->err)]; uint64_t r1;
+        if (plan[i].group >= 0 && fail)
+            snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
+                    fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
+        else (void)wx_check_window(ctx, &windows[i], text, sizeof(text), &r1);
+        if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
+        else snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
+        return windows[i].result;
+    }
+    return LNN_OK;
+}
+
 extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
 {
     if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
     if (num_windows == 0) return LNN_OK;
     if (!windows) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    const uint32_t *fail = NULL;
-    int ret;
-    WxPlan *plan = (WxPlan *)malloc(sizeof(WxPlan) * (size_t)num_windows);
-    if (!plan) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
-    else {
-        try { ret = wx_decode(ctx, windows, num_windows, group_frames, plan, &fail); }
-        catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
-    }
-    if (ret != LNN_OK) {
-        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
-        (void)hipStreamSynchronize(ctx->stream);
-        for (uint32_t i = 0; i < num_windows; i++) windows[i].result = LNN_NG;
-        free(plan);
-        return LNN_NG;
-    }
-    /* the lowest-numbered failing window's code, and its text behind its number */
-    ret = LNN_OK;
-    for (uint32_t i = 0; i < num_windows; i++) {
-        if (windows[i].result == LNN_OK) continue;
-        char text[sizeof(ctx->err)]; uint64_t r1;
-        ret = windows[i].result;
-        if (plan[i].group >= 0 && fail)
-            snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
-                    fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
-        else (void)wx_check_window(ctx, &windows[i], text, sizeof(text), &r1);
-        snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
-        break;
-    }
-    free(plan);
-    return ret;
+    return wx_run(ctx, windows, num_windows, group_frames, false);
+}
+
+/* one window of one stream */
+extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *x, const uint8_t *d_stream,
+        uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    struct LINNEAmdWindow w;
+    w.index = x; w.d_stream = d_stream; w.first_sample = first_sample; w.num_samples = num_samples; w.d_pcm = d_pcm; w.pcm_stride = pcm_stride; w.result = LNN_OK;
+    return wx_run(ctx, &w, 1, 0, true);
 }
 
 

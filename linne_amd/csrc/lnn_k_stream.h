@@ -1,5 +1,5 @@
-/* lnn_k_stream.h -- the front end of decoding a .lnn stream that lies in device memory (LINNEAmd_StreamIndexCreate,
- * LINNEAmd_DecodeStreamDevice).
+/* lnn_k_stream.h -- the block index of a .lnn stream that lies in device memory (LINNEAmd_StreamIndexCreate),
+ * and the bit reader and parameter walk that decoding its blocks shares with it.
  *
  * Block index, built once per stream:
  *   k_sx_count / k_sx_write   every position from the first block on that passes the checks lnn_parse_block_head makes before the
@@ -13,12 +13,7 @@
  *   k_sx_scan                 exclusive prefix sums (one workgroup): candidate offsets, the blocks' first samples
  *   k_sx_check                a wave per block: CRC16 over lanes (partial CRCs shifted by the bytes behind them and XORed),
  *                             then the checks lnn_parse_block_head makes after the CRC, in its order
- * Decoding a range:
- *   k_sx_params               a lane per COMPRESS block: its parameter records, where its Rice code starts and ends
- *   (k_rice_decode and the synthesis kernels of lnn_k_rice.h / lnn_k_decode*.h)
- *   k_sx_rice_check           did the Rice decoder consume exactly the bytes the block's size field names?
- *   k_sx_place                the range's samples into planar output: COMPRESS from the synthesis, RAW un-zig-zagged from the
- *                             stream, SILENT and whatever lies beyond the last block as zeros
+ * Decoding sample ranges with the index, one or many in a call: lnn_k_windows.h.
  * Every read of the stream is a byte load inside [0, stream_bytes): the caller's bytes may lie at any alignment.
  */
 #ifndef LNN_K_STREAM_H_INCLUDED
@@ -231,17 +226,6 @@ struct SxBits {
     }
 };
 
-struct SxParamArgs {
-    const uint8_t *b; uint64_t N;
-    const uint64_t *off; const uint32_t *size, *nsmp;
-    const uint32_t *comp;               /* [ncomp] the range's COMPRESS blocks (block numbers) */
-    uint32_t ncomp, C, bits, L, P[LNN_MAXL], coef_off[LNN_MAXL];
-    uint64_t seg_first;                 /* stream position of the Rice decoder's segment */
-    const SxTables *tab;
-    int32_t *prm;                       /* [ncomp][C][LINNE_AMD_PARAM_WORDS] */
-    uint64_t *bitpos, *bitend;          /* [ncomp], bits from seg_first */
-    uint32_t *out_nsmp;                 /* [ncomp] */
-};
 /* lnn_parse_block_head's parameter part (lnn_entropy.c:912-932) of one block, read from r into base[C][LINNE_AMD_PARAM_WORDS]:
  * the records are serial within a block.  child: the Huffman tree (in LDS) */
 __device__ __forceinline__ void sx_parse_params(SxBits &r, const uint16_t (*child)[2], uint32_t root, uint32_t C, uint32_t bits, uint32_t L,
@@ -266,78 +250,6 @@ __device__ __forceinline__ void sx_parse_params(SxBits &r, const uint16_t (*chil
                 rec[LINNE_AMD_PRM_COEF + coef_off[l] + i] = sx_unzz(node);
             }
         }
-    }
-}
-/* a lane per COMPRESS block of the range */
-__global__ __launch_bounds__(64) void k_sx_params(SxParamArgs a)
-{
-    __shared__ uint16_t child[512][2];
-    for (uint32_t i = threadIdx.x; i < 512u; i += 64u) { child[i][0] = a.tab->child[i][0]; child[i][1] = a.tab->child[i][1]; }
-    __syncthreads();
-    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
-    if (k >= a.ncomp) return;
-    const uint32_t blk = a.comp[k];
-    const uint64_t p = a.off[blk];
-    SxBits r; r.open(a.b, a.N, p + 11u);
-    sx_parse_params(r, child, a.tab->root, a.C, a.bits, a.L, a.P, a.coef_off, a.prm + (uint64_t)k * a.C * LINNE_AMD_PARAM_WORDS);
-    a.bitpos[k] = (p - a.seg_first) * 8u + 88u + r.consumed;
-    a.bitend[k] = (p - a.seg_first + (uint64_t)a.size[blk] + 6u) * 8u;
-    a.out_nsmp[k] = a.nsmp[blk];
-}
-
-/* DecodeWhole's test of the device's Rice decoder (lnn_api.c:860-868): the codes must end in the block's last byte.  fail = the
- * lowest block number that fails it */
-__global__ __launch_bounds__(256) void k_sx_rice_check(const uint64_t *endbit, const uint32_t *comp, const uint64_t *off, const uint32_t *size,
-        uint32_t ncomp, uint64_t seg_first, uint32_t *fail)
-{
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k >= ncomp) return;
-    const uint32_t blk = comp[k];
-    const uint64_t eb = endbit[k], pay = (off[blk] - seg_first + 11u) * 8u;
-    if (eb == ~0ull || eb < pay || 11u + ((eb - pay + 7u) >> 3) != (uint64_t)size[blk] + 6u) atomicMin(fail, blk);
-}
-
-struct SxPlaceArgs {
-    const uint8_t *b; uint64_t N;
-    const uint64_t *off, *first; const uint32_t *type, *nsmp;
-    const uint32_t *cidx;               /* [nr] the range's blocks: index among the range's COMPRESS blocks, or ~0 */
-    uint32_t r0, nr, C, S, bits;
-    const int32_t *pcm;                 /* [ncomp][C][S]: the synthesis' output */
-    uint64_t lo, hi;                    /* the range [lo, hi) */
-    uint64_t covered;                   /* samples the stream's blocks hold: [covered, hi) is zeros */
-    int32_t *out; uint64_t stride;
-    uint32_t xch;                       /* workgroups per block */
-};
-/* (nr + 1) * xch workgroups: the y-th xch of them place block r0 + y's samples, the last xch zero the part of the range beyond the
- * last block */
-__global__ __launch_bounds__(SX_PLACE_THREADS) void k_sx_place(SxPlaceArgs a)
-{
-    const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
-    if (y == a.nr) {
-        const uint64_t z0 = a.covered > a.lo ? a.covered : a.lo;
-        for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS + threadIdx.x; s < a.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-            for (uint32_t ch = 0; ch < a.C; ch++) a.out[(uint64_t)ch * a.stride + (s - a.lo)] = 0;
-        return;
-    }
-    const uint32_t r = a.r0 + y, n = a.nsmp[r], type = a.type[r];
-    const uint64_t f0 = a.first[r];
-    for (uint32_t i = x * SX_PLACE_THREADS + threadIdx.x; i < n; i += a.xch * SX_PLACE_THREADS) {
-        const uint64_t s = f0 + i;
-        if (s < a.lo || s >= a.hi) continue;
-        int32_t *dst = a.out + (s - a.lo);
-        if (type == SX_COMPRESS) {
-            const int32_t *src = a.pcm + (uint64_t)a.cidx[y] * a.C * a.S + i;
-            for (uint32_t ch = 0; ch < a.C; ch++) dst[(uint64_t)ch * a.stride] = src[(uint64_t)ch * a.S];
-        } else if (type == SX_RAW) {
-            const uint32_t w = a.bits >> 3;
-            uint64_t q = a.off[r] + 11u + (uint64_t)i * a.C * w;
-            for (uint32_t ch = 0; ch < a.C; ch++, q += w) {
-                uint32_t u = 0;
-                for (uint32_t j = 0; j < w; j++) u = (u << 8) | a.b[q + j];
-                dst[(uint64_t)ch * a.stride] = sx_unzz(u);
-            }
-        } else
-            for (uint32_t ch = 0; ch < a.C; ch++) dst[(uint64_t)ch * a.stride] = 0;
     }
 }
 

@@ -1,19 +1,21 @@
-/* lnn_k_windows.h -- decoding many sample windows of many resident .lnn streams in one call (LINNEAmd_DecodeWindowsDevice;
- * DESIGN.md section 5, "Many windows in one call").
+/* lnn_k_windows.h -- decoding sample windows of resident .lnn streams with their block indexes (lnn_k_stream.h): many windows of
+ * many streams in one call (LINNEAmd_DecodeWindowsDevice) or one (LINNEAmd_DecodeStreamDevice, the same with one window); DESIGN.md
+ * section 5, "Many windows in one call".
  *
  * The host flattens the windows of one stream shape into block records (one per block of every window, in window order) and
  * window records, uploads them once, and launches per pass:
  *   k_wx_gather               the bytes of the pass's COMPRESS blocks, each from its own stream, into one packed segment the Rice
  *                             decoder reads as words
- *   k_wx_params               k_sx_params with the block taken from its record: parameter records, where the Rice code starts
- *                             and ends in the packed segment
- *   (k_rice_decode)
- *   k_wx_rice_check           k_sx_rice_check per record, the failing block's number into its window's fail word
- *   (the synthesis kernels)
+ *   k_wx_params               a lane per COMPRESS block: its parameter records, where its Rice code starts and ends in the
+ *                             packed segment
+ *   (k_rice_decode of lnn_k_rice.h)
+ *   k_wx_rice_check           did the Rice decoder consume exactly the bytes the block's size field names?  The lowest failing
+ *                             block's number goes into its window's fail word
+ *   (the synthesis kernels of lnn_k_decode*.h)
  *   k_wx_place                every record's samples, cropped to its window, into that window's planar output; a record of type
  *                             WX_TAIL is the part of a window beyond the stream's last block (zeros).  The records of a window whose
  *                             fail word is set are skipped: a failing window's output is not written
- * As in lnn_k_stream.h, no read of a stream leaves [0, stream_bytes).
+ * As in lnn_k_stream.h, no read of a stream leaves [0, stream_bytes): RAW samples are un-zig-zagged straight from the stream.
  */
 #ifndef LNN_K_WINDOWS_H_INCLUDED
 #define LNN_K_WINDOWS_H_INCLUDED
@@ -78,7 +80,7 @@ struct WxParamArgs {
     uint64_t *bitpos, *bitend;          /* [ncomp], bits from the packed segment's start */
     uint32_t *out_nsmp;                 /* [ncomp] */
 };
-/* a lane per COMPRESS block of the pass; the bits are read from the block's own stream, as k_sx_params reads them */
+/* a lane per COMPRESS block of the pass; the bits are read from the block's own stream, not from the packed segment */
 __global__ __launch_bounds__(64) void k_wx_params(WxParamArgs a)
 {
     __shared__ uint16_t child[512][2];
@@ -94,7 +96,8 @@ __global__ __launch_bounds__(64) void k_wx_params(WxParamArgs a)
     a.out_nsmp[k] = rc->nsmp;
 }
 
-/* k_sx_rice_check per record: fail[window] = the lowest block number of the window's stream that fails it (preset to WX_NOFAIL) */
+/* DecodeWhole's test of the device's Rice decoder (lnn_api.c:860-868): the codes must end in the block's last byte.  fail[window] =
+ * the lowest block number of the window's stream that fails it (preset to WX_NOFAIL) */
 __global__ __launch_bounds__(256) void k_wx_rice_check(const uint64_t *endbit, const WxBlock *recs, const uint32_t *crec, const WxWindow *wins,
         uint32_t ncomp, uint32_t *fail)
 {

@@ -223,15 +223,21 @@ def codes_alone(ctx, wins):
     return out
 
 
+def crc_damaged(t):
+    """(the track's stream with a payload byte of block k flipped, so that the block's CRC fails; k)"""
+    k = len(t.bl) // 2
+    off, size = t.bl[k][:2]
+    bad = bytearray(t.stream)
+    bad[off + size - 2] ^= 0x10
+    return bytes(bad), k
+
+
 def test_damage_stays_in_its_window(ctx, corpus):
     import torch
     t, u, v = corpus[1], corpus[2], corpus[6]                    # all stereo
     bl = t.bl
-    k = len(bl) // 2
-    off, size = bl[k][:2]
-    bad = bytearray(t.stream)
-    bad[off + size - 2] ^= 0x10                                  # a payload byte of block k: its CRC fails
-    d_bad = to_device(bytes(bad))
+    bad, k = crc_damaged(t)
+    d_bad = to_device(bad)
     index = ctx.index_stream(d_bad)
     n = 900
     before, after = bl[k - 2], bl[k + 1]
@@ -254,10 +260,11 @@ def test_damage_stays_in_its_window(ctx, corpus):
     index.close()
 
 
-def test_the_consumption_check(ctx, product, corpus):
-    """a payload bit of a COMPRESS block flipped and the CRC16 made right again: the index finds nothing, the Rice decoder does"""
-    import torch
-    t, u = corpus[1], corpus[6]
+@pytest.fixture(scope="module")
+def rice_damaged(ctx, product, corpus):
+    """corpus[1] with a payload bit of COMPRESS block k flipped and the CRC16 made right again, such that DecodeWhole fails on it:
+    (the stream on the device, its index, k, DecodeWhole's code)"""
+    t = corpus[1]
     bl = t.bl
     k = max(i for i, b in enumerate(bl[:-1]) if b[2] == COMPRESS and bl[i - 1][2] == COMPRESS)
     off, size = bl[k][:2]
@@ -273,15 +280,24 @@ def test_the_consumption_check(ctx, product, corpus):
         if ret == OK:
             continue
         d_bad = to_device(bad)
-        index = ctx.index_stream(d_bad)
-        found = (d_bad, index)
+        found = (d_bad, ctx.index_stream(d_bad), k, ret)
         break
     assert found is not None, "no flip in 64 made DecodeWhole fail"
-    d_bad, index = found
+    yield found
+    found[1].close()
+
+
+def test_the_consumption_check(ctx, corpus, rice_damaged):
+    """a payload bit of a COMPRESS block flipped and the CRC16 made right again: the index finds nothing, the Rice decoder does"""
+    import torch
+    t, u = corpus[1], corpus[6]
+    bl = t.bl
+    d_bad, index, k, whole = rice_damaged
+    assert whole != OK                                           # DecodeWhole's verdict on that stream
     n = 700
     wins = [(d_bad, index, bl[k][4] + 10, n), (d_bad, index, bl[k - 1][4] + 10, n), u.win(999, n), (d_bad, index, bl[k + 1][4], 50)]
     alone = codes_alone(ctx, wins)
-    assert alone[0] != OK and alone[1:] == [OK, OK, OK]
+    assert alone[0] == NG and alone[1:] == [OK, OK, OK]
     for gf in (0, 1):
         arr = torch.full((3, 2, n), -4242, dtype=torch.int32, device="cuda")
         back, codes = ctx.decode_windows(wins[:3], out=arr, group_frames=gf, return_codes=True)
@@ -298,7 +314,36 @@ def test_the_consumption_check(ctx, product, corpus):
     with pytest.raises(linne_amd.LinneAmdError) as e:
         ctx.decode_windows(wins)
     assert e.value.code == alone[0] and e.value.codes == alone and "window 0:" in str(e.value)
-    index.close()
+
+
+def test_single_call_text_is_the_windows_text(ctx, corpus, rice_damaged):
+    """one window of each kind of failure -- the index's, the consumption check's, an argument's: decode_windows reads "window 0: "
+    and then exactly what decode_stream reads for that window.  The index's text is also held to what the separate single-call path
+    gave before both calls shared one implementation, recorded from that build"""
+    t = corpus[1]
+    bad, kc = crc_damaged(t)
+    d_crc = to_device(bad)
+    crc_index = ctx.index_stream(d_crc)
+    d_rice, rice_index, kr, _ = rice_damaged
+    texts = {}
+    for name, win, code in [("crc", (d_crc, crc_index, t.bl[kc][4] + 3, 900), CORRUPTION),
+                            ("rice", (d_rice, rice_index, t.bl[kr][4] + 10, 700), NG),
+                            ("argument", t.win(t.ns, 1), INVALID_ARGUMENT)]:
+        dev, index, a, n = win
+        with pytest.raises(linne_amd.LinneAmdError) as single:
+            ctx.decode_stream(dev, a, n, index=index)
+        with pytest.raises(linne_amd.LinneAmdError) as batch:
+            ctx.decode_windows([win])
+        assert single.value.code == code and batch.value.code == code and batch.value.codes == [code], name
+        head_single, head_batch = f"DecodeStreamDevice -> {code}: ", f"DecodeWindowsDevice -> {code}: "
+        assert str(single.value).startswith(head_single) and str(batch.value).startswith(head_batch), name
+        text = str(single.value)[len(head_single):]
+        assert text and "window" not in text, (name, text)
+        assert str(batch.value)[len(head_batch):] == "window 0: " + text, name
+        texts[name] = text
+    assert texts["crc"] == f"block {kc} (byte {t.bl[kc][0]} of the stream): damaged or truncated stream"
+    assert texts["rice"].startswith(f"block {kr} (byte {t.bl[kr][0]} of the stream): ") and "no encoder writes" in texts["rice"]
+    crc_index.close()
 
 
 def test_bad_arguments_per_window(ctx, corpus):

@@ -52,7 +52,7 @@ t_window, _ = median_ms(lambda: ctx.decode_stream(d_stream, first, win, index=in
 # the kernels of one whole decode (timing on: events around every launch)
 ctx.enable_timing(True)
 ctx.decode_stream(d_stream, index=index)
-kinds = {k: round(ctx.last_ms(k), 3) for k in (45, 28, 46, 47, 32, 33, 34, 35, 36, 30, 31, 11, 12) if ctx.last_launches(k) > 0}
+kinds = {k: round(ctx.last_ms(k), 3) for k in (56, 57, 28, 58, 32, 33, 34, 35, 36, 30, 31, 11, 12, 59) if ctx.last_launches(k) > 0}
 ctx.index_stream(d_stream).close()
 kinds_index = {k: round(ctx.last_ms(k), 3) for k in range(37, 45) if ctx.last_launches(k) > 0}
 ctx.enable_timing(False)
