@@ -20,6 +20,7 @@
 #define LINNE_AMD_H_INCLUDED
 
 #include <stdint.h>
+#include "linne.h"                        /* struct LINNEHeader, a member of struct LINNEAmdTrack */
 
 #define LINNE_AMD_MAX_LAYERS      3
 #define LINNE_AMD_MAX_PARAMS      128
@@ -339,7 +340,18 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_WX_GATHER = 56,         /* gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather) */
     LINNE_AMD_T_WX_PARAMS = 57,         /* parameter records (k_wx_params) */
     LINNE_AMD_T_WX_RICE_CHECK = 58,     /* the consumption check per window (k_wx_rice_check) */
-    LINNE_AMD_T_WX_PLACE = 59           /* placing every window's samples (k_wx_place) */
+    LINNE_AMD_T_WX_PLACE = 59,          /* placing every window's samples (k_wx_place) */
+    /* many tracks into streams (LINNEAmd_EncodeStreamsDevice, a call of its own; per pass a launch of each of 60-67, with 49, 51,
+     * the analysis' kinds and 17 between them; 68 once per shape) */
+    LINNE_AMD_T_SB_GATHER = 60,         /* gathering the rows of a pass from their tracks (k_sb_gather) */
+    LINNE_AMD_T_SB_SIZE = 61,           /* block sizes into stream-order slots (k_se_size<true>) */
+    LINNE_AMD_T_SB_REDUCE = 62,         /* per track: bytes, lowest failing block (k_sb_reduce) */
+    LINNE_AMD_T_SB_ZERO = 63,           /* zeroing the written tracks' regions (k_sb_zero) */
+    LINNE_AMD_T_SB_PARAMS = 64,         /* parameter bits (k_se_params<true>) */
+    LINNE_AMD_T_SB_RICE = 65,           /* Rice codes (k_se_rice<., true>) */
+    LINNE_AMD_T_SB_RAW = 66,            /* RAW payloads (k_se_raw<true>) */
+    LINNE_AMD_T_SB_CRC = 67,            /* CRC16 and block headers (k_se_crc<true>) */
+    LINNE_AMD_T_SB_HEADER = 68          /* the finished tracks' stream headers (k_sb_header) */
 };
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
@@ -464,6 +476,40 @@ int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEH
 /* how the last EncodeStreamDevice call of this context went: which 0 / 1 / 2 = its COMPRESS / SILENT / RAW blocks, 3 = the
  * channel-frames whose Rice plan the host settled (a mean in a guard band); -1 for a NULL context or another `which` */
 int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx, int which);
+
+/* ---- many tracks of planar PCM in device memory -> their .lnn streams in device memory, in one call ----
+ * LINNEAmd_EncodeStreamsDevice encodes num_tracks tracks; tracks of different shapes (channels, bits, block size, preset, MS) may be
+ * mixed, and two tracks may read the same PCM.  Every track's `result`, `out_bytes`, new `parcor_state` and bytes
+ * d_out[0, out_bytes) are what LINNEAmd_EncodeStreamDevice(ctx, &header, d_pcm, pcm_stride, g, d_out, capacity, &out_bytes,
+ * &parcor_state) returns and writes for it alone, for any g -- its argument checks (a NULL pointer or a misaligned d_out of one track
+ * is that track's INVALID_ARGUMENT, its out_bytes left as it was), its header codes, its first refused block with that block's code
+ * (out_bytes 0 after a header or block error), INSUFFICIENT_BUFFER with the needed size in out_bytes and nothing written at or beyond
+ * `capacity`; parcor_state is replaced only on OK -- and a failing track does not disturb the others.  Returns LINNE_APIRESULT_OK when
+ * every track is OK, otherwise the result of the lowest-numbered failing track; GetLastError then reads "track <i>: " and the single
+ * call's text.  A HIP error or running out of memory fails the whole call: LINNE_APIRESULT_NG, in every `result` too.  num_tracks == 0
+ * is OK; a NULL ctx, or NULL tracks with num_tracks > 0, INVALID_ARGUMENT; more than 2^31 - 1 frames in one call, NG.
+ * -a / -l come from the context and apply to every track; LINNE_AMD_RICE_GUARD applies as in the single call;
+ * LINNEAmd_GetLastStreamEncodeCount reports the sums over the call.
+ * The tracks of one shape are encoded together: their frames, in the caller's track order, form one list that is cut into passes of
+ * group_frames frames (0 = one pass per shape; a track may span passes); group_frames never changes a byte.  The kernel launches,
+ * memsets, copies and host synchronisations of a pass do not depend on how many tracks it holds, with one exception: the analysis
+ * (LINNEAmd_EncodeFramesDevice) takes at most 16 distinct frame lengths per call, so a pass whose frames have d distinct lengths
+ * takes 1 call when d <= 16 and 1 + ceil((d - 16) / 16) otherwise.  Scratch (kept by the context) is the single call's per frame of a
+ * pass plus 16 bytes per frame and about 100 per track.  The tracks' output buffers must be 4-byte aligned and must not overlap.
+ * Enqueued on the context's stream and synchronous. */
+struct LINNEAmdTrack {
+    struct LINNEHeader header;                 /* as EncodeStreamDevice's header argument */
+    const int32_t *d_pcm; uint64_t pcm_stride; /* channel ch at d_pcm + ch * pcm_stride */
+    uint8_t *d_out; uint64_t capacity;         /* 4-byte aligned; the tracks' buffers do not overlap */
+    uint64_t out_bytes;                        /* out */
+    double parcor_state;                       /* in/out, quirk Q2; 0.0 = a fresh encoder */
+    int32_t result;                            /* out: this track's LINNEApiResult */
+};
+int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks,
+        uint32_t num_tracks, uint32_t group_frames);
+/* how the last EncodeStreamsDevice call of this context went: which 0 = its shape groups, 1 = its passes, 2 = its EncodeFramesDevice
+ * calls; -1 for a NULL context or another `which` */
+int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx, int which);
 
 #ifdef __cplusplus
 }

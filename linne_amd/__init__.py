@@ -50,6 +50,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_SlotPcmWidth", "LINNEAmd_SlotDecodeStreamSubmit", "LINNEAmd_SlotFetchPcm32", "LINNEAmd_RiceDecodeDevice", "LINNEAmd_SlotBitEnd", "LINNEAmd_LastDecodeWholeMode", "LINNEAmd_RiceEmitDevice", "LINNEAmd_PackFramesEmitted", "LINNEAmd_RicePlanDevice", "LINNEAmd_PackFramesPlanned", "LINNEAmd_SlotEncodeSubmit", "LINNEAmd_SlotDecodeSubmit", "LINNEAmd_SlotWait",
     "LINNEAmd_StreamIndexCreate", "LINNEAmd_StreamIndexDestroy", "LINNEAmd_StreamIndexHeader", "LINNEAmd_StreamIndexNumBlocks",
     "LINNEAmd_DecodeStreamDevice", "LINNEAmd_DecodeWindowsDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
+    "LINNEAmd_EncodeStreamsDevice", "LINNEAmd_GetLastStreamBatchCount",
 ]
 
 
@@ -69,6 +70,12 @@ class Window(C.Structure):
     """struct LINNEAmdWindow (include/linne_amd.h)"""
     _fields_ = [("index", C.c_void_p), ("d_stream", C.c_void_p), ("first_sample", C.c_uint64), ("num_samples", C.c_uint64),
                 ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("result", C.c_int32)]
+
+
+class Track(C.Structure):
+    """struct LINNEAmdTrack (include/linne_amd.h)"""
+    _fields_ = [("header", Header), ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("d_out", C.c_void_p), ("capacity", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("parcor_state", C.c_double), ("result", C.c_int32)]
 
 
 def _load():
@@ -138,6 +145,9 @@ def _load():
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     L.LINNEAmd_GetLastStreamEncodeCount.restype = C.c_int64
     L.LINNEAmd_GetLastStreamEncodeCount.argtypes = [C.c_void_p, C.c_int]
+    L.LINNEAmd_EncodeStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Track), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_GetLastStreamBatchCount.restype = C.c_int64
+    L.LINNEAmd_GetLastStreamBatchCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
     L.LINNEAmd_MultiCreate.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.LINNEAmd_MultiDestroy.argtypes = [C.c_void_p]
@@ -162,7 +172,8 @@ def device_count():
 
 
 class LinneAmdError(RuntimeError):
-    """code: the LINNEApiResult of the failing call, where one is known; codes: those of a batch's members (decode_windows)"""
+    """code: the LINNEApiResult of the failing call, where one is known; codes: those of a batch's members (decode_windows,
+    encode_streams)"""
 
     def __init__(self, msg, code=None, codes=None):
         super().__init__(msg)
@@ -467,6 +478,76 @@ class Context:
     def last_stream_encode_count(self, which):
         """the last encode_stream call: 0 / 1 / 2 its COMPRESS / SILENT / RAW blocks, 3 the channel-frames whose Rice plan the host settled"""
         return int(lib.LINNEAmd_GetLastStreamEncodeCount(self.h, int(which)))
+
+    def encode_streams(self, tracks, group_frames=0, parcor_states=None, return_codes=False):
+        """many tracks into their .lnn streams in one call (include/linne_amd.h LINNEAmd_EncodeStreamsDevice).  tracks: a sequence of
+        (pcm, bits, rate, block, preset, ms), pcm as in encode_stream (an int32 CUDA tensor (C, N) with contiguous rows and any row
+        stride, or numpy); shapes may be mixed.  -> a list of 1-D uint8 CUDA tensors, views of one allocation at 4-byte-aligned
+        offsets (None for a track that failed); every stream is what encode_stream gives for its track alone.  Each track gets the
+        default room encode_stream gives it; the tracks that do not fit are encoded once more, together, at their exact sizes.  With
+        parcor_states (a list of floats, the tracks' quirk-Q2 states) -> (streams, new states).  Raises LinneAmdError with .code =
+        the call's result and .codes = the per-track LINNEApiResults when a track fails; with return_codes the codes are appended
+        to the result, and only a failure of the whole call raises.  group_frames bounds the frames of one pass (0: one pass per
+        shape) and never changes a byte"""
+        import torch
+        dev = f"cuda:{self.device}"
+        T = len(tracks)
+        assert parcor_states is None or len(parcor_states) == T
+        arr = (Track * max(T, 1))()
+        keep, rooms = [], []
+        for i, (pcm, bits, rate, block, preset, ms) in enumerate(tracks):
+            if not isinstance(pcm, torch.Tensor):
+                pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int32)).to(dev)
+            assert pcm.dtype == torch.int32 and pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1, \
+                f"track {i}: pcm is an int32 CUDA tensor (C, N) whose rows are contiguous"
+            assert pcm.device.index == self.device, f"track {i}: the PCM is on {pcm.device}, the context on cuda:{self.device}"
+            nch, ns = pcm.shape
+            keep.append(pcm)
+            arr[i].header = Header(1, 2, nch, ns, rate, bits, block, preset, int(bool(ms)))
+            arr[i].d_pcm, arr[i].pcm_stride = pcm.data_ptr(), pcm.stride(0) if nch > 1 else ns
+            rooms.append(2 * nch * ns * ((bits + 7) // 8) + 30)
+
+        def run(which, sizes):
+            """one call over the tracks `which` with sizes[j] bytes of room each -> (result, error text, buffer views)"""
+            offs, at = [], 0
+            for n in sizes:
+                offs.append(at)
+                at += (n + 3) & ~3
+            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
+            sub = (Track * max(len(which), 1))()
+            for j, i in enumerate(which):
+                C.memmove(C.byref(sub[j]), C.byref(arr[i]), C.sizeof(Track))
+                sub[j].d_out, sub[j].capacity, sub[j].out_bytes, sub[j].result = flat.data_ptr() + offs[j], sizes[j], 0, 0
+                sub[j].parcor_state = 0.0 if parcor_states is None else float(parcor_states[i])
+            self._fence()
+            ret = lib.LINNEAmd_EncodeStreamsDevice(self.h, sub, len(which), int(group_frames))
+            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
+            if ret != 0 and not msg.startswith("track "):                # (a failing track's text starts with its number)
+                raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
+            for j, i in enumerate(which):
+                codes[i], states[i], nbytes[i] = int(sub[j].result), float(sub[j].parcor_state), int(sub[j].out_bytes)
+                streams[i] = flat[offs[j]:offs[j] + nbytes[i]] if codes[i] == 0 else None
+            return ret, msg
+
+        codes, states, nbytes, streams = [0] * T, [0.0] * T, [0] * T, [None] * T
+        ret, msg = run(list(range(T)), rooms)
+        again = [i for i in range(T) if codes[i] == 3 and nbytes[i] > rooms[i]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
+        if again:
+            run(again, [nbytes[i] for i in again])
+            bad = [i for i in range(T) if codes[i] != 0]
+            ret = codes[bad[0]] if bad else 0
+            msg = f"track {bad[0]} failed" if bad else ""
+        if ret != 0 and not return_codes:
+            raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, codes)
+        out = (streams,) if parcor_states is None else (streams, states)
+        if return_codes:
+            out += (codes,)
+        return out[0] if len(out) == 1 else out
+
+    def last_stream_batch_count(self, which):
+        """the last encode_streams call (its second one, where tracks were encoded again): 0 its shape groups, 1 its passes, 2 its
+        EncodeFramesDevice calls"""
+        return int(lib.LINNEAmd_GetLastStreamBatchCount(self.h, int(which)))
 
     def encode_frames_host(self, shape, pcm, num_samples=None):
         """numpy int32 [F][C][S] -> numpy (residual, params, stats)"""

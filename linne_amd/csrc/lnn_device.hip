@@ -48,6 +48,7 @@
 #include "lnn_k_stream.h"
 #include "lnn_k_windows.h"
 #include "lnn_k_stream_enc.h"
+#include "lnn_stream_batch.h"
 /* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
@@ -98,7 +99,8 @@ struct LINNEAmdContext {
     void *wdec; uint64_t wdec_cap;      /* DecodeWindowsDevice: fail words, window and block records of one call (its passes' buffers are sdec) */
     void *wstage; uint64_t wstage_cap;  /* pinned: the same lists on the host, uploaded in one copy; the fail words come back into it */
     int64_t senc_count[4];              /* the last EncodeStreamDevice call: COMPRESS, SILENT, RAW blocks, host-settled Rice plans */
-    int span_keep;                      /* EncodeFramesDevice inside EncodeStreamDevice: keep the call's spans and start event */
+    int64_t sbatch_count[3];            /* the last EncodeStreamsDevice call: shape groups, passes, EncodeFramesDevice calls */
+    int span_keep;                      /* EncodeFramesDevice inside EncodeStream(s)Device: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
     LnnKnobs knob;                      /* every form-selecting knob (lnn_forms.h): some read when the context is created, the others at the top of each call */
@@ -2319,7 +2321,7 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.out = d_out; a.base = pos;
         a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
         HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
-        SX_LAUNCH(LINNE_AMD_T_SE_SIZE, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(LINNE_AMD_T_SE_SIZE, k_se_size<false>, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
         SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
         uint64_t pass_bytes = 0;
         uint32_t fail = 0;
@@ -2338,11 +2340,11 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         if (writing && pos + pass_bytes > room) writing = false;
         if (writing) {
             HIPCHK(ctx, hipMemsetAsync(d_out + pos, 0, pass_bytes, ctx->stream));
-            SX_LAUNCH(LINNE_AMD_T_SE_PARAMS, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
-            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SE_RICE, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
-            else SX_LAUNCH(LINNE_AMD_T_SE_RICE, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
-            SX_LAUNCH(LINNE_AMD_T_SE_RAW, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
-            SX_LAUNCH(LINNE_AMD_T_SE_CRC, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SE_PARAMS, k_se_params<false>, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SE_RICE, (k_se_rice<true, false>), dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(LINNE_AMD_T_SE_RICE, (k_se_rice<false, false>), dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SE_RAW, k_se_raw<false>, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(LINNE_AMD_T_SE_CRC, k_se_crc<false>, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
         }
         pos += pass_bytes;
     }
@@ -2397,6 +2399,333 @@ extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
     return ret;
 }
+
+/* ================================================================================================
+ * many tracks -> their streams, in one call (lnn_k_stream_enc.h, lnn_stream_batch.h)
+ * ============================================================================================== */
+static_assert(SB_MAXLEN == LNN_MAXCLS, "lnn_stream_batch.h cuts the rows of a pass by the analysis' limit");
+
+extern "C" int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx, int which)
+{
+    if (!ctx || which < 0 || which > 2) return -1;
+    return ctx->sbatch_count[which];
+}
+
+/* a track of the call on the host: what the single call keeps in locals */
+struct SbHost {
+    int32_t result; char text[160];
+    struct LINNEAmdShape shape;
+    bool live;                          /* it passed its checks and no block of it was refused so far */
+    bool writing; uint64_t pos, room; double state;
+    uint32_t id;                        /* its number in its shape group */
+};
+
+/* the argument and header checks of LINNEAmd_EncodeStreamDevice on one track, with their codes and texts, in its order */
+static int sb_check_track(struct LINNEAmdTrack *t, SbHost *h)
+{
+    char *err = h->text; const size_t cap = sizeof(h->text);
+    const struct LINNEHeader *header = &t->header;
+    err[0] = 0;
+    if (!t->d_pcm || !t->d_out) { snprintf(err, cap, "EncodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if ((uintptr_t)t->d_out & 3u) { snprintf(err, cap, "EncodeStreamDevice: d_out is not 4-byte aligned"); return LNN_INVALID_ARGUMENT; }
+    t->out_bytes = 0;
+    int ret = se_parameter_code(header);
+    if (ret != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: header refused by SetEncodeParameter's checks"); return ret; }
+    {
+        uint8_t hb[LINNE_HEADER_SIZE];
+        ret = (int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE);
+        if (ret != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: header refused by EncodeHeader"); return t->capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : ret; }
+    }
+    h->shape.num_channels = header->num_channels; h->shape.bits_per_sample = header->bits_per_sample; h->shape.num_samples_per_block = header->num_samples_per_block;
+    h->shape.preset = header->preset; h->shape.ch_process_method = (uint32_t)header->ch_process_method;
+    HostShape hs;
+    if ((ret = shape_info(&h->shape, &hs)) != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: a shape the device path does not take"); return ret; }
+    if (h->shape.num_channels > 1u && t->pcm_stride < header->num_samples) { snprintf(err, cap, "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)t->pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+
+/* The tracks `members` (numbers in `tracks`, all of `shape`, all live) through their passes.  LNN_OK: every member has its result in
+ * host[]; anything else fails the whole call. */
+static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHost *host, const std::vector<uint32_t> &members,
+        const struct LINNEAmdShape &shape, uint32_t group_frames)
+{
+    HostShape hs;
+    SX_TRY(shape_info(&shape, &hs));
+    const uint32_t C = shape.num_channels, S = shape.num_samples_per_block, n = (uint32_t)members.size();
+    const uint64_t CS = (uint64_t)C * S;
+    std::vector<uint64_t> samples(n);
+    uint64_t F = 0;
+    for (uint32_t k = 0; k < n; k++) { samples[k] = tracks[members[k]].header.num_samples; F += sb_frames(samples[k], S); host[members[k]].id = k; }
+    uint64_t G = group_frames ? (group_frames < F ? group_frames : F) : F;
+    if (G * C > 0x7FFFFFFFull) G = 0x7FFFFFFFull / C;              /* grid.x of the channel-frame kernels */
+    const uint64_t T = n < G ? n : G;                               /* the tracks of a pass: each has a frame in it */
+    /* scratch of one pass: the single call's, then the tables */
+    uint64_t at = 0;
+    const uint64_t o_frames = at; at = align_up(at + sizeof(int32_t) * CS * G);
+    const uint64_t o_resid = at; at = align_up(at + sizeof(int32_t) * CS * G);
+    const uint64_t o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * G);
+    const uint64_t o_st = at; at = align_up(at + sizeof(double) * LINNE_AMD_STAT_WORDS * C * G);
+    const uint64_t o_plan = at; at = align_up(at + (uint64_t)LINNE_AMD_RICE_PLAN_BYTES * C * G);
+    const uint64_t o_nz = at; at = align_up(at + sizeof(uint32_t) * G);
+    const uint64_t o_cmp = at; at = align_up(at + sizeof(uint2) * C * G);
+    const uint64_t o_types = at; at = align_up(at + G);
+    const uint64_t o_size = at; at = align_up(at + sizeof(uint32_t) * G);
+    const uint64_t o_status = at; at = align_up(at + sizeof(int32_t) * G);
+    const uint64_t o_off = at; at = align_up(at + sizeof(uint64_t) * (G + 1u));
+    const uint64_t o_cfbit = at; at = align_up(at + sizeof(uint64_t) * C * G);
+    const uint64_t o_fail = at; at = align_up(at + sizeof(uint32_t) * (2u + (uint64_t)n));
+    const uint64_t o_tab = at; at = align_up(at + sizeof(SeTables));
+    const uint64_t tables_bytes = align_up(sizeof(SbTrack) * T) + sizeof(SbRow) * G;
+    const uint64_t o_tables = at; at = align_up(at + tables_bytes);             /* SbTrack[T], then SbRow[G] */
+    const uint64_t o_tout = at; at = align_up(at + sizeof(SbTrackOut) * T);
+    const uint64_t o_hdr = at; at = align_up(at + (sizeof(uint8_t *) + 32u) * (uint64_t)n);     /* n pointers, then n * 32 bytes */
+    SX_TRY(ensure_buf(ctx, &ctx->senc, &ctx->senc_cap, at));
+    uint8_t *sd = (uint8_t *)ctx->senc;
+    int32_t *d_frames = (int32_t *)(sd + o_frames), *d_resid = (int32_t *)(sd + o_resid), *d_prm = (int32_t *)(sd + o_prm), *d_status = (int32_t *)(sd + o_status);
+    double *d_st = (double *)(sd + o_st);
+    uint8_t *d_plan = sd + o_plan, *d_types = sd + o_types;
+    uint32_t *d_nz = (uint32_t *)(sd + o_nz), *d_size = (uint32_t *)(sd + o_size), *d_fail = (uint32_t *)(sd + o_fail);
+    uint2 *d_cmp = (uint2 *)(sd + o_cmp);
+    uint64_t *d_off = (uint64_t *)(sd + o_off), *d_cfbit = (uint64_t *)(sd + o_cfbit);
+    SeTables *d_tab = (SeTables *)(sd + o_tab);
+    SbTrack *d_trk = (SbTrack *)(sd + o_tables);
+    SbRow *d_rows = (SbRow *)(sd + o_tables + align_up(sizeof(SbTrack) * T));
+    SbTrackOut *d_tout = (SbTrackOut *)(sd + o_tout);
+    /* host buffers (std::bad_alloc is the caller's to catch): per row, per slot, per track of a pass */
+    std::vector<uint2> h_cmp(C * G);
+    std::vector<double> h_st(LINNE_AMD_STAT_WORDS * C * G), s_st(LINNE_AMD_STAT_WORDS * C * G);
+    std::vector<uint32_t> h_nz(G), h_nsmp(G), s_nsmp(G), h_settle(C * G), h_settle_n(C * G), h_bad(2u + (uint64_t)n);
+    std::vector<uint8_t> s_nz(G), s_types(G), h_types(G), h_tables(tables_bytes), h_plans;
+    std::vector<int32_t> h_res;
+    std::vector<SbTrack> h_trk2(T);                                 /* the second upload of a pass (pos, write) has a buffer of its own */
+    std::vector<SbTrackOut> h_tout(T);
+    {
+        SeTables t;
+        sx_tables(&t.sx);
+        lnn_huff_code_table(t.code, t.len);
+        HIPCHK(ctx, hipMemcpyAsync(d_tab, &t, sizeof(t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * (2u + (uint64_t)n), ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (t lives on this frame) */
+    }
+    ctx->sbatch_count[0]++;
+    SbPlanner planner;
+    sb_planner_init(&planner, samples.data(), n, S);
+    SbPassPlan pp;
+    while (F && sb_next_pass(&planner, G, &pp)) {
+        const uint32_t Fp = (uint32_t)pp.rows.size(), Tp = (uint32_t)pp.segs.size(), CF = Fp * C;
+        ctx->sbatch_count[1]++;
+        /* 0. the tables of the pass, in one copy */
+        SbTrack *h_trk = (SbTrack *)h_tables.data();
+        SbRow *h_rows = (SbRow *)(h_tables.data() + align_up(sizeof(SbTrack) * T));
+        for (uint32_t k = 0; k < Tp; k++) {
+            const SbPlanSeg &sg = pp.segs[k];
+            const struct LINNEAmdTrack &tr = tracks[members[sg.track]];
+            SbTrack &d = h_trk[k];
+            d.pcm = tr.d_pcm; d.stride = tr.pcm_stride; d.total = samples[sg.track]; d.out = tr.d_out; d.pos = host[members[sg.track]].pos;
+            d.slot0 = sg.slot0; d.nslots = sg.nslots; d.write = 0; d.id = sg.track;
+        }
+        for (uint32_t r = 0; r < Fp; r++) {
+            const SbPlanRow &pr = pp.rows[r];
+            h_rows[r].track = pr.seg; h_rows[r].slot = pr.slot; h_rows[r].first = pr.first;
+            h_nsmp[r] = pr.nsmp; s_nsmp[pr.slot] = pr.nsmp;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(sd + o_tables, h_tables.data(), align_up(sizeof(SbTrack) * T) + sizeof(SbRow) * Fp, hipMemcpyHostToDevice, ctx->stream));
+        /* 1. gather */
+        HIPCHK(ctx, hipMemsetAsync(d_nz, 0, sizeof(uint32_t) * Fp, ctx->stream));
+        {
+            SeGatherArgs g; memset(&g, 0, sizeof(g));
+            g.frames = d_frames; g.nonzero = d_nz; g.F = Fp; g.C = C; g.S = S;
+            SX_LAUNCH(LINNE_AMD_T_SB_GATHER, k_sb_gather, dim3(CF), dim3(SE_THREADS), 0, ctx->stream, g, (const SbRow *)d_rows, (const SbTrack *)d_trk);
+        }
+        /* 2. analysis, a call per slice of at most LNN_MAXCLS distinct lengths; the Rice plan of all rows */
+        for (size_t k = 0; k + 1 < pp.slice.size(); k++) {
+            const uint32_t r0 = pp.slice[k], cnt = pp.slice[k + 1] - r0;
+            SX_TRY(LINNEAmd_EncodeFramesDevice(ctx, &shape, d_frames + CS * r0, h_nsmp.data() + r0, cnt, d_resid + CS * r0,
+                    d_prm + (uint64_t)LINNE_AMD_PARAM_WORDS * C * r0, d_st + (uint64_t)LINNE_AMD_STAT_WORDS * C * r0));
+            ctx->sbatch_count[2]++;
+        }
+        SX_TRY(LINNEAmd_RicePlanDevice(ctx, &shape, d_resid, h_nsmp.data(), Fp, d_plan));
+        const uint32_t *d_nsmp = ctx->d_plan_nsmp;                 /* (RicePlanDevice's copy of this pass's lengths, by row) */
+        SX_LAUNCH(LINNE_AMD_T_SE_COMPACT, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
+        /* 3. the host step: per track, in stream order, with the track's own state */
+        HIPCHK(ctx, hipMemcpyAsync(h_cmp.data(), d_cmp, sizeof(uint2) * CF, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_st.data(), d_st, sizeof(double) * LINNE_AMD_STAT_WORDS * CF, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_nz.data(), d_nz, sizeof(uint32_t) * Fp, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t stw = (size_t)LINNE_AMD_STAT_WORDS * C;
+        for (uint32_t r = 0; r < Fp; r++) {
+            const uint32_t slot = pp.rows[r].slot;
+            memcpy(&s_st[stw * slot], &h_st[stw * r], sizeof(double) * stw);
+            s_nz[slot] = h_nz[r] ? 1u : 0u;
+        }
+        for (uint32_t k = 0; k < Tp; k++) {
+            const SbPlanSeg &sg = pp.segs[k];
+            SbHost &th = host[members[sg.track]];
+            if (!th.live) { memset(&s_types[sg.slot0], LNN_BLOCK_SILENT, sg.nslots); continue; }       /* (an 11-byte block nobody writes) */
+            if (lnn_decide_block_types(&shape, &s_nsmp[sg.slot0], sg.nslots, &s_st[stw * sg.slot0], &s_nz[sg.slot0], &s_types[sg.slot0], &th.state) != 0) { snprintf(ctx->err, sizeof(ctx->err), "block types: invalid shape"); return LNN_NG; }
+        }
+        uint32_t nsettle = 0;
+        for (uint32_t r = 0; r < Fp; r++) {
+            const uint8_t type = s_types[pp.rows[r].slot];
+            h_types[r] = type;
+            if (!host[members[pp.segs[pp.rows[r].seg].track]].live) continue;
+            ctx->senc_count[type == LNN_BLOCK_COMPRESS ? 0 : (type == LNN_BLOCK_SILENT ? 1 : 2)]++;
+            if (type != LNN_BLOCK_COMPRESS) continue;
+            for (uint32_t ch = 0; ch < C; ch++) {
+                const uint2 q = h_cmp[r * C + ch];
+                const uint32_t order = q.x & 0xFFu, flag = (q.x >> 8) & 0xFFu;
+                if (flag || order > 10u || (h_nsmp[r] % (1u << order)) != 0u) { h_settle[nsettle] = r * C + ch; h_settle_n[nsettle] = h_nsmp[r]; nsettle++; }
+            }
+        }
+        ctx->senc_count[3] += nsettle;
+        if (nsettle) {
+            if (h_res.size() < (uint64_t)nsettle * S) { h_res.resize((uint64_t)nsettle * S); h_plans.resize((uint64_t)LINNE_AMD_RICE_PLAN_BYTES * nsettle); }
+            for (uint32_t k = 0; k < nsettle; k++)
+                HIPCHK(ctx, hipMemcpyAsync(h_res.data() + (uint64_t)k * S, d_resid + (uint64_t)h_settle[k] * S, sizeof(int32_t) * h_settle_n[k], hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            if (lnn_rice_plan_host(h_res.data(), S, h_settle_n.data(), nsettle, h_plans.data()) != 0) { snprintf(ctx->err, sizeof(ctx->err), "host Rice search failed"); return LNN_NG; }
+            for (uint32_t k = 0; k < nsettle; k++) {
+                const uint8_t *rec = h_plans.data() + (uint64_t)k * LINNE_AMD_RICE_PLAN_BYTES;
+                HIPCHK(ctx, hipMemcpyAsync(d_plan + (uint64_t)h_settle[k] * LINNE_AMD_RICE_PLAN_BYTES, rec, LINNE_AMD_RICE_PLAN_K2 + (1u << rec[0]), hipMemcpyHostToDevice, ctx->stream));
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(d_types, h_types.data(), Fp, hipMemcpyHostToDevice, ctx->stream));
+        /* 4. sizes into slots, offsets over stream order, the tracks' totals and failures in one copy */
+        SeBlockArgs a; memset(&a, 0, sizeof(a));
+        a.types = d_types; a.nsmp = d_nsmp; a.prm = d_prm; a.plan = d_plan; a.resid = d_resid; a.tab = d_tab;
+        a.F = Fp; a.C = C; a.S = S; a.bits = shape.bits_per_sample; a.L = hs.L;
+        for (uint32_t l = 0; l < hs.L; l++) { a.P[l] = hs.P[l]; a.coef_off[l] = hs.coef_off[l]; }
+        a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.rows = d_rows; a.trk = d_trk;
+        a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
+        SX_LAUNCH(LINNE_AMD_T_SB_SIZE, k_se_size<true>, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
+        SX_LAUNCH(LINNE_AMD_T_SB_REDUCE, k_sb_reduce, dim3(Tp), dim3(64), 0, ctx->stream, (const SbTrack *)d_trk, Tp, (const int32_t *)d_status, (const uint64_t *)d_off, d_tout);
+        SX_TRY(sx_fetch(ctx, h_tout.data(), d_tout, sizeof(SbTrackOut) * Tp));
+        /* the host decides per track: a refused block ends it; a track that no longer fits goes on being measured */
+        uint64_t most = 0; bool any = false;
+        for (uint32_t k = 0; k < Tp; k++) {
+            const SbPlanSeg &sg = pp.segs[k];
+            struct LINNEAmdTrack &tr = tracks[members[sg.track]];
+            SbHost &th = host[members[sg.track]];
+            h_trk2[k] = h_trk[k];
+            if (!th.live) continue;
+            const SbTrackOut &o = h_tout[k];
+            if (o.fail != 0xFFFFFFFFu) {
+                snprintf(th.text, sizeof(th.text), "block %llu: %s", (unsigned long long)(sg.frame0 + o.fail),
+                        o.status == LNN_INVALID_FORMAT ? "a RAW block at a width other than 8, 16 or 24 bits" : "longer than the host stitcher's 64 + C * S * 8 bytes");
+                th.live = false; th.result = tr.capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : o.status; tr.out_bytes = 0;
+                continue;
+            }
+            if (th.writing && th.pos + o.bytes > th.room) th.writing = false;
+            if (th.writing) { h_trk2[k].write = 1u; any = true; if (o.bytes > most) most = o.bytes; }
+            th.pos += o.bytes;
+        }
+        /* 5. 6. the writers and the CRC, into the zeroed regions of the tracks that are written */
+        if (any) {
+            const uint64_t xz = (most + SB_ZERO_CHUNK - 1u) / SB_ZERO_CHUNK;
+            if (xz * Tp > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: a pass of %u tracks with up to %llu bytes each: give group_frames", Tp, (unsigned long long)most); return LNN_NG; }
+            HIPCHK(ctx, hipMemcpyAsync(d_trk, h_trk2.data(), sizeof(SbTrack) * Tp, hipMemcpyHostToDevice, ctx->stream));
+            SX_LAUNCH(LINNE_AMD_T_SB_ZERO, k_sb_zero, dim3((uint32_t)(xz * Tp)), dim3(SB_ZERO_THREADS), 0, ctx->stream, (const SbTrack *)d_trk, (const SbTrackOut *)d_tout, (uint32_t)xz);
+            SX_LAUNCH(LINNE_AMD_T_SB_PARAMS, k_se_params<true>, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SB_RICE, (k_se_rice<true, true>), dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(LINNE_AMD_T_SB_RICE, (k_se_rice<false, true>), dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SB_RAW, k_se_raw<true>, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(LINNE_AMD_T_SB_CRC, k_se_crc<true>, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+        }
+    }
+    /* 7. the tracks' ends: does it fit, the length check of the Rice writers, the header */
+    SX_TRY(sx_fetch(ctx, h_bad.data(), d_fail, sizeof(uint32_t) * (2u + (uint64_t)n)));
+    std::vector<uint8_t> h_hdr((sizeof(uint8_t *) + 32u) * (uint64_t)n);
+    uint8_t **h_dst = (uint8_t **)h_hdr.data();
+    uint32_t nh = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        struct LINNEAmdTrack &tr = tracks[members[k]];
+        SbHost &th = host[members[k]];
+        if (!th.live) continue;
+        tr.out_bytes = th.pos;
+        if (!th.writing || th.pos > th.room) {
+            snprintf(th.text, sizeof(th.text), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)th.pos, (unsigned long long)tr.capacity);
+            th.result = LNN_INSUFFICIENT_BUFFER; continue;
+        }
+        if (h_bad[2u + k]) { snprintf(th.text, sizeof(th.text), "a Rice code's length is not its plan's (a wrapped 32-bit length count)"); th.result = LNN_NG; continue; }
+        SX_TRY((int)LINNEEncoder_EncodeHeader(&tr.header, h_hdr.data() + sizeof(uint8_t *) * (uint64_t)n + 32u * (uint64_t)nh, LINNE_HEADER_SIZE));
+        h_dst[nh++] = tr.d_out;
+        th.result = LNN_OK;
+    }
+    if (nh) {
+        /* (the bytes of entry i lie at n pointers + 32 * i, whatever nh is) */
+        HIPCHK(ctx, hipMemcpyAsync(sd + o_hdr, h_hdr.data(), h_hdr.size(), hipMemcpyHostToDevice, ctx->stream));
+        SX_LAUNCH(LINNE_AMD_T_SB_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hdr), (const uint8_t *)(sd + o_hdr + sizeof(uint8_t *) * (uint64_t)n), nh);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (h_hdr lives on this frame) */
+    }
+    return LNN_OK;
+}
+
+static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames, std::vector<SbHost> &host)
+{
+    struct Group { struct LINNEAmdShape shape; std::vector<uint32_t> members; };
+    std::vector<Group> groups;
+    host.resize(num_tracks);
+    uint64_t frames = 0;
+    for (uint32_t i = 0; i < num_tracks; i++) {
+        SbHost &h = host[i];
+        memset(&h, 0, sizeof(h));
+        h.result = sb_check_track(&tracks[i], &h);
+        if (h.result != LNN_OK) continue;
+        h.live = true; h.pos = LINNE_HEADER_SIZE; h.state = tracks[i].parcor_state;
+        h.room = tracks[i].capacity < 0xFFFFFFFFull ? tracks[i].capacity : 0xFFFFFFFFull;     /* EncodeWhole's buffer size is a uint32 */
+        h.writing = tracks[i].capacity >= LINNE_HEADER_SIZE;
+        frames += sb_frames(tracks[i].header.num_samples, h.shape.num_samples_per_block);
+        size_t g = 0;
+        while (g < groups.size() && memcmp(&groups[g].shape, &h.shape, sizeof(h.shape)) != 0) g++;
+        if (g == groups.size()) { groups.emplace_back(); groups[g].shape = h.shape; }
+        groups[g].members.push_back(i);
+    }
+    if (frames > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: %llu frames in one call: too many", (unsigned long long)frames); return LNN_NG; }
+    if (groups.empty()) return LNN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob, as in the single call */
+    ctx->nspans = 0; ctx->span_keep = 1;
+    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
+    int ret = LNN_OK;
+    for (size_t g = 0; ret == LNN_OK && g < groups.size(); g++) ret = sb_group_run(ctx, tracks, host.data(), groups[g].members, groups[g].shape, group_frames);
+    if (ret != LNN_OK && !ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: a pass failed with %d", ret);
+    return ret == LNN_OK ? LNN_OK : LNN_NG;
+}
+
+extern "C" int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    for (int i = 0; i < 4; i++) ctx->senc_count[i] = 0;
+    for (int i = 0; i < 3; i++) ctx->sbatch_count[i] = 0;
+    if (num_tracks == 0) return LNN_OK;
+    if (!tracks) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    std::vector<SbHost> host;
+    int ret;
+    try { ret = sb_run(ctx, tracks, num_tracks, group_frames, host); }
+    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    const bool began = ctx->span_keep != 0;
+    ctx->span_keep = 0; ctx->rice_guard = 0.0;
+    if (began && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    /* (whatever was enqueued is waited for: it reads the context's buffers) */
+    if (began && hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
+    if (ret != LNN_OK) {
+        for (uint32_t i = 0; i < num_tracks; i++) tracks[i].result = LNN_NG;
+        return LNN_NG;
+    }
+    /* the tracks' results, then the call's: the lowest-numbered failing track's code, its text behind its number */
+    int first = -1;
+    for (uint32_t i = 0; i < num_tracks; i++) {
+        tracks[i].result = host[i].result;
+        if (host[i].result == LNN_OK) tracks[i].parcor_state = host[i].state;
+        else if (first < 0) first = (int)i;
+    }
+    if (first < 0) return LNN_OK;
+    snprintf(ctx->err, sizeof(ctx->err), "track %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    return host[first].result;
+}
+
 
 /* ------------------------------------------------------------------------------------------------
  * test infrastructure (like lnn_preset_info: exported, not in include/): what the rules of lnn_forms.h say for a call, without a GPU

@@ -19,6 +19,22 @@
  * rule).  Byte stores (RAW payloads, block headers) go to bytes no other writer of the same launch touches: a RAW payload shares
  * no word with any code (11 header bytes lie between blocks), and the header bytes, whose words the codes of the block before and
  * after may share, are written by k_se_crc, a launch of its own after every writer of the pass.
+ *
+ * Many tracks in one call (LINNEAmd_EncodeStreamsDevice; DESIGN.md section 5, "Encoding many tracks in one call").  The rows of a
+ * pass are frames of several tracks, full frames first, the ragged ones sorted by length behind them; a per-row table (SbRow: the
+ * track, the row's slot in stream order, the frame's first sample) and a per-track table (SbTrack) connect rows to streams.  The
+ * analysis, the Rice plan and every k_se_* kernel work per row as above; sizes, statuses and offsets are indexed by SLOT, so that
+ * the scan runs over stream order, and the writers (the <true> instantiations) place a row at
+ * track.out + track.pos + (off[slot] - off[track.slot0]) and skip the rows of a track that is not written.  Beside them:
+ *   k_sb_gather    k_se_gather with each row's source read from the tables
+ *   k_sb_reduce    a wave per track of the pass: its bytes, its lowest failing block and that block's status (one copy to the host)
+ *   k_sb_zero      zeroes exactly [pos, pos + bytes) of every written track: whole words where all four bytes are the region's,
+ *                  byte stores at its edges
+ *   k_sb_header    the 30 header bytes of every finished track, from an uploaded table, by byte stores
+ * The shared-word rule holds unchanged inside a track.  Across tracks it holds because the tracks' buffers are 4-byte aligned and
+ * do not overlap: a 32-bit word belongs to one track only, and the one word two launches of a track may both touch by bytes (the
+ * edge of a pass's region, the word holding header bytes 28-29 and stream bytes 30-31) is touched by launches that follow each
+ * other on the stream.
  */
 #ifndef LNN_K_STREAM_ENC_H_INCLUDED
 #define LNN_K_STREAM_ENC_H_INCLUDED
@@ -31,6 +47,16 @@ struct SeTables {
     uint32_t code[256];                 /* code word of each coefficient symbol (lnn_entropy.c huff_walk), its low len[sym] bits */
     uint8_t len[256];
 };
+
+/* the tables of a many-track pass */
+struct SbRow { uint32_t track, slot; uint64_t first; };        /* index into the pass's SbTrack table; slot in stream order; the frame's first sample in its track */
+struct SbTrack {
+    const int32_t *pcm; uint64_t stride, total;                 /* channel ch at pcm + ch * stride; samples per channel */
+    uint8_t *out; uint64_t pos;                                 /* the track's stream and the byte at which this pass's blocks start */
+    uint32_t slot0, nslots;                                     /* its slots in this pass: [slot0, slot0 + nslots) */
+    uint32_t write, id;                                         /* write 0: the track is not written (it failed, or does not fit); id: its number in its shape group */
+};
+struct SbTrackOut { uint64_t bytes; uint32_t fail; int32_t status; };  /* of a track in a pass: bytes; lowest failing slot - slot0 (~0: none), its status */
 
 struct SeGatherArgs {
     const int32_t *pcm; uint64_t stride;        /* channel ch at pcm + ch * stride */
@@ -46,6 +72,24 @@ __global__ __launch_bounds__(SE_THREADS) void k_se_gather(SeGatherArgs a)
     const uint64_t s0 = a.first + (uint64_t)f * a.S;
     const uint32_t n = (a.total - s0 < a.S) ? (uint32_t)(a.total - s0) : a.S;
     const int32_t *src = a.pcm + (uint64_t)ch * a.stride + s0;
+    int32_t *dst = a.frames + (uint64_t)cf * a.S;
+    int any = 0;
+    for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
+        const int32_t v = (s < n) ? src[s] : 0;
+        dst[s] = v;
+        any |= (v != 0);
+    }
+    if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&a.nonzero[f], 1u);
+}
+
+/* the same for the rows of many tracks (a.pcm, a.stride, a.first, a.total are not used) */
+__global__ __launch_bounds__(SE_THREADS) void k_sb_gather(SeGatherArgs a, const SbRow *rows, const SbTrack *trk)
+{
+    const uint32_t cf = blockIdx.x, f = cf / a.C, ch = cf - f * a.C;
+    const SbRow r = rows[f];
+    const SbTrack &t = trk[r.track];
+    const uint32_t n = (t.total - r.first < a.S) ? (uint32_t)(t.total - r.first) : a.S;
+    const int32_t *src = t.pcm + (uint64_t)ch * t.stride + r.first;
     int32_t *dst = a.frames + (uint64_t)cf * a.S;
     int any = 0;
     for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
@@ -79,7 +123,18 @@ struct SeBlockArgs {
     const uint64_t *off;                /* [F + 1] offsets of the blocks from `base` (k_sx_scan) */
     uint8_t *out; uint64_t base;        /* the stream and the pass's first byte in it */
     uint32_t xch;                       /* k_se_raw: workgroups per block */
+    const SbRow *rows; const SbTrack *trk;      /* the <true> instantiations (many tracks): size, status and off are indexed by slot, out / base are not used */
 };
+
+/* where row f's block goes: the stream, the block's first byte in it, the row's slot; false: the row's track is not written */
+template <bool TRACKS> __device__ __forceinline__ bool se_where(const SeBlockArgs &a, uint32_t f, uint8_t *&out, uint64_t &p, uint32_t &slot)
+{
+    if (!TRACKS) { out = a.out; p = a.base + a.off[f]; slot = f; return true; }
+    const SbRow r = a.rows[f];
+    const SbTrack &t = a.trk[r.track];
+    out = t.out; p = t.pos + (a.off[r.slot] - a.off[t.slot0]); slot = r.slot;
+    return t.write != 0u;
+}
 
 /* the parameter bits of one channel-frame's record, as pack_block writes them (lnn_entropy.c) */
 __device__ __forceinline__ uint64_t se_param_bits(const SeBlockArgs &a, const int32_t *rec)
@@ -94,7 +149,7 @@ __device__ __forceinline__ uint64_t se_param_bits(const SeBlockArgs &a, const in
 
 /* a lane per block: its size, the start of every channel's code, the host stitcher's per-block errors (lnn_entropy.c pack_block:
  * a RAW block at a width other than 8, 16 or 24 bits; a block over its 64 + C * S * 8 bytes; a size field over 32 bits) */
-__global__ __launch_bounds__(SE_THREADS) void k_se_size(SeBlockArgs a)
+template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_size(SeBlockArgs a)
 {
     const uint32_t f = blockIdx.x * SE_THREADS + threadIdx.x;
     if (f >= a.F) return;
@@ -116,13 +171,14 @@ __global__ __launch_bounds__(SE_THREADS) void k_se_size(SeBlockArgs a)
         bytes = (at + 7u) >> 3;
         if (bytes > 64u + (uint64_t)a.C * a.S * 8u || bytes - 11u + 5u > 0xFFFFFFFFull) st = LNN_INSUFFICIENT_BUFFER;
     }
-    a.status[f] = st;
-    a.size[f] = (st == LNN_OK) ? (uint32_t)bytes : 0u;
-    if (st != LNN_OK) atomicMin(&a.fail[0], f);
+    const uint32_t slot = TRACKS ? a.rows[f].slot : f;
+    a.status[slot] = st;
+    a.size[slot] = (st == LNN_OK) ? (uint32_t)bytes : 0u;
+    if (!TRACKS && st != LNN_OK) atomicMin(&a.fail[0], f);            /* (many tracks: k_sb_reduce finds each track's) */
 }
 
 /* a lane per COMPRESS block: the parameter bits (linne_encoder.c:698-735) from bit 88 of the block on */
-__global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
+template <bool TRACKS> __global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
 {
     __shared__ uint32_t code[256];
     __shared__ uint8_t len[256];
@@ -130,8 +186,10 @@ __global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
     __syncthreads();
     const uint32_t f = blockIdx.x * 64u + threadIdx.x;
     if (f >= a.F || a.types[f] != SX_COMPRESS) return;
-    const uint64_t start = (a.base + a.off[f]) * 8u + 88u;
-    RiceBW bw; bw.dst = (uint32_t *)a.out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
+    uint8_t *out; uint64_t p; uint32_t slot;
+    if (!se_where<TRACKS>(a, f, out, p, slot)) return;
+    const uint64_t start = p * 8u + 88u;
+    RiceBW bw; bw.dst = (uint32_t *)out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
     auto put = [&](uint32_t v, uint32_t nb) { if (nb) bw.put(v & (0xFFFFFFFFu >> (32u - nb)), nb); };
     const int32_t *base = a.prm + (uint64_t)f * a.C * LINNE_AMD_PARAM_WORDS;
     for (uint32_t ch = 0; ch < a.C; ch++) {
@@ -153,7 +211,7 @@ __global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
  * channel's bit in the stream.  The code's length must be its plan's (the block's size was computed from it): a channel whose code
  * would come out longer or shorter writes nothing and raises fail[1] (the call then fails; only a uint32 wrap-around of the
  * reference's length count could do it). */
-template <bool LDS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(SeBlockArgs a)
+template <bool LDS, bool TRACKS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(SeBlockArgs a)
 {
     extern __shared__ uint32_t zbuf[];
     __shared__ uint8_t kk[1024];
@@ -161,6 +219,8 @@ template <bool LDS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(S
     const uint32_t cf = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t f = cf / a.C;
     if (a.types[f] != SX_COMPRESS) return;                    /* block-uniform */
+    uint8_t *out; uint64_t p; uint32_t slot;
+    if (!se_where<TRACKS>(a, f, out, p, slot)) return;        /* block-uniform */
     const uint8_t *rec = a.plan + (uint64_t)cf * LINNE_AMD_RICE_PLAN_BYTES;
     const uint32_t nbits = *(const uint32_t *)(rec + LINNE_AMD_RICE_PLAN_NBITS);
     const uint32_t n = a.nsmp[f], best = rec[0], ns = n >> best, parts = 1u << best;
@@ -189,10 +249,10 @@ template <bool LDS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(S
     __syncthreads();
     uint64_t start = incl - mybits, total = 0;
     for (uint32_t w = 0; w < REMIT_THREADS / 64; w++) { if (w < wave) start += wsum[w]; total += wsum[w]; }
-    if (total != nbits) { if (tid == 0) atomicOr(&a.fail[1], 1u); return; }          /* block-uniform */
+    if (total != nbits) { if (tid == 0) atomicOr(TRACKS ? &a.fail[2u + a.trk[a.rows[f].track].id] : &a.fail[1], 1u); return; }          /* block-uniform; many tracks: a word per track of the shape group */
     if (s0 >= s1) return;
-    start += (a.base + a.off[f]) * 8u + a.cfbit[cf];
-    RiceBW bw; bw.dst = (uint32_t *)a.out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
+    start += p * 8u + a.cfbit[cf];
+    RiceBW bw; bw.dst = (uint32_t *)out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
     {
         uint32_t part = ns ? s0 / ns : 0, loc = ns ? s0 - part * ns : 0;
         for (uint32_t s = s0; s < s1; s++) {
@@ -219,12 +279,14 @@ template <bool LDS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(S
 }
 
 /* xch workgroups per block: the samples of RAW blocks, zig-zagged, big-endian, channels interleaved; `pcm` is the pass's [F][C][S] */
-__global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int32_t *pcm)
+template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int32_t *pcm)
 {
     const uint32_t f = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
     if (a.types[f] != SX_RAW) return;
+    uint8_t *out; uint64_t p; uint32_t slot;
+    if (!se_where<TRACKS>(a, f, out, p, slot)) return;
     const uint32_t n = a.nsmp[f], w = a.bits >> 3;
-    uint8_t *dst = a.out + a.base + a.off[f] + 11u;
+    uint8_t *dst = out + p + 11u;
     for (uint32_t s = x * SE_THREADS + threadIdx.x; s < n; s += a.xch * SE_THREADS)
         for (uint32_t ch = 0; ch < a.C; ch++) {
             const uint32_t u = se_zz(pcm[((uint64_t)f * a.C + ch) * a.S + s]);
@@ -236,7 +298,7 @@ __global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int3
 /* A wave per block (four per workgroup), after every other writer of the pass: the CRC16 over [p + 8, p + 6 + size) -- the type and
  * sample count, which this launch writes, taken from registers, the payload from memory -- from lane partials shifted by the bytes
  * behind them (k_sx_check), then the 11 header bytes: FF FF, size - 6, CRC, type, n (linne_encoder.c:806-855). */
-__global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
+template <bool TRACKS> __global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
 {
     __shared__ uint16_t crc_t[256];
     __shared__ uint16_t shift_t[SX_CRC_LEVELS][16];
@@ -245,12 +307,13 @@ __global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
     __syncthreads();
     const uint32_t f = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (f >= a.F) return;
-    const uint64_t p = a.base + a.off[f];
-    const uint32_t size = a.size[f], type = a.types[f], n = a.nsmp[f];
+    uint8_t *out; uint64_t p; uint32_t slot;
+    if (!se_where<TRACKS>(a, f, out, p, slot)) return;        /* wave-uniform */
+    const uint32_t size = a.size[slot], type = a.types[f], n = a.nsmp[f];
     const uint32_t h0 = type & 0xFFu, h1 = (n >> 8) & 0xFFu, h2 = n & 0xFFu;
     const uint64_t len = (uint64_t)size - 8u;                      /* 3 header bytes + the payload */
     const uint64_t chunk = (len + 63u) >> 6, s = (uint64_t)lane * chunk, e = (s + chunk < len) ? s + chunk : len;
-    const uint8_t *q = a.out + p + 8u;
+    const uint8_t *q = out + p + 8u;
     uint32_t crc = 0;
     if (s < len) {
         uint64_t i = s;
@@ -268,12 +331,61 @@ __global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
     }
     for (uint32_t m = 32; m >= 1u; m >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, (int)m, 64);
     if (lane != 0u) return;
-    uint8_t *h = a.out + p;
+    uint8_t *h = out + p;
     const uint32_t field = size - 6u;
     h[0] = 0xFFu; h[1] = 0xFFu;
     h[2] = (uint8_t)(field >> 24); h[3] = (uint8_t)(field >> 16); h[4] = (uint8_t)(field >> 8); h[5] = (uint8_t)field;
     h[6] = (uint8_t)(crc >> 8); h[7] = (uint8_t)crc;
     h[8] = (uint8_t)h0; h[9] = (uint8_t)h1; h[10] = (uint8_t)h2;
+}
+
+/* ---- many tracks ---- */
+#define SB_ZERO_THREADS 256u
+#define SB_ZERO_CHUNK 65536u            /* bytes a workgroup of k_sb_zero clears */
+
+/* A wave per track of the pass, behind k_se_size<true> and the scan: the bytes of the track's blocks, the lowest slot whose block
+ * the host stitcher refuses (relative to the track's first slot) and that block's status. */
+__global__ __launch_bounds__(64) void k_sb_reduce(const SbTrack *trk, uint32_t ntrk, const int32_t *status, const uint64_t *off, SbTrackOut *out)
+{
+    const uint32_t t = blockIdx.x, lane = threadIdx.x;
+    if (t >= ntrk) return;
+    const uint32_t s0 = trk[t].slot0, n = trk[t].nslots;
+    uint32_t low = 0xFFFFFFFFu;
+    for (uint32_t i = lane; i < n; i += 64u) if (status[s0 + i] != LNN_OK) { low = i; break; }        /* (a lane's slots ascend) */
+    for (uint32_t m = 32; m >= 1u; m >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)low, (int)m, 64); low = o < low ? o : low; }
+    if (lane != 0u) return;
+    SbTrackOut r;
+    r.bytes = off[s0 + n] - off[s0]; r.fail = low; r.status = (low != 0xFFFFFFFFu) ? status[s0 + low] : LNN_OK;
+    out[t] = r;
+}
+
+/* xz workgroups per track of the pass; workgroup x of a written track clears bytes [x * SB_ZERO_CHUNK, (x + 1) * SB_ZERO_CHUNK)
+ * of the track's region [pos, pos + bytes): 32-bit stores to the words that lie wholly inside the region (the track's buffer is
+ * 4-byte aligned, so these are words of this track alone), byte stores to the up to three bytes at either edge. */
+__global__ __launch_bounds__(SB_ZERO_THREADS) void k_sb_zero(const SbTrack *trk, const SbTrackOut *res, uint32_t xz)
+{
+    const uint32_t t = blockIdx.x / xz, x = blockIdx.x - t * xz;
+    if (!trk[t].write) return;
+    const uint64_t lo = trk[t].pos, hi = lo + res[t].bytes;
+    const uint64_t c0 = lo + (uint64_t)x * SB_ZERO_CHUNK;
+    if (c0 >= hi) return;
+    const uint64_t c1 = (hi - c0 > SB_ZERO_CHUNK) ? c0 + SB_ZERO_CHUNK : hi;      /* this workgroup's bytes [c0, c1) */
+    uint8_t *out = trk[t].out;
+    uint64_t w0 = (c0 + 3u) & ~(uint64_t)3u, w1 = c1 & ~(uint64_t)3u;           /* whole words [w0, w1) */
+    if (w0 > w1) w0 = w1 = c1;                                                  /* fewer than four bytes inside one word */
+    if (threadIdx.x < 3u && c0 + threadIdx.x < (w0 < c1 ? w0 : c1)) out[c0 + threadIdx.x] = 0u;
+    if (threadIdx.x < 3u && w1 + threadIdx.x < c1 && w1 >= w0) out[w1 + threadIdx.x] = 0u;
+    uint32_t *w = (uint32_t *)(out + w0);
+    const uint64_t nw = (w1 - w0) >> 2;
+    for (uint64_t i = threadIdx.x; i < nw; i += SB_ZERO_THREADS) w[i] = 0u;
+}
+
+/* the stream headers of the finished tracks: entry i is 30 bytes of `bytes` (stride 32) for the stream dst[i]; a thread per byte */
+__global__ __launch_bounds__(256) void k_sb_header(uint8_t *const *dst, const uint8_t *bytes, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, t = i >> 5, b = i & 31u;
+    if (t >= n || b >= 30u) return;
+    dst[t][b] = bytes[(uint64_t)t * 32u + b];
 }
 
 #endif
