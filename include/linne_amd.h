@@ -511,6 +511,40 @@ int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTra
  * calls; -1 for a NULL context or another `which` */
 int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx, int which);
 
+/* ---- resident streams from and into int16, packed 24-bit and float PCM, planar or interleaved ----
+ * A struct LINNEAmdPcmLayout names how the caller's PCM lies in device memory: sample i of channel ch is element
+ * ch * channel_stride + i * sample_stride from the base pointer, the strides counted in elements of the format (an S24 element is
+ * 3 bytes, little-endian).  Planar is (stride, 1), interleaved is (1, C); padded variants of both are legal.  With a layout the
+ * track's or window's d_pcm (the single call's d_pcm) is that base pointer, whatever its declared type, and pcm_stride is ignored.
+ * The three calls below are the calls above with a layout per track / window (the single call: one); `layout(s) == NULL` is
+ * exactly the call above, which is that case of the same code.
+ *   encode  the samples are sign-extended from the format and taken as right-justified values: result, out_bytes, parcor_state and
+ *           bytes are those of the call above on an int32 planar copy of the same values (header.bits_per_sample is independent of
+ *           the format).  LINNE_AMD_PCM_F32, or an unknown format, is that track's INVALID_ARGUMENT.
+ *   decode  every window's result and samples are those of LINNEAmd_DecodeStreamDevice, converted: S32 as is; S16 and S24
+ *           saturated to the format's range, `saturated` = 1 when some sample of the window lay outside it; F32 =
+ *           (float)v * 2^-(bits_per_sample - 1), the conversion rounding to nearest-even (exact up to 25 bits).  `saturated` is 0
+ *           otherwise and left untouched for a failing window, whose memory is still never written.
+ * Checked per track / window (INVALID_ARGUMENT for it alone, out_bytes left as it was): the base is aligned to the element (2 bytes
+ * for S16, 4 for S32 and F32, any for S24), and for C > 1 channels of n samples the index map is injective in one of two ways:
+ * sample_stride >= 1 && channel_stride >= n * sample_stride, or channel_stride >= 1 && sample_stride >= C * channel_stride (C == 1:
+ * sample_stride >= 1).  No load or store touches a byte outside the elements the layout names; an element is written by plain
+ * stores that touch no byte of another element's owner.  Tracks and windows of one stream shape stay in one shape group and one
+ * pass whatever their layouts: the launches, copies and synchronisations of a pass are those of the int32 planar call. */
+enum { LINNE_AMD_PCM_S32 = 0, LINNE_AMD_PCM_S16 = 1, LINNE_AMD_PCM_S24 = 2 /* packed 3-byte little-endian */, LINNE_AMD_PCM_F32 = 3 /* decode only */ };
+struct LINNEAmdPcmLayout {
+    uint32_t format;
+    uint32_t saturated;                 /* out, decode only: 1 if some sample of the window lay outside the format's range */
+    uint64_t channel_stride, sample_stride;   /* in elements of the format (an S24 element is 3 bytes) */
+};
+int LINNEAmd_EncodeStreamDeviceLayout(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const void *d_pcm, const struct LINNEAmdPcmLayout *layout, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state);
+int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks,
+        const struct LINNEAmdPcmLayout *layouts /* [num_tracks] */, uint32_t num_tracks, uint32_t group_frames);
+int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        struct LINNEAmdPcmLayout *layouts /* [num_windows], in/out */, uint32_t num_windows, uint32_t group_frames);
+
 #ifdef __cplusplus
 }
 #endif

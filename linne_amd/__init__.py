@@ -51,7 +51,9 @@ AMD_SYMBOLS = [
     "LINNEAmd_StreamIndexCreate", "LINNEAmd_StreamIndexDestroy", "LINNEAmd_StreamIndexHeader", "LINNEAmd_StreamIndexNumBlocks",
     "LINNEAmd_DecodeStreamDevice", "LINNEAmd_DecodeWindowsDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
     "LINNEAmd_EncodeStreamsDevice", "LINNEAmd_GetLastStreamBatchCount",
+    "LINNEAmd_EncodeStreamDeviceLayout", "LINNEAmd_EncodeStreamsDeviceLayout", "LINNEAmd_DecodeWindowsDeviceLayout",
 ]
+PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
 
 class Shape(C.Structure):
@@ -76,6 +78,11 @@ class Track(C.Structure):
     """struct LINNEAmdTrack (include/linne_amd.h)"""
     _fields_ = [("header", Header), ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("d_out", C.c_void_p), ("capacity", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("parcor_state", C.c_double), ("result", C.c_int32)]
+
+
+class PcmLayout(C.Structure):
+    """struct LINNEAmdPcmLayout (include/linne_amd.h)"""
+    _fields_ = [("format", C.c_uint32), ("saturated", C.c_uint32), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64)]
 
 
 def _load():
@@ -146,6 +153,10 @@ def _load():
     L.LINNEAmd_GetLastStreamEncodeCount.restype = C.c_int64
     L.LINNEAmd_GetLastStreamEncodeCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_EncodeStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Track), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_EncodeStreamDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Header), C.c_void_p, C.POINTER(PcmLayout), C.c_uint32, C.c_void_p, C.c_uint64,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    L.LINNEAmd_EncodeStreamsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Track), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_DecodeWindowsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastStreamBatchCount.restype = C.c_int64
     L.LINNEAmd_GetLastStreamBatchCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
@@ -365,16 +376,24 @@ class Context:
         header = {k: int(getattr(hd, k)) for k, _ in Header._fields_}
         return StreamIndex(h, header, int(lib.LINNEAmd_StreamIndexNumBlocks(h)), t.numel())
 
-    def decode_stream(self, data, first_sample=0, num_samples=None, index=None):
+    def decode_stream(self, data, first_sample=0, num_samples=None, index=None, dtype=None, channels_last=False, s24=False,
+                      return_saturated=False):
         """samples [first_sample, first_sample + num_samples) of a .lnn stream in device memory -> int32 CUDA tensor (C, n), decoded
         on the device (include/linne_amd.h LINNEAmd_DecodeStreamDevice states the result contract).  Without an index a temporary
-        one is built.  Raises LinneAmdError with .code = the LINNEApiResult"""
+        one is built.  Raises LinneAmdError with .code = the LINNEApiResult.  dtype (torch.int32, int16 or float32), channels_last
+        ((n, C)), s24 (packed 3-byte samples: uint8 (..., 3)) and return_saturated (-> (pcm, flag)) are decode_windows' for its one
+        window"""
         import torch
         t = self._stream_bytes(data)
         own = index is None
         if own:
             index = self.index_stream(t)
         try:
+            if dtype not in (None, torch.int32) or channels_last or s24 or return_saturated:
+                assert index.nbytes == t.numel(), "the index was built for a stream of another length"
+                r = self.decode_windows([(t, index, first_sample, num_samples)], dtype=dtype, channels_last=channels_last, s24=s24,
+                                        return_saturated=return_saturated)
+                return (r[0][0], r[1][0]) if return_saturated else r[0]
             assert index.nbytes == t.numel(), "the index was built for a stream of another length"
             total = index.header["num_samples"]
             n = total - int(first_sample) if num_samples is None else int(num_samples)
@@ -390,7 +409,8 @@ class Context:
             if own:
                 index.close()
 
-    def decode_windows(self, windows, out=None, group_frames=0, return_codes=False):
+    def decode_windows(self, windows, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False, s24=False,
+                       return_saturated=False):
         """many sample windows of resident .lnn streams in one call (include/linne_amd.h LINNEAmd_DecodeWindowsDevice).  windows: a
         sequence of (stream, index, first_sample, num_samples): a 1-D uint8 CUDA tensor, its StreamIndex, and the range (num_samples
         None: to the stream's end).  Without `out` -> a list of int32 CUDA tensors (C_w, n_w), views of one allocation; with `out`, an
@@ -398,7 +418,11 @@ class Context:
         (the form of a training batch).  Every window's PCM is what decode_stream gives for it alone; a failing window's is not
         written.  Raises LinneAmdError with .code = the call's result and .codes = the per-window LINNEApiResults when a window
         fails; with return_codes -> (pcm, codes), and only a failure of the whole call raises.  group_frames bounds the COMPRESS
-        blocks decoded per pass (0: one pass per stream shape) and never changes the result"""
+        blocks decoded per pass (0: one pass per stream shape) and never changes the result.
+        Other sample formats (LINNEAmd_DecodeWindowsDeviceLayout): dtype torch.int16 (saturating), torch.float32 (v * 2^-(bits - 1))
+        or torch.int32 (the default); s24=True gives packed 3-byte little-endian samples (saturating) as uint8 tensors with a trailing
+        dimension of 3; channels_last=True gives (n_w, C_w) windows, and says that `out` is (W, n, C).  `out` then has that dtype and
+        any strides.  return_saturated appends the list of the windows' flags "a sample was clipped" to the result"""
         import torch
         W = len(windows)
         arr = (Window * max(W, 1))()
@@ -413,33 +437,78 @@ class Context:
             arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
             arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
         dev = f"cuda:{self.device}"
+        if s24:
+            assert dtype in (None, torch.uint8), "s24 samples are uint8 triples"
+            fmt, tdtype, esize = PCM_S24, torch.uint8, 3
+        else:
+            tdtype = torch.int32 if dtype is None else dtype
+            assert tdtype in (torch.int32, torch.int16, torch.float32), "dtype is torch.int32, torch.int16 or torch.float32"
+            fmt, esize = {torch.int32: (PCM_S32, 4), torch.int16: (PCM_S16, 2), torch.float32: (PCM_F32, 4)}[tdtype]
+        plain = fmt == PCM_S32 and not channels_last and not return_saturated and (out is None or out.dim() != 3 or out.stride(2) == 1 or out.shape[2] <= 1)
+        lays = (PcmLayout * max(W, 1))()
+        cdim, sdim = (2, 1) if channels_last else (1, 2)
         if out is not None:
-            assert out.dtype == torch.int32 and out.is_cuda and out.dim() == 3 and out.shape[0] == W and (out.stride(2) == 1 or out.shape[2] <= 1), \
-                "out is an int32 CUDA tensor (W, C, n), contiguous in its last dimension"
+            if plain:
+                assert out.dtype == torch.int32 and out.is_cuda and out.dim() == 3 and out.shape[0] == W and (out.stride(2) == 1 or out.shape[2] <= 1), \
+                    "out is an int32 CUDA tensor (W, C, n), contiguous in its last dimension"
+            else:
+                assert out.dtype == tdtype and out.is_cuda and out.dim() == (4 if s24 else 3) and out.shape[0] == W, \
+                    f"out is a {tdtype} CUDA tensor (W, C, n) or, channels_last, (W, n, C)" + (" with a trailing dimension of 3" if s24 else "")
+                assert not s24 or (out.shape[3] == 3 and out.stride(3) == 1 and all(out.stride(d) % 3 == 0 for d in range(3))), \
+                    "the three bytes of an s24 sample are contiguous, and samples lie whole samples apart"
             assert out.device.index == self.device, f"out is on {out.device}, the context on cuda:{self.device}"
+            unit = 3 if s24 else 1
             for i, (c, n) in enumerate(shapes):
-                assert (c, n) == (out.shape[1], out.shape[2]), f"window {i} is {(c, n)}, out holds {tuple(out.shape[1:])} per window"
-                arr[i].d_pcm, arr[i].pcm_stride = out.data_ptr() + 4 * i * out.stride(0), out.stride(1) if c > 1 else n
+                assert (c, n) == (out.shape[cdim], out.shape[sdim]), f"window {i} is {(c, n)}, out holds {tuple(out.shape[1:])} per window"
+                arr[i].d_pcm, arr[i].pcm_stride = out.data_ptr() + out.element_size() * i * out.stride(0), out.stride(1) if c > 1 else n
+                lays[i].format, lays[i].channel_stride = fmt, out.stride(cdim) // unit if c > 1 else 0
+                lays[i].sample_stride = out.stride(sdim) // unit if n > 1 else 1
             pcm = out
         else:
-            flat = torch.empty(sum(c * n for c, n in shapes), dtype=torch.int32, device=dev)
+            flat = torch.empty(sum(c * n for c, n in shapes) * (3 if s24 else 1), dtype=tdtype, device=dev)
             pcm, at = [], 0
             for i, (c, n) in enumerate(shapes):
-                v = flat[at:at + c * n].view(c, n)
-                at += c * n
+                v = flat[at:at + c * n * (3 if s24 else 1)].view(*((n, c) if channels_last else (c, n)), *((3,) if s24 else ()))
+                at += c * n * (3 if s24 else 1)
                 pcm.append(v)
                 arr[i].d_pcm, arr[i].pcm_stride = v.data_ptr(), n
+                lays[i].format = fmt
+                lays[i].channel_stride, lays[i].sample_stride = (1, c) if channels_last else (n, 1)
         self._fence()
-        ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
+        if plain:
+            ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
+        else:
+            ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
         codes = [int(arr[i].result) for i in range(W)]
         if ret != 0:
             msg = lib.LINNEAmd_GetLastError(self.h).decode()
             if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
                 raise LinneAmdError(f"DecodeWindowsDevice -> {ret}: {msg}", ret, codes)
-        return (pcm, codes) if return_codes else pcm
+        res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
+        return res[0] if len(res) == 1 else res
+
+    @staticmethod
+    def _pcm_layout(pcm, what="pcm"):
+        """(format, channel stride, sample stride, channels, samples, plain) of a PCM tensor: int32 or int16 (C, N), or uint8 (C, N, 3)
+        for packed 24-bit samples, with any strides (a channels-last view is x.T); plain: int32 with contiguous rows"""
+        import torch
+        assert pcm.is_cuda and pcm.dtype in (torch.int32, torch.int16, torch.uint8), \
+            f"{what} is an int32 or int16 CUDA tensor (C, N), or a uint8 one (C, N, 3) of packed 24-bit samples"
+        if pcm.dtype == torch.uint8:
+            assert pcm.dim() == 3 and pcm.shape[2] == 3 and pcm.stride(2) == 1 and pcm.stride(0) % 3 == 0 and pcm.stride(1) % 3 == 0, \
+                f"{what}: a uint8 tensor is (C, N, 3), the three bytes of a sample contiguous, samples whole samples apart"
+            fmt, unit = PCM_S24, 3
+        else:
+            assert pcm.dim() == 2, f"{what} is (C, N)"
+            fmt, unit = (PCM_S32 if pcm.dtype == torch.int32 else PCM_S16), 1
+        nch, ns = int(pcm.shape[0]), int(pcm.shape[1])
+        cs = pcm.stride(0) // unit if nch > 1 else 0
+        ss = pcm.stride(1) // unit if ns > 1 else 1
+        return fmt, cs, ss, nch, ns, (fmt == PCM_S32 and ss == 1)
 
     def encode_stream(self, pcm, bits, rate, block, preset, ms, group_frames=0, parcor_state=None, out=None):
-        """planar PCM (int32 CUDA tensor (C, N), any row stride, or numpy: copied to the device) -> a .lnn stream encoded on the device,
+        """PCM (an int32 or int16 CUDA tensor (C, N) with any strides -- x.T of a channels-last (N, C) one included --, a uint8 one
+        (C, N, 3) of packed little-endian 24-bit samples, or numpy: copied to the device as int32) -> a .lnn stream encoded on the device,
         as a 1-D uint8 CUDA tensor (a view of `out` when one is given); with parcor_state (a float, the quirk-Q2 state) not None, the
         pair (stream, new state).  include/linne_amd.h LINNEAmd_EncodeStreamDevice states the result contract.  The default buffer is
         what the reference's command line tool allocates (twice the PCM's bytes at `bits` width, plus the header); a stream that does not
@@ -447,10 +516,9 @@ class Context:
         import torch
         if not isinstance(pcm, torch.Tensor):
             pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int32)).to(f"cuda:{self.device}")
-        assert pcm.dtype == torch.int32 and pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1, \
-            "pcm is an int32 CUDA tensor (C, N) whose rows are contiguous"
+        fmt, cs, ss, nch, ns, plain = self._pcm_layout(pcm)
         assert pcm.device.index == self.device, f"the PCM is on {pcm.device}, the context on cuda:{self.device}"
-        nch, ns = pcm.shape
+        lay = PcmLayout(fmt, 0, cs, ss)
         hd = Header(1, 2, nch, ns, rate, bits, block, preset, int(bool(ms)))
         state = C.c_double(0.0 if parcor_state is None else float(parcor_state))
         nbytes = C.c_uint64(0)
@@ -458,6 +526,9 @@ class Context:
         def run(buf):
             state.value = 0.0 if parcor_state is None else float(parcor_state)
             self._fence()
+            if not plain:
+                return lib.LINNEAmd_EncodeStreamDeviceLayout(self.h, C.byref(hd), C.c_void_p(pcm.data_ptr()), C.byref(lay), int(group_frames),
+                                                             C.c_void_p(buf.data_ptr()), buf.numel(), C.byref(nbytes), C.byref(state))
             return lib.LINNEAmd_EncodeStreamDevice(self.h, C.byref(hd), C.c_void_p(pcm.data_ptr()), pcm.stride(0) if nch > 1 else ns,
                                                    int(group_frames), C.c_void_p(buf.data_ptr()), buf.numel(), C.byref(nbytes),
                                                    C.byref(state))
@@ -481,8 +552,8 @@ class Context:
 
     def encode_streams(self, tracks, group_frames=0, parcor_states=None, return_codes=False):
         """many tracks into their .lnn streams in one call (include/linne_amd.h LINNEAmd_EncodeStreamsDevice).  tracks: a sequence of
-        (pcm, bits, rate, block, preset, ms), pcm as in encode_stream (an int32 CUDA tensor (C, N) with contiguous rows and any row
-        stride, or numpy); shapes may be mixed.  -> a list of 1-D uint8 CUDA tensors, views of one allocation at 4-byte-aligned
+        (pcm, bits, rate, block, preset, ms), pcm as in encode_stream (an int32 or int16 CUDA tensor (C, N) with any strides, a uint8
+        one (C, N, 3) of packed 24-bit samples, or numpy); shapes and sample formats may be mixed.  -> a list of 1-D uint8 CUDA tensors, views of one allocation at 4-byte-aligned
         offsets (None for a track that failed); every stream is what encode_stream gives for its track alone.  Each track gets the
         default room encode_stream gives it; the tracks that do not fit are encoded once more, together, at their exact sizes.  With
         parcor_states (a list of floats, the tracks' quirk-Q2 states) -> (streams, new states).  Raises LinneAmdError with .code =
@@ -494,14 +565,19 @@ class Context:
         T = len(tracks)
         assert parcor_states is None or len(parcor_states) == T
         arr = (Track * max(T, 1))()
-        keep, rooms = [], []
+        lays = (PcmLayout * max(T, 1))()
+        keep, rooms, all_plain = [], [], True
         for i, (pcm, bits, rate, block, preset, ms) in enumerate(tracks):
             if not isinstance(pcm, torch.Tensor):
                 pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int32)).to(dev)
-            assert pcm.dtype == torch.int32 and pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1, \
-                f"track {i}: pcm is an int32 CUDA tensor (C, N) whose rows are contiguous"
+            if pcm.dtype == torch.int32 and pcm.is_cuda and pcm.dim() == 2 and pcm.stride(1) == 1:      # int32 planar: the call without layouts
+                nch, ns = pcm.shape
+                lays[i].channel_stride, lays[i].sample_stride = pcm.stride(0) if nch > 1 else 0, 1
+            else:
+                fmt, cs, ss, nch, ns, plain = self._pcm_layout(pcm, f"track {i}: pcm")
+                lays[i].format, lays[i].channel_stride, lays[i].sample_stride = fmt, cs, ss
+                all_plain = all_plain and plain
             assert pcm.device.index == self.device, f"track {i}: the PCM is on {pcm.device}, the context on cuda:{self.device}"
-            nch, ns = pcm.shape
             keep.append(pcm)
             arr[i].header = Header(1, 2, nch, ns, rate, bits, block, preset, int(bool(ms)))
             arr[i].d_pcm, arr[i].pcm_stride = pcm.data_ptr(), pcm.stride(0) if nch > 1 else ns
@@ -515,12 +591,18 @@ class Context:
                 at += (n + 3) & ~3
             flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
             sub = (Track * max(len(which), 1))()
+            sublay = None if all_plain else (PcmLayout * max(len(which), 1))()
             for j, i in enumerate(which):
                 C.memmove(C.byref(sub[j]), C.byref(arr[i]), C.sizeof(Track))
+                if sublay is not None:
+                    C.memmove(C.byref(sublay[j]), C.byref(lays[i]), C.sizeof(PcmLayout))
                 sub[j].d_out, sub[j].capacity, sub[j].out_bytes, sub[j].result = flat.data_ptr() + offs[j], sizes[j], 0, 0
                 sub[j].parcor_state = 0.0 if parcor_states is None else float(parcor_states[i])
             self._fence()
-            ret = lib.LINNEAmd_EncodeStreamsDevice(self.h, sub, len(which), int(group_frames))
+            if all_plain:
+                ret = lib.LINNEAmd_EncodeStreamsDevice(self.h, sub, len(which), int(group_frames))
+            else:
+                ret = lib.LINNEAmd_EncodeStreamsDeviceLayout(self.h, sub, sublay, len(which), int(group_frames))
             msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
             if ret != 0 and not msg.startswith("track "):                # (a failing track's text starts with its number)
                 raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])

@@ -1924,7 +1924,7 @@ static uint64_t sx_block_of(const LINNEAmdStreamIndex *x, uint64_t s)
 /* the argument and index checks on one window, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are).  *r1 = the last block the window overlaps (nb: it reaches behind the last block); not set for a window of 0
  * samples */
-static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, char *err, size_t cap, uint64_t *r1)
+static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, const struct LINNEAmdPcmLayout *ly, char *err, size_t cap, uint64_t *r1)
 {
     const LINNEAmdStreamIndex *x = w->index;
     err[0] = 0;
@@ -1932,7 +1932,10 @@ static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWind
     if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
     const uint64_t total = x->header.num_samples;
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
-    if (x->shape.num_channels > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
+    if (ly) {
+        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, x->shape.num_channels, w->num_samples, true);
+        if (why != SB_LY_OK) { snprintf(err, cap, "DecodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
+    } else if (x->shape.num_channels > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
     if (w->num_samples == 0) return LNN_OK;
     const uint64_t hi = w->first_sample + w->num_samples;
     *r1 = (hi - 1u < x->covered) ? sx_block_of(x, hi - 1u) : x->nb;
@@ -1965,7 +1968,7 @@ static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_by
 
 /* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call.  single: the call
  * is LINNEAmd_DecodeStreamDevice, which its texts then name */
-static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, bool single, WxPlan *plan, const uint32_t **fail_out)
+static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LINNEAmdPcmLayout *layouts, uint32_t W, uint32_t group_frames, bool single, WxPlan *plan, const uint32_t **fail_out)
 {
     const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
     const char *who = single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
@@ -1975,7 +1978,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     for (uint32_t i = 0; i < W; i++) {
         uint64_t r1 = 0;
         plan[i].group = -1; plan[i].r0 = plan[i].nr = plan[i].ncomp = 0;
-        win[i].result = wx_check_window(ctx, &win[i], text, sizeof(text), &r1);
+        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, text, sizeof(text), &r1);
         if (win[i].result != LNN_OK || win[i].num_samples == 0) continue;
         const LINNEAmdStreamIndex *x = win[i].index;
         const uint64_t lo = win[i].first_sample;
@@ -1998,8 +2001,8 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu blocks in one call: too many", who, (unsigned long long)total_rec); return LNN_NG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
-    /* 2. the lists, in pinned memory: fail words | window records | block records | the passes' COMPRESS records */
-    const uint64_t o_fail = 0, o_win = align_up(sizeof(uint32_t) * (uint64_t)W), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
+    /* 2. the lists, in pinned memory: fail words, saturation words | window records | block records | the passes' COMPRESS records */
+    const uint64_t o_fail = 0, o_win = align_up(2u * sizeof(uint32_t) * (uint64_t)W), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
             o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
     if (ctx->wstage_cap < list_bytes) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2012,7 +2015,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
     uint32_t *h_fail = (uint32_t *)(hs_ + o_fail), *h_crec = (uint32_t *)(hs_ + o_crec);
     WxWindow *h_win = (WxWindow *)(hs_ + o_win);
     WxBlock *h_rec = (WxBlock *)(hs_ + o_rec);
-    for (uint32_t i = 0; i < W; i++) h_fail[i] = WX_NOFAIL;
+    for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
     std::vector<WxPass> passes;
     uint32_t nrec = 0, ncrec = 0, nwin = 0;
     uint64_t scratch_bytes = 0;
@@ -2048,7 +2051,9 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
             const LINNEAmdStreamIndex *x = win[i].index;
             const uint32_t wi = nwin++;
             WxWindow &ww = h_win[wi];
-            ww.lo = win[i].first_sample; ww.hi = ww.lo + win[i].num_samples; ww.covered = x->covered; ww.out = win[i].d_pcm; ww.stride = win[i].pcm_stride; ww.fidx = i; ww.pad = 0;
+            ww.lo = win[i].first_sample; ww.hi = ww.lo + win[i].num_samples; ww.covered = x->covered; ww.out = win[i].d_pcm; ww.fidx = i;
+            if (layouts) { ww.fmt = layouts[i].format; ww.stride = layouts[i].channel_stride; ww.sstride = layouts[i].sample_stride; }
+            else { ww.fmt = LINNE_AMD_PCM_S32; ww.stride = win[i].pcm_stride; ww.sstride = 1u; }
             const bool big = group_frames && plan[i].ncomp > group_frames;
             if (big) {
                 /* a window of more COMPRESS blocks than a pass takes: its Rice codes are checked first, in passes that place
@@ -2109,12 +2114,13 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
         if (p.check_only) continue;
         WxPlaceArgs la; memset(&la, 0, sizeof(la));
         la.recs = d_rec; la.nrec = p.nrec; la.wins = d_win; la.fail = d_fail; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
+        la.sat = d_fail + W; la.scale = ldexpf(1.0f, 1 - (int)x->shape.bits_per_sample);
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
         if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
         SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
-    /* 5. the fail words, with the call's one wait */
-    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, sizeof(uint32_t) * (uint64_t)W, hipMemcpyDeviceToHost, ctx->stream));
+    /* 5. the fail words and the saturation words behind them, with the call's one wait */
+    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, 2u * sizeof(uint32_t) * (uint64_t)W, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t i = 0; i < W; i++) if (plan[i].group >= 0 && h_fail[i] != WX_NOFAIL) win[i].result = LNN_NG;
@@ -2124,13 +2130,13 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, uint32_t 
 
 /* Both entry points behind their argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
  * with its text in ctx->err (behind the window's number unless the call is the single one) */
-static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames, bool single)
+static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct LINNEAmdPcmLayout *layouts, uint32_t num_windows, uint32_t group_frames, bool single)
 {
     ctx->err[0] = 0;
     const uint32_t *fail = NULL;
     std::vector<WxPlan> plan;
     int ret;
-    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, num_windows, group_frames, single, plan.data(), &fail); }
+    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, layouts, num_windows, group_frames, single, plan.data(), &fail); }
     catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
     if (ret != LNN_OK) {
         /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
@@ -2138,13 +2144,16 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t
         for (uint32_t i = 0; i < num_windows; i++) windows[i].result = LNN_NG;
         return LNN_NG;
     }
+    /* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
+    if (layouts) for (uint32_t i = 0; i < num_windows; i++)
+        if (windows[i].result == LNN_OK) layouts[i].saturated = (plan[i].group >= 0 && fail && fail[num_windows + i]) ? 1u : 0u;
     for (uint32_t i = 0; i < num_windows; i++) {
         if (windows[i].result == LNN_OK) continue;
         char text[sizeof(ctx->err)]; uint64_t r1;
         if (plan[i].group >= 0 && fail)
             snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
                     fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
-        else (void)wx_check_window(ctx, &windows[i], text, sizeof(text), &r1);
+        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, text, sizeof(text), &r1);
         if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
         else snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
         return windows[i].result;
@@ -2152,13 +2161,19 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t
     return LNN_OK;
 }
 
-extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
+extern "C" int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct LINNEAmdPcmLayout *layouts,
+        uint32_t num_windows, uint32_t group_frames)
 {
     if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
     if (num_windows == 0) return LNN_OK;
     if (!windows) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, num_windows, group_frames, false);
+    return wx_run(ctx, windows, layouts, num_windows, group_frames, false);
+}
+/* int32 planar windows: the call above without layouts */
+extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
+{
+    return LINNEAmd_DecodeWindowsDeviceLayout(ctx, windows, NULL, num_windows, group_frames);
 }
 
 /* one window of one stream */
@@ -2168,7 +2183,7 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (!ctx) return LNN_INVALID_ARGUMENT;
     struct LINNEAmdWindow w;
     w.index = x; w.d_stream = d_stream; w.first_sample = first_sample; w.num_samples = num_samples; w.d_pcm = d_pcm; w.pcm_stride = pcm_stride; w.result = LNN_OK;
-    return wx_run(ctx, &w, 1, 0, true);
+    return wx_run(ctx, &w, NULL, 1, 0, true);
 }
 
 
@@ -2212,7 +2227,7 @@ struct SeHost {
 };
 
 static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const struct LINNEAmdShape &shape, const HostShape &hs,
-        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes,
+        const void *d_pcm, const struct LINNEAmdPcmLayout &ly, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes,
         double *parcor_state)
 {
     const uint32_t C = shape.num_channels, S = shape.num_samples_per_block;
@@ -2268,7 +2283,7 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
         /* 1. gather */
         HIPCHK(ctx, hipMemsetAsync(d_nz, 0, sizeof(uint32_t) * Fp, ctx->stream));
         {
-            SeGatherArgs g; g.pcm = d_pcm; g.stride = pcm_stride; g.first = f0 * S; g.total = N; g.frames = d_frames; g.nonzero = d_nz;
+            SeGatherArgs g; g.pcm = d_pcm; g.stride = ly.channel_stride; g.sstride = ly.sample_stride; g.fmt = ly.format; g.first = f0 * S; g.total = N; g.frames = d_frames; g.nonzero = d_nz;
             g.F = Fp; g.C = C; g.S = S;
             SX_LAUNCH(LINNE_AMD_T_SE_GATHER, k_se_gather, dim3(Fp * C), dim3(SE_THREADS), 0, ctx->stream, g);
         }
@@ -2365,15 +2380,19 @@ static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const 
     return LNN_OK;
 }
 
-extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
-        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
-        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+/* both single entry points: layout NULL is int32 planar with pcm_stride */
+static int se_entry(struct LINNEAmdContext *ctx, const struct LINNEHeader *header, const void *d_pcm, uint64_t pcm_stride,
+        const struct LINNEAmdPcmLayout *layout, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
 {
     if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
     for (int i = 0; i < 4; i++) ctx->senc_count[i] = 0;
     if (!header || !d_pcm || !d_out || !out_bytes) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if ((uintptr_t)d_out & 3u) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: d_out is not 4-byte aligned"); return LNN_INVALID_ARGUMENT; }
+    if (layout) {
+        const int why = sb_layout_check(layout->format, layout->channel_stride, layout->sample_stride, (uint64_t)(uintptr_t)d_pcm, header->num_channels, header->num_samples, false);
+        if (why != SB_LY_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
+    }
     *out_bytes = 0;
     /* the header as SetEncodeParameter, then EncodeHeader see it (a buffer under 30 bytes is EncodeHeader's first complaint) */
     int ret = se_parameter_code(header);
@@ -2388,16 +2407,31 @@ extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const st
     shape.preset = header->preset; shape.ch_process_method = (uint32_t)header->ch_process_method;
     HostShape hs;
     if ((ret = shape_info(&shape, &hs)) != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: a shape the device path does not take"); return ret; }
-    if (shape.num_channels > 1u && pcm_stride < header->num_samples) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
+    if (!layout && shape.num_channels > 1u && pcm_stride < header->num_samples) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob: wider guard band, more plans for the host */
     ctx->nspans = 0; ctx->span_keep = 1;
     if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
-    ret = se_run(ctx, header, shape, hs, d_pcm, pcm_stride, group_frames, d_out, capacity, out_bytes, parcor_state);
+    struct LINNEAmdPcmLayout ly;
+    if (layout) ly = *layout; else { ly.format = LINNE_AMD_PCM_S32; ly.saturated = 0; ly.channel_stride = pcm_stride; ly.sample_stride = 1u; }
+    ret = se_run(ctx, header, shape, hs, d_pcm, ly, group_frames, d_out, capacity, out_bytes, parcor_state);
     ctx->span_keep = 0; ctx->rice_guard = 0.0;
     if (ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
     return ret;
+}
+
+extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    return se_entry(ctx, header, d_pcm, pcm_stride, NULL, group_frames, d_out, capacity, out_bytes, parcor_state);
+}
+extern "C" int LINNEAmd_EncodeStreamDeviceLayout(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const void *d_pcm, const struct LINNEAmdPcmLayout *layout, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    return se_entry(ctx, header, d_pcm, 0, layout, group_frames, d_out, capacity, out_bytes, parcor_state);
 }
 
 /* ================================================================================================
@@ -2418,16 +2452,22 @@ struct SbHost {
     bool live;                          /* it passed its checks and no block of it was refused so far */
     bool writing; uint64_t pos, room; double state;
     uint32_t id;                        /* its number in its shape group */
+    uint32_t fmt; uint64_t cs, ss;      /* its PCM's layout */
 };
 
 /* the argument and header checks of LINNEAmd_EncodeStreamDevice on one track, with their codes and texts, in its order */
-static int sb_check_track(struct LINNEAmdTrack *t, SbHost *h)
+static int sb_check_track(struct LINNEAmdTrack *t, const struct LINNEAmdPcmLayout *ly, SbHost *h)
 {
     char *err = h->text; const size_t cap = sizeof(h->text);
     const struct LINNEHeader *header = &t->header;
     err[0] = 0;
     if (!t->d_pcm || !t->d_out) { snprintf(err, cap, "EncodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if ((uintptr_t)t->d_out & 3u) { snprintf(err, cap, "EncodeStreamDevice: d_out is not 4-byte aligned"); return LNN_INVALID_ARGUMENT; }
+    if (ly) {
+        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)t->d_pcm, header->num_channels, header->num_samples, false);
+        if (why != SB_LY_OK) { snprintf(err, cap, "EncodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
+        h->fmt = ly->format; h->cs = ly->channel_stride; h->ss = ly->sample_stride;
+    } else { h->fmt = LINNE_AMD_PCM_S32; h->cs = t->pcm_stride; h->ss = 1u; }
     t->out_bytes = 0;
     int ret = se_parameter_code(header);
     if (ret != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: header refused by SetEncodeParameter's checks"); return ret; }
@@ -2440,7 +2480,7 @@ static int sb_check_track(struct LINNEAmdTrack *t, SbHost *h)
     h->shape.preset = header->preset; h->shape.ch_process_method = (uint32_t)header->ch_process_method;
     HostShape hs;
     if ((ret = shape_info(&h->shape, &hs)) != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: a shape the device path does not take"); return ret; }
-    if (h->shape.num_channels > 1u && t->pcm_stride < header->num_samples) { snprintf(err, cap, "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)t->pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
+    if (!ly && h->shape.num_channels > 1u && t->pcm_stride < header->num_samples) { snprintf(err, cap, "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)t->pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
     return LNN_OK;
 }
 
@@ -2521,7 +2561,8 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
             const SbPlanSeg &sg = pp.segs[k];
             const struct LINNEAmdTrack &tr = tracks[members[sg.track]];
             SbTrack &d = h_trk[k];
-            d.pcm = tr.d_pcm; d.stride = tr.pcm_stride; d.total = samples[sg.track]; d.out = tr.d_out; d.pos = host[members[sg.track]].pos;
+            const SbHost &th = host[members[sg.track]];
+            d.pcm = tr.d_pcm; d.stride = th.cs; d.sstride = th.ss; d.fmt = th.fmt; d.pad = 0; d.total = samples[sg.track]; d.out = tr.d_out; d.pos = host[members[sg.track]].pos;
             d.slot0 = sg.slot0; d.nslots = sg.nslots; d.write = 0; d.id = sg.track;
         }
         for (uint32_t r = 0; r < Fp; r++) {
@@ -2661,7 +2702,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
     return LNN_OK;
 }
 
-static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames, std::vector<SbHost> &host)
+static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const struct LINNEAmdPcmLayout *layouts, uint32_t num_tracks, uint32_t group_frames, std::vector<SbHost> &host)
 {
     struct Group { struct LINNEAmdShape shape; std::vector<uint32_t> members; };
     std::vector<Group> groups;
@@ -2670,7 +2711,7 @@ static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t n
     for (uint32_t i = 0; i < num_tracks; i++) {
         SbHost &h = host[i];
         memset(&h, 0, sizeof(h));
-        h.result = sb_check_track(&tracks[i], &h);
+        h.result = sb_check_track(&tracks[i], layouts ? &layouts[i] : NULL, &h);
         if (h.result != LNN_OK) continue;
         h.live = true; h.pos = LINNE_HEADER_SIZE; h.state = tracks[i].parcor_state;
         h.room = tracks[i].capacity < 0xFFFFFFFFull ? tracks[i].capacity : 0xFFFFFFFFull;     /* EncodeWhole's buffer size is a uint32 */
@@ -2693,7 +2734,14 @@ static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t n
     return ret == LNN_OK ? LNN_OK : LNN_NG;
 }
 
+/* int32 planar tracks: the call below without layouts */
 extern "C" int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames)
+{
+    return LINNEAmd_EncodeStreamsDeviceLayout(ctx, tracks, NULL, num_tracks, group_frames);
+}
+
+extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const struct LINNEAmdPcmLayout *layouts,
+        uint32_t num_tracks, uint32_t group_frames)
 {
     if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
@@ -2703,7 +2751,7 @@ extern "C" int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct 
     if (!tracks) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     std::vector<SbHost> host;
     int ret;
-    try { ret = sb_run(ctx, tracks, num_tracks, group_frames, host); }
+    try { ret = sb_run(ctx, tracks, layouts, num_tracks, group_frames, host); }
     catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
     const bool began = ctx->span_keep != 0;
     ctx->span_keep = 0; ctx->rice_guard = 0.0;

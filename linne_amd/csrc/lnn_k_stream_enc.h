@@ -2,8 +2,9 @@
  * (LINNEAmd_EncodeStreamDevice; DESIGN.md section 5, "Encoding into a stream in HBM").
  *
  * Per pass of frames (between the analysis and the writers sits the one host step: block types, flagged Rice plans):
- *   k_se_gather    planar input -> the [F][C][S] frame layout of the analysis, the last frame zero-padded; per frame a flag
- *                  "some sample is not 0" (the SILENT test of the block-type decision)
+ *   k_se_gather    the input (int32 planar, or any struct LINNEAmdPcmLayout: int16 / packed 24-bit, interleaved, padded) -> the
+ *                  [F][C][S] frame layout of the analysis, the last frame zero-padded; per frame a flag "some sample is not 0" (the
+ *                  SILENT test of the block-type decision)
  *   k_se_compact   each channel-frame's plan flag, partition order and code length in 8 bytes (what the host step reads)
  *   k_se_size      each block's size, where each channel's Rice code starts in it, and the host stitcher's per-block errors
  *   k_sx_scan      (lnn_k_stream.h) the blocks' offsets
@@ -51,52 +52,151 @@ struct SeTables {
 /* the tables of a many-track pass */
 struct SbRow { uint32_t track, slot; uint64_t first; };        /* index into the pass's SbTrack table; slot in stream order; the frame's first sample in its track */
 struct SbTrack {
-    const int32_t *pcm; uint64_t stride, total;                 /* channel ch at pcm + ch * stride; samples per channel */
+    const void *pcm; uint64_t stride, total;                    /* element (ch, i) at pcm + (ch * stride + i * sstride) elements; samples per channel */
     uint8_t *out; uint64_t pos;                                 /* the track's stream and the byte at which this pass's blocks start */
     uint32_t slot0, nslots;                                     /* its slots in this pass: [slot0, slot0 + nslots) */
     uint32_t write, id;                                         /* write 0: the track is not written (it failed, or does not fit); id: its number in its shape group */
+    uint64_t sstride; uint32_t fmt, pad;                        /* the layout: sample stride, LINNE_AMD_PCM_* (int32 planar: 1, S32) */
 };
 struct SbTrackOut { uint64_t bytes; uint32_t fail; int32_t status; };  /* of a track in a pass: bytes; lowest failing slot - slot0 (~0: none), its status */
 
 struct SeGatherArgs {
-    const int32_t *pcm; uint64_t stride;        /* channel ch at pcm + ch * stride */
+    const void *pcm; uint64_t stride;           /* element (ch, i) at pcm + (ch * stride + i * sstride) elements */
     uint64_t first, total;                      /* the pass's first sample, the stream's samples per channel */
     int32_t *frames;                            /* [F][C][S] */
     uint32_t *nonzero;                          /* [F], zeroed */
     uint32_t F, C, S;
+    uint32_t fmt; uint64_t sstride;             /* the layout (int32 planar: S32, 1) */
 };
+
+/* ---- reading PCM of any layout (include/linne_amd.h struct LINNEAmdPcmLayout) ----
+ * Four consecutive elements -- 8, 12 or 16 bytes at q, aligned to the element only -- from the aligned 32-bit words that hold them.
+ * [lo, hi) are the bytes of the contiguous run of elements q lies in (a planar channel, or a whole packed interleaved track): a word
+ * is loaded whole where all of it lies in the run and put together from the run's bytes where it does not (the run's two ends), so
+ * no byte outside the run is touched.  Only the words that hold the first cnt (1 .. 4) elements are read; v[cnt ..] = 0. */
+__device__ __forceinline__ uint32_t ly_word(const uint8_t *w, const uint8_t *lo, const uint8_t *hi)
+{
+    if (w >= lo && w + 4 <= hi) return *(const uint32_t *)w;
+    uint32_t v = 0;
+    for (uint32_t t = 0; t < 4u; t++) if (w + t >= lo && w + t < hi) v |= (uint32_t)w[t] << (8u * t);
+    return v;
+}
+__device__ __forceinline__ void ly_load4(const uint8_t *q, const uint8_t *lo, const uint8_t *hi, uint32_t fmt, uint32_t cnt, int32_t v[4])
+{
+    const uint32_t es = fmt == LINNE_AMD_PCM_S16 ? 2u : (fmt == LINNE_AMD_PCM_S24 ? 3u : 4u);
+    const uint32_t mis = (uint32_t)((uintptr_t)q & 3u), sh = mis * 8u, nw = (mis + cnt * es + 3u) >> 2;      /* nw <= 4 */
+    const uint8_t *w0 = q - mis;
+    uint32_t W[5], B[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++) W[i] = (i < nw) ? ly_word(w0 + 4u * i, lo, hi) : 0u;
+    W[4] = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++) B[i] = sh ? ((W[i] >> sh) | (W[i + 1] << (32u - sh))) : W[i];
+    if (fmt == LINNE_AMD_PCM_S16) {
+        v[0] = (int16_t)B[0]; v[1] = (int16_t)(B[0] >> 16); v[2] = (int16_t)B[1]; v[3] = (int16_t)(B[1] >> 16);
+    } else if (fmt == LINNE_AMD_PCM_S24) {
+        v[0] = (int32_t)(B[0] << 8) >> 8; v[1] = (int32_t)(((B[0] >> 24) | (B[1] << 8)) << 8) >> 8;
+        v[2] = (int32_t)(((B[1] >> 16) | (B[2] << 16)) << 8) >> 8; v[3] = (int32_t)B[2] >> 8;
+    } else { v[0] = (int32_t)B[0]; v[1] = (int32_t)B[1]; v[2] = (int32_t)B[2]; v[3] = (int32_t)B[3]; }
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++) if (i >= cnt) v[i] = 0;
+}
+/* one element by loads of its own bytes */
+__device__ __forceinline__ int32_t ly_load1(const uint8_t *q, uint32_t fmt)
+{
+    if (fmt == LINNE_AMD_PCM_S16) return *(const int16_t *)q;
+    if (fmt == LINNE_AMD_PCM_S24) return (int32_t)(((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16)) << 8) >> 8;
+    return *(const int32_t *)q;
+}
+
+/* Workgroup x of frame f's C, for a layout other than int32 with sample stride 1: the frame has n samples from `first` of a track
+ * of `total`.  Returns "one of my samples is not 0".
+ *   sample stride 1 (planar)   x is a channel: its n elements are contiguous and read four at a time (ly_load4) into row (f, x)
+ *   otherwise                  x is a quarter-aligned C-th of the frame's samples with all their channels.  Packed interleaved
+ *                              (channel stride 1, sample stride C): those are contiguous too, read four at a time and scattered to
+ *                              the C rows; any other strides: element by element, the channels of a sample on neighbouring lanes
+ * Samples n .. S of the rows are zeroed as the int32 planar path zeroes them. */
+__device__ __forceinline__ int se_gather_layout(const void *pcm, uint32_t fmt, uint64_t cs, uint64_t ss, uint64_t total, uint64_t first,
+        uint32_t n, int32_t *frames, uint32_t f, uint32_t x, uint32_t C, uint32_t S)
+{
+    const uint32_t es = fmt == LINNE_AMD_PCM_S16 ? 2u : (fmt == LINNE_AMD_PCM_S24 ? 3u : 4u);
+    const uint8_t *base = (const uint8_t *)pcm;
+    int32_t *rows = frames + (uint64_t)f * C * S;
+    int any = 0;
+    if (ss == 1u) {
+        const uint8_t *lo = base + (uint64_t)x * cs * es, *hi = lo + total * es, *p = lo + first * es;
+        int32_t *dst = rows + (uint64_t)x * S;
+        for (uint32_t k0 = threadIdx.x * 4u; k0 < S; k0 += SE_THREADS * 4u) {
+            int32_t v[4] = { 0, 0, 0, 0 };
+            if (k0 < n) ly_load4(p + (uint64_t)k0 * es, lo, hi, fmt, (n - k0 < 4u) ? n - k0 : 4u, v);
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++) if (k0 + i < S) { dst[k0 + i] = v[i]; any |= (v[i] != 0); }
+        }
+        return any;
+    }
+    const uint32_t chunk = ((S + C - 1u) / C + 3u) & ~3u, s_lo = x * chunk;
+    if (s_lo >= S) return 0;
+    const uint32_t s_hi = (S - s_lo < chunk) ? S : s_lo + chunk;
+    const uint32_t ne = (s_hi - s_lo) * C, live = (n > s_lo) ? ((n < s_hi ? n : s_hi) - s_lo) * C : 0u;       /* elements to write, and those of them the track holds */
+    if (cs == 1u && ss == C) {
+        const uint8_t *lo = base, *hi = base + total * C * es, *p = base + (first + s_lo) * C * es;
+        for (uint32_t k0 = threadIdx.x * 4u; k0 < ne; k0 += SE_THREADS * 4u) {
+            int32_t v[4] = { 0, 0, 0, 0 };
+            if (k0 < live) ly_load4(p + (uint64_t)k0 * es, lo, hi, fmt, (live - k0 < 4u) ? live - k0 : 4u, v);
+            uint32_t smp = k0 / C, ch = k0 - smp * C;
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++) {
+                if (k0 + i < ne) { rows[(uint64_t)ch * S + s_lo + smp] = v[i]; any |= (v[i] != 0); }
+                if (++ch == C) { ch = 0; smp++; }
+            }
+        }
+        return any;
+    }
+    for (uint32_t k = threadIdx.x; k < ne; k += SE_THREADS) {
+        const uint32_t smp = k / C, ch = k - smp * C;
+        const int32_t v = (k < live) ? ly_load1(base + ((uint64_t)ch * cs + (first + s_lo + smp) * ss) * es, fmt) : 0;
+        rows[(uint64_t)ch * S + s_lo + smp] = v;
+        any |= (v != 0);
+    }
+    return any;
+}
+
 /* a workgroup per channel-frame */
 __global__ __launch_bounds__(SE_THREADS) void k_se_gather(SeGatherArgs a)
 {
     const uint32_t cf = blockIdx.x, f = cf / a.C, ch = cf - f * a.C;
     const uint64_t s0 = a.first + (uint64_t)f * a.S;
     const uint32_t n = (a.total - s0 < a.S) ? (uint32_t)(a.total - s0) : a.S;
-    const int32_t *src = a.pcm + (uint64_t)ch * a.stride + s0;
-    int32_t *dst = a.frames + (uint64_t)cf * a.S;
     int any = 0;
-    for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
-        const int32_t v = (s < n) ? src[s] : 0;
-        dst[s] = v;
-        any |= (v != 0);
-    }
+    if (a.fmt == LINNE_AMD_PCM_S32 && a.sstride == 1u) {
+        const int32_t *src = (const int32_t *)a.pcm + (uint64_t)ch * a.stride + s0;
+        int32_t *dst = a.frames + (uint64_t)cf * a.S;
+        for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
+            const int32_t v = (s < n) ? src[s] : 0;
+            dst[s] = v;
+            any |= (v != 0);
+        }
+    } else any = se_gather_layout(a.pcm, a.fmt, a.stride, a.sstride, a.total, s0, n, a.frames, f, ch, a.C, a.S);      /* block-uniform */
     if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&a.nonzero[f], 1u);
 }
 
-/* the same for the rows of many tracks (a.pcm, a.stride, a.first, a.total are not used) */
+/* the same for the rows of many tracks (a.pcm, a.stride, a.first, a.total, a.fmt, a.sstride are not used: every row's track has its own) */
 __global__ __launch_bounds__(SE_THREADS) void k_sb_gather(SeGatherArgs a, const SbRow *rows, const SbTrack *trk)
 {
     const uint32_t cf = blockIdx.x, f = cf / a.C, ch = cf - f * a.C;
     const SbRow r = rows[f];
     const SbTrack &t = trk[r.track];
     const uint32_t n = (t.total - r.first < a.S) ? (uint32_t)(t.total - r.first) : a.S;
-    const int32_t *src = t.pcm + (uint64_t)ch * t.stride + r.first;
-    int32_t *dst = a.frames + (uint64_t)cf * a.S;
     int any = 0;
-    for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
-        const int32_t v = (s < n) ? src[s] : 0;
-        dst[s] = v;
-        any |= (v != 0);
-    }
+    if (t.fmt == LINNE_AMD_PCM_S32 && t.sstride == 1u) {
+        const int32_t *src = (const int32_t *)t.pcm + (uint64_t)ch * t.stride + r.first;
+        int32_t *dst = a.frames + (uint64_t)cf * a.S;
+        for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
+            const int32_t v = (s < n) ? src[s] : 0;
+            dst[s] = v;
+            any |= (v != 0);
+        }
+    } else any = se_gather_layout(t.pcm, t.fmt, t.stride, t.sstride, t.total, r.first, n, a.frames, f, ch, a.C, a.S);        /* block-uniform */
     if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&a.nonzero[f], 1u);
 }
 

@@ -12,7 +12,8 @@
  *   k_wx_rice_check           did the Rice decoder consume exactly the bytes the block's size field names?  The lowest failing
  *                             block's number goes into its window's fail word
  *   (the synthesis kernels of lnn_k_decode*.h)
- *   k_wx_place                every record's samples, cropped to its window, into that window's planar output; a record of type
+ *   k_wx_place                every record's samples, cropped to its window, into that window's output (int32 planar, or converted
+ *                             to the window's struct LINNEAmdPcmLayout: int16, packed 24-bit, float32; interleaved, padded); a record of type
  *                             WX_TAIL is the part of a window beyond the stream's last block (zeros).  The records of a window whose
  *                             fail word is set are skipped: a failing window's output is not written
  * As in lnn_k_stream.h, no read of a stream leaves [0, stream_bytes): RAW samples are un-zig-zagged straight from the stream.
@@ -35,11 +36,12 @@ struct WxBlock {
     uint32_t cidx;                      /* index among the pass's COMPRESS blocks, or ~0 */
     uint32_t blk;                       /* its number in its stream */
 };
-/* one window (48 bytes) */
+/* one window (64 bytes) */
 struct WxWindow {
     uint64_t lo, hi, covered;           /* the range [lo, hi); the samples the stream's blocks hold */
-    int32_t *out; uint64_t stride;
-    uint32_t fidx, pad;                 /* its fail word */
+    void *out; uint64_t stride;         /* element (ch, i) at out + (ch * stride + i * sstride) elements of fmt */
+    uint32_t fidx, fmt;                 /* its fail word (its saturation word lies W words behind it); LINNE_AMD_PCM_* */
+    uint64_t sstride;                   /* (int32 planar: fmt S32, sstride 1) */
 };
 
 /* Workgroup k copies COMPRESS block k's size + 6 bytes to seg + dst.  Source and destination have the same address modulo 16 (the
@@ -114,20 +116,123 @@ struct WxPlaceArgs {
     uint32_t C, S, bits;
     const int32_t *pcm;                 /* [ncomp][C][S]: the synthesis' output */
     uint32_t xch;                       /* workgroups per record */
+    uint32_t *sat;                      /* [W] beside the fail words: set when a sample of the window lay outside its format's range */
+    float scale;                        /* 2^-(bits - 1): the F32 format's */
 };
+
+/* ---- writing PCM of any layout (include/linne_amd.h struct LINNEAmdPcmLayout) ---- */
+#define WX_IMG_BYTES (SX_PLACE_THREADS * LINNE_MAX_NUM_CHANNELS * 4u + 8u * LINNE_MAX_NUM_CHANNELS)
+
+/* sample s (block sample i) of channel ch of record rc, as the int32 planar path takes it */
+__device__ __forceinline__ int32_t wx_value(const WxPlaceArgs &a, const WxBlock *rc, uint32_t type, uint32_t i, uint32_t ch)
+{
+    if (type == SX_COMPRESS) return a.pcm[((uint64_t)rc->cidx * a.C + ch) * a.S + i];
+    if (type == SX_RAW) {
+        const uint32_t wd = a.bits >> 3;
+        const uint64_t q = rc->off + 11u + ((uint64_t)i * a.C + ch) * wd;
+        uint32_t u = 0;
+        for (uint32_t j = 0; j < wd; j++) u = (u << 8) | rc->b[q + j];
+        return sx_unzz(u);
+    }
+    return 0;
+}
+/* v in the window's format: the element's bits (its low 2, 3 or 4 bytes); sat is set when v had to be clipped */
+__device__ __forceinline__ uint32_t wx_convert(int32_t v, uint32_t fmt, float scale, int &sat)
+{
+    if (fmt == LINNE_AMD_PCM_F32) return __float_as_uint((float)v * scale);
+    if (fmt == LINNE_AMD_PCM_S32) return (uint32_t)v;
+    const int32_t top = (fmt == LINNE_AMD_PCM_S16) ? 32767 : 8388607;
+    const int32_t c = v > top ? top : (v < -top - 1 ? -top - 1 : v);
+    sat |= (c != v);
+    return (uint32_t)c;
+}
+/* an element of es bytes at p, aligned to the element (S24: to nothing), in global memory or LDS: stores of its own bytes only */
+__device__ __forceinline__ void wx_store1(uint8_t *p, uint32_t u, uint32_t es)
+{
+    if (es == 4u) *(uint32_t *)p = u;
+    else if (es == 2u) *(uint16_t *)p = (uint16_t)u;
+    else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); p[2] = (uint8_t)(u >> 16); }
+}
+
+/* The workgroup places samples [sa, sb) (at most SX_PLACE_THREADS, inside the window) of record rc, whose sample 0 is stream sample
+ * f0, in a layout other than int32 with sample stride 1.  Where the elements of this piece are contiguous in memory -- every channel's
+ * for sample stride 1, the whole piece's for packed interleaved (channel stride 1, sample stride C) -- they are first laid out in
+ * LDS at their address modulo 4 and then stored as aligned 32-bit words; a word that reaches outside the run [A, A + len) holds
+ * elements other workgroups (or nobody) write, and only its bytes inside the run are stored, one by one.  With any other strides
+ * every element is stored by itself.  Returns (to every thread) whether a sample was clipped. */
+__device__ __forceinline__ int wx_place_layout(const WxPlaceArgs &a, const WxWindow &w, const WxBlock *rc, uint32_t type, uint64_t f0,
+        uint64_t sa, uint64_t sb, uint8_t *img)
+{
+    const uint32_t fmt = w.fmt, es = fmt == LINNE_AMD_PCM_S16 ? 2u : (fmt == LINNE_AMD_PCM_S24 ? 3u : 4u);
+    const uint32_t m = (uint32_t)(sb - sa), t = threadIdx.x, C = a.C;
+    uint8_t *base = (uint8_t *)w.out;
+    const bool packed = (w.stride == 1u && w.sstride == C), planar = (w.sstride == 1u);
+    int sat = 0;
+    if (!packed && !planar) {
+        for (uint32_t k = t; k < m * C; k += SX_PLACE_THREADS) {
+            const uint32_t smp = k / C, ch = k - smp * C;
+            const uint32_t u = wx_convert(wx_value(a, rc, type, (uint32_t)(sa + smp - f0), ch), fmt, a.scale, sat);
+            wx_store1(base + ((uint64_t)ch * w.stride + (sa + smp - w.lo) * w.sstride) * es, u, es);
+        }
+        return __syncthreads_or(sat);
+    }
+    /* runs: planar C of m elements, packed one of m * C; run r starts at byte A(r) and lies in LDS at r * pitch + (A(r) & 3) */
+    const uint32_t nrun = planar ? C : 1u, len = (planar ? m : m * C) * es, pitch = ((len + 3u) & ~3u) + 8u;
+    if (t < m)
+        for (uint32_t ch = 0; ch < C; ch++) {
+            const uint32_t u = wx_convert(wx_value(a, rc, type, (uint32_t)(sa + t - f0), ch), fmt, a.scale, sat);
+            const uint32_t r = planar ? ch : 0u;
+            const uint64_t A = (uint64_t)(uintptr_t)base + ((uint64_t)r * w.stride + (sa - w.lo) * w.sstride) * es;
+            wx_store1(img + r * pitch + (uint32_t)(A & 3u) + (planar ? t : t * C + ch) * es, u, es);
+        }
+    sat = __syncthreads_or(sat);
+    for (uint32_t r = 0; r < nrun; r++) {
+        const uint64_t A = (uint64_t)(uintptr_t)base + ((uint64_t)r * w.stride + (sa - w.lo) * w.sstride) * es, E = A + len, W0 = A & ~(uint64_t)3u;
+        const uint32_t nw = (uint32_t)((E + 3u - W0) >> 2);
+        const uint32_t *src = (const uint32_t *)(img + r * pitch);
+        for (uint32_t k = t; k < nw; k += SX_PLACE_THREADS) {
+            const uint64_t g = W0 + 4u * (uint64_t)k;
+            const uint32_t v = src[k];
+            if (g >= A && g + 4u <= E) *(uint32_t *)(uintptr_t)g = v;
+            else for (uint32_t j = 0; j < 4u; j++) if (g + j >= A && g + j < E) *(uint8_t *)(uintptr_t)(g + j) = (uint8_t)(v >> (8u * j));
+        }
+    }
+    __syncthreads();                    /* (the image is filled again by the next piece) */
+    return sat;
+}
+
 /* nrec * xch workgroups: the y-th xch of them place record y */
 __global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_place(WxPlaceArgs a)
 {
+    __shared__ __attribute__((aligned(16))) uint8_t img[WX_IMG_BYTES];
     const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
     if (y >= a.nrec) return;
     const WxBlock *rc = a.recs + y;
     const WxWindow w = a.wins[rc->win];
     if (a.fail[w.fidx] != WX_NOFAIL) return;
     const uint32_t type = rc->type;
+    if (w.fmt != LINNE_AMD_PCM_S32 || w.sstride != 1u) {         /* block-uniform */
+        int sat = 0;
+        if (type == WX_TAIL) {
+            const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
+            for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
+                sat |= wx_place_layout(a, w, rc, type, s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS, img);
+        } else {
+            const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
+            for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
+                const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
+                const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
+                if (sa < sb) sat |= wx_place_layout(a, w, rc, type, f0, sa, sb, img);
+            }
+        }
+        if (sat && threadIdx.x == 0) atomicOr(&a.sat[w.fidx], 1u);
+        return;
+    }
+    int32_t *out = (int32_t *)w.out;
     if (type == WX_TAIL) {
         const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
         for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS + threadIdx.x; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-            for (uint32_t ch = 0; ch < a.C; ch++) w.out[(uint64_t)ch * w.stride + (s - w.lo)] = 0;
+            for (uint32_t ch = 0; ch < a.C; ch++) out[(uint64_t)ch * w.stride + (s - w.lo)] = 0;
         return;
     }
     const uint32_t n = rc->nsmp;
@@ -135,7 +240,7 @@ __global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_place(WxPlaceArgs a)
     for (uint32_t i = x * SX_PLACE_THREADS + threadIdx.x; i < n; i += a.xch * SX_PLACE_THREADS) {
         const uint64_t s = f0 + i;
         if (s < w.lo || s >= w.hi) continue;
-        int32_t *dst = w.out + (s - w.lo);
+        int32_t *dst = out + (s - w.lo);
         if (type == SX_COMPRESS) {
             const int32_t *src = a.pcm + (uint64_t)rc->cidx * a.C * a.S + i;
             for (uint32_t ch = 0; ch < a.C; ch++) dst[(uint64_t)ch * w.stride] = src[(uint64_t)ch * a.S];

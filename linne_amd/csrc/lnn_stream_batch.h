@@ -30,6 +30,41 @@ struct SbPlanner {
     uint32_t t; uint64_t f;                             /* the next frame: frame f of track t */
 };
 
+/* ---- the PCM layout of a track or window (include/linne_amd.h struct LINNEAmdPcmLayout) ----
+ * formats as LINNE_AMD_PCM_*; SB_LY_* = why a layout is refused (0: it is taken) */
+#define SB_PCM_S32 0u
+#define SB_PCM_S16 1u
+#define SB_PCM_S24 2u
+#define SB_PCM_F32 3u
+enum { SB_LY_OK = 0, SB_LY_FORMAT, SB_LY_ALIGN, SB_LY_STRIDES };
+
+static inline uint32_t sb_elem_bytes(uint32_t format) { return format == SB_PCM_S16 ? 2u : (format == SB_PCM_S24 ? 3u : 4u); }
+
+/* The argument check on a layout: `base` the PCM's address, C channels of n samples, decode: the call writes PCM (F32 is a decode
+ * format only).  The strides must make (ch, i) -> ch * cs + i * ss injective in one of the two ways the header names: channels apart
+ * by at least a channel's span (planar), or samples apart by at least C channels' span (interleaved). */
+static inline int sb_layout_check(uint32_t format, uint64_t cs, uint64_t ss, uint64_t base, uint32_t C, uint64_t n, bool decode)
+{
+    if (format > SB_PCM_F32 || (format == SB_PCM_F32 && !decode)) return SB_LY_FORMAT;
+    const uint64_t align = format == SB_PCM_S16 ? 2u : (format == SB_PCM_S24 ? 1u : 4u);
+    if (base & (align - 1u)) return SB_LY_ALIGN;
+    typedef unsigned __int128 u128;
+    if (C <= 1u) { if (ss < 1u) return SB_LY_STRIDES; cs = 0; }
+    else {
+        const bool planar = ss >= 1u && (u128)cs >= (u128)n * ss;
+        const bool interleaved = cs >= 1u && (u128)ss >= (u128)C * cs;
+        if (!planar && !interleaved) return SB_LY_STRIDES;
+    }
+    /* the last element's byte offset must be a uint64 the kernels can add to the base */
+    const u128 last = ((u128)(C ? C - 1u : 0u) * cs + (u128)(n ? n - 1u : 0u) * ss + 1u) * sb_elem_bytes(format);
+    return last < ((u128)1 << 62) ? SB_LY_OK : SB_LY_STRIDES;
+}
+static inline const char *sb_layout_text(int why)
+{
+    return why == SB_LY_FORMAT ? "a PCM format this call does not take" : why == SB_LY_ALIGN ? "the PCM base is not aligned to its format's element"
+         : "channel_stride and sample_stride let two samples share an element";
+}
+
 static inline uint64_t sb_frames(uint64_t samples, uint32_t S) { return (samples + S - 1u) / S; }
 
 static inline void sb_planner_init(SbPlanner *pl, const uint64_t *samples, uint32_t ntracks, uint32_t S)
