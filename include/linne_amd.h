@@ -351,7 +351,12 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_SB_RICE = 65,           /* Rice codes (k_se_rice<., true>) */
     LINNE_AMD_T_SB_RAW = 66,            /* RAW payloads (k_se_raw<true>) */
     LINNE_AMD_T_SB_CRC = 67,            /* CRC16 and block headers (k_se_crc<true>) */
-    LINNE_AMD_T_SB_HEADER = 68          /* the finished tracks' stream headers (k_sb_header) */
+    LINNE_AMD_T_SB_HEADER = 68,         /* the finished tracks' stream headers (k_sb_header) */
+    /* the indexes of many streams (LINNEAmd_StreamIndexesCreate, a call of its own): its segmented kernels report under 37-44, the
+     * two without a single-call counterpart follow here, numbered on from the kind above (lnn_device.hip asserts 69 and 70: a kind
+     * put between them and 68 does not compile) */
+    LINNE_AMD_T_IB_HEADERS,             /* 69: gathering every stream's header bytes (k_ib_headers) */
+    LINNE_AMD_T_IB_BEHIND               /* 70: the place behind a chain that ends early (k_ib_behind) */
 };
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
@@ -421,6 +426,40 @@ int      LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, str
 uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index);   /* the blocks a whole decode walks */
 int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *index,
         const uint8_t *d_stream, uint64_t first_sample, uint64_t num_samples, int32_t *d_pcm, uint64_t pcm_stride);
+/* host tables of the blocks a whole decode walks, NumBlocks entries each (first: NumBlocks + 1), valid until Destroy: a block's byte
+ * offset in the stream, first sample, size field (the block holds size + 6 bytes), type (0 COMPRESS, 1 SILENT, 2 RAW) and samples.
+ * Any of the out pointers may be NULL; a NULL index is INVALID_ARGUMENT */
+int LINNEAmd_StreamIndexBlocks(const struct LINNEAmdStreamIndex *index, const uint64_t **off, const uint64_t **first,
+        const uint32_t **size, const uint32_t **type, const uint32_t **nsmp);
+/* the lowest failing block (-1: none; NumBlocks: the place behind the last block), its LINNEApiResult and byte offset */
+int LINNEAmd_StreamIndexFailure(const struct LINNEAmdStreamIndex *index, int64_t *block, int32_t *code, uint64_t *byte);
+
+/* ---- the indexes of many resident streams in one call ----
+ * LINNEAmd_StreamIndexesCreate builds the indexes of num_streams streams.  For every stream i, indexes[i] and results[i] are what
+ * LINNEAmd_StreamIndexCreate(ctx, d_streams[i], stream_bytes[i], &r) returns for it alone: a header error gives NULL and the single
+ * call's code for that stream only, damage in the blocks an index with the same failing block, code and byte offset
+ * (LINNEAmd_StreamIndexFailure); a NULL d_streams[i] is that stream's INVALID_ARGUMENT.  A failing stream does not disturb the
+ * others.  Streams of different shapes may be mixed, a stream may be named twice (two independent indexes), and streams may be
+ * adjacent views of one buffer at any alignment: every read of stream i is a byte load inside [0, stream_bytes[i]).
+ * Returns LINNE_APIRESULT_OK when every stream is OK, otherwise the result of the lowest-numbered failing stream; GetLastError then
+ * reads "stream <i>: " and the single call's text.  A HIP error or running out of memory fails the whole call: LINNE_APIRESULT_NG, in
+ * every results[i] too, every indexes[i] NULL, nothing kept.  num_streams == 0 is OK; a NULL ctx, or NULL arrays with num_streams
+ * > 0, INVALID_ARGUMENT; more than 2^32 - 2 block candidates (FF FF sync words with a plausible size field) over the whole call,
+ * LINNE_APIRESULT_NG.
+ * Every index is an ordinary one: it serves LINNEAmd_DecodeStreamDevice / LINNEAmd_DecodeWindowsDevice(Layout) next to indexes of
+ * the single call and is destroyed with LINNEAmd_StreamIndexDestroy on its own, in any order, at any time (the indexes of a call
+ * share one device and one host allocation, which the last of them frees).
+ * The number of kernel launches, copies, host synchronisations (four once the scratch has grown) and device allocations (one once the
+ * scratch has grown) does not depend on num_streams;
+ * only the pointer-doubling depth K does on the streams: the smallest K with 2^K > the largest candidate count of one stream, K - 1
+ * launches of kind 41.  Scratch, kept by the context and grown (an allocation and a wait more) when a call needs more than any
+ * before it: about 12 bytes per 4096 stream bytes, 8 + 4 K bytes per candidate, and 128 bytes per stream in a pinned host buffer and
+ * its device copy.
+ * LINNEAmd_GetLastIndexBatchCount: of the last such call, which = 0 the streams given, 1 the indexes built, 2 K, 3 its host
+ * synchronisations, 4 its device allocations; -1 for a NULL ctx or any other `which`. */
+int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes,
+        uint32_t num_streams, struct LINNEAmdStreamIndex **indexes /* out [num_streams] */, int32_t *results /* out [num_streams] */);
+int64_t LINNEAmd_GetLastIndexBatchCount(struct LINNEAmdContext *ctx, int which);
 
 /* ---- many sample windows of resident streams in one call ----
  * LINNEAmd_DecodeWindowsDevice decodes num_windows windows, each a sample range of some stream with a built index; streams of

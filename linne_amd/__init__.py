@@ -52,6 +52,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_DecodeStreamDevice", "LINNEAmd_DecodeWindowsDevice", "LINNEAmd_EncodeStreamBound", "LINNEAmd_EncodeStreamDevice", "LINNEAmd_GetLastStreamEncodeCount",
     "LINNEAmd_EncodeStreamsDevice", "LINNEAmd_GetLastStreamBatchCount",
     "LINNEAmd_EncodeStreamDeviceLayout", "LINNEAmd_EncodeStreamsDeviceLayout", "LINNEAmd_DecodeWindowsDeviceLayout",
+    "LINNEAmd_StreamIndexesCreate", "LINNEAmd_GetLastIndexBatchCount", "LINNEAmd_StreamIndexBlocks", "LINNEAmd_StreamIndexFailure",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -145,6 +146,11 @@ def _load():
     L.LINNEAmd_StreamIndexNumBlocks.restype = C.c_uint32
     L.LINNEAmd_StreamIndexNumBlocks.argtypes = [C.c_void_p]
     L.LINNEAmd_DecodeStreamDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    L.LINNEAmd_StreamIndexesCreate.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+    L.LINNEAmd_GetLastIndexBatchCount.restype = C.c_int64
+    L.LINNEAmd_GetLastIndexBatchCount.argtypes = [C.c_void_p, C.c_int]
+    L.LINNEAmd_StreamIndexBlocks.argtypes = [C.c_void_p] + [C.POINTER(C.POINTER(C.c_uint64))] * 2 + [C.POINTER(C.POINTER(C.c_uint32))] * 3
+    L.LINNEAmd_StreamIndexFailure.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     L.LINNEAmd_DecodeWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.c_uint32, C.c_uint32]
     L.LINNEAmd_EncodeStreamBound.restype = C.c_uint64
     L.LINNEAmd_EncodeStreamBound.argtypes = [C.POINTER(Header)]
@@ -200,6 +206,27 @@ class StreamIndex:
         self.header = header
         self.num_blocks = num_blocks
         self.nbytes = nbytes
+
+    def blocks(self):
+        """the blocks a whole decode walks -> numpy copies (off, first, size, type, nsmp): byte offsets, first samples (num_blocks + 1
+        entries), size fields, types (0 COMPRESS, 1 SILENT, 2 RAW) and sample counts (LINNEAmd_StreamIndexBlocks)"""
+        off, first = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        size, typ, nsmp = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        ret = lib.LINNEAmd_StreamIndexBlocks(self.h, C.byref(off), C.byref(first), C.byref(size), C.byref(typ), C.byref(nsmp))
+        if ret != 0:
+            raise LinneAmdError(f"StreamIndexBlocks -> {ret}", ret)
+        n = self.num_blocks
+        take = lambda p, k, dt: np.array(p[:k], dtype=dt)
+        return take(off, n, np.uint64), take(first, n + 1, np.uint64), take(size, n, np.uint32), take(typ, n, np.uint32), take(nsmp, n, np.uint32)
+
+    def failure(self):
+        """(block, code, byte) of the lowest failing block: block -1 (code 0) when there is none, num_blocks for the place behind the
+        last block (LINNEAmd_StreamIndexFailure)"""
+        block, code, byte = C.c_int64(0), C.c_int32(0), C.c_uint64(0)
+        ret = lib.LINNEAmd_StreamIndexFailure(self.h, C.byref(block), C.byref(code), C.byref(byte))
+        if ret != 0:
+            raise LinneAmdError(f"StreamIndexFailure -> {ret}", ret)
+        return int(block.value), int(code.value), int(byte.value)
 
     def close(self):
         if getattr(self, "h", None) and lib is not None:
@@ -375,6 +402,43 @@ class Context:
         lib.LINNEAmd_StreamIndexHeader(h, C.byref(hd))
         header = {k: int(getattr(hd, k)) for k, _ in Header._fields_}
         return StreamIndex(h, header, int(lib.LINNEAmd_StreamIndexNumBlocks(h)), t.numel())
+
+    def index_streams(self, streams, return_codes=False):
+        """the block indexes of many whole .lnn streams in one call (include/linne_amd.h LINNEAmd_StreamIndexesCreate).  streams: a
+        sequence of uint8 CUDA tensors, bytes or numpy arrays (None: a NULL stream pointer) -> a list of StreamIndex, each what
+        index_stream gives for its stream alone.  Raises LinneAmdError with .code = the call's result and .codes = the per-stream
+        LINNEApiResults when a stream fails (the indexes that were built are closed); with return_codes -> (indexes, codes), a failed
+        stream's index is None, and only a failure of the whole call raises"""
+        T = len(streams)
+        keep = [None if s is None else self._stream_bytes(s) for s in streams]
+        ptrs, sizes = (C.c_void_p * max(T, 1))(), (C.c_uint64 * max(T, 1))()
+        for i, t in enumerate(keep):
+            ptrs[i], sizes[i] = (None, 0) if t is None else (t.data_ptr(), t.numel())
+        handles, res = (C.c_void_p * max(T, 1))(), (C.c_int32 * max(T, 1))()
+        self._fence()
+        ret = lib.LINNEAmd_StreamIndexesCreate(self.h, ptrs, sizes, T, handles, res)
+        codes = [int(res[i]) for i in range(T)]
+        msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
+        out = []
+        for i in range(T):
+            if not handles[i]:
+                out.append(None)
+                continue
+            hd = Header()
+            lib.LINNEAmd_StreamIndexHeader(handles[i], C.byref(hd))
+            out.append(StreamIndex(handles[i], {k: int(getattr(hd, k)) for k, _ in Header._fields_}, int(lib.LINNEAmd_StreamIndexNumBlocks(handles[i])), keep[i].numel()))
+        whole_call = ret == 7 and all(x is None for x in out) and all(c == 7 for c in codes)      # LINNE_APIRESULT_NG everywhere, nothing built
+        if ret != 0 and (not return_codes or whole_call):
+            for x in out:
+                if x is not None:
+                    x.close()
+            raise LinneAmdError(f"StreamIndexesCreate -> {ret}: {msg}", ret, codes)
+        return (out, codes) if return_codes else out
+
+    def last_index_batch_count(self, which):
+        """the last index_streams call: 0 the streams given, 1 the indexes built, 2 the pointer-doubling depth K, 3 its host
+        synchronisations, 4 its device allocations"""
+        return int(lib.LINNEAmd_GetLastIndexBatchCount(self.h, int(which)))
 
     def decode_stream(self, data, first_sample=0, num_samples=None, index=None, dtype=None, channels_last=False, s24=False,
                       return_saturated=False):

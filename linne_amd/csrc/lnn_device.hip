@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <new>
 #include <vector>
 
@@ -46,10 +47,13 @@
 #include "lnn_k_finalize.h"
 #include "lnn_k_rice.h"
 #include "lnn_k_stream.h"
+#include "lnn_k_index_batch.h"
 #include "lnn_k_windows.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 /* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
+/* the two timing kinds linne_amd.h numbers by their place behind kind 68 */
+static_assert(LINNE_AMD_T_IB_HEADERS == 69 && LINNE_AMD_T_IB_BEHIND == 70, "the index batch's timing kinds are 69 and 70");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -100,6 +104,8 @@ struct LINNEAmdContext {
     void *wstage; uint64_t wstage_cap;  /* pinned: the same lists on the host, uploaded in one copy; the fail words come back into it */
     int64_t senc_count[4];              /* the last EncodeStreamDevice call: COMPRESS, SILENT, RAW blocks, host-settled Rice plans */
     int64_t sbatch_count[3];            /* the last EncodeStreamsDevice call: shape groups, passes, EncodeFramesDevice calls */
+    void *xcand; uint64_t xcand_cap;    /* StreamIndexesCreate: the candidates and pointer-doubling levels of one call (its rows' counts and offsets are sdec, its lists wdec / wstage) */
+    int64_t ibatch_count[5];            /* the last StreamIndexesCreate call: streams, indexes built, K, host synchronisations, device allocations */
     int span_keep;                      /* EncodeFramesDevice inside EncodeStream(s)Device: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
@@ -224,6 +230,7 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->sdec) hipFree(ctx->sdec);
     if (ctx->senc) hipFree(ctx->senc);
     if (ctx->wdec) hipFree(ctx->wdec);
+    if (ctx->xcand) hipFree(ctx->xcand);
     if (ctx->wstage) hipHostFree(ctx->wstage);
     if (ctx->af_h) hipHostFree(ctx->af_h);
     for (int i = 0; i < LNN_META; i++) { if (ctx->meta_h[i]) hipHostFree(ctx->meta_h[i]); if (ctx->meta_ev[i]) hipEventDestroy(ctx->meta_ev[i]); }
@@ -1694,11 +1701,23 @@ struct LINNEAmdStreamIndex {
     int fail_code; uint64_t fail_off;
     uint64_t *h_off, *h_first; uint32_t *h_size, *h_type, *h_nsmp;           /* host copies */
     uint64_t *d_off, *d_first; uint32_t *d_size, *d_type, *d_nsmp; int32_t *d_status; SxTables *d_tab;
+    struct SxSlab *slab;                /* LINNEAmd_StreamIndexesCreate: the tables above are parts of the call's two allocations, freed with the last index of the call */
 };
+/* what the indexes of one StreamIndexesCreate call share */
+struct SxSlab { std::atomic<uint32_t> refs; int device; void *dev, *host; };
+static void sx_slab_release(SxSlab *s)
+{
+    if (s->refs.fetch_sub(1u) != 1u) return;
+    (void)hipSetDevice(s->device);
+    if (s->dev) (void)hipFree(s->dev);
+    free(s->host);
+    delete s;
+}
 
 extern "C" void LINNEAmd_StreamIndexDestroy(struct LINNEAmdStreamIndex *x)
 {
     if (!x) return;
+    if (x->slab) { sx_slab_release(x->slab); free(x); return; }
     (void)hipSetDevice(x->device);
     void *dev[] = { x->d_off, x->d_first, x->d_size, x->d_type, x->d_nsmp, x->d_status, x->d_tab };
     for (void *p : dev) if (p) (void)hipFree(p);
@@ -1916,6 +1935,272 @@ static uint64_t sx_block_of(const LINNEAmdStreamIndex *x, uint64_t s)
     uint64_t lo = 0, hi = x->nb;
     while (hi - lo > 1u) { const uint64_t mid = lo + ((hi - lo) >> 1); if (x->h_first[mid] <= s) lo = mid; else hi = mid; }
     return lo;
+}
+
+extern "C" int LINNEAmd_StreamIndexBlocks(const struct LINNEAmdStreamIndex *index, const uint64_t **off, const uint64_t **first,
+        const uint32_t **size, const uint32_t **type, const uint32_t **nsmp)
+{
+    if (!index) return LNN_INVALID_ARGUMENT;
+    if (off) *off = index->h_off;
+    if (first) *first = index->h_first;
+    if (size) *size = index->h_size;
+    if (type) *type = index->h_type;
+    if (nsmp) *nsmp = index->h_nsmp;
+    return LNN_OK;
+}
+extern "C" int LINNEAmd_StreamIndexFailure(const struct LINNEAmdStreamIndex *index, int64_t *block, int32_t *code, uint64_t *byte)
+{
+    if (!index) return LNN_INVALID_ARGUMENT;
+    if (block) *block = index->fail_block;
+    if (code) *code = index->fail_block < 0 ? LNN_OK : index->fail_code;
+    if (byte) *byte = index->fail_block < 0 ? 0u : index->fail_off;
+    return LNN_OK;
+}
+
+/* ================================================================================================
+ * the block indexes of many resident streams in one call (lnn_k_index_batch.h)
+ * ============================================================================================== */
+extern "C" int64_t LINNEAmd_GetLastIndexBatchCount(struct LINNEAmdContext *ctx, int which)
+{
+    if (!ctx || which < 0 || which > 4) return -1;
+    return ctx->ibatch_count[which];
+}
+
+/* the header part of LINNEAmd_StreamIndexCreate on header bytes that are on the host: *out = an index without tables, or NULL with the
+ * single call's code and text; *whole_call: the failure is no answer about the stream (no host memory) and fails the call */
+static int ib_open(int device, const uint8_t *hb, uint64_t stream_bytes, LINNEAmdStreamIndex **out, char *text, size_t cap, bool *whole_call)
+{
+    struct LINNEHeader h;
+    const uint64_t hn = stream_bytes < LINNE_HEADER_SIZE ? stream_bytes : LINNE_HEADER_SIZE;
+    int ret;
+    *out = NULL; text[0] = 0; *whole_call = false;
+    if ((ret = (int)LINNEDecoder_DecodeHeader(hb, (uint32_t)hn, &h)) != LNN_OK) { snprintf(text, cap, "stream header: LINNEDecoder_DecodeHeader -> %d", ret); return ret; }
+    {
+        struct LINNEDecoderConfig cfg;
+        memset(&cfg, 0, sizeof(cfg));
+        cfg.max_num_channels = h.num_channels ? h.num_channels : 1u; cfg.max_num_layers = LINNE_AMD_MAX_LAYERS; cfg.max_num_parameters_per_layer = 128; cfg.check_crc = 1;
+        struct LINNEDecoder *dec = LINNEDecoder_Create(&cfg, NULL, 0);
+        if (!dec) { snprintf(text, cap, "LINNEDecoder_Create failed"); *whole_call = true; return LNN_NG; }
+        ret = (int)LINNEDecoder_SetHeader(dec, &h);
+        LINNEDecoder_Destroy(dec);
+        if (ret != LNN_OK) { snprintf(text, cap, "stream header: LINNEDecoder_SetHeader -> %d", ret); return ret; }
+    }
+    LINNEAmdStreamIndex *x = (LINNEAmdStreamIndex *)calloc(1, sizeof(LINNEAmdStreamIndex));
+    if (!x) { snprintf(text, cap, "out of host memory"); *whole_call = true; return LNN_NG; }
+    x->device = device; x->header = h; x->stream_bytes = stream_bytes;
+    x->shape.num_channels = h.num_channels; x->shape.bits_per_sample = h.bits_per_sample; x->shape.num_samples_per_block = h.num_samples_per_block;
+    x->shape.preset = h.preset; x->shape.ch_process_method = (uint32_t)h.ch_process_method;
+    HostShape hs;
+    if (shape_info(&x->shape, &hs) != LNN_OK) {
+        snprintf(text, cap, "stream header: a shape the device decoder does not take (%u bits, %u samples per block)", h.bits_per_sample, h.num_samples_per_block);
+        free(x); return LNN_INVALID_FORMAT;
+    }
+    x->fail_block = -1; x->fail_code = LNN_OK;
+    *out = x;
+    return LNN_OK;
+}
+
+/* the call's waits and device allocations are counted (LINNEAmd_GetLastIndexBatchCount 3 and 4) */
+static int ib_sync(LINNEAmdContext *ctx)
+{
+    ctx->ibatch_count[3]++;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LNN_OK;
+}
+static int ib_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need)
+{
+    if (*cap < need) { ctx->ibatch_count[3]++; ctx->ibatch_count[4]++; }      /* (a buffer that grows waits for the stream first) */
+    return ensure_buf(ctx, ptr, cap, need);
+}
+
+/* LNN_OK: every stream has its index or its own code, the lowest-numbered failing stream's text is in ctx->err behind its number and
+ * its code in *first_code; anything else fails the whole call, and the caller destroys what indexes[] holds by then */
+static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t T,
+        struct LINNEAmdStreamIndex **indexes, int32_t *results, SxSlab **slab_out, int *first_code)
+{
+    char text[sizeof(ctx->err)];
+    int64_t first_fail = -1;
+    auto fail_stream = [&](uint32_t i, int code, const char *why) {
+        results[i] = code;
+        if (first_fail < 0 || (int64_t)i < first_fail) {
+            first_fail = (int64_t)i; *first_code = code;
+            snprintf(ctx->err, sizeof(ctx->err), "stream %u: %.*s", i, (int)sizeof(ctx->err) - 24, why);
+        }
+    };
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    /* the lists of the call, pinned on the host and at the same offsets on the device */
+    const uint64_t o_st = 0, o_row0 = align_up(o_st + sizeof(IbStream) * (uint64_t)T), o_crow = align_up(o_row0 + sizeof(uint64_t) * (T + 1ull)),
+            o_tab = align_up(o_crow + sizeof(uint64_t) * (T + 1ull)), o_hdr = align_up(o_tab + sizeof(SxTables)), o_seg = align_up(o_hdr + (uint64_t)IB_HDR_SLOT * T),
+            o_len = align_up(o_seg + sizeof(uint64_t) * (T + 1ull)), list_bytes = align_up(o_len + sizeof(uint64_t) * (uint64_t)T);
+    if (ctx->wstage_cap < list_bytes) {
+        SX_TRY(ib_sync(ctx));
+        if (ctx->wstage) HIPCHK(ctx, hipHostFree(ctx->wstage));
+        ctx->wstage = NULL; ctx->wstage_cap = 0;
+        HIPCHK(ctx, hipHostMalloc(&ctx->wstage, list_bytes, hipHostMallocDefault));
+        ctx->wstage_cap = list_bytes;
+    }
+    SX_TRY(ib_ensure(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
+    uint8_t *hl = (uint8_t *)ctx->wstage, *dl = (uint8_t *)ctx->wdec;
+    IbStream *h_st = (IbStream *)(hl + o_st);
+    uint64_t *h_row0 = (uint64_t *)(hl + o_row0), *h_crow = (uint64_t *)(hl + o_crow), *h_seg = (uint64_t *)(hl + o_seg), *h_len = (uint64_t *)(hl + o_len);
+    const uint8_t *h_hdr = hl + o_hdr;
+    const IbStream *d_st = (const IbStream *)(dl + o_st);
+    const uint64_t *d_row0 = (const uint64_t *)(dl + o_row0), *d_crow = (const uint64_t *)(dl + o_crow);
+    uint64_t *d_seg = (uint64_t *)(dl + o_seg), *d_len = (uint64_t *)(dl + o_len);
+    const uint32_t gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
+    ctx->nspans = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    /* 1. the headers: one gather, one fetch; the host reads them as the single call does */
+    memset(h_st, 0, sizeof(IbStream) * (uint64_t)T);
+    for (uint32_t i = 0; i < T; i++) { h_st[i].b = d_streams[i]; h_st[i].N = d_streams[i] ? stream_bytes[i] : 0u; }
+    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
+    SX_LAUNCH(LINNE_AMD_T_IB_HEADERS, k_ib_headers, dim3((uint32_t)(((uint64_t)T * IB_HDR_SLOT + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, T, dl + o_hdr);
+    HIPCHK(ctx, hipMemcpyAsync(hl + o_hdr, dl + o_hdr, (uint64_t)IB_HDR_SLOT * T, hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(ib_sync(ctx));
+    uint64_t nrows = 0;
+    for (uint32_t i = 0; i < T; i++) {
+        h_row0[i] = nrows;
+        if (!d_streams[i]) { fail_stream(i, LNN_INVALID_ARGUMENT, "null stream pointer"); continue; }
+        bool whole_call;
+        const int r = ib_open(ctx->device, h_hdr + (uint64_t)IB_HDR_SLOT * i, stream_bytes[i], &indexes[i], text, sizeof(text), &whole_call);
+        if (whole_call) { snprintf(ctx->err, sizeof(ctx->err), "StreamIndexesCreate: %.*s", (int)sizeof(ctx->err) - 32, text); return LNN_NG; }
+        if (r != LNN_OK) { fail_stream(i, r, text); h_st[i].b = NULL; h_st[i].N = 0; continue; }
+        const LINNEAmdStreamIndex *x = indexes[i];
+        h_st[i].num_samples = x->header.num_samples; h_st[i].C = x->shape.num_channels; h_st[i].S = x->shape.num_samples_per_block; h_st[i].bits = x->shape.bits_per_sample;
+        if (stream_bytes[i] > SX_FIRST_BLOCK) nrows += (stream_bytes[i] - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
+    }
+    h_row0[T] = nrows;
+    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "StreamIndexesCreate: %llu stream bytes in one call: too many", (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
+    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, o_crow - o_st, hipMemcpyHostToDevice, ctx->stream));      /* the streams and row0 */
+    /* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back */
+    const uint64_t o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
+    SX_TRY(ib_ensure(ctx, &ctx->sdec, &ctx->sdec_cap, align_up(o_cofs + sizeof(uint64_t) * (nrows + 1u))));
+    uint32_t *counts = (uint32_t *)((uint8_t *)ctx->sdec + o_counts);
+    uint64_t *cofs = (uint64_t *)((uint8_t *)ctx->sdec + o_cofs);
+    const uint32_t grow = (uint32_t)((nrows + 3u) / 4u);
+    if (nrows) SX_LAUNCH(LINNE_AMD_T_SX_COUNT, k_ib_count, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, counts);
+    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nrows, cofs);
+    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)cofs, d_row0, T, d_seg);
+    HIPCHK(ctx, hipMemcpyAsync(h_seg, d_seg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(ib_sync(ctx));
+    const uint64_t M = h_seg[T];
+    if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
+    uint64_t Mmax = 0;
+    for (uint32_t i = 0; i < T; i++) if (h_seg[i + 1] - h_seg[i] > Mmax) Mmax = h_seg[i + 1] - h_seg[i];
+    uint32_t K = 1;
+    while ((1ull << K) <= Mmax) K++;                              /* 2^K > the longest segment: K levels cover any chain */
+    ctx->ibatch_count[2] = K;
+    /* 3. successors inside the segments, pointer doubling over the global array, the chains' lengths.  cand has M + 1 entries: the
+     * scan of the chains' sample counts takes its place once the chains are read (no more chain blocks than candidates) */
+    const uint64_t o_cand = 0, o_jump = align_up(sizeof(uint64_t) * (M + 1u));
+    SX_TRY(ib_ensure(ctx, &ctx->xcand, &ctx->xcand_cap, align_up(o_jump + sizeof(uint32_t) * (uint64_t)K * (M + 1u))));
+    uint64_t *cand = (uint64_t *)((uint8_t *)ctx->xcand + o_cand);
+    uint32_t *jump = (uint32_t *)((uint8_t *)ctx->xcand + o_jump);
+    const uint32_t M32 = (uint32_t)M, gM = (uint32_t)((M + 1u + 255u) / 256u);
+    if (M) {
+        SX_LAUNCH(LINNE_AMD_T_SX_WRITE, k_ib_write, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, (const uint64_t *)cofs, cand);
+        SX_LAUNCH(LINNE_AMD_T_SX_SUCC, k_ib_succ, dim3(gM), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_seg, T, (const uint64_t *)cand, M32, jump);
+        for (uint32_t k = 1; k < K; k++)
+            SX_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
+    }
+    SX_LAUNCH(LINNE_AMD_T_SX_CHAIN_LEN, k_ib_chain_len, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)d_seg, T, (const uint64_t *)cand, (const uint32_t *)jump, K, M32, d_len);
+    HIPCHK(ctx, hipMemcpyAsync(h_len, d_len, sizeof(uint64_t) * (uint64_t)T, hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(ib_sync(ctx));
+    uint64_t nchain = 0;
+    for (uint32_t i = 0; i < T; i++) { h_crow[i] = nchain; nchain += h_len[i]; }
+    h_crow[T] = nchain;
+    /* 4. the tables of all indexes: one device allocation (the CRC and Huffman tables first) and one on the host, laid out alike from
+     * `off` on: off | first (a stream's len + 1 entries from crow[i] + i on) | size | type | nsmp | status | behind */
+    const uint64_t nfirst = nchain + T, s_off = align_up(sizeof(SxTables)), s_first = s_off + sizeof(uint64_t) * (nchain + 1u), s_size = s_first + sizeof(uint64_t) * (nfirst + 1u),
+            s_type = s_size + sizeof(uint32_t) * (nchain + 1u), s_nsmp = s_type + sizeof(uint32_t) * (nchain + 1u), s_status = s_nsmp + sizeof(uint32_t) * (nchain + 1u),
+            s_behind = s_status + sizeof(int32_t) * (nchain + 1u), s_end = s_behind + sizeof(int32_t) * (uint64_t)T;
+    SxSlab *slab = new (std::nothrow) SxSlab;
+    if (!slab) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+    slab->refs.store(1u); slab->device = ctx->device; slab->dev = NULL; slab->host = NULL;
+    *slab_out = slab;
+    slab->host = malloc(s_end - s_off);
+    if (!slab->host) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+    ctx->ibatch_count[4]++;
+    HIPCHK(ctx, hipMalloc(&slab->dev, s_end));
+    uint8_t *ds = (uint8_t *)slab->dev;
+    auto hp = [&](uint64_t o) { return (uint8_t *)slab->host + (o - s_off); };          /* the host copy of the part at o */
+    uint64_t *d_off = (uint64_t *)(ds + s_off), *d_first = (uint64_t *)(ds + s_first);
+    uint32_t *d_size = (uint32_t *)(ds + s_size), *d_type = (uint32_t *)(ds + s_type), *d_nsmp = (uint32_t *)(ds + s_nsmp);
+    int32_t *d_status = (int32_t *)(ds + s_status), *d_behind = (int32_t *)(ds + s_behind);
+    sx_tables((SxTables *)(hl + o_tab));
+    HIPCHK(ctx, hipMemcpyAsync(ds, hl + o_tab, sizeof(SxTables), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dl + o_crow, hl + o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
+    if (nchain) {
+        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_seg, d_crow, T, (const uint64_t *)cand,
+                (const uint32_t *)jump, K, M32, nchain, d_off, d_size, d_type, d_nsmp);
+    }
+    uint64_t *scan = cand;                                         /* (the candidates are read: see 3.) */
+    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_nsmp, nchain, scan);
+    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_first, dim3((uint32_t)((nfirst + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint64_t *)scan, d_crow, T, nfirst, d_first);
+    if (nchain) {
+        IbCheckArgs a;
+        a.st = d_st; a.crow = d_crow; a.T = T; a.nchain = nchain; a.off = d_off; a.first = d_first; a.size = d_size; a.type = d_type; a.nsmp = d_nsmp;
+        a.tab = (const SxTables *)ds; a.status = d_status;
+        SX_LAUNCH(LINNE_AMD_T_SX_CHECK, k_ib_check, dim3((uint32_t)((nchain + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
+    }
+    SX_LAUNCH(LINNE_AMD_T_IB_BEHIND, k_ib_behind, dim3(gT), dim3(256), 0, ctx->stream, d_st, d_crow, T, (const uint64_t *)d_off, (const uint32_t *)d_size, (const uint64_t *)d_first, d_behind);
+    /* 5. everything comes back in one copy behind the call's last wait */
+    HIPCHK(ctx, hipMemcpyAsync(slab->host, ds + s_off, s_end - s_off, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
+    SX_TRY(ib_sync(ctx));
+    const int32_t *h_status = (const int32_t *)(hp(s_status)), *h_behind = (const int32_t *)(hp(s_behind));
+    for (uint32_t i = 0; i < T; i++) {
+        LINNEAmdStreamIndex *x = indexes[i];
+        if (!x) continue;
+        const uint64_t c0 = h_crow[i], len = h_len[i], ns = x->header.num_samples, N = x->stream_bytes;
+        x->slab = slab; slab->refs.fetch_add(1u);
+        x->d_tab = (SxTables *)ds;
+        x->d_off = d_off + c0; x->d_first = d_first + c0 + i; x->d_size = d_size + c0; x->d_type = d_type + c0; x->d_nsmp = d_nsmp + c0; x->d_status = d_status + c0;
+        x->h_off = (uint64_t *)(hp(s_off)) + c0; x->h_first = (uint64_t *)(hp(s_first)) + c0 + i;
+        x->h_size = (uint32_t *)(hp(s_size)) + c0; x->h_type = (uint32_t *)(hp(s_type)) + c0; x->h_nsmp = (uint32_t *)(hp(s_nsmp)) + c0;
+        /* DecodeWhole's loop ends once the samples reach the header's count (sx_build) */
+        uint64_t nb = 0;
+        while (nb < len && x->h_first[nb] < ns) nb++;
+        x->nb = (uint32_t)nb; x->covered = x->h_first[nb];
+        for (uint64_t r = 0; r < nb; r++) if (h_status[c0 + r] != LNN_OK) { x->fail_block = (int64_t)r; x->fail_code = h_status[c0 + r]; x->fail_off = x->h_off[r]; break; }
+        if (x->fail_block < 0 && nb == len && x->covered < ns) {
+            const uint64_t q = nb ? x->h_off[nb - 1] + x->h_size[nb - 1] + 6u : SX_FIRST_BLOCK;
+            if (q < N) {
+                if (h_behind[i] == LNN_NG || h_behind[i] == 0) {
+                    snprintf(text, sizeof(text), "internal: a block head at byte %llu the index did not find", (unsigned long long)q);
+                    fail_stream(i, LNN_NG, text);
+                    LINNEAmd_StreamIndexDestroy(x); indexes[i] = NULL;
+                    continue;
+                }
+                x->fail_block = (int64_t)nb; x->fail_code = h_behind[i]; x->fail_off = q;
+            }
+        }
+        ctx->ibatch_count[1]++;
+    }
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t num_streams,
+        struct LINNEAmdStreamIndex **indexes, int32_t *results)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    for (int i = 0; i < 5; i++) ctx->ibatch_count[i] = 0;
+    if (num_streams == 0) return LNN_OK;
+    if (!d_streams || !stream_bytes || !indexes || !results) { snprintf(ctx->err, sizeof(ctx->err), "StreamIndexesCreate: null argument"); return LNN_INVALID_ARGUMENT; }
+    ctx->ibatch_count[0] = num_streams;
+    for (uint32_t i = 0; i < num_streams; i++) { indexes[i] = NULL; results[i] = LNN_OK; }
+    SxSlab *slab = NULL;
+    int first_code = LNN_OK;
+    const int ret = ib_build(ctx, d_streams, stream_bytes, num_streams, indexes, results, &slab, &first_code);
+    if (ret != LNN_OK) {
+        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
+        (void)hipStreamSynchronize(ctx->stream);
+        for (uint32_t i = 0; i < num_streams; i++) { LINNEAmd_StreamIndexDestroy(indexes[i]); indexes[i] = NULL; results[i] = LNN_NG; }
+        ctx->ibatch_count[1] = 0;
+    }
+    if (slab) sx_slab_release(slab);                               /* the call's own reference */
+    return ret != LNN_OK ? LNN_NG : first_code;
 }
 
 /* ================================================================================================
