@@ -77,7 +77,12 @@ struct LINNEAmdContext {
     hipStream_t sub[LNN_MAXSUB]; hipEvent_t sub_done[LNN_MAXSUB]; hipEvent_t ev_start; int nsub, nsub_forced /* LINNE_AMD_STREAMS was given */;
     int enc_streams_done;
     hipStream_t side; hipEvent_t side_done; int has_side;     /* block-type statistics run beside the analysis */
-    hipEvent_t fork_ev, join_ev;        /* side stream: the general autocorrelation kernel for the few frames the lanes = jobs kernels do not take */
+    /* Sibling streams: what a chunk runs beside its own stream's work -- the general autocorrelation kernel for the few frames the lanes =
+     * jobs kernels do not take, and the long layer's order-128 Levinson launch (LnnLayerForms.lev_beside).  Two of them, sib[0] the side
+     * stream: the chunk in stream slot s forks to sib[s & 1], so that a call keeps at most four streams busy (two halves, a sibling
+     * each).  Events per slot: the halves of a call never share a pair. */
+    hipStream_t sib[2]; int sib1_tried;
+    hipEvent_t fork_ev[LNN_MAXSUB], join_ev[LNN_MAXSUB], lev_fork_ev[LNN_MAXSUB], lev_join_ev[LNN_MAXSUB];
     DevClass *d_cls; double *d_sin; uint64_t sin_cap; double *d_wt; uint64_t wt_cap; uint32_t *d_clsidx; uint64_t clsidx_cap; uint32_t *d_map;   /* class index per sorted row, then the sorted row's frame (same buffer) */ uint32_t *d_nsmp; uint64_t nsmp_cap;
     /* what the resident class tables were built for: a call with the same shape and frame lengths re-uses them */
     LnnClassTable tab;
@@ -176,9 +181,15 @@ static int ctx_encode_streams(LINNEAmdContext *ctx)
         const bool have_start = hipEventCreateWithFlags(&ctx->ev_start, hipEventDisableTiming) == hipSuccess;
         if (!have_start) ctx->nsub = 0;
         ctx->has_side = have_start && hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) == hipSuccess
-                && hipEventCreateWithFlags(&ctx->side_done, hipEventDisableTiming) == hipSuccess
-                && hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming) == hipSuccess
-                && hipEventCreateWithFlags(&ctx->join_ev, hipEventDisableTiming) == hipSuccess;
+                && hipEventCreateWithFlags(&ctx->side_done, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < LNN_MAXSUB && ctx->has_side; i++)
+            ctx->has_side = hipEventCreateWithFlags(&ctx->fork_ev[i], hipEventDisableTiming) == hipSuccess
+                    && hipEventCreateWithFlags(&ctx->join_ev[i], hipEventDisableTiming) == hipSuccess
+                    && hipEventCreateWithFlags(&ctx->lev_fork_ev[i], hipEventDisableTiming) == hipSuccess
+                    && hipEventCreateWithFlags(&ctx->lev_join_ev[i], hipEventDisableTiming) == hipSuccess;
+        /* (the second sibling is created when a chunk first sends its Levinson launch there -- sibling_for_levinson: a context whose calls
+         * stay below that size keeps the streams, and so the hardware queues, it always had) */
+        if (ctx->has_side) { ctx->sib[0] = ctx->side; ctx->sib[1] = ctx->side; }
     }
     return LNN_OK;
 }
@@ -220,7 +231,14 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->d_capture) hipFree(ctx->d_capture);
     for (int i = 0; i < ctx->nsub; i++) { hipStreamSynchronize(ctx->sub[i]); hipStreamDestroy(ctx->sub[i]); hipEventDestroy(ctx->sub_done[i]); }
     if (ctx->ev_start) hipEventDestroy(ctx->ev_start);
-    if (ctx->has_side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); hipEventDestroy(ctx->side_done); hipEventDestroy(ctx->fork_ev); hipEventDestroy(ctx->join_ev); }
+    if (ctx->has_side && ctx->sib[1] != ctx->side) { hipStreamSynchronize(ctx->sib[1]); hipStreamDestroy(ctx->sib[1]); }
+    if (ctx->has_side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); hipEventDestroy(ctx->side_done); }
+    for (int i = 0; i < LNN_MAXSUB; i++) {
+        if (ctx->fork_ev[i]) hipEventDestroy(ctx->fork_ev[i]);
+        if (ctx->join_ev[i]) hipEventDestroy(ctx->join_ev[i]);
+        if (ctx->lev_fork_ev[i]) hipEventDestroy(ctx->lev_fork_ev[i]);
+        if (ctx->lev_join_ev[i]) hipEventDestroy(ctx->lev_join_ev[i]);
+    }
     if (ctx->d_sin) hipFree(ctx->d_sin);
     if (ctx->d_wt) hipFree(ctx->d_wt);
     if (ctx->d_clsidx) hipFree(ctx->d_clsidx);
@@ -610,6 +628,7 @@ struct EncodeCall {             /* one LINNEAmd_EncodeFramesDevice call */
 };
 struct Chunk {                  /* one chunk of it on its stream */
     LINNEAmdContext *ctx; hipStream_t st; const HostShape *hs;
+    hipStream_t sib; uint32_t slot;     /* its sibling stream (valid when the context has a side stream) and its stream slot: the index of its events */
     uint32_t C, S, f0, Fc; uint64_t CF, J;
     const uint32_t *idx;        /* class slot of each of its frames (host copy) */
     Plan p; LnnChunkForms forms;
@@ -658,6 +677,7 @@ static int chunk_setup(Chunk &k, LINNEAmdContext *ctx, const EncodeCall &e, uint
     const uint32_t S = e.S;
     k.ctx = ctx; k.hs = &e.hs; k.C = e.C; k.S = S; k.f0 = f0;
     k.st = e.split.use_sub ? ctx->sub[slot] : ctx->stream;
+    k.slot = slot; k.sib = ctx->sib[slot & 1u];
     k.Fc = (e.num_frames - f0 < e.split.chunk) ? (e.num_frames - f0) : (uint32_t)e.split.chunk;
     k.CF = (uint64_t)k.Fc * e.C; k.J = k.CF * e.hs.R;
     k.idx = ctx->cur_idx + f0;
@@ -721,23 +741,50 @@ static int launch_prep(Chunk &k)
     return LNN_OK;
 }
 
+/* the sibling stream of a chunk whose order-128 Levinson launch runs beside its lag kernels: the odd stream slots get a stream of
+ * their own at the first such chunk (failing that they share the side stream: slower, same results) */
+static void sibling_for_levinson(Chunk &k)
+{
+    LINNEAmdContext *ctx = k.ctx;
+    if ((k.slot & 1u) && ctx->sib[1] == ctx->side && !ctx->sib1_tried) {
+        ctx->sib1_tried = 1;
+        if (hipStreamCreateWithFlags(&ctx->sib[1], hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->sib[1] = ctx->side; }
+    }
+    k.sib = ctx->sib[k.slot & 1u];
+}
+
 /* lags of layer l: the lanes = jobs kernels for the frames they take (hist_takes), the general kernels for the others */
 static int launch_lags(Chunk &k, const Pass &ps, uint32_t l)
 {
     LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
     const uint32_t P = k.hs->P[l];
+    if (lf.lev_beside && !lf.lev_inline) sibling_for_levinson(k);
     if (lf.beside) {
-        HIPCHK(ctx, hipEventRecord(ctx->fork_ev, st)); HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->fork_ev, 0));
-        const int sp_ = span_begin(ctx, LINNE_AMD_T_AUTOCORR, ctx->side); dispatch_autocorr2(ctx->side, q, l, ps.cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, ctx->side);
-        HIPCHK(ctx, hipEventRecord(ctx->join_ev, ctx->side));
+        HIPCHK(ctx, hipEventRecord(ctx->fork_ev[k.slot], st)); HIPCHK(ctx, hipStreamWaitEvent(k.sib, ctx->fork_ev[k.slot], 0));
+        const int sp_ = span_begin(ctx, LINNE_AMD_T_AUTOCORR, k.sib); dispatch_autocorr2(k.sib, q, l, ps.cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, k.sib);
+        HIPCHK(ctx, hipEventRecord(ctx->join_ev[k.slot], k.sib));
     }
     if (lf.hist_layer) {
         for (int w = 0; w < 3; w++) {
             if (P == 64u && w == 1) continue;
-            const int sp_ = span_begin(ctx, LINNE_AMD_T_HIST_P + w, st); (void)launch_autocorr_hist(st, q, l, ps.cur, w); span_end(ctx, sp_, st);
+            const int sp_ = span_begin(ctx, LINNE_AMD_T_HIST_P + w, st); (void)launch_autocorr_hist(st, q, l, ps.cur, w, w == 2 && lf.lev_beside); span_end(ctx, sp_, st);
+            if (w == 0 && lf.lev_beside) {
+                /* Trial 0's lags are there (those of the frames the general kernel has: in stream order on the sibling, in front of the
+                 * solver): the order-128 Levinson launch starts on the sibling, BEFORE the lag kernels behind this one are
+                 * launched.  Its 130 KB blocks and k_autocorr_hist<P,1>'s 66 KB blocks cannot share a CU: while that kernel runs the
+                 * two compete for whole CUs; once k_autocorr_sub follows, its small-LDS blocks fit in beside the solver's.  It takes
+                 * no timing span of its own; launch_levinson joins.  (lev_inline: the solver on the chunk's own stream -- behind
+                 * the general kernel's lags too, which only an event orders there.) */
+                const LnnLevLaunch &v = lf.lev[0];
+                const hipStream_t ls = lf.lev_inline ? st : k.sib;
+                if (lf.lev_inline && lf.beside) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join_ev[k.slot], 0));
+                if (!lf.lev_inline) { HIPCHK(ctx, hipEventRecord(ctx->lev_fork_ev[k.slot], st)); HIPCHK(ctx, hipStreamWaitEvent(k.sib, ctx->lev_fork_ev[k.slot], 0)); }
+                hipLaunchKernelGGL(k_levinson_lds, dim3((ps.J + 63) / 64, v.u), dim3(v.threads), v.lds, ls, q, l, v.t, v.ride);
+                if (!lf.lev_inline) HIPCHK(ctx, hipEventRecord(ctx->lev_join_ev[k.slot], k.sib));
+            }
         }
     }
-    if (lf.beside) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join_ev, 0));
+    if (lf.beside) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->join_ev[k.slot], 0));
     else if (!lf.hist_all) {
         const int sp_ = span_begin(ctx, (P >= 32u) ? LINNE_AMD_T_AUTOCORR : LINNE_AMD_T_AUTOCORR_SHORT, st); dispatch_autocorr2(st, q, l, ps.cur, ctx->na_max, (ctx->prod_ok >> l) & 1); span_end(ctx, sp_, st);
     }
@@ -748,9 +795,10 @@ static void launch_levinson(Chunk &k, const Pass &ps, uint32_t l)
 {
     LINNEAmdContext *ctx = k.ctx; hipStream_t st = k.st; const Plan &q = *ps.q; const LnnLayerForms &lf = ps.forms->layer[l];
     const uint32_t P = k.hs->P[l], maxu = P < 128u ? P : 128u;
+    if (lf.lev_beside && !lf.lev_inline) (void)hipStreamWaitEvent(st, ctx->lev_join_ev[k.slot], 0);      /* lev[0] went ahead on the sibling (launch_lags) */
     const int sp_ = span_begin(ctx, LINNE_AMD_T_LEVINSON, st);
     if (lf.lev_wave) hipLaunchKernelGGL(k_levinson_wave, dim3(ps.J, 2u * maxu - 1u), dim3(64), 0, st, q, l);
-    else for (uint32_t i = 0; i < lf.nlev; i++) {
+    else for (uint32_t i = lf.lev_beside ? 1u : 0u; i < lf.nlev; i++) {
         const LnnLevLaunch &v = lf.lev[i];
         hipLaunchKernelGGL(k_levinson_lds, dim3((ps.J + 63) / 64, v.u), dim3(v.threads), v.lds, st, q, l, v.t, v.ride);
     }
@@ -1028,7 +1076,7 @@ extern "C" int LINNEAmd_EncodeFramesDevice(struct LINNEAmdContext *ctx, const st
     /* join */
     if (loop_ret != LNN_OK) {       /* what was forked is waited for before the error goes back (the callers synchronise ctx->stream only) */
         if (sp.use_sub) for (uint32_t i = 0; i < sp.nsub; i++) (void)hipStreamSynchronize(ctx->sub[i]);
-        if (ctx->has_side) (void)hipStreamSynchronize(ctx->side);
+        if (ctx->has_side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamSynchronize(ctx->sib[1]); }
         return loop_ret;
     }
     if (ctx->has_side) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
@@ -3121,7 +3169,7 @@ extern "C" int64_t lnn_forms_query(int mode, const struct LINNEAmdShape *shape, 
                     for (uint32_t f = 0, g = 0; lnn_next_left_run(&lf, meta + f0, Fc, g, &f, &g); nleft++) { if (!nleft) left_first = f; left_frames += g - f; }
                 PUT(lf.fir_spec); PUT(lf.hist_layer); PUT(lf.hist_all); PUT(lf.beside); PUT(lf.lev_wave); PUT(lf.nlev); PUT(lf.nlev ? lf.lev[0].ride : 0); PUT(lf.last_layer);
                 PUT(lf.long_any); PUT(lf.long_all); PUT(lf.search_form); PUT(lf.fir_small); PUT(lf.sel_wave); PUT(lf.fwd_loss); PUT(lf.fwd_loss_mw); PUT(lf.forward);
-                PUT(lf.forward_walk); PUT(nleft); PUT(left_first); PUT(left_frames); PUT(lf.long_mask); PUT(0); PUT(0); PUT(0);
+                PUT(lf.forward_walk); PUT(nleft); PUT(left_first); PUT(left_frames); PUT(lf.long_mask); PUT(lf.lev_beside); PUT(lf.lev_carrier); PUT(lf.lev_carrier < lf.nlev ? lf.lev[lf.lev_carrier].ride : LNN_MAXT);
             }
         }
     }

@@ -38,6 +38,10 @@
 #define LNN_LEV_MAXRIDE 3u              /* short Levinson trials that ride with the one-unit trial: LEV_MAXRIDE */
 #define LEV_LDS(np_) (sizeof(double) * 64 * (size_t)(2 * (np_) + 3))       /* LDS columns of one Levinson problem set of order np_ */
 #define LEV_LDS_BUDGET ((size_t)160 * 1024)                                   /* LDS of a CU */
+#define LNN_SUB_TILE_SMALL 16u          /* tile depth of the small-LDS k_autocorr_sub (every other caller of autocorr_rows: 32) */
+#define LNN_SUB_SMALL_LDS ((size_t)8 * (2 * LNN_SUB_TILE_SMALL * 65 + 2 * LNN_MAXT * 32))      /* its static LDS: tile[2][16][65] + wts_mem, 20 736 bytes */
+#define LNN_LEV_BESIDE_MIN 32768u       /* jobs of a chunk from which the order-128 Levinson launch runs beside the lag kernels */
+#define LNN_LEV_BESIDE_DEFAULT 1        /* the size rule is in force (0: only LINNE_AMD_LEV_BESIDE=1 turns the form on) */
 
 /* one distinct frame length of a batch (full frames, the ragged tail, ...) */
 struct DevClass {
@@ -101,6 +105,7 @@ struct LnnKnobs {
     /* read once, when the context is created (lnn_knobs_read_context) */
     int fwd_loss;                       /* LINNE_AMD_FWD_LOSS: last layer's forward pass and loss in one kernel (k_fwd_loss); -1 = by batch size */
     int lev_ride;                       /* short Levinson trials ride along with the one-unit trial (LINNE_AMD_LEV_RIDE, default 1) */
+    int lev_beside;                     /* LINNE_AMD_LEV_BESIDE: the long layer's order-128 Levinson launch on the chunk's sibling stream beside the short-trial lags; 0 / 1 never / always, -1 = by chunk size; 2 (a measuring knob) = the same launches -- riders moved, small-LDS lag form -- all on the chunk's own stream, nothing overlapped */
     int lev_wave;                       /* batches of <= 64 jobs: a wave per Levinson problem (LINNE_AMD_LEV_WAVE, default 1) */
     int search_two;                     /* k_search_long in two passes over the window, five waves per SIMD (LINNE_AMD_SEARCH_TWO) */
     int search_job;                     /* k_search_long with one block per job that walks the job's tiles: 1 always, 0 never ((jobs, tiles) blocks), -1 by the size of the batch (LINNE_AMD_SEARCH_JOB, default -1) */
@@ -128,6 +133,7 @@ static inline void lnn_knobs_read_context(LnnKnobs *k)
     k->fir_spec = lnn_env_int("LINNE_AMD_SPECULATE", 1);
     k->lev_ride = lnn_env_int("LINNE_AMD_LEV_RIDE", 1);
     k->lev_wave = lnn_env_int("LINNE_AMD_LEV_WAVE", 1);
+    k->lev_beside = lnn_env_int("LINNE_AMD_LEV_BESIDE", -1);
     k->search_two = lnn_env_int("LINNE_AMD_SEARCH_TWO", 1);
     k->search_job = lnn_env_int("LINNE_AMD_SEARCH_JOB", -1);
     k->fwd_loss = lnn_env_int("LINNE_AMD_FWD_LOSS", -1);
@@ -374,6 +380,9 @@ struct LnnLayerForms {
     bool hist_layer, hist_all;          /* lanes = jobs lag kernels launched / they take every frame of the chunk (no general kernel then) */
     bool beside;                        /* the general lag kernel runs beside them on the side stream */
     bool lev_wave;                      /* k_levinson_wave: all trials in one launch */
+    bool lev_inline;                    /* ... the same launches in the same order, but lev[0] on the chunk's own stream (LINNE_AMD_LEV_BESIDE=2: what the forms cost without the overlap) */
+    bool lev_beside;                    /* lev[0] (order 128, no riders) runs on the chunk's sibling stream beside k_autocorr_hist<P,1> and the small-LDS k_autocorr_sub */
+    uint32_t lev_carrier;               /* index in lev[] of the launch the riding waves go with: 0, or 1 when lev_beside (LNN_MAXT: none rides) */
     uint32_t nlev; LnnLevLaunch lev[LNN_MAXT];          /* else: these k_levinson_lds launches */
     bool last_layer;                    /* k_last_layer + k_select(2), nothing else of this layer's search and loss */
     bool long_any, long_all;            /* k_search_long is launched / takes every frame (no other search kernel then) */
@@ -459,12 +468,32 @@ static inline void lnn_chunk_forms(const LnnChunkIn *in, LnnChunkForms *cf)
          * order on LDS columns -- except that the short trials whose columns fit beside the one-unit trial's ride along with it on
          * a second wave (k_levinson_lds) */
         lf.lev_wave = J <= 64u && k.lev_wave;
+        lf.lev_carrier = LNN_MAXT;
         if (!lf.lev_wave) {
             uint32_t ride = LNN_MAXT;
             for (uint32_t t = 1, u = 2; u <= maxu && k.lev_ride; u <<= 1, t++)
                 if (LEV_LDS(P) + LNN_LEV_MAXRIDE * LEV_LDS(P / u) <= LEV_LDS_BUDGET) { ride = t; break; }
+            /* The order-128 launch is one 130 KB block per CU, a lone wave on one of its four SIMDs: 2.8 ms of the 60-minute step with
+             * the chip nearly empty.  It needs only trial 0's lags (k_autocorr_hist<P,0>), so it runs on the chunk's sibling stream
+             * beside k_autocorr_hist<P,1> and k_autocorr_sub, whose small-LDS form (LNN_SUB_SMALL_LDS) fits in the 31 232 bytes the
+             * solver leaves.  The riding waves need k_autocorr_sub's lags: they move to the trial-1 launch.  Only where the lanes = jobs lag
+             * kernels run (hist_layer), only for order 128 (an order-64 solver block is 67 KB: the lag kernels fit beside it as
+             * they are), and only for a chunk whose solver has more than a block per CU to hide -- LNN_LEV_BESIDE_MIN jobs.
+             * Measured (profiles/ab_lev_beside.txt; two streams, three alternating runs each against the build without the form, every
+             * run with the form ahead of every run without): the 60-minute batch, two chunks of 62 016 jobs, 70.56 -> 69.01 ms per
+             * step; a 32-minute batch, two chunks of 33 076 jobs -- the smallest a two-stream call makes are 32 768 (lnn_call_split) --
+             * 40.83 -> 40.25.  The threshold is that smallest two-stream chunk: a smaller chunk runs alone on one stream, where the
+             * overlap gave 0.2-0.5 ms at 124 032 jobs and was not measured below; a group of EncodeWhole (31 008 jobs) and block-at-a-
+             * time calls keep the launches they had.  The forms alone cost 0.67 ms of the 60-minute step (LINNE_AMD_LEV_BESIDE=2: the
+             * riders with the trial-1 launch, the 16-position tiles of k_autocorr_sub), the overlap gives 2.2 back.
+             * LINNE_AMD_LEV_BESIDE=0/1 forces the size term either way. */
+            const bool beside_size = k.lev_beside >= 0 ? (k.lev_beside != 0) : (LNN_LEV_BESIDE_DEFAULT && J >= LNN_LEV_BESIDE_MIN);
+            lf.lev_beside = beside_size && lf.hist_layer && P == 128u && in->has_side && ride >= 2u && ride < LNN_MAXT
+                    && LEV_LDS(P / 2u) + LNN_LEV_MAXRIDE * LEV_LDS(P >> ride) <= LEV_LDS_BUDGET && LEV_LDS(P) + LNN_SUB_SMALL_LDS <= LEV_LDS_BUDGET;
+            lf.lev_inline = lf.lev_beside && k.lev_beside == 2;
+            if (ride < LNN_MAXT) lf.lev_carrier = lf.lev_beside ? 1u : 0u;
             for (uint32_t t = 0, u = 1; u <= maxu && t < (ride < LNN_MAXT ? ride : LNN_MAXT); u <<= 1, t++) {
-                const bool carry = (t == 0 && ride < LNN_MAXT);
+                const bool carry = (t == lf.lev_carrier);
                 LnnLevLaunch &v = lf.lev[lf.nlev++];
                 v.t = t; v.u = u;
                 v.lds = LEV_LDS(P / u) + (carry ? LNN_LEV_MAXRIDE * LEV_LDS(P >> ride) : 0);

@@ -503,26 +503,30 @@ __device__ __forceinline__ void autocorr_shared(const Plan &p, uint32_t layer, u
  * m arrives -- the reference's products in the reference's order (the pairs that would reach past a unit's end simply never
  * form; in the padded-stream kernels they add +0.0).  No window generator, no stream bookkeeping: 1 + 2 JN multiply/adds
  * per sample.  Units end at multiples of the finest unit (a multiple of 4 samples), checked once per 4 samples. */
-template <int P, bool L0, int TT, int J0, int JN, int NW>
+/* T: positions per tile (32; k_autocorr_sub's small-LDS form: 16 -- the tile loop is then unrolled over the TU = 2 tiles an order-32
+ * ring spans, so that ring slots stay compile-time; same products, same adds, same order). */
+template <int P, bool L0, int TT, int J0, int JN, int NW, int T = 32>
 __device__ __forceinline__ void autocorr_rows(const Plan &p, uint32_t layer, uint32_t cur, uint32_t row0, uint32_t nrows, uint32_t rstride,
-        uint32_t na, const DevClass &c0, uint32_t wave, uint32_t lane, double (*xt)[32][65], double (*wtile)[32])
+        uint32_t na, const DevClass &c0, uint32_t wave, uint32_t lane, double (*xt)[T][65], double (*wtile)[32])
 {
-    constexpr int NT = AcCfg<P>::NT, T = 32, NLD = L0 ? 8 : 16, PT = P >> TT;      /* PT: order of my trial = ring length (divides 4) */
+    constexpr int NT = AcCfg<P>::NT, NLD = L0 ? T / 4 : T / 2, PT = P >> TT;      /* PT: order of my trial = ring length (divides 4) */
     constexpr int NSLOT = (NLD + NW - 1) / NW;
-    static_assert(PT <= 32 && T % PT == 0 && J0 + JN <= PT + 1, "register rings: sample m lives in slot m % PT, and the tile loop is unrolled over T samples");
+    constexpr int TU = (PT > T) ? PT / T : 1;                /* tiles per trip of the tile loop */
+    constexpr uint32_t RPI = L0 ? 256u / T : 128u / T, LPR = 64u / RPI;       /* rows per load instruction, lanes per row */
+    static_assert((T == 32 || T == 16) && PT <= 32 && (TU * T) % PT == 0 && J0 + JN <= PT + 1, "register rings: sample m lives in slot m % PT, and the tile loop is unrolled over TU * T samples");
     typedef typename std::conditional<L0, int4, lnn_d2>::type XV;
     const uint32_t ntiles = na / T, seg = na >> (NT - 1), nt = na >> TT;
     uint32_t myrow = row0 + lane; if (myrow >= nrows) myrow = nrows - 1;
     const bool store = (row0 + lane) < nrows;
     double *out = p.acorr + ((size_t)myrow * rstride * LNN_MAXT + TT) * LNN_ACW + J0;
-    /* tile loads: L0 -- instruction k covers rows 8k + lane/8, samples 4(lane%8)..+3; else rows 4k + lane/16, samples 2(lane%16)..+1;
+    /* tile loads (T = 32): L0 -- instruction k covers rows 8k + lane/8, samples 4(lane%8)..+3; else rows 4k + lane/16, samples 2(lane%16)..+1;
      * wave w issues the instructions k = w, w + NW, ... */
-    const uint32_t lrow = L0 ? (lane >> 3) : (lane >> 4), lsmp = L0 ? 4u * (lane & 7u) : 2u * (lane & 15u);
+    const uint32_t lrow = lane / LPR, lsmp = (L0 ? 4u : 2u) * (lane % LPR);
     const void *src[NSLOT];
 #pragma unroll
     for (int i = 0; i < NSLOT; i++) {
         const uint32_t k = wave + (uint32_t)i * NW;
-        uint32_t r = row0 + (L0 ? 8u : 4u) * (k < (uint32_t)NLD ? k : 0u) + lrow; if (r >= nrows) r = nrows - 1;
+        uint32_t r = row0 + RPI * (k < (uint32_t)NLD ? k : 0u) + lrow; if (r >= nrows) r = nrows - 1;
         if (L0) src[i] = p.xint + (size_t)r * p.S + lsmp;                   /* rows are channel-frames */
         else src[i] = p.sig + ((size_t)r * 2 + cur) * p.S + lsmp;
     }
@@ -548,7 +552,7 @@ __device__ __forceinline__ void autocorr_rows(const Plan &p, uint32_t layer, uin
         for (int i = 0; i < NSLOT; i++) {
             const uint32_t k = wave + (uint32_t)i * NW;
             if (k < (uint32_t)NLD) {
-                const uint32_t r = (L0 ? 8u : 4u) * k + lrow;
+                const uint32_t r = RPI * k + lrow;
                 if (L0) {
                     const int4 v = *(const int4 *)&pre[i];
                     xt[buf][lsmp][r] = (double)v.x * p.scale; xt[buf][lsmp + 1][r] = (double)v.y * p.scale;
@@ -579,8 +583,10 @@ __device__ __forceinline__ void autocorr_rows(const Plan &p, uint32_t layer, uin
     vcur = xv[0] * wv[0];
     uint32_t to_b = seg, bcount = 0, unit = 0;
 #pragma unroll 1
-    for (uint32_t ti = 0; ti < ntiles; ti++) {
-        const uint32_t buf = ti & 1u;
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += TU) {
+#pragma unroll
+      for (int h = 0; h < TU; h++) {                                /* (TU > 1: the analysis length is whole finest units of 2^(NT-1) x 16 samples, ntiles a multiple of TU) */
+        const uint32_t ti = t0 + (uint32_t)h, buf = ti & 1u;
         if (ti + 1 < ntiles) issue(ti + 1);
 #pragma unroll
         for (int g = 0; g < T / 4; g++) {
@@ -596,8 +602,8 @@ __device__ __forceinline__ void autocorr_rows(const Plan &p, uint32_t layer, uin
                 for (int j = 0; j < JN; j++) r[j] += q[j];          /* adds of the previous sample's products */
                 const double v = vcur;
 #pragma unroll
-                for (int j = 0; j < JN; j++) q[j] = (J0 + j == 0) ? (v * v) : (ring[((4 * g + i - (J0 + j)) % PT + PT) % PT] * v);
-                ring[(4 * g + i) % PT] = v;
+                for (int j = 0; j < JN; j++) q[j] = (J0 + j == 0) ? (v * v) : (ring[((h * T + 4 * g + i - (J0 + j)) % PT + PT) % PT] * v);
+                ring[(h * T + 4 * g + i) % PT] = v;
                 vcur = (i < 3) ? (xv[(i + 1) & 3] * wv[(i + 1) & 3]) : (nx[0] * nw[0]);          /* window the next one */
             }
 #pragma unroll
@@ -621,6 +627,7 @@ __device__ __forceinline__ void autocorr_rows(const Plan &p, uint32_t layer, uin
                 }
             }
         }
+      }
     }
 }
 
@@ -892,13 +899,16 @@ template <int P> static void launch_autocorr2(hipStream_t st, const Plan &p, uin
 
 /* the long layer's lanes = jobs kernels, for the frames they take (hist_takes); which: 0 / 1 the trials of order P and P/2
  * (k_autocorr_hist), 2 the shorter ones (k_autocorr_sub).  Returns false when the layer has no such kernel. */
-static bool launch_autocorr_hist(hipStream_t st, const Plan &p, uint32_t layer, uint32_t cur, int which)
+/* which: 0 / 1 k_autocorr_hist<P, 0 / 1>, 2 k_autocorr_sub; small_sub: its small-LDS form (order 128 only: the form that fits beside
+ * the order-128 Levinson block) */
+static bool launch_autocorr_hist(hipStream_t st, const Plan &p, uint32_t layer, uint32_t cur, int which, bool small_sub = false)
 {
     const RowRuns &rr = p.runs[1];
     const dim3 grid(rr.blk_begin[rr.n]);
     if (p.P[layer] == 128u) {
         if (which == 0) hipLaunchKernelGGL((k_autocorr_hist<128, 0>), grid, dim3(64 * HIST_WAVES(128)), 0, st, p, layer, cur);
         else if (which == 1) hipLaunchKernelGGL((k_autocorr_hist<128, 1>), grid, dim3(64 * HIST_WAVES(64)), 0, st, p, layer, cur);
+        else if (small_sub) hipLaunchKernelGGL((k_autocorr_sub<128, LNN_SUB_TILE_SMALL>), grid, dim3(640), 0, st, p, layer, cur);
         else hipLaunchKernelGGL((k_autocorr_sub<128>), grid, dim3(640), 0, st, p, layer, cur);
         return true;
     }

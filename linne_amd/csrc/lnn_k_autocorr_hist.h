@@ -178,12 +178,19 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
 
 /* k_autocorr_sub<P>: the trials of orders 32 .. 1 of a layer of order P >= 64, for the frames hist_takes: autocorr_rows
  * with its register rings, 10 waves per 64 jobs (lags per wave: 9 8 8 8 | 9 8 | 9 | 5 | 3 | 2). */
-template <int P>
+/* T: positions per tile.  32 is the form every chunk took until the order-128 Levinson launch moved beside this kernel; 16
+ * (LNN_SUB_TILE_SMALL) is the small-LDS form, 20 736 bytes of LDS instead of 37 376: a block of it fits in the 31 232 bytes an order-128
+ * Levinson block leaves of a CU's 160 KB.  Twice the barriers per sample; the arithmetic is the same, bit for bit. */
+template <int P, int T = 32>
 __global__ __launch_bounds__(640, 3) void k_autocorr_sub(Plan p, uint32_t layer, uint32_t cur)
 {
     constexpr int NT = AcCfg<P>::NT, NW = 10, T0 = NT - 6;     /* T0: the trial of order 32 */
-    __shared__ double tile[2][32][65];
+    __shared__ double tile[2][T][65];
     __shared__ __attribute__((aligned(16))) double wts_mem[2 * NT * 32];
+    static_assert(T == 32 || sizeof(double) * (2 * T * 65 + 2 * NT * 32) <= LNN_SUB_SMALL_LDS, "lnn_forms.h counts on the small form's LDS");
+    /* the waves of order 32 walk two tiles per trip of autocorr_rows' tile loop when T < 32, the others one: every wave meets the same
+     * barriers only if the tile count is even.  hist_takes admits analysis lengths that are whole multiples of 16 << (NT - 1) only. */
+    static_assert((16 << (NT - 1)) % (2 * T) == 0, "hist_takes must imply an even number of tiles");
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const RowRuns &rr = p.runs[1];
     const uint32_t b = gridDim.x - 1u - blockIdx.x;
@@ -197,7 +204,7 @@ __global__ __launch_bounds__(640, 3) void k_autocorr_sub(Plan p, uint32_t layer,
     if (!__all(ci == ci0) || !hist_takes(p, layer, c0)) return;
     const uint32_t na = (uint32_t)__builtin_amdgcn_readfirstlane((int)c0.na);
     double (*wtile)[32] = (double (*)[32])wts_mem;
-#define SUB_RUN(T_, J0_, JN_) autocorr_rows<P, false, T_, J0_, JN_, NW>(p, layer, cur, row0, nrows, 1u, na, c0, wave, lane, tile, wtile)
+#define SUB_RUN(T_, J0_, JN_) autocorr_rows<P, false, T_, J0_, JN_, NW, T>(p, layer, cur, row0, nrows, 1u, na, c0, wave, lane, tile, wtile)
     switch (wave) {
         case 0: SUB_RUN(T0, 0, 9); break;      case 1: SUB_RUN(T0, 9, 8); break;      case 2: SUB_RUN(T0, 17, 8); break;   case 3: SUB_RUN(T0, 25, 8); break;
         case 4: SUB_RUN(T0 + 1, 0, 9); break;  case 5: SUB_RUN(T0 + 1, 9, 8); break;  case 6: SUB_RUN(T0 + 2, 0, 9); break;

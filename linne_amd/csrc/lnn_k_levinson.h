@@ -94,8 +94,9 @@ __device__ __forceinline__ void levinson_problem(const Plan &p, uint32_t layer, 
 }
 
 /* grid = (job groups, units of trial t).  Wave 0 of a block solves problem (t, blockIdx.y).  A block may carry riding waves
- * (blockDim 64 * (1 + nride), `ride` < LNN_MAXT): together they solve every problem of the trials ride, ride+1, ... of the
- * same 64 jobs, dealt out in turn, one after the other in each wave's own LDS columns behind wave 0's.  The long layer's
+ * (blockDim 64 * (1 + nride), `ride` < LNN_MAXT): together the riding waves of the gridDim.y blocks of the same 64 jobs solve every
+ * problem of the trials ride, ride+1, ... of those jobs, dealt out in turn over (blockIdx.y, wave) -- each problem exactly once --
+ * one after the other in each wave's own LDS columns behind wave 0's.  The long layer's
  * one-unit trial holds 130 KB of LDS -- one wave per CU, on one of its four SIMDs -- so the many tiny problems of its short
  * trials (latency, not arithmetic) ride along on the other three instead of taking launches of their own. */
 #define LEV_MAXRIDE 3
@@ -104,13 +105,13 @@ __global__ __launch_bounds__(64 * (1 + LEV_MAXRIDE)) void k_levinson_lds(Plan p,
     extern __shared__ __attribute__((aligned(16))) double lev_lds[];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, job0 = blockIdx.x * 64;
     if (wave == 0) { levinson_problem(p, layer, t, blockIdx.y, lev_lds, lane, job0); return; }
-    const uint32_t nride = (blockDim.x >> 6) - 1u;
+    const uint32_t nride = (blockDim.x >> 6) - 1u, nseat = nride * gridDim.y, seat = blockIdx.y * nride + (wave - 1u);
     double *mine = lev_lds + (size_t)(2 * (p.P[layer] >> t) + 3) * 64 + (size_t)(wave - 1u) * (2 * (p.P[layer] >> ride) + 3) * 64;
     const uint32_t maxu = p.P[layer] < (uint32_t)LNN_MAXU ? p.P[layer] : (uint32_t)LNN_MAXU;
     uint32_t q = 0;
     for (uint32_t tt = ride, u = 1u << ride; u <= maxu; tt++, u <<= 1)
         for (uint32_t unit = 0; unit < u; unit++, q++)
-            if (q % nride == wave - 1u) levinson_problem(p, layer, tt, unit, mine, lane, job0);
+            if (q % nseat == seat) levinson_problem(p, layer, tt, unit, mine, lane, job0);
 }
 
 /* The same recursion for a SMALL batch (block-at-a-time calls: a handful of jobs): a WAVE per (job, trial, unit) problem, all
