@@ -109,7 +109,7 @@ def base_frames(nch, bits, block, seed):
     return out, np.array(loud)
 
 
-def make_batch(F, nch, bits, block, preset, seed, keep_last_layer=False, loud_every_other=False):
+def make_batch(F, nch, bits, block, preset, seed, keep_last_layer=False, loud_every_other=False, nragged=NRAGGED):
     rng = np.random.default_rng(seed)
     bases, loud = base_frames(nch, bits, block, seed)
     bmap = rng.integers(0, B, size=F)
@@ -117,8 +117,8 @@ def make_batch(F, nch, bits, block, preset, seed, keep_last_layer=False, loud_ev
         bmap[1::2] = rng.choice(loud, size=len(bmap[1::2]))
     ns = np.full(F, block, dtype=np.uint32)
     pool = ragged_pool(preset, block, keep_last_layer)
-    where = rng.choice(F, size=NRAGGED, replace=False)
-    ns[where] = rng.choice(pool, size=NRAGGED)
+    where = rng.choice(F, size=nragged, replace=False)
+    ns[where] = rng.choice(pool, size=nragged)
     ns[where[:len(pool)]] = pool                                # every length of the pool occurs
     assert len(set(ns.tolist())) <= 16, "an encode call takes up to 16 distinct frame lengths"
     frames = bases[bmap]
