@@ -358,6 +358,12 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_IB_HEADERS,             /* 69: gathering every stream's header bytes (k_ib_headers) */
     LINNE_AMD_T_IB_BEHIND               /* 70: the place behind a chain that ends early (k_ib_behind) */
 };
+/* further kinds, numbered on (`which` is a plain integer): cutting and joining streams (LINNEAmd_SpliceStreamsDevice, a call of its own:
+ * the kinds of LINNEAmd_DecodeWindowsDevice and LINNEAmd_EncodeStreamsDevice for its edge blocks, then one launch of each of these) */
+enum LINNEAmdSpliceTimingKind {
+    LINNE_AMD_SPLICE_T_COPY = 71,           /* every run of bytes of every output (k_sp_copy) */
+    LINNE_AMD_SPLICE_T_HEADER = 72          /* the outputs' stream headers (k_sb_header) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -583,6 +589,65 @@ int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNE
         const struct LINNEAmdPcmLayout *layouts /* [num_tracks] */, uint32_t num_tracks, uint32_t group_frames);
 int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         struct LINNEAmdPcmLayout *layouts /* [num_windows], in/out */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
+ * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder
+ * carries nothing from one block to the next (linne_decoder.c:564-668: a block brings its own sample count, parameters and
+ * de-emphasis history), so a stream that keeps untouched blocks byte for byte is a valid .lnn stream; only the blocks a cut's ends
+ * lie inside are decoded and encoded again.
+ * The stream: output k holds the 30 bytes LINNEEncoder_EncodeHeader writes from the header of its first cut's stream with num_samples
+ * set to the sum of its cuts, then, cut by cut and in sample order, one block per source block the cut overlaps:
+ *   - a source block that lies wholly inside the cut is its size + 6 bytes, unchanged (COMPRESS, SILENT and RAW alike);
+ *   - a source block the cut covers partly becomes one new block of exactly the covered samples: bytes [30, end) of what
+ *     LINNEEncoder_EncodeWhole writes on a fresh encoder (quirk Q2: its parcor state starts at 0.0) for those samples alone, with the
+ *     stream's shape and the context's -a / -l settings (LINNEAmd_SetAfIterations / SetLearning).
+ * A cut inside one source block gives one such block; the neighbouring edge blocks of two cuts are not merged; a cut of 0 samples
+ * contributes nothing.  An edge block of no more samples than the preset's largest layer (32 at -m 0..1, 64 at -m 2..4, 128 at -m
+ * 5..7) is outside the contract, as such a tail is for the encoder (the reference's own encoder crashes on it); this call refuses an
+ * output that needs one with INVALID_ARGUMENT.
+ * Per output, for it alone (`result`):
+ *   - INVALID_ARGUMENT: a NULL d_out, cuts, index or d_stream; a d_out that is not 4-byte aligned; an index of another device;
+ *     num_cuts == 0 or 0 samples in all; more than 2^32 - 1 samples in all; a cut beyond its stream's num_samples, or beyond the
+ *     samples the blocks of an undamaged stream reach; cuts whose streams differ in channels, bits, rate, block size, preset or MS;
+ *     an edge block outside the contract (above).  These are checked first, over all cuts of the output;
+ *   - then damage, cut by cut: the code of the index's failing block when that block lies at or before the last block the cut
+ *     overlaps (LINNEAmd_DecodeStreamDevice's rule: damage behind the cut does not matter).  An edge block whose Rice codes do not
+ *     end where its size field says gives DecodeStreamDevice's LINNE_APIRESULT_NG;
+ *   - an edge block the encoder refuses gives the code LINNEAmd_EncodeStreamDevice gives for it;
+ *   - INSUFFICIENT_BUFFER with the needed size in out_bytes when the stream is longer than `capacity` (or than 2^32 - 1 bytes).
+ * A failing output has no byte of d_out written and out_bytes 0 (INSUFFICIENT_BUFFER: the needed size), copied_blocks and
+ * encoded_blocks 0, and does not disturb the others.  On OK, copied_blocks and encoded_blocks count the output's blocks of either kind.
+ * The call returns LINNE_APIRESULT_OK when every output is OK, otherwise the result of the lowest-numbered failing output;
+ * GetLastError then reads "splice <i>: " and that output's text.  A HIP error or running out of memory fails the whole call:
+ * LINNE_APIRESULT_NG, in every `result` too.  num_splices == 0 is OK; a NULL ctx, or NULL splices with num_splices > 0,
+ * INVALID_ARGUMENT.
+ * Cost: the edge blocks of all outputs are decoded by ONE LINNEAmd_DecodeWindowsDevice call and encoded by ONE
+ * LINNEAmd_EncodeStreamsDevice call, whose passes cost what those calls document (an analysis call per 16 distinct edge lengths of a
+ * pass); group_frames is handed to both and never changes a byte.  Behind them one copy launch (kind 71) places every run of bytes
+ * of every output -- a cut's whole blocks are contiguous in their source: one run; an edge block: one run -- and one launch (kind 72)
+ * writes the headers, after one upload; then the call's one wait.  Launches, copies, waits and allocations of the call's own steps
+ * do not depend on the number of outputs or cuts.  Scratch (kept by the context, grown with a wait and an allocation more when a
+ * call needs more than any before it): per edge block its samples as int32 and EncodeStreamBound's bytes, 32 bytes per run, 40 per
+ * output.  LINNEAmd_GetLastStreamEncodeCount / GetLastStreamBatchCount report the edge blocks' encode.
+ * Memory: no byte outside [0, stream_bytes) of a source is read, no byte outside [0, out_bytes) of an output is written.  d_out
+ * must be 4-byte aligned; the outputs must not overlap each other or any source.  Enqueued on the context's stream and synchronous.
+ * LINNEAmd_GetLastSpliceCount: of the last such call, which = 0 the outputs written, 1 their copied blocks, 2 their re-encoded
+ * blocks, 3 the copy runs, 4 the bytes they moved, 5 the host synchronisations of the call's own steps (1 once the scratch has grown;
+ * the two calls above add theirs); -1 for a NULL ctx or any other `which`. */
+struct LINNEAmdCut {                            /* samples [first_sample, first_sample + num_samples) of one indexed stream */
+    const struct LINNEAmdStreamIndex *index;    /* of the stream below, same device as the context */
+    const uint8_t *d_stream;                    /* the stream's device bytes, any alignment */
+    uint64_t first_sample, num_samples;
+};
+struct LINNEAmdSplice {                         /* one output stream: its cuts, in order */
+    const struct LINNEAmdCut *cuts; uint32_t num_cuts;
+    uint8_t *d_out; uint64_t capacity;          /* 4-byte aligned; outputs do not overlap each other or any source */
+    uint64_t out_bytes;                         /* out */
+    uint32_t copied_blocks, encoded_blocks;     /* out */
+    int32_t result;                             /* out: this output's LINNEApiResult */
+};
+int LINNEAmd_SpliceStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t num_splices, uint32_t group_frames);
+int64_t LINNEAmd_GetLastSpliceCount(struct LINNEAmdContext *ctx, int which);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_EncodeStreamsDevice", "LINNEAmd_GetLastStreamBatchCount",
     "LINNEAmd_EncodeStreamDeviceLayout", "LINNEAmd_EncodeStreamsDeviceLayout", "LINNEAmd_DecodeWindowsDeviceLayout",
     "LINNEAmd_StreamIndexesCreate", "LINNEAmd_GetLastIndexBatchCount", "LINNEAmd_StreamIndexBlocks", "LINNEAmd_StreamIndexFailure",
+    "LINNEAmd_SpliceStreamsDevice", "LINNEAmd_GetLastSpliceCount",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -79,6 +80,17 @@ class Track(C.Structure):
     """struct LINNEAmdTrack (include/linne_amd.h)"""
     _fields_ = [("header", Header), ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("d_out", C.c_void_p), ("capacity", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("parcor_state", C.c_double), ("result", C.c_int32)]
+
+
+class Cut(C.Structure):
+    """struct LINNEAmdCut (include/linne_amd.h)"""
+    _fields_ = [("index", C.c_void_p), ("d_stream", C.c_void_p), ("first_sample", C.c_uint64), ("num_samples", C.c_uint64)]
+
+
+class Splice(C.Structure):
+    """struct LINNEAmdSplice (include/linne_amd.h)"""
+    _fields_ = [("cuts", C.POINTER(Cut)), ("num_cuts", C.c_uint32), ("d_out", C.c_void_p), ("capacity", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("copied_blocks", C.c_uint32), ("encoded_blocks", C.c_uint32), ("result", C.c_int32)]
 
 
 class PcmLayout(C.Structure):
@@ -163,6 +175,9 @@ def _load():
                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     L.LINNEAmd_EncodeStreamsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Track), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_DecodeWindowsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
+    L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_GetLastStreamBatchCount.restype = C.c_int64
     L.LINNEAmd_GetLastStreamBatchCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
@@ -694,6 +709,78 @@ class Context:
         """the last encode_streams call (its second one, where tracks were encoded again): 0 its shape groups, 1 its passes, 2 its
         EncodeFramesDevice calls"""
         return int(lib.LINNEAmd_GetLastStreamBatchCount(self.h, int(which)))
+
+    def splice_streams(self, splices, group_frames=0, return_codes=False):
+        """cuts of resident .lnn streams joined into new streams in one call, only the blocks a cut goes through re-encoded
+        (include/linne_amd.h LINNEAmd_SpliceStreamsDevice).  splices: a sequence of outputs, each a list of cuts (data, index,
+        first_sample, num_samples): a 1-D uint8 CUDA tensor, its StreamIndex and the range (num_samples None: to the stream's end).
+        -> a list of 1-D uint8 CUDA tensors, views of one allocation at 4-byte-aligned offsets (None for an output that failed).
+        Each output gets the room of its cuts' streams whole plus an edge block's bound per cut end; one that still does not fit is
+        spliced once more at its exact size.  Raises LinneAmdError with .code = the call's result and .codes = the per-output
+        LINNEApiResults when an output fails; with return_codes -> (streams, codes), and only a failure of the whole call raises.
+        group_frames bounds the edge blocks decoded and encoded per pass and never changes a byte.  Afterwards self.last_splice_blocks
+        holds every output's (copied, re-encoded) block counts"""
+        import torch
+        dev = f"cuda:{self.device}"
+        K = len(splices)
+        arr = (Splice * max(K, 1))()
+        keep, rooms = [], []
+        for k, cuts in enumerate(splices):
+            cs = (Cut * max(len(cuts), 1))()
+            room = 30
+            for i, (data, index, first, n) in enumerate(cuts):
+                t = self._stream_bytes(data)
+                assert index.nbytes == t.numel(), f"splice {k}, cut {i}: the index was built for a stream of another length"
+                first = int(first)
+                n = index.header["num_samples"] - first if n is None else int(n)
+                cs[i].index, cs[i].d_stream, cs[i].first_sample = index.h, t.data_ptr(), first
+                cs[i].num_samples = n if n >= 0 else (1 << 64) - 1
+                keep.append(t)
+                room += t.numel() + 2 * (64 + index.header["num_channels"] * index.header["num_samples_per_block"] * 8)
+            keep.append(cs)
+            arr[k].cuts, arr[k].num_cuts = cs, len(cuts)
+            rooms.append(room)
+
+        codes, nbytes, streams = [0] * K, [0] * K, [None] * K
+
+        def run(which, sizes):
+            offs, at = [], 0
+            for n in sizes:
+                offs.append(at)
+                at += (n + 3) & ~3
+            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
+            sub = (Splice * max(len(which), 1))()
+            for j, k in enumerate(which):
+                sub[j].cuts, sub[j].num_cuts = arr[k].cuts, arr[k].num_cuts
+                sub[j].d_out, sub[j].capacity = flat.data_ptr() + offs[j], sizes[j]
+            self._fence()
+            ret = lib.LINNEAmd_SpliceStreamsDevice(self.h, sub, len(which), int(group_frames))
+            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
+            if ret != 0 and not msg.startswith("splice "):              # (a failing output's text starts with its number)
+                raise LinneAmdError(f"SpliceStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
+            for j, k in enumerate(which):
+                codes[k], nbytes[k] = int(sub[j].result), int(sub[j].out_bytes)
+                streams[k] = flat[offs[j]:offs[j] + nbytes[k]] if codes[k] == 0 else None
+                counts[k] = (int(sub[j].copied_blocks), int(sub[j].encoded_blocks))
+            return ret, msg
+
+        counts = [(0, 0)] * K
+        ret, msg = run(list(range(K)), rooms)
+        again = [k for k in range(K) if codes[k] == 3 and nbytes[k] > rooms[k]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
+        if again:
+            run(again, [nbytes[k] for k in again])
+            bad = [k for k in range(K) if codes[k] != 0]
+            ret = codes[bad[0]] if bad else 0
+            msg = f"splice {bad[0]} failed" if bad else ""
+        self.last_splice_blocks = counts
+        if ret != 0 and not return_codes:
+            raise LinneAmdError(f"SpliceStreamsDevice -> {ret}: {msg}", ret, codes)
+        return (streams, codes) if return_codes else streams
+
+    def last_splice_count(self, which):
+        """the last splice_streams call (its second one, where outputs were spliced again): 0 the outputs written, 1 their copied
+        blocks, 2 their re-encoded blocks, 3 the copy runs, 4 the bytes they moved, 5 the host synchronisations of the call's own steps"""
+        return int(lib.LINNEAmd_GetLastSpliceCount(self.h, int(which)))
 
     def encode_frames_host(self, shape, pcm, num_samples=None):
         """numpy int32 [F][C][S] -> numpy (residual, params, stats)"""

@@ -51,9 +51,11 @@
 #include "lnn_k_windows.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
+#include "lnn_k_splice.h"               /* (brings lnn_splice.h: the host's plan of a splice call) */
 /* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
 /* the two timing kinds linne_amd.h numbers by their place behind kind 68 */
 static_assert(LINNE_AMD_T_IB_HEADERS == 69 && LINNE_AMD_T_IB_BEHIND == 70, "the index batch's timing kinds are 69 and 70");
+static_assert(LINNE_AMD_SPLICE_T_COPY == 71 && LINNE_AMD_SPLICE_T_HEADER == 72, "the splice call's timing kinds are 71 and 72");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -114,6 +116,10 @@ struct LINNEAmdContext {
     int span_keep;                      /* EncodeFramesDevice inside EncodeStream(s)Device: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
+    void *spl; uint64_t spl_cap;        /* SpliceStreamsDevice: the fragments' PCM and scratch streams, then the run table and the headers of one call */
+    void *spl_stage; uint64_t spl_stage_cap;    /* pinned: the run table and the headers on the host, uploaded in one copy */
+    int64_t splice_count[6];            /* the last SpliceStreamsDevice call: outputs written, copied blocks, re-encoded blocks, copy runs, bytes copied, its own host synchronisations */
+    int outer_keep;                     /* DecodeWindowsDevice / EncodeStreamsDevice inside SpliceStreamsDevice: keep the call's spans and start event */
     LnnKnobs knob;                      /* every form-selecting knob (lnn_forms.h): some read when the context is created, the others at the top of each call */
 };
 
@@ -249,6 +255,8 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     if (ctx->senc) hipFree(ctx->senc);
     if (ctx->wdec) hipFree(ctx->wdec);
     if (ctx->xcand) hipFree(ctx->xcand);
+    if (ctx->spl) hipFree(ctx->spl);
+    if (ctx->spl_stage) hipHostFree(ctx->spl_stage);
     if (ctx->wstage) hipHostFree(ctx->wstage);
     if (ctx->af_h) hipHostFree(ctx->af_h);
     for (int i = 0; i < LNN_META; i++) { if (ctx->meta_h[i]) hipHostFree(ctx->meta_h[i]); if (ctx->meta_ev[i]) hipEventDestroy(ctx->meta_ev[i]); }
@@ -2417,8 +2425,8 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LI
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     uint32_t *d_fail = (uint32_t *)(wd + o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + o_win);
-    ctx->nspans = 0;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (!ctx->outer_keep) ctx->nspans = 0;
+    if (ctx->timing && !ctx->outer_keep) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(wd, hs_, list_bytes, hipMemcpyHostToDevice, ctx->stream));
     /* 4. the passes */
     for (const WxPass &p : passes) {
@@ -3059,8 +3067,9 @@ static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const stru
     if (groups.empty()) return LNN_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob, as in the single call */
-    ctx->nspans = 0; ctx->span_keep = 1;
-    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
+    if (!ctx->outer_keep) ctx->nspans = 0;
+    ctx->span_keep = 1;
+    if (ctx->timing && !ctx->outer_keep) (void)hipEventRecord(ctx->ev[0], ctx->stream);
     int ret = LNN_OK;
     for (size_t g = 0; ret == LNN_OK && g < groups.size(); g++) ret = sb_group_run(ctx, tracks, host.data(), groups[g].members, groups[g].shape, group_frames);
     if (ret != LNN_OK && !ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: a pass failed with %d", ret);
@@ -3105,6 +3114,284 @@ extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, s
     if (first < 0) return LNN_OK;
     snprintf(ctx->err, sizeof(ctx->err), "track %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
     return host[first].result;
+}
+
+
+/* ================================================================================================
+ * cutting and joining resident streams (lnn_splice.h, lnn_k_splice.h)
+ * ============================================================================================== */
+extern "C" int64_t LINNEAmd_GetLastSpliceCount(struct LINNEAmdContext *ctx, int which)
+{
+    if (!ctx || which < 0 || which > 5) return -1;
+    return ctx->splice_count[which];
+}
+
+/* a buffer of the splice call that grows: the wait and the allocation are the call's own (LINNEAmd_GetLastSpliceCount 5) */
+static int sp_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need, bool pinned)
+{
+    if (*cap >= need) return LNN_OK;
+    ctx->splice_count[5]++;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (*ptr) HIPCHK(ctx, pinned ? hipHostFree(*ptr) : hipFree(*ptr));
+    *ptr = NULL; *cap = 0;
+    if (pinned) HIPCHK(ctx, hipHostMalloc(ptr, need, hipHostMallocDefault)); else HIPCHK(ctx, hipMalloc(ptr, need));
+    *cap = need;
+    return LNN_OK;
+}
+
+struct SpHost { char text[200]; };
+
+/* LNN_OK: every output has its result in outs[] / host[]; anything else fails the whole call */
+static int sp_run(LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t N, uint32_t group_frames, std::vector<SpOutput> &outs, std::vector<SpHost> &host)
+{
+    /* 1. the plan's inputs: the distinct indexes as streams, the cuts, the outputs */
+    std::vector<SpStream> streams;
+    std::vector<const LINNEAmdStreamIndex *> sx;
+    std::vector<SpCut> cuts;
+    std::vector<const uint8_t *> cut_bytes;
+    outs.resize(N); host.resize(N);
+    for (uint32_t k = 0; k < N; k++) {
+        const struct LINNEAmdSplice &s = splices[k];
+        SpOutput &o = outs[k];
+        memset(&o, 0, sizeof(o)); host[k].text[0] = 0;
+        o.cut0 = (uint32_t)cuts.size(); o.ncuts = 0; o.capacity = s.capacity;
+        o.why0 = (!s.d_out || (!s.cuts && s.num_cuts)) ? SP_WHY_NULL : (((uintptr_t)s.d_out & 3u) ? SP_WHY_ALIGN : SP_WHY_NONE);
+        if (o.why0 || !s.num_cuts) continue;
+        if ((uint64_t)cuts.size() + s.num_cuts > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: too many cuts in one call"); return LNN_NG; }
+        o.ncuts = s.num_cuts;
+        for (uint32_t i = 0; i < s.num_cuts; i++) {
+            const struct LINNEAmdCut &c = s.cuts[i];
+            SpCut pc; pc.stream = -1; pc.first = c.first_sample; pc.n = c.num_samples;
+            if (c.index && c.d_stream) {
+                if (c.index->device != ctx->device) o.why0 = SP_WHY_DEVICE;
+                size_t j = sx.size();
+                /* (the cuts of a call mostly name few streams, and neighbours the same one) */
+                while (j > 0 && sx[j - 1] != c.index) j--;
+                if (j == 0) {
+                    const LINNEAmdStreamIndex *x = c.index;
+                    SpStream st;
+                    st.off = x->h_off; st.first = x->h_first; st.size = x->h_size; st.nsmp = x->h_nsmp; st.nb = x->nb; st.num_samples = x->header.num_samples;
+                    st.channels = x->header.num_channels; st.bits = x->header.bits_per_sample; st.rate = x->header.sampling_rate;
+                    st.block = x->header.num_samples_per_block; st.preset = x->header.preset; st.ms = (uint32_t)x->header.ch_process_method;
+                    st.fail_block = x->fail_block; st.fail_code = x->fail_code;
+                    sx.push_back(x); streams.push_back(st); j = sx.size();
+                }
+                pc.stream = (int32_t)(j - 1);
+            }
+            cuts.push_back(pc); cut_bytes.push_back(c.d_stream);
+        }
+    }
+    std::vector<SpPiece> pieces;
+    sp_plan(streams.data(), cuts.data(), outs.data(), N, pieces);
+    auto refuse = [&](uint32_t k, int code, const char *text) {
+        outs[k].result = code; outs[k].copied_blocks = outs[k].encoded_blocks = 0; outs[k].bytes = 0;
+        snprintf(host[k].text, sizeof(host[k].text), "%s", text);
+    };
+    for (uint32_t k = 0; k < N; k++) {
+        const SpOutput &o = outs[k];
+        if (o.result == LNN_OK) continue;
+        if (o.result == LNN_INVALID_ARGUMENT && o.why) snprintf(host[k].text, sizeof(host[k].text), "SpliceStreamsDevice: %s", sp_why_text(o.why));
+        else {
+            const LINNEAmdStreamIndex *x = sx[cuts[o.cut0 + o.fail_cut].stream];
+            snprintf(host[k].text, sizeof(host[k].text), "cut %u: block %lld (byte %llu of the stream): %s", o.fail_cut, (long long)x->fail_block, (unsigned long long)x->fail_off,
+                    x->fail_code == LNN_NG ? "a block no encoder writes" : "damaged or truncated stream");
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->nspans = 0; ctx->outer_keep = 1;
+    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
+    /* 2. the fragments: decoded as windows into scratch, int32 planar, and encoded as tracks into scratch streams */
+    std::vector<uint32_t> frag;                                 /* the fragment pieces of the live outputs */
+    uint64_t runs_max = 0, live = 0;
+    for (uint32_t k = 0; k < N; k++) if (outs[k].result == LNN_OK) { live++; runs_max += outs[k].npieces; }
+    for (uint32_t i = 0; i < pieces.size(); i++) if (pieces[i].frag) frag.push_back(i);
+    if (!live) return LNN_OK;
+    const uint32_t nfrag = (uint32_t)frag.size();
+    /* scratch: per fragment C * n samples and a stream of EncodeStreamBound's bytes, 16-byte aligned; then the run table and the headers */
+    std::vector<uint64_t> o_pcm(nfrag), o_str(nfrag), room(nfrag);
+    uint64_t at = 0;
+    for (uint32_t f = 0; f < nfrag; f++) {
+        const SpPiece &p = pieces[frag[f]];
+        const SpStream &st = streams[cuts[outs[p.out].cut0 + p.cut].stream];
+        o_pcm[f] = at; at = (at + sizeof(int32_t) * (uint64_t)st.channels * (p.b - p.a) + 15u) & ~(uint64_t)15u;
+        room[f] = LINNE_HEADER_SIZE + 64u + (uint64_t)st.channels * st.block * 8u;
+        o_str[f] = at; at = (at + room[f] + 15u) & ~(uint64_t)15u;
+    }
+    const uint64_t o_runs = at; at = align_up(at + sizeof(SpRun) * (runs_max + 1u));
+    const uint64_t o_hptr = at; at = align_up(at + sizeof(uint8_t *) * live);
+    const uint64_t o_hbytes = at; at = align_up(at + 32u * live);
+    const uint64_t stage_bytes = at - o_runs;
+    SX_TRY(sp_ensure(ctx, &ctx->spl, &ctx->spl_cap, at, false));
+    SX_TRY(sp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true));
+    uint8_t *sd = (uint8_t *)ctx->spl, *hs_ = (uint8_t *)ctx->spl_stage;
+    if (nfrag) {
+        std::vector<struct LINNEAmdWindow> win(nfrag);
+        for (uint32_t f = 0; f < nfrag; f++) {
+            const SpPiece &p = pieces[frag[f]];
+            const uint32_t ci = outs[p.out].cut0 + p.cut;
+            win[f].index = sx[cuts[ci].stream]; win[f].d_stream = cut_bytes[ci]; win[f].first_sample = p.a; win[f].num_samples = p.b - p.a;
+            win[f].d_pcm = (int32_t *)(sd + o_pcm[f]); win[f].pcm_stride = p.b - p.a; win[f].result = LNN_OK;
+        }
+        int ret = LINNEAmd_DecodeWindowsDevice(ctx, win.data(), nfrag, group_frames);
+        if (ret != LNN_OK && strncmp(ctx->err, "window ", 7) != 0) return LNN_NG;         /* (a failing window's text starts with its number) */
+        for (uint32_t f = 0; f < nfrag; f++) {
+            const SpPiece &p = pieces[frag[f]];
+            if (win[f].result != LNN_OK && outs[p.out].result == LNN_OK) {
+                char text[sizeof(host[0].text)];
+                snprintf(text, sizeof(text), "cut %u, samples [%llu, %llu): DecodeWindowsDevice -> %d (a block whose Rice codes do not end where its size field says)", p.cut,
+                        (unsigned long long)p.a, (unsigned long long)p.b, win[f].result);
+                refuse(p.out, win[f].result, text);
+            }
+        }
+        std::vector<struct LINNEAmdTrack> trk;
+        std::vector<uint32_t> trk_frag;
+        for (uint32_t f = 0; f < nfrag; f++) {
+            const SpPiece &p = pieces[frag[f]];
+            if (outs[p.out].result != LNN_OK) continue;
+            struct LINNEAmdTrack t; memset(&t, 0, sizeof(t));
+            t.header = sx[cuts[outs[p.out].cut0 + p.cut].stream]->header; t.header.num_samples = (uint32_t)(p.b - p.a);
+            t.d_pcm = (const int32_t *)(sd + o_pcm[f]); t.pcm_stride = p.b - p.a; t.d_out = sd + o_str[f]; t.capacity = room[f];
+            t.parcor_state = 0.0;                               /* a fresh encoder (quirk Q2) */
+            trk.push_back(t); trk_frag.push_back(f);
+        }
+        if (!trk.empty()) {
+            ret = LINNEAmd_EncodeStreamsDevice(ctx, trk.data(), (uint32_t)trk.size(), group_frames);
+            if (ret != LNN_OK && strncmp(ctx->err, "track ", 6) != 0) return LNN_NG;      /* (a failing track's text starts with its number) */
+            for (size_t j = 0; j < trk.size(); j++) {
+                SpPiece &p = pieces[frag[trk_frag[j]]];
+                if (trk[j].result == LNN_OK) { p.bytes = trk[j].out_bytes - LINNE_HEADER_SIZE; continue; }
+                if (outs[p.out].result != LNN_OK) continue;
+                char text[sizeof(host[0].text)];
+                snprintf(text, sizeof(text), "cut %u, samples [%llu, %llu): EncodeStreamDevice refuses the edge block with %d", p.cut, (unsigned long long)p.a, (unsigned long long)p.b, trk[j].result);
+                refuse(p.out, trk[j].result, text);
+            }
+        }
+        ctx->err[0] = 0;
+    }
+    /* 3. where everything lands, which outputs fit; then one copy launch and one header launch for those */
+    sp_place(outs.data(), N, pieces.data());
+    SpRun *h_runs = (SpRun *)hs_;
+    uint8_t **h_hptr = (uint8_t **)(hs_ + (o_hptr - o_runs));
+    uint8_t *h_hbytes = hs_ + (o_hbytes - o_runs);
+    uint32_t nruns = 0, nh = 0; uint64_t nchunks = 0;
+    std::vector<uint32_t> frag_of(pieces.size(), 0u);
+    for (uint32_t f = 0; f < nfrag; f++) frag_of[frag[f]] = f;
+    for (uint32_t k = 0; k < N; k++) {
+        SpOutput &o = outs[k];
+        if (o.result == LNN_INSUFFICIENT_BUFFER) {
+            snprintf(host[k].text, sizeof(host[k].text), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)o.bytes, (unsigned long long)o.capacity);
+            o.copied_blocks = o.encoded_blocks = 0;
+        }
+        if (o.result != LNN_OK) continue;
+        struct LINNEHeader h = sx[cuts[o.cut0].stream]->header;
+        h.num_samples = (uint32_t)o.total_samples;
+        SX_TRY((int)LINNEEncoder_EncodeHeader(&h, h_hbytes + 32u * (uint64_t)nh, LINNE_HEADER_SIZE));
+        h_hptr[nh++] = splices[k].d_out;
+        for (uint32_t i = 0; i < o.npieces; i++) {
+            const SpPiece &p = pieces[o.piece0 + i];
+            if (!p.bytes) continue;
+            SpRun &r = h_runs[nruns++];
+            r.src = p.frag ? sd + o_str[frag_of[o.piece0 + i]] + LINNE_HEADER_SIZE : cut_bytes[o.cut0 + p.cut] + p.a;
+            r.dst = splices[k].d_out + p.dst; r.n = p.bytes; r.chunk0 = nchunks;
+            nchunks += sp_run_chunks((uint64_t)(uintptr_t)r.dst, r.n);
+            ctx->splice_count[4] += (int64_t)p.bytes;
+        }
+        ctx->splice_count[0]++; ctx->splice_count[1] += o.copied_blocks; ctx->splice_count[2] += o.encoded_blocks;
+    }
+    ctx->splice_count[3] = nruns;
+    if (nh) {
+        memset(&h_runs[nruns], 0, sizeof(SpRun)); h_runs[nruns].chunk0 = nchunks;
+        HIPCHK(ctx, hipMemcpyAsync(sd + o_runs, hs_, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (nruns) {
+            const uint32_t grid = nchunks < SP_MAX_GRID ? (uint32_t)nchunks : SP_MAX_GRID;
+            SX_LAUNCH(LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)(sd + o_runs), nruns, nchunks);
+        }
+        SX_LAUNCH(LINNE_AMD_SPLICE_T_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hptr), (const uint8_t *)(sd + o_hbytes), nh);
+    }
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_SpliceStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t num_splices, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    for (int i = 0; i < 6; i++) ctx->splice_count[i] = 0;
+    if (num_splices == 0) return LNN_OK;
+    if (!splices) { snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    std::vector<SpOutput> outs;
+    std::vector<SpHost> host;
+    int ret;
+    try { ret = sp_run(ctx, splices, num_splices, group_frames, outs, host); }
+    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    const bool began = ctx->outer_keep != 0;
+    ctx->outer_keep = 0; ctx->span_keep = 0;
+    if (began && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    /* the call's one wait of its own (whatever was enqueued is waited for: it reads the context's buffers) */
+    if (began) {
+        ctx->splice_count[5]++;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
+    }
+    if (ret != LNN_OK) {
+        if (!ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: failed with %d", ret);
+        for (uint32_t i = 0; i < num_splices; i++) { splices[i].result = LNN_NG; splices[i].out_bytes = 0; splices[i].copied_blocks = splices[i].encoded_blocks = 0; }
+        for (int i = 0; i < 5; i++) ctx->splice_count[i] = 0;
+        return LNN_NG;
+    }
+    int first = -1;
+    for (uint32_t i = 0; i < num_splices; i++) {
+        const SpOutput &o = outs[i];
+        splices[i].result = o.result;
+        splices[i].out_bytes = (o.result == LNN_OK || o.result == LNN_INSUFFICIENT_BUFFER) ? o.bytes : 0u;
+        splices[i].copied_blocks = o.result == LNN_OK ? o.copied_blocks : 0u;
+        splices[i].encoded_blocks = o.result == LNN_OK ? o.encoded_blocks : 0u;
+        if (o.result != LNN_OK && first < 0) first = (int)i;
+    }
+    if (first < 0) return LNN_OK;
+    snprintf(ctx->err, sizeof(ctx->err), "splice %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    return outs[first].result;
+}
+
+/* test infrastructure (like lnn_forms_query: exported, not in include/): lnn_splice.h's plan on host tables, without a GPU.
+ * streams: per stream 10 words { nb, num_samples, channels, bits, rate, block, preset, ms, fail_block (as int64), fail_code }, its
+ * tables tab[s] = { off, first, size, nsmp } (size and nsmp widened to uint64).  cuts: per cut { stream (as int64, -1: NULL), first, n }.
+ * outputs: per output { cut0, ncuts, capacity, why0 }.  frag_bytes: the size of every fragment's block, in the order the plan lists
+ * the fragments (read up to nfrag_bytes of them; a missing one counts as 0).  out_rec: per output 8 words { result, why, bytes,
+ * total samples, copied blocks, encoded blocks, piece0, npieces }; piece_rec: per piece 8 words { out, cut, frag, blocks, a, b, bytes,
+ * dst }, up to piece_cap pieces.  Returns the number of pieces. */
+extern "C" int64_t lnn_splice_plan(const uint64_t *stream_rec, const uint64_t *const *tabs, uint32_t nstreams, const uint64_t *cut_rec, uint32_t ncuts,
+        const uint64_t *out_in, uint32_t nouts, const uint64_t *frag_bytes, uint32_t nfrag_bytes, uint64_t *out_rec, uint64_t *piece_rec, uint64_t piece_cap)
+{
+    try {
+        std::vector<SpStream> streams(nstreams);
+        std::vector<std::vector<uint32_t>> narrow(2 * (size_t)nstreams);
+        for (uint32_t s = 0; s < nstreams; s++) {
+            const uint64_t *r = stream_rec + 10u * (uint64_t)s;
+            SpStream &st = streams[s];
+            st.nb = (uint32_t)r[0]; st.num_samples = r[1]; st.channels = (uint32_t)r[2]; st.bits = (uint32_t)r[3]; st.rate = (uint32_t)r[4]; st.block = (uint32_t)r[5];
+            st.preset = (uint32_t)r[6]; st.ms = (uint32_t)r[7]; st.fail_block = (int64_t)r[8]; st.fail_code = (int32_t)r[9];
+            st.off = tabs[4u * s]; st.first = tabs[4u * s + 1u];
+            for (int w = 0; w < 2; w++) { std::vector<uint32_t> &v = narrow[2u * s + w]; v.resize(st.nb); for (uint32_t i = 0; i < st.nb; i++) v[i] = (uint32_t)tabs[4u * s + 2u + w][i]; }
+            st.size = narrow[2u * s].data(); st.nsmp = narrow[2u * s + 1u].data();
+        }
+        std::vector<SpCut> cuts(ncuts);
+        for (uint32_t i = 0; i < ncuts; i++) { cuts[i].stream = (int32_t)(int64_t)cut_rec[3u * i]; cuts[i].first = cut_rec[3u * i + 1u]; cuts[i].n = cut_rec[3u * i + 2u]; }
+        std::vector<SpOutput> outs(nouts);
+        for (uint32_t k = 0; k < nouts; k++) { memset(&outs[k], 0, sizeof(SpOutput)); outs[k].cut0 = (uint32_t)out_in[4u * k]; outs[k].ncuts = (uint32_t)out_in[4u * k + 1u]; outs[k].capacity = out_in[4u * k + 2u]; outs[k].why0 = (int)out_in[4u * k + 3u]; }
+        std::vector<SpPiece> pieces;
+        sp_plan(streams.data(), cuts.data(), outs.data(), nouts, pieces);
+        uint32_t f = 0;
+        for (SpPiece &p : pieces) if (p.frag) { p.bytes = f < nfrag_bytes ? frag_bytes[f] : 0u; f++; }
+        sp_place(outs.data(), nouts, pieces.data());
+        for (uint32_t k = 0; k < nouts; k++) {
+            const SpOutput &o = outs[k]; uint64_t *r = out_rec + 8u * (uint64_t)k;
+            r[0] = (uint64_t)(int64_t)o.result; r[1] = (uint64_t)o.why; r[2] = o.bytes; r[3] = o.total_samples; r[4] = o.copied_blocks; r[5] = o.encoded_blocks; r[6] = o.piece0; r[7] = o.npieces;
+        }
+        for (size_t i = 0; i < pieces.size() && i < piece_cap; i++) {
+            const SpPiece &p = pieces[i]; uint64_t *r = piece_rec + 8u * i;
+            r[0] = p.out; r[1] = p.cut; r[2] = p.frag; r[3] = p.blocks; r[4] = p.a; r[5] = p.b; r[6] = p.bytes; r[7] = p.dst;
+        }
+        return (int64_t)pieces.size();
+    } catch (const std::bad_alloc &) { return -1; }
 }
 
 
