@@ -364,6 +364,16 @@ enum LINNEAmdSpliceTimingKind {
     LINNE_AMD_SPLICE_T_COPY = 71,           /* every run of bytes of every output (k_sp_copy) */
     LINNE_AMD_SPLICE_T_HEADER = 72          /* the outputs' stream headers (k_sb_header) */
 };
+/* repairing damaged streams (LINNEAmd_RepairStreamsDevice, a call of its own: the batch index's kinds 37-39, 41, 43 and 69 for the
+ * kernels it shares with it, 71 for its one copy launch, and one launch of each of these) */
+enum LINNEAmdRepairTimingKind {
+    LINNE_AMD_REPAIR_T_SOUND = 73,          /* which candidates are sound blocks: size bound, CRC16, structure (k_rp_sound) */
+    LINNE_AMD_REPAIR_T_COMPACT = 74,        /* the sound ones in stream order (k_rp_compact) */
+    LINNE_AMD_REPAIR_T_SUCC = 75,           /* their successors in the salvage chain (k_rp_succ) */
+    LINNE_AMD_REPAIR_T_CHAIN_LEN = 76,      /* the chains' lengths (k_rp_chain_len) */
+    LINNE_AMD_REPAIR_T_MARK = 77,           /* the cut at the header's sample count, where runs of adjacent kept blocks begin (k_rp_mark) */
+    LINNE_AMD_REPAIR_T_RUNS = 78            /* a record per run (k_rp_runs) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -648,6 +658,76 @@ struct LINNEAmdSplice {                         /* one output stream: its cuts, 
 };
 int LINNEAmd_SpliceStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t num_splices, uint32_t group_frames);
 int64_t LINNEAmd_GetLastSpliceCount(struct LINNEAmdContext *ctx, int which);
+
+/* ---- repairing damaged resident streams: sound blocks kept byte for byte, lost stretches replaced by SILENT blocks ----
+ * The index and every call on it stop at the first damaged block (LINNEAmd_DecodeStreamDevice: "damage before [the range] does"
+ * matter), as the reference's decoder does.  LINNEAmd_RepairStreamsDevice turns num_streams damaged streams into valid .lnn streams:
+ * the index finds no failing block in an output, LINNEAmd_DecodeWindowsDevice and LINNEAmd_SpliceStreamsDevice take it, the reference
+ * decodes it.  It rests on what the splice call rests on: a block brings everything its decoding needs, so a stream that keeps
+ * untouched blocks and holds blocks of fewer than S samples between them is a valid stream.
+ * Per stream (N: the header's sample count, S its block size, C its channels):
+ *   1. Header.  Read as LINNEAmd_StreamIndexCreate reads it; a header error is that stream's result, with the index's code, nothing
+ *      is written and out_bytes is 0.  A damaged header is out of scope.
+ *   2. Sound block.  A candidate is a position p >= 30 that passes the checks lnn's block parser makes before the CRC with
+ *      left = stream_bytes - p: FF FF, size + 6 <= left, size >= 5.  It is sound when size + 6 <= B, its CRC16 matches, and it passes
+ *      the parser's checks behind the CRC with the room replaced by S: type 0 .. 2, 1 <= samples <= S, a RAW block at 8, 16 or 24
+ *      bits, a RAW or SILENT payload exactly as long as the size field says.
+ *      B bounds the bytes the reference's encoder can write for one block of the stream's shape:
+ *          B = 11 + ceil(C * (2 * (bits + 5) + 7 * L + 32 * P + 15 + 36 * S) / 8)
+ *      with L the layers and P the coefficients per channel of the header's preset (DESIGN.md derives it).  It keeps the CRC work
+ *      linear in the stream: a false candidate carries a random size field.  A true block larger than B -- none the reference's
+ *      encoder or this library's writes -- is treated as damage.
+ *   3. The salvage chain.  Its first block is the lowest sound candidate; the block behind a block at p with size field z is the
+ *      lowest sound candidate at byte >= p + z + 6.  The chain stops before the block with which the kept samples would exceed N (as
+ *      the decoder's loop stops at N); what lies behind is dropped and is no gap.  On an undamaged stream this is the index's chain.
+ *   4. Gaps.  A gap lies before the first kept block when that is not at byte 30, between two kept blocks that are not adjacent, and
+ *      behind the last kept block when the kept samples are fewer than N and bytes lie behind it or there is no other gap (alone, this
+ *      trailing gap may hold 0 bytes: a stream cut at a block boundary; where a gap lies before a last block that ends the stream, that
+ *      gap stands for the missing samples; a stream without a sound block is one trailing gap from byte 30 on).  M = N - kept samples are lost in all.  One
+ *      gap gets all of M and exact = 1.  Several gaps: gap i of b_i source bytes gets floor(M * b_i / sum b), the last gap the
+ *      remainder (with sum b == 0, everything), and exact = 0: the kept runs between the gaps are then placed by estimate, not by
+ *      proof.  A gap given 0 samples gets no fill: junk bytes between sound blocks are dropped.  No gap: exact = 1.
+ *   5. Fill.  A gap of g samples becomes ceil(g / min(S, 65535)) SILENT blocks of 11 bytes (size field 5), every one full but the
+ *      last.
+ *   6. Output.  The source's 30 header bytes, then kept runs and fills in order.  It holds out_bytes bytes; when capacity is smaller
+ *      (or the output longer than 2^32 - 1 bytes) the result is LINNE_APIRESULT_INSUFFICIENT_BUFFER, out_bytes the size needed, no
+ *      byte is written and the other out fields are 0.  Damage is no failure: a stream with gaps returns OK and the out fields say
+ *      what happened; a stream without a sound block returns OK with kept_blocks = 0.
+ *   7. An undamaged stream whose blocks reach N gives bytes [0, end of the last block a whole decode walks) of the input,
+ *      num_gaps = 0, exact = 1.
+ * Two limits.  A CRC-valid block whose Rice codes do not end where the block does is kept as it is: the output then fails where the
+ * input did.  A false candidate inside a LOST stretch passes CRC16 with chance 2^-16 and is then kept as a block (inside a sound
+ * block it is skipped: the chain continues behind that block's end).
+ * A NULL d_stream or d_out is that stream's INVALID_ARGUMENT.  d_out may lie at any alignment; the outputs must not overlap each
+ * other or any source.  Streams of different shapes may be mixed; streams may lie at any alignment and be adjacent views of one
+ * buffer: every read of stream i is a byte load inside [0, stream_bytes[i]), no byte outside [0, out_bytes) of an output is written.
+ * A failing stream does not disturb the others.  The call returns LINNE_APIRESULT_OK when every stream is OK, otherwise the result of
+ * the lowest-numbered failing stream; GetLastError then reads "repair <i>: " and that stream's text.  A HIP error or running out of
+ * memory fails the whole call: LINNE_APIRESULT_NG, in every `result` too.  num_streams == 0 is OK; a NULL ctx, or NULL streams with
+ * num_streams > 0, INVALID_ARGUMENT.
+ * Cost: kernel launches, copies, host synchronisations (five once the scratch has grown) and device allocations do not depend on
+ * the number of streams or gaps; only the pointer-doubling depth K does on the streams (the batch index's K: K - 1 launches of kind
+ * 41).  One copy launch (kind 71) places every run and fill of every output, after one upload of the fill bytes and the run table.
+ * Scratch is kept by the context and grown as the batch index grows it: about 120 + 4 K bytes per candidate.  Enqueued on the
+ * context's stream and synchronous.
+ * LINNEAmd_GetLastRepairGaps: the gaps of stream i of the context's last repair call (none for a failing stream), valid until its
+ * next one.  LINNEAmd_GetLastRepairCount: of the last such call, which = 0 the outputs written, 1 their kept blocks, 2 their fill
+ * blocks, 3 their gaps, 4 the copy runs, 5 its host synchronisations, 6 its kernel launches; -1 for a NULL ctx or any other `which`. */
+struct LINNEAmdGap {
+    uint64_t first_sample, num_samples;         /* in the output's timeline */
+    uint64_t src_offset, src_bytes;             /* the bytes of the source it stands for */
+    uint32_t fill_blocks, reserved;             /* the SILENT blocks written for it */
+};
+struct LINNEAmdRepair {
+    const uint8_t *d_stream; uint64_t stream_bytes;     /* the damaged stream's device bytes, any alignment */
+    uint8_t *d_out; uint64_t capacity;
+    uint64_t out_bytes, lost_samples;           /* out */
+    uint32_t kept_blocks, fill_blocks, num_gaps, exact;     /* out */
+    int32_t result;                             /* out: this stream's LINNEApiResult */
+};
+int LINNEAmd_RepairStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdRepair *streams, uint32_t num_streams);
+int LINNEAmd_GetLastRepairGaps(struct LINNEAmdContext *ctx, uint32_t stream, const struct LINNEAmdGap **gaps, uint32_t *num_gaps);
+int64_t LINNEAmd_GetLastRepairCount(struct LINNEAmdContext *ctx, int which);
 
 #ifdef __cplusplus
 }

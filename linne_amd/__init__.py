@@ -54,6 +54,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_EncodeStreamDeviceLayout", "LINNEAmd_EncodeStreamsDeviceLayout", "LINNEAmd_DecodeWindowsDeviceLayout",
     "LINNEAmd_StreamIndexesCreate", "LINNEAmd_GetLastIndexBatchCount", "LINNEAmd_StreamIndexBlocks", "LINNEAmd_StreamIndexFailure",
     "LINNEAmd_SpliceStreamsDevice", "LINNEAmd_GetLastSpliceCount",
+    "LINNEAmd_RepairStreamsDevice", "LINNEAmd_GetLastRepairGaps", "LINNEAmd_GetLastRepairCount",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -91,6 +92,19 @@ class Splice(C.Structure):
     """struct LINNEAmdSplice (include/linne_amd.h)"""
     _fields_ = [("cuts", C.POINTER(Cut)), ("num_cuts", C.c_uint32), ("d_out", C.c_void_p), ("capacity", C.c_uint64), ("out_bytes", C.c_uint64),
                 ("copied_blocks", C.c_uint32), ("encoded_blocks", C.c_uint32), ("result", C.c_int32)]
+
+
+class Gap(C.Structure):
+    """struct LINNEAmdGap (include/linne_amd.h)"""
+    _fields_ = [("first_sample", C.c_uint64), ("num_samples", C.c_uint64), ("src_offset", C.c_uint64), ("src_bytes", C.c_uint64),
+                ("fill_blocks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Repair(C.Structure):
+    """struct LINNEAmdRepair (include/linne_amd.h)"""
+    _fields_ = [("d_stream", C.c_void_p), ("stream_bytes", C.c_uint64), ("d_out", C.c_void_p), ("capacity", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("lost_samples", C.c_uint64), ("kept_blocks", C.c_uint32), ("fill_blocks", C.c_uint32), ("num_gaps", C.c_uint32), ("exact", C.c_uint32),
+                ("result", C.c_int32)]
 
 
 class PcmLayout(C.Structure):
@@ -178,6 +192,10 @@ def _load():
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
+    L.LINNEAmd_RepairStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Repair), C.c_uint32]
+    L.LINNEAmd_GetLastRepairGaps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(Gap)), C.POINTER(C.c_uint32)]
+    L.LINNEAmd_GetLastRepairCount.restype = C.c_int64
+    L.LINNEAmd_GetLastRepairCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_GetLastStreamBatchCount.restype = C.c_int64
     L.LINNEAmd_GetLastStreamBatchCount.argtypes = [C.c_void_p, C.c_int]
     L.LINNEAmd_MultiCreate.restype = C.c_void_p
@@ -781,6 +799,69 @@ class Context:
         """the last splice_streams call (its second one, where outputs were spliced again): 0 the outputs written, 1 their copied
         blocks, 2 their re-encoded blocks, 3 the copy runs, 4 the bytes they moved, 5 the host synchronisations of the call's own steps"""
         return int(lib.LINNEAmd_GetLastSpliceCount(self.h, int(which)))
+
+    def repair_streams(self, streams, return_codes=False):
+        """damaged resident .lnn streams turned into valid ones in one call: sound blocks kept byte for byte, lost stretches replaced
+        by SILENT blocks (include/linne_amd.h LINNEAmd_RepairStreamsDevice).  streams: a sequence of 1-D uint8 CUDA tensors, bytes
+        or numpy arrays -> a list of (stream, report): stream a 1-D uint8 CUDA view of one allocation at a 4-byte-aligned offset
+        (None for a stream that failed), report a dict of out_bytes, result, kept_blocks, fill_blocks, num_gaps, lost_samples, exact
+        and gaps (a list of dicts: first_sample, num_samples, src_offset, src_bytes, fill_blocks).  Every stream gets the room of its
+        own bytes plus the fill blocks of a wholly lost stream; one that still does not fit is repaired once more at its exact size.
+        Raises LinneAmdError with .code = the call's result and .codes = the per-stream LINNEApiResults when a stream fails; with
+        return_codes -> (list, codes), and only a failure of the whole call raises"""
+        import torch
+        dev = f"cuda:{self.device}"
+        T = len(streams)
+        keep = [self._stream_bytes(s) for s in streams]
+        whole = [k for k in range(T) if keep[k].numel() >= 30]              # the headers' sample counts and block sizes: one copy
+        heads = torch.stack([keep[k][:30] for k in whole]).cpu().numpy() if whole else np.zeros((0, 30), np.uint8)
+        rooms = [t.numel() + 22 for t in keep]
+        for row, k in zip(heads, whole):
+            n, s = int.from_bytes(bytes(row[14:18]), "big"), int.from_bytes(bytes(row[24:28]), "big")
+            rooms[k] = keep[k].numel() + 11 * (n // max(min(s, 65535), 1) + 2)
+        out = [(None, None)] * T
+        codes = [0] * T
+
+        def run(which, sizes):
+            offs, at = [], 0
+            for n in sizes:
+                offs.append(at)
+                at += (n + 3) & ~3
+            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
+            sub = (Repair * max(len(which), 1))()
+            for j, k in enumerate(which):
+                sub[j].d_stream, sub[j].stream_bytes = keep[k].data_ptr(), keep[k].numel()
+                sub[j].d_out, sub[j].capacity = flat.data_ptr() + offs[j], sizes[j]
+            self._fence()
+            ret = lib.LINNEAmd_RepairStreamsDevice(self.h, sub, len(which))
+            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
+            if ret != 0 and not msg.startswith("repair "):              # (a failing stream's text starts with its number)
+                raise LinneAmdError(f"RepairStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
+            for j, k in enumerate(which):
+                r = sub[j]
+                codes[k] = int(r.result)
+                report = {f: int(getattr(r, f)) for f in ("out_bytes", "result", "kept_blocks", "fill_blocks", "num_gaps", "lost_samples", "exact")}
+                gaps, n = C.POINTER(Gap)(), C.c_uint32(0)
+                self._check(lib.LINNEAmd_GetLastRepairGaps(self.h, j, C.byref(gaps), C.byref(n)), "GetLastRepairGaps")
+                report["gaps"] = [{f: int(getattr(gaps[i], f)) for f in ("first_sample", "num_samples", "src_offset", "src_bytes", "fill_blocks")} for i in range(n.value)]
+                out[k] = (flat[offs[j]:offs[j] + report["out_bytes"]] if codes[k] == 0 else None, report)
+            return ret, msg
+
+        ret, msg = run(list(range(T)), rooms)
+        again = [k for k in range(T) if codes[k] == 3 and out[k][1]["out_bytes"] > rooms[k]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
+        if again:
+            run(again, [out[k][1]["out_bytes"] for k in again])
+            bad = [k for k in range(T) if codes[k] != 0]
+            ret = codes[bad[0]] if bad else 0
+            msg = f"repair {bad[0]} failed" if bad else ""
+        if ret != 0 and not return_codes:
+            raise LinneAmdError(f"RepairStreamsDevice -> {ret}: {msg}", ret, codes)
+        return (out, codes) if return_codes else out
+
+    def last_repair_count(self, which):
+        """the last repair_streams call (its second one, where streams were repaired again): 0 the outputs written, 1 their kept
+        blocks, 2 their fill blocks, 3 their gaps, 4 the copy runs, 5 its host synchronisations, 6 its kernel launches"""
+        return int(lib.LINNEAmd_GetLastRepairCount(self.h, int(which)))
 
     def encode_frames_host(self, shape, pcm, num_samples=None):
         """numpy int32 [F][C][S] -> numpy (residual, params, stats)"""

@@ -52,10 +52,13 @@
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_k_splice.h"               /* (brings lnn_splice.h: the host's plan of a splice call) */
+#include "lnn_repair.h"                 /* the host's plan of a repair call */
+#include "lnn_k_repair.h"
 /* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
 /* the two timing kinds linne_amd.h numbers by their place behind kind 68 */
 static_assert(LINNE_AMD_T_IB_HEADERS == 69 && LINNE_AMD_T_IB_BEHIND == 70, "the index batch's timing kinds are 69 and 70");
 static_assert(LINNE_AMD_SPLICE_T_COPY == 71 && LINNE_AMD_SPLICE_T_HEADER == 72, "the splice call's timing kinds are 71 and 72");
+static_assert(LINNE_AMD_REPAIR_T_SOUND == 73 && LINNE_AMD_REPAIR_T_RUNS == 78, "the repair call's timing kinds are 73 to 78");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -120,6 +123,8 @@ struct LINNEAmdContext {
     void *spl_stage; uint64_t spl_stage_cap;    /* pinned: the run table and the headers on the host, uploaded in one copy */
     int64_t splice_count[6];            /* the last SpliceStreamsDevice call: outputs written, copied blocks, re-encoded blocks, copy runs, bytes copied, its own host synchronisations */
     int outer_keep;                     /* DecodeWindowsDevice / EncodeStreamsDevice inside SpliceStreamsDevice: keep the call's spans and start event */
+    int64_t repair_count[7];            /* the last RepairStreamsDevice call: outputs written, kept blocks, fill blocks, gaps, copy runs, host synchronisations, kernel launches */
+    struct LINNEAmdGap *rp_gaps; uint64_t *rp_gap0; uint32_t rp_streams;     /* its gaps, stream i's are [rp_gap0[i], rp_gap0[i + 1]) (LINNEAmd_GetLastRepairGaps; host memory) */
     LnnKnobs knob;                      /* every form-selecting knob (lnn_forms.h): some read when the context is created, the others at the top of each call */
 };
 
@@ -266,6 +271,7 @@ extern "C" void LINNEAmd_ContextDestroy(struct LINNEAmdContext *ctx)
     for (int i = 0; i < 2 * ctx->span_cap; i++) hipEventDestroy(ctx->span_ev[i]);
     free(ctx->span_ev); free(ctx->span_kind);
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
+    free(ctx->rp_gaps); free(ctx->rp_gap0);
     free(ctx);
 }
 
@@ -3391,6 +3397,311 @@ extern "C" int64_t lnn_splice_plan(const uint64_t *stream_rec, const uint64_t *c
             r[0] = p.out; r[1] = p.cut; r[2] = p.frag; r[3] = p.blocks; r[4] = p.a; r[5] = p.b; r[6] = p.bytes; r[7] = p.dst;
         }
         return (int64_t)pieces.size();
+    } catch (const std::bad_alloc &) { return -1; }
+}
+
+
+/* ================================================================================================
+ * repairing damaged resident streams (lnn_repair.h, lnn_k_repair.h)
+ * ============================================================================================== */
+extern "C" int64_t LINNEAmd_GetLastRepairCount(struct LINNEAmdContext *ctx, int which)
+{
+    if (!ctx || which < 0 || which > 6) return -1;
+    return ctx->repair_count[which];
+}
+
+extern "C" int LINNEAmd_GetLastRepairGaps(struct LINNEAmdContext *ctx, uint32_t stream, const struct LINNEAmdGap **gaps, uint32_t *num_gaps)
+{
+    if (!ctx || !gaps || !num_gaps || stream >= ctx->rp_streams || !ctx->rp_gap0) return LNN_INVALID_ARGUMENT;
+    *gaps = ctx->rp_gaps + ctx->rp_gap0[stream];
+    *num_gaps = (uint32_t)(ctx->rp_gap0[stream + 1u] - ctx->rp_gap0[stream]);
+    return LNN_OK;
+}
+
+/* the call's waits and launches are counted (LINNEAmd_GetLastRepairCount 5 and 6) */
+static int rp_sync(LINNEAmdContext *ctx)
+{
+    ctx->repair_count[5]++;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LNN_OK;
+}
+static int rp_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need, bool pinned)
+{
+    if (*cap >= need) return LNN_OK;
+    SX_TRY(rp_sync(ctx));                                           /* (a buffer that grows waits for the stream first) */
+    if (*ptr) HIPCHK(ctx, pinned ? hipHostFree(*ptr) : hipFree(*ptr));
+    *ptr = NULL; *cap = 0;
+    if (pinned) HIPCHK(ctx, hipHostMalloc(ptr, need, hipHostMallocDefault)); else HIPCHK(ctx, hipMalloc(ptr, need));
+    *cap = need;
+    return LNN_OK;
+}
+#define RP_LAUNCH(kind, ...) do { ctx->repair_count[6]++; SX_LAUNCH(kind, __VA_ARGS__); } while (0)
+
+struct RpHost { int32_t result; char text[200]; };
+
+/* LNN_OK: every stream has its result in host[] and, where that is OK or INSUFFICIENT_BUFFER, its plan; anything else fails the
+ * whole call */
+static int rp_run(LINNEAmdContext *ctx, struct LINNEAmdRepair *rep, uint32_t T, std::vector<RpHost> &host, std::vector<RpPlan> &plans)
+{
+    char text[sizeof(ctx->err)];
+    host.resize(T); plans.resize(T);
+    for (uint32_t i = 0; i < T; i++) { host[i].result = LNN_OK; host[i].text[0] = 0; plans[i].result = RP_OK; plans[i].bytes = 0; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    /* the lists of the call, pinned on the host and at the same offsets on the device (the batch index's, and its buffers) */
+    const uint64_t o_st = 0, o_row0 = align_up(o_st + sizeof(IbStream) * (uint64_t)T), o_bound = align_up(o_row0 + sizeof(uint64_t) * (T + 1ull)),
+            o_tab = align_up(o_bound + sizeof(uint64_t) * (uint64_t)T), o_crow = align_up(o_tab + sizeof(SxTables)), o_hdr = align_up(o_crow + sizeof(uint64_t) * (T + 1ull)),
+            o_seg = align_up(o_hdr + (uint64_t)IB_HDR_SLOT * T), o_sseg = align_up(o_seg + sizeof(uint64_t) * (T + 1ull)), o_len = align_up(o_sseg + sizeof(uint64_t) * (T + 1ull)),
+            o_rseg = align_up(o_len + sizeof(uint64_t) * (uint64_t)T), list_bytes = align_up(o_rseg + sizeof(uint64_t) * (T + 1ull));
+    SX_TRY(rp_ensure(ctx, &ctx->wstage, &ctx->wstage_cap, list_bytes, true));
+    SX_TRY(rp_ensure(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes, false));
+    uint8_t *hl = (uint8_t *)ctx->wstage, *dl = (uint8_t *)ctx->wdec;
+    IbStream *h_st = (IbStream *)(hl + o_st);
+    uint64_t *h_row0 = (uint64_t *)(hl + o_row0), *h_bound = (uint64_t *)(hl + o_bound), *h_crow = (uint64_t *)(hl + o_crow), *h_seg = (uint64_t *)(hl + o_seg),
+            *h_len = (uint64_t *)(hl + o_len), *h_rseg = (uint64_t *)(hl + o_rseg);
+    const uint8_t *h_hdr = hl + o_hdr;
+    const IbStream *d_st = (const IbStream *)(dl + o_st);
+    const uint64_t *d_row0 = (const uint64_t *)(dl + o_row0), *d_bound = (const uint64_t *)(dl + o_bound), *d_crow = (const uint64_t *)(dl + o_crow);
+    uint64_t *d_seg = (uint64_t *)(dl + o_seg), *d_sseg = (uint64_t *)(dl + o_sseg), *d_len = (uint64_t *)(dl + o_len), *d_rseg = (uint64_t *)(dl + o_rseg);
+    const uint32_t gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
+    ctx->nspans = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    /* 1. the headers: one gather, one fetch; the host reads them as the index does */
+    memset(h_st, 0, sizeof(IbStream) * (uint64_t)T);
+    for (uint32_t i = 0; i < T; i++) {
+        if (!rep[i].d_stream || !rep[i].d_out) { host[i].result = LNN_INVALID_ARGUMENT; snprintf(host[i].text, sizeof(host[i].text), "RepairStreamsDevice: null argument"); continue; }
+        h_st[i].b = rep[i].d_stream; h_st[i].N = rep[i].stream_bytes;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
+    RP_LAUNCH(LINNE_AMD_T_IB_HEADERS, k_ib_headers, dim3((uint32_t)(((uint64_t)T * IB_HDR_SLOT + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, T, dl + o_hdr);
+    HIPCHK(ctx, hipMemcpyAsync(hl + o_hdr, dl + o_hdr, (uint64_t)IB_HDR_SLOT * T, hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(rp_sync(ctx));
+    uint64_t nrows = 0;
+    for (uint32_t i = 0; i < T; i++) {
+        h_row0[i] = nrows; h_bound[i] = 0;
+        if (host[i].result != LNN_OK) continue;
+        LINNEAmdStreamIndex *x = NULL;
+        bool whole_call;
+        const int r = ib_open(ctx->device, h_hdr + (uint64_t)IB_HDR_SLOT * i, rep[i].stream_bytes, &x, text, sizeof(text), &whole_call);
+        if (whole_call) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: %.*s", (int)sizeof(ctx->err) - 32, text); return LNN_NG; }
+        if (r != LNN_OK) { host[i].result = r; snprintf(host[i].text, sizeof(host[i].text), "%.*s", (int)sizeof(host[i].text) - 1, text); h_st[i].b = NULL; h_st[i].N = 0; continue; }
+        h_st[i].num_samples = x->header.num_samples; h_st[i].C = x->shape.num_channels; h_st[i].S = x->shape.num_samples_per_block; h_st[i].bits = x->shape.bits_per_sample;
+        uint32_t L = 0, P[LINNE_AMD_MAX_LAYERS] = { 0, 0, 0 }, sum = 0;
+        (void)lnn_preset_info(x->shape.preset, &L, P, NULL, NULL);
+        for (uint32_t l = 0; l < L; l++) sum += P[l];
+        h_bound[i] = rp_block_bound(h_st[i].C, h_st[i].S, h_st[i].bits, L, sum);
+        free(x);
+        if (rep[i].stream_bytes > SX_FIRST_BLOCK) nrows += (rep[i].stream_bytes - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
+    }
+    h_row0[T] = nrows;
+    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: %llu stream bytes in one call: too many", (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
+    sx_tables((SxTables *)(hl + o_tab));
+    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, o_crow - o_st, hipMemcpyHostToDevice, ctx->stream));      /* the streams, row0, the bounds, the tables */
+    /* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back */
+    const uint64_t o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
+    SX_TRY(rp_ensure(ctx, &ctx->sdec, &ctx->sdec_cap, align_up(o_cofs + sizeof(uint64_t) * (nrows + 1u)), false));
+    uint32_t *counts = (uint32_t *)((uint8_t *)ctx->sdec + o_counts);
+    uint64_t *cofs = (uint64_t *)((uint8_t *)ctx->sdec + o_cofs);
+    const uint32_t grow = (uint32_t)((nrows + 3u) / 4u);
+    if (nrows) RP_LAUNCH(LINNE_AMD_T_SX_COUNT, k_ib_count, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, counts);
+    RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nrows, cofs);
+    RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)cofs, d_row0, T, d_seg);
+    HIPCHK(ctx, hipMemcpyAsync(h_seg, d_seg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(rp_sync(ctx));
+    const uint64_t M = h_seg[T];
+    if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
+    uint64_t Mmax = 0;
+    for (uint32_t i = 0; i < T; i++) if (h_seg[i + 1] - h_seg[i] > Mmax) Mmax = h_seg[i + 1] - h_seg[i];
+    uint32_t K = 1;
+    while ((1ull << K) <= Mmax) K++;                              /* 2^K > the longest segment: K levels cover any chain */
+    /* 3. the sound candidates, their successors, pointer doubling, the chains' lengths.  No more sound candidates than candidates
+     * and no more chain blocks than sound candidates: every table below has room for M of them, so nothing waits for a count */
+    uint64_t at = 0;
+    auto part = [&](uint64_t bytes) { const uint64_t o = at; at = align_up(at + bytes); return o; };
+    const uint64_t o_cand = part(sizeof(uint64_t) * (M + 1u)), o_flag = part(sizeof(uint32_t) * (M + 1u)), o_sofs = part(sizeof(uint64_t) * (M + 2u)),
+            o_spos = part(sizeof(uint64_t) * (M + 1u)), o_jump = part(sizeof(uint32_t) * (uint64_t)K * (M + 1u)), o_off = part(sizeof(uint64_t) * (M + 1u)),
+            o_size = part(sizeof(uint32_t) * (M + 1u)), o_type = part(sizeof(uint32_t) * (M + 1u)), o_nsmp = part(sizeof(uint32_t) * (M + 1u)),
+            o_scan = part(sizeof(uint64_t) * (M + 2u)), o_mark = part(sizeof(uint32_t) * (M + 1u)), o_rofs = part(sizeof(uint64_t) * (M + 2u)),
+            o_rec = part(sizeof(RpRunRec) * (M + 1u));
+    SX_TRY(rp_ensure(ctx, &ctx->xcand, &ctx->xcand_cap, at, false));
+    uint8_t *xc = (uint8_t *)ctx->xcand;
+    uint64_t *cand = (uint64_t *)(xc + o_cand), *sofs = (uint64_t *)(xc + o_sofs), *spos = (uint64_t *)(xc + o_spos), *c_off = (uint64_t *)(xc + o_off),
+            *scan = (uint64_t *)(xc + o_scan), *rofs = (uint64_t *)(xc + o_rofs);
+    uint32_t *flag = (uint32_t *)(xc + o_flag), *jump = (uint32_t *)(xc + o_jump), *c_size = (uint32_t *)(xc + o_size), *c_type = (uint32_t *)(xc + o_type),
+            *c_nsmp = (uint32_t *)(xc + o_nsmp), *mark = (uint32_t *)(xc + o_mark);
+    RpRunRec *rec = (RpRunRec *)(xc + o_rec);
+    const uint32_t M32 = (uint32_t)M, gM = (uint32_t)((M + 1u + 255u) / 256u);
+    uint64_t nchain = 0;
+    for (uint32_t i = 0; i <= T; i++) h_crow[i] = 0;
+    if (M) {
+        RP_LAUNCH(LINNE_AMD_T_SX_WRITE, k_ib_write, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, (const uint64_t *)cofs, cand);
+        RpSoundArgs sa;
+        sa.st = d_st; sa.bound = d_bound; sa.seg = d_seg; sa.T = T; sa.M = M32; sa.cand = cand; sa.tab = (const SxTables *)(dl + o_tab); sa.flag = flag;
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_SOUND, k_rp_sound, dim3((uint32_t)((M + 3u) / 4u)), dim3(256), 0, ctx->stream, sa);
+        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)flag, M, sofs);
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_COMPACT, k_rp_compact, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)flag, (const uint64_t *)sofs, (const uint64_t *)cand, M32, spos);
+        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)sofs, (const uint64_t *)d_seg, T, d_sseg);
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_SUCC, k_rp_succ, dim3(gM), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, T, (const uint64_t *)spos, M32, jump);
+        for (uint32_t k = 1; k < K; k++)
+            RP_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_CHAIN_LEN, k_rp_chain_len, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)d_sseg, T, (const uint32_t *)jump, K, M32, d_len);
+        HIPCHK(ctx, hipMemcpyAsync(h_len, d_len, sizeof(uint64_t) * (uint64_t)T, hipMemcpyDeviceToHost, ctx->stream));
+        SX_TRY(rp_sync(ctx));
+        for (uint32_t i = 0; i < T; i++) { h_crow[i] = nchain; nchain += h_len[i]; }
+        h_crow[T] = nchain;
+        if (nchain > M) { snprintf(ctx->err, sizeof(ctx->err), "internal: %llu chain blocks of %llu candidates", (unsigned long long)nchain, (unsigned long long)M); return LNN_NG; }
+    }
+    /* 4. the chains' blocks, the cut at the headers' sample counts, a record per run of adjacent kept blocks: one fetch */
+    std::vector<std::vector<RpPiece>> pieces(T);
+    if (nchain) {
+        SX_TRY(rp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, sizeof(RpRunRec) * nchain, true));
+        HIPCHK(ctx, hipMemcpyAsync(dl + o_crow, hl + o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
+        RP_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, d_crow, T, (const uint64_t *)spos,
+                (const uint32_t *)jump, K, M32, nchain, c_off, c_size, c_type, c_nsmp);
+        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)c_nsmp, nchain, scan);
+        RpRunArgs ra;
+        ra.st = d_st; ra.crow = d_crow; ra.T = T; ra.nchain = nchain; ra.off = c_off; ra.size = c_size; ra.scan = scan; ra.mark = mark; ra.rofs = rofs; ra.rec = rec;
+        const uint32_t gc = (uint32_t)((nchain + 255u) / 256u);
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_MARK, k_rp_mark, dim3(gc), dim3(256), 0, ctx->stream, ra);
+        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)mark, nchain, rofs);
+        RP_LAUNCH(LINNE_AMD_REPAIR_T_RUNS, k_rp_runs, dim3(gc), dim3(256), 0, ctx->stream, ra);
+        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)rofs, d_crow, T, d_rseg);
+        HIPCHK(ctx, hipMemcpyAsync(h_rseg, d_rseg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
+        /* (no more runs than chain blocks: the records of all of them come back without waiting for their count) */
+        HIPCHK(ctx, hipMemcpyAsync(ctx->spl_stage, rec, sizeof(RpRunRec) * nchain, hipMemcpyDeviceToHost, ctx->stream));
+        SX_TRY(rp_sync(ctx));
+        const RpRunRec *h_rec = (const RpRunRec *)ctx->spl_stage;
+        if (h_rseg[T] > nchain) { snprintf(ctx->err, sizeof(ctx->err), "internal: %llu runs of %llu chain blocks", (unsigned long long)h_rseg[T], (unsigned long long)nchain); return LNN_NG; }
+        for (uint32_t i = 0; i < T; i++)
+            for (uint64_t j = h_rseg[i]; j < h_rseg[i + 1]; j++) {
+                const RpRunRec &r = h_rec[j];
+                const RpPiece q = { r.off0, r.off1 - r.off0, r.smp1 - r.smp0, (uint64_t)(r.rank1 - r.rank0) };
+                pieces[i].push_back(q);
+            }
+    }
+    /* 5. the host's plan; one upload of the run table and the fill bytes; one copy launch */
+    lnn_tables_init();                                              /* (lnn_crc16's table) */
+    uint64_t nruns = 0, fill_bytes = 0;
+    for (uint32_t i = 0; i < T; i++) {
+        if (host[i].result != LNN_OK) continue;
+        RpPlan &p = plans[i];
+        rp_plan(pieces[i].data(), pieces[i].size(), h_st[i].num_samples, h_st[i].S, rep[i].stream_bytes, rep[i].capacity, lnn_crc16, p);
+        host[i].result = p.result;
+        if (p.result != RP_OK) { snprintf(host[i].text, sizeof(host[i].text), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)p.bytes, (unsigned long long)rep[i].capacity); continue; }
+        nruns += p.runs.size(); fill_bytes += p.fill.size();
+    }
+    if (nruns >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: too many runs in one call"); return LNN_NG; }
+    if (nruns) {
+        const uint64_t o_fill = align_up(sizeof(SpRun) * (nruns + 1u)), stage_bytes = align_up(o_fill + fill_bytes);
+        SX_TRY(rp_ensure(ctx, &ctx->spl, &ctx->spl_cap, stage_bytes, false));
+        SX_TRY(rp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true));
+        uint8_t *sd = (uint8_t *)ctx->spl, *hs_ = (uint8_t *)ctx->spl_stage;
+        SpRun *h_runs = (SpRun *)hs_;
+        uint64_t r = 0, f = o_fill, nchunks = 0;
+        for (uint32_t i = 0; i < T; i++) {
+            if (host[i].result != LNN_OK) continue;
+            const RpPlan &p = plans[i];
+            if (!p.fill.empty()) memcpy(hs_ + f, p.fill.data(), p.fill.size());
+            for (const RpRun &q : p.runs) {
+                SpRun &o = h_runs[r++];
+                o.src = q.fill ? sd + f + q.src : rep[i].d_stream + q.src; o.dst = rep[i].d_out + q.dst; o.n = q.bytes; o.chunk0 = nchunks;
+                nchunks += sp_run_chunks((uint64_t)(uintptr_t)o.dst, o.n);
+            }
+            f += p.fill.size();
+        }
+        memset(&h_runs[nruns], 0, sizeof(SpRun)); h_runs[nruns].chunk0 = nchunks;
+        HIPCHK(ctx, hipMemcpyAsync(sd, hs_, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
+        const uint32_t grid = nchunks < SP_MAX_GRID ? (uint32_t)nchunks : SP_MAX_GRID;
+        RP_LAUNCH(LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)sd, (uint32_t)nruns, nchunks);
+    }
+    ctx->repair_count[4] = (int64_t)nruns;
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_RepairStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdRepair *streams, uint32_t num_streams)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    for (int i = 0; i < 7; i++) ctx->repair_count[i] = 0;
+    free(ctx->rp_gaps); free(ctx->rp_gap0); ctx->rp_gaps = NULL; ctx->rp_gap0 = NULL; ctx->rp_streams = 0;
+    if (num_streams == 0) return LNN_OK;
+    if (!streams) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    std::vector<RpHost> host;
+    std::vector<RpPlan> plans;
+    int ret;
+    try { ret = rp_run(ctx, streams, num_streams, host, plans); }
+    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    if (ret == LNN_OK && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    /* the call's last wait (whatever was enqueued is waited for: it reads the context's buffers) */
+    ctx->repair_count[5]++;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
+    uint64_t ngaps = 0;
+    if (ret == LNN_OK) {
+        for (uint32_t i = 0; i < num_streams; i++) if (host[i].result == LNN_OK) ngaps += plans[i].gaps.size();
+        ctx->rp_gaps = (struct LINNEAmdGap *)malloc(sizeof(struct LINNEAmdGap) * (ngaps + 1u));
+        ctx->rp_gap0 = (uint64_t *)malloc(sizeof(uint64_t) * ((uint64_t)num_streams + 1u));
+        if (!ctx->rp_gaps || !ctx->rp_gap0) { free(ctx->rp_gaps); free(ctx->rp_gap0); ctx->rp_gaps = NULL; ctx->rp_gap0 = NULL; snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    }
+    if (ret != LNN_OK) {
+        if (!ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: failed with %d", ret);
+        for (uint32_t i = 0; i < num_streams; i++) {
+            streams[i].result = LNN_NG; streams[i].out_bytes = streams[i].lost_samples = 0;
+            streams[i].kept_blocks = streams[i].fill_blocks = streams[i].num_gaps = streams[i].exact = 0;
+        }
+        for (int i = 0; i < 5; i++) ctx->repair_count[i] = 0;
+        return LNN_NG;
+    }
+    int first = -1;
+    uint64_t g = 0;
+    for (uint32_t i = 0; i < num_streams; i++) {
+        struct LINNEAmdRepair &s = streams[i];
+        const RpPlan &p = plans[i];
+        const bool ok = host[i].result == LNN_OK;
+        ctx->rp_gap0[i] = g;
+        s.result = host[i].result;
+        s.out_bytes = (ok || host[i].result == LNN_INSUFFICIENT_BUFFER) ? p.bytes : 0u;
+        s.lost_samples = ok ? p.lost_samples : 0u;
+        s.kept_blocks = ok ? (uint32_t)p.kept_blocks : 0u; s.fill_blocks = ok ? (uint32_t)p.fill_blocks : 0u;
+        s.num_gaps = ok ? (uint32_t)p.gaps.size() : 0u; s.exact = ok ? p.exact : 0u;
+        if (!ok) { if (first < 0) first = (int)i; continue; }
+        for (const RpGap &q : p.gaps) {
+            struct LINNEAmdGap &o = ctx->rp_gaps[g++];
+            o.first_sample = q.first_sample; o.num_samples = q.num_samples; o.src_offset = q.src_off; o.src_bytes = q.src_bytes; o.fill_blocks = (uint32_t)q.fill_blocks; o.reserved = 0;
+        }
+        ctx->repair_count[0]++; ctx->repair_count[1] += (int64_t)p.kept_blocks; ctx->repair_count[2] += (int64_t)p.fill_blocks; ctx->repair_count[3] += (int64_t)p.gaps.size();
+    }
+    ctx->rp_gap0[num_streams] = g; ctx->rp_streams = num_streams;
+    if (first < 0) return LNN_OK;
+    snprintf(ctx->err, sizeof(ctx->err), "repair %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    return host[first].result;
+}
+
+/* test infrastructure (like lnn_splice_plan: exported, not in include/): lnn_repair.h's plan on host tables, without a GPU.
+ * in: { N, S, stream_bytes, capacity }; blocks: per kept block { offset, size field, samples }.  out_rec: 9 words { result, bytes,
+ * kept blocks, fill blocks, gaps, lost samples, exact, runs, fill bytes }; gap_rec: per gap 6 words { first sample, samples, source
+ * offset, source bytes, fill blocks, offset in the fill bytes }; run_rec: per run 4 words { fill, src, dst, bytes }; fill: the fill
+ * bytes.  Nothing is written beyond the capacities given.  Returns 0, -1 on a bad argument or without memory. */
+extern "C" int64_t lnn_repair_plan(const uint64_t *in, const uint64_t *blocks, uint64_t nblocks, uint64_t *out_rec, uint64_t *gap_rec, uint64_t gap_cap,
+        uint64_t *run_rec, uint64_t run_cap, uint8_t *fill, uint64_t fill_cap)
+{
+    if (!in || !out_rec || in[1] == 0u || (nblocks && !blocks)) return -1;
+    try {
+        lnn_tables_init();                                          /* (lnn_crc16's table) */
+        std::vector<RpPiece> pieces(nblocks);
+        for (uint64_t i = 0; i < nblocks; i++) { const RpPiece q = { blocks[3u * i], blocks[3u * i + 1u] + 6u, blocks[3u * i + 2u], 1u }; pieces[i] = q; }
+        RpPlan p;
+        rp_plan(pieces.data(), nblocks, in[0], in[1], in[2], in[3], lnn_crc16, p);
+        out_rec[0] = (uint64_t)(int64_t)p.result; out_rec[1] = p.bytes; out_rec[2] = p.kept_blocks; out_rec[3] = p.fill_blocks; out_rec[4] = p.gaps.size();
+        out_rec[5] = p.lost_samples; out_rec[6] = p.exact; out_rec[7] = p.runs.size(); out_rec[8] = p.fill.size();
+        for (size_t i = 0; i < p.gaps.size() && i < gap_cap && gap_rec; i++) {
+            const RpGap &g = p.gaps[i]; uint64_t *r = gap_rec + 6u * i;
+            r[0] = g.first_sample; r[1] = g.num_samples; r[2] = g.src_off; r[3] = g.src_bytes; r[4] = g.fill_blocks; r[5] = g.fill_at;
+        }
+        for (size_t i = 0; i < p.runs.size() && i < run_cap && run_rec; i++) {
+            const RpRun &q = p.runs[i]; uint64_t *r = run_rec + 4u * i;
+            r[0] = q.fill; r[1] = q.src; r[2] = q.dst; r[3] = q.bytes;
+        }
+        if (fill) for (size_t i = 0; i < p.fill.size() && i < fill_cap; i++) fill[i] = p.fill[i];
+        return 0;
     } catch (const std::bad_alloc &) { return -1; }
 }
 

@@ -7,11 +7,16 @@
  *     threads; identical bytes); -B / --block-at-a-time walks LINNEEncoder_EncodeBlock like the reference tool does;
  *   - --batch DIR encodes (or decodes) every remaining argument into DIR with ONE handle, so the GPU context and the
  *     pinned staging slots are set up once (BASELINE config 4: many independent tracks);
- *   - -l and -a N are parsed and refused: the MI355X path does not offer them.
+ *   - -l and -a N are parsed and refused: the MI355X path does not offer them;
+ *   - -r / --repair IN.lnn OUT.lnn repairs a damaged stream on the device (LINNEAmd_RepairStreamsDevice: sound blocks kept, lost
+ *     stretches replaced by SILENT blocks), prints the report to stderr and exits 0 when the output was written.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
+#include "linne_amd.h"
 #include "wavio.h"
+
+#include <hip/hip_runtime_api.h>
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,7 +24,7 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
     const char *batch_dir;
     const char *files[4096];
@@ -35,6 +40,7 @@ static void usage(const char *argv0)
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
+           "  -r, --repair                           Repair a damaged .lnn stream into a valid one (report on stderr) \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -69,6 +75,7 @@ static void parse(int argc, char **argv, struct options *o)
         const char *a = argv[i], *v = NULL;
         if (strcmp(a, "-e") == 0 || strcmp(a, "--encode") == 0) o->encode = 1;
         else if (strcmp(a, "-d") == 0 || strcmp(a, "--decode") == 0) o->decode = 1;
+        else if (strcmp(a, "-r") == 0 || strcmp(a, "--repair") == 0) o->repair = 1;
         else if (strcmp(a, "-c") == 0 || strcmp(a, "--no-crc-check") == 0) o->no_crc = 1;
         else if (strcmp(a, "-l") == 0 || strcmp(a, "--enable-learning") == 0) o->learning = 1;
         else if (strcmp(a, "-B") == 0 || strcmp(a, "--block-at-a-time") == 0) o->block_at_a_time = 1;
@@ -190,6 +197,55 @@ static int decode_one(struct LINNEDecoder *dec, const struct options *o, const c
     return 0;
 }
 
+/* -r: the stream goes to the device, LINNEAmd_RepairStreamsDevice repairs it there, the result comes back */
+static int repair_one(const char *in_path, const char *out_path)
+{
+    uint8_t *buf = NULL, *out = NULL;
+    void *d_in = NULL, *d_out = NULL;
+    uint32_t size = 0, i, ngaps = 0;
+    struct LINNEHeader h;
+    struct LINNEAmdContext *ctx = NULL;
+    struct LINNEAmdRepair rep;
+    const struct LINNEAmdGap *gaps = NULL;
+    uint64_t cap;
+    FILE *fp;
+    int ret, rc = 1, pass;
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    cap = (uint64_t)size + 22;
+    if (LINNEDecoder_DecodeHeader(buf, size, &h) == LINNE_APIRESULT_OK && h.num_samples_per_block > 0) {
+        const uint32_t full = h.num_samples_per_block < 65535u ? h.num_samples_per_block : 65535u;
+        cap = (uint64_t)size + 11ull * (h.num_samples / full + 2u);
+    }
+    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { fprintf(stderr, "Failed to create a device context. \n"); goto done; }
+    if (hipMalloc(&d_in, size ? size : 1) != hipSuccess || hipMemcpy(d_in, buf, size, hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "Failed to copy the stream to the device. \n"); goto done; }
+    memset(&rep, 0, sizeof(rep));
+    for (pass = 0; pass < 2; pass++) {                             /* (a stream of many gaps may need more room: once more at its exact size) */
+        if (hipMalloc(&d_out, cap) != hipSuccess) { fprintf(stderr, "Failed to allocate %llu bytes on the device. \n", (unsigned long long)cap); d_out = NULL; goto done; }
+        rep.d_stream = d_in; rep.stream_bytes = size; rep.d_out = d_out; rep.capacity = cap;
+        ret = LINNEAmd_RepairStreamsDevice(ctx, &rep, 1);
+        if (ret != LINNE_APIRESULT_INSUFFICIENT_BUFFER || pass == 1) break;
+        (void)hipFree(d_out); d_out = NULL; cap = rep.out_bytes;
+    }
+    if (ret != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to repair! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    if (!(out = malloc(rep.out_bytes ? (size_t)rep.out_bytes : 1)) || hipMemcpy(out, d_out, rep.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the repaired stream. \n"); goto done; }
+    if (!(fp = fopen(out_path, "wb")) || fwrite(out, 1, (size_t)rep.out_bytes, fp) != rep.out_bytes) { fprintf(stderr, "File output error! %s \n", out_path); if (fp) fclose(fp); goto done; }
+    fclose(fp);
+    rc = 0;
+    fprintf(stderr, "repaired: %u -> %llu bytes, kept blocks %u, fill blocks %u, gaps %u, lost samples %llu, exact %u \n", size, (unsigned long long)rep.out_bytes,
+            rep.kept_blocks, rep.fill_blocks, rep.num_gaps, (unsigned long long)rep.lost_samples, rep.exact);
+    if (LINNEAmd_GetLastRepairGaps(ctx, 0, &gaps, &ngaps) == LINNE_APIRESULT_OK)
+        for (i = 0; i < ngaps; i++)
+            fprintf(stderr, "gap %u: samples [%llu, %llu), source bytes [%llu, %llu), fill blocks %u \n", i, (unsigned long long)gaps[i].first_sample,
+                    (unsigned long long)(gaps[i].first_sample + gaps[i].num_samples), (unsigned long long)gaps[i].src_offset,
+                    (unsigned long long)(gaps[i].src_offset + gaps[i].src_bytes), gaps[i].fill_blocks);
+done:
+    if (d_out) (void)hipFree(d_out);
+    if (d_in) (void)hipFree(d_in);
+    if (ctx) LINNEAmd_ContextDestroy(ctx);
+    free(out); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -198,6 +254,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.repair) {
+        if (o.encode || o.decode || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        return repair_one(o.files[0], o.files[1]);
+    }
     if (o.encode && o.decode) { fprintf(stderr, "%s: encode and decode mode cannot specify simultaneously. \n", argv[0]); return 1; }
     if (!o.encode && !o.decode) { fprintf(stderr, "%s: decode(-d) or encode(-e) option must be specified. \n", argv[0]); return 1; }
     if (o.batch_dir ? (o.num_files < 1) : (o.num_files != 2)) { fprintf(stderr, "%s: input and output file name must be specified. \n", argv[0]); return 1; }
