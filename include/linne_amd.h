@@ -374,6 +374,11 @@ enum LINNEAmdRepairTimingKind {
     LINNE_AMD_REPAIR_T_MARK = 77,           /* the cut at the header's sample count, where runs of adjacent kept blocks begin (k_rp_mark) */
     LINNE_AMD_REPAIR_T_RUNS = 78            /* a record per run (k_rp_runs) */
 };
+/* comparing windows with resident PCM (LINNEAmd_CompareWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of
+ * this one wherever that call has one of kind 59) */
+enum LINNEAmdCompareTimingKind {
+    LINNE_AMD_COMPARE_T_COMPARE = 79        /* comparing every window's samples with the caller's PCM (k_wx_compare) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -599,6 +604,36 @@ int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNE
         const struct LINNEAmdPcmLayout *layouts /* [num_tracks] */, uint32_t num_tracks, uint32_t group_frames);
 int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         struct LINNEAmdPcmLayout *layouts /* [num_windows], in/out */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- comparing sample windows of resident streams with resident PCM: the proof that a stream holds the samples it was made from ----
+ * LINNEAmd_CompareWindowsDevice takes the windows and layouts of LINNEAmd_DecodeWindowsDeviceLayout (layouts == NULL: int32 planar,
+ * pcm_stride) and, instead of writing every window's samples to its d_pcm, compares them with what d_pcm holds.
+ * Every window's `result` is what LINNEAmd_DecodeWindowsDeviceLayout gives it -- its argument, layout and alignment checks, the
+ * index's failing block at or before the range, the Rice consumption check -- with one exception: LINNE_AMD_PCM_F32 is that window's
+ * INVALID_ARGUMENT, as on encode.  For an OK window diffs[i] describes the difference between what that call would have written and
+ * what d_pcm holds: num_differing counts the (sample, channel) elements that differ, first_sample / first_channel name the first of
+ * them -- the lowest sample, then the lowest channel; both 0 when there is none.  A window that differs is still LINNE_APIRESULT_OK:
+ * a difference is an answer, not an error.  S32 elements are compared as they are; S16 and S24 elements are sign-extended and
+ * compared with the decoded value, nothing is saturated: a decoded sample outside the format's range differs from every element
+ * (where the decode call would have clipped and set `saturated`).  A failing window's diffs[i] is left as it was, and a failing
+ * window does not disturb the others.
+ * d_pcm is only read -- no load touches a byte outside the elements the layout names -- and layouts[i].saturated is not written.
+ * Shape groups, passes, group_frames, scratch and whole-call failures are the decode call's: LINNE_APIRESULT_OK when every window is
+ * OK, otherwise the result of the lowest-numbered failing window, with "window <i>: " and the single call's text in GetLastError; a
+ * HIP error or running out of memory fails the whole call (LINNE_APIRESULT_NG, in every `result` too, diffs untouched).  The number
+ * of kernel launches, copies (one upload, one fetch) and host synchronisations (one) does not depend on num_windows; a pass has the
+ * decode call's launches with kind 79 in place of kind 59, and a window that spans passes collects its answer over them.
+ * num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL diffs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the
+ * context's stream and synchronous. */
+struct LINNEAmdDiff {
+    uint64_t num_differing;             /* (sample, channel) elements of the window that differ */
+    uint64_t first_sample;              /* stream sample index of the first one: lowest sample, then lowest channel; 0 when none */
+    uint32_t first_channel;             /* 0 when none */
+    uint32_t reserved;
+};
+int LINNEAmd_CompareWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdPcmLayout *layouts /* [num_windows]; NULL: int32 planar, pcm_stride */,
+        struct LINNEAmdDiff *diffs /* [num_windows], out */, uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

@@ -55,6 +55,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_StreamIndexesCreate", "LINNEAmd_GetLastIndexBatchCount", "LINNEAmd_StreamIndexBlocks", "LINNEAmd_StreamIndexFailure",
     "LINNEAmd_SpliceStreamsDevice", "LINNEAmd_GetLastSpliceCount",
     "LINNEAmd_RepairStreamsDevice", "LINNEAmd_GetLastRepairGaps", "LINNEAmd_GetLastRepairCount",
+    "LINNEAmd_CompareWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -110,6 +111,11 @@ class Repair(C.Structure):
 class PcmLayout(C.Structure):
     """struct LINNEAmdPcmLayout (include/linne_amd.h)"""
     _fields_ = [("format", C.c_uint32), ("saturated", C.c_uint32), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64)]
+
+
+class Diff(C.Structure):
+    """struct LINNEAmdDiff (include/linne_amd.h)"""
+    _fields_ = [("num_differing", C.c_uint64), ("first_sample", C.c_uint64), ("first_channel", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 def _load():
@@ -189,6 +195,7 @@ def _load():
                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     L.LINNEAmd_EncodeStreamsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Track), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_DecodeWindowsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_CompareWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.POINTER(Diff), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -223,7 +230,7 @@ def device_count():
 
 class LinneAmdError(RuntimeError):
     """code: the LINNEApiResult of the failing call, where one is known; codes: those of a batch's members (decode_windows,
-    encode_streams)"""
+    encode_streams; a verified encode: 7 for a track that differs)"""
 
     def __init__(self, msg, code=None, codes=None):
         super().__init__(msg)
@@ -279,6 +286,7 @@ class Context:
             raise LinneAmdError(f"LINNEAmd_ContextCreate(device={device}) failed: no usable HIP device "
                                 "(the prediction path has no CPU fallback)")
         self.device = int(device)
+        self._verify = False
         # With its own stream the library's kernels are NOT ordered behind what torch enqueued on torch's stream -- the fill kernel of a
         # torch.zeros, a clone, a copy from the host: the binding then drains torch's stream before every call that touches tensors
         # (_fence).  It went unnoticed while both streams happened to share a hardware queue; with the library's 24 queues they do not.
@@ -327,6 +335,12 @@ class Context:
 
     def set_learning(self, on):
         self._check(lib.LINNEAmd_SetLearning(self.h, int(bool(on))), "SetLearning")
+
+    def set_verify(self, on):
+        """a setting of the context like -l and -a N: encode_stream and encode_streams compare every stream they are about to return
+        with the PCM it was made from (verify_streams) and raise LinneAmdError (code 7) when one differs.  (A setting, not a
+        parameter of the two calls: their parameter lists are pinned.)  The bytes do not change"""
+        self._verify = bool(on)
 
     def set_af_iterations(self, n):
         self._check(lib.LINNEAmd_SetAfIterations(self.h, int(n)), "SetAfIterations")
@@ -584,6 +598,94 @@ class Context:
         res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
         return res[0] if len(res) == 1 else res
 
+    def compare_windows(self, windows, group_frames=0, return_codes=False):
+        """many sample windows of resident .lnn streams compared with resident PCM in one call, nothing decoded into memory of the
+        caller's (include/linne_amd.h LINNEAmd_CompareWindowsDevice).  windows: a sequence of (stream, index, first_sample,
+        num_samples, pcm): the first four as decode_windows takes them, pcm as encode_stream takes it -- an int32 or int16 CUDA tensor
+        (C, n) with any strides, or a uint8 one (C, n, 3) of packed 24-bit samples -- of exactly the window's (C, n).  -> a list of
+        (num_differing, first_sample, first_channel) per window: the (sample, channel) elements at which the PCM is not what
+        decode_windows would have written, and the first of them (lowest stream sample, then lowest channel; 0, 0 when none).  A
+        window that differs is not an error.  Errors follow decode_windows: LinneAmdError with .code and .codes when a window fails;
+        with return_codes -> (answers, codes), a failing window's answer is None, and only a failure of the whole call raises.  The
+        PCM is only read"""
+        W = len(windows)
+        arr = (Window * max(W, 1))()
+        lays = (PcmLayout * max(W, 1))()
+        diffs = (Diff * max(W, 1))()
+        keep = []
+        for i, (stream, index, first, n, pcm) in enumerate(windows):
+            t = self._stream_bytes(stream)
+            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            fmt, cs, ss, nch, ns, _ = self._pcm_layout(pcm, f"window {i}: pcm")
+            assert pcm.device.index == self.device, f"window {i}: the PCM is on {pcm.device}, the context on cuda:{self.device}"
+            assert (nch, ns) == (index.header["num_channels"], max(n, 0)), \
+                f"window {i} is {(index.header['num_channels'], max(n, 0))}, its pcm holds {(nch, ns)}"
+            keep.append((t, pcm))
+            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
+            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+            arr[i].d_pcm, arr[i].pcm_stride = pcm.data_ptr(), ns
+            lays[i].format, lays[i].channel_stride, lays[i].sample_stride = fmt, cs, ss
+        self._fence()
+        ret = lib.LINNEAmd_CompareWindowsDevice(self.h, arr, lays, diffs, W, int(group_frames))
+        codes = [int(arr[i].result) for i in range(W)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
+                raise LinneAmdError(f"CompareWindowsDevice -> {ret}: {msg}", ret, codes)
+        out = [(int(diffs[i].num_differing), int(diffs[i].first_sample), int(diffs[i].first_channel)) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def verify_streams(self, pairs, group_frames=0):
+        """do these .lnn streams hold exactly these samples?  pairs: a sequence of (stream, pcm), a whole stream (as index_streams
+        takes it) and the PCM it should decode to (as compare_windows takes it).  One index_streams call and one compare_windows
+        call over the whole streams -> a list of (num_differing, first_sample, first_channel, reason) per pair: (0, 0, 0, None) for a
+        stream that holds its PCM; the count and the first differing element (reason None) for one that decodes to other samples;
+        num_differing None with the reason as text for one that does not index or decode, or whose header names other channel or
+        sample counts than the PCM has.  Only a failure of a whole call raises"""
+        T = len(pairs)
+        if T == 0:
+            return []
+        streams = [self._stream_bytes(s) for s, _ in pairs]
+        indexes, icodes = self.index_streams(streams, return_codes=True)
+        try:
+            out, wins, at = [None] * T, [], []
+            for i, (x, (_, pcm)) in enumerate(zip(indexes, pairs)):
+                if x is None:
+                    out[i] = (None, 0, 0, f"the stream does not index (LINNEApiResult {icodes[i]})")
+                    continue
+                _, _, _, nch, ns, _ = self._pcm_layout(pcm, f"pair {i}: pcm")
+                if (x.header["num_channels"], x.header["num_samples"]) != (nch, ns):
+                    out[i] = (None, 0, 0, f"the header names {x.header['num_channels']} channels of {x.header['num_samples']} samples, the PCM has {nch} of {ns}")
+                    continue
+                wins.append((streams[i], x, 0, ns, pcm))
+                at.append(i)
+            if wins:
+                answers, codes = self.compare_windows(wins, group_frames=group_frames, return_codes=True)
+                for i, a, c in zip(at, answers, codes):
+                    out[i] = a + (None,) if c == 0 else (None, 0, 0, f"the stream does not decode (LINNEApiResult {c})")
+            return out
+        finally:
+            for x in indexes:
+                if x is not None:
+                    x.close()
+
+    def _verified(self, streams, pcms, what):
+        """set_verify(True) in encode_stream / encode_streams: raises when a stream that was encoded does not hold its track's PCM"""
+        live = [i for i, s in enumerate(streams) if s is not None]
+        res = self.verify_streams([(streams[i], pcms[i]) for i in live])
+        codes, first = [0] * len(streams), None
+        for i, (k, s, c, reason) in zip(live, res):
+            if k == 0:
+                continue
+            codes[i] = 7                                               # LINNE_APIRESULT_NG
+            if first is None:
+                first = f"track {i}: verification failed: {reason}" if k is None else \
+                    f"track {i}: verification failed at sample {s}, channel {c} ({k} elements differ)"
+        if first is not None:
+            raise LinneAmdError(f"{what} -> 7: {first}", 7, codes)
+
     @staticmethod
     def _pcm_layout(pcm, what="pcm"):
         """(format, channel stride, sample stride, channels, samples, plain) of a PCM tensor: int32 or int16 (C, N), or uint8 (C, N, 3)
@@ -609,7 +711,9 @@ class Context:
         as a 1-D uint8 CUDA tensor (a view of `out` when one is given); with parcor_state (a float, the quirk-Q2 state) not None, the
         pair (stream, new state).  include/linne_amd.h LINNEAmd_EncodeStreamDevice states the result contract.  The default buffer is
         what the reference's command line tool allocates (twice the PCM's bytes at `bits` width, plus the header); a stream that does not
-        fit is encoded again into a buffer of its exact size.  Raises LinneAmdError with .code = the LINNEApiResult"""
+        fit is encoded again into a buffer of its exact size.  Raises LinneAmdError with .code = the LINNEApiResult.  After
+        set_verify(True) the stream is compared with the PCM before it is returned (verify_streams): LinneAmdError with .code = 7
+        (LINNE_APIRESULT_NG) and the text "track 0: verification failed at sample s, channel c (k elements differ)" when they differ"""
         import torch
         if not isinstance(pcm, torch.Tensor):
             pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int32)).to(f"cuda:{self.device}")
@@ -641,6 +745,8 @@ class Context:
         if ret != 0:
             raise LinneAmdError(f"EncodeStreamDevice -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
         stream = buf[:nbytes.value]
+        if self._verify:
+            self._verified([stream], [pcm], "EncodeStreamDevice")
         return stream if parcor_state is None else (stream, state.value)
 
     def last_stream_encode_count(self, which):
@@ -656,7 +762,9 @@ class Context:
         parcor_states (a list of floats, the tracks' quirk-Q2 states) -> (streams, new states).  Raises LinneAmdError with .code =
         the call's result and .codes = the per-track LINNEApiResults when a track fails; with return_codes the codes are appended
         to the result, and only a failure of the whole call raises.  group_frames bounds the frames of one pass (0: one pass per
-        shape) and never changes a byte"""
+        shape) and never changes a byte.  After set_verify(True) every encoded stream is compared with its track's PCM before anything is
+        returned (one verify_streams call): LinneAmdError with .code = 7 (LINNE_APIRESULT_NG), .codes per track (7 where a track
+        differs) and the text "track i: verification failed at sample s, channel c (k elements differ)" when one differs"""
         import torch
         dev = f"cuda:{self.device}"
         T = len(tracks)
@@ -718,6 +826,8 @@ class Context:
             msg = f"track {bad[0]} failed" if bad else ""
         if ret != 0 and not return_codes:
             raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, codes)
+        if self._verify:
+            self._verified(streams, keep, "EncodeStreamsDevice")
         out = (streams,) if parcor_states is None else (streams, states)
         if return_codes:
             out += (codes,)

@@ -49,6 +49,7 @@
 #include "lnn_k_stream.h"
 #include "lnn_k_index_batch.h"
 #include "lnn_k_windows.h"
+#include "lnn_k_compare.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_k_splice.h"               /* (brings lnn_splice.h: the host's plan of a splice call) */
@@ -59,6 +60,7 @@
 static_assert(LINNE_AMD_T_IB_HEADERS == 69 && LINNE_AMD_T_IB_BEHIND == 70, "the index batch's timing kinds are 69 and 70");
 static_assert(LINNE_AMD_SPLICE_T_COPY == 71 && LINNE_AMD_SPLICE_T_HEADER == 72, "the splice call's timing kinds are 71 and 72");
 static_assert(LINNE_AMD_REPAIR_T_SOUND == 73 && LINNE_AMD_REPAIR_T_RUNS == 78, "the repair call's timing kinds are 73 to 78");
+static_assert(LINNE_AMD_COMPARE_T_COMPARE == 79, "the compare call's timing kind is 79");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2270,8 +2272,8 @@ extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const u
  * ============================================================================================== */
 /* the argument and index checks on one window, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are).  *r1 = the last block the window overlaps (nb: it reaches behind the last block); not set for a window of 0
- * samples */
-static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, const struct LINNEAmdPcmLayout *ly, char *err, size_t cap, uint64_t *r1)
+ * samples.  compare: the window's PCM is read, not written, and LINNE_AMD_PCM_F32 is refused as on encode */
+static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, const struct LINNEAmdPcmLayout *ly, bool compare, char *err, size_t cap, uint64_t *r1)
 {
     const LINNEAmdStreamIndex *x = w->index;
     err[0] = 0;
@@ -2280,7 +2282,7 @@ static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWind
     const uint64_t total = x->header.num_samples;
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
     if (ly) {
-        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, x->shape.num_channels, w->num_samples, true);
+        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, x->shape.num_channels, w->num_samples, !compare);
         if (why != SB_LY_OK) { snprintf(err, cap, "DecodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
     } else if (x->shape.num_channels > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
     if (w->num_samples == 0) return LNN_OK;
@@ -2314,18 +2316,21 @@ static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_by
 #define WX_MAXGROUPS 64
 
 /* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call.  single: the call
- * is LINNEAmd_DecodeStreamDevice, which its texts then name */
-static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LINNEAmdPcmLayout *layouts, uint32_t W, uint32_t group_frames, bool single, WxPlan *plan, const uint32_t **fail_out)
+ * is LINNEAmd_DecodeStreamDevice, which its texts then name.  compare: the call is LINNEAmd_CompareWindowsDevice -- every pass that
+ * would place compares instead (k_wx_compare for k_wx_place, nothing else differs), and behind the fail and saturation words the
+ * list carries two 64-bit words per window, its count of differing elements and their least key, which come back with them */
+static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const struct LINNEAmdPcmLayout *layouts, uint32_t W, uint32_t group_frames, bool single, bool compare,
+        WxPlan *plan, const uint32_t **fail_out)
 {
     const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
-    const char *who = single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
+    const char *who = compare ? "CompareWindowsDevice" : single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
     char text[sizeof(ctx->err)];
     /* 1. the checks per window; the live ones get their blocks and the group of their shape */
     uint64_t nlive = 0, total_rec = 0, total_crec = 0;
     for (uint32_t i = 0; i < W; i++) {
         uint64_t r1 = 0;
         plan[i].group = -1; plan[i].r0 = plan[i].nr = plan[i].ncomp = 0;
-        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, text, sizeof(text), &r1);
+        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, compare, text, sizeof(text), &r1);
         if (win[i].result != LNN_OK || win[i].num_samples == 0) continue;
         const LINNEAmdStreamIndex *x = win[i].index;
         const uint64_t lo = win[i].first_sample;
@@ -2348,8 +2353,10 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LI
     if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu blocks in one call: too many", who, (unsigned long long)total_rec); return LNN_NG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
-    /* 2. the lists, in pinned memory: fail words, saturation words | window records | block records | the passes' COMPRESS records */
-    const uint64_t o_fail = 0, o_win = align_up(2u * sizeof(uint32_t) * (uint64_t)W), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
+    /* 2. the lists, in pinned memory: fail words, saturation words (compare: and the difference words) | window records | block
+     * records | the passes' COMPRESS records */
+    const uint64_t o_fail = 0, o_diff = 2u * sizeof(uint32_t) * (uint64_t)W, back_bytes = o_diff + (compare ? 2u * sizeof(uint64_t) * (uint64_t)W : 0u);
+    const uint64_t o_win = align_up(back_bytes), o_rec = align_up(o_win + sizeof(WxWindow) * nlive),
             o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
     if (ctx->wstage_cap < list_bytes) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2363,6 +2370,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LI
     WxWindow *h_win = (WxWindow *)(hs_ + o_win);
     WxBlock *h_rec = (WxBlock *)(hs_ + o_rec);
     for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
+    if (compare) { uint64_t *h_diff = (uint64_t *)(hs_ + o_diff); for (uint32_t i = 0; i < W; i++) { h_diff[2u * i] = 0u; h_diff[2u * i + 1u] = ~(uint64_t)0; } }
     std::vector<WxPass> passes;
     uint32_t nrec = 0, ncrec = 0, nwin = 0;
     uint64_t scratch_bytes = 0;
@@ -2464,10 +2472,14 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LI
         la.sat = d_fail + W; la.scale = ldexpf(1.0f, 1 - (int)x->shape.bits_per_sample);
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
         if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
-        SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+        if (compare) {
+            WxCompareArgs ca; ca.p = la; ca.diff = (unsigned long long *)(wd + o_diff);
+            SX_LAUNCH(LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
+        } else
+            SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
-    /* 5. the fail words and the saturation words behind them, with the call's one wait */
-    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, 2u * sizeof(uint32_t) * (uint64_t)W, hipMemcpyDeviceToHost, ctx->stream));
+    /* 5. the fail words and the saturation words (and the difference words) behind them, with the call's one wait */
+    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t i = 0; i < W; i++) if (plan[i].group >= 0 && h_fail[i] != WX_NOFAIL) win[i].result = LNN_NG;
@@ -2477,13 +2489,15 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, struct LI
 
 /* Both entry points behind their argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
  * with its text in ctx->err (behind the window's number unless the call is the single one) */
-static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct LINNEAmdPcmLayout *layouts, uint32_t num_windows, uint32_t group_frames, bool single)
+static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdPcmLayout *layouts, struct LINNEAmdPcmLayout *layouts_out,
+        uint32_t num_windows, uint32_t group_frames, bool single, struct LINNEAmdDiff *diffs)
 {
+    const bool compare = diffs != NULL;
     ctx->err[0] = 0;
     const uint32_t *fail = NULL;
     std::vector<WxPlan> plan;
     int ret;
-    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, layouts, num_windows, group_frames, single, plan.data(), &fail); }
+    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, layouts, num_windows, group_frames, single, compare, plan.data(), &fail); }
     catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
     if (ret != LNN_OK) {
         /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
@@ -2492,15 +2506,25 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct L
         return LNN_NG;
     }
     /* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
-    if (layouts) for (uint32_t i = 0; i < num_windows; i++)
-        if (windows[i].result == LNN_OK) layouts[i].saturated = (plan[i].group >= 0 && fail && fail[num_windows + i]) ? 1u : 0u;
+    if (layouts_out) for (uint32_t i = 0; i < num_windows; i++)
+        if (windows[i].result == LNN_OK) layouts_out[i].saturated = (plan[i].group >= 0 && fail && fail[num_windows + i]) ? 1u : 0u;
+    /* (a failing window's diffs[i] stays too; an OK window of no samples took no pass and differs nowhere) */
+    if (compare) for (uint32_t i = 0; i < num_windows; i++) {
+        if (windows[i].result != LNN_OK) continue;
+        const uint64_t *dw = (plan[i].group >= 0 && fail) ? (const uint64_t *)(fail + 2u * (uint64_t)num_windows) + 2u * (uint64_t)i : NULL;
+        const uint64_t cnt = dw ? dw[0] : 0u;
+        diffs[i].num_differing = cnt;
+        diffs[i].first_sample = cnt ? windows[i].first_sample + (dw[1] >> 3) : 0u;
+        diffs[i].first_channel = cnt ? (uint32_t)(dw[1] & 7u) : 0u;
+        diffs[i].reserved = 0u;
+    }
     for (uint32_t i = 0; i < num_windows; i++) {
         if (windows[i].result == LNN_OK) continue;
         char text[sizeof(ctx->err)]; uint64_t r1;
         if (plan[i].group >= 0 && fail)
             snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
                     fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
-        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, text, sizeof(text), &r1);
+        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, compare, text, sizeof(text), &r1);
         if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
         else snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
         return windows[i].result;
@@ -2515,12 +2539,23 @@ extern "C" int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, s
     ctx->err[0] = 0;
     if (num_windows == 0) return LNN_OK;
     if (!windows) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, layouts, num_windows, group_frames, false);
+    return wx_run(ctx, windows, layouts, layouts, num_windows, group_frames, false, NULL);
 }
 /* int32 planar windows: the call above without layouts */
 extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
 {
     return LINNEAmd_DecodeWindowsDeviceLayout(ctx, windows, NULL, num_windows, group_frames);
+}
+
+/* the windows compared with the PCM they name instead of written into it */
+extern "C" int LINNEAmd_CompareWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdPcmLayout *layouts,
+        struct LINNEAmdDiff *diffs, uint32_t num_windows, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (num_windows == 0) return LNN_OK;
+    if (!windows || !diffs) { snprintf(ctx->err, sizeof(ctx->err), "CompareWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    return wx_run(ctx, windows, layouts, NULL, num_windows, group_frames, false, diffs);
 }
 
 /* one window of one stream */
@@ -2530,7 +2565,7 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (!ctx) return LNN_INVALID_ARGUMENT;
     struct LINNEAmdWindow w;
     w.index = x; w.d_stream = d_stream; w.first_sample = first_sample; w.num_samples = num_samples; w.d_pcm = d_pcm; w.pcm_stride = pcm_stride; w.result = LNN_OK;
-    return wx_run(ctx, &w, NULL, 1, 0, true);
+    return wx_run(ctx, &w, NULL, NULL, 1, 0, true, NULL);
 }
 
 

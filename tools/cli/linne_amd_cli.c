@@ -9,7 +9,10 @@
  *     pinned staging slots are set up once (BASELINE config 4: many independent tracks);
  *   - -l and -a N are parsed and refused: the MI355X path does not offer them;
  *   - -r / --repair IN.lnn OUT.lnn repairs a damaged stream on the device (LINNEAmd_RepairStreamsDevice: sound blocks kept, lost
- *     stretches replaced by SILENT blocks), prints the report to stderr and exits 0 when the output was written.
+ *     stretches replaced by SILENT blocks), prints the report to stderr and exits 0 when the output was written;
+ *   - -V / --verify (with -e) compares the encoded stream with the WAV's samples on the device (LINNEAmd_CompareWindowsDevice) before
+ *     the output file is written, and writes nothing when they differ; -C / --compare STREAM.lnn PCM.wav does the same for a stream
+ *     and a WAV file that exist: exit 0 and "identical", or exit 1 and the first differing sample.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -24,7 +27,7 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
     const char *batch_dir;
     const char *files[4096];
@@ -37,10 +40,13 @@ static void usage(const char *argv0)
 {
     printf("Usage: %s [options] INPUT_FILE_NAME OUTPUT_FILE_NAME \n", argv0);
     printf("       %s [options] --batch OUTPUT_DIRECTORY INPUT_FILE_NAME... \n", argv0);
+    printf("       %s -C STREAM.lnn PCM.wav \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
            "  -r, --repair                           Repair a damaged .lnn stream into a valid one (report on stderr) \n"
+           "  -V, --verify                           With -e: compare the stream with the input's samples on the device before writing it \n"
+           "  -C, --compare                          Compare a .lnn stream with a WAV file's samples on the device (exit 0: identical) \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -76,6 +82,8 @@ static void parse(int argc, char **argv, struct options *o)
         if (strcmp(a, "-e") == 0 || strcmp(a, "--encode") == 0) o->encode = 1;
         else if (strcmp(a, "-d") == 0 || strcmp(a, "--decode") == 0) o->decode = 1;
         else if (strcmp(a, "-r") == 0 || strcmp(a, "--repair") == 0) o->repair = 1;
+        else if (strcmp(a, "-V") == 0 || strcmp(a, "--verify") == 0) o->verify = 1;
+        else if (strcmp(a, "-C") == 0 || strcmp(a, "--compare") == 0) o->compare = 1;
         else if (strcmp(a, "-c") == 0 || strcmp(a, "--no-crc-check") == 0) o->no_crc = 1;
         else if (strcmp(a, "-l") == 0 || strcmp(a, "--enable-learning") == 0) o->learning = 1;
         else if (strcmp(a, "-B") == 0 || strcmp(a, "--block-at-a-time") == 0) o->block_at_a_time = 1;
@@ -118,6 +126,78 @@ static int read_file(const char *path, uint8_t **data, uint32_t *size)
     fclose(fp);
     *size = (uint32_t)n;
     return 0;
+}
+
+/* The stream and the WAV's int32 planes go to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_CompareWindowsDevice window over
+ * the whole stream answer.  0: *diff is the answer; 1: the stream does not index or decode, or the device failed (text in err) */
+static int device_compare(const uint8_t *stream, uint32_t size, const struct wav_pcm *wav, struct LINNEAmdDiff *diff, char *err, size_t cap)
+{
+    struct LINNEAmdContext *ctx = NULL;
+    struct LINNEAmdStreamIndex *index = NULL;
+    struct LINNEAmdWindow w;
+    void *d_stream = NULL, *d_pcm = NULL;
+    const uint64_t n = wav->num_samples, plane = n * sizeof(int32_t);
+    uint32_t ch;
+    int ret = LINNE_APIRESULT_OK, rc = 1;
+    memset(diff, 0, sizeof(*diff));
+    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { snprintf(err, cap, "Failed to create a device context."); return 1; }
+    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, stream, size, hipMemcpyHostToDevice) != hipSuccess
+            || hipMalloc(&d_pcm, (plane && wav->num_channels) ? plane * wav->num_channels : 1) != hipSuccess) { snprintf(err, cap, "Failed to copy the stream and the samples to the device."); goto done; }
+    for (ch = 0; ch < wav->num_channels; ch++)
+        if (plane && hipMemcpy((uint8_t *)d_pcm + ch * plane, wav->plane[ch], plane, hipMemcpyHostToDevice) != hipSuccess) { snprintf(err, cap, "Failed to copy the stream and the samples to the device."); goto done; }
+    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { snprintf(err, cap, "the stream does not index: %d (%s)", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    memset(&w, 0, sizeof(w));
+    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n; w.d_pcm = d_pcm; w.pcm_stride = n;
+    if ((ret = LINNEAmd_CompareWindowsDevice(ctx, &w, NULL, diff, 1, 0)) != LINNE_APIRESULT_OK) { snprintf(err, cap, "the stream does not decode: %d (%s)", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    rc = 0;
+done:
+    if (index) LINNEAmd_StreamIndexDestroy(index);
+    if (d_pcm) (void)hipFree(d_pcm);
+    if (d_stream) (void)hipFree(d_stream);
+    LINNEAmd_ContextDestroy(ctx);
+    return rc;
+}
+
+/* is the stream's header the WAV's format?  (0: yes; otherwise the text says what is not) */
+static int header_matches(const struct LINNEHeader *h, const struct wav_pcm *wav, char *err, size_t cap)
+{
+    if (h->num_channels == wav->num_channels && h->bits_per_sample == wav->bits_per_sample && h->sampling_rate == wav->sampling_rate && h->num_samples == wav->num_samples) return 0;
+    snprintf(err, cap, "the stream holds %u channels, %u bits, %u Hz, %u samples; the WAV file %u channels, %u bits, %u Hz, %u samples",
+            (unsigned)h->num_channels, (unsigned)h->bits_per_sample, (unsigned)h->sampling_rate, (unsigned)h->num_samples,
+            wav->num_channels, wav->bits_per_sample, wav->sampling_rate, wav->num_samples);
+    return 1;
+}
+
+/* the verdict of -V and -C on stderr; 0: identical */
+static int report_compare(const uint8_t *stream, uint32_t size, const struct wav_pcm *wav)
+{
+    struct LINNEHeader h;
+    struct LINNEAmdDiff diff;
+    char err[512];
+    LINNEApiResult ret;
+    if ((ret = LINNEDecoder_DecodeHeader(stream, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "verification failed: the stream's header does not decode: %d \n", ret); return 1; }
+    if (header_matches(&h, wav, err, sizeof(err)) != 0 || device_compare(stream, size, wav, &diff, err, sizeof(err)) != 0) { fprintf(stderr, "verification failed: %s \n", err); return 1; }
+    if (diff.num_differing) {
+        fprintf(stderr, "verification failed: sample %llu channel %u (%llu elements differ) \n", (unsigned long long)diff.first_sample, diff.first_channel, (unsigned long long)diff.num_differing);
+        return 1;
+    }
+    return 0;
+}
+
+/* -C: a stream and a WAV file that exist */
+static int compare_one(const char *lnn_path, const char *wav_path)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0;
+    struct wav_pcm wav;
+    char err[256];
+    int rc;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if (wav_read(wav_path, &wav, err, sizeof(err)) != 0) { fprintf(stderr, "Failed to open %s. (%s) \n", wav_path, err); free(buf); return 1; }
+    rc = report_compare(buf, size, &wav);
+    if (rc == 0) printf("identical \n");
+    free(buf); wav_free(&wav);
+    return rc;
 }
 
 static int encode_one(struct LINNEEncoder *enc, const struct options *o, const char *in_path, const char *out_path)
@@ -164,11 +244,12 @@ static int encode_one(struct LINNEEncoder *enc, const struct options *o, const c
             if (!o->quiet) { printf("progress... %5.2f%% \r", (progress * 100.0f) / wav.num_samples); fflush(stdout); }
         }
     }
+    if (o->verify && report_compare(buf, out_size, &wav) != 0) { free(buf); wav_free(&wav); return 1; }      /* nothing is written */
     if (!(fp = fopen(out_path, "wb")) || fwrite(buf, 1, out_size, fp) != out_size) { fprintf(stderr, "File output error! %s \n", out_path); if (fp) fclose(fp); free(buf); wav_free(&wav); return 1; }
     fclose(fp);
     if (!o->quiet) {
         const uint64_t in_bytes = (uint64_t)wav.num_samples * wav.num_channels * (wav.bits_per_sample / 8) + 44;
-        printf("finished: %llu -> %u (%6.2f %%) in %.3f s \n", (unsigned long long)in_bytes, out_size, 100.0 * (double)out_size / (double)in_bytes, now_s() - t0);
+        printf("finished: %llu -> %u (%6.2f %%) in %.3f s%s \n", (unsigned long long)in_bytes, out_size, 100.0 * (double)out_size / (double)in_bytes, now_s() - t0, o->verify ? ", verified" : "");
     }
     free(buf); wav_free(&wav);
     return 0;
@@ -255,9 +336,14 @@ int main(int argc, char **argv)
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
     if (o.repair) {
-        if (o.encode || o.decode || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.compare || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return repair_one(o.files[0], o.files[1]);
     }
+    if (o.compare) {
+        if (o.encode || o.decode || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -C takes a stream and a WAV file name and no other mode. \n", argv[0]); return 1; }
+        return compare_one(o.files[0], o.files[1]);
+    }
+    if (o.verify && !o.encode) { fprintf(stderr, "%s: -V goes with encode mode (-e) only. \n", argv[0]); return 1; }
     if (o.encode && o.decode) { fprintf(stderr, "%s: encode and decode mode cannot specify simultaneously. \n", argv[0]); return 1; }
     if (!o.encode && !o.decode) { fprintf(stderr, "%s: decode(-d) or encode(-e) option must be specified. \n", argv[0]); return 1; }
     if (o.batch_dir ? (o.num_files < 1) : (o.num_files != 2)) { fprintf(stderr, "%s: input and output file name must be specified. \n", argv[0]); return 1; }
