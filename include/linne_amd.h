@@ -379,6 +379,13 @@ enum LINNEAmdRepairTimingKind {
 enum LINNEAmdCompareTimingKind {
     LINNE_AMD_COMPARE_T_COMPARE = 79        /* comparing every window's samples with the caller's PCM (k_wx_compare) */
 };
+/* measuring windows (LINNEAmd_MeasureWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of kind 80 wherever that
+ * call has one of kind 59, and one launch each of kinds 81 and 82 per call that takes a pass) */
+enum LINNEAmdMeasureTimingKind {
+    LINNE_AMD_MEASURE_T_MEASURE = 80,       /* reducing every window's samples into its buckets' accumulators (k_wx_measure) */
+    LINNE_AMD_MEASURE_T_PRESET = 81,        /* the call's accumulators preset, once, in front of the first pass (k_wx_measure_preset) */
+    LINNE_AMD_MEASURE_T_COMMIT = 82         /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_measure_commit) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -634,6 +641,43 @@ struct LINNEAmdDiff {
 int LINNEAmd_CompareWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdPcmLayout *layouts /* [num_windows]; NULL: int32 planar, pcm_stride */,
         struct LINNEAmdDiff *diffs /* [num_windows], out */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- measuring sample windows of resident streams: min, max, sum and energy per channel and bucket, no PCM written ----
+ * LINNEAmd_MeasureWindowsDevice takes the windows of LINNEAmd_DecodeWindowsDevice and, instead of writing every window's samples,
+ * reduces them: the only output is a table of struct LINNEAmdMeasure per window, in device memory.  A window of n samples with
+ * specs[i].bucket_samples = b > 0 has nb = ceil(n / b) buckets, bucket k holding the window's samples [k * b, min((k + 1) * b, n))
+ * (the last one may be short); b == 0 is one bucket of the whole window; a window of no samples has no buckets and nothing is
+ * written.  The samples are exactly those LINNEAmd_DecodeStreamDevice writes for the range -- int32, nothing saturated, the zeros of
+ * SILENT blocks and of the range behind the stream's last block included -- and every number is exact integer arithmetic: the sum
+ * of squares is kept as a 128-bit unsigned integer.  The windows' d_pcm and pcm_stride are ignored and may be NULL and 0.
+ * Every window's `result` is what LINNEAmd_DecodeWindowsDevice gives it (its argument checks but those of d_pcm and pcm_stride, the
+ * index's failing block at or before the range, the Rice consumption check), and for that window alone INVALID_ARGUMENT when d_out
+ * is NULL (with n > 0) or not 8-byte aligned, when channel_stride < nb, or when nb > 2^32 - 1.  A failing window's d_out is never
+ * written, and a failing window does not disturb the others.  No byte outside d_out[ch * channel_stride + k], ch < channels,
+ * k < nb, is written; the outputs of different windows must not overlap; the streams are only read.
+ * Shape groups, passes, group_frames, scratch and whole-call failures are the decode call's: LINNE_APIRESULT_OK when every window is
+ * OK, otherwise the result of the lowest-numbered failing window, with "window <i>: " and the single call's text in GetLastError; a
+ * HIP error or running out of memory fails the whole call (LINNE_APIRESULT_NG, in every `result` too).  A pass has the decode
+ * call's launches with kind 80 in place of kind 59; a call that takes at least one pass adds exactly two launches, whatever
+ * num_windows is: kind 81 in front of the first pass (the accumulators preset) and kind 82 behind the last (the tables of the windows
+ * whose Rice check passed written to their d_out); a window that spans passes collects its answer over them.  Copies (one upload,
+ * one fetch) and host synchronisations (one) do not depend on num_windows.  The accumulators live in the context's scratch: one
+ * record per (channel, bucket) of every window, times up to 64 for windows whose buckets are 8192 samples or longer (so that the
+ * workgroups of a long bucket do not queue on one address) -- at most 1/32 of the windows' int32 PCM for those.
+ * num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the
+ * context's stream and synchronous. */
+struct LINNEAmdMeasure {                /* 32 bytes: one channel of one bucket of one window */
+    int32_t min, max;                   /* over the bucket's samples */
+    int64_t sum;                        /* exact */
+    uint64_t sumsq_lo, sumsq_hi;        /* the exact sum of squares, a 128-bit unsigned integer */
+};
+struct LINNEAmdMeasureSpec {
+    uint64_t bucket_samples;            /* 0: the whole window is one bucket */
+    struct LINNEAmdMeasure *d_out;      /* device, 8-byte aligned: channel ch, bucket k at d_out[ch * channel_stride + k] */
+    uint64_t channel_stride;            /* in records, >= the window's bucket count */
+};
+int LINNEAmd_MeasureWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdMeasureSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

@@ -56,6 +56,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_SpliceStreamsDevice", "LINNEAmd_GetLastSpliceCount",
     "LINNEAmd_RepairStreamsDevice", "LINNEAmd_GetLastRepairGaps", "LINNEAmd_GetLastRepairCount",
     "LINNEAmd_CompareWindowsDevice",
+    "LINNEAmd_MeasureWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -116,6 +117,43 @@ class PcmLayout(C.Structure):
 class Diff(C.Structure):
     """struct LINNEAmdDiff (include/linne_amd.h)"""
     _fields_ = [("num_differing", C.c_uint64), ("first_sample", C.c_uint64), ("first_channel", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Measure(C.Structure):
+    """struct LINNEAmdMeasure (include/linne_amd.h): one channel of one bucket of one window"""
+    _fields_ = [("min", C.c_int32), ("max", C.c_int32), ("sum", C.c_int64), ("sumsq_lo", C.c_uint64), ("sumsq_hi", C.c_uint64)]
+
+
+class MeasureSpec(C.Structure):
+    """struct LINNEAmdMeasureSpec (include/linne_amd.h)"""
+    _fields_ = [("bucket_samples", C.c_uint64), ("d_out", C.c_void_p), ("channel_stride", C.c_uint64)]
+
+
+MEASURE_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("sumsq_lo", "<u8"), ("sumsq_hi", "<u8")])
+
+
+class Measurement:
+    """one window's table of measure_windows: `records`, an int64 CUDA tensor (C, nb, 4) holding a struct LINNEAmdMeasure per channel
+    and bucket, and strided views of it -- min, max (int32, (C, nb)), sum (int64), sumsq_lo / sumsq_hi (int64 views of the two
+    unsigned words of the 128-bit sum of squares)"""
+
+    def __init__(self, records, bucket_samples):
+        import torch
+        self.records, self.bucket_samples = records, bucket_samples
+        w = records.view(torch.int32)                                  # (C, nb, 8)
+        self.min, self.max = w[..., 0], w[..., 1]
+        self.sum, self.sumsq_lo, self.sumsq_hi = records[..., 1], records[..., 2], records[..., 3]
+
+    def energy(self):
+        """the sum of squares as float64 (C, nb): hi * 2^64 + lo, lo taken as unsigned"""
+        lo = self.sumsq_lo.double() + (self.sumsq_lo < 0).double() * 2.0 ** 64
+        hi = self.sumsq_hi.double() + (self.sumsq_hi < 0).double() * 2.0 ** 64
+        return hi * 2.0 ** 64 + lo
+
+    def cpu(self):
+        """-> a numpy structured array (C, nb) with the fields min, max, sum, sumsq_lo, sumsq_hi (the last two unsigned)"""
+        a = np.ascontiguousarray(self.records.cpu().numpy())
+        return a.view(MEASURE_DTYPE).reshape(a.shape[:2])
 
 
 def _load():
@@ -196,6 +234,7 @@ def _load():
     L.LINNEAmd_EncodeStreamsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Track), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_DecodeWindowsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_CompareWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.POINTER(Diff), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_MeasureWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MeasureSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -636,6 +675,64 @@ class Context:
                 raise LinneAmdError(f"CompareWindowsDevice -> {ret}: {msg}", ret, codes)
         out = [(int(diffs[i].num_differing), int(diffs[i].first_sample), int(diffs[i].first_channel)) if codes[i] == 0 else None for i in range(W)]
         return (out, codes) if return_codes else out
+
+    def measure_windows(self, windows, bucket_samples=0, group_frames=0, return_codes=False):
+        """min, max, sum and sum of squares of many sample windows of resident .lnn streams in one call, per channel and per bucket
+        of bucket_samples samples, no PCM written (include/linne_amd.h LINNEAmd_MeasureWindowsDevice).  windows: a sequence of
+        (stream, index, first_sample, num_samples) as decode_windows takes them; bucket_samples: one value or one per window (0: the
+        whole window is one bucket; the last bucket may be short).  -> a list of Measurement, one per window, views of one
+        allocation.  Every number is exact and is what numpy gives on decode_windows' int32 samples.  Errors follow
+        compare_windows: LinneAmdError with .code and .codes when a window fails; with return_codes -> (answers, codes), a failing
+        window's answer is None, and only a failure of the whole call raises"""
+        import torch
+        W = len(windows)
+        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
+        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
+        arr = (Window * max(W, 1))()
+        specs = (MeasureSpec * max(W, 1))()
+        keep, shapes = [], []
+        for i, (stream, index, first, n) in enumerate(windows):
+            t = self._stream_bytes(stream)
+            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            keep.append(t)
+            b = buckets[i]
+            nb = 0 if n <= 0 else (1 if b == 0 else -(-n // b))
+            shapes.append((index.header["num_channels"], nb))
+            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
+            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+            arr[i].d_pcm, arr[i].pcm_stride = None, 0
+        flat = torch.empty(max(sum(c * nb for c, nb in shapes), 1) * 4, dtype=torch.int64, device=f"cuda:{self.device}")
+        recs, at = [], 0
+        for i, (c, nb) in enumerate(shapes):
+            recs.append(flat[at:at + c * nb * 4].view(c, nb, 4))
+            specs[i].bucket_samples, specs[i].channel_stride = buckets[i], nb
+            specs[i].d_out = flat.data_ptr() + 8 * at                  # (an empty view has no address of its own)
+            at += c * nb * 4
+        self._fence()
+        ret = lib.LINNEAmd_MeasureWindowsDevice(self.h, arr, specs, W, int(group_frames))
+        codes = [int(arr[i].result) for i in range(W)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
+                raise LinneAmdError(f"MeasureWindowsDevice -> {ret}: {msg}", ret, codes)
+        out = [Measurement(recs[i], buckets[i]) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def measure_streams(self, streams, bucket_samples=0, group_frames=0):
+        """min, max, sum and sum of squares of whole resident .lnn streams, per channel and bucket: one index_streams call and one
+        measure_windows call over the whole streams -> a list of Measurement.  streams as index_streams takes them; bucket_samples as
+        measure_windows takes it.  Raises LinneAmdError when a stream does not index or decode"""
+        if len(streams) == 0:
+            return []
+        ts = [self._stream_bytes(s) for s in streams]
+        indexes = self.index_streams(ts)
+        try:
+            return self.measure_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], bucket_samples=bucket_samples, group_frames=group_frames)
+        finally:
+            for x in indexes:
+                x.close()
 
     def verify_streams(self, pairs, group_frames=0):
         """do these .lnn streams hold exactly these samples?  pairs: a sequence of (stream, pcm), a whole stream (as index_streams

@@ -12,7 +12,10 @@
  *     stretches replaced by SILENT blocks), prints the report to stderr and exits 0 when the output was written;
  *   - -V / --verify (with -e) compares the encoded stream with the WAV's samples on the device (LINNEAmd_CompareWindowsDevice) before
  *     the output file is written, and writes nothing when they differ; -C / --compare STREAM.lnn PCM.wav does the same for a stream
- *     and a WAV file that exist: exit 0 and "identical", or exit 1 and the first differing sample.
+ *     and a WAV file that exist: exit 0 and "identical", or exit 1 and the first differing sample;
+ *   - -M / --measure [BUCKET] STREAM.lnn measures a stream on the device without decoding it into memory
+ *     (LINNEAmd_MeasureWindowsDevice): per channel the minimum, maximum, exact sum and sum of squares, mean and RMS of the whole
+ *     stream on stdout, or with BUCKET one such line per BUCKET samples and channel.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -21,13 +24,14 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
     const char *batch_dir;
     const char *files[4096];
@@ -41,12 +45,14 @@ static void usage(const char *argv0)
     printf("Usage: %s [options] INPUT_FILE_NAME OUTPUT_FILE_NAME \n", argv0);
     printf("       %s [options] --batch OUTPUT_DIRECTORY INPUT_FILE_NAME... \n", argv0);
     printf("       %s -C STREAM.lnn PCM.wav \n", argv0);
+    printf("       %s -M [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
            "  -r, --repair                           Repair a damaged .lnn stream into a valid one (report on stderr) \n"
            "  -V, --verify                           With -e: compare the stream with the input's samples on the device before writing it \n"
            "  -C, --compare                          Compare a .lnn stream with a WAV file's samples on the device (exit 0: identical) \n"
+           "  -M, --measure                          Measure a .lnn stream on the device: min, max, sum, energy, mean, RMS per channel (and bucket) \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -84,6 +90,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (strcmp(a, "-r") == 0 || strcmp(a, "--repair") == 0) o->repair = 1;
         else if (strcmp(a, "-V") == 0 || strcmp(a, "--verify") == 0) o->verify = 1;
         else if (strcmp(a, "-C") == 0 || strcmp(a, "--compare") == 0) o->compare = 1;
+        else if (strcmp(a, "-M") == 0 || strcmp(a, "--measure") == 0) o->measure = 1;
         else if (strcmp(a, "-c") == 0 || strcmp(a, "--no-crc-check") == 0) o->no_crc = 1;
         else if (strcmp(a, "-l") == 0 || strcmp(a, "--enable-learning") == 0) o->learning = 1;
         else if (strcmp(a, "-B") == 0 || strcmp(a, "--block-at-a-time") == 0) o->block_at_a_time = 1;
@@ -197,6 +204,53 @@ static int compare_one(const char *lnn_path, const char *wav_path)
     rc = report_compare(buf, size, &wav);
     if (rc == 0) printf("identical \n");
     free(buf); wav_free(&wav);
+    return rc;
+}
+
+/* -M: the stream goes to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_MeasureWindowsDevice window over the whole stream
+ * answer, and the table comes back: a line per channel, or with a bucket per bucket and channel */
+static int measure_one(const char *lnn_path, uint64_t bucket)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0, ch;
+    struct LINNEAmdContext *ctx = NULL;
+    struct LINNEAmdStreamIndex *index = NULL;
+    struct LINNEAmdWindow w;
+    struct LINNEAmdMeasureSpec spec;
+    struct LINNEAmdMeasure *tab = NULL;
+    struct LINNEHeader h;
+    void *d_stream = NULL, *d_out = NULL;
+    uint64_t n, nb, k;
+    int ret = LINNE_APIRESULT_OK, rc = 1;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    n = h.num_samples;
+    nb = n == 0 ? 0 : (bucket == 0 || bucket >= n) ? 1 : (n + bucket - 1) / bucket;
+    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { fprintf(stderr, "Failed to create a device context. \n"); goto done; }
+    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, buf, size, hipMemcpyHostToDevice) != hipSuccess
+            || hipMalloc(&d_out, nb ? sizeof(*tab) * nb * h.num_channels : 1) != hipSuccess) { fprintf(stderr, "Failed to copy the stream to the device. \n"); goto done; }
+    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { fprintf(stderr, "Failed to measure! the stream does not index: %d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    memset(&w, 0, sizeof(w)); memset(&spec, 0, sizeof(spec));
+    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n;
+    spec.bucket_samples = bucket; spec.d_out = d_out; spec.channel_stride = nb;
+    if ((ret = LINNEAmd_MeasureWindowsDevice(ctx, &w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to measure! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * nb * h.num_channels : 1)) || (nb && hipMemcpy(tab, d_out, sizeof(*tab) * nb * h.num_channels, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    for (k = 0; k < nb; k++)
+        for (ch = 0; ch < h.num_channels; ch++) {
+            const struct LINNEAmdMeasure *m = tab + ch * nb + k;
+            const uint64_t first = bucket ? k * bucket : 0, cnt = (bucket && first + bucket < n) ? bucket : n - first;
+            const double energy = ldexp((double)m->sumsq_hi, 64) + (double)m->sumsq_lo;
+            if (bucket) printf("bucket %llu ", (unsigned long long)k);
+            printf("channel %u: samples %llu min %d max %d sum %lld sumsq_hi %llu sumsq_lo %llu mean %.6f rms %.6f \n", ch, (unsigned long long)cnt, m->min, m->max,
+                    (long long)m->sum, (unsigned long long)m->sumsq_hi, (unsigned long long)m->sumsq_lo, (double)m->sum / (double)cnt, sqrt(energy / (double)cnt));
+        }
+    rc = 0;
+done:
+    if (index) LINNEAmd_StreamIndexDestroy(index);
+    if (d_out) (void)hipFree(d_out);
+    if (d_stream) (void)hipFree(d_stream);
+    if (ctx) LINNEAmd_ContextDestroy(ctx);
+    free(tab); free(buf);
     return rc;
 }
 
@@ -336,12 +390,21 @@ int main(int argc, char **argv)
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
     if (o.repair) {
-        if (o.encode || o.decode || o.compare || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.compare || o.measure || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return repair_one(o.files[0], o.files[1]);
     }
     if (o.compare) {
-        if (o.encode || o.decode || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -C takes a stream and a WAV file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.measure || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -C takes a stream and a WAV file name and no other mode. \n", argv[0]); return 1; }
         return compare_one(o.files[0], o.files[1]);
+    }
+    if (o.measure) {
+        unsigned long long bucket = 0;
+        if (o.encode || o.decode || o.verify || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -M takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
+        if (o.num_files == 2) {
+            char *end; bucket = strtoull(o.files[0], &end, 10);
+            if (*end != '\0' || o.files[0][0] < '0' || o.files[0][0] > '9' || bucket == 0) { fprintf(stderr, "%s: bucket sample count is out of range. \n", argv[0]); return 1; }
+        }
+        return measure_one(o.files[o.num_files - 1], bucket);
     }
     if (o.verify && !o.encode) { fprintf(stderr, "%s: -V goes with encode mode (-e) only. \n", argv[0]); return 1; }
     if (o.encode && o.decode) { fprintf(stderr, "%s: encode and decode mode cannot specify simultaneously. \n", argv[0]); return 1; }
