@@ -325,32 +325,27 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_SX_CHECK = 44,          /* CRC16 and block checks (k_sx_check) */
     /* 45-47 were the kinds of LINNEAmd_DecodeStreamDevice's own kernels, which are gone (it reports 56-59 now); the numbers are not
      * reused, so that recorded profiles stay readable */
-    /* the stream encoder (LINNEAmd_EncodeStreamDevice, a call of its own; its analysis and Rice plan report as the kinds above); a
-     * launch of each per pass */
-    LINNE_AMD_T_SE_GATHER = 48,         /* gathering the planar input into frames (k_se_gather) */
+    /* the stream encoders (LINNEAmd_EncodeStreamsDevice, and LINNEAmd_EncodeStreamDevice as its one-track case; the analysis and
+     * the Rice plan report as the kinds above); a launch of each per pass.  48, 50 and 52-55 were the kinds of the single call's own
+     * launches, which are gone (it reports 60-68 now); the numbers are not reused, so that recorded profiles stay readable */
     LINNE_AMD_T_SE_COMPACT = 49,        /* compacting the Rice plans for the host step (k_se_compact) */
-    LINNE_AMD_T_SE_SIZE = 50,           /* block sizes (k_se_size) */
-    LINNE_AMD_T_SE_SCAN = 51,           /* their offsets (k_sx_scan) */
-    LINNE_AMD_T_SE_PARAMS = 52,         /* parameter bits (k_se_params) */
-    LINNE_AMD_T_SE_RICE = 53,           /* Rice codes (k_se_rice) */
-    LINNE_AMD_T_SE_RAW = 54,            /* RAW payloads (k_se_raw) */
-    LINNE_AMD_T_SE_CRC = 55,            /* CRC16 and block headers (k_se_crc) */
+    LINNE_AMD_T_SE_SCAN = 51,           /* the blocks' offsets (k_sx_scan) */
     /* sample windows of indexed streams (LINNEAmd_DecodeWindowsDevice, and LINNEAmd_DecodeStreamDevice as its one-window case; a
      * launch of each per pass, with 28 and the synthesis' kinds 11-12, 30-36 between them) */
     LINNE_AMD_T_WX_GATHER = 56,         /* gathering the COMPRESS blocks' bytes into the packed segment (k_wx_gather) */
     LINNE_AMD_T_WX_PARAMS = 57,         /* parameter records (k_wx_params) */
     LINNE_AMD_T_WX_RICE_CHECK = 58,     /* the consumption check per window (k_wx_rice_check) */
     LINNE_AMD_T_WX_PLACE = 59,          /* placing every window's samples (k_wx_place) */
-    /* many tracks into streams (LINNEAmd_EncodeStreamsDevice, a call of its own; per pass a launch of each of 60-67, with 49, 51,
-     * the analysis' kinds and 17 between them; 68 once per shape) */
+    /* ... and the rest of them (both calls; per pass a launch of each of 60-67, with 49, 51, the analysis' kinds and 17 between
+     * them; 68 once per shape) */
     LINNE_AMD_T_SB_GATHER = 60,         /* gathering the rows of a pass from their tracks (k_sb_gather) */
-    LINNE_AMD_T_SB_SIZE = 61,           /* block sizes into stream-order slots (k_se_size<true>) */
+    LINNE_AMD_T_SB_SIZE = 61,           /* block sizes into stream-order slots (k_se_size) */
     LINNE_AMD_T_SB_REDUCE = 62,         /* per track: bytes, lowest failing block (k_sb_reduce) */
     LINNE_AMD_T_SB_ZERO = 63,           /* zeroing the written tracks' regions (k_sb_zero) */
-    LINNE_AMD_T_SB_PARAMS = 64,         /* parameter bits (k_se_params<true>) */
-    LINNE_AMD_T_SB_RICE = 65,           /* Rice codes (k_se_rice<., true>) */
-    LINNE_AMD_T_SB_RAW = 66,            /* RAW payloads (k_se_raw<true>) */
-    LINNE_AMD_T_SB_CRC = 67,            /* CRC16 and block headers (k_se_crc<true>) */
+    LINNE_AMD_T_SB_PARAMS = 64,         /* parameter bits (k_se_params) */
+    LINNE_AMD_T_SB_RICE = 65,           /* Rice codes (k_se_rice) */
+    LINNE_AMD_T_SB_RAW = 66,            /* RAW payloads (k_se_raw) */
+    LINNE_AMD_T_SB_CRC = 67,            /* CRC16 and block headers (k_se_crc) */
     LINNE_AMD_T_SB_HEADER = 68,         /* the finished tracks' stream headers (k_sb_header) */
     /* the indexes of many streams (LINNEAmd_StreamIndexesCreate, a call of its own): its segmented kernels report under 37-44, the
      * two without a single-call counterpart follow here, numbered on from the kind above (lnn_device.hip asserts 69 and 70: a kind
@@ -516,6 +511,7 @@ int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWin
         uint32_t num_windows, uint32_t group_frames);
 
 /* ---- planar PCM held in device memory -> a .lnn stream in device memory ----
+ * (the one-track case of the call below: the same code, so a track there and a call here cannot come apart)
  * LINNEAmd_EncodeStreamDevice encodes header->num_samples samples of every channel ch, read from d_pcm + ch * pcm_stride (int32,
  * right-justified; any element offset), into d_out[0, *out_bytes).  header's num_channels, num_samples, sampling_rate,
  * bits_per_sample, num_samples_per_block, preset and ch_process_method are used (the version fields are not); -a / -l come from
@@ -540,7 +536,7 @@ uint64_t LINNEAmd_EncodeStreamBound(const struct LINNEHeader *header);      /* 3
 int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
         const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
         uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state);
-/* how the last EncodeStreamDevice call of this context went: which 0 / 1 / 2 = its COMPRESS / SILENT / RAW blocks, 3 = the
+/* how the last EncodeStream(s)Device call of this context went (many tracks: the sums over the call): which 0 / 1 / 2 = its COMPRESS / SILENT / RAW blocks, 3 = the
  * channel-frames whose Rice plan the host settled (a mean in a guard band); -1 for a NULL context or another `which` */
 int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx, int which);
 
@@ -561,8 +557,8 @@ int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx, int which
  * group_frames frames (0 = one pass per shape; a track may span passes); group_frames never changes a byte.  The kernel launches,
  * memsets, copies and host synchronisations of a pass do not depend on how many tracks it holds, with one exception: the analysis
  * (LINNEAmd_EncodeFramesDevice) takes at most 16 distinct frame lengths per call, so a pass whose frames have d distinct lengths
- * takes 1 call when d <= 16 and 1 + ceil((d - 16) / 16) otherwise.  Scratch (kept by the context) is the single call's per frame of a
- * pass plus 16 bytes per frame and about 100 per track.  The tracks' output buffers must be 4-byte aligned and must not overlap.
+ * takes 1 call when d <= 16 and 1 + ceil((d - 16) / 16) otherwise.  Scratch (kept by the context) is about 8 * C * S bytes per frame
+ * of a pass, plus 16 bytes per frame and about 100 per track, for the single call too.  The tracks' output buffers must be 4-byte aligned and must not overlap.
  * Enqueued on the context's stream and synchronous. */
 struct LINNEAmdTrack {
     struct LINNEHeader header;                 /* as EncodeStreamDevice's header argument */
@@ -574,8 +570,9 @@ struct LINNEAmdTrack {
 };
 int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks,
         uint32_t num_tracks, uint32_t group_frames);
-/* how the last EncodeStreamsDevice call of this context went: which 0 = its shape groups, 1 = its passes, 2 = its EncodeFramesDevice
- * calls; -1 for a NULL context or another `which` */
+/* how the last EncodeStream(s)Device call of this context went: which 0 = its shape groups, 1 = its passes, 2 = its EncodeFramesDevice
+ * calls (after a single call: 1 group, its passes, one analysis call per pass; 0, 0, 0 when the track failed its argument or header
+ * checks); -1 for a NULL context or another `which` */
 int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx, int which);
 
 /* ---- resident streams from and into int16, packed 24-bit and float PCM, planar or interleaved ----

@@ -806,7 +806,8 @@ class Context:
         """PCM (an int32 or int16 CUDA tensor (C, N) with any strides -- x.T of a channels-last (N, C) one included --, a uint8 one
         (C, N, 3) of packed little-endian 24-bit samples, or numpy: copied to the device as int32) -> a .lnn stream encoded on the device,
         as a 1-D uint8 CUDA tensor (a view of `out` when one is given); with parcor_state (a float, the quirk-Q2 state) not None, the
-        pair (stream, new state).  include/linne_amd.h LINNEAmd_EncodeStreamDevice states the result contract.  The default buffer is
+        pair (stream, new state).  include/linne_amd.h LINNEAmd_EncodeStreamDevice states the result contract (the library runs it as
+        the one-track case of encode_streams' call).  The default buffer is
         what the reference's command line tool allocates (twice the PCM's bytes at `bits` width, plus the header); a stream that does not
         fit is encoded again into a buffer of its exact size.  Raises LinneAmdError with .code = the LINNEApiResult.  After
         set_verify(True) the stream is compared with the PCM before it is returned (verify_streams): LinneAmdError with .code = 7
@@ -847,7 +848,7 @@ class Context:
         return stream if parcor_state is None else (stream, state.value)
 
     def last_stream_encode_count(self, which):
-        """the last encode_stream call: 0 / 1 / 2 its COMPRESS / SILENT / RAW blocks, 3 the channel-frames whose Rice plan the host settled"""
+        """the last encode_stream or encode_streams call: 0 / 1 / 2 its COMPRESS / SILENT / RAW blocks, 3 the channel-frames whose Rice plan the host settled"""
         return int(lib.LINNEAmd_GetLastStreamEncodeCount(self.h, int(which)))
 
     def encode_streams(self, tracks, group_frames=0, parcor_states=None, return_codes=False):
@@ -932,7 +933,7 @@ class Context:
 
     def last_stream_batch_count(self, which):
         """the last encode_streams call (its second one, where tracks were encoded again): 0 its shape groups, 1 its passes, 2 its
-        EncodeFramesDevice calls"""
+        EncodeFramesDevice calls; after an encode_stream call: 1 group, its passes, one analysis call per pass"""
         return int(lib.LINNEAmd_GetLastStreamBatchCount(self.h, int(which)))
 
     def splice_streams(self, splices, group_frames=0, return_codes=False):

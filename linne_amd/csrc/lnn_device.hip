@@ -418,6 +418,15 @@ static int ensure_buf(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t 
     return LNN_OK;
 }
 
+/* the stream parameters a header names */
+static struct LINNEAmdShape header_shape(const struct LINNEHeader *h)
+{
+    struct LINNEAmdShape s;
+    s.num_channels = h->num_channels; s.bits_per_sample = h->bits_per_sample; s.num_samples_per_block = h->num_samples_per_block;
+    s.preset = h->preset; s.ch_process_method = (uint32_t)h->ch_process_method;
+    return s;
+}
+
 static int shape_info(const struct LINNEAmdShape *s, HostShape *h)
 {
     if (!s || s->preset >= 8 || s->num_channels == 0 || s->num_channels > LNN_MAXCH || s->bits_per_sample == 0 || s->bits_per_sample > 32
@@ -1970,8 +1979,7 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
     LINNEAmdStreamIndex *x = (LINNEAmdStreamIndex *)calloc(1, sizeof(LINNEAmdStreamIndex));
     if (!x) { *result = LNN_NG; return NULL; }
     x->device = ctx->device; x->header = h; x->stream_bytes = stream_bytes;
-    x->shape.num_channels = h.num_channels; x->shape.bits_per_sample = h.bits_per_sample; x->shape.num_samples_per_block = h.num_samples_per_block;
-    x->shape.preset = h.preset; x->shape.ch_process_method = (uint32_t)h.ch_process_method;
+    x->shape = header_shape(&h);
     HostShape hs;
     if (shape_info(&x->shape, &hs) != LNN_OK) {
         snprintf(ctx->err, sizeof(ctx->err), "stream header: a shape the device decoder does not take (%u bits, %u samples per block)", h.bits_per_sample, h.num_samples_per_block);
@@ -2054,8 +2062,7 @@ static int ib_open(int device, const uint8_t *hb, uint64_t stream_bytes, LINNEAm
     LINNEAmdStreamIndex *x = (LINNEAmdStreamIndex *)calloc(1, sizeof(LINNEAmdStreamIndex));
     if (!x) { snprintf(text, cap, "out of host memory"); *whole_call = true; return LNN_NG; }
     x->device = device; x->header = h; x->stream_bytes = stream_bytes;
-    x->shape.num_channels = h.num_channels; x->shape.bits_per_sample = h.bits_per_sample; x->shape.num_samples_per_block = h.num_samples_per_block;
-    x->shape.preset = h.preset; x->shape.ch_process_method = (uint32_t)h.ch_process_method;
+    x->shape = header_shape(&h);
     HostShape hs;
     if (shape_info(&x->shape, &hs) != LNN_OK) {
         snprintf(text, cap, "stream header: a shape the device decoder does not take (%u bits, %u samples per block)", h.bits_per_sample, h.num_samples_per_block);
@@ -2621,7 +2628,8 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
 
 
 /* ================================================================================================
- * planar PCM in device memory -> a .lnn stream in device memory (lnn_k_stream_enc.h)
+ * PCM in device memory -> .lnn streams in device memory: many tracks in one call, and one track as the one-track case of it
+ * (lnn_k_stream_enc.h, lnn_stream_batch.h)
  * ============================================================================================== */
 extern "C" uint64_t LINNEAmd_EncodeStreamBound(const struct LINNEHeader *header)
 {
@@ -2639,237 +2647,17 @@ extern "C" int64_t LINNEAmd_GetLastStreamEncodeCount(struct LINNEAmdContext *ctx
 /* LINNEEncoder_SetEncodeParameter's checks (lnn_api.c), in its order, on an encoder with room for the header */
 static int se_parameter_code(const struct LINNEHeader *h)
 {
-    struct LINNEAmdShape shape;
     struct lnn_layers ly;
     if (h->num_channels == 0 || h->bits_per_sample == 0 || h->sampling_rate == 0 || h->num_samples_per_block == 0
             || h->preset >= LINNE_NUM_PARAMETER_PRESETS || (int)h->ch_process_method >= (int)LINNE_CH_PROCESS_METHOD_INVALID
             || (int)h->ch_process_method < 0) return LNN_INVALID_FORMAT;
-    shape.num_channels = h->num_channels; shape.bits_per_sample = h->bits_per_sample; shape.num_samples_per_block = h->num_samples_per_block;
-    shape.preset = h->preset; shape.ch_process_method = (uint32_t)h->ch_process_method;
+    const struct LINNEAmdShape shape = header_shape(h);
     if (lnn_shape_layers(&shape, &ly) != 0) return LNN_INVALID_FORMAT;
     for (uint32_t l = 0; l < ly.num_layers; l++) if (h->num_samples_per_block <= ly.size[l]) return LNN_INVALID_FORMAT;
     if (h->num_channels > LINNE_MAX_NUM_CHANNELS) return LNN_INSUFFICIENT_BUFFER;
     return LNN_OK;
 }
 
-/* host buffers of one call */
-struct SeHost {
-    uint2 *cmp = NULL; double *st = NULL; uint32_t *nz32 = NULL, *nsmp = NULL, *settle = NULL, *settle_n = NULL; uint8_t *nz8 = NULL, *types = NULL;
-    int32_t *res = NULL; uint8_t *plans = NULL; uint64_t res_cap = 0;
-    ~SeHost() { free(cmp); free(st); free(nz32); free(nsmp); free(settle); free(settle_n); free(nz8); free(types); free(res); free(plans); }
-};
-
-static int se_run(LINNEAmdContext *ctx, const struct LINNEHeader *header, const struct LINNEAmdShape &shape, const HostShape &hs,
-        const void *d_pcm, const struct LINNEAmdPcmLayout &ly, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes,
-        double *parcor_state)
-{
-    const uint32_t C = shape.num_channels, S = shape.num_samples_per_block;
-    const uint64_t N = header->num_samples, F = (N + S - 1u) / S, CS = (uint64_t)C * S;
-    uint64_t G = group_frames ? (group_frames < F ? group_frames : F) : F;
-    if (G * C > 0x7FFFFFFFull) G = 0x7FFFFFFFull / C;              /* grid.x of the channel-frame kernels */
-    /* scratch of one pass */
-    uint64_t at = 0;
-    const uint64_t o_frames = at; at = align_up(at + sizeof(int32_t) * CS * G);
-    const uint64_t o_resid = at; at = align_up(at + sizeof(int32_t) * CS * G);
-    const uint64_t o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * G);
-    const uint64_t o_st = at; at = align_up(at + sizeof(double) * LINNE_AMD_STAT_WORDS * C * G);
-    const uint64_t o_plan = at; at = align_up(at + (uint64_t)LINNE_AMD_RICE_PLAN_BYTES * C * G);
-    const uint64_t o_nz = at; at = align_up(at + sizeof(uint32_t) * G);
-    const uint64_t o_cmp = at; at = align_up(at + sizeof(uint2) * C * G);
-    const uint64_t o_types = at; at = align_up(at + G);
-    const uint64_t o_size = at; at = align_up(at + sizeof(uint32_t) * G);
-    const uint64_t o_status = at; at = align_up(at + sizeof(int32_t) * G);
-    const uint64_t o_off = at; at = align_up(at + sizeof(uint64_t) * (G + 1u));
-    const uint64_t o_cfbit = at; at = align_up(at + sizeof(uint64_t) * C * G);
-    const uint64_t o_fail = at; at = align_up(at + 2u * sizeof(uint32_t));
-    const uint64_t o_tab = at; at = align_up(at + sizeof(SeTables));
-    SX_TRY(ensure_buf(ctx, &ctx->senc, &ctx->senc_cap, at));
-    uint8_t *sd = (uint8_t *)ctx->senc;
-    int32_t *d_frames = (int32_t *)(sd + o_frames), *d_resid = (int32_t *)(sd + o_resid), *d_prm = (int32_t *)(sd + o_prm), *d_status = (int32_t *)(sd + o_status);
-    double *d_st = (double *)(sd + o_st);
-    uint8_t *d_plan = sd + o_plan, *d_types = sd + o_types;
-    uint32_t *d_nz = (uint32_t *)(sd + o_nz), *d_size = (uint32_t *)(sd + o_size), *d_fail = (uint32_t *)(sd + o_fail);
-    uint2 *d_cmp = (uint2 *)(sd + o_cmp);
-    uint64_t *d_off = (uint64_t *)(sd + o_off), *d_cfbit = (uint64_t *)(sd + o_cfbit);
-    SeTables *d_tab = (SeTables *)(sd + o_tab);
-    SeHost h;
-    h.cmp = (uint2 *)malloc(sizeof(uint2) * C * G); h.st = (double *)malloc(sizeof(double) * LINNE_AMD_STAT_WORDS * C * G);
-    h.nz32 = (uint32_t *)malloc(sizeof(uint32_t) * G); h.nsmp = (uint32_t *)malloc(sizeof(uint32_t) * G);
-    h.settle = (uint32_t *)malloc(sizeof(uint32_t) * C * G); h.settle_n = (uint32_t *)malloc(sizeof(uint32_t) * C * G);
-    h.nz8 = (uint8_t *)malloc(G); h.types = (uint8_t *)malloc(G);
-    if (!h.cmp || !h.st || !h.nz32 || !h.nsmp || !h.settle || !h.settle_n || !h.nz8 || !h.types) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-    {
-        SeTables t;
-        sx_tables(&t.sx);
-        lnn_huff_code_table(t.code, t.len);
-        HIPCHK(ctx, hipMemcpyAsync(d_tab, &t, sizeof(t), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_fail + 1, 0, sizeof(uint32_t), ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (t lives on this frame) */
-    }
-    double state = parcor_state ? *parcor_state : 0.0;
-    const uint64_t room = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;     /* EncodeWhole's buffer size is a uint32 */
-    bool writing = capacity >= LINNE_HEADER_SIZE;
-    uint64_t pos = LINNE_HEADER_SIZE;
-    for (uint64_t f0 = 0; f0 < F; f0 += G) {
-        const uint32_t Fp = (uint32_t)((F - f0 < G) ? F - f0 : G);
-        for (uint32_t f = 0; f < Fp; f++) { const uint64_t s0 = (f0 + f) * S; h.nsmp[f] = (N - s0 < S) ? (uint32_t)(N - s0) : S; }
-        /* 1. gather */
-        HIPCHK(ctx, hipMemsetAsync(d_nz, 0, sizeof(uint32_t) * Fp, ctx->stream));
-        {
-            SeGatherArgs g; g.pcm = d_pcm; g.stride = ly.channel_stride; g.sstride = ly.sample_stride; g.fmt = ly.format; g.first = f0 * S; g.total = N; g.frames = d_frames; g.nonzero = d_nz;
-            g.F = Fp; g.C = C; g.S = S;
-            SX_LAUNCH(LINNE_AMD_T_SE_GATHER, k_se_gather, dim3(Fp * C), dim3(SE_THREADS), 0, ctx->stream, g);
-        }
-        /* 2. analysis and Rice plan, unchanged */
-        SX_TRY(LINNEAmd_EncodeFramesDevice(ctx, &shape, d_frames, h.nsmp, Fp, d_resid, d_prm, d_st));
-        SX_TRY(LINNEAmd_RicePlanDevice(ctx, &shape, d_resid, h.nsmp, Fp, d_plan));
-        const uint32_t *d_nsmp = ctx->d_plan_nsmp;                 /* (RicePlanDevice's copy of this pass's lengths) */
-        const uint32_t CF = Fp * C;
-        SX_LAUNCH(LINNE_AMD_T_SE_COMPACT, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
-        /* 3. the host step: block types in stream order (quirk Q2, host libm), the plans the device could not settle */
-        HIPCHK(ctx, hipMemcpyAsync(h.cmp, d_cmp, sizeof(uint2) * CF, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(h.st, d_st, sizeof(double) * LINNE_AMD_STAT_WORDS * CF, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(h.nz32, d_nz, sizeof(uint32_t) * Fp, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        for (uint32_t f = 0; f < Fp; f++) h.nz8[f] = h.nz32[f] ? 1u : 0u;
-        if (lnn_decide_block_types(&shape, h.nsmp, Fp, h.st, h.nz8, h.types, &state) != 0) { snprintf(ctx->err, sizeof(ctx->err), "block types: invalid shape"); return LNN_INVALID_FORMAT; }
-        uint32_t nsettle = 0;
-        for (uint32_t f = 0; f < Fp; f++) {
-            ctx->senc_count[h.types[f] == LNN_BLOCK_COMPRESS ? 0 : (h.types[f] == LNN_BLOCK_SILENT ? 1 : 2)]++;
-            if (h.types[f] != LNN_BLOCK_COMPRESS) continue;
-            for (uint32_t ch = 0; ch < C; ch++) {
-                const uint2 r = h.cmp[f * C + ch];
-                const uint32_t order = r.x & 0xFFu, flag = (r.x >> 8) & 0xFFu;
-                if (flag || order > 10u || (h.nsmp[f] % (1u << order)) != 0u) { h.settle[nsettle] = f * C + ch; h.settle_n[nsettle] = h.nsmp[f]; nsettle++; }
-            }
-        }
-        ctx->senc_count[3] += nsettle;
-        if (nsettle) {
-            if (h.res_cap < (uint64_t)nsettle * S) {
-                free(h.res); free(h.plans); h.res_cap = 0;
-                h.res = (int32_t *)malloc(sizeof(int32_t) * (uint64_t)nsettle * S); h.plans = (uint8_t *)malloc((uint64_t)LINNE_AMD_RICE_PLAN_BYTES * nsettle);
-                if (!h.res || !h.plans) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-                h.res_cap = (uint64_t)nsettle * S;
-            }
-            for (uint32_t k = 0; k < nsettle; k++)
-                HIPCHK(ctx, hipMemcpyAsync(h.res + (uint64_t)k * S, d_resid + (uint64_t)h.settle[k] * S, sizeof(int32_t) * h.settle_n[k], hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            if (lnn_rice_plan_host(h.res, S, h.settle_n, nsettle, h.plans) != 0) { snprintf(ctx->err, sizeof(ctx->err), "host Rice search failed"); return LNN_NG; }
-            for (uint32_t k = 0; k < nsettle; k++) {
-                const uint8_t *rec = h.plans + (uint64_t)k * LINNE_AMD_RICE_PLAN_BYTES;
-                HIPCHK(ctx, hipMemcpyAsync(d_plan + (uint64_t)h.settle[k] * LINNE_AMD_RICE_PLAN_BYTES, rec, LINNE_AMD_RICE_PLAN_K2 + (1u << rec[0]), hipMemcpyHostToDevice, ctx->stream));
-            }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(d_types, h.types, Fp, hipMemcpyHostToDevice, ctx->stream));
-        /* 4. sizes and offsets */
-        SeBlockArgs a; memset(&a, 0, sizeof(a));
-        a.types = d_types; a.nsmp = d_nsmp; a.prm = d_prm; a.plan = d_plan; a.resid = d_resid; a.tab = d_tab;
-        a.F = Fp; a.C = C; a.S = S; a.bits = shape.bits_per_sample; a.L = hs.L;
-        for (uint32_t l = 0; l < hs.L; l++) { a.P[l] = hs.P[l]; a.coef_off[l] = hs.coef_off[l]; }
-        a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.out = d_out; a.base = pos;
-        a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
-        HIPCHK(ctx, hipMemsetAsync(d_fail, 0xFF, sizeof(uint32_t), ctx->stream));
-        SX_LAUNCH(LINNE_AMD_T_SE_SIZE, k_se_size<false>, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
-        SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
-        uint64_t pass_bytes = 0;
-        uint32_t fail = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&fail, d_fail, sizeof(fail), hipMemcpyDeviceToHost, ctx->stream));
-        SX_TRY(sx_fetch(ctx, &pass_bytes, d_off + Fp, sizeof(pass_bytes)));
-        if (fail != 0xFFFFFFFFu) {
-            /* a block the host stitcher refuses: its code, as EncodeWhole returns it (after the header's: a buffer under 30 bytes) */
-            int32_t st = LNN_NG;
-            SX_TRY(sx_fetch(ctx, &st, d_status + fail, sizeof(st)));
-            snprintf(ctx->err, sizeof(ctx->err), "block %llu: %s", (unsigned long long)(f0 + fail),
-                    st == LNN_INVALID_FORMAT ? "a RAW block at a width other than 8, 16 or 24 bits" : "longer than the host stitcher's 64 + C * S * 8 bytes");
-            *out_bytes = 0;
-            return capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : st;
-        }
-        /* 5. 6. the writers and the CRC, into the zeroed region of this pass -- unless the stream does not fit */
-        if (writing && pos + pass_bytes > room) writing = false;
-        if (writing) {
-            HIPCHK(ctx, hipMemsetAsync(d_out + pos, 0, pass_bytes, ctx->stream));
-            SX_LAUNCH(LINNE_AMD_T_SE_PARAMS, k_se_params<false>, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
-            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SE_RICE, (k_se_rice<true, false>), dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
-            else SX_LAUNCH(LINNE_AMD_T_SE_RICE, (k_se_rice<false, false>), dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
-            SX_LAUNCH(LINNE_AMD_T_SE_RAW, k_se_raw<false>, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
-            SX_LAUNCH(LINNE_AMD_T_SE_CRC, k_se_crc<false>, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
-        }
-        pos += pass_bytes;
-    }
-    *out_bytes = pos;
-    if (!writing || pos > room) {
-        snprintf(ctx->err, sizeof(ctx->err), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)pos, (unsigned long long)capacity);
-        return LNN_INSUFFICIENT_BUFFER;
-    }
-    uint32_t bad_length = 0;
-    SX_TRY(sx_fetch(ctx, &bad_length, d_fail + 1, sizeof(bad_length)));
-    if (bad_length) { snprintf(ctx->err, sizeof(ctx->err), "a Rice code's length is not its plan's (a wrapped 32-bit length count)"); return LNN_NG; }
-    /* 7. the stream header (LINNEEncoder_EncodeHeader, host) */
-    uint8_t hb[LINNE_HEADER_SIZE];
-    SX_TRY((int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE));
-    HIPCHK(ctx, hipMemcpyAsync(d_out, hb, LINNE_HEADER_SIZE, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (parcor_state) *parcor_state = state;
-    return LNN_OK;
-}
-
-/* both single entry points: layout NULL is int32 planar with pcm_stride */
-static int se_entry(struct LINNEAmdContext *ctx, const struct LINNEHeader *header, const void *d_pcm, uint64_t pcm_stride,
-        const struct LINNEAmdPcmLayout *layout, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
-{
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    for (int i = 0; i < 4; i++) ctx->senc_count[i] = 0;
-    if (!header || !d_pcm || !d_out || !out_bytes) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    if ((uintptr_t)d_out & 3u) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: d_out is not 4-byte aligned"); return LNN_INVALID_ARGUMENT; }
-    if (layout) {
-        const int why = sb_layout_check(layout->format, layout->channel_stride, layout->sample_stride, (uint64_t)(uintptr_t)d_pcm, header->num_channels, header->num_samples, false);
-        if (why != SB_LY_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
-    }
-    *out_bytes = 0;
-    /* the header as SetEncodeParameter, then EncodeHeader see it (a buffer under 30 bytes is EncodeHeader's first complaint) */
-    int ret = se_parameter_code(header);
-    if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: header refused by SetEncodeParameter's checks"); return ret; }
-    {
-        uint8_t hb[LINNE_HEADER_SIZE];
-        ret = (int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE);
-        if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: header refused by EncodeHeader"); return capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : ret; }
-    }
-    struct LINNEAmdShape shape;
-    shape.num_channels = header->num_channels; shape.bits_per_sample = header->bits_per_sample; shape.num_samples_per_block = header->num_samples_per_block;
-    shape.preset = header->preset; shape.ch_process_method = (uint32_t)header->ch_process_method;
-    HostShape hs;
-    if ((ret = shape_info(&shape, &hs)) != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: a shape the device path does not take"); return ret; }
-    if (!layout && shape.num_channels > 1u && pcm_stride < header->num_samples) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob: wider guard band, more plans for the host */
-    ctx->nspans = 0; ctx->span_keep = 1;
-    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
-    struct LINNEAmdPcmLayout ly;
-    if (layout) ly = *layout; else { ly.format = LINNE_AMD_PCM_S32; ly.saturated = 0; ly.channel_stride = pcm_stride; ly.sample_stride = 1u; }
-    ret = se_run(ctx, header, shape, hs, d_pcm, ly, group_frames, d_out, capacity, out_bytes, parcor_state);
-    ctx->span_keep = 0; ctx->rice_guard = 0.0;
-    if (ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
-    return ret;
-}
-
-extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
-        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
-        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
-{
-    return se_entry(ctx, header, d_pcm, pcm_stride, NULL, group_frames, d_out, capacity, out_bytes, parcor_state);
-}
-extern "C" int LINNEAmd_EncodeStreamDeviceLayout(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
-        const void *d_pcm, const struct LINNEAmdPcmLayout *layout, uint32_t group_frames,
-        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
-{
-    return se_entry(ctx, header, d_pcm, 0, layout, group_frames, d_out, capacity, out_bytes, parcor_state);
-}
-
-/* ================================================================================================
- * many tracks -> their streams, in one call (lnn_k_stream_enc.h, lnn_stream_batch.h)
- * ============================================================================================== */
 static_assert(SB_MAXLEN == LNN_MAXCLS, "lnn_stream_batch.h cuts the rows of a pass by the analysis' limit");
 
 extern "C" int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx, int which)
@@ -2878,7 +2666,7 @@ extern "C" int64_t LINNEAmd_GetLastStreamBatchCount(struct LINNEAmdContext *ctx,
     return ctx->sbatch_count[which];
 }
 
-/* a track of the call on the host: what the single call keeps in locals */
+/* a track of the call on the host */
 struct SbHost {
     int32_t result; char text[160];
     struct LINNEAmdShape shape;
@@ -2888,7 +2676,7 @@ struct SbHost {
     uint32_t fmt; uint64_t cs, ss;      /* its PCM's layout */
 };
 
-/* the argument and header checks of LINNEAmd_EncodeStreamDevice on one track, with their codes and texts, in its order */
+/* the argument and header checks of one track, with the codes, the texts and the order LINNEAmd_EncodeStreamDevice documents */
 static int sb_check_track(struct LINNEAmdTrack *t, const struct LINNEAmdPcmLayout *ly, SbHost *h)
 {
     char *err = h->text; const size_t cap = sizeof(h->text);
@@ -2909,8 +2697,7 @@ static int sb_check_track(struct LINNEAmdTrack *t, const struct LINNEAmdPcmLayou
         ret = (int)LINNEEncoder_EncodeHeader(header, hb, LINNE_HEADER_SIZE);
         if (ret != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: header refused by EncodeHeader"); return t->capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : ret; }
     }
-    h->shape.num_channels = header->num_channels; h->shape.bits_per_sample = header->bits_per_sample; h->shape.num_samples_per_block = header->num_samples_per_block;
-    h->shape.preset = header->preset; h->shape.ch_process_method = (uint32_t)header->ch_process_method;
+    h->shape = header_shape(header);
     HostShape hs;
     if ((ret = shape_info(&h->shape, &hs)) != LNN_OK) { snprintf(err, cap, "EncodeStreamDevice: a shape the device path does not take"); return ret; }
     if (!ly && h->shape.num_channels > 1u && t->pcm_stride < header->num_samples) { snprintf(err, cap, "EncodeStreamDevice: pcm_stride %llu < %u samples", (unsigned long long)t->pcm_stride, header->num_samples); return LNN_INVALID_ARGUMENT; }
@@ -2932,7 +2719,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
     uint64_t G = group_frames ? (group_frames < F ? group_frames : F) : F;
     if (G * C > 0x7FFFFFFFull) G = 0x7FFFFFFFull / C;              /* grid.x of the channel-frame kernels */
     const uint64_t T = n < G ? n : G;                               /* the tracks of a pass: each has a frame in it */
-    /* scratch of one pass: the single call's, then the tables */
+    /* scratch of one pass */
     uint64_t at = 0;
     const uint64_t o_frames = at; at = align_up(at + sizeof(int32_t) * CS * G);
     const uint64_t o_resid = at; at = align_up(at + sizeof(int32_t) * CS * G);
@@ -2946,7 +2733,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
     const uint64_t o_status = at; at = align_up(at + sizeof(int32_t) * G);
     const uint64_t o_off = at; at = align_up(at + sizeof(uint64_t) * (G + 1u));
     const uint64_t o_cfbit = at; at = align_up(at + sizeof(uint64_t) * C * G);
-    const uint64_t o_fail = at; at = align_up(at + sizeof(uint32_t) * (2u + (uint64_t)n));
+    const uint64_t o_fail = at; at = align_up(at + sizeof(uint32_t) * (uint64_t)n);                /* a word per track */
     const uint64_t o_tab = at; at = align_up(at + sizeof(SeTables));
     const uint64_t tables_bytes = align_up(sizeof(SbTrack) * T) + sizeof(SbRow) * G;
     const uint64_t o_tables = at; at = align_up(at + tables_bytes);             /* SbTrack[T], then SbRow[G] */
@@ -2967,7 +2754,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
     /* host buffers (std::bad_alloc is the caller's to catch): per row, per slot, per track of a pass */
     std::vector<uint2> h_cmp(C * G);
     std::vector<double> h_st(LINNE_AMD_STAT_WORDS * C * G), s_st(LINNE_AMD_STAT_WORDS * C * G);
-    std::vector<uint32_t> h_nz(G), h_nsmp(G), s_nsmp(G), h_settle(C * G), h_settle_n(C * G), h_bad(2u + (uint64_t)n);
+    std::vector<uint32_t> h_nz(G), h_nsmp(G), s_nsmp(G), h_settle(C * G), h_settle_n(C * G), h_bad(n);
     std::vector<uint8_t> s_nz(G), s_types(G), h_types(G), h_tables(tables_bytes), h_plans;
     std::vector<int32_t> h_res;
     std::vector<SbTrack> h_trk2(T);                                 /* the second upload of a pass (pos, write) has a buffer of its own */
@@ -2977,14 +2764,15 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         sx_tables(&t.sx);
         lnn_huff_code_table(t.code, t.len);
         HIPCHK(ctx, hipMemcpyAsync(d_tab, &t, sizeof(t), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * (2u + (uint64_t)n), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * (uint64_t)n, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (t lives on this frame) */
     }
     ctx->sbatch_count[0]++;
     SbPlanner planner;
     sb_planner_init(&planner, samples.data(), n, S);
     SbPassPlan pp;
-    while (F && sb_next_pass(&planner, G, &pp)) {
+    uint32_t live = n;                                              /* tracks no block of which was refused so far */
+    while (F && live && sb_next_pass(&planner, G, &pp)) {
         const uint32_t Fp = (uint32_t)pp.rows.size(), Tp = (uint32_t)pp.segs.size(), CF = Fp * C;
         ctx->sbatch_count[1]++;
         /* 0. the tables of the pass, in one copy */
@@ -3007,7 +2795,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         /* 1. gather */
         HIPCHK(ctx, hipMemsetAsync(d_nz, 0, sizeof(uint32_t) * Fp, ctx->stream));
         {
-            SeGatherArgs g; memset(&g, 0, sizeof(g));
+            SeGatherArgs g;
             g.frames = d_frames; g.nonzero = d_nz; g.F = Fp; g.C = C; g.S = S;
             SX_LAUNCH(LINNE_AMD_T_SB_GATHER, k_sb_gather, dim3(CF), dim3(SE_THREADS), 0, ctx->stream, g, (const SbRow *)d_rows, (const SbTrack *)d_trk);
         }
@@ -3071,7 +2859,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         for (uint32_t l = 0; l < hs.L; l++) { a.P[l] = hs.P[l]; a.coef_off[l] = hs.coef_off[l]; }
         a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.rows = d_rows; a.trk = d_trk;
         a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
-        SX_LAUNCH(LINNE_AMD_T_SB_SIZE, k_se_size<true>, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(LINNE_AMD_T_SB_SIZE, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
         SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
         SX_LAUNCH(LINNE_AMD_T_SB_REDUCE, k_sb_reduce, dim3(Tp), dim3(64), 0, ctx->stream, (const SbTrack *)d_trk, Tp, (const int32_t *)d_status, (const uint64_t *)d_off, d_tout);
         SX_TRY(sx_fetch(ctx, h_tout.data(), d_tout, sizeof(SbTrackOut) * Tp));
@@ -3087,7 +2875,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
             if (o.fail != 0xFFFFFFFFu) {
                 snprintf(th.text, sizeof(th.text), "block %llu: %s", (unsigned long long)(sg.frame0 + o.fail),
                         o.status == LNN_INVALID_FORMAT ? "a RAW block at a width other than 8, 16 or 24 bits" : "longer than the host stitcher's 64 + C * S * 8 bytes");
-                th.live = false; th.result = tr.capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : o.status; tr.out_bytes = 0;
+                live--; th.live = false; th.result = tr.capacity < LINNE_HEADER_SIZE ? LNN_INSUFFICIENT_BUFFER : o.status; tr.out_bytes = 0;
                 continue;
             }
             if (th.writing && th.pos + o.bytes > th.room) th.writing = false;
@@ -3100,15 +2888,15 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
             if (xz * Tp > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: a pass of %u tracks with up to %llu bytes each: give group_frames", Tp, (unsigned long long)most); return LNN_NG; }
             HIPCHK(ctx, hipMemcpyAsync(d_trk, h_trk2.data(), sizeof(SbTrack) * Tp, hipMemcpyHostToDevice, ctx->stream));
             SX_LAUNCH(LINNE_AMD_T_SB_ZERO, k_sb_zero, dim3((uint32_t)(xz * Tp)), dim3(SB_ZERO_THREADS), 0, ctx->stream, (const SbTrack *)d_trk, (const SbTrackOut *)d_tout, (uint32_t)xz);
-            SX_LAUNCH(LINNE_AMD_T_SB_PARAMS, k_se_params<true>, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
-            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SB_RICE, (k_se_rice<true, true>), dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
-            else SX_LAUNCH(LINNE_AMD_T_SB_RICE, (k_se_rice<false, true>), dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
-            SX_LAUNCH(LINNE_AMD_T_SB_RAW, k_se_raw<true>, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
-            SX_LAUNCH(LINNE_AMD_T_SB_CRC, k_se_crc<true>, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SB_PARAMS, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SB_RICE, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(LINNE_AMD_T_SB_RICE, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(LINNE_AMD_T_SB_RAW, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(LINNE_AMD_T_SB_CRC, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
         }
     }
     /* 7. the tracks' ends: does it fit, the length check of the Rice writers, the header */
-    SX_TRY(sx_fetch(ctx, h_bad.data(), d_fail, sizeof(uint32_t) * (2u + (uint64_t)n)));
+    SX_TRY(sx_fetch(ctx, h_bad.data(), d_fail, sizeof(uint32_t) * (uint64_t)n));
     std::vector<uint8_t> h_hdr((sizeof(uint8_t *) + 32u) * (uint64_t)n);
     uint8_t **h_dst = (uint8_t **)h_hdr.data();
     uint32_t nh = 0;
@@ -3121,7 +2909,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
             snprintf(th.text, sizeof(th.text), "the stream takes %llu bytes, the buffer holds %llu", (unsigned long long)th.pos, (unsigned long long)tr.capacity);
             th.result = LNN_INSUFFICIENT_BUFFER; continue;
         }
-        if (h_bad[2u + k]) { snprintf(th.text, sizeof(th.text), "a Rice code's length is not its plan's (a wrapped 32-bit length count)"); th.result = LNN_NG; continue; }
+        if (h_bad[k]) { snprintf(th.text, sizeof(th.text), "a Rice code's length is not its plan's (a wrapped 32-bit length count)"); th.result = LNN_NG; continue; }
         SX_TRY((int)LINNEEncoder_EncodeHeader(&tr.header, h_hdr.data() + sizeof(uint8_t *) * (uint64_t)n + 32u * (uint64_t)nh, LINNE_HEADER_SIZE));
         h_dst[nh++] = tr.d_out;
         th.result = LNN_OK;
@@ -3158,7 +2946,7 @@ static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const stru
     if (frames > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: %llu frames in one call: too many", (unsigned long long)frames); return LNN_NG; }
     if (groups.empty()) return LNN_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob, as in the single call */
+    { const char *g = getenv("LINNE_AMD_RICE_GUARD"); ctx->rice_guard = g ? atof(g) : 0.0; }      /* test knob: wider guard band, more plans for the host */
     if (!ctx->outer_keep) ctx->nspans = 0;
     ctx->span_keep = 1;
     if (ctx->timing && !ctx->outer_keep) (void)hipEventRecord(ctx->ev[0], ctx->stream);
@@ -3168,16 +2956,10 @@ static int sb_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const stru
     return ret == LNN_OK ? LNN_OK : LNN_NG;
 }
 
-/* int32 planar tracks: the call below without layouts */
-extern "C" int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames)
+/* Both pairs of entry points behind their context check: the tracks' results, then the call's -- the lowest-numbered failing
+ * track's code, with its text in ctx->err (behind the track's number unless the call is the single one) */
+static int sb_call(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const struct LINNEAmdPcmLayout *layouts, uint32_t num_tracks, uint32_t group_frames, bool single)
 {
-    return LINNEAmd_EncodeStreamsDeviceLayout(ctx, tracks, NULL, num_tracks, group_frames);
-}
-
-extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const struct LINNEAmdPcmLayout *layouts,
-        uint32_t num_tracks, uint32_t group_frames)
-{
-    if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
     for (int i = 0; i < 4; i++) ctx->senc_count[i] = 0;
     for (int i = 0; i < 3; i++) ctx->sbatch_count[i] = 0;
@@ -3191,12 +2973,11 @@ extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, s
     ctx->span_keep = 0; ctx->rice_guard = 0.0;
     if (began && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
     /* (whatever was enqueued is waited for: it reads the context's buffers) */
-    if (began && hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
+    if (began && hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStream%sDevice: hipStreamSynchronize failed", single ? "" : "s"); ret = LNN_NG; }
     if (ret != LNN_OK) {
         for (uint32_t i = 0; i < num_tracks; i++) tracks[i].result = LNN_NG;
         return LNN_NG;
     }
-    /* the tracks' results, then the call's: the lowest-numbered failing track's code, its text behind its number */
     int first = -1;
     for (uint32_t i = 0; i < num_tracks; i++) {
         tracks[i].result = host[i].result;
@@ -3204,8 +2985,51 @@ extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, s
         else if (first < 0) first = (int)i;
     }
     if (first < 0) return LNN_OK;
-    snprintf(ctx->err, sizeof(ctx->err), "track %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", host[first].text);
+    else snprintf(ctx->err, sizeof(ctx->err), "track %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
     return host[first].result;
+}
+
+/* int32 planar tracks: the call below without layouts */
+extern "C" int LINNEAmd_EncodeStreamsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, uint32_t num_tracks, uint32_t group_frames)
+{
+    return LINNEAmd_EncodeStreamsDeviceLayout(ctx, tracks, NULL, num_tracks, group_frames);
+}
+
+extern "C" int LINNEAmd_EncodeStreamsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const struct LINNEAmdPcmLayout *layouts,
+        uint32_t num_tracks, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    return sb_call(ctx, tracks, layouts, num_tracks, group_frames, false);
+}
+
+/* One track, int32 planar with pcm_stride (layout NULL) or as its layout says.  A NULL header or out_bytes leaves the track without
+ * its d_pcm, which its check reports as the null argument it is; *out_bytes and *parcor_state are the track's, the state only on OK. */
+static int se_single(struct LINNEAmdContext *ctx, const struct LINNEHeader *header, const void *d_pcm, uint64_t pcm_stride,
+        const struct LINNEAmdPcmLayout *layout, uint32_t group_frames, uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    struct LINNEAmdTrack t;
+    memset(&t, 0, sizeof(t));
+    if (header && out_bytes) { t.header = *header; t.d_pcm = (const int32_t *)d_pcm; }
+    if (out_bytes) t.out_bytes = *out_bytes;
+    t.pcm_stride = pcm_stride; t.d_out = d_out; t.capacity = capacity; t.parcor_state = parcor_state ? *parcor_state : 0.0;
+    const int ret = sb_call(ctx, &t, layout, 1, group_frames, true);
+    if (out_bytes) *out_bytes = t.out_bytes;
+    if (ret == LNN_OK && parcor_state) *parcor_state = t.parcor_state;
+    return ret;
+}
+extern "C" int LINNEAmd_EncodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const int32_t *d_pcm, uint64_t pcm_stride, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    return se_single(ctx, header, d_pcm, pcm_stride, NULL, group_frames, d_out, capacity, out_bytes, parcor_state);
+}
+extern "C" int LINNEAmd_EncodeStreamDeviceLayout(struct LINNEAmdContext *ctx, const struct LINNEHeader *header,
+        const void *d_pcm, const struct LINNEAmdPcmLayout *layout, uint32_t group_frames,
+        uint8_t *d_out, uint64_t capacity, uint64_t *out_bytes, double *parcor_state)
+{
+    return se_single(ctx, header, d_pcm, 0, layout, group_frames, d_out, capacity, out_bytes, parcor_state);
 }
 
 

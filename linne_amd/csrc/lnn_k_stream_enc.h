@@ -1,10 +1,11 @@
-/* lnn_k_stream_enc.h -- encoding planar PCM that lies in device memory into a .lnn stream in device memory
- * (LINNEAmd_EncodeStreamDevice; DESIGN.md section 5, "Encoding into a stream in HBM").
+/* lnn_k_stream_enc.h -- encoding PCM that lies in device memory into .lnn streams in device memory
+ * (LINNEAmd_EncodeStreamsDevice, and LINNEAmd_EncodeStreamDevice as its one-track case; DESIGN.md section 5, "Encoding into a
+ * stream in HBM" and "Encoding many tracks in one call").
  *
  * Per pass of frames (between the analysis and the writers sits the one host step: block types, flagged Rice plans):
- *   k_se_gather    the input (int32 planar, or any struct LINNEAmdPcmLayout: int16 / packed 24-bit, interleaved, padded) -> the
- *                  [F][C][S] frame layout of the analysis, the last frame zero-padded; per frame a flag "some sample is not 0" (the
- *                  SILENT test of the block-type decision)
+ *   k_sb_gather    the input (int32 planar, or any struct LINNEAmdPcmLayout: int16 / packed 24-bit, interleaved, padded) -> the
+ *                  [F][C][S] frame layout of the analysis, a track's last frame zero-padded; per frame a flag "some sample is not
+ *                  0" (the SILENT test of the block-type decision)
  *   k_se_compact   each channel-frame's plan flag, partition order and code length in 8 bytes (what the host step reads)
  *   k_se_size      each block's size, where each channel's Rice code starts in it, and the host stitcher's per-block errors
  *   k_sx_scan      (lnn_k_stream.h) the blocks' offsets
@@ -21,13 +22,11 @@
  * no word with any code (11 header bytes lie between blocks), and the header bytes, whose words the codes of the block before and
  * after may share, are written by k_se_crc, a launch of its own after every writer of the pass.
  *
- * Many tracks in one call (LINNEAmd_EncodeStreamsDevice; DESIGN.md section 5, "Encoding many tracks in one call").  The rows of a
- * pass are frames of several tracks, full frames first, the ragged ones sorted by length behind them; a per-row table (SbRow: the
- * track, the row's slot in stream order, the frame's first sample) and a per-track table (SbTrack) connect rows to streams.  The
- * analysis, the Rice plan and every k_se_* kernel work per row as above; sizes, statuses and offsets are indexed by SLOT, so that
- * the scan runs over stream order, and the writers (the <true> instantiations) place a row at
+ * Rows, slots and tracks.  The rows of a pass are frames of one or several tracks, full frames first, the ragged ones sorted by
+ * length behind them; a per-row table (SbRow: the track, the row's slot in stream order, the frame's first sample) and a per-track
+ * table (SbTrack) connect rows to streams.  The analysis, the Rice plan and every kernel above work per row; sizes, statuses and
+ * offsets are indexed by SLOT, so that the scan runs over stream order, and the writers place a row at
  * track.out + track.pos + (off[slot] - off[track.slot0]) and skip the rows of a track that is not written.  Beside them:
- *   k_sb_gather    k_se_gather with each row's source read from the tables
  *   k_sb_reduce    a wave per track of the pass: its bytes, its lowest failing block and that block's status (one copy to the host)
  *   k_sb_zero      zeroes exactly [pos, pos + bytes) of every written track: whole words where all four bytes are the region's,
  *                  byte stores at its edges
@@ -51,7 +50,7 @@ struct SeTables {
     uint8_t len[256];
 };
 
-/* the tables of a many-track pass */
+/* the tables of a pass */
 struct SbRow { uint32_t track, slot; uint64_t first; };        /* index into the pass's SbTrack table; slot in stream order; the frame's first sample in its track */
 struct SbTrack {
     const void *pcm; uint64_t stride, total;                    /* element (ch, i) at pcm + (ch * stride + i * sstride) elements; samples per channel */
@@ -63,12 +62,9 @@ struct SbTrack {
 struct SbTrackOut { uint64_t bytes; uint32_t fail; int32_t status; };  /* of a track in a pass: bytes; lowest failing slot - slot0 (~0: none), its status */
 
 struct SeGatherArgs {
-    const void *pcm; uint64_t stride;           /* element (ch, i) at pcm + (ch * stride + i * sstride) elements */
-    uint64_t first, total;                      /* the pass's first sample, the stream's samples per channel */
     int32_t *frames;                            /* [F][C][S] */
     uint32_t *nonzero;                          /* [F], zeroed */
     uint32_t F, C, S;
-    uint32_t fmt; uint64_t sstride;             /* the layout (int32 planar: S32, 1) */
 };
 
 /* (reading PCM of any layout: ly_word / ly_load4 / ly_load1 of lnn_k_pcm_load.h) */
@@ -124,26 +120,7 @@ __device__ __forceinline__ int se_gather_layout(const void *pcm, uint32_t fmt, u
     return any;
 }
 
-/* a workgroup per channel-frame */
-__global__ __launch_bounds__(SE_THREADS) void k_se_gather(SeGatherArgs a)
-{
-    const uint32_t cf = blockIdx.x, f = cf / a.C, ch = cf - f * a.C;
-    const uint64_t s0 = a.first + (uint64_t)f * a.S;
-    const uint32_t n = (a.total - s0 < a.S) ? (uint32_t)(a.total - s0) : a.S;
-    int any = 0;
-    if (a.fmt == LINNE_AMD_PCM_S32 && a.sstride == 1u) {
-        const int32_t *src = (const int32_t *)a.pcm + (uint64_t)ch * a.stride + s0;
-        int32_t *dst = a.frames + (uint64_t)cf * a.S;
-        for (uint32_t s = threadIdx.x; s < a.S; s += SE_THREADS) {
-            const int32_t v = (s < n) ? src[s] : 0;
-            dst[s] = v;
-            any |= (v != 0);
-        }
-    } else any = se_gather_layout(a.pcm, a.fmt, a.stride, a.sstride, a.total, s0, n, a.frames, f, ch, a.C, a.S);      /* block-uniform */
-    if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&a.nonzero[f], 1u);
-}
-
-/* the same for the rows of many tracks (a.pcm, a.stride, a.first, a.total, a.fmt, a.sstride are not used: every row's track has its own) */
+/* a workgroup per channel-frame: row f's source is its track's */
 __global__ __launch_bounds__(SE_THREADS) void k_sb_gather(SeGatherArgs a, const SbRow *rows, const SbTrack *trk)
 {
     const uint32_t cf = blockIdx.x, f = cf / a.C, ch = cf - f * a.C;
@@ -181,18 +158,16 @@ struct SeBlockArgs {
     uint32_t F, C, S, bits, L, P[LNN_MAXL], coef_off[LNN_MAXL];
     uint32_t *size;                     /* [F] bytes of each block (k_se_size) */
     int32_t *status;                    /* [F] LNN_* of each block (k_se_size) */
-    uint32_t *fail;                     /* [0] lowest failing block (atomicMin), [1] set when a Rice code's length is not its plan's */
+    uint32_t *fail;                     /* a word per track of the shape group, set when a Rice code's length is not its plan's */
     uint64_t *cfbit;                    /* [F * C] bit offset of each channel's code from its block's first byte */
-    const uint64_t *off;                /* [F + 1] offsets of the blocks from `base` (k_sx_scan) */
-    uint8_t *out; uint64_t base;        /* the stream and the pass's first byte in it */
+    const uint64_t *off;                /* [F + 1] offsets of the slots' blocks from the first one's (k_sx_scan) */
     uint32_t xch;                       /* k_se_raw: workgroups per block */
-    const SbRow *rows; const SbTrack *trk;      /* the <true> instantiations (many tracks): size, status and off are indexed by slot, out / base are not used */
+    const SbRow *rows; const SbTrack *trk;      /* (size, status and off are indexed by slot, everything else by row) */
 };
 
 /* where row f's block goes: the stream, the block's first byte in it, the row's slot; false: the row's track is not written */
-template <bool TRACKS> __device__ __forceinline__ bool se_where(const SeBlockArgs &a, uint32_t f, uint8_t *&out, uint64_t &p, uint32_t &slot)
+__device__ __forceinline__ bool se_where(const SeBlockArgs &a, uint32_t f, uint8_t *&out, uint64_t &p, uint32_t &slot)
 {
-    if (!TRACKS) { out = a.out; p = a.base + a.off[f]; slot = f; return true; }
     const SbRow r = a.rows[f];
     const SbTrack &t = a.trk[r.track];
     out = t.out; p = t.pos + (a.off[r.slot] - a.off[t.slot0]); slot = r.slot;
@@ -212,7 +187,7 @@ __device__ __forceinline__ uint64_t se_param_bits(const SeBlockArgs &a, const in
 
 /* a lane per block: its size, the start of every channel's code, the host stitcher's per-block errors (lnn_entropy.c pack_block:
  * a RAW block at a width other than 8, 16 or 24 bits; a block over its 64 + C * S * 8 bytes; a size field over 32 bits) */
-template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_size(SeBlockArgs a)
+__global__ __launch_bounds__(SE_THREADS) void k_se_size(SeBlockArgs a)
 {
     const uint32_t f = blockIdx.x * SE_THREADS + threadIdx.x;
     if (f >= a.F) return;
@@ -234,14 +209,13 @@ template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_size(S
         bytes = (at + 7u) >> 3;
         if (bytes > 64u + (uint64_t)a.C * a.S * 8u || bytes - 11u + 5u > 0xFFFFFFFFull) st = LNN_INSUFFICIENT_BUFFER;
     }
-    const uint32_t slot = TRACKS ? a.rows[f].slot : f;
+    const uint32_t slot = a.rows[f].slot;
     a.status[slot] = st;
     a.size[slot] = (st == LNN_OK) ? (uint32_t)bytes : 0u;
-    if (!TRACKS && st != LNN_OK) atomicMin(&a.fail[0], f);            /* (many tracks: k_sb_reduce finds each track's) */
 }
 
 /* a lane per COMPRESS block: the parameter bits (linne_encoder.c:698-735) from bit 88 of the block on */
-template <bool TRACKS> __global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
+__global__ __launch_bounds__(64) void k_se_params(SeBlockArgs a)
 {
     __shared__ uint32_t code[256];
     __shared__ uint8_t len[256];
@@ -250,7 +224,7 @@ template <bool TRACKS> __global__ __launch_bounds__(64) void k_se_params(SeBlock
     const uint32_t f = blockIdx.x * 64u + threadIdx.x;
     if (f >= a.F || a.types[f] != SX_COMPRESS) return;
     uint8_t *out; uint64_t p; uint32_t slot;
-    if (!se_where<TRACKS>(a, f, out, p, slot)) return;
+    if (!se_where(a, f, out, p, slot)) return;
     const uint64_t start = p * 8u + 88u;
     RiceBW bw; bw.dst = (uint32_t *)out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
     auto put = [&](uint32_t v, uint32_t nb) { if (nb) bw.put(v & (0xFFFFFFFFu >> (32u - nb)), nb); };
@@ -272,9 +246,9 @@ template <bool TRACKS> __global__ __launch_bounds__(64) void k_se_params(SeBlock
 
 /* A workgroup per channel-frame of a COMPRESS block: k_rice_emit's two passes (lengths, then codes) with the writer started at the
  * channel's bit in the stream.  The code's length must be its plan's (the block's size was computed from it): a channel whose code
- * would come out longer or shorter writes nothing and raises fail[1] (the call then fails; only a uint32 wrap-around of the
- * reference's length count could do it). */
-template <bool LDS, bool TRACKS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(SeBlockArgs a)
+ * would come out longer or shorter writes nothing and raises its track's fail word (the track then fails; only a uint32
+ * wrap-around of the reference's length count could do it). */
+template <bool LDS> __global__ __launch_bounds__(REMIT_THREADS) void k_se_rice(SeBlockArgs a)
 {
     extern __shared__ uint32_t zbuf[];
     __shared__ uint8_t kk[1024];
@@ -283,7 +257,7 @@ template <bool LDS, bool TRACKS> __global__ __launch_bounds__(REMIT_THREADS) voi
     const uint32_t f = cf / a.C;
     if (a.types[f] != SX_COMPRESS) return;                    /* block-uniform */
     uint8_t *out; uint64_t p; uint32_t slot;
-    if (!se_where<TRACKS>(a, f, out, p, slot)) return;        /* block-uniform */
+    if (!se_where(a, f, out, p, slot)) return;        /* block-uniform */
     const uint8_t *rec = a.plan + (uint64_t)cf * LINNE_AMD_RICE_PLAN_BYTES;
     const uint32_t nbits = *(const uint32_t *)(rec + LINNE_AMD_RICE_PLAN_NBITS);
     const uint32_t n = a.nsmp[f], best = rec[0], ns = n >> best, parts = 1u << best;
@@ -312,7 +286,7 @@ template <bool LDS, bool TRACKS> __global__ __launch_bounds__(REMIT_THREADS) voi
     __syncthreads();
     uint64_t start = incl - mybits, total = 0;
     for (uint32_t w = 0; w < REMIT_THREADS / 64; w++) { if (w < wave) start += wsum[w]; total += wsum[w]; }
-    if (total != nbits) { if (tid == 0) atomicOr(TRACKS ? &a.fail[2u + a.trk[a.rows[f].track].id] : &a.fail[1], 1u); return; }          /* block-uniform; many tracks: a word per track of the shape group */
+    if (total != nbits) { if (tid == 0) atomicOr(&a.fail[a.trk[a.rows[f].track].id], 1u); return; }          /* block-uniform */
     if (s0 >= s1) return;
     start += p * 8u + a.cfbit[cf];
     RiceBW bw; bw.dst = (uint32_t *)out; bw.w = bw.first_w = (uint32_t)(start >> 5); bw.fill = (uint32_t)(start & 31u); bw.cur = 0;
@@ -342,12 +316,12 @@ template <bool LDS, bool TRACKS> __global__ __launch_bounds__(REMIT_THREADS) voi
 }
 
 /* xch workgroups per block: the samples of RAW blocks, zig-zagged, big-endian, channels interleaved; `pcm` is the pass's [F][C][S] */
-template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int32_t *pcm)
+__global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int32_t *pcm)
 {
     const uint32_t f = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
     if (a.types[f] != SX_RAW) return;
     uint8_t *out; uint64_t p; uint32_t slot;
-    if (!se_where<TRACKS>(a, f, out, p, slot)) return;
+    if (!se_where(a, f, out, p, slot)) return;
     const uint32_t n = a.nsmp[f], w = a.bits >> 3;
     uint8_t *dst = out + p + 11u;
     for (uint32_t s = x * SE_THREADS + threadIdx.x; s < n; s += a.xch * SE_THREADS)
@@ -361,7 +335,7 @@ template <bool TRACKS> __global__ __launch_bounds__(SE_THREADS) void k_se_raw(Se
 /* A wave per block (four per workgroup), after every other writer of the pass: the CRC16 over [p + 8, p + 6 + size) -- the type and
  * sample count, which this launch writes, taken from registers, the payload from memory -- from lane partials shifted by the bytes
  * behind them (k_sx_check), then the 11 header bytes: FF FF, size - 6, CRC, type, n (linne_encoder.c:806-855). */
-template <bool TRACKS> __global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
+__global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
 {
     __shared__ uint16_t crc_t[256];
     __shared__ uint16_t shift_t[SX_CRC_LEVELS][16];
@@ -371,7 +345,7 @@ template <bool TRACKS> __global__ __launch_bounds__(256) void k_se_crc(SeBlockAr
     const uint32_t f = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (f >= a.F) return;
     uint8_t *out; uint64_t p; uint32_t slot;
-    if (!se_where<TRACKS>(a, f, out, p, slot)) return;        /* wave-uniform */
+    if (!se_where(a, f, out, p, slot)) return;        /* wave-uniform */
     const uint32_t size = a.size[slot], type = a.types[f], n = a.nsmp[f];
     const uint32_t h0 = type & 0xFFu, h1 = (n >> 8) & 0xFFu, h2 = n & 0xFFu;
     const uint64_t len = (uint64_t)size - 8u;                      /* 3 header bytes + the payload */
@@ -402,11 +376,11 @@ template <bool TRACKS> __global__ __launch_bounds__(256) void k_se_crc(SeBlockAr
     h[8] = (uint8_t)h0; h[9] = (uint8_t)h1; h[10] = (uint8_t)h2;
 }
 
-/* ---- many tracks ---- */
+/* ---- per track of a pass ---- */
 #define SB_ZERO_THREADS 256u
 #define SB_ZERO_CHUNK 65536u            /* bytes a workgroup of k_sb_zero clears */
 
-/* A wave per track of the pass, behind k_se_size<true> and the scan: the bytes of the track's blocks, the lowest slot whose block
+/* A wave per track of the pass, behind k_se_size and the scan: the bytes of the track's blocks, the lowest slot whose block
  * the host stitcher refuses (relative to the track's first slot) and that block's status. */
 __global__ __launch_bounds__(64) void k_sb_reduce(const SbTrack *trk, uint32_t ntrk, const int32_t *status, const uint64_t *off, SbTrackOut *out)
 {

@@ -376,7 +376,7 @@ def test_launch_counts(s16):
         c.encode_stream(torch.from_numpy(xs[0]).cuda(), 16, 44100, block, 4, True)
         one = {k: c.last_launches(k) for k in enc_kinds}
         c.encode_stream(device_pcm(xs[0], PCM_S24, True), 16, 44100, block, 4, True)
-        assert one == {k: c.last_launches(k) for k in enc_kinds} and one[48] >= 1
+        assert one == {k: c.last_launches(k) for k in enc_kinds} and one == census[0] and one[60] >= 1          # the one-track batch's
         index = c.index_stream(s16.dev)
         starts = [int(a) for a in np.random.default_rng(8).integers(0, s16.ns - 2500, size=24)]
         starts[0] = 10                                           # music: COMPRESS blocks

@@ -197,6 +197,48 @@ def test_failing_tracks_among_good_ones(ctx, product):
     assert e.value.code == codes[1] and e.value.codes == codes
 
 
+def test_single_call_text_is_the_track_text(ctx):
+    """LINNEAmd_EncodeStreamDevice is the one-track case of LINNEAmd_EncodeStreamsDevice: for every kind of failure the batch call on
+    the one track reads "track 0: " and exactly the single call's text, with the same code, out_bytes and parcor_state -- and the
+    single call's texts are the ones it has always had."""
+    import torch
+    ns, block = 20000, 4096
+    sound = torch.from_numpy(music(2, ns, 16, seed=220)).cuda()
+    noise12 = torch.from_numpy(np.random.default_rng(7).integers(-2048, 2048, size=(2, ns)).astype(np.int32)).cuda()
+    room = 4 * ns * 2 + 65536
+    buf = torch.zeros(room + 64, dtype=torch.uint8, device="cuda")
+
+    def both(pcm, bits, preset, ms, capacity, shift=0):
+        """((code, out_bytes, state, text) of the single call, the same of the batch call on the one track)"""
+        hdr = linne_amd.Header(1, 2, 2, ns, 44100, bits, block, preset, ms)
+        nbytes, state = C.c_uint64(12345), C.c_double(0.25)
+        ctx._fence()
+        ret = linne_amd.lib.LINNEAmd_EncodeStreamDevice(ctx.h, C.byref(hdr), C.c_void_p(pcm.data_ptr()), pcm.stride(0), 0,
+                                                        C.c_void_p(buf.data_ptr() + shift), capacity, C.byref(nbytes), C.byref(state))
+        single = (ret, nbytes.value, state.value, linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode())
+        arr = (linne_amd.Track * 1)()
+        arr[0].header, arr[0].d_pcm, arr[0].pcm_stride = hdr, pcm.data_ptr(), pcm.stride(0)
+        arr[0].d_out, arr[0].capacity = buf.data_ptr() + shift, capacity
+        arr[0].out_bytes, arr[0].parcor_state, arr[0].result = 12345, 0.25, -1
+        ret = linne_amd.lib.LINNEAmd_EncodeStreamsDevice(ctx.h, arr, 1, 0)
+        assert ret == arr[0].result
+        return single, (ret, arr[0].out_bytes, arr[0].parcor_state, linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode())
+
+    single, batch = both(sound, 16, 4, 1, room)
+    assert single == batch and single[0] == OK and single[3] == "" and single[2] != 0.25        # the state is replaced on OK
+    n = single[1]
+    cases = [
+        ((sound, 16, 4, 1, room, 2), INVALID_ARGUMENT, 12345, "EncodeStreamDevice: d_out is not 4-byte aligned"),
+        ((sound, 16, 8, 1, room), INVALID_FORMAT, 0, "EncodeStreamDevice: header refused by SetEncodeParameter's checks"),
+        ((noise12, 12, 3, 0, room), INVALID_FORMAT, 0, "block 0: a RAW block at a width other than 8, 16 or 24 bits"),
+        ((sound, 16, 4, 1, n - 1), INSUFFICIENT_BUFFER, n, f"the stream takes {n} bytes, the buffer holds {n - 1}"),
+    ]
+    for args, code, out_bytes, text in cases:
+        single, batch = both(*args)
+        assert single == (code, out_bytes, 0.25, text), text                                # a failing call leaves the state alone
+        assert batch == (code, out_bytes, 0.25, "track 0: " + text), text
+
+
 MATRIX = [
     (1, 16, 4096, 0, False, 50000),
     (2, 16, 4096, 1, True, 60000),

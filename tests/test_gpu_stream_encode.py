@@ -217,6 +217,15 @@ def test_capacity(ctx, product):
     ret, nbytes = raw_call(ctx, pcm, hdr, buf.data_ptr(), n)
     assert (ret, nbytes) == (OK, n)
     assert bytes(buf[:n].cpu().numpy()) == want and bool((buf[n:] == 0xA5).all())
+    # passes: each one's region [first byte, first byte of the next) is cleared on its own, whole words inside it and single bytes at
+    # its edges, so the passes' first bytes have to meet every place in a 32-bit word
+    offs = [b[0] for b in blocks(bytes(buf[:n].cpu().numpy()))]
+    assert {o % 4 for g in (1, 3) for o in offs[::g]} == {0, 1, 2, 3}, offs
+    for g in (1, 3):
+        buf.fill_(0xA5)
+        ret, nbytes = raw_call(ctx, pcm, hdr, buf.data_ptr(), n, group_frames=g)
+        assert (ret, nbytes) == (OK, n), g
+        assert bytes(buf[:n].cpu().numpy()) == want and bool((buf[n:] == 0xA5).all()), g
     assert raw_call(ctx, pcm, hdr, buf.data_ptr() + 2, n)[0] == INVALID_ARGUMENT
     # full-scale noise: every block RAW
     rng = np.random.default_rng(9)
@@ -267,9 +276,11 @@ def test_timing_kinds(product):
     try:
         c.enable_timing(True)
         stream = c.encode_stream(x, 16, 44100, 4096, 7, True, group_frames=5)
-        for k in range(48, 56):
+        for k in list(range(60, 68)) + [49, 51, 17]:
             assert c.last_launches(k) >= 2, k                               # two passes
-        assert c.last_launches(17) >= 2 and c.last_ms(0) > 0
+        assert c.last_launches(68) >= 1 and c.last_ms(0) > 0
+        for k in (48, 50, 52, 53, 54, 55):                                  # the kinds of the single call's own launches: retired
+            assert c.last_launches(k) == 0, k
         assert bytes(stream.cpu().numpy()) == product.encode_whole(x, 16, 44100, 4096, 7, True)
     finally:
         c.close()

@@ -2,8 +2,9 @@
 stereo, -m 7, block 10240, MS, resident in HBM as planar int32.  Reports the median of --reps runs after a warm-up, each run ending in
 a device synchronise: encode_stream with the whole stream in one pass, the resident analysis step alone (EncodeFramesDevice on the
 same frames, already in the [F][C][S] layout), and LINNEEncoder_EncodeWhole from host memory.  Checks that the device's stream equals
-EncodeWhole's bytes and that decode_stream(encode_stream(x)) == x without leaving the device.  Prints one JSON line
-(profiles/stream_encode.json holds the MI355X's)."""
+EncodeWhole's bytes and that decode_stream(encode_stream(x)) == x without leaving the device.  Two options add what a pass and what
+a call cost: --group-frames G encodes the same track in passes of G frames, --calls N makes N encode_stream calls on 3-second stereo
+tracks at block 4096.  Prints one JSON line (profiles/stream_encode.json holds the MI355X's)."""
 import argparse, ctypes as C, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,6 +16,8 @@ from bench import synth_track
 ap = argparse.ArgumentParser()
 ap.add_argument("--minutes", type=float, default=60.0)
 ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--group-frames", type=int, default=0, help="also time the track in passes of this many frames")
+ap.add_argument("--calls", type=int, default=0, help="also time this many encode_stream calls on 3-second tracks at block 4096")
 args = ap.parse_args()
 nch, bits, rate, block, preset, ms = 2, 16, 44100, 10240, 7, True
 ns = int(args.minutes * 60 * rate)
@@ -40,6 +43,22 @@ stream = ctx.encode_stream(d_x, bits, rate, block, preset, ms)
 counts = {k: ctx.last_stream_encode_count(i) for i, k in enumerate(("compress", "silent", "raw", "host_settled_plans"))}
 ok_round_trip = bool(torch.equal(ctx.decode_stream(stream), d_x))
 t_stream, _ = median_ms(lambda: ctx.encode_stream(d_x, bits, rate, block, preset, ms), args.reps)
+extra = {}
+if args.group_frames:
+    g = args.group_frames
+    same = bool(torch.equal(ctx.encode_stream(d_x, bits, rate, block, preset, ms, group_frames=g), stream))
+    t_g, _ = median_ms(lambda: ctx.encode_stream(d_x, bits, rate, block, preset, ms, group_frames=g), args.reps)
+    extra.update({"group_frames": g, "passes": -(-((ns + block - 1) // block) // g), "encode_stream_passes_ms": round(t_g, 3), "passes_same_bytes": same})
+if args.calls:
+    n3 = 3 * rate
+    clips = [d_x[:, i * n3:(i + 1) * n3] for i in range(min(args.calls, ns // n3))]
+    assert clips, "--calls needs a track of 3 seconds or more"
+
+    def many():
+        for i in range(args.calls):
+            ctx.encode_stream(clips[i % len(clips)], bits, rate, 4096, preset, ms)
+    t_c, _ = median_ms(many, args.reps)
+    extra.update({"calls": args.calls, "clip": "3 s stereo, block 4096, -m 7", "encode_stream_calls_ms": round(t_c, 3)})
 # the resident analysis step alone, on the same frames in the [F][C][S] layout
 F = (ns + block - 1) // block
 frames = torch.zeros((F * block, nch), dtype=torch.int32, device="cuda")
@@ -54,7 +73,7 @@ del frames, bufs
 # the kernels of one encode_stream call (timing on: events around every launch)
 ctx.enable_timing(True)
 ctx.encode_stream(d_x, bits, rate, block, preset, ms)
-kinds = {k: round(ctx.last_ms(k), 3) for k in (48, 17, 49, 50, 51, 52, 53, 54, 55) if ctx.last_launches(k) > 0}
+kinds = {k: round(ctx.last_ms(k), 3) for k in (60, 17, 49, 61, 51, 62, 63, 64, 65, 66, 67, 68) if ctx.last_launches(k) > 0}
 ctx.enable_timing(False)
 # EncodeWhole from host memory
 enc = api.new_encoder(nch, bits, rate, block, preset, ms)
@@ -73,7 +92,7 @@ print(json.dumps({
     "config": f"{args.minutes:g} min 44.1 kHz int16 stereo, -m 7, block 10240, MS (BASELINE configs[1])", "stream_bytes": int(stream.numel()),
     "frames": F, "blocks": counts, "reps": args.reps, "statistic": "median ms, warm-up excluded, each run ends in a device synchronise",
     "encode_stream_one_pass_ms": round(t_stream, 3), "encode_frames_device_ms": round(t_frames, 3),
-    "encode_whole_host_memory_ms": round(t_whole, 3),
+    "encode_whole_host_memory_ms": round(t_whole, 3), **extra,
     "kernel_ms_encode_stream": {str(k): v for k, v in kinds.items()},
     "exact": {"equal_to_encode_whole": ok_bytes, "device_round_trip": ok_round_trip},
 }))
