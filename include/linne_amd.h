@@ -314,15 +314,16 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_DEEMPH_LR = 34,         /* the de-emphasis behind it (k_deemph_lr; it includes MS->LR when whole frames lie in a block of 64 rows: no kind 12 then) */
     LINNE_AMD_T_SYNTH_L0_DE = 35,       /* layer 0 + de-emphasis + MS->LR in one launch (k_synth_l0_de) */
     LINNE_AMD_T_SYNTH_ROWS_SHORT = 36,  /* the throughput form of a short layer (k_synth_rows<0> / k_synth_rows8: four or eight channel-frames per wave) */
-    /* the stream index (LINNEAmd_StreamIndexCreate, a call of its own) */
-    LINNE_AMD_T_SX_COUNT = 37,          /* counting the block candidates (k_sx_count) */
-    LINNE_AMD_T_SX_WRITE = 38,          /* writing them (k_sx_write) */
-    LINNE_AMD_T_SX_SCAN = 39,           /* prefix sums (k_sx_scan) */
-    LINNE_AMD_T_SX_SUCC = 40,           /* successors (k_sx_succ) */
+    /* the stream indexes (LINNEAmd_StreamIndexesCreate, and LINNEAmd_StreamIndexCreate as its one-stream case; a call of its own,
+     * with 69 and 70 below) */
+    LINNE_AMD_T_SX_COUNT = 37,          /* counting the block candidates (k_ib_count) */
+    LINNE_AMD_T_SX_WRITE = 38,          /* writing them (k_ib_write) */
+    LINNE_AMD_T_SX_SCAN = 39,           /* prefix sums and what reads them per stream (k_sx_scan, k_ib_seg, k_ib_first) */
+    LINNE_AMD_T_SX_SUCC = 40,           /* successors (k_ib_succ) */
     LINNE_AMD_T_SX_JUMP = 41,           /* pointer doubling (k_sx_jump, a launch per level) */
-    LINNE_AMD_T_SX_CHAIN_LEN = 42,      /* the chain's length (k_sx_chain_len) */
-    LINNE_AMD_T_SX_CHAIN = 43,          /* its blocks (k_sx_chain) */
-    LINNE_AMD_T_SX_CHECK = 44,          /* CRC16 and block checks (k_sx_check) */
+    LINNE_AMD_T_SX_CHAIN_LEN = 42,      /* the chains' lengths (k_ib_chain_len) */
+    LINNE_AMD_T_SX_CHAIN = 43,          /* their blocks (k_ib_chain) */
+    LINNE_AMD_T_SX_CHECK = 44,          /* CRC16 and block checks (k_ib_check) */
     /* 45-47 were the kinds of LINNEAmd_DecodeStreamDevice's own kernels, which are gone (it reports 56-59 now); the numbers are not
      * reused, so that recorded profiles stay readable */
     /* the stream encoders (LINNEAmd_EncodeStreamsDevice, and LINNEAmd_EncodeStreamDevice as its one-track case; the analysis and
@@ -347,8 +348,7 @@ enum LINNEAmdTimingKind {
     LINNE_AMD_T_SB_RAW = 66,            /* RAW payloads (k_se_raw) */
     LINNE_AMD_T_SB_CRC = 67,            /* CRC16 and block headers (k_se_crc) */
     LINNE_AMD_T_SB_HEADER = 68,         /* the finished tracks' stream headers (k_sb_header) */
-    /* the indexes of many streams (LINNEAmd_StreamIndexesCreate, a call of its own): its segmented kernels report under 37-44, the
-     * two without a single-call counterpart follow here, numbered on from the kind above (lnn_device.hip asserts 69 and 70: a kind
+    /* the rest of the stream indexes' kinds (both calls), numbered on from the kind above (lnn_device.hip asserts 69 and 70: a kind
      * put between them and 68 does not compile) */
     LINNE_AMD_T_IB_HEADERS,             /* 69: gathering every stream's header bytes (k_ib_headers) */
     LINNE_AMD_T_IB_BEHIND               /* 70: the place behind a chain that ends early (k_ib_behind) */
@@ -424,8 +424,12 @@ int LINNEAmd_PackFramesEmitted(const struct LINNEAmdShape *shape, const int32_t 
  * LINNEAmd_StreamIndexCreate reads the 30-byte header through LINNEDecoder_DecodeHeader (the header errors of
  * LINNEDecoder_DecodeWhole), finds the chain of blocks, checks every block's CRC16 and the checks lnn's block parser makes
  * after it, all on the device.  d_stream: the device bytes of a whole stream, at any alignment.  Synchronous; returns NULL and
- * *result = LINNEApiResult when it fails.  The index holds O(blocks) device memory; the stream's bytes stay the caller's and must
- * be passed again, unchanged, to every decode.
+ * *result = LINNEApiResult when it fails (a NULL result is tolerated; a NULL ctx or d_stream is INVALID_ARGUMENT and writes no
+ * text).  The call is the one-stream case of LINNEAmd_StreamIndexesCreate below, run by the same code: indexes[0] and results[0] of
+ * that call, GetLastError's text without "stream 0: " before it.  The index holds O(blocks) memory, one device and one host
+ * allocation freed by LINNEAmd_StreamIndexDestroy; building it uses scratch kept by the context, at the sizes stated there, and
+ * counts as a call of one stream in LINNEAmd_GetLastIndexBatchCount.  The stream's bytes stay the caller's and must be passed again,
+ * unchanged, to every decode.
  *
  * LINNEAmd_DecodeStreamDevice writes samples [first_sample, first_sample + num_samples) of every channel ch to
  * d_pcm[ch * pcm_stride + i], int32.  Enqueued on the context's stream and synchronous.  The result:
@@ -478,7 +482,7 @@ int LINNEAmd_StreamIndexFailure(const struct LINNEAmdStreamIndex *index, int64_t
  * launches of kind 41.  Scratch, kept by the context and grown (an allocation and a wait more) when a call needs more than any
  * before it: about 12 bytes per 4096 stream bytes, 8 + 4 K bytes per candidate, and 128 bytes per stream in a pinned host buffer and
  * its device copy.
- * LINNEAmd_GetLastIndexBatchCount: of the last such call, which = 0 the streams given, 1 the indexes built, 2 K, 3 its host
+ * LINNEAmd_GetLastIndexBatchCount: of the last such call (a LINNEAmd_StreamIndexCreate call is one, of one stream), which = 0 the streams given, 1 the indexes built, 2 K, 3 its host
  * synchronisations, 4 its device allocations; -1 for a NULL ctx or any other `which`. */
 int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes,
         uint32_t num_streams, struct LINNEAmdStreamIndex **indexes /* out [num_streams] */, int32_t *results /* out [num_streams] */);

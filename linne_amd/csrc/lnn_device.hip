@@ -1776,9 +1776,9 @@ struct LINNEAmdStreamIndex {
     int fail_code; uint64_t fail_off;
     uint64_t *h_off, *h_first; uint32_t *h_size, *h_type, *h_nsmp;           /* host copies */
     uint64_t *d_off, *d_first; uint32_t *d_size, *d_type, *d_nsmp; int32_t *d_status; SxTables *d_tab;
-    struct SxSlab *slab;                /* LINNEAmd_StreamIndexesCreate: the tables above are parts of the call's two allocations, freed with the last index of the call */
+    struct SxSlab *slab;                /* the tables above are parts of the call's two allocations, freed with the last index of the call */
 };
-/* what the indexes of one StreamIndexesCreate call share */
+/* what the indexes of one StreamIndexesCreate call share (a StreamIndexCreate call: its one index) */
 struct SxSlab { std::atomic<uint32_t> refs; int device; void *dev, *host; };
 static void sx_slab_release(SxSlab *s)
 {
@@ -1792,31 +1792,10 @@ static void sx_slab_release(SxSlab *s)
 extern "C" void LINNEAmd_StreamIndexDestroy(struct LINNEAmdStreamIndex *x)
 {
     if (!x) return;
-    if (x->slab) { sx_slab_release(x->slab); free(x); return; }
-    (void)hipSetDevice(x->device);
-    void *dev[] = { x->d_off, x->d_first, x->d_size, x->d_type, x->d_nsmp, x->d_status, x->d_tab };
-    for (void *p : dev) if (p) (void)hipFree(p);
-    free(x->h_off); free(x->h_first); free(x->h_size); free(x->h_type); free(x->h_nsmp);
+    if (x->slab) sx_slab_release(x->slab);                         /* (NULL: an index without tables yet, as ib_open leaves it) */
     free(x);
 }
 
-/* device allocations of one index build, freed when it returns (the stream is synchronised by then) */
-struct SxTemp {
-    void *p[8]; int n = 0;
-    ~SxTemp() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-static int sx_malloc(LINNEAmdContext *ctx, void **out, uint64_t bytes)
-{
-    *out = NULL;
-    HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 8u));
-    return LNN_OK;
-}
-static int sx_temp(LINNEAmdContext *ctx, SxTemp &t, void **out, uint64_t bytes)
-{
-    const int r = sx_malloc(ctx, out, bytes);
-    if (r == LNN_OK) t.p[t.n++] = *out;
-    return r;
-}
 /* device -> host, synchronous, behind the context's stream */
 static int sx_fetch(LINNEAmdContext *ctx, void *dst, const void *src, uint64_t bytes)
 {
@@ -1839,160 +1818,6 @@ static void sx_tables(SxTables *t)
             for (uint32_t i = 0; i < 16u; i++) if ((v >> i) & 1u) r ^= t->shift[k - 1][i];
             t->shift[k][j] = (uint16_t)r;
         }
-}
-
-/* the checks of lnn_parse_block_head before the CRC, for the place behind the chain's last block (no candidate is there) */
-static int sx_head_code(LINNEAmdContext *ctx, const uint8_t *d_stream, uint64_t N, uint64_t q)
-{
-    uint8_t h[6];
-    if (N - q < 11u) return LNN_INSUFFICIENT_DATA;
-    SX_TRY(sx_fetch(ctx, h, d_stream + q, 6));
-    if (h[0] != 0xFFu || h[1] != 0xFFu) return LNN_INVALID_FORMAT;
-    const uint32_t bsize = ((uint32_t)h[2] << 24) | ((uint32_t)h[3] << 16) | ((uint32_t)h[4] << 8) | h[5];
-    if ((uint64_t)bsize + 6u > N - q) return LNN_INSUFFICIENT_DATA;
-    if (bsize < 5u) return LNN_INVALID_FORMAT;
-    snprintf(ctx->err, sizeof(ctx->err), "internal: a block head at byte %llu the index did not find", (unsigned long long)q);
-    return LNN_NG;
-}
-
-static int sx_build(LINNEAmdContext *ctx, LINNEAmdStreamIndex *x, const uint8_t *b)
-{
-    const uint64_t N = x->stream_bytes, ns = x->header.num_samples;
-    SxTemp tmp;
-    SxTables h_tab;
-    sx_tables(&h_tab);
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_tab, sizeof(SxTables)));
-    HIPCHK(ctx, hipMemcpyAsync(x->d_tab, &h_tab, sizeof(SxTables), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));             /* (h_tab lives on this frame) */
-    /* candidates, in stream order */
-    uint64_t M = 0, *cand = NULL;
-    if (N > SX_FIRST_BLOCK) {
-        const uint64_t nw = (N - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
-        uint32_t *counts; uint64_t *cofs;
-        SX_TRY(sx_temp(ctx, tmp, (void **)&counts, sizeof(uint32_t) * nw));
-        SX_TRY(sx_temp(ctx, tmp, (void **)&cofs, sizeof(uint64_t) * (nw + 1u)));
-        SX_LAUNCH(LINNE_AMD_T_SX_COUNT, k_sx_count, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, counts);
-        SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nw, cofs);
-        SX_TRY(sx_fetch(ctx, &M, cofs + nw, sizeof(M)));
-        if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
-        if (M) {
-            SX_TRY(sx_temp(ctx, tmp, (void **)&cand, sizeof(uint64_t) * M));
-            SX_LAUNCH(LINNE_AMD_T_SX_WRITE, k_sx_write, dim3((uint32_t)((nw + 3u) / 4u)), dim3(256), 0, ctx->stream, b, N, nw, (const uint64_t *)cofs, cand);
-        }
-    }
-    uint64_t head = 0, nchain = 0;
-    if (M) SX_TRY(sx_fetch(ctx, &head, cand, sizeof(head)));
-    uint32_t K = 1, *jump = NULL;
-    if (M && head == SX_FIRST_BLOCK) {
-        /* the head's chain: successors, pointer doubling (2^K > M: K levels cover any chain), its length */
-        const uint32_t M32 = (uint32_t)M, g = (uint32_t)((M + 1u + 255u) / 256u);
-        while ((1ull << K) <= M) K++;
-        SX_TRY(sx_temp(ctx, tmp, (void **)&jump, sizeof(uint32_t) * (uint64_t)K * (M + 1u)));
-        SX_LAUNCH(LINNE_AMD_T_SX_SUCC, k_sx_succ, dim3(g), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, M32, jump);
-        for (uint32_t k = 1; k < K; k++)
-            SX_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
-        uint64_t *d_len;
-        SX_TRY(sx_temp(ctx, tmp, (void **)&d_len, sizeof(uint64_t)));
-        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN_LEN, k_sx_chain_len, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t *)jump, K, M32, d_len);
-        SX_TRY(sx_fetch(ctx, &nchain, d_len, sizeof(nchain)));
-        nchain++;
-    }
-    /* the chain's blocks and their first samples */
-    const uint64_t nc1 = nchain ? nchain : 1u;
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_off, sizeof(uint64_t) * nc1));
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_first, sizeof(uint64_t) * (nchain + 1u)));
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_size, sizeof(uint32_t) * nc1));
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_type, sizeof(uint32_t) * nc1));
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_nsmp, sizeof(uint32_t) * nc1));
-    SX_TRY(sx_malloc(ctx, (void **)&x->d_status, sizeof(int32_t) * nc1));
-    x->h_off = (uint64_t *)malloc(sizeof(uint64_t) * nc1); x->h_first = (uint64_t *)malloc(sizeof(uint64_t) * (nchain + 1u));
-    x->h_size = (uint32_t *)malloc(sizeof(uint32_t) * nc1); x->h_type = (uint32_t *)malloc(sizeof(uint32_t) * nc1); x->h_nsmp = (uint32_t *)malloc(sizeof(uint32_t) * nc1);
-    if (!x->h_off || !x->h_first || !x->h_size || !x->h_type || !x->h_nsmp) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-    x->h_first[0] = 0;
-    if (nchain) {
-        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_sx_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, b, (const uint64_t *)cand, (const uint32_t *)jump, K, (uint32_t)M,
-                (uint32_t)nchain, x->d_off, x->d_size, x->d_type, x->d_nsmp);
-        SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)x->d_nsmp, nchain, x->d_first);
-        HIPCHK(ctx, hipMemcpyAsync(x->h_off, x->d_off, sizeof(uint64_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(x->h_size, x->d_size, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(x->h_type, x->d_type, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(x->h_nsmp, x->d_nsmp, sizeof(uint32_t) * nchain, hipMemcpyDeviceToHost, ctx->stream));
-        SX_TRY(sx_fetch(ctx, x->h_first, x->d_first, sizeof(uint64_t) * (nchain + 1u)));
-    } else
-        HIPCHK(ctx, hipMemcpyAsync(x->d_first, x->h_first, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    /* DecodeWhole's loop ends once the samples reach the header's count (lnn_api.c:772) */
-    uint64_t nb = 0;
-    while (nb < nchain && x->h_first[nb] < ns) nb++;
-    x->nb = (uint32_t)nb; x->covered = x->h_first[nb];
-    x->fail_block = -1; x->fail_code = LNN_OK;
-    if (nb) {
-        SxCheckArgs a;
-        a.b = b; a.N = N; a.off = x->d_off; a.first = x->d_first; a.size = x->d_size; a.type = x->d_type; a.nsmp = x->d_nsmp;
-        a.nb = (uint32_t)nb; a.C = x->shape.num_channels; a.S = x->shape.num_samples_per_block; a.bits = x->shape.bits_per_sample; a.num_samples = ns;
-        a.tab = x->d_tab; a.status = x->d_status;
-        SX_LAUNCH(LINNE_AMD_T_SX_CHECK, k_sx_check, dim3((uint32_t)((nb + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
-        int32_t *st = (int32_t *)malloc(sizeof(int32_t) * nb);
-        if (!st) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
-        const int r = sx_fetch(ctx, st, x->d_status, sizeof(int32_t) * nb);
-        for (uint64_t i = 0; r == LNN_OK && i < nb; i++) if (st[i] != LNN_OK) { x->fail_block = (int64_t)i; x->fail_code = st[i]; x->fail_off = x->h_off[i]; break; }
-        free(st);
-        if (r != LNN_OK) return r;
-    }
-    if (x->fail_block < 0 && nb == nchain && x->covered < ns) {
-        /* the chain ends before the header's sample count: behind its last block lies the end of the stream (DecodeWhole stops
-         * there, the rest of its buffer untouched) or something that is no block head (DecodeWhole fails on it) */
-        const uint64_t q = nb ? x->h_off[nb - 1] + x->h_size[nb - 1] + 6u : SX_FIRST_BLOCK;
-        if (q < N) {
-            const int code = sx_head_code(ctx, b, N, q);
-            if (code == LNN_NG) return code;
-            x->fail_block = (int64_t)nb; x->fail_code = code; x->fail_off = q;
-        }
-    }
-    return LNN_OK;
-}
-
-extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAmdContext *ctx, const uint8_t *d_stream,
-        uint64_t stream_bytes, int *result)
-{
-    int dummy;
-    if (!result) result = &dummy;
-    if (!ctx || !d_stream) { *result = LNN_INVALID_ARGUMENT; return NULL; }
-    ctx->err[0] = 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "hipSetDevice(%d) failed", ctx->device); *result = LNN_NG; return NULL; }
-    /* the header as DecodeWhole reads it: LINNEDecoder_DecodeHeader, then SetHeader's checks on a decoder with room for it */
-    uint8_t hb[LINNE_HEADER_SIZE];
-    struct LINNEHeader h;
-    const uint64_t hn = stream_bytes < LINNE_HEADER_SIZE ? stream_bytes : LINNE_HEADER_SIZE;
-    int ret = sx_fetch(ctx, hb, d_stream, hn);
-    if (ret != LNN_OK) { *result = ret; return NULL; }
-    if ((ret = (int)LINNEDecoder_DecodeHeader(hb, (uint32_t)hn, &h)) != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "stream header: LINNEDecoder_DecodeHeader -> %d", ret); *result = ret; return NULL; }
-    {
-        struct LINNEDecoderConfig cfg;
-        memset(&cfg, 0, sizeof(cfg));
-        cfg.max_num_channels = h.num_channels ? h.num_channels : 1u; cfg.max_num_layers = LINNE_AMD_MAX_LAYERS; cfg.max_num_parameters_per_layer = 128; cfg.check_crc = 1;
-        struct LINNEDecoder *dec = LINNEDecoder_Create(&cfg, NULL, 0);
-        if (!dec) { snprintf(ctx->err, sizeof(ctx->err), "LINNEDecoder_Create failed"); *result = LNN_NG; return NULL; }
-        ret = (int)LINNEDecoder_SetHeader(dec, &h);
-        LINNEDecoder_Destroy(dec);
-        if (ret != LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "stream header: LINNEDecoder_SetHeader -> %d", ret); *result = ret; return NULL; }
-    }
-    LINNEAmdStreamIndex *x = (LINNEAmdStreamIndex *)calloc(1, sizeof(LINNEAmdStreamIndex));
-    if (!x) { *result = LNN_NG; return NULL; }
-    x->device = ctx->device; x->header = h; x->stream_bytes = stream_bytes;
-    x->shape = header_shape(&h);
-    HostShape hs;
-    if (shape_info(&x->shape, &hs) != LNN_OK) {
-        snprintf(ctx->err, sizeof(ctx->err), "stream header: a shape the device decoder does not take (%u bits, %u samples per block)", h.bits_per_sample, h.num_samples_per_block);
-        LINNEAmd_StreamIndexDestroy(x); *result = LNN_INVALID_FORMAT; return NULL;
-    }
-    ctx->nspans = 0;
-    if (ctx->timing) (void)hipEventRecord(ctx->ev[0], ctx->stream);
-    ret = sx_build(ctx, x, d_stream);
-    if (ret == LNN_OK && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
-    if (ret == LNN_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "index build: hipStreamSynchronize failed"); ret = LNN_NG; }
-    if (ret != LNN_OK) { (void)hipStreamSynchronize(ctx->stream); LINNEAmd_StreamIndexDestroy(x); *result = ret; return NULL; }
-    *result = LNN_OK;
-    return x;
 }
 
 extern "C" int LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *index, struct LINNEHeader *header)
@@ -2040,8 +1865,9 @@ extern "C" int64_t LINNEAmd_GetLastIndexBatchCount(struct LINNEAmdContext *ctx, 
     return ctx->ibatch_count[which];
 }
 
-/* the header part of LINNEAmd_StreamIndexCreate on header bytes that are on the host: *out = an index without tables, or NULL with the
- * single call's code and text; *whole_call: the failure is no answer about the stream (no host memory) and fails the call */
+/* a stream's header, on header bytes that are on the host, as DecodeWhole reads it: LINNEDecoder_DecodeHeader, then SetHeader's checks on
+ * a decoder with room for it.  *out = an index without tables, or NULL with the stream's code and text; *whole_call: the failure is no
+ * answer about the stream (no host memory) and fails the call */
 static int ib_open(int device, const uint8_t *hb, uint64_t stream_bytes, LINNEAmdStreamIndex **out, char *text, size_t cap, bool *whole_call)
 {
     struct LINNEHeader h;
@@ -2086,18 +1912,21 @@ static int ib_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t n
     return ensure_buf(ctx, ptr, cap, need);
 }
 
-/* LNN_OK: every stream has its index or its own code, the lowest-numbered failing stream's text is in ctx->err behind its number and
- * its code in *first_code; anything else fails the whole call, and the caller destroys what indexes[] holds by then */
-static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t T,
+/* LNN_OK: every stream has its index or its own code, the lowest-numbered failing stream's text is in ctx->err (behind its number
+ * unless the call is the single one) and its code in *first_code; anything else fails the whole call, and the caller destroys what
+ * indexes[] holds by then */
+static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t T, bool single,
         struct LINNEAmdStreamIndex **indexes, int32_t *results, SxSlab **slab_out, int *first_code)
 {
+    const char *who = single ? "StreamIndexCreate" : "StreamIndexesCreate";
     char text[sizeof(ctx->err)];
     int64_t first_fail = -1;
     auto fail_stream = [&](uint32_t i, int code, const char *why) {
         results[i] = code;
         if (first_fail < 0 || (int64_t)i < first_fail) {
             first_fail = (int64_t)i; *first_code = code;
-            snprintf(ctx->err, sizeof(ctx->err), "stream %u: %.*s", i, (int)sizeof(ctx->err) - 24, why);
+            if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", why);
+            else snprintf(ctx->err, sizeof(ctx->err), "stream %u: %.*s", i, (int)sizeof(ctx->err) - 24, why);
         }
     };
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2123,7 +1952,7 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
     const uint32_t gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
     ctx->nspans = 0;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    /* 1. the headers: one gather, one fetch; the host reads them as the single call does */
+    /* 1. the headers: one gather, one fetch */
     memset(h_st, 0, sizeof(IbStream) * (uint64_t)T);
     for (uint32_t i = 0; i < T; i++) { h_st[i].b = d_streams[i]; h_st[i].N = d_streams[i] ? stream_bytes[i] : 0u; }
     HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
@@ -2136,14 +1965,18 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
         if (!d_streams[i]) { fail_stream(i, LNN_INVALID_ARGUMENT, "null stream pointer"); continue; }
         bool whole_call;
         const int r = ib_open(ctx->device, h_hdr + (uint64_t)IB_HDR_SLOT * i, stream_bytes[i], &indexes[i], text, sizeof(text), &whole_call);
-        if (whole_call) { snprintf(ctx->err, sizeof(ctx->err), "StreamIndexesCreate: %.*s", (int)sizeof(ctx->err) - 32, text); return LNN_NG; }
+        if (whole_call) {                                         /* (the single call's texts are older than the batch call and stay as they were) */
+            if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
+            else snprintf(ctx->err, sizeof(ctx->err), "%s: %.*s", who, (int)sizeof(ctx->err) - 32, text);
+            return LNN_NG;
+        }
         if (r != LNN_OK) { fail_stream(i, r, text); h_st[i].b = NULL; h_st[i].N = 0; continue; }
         const LINNEAmdStreamIndex *x = indexes[i];
         h_st[i].num_samples = x->header.num_samples; h_st[i].C = x->shape.num_channels; h_st[i].S = x->shape.num_samples_per_block; h_st[i].bits = x->shape.bits_per_sample;
         if (stream_bytes[i] > SX_FIRST_BLOCK) nrows += (stream_bytes[i] - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
     }
     h_row0[T] = nrows;
-    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "StreamIndexesCreate: %llu stream bytes in one call: too many", (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
+    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu stream bytes in one call: too many", who, (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
     HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, o_crow - o_st, hipMemcpyHostToDevice, ctx->stream));      /* the streams and row0 */
     /* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back */
     const uint64_t o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
@@ -2231,7 +2064,7 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
         x->d_off = d_off + c0; x->d_first = d_first + c0 + i; x->d_size = d_size + c0; x->d_type = d_type + c0; x->d_nsmp = d_nsmp + c0; x->d_status = d_status + c0;
         x->h_off = (uint64_t *)(hp(s_off)) + c0; x->h_first = (uint64_t *)(hp(s_first)) + c0 + i;
         x->h_size = (uint32_t *)(hp(s_size)) + c0; x->h_type = (uint32_t *)(hp(s_type)) + c0; x->h_nsmp = (uint32_t *)(hp(s_nsmp)) + c0;
-        /* DecodeWhole's loop ends once the samples reach the header's count (sx_build) */
+        /* DecodeWhole's loop ends once the samples reach the header's count (lnn_api.c LINNEDecoder_DecodeWhole) */
         uint64_t nb = 0;
         while (nb < len && x->h_first[nb] < ns) nb++;
         x->nb = (uint32_t)nb; x->covered = x->h_first[nb];
@@ -2253,10 +2086,11 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
     return LNN_OK;
 }
 
-extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t num_streams,
-        struct LINNEAmdStreamIndex **indexes, int32_t *results)
+/* Both entry points behind their own first checks: the streams' indexes and results, then the call's -- the lowest-numbered failing
+ * stream's code, with its text in ctx->err (behind the stream's number unless the call is the single one) */
+static int ib_call(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t num_streams,
+        struct LINNEAmdStreamIndex **indexes, int32_t *results, bool single)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
     ctx->err[0] = 0;
     for (int i = 0; i < 5; i++) ctx->ibatch_count[i] = 0;
     if (num_streams == 0) return LNN_OK;
@@ -2265,7 +2099,7 @@ extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const u
     for (uint32_t i = 0; i < num_streams; i++) { indexes[i] = NULL; results[i] = LNN_OK; }
     SxSlab *slab = NULL;
     int first_code = LNN_OK;
-    const int ret = ib_build(ctx, d_streams, stream_bytes, num_streams, indexes, results, &slab, &first_code);
+    const int ret = ib_build(ctx, d_streams, stream_bytes, num_streams, single, indexes, results, &slab, &first_code);
     if (ret != LNN_OK) {
         /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
         (void)hipStreamSynchronize(ctx->stream);
@@ -2274,6 +2108,29 @@ extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const u
     }
     if (slab) sx_slab_release(slab);                               /* the call's own reference */
     return ret != LNN_OK ? LNN_NG : first_code;
+}
+
+extern "C" int LINNEAmd_StreamIndexesCreate(struct LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t num_streams,
+        struct LINNEAmdStreamIndex **indexes, int32_t *results)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    return ib_call(ctx, d_streams, stream_bytes, num_streams, indexes, results, false);
+}
+
+/* one stream: indexes[0] and results[0] of the call above */
+extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAmdContext *ctx, const uint8_t *d_stream,
+        uint64_t stream_bytes, int *result)
+{
+    int dummy;
+    if (!result) result = &dummy;
+    if (!ctx || !d_stream) { *result = LNN_INVALID_ARGUMENT; return NULL; }
+    ctx->err[0] = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "hipSetDevice(%d) failed", ctx->device); *result = LNN_NG; return NULL; }
+    struct LINNEAmdStreamIndex *x = NULL;
+    int32_t r = LNN_OK;
+    (void)ib_call(ctx, &d_stream, &stream_bytes, 1, &x, &r, true);
+    *result = r;
+    return x;
 }
 
 /* ================================================================================================

@@ -1,5 +1,19 @@
-/* lnn_k_index_batch.h -- the block indexes of many resident .lnn streams in one call (LINNEAmd_StreamIndexesCreate; DESIGN.md
- * section 5): the kernels of lnn_k_stream.h in segmented form, over all streams at once.
+/* lnn_k_index_batch.h -- the block indexes of the resident .lnn streams of one call, all streams at once (LINNEAmd_StreamIndexesCreate,
+ * and LINNEAmd_StreamIndexCreate as its one-stream case).
+ *
+ *   k_ib_headers              every stream's header bytes, gathered for the host
+ *   k_ib_count / k_ib_write   every position from the first block on that passes sx_candidate is a candidate; a wave scans 4096
+ *                             positions of one stream, counts, and after a scan of the counts (k_sx_scan, k_ib_seg) writes its
+ *                             candidates in stream order
+ *   k_ib_succ                 a candidate's successor: the candidate of its stream at position + size + 6 (binary search), or none
+ *   k_sx_jump                 pointer doubling: level k + 1 = level k applied twice
+ *   k_ib_chain_len, k_ib_chain  a stream's chain from its head (position 30) enumerated by its ranks: rank r is the head's
+ *                             successor taken r times, read off the levels by the bits of r.  A false candidate (FF FF inside a
+ *                             payload) is never the successor of a node the head reaches, so the chain never holds one
+ *   k_sx_scan, k_ib_first     the blocks' first samples
+ *   k_ib_check                a wave per block: CRC16 over lanes (partial CRCs shifted by the bytes behind them and XORed), then the
+ *                             checks lnn_parse_block_head makes after the CRC, in its order
+ *   k_ib_behind               what stands behind a chain that ends before the header's sample count
  *
  * Three prefix tables of T + 1 entries place a thread in its stream (ib_owner, a binary search):
  *   row0   the 4096-position waves of the streams before it (host: from the streams' lengths)
@@ -41,7 +55,7 @@ __global__ __launch_bounds__(256) void k_ib_headers(const IbStream *st, uint32_t
     out[t] = (b && j < SX_FIRST_BLOCK && j < st[i].N) ? b[j] : (uint8_t)0;
 }
 
-/* k_sx_count / k_sx_write over (stream, wave) rows */
+/* the candidates of (stream, wave) rows: counted, then written in stream order from the scan of the counts on */
 __global__ __launch_bounds__(256) void k_ib_count(const IbStream *st, const uint64_t *row0, uint32_t T, uint64_t nrows, uint32_t *counts)
 {
     const uint64_t w = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -94,7 +108,8 @@ __global__ __launch_bounds__(256) void k_ib_succ(const IbStream *st, const uint6
     succ[g] = (lo < end && cand[lo] == q) ? lo : M;
 }
 
-/* per stream: the blocks of the chain from its head, 0 where its first candidate is not at byte 30 (k_sx_chain_len + 1) */
+/* per stream: the blocks of the chain from its head (levels K - 1 .. 0, greedily: the steps to its end, and the head itself), 0 where
+ * its first candidate is not at byte 30 */
 __global__ __launch_bounds__(256) void k_ib_chain_len(const uint64_t *seg, uint32_t T, const uint64_t *cand, const uint32_t *jump, uint32_t K, uint32_t M, uint64_t *len)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -135,8 +150,10 @@ __global__ __launch_bounds__(256) void k_ib_first(const uint64_t *scan, const ui
     first[e] = scan[e - i] - scan[crow[i]];
 }
 
-/* k_sx_check over all streams' chains: a wave per chain block; only the blocks a whole decode walks (first sample below the
- * header's count) are looked at, the others read LNN_OK */
+/* A wave per chain block of the call (four per workgroup): the CRC, then what lnn_parse_block_head checks after it, in its order, with
+ * the consumption test DecodeWhole makes on RAW and SILENT blocks (a block whose payload is not what its size field says is one no
+ * encoder writes: LNN_NG).  status[g] = LNN_*; only the blocks a whole decode walks (first sample below the header's count) are looked
+ * at, the others read LNN_OK */
 struct IbCheckArgs {
     const IbStream *st; const uint64_t *crow; uint32_t T; uint64_t nchain;
     const uint64_t *off, *first; const uint32_t *size, *type, *nsmp;
@@ -173,7 +190,7 @@ __global__ __launch_bounds__(256) void k_ib_check(IbCheckArgs a)
             crc = (crc >> 8) ^ crc_t[(crc ^ b3) & 0xFFu];
         }
         for (; i < hi; i++) crc = (crc >> 8) ^ crc_t[(crc ^ q[i]) & 0xFFu];
-        uint64_t behind = len - hi;                                /* the lane's part followed by the bytes behind it (k_sx_check) */
+        uint64_t behind = len - hi;                                /* the CRC is linear (initial 0, no final XOR): the lane's part, then the bytes behind it */
         for (uint32_t k = 0; behind != 0u && k < SX_CRC_LEVELS; k++, behind >>= 1) if (behind & 1u) crc = sx_apply(shift_t[k], crc);
     }
     for (uint32_t m = 32; m >= 1u; m >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, (int)m, 64);

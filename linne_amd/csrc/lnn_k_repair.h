@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_rp_sound(RpSoundArgs a)
             crc = (crc >> 8) ^ crc_t[(crc ^ b3) & 0xFFu];
         }
         for (; i < hi; i++) crc = (crc >> 8) ^ crc_t[(crc ^ q[i]) & 0xFFu];
-        uint64_t behind = len - hi;                                /* the lane's part followed by the bytes behind it (k_sx_check) */
+        uint64_t behind = len - hi;                                /* the lane's part followed by the bytes behind it (k_ib_check) */
         for (uint32_t k = 0; behind != 0u && k < SX_CRC_LEVELS; k++, behind >>= 1) if (behind & 1u) crc = sx_apply(shift_t[k], crc);
     }
     for (uint32_t m = 32; m >= 1u; m >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, (int)m, 64);

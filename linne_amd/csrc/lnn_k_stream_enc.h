@@ -334,7 +334,7 @@ __global__ __launch_bounds__(SE_THREADS) void k_se_raw(SeBlockArgs a, const int3
 
 /* A wave per block (four per workgroup), after every other writer of the pass: the CRC16 over [p + 8, p + 6 + size) -- the type and
  * sample count, which this launch writes, taken from registers, the payload from memory -- from lane partials shifted by the bytes
- * behind them (k_sx_check), then the 11 header bytes: FF FF, size - 6, CRC, type, n (linne_encoder.c:806-855). */
+ * behind them (k_ib_check), then the 11 header bytes: FF FF, size - 6, CRC, type, n (linne_encoder.c:806-855). */
 __global__ __launch_bounds__(256) void k_se_crc(SeBlockArgs a)
 {
     __shared__ uint16_t crc_t[256];

@@ -1,94 +1,21 @@
-"""GPU tests of building the block indexes of many resident .lnn streams in one call (Context.index_streams; include/linne_amd.h
-LINNEAmd_StreamIndexesCreate).  Three yardsticks, none of them the new code: Context.index_stream on a private copy of each stream
-alone (header, num_blocks, the blocks() tables, failure()); the Python walk blocks(stream) for well-formed streams; and
-LINNEDecoder_DecodeWhole, whose code and PCM a whole decode and two inner ranges through the batch's indexes must give."""
+"""GPU tests of the block indexes of resident .lnn streams, many in one call (Context.index_streams; include/linne_amd.h
+LINNEAmd_StreamIndexesCreate) or one (Context.index_stream, LINNEAmd_StreamIndexCreate: the same code on one stream).  The yardsticks:
+index_cases.index_walk, a serial walk of the stream's bytes in plain Python that shares nothing with the device code and is itself
+held to LINNEDecoder_DecodeWhole (tests/test_stream_index_walk_cpu.py) -- code, header, num_blocks, the blocks() tables, failure() of
+both calls; the stream indexed alone on a private copy, which company in a call must not change; the walk blocks(stream) for
+well-formed streams; and LINNEDecoder_DecodeWhole, whose code and PCM a whole decode and two inner ranges through the indexes must
+give."""
 import numpy as np
 import pytest
 
 import linne_amd
-from test_gpu_stream_windows import SHAPES, blocks, crc16, mixed_signal, to_device
+from index_cases import SILENT_BLOCKS, build_corpus, index_walk
+from test_gpu_stream_windows import SHAPES, blocks, mixed_signal, to_device
 
 pytestmark = pytest.mark.gpu
 
 OK, INVALID_ARGUMENT, INVALID_FORMAT, INSUFFICIENT_DATA, CORRUPTION, NG = 0, 1, 2, 4, 6, 7
-RAW = 2
 INDEX_KINDS = tuple(range(37, 45)) + (69, 70)
-SILENT_BLOCKS = 1000
-
-
-class Case:
-    """one stream of the corpus: its bytes (None: a NULL pointer), whether an encoder wrote it as it is, and the yardsticks"""
-
-    def __init__(self, name, data, well_formed=False):
-        self.name, self.data, self.well_formed = name, data, well_formed
-
-
-def build_corpus(product):
-    from test_gpu_parity import many_block_lengths, stream_of_blocks
-    cases = []
-    base = []
-    for k in (0, 1, 3, 4, 5):                                       # five shapes at reduced length
-        nch, bits, block, preset, ms, _, seed = SHAPES[k]
-        ns = max(7 * block + 1000, 20000) + 37 * k
-        assert 20000 <= ns <= 60000
-        x = mixed_signal(nch, bits, ns, seed=seed, block=block)
-        s = product.encode_whole(x, bits, 44100, block, preset, ms)
-        base.append(s)
-        cases.append(Case(f"{nch}ch {bits}b {block} -m{preset}", s, True))
-    x, lens = many_block_lengths()
-    cases.append(Case("variable block lengths", stream_of_blocks(product, np.array(x, dtype=np.int32), 16, 44100, 4096, 7, True, lens), True))
-    # 1000 SILENT blocks of 11 bytes: heads at every residue of the 4096-position waves; the stream with the most candidates
-    silent = product.encode_whole(np.zeros((1, SILENT_BLOCKS * 256), dtype=np.int32), 16, 44100, 256, 0, False)
-    assert len(silent) == 30 + 11 * SILENT_BLOCKS
-    cases.append(Case("1000 silent blocks", silent, True))
-    s = base[1]                                                     # stereo 16-bit: the stream the damaged ones derive from
-    bl = blocks(s)
-    assert len(s) > 30 + 2 * 4096 + 11 and len(bl) >= 7
-    cases.append(Case("cut to the header", s[:30]))
-    for d in range(1, 12):
-        cases.append(Case(f"cut to 30 + {d}", s[:30 + d]))
-    for k in (1, 2):
-        for d in (-1, 0, 1, 10, 11):
-            cases.append(Case(f"cut to 30 + 4096 * {k} + {d}", s[:30 + 4096 * k + d]))
-    mid = len(bl) // 2
-    cases.append(Case("cut inside a block", s[:bl[mid][0] + bl[mid][1] // 2]))
-    cases.append(Case("trailing bytes", s + bytes(range(1, 18))))
-    for name, k in (("first", 0), ("middle", mid), ("last", len(bl) - 1)):
-        bad = bytearray(s)
-        bad[bl[k][0] + bl[k][1] - 2] ^= 0x10
-        cases.append(Case(f"CRC damage in the {name} block", bytes(bad)))
-    off = bl[mid][0]
-    for name, field in (("beyond the stream", (len(s)).to_bytes(4, "big")), ("below 5", (3).to_bytes(4, "big")),
-                        ("one less", (bl[mid][1] - 7).to_bytes(4, "big"))):
-        bad = bytearray(s)
-        bad[off + 2:off + 6] = field
-        cases.append(Case(f"size field {name}", bytes(bad)))
-    bad = bytearray(s)
-    bad[off] = 0x7F
-    cases.append(Case("sync word damaged", bytes(bad)))
-    # a false candidate: FF FF and a size inside a RAW payload, such that its "next block" is the real next block; CRC repaired
-    k = next(i for i, b in enumerate(bl[:-1]) if b[2] == RAW)
-    off, size = bl[k][:2]
-    p = off + 11 + 100
-    bad = bytearray(s)
-    bad[p:p + 2] = b"\xff\xff"
-    bad[p + 2:p + 6] = (bl[k + 1][0] - p - 6).to_bytes(4, "big")
-    bad[off + 6:off + 8] = crc16(bad[off + 8:off + size]).to_bytes(2, "big")
-    cases.append(Case("false candidate in a RAW payload", bytes(bad), True))
-    # adjacency: a stream that ends FF FF 00 00 00, and directly behind it the bytes that would complete the block head
-    sb = blocks(silent)
-    cut = sb[500][0] + 5
-    assert silent[cut - 5:cut] == b"\xff\xff\x00\x00\x00" and silent[cut] == 5
-    cases.append(Case("silent cut inside a block head", silent[:cut]))
-    cases.append(Case("the rest of that block head (no signature)", silent[cut:]))
-    cases.append(Case("fewer than 30 bytes", s[:29]))
-    bad = bytearray(s); bad[0] ^= 0xFF
-    cases.append(Case("bad signature", bytes(bad)))
-    bad = bytearray(s); bad[7] = 2
-    cases.append(Case("bad format version", bytes(bad)))
-    cases.append(Case("NULL pointer", None))
-    cases.append(Case("the first stream again", base[0], True))
-    return cases
 
 
 def index_facts(ix):
@@ -98,12 +25,14 @@ def index_facts(ix):
 
 @pytest.fixture(scope="module")
 def corpus(ctx, product):
-    """the cases with their yardsticks: .alone = (code, facts of index_stream on a private copy), .whole = DecodeWhole's (code, PCM)"""
+    """the cases with their yardsticks: .walk = index_walk's answer, .alone = (code, facts of index_stream on a private copy),
+    .whole = DecodeWhole's (code, PCM)"""
     cases = build_corpus(product)
     for c in cases:
         if c.data is None:
-            c.alone, c.whole, c.dev = (INVALID_ARGUMENT, None), None, None
+            c.walk, c.alone, c.whole, c.dev = None, (INVALID_ARGUMENT, None), None, None
             continue
+        c.walk = index_walk(c.data)
         c.dev = to_device(c.data)
         try:
             ix = ctx.index_stream(to_device(c.data))
@@ -150,6 +79,91 @@ def compare(ctx, cases, streams):
         if ix is not None:
             ix.close()
     return codes
+
+
+def walk_facts(c):
+    """index_facts as index_walk gives them"""
+    code, header, nb, tables, failure = c.walk
+    return (header, nb, len(c.data), tuple(tables), failure)
+
+
+def test_both_calls_equal_the_walk(ctx, corpus):
+    """for every case, index_stream and index_streams give what the serial walk of the bytes gives: the code, and where an index is
+    built its header, num_blocks, tables and failure triple"""
+    cases = [c for c in corpus if c.data is not None]
+    built, codes = ctx.index_streams([c.dev for c in cases], return_codes=True)
+    for c, ix, code in zip(cases, built, codes):
+        assert code == c.walk[0], c.name
+        assert (ix is None) == (code != OK), c.name
+        try:
+            one, one_code = ctx.index_stream(to_device(c.data)), OK
+        except linne_amd.LinneAmdError as e:
+            one, one_code = None, e.code
+        assert one_code == c.walk[0], c.name
+        if code != OK:
+            continue
+        assert index_facts(ix) == walk_facts(c), c.name
+        assert index_facts(one) == walk_facts(c), c.name
+        ix.close()
+        one.close()
+    assert sum(1 for c in cases if c.walk[0] == OK and c.walk[4][0] >= 0) >= 20      # damaged streams that still have an index
+    assert sum(1 for c in cases if c.walk[0] == OK and c.walk[2] == 0) >= 12         # ... and streams without a block
+
+
+def test_single_call_text_is_the_stream_text(ctx, corpus):
+    """raw calls: a header the single call refuses gives NULL, the code and the text it always gave; the batch call on that one
+    stream gives the code and "stream 0: " before the same text.  A NULL stream is the single call's INVALID_ARGUMENT, a NULL result
+    pointer is tolerated"""
+    import ctypes as C
+    lib = linne_amd.lib
+    by = {c.name: c for c in corpus}
+    want = {"fewer than 30 bytes": (INSUFFICIENT_DATA, "stream header: LINNEDecoder_DecodeHeader -> 4"),
+            "bad signature": (INVALID_FORMAT, "stream header: LINNEDecoder_DecodeHeader -> 2"),
+            "bad format version": (INVALID_FORMAT, "stream header: LINNEDecoder_SetHeader -> 2"),
+            "the rest of that block head (no signature)": (INVALID_FORMAT, "stream header: LINNEDecoder_DecodeHeader -> 2")}
+    for name, (code, text) in want.items():
+        dev = by[name].dev
+        res = C.c_int(-5)
+        h = lib.LINNEAmd_StreamIndexCreate(ctx.h, C.c_void_p(dev.data_ptr()), dev.numel(), C.byref(res))
+        assert not h and res.value == code, name
+        assert lib.LINNEAmd_GetLastError(ctx.h).decode() == text, name
+        assert not lib.LINNEAmd_StreamIndexCreate(ctx.h, C.c_void_p(dev.data_ptr()), dev.numel(), None), name      # NULL result: tolerated
+        ptrs, sizes = (C.c_void_p * 1)(dev.data_ptr()), (C.c_uint64 * 1)(dev.numel())
+        handles, codes = (C.c_void_p * 1)(0x77), (C.c_int32 * 1)(-5)
+        assert lib.LINNEAmd_StreamIndexesCreate(ctx.h, ptrs, sizes, 1, handles, codes) == code, name
+        assert not handles[0] and codes[0] == code, name
+        assert lib.LINNEAmd_GetLastError(ctx.h).decode() == "stream 0: " + text, name
+    good = by["1000 silent blocks"].dev
+    res = C.c_int(-5)
+    assert not lib.LINNEAmd_StreamIndexCreate(ctx.h, None, good.numel(), C.byref(res)) and res.value == INVALID_ARGUMENT
+    assert not lib.LINNEAmd_StreamIndexCreate(ctx.h, None, good.numel(), None)
+    assert not lib.LINNEAmd_StreamIndexCreate(None, C.c_void_p(good.data_ptr()), good.numel(), C.byref(res)) and res.value == INVALID_ARGUMENT
+    h = lib.LINNEAmd_StreamIndexCreate(ctx.h, C.c_void_p(good.data_ptr()), good.numel(), None)                      # NULL result, a sound stream
+    assert h and lib.LINNEAmd_StreamIndexNumBlocks(h) == SILENT_BLOCKS
+    lib.LINNEAmd_StreamIndexDestroy(h)
+
+
+def test_a_single_call_is_a_one_stream_call(corpus):
+    """scratch grown and timing on: the single call on the silent stream counts as a call of one stream, and launches what
+    index_streams([that stream]) launches"""
+    silent = next(c for c in corpus if c.name == "1000 silent blocks")
+    c = linne_amd.Context(0, use_torch_stream=False)
+    try:
+        c.enable_timing(True)
+        c.index_streams([silent.dev])[0].close()                  # (grows the context's scratch)
+        ix = c.index_streams([silent.dev])[0]
+        batch = {k: c.last_launches(k) for k in INDEX_KINDS}
+        assert [c.last_index_batch_count(w) for w in range(5)] == [1, 1, 10, 4, 1]
+        facts = index_facts(ix)
+        ix.close()
+        ix = c.index_stream(silent.dev)
+        assert [c.last_index_batch_count(w) for w in range(5)] == [1, 1, 10, 4, 1]
+        assert {k: c.last_launches(k) for k in INDEX_KINDS} == batch and all(v >= 1 for v in batch.values()), batch
+        assert c.last_ms(0) > 0
+        assert index_facts(ix) == facts == walk_facts(silent)
+        ix.close()
+    finally:
+        c.close()
 
 
 def test_corpus_is_what_it_says(corpus):

@@ -38,7 +38,7 @@ def median_ms(fn, reps):
 
 
 index = ctx.index_stream(d_stream)
-t_index, _ = median_ms(lambda: ctx.index_stream(d_stream).close(), args.reps)
+t_index, ts_index = median_ms(lambda: ctx.index_stream(d_stream).close(), args.reps)
 out = ctx.decode_stream(d_stream, index=index)
 ok_whole = bool(np.array_equal(out.cpu().numpy(), x))
 del out
@@ -54,7 +54,9 @@ ctx.enable_timing(True)
 ctx.decode_stream(d_stream, index=index)
 kinds = {k: round(ctx.last_ms(k), 3) for k in (56, 57, 28, 58, 32, 33, 34, 35, 36, 30, 31, 11, 12, 59) if ctx.last_launches(k) > 0}
 ctx.index_stream(d_stream).close()
-kinds_index = {k: round(ctx.last_ms(k), 3) for k in range(37, 45) if ctx.last_launches(k) > 0}
+INDEX_KINDS = tuple(range(37, 45)) + (69, 70)
+kinds_index = {k: round(ctx.last_ms(k), 3) for k in INDEX_KINDS if ctx.last_launches(k) > 0}
+launches_index = {k: ctx.last_launches(k) for k in INDEX_KINDS if ctx.last_launches(k) > 0}
 ctx.enable_timing(False)
 # DecodeWhole of the same bytes from host memory
 cfg = _RefDecoderConfig(nch, 5, 128, 1)
@@ -69,10 +71,11 @@ ok_dw = all(r == 0 for r in rets) and bool(np.array_equal(back, x))
 print(json.dumps({
     "config": f"{args.minutes:g} min 44.1 kHz int16 stereo, -m 7, block 10240 (BASELINE configs[1])", "stream_bytes": len(stream),
     "blocks": index.num_blocks, "reps": args.reps, "statistic": "median ms, warm-up excluded, each run ends in a device synchronise",
-    "index_stream_ms": round(t_index, 3), "decode_stream_whole_ms": round(t_whole, 3),
+    "index_stream_ms": round(t_index, 3), "index_stream_min_max_ms": [round(min(ts_index), 3), round(max(ts_index), 3)], "decode_stream_whole_ms": round(t_whole, 3),
     "decode_stream_window_ms": round(t_window, 3), "window": {"first_sample": first, "num_samples": win},
     "decode_whole_host_bytes_ms": round(t_dw, 3),
     "kernel_ms_whole_decode": {str(k): v for k, v in kinds.items()}, "kernel_ms_index": {str(k): v for k, v in kinds_index.items()},
+    "kernel_launches_index": {str(k): v for k, v in launches_index.items()},
     "exact": {"whole": ok_whole, "window": ok_window, "decode_whole": ok_dw},
 }))
 index.close()

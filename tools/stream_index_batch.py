@@ -3,8 +3,8 @@ device bytes, on one context: streams of 44.1 kHz, 16 bit, stereo, -m 7, MS, blo
 windows of one synthetic 60-minute signal.  Three sets, the shapes of tools/stream_batch_encode.py:
   a  256 five-second clips of 256 different lengths      b  64 three-minute tracks, each with its own tail      c  one 60-minute track
 Per set: median of --reps runs after a warm-up, minimum, maximum and the run-to-run spread (max - min) beside it, each run ending in
-a device synchronise; the timed region builds the indexes, closing them happens outside it (and is timed separately: a single-built
-index frees its seven device buffers one by one).  Records LINNEAmd_GetLastIndexBatchCount, the batch call's kernel times by kind,
+a device synchronise; the timed region builds the indexes, closing them happens outside it (and is timed separately: every index
+of either call is a part of its call's two allocations, which the last index of the call frees).  Records LINNEAmd_GetLastIndexBatchCount, the batch call's kernel times by kind,
 whether every batch index equals its single-call index, and the criterion: for a and b the batch median lies below the loop's by
 more than the larger spread; for c the batch is no slower than the single call beyond that spread.  Prints one JSON line
 (profiles/stream_index_batch.json holds the MI355X's)."""
