@@ -53,7 +53,8 @@
 #include "lnn_k_measure.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
-#include "lnn_k_splice.h"               /* (brings lnn_splice.h: the host's plan of a splice call) */
+#include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
+#include "lnn_k_splice.h"              /* (brings lnn_splice.h: the host's plan of a splice call) */
 #include "lnn_repair.h"                 /* the host's plan of a repair call */
 #include "lnn_k_repair.h"
 /* what lnn_forms.h knows of the kernels' tiling is the kernels' own */
@@ -112,19 +113,19 @@ struct LINNEAmdContext {
     int pcm16_next;                     /* the next EncodeFramesDevice call reads narrow samples: 1 int16, 2 packed 3-byte (set by the staging slots, cleared by the call) */
     int capture_on;                     /* LINNEAmd_SetSearchCapture: the encode calls leave what k_select decided from (tests; off: Plan.capture is NULL) */
     double *d_capture; uint64_t capture_cap, capture_n;      /* its records on the device: capacity, and those of the last call */
-    void *sdec; uint64_t sdec_cap;      /* scratch of DecodeStreamDevice: grows with the blocks of the range decoded */
+    void *sdec; uint64_t sdec_cap;      /* the windows calls: the buffers of one pass (wx_scratch).  The block-head scan (IbScan): its rows' counts and offsets */
     void *senc; uint64_t senc_cap;      /* scratch of EncodeStreamDevice: the buffers of one pass */
-    void *wdec; uint64_t wdec_cap;      /* DecodeWindowsDevice: fail words, window and block records of one call (its passes' buffers are sdec) */
-    void *wstage; uint64_t wstage_cap;  /* pinned: the same lists on the host, uploaded in one copy; the fail words come back into it */
+    void *wdec; uint64_t wdec_cap;      /* the windows calls: fail words, window and block records of one call.  The block-head scan: its lists (lnn_block_scan.h) */
+    void *wstage; uint64_t wstage_cap;  /* pinned: the same lists on the host, at the same offsets; what the device answers comes back into it */
     int64_t senc_count[4];              /* the last EncodeStreamDevice call: COMPRESS, SILENT, RAW blocks, host-settled Rice plans */
     int64_t sbatch_count[3];            /* the last EncodeStreamsDevice call: shape groups, passes, EncodeFramesDevice calls */
-    void *xcand; uint64_t xcand_cap;    /* StreamIndexesCreate: the candidates and pointer-doubling levels of one call (its rows' counts and offsets are sdec, its lists wdec / wstage) */
+    void *xcand; uint64_t xcand_cap;    /* behind the block-head scan, laid out by its caller: StreamIndexesCreate's candidates and pointer-doubling levels; RepairStreamsDevice's, with its sound candidates, chain blocks and run records */
     int64_t ibatch_count[5];            /* the last StreamIndexesCreate call: streams, indexes built, K, host synchronisations, device allocations */
     int span_keep;                      /* EncodeFramesDevice inside EncodeStream(s)Device: keep the call's spans and start event */
     double rice_guard;                  /* guard band of k_rice_plan (0: LNN_RICE_GUARD); set by EncodeStreamDevice's test knob */
     void *hstage; uint64_t hstage_cap;  /* device staging of the host-buffer forms (EncodeFramesHost / DecodeFramesHost: block-at-a-time calls), kept between calls */
-    void *spl; uint64_t spl_cap;        /* SpliceStreamsDevice: the fragments' PCM and scratch streams, then the run table and the headers of one call */
-    void *spl_stage; uint64_t spl_stage_cap;    /* pinned: the run table and the headers on the host, uploaded in one copy */
+    void *spl; uint64_t spl_cap;        /* SpliceStreamsDevice: the fragments' PCM and scratch streams, then the run table and the headers of one call.  RepairStreamsDevice: its run table and fill bytes */
+    void *spl_stage; uint64_t spl_stage_cap;    /* pinned: the run table and what lies behind it on the host, uploaded in one copy; RepairStreamsDevice fetches its run records into it first */
     int64_t splice_count[6];            /* the last SpliceStreamsDevice call: outputs written, copied blocks, re-encoded blocks, copy runs, bytes copied, its own host synchronisations */
     int outer_keep;                     /* DecodeWindowsDevice / EncodeStreamsDevice inside SpliceStreamsDevice: keep the call's spans and start event */
     int64_t repair_count[7];            /* the last RepairStreamsDevice call: outputs written, kept blocks, fill blocks, gaps, copy runs, host synchronisations, kernel launches */
@@ -407,13 +408,27 @@ extern "C" int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int w
     return cnt;
 }
 
-static int ensure_buf(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need)
+/* What a call counts of its own work, each in a slot of its *_count[]: waits for the stream, device allocations, kernel launches.
+ * A NULL slot, or no tally at all, counts nothing. */
+struct LnnTally { int64_t *waits, *allocs, *launches; };
+static inline void tally_launch(const LnnTally *t) { if (t && t->launches) ++*t->launches; }
+static int tally_wait(LINNEAmdContext *ctx, const LnnTally *t)
+{
+    if (t && t->waits) ++*t->waits;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LNN_OK;
+}
+
+/* a buffer of the context, device or pinned, that holds `need` bytes from here on: one that grows waits for the stream first */
+static int ensure_buf(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need, bool pinned = false, const LnnTally *t = NULL)
 {
     if (*cap >= need) return LNN_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (*ptr) HIPCHK(ctx, hipFree(*ptr));
+    if (t && t->allocs) ++*t->allocs;
+    const int ret = tally_wait(ctx, t);
+    if (ret != LNN_OK) return ret;
+    if (*ptr) HIPCHK(ctx, pinned ? hipHostFree(*ptr) : hipFree(*ptr));
     *ptr = NULL; *cap = 0;
-    HIPCHK(ctx, hipMalloc(ptr, need));
+    if (pinned) HIPCHK(ctx, hipHostMalloc(ptr, need, hipHostMallocDefault)); else HIPCHK(ctx, hipMalloc(ptr, need));
     *cap = need;
     return LNN_OK;
 }
@@ -1805,7 +1820,38 @@ static int sx_fetch(LINNEAmdContext *ctx, void *dst, const void *src, uint64_t b
     return LNN_OK;
 }
 #define SX_TRY(call) do { const int r_ = (call); if (r_ != LNN_OK) return r_; } while (0)
-#define SX_LAUNCH(kind, ...) do { const int sp_ = span_begin(ctx, (kind), ctx->stream); hipLaunchKernelGGL(__VA_ARGS__); span_end(ctx, sp_, ctx->stream); HIPCHK(ctx, hipGetLastError()); } while (0)
+/* a launch on the context's stream inside its span; tally: the calling call's (const LnnTally *, NULL for none) */
+#define SX_LAUNCH(tally, kind, ...) do { tally_launch(tally); const int sp_ = span_begin(ctx, (kind), ctx->stream); hipLaunchKernelGGL(__VA_ARGS__); span_end(ctx, sp_, ctx->stream); HIPCHK(ctx, hipGetLastError()); } while (0)
+
+/* ---- how the calls over many items (streams, windows, tracks, splices, repairs) end ---- */
+/* the body of such a call, which may run out of host memory */
+template <class Body> static int items_try(LINNEAmdContext *ctx, Body body)
+{
+    try { return body(); }
+    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
+}
+/* Behind the body and its `ret`: the end event if `record` (a body that fetches results behind its last launch records its own), the
+ * wait for whatever was enqueued if `wait` (it reads the context's buffers; counted in *waits), and behind a failure of the whole
+ * call every item marked.  who: the call's name in the texts of a failed wait and of a failure that left none (NULL: the body leaves
+ * one with every failure).  LNN_OK or LNN_NG */
+template <class Mark> static int items_end(LINNEAmdContext *ctx, const char *who, int ret, bool record, bool wait, int64_t *waits, uint32_t n, Mark mark_failed)
+{
+    if (record && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
+    if (wait) {
+        if (waits) ++*waits;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "%s: hipStreamSynchronize failed", who); ret = LNN_NG; }
+    }
+    if (ret == LNN_OK) return LNN_OK;
+    if (who && !ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "%s: failed with %d", who, ret);
+    for (uint32_t i = 0; i < n; i++) mark_failed(i);
+    return LNN_NG;
+}
+/* the text of the lowest-numbered failing item in ctx->err: behind its noun and number, bare where the call is the single one */
+static void items_first_text(LINNEAmdContext *ctx, const char *noun, uint32_t i, bool single, const char *text)
+{
+    if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
+    else snprintf(ctx->err, sizeof(ctx->err), "%s %u: %.*s", noun, i, (int)sizeof(ctx->err) - 24, text);
+}
 
 static void sx_tables(SxTables *t)
 {
@@ -1899,20 +1945,140 @@ static int ib_open(int device, const uint8_t *hb, uint64_t stream_bytes, LINNEAm
     return LNN_OK;
 }
 
-/* the call's waits and device allocations are counted (LINNEAmd_GetLastIndexBatchCount 3 and 4) */
-static int ib_sync(LINNEAmdContext *ctx)
+/* ---- the block-head scan of the T streams of one call: StreamIndexesCreate's, and RepairStreamsDevice's first half ----
+ * Its steps, in the caller's order: ib_scan_lists, ib_scan_headers, ib_scan_candidates; then, the caller's candidate buffers (xcand)
+ * being there, ib_scan_write, the caller's own successor pass, ib_scan_jumps, the caller's own chain lengths, ib_scan_chains.  The
+ * scan owns the lists (pinned wstage, device wdec: lnn_block_scan.h) and the rows' counts and offsets (sdec); waits, growing buffers
+ * and launches go to the caller's tally. */
+struct IbScan {
+    LINNEAmdContext *ctx; const char *who; bool bare;      /* the call's name in its texts; bare: a failure of the whole call inside ib_open keeps ib_open's text as it is */
+    uint32_t T; LnnTally tally;
+    IbLists at; uint8_t *hl, *dl;                           /* the lists on the host and on the device */
+    IbStream *h_st; uint64_t *h_row0, *h_crow, *h_seg, *h_len;
+    const IbStream *d_st; const uint64_t *d_row0, *d_crow; uint64_t *d_seg, *d_len;
+    uint64_t nrows, M, nchain; const uint64_t *cofs;       /* (stream, wave) rows and their candidates' offsets; candidates; chain blocks */
+    uint32_t K, M32, gT, gM, grow;                          /* pointer-doubling levels; the grids over streams, candidates, rows */
+};
+
+/* the lists with the caller's own parts, and the call's start: its spans and start event */
+static int ib_scan_lists(IbScan &s, LINNEAmdContext *ctx, const char *who, bool bare, uint32_t T, const LnnTally &tally, uint64_t early_bytes, uint64_t late_bytes)
 {
-    ctx->ibatch_count[3]++;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    s.ctx = ctx; s.who = who; s.bare = bare; s.T = T; s.tally = tally;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    s.at = ib_lists(T, sizeof(IbStream), IB_HDR_SLOT, early_bytes, late_bytes);
+    const LnnTally wait_only = { tally.waits, NULL, NULL };       /* (the pinned list is no device allocation) */
+    SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, s.at.bytes, true, &wait_only));
+    SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, s.at.bytes, false, &s.tally));
+    uint8_t *hl = s.hl = (uint8_t *)ctx->wstage, *dl = s.dl = (uint8_t *)ctx->wdec;
+    s.h_st = (IbStream *)(hl + s.at.o_st); s.d_st = (const IbStream *)(dl + s.at.o_st);
+    s.h_row0 = (uint64_t *)(hl + s.at.o_row0); s.d_row0 = (const uint64_t *)(dl + s.at.o_row0);
+    s.h_crow = (uint64_t *)(hl + s.at.o_crow); s.d_crow = (const uint64_t *)(dl + s.at.o_crow);
+    s.h_seg = (uint64_t *)(hl + s.at.o_seg); s.d_seg = (uint64_t *)(dl + s.at.o_seg);
+    s.h_len = (uint64_t *)(hl + s.at.o_len); s.d_len = (uint64_t *)(dl + s.at.o_len);
+    s.gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
+    s.nrows = s.M = s.nchain = 0; s.cofs = NULL; s.K = s.M32 = s.gM = s.grow = 0;
+    ctx->nspans = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     return LNN_OK;
 }
-static int ib_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need)
+
+/* 1. the headers: one gather, one fetch, one wait; then the host reads them as DecodeWhole does (ib_open), and the streams, row0 and
+ * the caller's early part go up.  bytes_of(i, &N): stream i's bytes, or NULL for a stream the caller has refused already.
+ * opened(i, code, text, x): what ib_open says of stream i -- x an index without tables that is the caller's from here on (the stream's
+ * record h_st[i] is filled in by then), or NULL with the stream's code and text. */
+template <class BytesOf, class Opened> static int ib_scan_headers(IbScan &s, BytesOf bytes_of, Opened opened)
 {
-    if (*cap < need) { ctx->ibatch_count[3]++; ctx->ibatch_count[4]++; }      /* (a buffer that grows waits for the stream first) */
-    return ensure_buf(ctx, ptr, cap, need);
+    LINNEAmdContext *ctx = s.ctx;
+    const uint32_t T = s.T;
+    const LnnTally *tl = &s.tally;
+    char text[sizeof(ctx->err)];
+    memset(s.h_st, 0, sizeof(IbStream) * (uint64_t)T);
+    for (uint32_t i = 0; i < T; i++) { uint64_t N = 0; s.h_st[i].b = bytes_of(i, &N); s.h_st[i].N = s.h_st[i].b ? N : 0u; }
+    HIPCHK(ctx, hipMemcpyAsync(s.dl + s.at.o_st, s.hl + s.at.o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
+    SX_LAUNCH(tl, LINNE_AMD_T_IB_HEADERS, k_ib_headers, dim3((uint32_t)(((uint64_t)T * IB_HDR_SLOT + 255u) / 256u)), dim3(256), 0, ctx->stream, s.d_st, T, s.dl + s.at.o_hdr);
+    HIPCHK(ctx, hipMemcpyAsync(s.hl + s.at.o_hdr, s.dl + s.at.o_hdr, (uint64_t)IB_HDR_SLOT * T, hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(tally_wait(ctx, tl));
+    uint64_t nrows = 0;
+    for (uint32_t i = 0; i < T; i++) {
+        IbStream &st = s.h_st[i];
+        s.h_row0[i] = nrows;
+        if (!st.b) continue;
+        LINNEAmdStreamIndex *x = NULL;
+        bool whole_call;
+        const uint64_t N = st.N;
+        const int r = ib_open(ctx->device, s.hl + s.at.o_hdr + (uint64_t)IB_HDR_SLOT * i, N, &x, text, sizeof(text), &whole_call);
+        if (whole_call) {                                         /* (the single call's texts are older than the batch call and stay as they were) */
+            if (s.bare) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
+            else snprintf(ctx->err, sizeof(ctx->err), "%s: %.*s", s.who, (int)sizeof(ctx->err) - 32, text);
+            return LNN_NG;
+        }
+        if (r != LNN_OK) { st.b = NULL; st.N = 0; opened(i, r, text, (LINNEAmdStreamIndex *)NULL); continue; }
+        st.num_samples = x->header.num_samples; st.C = x->shape.num_channels; st.S = x->shape.num_samples_per_block; st.bits = x->shape.bits_per_sample;
+        opened(i, LNN_OK, text, x);
+        if (N > SX_FIRST_BLOCK) nrows += (N - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
+    }
+    s.h_row0[T] = s.nrows = nrows;
+    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu stream bytes in one call: too many", s.who, (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
+    HIPCHK(ctx, hipMemcpyAsync(s.dl + s.at.o_st, s.hl + s.at.o_st, s.at.o_crow - s.at.o_st, hipMemcpyHostToDevice, ctx->stream));
+    return LNN_OK;
 }
 
-/* LNN_OK: every stream has its index or its own code, the lowest-numbered failing stream's text is in ctx->err (behind its number
+/* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back behind one wait, and with
+ * them M, and K with 2^K > the longest segment: K levels of pointer doubling cover any chain */
+static int ib_scan_candidates(IbScan &s)
+{
+    LINNEAmdContext *ctx = s.ctx;
+    const uint32_t T = s.T;
+    const LnnTally *tl = &s.tally;
+    const uint64_t nrows = s.nrows, o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, align_up(o_cofs + sizeof(uint64_t) * (nrows + 1u)), false, tl));
+    uint32_t *counts = (uint32_t *)((uint8_t *)ctx->sdec + o_counts);
+    uint64_t *cofs = (uint64_t *)((uint8_t *)ctx->sdec + o_cofs);
+    s.cofs = cofs; s.grow = (uint32_t)((nrows + 3u) / 4u);
+    if (nrows) SX_LAUNCH(tl, LINNE_AMD_T_SX_COUNT, k_ib_count, dim3(s.grow), dim3(256), 0, ctx->stream, s.d_st, s.d_row0, T, nrows, counts);
+    SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nrows, cofs);
+    SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(s.gT), dim3(256), 0, ctx->stream, (const uint64_t *)cofs, s.d_row0, T, s.d_seg);
+    HIPCHK(ctx, hipMemcpyAsync(s.h_seg, s.d_seg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(tally_wait(ctx, tl));
+    const uint64_t M = s.h_seg[T];
+    if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
+    uint64_t Mmax = 0;
+    for (uint32_t i = 0; i < T; i++) if (s.h_seg[i + 1] - s.h_seg[i] > Mmax) Mmax = s.h_seg[i + 1] - s.h_seg[i];
+    uint32_t K = 1;
+    while ((1ull << K) <= Mmax) K++;
+    s.M = M; s.K = K; s.M32 = (uint32_t)M; s.gM = (uint32_t)((M + 1u + 255u) / 256u);
+    return LNN_OK;
+}
+
+/* 3. the candidates' positions into cand (M + 1 entries); the levels of jump (K of M + 1 entries) above the caller's level 0; the
+ * chains' lengths, which the caller's pass has left in d_len, come back behind one wait: crow = their prefix sums, nchain their sum */
+static int ib_scan_write(IbScan &s, uint64_t *cand)
+{
+    LINNEAmdContext *ctx = s.ctx;
+    SX_LAUNCH(&s.tally, LINNE_AMD_T_SX_WRITE, k_ib_write, dim3(s.grow), dim3(256), 0, ctx->stream, s.d_st, s.d_row0, s.T, s.nrows, s.cofs, cand);
+    return LNN_OK;
+}
+static int ib_scan_jumps(IbScan &s, uint32_t *jump)
+{
+    LINNEAmdContext *ctx = s.ctx;
+    for (uint32_t k = 1; k < s.K; k++)
+        SX_LAUNCH(&s.tally, LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(s.gM), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (s.M + 1u)), jump + (uint64_t)k * (s.M + 1u), s.M32);
+    return LNN_OK;
+}
+static int ib_scan_chains(IbScan &s)
+{
+    LINNEAmdContext *ctx = s.ctx;
+    HIPCHK(ctx, hipMemcpyAsync(s.h_len, s.d_len, sizeof(uint64_t) * (uint64_t)s.T, hipMemcpyDeviceToHost, ctx->stream));
+    SX_TRY(tally_wait(ctx, &s.tally));
+    uint64_t nchain = 0;
+    for (uint32_t i = 0; i < s.T; i++) { s.h_crow[i] = nchain; nchain += s.h_len[i]; }
+    s.h_crow[s.T] = s.nchain = nchain;
+    return LNN_OK;
+}
+
+/* The block-head scan (IbScan), then the index's own: successors, chains, first samples, checks and the slab of tables; the call's
+ * waits and device allocations are counted (LINNEAmd_GetLastIndexBatchCount 3 and 4).
+ * LNN_OK: every stream has its index or its own code, the lowest-numbered failing stream's text is in ctx->err (behind its number
  * unless the call is the single one) and its code in *first_code; anything else fails the whole call, and the caller destroys what
  * indexes[] holds by then */
 static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const uint64_t *stream_bytes, uint32_t T, bool single,
@@ -1925,96 +2091,37 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
         results[i] = code;
         if (first_fail < 0 || (int64_t)i < first_fail) {
             first_fail = (int64_t)i; *first_code = code;
-            if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", why);
-            else snprintf(ctx->err, sizeof(ctx->err), "stream %u: %.*s", i, (int)sizeof(ctx->err) - 24, why);
+            items_first_text(ctx, "stream", i, single, why);
         }
     };
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    /* the lists of the call, pinned on the host and at the same offsets on the device */
-    const uint64_t o_st = 0, o_row0 = align_up(o_st + sizeof(IbStream) * (uint64_t)T), o_crow = align_up(o_row0 + sizeof(uint64_t) * (T + 1ull)),
-            o_tab = align_up(o_crow + sizeof(uint64_t) * (T + 1ull)), o_hdr = align_up(o_tab + sizeof(SxTables)), o_seg = align_up(o_hdr + (uint64_t)IB_HDR_SLOT * T),
-            o_len = align_up(o_seg + sizeof(uint64_t) * (T + 1ull)), list_bytes = align_up(o_len + sizeof(uint64_t) * (uint64_t)T);
-    if (ctx->wstage_cap < list_bytes) {
-        SX_TRY(ib_sync(ctx));
-        if (ctx->wstage) HIPCHK(ctx, hipHostFree(ctx->wstage));
-        ctx->wstage = NULL; ctx->wstage_cap = 0;
-        HIPCHK(ctx, hipHostMalloc(&ctx->wstage, list_bytes, hipHostMallocDefault));
-        ctx->wstage_cap = list_bytes;
-    }
-    SX_TRY(ib_ensure(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
-    uint8_t *hl = (uint8_t *)ctx->wstage, *dl = (uint8_t *)ctx->wdec;
-    IbStream *h_st = (IbStream *)(hl + o_st);
-    uint64_t *h_row0 = (uint64_t *)(hl + o_row0), *h_crow = (uint64_t *)(hl + o_crow), *h_seg = (uint64_t *)(hl + o_seg), *h_len = (uint64_t *)(hl + o_len);
-    const uint8_t *h_hdr = hl + o_hdr;
-    const IbStream *d_st = (const IbStream *)(dl + o_st);
-    const uint64_t *d_row0 = (const uint64_t *)(dl + o_row0), *d_crow = (const uint64_t *)(dl + o_crow);
-    uint64_t *d_seg = (uint64_t *)(dl + o_seg), *d_len = (uint64_t *)(dl + o_len);
-    const uint32_t gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
-    ctx->nspans = 0;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    /* 1. the headers: one gather, one fetch */
-    memset(h_st, 0, sizeof(IbStream) * (uint64_t)T);
-    for (uint32_t i = 0; i < T; i++) { h_st[i].b = d_streams[i]; h_st[i].N = d_streams[i] ? stream_bytes[i] : 0u; }
-    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
-    SX_LAUNCH(LINNE_AMD_T_IB_HEADERS, k_ib_headers, dim3((uint32_t)(((uint64_t)T * IB_HDR_SLOT + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, T, dl + o_hdr);
-    HIPCHK(ctx, hipMemcpyAsync(hl + o_hdr, dl + o_hdr, (uint64_t)IB_HDR_SLOT * T, hipMemcpyDeviceToHost, ctx->stream));
-    SX_TRY(ib_sync(ctx));
-    uint64_t nrows = 0;
-    for (uint32_t i = 0; i < T; i++) {
-        h_row0[i] = nrows;
-        if (!d_streams[i]) { fail_stream(i, LNN_INVALID_ARGUMENT, "null stream pointer"); continue; }
-        bool whole_call;
-        const int r = ib_open(ctx->device, h_hdr + (uint64_t)IB_HDR_SLOT * i, stream_bytes[i], &indexes[i], text, sizeof(text), &whole_call);
-        if (whole_call) {                                         /* (the single call's texts are older than the batch call and stay as they were) */
-            if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
-            else snprintf(ctx->err, sizeof(ctx->err), "%s: %.*s", who, (int)sizeof(ctx->err) - 32, text);
-            return LNN_NG;
-        }
-        if (r != LNN_OK) { fail_stream(i, r, text); h_st[i].b = NULL; h_st[i].N = 0; continue; }
-        const LINNEAmdStreamIndex *x = indexes[i];
-        h_st[i].num_samples = x->header.num_samples; h_st[i].C = x->shape.num_channels; h_st[i].S = x->shape.num_samples_per_block; h_st[i].bits = x->shape.bits_per_sample;
-        if (stream_bytes[i] > SX_FIRST_BLOCK) nrows += (stream_bytes[i] - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
-    }
-    h_row0[T] = nrows;
-    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu stream bytes in one call: too many", who, (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
-    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, o_crow - o_st, hipMemcpyHostToDevice, ctx->stream));      /* the streams and row0 */
-    /* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back */
-    const uint64_t o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
-    SX_TRY(ib_ensure(ctx, &ctx->sdec, &ctx->sdec_cap, align_up(o_cofs + sizeof(uint64_t) * (nrows + 1u))));
-    uint32_t *counts = (uint32_t *)((uint8_t *)ctx->sdec + o_counts);
-    uint64_t *cofs = (uint64_t *)((uint8_t *)ctx->sdec + o_cofs);
-    const uint32_t grow = (uint32_t)((nrows + 3u) / 4u);
-    if (nrows) SX_LAUNCH(LINNE_AMD_T_SX_COUNT, k_ib_count, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, counts);
-    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nrows, cofs);
-    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)cofs, d_row0, T, d_seg);
-    HIPCHK(ctx, hipMemcpyAsync(h_seg, d_seg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
-    SX_TRY(ib_sync(ctx));
-    const uint64_t M = h_seg[T];
-    if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
-    uint64_t Mmax = 0;
-    for (uint32_t i = 0; i < T; i++) if (h_seg[i + 1] - h_seg[i] > Mmax) Mmax = h_seg[i + 1] - h_seg[i];
-    uint32_t K = 1;
-    while ((1ull << K) <= Mmax) K++;                              /* 2^K > the longest segment: K levels cover any chain */
+    /* 1. 2. the scan (the tables wait in its lists' late part for the slab); an opened stream's index is the stream's from here on */
+    const LnnTally tally = { &ctx->ibatch_count[3], &ctx->ibatch_count[4], NULL }, *tl = &tally;
+    IbScan s;
+    SX_TRY(ib_scan_lists(s, ctx, who, single, T, tally, 0, sizeof(SxTables)));
+    SX_TRY(ib_scan_headers(s,
+            [&](uint32_t i, uint64_t *N) { if (!d_streams[i]) fail_stream(i, LNN_INVALID_ARGUMENT, "null stream pointer"); *N = stream_bytes[i]; return d_streams[i]; },
+            [&](uint32_t i, int code, const char *why, LINNEAmdStreamIndex *x) { if (x) indexes[i] = x; else fail_stream(i, code, why); }));
+    SX_TRY(ib_scan_candidates(s));
+    const uint32_t K = s.K, M32 = s.M32, gT = s.gT;
+    const uint64_t M = s.M, o_tab = s.at.o_late;
+    uint8_t *hl = s.hl;
+    const IbStream *d_st = s.d_st;
+    const uint64_t *d_crow = s.d_crow, *d_seg = s.d_seg, *h_crow = s.h_crow, *h_len = s.h_len;
     ctx->ibatch_count[2] = K;
     /* 3. successors inside the segments, pointer doubling over the global array, the chains' lengths.  cand has M + 1 entries: the
      * scan of the chains' sample counts takes its place once the chains are read (no more chain blocks than candidates) */
     const uint64_t o_cand = 0, o_jump = align_up(sizeof(uint64_t) * (M + 1u));
-    SX_TRY(ib_ensure(ctx, &ctx->xcand, &ctx->xcand_cap, align_up(o_jump + sizeof(uint32_t) * (uint64_t)K * (M + 1u))));
+    SX_TRY(ensure_buf(ctx, &ctx->xcand, &ctx->xcand_cap, align_up(o_jump + sizeof(uint32_t) * (uint64_t)K * (M + 1u)), false, tl));
     uint64_t *cand = (uint64_t *)((uint8_t *)ctx->xcand + o_cand);
     uint32_t *jump = (uint32_t *)((uint8_t *)ctx->xcand + o_jump);
-    const uint32_t M32 = (uint32_t)M, gM = (uint32_t)((M + 1u + 255u) / 256u);
     if (M) {
-        SX_LAUNCH(LINNE_AMD_T_SX_WRITE, k_ib_write, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, (const uint64_t *)cofs, cand);
-        SX_LAUNCH(LINNE_AMD_T_SX_SUCC, k_ib_succ, dim3(gM), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_seg, T, (const uint64_t *)cand, M32, jump);
-        for (uint32_t k = 1; k < K; k++)
-            SX_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
+        SX_TRY(ib_scan_write(s, cand));
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SUCC, k_ib_succ, dim3(s.gM), dim3(256), 0, ctx->stream, d_st, d_seg, T, (const uint64_t *)cand, M32, jump);
+        SX_TRY(ib_scan_jumps(s, jump));
     }
-    SX_LAUNCH(LINNE_AMD_T_SX_CHAIN_LEN, k_ib_chain_len, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)d_seg, T, (const uint64_t *)cand, (const uint32_t *)jump, K, M32, d_len);
-    HIPCHK(ctx, hipMemcpyAsync(h_len, d_len, sizeof(uint64_t) * (uint64_t)T, hipMemcpyDeviceToHost, ctx->stream));
-    SX_TRY(ib_sync(ctx));
-    uint64_t nchain = 0;
-    for (uint32_t i = 0; i < T; i++) { h_crow[i] = nchain; nchain += h_len[i]; }
-    h_crow[T] = nchain;
+    SX_LAUNCH(tl, LINNE_AMD_T_SX_CHAIN_LEN, k_ib_chain_len, dim3(gT), dim3(256), 0, ctx->stream, d_seg, T, (const uint64_t *)cand, (const uint32_t *)jump, K, M32, s.d_len);
+    SX_TRY(ib_scan_chains(s));
+    const uint64_t nchain = s.nchain;
     /* 4. the tables of all indexes: one device allocation (the CRC and Huffman tables first) and one on the host, laid out alike from
      * `off` on: off | first (a stream's len + 1 entries from crow[i] + i on) | size | type | nsmp | status | behind */
     const uint64_t nfirst = nchain + T, s_off = align_up(sizeof(SxTables)), s_first = s_off + sizeof(uint64_t) * (nchain + 1u), s_size = s_first + sizeof(uint64_t) * (nfirst + 1u),
@@ -2035,25 +2142,25 @@ static int ib_build(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const
     int32_t *d_status = (int32_t *)(ds + s_status), *d_behind = (int32_t *)(ds + s_behind);
     sx_tables((SxTables *)(hl + o_tab));
     HIPCHK(ctx, hipMemcpyAsync(ds, hl + o_tab, sizeof(SxTables), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dl + o_crow, hl + o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s.dl + s.at.o_crow, hl + s.at.o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
     if (nchain) {
-        SX_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_seg, d_crow, T, (const uint64_t *)cand,
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, d_seg, d_crow, T, (const uint64_t *)cand,
                 (const uint32_t *)jump, K, M32, nchain, d_off, d_size, d_type, d_nsmp);
     }
     uint64_t *scan = cand;                                         /* (the candidates are read: see 3.) */
-    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_nsmp, nchain, scan);
-    SX_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_first, dim3((uint32_t)((nfirst + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint64_t *)scan, d_crow, T, nfirst, d_first);
+    SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_nsmp, nchain, scan);
+    SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_ib_first, dim3((uint32_t)((nfirst + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint64_t *)scan, d_crow, T, nfirst, d_first);
     if (nchain) {
         IbCheckArgs a;
         a.st = d_st; a.crow = d_crow; a.T = T; a.nchain = nchain; a.off = d_off; a.first = d_first; a.size = d_size; a.type = d_type; a.nsmp = d_nsmp;
         a.tab = (const SxTables *)ds; a.status = d_status;
-        SX_LAUNCH(LINNE_AMD_T_SX_CHECK, k_ib_check, dim3((uint32_t)((nchain + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_CHECK, k_ib_check, dim3((uint32_t)((nchain + 3u) / 4u)), dim3(256), 0, ctx->stream, a);
     }
-    SX_LAUNCH(LINNE_AMD_T_IB_BEHIND, k_ib_behind, dim3(gT), dim3(256), 0, ctx->stream, d_st, d_crow, T, (const uint64_t *)d_off, (const uint32_t *)d_size, (const uint64_t *)d_first, d_behind);
+    SX_LAUNCH(tl, LINNE_AMD_T_IB_BEHIND, k_ib_behind, dim3(gT), dim3(256), 0, ctx->stream, d_st, d_crow, T, (const uint64_t *)d_off, (const uint32_t *)d_size, (const uint64_t *)d_first, d_behind);
     /* 5. everything comes back in one copy behind the call's last wait */
     HIPCHK(ctx, hipMemcpyAsync(slab->host, ds + s_off, s_end - s_off, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
-    SX_TRY(ib_sync(ctx));
+    SX_TRY(tally_wait(ctx, tl));
     const int32_t *h_status = (const int32_t *)(hp(s_status)), *h_behind = (const int32_t *)(hp(s_behind));
     for (uint32_t i = 0; i < T; i++) {
         LINNEAmdStreamIndex *x = indexes[i];
@@ -2099,13 +2206,10 @@ static int ib_call(LINNEAmdContext *ctx, const uint8_t *const *d_streams, const 
     for (uint32_t i = 0; i < num_streams; i++) { indexes[i] = NULL; results[i] = LNN_OK; }
     SxSlab *slab = NULL;
     int first_code = LNN_OK;
-    const int ret = ib_build(ctx, d_streams, stream_bytes, num_streams, single, indexes, results, &slab, &first_code);
-    if (ret != LNN_OK) {
-        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
-        (void)hipStreamSynchronize(ctx->stream);
-        for (uint32_t i = 0; i < num_streams; i++) { LINNEAmd_StreamIndexDestroy(indexes[i]); indexes[i] = NULL; results[i] = LNN_NG; }
-        ctx->ibatch_count[1] = 0;
-    }
+    int ret = ib_build(ctx, d_streams, stream_bytes, num_streams, single, indexes, results, &slab, &first_code);
+    /* a HIP error, no memory: the whole call fails (ib_build has waited and recorded where it did not) */
+    ret = items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, num_streams, [&](uint32_t i) { LINNEAmd_StreamIndexDestroy(indexes[i]); indexes[i] = NULL; results[i] = LNN_NG; });
+    if (ret != LNN_OK) ctx->ibatch_count[1] = 0;
     if (slab) sx_slab_release(slab);                               /* the call's own reference */
     return ret != LNN_OK ? LNN_NG : first_code;
 }
@@ -2240,13 +2344,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     const uint64_t o_fail = 0, o_diff = 2u * sizeof(uint32_t) * (uint64_t)W, back_bytes = o_diff + (compare ? 2u * sizeof(uint64_t) * (uint64_t)W : 0u);
     const uint64_t o_win = align_up(back_bytes), o_mwin = align_up(o_win + sizeof(WxWindow) * nlive), o_rec = align_up(o_mwin + (measure ? sizeof(WxMeasure) * nlive : 0u)),
             o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
-    if (ctx->wstage_cap < list_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->wstage) HIPCHK(ctx, hipHostFree(ctx->wstage));
-        ctx->wstage = NULL; ctx->wstage_cap = 0;
-        HIPCHK(ctx, hipHostMalloc(&ctx->wstage, list_bytes, hipHostMallocDefault));
-        ctx->wstage_cap = list_bytes;
-    }
+    SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, list_bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + o_fail), *h_crec = (uint32_t *)(hs_ + o_crec);
     WxWindow *h_win = (WxWindow *)(hs_ + o_win);
@@ -2341,7 +2439,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     /* 4. the passes */
     const uint64_t ga_ = (nacc + WXM_THREADS - 1u) / WXM_THREADS, go_ = (nout + WXM_THREADS - 1u) / WXM_THREADS;    /* (grid-stride kernels) */
     const uint32_t mgrid_acc = (uint32_t)(ga_ < 65536u ? ga_ : 65536u), mgrid_out = (uint32_t)(go_ < 65536u ? go_ : 65536u);
-    if (measure) SX_LAUNCH(LINNE_AMD_MEASURE_T_PRESET, k_wx_measure_preset, dim3(mgrid_acc), dim3(WXM_THREADS), 0, ctx->stream, d_acc, nacc);
+    if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_PRESET, k_wx_measure_preset, dim3(mgrid_acc), dim3(WXM_THREADS), 0, ctx->stream, d_acc, nacc);
     for (const WxPass &p : passes) {
         const LINNEAmdStreamIndex *x = gx[p.group];
         const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
@@ -2355,14 +2453,14 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
         int32_t *d_prm = (int32_t *)(sd + sc.o_prm), *d_data = (int32_t *)(sd + sc.o_data);
         uint8_t *d_seg = sd + sc.o_seg;
         if (p.nc) {
-            SX_LAUNCH(LINNE_AMD_T_WX_GATHER, k_wx_gather, dim3(p.nc), dim3(WX_GATHER_THREADS), 0, ctx->stream, d_rec, d_crec, p.nc, d_seg);
+            SX_LAUNCH(NULL, LINNE_AMD_T_WX_GATHER, k_wx_gather, dim3(p.nc), dim3(WX_GATHER_THREADS), 0, ctx->stream, d_rec, d_crec, p.nc, d_seg);
             WxParamArgs pa; memset(&pa, 0, sizeof(pa));
             pa.recs = d_rec; pa.crec = d_crec; pa.ncomp = p.nc; pa.C = C; pa.bits = x->shape.bits_per_sample; pa.L = hs.L;
             for (uint32_t l = 0; l < hs.L; l++) { pa.P[l] = hs.P[l]; pa.coef_off[l] = hs.coef_off[l]; }
             pa.tab = x->d_tab; pa.prm = d_prm; pa.bitpos = d_bpos; pa.bitend = d_bend; pa.out_nsmp = d_nsmp;
-            SX_LAUNCH(LINNE_AMD_T_WX_PARAMS, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
+            SX_LAUNCH(NULL, LINNE_AMD_T_WX_PARAMS, k_wx_params, dim3((p.nc + 63u) / 64u), dim3(64), 0, ctx->stream, pa);
             SX_TRY(rice_decode_launch(ctx, ctx->stream, &x->shape, d_seg, p.seg_bytes, d_bpos, d_bend, d_nsmp, p.nc, d_data, d_eb));
-            SX_LAUNCH(LINNE_AMD_T_WX_RICE_CHECK, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
+            SX_LAUNCH(NULL, LINNE_AMD_T_WX_RICE_CHECK, k_wx_rice_check, dim3((p.nc + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint64_t *)d_eb, d_rec, d_crec, d_win, p.nc, d_fail);
             if (!p.check_only) SX_TRY(decode_frames_dev(ctx, &x->shape, hs, d_data, d_nsmp, p.nc, d_prm));
         }
         if (p.check_only) continue;
@@ -2373,14 +2471,14 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
         if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
         if (measure) {
             WxMeasureArgs ma; ma.p = la; ma.mwin = d_mwin; ma.acc = d_acc;
-            SX_LAUNCH(LINNE_AMD_MEASURE_T_MEASURE, k_wx_measure, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
+            SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_MEASURE, k_wx_measure, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
         } else if (compare) {
             WxCompareArgs ca; ca.p = la; ca.diff = (unsigned long long *)(wd + o_diff);
-            SX_LAUNCH(LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
+            SX_LAUNCH(NULL, LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
         } else
-            SX_LAUNCH(LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+            SX_LAUNCH(NULL, LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
-    if (measure) SX_LAUNCH(LINNE_AMD_MEASURE_T_COMMIT, k_wx_measure_commit, dim3(mgrid_out), dim3(WXM_THREADS), 0, ctx->stream, d_mwin, nwin, (const struct LINNEAmdMeasure *)d_acc, (const uint32_t *)d_fail, nout);
+    if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_COMMIT, k_wx_measure_commit, dim3(mgrid_out), dim3(WXM_THREADS), 0, ctx->stream, d_mwin, nwin, (const struct LINNEAmdMeasure *)d_acc, (const uint32_t *)d_fail, nout);
     /* 5. the fail words and the saturation words (and the difference words) behind them, with the call's one wait */
     HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
@@ -2400,15 +2498,9 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const st
     ctx->err[0] = 0;
     const uint32_t *fail = NULL;
     std::vector<WxPlan> plan;
-    int ret;
-    try { plan.resize(num_windows); ret = wx_decode(ctx, windows, layouts, num_windows, group_frames, single, mode, specs, plan.data(), &fail); }
-    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
-    if (ret != LNN_OK) {
-        /* a HIP error, no memory: the whole call fails (whatever was enqueued is waited for: it reads the context's buffers) */
-        (void)hipStreamSynchronize(ctx->stream);
-        for (uint32_t i = 0; i < num_windows; i++) windows[i].result = LNN_NG;
-        return LNN_NG;
-    }
+    int ret = items_try(ctx, [&] { plan.resize(num_windows); return wx_decode(ctx, windows, layouts, num_windows, group_frames, single, mode, specs, plan.data(), &fail); });
+    /* a HIP error, no memory: the whole call fails (wx_decode has waited and recorded where it did not) */
+    if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, num_windows, [&](uint32_t i) { windows[i].result = LNN_NG; }) != LNN_OK) return LNN_NG;
     /* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
     if (layouts_out) for (uint32_t i = 0; i < num_windows; i++)
         if (windows[i].result == LNN_OK) layouts_out[i].saturated = (plan[i].group >= 0 && fail && fail[num_windows + i]) ? 1u : 0u;
@@ -2429,8 +2521,7 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const st
             snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
                     fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
         else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, mode, specs ? &specs[i] : NULL, text, sizeof(text), &r1);
-        if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", text);
-        else snprintf(ctx->err, sizeof(ctx->err), "window %u: %.*s", i, (int)sizeof(ctx->err) - 24, text);
+        items_first_text(ctx, "window", i, single, text);
         return windows[i].result;
     }
     return LNN_OK;
@@ -2654,7 +2745,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         {
             SeGatherArgs g;
             g.frames = d_frames; g.nonzero = d_nz; g.F = Fp; g.C = C; g.S = S;
-            SX_LAUNCH(LINNE_AMD_T_SB_GATHER, k_sb_gather, dim3(CF), dim3(SE_THREADS), 0, ctx->stream, g, (const SbRow *)d_rows, (const SbTrack *)d_trk);
+            SX_LAUNCH(NULL, LINNE_AMD_T_SB_GATHER, k_sb_gather, dim3(CF), dim3(SE_THREADS), 0, ctx->stream, g, (const SbRow *)d_rows, (const SbTrack *)d_trk);
         }
         /* 2. analysis, a call per slice of at most LNN_MAXCLS distinct lengths; the Rice plan of all rows */
         for (size_t k = 0; k + 1 < pp.slice.size(); k++) {
@@ -2665,7 +2756,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         }
         SX_TRY(LINNEAmd_RicePlanDevice(ctx, &shape, d_resid, h_nsmp.data(), Fp, d_plan));
         const uint32_t *d_nsmp = ctx->d_plan_nsmp;                 /* (RicePlanDevice's copy of this pass's lengths, by row) */
-        SX_LAUNCH(LINNE_AMD_T_SE_COMPACT, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
+        SX_LAUNCH(NULL, LINNE_AMD_T_SE_COMPACT, k_se_compact, dim3((CF + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, (const uint8_t *)d_plan, CF, d_cmp);
         /* 3. the host step: per track, in stream order, with the track's own state */
         HIPCHK(ctx, hipMemcpyAsync(h_cmp.data(), d_cmp, sizeof(uint2) * CF, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(h_st.data(), d_st, sizeof(double) * LINNE_AMD_STAT_WORDS * CF, hipMemcpyDeviceToHost, ctx->stream));
@@ -2716,9 +2807,9 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
         for (uint32_t l = 0; l < hs.L; l++) { a.P[l] = hs.P[l]; a.coef_off[l] = hs.coef_off[l]; }
         a.size = d_size; a.status = d_status; a.fail = d_fail; a.cfbit = d_cfbit; a.off = d_off; a.rows = d_rows; a.trk = d_trk;
         a.xch = (S + SE_THREADS - 1u) / SE_THREADS;
-        SX_LAUNCH(LINNE_AMD_T_SB_SIZE, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
-        SX_LAUNCH(LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
-        SX_LAUNCH(LINNE_AMD_T_SB_REDUCE, k_sb_reduce, dim3(Tp), dim3(64), 0, ctx->stream, (const SbTrack *)d_trk, Tp, (const int32_t *)d_status, (const uint64_t *)d_off, d_tout);
+        SX_LAUNCH(NULL, LINNE_AMD_T_SB_SIZE, k_se_size, dim3((Fp + SE_THREADS - 1u) / SE_THREADS), dim3(SE_THREADS), 0, ctx->stream, a);
+        SX_LAUNCH(NULL, LINNE_AMD_T_SE_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)d_size, (uint64_t)Fp, d_off);
+        SX_LAUNCH(NULL, LINNE_AMD_T_SB_REDUCE, k_sb_reduce, dim3(Tp), dim3(64), 0, ctx->stream, (const SbTrack *)d_trk, Tp, (const int32_t *)d_status, (const uint64_t *)d_off, d_tout);
         SX_TRY(sx_fetch(ctx, h_tout.data(), d_tout, sizeof(SbTrackOut) * Tp));
         /* the host decides per track: a refused block ends it; a track that no longer fits goes on being measured */
         uint64_t most = 0; bool any = false;
@@ -2744,12 +2835,12 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
             const uint64_t xz = (most + SB_ZERO_CHUNK - 1u) / SB_ZERO_CHUNK;
             if (xz * Tp > 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: a pass of %u tracks with up to %llu bytes each: give group_frames", Tp, (unsigned long long)most); return LNN_NG; }
             HIPCHK(ctx, hipMemcpyAsync(d_trk, h_trk2.data(), sizeof(SbTrack) * Tp, hipMemcpyHostToDevice, ctx->stream));
-            SX_LAUNCH(LINNE_AMD_T_SB_ZERO, k_sb_zero, dim3((uint32_t)(xz * Tp)), dim3(SB_ZERO_THREADS), 0, ctx->stream, (const SbTrack *)d_trk, (const SbTrackOut *)d_tout, (uint32_t)xz);
-            SX_LAUNCH(LINNE_AMD_T_SB_PARAMS, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
-            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(LINNE_AMD_T_SB_RICE, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
-            else SX_LAUNCH(LINNE_AMD_T_SB_RICE, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
-            SX_LAUNCH(LINNE_AMD_T_SB_RAW, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
-            SX_LAUNCH(LINNE_AMD_T_SB_CRC, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
+            SX_LAUNCH(NULL, LINNE_AMD_T_SB_ZERO, k_sb_zero, dim3((uint32_t)(xz * Tp)), dim3(SB_ZERO_THREADS), 0, ctx->stream, (const SbTrack *)d_trk, (const SbTrackOut *)d_tout, (uint32_t)xz);
+            SX_LAUNCH(NULL, LINNE_AMD_T_SB_PARAMS, k_se_params, dim3((Fp + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+            if (S <= REMIT_LDS_SAMPLES) SX_LAUNCH(NULL, LINNE_AMD_T_SB_RICE, k_se_rice<true>, dim3(CF), dim3(REMIT_THREADS), sizeof(uint32_t) * (S + REMIT_THREADS + 1u), ctx->stream, a);
+            else SX_LAUNCH(NULL, LINNE_AMD_T_SB_RICE, k_se_rice<false>, dim3(CF), dim3(REMIT_THREADS), 0, ctx->stream, a);
+            SX_LAUNCH(NULL, LINNE_AMD_T_SB_RAW, k_se_raw, dim3(Fp * a.xch), dim3(SE_THREADS), 0, ctx->stream, a, (const int32_t *)d_frames);
+            SX_LAUNCH(NULL, LINNE_AMD_T_SB_CRC, k_se_crc, dim3((Fp + 3u) / 4u), dim3(256), 0, ctx->stream, a);
         }
     }
     /* 7. the tracks' ends: does it fit, the length check of the Rice writers, the header */
@@ -2774,7 +2865,7 @@ static int sb_group_run(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, SbHo
     if (nh) {
         /* (the bytes of entry i lie at n pointers + 32 * i, whatever nh is) */
         HIPCHK(ctx, hipMemcpyAsync(sd + o_hdr, h_hdr.data(), h_hdr.size(), hipMemcpyHostToDevice, ctx->stream));
-        SX_LAUNCH(LINNE_AMD_T_SB_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hdr), (const uint8_t *)(sd + o_hdr + sizeof(uint8_t *) * (uint64_t)n), nh);
+        SX_LAUNCH(NULL, LINNE_AMD_T_SB_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hdr), (const uint8_t *)(sd + o_hdr + sizeof(uint8_t *) * (uint64_t)n), nh);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         /* (h_hdr lives on this frame) */
     }
     return LNN_OK;
@@ -2823,18 +2914,10 @@ static int sb_call(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const str
     if (num_tracks == 0) return LNN_OK;
     if (!tracks) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     std::vector<SbHost> host;
-    int ret;
-    try { ret = sb_run(ctx, tracks, layouts, num_tracks, group_frames, host); }
-    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    const int ret = items_try(ctx, [&] { return sb_run(ctx, tracks, layouts, num_tracks, group_frames, host); });
     const bool began = ctx->span_keep != 0;
     ctx->span_keep = 0; ctx->rice_guard = 0.0;
-    if (began && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
-    /* (whatever was enqueued is waited for: it reads the context's buffers) */
-    if (began && hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "EncodeStream%sDevice: hipStreamSynchronize failed", single ? "" : "s"); ret = LNN_NG; }
-    if (ret != LNN_OK) {
-        for (uint32_t i = 0; i < num_tracks; i++) tracks[i].result = LNN_NG;
-        return LNN_NG;
-    }
+    if (items_end(ctx, single ? "EncodeStreamDevice" : "EncodeStreamsDevice", ret, began, began, NULL, num_tracks, [&](uint32_t i) { tracks[i].result = LNN_NG; }) != LNN_OK) return LNN_NG;
     int first = -1;
     for (uint32_t i = 0; i < num_tracks; i++) {
         tracks[i].result = host[i].result;
@@ -2842,8 +2925,7 @@ static int sb_call(LINNEAmdContext *ctx, struct LINNEAmdTrack *tracks, const str
         else if (first < 0) first = (int)i;
     }
     if (first < 0) return LNN_OK;
-    if (single) snprintf(ctx->err, sizeof(ctx->err), "%s", host[first].text);
-    else snprintf(ctx->err, sizeof(ctx->err), "track %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    items_first_text(ctx, "track", (uint32_t)first, single, host[first].text);
     return host[first].result;
 }
 
@@ -2897,19 +2979,6 @@ extern "C" int64_t LINNEAmd_GetLastSpliceCount(struct LINNEAmdContext *ctx, int 
 {
     if (!ctx || which < 0 || which > 5) return -1;
     return ctx->splice_count[which];
-}
-
-/* a buffer of the splice call that grows: the wait and the allocation are the call's own (LINNEAmd_GetLastSpliceCount 5) */
-static int sp_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need, bool pinned)
-{
-    if (*cap >= need) return LNN_OK;
-    ctx->splice_count[5]++;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (*ptr) HIPCHK(ctx, pinned ? hipHostFree(*ptr) : hipFree(*ptr));
-    *ptr = NULL; *cap = 0;
-    if (pinned) HIPCHK(ctx, hipHostMalloc(ptr, need, hipHostMallocDefault)); else HIPCHK(ctx, hipMalloc(ptr, need));
-    *cap = need;
-    return LNN_OK;
 }
 
 struct SpHost { char text[200]; };
@@ -2994,8 +3063,9 @@ static int sp_run(LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t
     const uint64_t o_hptr = at; at = align_up(at + sizeof(uint8_t *) * live);
     const uint64_t o_hbytes = at; at = align_up(at + 32u * live);
     const uint64_t stage_bytes = at - o_runs;
-    SX_TRY(sp_ensure(ctx, &ctx->spl, &ctx->spl_cap, at, false));
-    SX_TRY(sp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true));
+    const LnnTally tally = { &ctx->splice_count[5], NULL, NULL };  /* the waits of its growing buffers are the call's own */
+    SX_TRY(ensure_buf(ctx, &ctx->spl, &ctx->spl_cap, at, false, &tally));
+    SX_TRY(ensure_buf(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true, &tally));
     uint8_t *sd = (uint8_t *)ctx->spl, *hs_ = (uint8_t *)ctx->spl_stage;
     if (nfrag) {
         std::vector<struct LINNEAmdWindow> win(nfrag);
@@ -3077,9 +3147,9 @@ static int sp_run(LINNEAmdContext *ctx, struct LINNEAmdSplice *splices, uint32_t
         HIPCHK(ctx, hipMemcpyAsync(sd + o_runs, hs_, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
         if (nruns) {
             const uint32_t grid = nchunks < SP_MAX_GRID ? (uint32_t)nchunks : SP_MAX_GRID;
-            SX_LAUNCH(LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)(sd + o_runs), nruns, nchunks);
+            SX_LAUNCH(NULL, LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)(sd + o_runs), nruns, nchunks);
         }
-        SX_LAUNCH(LINNE_AMD_SPLICE_T_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hptr), (const uint8_t *)(sd + o_hbytes), nh);
+        SX_LAUNCH(NULL, LINNE_AMD_SPLICE_T_HEADER, k_sb_header, dim3((nh * 32u + 255u) / 256u), dim3(256), 0, ctx->stream, (uint8_t *const *)(sd + o_hptr), (const uint8_t *)(sd + o_hbytes), nh);
     }
     return LNN_OK;
 }
@@ -3093,20 +3163,12 @@ extern "C" int LINNEAmd_SpliceStreamsDevice(struct LINNEAmdContext *ctx, struct 
     if (!splices) { snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     std::vector<SpOutput> outs;
     std::vector<SpHost> host;
-    int ret;
-    try { ret = sp_run(ctx, splices, num_splices, group_frames, outs, host); }
-    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
+    const int ret = items_try(ctx, [&] { return sp_run(ctx, splices, num_splices, group_frames, outs, host); });
     const bool began = ctx->outer_keep != 0;
     ctx->outer_keep = 0; ctx->span_keep = 0;
-    if (began && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
-    /* the call's one wait of its own (whatever was enqueued is waited for: it reads the context's buffers) */
-    if (began) {
-        ctx->splice_count[5]++;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
-    }
-    if (ret != LNN_OK) {
-        if (!ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "SpliceStreamsDevice: failed with %d", ret);
-        for (uint32_t i = 0; i < num_splices; i++) { splices[i].result = LNN_NG; splices[i].out_bytes = 0; splices[i].copied_blocks = splices[i].encoded_blocks = 0; }
+    /* (the wait is the call's one wait of its own) */
+    if (items_end(ctx, "SpliceStreamsDevice", ret, began, began, &ctx->splice_count[5], num_splices,
+            [&](uint32_t i) { splices[i].result = LNN_NG; splices[i].out_bytes = 0; splices[i].copied_blocks = splices[i].encoded_blocks = 0; }) != LNN_OK) {
         for (int i = 0; i < 5; i++) ctx->splice_count[i] = 0;
         return LNN_NG;
     }
@@ -3120,7 +3182,7 @@ extern "C" int LINNEAmd_SpliceStreamsDevice(struct LINNEAmdContext *ctx, struct 
         if (o.result != LNN_OK && first < 0) first = (int)i;
     }
     if (first < 0) return LNN_OK;
-    snprintf(ctx->err, sizeof(ctx->err), "splice %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    items_first_text(ctx, "splice", (uint32_t)first, false, host[first].text);
     return outs[first].result;
 }
 
@@ -3185,101 +3247,49 @@ extern "C" int LINNEAmd_GetLastRepairGaps(struct LINNEAmdContext *ctx, uint32_t 
     return LNN_OK;
 }
 
-/* the call's waits and launches are counted (LINNEAmd_GetLastRepairCount 5 and 6) */
-static int rp_sync(LINNEAmdContext *ctx)
-{
-    ctx->repair_count[5]++;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LNN_OK;
-}
-static int rp_ensure(LINNEAmdContext *ctx, void **ptr, uint64_t *cap, uint64_t need, bool pinned)
-{
-    if (*cap >= need) return LNN_OK;
-    SX_TRY(rp_sync(ctx));                                           /* (a buffer that grows waits for the stream first) */
-    if (*ptr) HIPCHK(ctx, pinned ? hipHostFree(*ptr) : hipFree(*ptr));
-    *ptr = NULL; *cap = 0;
-    if (pinned) HIPCHK(ctx, hipHostMalloc(ptr, need, hipHostMallocDefault)); else HIPCHK(ctx, hipMalloc(ptr, need));
-    *cap = need;
-    return LNN_OK;
-}
-#define RP_LAUNCH(kind, ...) do { ctx->repair_count[6]++; SX_LAUNCH(kind, __VA_ARGS__); } while (0)
-
 struct RpHost { int32_t result; char text[200]; };
 
-/* LNN_OK: every stream has its result in host[] and, where that is OK or INSUFFICIENT_BUFFER, its plan; anything else fails the
+/* The block-head scan (IbScan), then the repair's own: sound candidates, their chains, the runs of kept blocks, the host's plan and
+ * the copy launch (run table and fill bytes in spl / spl_stage).
+ * LNN_OK: every stream has its result in host[] and, where that is OK or INSUFFICIENT_BUFFER, its plan; anything else fails the
  * whole call */
 static int rp_run(LINNEAmdContext *ctx, struct LINNEAmdRepair *rep, uint32_t T, std::vector<RpHost> &host, std::vector<RpPlan> &plans)
 {
     char text[sizeof(ctx->err)];
     host.resize(T); plans.resize(T);
     for (uint32_t i = 0; i < T; i++) { host[i].result = LNN_OK; host[i].text[0] = 0; plans[i].result = RP_OK; plans[i].bytes = 0; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    /* the lists of the call, pinned on the host and at the same offsets on the device (the batch index's, and its buffers) */
-    const uint64_t o_st = 0, o_row0 = align_up(o_st + sizeof(IbStream) * (uint64_t)T), o_bound = align_up(o_row0 + sizeof(uint64_t) * (T + 1ull)),
-            o_tab = align_up(o_bound + sizeof(uint64_t) * (uint64_t)T), o_crow = align_up(o_tab + sizeof(SxTables)), o_hdr = align_up(o_crow + sizeof(uint64_t) * (T + 1ull)),
-            o_seg = align_up(o_hdr + (uint64_t)IB_HDR_SLOT * T), o_sseg = align_up(o_seg + sizeof(uint64_t) * (T + 1ull)), o_len = align_up(o_sseg + sizeof(uint64_t) * (T + 1ull)),
-            o_rseg = align_up(o_len + sizeof(uint64_t) * (uint64_t)T), list_bytes = align_up(o_rseg + sizeof(uint64_t) * (T + 1ull));
-    SX_TRY(rp_ensure(ctx, &ctx->wstage, &ctx->wstage_cap, list_bytes, true));
-    SX_TRY(rp_ensure(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes, false));
-    uint8_t *hl = (uint8_t *)ctx->wstage, *dl = (uint8_t *)ctx->wdec;
-    IbStream *h_st = (IbStream *)(hl + o_st);
-    uint64_t *h_row0 = (uint64_t *)(hl + o_row0), *h_bound = (uint64_t *)(hl + o_bound), *h_crow = (uint64_t *)(hl + o_crow), *h_seg = (uint64_t *)(hl + o_seg),
-            *h_len = (uint64_t *)(hl + o_len), *h_rseg = (uint64_t *)(hl + o_rseg);
-    const uint8_t *h_hdr = hl + o_hdr;
-    const IbStream *d_st = (const IbStream *)(dl + o_st);
-    const uint64_t *d_row0 = (const uint64_t *)(dl + o_row0), *d_bound = (const uint64_t *)(dl + o_bound), *d_crow = (const uint64_t *)(dl + o_crow);
-    uint64_t *d_seg = (uint64_t *)(dl + o_seg), *d_sseg = (uint64_t *)(dl + o_sseg), *d_len = (uint64_t *)(dl + o_len), *d_rseg = (uint64_t *)(dl + o_rseg);
-    const uint32_t gT = (uint32_t)(((uint64_t)T + 256u) / 256u);
-    ctx->nspans = 0;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    /* 1. the headers: one gather, one fetch; the host reads them as the index does */
-    memset(h_st, 0, sizeof(IbStream) * (uint64_t)T);
-    for (uint32_t i = 0; i < T; i++) {
-        if (!rep[i].d_stream || !rep[i].d_out) { host[i].result = LNN_INVALID_ARGUMENT; snprintf(host[i].text, sizeof(host[i].text), "RepairStreamsDevice: null argument"); continue; }
-        h_st[i].b = rep[i].d_stream; h_st[i].N = rep[i].stream_bytes;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, sizeof(IbStream) * (uint64_t)T, hipMemcpyHostToDevice, ctx->stream));
-    RP_LAUNCH(LINNE_AMD_T_IB_HEADERS, k_ib_headers, dim3((uint32_t)(((uint64_t)T * IB_HDR_SLOT + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, T, dl + o_hdr);
-    HIPCHK(ctx, hipMemcpyAsync(hl + o_hdr, dl + o_hdr, (uint64_t)IB_HDR_SLOT * T, hipMemcpyDeviceToHost, ctx->stream));
-    SX_TRY(rp_sync(ctx));
-    uint64_t nrows = 0;
-    for (uint32_t i = 0; i < T; i++) {
-        h_row0[i] = nrows; h_bound[i] = 0;
-        if (host[i].result != LNN_OK) continue;
-        LINNEAmdStreamIndex *x = NULL;
-        bool whole_call;
-        const int r = ib_open(ctx->device, h_hdr + (uint64_t)IB_HDR_SLOT * i, rep[i].stream_bytes, &x, text, sizeof(text), &whole_call);
-        if (whole_call) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: %.*s", (int)sizeof(ctx->err) - 32, text); return LNN_NG; }
-        if (r != LNN_OK) { host[i].result = r; snprintf(host[i].text, sizeof(host[i].text), "%.*s", (int)sizeof(host[i].text) - 1, text); h_st[i].b = NULL; h_st[i].N = 0; continue; }
-        h_st[i].num_samples = x->header.num_samples; h_st[i].C = x->shape.num_channels; h_st[i].S = x->shape.num_samples_per_block; h_st[i].bits = x->shape.bits_per_sample;
-        uint32_t L = 0, P[LINNE_AMD_MAX_LAYERS] = { 0, 0, 0 }, sum = 0;
-        (void)lnn_preset_info(x->shape.preset, &L, P, NULL, NULL);
-        for (uint32_t l = 0; l < L; l++) sum += P[l];
-        h_bound[i] = rp_block_bound(h_st[i].C, h_st[i].S, h_st[i].bits, L, sum);
-        free(x);
-        if (rep[i].stream_bytes > SX_FIRST_BLOCK) nrows += (rep[i].stream_bytes - SX_FIRST_BLOCK + SX_WAVE_POS - 1u) / SX_WAVE_POS;
-    }
-    h_row0[T] = nrows;
-    if (nrows >= 0x1FFFFFFFCull) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: %llu stream bytes in one call: too many", (unsigned long long)(nrows * SX_WAVE_POS)); return LNN_NG; }
-    sx_tables((SxTables *)(hl + o_tab));
-    HIPCHK(ctx, hipMemcpyAsync(dl + o_st, hl + o_st, o_crow - o_st, hipMemcpyHostToDevice, ctx->stream));      /* the streams, row0, the bounds, the tables */
-    /* 2. candidates over (stream, wave) rows, numbered over the whole call; the T + 1 segment bounds come back */
-    const uint64_t o_counts = 0, o_cofs = align_up(sizeof(uint32_t) * nrows);
-    SX_TRY(rp_ensure(ctx, &ctx->sdec, &ctx->sdec_cap, align_up(o_cofs + sizeof(uint64_t) * (nrows + 1u)), false));
-    uint32_t *counts = (uint32_t *)((uint8_t *)ctx->sdec + o_counts);
-    uint64_t *cofs = (uint64_t *)((uint8_t *)ctx->sdec + o_cofs);
-    const uint32_t grow = (uint32_t)((nrows + 3u) / 4u);
-    if (nrows) RP_LAUNCH(LINNE_AMD_T_SX_COUNT, k_ib_count, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, counts);
-    RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)counts, nrows, cofs);
-    RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)cofs, d_row0, T, d_seg);
-    HIPCHK(ctx, hipMemcpyAsync(h_seg, d_seg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
-    SX_TRY(rp_sync(ctx));
-    const uint64_t M = h_seg[T];
-    if (M >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%llu block candidates: too many", (unsigned long long)M); return LNN_NG; }
-    uint64_t Mmax = 0;
-    for (uint32_t i = 0; i < T; i++) if (h_seg[i + 1] - h_seg[i] > Mmax) Mmax = h_seg[i + 1] - h_seg[i];
-    uint32_t K = 1;
-    while ((1ull << K) <= Mmax) K++;                              /* 2^K > the longest segment: K levels cover any chain */
+    /* 1. 2. the index's scan over the call's streams, through its host code and in its buffers (ib_scan_*).  Behind row0 its lists
+     * carry the streams' block bounds and the tables, which go up with them; at their end the segment bounds of the sound candidates
+     * and of the runs.  An opened stream's index is read for its shape and freed.  The call's waits and launches are counted
+     * (LINNEAmd_GetLastRepairCount 5 and 6) */
+    const LnnTally tally = { &ctx->repair_count[5], NULL, &ctx->repair_count[6] }, *tl = &tally;
+    const uint64_t e_tab = align_up(sizeof(uint64_t) * (uint64_t)T), l_rseg = align_up(sizeof(uint64_t) * (T + 1ull));
+    IbScan s;
+    SX_TRY(ib_scan_lists(s, ctx, "RepairStreamsDevice", false, T, tally, e_tab + sizeof(SxTables), l_rseg + sizeof(uint64_t) * (T + 1ull)));
+    uint8_t *hl = s.hl, *dl = s.dl;
+    uint64_t *h_bound = (uint64_t *)(hl + s.at.o_early), *h_rseg = (uint64_t *)(hl + s.at.o_late + l_rseg);
+    const uint64_t *d_bound = (const uint64_t *)(dl + s.at.o_early);
+    uint64_t *d_sseg = (uint64_t *)(dl + s.at.o_late), *d_rseg = (uint64_t *)(dl + s.at.o_late + l_rseg);
+    sx_tables((SxTables *)(hl + s.at.o_early + e_tab));
+    SX_TRY(ib_scan_headers(s,
+            [&](uint32_t i, uint64_t *N) -> const uint8_t * {
+                h_bound[i] = 0;
+                if (!rep[i].d_stream || !rep[i].d_out) { host[i].result = LNN_INVALID_ARGUMENT; snprintf(host[i].text, sizeof(host[i].text), "RepairStreamsDevice: null argument"); return NULL; }
+                *N = rep[i].stream_bytes; return rep[i].d_stream;
+            },
+            [&](uint32_t i, int code, const char *why, LINNEAmdStreamIndex *x) {
+                if (!x) { host[i].result = code; snprintf(host[i].text, sizeof(host[i].text), "%.*s", (int)sizeof(host[i].text) - 1, why); return; }
+                uint32_t L = 0, P[LINNE_AMD_MAX_LAYERS] = { 0, 0, 0 }, sum = 0;
+                (void)lnn_preset_info(x->shape.preset, &L, P, NULL, NULL);
+                for (uint32_t l = 0; l < L; l++) sum += P[l];
+                h_bound[i] = rp_block_bound(s.h_st[i].C, s.h_st[i].S, s.h_st[i].bits, L, sum);
+                free(x);
+            }));
+    SX_TRY(ib_scan_candidates(s));
+    const uint32_t K = s.K, M32 = s.M32, gT = s.gT, gM = s.gM;
+    const uint64_t M = s.M;
+    const IbStream *h_st = s.h_st, *d_st = s.d_st;
+    const uint64_t *d_crow = s.d_crow, *d_seg = s.d_seg;
     /* 3. the sound candidates, their successors, pointer doubling, the chains' lengths.  No more sound candidates than candidates
      * and no more chain blocks than sound candidates: every table below has room for M of them, so nothing waits for a count */
     uint64_t at = 0;
@@ -3289,53 +3299,48 @@ static int rp_run(LINNEAmdContext *ctx, struct LINNEAmdRepair *rep, uint32_t T, 
             o_size = part(sizeof(uint32_t) * (M + 1u)), o_type = part(sizeof(uint32_t) * (M + 1u)), o_nsmp = part(sizeof(uint32_t) * (M + 1u)),
             o_scan = part(sizeof(uint64_t) * (M + 2u)), o_mark = part(sizeof(uint32_t) * (M + 1u)), o_rofs = part(sizeof(uint64_t) * (M + 2u)),
             o_rec = part(sizeof(RpRunRec) * (M + 1u));
-    SX_TRY(rp_ensure(ctx, &ctx->xcand, &ctx->xcand_cap, at, false));
+    SX_TRY(ensure_buf(ctx, &ctx->xcand, &ctx->xcand_cap, at, false, tl));
     uint8_t *xc = (uint8_t *)ctx->xcand;
     uint64_t *cand = (uint64_t *)(xc + o_cand), *sofs = (uint64_t *)(xc + o_sofs), *spos = (uint64_t *)(xc + o_spos), *c_off = (uint64_t *)(xc + o_off),
             *scan = (uint64_t *)(xc + o_scan), *rofs = (uint64_t *)(xc + o_rofs);
     uint32_t *flag = (uint32_t *)(xc + o_flag), *jump = (uint32_t *)(xc + o_jump), *c_size = (uint32_t *)(xc + o_size), *c_type = (uint32_t *)(xc + o_type),
             *c_nsmp = (uint32_t *)(xc + o_nsmp), *mark = (uint32_t *)(xc + o_mark);
     RpRunRec *rec = (RpRunRec *)(xc + o_rec);
-    const uint32_t M32 = (uint32_t)M, gM = (uint32_t)((M + 1u + 255u) / 256u);
-    uint64_t nchain = 0;
-    for (uint32_t i = 0; i <= T; i++) h_crow[i] = 0;
+    for (uint32_t i = 0; i <= T; i++) s.h_crow[i] = 0;
     if (M) {
-        RP_LAUNCH(LINNE_AMD_T_SX_WRITE, k_ib_write, dim3(grow), dim3(256), 0, ctx->stream, d_st, d_row0, T, nrows, (const uint64_t *)cofs, cand);
+        SX_TRY(ib_scan_write(s, cand));
         RpSoundArgs sa;
-        sa.st = d_st; sa.bound = d_bound; sa.seg = d_seg; sa.T = T; sa.M = M32; sa.cand = cand; sa.tab = (const SxTables *)(dl + o_tab); sa.flag = flag;
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_SOUND, k_rp_sound, dim3((uint32_t)((M + 3u) / 4u)), dim3(256), 0, ctx->stream, sa);
-        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)flag, M, sofs);
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_COMPACT, k_rp_compact, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)flag, (const uint64_t *)sofs, (const uint64_t *)cand, M32, spos);
-        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)sofs, (const uint64_t *)d_seg, T, d_sseg);
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_SUCC, k_rp_succ, dim3(gM), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, T, (const uint64_t *)spos, M32, jump);
-        for (uint32_t k = 1; k < K; k++)
-            RP_LAUNCH(LINNE_AMD_T_SX_JUMP, k_sx_jump, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)(jump + (uint64_t)(k - 1u) * (M + 1u)), jump + (uint64_t)k * (M + 1u), M32);
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_CHAIN_LEN, k_rp_chain_len, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)d_sseg, T, (const uint32_t *)jump, K, M32, d_len);
-        HIPCHK(ctx, hipMemcpyAsync(h_len, d_len, sizeof(uint64_t) * (uint64_t)T, hipMemcpyDeviceToHost, ctx->stream));
-        SX_TRY(rp_sync(ctx));
-        for (uint32_t i = 0; i < T; i++) { h_crow[i] = nchain; nchain += h_len[i]; }
-        h_crow[T] = nchain;
-        if (nchain > M) { snprintf(ctx->err, sizeof(ctx->err), "internal: %llu chain blocks of %llu candidates", (unsigned long long)nchain, (unsigned long long)M); return LNN_NG; }
+        sa.st = d_st; sa.bound = d_bound; sa.seg = s.d_seg; sa.T = T; sa.M = M32; sa.cand = cand; sa.tab = (const SxTables *)(dl + s.at.o_early + e_tab); sa.flag = flag;
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_SOUND, k_rp_sound, dim3((uint32_t)((M + 3u) / 4u)), dim3(256), 0, ctx->stream, sa);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)flag, M, sofs);
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_COMPACT, k_rp_compact, dim3(gM), dim3(256), 0, ctx->stream, (const uint32_t *)flag, (const uint64_t *)sofs, (const uint64_t *)cand, M32, spos);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)sofs, d_seg, T, d_sseg);
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_SUCC, k_rp_succ, dim3(gM), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, T, (const uint64_t *)spos, M32, jump);
+        SX_TRY(ib_scan_jumps(s, jump));
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_CHAIN_LEN, k_rp_chain_len, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)d_sseg, T, (const uint32_t *)jump, K, M32, s.d_len);
+        SX_TRY(ib_scan_chains(s));
+        if (s.nchain > M) { snprintf(ctx->err, sizeof(ctx->err), "internal: %llu chain blocks of %llu candidates", (unsigned long long)s.nchain, (unsigned long long)M); return LNN_NG; }
     }
+    const uint64_t nchain = s.nchain;
     /* 4. the chains' blocks, the cut at the headers' sample counts, a record per run of adjacent kept blocks: one fetch */
     std::vector<std::vector<RpPiece>> pieces(T);
     if (nchain) {
-        SX_TRY(rp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, sizeof(RpRunRec) * nchain, true));
-        HIPCHK(ctx, hipMemcpyAsync(dl + o_crow, hl + o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
-        RP_LAUNCH(LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, d_crow, T, (const uint64_t *)spos,
+        SX_TRY(ensure_buf(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, sizeof(RpRunRec) * nchain, true, tl));
+        HIPCHK(ctx, hipMemcpyAsync(dl + s.at.o_crow, hl + s.at.o_crow, sizeof(uint64_t) * (T + 1ull), hipMemcpyHostToDevice, ctx->stream));
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_CHAIN, k_ib_chain, dim3((uint32_t)((nchain + 255u) / 256u)), dim3(256), 0, ctx->stream, d_st, (const uint64_t *)d_sseg, d_crow, T, (const uint64_t *)spos,
                 (const uint32_t *)jump, K, M32, nchain, c_off, c_size, c_type, c_nsmp);
-        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)c_nsmp, nchain, scan);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)c_nsmp, nchain, scan);
         RpRunArgs ra;
         ra.st = d_st; ra.crow = d_crow; ra.T = T; ra.nchain = nchain; ra.off = c_off; ra.size = c_size; ra.scan = scan; ra.mark = mark; ra.rofs = rofs; ra.rec = rec;
         const uint32_t gc = (uint32_t)((nchain + 255u) / 256u);
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_MARK, k_rp_mark, dim3(gc), dim3(256), 0, ctx->stream, ra);
-        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)mark, nchain, rofs);
-        RP_LAUNCH(LINNE_AMD_REPAIR_T_RUNS, k_rp_runs, dim3(gc), dim3(256), 0, ctx->stream, ra);
-        RP_LAUNCH(LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)rofs, d_crow, T, d_rseg);
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_MARK, k_rp_mark, dim3(gc), dim3(256), 0, ctx->stream, ra);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)mark, nchain, rofs);
+        SX_LAUNCH(tl, LINNE_AMD_REPAIR_T_RUNS, k_rp_runs, dim3(gc), dim3(256), 0, ctx->stream, ra);
+        SX_LAUNCH(tl, LINNE_AMD_T_SX_SCAN, k_ib_seg, dim3(gT), dim3(256), 0, ctx->stream, (const uint64_t *)rofs, d_crow, T, d_rseg);
         HIPCHK(ctx, hipMemcpyAsync(h_rseg, d_rseg, sizeof(uint64_t) * (T + 1ull), hipMemcpyDeviceToHost, ctx->stream));
         /* (no more runs than chain blocks: the records of all of them come back without waiting for their count) */
         HIPCHK(ctx, hipMemcpyAsync(ctx->spl_stage, rec, sizeof(RpRunRec) * nchain, hipMemcpyDeviceToHost, ctx->stream));
-        SX_TRY(rp_sync(ctx));
+        SX_TRY(tally_wait(ctx, tl));
         const RpRunRec *h_rec = (const RpRunRec *)ctx->spl_stage;
         if (h_rseg[T] > nchain) { snprintf(ctx->err, sizeof(ctx->err), "internal: %llu runs of %llu chain blocks", (unsigned long long)h_rseg[T], (unsigned long long)nchain); return LNN_NG; }
         for (uint32_t i = 0; i < T; i++)
@@ -3359,8 +3364,8 @@ static int rp_run(LINNEAmdContext *ctx, struct LINNEAmdRepair *rep, uint32_t T, 
     if (nruns >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: too many runs in one call"); return LNN_NG; }
     if (nruns) {
         const uint64_t o_fill = align_up(sizeof(SpRun) * (nruns + 1u)), stage_bytes = align_up(o_fill + fill_bytes);
-        SX_TRY(rp_ensure(ctx, &ctx->spl, &ctx->spl_cap, stage_bytes, false));
-        SX_TRY(rp_ensure(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true));
+        SX_TRY(ensure_buf(ctx, &ctx->spl, &ctx->spl_cap, stage_bytes, false, tl));
+        SX_TRY(ensure_buf(ctx, &ctx->spl_stage, &ctx->spl_stage_cap, stage_bytes, true, tl));
         uint8_t *sd = (uint8_t *)ctx->spl, *hs_ = (uint8_t *)ctx->spl_stage;
         SpRun *h_runs = (SpRun *)hs_;
         uint64_t r = 0, f = o_fill, nchunks = 0;
@@ -3378,9 +3383,15 @@ static int rp_run(LINNEAmdContext *ctx, struct LINNEAmdRepair *rep, uint32_t T, 
         memset(&h_runs[nruns], 0, sizeof(SpRun)); h_runs[nruns].chunk0 = nchunks;
         HIPCHK(ctx, hipMemcpyAsync(sd, hs_, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
         const uint32_t grid = nchunks < SP_MAX_GRID ? (uint32_t)nchunks : SP_MAX_GRID;
-        RP_LAUNCH(LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)sd, (uint32_t)nruns, nchunks);
+        SX_LAUNCH(tl, LINNE_AMD_SPLICE_T_COPY, k_sp_copy, dim3(grid), dim3(SP_THREADS), 0, ctx->stream, (const SpRun *)sd, (uint32_t)nruns, nchunks);
     }
     ctx->repair_count[4] = (int64_t)nruns;
+    /* room for the gaps LINNEAmd_GetLastRepairGaps hands out (filled behind the call's last wait) */
+    uint64_t ngaps = 0;
+    for (uint32_t i = 0; i < T; i++) if (host[i].result == LNN_OK) ngaps += plans[i].gaps.size();
+    ctx->rp_gaps = (struct LINNEAmdGap *)malloc(sizeof(struct LINNEAmdGap) * (ngaps + 1u));
+    ctx->rp_gap0 = (uint64_t *)malloc(sizeof(uint64_t) * ((uint64_t)T + 1u));
+    if (!ctx->rp_gaps || !ctx->rp_gap0) { free(ctx->rp_gaps); free(ctx->rp_gap0); ctx->rp_gaps = NULL; ctx->rp_gap0 = NULL; snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); return LNN_NG; }
     return LNN_OK;
 }
 
@@ -3394,26 +3405,12 @@ extern "C" int LINNEAmd_RepairStreamsDevice(struct LINNEAmdContext *ctx, struct 
     if (!streams) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     std::vector<RpHost> host;
     std::vector<RpPlan> plans;
-    int ret;
-    try { ret = rp_run(ctx, streams, num_streams, host, plans); }
-    catch (const std::bad_alloc &) { snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
-    if (ret == LNN_OK && ctx->timing) { (void)hipEventRecord(ctx->ev[1], ctx->stream); ctx->ev_valid = 1; }
-    /* the call's last wait (whatever was enqueued is waited for: it reads the context's buffers) */
-    ctx->repair_count[5]++;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && ret == LNN_OK) { snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: hipStreamSynchronize failed"); ret = LNN_NG; }
-    uint64_t ngaps = 0;
-    if (ret == LNN_OK) {
-        for (uint32_t i = 0; i < num_streams; i++) if (host[i].result == LNN_OK) ngaps += plans[i].gaps.size();
-        ctx->rp_gaps = (struct LINNEAmdGap *)malloc(sizeof(struct LINNEAmdGap) * (ngaps + 1u));
-        ctx->rp_gap0 = (uint64_t *)malloc(sizeof(uint64_t) * ((uint64_t)num_streams + 1u));
-        if (!ctx->rp_gaps || !ctx->rp_gap0) { free(ctx->rp_gaps); free(ctx->rp_gap0); ctx->rp_gaps = NULL; ctx->rp_gap0 = NULL; snprintf(ctx->err, sizeof(ctx->err), "out of host memory"); ret = LNN_NG; }
-    }
-    if (ret != LNN_OK) {
-        if (!ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "RepairStreamsDevice: failed with %d", ret);
-        for (uint32_t i = 0; i < num_streams; i++) {
-            streams[i].result = LNN_NG; streams[i].out_bytes = streams[i].lost_samples = 0;
-            streams[i].kept_blocks = streams[i].fill_blocks = streams[i].num_gaps = streams[i].exact = 0;
-        }
+    const int ret = items_try(ctx, [&] { return rp_run(ctx, streams, num_streams, host, plans); });
+    /* (the wait is the call's last) */
+    if (items_end(ctx, "RepairStreamsDevice", ret, ret == LNN_OK, true, &ctx->repair_count[5], num_streams, [&](uint32_t i) {
+                streams[i].result = LNN_NG; streams[i].out_bytes = streams[i].lost_samples = 0;
+                streams[i].kept_blocks = streams[i].fill_blocks = streams[i].num_gaps = streams[i].exact = 0;
+            }) != LNN_OK) {
         for (int i = 0; i < 5; i++) ctx->repair_count[i] = 0;
         return LNN_NG;
     }
@@ -3438,7 +3435,7 @@ extern "C" int LINNEAmd_RepairStreamsDevice(struct LINNEAmdContext *ctx, struct 
     }
     ctx->rp_gap0[num_streams] = g; ctx->rp_streams = num_streams;
     if (first < 0) return LNN_OK;
-    snprintf(ctx->err, sizeof(ctx->err), "repair %d: %.*s", first, (int)sizeof(ctx->err) - 24, host[first].text);
+    items_first_text(ctx, "repair", (uint32_t)first, false, host[first].text);
     return host[first].result;
 }
 
