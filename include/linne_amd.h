@@ -381,6 +381,13 @@ enum LINNEAmdMeasureTimingKind {
     LINNE_AMD_MEASURE_T_PRESET = 81,        /* the call's accumulators preset, once, in front of the first pass (k_wx_measure_preset) */
     LINNE_AMD_MEASURE_T_COMMIT = 82         /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_measure_commit) */
 };
+/* digesting windows (LINNEAmd_DigestWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of kind 83 wherever that
+ * call has one of kind 59, and one launch each of kinds 84 and 85 per call that takes a pass) */
+enum LINNEAmdDigestTimingKind {
+    LINNE_AMD_DIGEST_T_DIGEST = 83,         /* hashing every window's samples into its buckets' accumulators (k_wx_digest) */
+    LINNE_AMD_DIGEST_T_PRESET = 84,         /* the call's accumulators zeroed and the tables of powers filled, once, in front of the first pass (k_wx_digest_preset) */
+    LINNE_AMD_DIGEST_T_COMMIT = 85          /* the answers of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_digest_commit) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -679,6 +686,46 @@ struct LINNEAmdMeasureSpec {
 };
 int LINNEAmd_MeasureWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdMeasureSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- digesting sample windows of resident streams: the CRC-32 of the decoded PCM per bucket, no PCM written ----
+ * LINNEAmd_DigestWindowsDevice takes the windows of LINNEAmd_DecodeWindowsDevice and, instead of writing every window's samples,
+ * hashes them: the only output is a table of struct LINNEAmdDigest per window, in device memory.  The digest of a whole stream
+ * equals zlib's crc32() of the `data` chunk of the WAV file that the reference's `linne -d` (and linne_amd_cli -d) writes for it.
+ * The byte string of the samples [first, first + n) of a stream of C channels and `bits` bits per sample: the samples in sample
+ * order and, within a sample, in channel order (interleaved); every value in w = ceil(bits / 8) bytes, little-endian, the low w
+ * bytes of the two's-complement int32 that LINNEAmd_DecodeStreamDevice writes; for w == 1 the byte is (v + 128) & 0xFF, WAV's 8-bit
+ * form being unsigned (libs/wav/src/wav.c, the writer's 8/16/24/32 cases).  Nothing is saturated: a value outside the width is
+ * truncated, as in the reference's writer.  The zeros of SILENT blocks and of the range behind the stream's last block are part of
+ * the string (for 8-bit streams they are 0x80 bytes, not nothing).
+ * Buckets are LINNEAmd_MeasureWindowsDevice's: specs[i].bucket_samples = b > 0 gives nb = ceil(n / b) buckets, bucket k covering the
+ * window's samples [k * b, min((k + 1) * b, n)), all channels (the last one may be short); b == 0 is one bucket of the whole window;
+ * a window of no samples has no buckets and nothing is written.  Bucket k's answer, at d_out[k]: crc32, the zlib / IEEE 802.3
+ * CRC-32 of the bucket's byte string (reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF), and num_bytes, the
+ * string's length.  CRC-32 is linear over GF(2): the pieces of a bucket are hashed independently and folded with XOR in any order,
+ * so the answer is exact and does not depend on the order the device takes them in.
+ * Everything LINNEAmd_MeasureWindowsDevice says about results holds unchanged: the windows' d_pcm and pcm_stride are ignored;
+ * every window's `result` is what LINNEAmd_DecodeWindowsDevice gives it, and for that window alone INVALID_ARGUMENT when d_out is
+ * NULL (with n > 0) or not 8-byte aligned, or when nb > 2^32 - 1.  A failing window's d_out is never written, and a failing window
+ * does not disturb the others.  No byte outside d_out[0 .. nb) is written; the outputs of different windows must not overlap; the
+ * streams are only read.  Shape groups, passes, group_frames, scratch and whole-call failures are the decode call's, with
+ * "window <i>: " and the single call's text in GetLastError.  A pass has the decode call's launches with kind 83 in place of
+ * kind 59; a call that takes at least one pass adds exactly two launches, whatever num_windows is: kind 84 in front of the first
+ * pass and kind 85 behind the last; a window that spans passes collects its answer over them.  Copies (one upload, one fetch) and
+ * host synchronisations (one) are the measure call's.  The accumulators live in the context's scratch: one 32-bit word per bucket
+ * of every window, times up to 64 (16 words apart) for windows whose buckets are 8192 samples or longer, behind 40 KiB of tables.
+ * num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the
+ * context's stream and synchronous. */
+struct LINNEAmdDigest {                 /* 16 bytes: one bucket of one window */
+    uint32_t crc32;                     /* of the bucket's byte string, as zlib's crc32() gives it */
+    uint32_t reserved;                  /* 0 */
+    uint64_t num_bytes;                 /* the byte string's length */
+};
+struct LINNEAmdDigestSpec {
+    uint64_t bucket_samples;            /* 0: the whole window is one bucket */
+    struct LINNEAmdDigest *d_out;       /* device, 8-byte aligned: bucket k at d_out[k] */
+};
+int LINNEAmd_DigestWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdDigestSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

@@ -57,6 +57,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_RepairStreamsDevice", "LINNEAmd_GetLastRepairGaps", "LINNEAmd_GetLastRepairCount",
     "LINNEAmd_CompareWindowsDevice",
     "LINNEAmd_MeasureWindowsDevice",
+    "LINNEAmd_DigestWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -156,6 +157,34 @@ class Measurement:
         return a.view(MEASURE_DTYPE).reshape(a.shape[:2])
 
 
+class Digest(C.Structure):
+    """struct LINNEAmdDigest (include/linne_amd.h): one bucket of one window"""
+    _fields_ = [("crc32", C.c_uint32), ("reserved", C.c_uint32), ("num_bytes", C.c_uint64)]
+
+
+class DigestSpec(C.Structure):
+    """struct LINNEAmdDigestSpec (include/linne_amd.h)"""
+    _fields_ = [("bucket_samples", C.c_uint64), ("d_out", C.c_void_p)]
+
+
+DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("reserved", "<u4"), ("num_bytes", "<u8")])
+
+
+class DigestTable:
+    """one window's table of digest_windows: `records`, an int64 CUDA tensor (nb, 2) holding a struct LINNEAmdDigest per bucket, and
+    views of it -- crc32 and num_bytes (int64, (nb,); the reserved word behind crc32 is 0, so the 64-bit word is the CRC).  `header`
+    is the stream's (channels, bits, samples), which same_audio compares beside the digests"""
+
+    def __init__(self, records, bucket_samples, header):
+        self.records, self.bucket_samples, self.header = records, bucket_samples, header
+        self.crc32, self.num_bytes = records[:, 0], records[:, 1]
+
+    def cpu(self):
+        """-> a numpy structured array (nb,) with the fields crc32, reserved and num_bytes"""
+        a = np.ascontiguousarray(self.records.cpu().numpy())
+        return a.view(DIGEST_DTYPE).reshape(a.shape[0])
+
+
 def _load():
     # torch bundles its own HIP runtime (same soname as /opt/rocm's).  Importing torch FIRST makes
     # liblinne_amd.so bind to that already-loaded runtime, so both share one HIP context: torch tensors can
@@ -235,6 +264,7 @@ def _load():
     L.LINNEAmd_DecodeWindowsDeviceLayout.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_CompareWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.POINTER(Diff), C.c_uint32, C.c_uint32]
     L.LINNEAmd_MeasureWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MeasureSpec), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_DigestWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(DigestSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -733,6 +763,75 @@ class Context:
         finally:
             for x in indexes:
                 x.close()
+
+    def digest_windows(self, windows, bucket_samples=0, group_frames=0, return_codes=False):
+        """the CRC-32 of the decoded PCM of many sample windows of resident .lnn streams in one call, per bucket of bucket_samples
+        samples, no PCM written (include/linne_amd.h LINNEAmd_DigestWindowsDevice).  windows: a sequence of (stream, index,
+        first_sample, num_samples) as decode_windows takes them; bucket_samples: one value or one per window (0: the whole window is
+        one bucket; the last bucket may be short).  -> a list of DigestTable, one per window, views of one allocation.  A digest is
+        zlib.crc32 of the window's samples as a WAV file holds them (interleaved, ceil(bits / 8) bytes little-endian, 8-bit
+        unsigned).  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with return_codes ->
+        (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
+        import torch
+        W = len(windows)
+        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
+        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
+        arr = (Window * max(W, 1))()
+        specs = (DigestSpec * max(W, 1))()
+        keep, counts = [], []
+        for i, (stream, index, first, n) in enumerate(windows):
+            t = self._stream_bytes(stream)
+            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            keep.append(t)
+            b = buckets[i]
+            counts.append(0 if n <= 0 else (1 if b == 0 else -(-n // b)))
+            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
+            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+            arr[i].d_pcm, arr[i].pcm_stride = None, 0
+        flat = torch.empty(max(sum(counts), 1) * 2, dtype=torch.int64, device=f"cuda:{self.device}")
+        recs, at = [], 0
+        for i, nb in enumerate(counts):
+            recs.append(flat[at:at + nb * 2].view(nb, 2))
+            specs[i].bucket_samples = buckets[i]
+            specs[i].d_out = flat.data_ptr() + 8 * at                  # (an empty view has no address of its own)
+            at += nb * 2
+        self._fence()
+        ret = lib.LINNEAmd_DigestWindowsDevice(self.h, arr, specs, W, int(group_frames))
+        codes = [int(arr[i].result) for i in range(W)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
+                raise LinneAmdError(f"DigestWindowsDevice -> {ret}: {msg}", ret, codes)
+        out = [DigestTable(recs[i], buckets[i], windows[i][1].header) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def digest_streams(self, streams, bucket_samples=0, group_frames=0):
+        """the CRC-32 of the decoded PCM of whole resident .lnn streams, per bucket: one index_streams call and one digest_windows
+        call over the whole streams -> a list of DigestTable.  With one bucket a stream's crc32 is zlib.crc32 of the `data` chunk of
+        the WAV file the decoder writes for it.  streams as index_streams takes them; bucket_samples as digest_windows takes it.
+        Raises LinneAmdError when a stream does not index or decode"""
+        if len(streams) == 0:
+            return []
+        ts = [self._stream_bytes(s) for s in streams]
+        indexes = self.index_streams(ts)
+        try:
+            return self.digest_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], bucket_samples=bucket_samples, group_frames=group_frames)
+        finally:
+            for x in indexes:
+                x.close()
+
+    def same_audio(self, stream_a, stream_b, bucket_samples=0):
+        """do two resident .lnn streams hold the same samples, whatever their presets, block sizes and mid/side choices?  ->
+        (True, None), or (False, k) with k the first bucket of bucket_samples samples whose digests differ, or (False, None) when
+        the channels, bits or sample counts differ.  One digest_streams call; equal CRC-32s of different audio are possible, one
+        case in 2^32 per bucket"""
+        a, b = self.digest_streams([stream_a, stream_b], bucket_samples=bucket_samples)
+        if any(a.header[k] != b.header[k] for k in ("num_channels", "bits_per_sample", "num_samples")):
+            return False, None
+        ne = ((a.records != b.records).any(dim=1)).nonzero()
+        return (True, None) if ne.numel() == 0 else (False, int(ne[0, 0]))
 
     def verify_streams(self, pairs, group_frames=0):
         """do these .lnn streams hold exactly these samples?  pairs: a sequence of (stream, pcm), a whole stream (as index_streams

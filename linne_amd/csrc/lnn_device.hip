@@ -51,6 +51,7 @@
 #include "lnn_k_windows.h"
 #include "lnn_k_compare.h"
 #include "lnn_k_measure.h"
+#include "lnn_k_digest.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -64,6 +65,7 @@ static_assert(LINNE_AMD_SPLICE_T_COPY == 71 && LINNE_AMD_SPLICE_T_HEADER == 72, 
 static_assert(LINNE_AMD_REPAIR_T_SOUND == 73 && LINNE_AMD_REPAIR_T_RUNS == 78, "the repair call's timing kinds are 73 to 78");
 static_assert(LINNE_AMD_COMPARE_T_COMPARE == 79, "the compare call's timing kind is 79");
 static_assert(LINNE_AMD_MEASURE_T_MEASURE == 80 && LINNE_AMD_MEASURE_T_COMMIT == 82, "the measure call's timing kinds are 80 to 82");
+static_assert(LINNE_AMD_DIGEST_T_DIGEST == 83 && LINNE_AMD_DIGEST_T_COMMIT == 85, "the digest call's timing kinds are 83 to 85");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2243,17 +2245,18 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
 /* the argument and index checks on one window, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are).  *r1 = the last block the window overlaps (nb: it reaches behind the last block); not set for a window of 0
  * samples.  WX_COMPARE: the window's PCM is read, not written, and LINNE_AMD_PCM_F32 is refused as on encode.  WX_MEASURE: the
- * window's d_pcm and pcm_stride are not looked at; ms is its struct LINNEAmdMeasureSpec, checked behind the range */
-enum WxMode { WX_PLACE = 0, WX_COMPARE = 1, WX_MEASURE = 2 };
+ * window's d_pcm and pcm_stride are not looked at; ms is its struct LINNEAmdMeasureSpec, checked behind the range.  WX_DIGEST: the
+ * same with ds, its struct LINNEAmdDigestSpec */
+enum WxMode { WX_PLACE = 0, WX_COMPARE = 1, WX_MEASURE = 2, WX_DIGEST = 3 };
 /* the buckets of a window of n samples (0 for none) */
 static uint64_t wx_buckets(uint64_t n, uint64_t b) { return n == 0 ? 0u : (b == 0 || b >= n) ? 1u : n / b + (n % b != 0); }
 static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, const struct LINNEAmdPcmLayout *ly, WxMode mode, const struct LINNEAmdMeasureSpec *ms,
-        char *err, size_t cap, uint64_t *r1)
+        const struct LINNEAmdDigestSpec *ds, char *err, size_t cap, uint64_t *r1)
 {
     const LINNEAmdStreamIndex *x = w->index;
-    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE;
+    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE, digest = mode == WX_DIGEST;
     err[0] = 0;
-    if (!x || !w->d_stream || (!measure && !w->d_pcm && w->num_samples)) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if (!x || !w->d_stream || (!measure && !digest && !w->d_pcm && w->num_samples)) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
     const uint64_t total = x->header.num_samples;
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
@@ -2263,6 +2266,11 @@ static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWind
         if ((uint64_t)(uintptr_t)ms->d_out & 7u) { snprintf(err, cap, "MeasureWindowsDevice: d_out is not 8-byte aligned"); return LNN_INVALID_ARGUMENT; }
         if (nb > 0xFFFFFFFFull) { snprintf(err, cap, "MeasureWindowsDevice: %llu buckets in one window: too many", (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
         if (ms->channel_stride < nb) { snprintf(err, cap, "MeasureWindowsDevice: channel_stride %llu < %llu buckets", (unsigned long long)ms->channel_stride, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
+    } else if (digest) {
+        const uint64_t nb = wx_buckets(w->num_samples, ds->bucket_samples);
+        if (!ds->d_out && nb) { snprintf(err, cap, "DigestWindowsDevice: null d_out"); return LNN_INVALID_ARGUMENT; }
+        if ((uint64_t)(uintptr_t)ds->d_out & 7u) { snprintf(err, cap, "DigestWindowsDevice: d_out is not 8-byte aligned"); return LNN_INVALID_ARGUMENT; }
+        if (nb > 0xFFFFFFFFull) { snprintf(err, cap, "DigestWindowsDevice: %llu buckets in one window: too many", (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
     } else if (ly) {
         const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, x->shape.num_channels, w->num_samples, !compare);
         if (why != SB_LY_OK) { snprintf(err, cap, "DecodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
@@ -2303,20 +2311,22 @@ static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_by
  * list carries two 64-bit words per window, its count of differing elements and their least key, which come back with them.
  * WX_MEASURE: the call is LINNEAmd_MeasureWindowsDevice -- every pass that would place reduces instead (k_wx_measure for k_wx_place),
  * into accumulators behind the passes' scratch that one launch in front of the first pass presets and one behind the last commits to
- * the d_out of the windows whose fail word is clear; the list carries a WxMeasure record beside every window record */
+ * the d_out of the windows whose fail word is clear; the list carries a WxMeasure record beside every window record.
+ * WX_DIGEST: the call is LINNEAmd_DigestWindowsDevice -- the same with k_wx_digest, 32-bit accumulators behind the tables of powers
+ * (lnn_k_digest.h) and a WxDigest record beside every window record */
 static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const struct LINNEAmdPcmLayout *layouts, uint32_t W, uint32_t group_frames, bool single, WxMode mode,
-        const struct LINNEAmdMeasureSpec *specs, WxPlan *plan, const uint32_t **fail_out)
+        const struct LINNEAmdMeasureSpec *specs, const struct LINNEAmdDigestSpec *dspecs, WxPlan *plan, const uint32_t **fail_out)
 {
-    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE;
+    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE, digest = mode == WX_DIGEST;
     const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
-    const char *who = measure ? "MeasureWindowsDevice" : compare ? "CompareWindowsDevice" : single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
+    const char *who = digest ? "DigestWindowsDevice" : measure ? "MeasureWindowsDevice" : compare ? "CompareWindowsDevice" : single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
     char text[sizeof(ctx->err)];
     /* 1. the checks per window; the live ones get their blocks and the group of their shape */
     uint64_t nlive = 0, total_rec = 0, total_crec = 0;
     for (uint32_t i = 0; i < W; i++) {
         uint64_t r1 = 0;
         plan[i].group = -1; plan[i].r0 = plan[i].nr = plan[i].ncomp = 0;
-        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, mode, measure ? &specs[i] : NULL, text, sizeof(text), &r1);
+        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, mode, measure ? &specs[i] : NULL, digest ? &dspecs[i] : NULL, text, sizeof(text), &r1);
         if (win[i].result != LNN_OK || win[i].num_samples == 0) continue;
         const LINNEAmdStreamIndex *x = win[i].index;
         const uint64_t lo = win[i].first_sample;
@@ -2342,7 +2352,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     /* 2. the lists, in pinned memory: fail words, saturation words (compare: and the difference words) | window records | block
      * records | the passes' COMPRESS records */
     const uint64_t o_fail = 0, o_diff = 2u * sizeof(uint32_t) * (uint64_t)W, back_bytes = o_diff + (compare ? 2u * sizeof(uint64_t) * (uint64_t)W : 0u);
-    const uint64_t o_win = align_up(back_bytes), o_mwin = align_up(o_win + sizeof(WxWindow) * nlive), o_rec = align_up(o_mwin + (measure ? sizeof(WxMeasure) * nlive : 0u)),
+    const uint64_t o_win = align_up(back_bytes), o_mwin = align_up(o_win + sizeof(WxWindow) * nlive), o_rec = align_up(o_mwin + (measure ? sizeof(WxMeasure) * nlive : digest ? sizeof(WxDigest) * nlive : 0u)),
             o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, list_bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
@@ -2355,7 +2365,8 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     uint32_t nrec = 0, ncrec = 0, nwin = 0;
     uint64_t scratch_bytes = 0;
     WxMeasure *h_mwin = (WxMeasure *)(hs_ + o_mwin);
-    uint64_t nacc = 0, nout = 0;                                   /* measure: accumulator records, (channel, bucket) records */
+    WxDigest *h_dwin = (WxDigest *)(hs_ + o_mwin);                 /* (digest: in the measure records' place) */
+    uint64_t nacc = 0, nout = 0;                                   /* measure: accumulator records, (channel, bucket) records; digest: accumulator words, buckets */
     for (uint32_t g = 0; g < ngroups; g++) {
         WxPass cur;
         auto fresh = [&](int check_only) { cur.group = g; cur.rec0 = nrec; cur.nrec = 0; cur.c0 = ncrec; cur.nc = 0; cur.seg_bytes = 0; cur.check_only = check_only; };
@@ -2400,6 +2411,16 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
                 mm.abase = nacc; mm.obase = nout; mm.fidx = i; mm.C = (uint32_t)C; mm.pad = 0u;
                 nacc += mm.ns * C * mm.nb; nout += C * mm.nb;
             }
+            if (digest) {
+                /* the slots are the measure call's; they lie 16 words or more apart, no two in one 64-byte line */
+                WxDigest &dd = h_dwin[wi];
+                const uint64_t n = win[i].num_samples, b = dspecs[i].bucket_samples;
+                dd.out = dspecs[i].d_out; dd.b = (b == 0 || b > n) ? n : b; dd.nb = wx_buckets(n, b); dd.n = n;
+                dd.ns = 1u; while (dd.ns < WXD_MAXSLOTS && (dd.b >> 12) >= 2u * dd.ns) dd.ns *= 2u;
+                dd.sstride = (uint32_t)((dd.nb + 15u) & ~(uint64_t)15u);    /* (nb < 2^32 - 15 where ns > 1: such a bucket has 8192 samples) */
+                dd.abase = nacc; dd.obase = nout; dd.fidx = i; dd.F = x->shape.num_channels * ((x->shape.bits_per_sample + 7u) >> 3);
+                nacc += dd.ns > 1u ? (uint64_t)dd.ns * dd.sstride : dd.nb; nout += dd.nb;
+            }
             const bool big = group_frames && plan[i].ncomp > group_frames;
             if (big) {
                 /* a window of more COMPRESS blocks than a pass takes: its Rice codes are checked first, in passes that place
@@ -2427,10 +2448,12 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
     const uint64_t o_acc = align_up(scratch_bytes);                /* (measure: the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (measure ? sizeof(struct LINNEAmdMeasure) * nacc : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (measure ? sizeof(struct LINNEAmdMeasure) * nacc : digest ? sizeof(uint32_t) * (WXD_POW_WORDS + nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     struct LINNEAmdMeasure *d_acc = (struct LINNEAmdMeasure *)(sd + o_acc);
     const WxMeasure *d_mwin = (const WxMeasure *)(wd + o_mwin);
+    uint32_t *d_pow = (uint32_t *)(sd + o_acc), *d_dacc = d_pow + WXD_POW_WORDS;   /* (digest: the tables of powers, then the accumulators) */
+    const WxDigest *d_dwin = (const WxDigest *)(wd + o_mwin);
     uint32_t *d_fail = (uint32_t *)(wd + o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + o_win);
     if (!ctx->outer_keep) ctx->nspans = 0;
@@ -2440,6 +2463,8 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
     const uint64_t ga_ = (nacc + WXM_THREADS - 1u) / WXM_THREADS, go_ = (nout + WXM_THREADS - 1u) / WXM_THREADS;    /* (grid-stride kernels) */
     const uint32_t mgrid_acc = (uint32_t)(ga_ < 65536u ? ga_ : 65536u), mgrid_out = (uint32_t)(go_ < 65536u ? go_ : 65536u);
     if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_PRESET, k_wx_measure_preset, dim3(mgrid_acc), dim3(WXM_THREADS), 0, ctx->stream, d_acc, nacc);
+    const uint64_t gd_ = (nacc + WXD_POW_WORDS + WXD_THREADS - 1u) / WXD_THREADS;
+    if (digest) SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_PRESET, k_wx_digest_preset, dim3((uint32_t)(gd_ < 65536u ? gd_ : 65536u)), dim3(WXD_THREADS), 0, ctx->stream, d_pow, d_dacc, nacc);
     for (const WxPass &p : passes) {
         const LINNEAmdStreamIndex *x = gx[p.group];
         const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
@@ -2472,6 +2497,9 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
         if (measure) {
             WxMeasureArgs ma; ma.p = la; ma.mwin = d_mwin; ma.acc = d_acc;
             SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_MEASURE, k_wx_measure, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
+        } else if (digest) {
+            WxDigestArgs da; da.p = la; da.dwin = d_dwin; da.acc = d_dacc; da.pow = d_pow;
+            SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_DIGEST, k_wx_digest, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, da);
         } else if (compare) {
             WxCompareArgs ca; ca.p = la; ca.diff = (unsigned long long *)(wd + o_diff);
             SX_LAUNCH(NULL, LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
@@ -2479,6 +2507,7 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
             SX_LAUNCH(NULL, LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
     }
     if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_COMMIT, k_wx_measure_commit, dim3(mgrid_out), dim3(WXM_THREADS), 0, ctx->stream, d_mwin, nwin, (const struct LINNEAmdMeasure *)d_acc, (const uint32_t *)d_fail, nout);
+    if (digest) SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_COMMIT, k_wx_digest_commit, dim3(mgrid_out), dim3(WXD_THREADS), 0, ctx->stream, d_dwin, nwin, (const uint32_t *)d_dacc, (const uint32_t *)d_pow, (const uint32_t *)d_fail, nout);
     /* 5. the fail words and the saturation words (and the difference words) behind them, with the call's one wait */
     HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
@@ -2491,14 +2520,15 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
 /* Both entry points behind their argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
  * with its text in ctx->err (behind the window's number unless the call is the single one) */
 static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdPcmLayout *layouts, struct LINNEAmdPcmLayout *layouts_out,
-        uint32_t num_windows, uint32_t group_frames, bool single, struct LINNEAmdDiff *diffs, const struct LINNEAmdMeasureSpec *specs = NULL)
+        uint32_t num_windows, uint32_t group_frames, bool single, struct LINNEAmdDiff *diffs, const struct LINNEAmdMeasureSpec *specs = NULL,
+        const struct LINNEAmdDigestSpec *dspecs = NULL)
 {
     const bool compare = diffs != NULL;
-    const WxMode mode = specs ? WX_MEASURE : compare ? WX_COMPARE : WX_PLACE;
+    const WxMode mode = dspecs ? WX_DIGEST : specs ? WX_MEASURE : compare ? WX_COMPARE : WX_PLACE;
     ctx->err[0] = 0;
     const uint32_t *fail = NULL;
     std::vector<WxPlan> plan;
-    int ret = items_try(ctx, [&] { plan.resize(num_windows); return wx_decode(ctx, windows, layouts, num_windows, group_frames, single, mode, specs, plan.data(), &fail); });
+    int ret = items_try(ctx, [&] { plan.resize(num_windows); return wx_decode(ctx, windows, layouts, num_windows, group_frames, single, mode, specs, dspecs, plan.data(), &fail); });
     /* a HIP error, no memory: the whole call fails (wx_decode has waited and recorded where it did not) */
     if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, num_windows, [&](uint32_t i) { windows[i].result = LNN_NG; }) != LNN_OK) return LNN_NG;
     /* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
@@ -2520,7 +2550,7 @@ static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const st
         if (plan[i].group >= 0 && fail)
             snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
                     fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
-        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, mode, specs ? &specs[i] : NULL, text, sizeof(text), &r1);
+        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, mode, specs ? &specs[i] : NULL, dspecs ? &dspecs[i] : NULL, text, sizeof(text), &r1);
         items_first_text(ctx, "window", i, single, text);
         return windows[i].result;
     }
@@ -2562,6 +2592,17 @@ extern "C" int LINNEAmd_MeasureWindowsDevice(struct LINNEAmdContext *ctx, struct
     if (num_windows == 0) return LNN_OK;
     if (!windows || !specs) { snprintf(ctx->err, sizeof(ctx->err), "MeasureWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     return wx_run(ctx, windows, NULL, NULL, num_windows, group_frames, false, NULL, specs);
+}
+
+/* the windows hashed to a table per window instead of written */
+extern "C" int LINNEAmd_DigestWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdDigestSpec *specs,
+        uint32_t num_windows, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (num_windows == 0) return LNN_OK;
+    if (!windows || !specs) { snprintf(ctx->err, sizeof(ctx->err), "DigestWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    return wx_run(ctx, windows, NULL, NULL, num_windows, group_frames, false, NULL, NULL, specs);
 }
 
 /* one window of one stream */

@@ -15,7 +15,10 @@
  *     and a WAV file that exist: exit 0 and "identical", or exit 1 and the first differing sample;
  *   - -M / --measure [BUCKET] STREAM.lnn measures a stream on the device without decoding it into memory
  *     (LINNEAmd_MeasureWindowsDevice): per channel the minimum, maximum, exact sum and sum of squares, mean and RMS of the whole
- *     stream on stdout, or with BUCKET one such line per BUCKET samples and channel.
+ *     stream on stdout, or with BUCKET one such line per BUCKET samples and channel;
+ *   - -D / --digest [BUCKET] STREAM.lnn digests a stream on the device without decoding it into memory
+ *     (LINNEAmd_DigestWindowsDevice): "crc32 %08x bytes %llu" on stdout, the CRC-32 and length of the `data` chunk of the WAV file
+ *     that -d writes for the stream, or with BUCKET one such line per BUCKET samples.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -31,7 +34,7 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
     const char *batch_dir;
     const char *files[4096];
@@ -46,6 +49,7 @@ static void usage(const char *argv0)
     printf("       %s [options] --batch OUTPUT_DIRECTORY INPUT_FILE_NAME... \n", argv0);
     printf("       %s -C STREAM.lnn PCM.wav \n", argv0);
     printf("       %s -M [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
+    printf("       %s -D [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -53,6 +57,7 @@ static void usage(const char *argv0)
            "  -V, --verify                           With -e: compare the stream with the input's samples on the device before writing it \n"
            "  -C, --compare                          Compare a .lnn stream with a WAV file's samples on the device (exit 0: identical) \n"
            "  -M, --measure                          Measure a .lnn stream on the device: min, max, sum, energy, mean, RMS per channel (and bucket) \n"
+           "  -D, --digest                           Digest a .lnn stream on the device: the CRC-32 of the decoded PCM as -d writes it (per bucket) \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -91,6 +96,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (strcmp(a, "-V") == 0 || strcmp(a, "--verify") == 0) o->verify = 1;
         else if (strcmp(a, "-C") == 0 || strcmp(a, "--compare") == 0) o->compare = 1;
         else if (strcmp(a, "-M") == 0 || strcmp(a, "--measure") == 0) o->measure = 1;
+        else if (strcmp(a, "-D") == 0 || strcmp(a, "--digest") == 0) o->digest = 1;
         else if (strcmp(a, "-c") == 0 || strcmp(a, "--no-crc-check") == 0) o->no_crc = 1;
         else if (strcmp(a, "-l") == 0 || strcmp(a, "--enable-learning") == 0) o->learning = 1;
         else if (strcmp(a, "-B") == 0 || strcmp(a, "--block-at-a-time") == 0) o->block_at_a_time = 1;
@@ -254,6 +260,47 @@ done:
     return rc;
 }
 
+/* -D: the stream goes to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_DigestWindowsDevice window over the whole stream
+ * answer, and the table comes back: one line, or with a bucket one line per bucket */
+static int digest_one(const char *lnn_path, uint64_t bucket)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0;
+    struct LINNEAmdContext *ctx = NULL;
+    struct LINNEAmdStreamIndex *index = NULL;
+    struct LINNEAmdWindow w;
+    struct LINNEAmdDigestSpec spec;
+    struct LINNEAmdDigest *tab = NULL;
+    struct LINNEHeader h;
+    void *d_stream = NULL, *d_out = NULL;
+    uint64_t n, nb, k;
+    int ret = LINNE_APIRESULT_OK, rc = 1;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    n = h.num_samples;
+    nb = n == 0 ? 0 : (bucket == 0 || bucket >= n) ? 1 : (n + bucket - 1) / bucket;
+    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { fprintf(stderr, "Failed to create a device context. \n"); goto done; }
+    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, buf, size, hipMemcpyHostToDevice) != hipSuccess
+            || hipMalloc(&d_out, nb ? sizeof(*tab) * nb : 1) != hipSuccess) { fprintf(stderr, "Failed to copy the stream to the device. \n"); goto done; }
+    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { fprintf(stderr, "Failed to digest! the stream does not index: %d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    memset(&w, 0, sizeof(w)); memset(&spec, 0, sizeof(spec));
+    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n;
+    spec.bucket_samples = bucket; spec.d_out = d_out;
+    if ((ret = LINNEAmd_DigestWindowsDevice(ctx, &w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to digest! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * nb : 1)) || (nb && hipMemcpy(tab, d_out, sizeof(*tab) * nb, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    /* (a stream of no samples has the empty string's digest) */
+    if (nb == 0) printf("crc32 %08x bytes %llu \n", 0u, 0ull);
+    for (k = 0; k < nb; k++) printf("crc32 %08x bytes %llu \n", tab[k].crc32, (unsigned long long)tab[k].num_bytes);
+    rc = 0;
+done:
+    if (index) LINNEAmd_StreamIndexDestroy(index);
+    if (d_out) (void)hipFree(d_out);
+    if (d_stream) (void)hipFree(d_stream);
+    if (ctx) LINNEAmd_ContextDestroy(ctx);
+    free(tab); free(buf);
+    return rc;
+}
+
 static int encode_one(struct LINNEEncoder *enc, const struct options *o, const char *in_path, const char *out_path)
 {
     struct wav_pcm wav;
@@ -390,21 +437,30 @@ int main(int argc, char **argv)
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
     if (o.repair) {
-        if (o.encode || o.decode || o.compare || o.measure || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.compare || o.measure || o.digest || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return repair_one(o.files[0], o.files[1]);
     }
     if (o.compare) {
-        if (o.encode || o.decode || o.measure || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -C takes a stream and a WAV file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.measure || o.digest || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -C takes a stream and a WAV file name and no other mode. \n", argv[0]); return 1; }
         return compare_one(o.files[0], o.files[1]);
     }
     if (o.measure) {
         unsigned long long bucket = 0;
-        if (o.encode || o.decode || o.verify || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -M takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
+        if (o.encode || o.decode || o.digest || o.verify || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -M takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
         if (o.num_files == 2) {
             char *end; bucket = strtoull(o.files[0], &end, 10);
             if (*end != '\0' || o.files[0][0] < '0' || o.files[0][0] > '9' || bucket == 0) { fprintf(stderr, "%s: bucket sample count is out of range. \n", argv[0]); return 1; }
         }
         return measure_one(o.files[o.num_files - 1], bucket);
+    }
+    if (o.digest) {
+        unsigned long long bucket = 0;
+        if (o.encode || o.decode || o.verify || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -D takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
+        if (o.num_files == 2) {
+            char *end; bucket = strtoull(o.files[0], &end, 10);
+            if (*end != '\0' || o.files[0][0] < '0' || o.files[0][0] > '9' || bucket == 0) { fprintf(stderr, "%s: bucket sample count is out of range. \n", argv[0]); return 1; }
+        }
+        return digest_one(o.files[o.num_files - 1], bucket);
     }
     if (o.verify && !o.encode) { fprintf(stderr, "%s: -V goes with encode mode (-e) only. \n", argv[0]); return 1; }
     if (o.encode && o.decode) { fprintf(stderr, "%s: encode and decode mode cannot specify simultaneously. \n", argv[0]); return 1; }
