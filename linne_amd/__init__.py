@@ -12,6 +12,7 @@ There is no CPU fallback: importing works without a GPU (so the symbol table can
 compute call needs a HIP device, and a missing library raises ImportError.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -589,6 +590,66 @@ class Context:
             if own:
                 index.close()
 
+    def _windows_array(self, windows, extra=0):
+        """the Window array of a windows call.  windows: (stream, index, first_sample, num_samples) as decode_windows takes them,
+        each followed by `extra` fields of the caller's own -> (the array, with no PCM named yet; the stream tensors, to be kept alive
+        over the call; (index, first, n) per window, n the samples asked for, negative when the range is)"""
+        arr = (Window * max(len(windows), 1))()
+        keep, ranges = [], []
+        for i, w in enumerate(windows):
+            stream, index, first, n = w[:len(w) - extra]
+            t = self._stream_bytes(stream)
+            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            keep.append(t)
+            ranges.append((index, first, n))
+            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
+            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+            arr[i].d_pcm, arr[i].pcm_stride = None, 0
+        return arr, keep, ranges
+
+    def _windows_codes(self, ret, arr, W, what, return_codes):
+        """the per-window LINNEApiResults behind a windows call; raises LinneAmdError unless the call succeeded or, with return_codes,
+        only windows failed"""
+        codes = [int(arr[i].result) for i in range(W)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
+                raise LinneAmdError(f"{what} -> {ret}: {msg}", ret, codes)
+        return codes
+
+    def _bucket_tables(self, bucket_samples, ranges, words, per_channel):
+        """the tables of a call that answers per bucket: bucket_samples one value or one per window -> (the bucket length per window;
+        per window an int64 view (nb, words) -- per_channel: (C, nb, words) -- of one allocation; the views' device addresses; the
+        bucket counts nb)"""
+        import torch
+        W = len(ranges)
+        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
+        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
+        counts = [0 if n <= 0 else (1 if b == 0 else -(-n // b)) for (_, _, n), b in zip(ranges, buckets)]
+        shapes = [((x.header["num_channels"],) if per_channel else ()) + (nb, words) for (x, _, _), nb in zip(ranges, counts)]
+        sizes = [math.prod(shape) for shape in shapes]
+        flat = torch.empty(max(sum(sizes), words), dtype=torch.int64, device=f"cuda:{self.device}")
+        views, addresses, at = [], [], 0
+        for shape, size in zip(shapes, sizes):
+            views.append(flat[at:at + size].view(*shape))
+            addresses.append(flat.data_ptr() + 8 * at)                 # (an empty view has no address of its own)
+            at += size
+        return buckets, views, addresses, counts
+
+    def _over_whole_streams(self, streams, call, **kw):
+        """one index_streams call and one `call` over the whole streams"""
+        if len(streams) == 0:
+            return []
+        ts = [self._stream_bytes(s) for s in streams]
+        indexes = self.index_streams(ts)
+        try:
+            return call([(t, x, 0, None) for t, x in zip(ts, indexes)], **kw)
+        finally:
+            for x in indexes:
+                x.close()
+
     def decode_windows(self, windows, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False, s24=False,
                        return_saturated=False):
         """many sample windows of resident .lnn streams in one call (include/linne_amd.h LINNEAmd_DecodeWindowsDevice).  windows: a
@@ -605,17 +666,8 @@ class Context:
         any strides.  return_saturated appends the list of the windows' flags "a sample was clipped" to the result"""
         import torch
         W = len(windows)
-        arr = (Window * max(W, 1))()
-        keep, shapes = [], []
-        for i, (stream, index, first, n) in enumerate(windows):
-            t = self._stream_bytes(stream)
-            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
-            first = int(first)
-            n = index.header["num_samples"] - first if n is None else int(n)
-            keep.append(t)
-            shapes.append((index.header["num_channels"], max(n, 0)))
-            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
-            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
+        arr, keep, ranges = self._windows_array(windows)
+        shapes = [(x.header["num_channels"], max(n, 0)) for x, _, n in ranges]
         dev = f"cuda:{self.device}"
         if s24:
             assert dtype in (None, torch.uint8), "s24 samples are uint8 triples"
@@ -659,11 +711,7 @@ class Context:
             ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
         else:
             ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
-        codes = [int(arr[i].result) for i in range(W)]
-        if ret != 0:
-            msg = lib.LINNEAmd_GetLastError(self.h).decode()
-            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
-                raise LinneAmdError(f"DecodeWindowsDevice -> {ret}: {msg}", ret, codes)
+        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice", return_codes)
         res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
         return res[0] if len(res) == 1 else res
 
@@ -678,31 +726,20 @@ class Context:
         with return_codes -> (answers, codes), a failing window's answer is None, and only a failure of the whole call raises.  The
         PCM is only read"""
         W = len(windows)
-        arr = (Window * max(W, 1))()
+        arr, keep, ranges = self._windows_array(windows, extra=1)
         lays = (PcmLayout * max(W, 1))()
         diffs = (Diff * max(W, 1))()
-        keep = []
-        for i, (stream, index, first, n, pcm) in enumerate(windows):
-            t = self._stream_bytes(stream)
-            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
-            first = int(first)
-            n = index.header["num_samples"] - first if n is None else int(n)
+        for i, ((index, _, n), w) in enumerate(zip(ranges, windows)):
+            pcm = w[4]
             fmt, cs, ss, nch, ns, _ = self._pcm_layout(pcm, f"window {i}: pcm")
             assert pcm.device.index == self.device, f"window {i}: the PCM is on {pcm.device}, the context on cuda:{self.device}"
             assert (nch, ns) == (index.header["num_channels"], max(n, 0)), \
                 f"window {i} is {(index.header['num_channels'], max(n, 0))}, its pcm holds {(nch, ns)}"
-            keep.append((t, pcm))
-            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
-            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
             arr[i].d_pcm, arr[i].pcm_stride = pcm.data_ptr(), ns
             lays[i].format, lays[i].channel_stride, lays[i].sample_stride = fmt, cs, ss
         self._fence()
         ret = lib.LINNEAmd_CompareWindowsDevice(self.h, arr, lays, diffs, W, int(group_frames))
-        codes = [int(arr[i].result) for i in range(W)]
-        if ret != 0:
-            msg = lib.LINNEAmd_GetLastError(self.h).decode()
-            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
-                raise LinneAmdError(f"CompareWindowsDevice -> {ret}: {msg}", ret, codes)
+        codes = self._windows_codes(ret, arr, W, "CompareWindowsDevice", return_codes)
         out = [(int(diffs[i].num_differing), int(diffs[i].first_sample), int(diffs[i].first_channel)) if codes[i] == 0 else None for i in range(W)]
         return (out, codes) if return_codes else out
 
@@ -714,39 +751,15 @@ class Context:
         allocation.  Every number is exact and is what numpy gives on decode_windows' int32 samples.  Errors follow
         compare_windows: LinneAmdError with .code and .codes when a window fails; with return_codes -> (answers, codes), a failing
         window's answer is None, and only a failure of the whole call raises"""
-        import torch
         W = len(windows)
-        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
-        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
-        arr = (Window * max(W, 1))()
+        arr, keep, ranges = self._windows_array(windows)
+        buckets, recs, addresses, counts = self._bucket_tables(bucket_samples, ranges, 4, True)
         specs = (MeasureSpec * max(W, 1))()
-        keep, shapes = [], []
-        for i, (stream, index, first, n) in enumerate(windows):
-            t = self._stream_bytes(stream)
-            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
-            first = int(first)
-            n = index.header["num_samples"] - first if n is None else int(n)
-            keep.append(t)
-            b = buckets[i]
-            nb = 0 if n <= 0 else (1 if b == 0 else -(-n // b))
-            shapes.append((index.header["num_channels"], nb))
-            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
-            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
-            arr[i].d_pcm, arr[i].pcm_stride = None, 0
-        flat = torch.empty(max(sum(c * nb for c, nb in shapes), 1) * 4, dtype=torch.int64, device=f"cuda:{self.device}")
-        recs, at = [], 0
-        for i, (c, nb) in enumerate(shapes):
-            recs.append(flat[at:at + c * nb * 4].view(c, nb, 4))
-            specs[i].bucket_samples, specs[i].channel_stride = buckets[i], nb
-            specs[i].d_out = flat.data_ptr() + 8 * at                  # (an empty view has no address of its own)
-            at += c * nb * 4
+        for i in range(W):
+            specs[i].bucket_samples, specs[i].d_out, specs[i].channel_stride = buckets[i], addresses[i], counts[i]
         self._fence()
         ret = lib.LINNEAmd_MeasureWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = [int(arr[i].result) for i in range(W)]
-        if ret != 0:
-            msg = lib.LINNEAmd_GetLastError(self.h).decode()
-            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
-                raise LinneAmdError(f"MeasureWindowsDevice -> {ret}: {msg}", ret, codes)
+        codes = self._windows_codes(ret, arr, W, "MeasureWindowsDevice", return_codes)
         out = [Measurement(recs[i], buckets[i]) if codes[i] == 0 else None for i in range(W)]
         return (out, codes) if return_codes else out
 
@@ -754,15 +767,7 @@ class Context:
         """min, max, sum and sum of squares of whole resident .lnn streams, per channel and bucket: one index_streams call and one
         measure_windows call over the whole streams -> a list of Measurement.  streams as index_streams takes them; bucket_samples as
         measure_windows takes it.  Raises LinneAmdError when a stream does not index or decode"""
-        if len(streams) == 0:
-            return []
-        ts = [self._stream_bytes(s) for s in streams]
-        indexes = self.index_streams(ts)
-        try:
-            return self.measure_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], bucket_samples=bucket_samples, group_frames=group_frames)
-        finally:
-            for x in indexes:
-                x.close()
+        return self._over_whole_streams(streams, self.measure_windows, bucket_samples=bucket_samples, group_frames=group_frames)
 
     def digest_windows(self, windows, bucket_samples=0, group_frames=0, return_codes=False):
         """the CRC-32 of the decoded PCM of many sample windows of resident .lnn streams in one call, per bucket of bucket_samples
@@ -772,38 +777,15 @@ class Context:
         zlib.crc32 of the window's samples as a WAV file holds them (interleaved, ceil(bits / 8) bytes little-endian, 8-bit
         unsigned).  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with return_codes ->
         (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
-        import torch
         W = len(windows)
-        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
-        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
-        arr = (Window * max(W, 1))()
+        arr, keep, ranges = self._windows_array(windows)
+        buckets, recs, addresses, _ = self._bucket_tables(bucket_samples, ranges, 2, False)
         specs = (DigestSpec * max(W, 1))()
-        keep, counts = [], []
-        for i, (stream, index, first, n) in enumerate(windows):
-            t = self._stream_bytes(stream)
-            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
-            first = int(first)
-            n = index.header["num_samples"] - first if n is None else int(n)
-            keep.append(t)
-            b = buckets[i]
-            counts.append(0 if n <= 0 else (1 if b == 0 else -(-n // b)))
-            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
-            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
-            arr[i].d_pcm, arr[i].pcm_stride = None, 0
-        flat = torch.empty(max(sum(counts), 1) * 2, dtype=torch.int64, device=f"cuda:{self.device}")
-        recs, at = [], 0
-        for i, nb in enumerate(counts):
-            recs.append(flat[at:at + nb * 2].view(nb, 2))
-            specs[i].bucket_samples = buckets[i]
-            specs[i].d_out = flat.data_ptr() + 8 * at                  # (an empty view has no address of its own)
-            at += nb * 2
+        for i in range(W):
+            specs[i].bucket_samples, specs[i].d_out = buckets[i], addresses[i]
         self._fence()
         ret = lib.LINNEAmd_DigestWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = [int(arr[i].result) for i in range(W)]
-        if ret != 0:
-            msg = lib.LINNEAmd_GetLastError(self.h).decode()
-            if not (return_codes and msg.startswith("window ")):       # (a failing window's text starts with its number)
-                raise LinneAmdError(f"DigestWindowsDevice -> {ret}: {msg}", ret, codes)
+        codes = self._windows_codes(ret, arr, W, "DigestWindowsDevice", return_codes)
         out = [DigestTable(recs[i], buckets[i], windows[i][1].header) if codes[i] == 0 else None for i in range(W)]
         return (out, codes) if return_codes else out
 
@@ -812,15 +794,7 @@ class Context:
         call over the whole streams -> a list of DigestTable.  With one bucket a stream's crc32 is zlib.crc32 of the `data` chunk of
         the WAV file the decoder writes for it.  streams as index_streams takes them; bucket_samples as digest_windows takes it.
         Raises LinneAmdError when a stream does not index or decode"""
-        if len(streams) == 0:
-            return []
-        ts = [self._stream_bytes(s) for s in streams]
-        indexes = self.index_streams(ts)
-        try:
-            return self.digest_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], bucket_samples=bucket_samples, group_frames=group_frames)
-        finally:
-            for x in indexes:
-                x.close()
+        return self._over_whole_streams(streams, self.digest_windows, bucket_samples=bucket_samples, group_frames=group_frames)
 
     def same_audio(self, stream_a, stream_b, bucket_samples=0):
         """do two resident .lnn streams hold the same samples, whatever their presets, block sizes and mid/side choices?  ->

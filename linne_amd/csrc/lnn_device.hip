@@ -48,7 +48,7 @@
 #include "lnn_k_rice.h"
 #include "lnn_k_stream.h"
 #include "lnn_k_index_batch.h"
-#include "lnn_k_windows.h"
+#include "lnn_k_windows.h"              /* (brings lnn_windows_plan.h: the host's plan of a windows call) */
 #include "lnn_k_compare.h"
 #include "lnn_k_measure.h"
 #include "lnn_k_digest.h"
@@ -1876,14 +1876,6 @@ extern "C" int LINNEAmd_StreamIndexHeader(const struct LINNEAmdStreamIndex *inde
 }
 extern "C" uint32_t LINNEAmd_StreamIndexNumBlocks(const struct LINNEAmdStreamIndex *index) { return index ? index->nb : 0u; }
 
-/* the block holding sample s (s < covered): the last r < nb with first[r] <= s */
-static uint64_t sx_block_of(const LINNEAmdStreamIndex *x, uint64_t s)
-{
-    uint64_t lo = 0, hi = x->nb;
-    while (hi - lo > 1u) { const uint64_t mid = lo + ((hi - lo) >> 1); if (x->h_first[mid] <= s) lo = mid; else hi = mid; }
-    return lo;
-}
-
 extern "C" int LINNEAmd_StreamIndexBlocks(const struct LINNEAmdStreamIndex *index, const uint64_t **off, const uint64_t **first,
         const uint32_t **size, const uint32_t **type, const uint32_t **nsmp)
 {
@@ -2240,44 +2232,167 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
 }
 
 /* ================================================================================================
- * sample windows of resident streams: many in one call, or one (lnn_k_windows.h)
+ * sample windows of resident streams: many in one call, or one (lnn_k_windows.h; the plan: lnn_windows_plan.h)
  * ============================================================================================== */
-/* the argument and index checks on one window, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
- * window's fields are).  *r1 = the last block the window overlaps (nb: it reaches behind the last block); not set for a window of 0
- * samples.  WX_COMPARE: the window's PCM is read, not written, and LINNE_AMD_PCM_F32 is refused as on encode.  WX_MEASURE: the
- * window's d_pcm and pcm_stride are not looked at; ms is its struct LINNEAmdMeasureSpec, checked behind the range.  WX_DIGEST: the
- * same with ds, its struct LINNEAmdDigestSpec */
-enum WxMode { WX_PLACE = 0, WX_COMPARE = 1, WX_MEASURE = 2, WX_DIGEST = 3 };
-/* the buckets of a window of n samples (0 for none) */
-static uint64_t wx_buckets(uint64_t n, uint64_t b) { return n == 0 ? 0u : (b == 0 || b >= n) ? 1u : n / b + (n % b != 0); }
-static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWindow *w, const struct LINNEAmdPcmLayout *ly, WxMode mode, const struct LINNEAmdMeasureSpec *ms,
-        const struct LINNEAmdDigestSpec *ds, char *err, size_t cap, uint64_t *r1)
+struct WxCall;
+/* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
+ * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
+struct WxLaunch { const WxBucket *side; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout; };
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The four calls are the
+ * four constant instances below; a launch that a consumer does not have is NULL */
+struct WxConsumer {
+    const char *name;                   /* in the call's texts */
+    uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
+    void (*back_preset)(uint32_t *back, uint32_t W);
+    WxBucketing bucketing;              /* buckets: a WxBucket beside every window record, accumulators preset in front of the first pass and committed behind the last */
+    uint64_t acc_unit, acc_prefix;      /* an accumulator's bytes; units in front of the accumulators */
+    int (*check)(const WxCall &c, uint32_t i, char *err, size_t cap);      /* the window's own arguments, behind the range check */
+    void (*describe)(const WxCall &c, uint32_t i, WxRange &r);             /* where its samples go: its WxWindow's fields, its bucket spec */
+    int (*preset)(LINNEAmdContext *ctx, const WxLaunch &l);
+    int (*pass)(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la);
+    int (*commit)(LINNEAmdContext *ctx, const WxLaunch &l);
+    /* an OK window's answer into the caller's arrays; words: all that came back (fail words first), NULL for a window that took no pass */
+    void (*read_back)(const WxCall &c, uint32_t i, const uint32_t *words);
+};
+struct WxCall {
+    const WxConsumer *use;
+    bool single;                        /* the call is LINNEAmd_DecodeStreamDevice, which its texts then name */
+    struct LINNEAmdWindow *win; uint32_t W, group_frames;
+    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure and digest their specs */
+    void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff */
+};
+static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
+    WxCall c;
+    c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers;
+    return c;
+}
+/* a lane per unit, in a grid-stride kernel */
+static dim3 wx_grid(uint64_t n) { const uint64_t g = (n + WXB_THREADS - 1u) / WXB_THREADS; return dim3((uint32_t)(g < 65536u ? g : 65536u)); }
+
+/* ---- place, and compare, which reads the PCM that place writes (LINNE_AMD_PCM_F32 is refused as on encode) ---- */
+static int wx_pcm_check(const WxCall &c, uint32_t i, bool writes, char *err, size_t cap)
+{
+    const struct LINNEAmdWindow *w = &c.win[i];
+    const uint32_t C = w->index->shape.num_channels;
+    if (c.specs) {
+        const struct LINNEAmdPcmLayout *ly = (const struct LINNEAmdPcmLayout *)c.specs + i;
+        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, C, w->num_samples, writes);
+        if (why != SB_LY_OK) { snprintf(err, cap, "DecodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
+    } else if (C > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static int wx_place_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, true, err, cap); }
+static int wx_compare_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, false, err, cap); }
+static void wx_pcm_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdPcmLayout *ly = (const struct LINNEAmdPcmLayout *)c.specs;
+    r.out = c.win[i].d_pcm;
+    if (ly) { r.fmt = ly[i].format; r.stride = ly[i].channel_stride; r.sstride = ly[i].sample_stride; }
+    else { r.fmt = LINNE_AMD_PCM_S32; r.stride = c.win[i].pcm_stride; r.sstride = 1u; }
+}
+static int wx_place_pass(LINNEAmdContext *ctx, const WxLaunch &, const WxPlaceArgs &la) { SX_LAUNCH(NULL, LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la); return LNN_OK; }
+/* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
+static void wx_place_read_back(const WxCall &c, uint32_t i, const uint32_t *words) { if (c.answers) ((struct LINNEAmdPcmLayout *)c.answers)[i].saturated = (words && words[c.W + i]) ? 1u : 0u; }
+/* compare: two 64-bit words per window, its count of differing elements (0) and their least key (~0) */
+static void wx_compare_back_preset(uint32_t *back, uint32_t W) { uint64_t *d = (uint64_t *)back; for (uint32_t i = 0; i < W; i++) { d[2u * i] = 0u; d[2u * i + 1u] = ~(uint64_t)0; } }
+static int wx_compare_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxCompareArgs ca; ca.p = la; ca.diff = (unsigned long long *)l.back;
+    SX_LAUNCH(NULL, LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
+    return LNN_OK;
+}
+/* (a failing window's diffs[i] stays too; an OK window of no samples took no pass and differs nowhere) */
+static void wx_compare_read_back(const WxCall &c, uint32_t i, const uint32_t *words)
+{
+    const uint64_t *dw = words ? (const uint64_t *)(words + 2u * (uint64_t)c.W) + 2u * (uint64_t)i : NULL;
+    const uint64_t cnt = dw ? dw[0] : 0u;
+    struct LINNEAmdDiff &d = ((struct LINNEAmdDiff *)c.answers)[i];
+    d.num_differing = cnt; d.first_sample = cnt ? c.win[i].first_sample + (dw[1] >> 3) : 0u; d.first_channel = cnt ? (uint32_t)(dw[1] & 7u) : 0u; d.reserved = 0u;
+}
+
+/* ---- measure and digest: the window's d_pcm and pcm_stride are not looked at; its spec names buckets and a table ---- */
+static int wx_bucket_check(const char *who, uint64_t n, uint64_t b, const void *d_out, char *err, size_t cap)
+{
+    const uint64_t nb = wx_buckets(n, b);
+    if (!d_out && nb) { snprintf(err, cap, "%s: null d_out", who); return LNN_INVALID_ARGUMENT; }
+    if ((uint64_t)(uintptr_t)d_out & 7u) { snprintf(err, cap, "%s: d_out is not 8-byte aligned", who); return LNN_INVALID_ARGUMENT; }
+    if (nb > 0xFFFFFFFFull) { snprintf(err, cap, "%s: %llu buckets in one window: too many", who, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static int wx_measure_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdMeasureSpec &ms = ((const struct LINNEAmdMeasureSpec *)c.specs)[i];
+    const uint64_t nb = wx_buckets(c.win[i].num_samples, ms.bucket_samples);
+    SX_TRY(wx_bucket_check(c.use->name, c.win[i].num_samples, ms.bucket_samples, ms.d_out, err, cap));
+    if (ms.channel_stride < nb) { snprintf(err, cap, "%s: channel_stride %llu < %llu buckets", c.use->name, (unsigned long long)ms.channel_stride, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static int wx_digest_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdDigestSpec &ds = ((const struct LINNEAmdDigestSpec *)c.specs)[i];
+    return wx_bucket_check(c.use->name, c.win[i].num_samples, ds.bucket_samples, ds.d_out, err, cap);
+}
+static void wx_measure_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdMeasureSpec &ms = ((const struct LINNEAmdMeasureSpec *)c.specs)[i];
+    r.bucket_samples = ms.bucket_samples; r.bucket_out = ms.d_out; r.bucket_cstride = ms.channel_stride;
+}
+static void wx_digest_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdDigestSpec &ds = ((const struct LINNEAmdDigestSpec *)c.specs)[i];
+    r.bucket_samples = ds.bucket_samples; r.bucket_out = ds.d_out;
+}
+static int wx_measure_preset(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_PRESET, k_wx_measure_preset, wx_grid(l.nacc), dim3(WXB_THREADS), 0, ctx->stream, (struct LINNEAmdMeasure *)l.acc, l.nacc); return LNN_OK; }
+static int wx_measure_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxMeasureArgs ma; ma.p = la; ma.mwin = l.side; ma.acc = (struct LINNEAmdMeasure *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_MEASURE, k_wx_measure, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
+    return LNN_OK;
+}
+static int wx_measure_commit(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_COMMIT, k_wx_measure_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, (const struct LINNEAmdMeasure *)l.acc, l.fail, l.nout); return LNN_OK; }
+/* digest: the tables of powers (WXD_POW_WORDS words), then the 32-bit accumulators */
+static int wx_digest_preset(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    uint32_t *pow = (uint32_t *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_PRESET, k_wx_digest_preset, wx_grid(l.nacc + WXD_POW_WORDS), dim3(WXB_THREADS), 0, ctx->stream, pow, pow + WXD_POW_WORDS, l.nacc);
+    return LNN_OK;
+}
+static int wx_digest_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxDigestArgs da; da.p = la; da.dwin = l.side; da.pow = (const uint32_t *)l.acc; da.acc = (uint32_t *)l.acc + WXD_POW_WORDS;
+    SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_DIGEST, k_wx_digest, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, da);
+    return LNN_OK;
+}
+static int wx_digest_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    const uint32_t *pow = (const uint32_t *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_COMMIT, k_wx_digest_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, pow + WXD_POW_WORDS, pow, l.fail, l.nout);
+    return LNN_OK;
+}
+
+static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back };
+static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back };
+static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL };
+static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL };
+
+/* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
+ * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
+ * block); not set for a window of 0 samples */
+static int wx_check_window(const LINNEAmdContext *ctx, const WxCall &c, uint32_t i, char *err, size_t cap, uint64_t *r1)
+{
+    const struct LINNEAmdWindow *w = &c.win[i];
     const LINNEAmdStreamIndex *x = w->index;
-    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE, digest = mode == WX_DIGEST;
     err[0] = 0;
-    if (!x || !w->d_stream || (!measure && !digest && !w->d_pcm && w->num_samples)) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if (!x || !w->d_stream) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    if (c.use->bucketing == WX_NO_BUCKETS && !w->d_pcm && w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
     const uint64_t total = x->header.num_samples;
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
-    if (measure) {
-        const uint64_t nb = wx_buckets(w->num_samples, ms->bucket_samples);
-        if (!ms->d_out && nb) { snprintf(err, cap, "MeasureWindowsDevice: null d_out"); return LNN_INVALID_ARGUMENT; }
-        if ((uint64_t)(uintptr_t)ms->d_out & 7u) { snprintf(err, cap, "MeasureWindowsDevice: d_out is not 8-byte aligned"); return LNN_INVALID_ARGUMENT; }
-        if (nb > 0xFFFFFFFFull) { snprintf(err, cap, "MeasureWindowsDevice: %llu buckets in one window: too many", (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
-        if (ms->channel_stride < nb) { snprintf(err, cap, "MeasureWindowsDevice: channel_stride %llu < %llu buckets", (unsigned long long)ms->channel_stride, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
-    } else if (digest) {
-        const uint64_t nb = wx_buckets(w->num_samples, ds->bucket_samples);
-        if (!ds->d_out && nb) { snprintf(err, cap, "DigestWindowsDevice: null d_out"); return LNN_INVALID_ARGUMENT; }
-        if ((uint64_t)(uintptr_t)ds->d_out & 7u) { snprintf(err, cap, "DigestWindowsDevice: d_out is not 8-byte aligned"); return LNN_INVALID_ARGUMENT; }
-        if (nb > 0xFFFFFFFFull) { snprintf(err, cap, "DigestWindowsDevice: %llu buckets in one window: too many", (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
-    } else if (ly) {
-        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, x->shape.num_channels, w->num_samples, !compare);
-        if (why != SB_LY_OK) { snprintf(err, cap, "DecodeStreamDevice: %s", sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
-    } else if (x->shape.num_channels > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
+    SX_TRY(c.use->check(c, i, err, cap));
     if (w->num_samples == 0) return LNN_OK;
     const uint64_t hi = w->first_sample + w->num_samples;
-    *r1 = (hi - 1u < x->covered) ? sx_block_of(x, hi - 1u) : x->nb;
+    *r1 = (hi - 1u < x->covered) ? wx_block_of(x->h_first, x->nb, hi - 1u) : x->nb;
     if (x->fail_block >= 0 && (uint64_t)x->fail_block <= *r1) {
         snprintf(err, cap, "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
                 x->fail_code == LNN_NG ? "a block no encoder writes" : "damaged or truncated stream");
@@ -2286,193 +2401,70 @@ static int wx_check_window(const LINNEAmdContext *ctx, const struct LINNEAmdWind
     return LNN_OK;
 }
 
-struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
-struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
-/* the buffers of one pass in ctx->sdec */
-struct WxScratch { uint64_t o_nsmp, o_bpos, o_bend, o_eb, o_prm, o_data, o_seg, bytes; };
-static WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_bytes)
+/* LNN_OK: every window has its result (the words that came back, the Rice fail words first, are in fail_out); anything else fails
+ * the whole call.  The plan (lnn_windows_plan.h) says which records go into which pass; a pass gathers, parses, Rice-decodes and
+ * checks its COMPRESS blocks, synthesises them unless it is check-only, and hands its records to the call's consumer */
+static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const uint32_t **fail_out)
 {
-    WxScratch s; uint64_t at = 0;
-    s.o_nsmp = at; at = align_up(at + sizeof(uint32_t) * (nc + 1u));
-    s.o_bpos = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
-    s.o_bend = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
-    s.o_eb = at; at = align_up(at + sizeof(uint64_t) * (nc + 1u));
-    s.o_prm = at; at = align_up(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * (uint64_t)nc);
-    s.o_data = at; at = align_up(at + sizeof(int32_t) * (uint64_t)C * S * nc);
-    s.o_seg = at; at = align_up(at + seg_bytes + 16u);
-    s.bytes = at;
-    return s;
-}
-#define WX_MAXGROUPS 64
-
-/* LNN_OK: every window has its result (the Rice fail words are in fail_out); anything else fails the whole call.  single: the call
- * is LINNEAmd_DecodeStreamDevice, which its texts then name.  compare: the call is LINNEAmd_CompareWindowsDevice -- every pass that
- * would place compares instead (k_wx_compare for k_wx_place, nothing else differs), and behind the fail and saturation words the
- * list carries two 64-bit words per window, its count of differing elements and their least key, which come back with them.
- * WX_MEASURE: the call is LINNEAmd_MeasureWindowsDevice -- every pass that would place reduces instead (k_wx_measure for k_wx_place),
- * into accumulators behind the passes' scratch that one launch in front of the first pass presets and one behind the last commits to
- * the d_out of the windows whose fail word is clear; the list carries a WxMeasure record beside every window record.
- * WX_DIGEST: the call is LINNEAmd_DigestWindowsDevice -- the same with k_wx_digest, 32-bit accumulators behind the tables of powers
- * (lnn_k_digest.h) and a WxDigest record beside every window record */
-static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const struct LINNEAmdPcmLayout *layouts, uint32_t W, uint32_t group_frames, bool single, WxMode mode,
-        const struct LINNEAmdMeasureSpec *specs, const struct LINNEAmdDigestSpec *dspecs, WxPlan *plan, const uint32_t **fail_out)
-{
-    const bool compare = mode == WX_COMPARE, measure = mode == WX_MEASURE, digest = mode == WX_DIGEST;
-    const LINNEAmdStreamIndex *gx[WX_MAXGROUPS]; uint32_t ngroups = 0;
-    const char *who = digest ? "DigestWindowsDevice" : measure ? "MeasureWindowsDevice" : compare ? "CompareWindowsDevice" : single ? "DecodeStreamDevice" : "DecodeWindowsDevice", *advice = single ? "decode the range in parts" : "give group_frames";
+    const WxConsumer &u = *c.use;
+    const uint32_t W = c.W;
+    const char *who = c.single ? "DecodeStreamDevice" : u.name, *advice = c.single ? "decode the range in parts" : "give group_frames";
     char text[sizeof(ctx->err)];
-    /* 1. the checks per window; the live ones get their blocks and the group of their shape */
-    uint64_t nlive = 0, total_rec = 0, total_crec = 0;
-    for (uint32_t i = 0; i < W; i++) {
-        uint64_t r1 = 0;
-        plan[i].group = -1; plan[i].r0 = plan[i].nr = plan[i].ncomp = 0;
-        win[i].result = wx_check_window(ctx, &win[i], layouts ? &layouts[i] : NULL, mode, measure ? &specs[i] : NULL, digest ? &dspecs[i] : NULL, text, sizeof(text), &r1);
-        if (win[i].result != LNN_OK || win[i].num_samples == 0) continue;
-        const LINNEAmdStreamIndex *x = win[i].index;
-        const uint64_t lo = win[i].first_sample;
-        const uint64_t r0 = (lo < x->covered) ? sx_block_of(x, lo) : x->nb;
-        const uint64_t nr = (r0 < x->nb) ? ((r1 < x->nb ? r1 : x->nb - 1u) - r0 + 1u) : 0u;
-        uint32_t nc = 0;
-        for (uint64_t y = 0; y < nr; y++) nc += (x->h_type[r0 + y] == SX_COMPRESS);
-        uint32_t g = 0;
-        while (g < ngroups && memcmp(&gx[g]->shape, &x->shape, sizeof(x->shape)) != 0) g++;
-        if (g == ngroups) {
-            if (ngroups == WX_MAXGROUPS) { snprintf(ctx->err, sizeof(ctx->err), "%s: more than %d stream shapes in one call", who, WX_MAXGROUPS); return LNN_NG; }
-            gx[ngroups++] = x;
-        }
-        plan[i].r0 = (uint32_t)r0; plan[i].nr = (uint32_t)nr; plan[i].ncomp = nc; plan[i].group = (int32_t)g;
-        const bool big = group_frames && nc > group_frames;
-        nlive++; total_rec += nr + 1u + (big ? nc : 0u); total_crec += (uint64_t)nc * (big ? 2u : 1u);
-    }
     *fail_out = NULL;
-    if (!nlive) return LNN_OK;
-    if (total_rec >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu blocks in one call: too many", who, (unsigned long long)total_rec); return LNN_NG; }
+    /* 1. the checks per window; the live ones get their blocks, their group and their passes */
+    std::vector<WxRange> rg(W);
+    for (uint32_t i = 0; i < W; i++) {
+        const struct LINNEAmdWindow &w = c.win[i];
+        WxRange &r = rg[i];
+        c.win[i].result = wx_check_window(ctx, c, i, text, sizeof(text), &r.r1);
+        if (w.result != LNN_OK || w.num_samples == 0) continue;
+        const LINNEAmdStreamIndex *x = w.index;
+        r.live = 1; r.stream = w.d_stream; r.lo = w.first_sample; r.n = w.num_samples;
+        r.x.shape = x->shape; r.x.nb = x->nb; r.x.covered = x->covered; r.x.stream_bytes = x->stream_bytes;
+        r.x.h_off = x->h_off; r.x.h_first = x->h_first; r.x.h_size = x->h_size; r.x.h_type = x->h_type; r.x.h_nsmp = x->h_nsmp;
+        u.describe(c, i, r);
+    }
+    switch (wx_plan_count(rg.data(), W, c.group_frames, pl)) {
+    case WXP_SHAPES: snprintf(ctx->err, sizeof(ctx->err), "%s: more than %d stream shapes in one call", who, WX_MAXGROUPS); return LNN_NG;
+    case WXP_BLOCKS: snprintf(ctx->err, sizeof(ctx->err), "%s: %llu blocks in one call: too many", who, (unsigned long long)pl.total_rec); return LNN_NG;
+    default: break;
+    }
+    if (!pl.nlive) return LNN_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
-    /* 2. the lists, in pinned memory: fail words, saturation words (compare: and the difference words) | window records | block
-     * records | the passes' COMPRESS records */
-    const uint64_t o_fail = 0, o_diff = 2u * sizeof(uint32_t) * (uint64_t)W, back_bytes = o_diff + (compare ? 2u * sizeof(uint64_t) * (uint64_t)W : 0u);
-    const uint64_t o_win = align_up(back_bytes), o_mwin = align_up(o_win + sizeof(WxWindow) * nlive), o_rec = align_up(o_mwin + (measure ? sizeof(WxMeasure) * nlive : digest ? sizeof(WxDigest) * nlive : 0u)),
-            o_crec = align_up(o_rec + sizeof(WxBlock) * total_rec), list_bytes = align_up(o_crec + sizeof(uint32_t) * (total_crec + 1u));
-    SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, list_bytes, true));
+    /* 2. the lists, in pinned memory */
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : 0u);
+    SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
-    uint32_t *h_fail = (uint32_t *)(hs_ + o_fail), *h_crec = (uint32_t *)(hs_ + o_crec);
-    WxWindow *h_win = (WxWindow *)(hs_ + o_win);
-    WxBlock *h_rec = (WxBlock *)(hs_ + o_rec);
+    uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
     for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
-    if (compare) { uint64_t *h_diff = (uint64_t *)(hs_ + o_diff); for (uint32_t i = 0; i < W; i++) { h_diff[2u * i] = 0u; h_diff[2u * i + 1u] = ~(uint64_t)0; } }
-    std::vector<WxPass> passes;
-    uint32_t nrec = 0, ncrec = 0, nwin = 0;
-    uint64_t scratch_bytes = 0;
-    WxMeasure *h_mwin = (WxMeasure *)(hs_ + o_mwin);
-    WxDigest *h_dwin = (WxDigest *)(hs_ + o_mwin);                 /* (digest: in the measure records' place) */
-    uint64_t nacc = 0, nout = 0;                                   /* measure: accumulator records, (channel, bucket) records; digest: accumulator words, buckets */
-    for (uint32_t g = 0; g < ngroups; g++) {
-        WxPass cur;
-        auto fresh = [&](int check_only) { cur.group = g; cur.rec0 = nrec; cur.nrec = 0; cur.c0 = ncrec; cur.nc = 0; cur.seg_bytes = 0; cur.check_only = check_only; };
-        auto close = [&](int check_only) {
-            if (cur.nrec) {
-                const WxScratch sc = wx_scratch(cur.nc, gx[g]->shape.num_channels, gx[g]->shape.num_samples_per_block, cur.seg_bytes);
-                if (sc.bytes > scratch_bytes) scratch_bytes = sc.bytes;
-                passes.push_back(cur);
-            }
-            fresh(check_only);
-        };
-        auto add = [&](const struct LINNEAmdWindow &w, uint32_t wi, uint32_t type, uint32_t r) {
-            const LINNEAmdStreamIndex *x = w.index;
-            WxBlock &rc = h_rec[nrec++];
-            memset(&rc, 0, sizeof(rc));
-            rc.b = w.d_stream; rc.N = x->stream_bytes; rc.type = type; rc.win = wi; rc.cidx = 0xFFFFFFFFu; rc.blk = r;
-            if (type != WX_TAIL) { rc.off = x->h_off[r]; rc.first = x->h_first[r]; rc.size = x->h_size[r]; rc.nsmp = x->h_nsmp[r]; }
-            if (type == SX_COMPRESS) {
-                /* the block's slot in the packed segment: whole 16-byte groups, the block at its source's address modulo 16 */
-                rc.dst = cur.seg_bytes + ((uintptr_t)(w.d_stream + rc.off) & 15u);
-                cur.seg_bytes = (rc.dst + (uint64_t)rc.size + 6u + 15u) & ~(uint64_t)15u;
-                rc.cidx = cur.nc++;
-                h_crec[ncrec++] = cur.nrec;
-            }
-            cur.nrec++;
-        };
-        fresh(0);
-        for (uint32_t i = 0; i < W; i++) {
-            if (plan[i].group != (int32_t)g) continue;
-            const LINNEAmdStreamIndex *x = win[i].index;
-            const uint32_t wi = nwin++;
-            WxWindow &ww = h_win[wi];
-            ww.lo = win[i].first_sample; ww.hi = ww.lo + win[i].num_samples; ww.covered = x->covered; ww.out = win[i].d_pcm; ww.fidx = i;
-            if (layouts) { ww.fmt = layouts[i].format; ww.stride = layouts[i].channel_stride; ww.sstride = layouts[i].sample_stride; }
-            else { ww.fmt = LINNE_AMD_PCM_S32; ww.stride = win[i].pcm_stride; ww.sstride = 1u; }
-            if (measure) {
-                /* a bucket of L samples takes L / 256 pieces: from 8192 samples on they are spread over L / 4096 slots, 64 at most */
-                WxMeasure &mm = h_mwin[wi];
-                const uint64_t n = win[i].num_samples, b = specs[i].bucket_samples, C = x->shape.num_channels;
-                mm.out = specs[i].d_out; mm.cstride = specs[i].channel_stride; mm.b = (b == 0 || b > n) ? n : b; mm.nb = wx_buckets(n, b);
-                mm.ns = 1u; while (mm.ns < WXM_MAXSLOTS && (mm.b >> 12) >= 2u * mm.ns) mm.ns *= 2u;
-                mm.abase = nacc; mm.obase = nout; mm.fidx = i; mm.C = (uint32_t)C; mm.pad = 0u;
-                nacc += mm.ns * C * mm.nb; nout += C * mm.nb;
-            }
-            if (digest) {
-                /* the slots are the measure call's; they lie 16 words or more apart, no two in one 64-byte line */
-                WxDigest &dd = h_dwin[wi];
-                const uint64_t n = win[i].num_samples, b = dspecs[i].bucket_samples;
-                dd.out = dspecs[i].d_out; dd.b = (b == 0 || b > n) ? n : b; dd.nb = wx_buckets(n, b); dd.n = n;
-                dd.ns = 1u; while (dd.ns < WXD_MAXSLOTS && (dd.b >> 12) >= 2u * dd.ns) dd.ns *= 2u;
-                dd.sstride = (uint32_t)((dd.nb + 15u) & ~(uint64_t)15u);    /* (nb < 2^32 - 15 where ns > 1: such a bucket has 8192 samples) */
-                dd.abase = nacc; dd.obase = nout; dd.fidx = i; dd.F = x->shape.num_channels * ((x->shape.bits_per_sample + 7u) >> 3);
-                nacc += dd.ns > 1u ? (uint64_t)dd.ns * dd.sstride : dd.nb; nout += dd.nb;
-            }
-            const bool big = group_frames && plan[i].ncomp > group_frames;
-            if (big) {
-                /* a window of more COMPRESS blocks than a pass takes: its Rice codes are checked first, in passes that place
-                 * nothing, so that no sample of it is written before all its fail word can say is known */
-                close(1);
-                for (uint32_t y = 0; y < plan[i].nr; y++) {
-                    const uint32_t r = plan[i].r0 + y;
-                    if (x->h_type[r] != SX_COMPRESS) continue;
-                    if (cur.nc == group_frames) close(1);
-                    add(win[i], wi, SX_COMPRESS, r);
-                }
-                close(0);
-            } else if (group_frames && cur.nc + plan[i].ncomp > group_frames) close(0);
-            if (ww.hi > ww.covered) add(win[i], wi, WX_TAIL, 0);
-            for (uint32_t y = 0; y < plan[i].nr; y++) {
-                const uint32_t r = plan[i].r0 + y, type = x->h_type[r];
-                if (type == SX_COMPRESS && group_frames && cur.nc == group_frames) close(0);
-                add(win[i], wi, type, r);
-            }
-            if (big) close(0);
-        }
-        close(0);
-    }
-    for (const WxPass &p : passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
+    if (u.back_preset) u.back_preset((uint32_t *)(hs_ + ls.o_back), W);
+    wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
+            (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec));
+    for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
-    SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, list_bytes));
-    const uint64_t o_acc = align_up(scratch_bytes);                /* (measure: the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (measure ? sizeof(struct LINNEAmdMeasure) * nacc : digest ? sizeof(uint32_t) * (WXD_POW_WORDS + nacc) : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
+    const uint64_t o_acc = align_up(pl.scratch_bytes);             /* (the accumulators lie behind every pass's scratch) */
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
-    struct LINNEAmdMeasure *d_acc = (struct LINNEAmdMeasure *)(sd + o_acc);
-    const WxMeasure *d_mwin = (const WxMeasure *)(wd + o_mwin);
-    uint32_t *d_pow = (uint32_t *)(sd + o_acc), *d_dacc = d_pow + WXD_POW_WORDS;   /* (digest: the tables of powers, then the accumulators) */
-    const WxDigest *d_dwin = (const WxDigest *)(wd + o_mwin);
-    uint32_t *d_fail = (uint32_t *)(wd + o_fail);
-    const WxWindow *d_win = (const WxWindow *)(wd + o_win);
+    uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
+    const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
+    WxLaunch ln;
+    ln.side = (const WxBucket *)(wd + ls.o_side); ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
+    ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout;
     if (!ctx->outer_keep) ctx->nspans = 0;
     if (ctx->timing && !ctx->outer_keep) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(wd, hs_, list_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(wd, hs_, ls.bytes, hipMemcpyHostToDevice, ctx->stream));
     /* 4. the passes */
-    const uint64_t ga_ = (nacc + WXM_THREADS - 1u) / WXM_THREADS, go_ = (nout + WXM_THREADS - 1u) / WXM_THREADS;    /* (grid-stride kernels) */
-    const uint32_t mgrid_acc = (uint32_t)(ga_ < 65536u ? ga_ : 65536u), mgrid_out = (uint32_t)(go_ < 65536u ? go_ : 65536u);
-    if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_PRESET, k_wx_measure_preset, dim3(mgrid_acc), dim3(WXM_THREADS), 0, ctx->stream, d_acc, nacc);
-    const uint64_t gd_ = (nacc + WXD_POW_WORDS + WXD_THREADS - 1u) / WXD_THREADS;
-    if (digest) SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_PRESET, k_wx_digest_preset, dim3((uint32_t)(gd_ < 65536u ? gd_ : 65536u)), dim3(WXD_THREADS), 0, ctx->stream, d_pow, d_dacc, nacc);
-    for (const WxPass &p : passes) {
-        const LINNEAmdStreamIndex *x = gx[p.group];
+    if (u.preset) SX_TRY(u.preset(ctx, ln));
+    for (const WxPass &p : pl.passes) {
+        const LINNEAmdStreamIndex *x = c.win[pl.gwin[p.group]].index;
         const uint32_t C = x->shape.num_channels, S = x->shape.num_samples_per_block;
         HostShape hs;
         SX_TRY(shape_info(&x->shape, &hs));
         const WxScratch sc = wx_scratch(p.nc, C, S, p.seg_bytes);
-        const WxBlock *d_rec = (const WxBlock *)(wd + o_rec) + p.rec0;
-        const uint32_t *d_crec = (const uint32_t *)(wd + o_crec) + p.c0;
+        const WxBlock *d_rec = (const WxBlock *)(wd + ls.o_rec) + p.rec0;
+        const uint32_t *d_crec = (const uint32_t *)(wd + ls.o_crec) + p.c0;
         uint32_t *d_nsmp = (uint32_t *)(sd + sc.o_nsmp);
         uint64_t *d_bpos = (uint64_t *)(sd + sc.o_bpos), *d_bend = (uint64_t *)(sd + sc.o_bend), *d_eb = (uint64_t *)(sd + sc.o_eb);
         int32_t *d_prm = (int32_t *)(sd + sc.o_prm), *d_data = (int32_t *)(sd + sc.o_data);
@@ -2494,77 +2486,56 @@ static int wx_decode(LINNEAmdContext *ctx, struct LINNEAmdWindow *win, const str
         la.sat = d_fail + W; la.scale = ldexpf(1.0f, 1 - (int)x->shape.bits_per_sample);
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
         if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
-        if (measure) {
-            WxMeasureArgs ma; ma.p = la; ma.mwin = d_mwin; ma.acc = d_acc;
-            SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_MEASURE, k_wx_measure, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
-        } else if (digest) {
-            WxDigestArgs da; da.p = la; da.dwin = d_dwin; da.acc = d_dacc; da.pow = d_pow;
-            SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_DIGEST, k_wx_digest, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, da);
-        } else if (compare) {
-            WxCompareArgs ca; ca.p = la; ca.diff = (unsigned long long *)(wd + o_diff);
-            SX_LAUNCH(NULL, LINNE_AMD_COMPARE_T_COMPARE, k_wx_compare, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ca);
-        } else
-            SX_LAUNCH(NULL, LINNE_AMD_T_WX_PLACE, k_wx_place, dim3(p.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, la);
+        SX_TRY(u.pass(ctx, ln, la));
     }
-    if (measure) SX_LAUNCH(NULL, LINNE_AMD_MEASURE_T_COMMIT, k_wx_measure_commit, dim3(mgrid_out), dim3(WXM_THREADS), 0, ctx->stream, d_mwin, nwin, (const struct LINNEAmdMeasure *)d_acc, (const uint32_t *)d_fail, nout);
-    if (digest) SX_LAUNCH(NULL, LINNE_AMD_DIGEST_T_COMMIT, k_wx_digest_commit, dim3(mgrid_out), dim3(WXD_THREADS), 0, ctx->stream, d_dwin, nwin, (const uint32_t *)d_dacc, (const uint32_t *)d_pow, (const uint32_t *)d_fail, nout);
-    /* 5. the fail words and the saturation words (and the difference words) behind them, with the call's one wait */
-    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (u.commit) SX_TRY(u.commit(ctx, ln));
+    /* 5. the fail words and what lies behind them, with the call's one wait */
+    HIPCHK(ctx, hipMemcpyAsync(h_fail, d_fail, ls.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); ctx->ev_valid = 1; }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t i = 0; i < W; i++) if (plan[i].group >= 0 && h_fail[i] != WX_NOFAIL) win[i].result = LNN_NG;
+    for (uint32_t i = 0; i < W; i++) if (pl.win[i].group >= 0 && h_fail[i] != WX_NOFAIL) c.win[i].result = LNN_NG;
     *fail_out = h_fail;
     return LNN_OK;
 }
 
-/* Both entry points behind their argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
+/* Every entry point behind its argument checks: the windows' results, then the call's -- the lowest-numbered failing window's code,
  * with its text in ctx->err (behind the window's number unless the call is the single one) */
-static int wx_run(LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdPcmLayout *layouts, struct LINNEAmdPcmLayout *layouts_out,
-        uint32_t num_windows, uint32_t group_frames, bool single, struct LINNEAmdDiff *diffs, const struct LINNEAmdMeasureSpec *specs = NULL,
-        const struct LINNEAmdDigestSpec *dspecs = NULL)
+static int wx_run(LINNEAmdContext *ctx, const WxCall &c)
 {
-    const bool compare = diffs != NULL;
-    const WxMode mode = dspecs ? WX_DIGEST : specs ? WX_MEASURE : compare ? WX_COMPARE : WX_PLACE;
     ctx->err[0] = 0;
     const uint32_t *fail = NULL;
-    std::vector<WxPlan> plan;
-    int ret = items_try(ctx, [&] { plan.resize(num_windows); return wx_decode(ctx, windows, layouts, num_windows, group_frames, single, mode, specs, dspecs, plan.data(), &fail); });
+    WxPlanned pl;
+    int ret = items_try(ctx, [&] { return wx_decode(ctx, c, pl, &fail); });
     /* a HIP error, no memory: the whole call fails (wx_decode has waited and recorded where it did not) */
-    if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, num_windows, [&](uint32_t i) { windows[i].result = LNN_NG; }) != LNN_OK) return LNN_NG;
-    /* (a failing window's `saturated` stays as the caller left it; the saturation words lie behind the fail words) */
-    if (layouts_out) for (uint32_t i = 0; i < num_windows; i++)
-        if (windows[i].result == LNN_OK) layouts_out[i].saturated = (plan[i].group >= 0 && fail && fail[num_windows + i]) ? 1u : 0u;
-    /* (a failing window's diffs[i] stays too; an OK window of no samples took no pass and differs nowhere) */
-    if (compare) for (uint32_t i = 0; i < num_windows; i++) {
-        if (windows[i].result != LNN_OK) continue;
-        const uint64_t *dw = (plan[i].group >= 0 && fail) ? (const uint64_t *)(fail + 2u * (uint64_t)num_windows) + 2u * (uint64_t)i : NULL;
-        const uint64_t cnt = dw ? dw[0] : 0u;
-        diffs[i].num_differing = cnt;
-        diffs[i].first_sample = cnt ? windows[i].first_sample + (dw[1] >> 3) : 0u;
-        diffs[i].first_channel = cnt ? (uint32_t)(dw[1] & 7u) : 0u;
-        diffs[i].reserved = 0u;
-    }
-    for (uint32_t i = 0; i < num_windows; i++) {
-        if (windows[i].result == LNN_OK) continue;
+    if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, c.W, [&](uint32_t i) { c.win[i].result = LNN_NG; }) != LNN_OK) return LNN_NG;
+    if (c.use->read_back) for (uint32_t i = 0; i < c.W; i++)
+        if (c.win[i].result == LNN_OK) c.use->read_back(c, i, pl.win[i].group >= 0 ? fail : NULL);
+    for (uint32_t i = 0; i < c.W; i++) {
+        if (c.win[i].result == LNN_OK) continue;
         char text[sizeof(ctx->err)]; uint64_t r1;
-        if (plan[i].group >= 0 && fail)
+        if (pl.win[i].group >= 0 && fail)
             snprintf(text, sizeof(text), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
-                    fail[i], (unsigned long long)windows[i].index->h_off[fail[i]]);
-        else (void)wx_check_window(ctx, &windows[i], layouts ? &layouts[i] : NULL, mode, specs ? &specs[i] : NULL, dspecs ? &dspecs[i] : NULL, text, sizeof(text), &r1);
-        items_first_text(ctx, "window", i, single, text);
-        return windows[i].result;
+                    fail[i], (unsigned long long)c.win[i].index->h_off[fail[i]]);
+        else (void)wx_check_window(ctx, c, i, text, sizeof(text), &r1);
+        items_first_text(ctx, "window", i, c.single, text);
+        return c.win[i].result;
     }
     return LNN_OK;
+}
+/* the windows calls' own argument checks */
+static int wx_entry(LINNEAmdContext *ctx, WxCall c, bool complete)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    if (c.W == 0) return LNN_OK;
+    if (!complete) { snprintf(ctx->err, sizeof(ctx->err), "%s: null argument", c.use->name); return LNN_INVALID_ARGUMENT; }
+    return wx_run(ctx, c);
 }
 
 extern "C" int LINNEAmd_DecodeWindowsDeviceLayout(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct LINNEAmdPcmLayout *layouts,
         uint32_t num_windows, uint32_t group_frames)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (num_windows == 0) return LNN_OK;
-    if (!windows) { snprintf(ctx->err, sizeof(ctx->err), "DecodeWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, layouts, layouts, num_windows, group_frames, false, NULL);
+    return wx_entry(ctx, wx_call(&WX_PLACE, windows, num_windows, group_frames, layouts, layouts), windows != NULL);
 }
 /* int32 planar windows: the call above without layouts */
 extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, uint32_t num_windows, uint32_t group_frames)
@@ -2576,33 +2547,21 @@ extern "C" int LINNEAmd_DecodeWindowsDevice(struct LINNEAmdContext *ctx, struct 
 extern "C" int LINNEAmd_CompareWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdPcmLayout *layouts,
         struct LINNEAmdDiff *diffs, uint32_t num_windows, uint32_t group_frames)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (num_windows == 0) return LNN_OK;
-    if (!windows || !diffs) { snprintf(ctx->err, sizeof(ctx->err), "CompareWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, layouts, NULL, num_windows, group_frames, false, diffs);
+    return wx_entry(ctx, wx_call(&WX_COMPARE, windows, num_windows, group_frames, layouts, diffs), windows && diffs);
 }
 
 /* the windows reduced to a table per window instead of written */
 extern "C" int LINNEAmd_MeasureWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdMeasureSpec *specs,
         uint32_t num_windows, uint32_t group_frames)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (num_windows == 0) return LNN_OK;
-    if (!windows || !specs) { snprintf(ctx->err, sizeof(ctx->err), "MeasureWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, NULL, NULL, num_windows, group_frames, false, NULL, specs);
+    return wx_entry(ctx, wx_call(&WX_MEASURE, windows, num_windows, group_frames, specs, NULL), windows && specs);
 }
 
 /* the windows hashed to a table per window instead of written */
 extern "C" int LINNEAmd_DigestWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdDigestSpec *specs,
         uint32_t num_windows, uint32_t group_frames)
 {
-    if (!ctx) return LNN_INVALID_ARGUMENT;
-    ctx->err[0] = 0;
-    if (num_windows == 0) return LNN_OK;
-    if (!windows || !specs) { snprintf(ctx->err, sizeof(ctx->err), "DigestWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
-    return wx_run(ctx, windows, NULL, NULL, num_windows, group_frames, false, NULL, NULL, specs);
+    return wx_entry(ctx, wx_call(&WX_DIGEST, windows, num_windows, group_frames, specs, NULL), windows && specs);
 }
 
 /* one window of one stream */
@@ -2612,7 +2571,9 @@ extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const st
     if (!ctx) return LNN_INVALID_ARGUMENT;
     struct LINNEAmdWindow w;
     w.index = x; w.d_stream = d_stream; w.first_sample = first_sample; w.num_samples = num_samples; w.d_pcm = d_pcm; w.pcm_stride = pcm_stride; w.result = LNN_OK;
-    return wx_run(ctx, &w, NULL, NULL, 1, 0, true, NULL);
+    WxCall c = wx_call(&WX_PLACE, &w, 1, 0, NULL, NULL);
+    c.single = true;
+    return wx_run(ctx, c);
 }
 
 

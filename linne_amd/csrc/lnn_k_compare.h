@@ -1,8 +1,8 @@
 /* lnn_k_compare.h -- comparing sample windows of resident .lnn streams with the caller's resident PCM (LINNEAmd_CompareWindowsDevice;
  * DESIGN.md section 5, "Comparing instead of placing").
  *
- * k_wx_compare is the sibling of k_wx_place (lnn_k_windows.h): the same grid, the same record walk, the same values (wx_value) --
- * but where k_wx_place converts and stores a sample, this kernel loads the caller's element (lnn_k_pcm_load.h) and compares.  Per
+ * k_wx_compare is the sibling of k_wx_place (lnn_k_windows.h): its grid, its prologue and record walk (wx_prologue, wx_walk), its
+ * values (wx_value) -- but where k_wx_place converts and stores a sample, this kernel loads the caller's element (lnn_k_pcm_load.h) and compares.  Per
  * window the call wants two numbers: how many (sample, channel) elements differ, and the first of them -- lowest sample, then lowest
  * channel, which is the least key (s - lo) * 8 + ch (LINNE_MAX_NUM_CHANNELS is 8).  A thread keeps a count and a least key, a wave
  * reduces them across its lanes, the workgroup through LDS, and only a workgroup that found a difference touches global memory: one
@@ -90,25 +90,11 @@ __global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_compare(WxCompareArgs c
     __shared__ uint32_t s_cnt[SX_PLACE_THREADS / 64u];
     __shared__ uint64_t s_key[SX_PLACE_THREADS / 64u];
     const WxPlaceArgs &a = ca.p;
-    const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
-    if (y >= a.nrec) return;
-    const WxBlock *rc = a.recs + y;
-    const WxWindow w = a.wins[rc->win];
-    if (a.fail[w.fidx] != WX_NOFAIL) return;                       /* block-uniform, as every exit before the barrier below */
-    const uint32_t type = rc->type;
+    WxRecord r;
+    if (!wx_prologue(a, r)) return;                                /* block-uniform, as every exit before the barrier below */
+    const WxWindow &w = r.w;
     WxDiff d; d.cnt = 0u; d.key = ~(uint64_t)0;
-    if (type == WX_TAIL) {
-        const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
-        for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-            wx_compare_piece(a, w, rc, type, s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS, d);
-    } else {
-        const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
-        for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
-            const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
-            const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
-            if (sa < sb) wx_compare_piece(a, w, rc, type, f0, sa, sb, d);
-        }
-    }
+    wx_walk(a, r.rc, w, r.type, r.x, [&](uint64_t f0, uint64_t sa, uint64_t sb) { wx_compare_piece(a, w, r.rc, r.type, f0, sa, sb, d); });
     if (!__syncthreads_or(d.cnt != 0u)) return;                    /* equal: nothing more */
     for (int o = 32; o > 0; o >>= 1) {
         d.cnt += (uint32_t)__shfl_xor((int)d.cnt, o);

@@ -1,9 +1,9 @@
 /* lnn_k_digest.h -- the CRC-32 of the decoded PCM of sample windows of resident .lnn streams, per bucket, nothing of the window's size
  * written (LINNEAmd_DigestWindowsDevice; DESIGN.md section 5, "Hashing instead of placing").
  *
- * k_wx_digest is the sibling of k_wx_place (lnn_k_windows.h), k_wx_compare (lnn_k_compare.h) and k_wx_measure (lnn_k_measure.h): the
- * same grid, the same record walk, the same values (wx_value) -- but a sample that leaves the synthesis is hashed, not stored.  The
- * hash is the zlib / IEEE 802.3 CRC-32 of the bytes a WAV writer gives the samples (include/linne_amd.h has the byte string).
+ * k_wx_digest is the sibling of k_wx_place (lnn_k_windows.h): its grid, its prologue and record walk, its values (wx_value) -- but a
+ * sample that leaves the synthesis is hashed, not stored.  The buckets, the pieces among them, the slots of a long bucket and the
+ * commit behind the last pass are those of lnn_k_buckets.h, as for k_wx_measure (lnn_k_measure.h); this file adds the hash.  It is the zlib / IEEE 802.3 CRC-32 of the bytes a WAV writer gives the samples (include/linne_amd.h has the byte string).
  *
  * The algebra, in the reflected representation (bit 31 is x^0; a (x) b is the product modulo P = 0xEDB88320, wxd_mul): with raw(M)
  * the CRC register behind M from the initial value 0 and without the final XOR, a bucket whose string is M = M_0 || ... || M_k,
@@ -17,7 +17,7 @@
  * register shifted once per bit, a few integer operations a bit and no table: random byte-table reads would queue on the LDS banks --
  * and multiplies it by x^(8 F d), d < 256 the frames from its own to the end of its bucket's part of the piece, read from a table
  * in the scratch.  A piece of at most 256 frames lies in the buckets [k0, k1]:
- *   - at most WXD_SEGMENTS buckets: for every bucket the lanes of that bucket (the others carry 0) are XORed across the wave with
+ *   - at most WXB_SEGMENTS buckets: for every bucket the lanes of that bucket (the others carry 0) are XORed across the wave with
  *     shuffles and across the four waves through LDS, and lane g multiplies bucket k0 + g's word by x^(8 R), R the bytes from the
  *     part's end to the bucket's end, and issues the one atomicXor of that (piece, bucket);
  *   - more buckets (a small b): the terms go to LDS, and the first lane of every bucket XORs its bucket's terms there.
@@ -28,8 +28,7 @@
  * Zero-valued records (SILENT, WX_TAIL) contribute nothing when w >= 2 -- raw() of zeros is 0 -- and are skipped; with w == 1 a zero
  * is the byte 0x80 and is hashed like any other.
  *
- * Where a bucket is long, thousands of workgroups would queue on one address.  Such a window gets ns > 1 slots, copies of its
- * accumulators 64 bytes or more apart, and the piece at frames [256 j, 256 j + 256) of the window XORs into slot j % ns.  A term is
+ * A window's slots lie 64 bytes or more apart (sstride words, no two in one line).  A term is
  * taken to the bucket's end whichever slot it lands in, so k_wx_digest_commit, once per call behind the last pass, XORs a bucket's
  * slots, applies the length terms and writes {crc32, 0, num_bytes} to the caller's d_out -- only for windows whose fail word is
  * clear, so a failing window's d_out is never written.  Plain C++ and vector stores and atomics only.
@@ -37,11 +36,10 @@
 #ifndef LNN_K_DIGEST_H_INCLUDED
 #define LNN_K_DIGEST_H_INCLUDED
 
-static_assert(SX_PLACE_THREADS == 256u, "k_wx_digest reduces over four waves of 64, and a lane's power table has 256 entries");
+#include "lnn_k_buckets.h"
+
+static_assert(SX_PLACE_THREADS == 256u, "a lane's power table has 256 entries");
 static_assert(sizeof(struct LINNEAmdDigest) == 16, "a bucket's answer is one struct LINNEAmdDigest");
-#define WXD_SEGMENTS 4u                 /* up to this many buckets in a piece are reduced by the whole workgroup, one after the other */
-#define WXD_MAXSLOTS 64u
-#define WXD_THREADS 256u
 #define WXD_POLY 0xEDB88320u
 #define WXD_ONE 0x80000000u             /* x^0 */
 #define WXD_X8 0x00800000u              /* x^8 */
@@ -50,21 +48,9 @@ static_assert(sizeof(struct LINNEAmdDigest) == 16, "a bucket's answer is one str
 #define WXD_TB_WORDS (8u * 256u)                /* pow[WXD_TF_WORDS + k * 256 + v] = x^(8 v 256^k), k < 8, v < 256 */
 #define WXD_POW_WORDS (WXD_TF_WORDS + WXD_TB_WORDS)
 
-/* one window's digest (64 bytes), at its WxWindow's index */
-struct WxDigest {
-    struct LINNEAmdDigest *out;         /* the caller's table */
-    uint64_t b, nb;                     /* bucket length (the window's length for "one bucket"), buckets */
-    uint64_t abase;                     /* its accumulators in the scratch: slot s, bucket k at abase + s * sstride + k */
-    uint64_t obase;                     /* the number of buckets of the windows before it */
-    uint64_t n;                         /* its samples */
-    uint32_t ns, fidx;                  /* slots (a power of two); its fail word */
-    uint32_t F, sstride;                /* bytes per sample frame; words from one slot to the next */
-};
-static_assert(sizeof(WxDigest) == 64, "WxDigest is 64 bytes");
-
 struct WxDigestArgs {
     WxPlaceArgs p;                      /* the walk's arguments (sat and scale are not used) */
-    const WxDigest *dwin;
+    const WxBucket *dwin;               /* per frame: n, F and sstride are set; slot s, bucket k at abase + s * sstride + k */
     uint32_t *acc;
     const uint32_t *pow;                /* the two tables of powers */
 };
@@ -111,36 +97,31 @@ __device__ __forceinline__ uint32_t wxd_frame(const WxPlaceArgs &a, const WxBloc
 
 /* The workgroup hashes samples [sa, sb) (at most SX_PLACE_THREADS, inside the window) of record rc, whose sample 0 is stream
  * sample f0.  Every barrier in here is passed by the whole workgroup: sa, sb and the buckets are block-uniform. */
-__device__ __forceinline__ void wx_digest_piece(const WxDigestArgs &da, const WxWindow &w, const WxDigest &m, const WxBlock *rc, uint32_t type,
+__device__ __forceinline__ void wx_digest_piece(const WxDigestArgs &da, const WxWindow &w, const WxBucket &m, const WxBlock *rc, uint32_t type,
         uint64_t f0, uint64_t sa, uint64_t sb, uint32_t wd, uint32_t (*part)[SX_PLACE_THREADS / 64u], uint32_t *terms)
 {
     const WxPlaceArgs &a = da.p;
-    const uint32_t t = threadIdx.x, len = (uint32_t)(sb - sa);
-    const uint64_t ra = sa - w.lo, k0 = ra / m.b, k1 = (ra + len - 1u) / m.b;
-    const uint32_t nseg = (uint32_t)(k1 - k0) + 1u;                 /* <= 256 */
-    const uint32_t slot = (uint32_t)(ra / SX_PLACE_THREADS) & (m.ns - 1u);
-    uint32_t *acc = da.acc + m.abase + (uint64_t)slot * m.sstride;
+    const WxPiece pc = wx_piece(w, m, sa, sb);
+    const uint32_t t = threadIdx.x, len = pc.len, nseg = pc.nseg;
+    const uint64_t ra = pc.ra, k0 = pc.k0;
+    uint32_t *acc = da.acc + m.abase + (uint64_t)pc.slot * m.sstride;
     const uint32_t *tf = da.pow + (m.F - 1u) * 256u, *tb = da.pow + WXD_TF_WORDS;
     const uint32_t i0 = (uint32_t)(sa - f0);
-    if (nseg <= WXD_SEGMENTS) {
+    if (nseg <= WXB_SEGMENTS) {
         uint32_t end = 0u;                                          /* where the lane's bucket ends in the piece */
-        for (uint32_t g = 0; g < nseg; g++) {
-            const uint64_t ba = (k0 + g) * m.b, tb64 = ba + m.b - ra;
-            const uint32_t ta = ba > ra ? (uint32_t)(ba - ra) : 0u, te = tb64 > len ? len : (uint32_t)tb64;
-            if (t >= ta && t < te) end = te;
-        }
+        uint32_t ta, te;
+        for (uint32_t g = 0; g < nseg; g++) { pc.lanes(k0 + g, ta, te); if (t >= ta && t < te) end = te; }
         const uint32_t term = (t < len) ? wxd_mul(wxd_frame(a, rc, type, i0 + t, wd), tf[end - 1u - t]) : 0u;
         for (uint32_t g = 0; g < nseg; g++) {
-            const uint64_t ba = (k0 + g) * m.b, tb64 = ba + m.b - ra;
-            const uint32_t ta = ba > ra ? (uint32_t)(ba - ra) : 0u, te = tb64 > len ? len : (uint32_t)tb64;
+            pc.lanes(k0 + g, ta, te);
             uint32_t r = (t >= ta && t < te) ? term : 0u;
             for (int o = 32; o > 0; o >>= 1) r ^= __shfl_xor(r, o);
             if ((t & 63u) == 0u) part[g][t >> 6] = r;
         }
         __syncthreads();
         if (t < nseg) {
-            const uint64_t ba = (k0 + t) * m.b, tb64 = ba + m.b - ra, be = ba + m.b < m.n ? ba + m.b : m.n;
-            const uint32_t te = tb64 > len ? len : (uint32_t)tb64;
+            const uint64_t ba = (k0 + t) * m.b, be = ba + m.b < m.n ? ba + m.b : m.n;
+            pc.lanes(k0 + t, ta, te);
             uint32_t r = part[t][0];
             for (uint32_t k = 1; k < SX_PLACE_THREADS / 64u; k++) r ^= part[t][k];
             const uint64_t R = (be - (ra + te)) * m.F;
@@ -151,19 +132,18 @@ __device__ __forceinline__ void wx_digest_piece(const WxDigestArgs &da, const Wx
         return;
     }
     /* many short buckets: the piece's terms in LDS, and the first lane of every bucket XORs its bucket's */
-    uint64_t k = 0u, ba = 0u;
+    uint64_t k = 0u;
     uint32_t ta = 0u, te = 0u;
     if (t < len) {
-        k = (ra + t) / m.b; ba = k * m.b;
-        const uint64_t tb64 = ba + m.b - ra;
-        ta = ba > ra ? (uint32_t)(ba - ra) : 0u; te = tb64 > len ? len : (uint32_t)tb64;
+        k = (ra + t) / m.b;
+        pc.lanes(k, ta, te);
         terms[t] = wxd_mul(wxd_frame(a, rc, type, i0 + t, wd), tf[te - 1u - t]);
     }
     __syncthreads();
     if (t < len && t == ta) {
         uint32_t r = 0u;
         for (uint32_t j = ta; j < te; j++) r ^= terms[j];
-        const uint64_t be = ba + m.b < m.n ? ba + m.b : m.n, R = (be - (ra + te)) * m.F;
+        const uint64_t ba = k * m.b, be = ba + m.b < m.n ? ba + m.b : m.n, R = (be - (ra + te)) * m.F;
         if (r && R) r = wxd_mul(r, wxd_pow(tb, R));
         if (r) atomicXor(acc + k, r);
     }
@@ -173,35 +153,20 @@ __device__ __forceinline__ void wx_digest_piece(const WxDigestArgs &da, const Wx
 /* nrec * xch workgroups: the y-th xch of them hash record y, piece by piece as k_wx_place places it */
 __global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_digest(WxDigestArgs da)
 {
-    __shared__ uint32_t part[WXD_SEGMENTS][SX_PLACE_THREADS / 64u];
+    __shared__ uint32_t part[WXB_SEGMENTS][SX_PLACE_THREADS / 64u];
     __shared__ uint32_t terms[SX_PLACE_THREADS];
-    const WxPlaceArgs &a = da.p;
-    const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
-    if (y >= a.nrec) return;
-    const WxBlock *rc = a.recs + y;
-    const WxWindow w = a.wins[rc->win];
-    const WxDigest m = da.dwin[rc->win];
-    if (a.fail[w.fidx] != WX_NOFAIL) return;                       /* block-uniform, as every exit */
-    const uint32_t type = rc->type, wd = (a.bits + 7u) >> 3;
-    if (wd > 1u && type != SX_COMPRESS && type != SX_RAW) return;  /* zeros of two bytes or more: raw() is 0 */
-    if (type == WX_TAIL) {
-        const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
-        for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-            wx_digest_piece(da, w, m, rc, type, s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS, wd, part, terms);
-    } else {
-        const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
-        for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
-            const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
-            const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
-            if (sa < sb) wx_digest_piece(da, w, m, rc, type, f0, sa, sb, wd, part, terms);
-        }
-    }
+    WxRecord r;
+    if (!wx_prologue(da.p, r)) return;                             /* block-uniform, as every exit */
+    const uint32_t wd = (da.p.bits + 7u) >> 3;
+    if (wd > 1u && r.type != SX_COMPRESS && r.type != SX_RAW) return;      /* zeros of two bytes or more: raw() is 0 */
+    const WxBucket m = da.dwin[r.rc->win];
+    wx_walk(da.p, r.rc, r.w, r.type, r.x, [&](uint64_t f0, uint64_t sa, uint64_t sb) { wx_digest_piece(da, r.w, m, r.rc, r.type, f0, sa, sb, wd, part, terms); });
 }
 
 /* the two tables of powers filled and every accumulator of the call zeroed: a lane per word */
-__global__ __launch_bounds__(WXD_THREADS) void k_wx_digest_preset(uint32_t *pow, uint32_t *acc, uint64_t total)
+__global__ __launch_bounds__(WXB_THREADS) void k_wx_digest_preset(uint32_t *pow, uint32_t *acc, uint64_t total)
 {
-    for (uint64_t g = (uint64_t)blockIdx.x * WXD_THREADS + threadIdx.x; g < total + WXD_POW_WORDS; g += (uint64_t)gridDim.x * WXD_THREADS) {
+    for (uint64_t g = (uint64_t)blockIdx.x * WXB_THREADS + threadIdx.x; g < total + WXD_POW_WORDS; g += (uint64_t)gridDim.x * WXB_THREADS) {
         if (g >= WXD_POW_WORDS) acc[g - WXD_POW_WORDS] = 0u;
         else if (g < WXD_TF_WORDS) pow[g] = wxd_xpow8((uint64_t)((uint32_t)g / 256u + 1u) * ((uint32_t)g & 255u));
         else { const uint32_t j = (uint32_t)g - WXD_TF_WORDS; pow[g] = wxd_xpow8((uint64_t)(j & 255u) << (8u * (j / 256u))); }
@@ -210,12 +175,10 @@ __global__ __launch_bounds__(WXD_THREADS) void k_wx_digest_preset(uint32_t *pow,
 
 /* A lane per bucket of every digested window, numbered through the windows in their records' order (obase): the bucket's slots
  * XORed, the length terms applied and the answer stored in the caller's table, unless the window's fail word is set */
-__global__ __launch_bounds__(WXD_THREADS) void k_wx_digest_commit(const WxDigest *dwin, uint32_t nwin, const uint32_t *acc, const uint32_t *pow, const uint32_t *fail, uint64_t total)
+__global__ __launch_bounds__(WXB_THREADS) void k_wx_digest_commit(const WxBucket *dwin, uint32_t nwin, const uint32_t *acc, const uint32_t *pow, const uint32_t *fail, uint64_t total)
 {
-    for (uint64_t g = (uint64_t)blockIdx.x * WXD_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXD_THREADS) {
-        uint32_t lo = 0, hi = nwin;                                 /* the last window whose obase <= g */
-        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (dwin[mid].obase <= g) lo = mid; else hi = mid; }
-        const WxDigest m = dwin[lo];
+    for (uint64_t g = (uint64_t)blockIdx.x * WXB_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXB_THREADS) {
+        const WxBucket m = dwin[wx_bucket_window(dwin, nwin, g)];
         if (fail[m.fidx] != WX_NOFAIL) continue;
         const uint64_t k = g - m.obase, ba = k * m.b, bytes = ((ba + m.b < m.n ? ba + m.b : m.n) - ba) * m.F;
         const uint32_t *p = acc + m.abase + k;
@@ -223,7 +186,7 @@ __global__ __launch_bounds__(WXD_THREADS) void k_wx_digest_commit(const WxDigest
         for (uint32_t s = 0; s < m.ns; s++, p += m.sstride) r ^= *p;
         struct LINNEAmdDigest o;
         o.crc32 = r ^ wxd_mul(0xFFFFFFFFu, wxd_pow(pow + WXD_TF_WORDS, bytes)) ^ 0xFFFFFFFFu; o.reserved = 0u; o.num_bytes = bytes;
-        m.out[k] = o;
+        ((struct LINNEAmdDigest *)m.out)[k] = o;
     }
 }
 

@@ -1,49 +1,30 @@
 /* lnn_k_measure.h -- measuring sample windows of resident .lnn streams: min, max, sum and sum of squares per channel and bucket,
  * nothing of the window's size written (LINNEAmd_MeasureWindowsDevice; DESIGN.md section 5, "Reducing instead of placing").
  *
- * k_wx_measure is the sibling of k_wx_place (lnn_k_windows.h) and k_wx_compare (lnn_k_compare.h): the same grid, the same record
- * walk, the same values (wx_value) -- but a sample that leaves the synthesis is reduced, not stored.  A window of n samples with
- * bucket length b has nb = ceil(n / b) buckets; bucket k of channel ch owns one accumulator record (struct LINNEAmdMeasure) in the
- * context's scratch, preset by k_wx_measure_preset to (INT32_MAX, INT32_MIN, 0, 0, 0).  A piece of at most 256 samples lies in the
- * buckets [k0, k1]:
+ * k_wx_measure is the sibling of k_wx_place (lnn_k_windows.h): its grid, its prologue and record walk, its values (wx_value) -- but a
+ * sample that leaves the synthesis is reduced, not stored.  The buckets, the pieces among them, the slots of a long bucket and the
+ * commit behind the last pass are those of lnn_k_buckets.h; this file adds the reduction.  Bucket k of channel ch owns one
+ * accumulator record (struct LINNEAmdMeasure) in the context's scratch -- slot s of a window at abase + s * C * nb -- preset by
+ * k_wx_measure_preset to (INT32_MAX, INT32_MIN, 0, 0, 0).  A piece:
  *   - a SILENT or WX_TAIL record holds zeros: one lane per bucket of the piece lowers its min and raises its max to 0, no more;
- *   - at most WXM_SEGMENTS buckets: for every bucket the whole workgroup reduces the lanes of that bucket (the others carry the
- *     operations' identities) -- across the wave's lanes with shuffles, across the four waves through LDS -- and lane ch issues
- *     channel ch's atomics on the bucket's accumulator;
- *   - more buckets (a small b): the values go to LDS, and the first lane of every bucket walks its bucket's samples there.
- * No reduction crosses a bucket's boundary.  All of it is integer arithmetic, so the order of the atomics does not show: atomicMin
- * and atomicMax on the 32-bit fields (skipped when a plain load shows they would change nothing: the fields only ever move one
- * way), atomicAdd on sum, and atomicAdd on sumsq_lo whose returned value tells whether the addition carried into sumsq_hi.
- * One square fits 64 bits ((2^31)^2 = 2^62); a thread keeps the sum of squares as (lo, hi) with lo += q; hi += lo < q.
- *
- * Where a bucket is long (one bucket for a whole track) thousands of workgroups would queue on one address.  Such a window gets
- * ns > 1 slots, copies of its accumulator table, and piece j adds into slot j % ns.  k_wx_measure_commit, once per call behind the
- * last pass, folds a window's slots and writes its table to the caller's d_out -- only for windows whose fail word is clear, so a
- * failing window's d_out is never written.  Plain C++ and vector stores only.
+ *   - few buckets: the lanes of a bucket are folded across the wave with shuffles and across the four waves through LDS, and lane
+ *     (g, ch) issues channel ch's atomics on bucket k0 + g's accumulator;
+ *   - many: the first lane of every bucket walks its bucket's samples in LDS, channel by channel.
+ * All of it is integer arithmetic, so the order of the atomics does not show: atomicMin and atomicMax on the 32-bit fields (skipped
+ * when a plain load shows they would change nothing: the fields only ever move one way), atomicAdd on sum, and atomicAdd on sumsq_lo
+ * whose returned value tells whether the addition carried into sumsq_hi.  One square fits 64 bits ((2^31)^2 = 2^62); a thread keeps
+ * the sum of squares as (lo, hi) with lo += q; hi += lo < q.  Plain C++ and vector stores only.
  */
 #ifndef LNN_K_MEASURE_H_INCLUDED
 #define LNN_K_MEASURE_H_INCLUDED
 
-static_assert(SX_PLACE_THREADS == 256u, "k_wx_measure reduces over four waves of 64");
-static_assert(sizeof(struct LINNEAmdMeasure) == 32, "an accumulator is one struct LINNEAmdMeasure");
-#define WXM_SEGMENTS 4u                 /* up to this many buckets in a piece are reduced by the whole workgroup, one after the other */
-#define WXM_MAXSLOTS 64u
-#define WXM_THREADS 256u
+#include "lnn_k_buckets.h"
 
-/* one window's measuring (64 bytes), at its WxWindow's index */
-struct WxMeasure {
-    struct LINNEAmdMeasure *out; uint64_t cstride;      /* the caller's table */
-    uint64_t b, nb;                     /* bucket length (the window's length for "one bucket"), buckets */
-    uint64_t abase;                     /* its accumulators in the scratch: [ns][C][nb] records from here */
-    uint64_t obase;                     /* the number of (channel, bucket) records of the windows before it */
-    uint32_t ns, fidx;                  /* slots (a power of two); its fail word */
-    uint32_t C, pad;                    /* channels */
-};
-static_assert(sizeof(WxMeasure) == 64, "WxMeasure is 64 bytes");
+static_assert(sizeof(struct LINNEAmdMeasure) == 32, "an accumulator is one struct LINNEAmdMeasure");
 
 struct WxMeasureArgs {
     WxPlaceArgs p;                      /* the walk's arguments (sat and scale are not used) */
-    const WxMeasure *mwin;
+    const WxBucket *mwin;               /* per channel: cstride and C are set */
     struct LINNEAmdMeasure *acc;
 };
 
@@ -73,15 +54,14 @@ __device__ __forceinline__ void wxm_atomics(struct LINNEAmdMeasure *p, const WxA
 
 /* The workgroup measures samples [sa, sb) (at most SX_PLACE_THREADS, inside the window) of record rc, whose sample 0 is stream
  * sample f0.  Every barrier in here is passed by the whole workgroup: sa, sb and the buckets are block-uniform. */
-__device__ __forceinline__ void wx_measure_piece(const WxMeasureArgs &ma, const WxWindow &w, const WxMeasure &m, const WxBlock *rc, uint32_t type,
+__device__ __forceinline__ void wx_measure_piece(const WxMeasureArgs &ma, const WxWindow &w, const WxBucket &m, const WxBlock *rc, uint32_t type,
         uint64_t f0, uint64_t sa, uint64_t sb, WxAcc (*part)[SX_PLACE_THREADS / 64u][LINNE_MAX_NUM_CHANNELS], int32_t *vals)
 {
     const WxPlaceArgs &a = ma.p;
-    const uint32_t t = threadIdx.x, C = a.C, len = (uint32_t)(sb - sa);
-    const uint64_t ra = sa - w.lo, k0 = ra / m.b, k1 = (ra + len - 1u) / m.b;
-    const uint32_t nseg = (uint32_t)(k1 - k0) + 1u;                 /* <= 256 */
-    const uint32_t slot = (uint32_t)(ra / SX_PLACE_THREADS) & (m.ns - 1u);
-    struct LINNEAmdMeasure *acc = ma.acc + m.abase + (uint64_t)slot * C * m.nb;
+    const WxPiece pc = wx_piece(w, m, sa, sb);
+    const uint32_t t = threadIdx.x, C = a.C, len = pc.len, nseg = pc.nseg;
+    const uint64_t k0 = pc.k0;
+    struct LINNEAmdMeasure *acc = ma.acc + m.abase + (uint64_t)pc.slot * C * m.nb;
     if (type != SX_COMPRESS && type != SX_RAW) {
         /* zeros */
         for (uint32_t j = t; j < nseg * C; j += SX_PLACE_THREADS) {
@@ -93,14 +73,13 @@ __device__ __forceinline__ void wx_measure_piece(const WxMeasureArgs &ma, const 
         return;
     }
     const uint32_t i0 = (uint32_t)(sa - f0);
-    if (nseg <= WXM_SEGMENTS) {
+    if (nseg <= WXB_SEGMENTS) {
         for (uint32_t ch = 0; ch < C; ch++) {
             const int32_t v = (t < len) ? wx_value(a, rc, type, i0 + t, ch) : 0;
             for (uint32_t g = 0; g < nseg; g++) {
-                /* the lanes [ta, tb) of bucket k0 + g */
-                const uint64_t ba = (k0 + g) * m.b, tb64 = ba + m.b - ra;
-                const uint32_t ta = ba > ra ? (uint32_t)(ba - ra) : 0u, tb = tb64 > len ? len : (uint32_t)tb64;
-                const bool mine = (t >= ta && t < tb);
+                uint32_t ta, te;
+                pc.lanes(k0 + g, ta, te);
+                const bool mine = (t >= ta && t < te);
                 WxAcc r; wxm_clear(r);
                 if (__ballot(mine) != 0ull) {                       /* wave-uniform */
                     if (mine) wxm_note(r, v);
@@ -126,14 +105,13 @@ __device__ __forceinline__ void wx_measure_piece(const WxMeasureArgs &ma, const 
         for (uint32_t ch = 0; ch < C; ch++) vals[ch * SX_PLACE_THREADS + t] = wx_value(a, rc, type, i0 + t, ch);
     __syncthreads();
     if (t < len) {
-        const uint64_t k = (ra + t) / m.b, ba = k * m.b;
-        const uint32_t ta = ba > ra ? (uint32_t)(ba - ra) : 0u;
+        const uint64_t k = (pc.ra + t) / m.b;
+        uint32_t ta, te;
+        pc.lanes(k, ta, te);
         if (t == ta) {
-            const uint64_t tb64 = ba + m.b - ra;
-            const uint32_t tb = tb64 > len ? len : (uint32_t)tb64;
             for (uint32_t ch = 0; ch < C; ch++) {
                 WxAcc r; wxm_clear(r);
-                for (uint32_t j = ta; j < tb; j++) wxm_note(r, vals[ch * SX_PLACE_THREADS + j]);
+                for (uint32_t j = ta; j < te; j++) wxm_note(r, vals[ch * SX_PLACE_THREADS + j]);
                 wxm_atomics(acc + (uint64_t)ch * m.nb + k, r);
             }
         }
@@ -144,52 +122,34 @@ __device__ __forceinline__ void wx_measure_piece(const WxMeasureArgs &ma, const 
 /* nrec * xch workgroups: the y-th xch of them measure record y, piece by piece as k_wx_place places it */
 __global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_measure(WxMeasureArgs ma)
 {
-    __shared__ WxAcc part[WXM_SEGMENTS][SX_PLACE_THREADS / 64u][LINNE_MAX_NUM_CHANNELS];
+    __shared__ WxAcc part[WXB_SEGMENTS][SX_PLACE_THREADS / 64u][LINNE_MAX_NUM_CHANNELS];
     __shared__ int32_t vals[LINNE_MAX_NUM_CHANNELS * SX_PLACE_THREADS];
-    const WxPlaceArgs &a = ma.p;
-    const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
-    if (y >= a.nrec) return;
-    const WxBlock *rc = a.recs + y;
-    const WxWindow w = a.wins[rc->win];
-    const WxMeasure m = ma.mwin[rc->win];
-    if (a.fail[w.fidx] != WX_NOFAIL) return;                       /* block-uniform, as every exit */
-    const uint32_t type = rc->type;
-    if (type == WX_TAIL) {
-        const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
-        for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-            wx_measure_piece(ma, w, m, rc, type, s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS, part, vals);
-    } else {
-        const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
-        for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
-            const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
-            const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
-            if (sa < sb) wx_measure_piece(ma, w, m, rc, type, f0, sa, sb, part, vals);
-        }
-    }
+    WxRecord r;
+    if (!wx_prologue(ma.p, r)) return;
+    const WxBucket m = ma.mwin[r.rc->win];
+    wx_walk(ma.p, r.rc, r.w, r.type, r.x, [&](uint64_t f0, uint64_t sa, uint64_t sb) { wx_measure_piece(ma, r.w, m, r.rc, r.type, f0, sa, sb, part, vals); });
 }
 
 /* every accumulator of the call to the operations' identities */
-__global__ __launch_bounds__(WXM_THREADS) void k_wx_measure_preset(struct LINNEAmdMeasure *acc, uint64_t total)
+__global__ __launch_bounds__(WXB_THREADS) void k_wx_measure_preset(struct LINNEAmdMeasure *acc, uint64_t total)
 {
     struct LINNEAmdMeasure z; z.min = INT32_MAX; z.max = INT32_MIN; z.sum = 0; z.sumsq_lo = 0u; z.sumsq_hi = 0u;
-    for (uint64_t g = (uint64_t)blockIdx.x * WXM_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXM_THREADS) acc[g] = z;
+    for (uint64_t g = (uint64_t)blockIdx.x * WXB_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXB_THREADS) acc[g] = z;
 }
 
 /* A lane per (channel, bucket) of every measured window, numbered through the windows in their records' order (obase): the
  * window's slots folded and the record stored in the caller's table, unless the window's fail word is set */
-__global__ __launch_bounds__(WXM_THREADS) void k_wx_measure_commit(const WxMeasure *mwin, uint32_t nwin, const struct LINNEAmdMeasure *acc, const uint32_t *fail, uint64_t total)
+__global__ __launch_bounds__(WXB_THREADS) void k_wx_measure_commit(const WxBucket *mwin, uint32_t nwin, const struct LINNEAmdMeasure *acc, const uint32_t *fail, uint64_t total)
 {
-    for (uint64_t g = (uint64_t)blockIdx.x * WXM_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXM_THREADS) {
-        uint32_t lo = 0, hi = nwin;                                 /* the last window whose obase <= g */
-        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (mwin[mid].obase <= g) lo = mid; else hi = mid; }
-        const WxMeasure m = mwin[lo];
+    for (uint64_t g = (uint64_t)blockIdx.x * WXB_THREADS + threadIdx.x; g < total; g += (uint64_t)gridDim.x * WXB_THREADS) {
+        const WxBucket m = mwin[wx_bucket_window(mwin, nwin, g)];
         if (fail[m.fidx] != WX_NOFAIL) continue;
         const uint64_t e = g - m.obase, ch = e / m.nb, k = e - ch * m.nb, C = m.C;
         const struct LINNEAmdMeasure *p = acc + m.abase + e;
         WxAcc r; wxm_clear(r);
         for (uint32_t s = 0; s < m.ns; s++, p += C * m.nb) wxm_fold(r, p->min, p->max, p->sum, p->sumsq_lo, p->sumsq_hi);
         struct LINNEAmdMeasure o; o.min = r.mn; o.max = r.mx; o.sum = r.sum; o.sumsq_lo = r.qlo; o.sumsq_hi = r.qhi;
-        m.out[ch * m.cstride + k] = o;
+        ((struct LINNEAmdMeasure *)m.out)[ch * m.cstride + k] = o;
     }
 }
 

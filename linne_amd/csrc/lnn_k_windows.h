@@ -16,33 +16,17 @@
  *                             to the window's struct LINNEAmdPcmLayout: int16, packed 24-bit, float32; interleaved, padded); a record of type
  *                             WX_TAIL is the part of a window beyond the stream's last block (zeros).  The records of a window whose
  *                             fail word is set are skipped: a failing window's output is not written
+ * k_wx_place and the kernels that stand in its place in the sibling calls -- k_wx_compare (lnn_k_compare.h), k_wx_measure
+ * (lnn_k_measure.h), k_wx_digest (lnn_k_digest.h) -- begin with wx_prologue and cut their record into pieces with wx_walk, below;
+ * they differ in what they do with a piece.
  * As in lnn_k_stream.h, no read of a stream leaves [0, stream_bytes): RAW samples are un-zig-zagged straight from the stream.
  */
 #ifndef LNN_K_WINDOWS_H_INCLUDED
 #define LNN_K_WINDOWS_H_INCLUDED
 
-#define WX_TAIL 3u                      /* record type beside SX_COMPRESS / SX_SILENT / SX_RAW: a window's samples in [covered, hi) */
-#define WX_GATHER_THREADS 256u
-#define WX_NOFAIL 0xFFFFFFFFu
+#include "lnn_windows_plan.h"          /* the records the host's plan fills: WxBlock, WxWindow, WX_TAIL, WX_NOFAIL */
 
-/* one block of one window (64 bytes) */
-struct WxBlock {
-    const uint8_t *b; uint64_t N;       /* the block's stream and its length */
-    uint64_t off;                       /* the block's position in it */
-    uint64_t first;                     /* its first sample */
-    uint64_t dst;                       /* COMPRESS: where its first byte lies in the pass's packed segment; (dst & 15) == ((b + off) & 15) */
-    uint32_t size, type, nsmp;          /* the size field, SX_* / WX_TAIL, samples */
-    uint32_t win;                       /* its window's record */
-    uint32_t cidx;                      /* index among the pass's COMPRESS blocks, or ~0 */
-    uint32_t blk;                       /* its number in its stream */
-};
-/* one window (64 bytes) */
-struct WxWindow {
-    uint64_t lo, hi, covered;           /* the range [lo, hi); the samples the stream's blocks hold */
-    void *out; uint64_t stride;         /* element (ch, i) at out + (ch * stride + i * sstride) elements of fmt */
-    uint32_t fidx, fmt;                 /* its fail word (its saturation word lies W words behind it); LINNE_AMD_PCM_* */
-    uint64_t sstride;                   /* (int32 planar: fmt S32, sstride 1) */
-};
+#define WX_GATHER_THREADS 256u
 
 /* Workgroup k copies COMPRESS block k's size + 6 bytes to seg + dst.  Source and destination have the same address modulo 16 (the
  * host chose dst so): the 16-byte groups that lie wholly inside the block travel as one load and one store, the two at its ends
@@ -201,33 +185,60 @@ __device__ __forceinline__ int wx_place_layout(const WxPlaceArgs &a, const WxWin
     return sat;
 }
 
-/* nrec * xch workgroups: the y-th xch of them place record y */
-__global__ __launch_bounds__(SX_PLACE_THREADS) void k_wx_place(WxPlaceArgs a)
+/* ---- the record walk k_wx_place and its siblings (lnn_k_compare.h, lnn_k_measure.h, lnn_k_digest.h) share ---- */
+/* What workgroup blockIdx.x of a grid of nrec * xch starts with: the y-th xch workgroups take record y, this one as its x-th.  false:
+ * nothing to do -- no such record, or its window's fail word is set.  Every exit is block-uniform */
+struct WxRecord { const WxBlock *rc; WxWindow w; uint32_t type, x; };
+__device__ __forceinline__ bool wx_prologue(const WxPlaceArgs &a, WxRecord &r)
+{
+    const uint32_t y = blockIdx.x / a.xch;
+    r.x = blockIdx.x % a.xch;
+    if (y >= a.nrec) return false;
+    r.rc = a.recs + y;
+    r.w = a.wins[r.rc->win];
+    if (a.fail[r.w.fidx] != WX_NOFAIL) return false;
+    r.type = r.rc->type;
+    return true;
+}
+/* piece(f0, sa, sb) for every piece of record rc that this workgroup takes: samples [sa, sb) of the stream, at most SX_PLACE_THREADS
+ * of them and inside the window, of a record whose sample 0 is stream sample f0.  A WX_TAIL record is cut from max(covered, lo) on
+ * (f0 = sa: its "block" begins with the piece); a block record is cut from its first sample on and every piece cropped to [lo, hi).
+ * sa and sb are block-uniform, so a piece may hold barriers */
+template <class Piece> __device__ __forceinline__ void wx_walk(const WxPlaceArgs &a, const WxBlock *rc, const WxWindow &w, uint32_t type, uint32_t x, Piece piece)
+{
+    if (type == WX_TAIL) {
+        const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
+        for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
+            piece(s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS);
+    } else {
+        const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
+        for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
+            const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
+            const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
+            if (sa < sb) piece(f0, sa, sb);
+        }
+    }
+}
+
+/* nrec * xch workgroups: the y-th xch of them place record y.  Held to the 96 scalar registers it had before the layout branch went
+ * through wx_walk: 256-thread workgroups are admitted per CU by their scalar registers in steps of 16, seven at 96 and six at the 102
+ * the compiler takes otherwise, and the int32 path, a thread per sample and bound by how many workgroups are in flight, is a tenth
+ * slower with six (profiles/ab_windows_shared_walk.txt has both; nothing spills under the cap) */
+__global__ __launch_bounds__(SX_PLACE_THREADS) __attribute__((amdgpu_num_sgpr(96))) void k_wx_place(WxPlaceArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t img[WX_IMG_BYTES];
-    const uint32_t y = blockIdx.x / a.xch, x = blockIdx.x % a.xch;
-    if (y >= a.nrec) return;
-    const WxBlock *rc = a.recs + y;
-    const WxWindow w = a.wins[rc->win];
-    if (a.fail[w.fidx] != WX_NOFAIL) return;
-    const uint32_t type = rc->type;
+    WxRecord r;
+    if (!wx_prologue(a, r)) return;
+    const WxBlock *rc = r.rc;
+    const WxWindow w = r.w;
+    const uint32_t type = r.type, x = r.x;
     if (w.fmt != LINNE_AMD_PCM_S32 || w.sstride != 1u) {         /* block-uniform */
         int sat = 0;
-        if (type == WX_TAIL) {
-            const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;
-            for (uint64_t s = z0 + (uint64_t)x * SX_PLACE_THREADS; s < w.hi; s += (uint64_t)a.xch * SX_PLACE_THREADS)
-                sat |= wx_place_layout(a, w, rc, type, s, s, (w.hi - s < SX_PLACE_THREADS) ? w.hi : s + SX_PLACE_THREADS, img);
-        } else {
-            const uint64_t f0 = rc->first, e = f0 + rc->nsmp;
-            for (uint64_t s = f0 + (uint64_t)x * SX_PLACE_THREADS; s < e; s += (uint64_t)a.xch * SX_PLACE_THREADS) {
-                const uint64_t s1 = (e - s < SX_PLACE_THREADS) ? e : s + SX_PLACE_THREADS;
-                const uint64_t sa = s > w.lo ? s : w.lo, sb = s1 < w.hi ? s1 : w.hi;
-                if (sa < sb) sat |= wx_place_layout(a, w, rc, type, f0, sa, sb, img);
-            }
-        }
+        wx_walk(a, rc, w, type, x, [&](uint64_t f0, uint64_t sa, uint64_t sb) { sat |= wx_place_layout(a, w, rc, type, f0, sa, sb, img); });
         if (sat && threadIdx.x == 0) atomicOr(&a.sat[w.fidx], 1u);
         return;
     }
+    /* int32 with sample stride 1: a thread per sample, no pieces */
     int32_t *out = (int32_t *)w.out;
     if (type == WX_TAIL) {
         const uint64_t z0 = w.covered > w.lo ? w.covered : w.lo;

@@ -1,0 +1,263 @@
+/* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure
+ * and digest; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
+ * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
+ * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
+ *
+ * A call plans in two steps.  wx_plan_count: which group every live window belongs to, which of its stream's blocks it overlaps, and
+ * how many block records and COMPRESS entries the lists must have room for.  The caller sizes the lists from that (wx_lists) and
+ * hands their memory to wx_plan_fill, which writes the records pass by pass:
+ *   - the windows of one shape form a group; a group's windows are taken in the caller's order;
+ *   - a pass holds at most group_frames COMPRESS blocks (0: no limit); a window's blocks are not split from the window before it
+ *     unless they have to be;
+ *   - a window with more COMPRESS blocks than a pass takes first has all of them in check-only passes of its own (its Rice codes are
+ *     checked, nothing is placed), so that no sample of it is written before all that its fail word can say is known;
+ *   - a window that reaches beyond the samples its stream's blocks hold gets a WX_TAIL record in front of its blocks;
+ *   - a COMPRESS block's bytes get a slot of whole 16-byte groups in the pass's packed segment, at the source's address modulo 16.
+ */
+#ifndef LNN_WINDOWS_PLAN_H_INCLUDED
+#define LNN_WINDOWS_PLAN_H_INCLUDED
+
+#include <assert.h>
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+
+#include "linne_amd.h"
+
+#ifndef SX_COMPRESS                     /* (lnn_k_stream.h has the block types too) */
+#define SX_COMPRESS 0u
+#define SX_SILENT 1u
+#define SX_RAW 2u
+#endif
+#define WX_TAIL 3u                      /* record type beside SX_COMPRESS / SX_SILENT / SX_RAW: a window's samples in [covered, hi) */
+#define WX_NOFAIL 0xFFFFFFFFu
+#define WX_MAXGROUPS 64
+/* the bucketed consumers (lnn_k_buckets.h) */
+#define WXB_SEGMENTS 4u                 /* up to this many buckets in a piece are reduced by the whole workgroup, one after the other */
+#define WXB_MAXSLOTS 64u
+#define WXB_THREADS 256u
+
+/* one block of one window (64 bytes) */
+struct WxBlock {
+    const uint8_t *b; uint64_t N;       /* the block's stream and its length */
+    uint64_t off;                       /* the block's position in it */
+    uint64_t first;                     /* its first sample */
+    uint64_t dst;                       /* COMPRESS: where its first byte lies in the pass's packed segment; (dst & 15) == ((b + off) & 15) */
+    uint32_t size, type, nsmp;          /* the size field, SX_* / WX_TAIL, samples */
+    uint32_t win;                       /* its window's record */
+    uint32_t cidx;                      /* index among the pass's COMPRESS blocks, or ~0 */
+    uint32_t blk;                       /* its number in its stream */
+};
+/* one window (56 bytes) */
+struct WxWindow {
+    uint64_t lo, hi, covered;           /* the range [lo, hi); the samples the stream's blocks hold */
+    void *out; uint64_t stride;         /* element (ch, i) at out + (ch * stride + i * sstride) elements of fmt */
+    uint32_t fidx, fmt;                 /* its fail word (its saturation word lies W words behind it); LINNE_AMD_PCM_* */
+    uint64_t sstride;                   /* (int32 planar: fmt S32, sstride 1) */
+};
+/* one window's buckets (64 bytes), at its WxWindow's index: what a bucketed consumer keeps per window.  A consumer leaves zero what it
+ * does not use */
+struct WxBucket {
+    void *out;                          /* the caller's table */
+    uint64_t b, nb;                     /* bucket length (the window's length for "one bucket"), buckets */
+    uint64_t abase;                     /* its accumulators in the scratch, in the consumer's units */
+    uint64_t obase;                     /* the number of output records of the windows before it */
+    union { uint64_t cstride, n; };     /* per channel: the caller's channel stride; per frame: the window's samples */
+    uint32_t ns, fidx;                  /* slots (a power of two); its fail word */
+    union { uint32_t C, F; };           /* per channel: channels; per frame: bytes per sample frame */
+    uint32_t sstride;                   /* per frame: units from one slot to the next (per channel: C * nb, not kept) */
+};
+static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record and a bucket record are 64 bytes");
+
+/* how a consumer keeps buckets: not at all; an accumulator per (channel, bucket), a window's slots C * nb apart (measure); one per
+ * bucket, a window's slots padded to whole 64-byte lines of 16 units (digest) */
+enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2 };
+
+/* what the plan reads of a block index */
+struct WxIndexView {
+    struct LINNEAmdShape shape;
+    uint32_t nb; uint64_t covered, stream_bytes;
+    const uint64_t *h_off, *h_first; const uint32_t *h_size, *h_type, *h_nsmp;
+};
+/* one window of the call */
+struct WxRange {
+    WxIndexView x; const uint8_t *stream;       /* (the address is used modulo 16, nothing is read) */
+    int live;                           /* it passed its checks and has samples: the fields below are set */
+    uint64_t lo, n, r1;                 /* [lo, lo + n); the last block it overlaps (nb: it reaches behind the last block) */
+    void *out; uint64_t stride, sstride; uint32_t fmt;          /* its WxWindow's */
+    uint64_t bucket_samples, bucket_cstride; void *bucket_out;  /* bucketed consumers: its spec */
+};
+struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
+struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
+struct WxPlanned {
+    std::vector<WxPlan> win;            /* [W] */
+    uint32_t ngroups, gwin[WX_MAXGROUPS];       /* a window of every group: its stream has the group's shape */
+    uint64_t nlive, total_rec, total_crec;      /* what the lists are reserved for (wx_plan_count) */
+    std::vector<WxPass> passes;
+    uint32_t nwin, nrec, ncrec;         /* records written (wx_plan_fill): nwin == nlive, nrec <= total_rec, ncrec <= total_crec */
+    uint64_t scratch_bytes;             /* the largest pass's */
+    uint64_t nacc, nout;                /* bucketed consumers: accumulator units, output records */
+};
+enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
+
+static inline uint64_t wx_align(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
+/* the block holding sample s (s < covered): the last r < nb with first[r] <= s */
+static inline uint64_t wx_block_of(const uint64_t *first, uint64_t nb, uint64_t s)
+{
+    uint64_t lo = 0, hi = nb;
+    while (hi - lo > 1u) { const uint64_t mid = lo + ((hi - lo) >> 1); if (first[mid] <= s) lo = mid; else hi = mid; }
+    return lo;
+}
+/* the buckets of a window of n samples (0 for none) */
+static inline uint64_t wx_buckets(uint64_t n, uint64_t b) { return n == 0 ? 0u : (b == 0 || b >= n) ? 1u : n / b + (n % b != 0); }
+/* A bucket of L samples takes L / 256 pieces, each one atomic per accumulator: from 8192 samples on they are spread over L / 4096
+ * slots, WXB_MAXSLOTS at most */
+static inline uint32_t wx_slots(uint64_t b) { uint32_t ns = 1u; while (ns < WXB_MAXSLOTS && (b >> 12) >= 2u * ns) ns *= 2u; return ns; }
+
+/* the buffers of one pass in the context's scratch */
+struct WxScratch { uint64_t o_nsmp, o_bpos, o_bend, o_eb, o_prm, o_data, o_seg, bytes; };
+static inline WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t seg_bytes)
+{
+    WxScratch s; uint64_t at = 0;
+    s.o_nsmp = at; at = wx_align(at + sizeof(uint32_t) * (nc + 1u));
+    s.o_bpos = at; at = wx_align(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_bend = at; at = wx_align(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_eb = at; at = wx_align(at + sizeof(uint64_t) * (nc + 1u));
+    s.o_prm = at; at = wx_align(at + sizeof(int32_t) * LINNE_AMD_PARAM_WORDS * C * (uint64_t)nc);
+    s.o_data = at; at = wx_align(at + sizeof(int32_t) * (uint64_t)C * S * nc);
+    s.o_seg = at; at = wx_align(at + seg_bytes + 16u);
+    s.bytes = at;
+    return s;
+}
+
+/* the lists, in pinned memory and at the same offsets on the device: the words that come back (fail words, saturation words and
+ * back_words 32-bit words per window of the consumer's own) | window records | the consumer's per-window records | block records |
+ * the passes' COMPRESS records */
+struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes; };
+static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes)
+{
+    WxLists l;
+    l.o_fail = 0; l.o_back = 2u * sizeof(uint32_t) * W; l.back_bytes = l.o_back + sizeof(uint32_t) * back_words * W;
+    l.o_win = wx_align(l.back_bytes);
+    l.o_side = wx_align(l.o_win + sizeof(WxWindow) * p.nlive);
+    l.o_rec = wx_align(l.o_side + side_bytes * p.nlive);
+    l.o_crec = wx_align(l.o_rec + sizeof(WxBlock) * p.total_rec);
+    l.bytes = wx_align(l.o_crec + sizeof(uint32_t) * (p.total_crec + 1u));
+    return l;
+}
+
+/* step 1: the live windows get their blocks and the group of their shape */
+static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_frames, WxPlanned &p)
+{
+    p.win.resize(W);
+    p.ngroups = 0; p.nlive = p.total_rec = p.total_crec = 0;
+    p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = 0;
+    for (uint32_t i = 0; i < W; i++) {
+        WxPlan &pl = p.win[i];
+        pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
+        if (!rg[i].live) continue;
+        const WxIndexView &x = rg[i].x;
+        const uint64_t lo = rg[i].lo, r1 = rg[i].r1;
+        const uint64_t r0 = (lo < x.covered) ? wx_block_of(x.h_first, x.nb, lo) : x.nb;
+        const uint64_t nr = (r0 < x.nb) ? ((r1 < x.nb ? r1 : x.nb - 1u) - r0 + 1u) : 0u;
+        uint32_t nc = 0;
+        for (uint64_t y = 0; y < nr; y++) nc += (x.h_type[r0 + y] == SX_COMPRESS);
+        uint32_t g = 0;
+        while (g < p.ngroups && memcmp(&rg[p.gwin[g]].x.shape, &x.shape, sizeof(x.shape)) != 0) g++;
+        if (g == p.ngroups) {
+            if (p.ngroups == WX_MAXGROUPS) return WXP_SHAPES;
+            p.gwin[p.ngroups++] = i;
+        }
+        pl.r0 = (uint32_t)r0; pl.nr = (uint32_t)nr; pl.ncomp = nc; pl.group = (int32_t)g;
+        const bool big = group_frames && nc > group_frames;
+        p.nlive++; p.total_rec += nr + 1u + (big ? nc : 0u); p.total_crec += (uint64_t)nc * (big ? 2u : 1u);
+    }
+    return (p.nlive && p.total_rec >= 0x7FFFFFFFull) ? WXP_BLOCKS : WXP_OK;
+}
+
+/* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
+ * entries; h_side NULL for WX_NO_BUCKETS */
+static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
+        WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec)
+{
+    for (uint32_t g = 0; g < p.ngroups; g++) {
+        const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
+        WxPass cur;
+        auto fresh = [&](int check_only) { cur.group = g; cur.rec0 = p.nrec; cur.nrec = 0; cur.c0 = p.ncrec; cur.nc = 0; cur.seg_bytes = 0; cur.check_only = check_only; };
+        auto close = [&](int check_only) {
+            if (cur.nrec) {
+                const WxScratch sc = wx_scratch(cur.nc, shape.num_channels, shape.num_samples_per_block, cur.seg_bytes);
+                if (sc.bytes > p.scratch_bytes) p.scratch_bytes = sc.bytes;
+                p.passes.push_back(cur);
+            }
+            fresh(check_only);
+        };
+        auto add = [&](const WxRange &w, uint32_t wi, uint32_t type, uint32_t r) {
+            const WxIndexView &x = w.x;
+            /* the counts of step 1 are what the lists were reserved for: nothing is written past them */
+            assert(p.nrec < p.total_rec && (type != SX_COMPRESS || p.ncrec < p.total_crec));
+            WxBlock &rc = h_rec[p.nrec++];
+            memset(&rc, 0, sizeof(rc));
+            rc.b = w.stream; rc.N = x.stream_bytes; rc.type = type; rc.win = wi; rc.cidx = 0xFFFFFFFFu; rc.blk = r;
+            if (type != WX_TAIL) { rc.off = x.h_off[r]; rc.first = x.h_first[r]; rc.size = x.h_size[r]; rc.nsmp = x.h_nsmp[r]; }
+            if (type == SX_COMPRESS) {
+                /* the block's slot in the packed segment: whole 16-byte groups, the block at its source's address modulo 16 */
+                rc.dst = cur.seg_bytes + ((uintptr_t)(w.stream + rc.off) & 15u);
+                cur.seg_bytes = (rc.dst + (uint64_t)rc.size + 6u + 15u) & ~(uint64_t)15u;
+                rc.cidx = cur.nc++;
+                h_crec[p.ncrec++] = cur.nrec;
+            }
+            cur.nrec++;
+        };
+        fresh(0);
+        for (uint32_t i = 0; i < W; i++) {
+            const WxPlan &pl = p.win[i];
+            if (pl.group != (int32_t)g) continue;
+            const WxRange &w = rg[i];
+            const WxIndexView &x = w.x;
+            assert(p.nwin < p.nlive);
+            const uint32_t wi = p.nwin++;
+            WxWindow &ww = h_win[wi];
+            ww.lo = w.lo; ww.hi = w.lo + w.n; ww.covered = x.covered; ww.out = w.out; ww.fidx = i;
+            ww.fmt = w.fmt; ww.stride = w.stride; ww.sstride = w.sstride;
+            if (bucketing != WX_NO_BUCKETS) {
+                WxBucket &m = h_side[wi];
+                const uint64_t b = w.bucket_samples, C = shape.num_channels;
+                memset(&m, 0, sizeof(m));
+                m.out = w.bucket_out; m.b = (b == 0 || b > w.n) ? w.n : b; m.nb = wx_buckets(w.n, b); m.ns = wx_slots(m.b);
+                m.abase = p.nacc; m.obase = p.nout; m.fidx = i;
+                if (bucketing == WX_BUCKETS_PER_CHANNEL) {
+                    m.cstride = w.bucket_cstride; m.C = (uint32_t)C;
+                    p.nacc += m.ns * C * m.nb; p.nout += C * m.nb;
+                } else {
+                    /* the slots lie 16 words or more apart, no two in one 64-byte line */
+                    m.n = w.n; m.F = (uint32_t)C * ((shape.bits_per_sample + 7u) >> 3);
+                    m.sstride = (uint32_t)((m.nb + 15u) & ~(uint64_t)15u);  /* (nb < 2^32 - 15 where ns > 1: such a bucket has 8192 samples) */
+                    p.nacc += m.ns > 1u ? (uint64_t)m.ns * m.sstride : m.nb; p.nout += m.nb;
+                }
+            }
+            const bool big = group_frames && pl.ncomp > group_frames;
+            if (big) {
+                close(1);
+                for (uint32_t y = 0; y < pl.nr; y++) {
+                    const uint32_t r = pl.r0 + y;
+                    if (x.h_type[r] != SX_COMPRESS) continue;
+                    if (cur.nc == group_frames) close(1);
+                    add(w, wi, SX_COMPRESS, r);
+                }
+                close(0);
+            } else if (group_frames && cur.nc + pl.ncomp > group_frames) close(0);
+            if (ww.hi > ww.covered) add(w, wi, WX_TAIL, 0);
+            for (uint32_t y = 0; y < pl.nr; y++) {
+                const uint32_t r = pl.r0 + y, type = x.h_type[r];
+                if (type == SX_COMPRESS && group_frames && cur.nc == group_frames) close(0);
+                add(w, wi, type, r);
+            }
+            if (big) close(0);
+        }
+        close(0);
+    }
+}
+
+#endif

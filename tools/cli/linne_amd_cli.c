@@ -141,33 +141,51 @@ static int read_file(const char *path, uint8_t **data, uint32_t *size)
     return 0;
 }
 
+/* A whole stream resident on the device 0, as -V, -C, -M and -D want it: a context, the stream's bytes, its block index, `extra` bytes
+ * beside it for what the call reads or writes, and the one window over all its samples */
+struct resident {
+    struct LINNEAmdContext *ctx;
+    struct LINNEAmdStreamIndex *index;
+    void *d_stream, *d_extra;
+    struct LINNEAmdWindow w;
+};
+/* 0, or the stage that failed with its text in err: 1 the context, 2 the copies (`what` went to the device), 3 the index */
+static int resident_open(struct resident *r, const uint8_t *stream, uint32_t size, uint64_t num_samples, uint64_t extra, const char *what, char *err, size_t cap)
+{
+    int ret = LINNE_APIRESULT_OK;
+    memset(r, 0, sizeof(*r));
+    if (!(r->ctx = LINNEAmd_ContextCreate(0, 0))) { snprintf(err, cap, "Failed to create a device context."); return 1; }
+    if (hipMalloc(&r->d_stream, size ? size : 1) != hipSuccess || hipMemcpy(r->d_stream, stream, size, hipMemcpyHostToDevice) != hipSuccess
+            || hipMalloc(&r->d_extra, extra ? extra : 1) != hipSuccess) { snprintf(err, cap, "Failed to copy %s to the device.", what); return 2; }
+    if (!(r->index = LINNEAmd_StreamIndexCreate(r->ctx, r->d_stream, size, &ret))) { snprintf(err, cap, "the stream does not index: %d (%s)", ret, LINNEAmd_GetLastError(r->ctx)); return 3; }
+    r->w.index = r->index; r->w.d_stream = r->d_stream; r->w.first_sample = 0; r->w.num_samples = num_samples;
+    return 0;
+}
+static void resident_close(struct resident *r)
+{
+    if (r->index) LINNEAmd_StreamIndexDestroy(r->index);
+    if (r->d_extra) (void)hipFree(r->d_extra);
+    if (r->d_stream) (void)hipFree(r->d_stream);
+    if (r->ctx) LINNEAmd_ContextDestroy(r->ctx);
+}
+
 /* The stream and the WAV's int32 planes go to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_CompareWindowsDevice window over
  * the whole stream answer.  0: *diff is the answer; 1: the stream does not index or decode, or the device failed (text in err) */
 static int device_compare(const uint8_t *stream, uint32_t size, const struct wav_pcm *wav, struct LINNEAmdDiff *diff, char *err, size_t cap)
 {
-    struct LINNEAmdContext *ctx = NULL;
-    struct LINNEAmdStreamIndex *index = NULL;
-    struct LINNEAmdWindow w;
-    void *d_stream = NULL, *d_pcm = NULL;
+    struct resident r;
     const uint64_t n = wav->num_samples, plane = n * sizeof(int32_t);
     uint32_t ch;
-    int ret = LINNE_APIRESULT_OK, rc = 1;
+    int ret, rc = 1;
     memset(diff, 0, sizeof(*diff));
-    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { snprintf(err, cap, "Failed to create a device context."); return 1; }
-    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, stream, size, hipMemcpyHostToDevice) != hipSuccess
-            || hipMalloc(&d_pcm, (plane && wav->num_channels) ? plane * wav->num_channels : 1) != hipSuccess) { snprintf(err, cap, "Failed to copy the stream and the samples to the device."); goto done; }
+    if (resident_open(&r, stream, size, n, plane * wav->num_channels, "the stream and the samples", err, cap) != 0) goto done;
     for (ch = 0; ch < wav->num_channels; ch++)
-        if (plane && hipMemcpy((uint8_t *)d_pcm + ch * plane, wav->plane[ch], plane, hipMemcpyHostToDevice) != hipSuccess) { snprintf(err, cap, "Failed to copy the stream and the samples to the device."); goto done; }
-    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { snprintf(err, cap, "the stream does not index: %d (%s)", ret, LINNEAmd_GetLastError(ctx)); goto done; }
-    memset(&w, 0, sizeof(w));
-    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n; w.d_pcm = d_pcm; w.pcm_stride = n;
-    if ((ret = LINNEAmd_CompareWindowsDevice(ctx, &w, NULL, diff, 1, 0)) != LINNE_APIRESULT_OK) { snprintf(err, cap, "the stream does not decode: %d (%s)", ret, LINNEAmd_GetLastError(ctx)); goto done; }
+        if (plane && hipMemcpy((uint8_t *)r.d_extra + ch * plane, wav->plane[ch], plane, hipMemcpyHostToDevice) != hipSuccess) { snprintf(err, cap, "Failed to copy the stream and the samples to the device."); goto done; }
+    r.w.d_pcm = r.d_extra; r.w.pcm_stride = n;
+    if ((ret = LINNEAmd_CompareWindowsDevice(r.ctx, &r.w, NULL, diff, 1, 0)) != LINNE_APIRESULT_OK) { snprintf(err, cap, "the stream does not decode: %d (%s)", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
     rc = 0;
 done:
-    if (index) LINNEAmd_StreamIndexDestroy(index);
-    if (d_pcm) (void)hipFree(d_pcm);
-    if (d_stream) (void)hipFree(d_stream);
-    LINNEAmd_ContextDestroy(ctx);
+    resident_close(&r);
     return rc;
 }
 
@@ -219,28 +237,22 @@ static int measure_one(const char *lnn_path, uint64_t bucket)
 {
     uint8_t *buf = NULL;
     uint32_t size = 0, ch;
-    struct LINNEAmdContext *ctx = NULL;
-    struct LINNEAmdStreamIndex *index = NULL;
-    struct LINNEAmdWindow w;
+    struct resident r;
     struct LINNEAmdMeasureSpec spec;
     struct LINNEAmdMeasure *tab = NULL;
     struct LINNEHeader h;
-    void *d_stream = NULL, *d_out = NULL;
+    char err[512];
     uint64_t n, nb, k;
-    int ret = LINNE_APIRESULT_OK, rc = 1;
+    int ret, stage, rc = 1;
     if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
     if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
     n = h.num_samples;
     nb = n == 0 ? 0 : (bucket == 0 || bucket >= n) ? 1 : (n + bucket - 1) / bucket;
-    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { fprintf(stderr, "Failed to create a device context. \n"); goto done; }
-    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, buf, size, hipMemcpyHostToDevice) != hipSuccess
-            || hipMalloc(&d_out, nb ? sizeof(*tab) * nb * h.num_channels : 1) != hipSuccess) { fprintf(stderr, "Failed to copy the stream to the device. \n"); goto done; }
-    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { fprintf(stderr, "Failed to measure! the stream does not index: %d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
-    memset(&w, 0, sizeof(w)); memset(&spec, 0, sizeof(spec));
-    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n;
-    spec.bucket_samples = bucket; spec.d_out = d_out; spec.channel_stride = nb;
-    if ((ret = LINNEAmd_MeasureWindowsDevice(ctx, &w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to measure! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
-    if (!(tab = malloc(nb ? sizeof(*tab) * nb * h.num_channels : 1)) || (nb && hipMemcpy(tab, d_out, sizeof(*tab) * nb * h.num_channels, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    if ((stage = resident_open(&r, buf, size, n, sizeof(*tab) * nb * h.num_channels, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to measure! %s \n" : "%s \n", err); goto done; }
+    memset(&spec, 0, sizeof(spec));
+    spec.bucket_samples = bucket; spec.d_out = r.d_extra; spec.channel_stride = nb;
+    if ((ret = LINNEAmd_MeasureWindowsDevice(r.ctx, &r.w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to measure! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * nb * h.num_channels : 1)) || (nb && hipMemcpy(tab, r.d_extra, sizeof(*tab) * nb * h.num_channels, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
     for (k = 0; k < nb; k++)
         for (ch = 0; ch < h.num_channels; ch++) {
             const struct LINNEAmdMeasure *m = tab + ch * nb + k;
@@ -252,10 +264,7 @@ static int measure_one(const char *lnn_path, uint64_t bucket)
         }
     rc = 0;
 done:
-    if (index) LINNEAmd_StreamIndexDestroy(index);
-    if (d_out) (void)hipFree(d_out);
-    if (d_stream) (void)hipFree(d_stream);
-    if (ctx) LINNEAmd_ContextDestroy(ctx);
+    resident_close(&r);
     free(tab); free(buf);
     return rc;
 }
@@ -266,37 +275,28 @@ static int digest_one(const char *lnn_path, uint64_t bucket)
 {
     uint8_t *buf = NULL;
     uint32_t size = 0;
-    struct LINNEAmdContext *ctx = NULL;
-    struct LINNEAmdStreamIndex *index = NULL;
-    struct LINNEAmdWindow w;
+    struct resident r;
     struct LINNEAmdDigestSpec spec;
     struct LINNEAmdDigest *tab = NULL;
     struct LINNEHeader h;
-    void *d_stream = NULL, *d_out = NULL;
+    char err[512];
     uint64_t n, nb, k;
-    int ret = LINNE_APIRESULT_OK, rc = 1;
+    int ret, stage, rc = 1;
     if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
     if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
     n = h.num_samples;
     nb = n == 0 ? 0 : (bucket == 0 || bucket >= n) ? 1 : (n + bucket - 1) / bucket;
-    if (!(ctx = LINNEAmd_ContextCreate(0, 0))) { fprintf(stderr, "Failed to create a device context. \n"); goto done; }
-    if (hipMalloc(&d_stream, size ? size : 1) != hipSuccess || hipMemcpy(d_stream, buf, size, hipMemcpyHostToDevice) != hipSuccess
-            || hipMalloc(&d_out, nb ? sizeof(*tab) * nb : 1) != hipSuccess) { fprintf(stderr, "Failed to copy the stream to the device. \n"); goto done; }
-    if (!(index = LINNEAmd_StreamIndexCreate(ctx, d_stream, size, &ret))) { fprintf(stderr, "Failed to digest! the stream does not index: %d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
-    memset(&w, 0, sizeof(w)); memset(&spec, 0, sizeof(spec));
-    w.index = index; w.d_stream = d_stream; w.first_sample = 0; w.num_samples = n;
-    spec.bucket_samples = bucket; spec.d_out = d_out;
-    if ((ret = LINNEAmd_DigestWindowsDevice(ctx, &w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to digest! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(ctx)); goto done; }
-    if (!(tab = malloc(nb ? sizeof(*tab) * nb : 1)) || (nb && hipMemcpy(tab, d_out, sizeof(*tab) * nb, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    if ((stage = resident_open(&r, buf, size, n, sizeof(*tab) * nb, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to digest! %s \n" : "%s \n", err); goto done; }
+    memset(&spec, 0, sizeof(spec));
+    spec.bucket_samples = bucket; spec.d_out = r.d_extra;
+    if ((ret = LINNEAmd_DigestWindowsDevice(r.ctx, &r.w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to digest! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * nb : 1)) || (nb && hipMemcpy(tab, r.d_extra, sizeof(*tab) * nb, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
     /* (a stream of no samples has the empty string's digest) */
     if (nb == 0) printf("crc32 %08x bytes %llu \n", 0u, 0ull);
     for (k = 0; k < nb; k++) printf("crc32 %08x bytes %llu \n", tab[k].crc32, (unsigned long long)tab[k].num_bytes);
     rc = 0;
 done:
-    if (index) LINNEAmd_StreamIndexDestroy(index);
-    if (d_out) (void)hipFree(d_out);
-    if (d_stream) (void)hipFree(d_stream);
-    if (ctx) LINNEAmd_ContextDestroy(ctx);
+    resident_close(&r);
     free(tab); free(buf);
     return rc;
 }
