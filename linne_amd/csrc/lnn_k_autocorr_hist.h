@@ -9,7 +9,7 @@
  * The block turns the trial's input into the PADDED WINDOWED STREAM of k_autocorr2 -- each unit's n windowed samples followed
  * by `pad` zeros (pad = PT: the longest lag) -- 16 positions at a time, transposed into an LDS ring of D + 16 positions x 64
  * rows (coalesced loads, the window applied once for all waves; the first 16 positions are mirrored behind the ring so that a
- * 16-position read never wraps).  Wave w owns LPW lags from J0 = LPW * w on: per position it reads the stream value v[m] and the
+ * 16-position read never wraps).  Wave w owns LPW lags from J0 = LPW * w on (the last wave: the NLAST that are left): per position it reads the stream value v[m] and the
  * DELAYED value v[m - J0] (one ds_read each), keeps the last 16 delayed values in a register ring, and adds ring[m-J0-j] * v[m]
  * to lag J0+j -- the reference's products in the reference's order; the pairs that reach across a unit's end meet the zeros
  * (+0.0 added).  No per-wave window generator, no stream bookkeeping in the inner loop: 2 LPW multiply/adds and 2 LDS reads per
@@ -24,24 +24,35 @@ __device__ __forceinline__ void lds_dma16(const void *g, void *lds_wave_base)
     uint32_t keep;                                                  /* M0 is the compiler's: handed back as it was (the s_nop: a scalar write of M0 needs a wait state before an LDS-DMA load reads it, and nothing inserts it inside an asm) */
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "s"(base), "v"(g) : "memory");
 }
+/* s_waitcnt vmcnt(0) that takes a wave's N lag accumulators as operands (commit(), below, says why); one operand list per lag count
+ * a wave role has: 11 and 9 (full waves), 8 and 2 (the last wave of order 128 and of order 64) */
+#define HIST_ACC(i_) "+v"(r[i_])
 template <int N> __device__ __forceinline__ void hist_wait_loads(double (&r)[N])
 {
-    static_assert(N == 9 || N == 11, "one operand list per lag count");
-    if constexpr (N == 9)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]) : : "memory");
+    static_assert(N == 2 || N == 8 || N == 9 || N == 11, "one operand list per lag count");
+    if constexpr (N == 2)
+        asm volatile("s_waitcnt vmcnt(0)" : HIST_ACC(0), HIST_ACC(1) : : "memory");
+    else if constexpr (N == 8)
+        asm volatile("s_waitcnt vmcnt(0)" : HIST_ACC(0), HIST_ACC(1), HIST_ACC(2), HIST_ACC(3), HIST_ACC(4), HIST_ACC(5), HIST_ACC(6), HIST_ACC(7) : : "memory");
+    else if constexpr (N == 9)
+        asm volatile("s_waitcnt vmcnt(0)" : HIST_ACC(0), HIST_ACC(1), HIST_ACC(2), HIST_ACC(3), HIST_ACC(4), HIST_ACC(5), HIST_ACC(6), HIST_ACC(7), HIST_ACC(8) : : "memory");
     else
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]), "+v"(r[10]) : : "memory");
+        asm volatile("s_waitcnt vmcnt(0)" : HIST_ACC(0), HIST_ACC(1), HIST_ACC(2), HIST_ACC(3), HIST_ACC(4), HIST_ACC(5), HIST_ACC(6), HIST_ACC(7), HIST_ACC(8), HIST_ACC(9), HIST_ACC(10) : : "memory");
 }
-/* lags per wave (measured): order 128 -- 11 (12 waves, one block per CU); order 64 -- 9 (8 waves, two blocks per CU) */
+#undef HIST_ACC
+/* lags per full wave (measured): order 128 -- 11 (12 waves, one block per CU); order 64 -- 9 (8 waves, two blocks per CU).  The last
+ * wave has what is left of the order's PT + 1 lags, 8 and 2, and runs a tile loop of its own with that many chains: no wave computes a
+ * lag it does not store. */
 #define HIST_LPW(PT_) ((PT_) >= 128 ? 11 : 9)
 #define HIST_TILE(PT_) 16                                    /* positions per tile (a multiple of 16; 32 was measured: far slower for order 128) */
 #define HIST_WAVES(PT_) (((PT_) + HIST_LPW(PT_)) / HIST_LPW(PT_))
 template <int P, int TT>
 __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 4) void k_autocorr_hist(Plan p, uint32_t layer, uint32_t cur)
 {
-    constexpr int PT = P >> TT, NLAG = PT + 1, LPW = HIST_LPW(PT), NW = HIST_WAVES(PT), T = HIST_TILE(PT), D = PT + 2 * T, NLD = T / 2, RPI = 128 / T;   /* RPI: rows per load instruction */
+    constexpr int PT = P >> TT, NLAG = PT + 1, LPW = HIST_LPW(PT), NW = HIST_WAVES(PT), NLAST = NLAG - LPW * (NW - 1), T = HIST_TILE(PT), D = PT + 2 * T, NLD = T / 2, RPI = 128 / T;   /* RPI: rows per load instruction */
     constexpr int NSLOT = (NLD + NW - 1) / NW;                /* tile load instructions per wave */
     static_assert(LPW <= 16, "a wave's lags come from a 16-deep register ring");
+    static_assert(NLAST >= 1 && NLAST <= LPW, "the last wave takes the lags the full waves leave");
     static_assert(PT % T == 0 && D % T == 0, "tiles must not straddle a unit's end or the ring's end");
     __shared__ __attribute__((aligned(16))) double ring_lds[D + T][65];
     __shared__ __attribute__((aligned(16))) lnn_d2 stage[NLD][64];      /* the tile on its way from memory: load instruction k's 64 x 16 bytes, as the lanes asked for them */
@@ -60,7 +71,7 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
     const uint32_t na = (uint32_t)__builtin_amdgcn_readfirstlane((int)c0.na);
     const uint32_t n = na >> TT, upl = n + (uint32_t)PT, units = 1u << TT, total = units * upl, ntiles = total / T;
     const double *wt = p.wtab + (uint32_t)__builtin_amdgcn_readfirstlane((int)c0.wt_off[layer][TT]);
-    const uint32_t J0 = wave * (uint32_t)LPW, JN = (J0 + (uint32_t)LPW <= (uint32_t)NLAG) ? (uint32_t)LPW : (uint32_t)NLAG - J0;
+    const uint32_t J0 = wave * (uint32_t)LPW;
     double *out = p.acorr + ((size_t)myrow * LNN_MAXT + TT) * LNN_ACW + J0;
     /* zero the ring: the stream before position 0 */
     for (uint32_t i = threadIdx.x; i < (uint32_t)(D + T) * 65u; i += blockDim.x) (&ring_lds[0][0])[i] = 0.0;
@@ -73,11 +84,6 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
         uint32_t lr = row0 + (uint32_t)RPI * (k < (uint32_t)NLD ? k : 0u) + lrow; if (lr >= nrows) lr = nrows - 1;
         src[i] = p.sig + ((size_t)lr * 2 + cur) * p.S + lsmp;
     }
-    double r[LPW], q[LPW], hist[16];
-#pragma unroll
-    for (int j = 0; j < LPW; j++) { r[j] = 0.0; q[j] = 0.0; }
-#pragma unroll
-    for (int j = 0; j < 16; j++) hist[j] = 0.0;
     /* the tile being fetched: place in the padded stream */
     uint32_t f_unit = 0, f_loc = 0;                          /* unit and place inside the padded unit of the NEXT tile to fetch */
     uint32_t p_loc = 0;                                       /* place of the tile that is on its way */
@@ -104,6 +110,14 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
         const uint32_t h = (loc < (n >> 1)) ? loc : (n - 1u - loc);
         return wdiv * (double)h * (double)(n - 1u - h);
     };
+    /* the rest of the kernel for a wave of NJ lags (block-uniform per wave: every wave meets the same barriers in either instance) */
+    auto lags = [&](auto nj) __attribute__((always_inline)) {
+    constexpr int NJ = decltype(nj)::value;
+    double r[NJ], q[NJ], hist[16];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) { r[j] = 0.0; q[j] = 0.0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) hist[j] = 0.0;
     auto commit = [&](uint32_t slot0) {                       /* slot0: ring slot of the tile's first position (multiple of T) */
         /* the tile has landed in `stage` (what this wave asked for: each lane reads its own 16 bytes back).  The wait takes the lags'
          * accumulators as operands: nothing of their arithmetic touches memory, and without a data dependence the compiler moves the
@@ -151,11 +165,11 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
 #pragma unroll
             for (int i = 0; i < 4; i++) {
 #pragma unroll
-                for (int j = 0; j < LPW; j++) r[j] += q[j];                                /* adds of the previous position's products */
+                for (int j = 0; j < NJ; j++) r[j] += q[j];                                 /* adds of the previous position's products */
                 hist[(4 * g + i) % 16] = dv[i];
                 const double v = cv[i];
 #pragma unroll
-                for (int j = 0; j < LPW; j++) q[j] = hist[((4 * g + i - j) % 16 + 16) % 16] * v;   /* (the last wave's lags beyond the order: computed, not stored) */
+                for (int j = 0; j < NJ; j++) q[j] = hist[((4 * g + i - j) % 16 + 16) % 16] * v;
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) { cv[i] = ncv[i]; dv[i] = ndv[i]; }
@@ -163,17 +177,20 @@ __global__ __launch_bounds__(64 * HIST_WAVES(P >> TT), ((P >> TT) >= 128) ? 3 : 
         a_loc += T;
         if (a_loc == upl) {                                   /* the unit and its zeros are through: store its lags */
 #pragma unroll
-            for (int j = 0; j < LPW; j++) { r[j] += q[j]; q[j] = 0.0; }
+            for (int j = 0; j < NJ; j++) { r[j] += q[j]; q[j] = 0.0; }
             if (store) {
                 double *o = out + (size_t)a_unit * NLAG;
 #pragma unroll
-                for (int j = 0; j < LPW; j++) if ((uint32_t)j < JN) o[j] = r[j];
+                for (int j = 0; j < NJ; j++) o[j] = r[j];
             }
 #pragma unroll
-            for (int j = 0; j < LPW; j++) r[j] = 0.0;
+            for (int j = 0; j < NJ; j++) r[j] = 0.0;
             a_loc = 0; a_unit++;
         }
     }
+    };
+    if (wave == (uint32_t)(NW - 1)) lags(std::integral_constant<int, NLAST>{});
+    else lags(std::integral_constant<int, LPW>{});
 }
 
 /* k_autocorr_sub<P>: the trials of orders 32 .. 1 of a layer of order P >= 64, for the frames hist_takes: autocorr_rows
