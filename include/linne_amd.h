@@ -388,6 +388,17 @@ enum LINNEAmdDigestTimingKind {
     LINNE_AMD_DIGEST_T_PRESET = 84,         /* the call's accumulators zeroed and the tables of powers filled, once, in front of the first pass (k_wx_digest_preset) */
     LINNE_AMD_DIGEST_T_COMMIT = 85          /* the answers of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_digest_commit) */
 };
+/* finding quiet runs in windows (LINNEAmd_QuietWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of kind 86
+ * wherever that call has one of kind 59, and one launch each of kinds 87 to 91 per call that takes a pass) */
+enum LINNEAmdQuietTimingKind {
+    LINNE_AMD_QUIET_T_QUIET = 86,           /* a bit per sample frame of every window into its mask (k_wx_quiet) */
+    LINNE_AMD_QUIET_T_PRESET = 87,          /* the call's masks zeroed, once, in front of the first pass (k_wx_quiet_preset) */
+    LINNE_AMD_QUIET_T_COUNT = 88,           /* behind the last pass: the runs of every chunk of every mask counted (k_wx_quiet_runs) */
+    LINNE_AMD_QUIET_T_SCAN = 89,            /* ... the counts' prefix sums (k_sx_scan) */
+    LINNE_AMD_QUIET_T_STARTS = 90,          /* ... the runs' first samples into the tables of the windows that did not fail (k_wx_quiet_runs) */
+    LINNE_AMD_QUIET_T_ENDS = 91             /* ... and their lengths (k_wx_quiet_runs) */
+};
+#define LINNE_AMD_QUIET_EXTRA_LAUNCHES 5    /* kinds 87 to 91, one launch each */
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -726,6 +737,52 @@ struct LINNEAmdDigestSpec {
 };
 int LINNEAmd_DigestWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdDigestSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- finding the quiet runs of sample windows of resident streams: where is the silence?  No PCM written ----
+ * LINNEAmd_QuietWindowsDevice takes the windows of LINNEAmd_DecodeWindowsDevice and, instead of writing every window's samples,
+ * lists the window's quiet runs: the only output in device memory is a table of struct LINNEAmdRun per window.  The samples are
+ * exactly those LINNEAmd_DecodeStreamDevice writes for the range -- int32, L/R after MS, nothing saturated, the zeros of SILENT blocks
+ * and of the range behind the stream's last block included.  A sample frame is quiet when |v| <= specs[i].threshold in EVERY
+ * channel; |v| is taken in 64 bits, so INT32_MIN has magnitude 2^31 and is quiet only for threshold >= 2^31.  A run is a maximal
+ * stretch of consecutive quiet frames inside the window: it ends at the window's ends, whatever lies outside.  The runs of at least
+ * max(min_samples, 1) frames are reported in ascending order: answers[i].num_runs counts them and quiet_samples adds their lengths,
+ * whether or not they fitted, and the first min(num_runs, capacity) of them are written to d_out; no byte of d_out behind those
+ * records is touched.  num_runs > capacity is not an error: count first (capacity 0, d_out NULL), then call again with room.
+ * lead_samples and trail_samples are the quiet frames at the window's start and at its end, whatever min_samples is; both are the
+ * window's length when no frame of it is loud.  A window of no samples is OK with all four answers 0.
+ * Everything LINNEAmd_MeasureWindowsDevice says about results holds unchanged: the windows' d_pcm and pcm_stride are ignored;
+ * every window's `result` is what LINNEAmd_DecodeWindowsDevice gives it, and for that window alone INVALID_ARGUMENT when d_out is
+ * NULL with capacity > 0 or not 8-byte aligned.  A failing window's d_out and answers[i] are never written, and a failing window
+ * does not disturb the others.  The outputs of different windows must not overlap; the streams are only read.  Shape groups, passes,
+ * group_frames, scratch and whole-call failures are the decode call's, with "window <i>: " and the single call's text in
+ * GetLastError.  A pass has the decode call's launches with kind 86 in place of kind 59; a call that takes at least one pass adds
+ * exactly LINNE_AMD_QUIET_EXTRA_LAUNCHES = 5 launches, whatever num_windows is: kind 87 in front of the first pass (the masks
+ * zeroed) and kinds 88, 89, 90 and 91 behind the last (the runs counted per chunk, the counts' prefix sums, the runs' first samples
+ * and their lengths written for the windows whose Rice check passed); a window that spans passes collects its mask over them.
+ * Copies (one upload, one fetch) and host synchronisations (one) do not depend on num_windows.  The context's scratch holds one bit
+ * per sample frame of every window, rounded up to 64 per window, and 24 bytes per 16384 frames (a commit workgroup's chunk) for the
+ * counts and their prefix sums: 1/32 of ONE channel's int32 PCM, and never a word per sample or per run.  A test of min_samples walks
+ * at most min_samples bits of its run in one lane, 64 at a time: a call with min_samples in the millions on material that has such
+ * runs spends that walk's time in kinds 88, 90 and 91.
+ * num_windows == 0 is OK; a NULL ctx, or NULL windows, NULL specs or NULL answers with num_windows > 0, INVALID_ARGUMENT.  Enqueued
+ * on the context's stream and synchronous. */
+struct LINNEAmdRun {                    /* 16 bytes: one quiet run of one window */
+    uint64_t first_sample, num_samples; /* stream sample index; length */
+};
+struct LINNEAmdQuietSpec {
+    uint32_t threshold, reserved;       /* a sample frame is quiet when |v| <= threshold in EVERY channel */
+    uint64_t min_samples;               /* report runs of at least this many frames; 0 is taken as 1 */
+    struct LINNEAmdRun *d_out;          /* device, 8-byte aligned; may be NULL when capacity == 0 */
+    uint64_t capacity;                  /* records d_out has room for */
+};
+struct LINNEAmdQuiet {                  /* host, out, per window */
+    uint64_t num_runs;                  /* runs found, whether or not they fitted */
+    uint64_t quiet_samples;             /* the sum of their lengths */
+    uint64_t lead_samples, trail_samples;   /* quiet frames at the window's start / end, whatever min_samples is; both n when no frame is loud */
+};
+int LINNEAmd_QuietWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdQuietSpec *specs /* [num_windows] */, struct LINNEAmdQuiet *answers /* [num_windows], out */,
+        uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

@@ -59,6 +59,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_CompareWindowsDevice",
     "LINNEAmd_MeasureWindowsDevice",
     "LINNEAmd_DigestWindowsDevice",
+    "LINNEAmd_QuietWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -186,6 +187,63 @@ class DigestTable:
         return a.view(DIGEST_DTYPE).reshape(a.shape[0])
 
 
+class Run(C.Structure):
+    """struct LINNEAmdRun (include/linne_amd.h): one quiet run of one window"""
+    _fields_ = [("first_sample", C.c_uint64), ("num_samples", C.c_uint64)]
+
+
+class QuietSpec(C.Structure):
+    """struct LINNEAmdQuietSpec (include/linne_amd.h)"""
+    _fields_ = [("threshold", C.c_uint32), ("reserved", C.c_uint32), ("min_samples", C.c_uint64), ("d_out", C.c_void_p), ("capacity", C.c_uint64)]
+
+
+class Quiet(C.Structure):
+    """struct LINNEAmdQuiet (include/linne_amd.h): one window's answer on the host"""
+    _fields_ = [("num_runs", C.c_uint64), ("quiet_samples", C.c_uint64), ("lead_samples", C.c_uint64), ("trail_samples", C.c_uint64)]
+
+
+QUIET_DEFAULT_CAPACITY = 256   # quiet_windows(capacity=None): records per window in the first call; windows with more runs get a second one
+
+
+class QuietRuns:
+    """one window's answer of quiet_windows: `runs`, an int64 CUDA tensor (k, 2) of (first sample in the stream, length), ascending,
+    k = min(num_runs, the capacity given); num_runs and quiet_samples describe all runs of at least min_samples frames whether or not
+    they fitted; lead_samples and trail_samples are the quiet frames at the window's ends whatever min_samples is"""
+
+    def __init__(self, runs, answer, threshold, min_samples):
+        self.runs, self.threshold, self.min_samples = runs, threshold, min_samples
+        self.num_runs, self.quiet_samples = int(answer.num_runs), int(answer.quiet_samples)
+        self.lead_samples, self.trail_samples = int(answer.lead_samples), int(answer.trail_samples)
+
+    def cpu(self):
+        """-> the runs as a list of (first, n) of Python integers"""
+        return [(int(a), int(b)) for a, b in self.runs.cpu().numpy()]
+
+
+def sound_segments(num_samples, runs, pad=0):
+    """the complement of quiet runs inside [0, num_samples): runs a sequence of (first, n) (a QuietRuns' .cpu(), or an array (k, 2)) ->
+    a list of (first, n) in ascending order, every segment widened by `pad` frames at both ends (not beyond [0, num_samples)) and
+    segments that then touch or overlap merged: what splice_streams takes as the cuts that keep the sound.  Pure host code"""
+    num_samples, pad = int(num_samples), int(pad)
+    assert pad >= 0, "pad is a number of frames >= 0"
+    quiet = sorted((max(int(a), 0), min(int(a) + int(n), num_samples)) for a, n in runs)
+    loud, at = [], 0
+    for a, b in quiet:
+        if a > at:
+            loud.append((at, a))
+        at = max(at, b)
+    if at < num_samples:
+        loud.append((at, num_samples))
+    out = []
+    for a, b in loud:
+        a, b = max(a - pad, 0), min(b + pad, num_samples)
+        if out and a <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], b))
+        else:
+            out.append((a, b))
+    return [(a, b - a) for a, b in out]
+
+
 def _load():
     # torch bundles its own HIP runtime (same soname as /opt/rocm's).  Importing torch FIRST makes
     # liblinne_amd.so bind to that already-loaded runtime, so both share one HIP context: torch tensors can
@@ -266,6 +324,7 @@ def _load():
     L.LINNEAmd_CompareWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(PcmLayout), C.POINTER(Diff), C.c_uint32, C.c_uint32]
     L.LINNEAmd_MeasureWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MeasureSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_DigestWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(DigestSpec), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_QuietWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(QuietSpec), C.POINTER(Quiet), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -795,6 +854,64 @@ class Context:
         the WAV file the decoder writes for it.  streams as index_streams takes them; bucket_samples as digest_windows takes it.
         Raises LinneAmdError when a stream does not index or decode"""
         return self._over_whole_streams(streams, self.digest_windows, bucket_samples=bucket_samples, group_frames=group_frames)
+
+    def quiet_windows(self, windows, threshold, min_samples=1, capacity=None, group_frames=0, return_codes=False):
+        """where is the silence?  The quiet runs of many sample windows of resident .lnn streams in one call, no PCM written
+        (include/linne_amd.h LINNEAmd_QuietWindowsDevice).  windows: a sequence of (stream, index, first_sample, num_samples) as
+        decode_windows takes them; threshold: a frame is quiet when |v| <= threshold in every channel; min_samples: runs of at least
+        so many frames are reported (0 is taken as 1); both one value or one per window.  capacity: the records per window (one value
+        or one per window) -- runs beyond it are counted but not written; None: QUIET_DEFAULT_CAPACITY records, and one more call, for
+        the windows that had more runs, with exactly their num_runs, so that every run is returned.  -> a list of QuietRuns, one per
+        window.  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with return_codes ->
+        (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
+        import torch
+        W = len(windows)
+        arr, keep, ranges = self._windows_array(windows)
+
+        def per_window(v, what):
+            vs = [int(v)] * W if isinstance(v, (int, np.integer)) else [int(e) for e in v]
+            assert len(vs) == W and all(e >= 0 for e in vs), f"{what} is one value >= 0, or one per window"
+            return vs
+        thr, mins = per_window(threshold, "threshold"), per_window(min_samples, "min_samples")
+        caps = per_window(QUIET_DEFAULT_CAPACITY if capacity is None else capacity, "capacity")
+        assert all(t < (1 << 32) for t in thr), "threshold is below 2^32"
+
+        def call(which, caps):
+            """the call over windows[which] -> (ret, the Window array, tables, answers)"""
+            w = (Window * max(len(which), 1))()
+            specs, answers = (QuietSpec * max(len(which), 1))(), (Quiet * max(len(which), 1))()
+            flat = torch.empty((max(sum(caps), 1), 2), dtype=torch.int64, device=f"cuda:{self.device}")
+            at = 0
+            for j, i in enumerate(which):
+                for name, _ in Window._fields_:
+                    setattr(w[j], name, getattr(arr[i], name))
+                specs[j].threshold, specs[j].min_samples, specs[j].capacity = thr[i], mins[i], caps[j]
+                specs[j].d_out = flat.data_ptr() + 16 * at if caps[j] else None
+                at += caps[j]
+            self._fence()
+            ret = lib.LINNEAmd_QuietWindowsDevice(self.h, w, specs, answers, len(which), int(group_frames))
+            tables, at = [], 0
+            for j in range(len(which)):
+                tables.append(flat[at:at + min(caps[j], int(answers[j].num_runs) if w[j].result == 0 else 0)])
+                at += caps[j]
+            return ret, w, tables, answers
+        ret, w, tables, answers = call(list(range(W)), caps)
+        codes = self._windows_codes(ret, w, W, "QuietWindowsDevice", return_codes)
+        if capacity is None:
+            more = [i for i in range(W) if codes[i] == 0 and int(answers[i].num_runs) > caps[i]]
+            if more:
+                ret2, w2, tables2, answers2 = call(more, [int(answers[i].num_runs) for i in more])
+                self._windows_codes(ret2, w2, len(more), "QuietWindowsDevice", False)
+                for j, i in enumerate(more):
+                    tables[i] = tables2[j]
+        out = [QuietRuns(tables[i], answers[i], thr[i], mins[i]) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def quiet_streams(self, streams, threshold, min_samples=1, capacity=None, group_frames=0):
+        """the quiet runs of whole resident .lnn streams: one index_streams call and quiet_windows over the whole streams -> a list
+        of QuietRuns.  streams as index_streams takes them; the rest as quiet_windows takes it.  sound_segments turns a stream's
+        runs into the cuts splice_streams takes.  Raises LinneAmdError when a stream does not index or decode"""
+        return self._over_whole_streams(streams, self.quiet_windows, threshold=threshold, min_samples=min_samples, capacity=capacity, group_frames=group_frames)
 
     def same_audio(self, stream_a, stream_b, bucket_samples=0):
         """do two resident .lnn streams hold the same samples, whatever their presets, block sizes and mid/side choices?  ->

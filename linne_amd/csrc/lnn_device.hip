@@ -52,6 +52,7 @@
 #include "lnn_k_compare.h"
 #include "lnn_k_measure.h"
 #include "lnn_k_digest.h"
+#include "lnn_k_quiet.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -66,6 +67,7 @@ static_assert(LINNE_AMD_REPAIR_T_SOUND == 73 && LINNE_AMD_REPAIR_T_RUNS == 78, "
 static_assert(LINNE_AMD_COMPARE_T_COMPARE == 79, "the compare call's timing kind is 79");
 static_assert(LINNE_AMD_MEASURE_T_MEASURE == 80 && LINNE_AMD_MEASURE_T_COMMIT == 82, "the measure call's timing kinds are 80 to 82");
 static_assert(LINNE_AMD_DIGEST_T_DIGEST == 83 && LINNE_AMD_DIGEST_T_COMMIT == 85, "the digest call's timing kinds are 83 to 85");
+static_assert(LINNE_AMD_QUIET_T_QUIET == 86 && LINNE_AMD_QUIET_T_ENDS == 91 && LINNE_AMD_QUIET_EXTRA_LAUNCHES == 5, "the quiet call's timing kinds are 86 to 91: the pass kind and five launches per call");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2237,9 +2239,9 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
 struct WxCall;
 /* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
  * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
-struct WxLaunch { const WxBucket *side; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout; };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The four calls are the
- * four constant instances below; a launch that a consumer does not have is NULL */
+struct WxLaunch { const WxBucket *side; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The five calls are the
+ * five constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2258,8 +2260,8 @@ struct WxCall {
     const WxConsumer *use;
     bool single;                        /* the call is LINNEAmd_DecodeStreamDevice, which its texts then name */
     struct LINNEAmdWindow *win; uint32_t W, group_frames;
-    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure and digest their specs */
-    void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff */
+    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest and quiet their specs */
+    void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
@@ -2371,10 +2373,63 @@ static int wx_digest_commit(LINNEAmdContext *ctx, const WxLaunch &l)
     return LNN_OK;
 }
 
+
+/* ---- quiet: a bit per frame in the scratch, runs extracted behind the last pass (lnn_k_quiet.h); four 64-bit words per window come
+ * back: the loud extent (~0, 0), the runs found and the sum of their lengths ---- */
+static int wx_quiet_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdQuietSpec &qs = ((const struct LINNEAmdQuietSpec *)c.specs)[i];
+    if (!qs.d_out && qs.capacity) { snprintf(err, cap, "%s: null d_out with capacity %llu", c.use->name, (unsigned long long)qs.capacity); return LNN_INVALID_ARGUMENT; }
+    if ((uint64_t)(uintptr_t)qs.d_out & 7u) { snprintf(err, cap, "%s: d_out is not 8-byte aligned", c.use->name); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static void wx_quiet_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdQuietSpec &qs = ((const struct LINNEAmdQuietSpec *)c.specs)[i];
+    r.bucket_out = qs.d_out; r.quiet_min = qs.min_samples ? qs.min_samples : 1u; r.quiet_capacity = qs.capacity; r.quiet_threshold = qs.threshold;
+}
+static void wx_quiet_back_preset(uint32_t *back, uint32_t W)
+{
+    uint64_t *d = (uint64_t *)back;
+    for (uint32_t i = 0; i < W; i++) { d[4u * i + WXQ_LOUD_LO] = ~(uint64_t)0; d[4u * i + WXQ_LOUD_HI] = 0u; d[4u * i + WXQ_RUNS] = 0u; d[4u * i + WXQ_QUIET] = 0u; }
+}
+static int wx_quiet_preset(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_PRESET, k_wx_quiet_preset, wx_grid(l.nmask), dim3(WXB_THREADS), 0, ctx->stream, (unsigned long long *)l.acc, l.nmask); return LNN_OK; }
+static int wx_quiet_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxQuietArgs qa; qa.p = la; qa.qwin = l.side; qa.mask = (unsigned long long *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_QUIET, k_wx_quiet, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, qa);
+    return LNN_OK;
+}
+/* behind the masks (lnn_windows_plan.h wxq_chunk_units): the prefix sums, then the counts */
+static int wx_quiet_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxQuietCommitArgs a;
+    uint64_t *ofs = (uint64_t *)l.acc + l.nmask;
+    a.qwin = l.side; a.wins = l.wins; a.nwin = l.nwin; a.mask = (const unsigned long long *)l.acc; a.fail = l.fail; a.nchunks = l.nout;
+    a.counts = (uint32_t *)(ofs + 2u * l.nout + 1u); a.ofs = ofs; a.back = (unsigned long long *)l.back;
+    const dim3 grid((uint32_t)(l.nout < 0x7FFFFFFFull ? l.nout : 0x7FFFFFFFull));
+    SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_COUNT, k_wx_quiet_runs<WXQ_COUNT>, grid, dim3(WXB_THREADS), 0, ctx->stream, a);
+    SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)a.counts, 2u * l.nout, ofs);
+    SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_STARTS, k_wx_quiet_runs<WXQ_STARTS>, grid, dim3(WXB_THREADS), 0, ctx->stream, a);
+    SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_ENDS, k_wx_quiet_runs<WXQ_ENDS>, grid, dim3(WXB_THREADS), 0, ctx->stream, a);
+    return LNN_OK;
+}
+/* (a failing window's answers[i] stays as the caller left it; an OK window of no samples took no pass: all four are 0) */
+static void wx_quiet_read_back(const WxCall &c, uint32_t i, const uint32_t *words)
+{
+    struct LINNEAmdQuiet &q = ((struct LINNEAmdQuiet *)c.answers)[i];
+    if (!words) { q.num_runs = q.quiet_samples = q.lead_samples = q.trail_samples = 0u; return; }
+    const uint64_t *d = (const uint64_t *)(words + 2u * (uint64_t)c.W) + 4u * (uint64_t)i, n = c.win[i].num_samples;
+    const bool none_loud = d[WXQ_LOUD_HI] == 0u;
+    q.num_runs = d[WXQ_RUNS]; q.quiet_samples = d[WXQ_QUIET];
+    q.lead_samples = none_loud ? n : d[WXQ_LOUD_LO]; q.trail_samples = none_loud ? n : n - d[WXQ_LOUD_HI];
+}
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL };
 static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL };
+static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2450,8 +2505,8 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
     WxLaunch ln;
-    ln.side = (const WxBucket *)(wd + ls.o_side); ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
-    ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout;
+    ln.side = (const WxBucket *)(wd + ls.o_side); ln.wins = d_win; ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
+    ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout; ln.nmask = pl.nmask;
     if (!ctx->outer_keep) ctx->nspans = 0;
     if (ctx->timing && !ctx->outer_keep) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(wd, hs_, ls.bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -2562,6 +2617,13 @@ extern "C" int LINNEAmd_DigestWindowsDevice(struct LINNEAmdContext *ctx, struct 
         uint32_t num_windows, uint32_t group_frames)
 {
     return wx_entry(ctx, wx_call(&WX_DIGEST, windows, num_windows, group_frames, specs, NULL), windows && specs);
+}
+
+/* the windows' quiet runs listed in a table per window instead of their samples written */
+extern "C" int LINNEAmd_QuietWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdQuietSpec *specs,
+        struct LINNEAmdQuiet *answers, uint32_t num_windows, uint32_t group_frames)
+{
+    return wx_entry(ctx, wx_call(&WX_QUIET, windows, num_windows, group_frames, specs, answers), windows && specs && answers);
 }
 
 /* one window of one stream */

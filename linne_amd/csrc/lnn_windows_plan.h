@@ -1,5 +1,5 @@
-/* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure
- * and digest; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+/* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
+ * digest and find quiet runs; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -37,6 +37,8 @@
 #define WXB_SEGMENTS 4u                 /* up to this many buckets in a piece are reduced by the whole workgroup, one after the other */
 #define WXB_MAXSLOTS 64u
 #define WXB_THREADS 256u
+/* the bitmask consumer (lnn_k_quiet.h): a bit per sample frame in 64-bit words; a commit workgroup takes a chunk of this many words */
+#define WXQ_CHUNK_WORDS 256u
 
 /* one block of one window (64 bytes) */
 struct WxBlock {
@@ -57,22 +59,27 @@ struct WxWindow {
     uint64_t sstride;                   /* (int32 planar: fmt S32, sstride 1) */
 };
 /* one window's buckets (64 bytes), at its WxWindow's index: what a bucketed consumer keeps per window.  A consumer leaves zero what it
- * does not use */
+ * does not use.  The bitmask consumer has no buckets but keeps the same record: min_run, capacity and threshold are its spec, abase the
+ * window's first mask word and obase the number of commit chunks of the windows before it */
 struct WxBucket {
     void *out;                          /* the caller's table */
-    uint64_t b, nb;                     /* bucket length (the window's length for "one bucket"), buckets */
+    union { uint64_t b, min_run; };     /* bucket length (the window's length for "one bucket"); bitmask: the shortest run reported, >= 1 */
+    union { uint64_t nb, capacity; };   /* buckets; bitmask: the records the caller's table has room for */
     uint64_t abase;                     /* its accumulators in the scratch, in the consumer's units */
     uint64_t obase;                     /* the number of output records of the windows before it */
-    union { uint64_t cstride, n; };     /* per channel: the caller's channel stride; per frame: the window's samples */
-    uint32_t ns, fidx;                  /* slots (a power of two); its fail word */
+    union { uint64_t cstride, n; };     /* per channel: the caller's channel stride; per frame and bitmask: the window's samples */
+    union { uint32_t ns, threshold; };  /* slots (a power of two); bitmask: the largest quiet magnitude */
+    uint32_t fidx;                      /* its fail word */
     union { uint32_t C, F; };           /* per channel: channels; per frame: bytes per sample frame */
     uint32_t sstride;                   /* per frame: units from one slot to the next (per channel: C * nb, not kept) */
 };
 static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record and a bucket record are 64 bytes");
 
 /* how a consumer keeps buckets: not at all; an accumulator per (channel, bucket), a window's slots C * nb apart (measure); one per
- * bucket, a window's slots padded to whole 64-byte lines of 16 units (digest) */
-enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2 };
+ * bucket, a window's slots padded to whole 64-byte lines of 16 units (digest); a bit per sample frame, in whole 64-bit words per window
+ * (quiet: the units are those words, and the "output records" counted in obase and nout are the commit's chunks of WXQ_CHUNK_WORDS
+ * words, of which every window has whole ones) */
+enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2, WX_BITMASK = 3 };
 
 /* what the plan reads of a block index */
 struct WxIndexView {
@@ -87,6 +94,7 @@ struct WxRange {
     uint64_t lo, n, r1;                 /* [lo, lo + n); the last block it overlaps (nb: it reaches behind the last block) */
     void *out; uint64_t stride, sstride; uint32_t fmt;          /* its WxWindow's */
     uint64_t bucket_samples, bucket_cstride; void *bucket_out;  /* bucketed consumers: its spec */
+    uint64_t quiet_min, quiet_capacity; uint32_t quiet_threshold;       /* the bitmask consumer: its spec beside bucket_out (quiet_min >= 1) */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -98,6 +106,7 @@ struct WxPlanned {
     uint32_t nwin, nrec, ncrec;         /* records written (wx_plan_fill): nwin == nlive, nrec <= total_rec, ncrec <= total_crec */
     uint64_t scratch_bytes;             /* the largest pass's */
     uint64_t nacc, nout;                /* bucketed consumers: accumulator units, output records */
+    uint64_t nmask;                     /* the bitmask consumer: the mask words among nacc; behind them the commit's units per chunk (wxq_chunk_units) */
 };
 enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
 
@@ -114,6 +123,13 @@ static inline uint64_t wx_buckets(uint64_t n, uint64_t b) { return n == 0 ? 0u :
 /* A bucket of L samples takes L / 256 pieces, each one atomic per accumulator: from 8192 samples on they are spread over L / 4096
  * slots, WXB_MAXSLOTS at most */
 static inline uint32_t wx_slots(uint64_t b) { uint32_t ns = 1u; while (ns < WXB_MAXSLOTS && (b >> 12) >= 2u * ns) ns *= 2u; return ns; }
+
+/* the 64-bit words of a window's mask, and the chunks the commit cuts them into */
+static inline uint64_t wxq_words(uint64_t n) { return (n >> 6) + ((n & 63u) != 0); }
+static inline uint64_t wxq_chunks(uint64_t n) { return (wxq_words(n) + WXQ_CHUNK_WORDS - 1u) / WXQ_CHUNK_WORDS; }
+/* what the commit keeps for nchunks chunks, in 64-bit units behind the masks: the prefix sums of the chunks' counts of run starts and of
+ * run ends (2 * nchunks + 1 words), then the counts themselves (2 * nchunks 32-bit words) */
+static inline uint64_t wxq_chunk_units(uint64_t nchunks) { return 3u * nchunks + 1u; }
 
 /* the buffers of one pass in the context's scratch */
 struct WxScratch { uint64_t o_nsmp, o_bpos, o_bend, o_eb, o_prm, o_data, o_seg, bytes; };
@@ -152,7 +168,7 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
 {
     p.win.resize(W);
     p.ngroups = 0; p.nlive = p.total_rec = p.total_crec = 0;
-    p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = 0;
+    p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = p.nmask = 0;
     for (uint32_t i = 0; i < W; i++) {
         WxPlan &pl = p.win[i];
         pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
@@ -221,7 +237,13 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             WxWindow &ww = h_win[wi];
             ww.lo = w.lo; ww.hi = w.lo + w.n; ww.covered = x.covered; ww.out = w.out; ww.fidx = i;
             ww.fmt = w.fmt; ww.stride = w.stride; ww.sstride = w.sstride;
-            if (bucketing != WX_NO_BUCKETS) {
+            if (bucketing == WX_BITMASK) {
+                WxBucket &m = h_side[wi];
+                memset(&m, 0, sizeof(m));
+                m.out = w.bucket_out; m.min_run = w.quiet_min; m.capacity = w.quiet_capacity; m.threshold = w.quiet_threshold;
+                m.abase = p.nacc; m.obase = p.nout; m.n = w.n; m.fidx = i; m.C = shape.num_channels;
+                p.nacc += wxq_words(w.n); p.nout += wxq_chunks(w.n);
+            } else if (bucketing != WX_NO_BUCKETS) {
                 WxBucket &m = h_side[wi];
                 const uint64_t b = w.bucket_samples, C = shape.num_channels;
                 memset(&m, 0, sizeof(m));
@@ -258,6 +280,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
         }
         close(0);
     }
+    if (bucketing == WX_BITMASK) { p.nmask = p.nacc; p.nacc += wxq_chunk_units(p.nout); }
 }
 
 #endif

@@ -18,7 +18,11 @@
  *     stream on stdout, or with BUCKET one such line per BUCKET samples and channel;
  *   - -D / --digest [BUCKET] STREAM.lnn digests a stream on the device without decoding it into memory
  *     (LINNEAmd_DigestWindowsDevice): "crc32 %08x bytes %llu" on stdout, the CRC-32 and length of the `data` chunk of the WAV file
- *     that -d writes for the stream, or with BUCKET one such line per BUCKET samples.
+ *     that -d writes for the stream, or with BUCKET one such line per BUCKET samples;
+ *   - -S / --silence THRESHOLD[,MIN_SAMPLES] STREAM.lnn lists a stream's quiet runs on the device without decoding it into memory
+ *     (LINNEAmd_QuietWindowsDevice): the stretches of at least MIN_SAMPLES (default 1) sample frames whose every channel stays within
+ *     +-THRESHOLD, "run %llu: first %llu samples %llu seconds %.6f" per run on stdout, then "runs %llu quiet_samples %llu lead %llu
+ *     trail %llu"; exit 0 when the stream decoded.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -34,9 +38,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir;
+    const char *batch_dir, *silence_spec;
     const char *files[4096];
     int num_files;
 };
@@ -50,6 +54,7 @@ static void usage(const char *argv0)
     printf("       %s -C STREAM.lnn PCM.wav \n", argv0);
     printf("       %s -M [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -D [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
+    printf("       %s -S THRESHOLD[,MIN_SAMPLES] STREAM.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -58,6 +63,7 @@ static void usage(const char *argv0)
            "  -C, --compare                          Compare a .lnn stream with a WAV file's samples on the device (exit 0: identical) \n"
            "  -M, --measure                          Measure a .lnn stream on the device: min, max, sum, energy, mean, RMS per channel (and bucket) \n"
            "  -D, --digest                           Digest a .lnn stream on the device: the CRC-32 of the decoded PCM as -d writes it (per bucket) \n"
+           "  -S, --silence THRESHOLD[,MIN_SAMPLES]  List a .lnn stream's quiet runs on the device: every channel within +-THRESHOLD \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -109,7 +115,8 @@ static void parse(int argc, char **argv, struct options *o)
         } else if (take_value(argc, argv, &i, "-a", "--auxiliary-function-iteration", &v)) {
             char *end; o->af_iterations = strtol(v, &end, 10);
             if (*end != '\0' || o->af_iterations < 0 || o->af_iterations > 255) { fprintf(stderr, "%s: auxiliary function iteration count is out of range. \n", argv[0]); exit(1); }
-        } else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
+        } else if (take_value(argc, argv, &i, "-S", "--silence", &v)) { o->silence = 1; o->silence_spec = v; }
+        else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
         else { fprintf(stderr, "%s: too many files. \n", argv[0]); exit(1); }
@@ -141,7 +148,7 @@ static int read_file(const char *path, uint8_t **data, uint32_t *size)
     return 0;
 }
 
-/* A whole stream resident on the device 0, as -V, -C, -M and -D want it: a context, the stream's bytes, its block index, `extra` bytes
+/* A whole stream resident on the device 0, as -V, -C, -M, -D and -S want it: a context, the stream's bytes, its block index, `extra` bytes
  * beside it for what the call reads or writes, and the one window over all its samples */
 struct resident {
     struct LINNEAmdContext *ctx;
@@ -301,6 +308,45 @@ done:
     return rc;
 }
 
+/* -S: the stream goes to the device; LINNEAmd_StreamIndexCreate and LINNEAmd_QuietWindowsDevice over the whole stream answer, first
+ * with no table (the count), then with a table of exactly that many records, which comes back: a line per run and the summary */
+static int silence_one(const char *lnn_path, uint32_t threshold, uint64_t min_samples)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0;
+    struct resident r;
+    struct LINNEAmdQuietSpec spec;
+    struct LINNEAmdQuiet q;
+    struct LINNEAmdRun *tab = NULL;
+    void *d_tab = NULL;
+    struct LINNEHeader h;
+    char err[512];
+    uint64_t k;
+    int ret, stage, rc = 1;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    if ((stage = resident_open(&r, buf, size, h.num_samples, 0, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to find the silence! %s \n" : "%s \n", err); goto done; }
+    memset(&spec, 0, sizeof(spec)); memset(&q, 0, sizeof(q));
+    spec.threshold = threshold; spec.min_samples = min_samples;
+    if ((ret = LINNEAmd_QuietWindowsDevice(r.ctx, &r.w, &spec, &q, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to find the silence! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (q.num_runs) {
+        if (hipMalloc(&d_tab, sizeof(*tab) * q.num_runs) != hipSuccess) { fprintf(stderr, "Failed to allocate %llu records on the device. \n", (unsigned long long)q.num_runs); d_tab = NULL; goto done; }
+        spec.d_out = d_tab; spec.capacity = q.num_runs;
+        if ((ret = LINNEAmd_QuietWindowsDevice(r.ctx, &r.w, &spec, &q, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to find the silence! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+        if (q.num_runs != spec.capacity || !(tab = malloc(sizeof(*tab) * q.num_runs)) || hipMemcpy(tab, d_tab, sizeof(*tab) * q.num_runs, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    }
+    for (k = 0; k < q.num_runs; k++)
+        printf("run %llu: first %llu samples %llu seconds %.6f \n", (unsigned long long)k, (unsigned long long)tab[k].first_sample, (unsigned long long)tab[k].num_samples,
+                h.sampling_rate ? (double)tab[k].num_samples / (double)h.sampling_rate : 0.0);
+    printf("runs %llu quiet_samples %llu lead %llu trail %llu \n", (unsigned long long)q.num_runs, (unsigned long long)q.quiet_samples, (unsigned long long)q.lead_samples, (unsigned long long)q.trail_samples);
+    rc = 0;
+done:
+    if (d_tab) (void)hipFree(d_tab);
+    resident_close(&r);
+    free(tab); free(buf);
+    return rc;
+}
+
 static int encode_one(struct LINNEEncoder *enc, const struct options *o, const char *in_path, const char *out_path)
 {
     struct wav_pcm wav;
@@ -436,6 +482,19 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.silence) {
+        unsigned long long threshold, min_samples = 1;
+        char *end;
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.batch_dir || o.num_files != 1) { fprintf(stderr, "%s: -S takes THRESHOLD[,MIN_SAMPLES] and a stream file name and no other mode. \n", argv[0]); return 1; }
+        threshold = strtoull(o.silence_spec, &end, 10);
+        if (o.silence_spec[0] < '0' || o.silence_spec[0] > '9' || (*end != '\0' && *end != ',') || threshold > 0xFFFFFFFFull) { fprintf(stderr, "%s: silence threshold is out of range. \n", argv[0]); return 1; }
+        if (*end == ',') {
+            const char *m = end + 1;
+            min_samples = strtoull(m, &end, 10);
+            if (m[0] < '0' || m[0] > '9' || *end != '\0' || min_samples == 0) { fprintf(stderr, "%s: silence minimum sample count is out of range. \n", argv[0]); return 1; }
+        }
+        return silence_one(o.files[0], (uint32_t)threshold, min_samples);
+    }
     if (o.repair) {
         if (o.encode || o.decode || o.compare || o.measure || o.digest || o.verify || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -r takes an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return repair_one(o.files[0], o.files[1]);
