@@ -14,6 +14,7 @@ from linne_amd import PCM_F32, PCM_S16, PCM_S24, PCM_S32
 from signals import music
 from test_cli_cpu import CLI, wav_bytes
 from test_gpu_pcm_layouts import device_pcm
+from stream_refs import expected_compare as expected
 from test_gpu_stream_windows import blocks, crc16, crc_damaged, mixed_signal, to_device
 
 pytestmark = pytest.mark.gpu
@@ -42,16 +43,6 @@ def encoded(ctx, oracle, x, bits, preset, ms, name=""):
     t = Stream(ctx, oracle, oracle.encode_whole(x, bits, 44100, S, preset, ms), name)
     assert np.array_equal(t.full, x), name
     return t
-
-
-def expected(full, first, n, held):
-    """what the call must answer for window [first, first + n) of a stream that decodes to `full` against PCM that holds the values
-    `held` (C, n)"""
-    d = full[:, first:first + n].astype(np.int64) != np.asarray(held).astype(np.int64)
-    if not d.any():
-        return (0, 0, 0)
-    s = int(np.flatnonzero(d.any(axis=0))[0])
-    return (int(d.sum()), first + s, int(np.flatnonzero(d[:, s])[0]))
 
 
 def storage_bytes(t):

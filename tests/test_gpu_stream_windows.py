@@ -7,50 +7,13 @@ import numpy as np
 import pytest
 
 import linne_amd
-from signals import music
+from stream_refs import be, blocks, crc16, mixed_signal  # noqa: F401  (other test modules import them from here)
 
 pytestmark = pytest.mark.gpu
 
 OK, INVALID_ARGUMENT, CORRUPTION, NG = 0, 1, 6, 7
 COMPRESS, SILENT, RAW = 0, 1, 2
 NEW_KINDS = (56, 57, 58, 59)
-
-
-def be(b):
-    return int.from_bytes(bytes(b), "big")
-
-
-def blocks(stream):
-    """(offset, bytes, type, samples, first sample) of the blocks DecodeWhole walks in a well-formed stream"""
-    ns, off, prog, out = be(stream[14:18]), 30, 0, []
-    while prog < ns and off + 11 <= len(stream):
-        size, typ, n = be(stream[off + 2:off + 6]), stream[off + 8], be(stream[off + 9:off + 11])
-        out.append((off, size + 6, typ, n, prog))
-        prog += n
-        off += size + 6
-    return out
-
-
-def mixed_signal(nch, bits, ns, seed, block=4096):
-    """music with a silent stretch (SILENT blocks) and a stretch of full-scale noise (RAW blocks), each two blocks long"""
-    ns = max(ns, 7 * block)
-    x = music(nch, ns, bits, seed=seed).astype(np.int64)
-    x[:, block:3 * block] = 0
-    rng = np.random.default_rng(seed)
-    lim = 1 << (bits - 1)
-    x[:, 4 * block:6 * block] = rng.integers(-lim, lim, size=(nch, 2 * block))
-    return np.ascontiguousarray(x, dtype=np.int32)
-
-
-def crc16(data):
-    """CRC-16/ARC (reflected 0xA001, initial value 0, no final XOR): what a block's bytes 6..7 hold, big-endian, over everything
-    behind them (lnn_entropy.c crc_init / lnn_crc16)"""
-    crc = 0
-    for b in data:
-        crc ^= b
-        for _ in range(8):
-            crc = (crc >> 1) ^ 0xA001 if crc & 1 else crc >> 1
-    return crc
 
 
 def to_device(stream):

@@ -17,40 +17,11 @@ import pytest
 import linne_amd
 from signals import music
 from test_cli_cpu import CLI
-from test_gpu_stream_windows import mixed_signal
+from stream_refs import digest_table as table, expected_digest, mixed_signal, pcm_bytes  # noqa: F401  (the GPU tests import them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_CLI = os.path.join(ROOT, "oracle", "_ref", "linne_ref")
 OK, INVALID_ARGUMENT = 0, 1
-
-
-def pcm_bytes(full, bits, first, n):
-    """the byte string of samples [first, first + n) of a stream that decodes to `full` (C, N) with `bits` bits per sample:
-    interleaved, ceil(bits / 8) little-endian bytes of the two's-complement value, truncated, 8-bit samples offset by 128"""
-    w = (bits + 7) // 8
-    x = np.ascontiguousarray(np.asarray(full)[:, first:first + n].T).astype(np.int64)       # (n, C)
-    if w == 1:
-        x = x + 128
-    u = (x & 0xFFFFFFFF).astype("<u4")
-    return np.ascontiguousarray(u.view(np.uint8).reshape(x.shape[0], x.shape[1], 4)[:, :, :w]).tobytes()
-
-
-def expected_digest(full, bits, first, n, b):
-    """the table LINNEAmd_DigestWindowsDevice must write for window [first, first + n) of a stream that decodes to `full` (C, N),
-    with bucket length b (0: one bucket): [bucket] of (crc32, num_bytes)"""
-    step = b if b > 0 else max(n, 1)
-    out = []
-    for at in range(0, n, step):
-        s = pcm_bytes(full, bits, first + at, min(step, n - at))
-        out.append((zlib.crc32(s), len(s)))
-    return out
-
-
-def table(d):
-    """a DigestTable's (or a structured array's) records in expected_digest's form"""
-    a = d if isinstance(d, np.ndarray) else d.cpu()
-    assert not a["reserved"].any()
-    return [(int(r["crc32"]), int(r["num_bytes"])) for r in a]
 
 
 def wav_data(path):

@@ -14,7 +14,7 @@ import pytest
 import linne_amd
 from signals import music
 from test_cli_cpu import CLI
-from test_gpu_stream_windows import blocks, crc16, mixed_signal
+from stream_refs import blocks, crc16, expected_measure, measure_table as table, mixed_signal  # noqa: F401  (the GPU tests import them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, INVALID_ARGUMENT = 0, 1
@@ -23,27 +23,6 @@ S = 1024
 TAIL = 300
 CARRY_NS = (1 << 18) + 1024
 CARRY_PEAK = (1 << 23) - 1
-
-
-def expected_measure(full, first, n, b):
-    """the table LINNEAmd_MeasureWindowsDevice must write for window [first, first + n) of a stream that decodes to `full` (C, N),
-    with bucket length b (0: one bucket): [channel][bucket] of (min, max, sum, sumsq_lo, sumsq_hi), Python integers"""
-    out = []
-    step = b if b > 0 else max(n, 1)
-    for row in np.asarray(full)[:, first:first + n]:
-        recs = []
-        for at in range(0, n, step):
-            v = [int(e) for e in row[at:at + step]]
-            q = sum(e * e for e in v)
-            recs.append((min(v), max(v), sum(v), q & ((1 << 64) - 1), q >> 64))
-        out.append(recs)
-    return out
-
-
-def table(m):
-    """a Measurement's (or a structured array's) records in expected_measure's form"""
-    a = m if isinstance(m, np.ndarray) else m.cpu()
-    return [[(int(r["min"]), int(r["max"]), int(r["sum"]), int(r["sumsq_lo"]), int(r["sumsq_hi"])) for r in row] for row in a]
 
 
 def carry_signal():

@@ -15,7 +15,7 @@ import pytest
 import linne_amd
 from signals import music
 from test_cli_cpu import CLI
-from test_gpu_stream_windows import blocks, mixed_signal
+from stream_refs import blocks, expected_quiet, mixed_signal, quiet_answer as answer  # noqa: F401  (the GPU tests import them from here)
 from test_windows_plan_cpu import programs, run as plan_run, stream as plan_stream  # noqa: F401  (programs is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,25 +35,6 @@ PLANTS_END = [(S, S + 1), (NS - 10, NS)]
 LOUD = 7                                    # what a sample of channel 0 that is not planted is at least, in magnitude
 LONG_BLOCKS = 64
 MIXED_PLANTS = [(S - 40, 3 * S + 25), (4 * S - 30, 4 * S + 20), (6 * S - 15, 6 * S + 45)]
-
-
-def expected_quiet(full, first, n, threshold, min_samples):
-    """what LINNEAmd_QuietWindowsDevice must answer for window [first, first + n) of a stream that decodes to `full` (C, N):
-    (runs, num_runs, quiet_samples, lead_samples, trail_samples), runs the list of (first sample in the stream, length)"""
-    x = np.abs(np.asarray(full)[:, first:first + n].astype(np.int64))
-    q = (x <= int(threshold)).all(axis=0)
-    edge = np.diff(np.concatenate([[0], q.astype(np.int8), [0]]))
-    starts, ends = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)
-    m = max(int(min_samples), 1)
-    runs = [(first + int(a), int(b - a)) for a, b in zip(starts, ends) if b - a >= m]
-    loud = np.flatnonzero(~q)
-    lead, trail = (n, n) if loud.size == 0 else (int(loud[0]), n - 1 - int(loud[-1]))
-    return runs, len(runs), sum(r[1] for r in runs), lead, trail
-
-
-def answer(q):
-    """a QuietRuns in expected_quiet's form"""
-    return q.cpu(), q.num_runs, q.quiet_samples, q.lead_samples, q.trail_samples
 
 
 def made_loud(x):
