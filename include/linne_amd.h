@@ -399,6 +399,13 @@ enum LINNEAmdQuietTimingKind {
     LINNE_AMD_QUIET_T_ENDS = 91             /* ... and their lengths (k_wx_quiet_runs) */
 };
 #define LINNE_AMD_QUIET_EXTRA_LAUNCHES 5    /* kinds 87 to 91, one launch each */
+/* histogramming windows (LINNEAmd_HistogramWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of kind 92 wherever
+ * that call has one of kind 59, and one launch each of kinds 93 and 94 per call that takes a pass) */
+enum LINNEAmdHistogramTimingKind {
+    LINNE_AMD_HISTOGRAM_T_HISTOGRAM = 92,   /* counting every window's samples into its bins' accumulators (k_wx_histogram) */
+    LINNE_AMD_HISTOGRAM_T_PRESET = 93,      /* the call's accumulators zeroed, once, in front of the first pass (k_wx_histogram_preset) */
+    LINNE_AMD_HISTOGRAM_T_COMMIT = 94       /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_histogram_commit) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -783,6 +790,47 @@ struct LINNEAmdQuiet {                  /* host, out, per window */
 int LINNEAmd_QuietWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdQuietSpec *specs /* [num_windows] */, struct LINNEAmdQuiet *answers /* [num_windows], out */,
         uint32_t num_windows, uint32_t group_frames);
+
+/* ---- histogramming the sample levels of windows of resident streams: how are the magnitudes distributed?  No PCM written ----
+ * LINNEAmd_HistogramWindowsDevice takes the windows of LINNEAmd_DecodeWindowsDevice and, instead of writing every window's samples,
+ * counts them by level: the only output is a table of uint64_t counts per window, in device memory, num_bins of them per channel and
+ * bucket.  The samples are exactly those LINNEAmd_DecodeStreamDevice writes for the range -- int32, L/R after MS, nothing saturated,
+ * the zeros of SILENT blocks and of the range behind the stream's last block included.  The bin of a sample v: m = |v| >> shift, |v|
+ * taken in 64 bits (INT32_MIN has magnitude 2^31); x = m for LINNE_AMD_HIST_LINEAR, x = the bit length of m for LINNE_AMD_HIST_LOG2
+ * (0 for m == 0, otherwise floor(log2 m) + 1: INT32_MIN at shift 0 has x = 32); the bin is min(x, num_bins - 1), so the last bin
+ * catches everything above.  Every count is exact, and the bins of one (channel, bucket) add up to the bucket's samples.
+ * Buckets are LINNEAmd_MeasureWindowsDevice's: specs[i].bucket_samples = b > 0 gives nb = ceil(n / b) buckets, bucket k holding the
+ * window's samples [k * b, min((k + 1) * b, n)) (the last one may be short); b == 0 is one bucket of the whole window; a window of no
+ * samples has no buckets and nothing is written.  The windows of one call may differ in every field of their specs.
+ * Everything LINNEAmd_MeasureWindowsDevice says about results holds unchanged: the windows' d_pcm and pcm_stride are ignored;
+ * every window's `result` is what LINNEAmd_DecodeWindowsDevice gives it, and for that window alone INVALID_ARGUMENT when num_bins is 0
+ * or above LINNE_AMD_HIST_MAX_BINS, shift > 31, scale is neither of the two, reserved != 0, d_out is NULL (with n > 0) or not 8-byte
+ * aligned, channel_stride < nb, or nb > 2^32 - 1.  A failing window's d_out is never written, and a failing window does not disturb
+ * the others.  No byte outside d_out[(ch * channel_stride + k) * num_bins + j], ch < channels, k < nb, j < num_bins, is written; the
+ * outputs of different windows must not overlap; the streams are only read.  Shape groups, passes, group_frames, scratch and
+ * whole-call failures are the decode call's, with "window <i>: " and the single call's text in GetLastError.  A pass has the decode
+ * call's launches with kind 92 in place of kind 59; a call that takes at least one pass adds exactly two launches, whatever
+ * num_windows is: kind 93 in front of the first pass (the accumulators zeroed) and kind 94 behind the last (the slots added up and the
+ * tables of the windows whose Rice check passed written to their d_out); a window that spans passes collects its counts over them.
+ * Copies (one upload, one fetch) and host synchronisations (one) are the measure call's.  The accumulators live in the context's
+ * scratch: one 32-bit counter per (channel, bucket, bin) of every window -- a stream holds at most 2^32 - 1 samples, so none can
+ * overflow -- half the bytes of the table itself -- times up to 64 for windows whose buckets are 8192 samples or longer (a bucket
+ * of b samples has at most b / 4096 such copies: at most num_bins / 1024 bytes per sample and channel, a quarter of the int32 PCM).
+ * num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the
+ * context's stream and synchronous. */
+enum { LINNE_AMD_HIST_LINEAR = 0, LINNE_AMD_HIST_LOG2 = 1 };
+#define LINNE_AMD_HIST_MAX_BINS 1024
+struct LINNEAmdHistogramSpec {
+    uint64_t bucket_samples;            /* 0: the whole window is one bucket */
+    uint32_t num_bins;                  /* 1 .. LINNE_AMD_HIST_MAX_BINS */
+    uint32_t shift;                     /* 0 .. 31 */
+    uint32_t scale;                     /* LINNE_AMD_HIST_LINEAR / LINNE_AMD_HIST_LOG2 */
+    uint32_t reserved;                  /* 0 */
+    uint64_t *d_out;                    /* device, 8-byte aligned: bin j of channel ch, bucket k at d_out[(ch * channel_stride + k) * num_bins + j] */
+    uint64_t channel_stride;            /* in buckets, >= the window's bucket count */
+};
+int LINNEAmd_HistogramWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdHistogramSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

@@ -59,7 +59,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_CompareWindowsDevice",
     "LINNEAmd_MeasureWindowsDevice",
     "LINNEAmd_DigestWindowsDevice",
-    "LINNEAmd_QuietWindowsDevice",
+    "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -220,6 +220,43 @@ class QuietRuns:
         return [(int(a), int(b)) for a, b in self.runs.cpu().numpy()]
 
 
+class HistogramSpec(C.Structure):
+    """struct LINNEAmdHistogramSpec (include/linne_amd.h)"""
+    _fields_ = [("bucket_samples", C.c_uint64), ("num_bins", C.c_uint32), ("shift", C.c_uint32), ("scale", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_out", C.c_void_p), ("channel_stride", C.c_uint64)]
+
+
+HIST_LINEAR, HIST_LOG2, HIST_MAX_BINS = 0, 1, 1024
+
+
+class Histogram:
+    """one window's table of histogram_windows: `counts`, an int64 CUDA tensor (C, nb, num_bins) -- bin min(x, num_bins - 1) of
+    x = |v| >> shift, or with log2 the bit length of that, per channel and bucket -- and the spec it was made with"""
+
+    def __init__(self, counts, num_bins, shift, log2, bucket_samples):
+        self.counts, self.num_bins, self.shift, self.log2, self.bucket_samples = counts, num_bins, shift, log2, bucket_samples
+
+    def cpu(self):
+        """-> the counts as a numpy int64 array (C, nb, num_bins)"""
+        return np.ascontiguousarray(self.counts.cpu().numpy())
+
+
+def level_threshold(counts, fraction, shift=0):
+    """the level below which `fraction` of the samples lie, from a linear histogram of one channel or of the channels' sum: counts a
+    sequence of num_bins counts (a Histogram's .cpu()[ch, k], or a sum of such rows) made with this shift -> the smallest
+    T = ((j + 1) << shift) - 1 such that at least fraction of the samples have |v| <= T, or None when that bin is the last one, which
+    holds everything above and so has no upper edge.  T is what quiet_streams takes as its threshold.  Pure host code"""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    assert len(c) >= 1 and all(v >= 0 for v in c) and 0.0 <= float(fraction) <= 1.0 and 0 <= int(shift) <= 31
+    from fractions import Fraction
+    need, run = Fraction(fraction) * sum(c), 0                  # (exact: the comparison below is made in rationals, not in floating point)
+    for j, v in enumerate(c):
+        run += v
+        if run >= need:
+            break
+    return None if j == len(c) - 1 else ((j + 1) << int(shift)) - 1
+
+
 def sound_segments(num_samples, runs, pad=0):
     """the complement of quiet runs inside [0, num_samples): runs a sequence of (first, n) (a QuietRuns' .cpu(), or an array (k, 2)) ->
     a list of (first, n) in ascending order, every segment widened by `pad` frames at both ends (not beyond [0, num_samples)) and
@@ -325,6 +362,7 @@ def _load():
     L.LINNEAmd_MeasureWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MeasureSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_DigestWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(DigestSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_QuietWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(QuietSpec), C.POINTER(Quiet), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_HistogramWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(HistogramSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -681,15 +719,16 @@ class Context:
     def _bucket_tables(self, bucket_samples, ranges, words, per_channel):
         """the tables of a call that answers per bucket: bucket_samples one value or one per window -> (the bucket length per window;
         per window an int64 view (nb, words) -- per_channel: (C, nb, words) -- of one allocation; the views' device addresses; the
-        bucket counts nb)"""
+        bucket counts nb).  words: one value, or one per window"""
         import torch
         W = len(ranges)
         buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
         assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
+        words = [words] * W if isinstance(words, int) else list(words)
         counts = [0 if n <= 0 else (1 if b == 0 else -(-n // b)) for (_, _, n), b in zip(ranges, buckets)]
-        shapes = [((x.header["num_channels"],) if per_channel else ()) + (nb, words) for (x, _, _), nb in zip(ranges, counts)]
+        shapes = [((x.header["num_channels"],) if per_channel else ()) + (nb, wd) for (x, _, _), nb, wd in zip(ranges, counts, words)]
         sizes = [math.prod(shape) for shape in shapes]
-        flat = torch.empty(max(sum(sizes), words), dtype=torch.int64, device=f"cuda:{self.device}")
+        flat = torch.empty(max(sum(sizes), max(words, default=1)), dtype=torch.int64, device=f"cuda:{self.device}")
         views, addresses, at = [], [], 0
         for shape, size in zip(shapes, sizes):
             views.append(flat[at:at + size].view(*shape))
@@ -912,6 +951,43 @@ class Context:
         of QuietRuns.  streams as index_streams takes them; the rest as quiet_windows takes it.  sound_segments turns a stream's
         runs into the cuts splice_streams takes.  Raises LinneAmdError when a stream does not index or decode"""
         return self._over_whole_streams(streams, self.quiet_windows, threshold=threshold, min_samples=min_samples, capacity=capacity, group_frames=group_frames)
+
+    def histogram_windows(self, windows, num_bins, shift=0, log2=False, bucket_samples=0, group_frames=0, return_codes=False):
+        """how are the sample levels distributed?  Histograms of |v| of many sample windows of resident .lnn streams in one call, per
+        channel and per bucket of bucket_samples samples, no PCM written (include/linne_amd.h LINNEAmd_HistogramWindowsDevice).
+        windows: a sequence of (stream, index, first_sample, num_samples) as decode_windows takes them.  A sample v counts in bin
+        min(x, num_bins - 1), x = |v| >> shift, or with log2 the bit length of |v| >> shift (0 for 0); num_bins (1 .. HIST_MAX_BINS),
+        shift (0 .. 31), log2 and bucket_samples (0: the whole window is one bucket) are one value or one per window.  -> a list of
+        Histogram, one per window, views of one allocation.  Every count is exact and is what numpy.bincount gives on
+        decode_windows' int32 samples.  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with
+        return_codes -> (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
+        W = len(windows)
+        arr, keep, ranges = self._windows_array(windows)
+
+        def per_window(v, what):
+            vs = [int(v)] * W if isinstance(v, (bool, int, np.integer, np.bool_)) else [int(e) for e in v]
+            assert len(vs) == W and all(0 <= e < (1 << 32) for e in vs), f"{what} is one value in 0 .. 2^32 - 1, or one per window"
+            return vs
+        bins, shifts, scales = per_window(num_bins, "num_bins"), per_window(shift, "shift"), per_window(log2, "log2")
+        # (a table is sized for bins the call will accept; a num_bins that it refuses gets no room)
+        buckets, tables, addresses, counts = self._bucket_tables(bucket_samples, ranges, [b if b <= HIST_MAX_BINS else 0 for b in bins], True)
+        specs = (HistogramSpec * max(W, 1))()
+        for i in range(W):
+            specs[i].bucket_samples, specs[i].num_bins, specs[i].shift, specs[i].scale = buckets[i], bins[i], shifts[i], scales[i]
+            specs[i].d_out, specs[i].channel_stride = addresses[i], counts[i]
+        self._fence()
+        ret = lib.LINNEAmd_HistogramWindowsDevice(self.h, arr, specs, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "HistogramWindowsDevice", return_codes)
+        out = [Histogram(tables[i], bins[i], shifts[i], bool(scales[i]), buckets[i]) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def histogram_streams(self, streams, num_bins, shift=0, log2=False, bucket_samples=0, group_frames=0):
+        """histograms of |v| of whole resident .lnn streams, per channel and bucket: one index_streams call and one histogram_windows
+        call over the whole streams -> a list of Histogram.  streams as index_streams takes them; the rest as histogram_windows takes
+        it.  level_threshold turns a linear histogram into the threshold quiet_streams takes.  Raises LinneAmdError when a stream does
+        not index or decode"""
+        return self._over_whole_streams(streams, self.histogram_windows, num_bins=num_bins, shift=shift, log2=log2, bucket_samples=bucket_samples,
+                                        group_frames=group_frames)
 
     def same_audio(self, stream_a, stream_b, bucket_samples=0):
         """do two resident .lnn streams hold the same samples, whatever their presets, block sizes and mid/side choices?  ->

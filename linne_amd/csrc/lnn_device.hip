@@ -53,6 +53,7 @@
 #include "lnn_k_measure.h"
 #include "lnn_k_digest.h"
 #include "lnn_k_quiet.h"
+#include "lnn_k_histogram.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -68,6 +69,7 @@ static_assert(LINNE_AMD_COMPARE_T_COMPARE == 79, "the compare call's timing kind
 static_assert(LINNE_AMD_MEASURE_T_MEASURE == 80 && LINNE_AMD_MEASURE_T_COMMIT == 82, "the measure call's timing kinds are 80 to 82");
 static_assert(LINNE_AMD_DIGEST_T_DIGEST == 83 && LINNE_AMD_DIGEST_T_COMMIT == 85, "the digest call's timing kinds are 83 to 85");
 static_assert(LINNE_AMD_QUIET_T_QUIET == 86 && LINNE_AMD_QUIET_T_ENDS == 91 && LINNE_AMD_QUIET_EXTRA_LAUNCHES == 5, "the quiet call's timing kinds are 86 to 91: the pass kind and five launches per call");
+static_assert(LINNE_AMD_HISTOGRAM_T_HISTOGRAM == 92 && LINNE_AMD_HISTOGRAM_T_COMMIT == 94, "the histogram call's timing kinds are 92 to 94");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2240,8 +2242,8 @@ struct WxCall;
 /* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
  * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
 struct WxLaunch { const WxBucket *side; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The five calls are the
- * five constant instances below; a launch that a consumer does not have is NULL */
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The six calls are the
+ * six constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2260,7 +2262,7 @@ struct WxCall {
     const WxConsumer *use;
     bool single;                        /* the call is LINNEAmd_DecodeStreamDevice, which its texts then name */
     struct LINNEAmdWindow *win; uint32_t W, group_frames;
-    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest and quiet their specs */
+    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet and histogram their specs */
     void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
@@ -2425,11 +2427,39 @@ static void wx_quiet_read_back(const WxCall &c, uint32_t i, const uint32_t *word
     q.lead_samples = none_loud ? n : d[WXQ_LOUD_LO]; q.trail_samples = none_loud ? n : n - d[WXQ_LOUD_HI];
 }
 
+/* ---- histogram: measure's buckets with num_bins 32-bit counters where that has a record (lnn_k_histogram.h) ---- */
+static int wx_histogram_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdHistogramSpec &hs = ((const struct LINNEAmdHistogramSpec *)c.specs)[i];
+    const uint64_t nb = wx_buckets(c.win[i].num_samples, hs.bucket_samples);
+    if (hs.num_bins == 0u || hs.num_bins > LINNE_AMD_HIST_MAX_BINS) { snprintf(err, cap, "%s: num_bins %u is not in 1 .. %d", c.use->name, hs.num_bins, LINNE_AMD_HIST_MAX_BINS); return LNN_INVALID_ARGUMENT; }
+    if (hs.shift > 31u) { snprintf(err, cap, "%s: shift %u > 31", c.use->name, hs.shift); return LNN_INVALID_ARGUMENT; }
+    if (hs.scale != LINNE_AMD_HIST_LINEAR && hs.scale != LINNE_AMD_HIST_LOG2) { snprintf(err, cap, "%s: unknown scale %u", c.use->name, hs.scale); return LNN_INVALID_ARGUMENT; }
+    if (hs.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", c.use->name); return LNN_INVALID_ARGUMENT; }
+    SX_TRY(wx_bucket_check(c.use->name, c.win[i].num_samples, hs.bucket_samples, hs.d_out, err, cap));
+    if (hs.channel_stride < nb) { snprintf(err, cap, "%s: channel_stride %llu < %llu buckets", c.use->name, (unsigned long long)hs.channel_stride, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static void wx_histogram_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdHistogramSpec &hs = ((const struct LINNEAmdHistogramSpec *)c.specs)[i];
+    r.bucket_samples = hs.bucket_samples; r.bucket_out = hs.d_out; r.bucket_cstride = hs.channel_stride; r.hist = WXH_SPEC(hs.num_bins, hs.shift, hs.scale);
+}
+static int wx_histogram_preset(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_HISTOGRAM_T_PRESET, k_wx_histogram_preset, wx_grid(l.nacc), dim3(WXB_THREADS), 0, ctx->stream, (uint32_t *)l.acc, l.nacc); return LNN_OK; }
+static int wx_histogram_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxHistogramArgs ha; ha.p = la; ha.hwin = l.side; ha.acc = (uint32_t *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_HISTOGRAM_T_HISTOGRAM, k_wx_histogram, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ha);
+    return LNN_OK;
+}
+static int wx_histogram_commit(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_HISTOGRAM_T_COMMIT, k_wx_histogram_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, (const uint32_t *)l.acc, l.fail, l.nout); return LNN_OK; }
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL };
 static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL };
 static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back };
+static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2624,6 +2654,13 @@ extern "C" int LINNEAmd_QuietWindowsDevice(struct LINNEAmdContext *ctx, struct L
         struct LINNEAmdQuiet *answers, uint32_t num_windows, uint32_t group_frames)
 {
     return wx_entry(ctx, wx_call(&WX_QUIET, windows, num_windows, group_frames, specs, answers), windows && specs && answers);
+}
+
+/* the windows' sample levels counted into a table per window instead of their samples written */
+extern "C" int LINNEAmd_HistogramWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdHistogramSpec *specs,
+        uint32_t num_windows, uint32_t group_frames)
+{
+    return wx_entry(ctx, wx_call(&WX_HISTOGRAM, windows, num_windows, group_frames, specs, NULL), windows && specs);
 }
 
 /* one window of one stream */

@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest and find quiet runs; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs and histogram; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -71,15 +71,23 @@ struct WxBucket {
     union { uint32_t ns, threshold; };  /* slots (a power of two); bitmask: the largest quiet magnitude */
     uint32_t fidx;                      /* its fail word */
     union { uint32_t C, F; };           /* per channel: channels; per frame: bytes per sample frame */
-    uint32_t sstride;                   /* per frame: units from one slot to the next (per channel: C * nb, not kept) */
+    union { uint32_t sstride, hist; };  /* per frame: units from one slot to the next (per channel: C * nb, not kept); per bin: the window's bins, shift and scale (WXH_SPEC) */
 };
 static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record and a bucket record are 64 bytes");
+
+/* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
+#define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
+#define WXH_BINS(h) ((h) & 0xFFFFu)
+#define WXH_SHIFT(h) (((h) >> 16) & 31u)
+#define WXH_LOG2(h) (((h) >> 24) & 1u)
 
 /* how a consumer keeps buckets: not at all; an accumulator per (channel, bucket), a window's slots C * nb apart (measure); one per
  * bucket, a window's slots padded to whole 64-byte lines of 16 units (digest); a bit per sample frame, in whole 64-bit words per window
  * (quiet: the units are those words, and the "output records" counted in obase and nout are the commit's chunks of WXQ_CHUNK_WORDS
- * words, of which every window has whole ones) */
-enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2, WX_BITMASK = 3 };
+ * words, of which every window has whole ones); a 32-bit counter per (channel, bucket, bin), laid out as per channel with the window's
+ * num_bins units where that has one -- bin j of channel ch, bucket k, slot s at abase + ((s * C + ch) * nb + k) * num_bins + j -- and
+ * an "output record" per bin, C * nb * num_bins of them: the commit has a lane per bin it stores (histogram) */
+enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2, WX_BITMASK = 3, WX_BUCKETS_PER_BIN = 4 };
 
 /* what the plan reads of a block index */
 struct WxIndexView {
@@ -95,6 +103,7 @@ struct WxRange {
     void *out; uint64_t stride, sstride; uint32_t fmt;          /* its WxWindow's */
     uint64_t bucket_samples, bucket_cstride; void *bucket_out;  /* bucketed consumers: its spec */
     uint64_t quiet_min, quiet_capacity; uint32_t quiet_threshold;       /* the bitmask consumer: its spec beside bucket_out (quiet_min >= 1) */
+    uint32_t hist;                      /* the per-bin consumer: WXH_SPEC beside bucket_samples, bucket_cstride and bucket_out */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -252,6 +261,9 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
                 if (bucketing == WX_BUCKETS_PER_CHANNEL) {
                     m.cstride = w.bucket_cstride; m.C = (uint32_t)C;
                     p.nacc += m.ns * C * m.nb; p.nout += C * m.nb;
+                } else if (bucketing == WX_BUCKETS_PER_BIN) {
+                    m.cstride = w.bucket_cstride; m.C = (uint32_t)C; m.hist = w.hist;
+                    p.nacc += m.ns * C * m.nb * WXH_BINS(w.hist); p.nout += C * m.nb * WXH_BINS(w.hist);
                 } else {
                     /* the slots lie 16 words or more apart, no two in one 64-byte line */
                     m.n = w.n; m.F = (uint32_t)C * ((shape.bits_per_sample + 7u) >> 3);

@@ -22,7 +22,11 @@
  *   - -S / --silence THRESHOLD[,MIN_SAMPLES] STREAM.lnn lists a stream's quiet runs on the device without decoding it into memory
  *     (LINNEAmd_QuietWindowsDevice): the stretches of at least MIN_SAMPLES (default 1) sample frames whose every channel stays within
  *     +-THRESHOLD, "run %llu: first %llu samples %llu seconds %.6f" per run on stdout, then "runs %llu quiet_samples %llu lead %llu
- *     trail %llu"; exit 0 when the stream decoded.
+ *     trail %llu"; exit 0 when the stream decoded;
+ *   - -L / --levels BINS[,SHIFT[,log2]] STREAM.lnn histograms a stream's sample levels on the device without decoding it into memory
+ *     (LINNEAmd_HistogramWindowsDevice, the whole stream one bucket): bin min(x, BINS - 1) of x = |v| >> SHIFT, or with log2 of that
+ *     value's bit length; "ch %u bin %u %llu..%llu %llu" per channel and non-empty bin on stdout -- the lowest and the highest |v| of the
+ *     bin, "inf" for the last bin's, and the count -- then "samples %llu"; exit 0 when the stream decoded.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -38,9 +42,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec;
+    const char *batch_dir, *silence_spec, *levels_spec;
     const char *files[4096];
     int num_files;
 };
@@ -55,6 +59,7 @@ static void usage(const char *argv0)
     printf("       %s -M [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -D [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -S THRESHOLD[,MIN_SAMPLES] STREAM.lnn \n", argv0);
+    printf("       %s -L BINS[,SHIFT[,log2]] STREAM.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -64,6 +69,7 @@ static void usage(const char *argv0)
            "  -M, --measure                          Measure a .lnn stream on the device: min, max, sum, energy, mean, RMS per channel (and bucket) \n"
            "  -D, --digest                           Digest a .lnn stream on the device: the CRC-32 of the decoded PCM as -d writes it (per bucket) \n"
            "  -S, --silence THRESHOLD[,MIN_SAMPLES]  List a .lnn stream's quiet runs on the device: every channel within +-THRESHOLD \n"
+           "  -L, --levels BINS[,SHIFT[,log2]]       Histogram a .lnn stream's sample levels on the device: |v| >> SHIFT, or its bit length \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -116,6 +122,7 @@ static void parse(int argc, char **argv, struct options *o)
             char *end; o->af_iterations = strtol(v, &end, 10);
             if (*end != '\0' || o->af_iterations < 0 || o->af_iterations > 255) { fprintf(stderr, "%s: auxiliary function iteration count is out of range. \n", argv[0]); exit(1); }
         } else if (take_value(argc, argv, &i, "-S", "--silence", &v)) { o->silence = 1; o->silence_spec = v; }
+        else if (take_value(argc, argv, &i, "-L", "--levels", &v)) { o->levels = 1; o->levels_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -148,7 +155,7 @@ static int read_file(const char *path, uint8_t **data, uint32_t *size)
     return 0;
 }
 
-/* A whole stream resident on the device 0, as -V, -C, -M, -D and -S want it: a context, the stream's bytes, its block index, `extra` bytes
+/* A whole stream resident on the device 0, as -V, -C, -M, -D, -S and -L want it: a context, the stream's bytes, its block index, `extra` bytes
  * beside it for what the call reads or writes, and the one window over all its samples */
 struct resident {
     struct LINNEAmdContext *ctx;
@@ -474,6 +481,47 @@ done:
     return rc;
 }
 
+/* -L: the stream goes to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_HistogramWindowsDevice window over the whole stream
+ * in one bucket answer, and the table comes back: a line per channel and non-empty bin, then the sample count */
+static int levels_one(const char *lnn_path, uint32_t bins, uint32_t shift, uint32_t scale)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0, ch, j;
+    struct resident r;
+    struct LINNEAmdHistogramSpec spec;
+    uint64_t *tab = NULL;
+    struct LINNEHeader h;
+    char err[512];
+    uint64_t n, nb;
+    int ret, stage, rc = 1;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    n = h.num_samples;
+    nb = n == 0 ? 0 : 1;
+    if ((stage = resident_open(&r, buf, size, n, sizeof(*tab) * nb * bins * h.num_channels, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to histogram! %s \n" : "%s \n", err); goto done; }
+    memset(&spec, 0, sizeof(spec));
+    spec.num_bins = bins; spec.shift = shift; spec.scale = scale; spec.d_out = r.d_extra; spec.channel_stride = nb;
+    if ((ret = LINNEAmd_HistogramWindowsDevice(r.ctx, &r.w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to histogram! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * bins * h.num_channels : 1)) || (nb && hipMemcpy(tab, r.d_extra, sizeof(*tab) * bins * h.num_channels, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    for (ch = 0; nb && ch < h.num_channels; ch++)
+        for (j = 0; j < bins; j++) {
+            /* bin j holds x == j: the values m = |v| >> shift in [mlo, mhi], |v| in [mlo << shift, ((mhi + 1) << shift) - 1] */
+            const uint64_t cnt = tab[(uint64_t)ch * bins + j];
+            const uint64_t mlo = scale == LINNE_AMD_HIST_LOG2 ? (j ? (uint64_t)1 << (j - 1u) : 0u) : j, mhi = scale == LINNE_AMD_HIST_LOG2 ? (j ? ((uint64_t)1 << j) - 1u : 0u) : j;
+            if (!cnt) continue;
+            printf("ch %u bin %u %llu..", ch, j, (unsigned long long)(mlo << shift));
+            if (j == bins - 1u) printf("inf");
+            else printf("%llu", (unsigned long long)(((mhi + 1u) << shift) - 1u));
+            printf(" %llu \n", (unsigned long long)cnt);
+        }
+    printf("samples %llu \n", (unsigned long long)n);
+    rc = 0;
+done:
+    resident_close(&r);
+    free(tab); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -482,6 +530,23 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.levels) {
+        unsigned long long bins, shift = 0, scale = LINNE_AMD_HIST_LINEAR;
+        char *end;
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.batch_dir || o.num_files != 1) { fprintf(stderr, "%s: -L takes BINS[,SHIFT[,log2]] and a stream file name and no other mode. \n", argv[0]); return 1; }
+        bins = strtoull(o.levels_spec, &end, 10);
+        if (o.levels_spec[0] < '0' || o.levels_spec[0] > '9' || (*end != '\0' && *end != ',') || bins == 0 || bins > LINNE_AMD_HIST_MAX_BINS) { fprintf(stderr, "%s: bin count is out of range. \n", argv[0]); return 1; }
+        if (*end == ',') {
+            const char *m = end + 1;
+            shift = strtoull(m, &end, 10);
+            if (m[0] < '0' || m[0] > '9' || (*end != '\0' && *end != ',') || shift > 31) { fprintf(stderr, "%s: level shift is out of range. \n", argv[0]); return 1; }
+            if (*end == ',') {
+                if (strcmp(end + 1, "log2") == 0) scale = LINNE_AMD_HIST_LOG2;
+                else if (strcmp(end + 1, "linear") != 0) { fprintf(stderr, "%s: level scale is neither linear nor log2. \n", argv[0]); return 1; }
+            }
+        }
+        return levels_one(o.files[0], (uint32_t)bins, (uint32_t)shift, (uint32_t)scale);
+    }
     if (o.silence) {
         unsigned long long threshold, min_samples = 1;
         char *end;
