@@ -406,6 +406,13 @@ enum LINNEAmdHistogramTimingKind {
     LINNE_AMD_HISTOGRAM_T_PRESET = 93,      /* the call's accumulators zeroed, once, in front of the first pass (k_wx_histogram_preset) */
     LINNE_AMD_HISTOGRAM_T_COMMIT = 94       /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_histogram_commit) */
 };
+/* relating the channels of windows (LINNEAmd_RelateWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of kind 95 wherever
+ * that call has one of kind 59, and one launch each of kinds 96 and 97 per call that takes a pass) */
+enum LINNEAmdRelateTimingKind {
+    LINNE_AMD_RELATE_T_RELATE = 95,         /* every window's channel pairs reduced into their buckets' accumulators (k_wx_relate) */
+    LINNE_AMD_RELATE_T_PRESET = 96,         /* the call's accumulators zeroed, once, in front of the first pass (k_wx_relate_preset) */
+    LINNE_AMD_RELATE_T_COMMIT = 97          /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_relate_commit) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -831,6 +838,51 @@ struct LINNEAmdHistogramSpec {
 };
 int LINNEAmd_HistogramWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdHistogramSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- relating the channels of windows of resident streams: dual mono?  Polarity turned?  Correlation?  No PCM written ----
+ * LINNEAmd_RelateWindowsDevice takes the windows of LINNEAmd_DecodeWindowsDevice and, instead of writing every window's samples,
+ * reduces the products of its channels: the only output is a table of struct LINNEAmdRelation per window, in device memory, one
+ * record per bucket and channel pair (i <= j) -- a Gram matrix per bucket, in exact integers.  The samples are exactly those
+ * LINNEAmd_DecodeStreamDevice writes for the range -- int32, L/R after MS, nothing saturated, the zeros of SILENT blocks and of the
+ * range behind the stream's last block included.  Per pair and bucket, over the bucket's sample frames: dot, the sum of a_i * a_j
+ * as a 128-bit two's-complement integer (dot_hi * 2^64 + dot_lo; one product is at most 2^62 in magnitude, and no stream is long
+ * enough to pass 2^127); num_equal, the frames with a_i == a_j; num_opposite, the frames with (int64)a_i + (int64)a_j == 0
+ * (INT32_MIN is nobody's opposite, not even its own).  A frame of zeros counts in both.  The diagonal pairs are part of the table on
+ * purpose: dot(i, i) is channel i's sum of squares (LINNEAmd_MeasureWindowsDevice's sumsq), num_equal(i, i) the bucket's frame count
+ * and num_opposite(i, i) the channel's count of zero samples, so one call gives dot(i, j) / sqrt(dot(i, i) * dot(j, j)) without a
+ * second decode.  The pairs are the upper triangle row by row: with C channels, LINNE_AMD_NUM_PAIRS(C) of them, pair (i, j) at
+ * LINNE_AMD_PAIR(C, i, j) -- (0,0) (0,1) .. (0,C-1) (1,1) .. (C-1,C-1).
+ * Buckets are LINNEAmd_MeasureWindowsDevice's: specs[i].bucket_samples = b > 0 gives nb = ceil(n / b) buckets, bucket k holding the
+ * window's samples [k * b, min((k + 1) * b, n)) (the last one may be short); b == 0 is one bucket of the whole window; a window of no
+ * samples has no buckets and nothing is written.  The windows of one call may differ in every field of their specs.
+ * Everything LINNEAmd_MeasureWindowsDevice says about results holds unchanged: the windows' d_pcm and pcm_stride are ignored;
+ * every window's `result` is what LINNEAmd_DecodeWindowsDevice gives it, and for that window alone INVALID_ARGUMENT when d_out is
+ * NULL (with n > 0) or not 8-byte aligned, pair_stride < nb, or nb > 2^32 - 1.  A failing window's d_out is never written, and a
+ * failing window does not disturb the others.  No byte outside d_out[p * pair_stride + k], p < LINNE_AMD_NUM_PAIRS(channels), k < nb,
+ * is written; the outputs of different windows must not overlap; the streams are only read.  Shape groups, passes, group_frames,
+ * scratch and whole-call failures are the decode call's, with "window <i>: " and the single call's text in GetLastError.  A pass has
+ * the decode call's launches with kind 95 in place of kind 59; a call that takes at least one pass adds exactly two launches,
+ * whatever num_windows is: kind 96 in front of the first pass (the accumulators zeroed) and kind 97 behind the last (the slots added
+ * up with carries and the tables of the windows whose Rice check passed written to their d_out); a window that spans passes collects
+ * its sums over them.  Copies (one upload, one fetch) and host synchronisations (one) are the measure call's.  The accumulators live
+ * in the context's scratch: one struct LINNEAmdRelation per (pair, bucket) of every window -- the bytes of the table itself -- times
+ * up to 64 for windows whose buckets are 8192 samples or longer (a bucket of b samples has at most b / 4096 such copies: at most
+ * 32 * P / 4096 bytes per sample frame, under 0.3 bytes at 8 channels).  num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL
+ * specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the context's stream and synchronous. */
+#define LINNE_AMD_NUM_PAIRS(C)      ((C) * ((C) + 1u) / 2u)                      /* 36 at 8 channels */
+#define LINNE_AMD_PAIR(C, i, j)     ((i) * (C) - (i) * ((i) - 1u) / 2u + ((j) - (i)))   /* i <= j < C: the upper triangle, row by row */
+struct LINNEAmdRelation {               /* 32 bytes: one channel pair (i <= j) of one bucket of one window */
+    uint64_t dot_lo; int64_t dot_hi;    /* the exact sum of a_i * a_j over the bucket's frames: a 128-bit two's-complement integer */
+    uint64_t num_equal;                 /* frames with a_i == a_j */
+    uint64_t num_opposite;              /* frames with (int64)a_i + (int64)a_j == 0 (INT32_MIN is nobody's opposite) */
+};
+struct LINNEAmdRelateSpec {
+    uint64_t bucket_samples;            /* 0: the whole window is one bucket */
+    struct LINNEAmdRelation *d_out;     /* device, 8-byte aligned: pair p, bucket k at d_out[p * pair_stride + k] */
+    uint64_t pair_stride;               /* in buckets, >= the window's bucket count */
+};
+int LINNEAmd_RelateWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdRelateSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

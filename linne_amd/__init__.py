@@ -59,7 +59,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_CompareWindowsDevice",
     "LINNEAmd_MeasureWindowsDevice",
     "LINNEAmd_DigestWindowsDevice",
-    "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice",
+    "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice", "LINNEAmd_RelateWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -257,6 +257,111 @@ def level_threshold(counts, fraction, shift=0):
     return None if j == len(c) - 1 else ((j + 1) << int(shift)) - 1
 
 
+class Relation(C.Structure):
+    """struct LINNEAmdRelation (include/linne_amd.h): one channel pair (i <= j) of one bucket of one window"""
+    _fields_ = [("dot_lo", C.c_uint64), ("dot_hi", C.c_int64), ("num_equal", C.c_uint64), ("num_opposite", C.c_uint64)]
+
+
+class RelateSpec(C.Structure):
+    """struct LINNEAmdRelateSpec (include/linne_amd.h)"""
+    _fields_ = [("bucket_samples", C.c_uint64), ("d_out", C.c_void_p), ("pair_stride", C.c_uint64)]
+
+
+RELATION_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("num_equal", "<u8"), ("num_opposite", "<u8")])
+
+
+def pair_index(C, i, j):
+    """LINNE_AMD_PAIR (include/linne_amd.h): the place of channel pair (i, j), i <= j < C, in the upper triangle taken row by row"""
+    C, i, j = int(C), int(i), int(j)
+    assert 0 <= i <= j < C, "a pair is i <= j < C"
+    return i * C - i * (i - 1) // 2 + (j - i)
+
+
+def _pair_channels(P):
+    """the channel count whose upper triangle has P pairs"""
+    C = (math.isqrt(8 * int(P) + 1) - 1) // 2
+    assert C >= 1 and C * (C + 1) // 2 == int(P), f"{P} is not a number of channel pairs"
+    return C
+
+
+class Relations:
+    """one window's table of relate_windows: `records`, an int64 CUDA tensor (P, nb, 4) holding a struct LINNEAmdRelation per channel
+    pair (pair_index) and bucket, and strided views of it -- dot_lo, dot_hi (the unsigned low and the signed high word of the 128-bit
+    sum of a_i * a_j), num_equal and num_opposite, each int64 (P, nb)"""
+
+    def __init__(self, records, bucket_samples):
+        self.records, self.bucket_samples = records, bucket_samples
+        self.dot_lo, self.dot_hi, self.num_equal, self.num_opposite = records[..., 0], records[..., 1], records[..., 2], records[..., 3]
+        self.num_channels = _pair_channels(records.shape[0])
+
+    def dot(self):
+        """the sums of products as float64 (P, nb), within two units in the last place.  A negative sum is negated in integers first
+        (hi * 2^64 + lo in floating point would cancel: a small negative sum has hi = -1 and lo just below 2^64)"""
+        import torch
+        neg = self.dot_hi < 0
+        lo = torch.where(neg, -self.dot_lo, self.dot_lo)               # (int64 wraps: the low word of the magnitude)
+        hi = torch.where(neg, ~self.dot_hi + (self.dot_lo == 0).to(torch.int64), self.dot_hi)
+        mag = hi.double() * 2.0 ** 64 + lo.double() + (lo < 0).double() * 2.0 ** 64
+        return torch.where(neg, -mag, mag)
+
+    def cpu(self):
+        """-> a numpy structured array (P, nb) with the fields dot_lo (unsigned), dot_hi, num_equal, num_opposite"""
+        a = np.ascontiguousarray(self.records.cpu().numpy())
+        return a.view(RELATION_DTYPE).reshape(a.shape[:2])
+
+
+def _relation_table(relation):
+    """a Relations or its .cpu() -> (the structured array (P, nb), C)"""
+    a = relation.cpu() if isinstance(relation, Relations) else np.asarray(relation)
+    assert a.dtype == RELATION_DTYPE and a.ndim == 2, "a relation is a Relations or a RELATION_DTYPE array (P, nb)"
+    return a, _pair_channels(a.shape[0])
+
+
+def relation_dots(relation):
+    """the exact sums of products of a Relations or its .cpu(): a list [P][nb] of Python integers, dot_hi * 2^64 + dot_lo"""
+    a, _ = _relation_table(relation)
+    return [[(int(r["dot_hi"]) << 64) + int(r["dot_lo"]) for r in row] for row in a]
+
+
+def correlation(relation):
+    """the correlation coefficients of a Relations or its .cpu() -> float64 (C, C, nb), symmetric: dot_ij / sqrt(dot_ii * dot_jj) per
+    bucket, NaN where a channel's energy is 0.  The integers are divided as such (a 128-bit sum has no exact float64).  Pure host
+    code"""
+    from fractions import Fraction
+    a, C = _relation_table(relation)
+    dots, nb = relation_dots(a), a.shape[1]
+    out = np.full((C, C, nb), np.nan, dtype=np.float64)
+    for i in range(C):
+        for j in range(i, C):
+            for k in range(nb):
+                ei, ej = dots[pair_index(C, i, i)][k], dots[pair_index(C, j, j)][k]
+                if ei > 0 and ej > 0:
+                    d = dots[pair_index(C, i, j)][k]
+                    r = math.sqrt(Fraction(d * d, ei * ej))
+                    out[i, j, k] = out[j, i, k] = -r if d < 0 else r
+    return out
+
+
+def channel_findings(relation):
+    """what a Relations or its .cpu() says in words -> a list, one dict per bucket: {"pairs": {(i, j): finding, i < j}, "channels":
+    {i: finding}}.  A pair is "identical" when num_equal is the bucket's frame count, "inverted" when num_opposite is and the two
+    channels are not all zero, otherwise None; a channel is "silent" when all its samples are zero (num_opposite(i, i) is the frame
+    count), otherwise None.  Pure host code"""
+    a, C = _relation_table(relation)
+    out = []
+    for k in range(a.shape[1]):
+        frames = int(a[0, k]["num_equal"])
+        silent = [int(a[pair_index(C, i, i), k]["num_opposite"]) == frames for i in range(C)]
+        pairs = {}
+        for i in range(C):
+            for j in range(i + 1, C):
+                r = a[pair_index(C, i, j), k]
+                pairs[(i, j)] = ("identical" if int(r["num_equal"]) == frames else
+                                 "inverted" if int(r["num_opposite"]) == frames and not (silent[i] and silent[j]) else None)
+        out.append({"pairs": pairs, "channels": {i: ("silent" if silent[i] else None) for i in range(C)}})
+    return out
+
+
 def sound_segments(num_samples, runs, pad=0):
     """the complement of quiet runs inside [0, num_samples): runs a sequence of (first, n) (a QuietRuns' .cpu(), or an array (k, 2)) ->
     a list of (first, n) in ascending order, every segment widened by `pad` frames at both ends (not beyond [0, num_samples)) and
@@ -363,6 +468,7 @@ def _load():
     L.LINNEAmd_DigestWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(DigestSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_QuietWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(QuietSpec), C.POINTER(Quiet), C.c_uint32, C.c_uint32]
     L.LINNEAmd_HistogramWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(HistogramSpec), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_RelateWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(RelateSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -719,14 +825,15 @@ class Context:
     def _bucket_tables(self, bucket_samples, ranges, words, per_channel):
         """the tables of a call that answers per bucket: bucket_samples one value or one per window -> (the bucket length per window;
         per window an int64 view (nb, words) -- per_channel: (C, nb, words) -- of one allocation; the views' device addresses; the
-        bucket counts nb).  words: one value, or one per window"""
+        bucket counts nb).  words: one value, or one per window; per_channel "pairs": (P, nb, words), P the channel pairs"""
         import torch
         W = len(ranges)
         buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
         assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
         words = [words] * W if isinstance(words, int) else list(words)
         counts = [0 if n <= 0 else (1 if b == 0 else -(-n // b)) for (_, _, n), b in zip(ranges, buckets)]
-        shapes = [((x.header["num_channels"],) if per_channel else ()) + (nb, wd) for (x, _, _), nb, wd in zip(ranges, counts, words)]
+        lead = {False: lambda c: (), True: lambda c: (c,), "pairs": lambda c: (c * (c + 1) // 2,)}[per_channel]
+        shapes = [lead(x.header["num_channels"]) + (nb, wd) for (x, _, _), nb, wd in zip(ranges, counts, words)]
         sizes = [math.prod(shape) for shape in shapes]
         flat = torch.empty(max(sum(sizes), max(words, default=1)), dtype=torch.int64, device=f"cuda:{self.device}")
         views, addresses, at = [], [], 0
@@ -988,6 +1095,34 @@ class Context:
         not index or decode"""
         return self._over_whole_streams(streams, self.histogram_windows, num_bins=num_bins, shift=shift, log2=log2, bucket_samples=bucket_samples,
                                         group_frames=group_frames)
+
+    def relate_windows(self, windows, bucket_samples=0, group_frames=0, return_codes=False):
+        """how do the channels relate?  Per channel pair i <= j and per bucket of bucket_samples samples, the exact sum of a_i * a_j
+        (128 bits) and the counts of frames with a_i == a_j and with a_i == -a_j, of many sample windows of resident .lnn streams in
+        one call, no PCM written (include/linne_amd.h LINNEAmd_RelateWindowsDevice).  windows: a sequence of (stream, index,
+        first_sample, num_samples) as decode_windows takes them; bucket_samples: one value or one per window (0: the whole window is
+        one bucket; the last bucket may be short).  -> a list of Relations, one per window, views of one allocation, pair (i, j) in
+        row pair_index(C, i, j).  Every number is exact and is what Python integers give on decode_windows' int32 samples;
+        correlation and channel_findings read the table on the host.  Errors follow measure_windows: LinneAmdError with .code and
+        .codes when a window fails; with return_codes -> (answers, codes), a failing window's answer is None, and only a failure of
+        the whole call raises"""
+        W = len(windows)
+        arr, keep, ranges = self._windows_array(windows)
+        buckets, recs, addresses, counts = self._bucket_tables(bucket_samples, ranges, 4, "pairs")
+        specs = (RelateSpec * max(W, 1))()
+        for i in range(W):
+            specs[i].bucket_samples, specs[i].d_out, specs[i].pair_stride = buckets[i], addresses[i], counts[i]
+        self._fence()
+        ret = lib.LINNEAmd_RelateWindowsDevice(self.h, arr, specs, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "RelateWindowsDevice", return_codes)
+        out = [Relations(recs[i], buckets[i]) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    def relate_streams(self, streams, bucket_samples=0, group_frames=0):
+        """the channel relations of whole resident .lnn streams, per pair and bucket: one index_streams call and one relate_windows
+        call over the whole streams -> a list of Relations.  streams as index_streams takes them; bucket_samples as relate_windows
+        takes it.  Raises LinneAmdError when a stream does not index or decode"""
+        return self._over_whole_streams(streams, self.relate_windows, bucket_samples=bucket_samples, group_frames=group_frames)
 
     def same_audio(self, stream_a, stream_b, bucket_samples=0):
         """do two resident .lnn streams hold the same samples, whatever their presets, block sizes and mid/side choices?  ->

@@ -54,6 +54,7 @@
 #include "lnn_k_digest.h"
 #include "lnn_k_quiet.h"
 #include "lnn_k_histogram.h"
+#include "lnn_k_relate.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -70,6 +71,7 @@ static_assert(LINNE_AMD_MEASURE_T_MEASURE == 80 && LINNE_AMD_MEASURE_T_COMMIT ==
 static_assert(LINNE_AMD_DIGEST_T_DIGEST == 83 && LINNE_AMD_DIGEST_T_COMMIT == 85, "the digest call's timing kinds are 83 to 85");
 static_assert(LINNE_AMD_QUIET_T_QUIET == 86 && LINNE_AMD_QUIET_T_ENDS == 91 && LINNE_AMD_QUIET_EXTRA_LAUNCHES == 5, "the quiet call's timing kinds are 86 to 91: the pass kind and five launches per call");
 static_assert(LINNE_AMD_HISTOGRAM_T_HISTOGRAM == 92 && LINNE_AMD_HISTOGRAM_T_COMMIT == 94, "the histogram call's timing kinds are 92 to 94");
+static_assert(LINNE_AMD_RELATE_T_RELATE == 95 && LINNE_AMD_RELATE_T_COMMIT == 97, "the relate call's timing kinds are 95 to 97");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2242,8 +2244,8 @@ struct WxCall;
 /* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
  * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
 struct WxLaunch { const WxBucket *side; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The six calls are the
- * six constant instances below; a launch that a consumer does not have is NULL */
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The seven calls are the
+ * seven constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2262,7 +2264,7 @@ struct WxCall {
     const WxConsumer *use;
     bool single;                        /* the call is LINNEAmd_DecodeStreamDevice, which its texts then name */
     struct LINNEAmdWindow *win; uint32_t W, group_frames;
-    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet and histogram their specs */
+    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet, histogram and relate their specs */
     void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
@@ -2454,12 +2456,36 @@ static int wx_histogram_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPl
 }
 static int wx_histogram_commit(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_HISTOGRAM_T_COMMIT, k_wx_histogram_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, (const uint32_t *)l.acc, l.fail, l.nout); return LNN_OK; }
 
+/* ---- relate: measure's buckets with a record per channel pair where that has one per channel (lnn_k_relate.h) ---- */
+static int wx_relate_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdRelateSpec &rs = ((const struct LINNEAmdRelateSpec *)c.specs)[i];
+    const uint64_t nb = wx_buckets(c.win[i].num_samples, rs.bucket_samples);
+    SX_TRY(wx_bucket_check(c.use->name, c.win[i].num_samples, rs.bucket_samples, rs.d_out, err, cap));
+    if (rs.pair_stride < nb) { snprintf(err, cap, "%s: pair_stride %llu < %llu buckets", c.use->name, (unsigned long long)rs.pair_stride, (unsigned long long)nb); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static void wx_relate_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    const struct LINNEAmdRelateSpec &rs = ((const struct LINNEAmdRelateSpec *)c.specs)[i];
+    r.bucket_samples = rs.bucket_samples; r.bucket_out = rs.d_out; r.bucket_cstride = rs.pair_stride;
+}
+static int wx_relate_preset(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_RELATE_T_PRESET, k_wx_relate_preset, wx_grid(l.nacc), dim3(WXB_THREADS), 0, ctx->stream, (struct LINNEAmdRelation *)l.acc, l.nacc); return LNN_OK; }
+static int wx_relate_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxRelateArgs ra; ra.p = la; ra.rwin = l.side; ra.acc = (struct LINNEAmdRelation *)l.acc;
+    SX_LAUNCH(NULL, LINNE_AMD_RELATE_T_RELATE, k_wx_relate, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ra);
+    return LNN_OK;
+}
+static int wx_relate_commit(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_RELATE_T_COMMIT, k_wx_relate_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, (const struct LINNEAmdRelation *)l.acc, l.fail, l.nout); return LNN_OK; }
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL };
 static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL };
 static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back };
 static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL };
+static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2661,6 +2687,13 @@ extern "C" int LINNEAmd_HistogramWindowsDevice(struct LINNEAmdContext *ctx, stru
         uint32_t num_windows, uint32_t group_frames)
 {
     return wx_entry(ctx, wx_call(&WX_HISTOGRAM, windows, num_windows, group_frames, specs, NULL), windows && specs);
+}
+
+/* the windows' channel pairs reduced into a table per window instead of their samples written */
+extern "C" int LINNEAmd_RelateWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdRelateSpec *specs,
+        uint32_t num_windows, uint32_t group_frames)
+{
+    return wx_entry(ctx, wx_call(&WX_RELATE, windows, num_windows, group_frames, specs, NULL), windows && specs);
 }
 
 /* one window of one stream */

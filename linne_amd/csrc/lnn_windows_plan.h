@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs and histogram; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram and relate; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -71,7 +71,7 @@ struct WxBucket {
     union { uint32_t ns, threshold; };  /* slots (a power of two); bitmask: the largest quiet magnitude */
     uint32_t fidx;                      /* its fail word */
     union { uint32_t C, F; };           /* per channel: channels; per frame: bytes per sample frame */
-    union { uint32_t sstride, hist; };  /* per frame: units from one slot to the next (per channel: C * nb, not kept); per bin: the window's bins, shift and scale (WXH_SPEC) */
+    union { uint32_t sstride, hist, npair; };   /* per frame: units from one slot to the next (per channel: C * nb, not kept); per bin: the window's bins, shift and scale (WXH_SPEC); per pair: P = C (C + 1) / 2 */
 };
 static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record and a bucket record are 64 bytes");
 
@@ -86,8 +86,11 @@ static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record a
  * (quiet: the units are those words, and the "output records" counted in obase and nout are the commit's chunks of WXQ_CHUNK_WORDS
  * words, of which every window has whole ones); a 32-bit counter per (channel, bucket, bin), laid out as per channel with the window's
  * num_bins units where that has one -- bin j of channel ch, bucket k, slot s at abase + ((s * C + ch) * nb + k) * num_bins + j -- and
- * an "output record" per bin, C * nb * num_bins of them: the commit has a lane per bin it stores (histogram) */
-enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2, WX_BITMASK = 3, WX_BUCKETS_PER_BIN = 4 };
+ * an "output record" per bin, C * nb * num_bins of them: the commit has a lane per bin it stores (histogram); an accumulator per
+ * (channel pair i <= j, bucket), laid out as per channel with the P = C (C + 1) / 2 pairs (LINNE_AMD_PAIR) where that has the
+ * channels -- pair p, bucket k, slot s at abase + (s * P + p) * nb + k, a window's slots P * nb apart -- P * nb output records, and
+ * cstride the caller's pair stride (relate) */
+enum WxBucketing { WX_NO_BUCKETS = 0, WX_BUCKETS_PER_CHANNEL = 1, WX_BUCKETS_PER_FRAME = 2, WX_BITMASK = 3, WX_BUCKETS_PER_BIN = 4, WX_BUCKETS_PER_PAIR = 5 };
 
 /* what the plan reads of a block index */
 struct WxIndexView {
@@ -264,6 +267,10 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
                 } else if (bucketing == WX_BUCKETS_PER_BIN) {
                     m.cstride = w.bucket_cstride; m.C = (uint32_t)C; m.hist = w.hist;
                     p.nacc += m.ns * C * m.nb * WXH_BINS(w.hist); p.nout += C * m.nb * WXH_BINS(w.hist);
+                } else if (bucketing == WX_BUCKETS_PER_PAIR) {
+                    const uint64_t P = LINNE_AMD_NUM_PAIRS(C);
+                    m.cstride = w.bucket_cstride; m.C = (uint32_t)C; m.npair = (uint32_t)P;
+                    p.nacc += m.ns * P * m.nb; p.nout += P * m.nb;
                 } else {
                     /* the slots lie 16 words or more apart, no two in one 64-byte line */
                     m.n = w.n; m.F = (uint32_t)C * ((shape.bits_per_sample + 7u) >> 3);

@@ -26,7 +26,13 @@
  *   - -L / --levels BINS[,SHIFT[,log2]] STREAM.lnn histograms a stream's sample levels on the device without decoding it into memory
  *     (LINNEAmd_HistogramWindowsDevice, the whole stream one bucket): bin min(x, BINS - 1) of x = |v| >> SHIFT, or with log2 of that
  *     value's bit length; "ch %u bin %u %llu..%llu %llu" per channel and non-empty bin on stdout -- the lowest and the highest |v| of the
- *     bin, "inf" for the last bin's, and the count -- then "samples %llu"; exit 0 when the stream decoded.
+ *     bin, "inf" for the last bin's, and the count -- then "samples %llu"; exit 0 when the stream decoded;
+ *   - -R / --relate [BUCKET] STREAM.lnn relates a stream's channels on the device without decoding it into memory
+ *     (LINNEAmd_RelateWindowsDevice): per channel pair i <= j "pair %u %u: samples %llu dot %s equal %llu opposite %llu correlation
+ *     %.6f" on stdout -- the exact sum of a_i * a_j in decimal, the frames with a_i == a_j and with a_i == -a_j, and
+ *     dot_ij / sqrt(dot_ii * dot_jj) ("nan" where a channel has no energy) -- followed by " identical" or " inverted" where every
+ *     frame says so, and "channel %u: silent" for a channel of zeros; with BUCKET one such group per BUCKET samples, every line
+ *     behind "bucket %llu ".
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -42,7 +48,7 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
     const char *batch_dir, *silence_spec, *levels_spec;
     const char *files[4096];
@@ -60,6 +66,7 @@ static void usage(const char *argv0)
     printf("       %s -D [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -S THRESHOLD[,MIN_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -L BINS[,SHIFT[,log2]] STREAM.lnn \n", argv0);
+    printf("       %s -R [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -70,6 +77,7 @@ static void usage(const char *argv0)
            "  -D, --digest                           Digest a .lnn stream on the device: the CRC-32 of the decoded PCM as -d writes it (per bucket) \n"
            "  -S, --silence THRESHOLD[,MIN_SAMPLES]  List a .lnn stream's quiet runs on the device: every channel within +-THRESHOLD \n"
            "  -L, --levels BINS[,SHIFT[,log2]]       Histogram a .lnn stream's sample levels on the device: |v| >> SHIFT, or its bit length \n"
+           "  -R, --relate                           Relate a .lnn stream's channels on the device: dot products, equal and opposite frames, correlation per pair (and bucket) \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -108,6 +116,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (strcmp(a, "-V") == 0 || strcmp(a, "--verify") == 0) o->verify = 1;
         else if (strcmp(a, "-C") == 0 || strcmp(a, "--compare") == 0) o->compare = 1;
         else if (strcmp(a, "-M") == 0 || strcmp(a, "--measure") == 0) o->measure = 1;
+        else if (strcmp(a, "-R") == 0 || strcmp(a, "--relate") == 0) o->relate = 1;
         else if (strcmp(a, "-D") == 0 || strcmp(a, "--digest") == 0) o->digest = 1;
         else if (strcmp(a, "-c") == 0 || strcmp(a, "--no-crc-check") == 0) o->no_crc = 1;
         else if (strcmp(a, "-l") == 0 || strcmp(a, "--enable-learning") == 0) o->learning = 1;
@@ -155,7 +164,7 @@ static int read_file(const char *path, uint8_t **data, uint32_t *size)
     return 0;
 }
 
-/* A whole stream resident on the device 0, as -V, -C, -M, -D, -S and -L want it: a context, the stream's bytes, its block index, `extra` bytes
+/* A whole stream resident on the device 0, as -V, -C, -M, -D, -S, -L and -R want it: a context, the stream's bytes, its block index, `extra` bytes
  * beside it for what the call reads or writes, and the one window over all its samples */
 struct resident {
     struct LINNEAmdContext *ctx;
@@ -522,6 +531,81 @@ done:
     return rc;
 }
 
+/* the 128-bit two's-complement integer hi * 2^64 + lo in decimal (at most 40 digits and a sign) */
+static const char *decimal128(int64_t hi, uint64_t lo, char text[48])
+{
+    unsigned __int128 u = ((unsigned __int128)(uint64_t)hi << 64) | lo;
+    const int neg = hi < 0;
+    char *p = text + 47;
+    if (neg) u = 0 - u;
+    *p = '\0';
+    do { *--p = (char)('0' + (int)(u % 10u)); u /= 10u; } while (u != 0);
+    if (neg) *--p = '-';
+    return p;
+}
+
+/* the same integer as a double: negated in integers first, so that a small negative sum (hi = -1, lo just below 2^64) does not cancel */
+static double double128(int64_t hi, uint64_t lo)
+{
+    unsigned __int128 u = ((unsigned __int128)(uint64_t)hi << 64) | lo;
+    const int neg = hi < 0;
+    double mag;
+    if (neg) u = 0 - u;
+    mag = ldexp((double)(uint64_t)(u >> 64), 64) + (double)(uint64_t)u;
+    return neg ? -mag : mag;
+}
+
+/* -R: the stream goes to the device; LINNEAmd_StreamIndexCreate and one LINNEAmd_RelateWindowsDevice window over the whole stream
+ * answer, and the table comes back: a line per channel pair, or with a bucket per bucket and pair, and a line per silent channel */
+static int relate_one(const char *lnn_path, uint64_t bucket)
+{
+    uint8_t *buf = NULL;
+    uint32_t size = 0, i, j, C, P;
+    struct resident r;
+    struct LINNEAmdRelateSpec spec;
+    struct LINNEAmdRelation *tab = NULL;
+    struct LINNEHeader h;
+    char err[512], text[48];
+    uint64_t n, nb, k;
+    int ret, stage, rc = 1;
+    if (read_file(lnn_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", lnn_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    n = h.num_samples; C = h.num_channels; P = LINNE_AMD_NUM_PAIRS(C);
+    nb = n == 0 ? 0 : (bucket == 0 || bucket >= n) ? 1 : (n + bucket - 1) / bucket;
+    if ((stage = resident_open(&r, buf, size, n, sizeof(*tab) * nb * P, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to relate! %s \n" : "%s \n", err); goto done; }
+    memset(&spec, 0, sizeof(spec));
+    spec.bucket_samples = bucket; spec.d_out = r.d_extra; spec.pair_stride = nb;
+    if ((ret = LINNEAmd_RelateWindowsDevice(r.ctx, &r.w, &spec, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to relate! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(tab = malloc(nb ? sizeof(*tab) * nb * P : 1)) || (nb && hipMemcpy(tab, r.d_extra, sizeof(*tab) * nb * P, hipMemcpyDeviceToHost) != hipSuccess)) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    for (k = 0; k < nb; k++) {
+        const uint64_t cnt = tab[k].num_equal;                     /* pair (0, 0): every frame equals itself */
+        for (i = 0; i < C; i++)
+            for (j = i; j < C; j++) {
+                const struct LINNEAmdRelation *m = tab + (uint64_t)LINNE_AMD_PAIR(C, i, j) * nb + k;
+                const struct LINNEAmdRelation *a = tab + (uint64_t)LINNE_AMD_PAIR(C, i, i) * nb + k, *b = tab + (uint64_t)LINNE_AMD_PAIR(C, j, j) * nb + k;
+                const double d = double128(m->dot_hi, m->dot_lo), ei = double128(a->dot_hi, a->dot_lo), ej = double128(b->dot_hi, b->dot_lo);
+                if (bucket) printf("bucket %llu ", (unsigned long long)k);
+                printf("pair %u %u: samples %llu dot %s equal %llu opposite %llu correlation ", i, j, (unsigned long long)cnt, decimal128(m->dot_hi, m->dot_lo, text),
+                        (unsigned long long)m->num_equal, (unsigned long long)m->num_opposite);
+                if (ei > 0.0 && ej > 0.0) printf("%.6f", d / sqrt(ei * ej));
+                else printf("nan");
+                if (i < j && m->num_equal == cnt) printf(" identical");
+                else if (i < j && m->num_opposite == cnt && !(a->num_opposite == cnt && b->num_opposite == cnt)) printf(" inverted");
+                printf(" \n");
+            }
+        for (i = 0; i < C; i++)
+            if (tab[(uint64_t)LINNE_AMD_PAIR(C, i, i) * nb + k].num_opposite == cnt) {
+                if (bucket) printf("bucket %llu ", (unsigned long long)k);
+                printf("channel %u: silent \n", i);
+            }
+    }
+    rc = 0;
+done:
+    resident_close(&r);
+    free(tab); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -530,6 +614,15 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.relate) {
+        unsigned long long bucket = 0;
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -R takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
+        if (o.num_files == 2) {
+            char *end; bucket = strtoull(o.files[0], &end, 10);
+            if (*end != '\0' || o.files[0][0] < '0' || o.files[0][0] > '9' || bucket == 0) { fprintf(stderr, "%s: bucket sample count is out of range. \n", argv[0]); return 1; }
+        }
+        return relate_one(o.files[o.num_files - 1], bucket);
+    }
     if (o.levels) {
         unsigned long long bins, shift = 0, scale = LINNE_AMD_HIST_LINEAR;
         char *end;
