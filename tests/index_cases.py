@@ -6,7 +6,8 @@ device code: no candidates, no chains, no tables."""
 import numpy as np
 
 from splice_cases import COMPRESS, HEADER, RAW, SILENT, header_fields
-from test_gpu_stream_windows import SHAPES, blocks, crc16, mixed_signal
+from stream_refs import blocks, crc16, mixed_signal
+from test_gpu_stream_windows import SHAPES
 
 OK, INVALID_ARGUMENT, INVALID_FORMAT, INSUFFICIENT_BUFFER, INSUFFICIENT_DATA, PARAMETER_NOT_SET, CORRUPTION, NG = range(8)
 SILENT_BLOCKS = 1000

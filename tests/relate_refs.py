@@ -1,11 +1,10 @@
 """The reference of the relate call's tests (tests/test_stream_relate_cpu.py, tests/test_gpu_stream_relate.py,
-tests/test_gpu_stream_relate_history.py): what LINNEAmd_RelateWindowsDevice must write, from numpy and Python integers on the
+tests/test_gpu_stream_history.py): what LINNEAmd_RelateWindowsDevice must write, from numpy and Python integers on the
 oracle's decode of a stream -- never from the library under test -- and the streams those tests write themselves."""
 import numpy as np
 
 import linne_amd
-from stream_refs import crc16
-from test_stream_measure_cpu import CARRY_NS, CARRY_PEAK, carry_signal
+from stream_refs import CARRY_NS, CARRY_PEAK, carry_signal, crc16
 
 RAW = 2
 S = 1024

@@ -26,6 +26,7 @@ OK, INVALID_ARGUMENT, CORRUPTION, NG = 0, 1, 6, 7
 COMPRESS, SILENT, RAW = 0, 1, 2
 CONSUMERS = ["place", "measure", "digest", "quiet", "compare"]
 ACCUMULATING = ("measure", "digest", "quiet")
+LATER = ("histogram", "relate")             # they run before and after every consumer, themselves included, in scenarios of their own below
 OTHER_CALLS = ["index_streams", "repair_streams", "splice_streams", "encode_streams", "set_verify"]
 RATE = 44100
 
@@ -143,6 +144,9 @@ BUCKETS = (1, 7, 441, 0)
 THRESHOLDS = (0, 3, 40, 1 << 15)
 MINS = (1, 2, 17, 64, 5)
 CAP = 512
+# cycled through the windows of a step from the step's own offset: histogram (num_bins, shift, log2, bucket_samples), relate bucket_samples
+SPECS = {"histogram": [(1024, 4, False, 0), (33, 0, True, 441), (64, 9, False, 7), (2, 0, True, 0), (1024, 0, False, 300), (65, 2, True, 1), (1, 0, False, 64)],
+         "relate": [0, 441, 7, 1, 300, 64, 256]}
 
 
 def step(call, wins, k=0, gf=0, note="", **kw):
@@ -158,6 +162,8 @@ def step(call, wins, k=0, gf=0, note="", **kw):
     elif call == "compare":
         # every other window holds PCM that differs in 1 + k % 3 elements; which windows alternates from one compare step to the next
         s["flips"] = {i: [((i + j) % SPEC_OF(wins[i][0])[0], (3 * k + 11 * j) % wins[i][2]) for j in range(1 + k % 3)] for i in range(W) if (i + k) % 2 == 0}
+    elif call in SPECS:
+        s["specs"] = [SPECS[call][(k + i) % len(SPECS[call])] for i in range(W)]
     s.update(kw)
     return s
 
@@ -390,6 +396,66 @@ def scenario_e():
 def scenario_f():
     """(context A's list, context B's): (a)'s calls, B's on other streams with other parameters"""
     return scenario_a(0), scenario_a(2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# histogram and relate: their counters and records lie in the context's scratch where the measure, digest and quiet calls keep their
+# accumulators, behind every pass's buffers.  Each runs before and after every other consumer, large, then small, then large again, and
+# behind failing calls
+
+def windows_of(k):
+    """an anchor over whole blocks of the largest shape and SPANS on four of the smaller streams, rotated from call to call"""
+    return [("loud", 1024, (9 - k % 3) * 1024 - 24)] + [(SMALL_STREAMS[(k + i) % 5], a, n) for i, (a, n) in enumerate(SPANS)]
+
+
+def scenario_between(x):
+    """x before and after every consumer that came before it"""
+    steps = [step(x, windows_of(0), k=0, note="the context's first call")]
+    for k, call in enumerate(CONSUMERS + list(LATER[:LATER.index(x)]), 1):
+        steps.append(step(call, windows_of(2 * k), k=k, note=f"behind the {x} call: its accumulators or samples where that call's tables lay"))
+        steps.append(step(x, windows_of(2 * k + 1), k=3 * k, gf=k % 2, note=f"behind {call}: its tables where that call's accumulators or scratch lay"))
+    return steps
+
+
+LARGE = {"histogram": ([(1024, 2, False, 0)], [(33, 0, True, 7)], [(1024, 2, False, 441)]), "relate": ([0], [7], [441])}
+
+
+def scenario_large_small_large(mat, x):
+    name = "mixed"
+    r = largest_block(mat, name)
+    first = mat.tables(name)[1][r]
+    whole, small = [(name, 0, num_samples(name))], [(name, first + 70, 64)]
+    big, few, passes = LARGE[x]
+    steps = [step(x, whole, specs=big, note="grows the scratch: samples of the whole stream, the slots of one long bucket"),
+             step(x, small, specs=few, note="its tables begin inside the whole-stream call's samples"),
+             step(x, whole, specs=passes, gf=1, note="many passes in one scratch, its tables where the small call's lay"),
+             step(x, small, specs=few, note="the same 64 samples again: the same answer"),
+             step(x, whole, specs=big, note="and the whole stream as at first")]
+    rng = np.random.default_rng(12)
+    wins = []
+    for i in range(64):
+        nm = NAMES[i % 6]
+        a = int(rng.integers(0, num_samples(nm) - 900))
+        wins.append((nm, a, int(rng.integers(1, 900))))
+    return steps + [step(x, wins, k=1, note="64 windows of every shape: long lists, tables of every window"),
+                    step(x, [(name, first + 5, 150)], k=3, note="one window: its tables inside the 64 windows' samples"),
+                    step(x, wins, k=4, note="the 64 windows with other specs")]
+
+
+def scenario_behind_failures(mat, x):
+    bl = mat.tables("loud")
+    k, r = mat.crc_block, mat.rice_block
+    good = [("mixed", 100, 900), ("three", 300, 1000)]
+    after = [("loud", 2000, 3000), ("mixed", 500, 2000), ("three", 0, 1500)]
+    return [step(x, [good[0], ("loud/rice", bl[1][r] + 10, 700), ("loud/rice", bl[1][r - 1] + 10, 700), good[1]], k=1, codes=[OK, NG, OK, OK],
+                 note="a window over a block whose Rice codes do not end where they should: its fail word is set on the device, its table is not committed"),
+            step(x, after, k=2, note="a good call behind it"),
+            step(x, [("loud/crc", bl[1][k] + 3, 600), good[0], ("loud/crc", 0, bl[1][k] - 24), ("loud", 1, num_samples("loud"))], k=2,
+                 codes=[CORRUPTION, OK, OK, INVALID_ARGUMENT], note="windows refused on the host, the others run"),
+            step(x, after, k=5, gf=2, note="a good call behind it"),
+            step(x, [(nm, 0, 50) for nm in mat.tiny], k=3, raises=NG, note="65 stream shapes: the call is refused as a whole"),
+            step(x, after, k=0, note="a good call behind it"),
+            step("measure", after, k=1, note="and a sibling behind that")]
 
 
 def entry_points(steps):

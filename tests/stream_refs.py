@@ -127,3 +127,53 @@ def expected_quiet(full, first, n, threshold, min_samples):
 def quiet_answer(q):
     """a QuietRuns in expected_quiet's form"""
     return q.cpu(), q.num_runs, q.quiet_samples, q.lead_samples, q.trail_samples
+
+
+# ---- histogram ----
+def bins_of(v, num_bins, shift, log2):
+    """the bin of every sample of v (any shape): m = |v| >> shift in 64 bits, x = m or m's bit length, min(x, num_bins - 1)"""
+    m = np.abs(np.asarray(v).astype(np.int64)) >> int(shift)
+    x = np.searchsorted(np.int64(1) << np.arange(33, dtype=np.int64), m, side="right") if log2 else m       # powers of two <= m: the bit length
+    return np.minimum(x, num_bins - 1)
+
+
+def expected_histogram(full, first, n, num_bins, shift=0, log2=False, b=0):
+    """the table LINNEAmd_HistogramWindowsDevice must write for window [first, first + n) of a stream that decodes to `full` (C, N),
+    with bucket length b (0: one bucket): int64 (C, nb, num_bins)"""
+    full = np.asarray(full)
+    step = b if b > 0 else max(n, 1)
+    nb = -(-n // step)
+    out = np.zeros((full.shape[0], nb, num_bins), dtype=np.int64)
+    for ch, row in enumerate(full[:, first:first + n]):
+        x = bins_of(row, num_bins, shift, log2)
+        for k in range(nb):
+            out[ch, k] = np.bincount(x[k * step:(k + 1) * step], minlength=num_bins)
+    return out
+
+
+# ---- a stream whose sum of squares passes 2^64 ----
+CARRY_BLOCK = 1024
+CARRY_NS = (1 << 18) + 1024
+CARRY_PEAK = (1 << 23) - 1
+
+
+def carry_signal():
+    """mono: a square wave between +-(2^23 - 1), 2^18 + 1024 samples -- its sum of squares is above 2^64"""
+    i = np.arange(CARRY_NS)
+    return np.where((i // 100) % 2 == 0, CARRY_PEAK, -CARRY_PEAK).astype(np.int32)[None, :]
+
+
+def carry_stream(oracle):
+    """carry_signal() as a 24-bit stream of RAW blocks of 1024 samples, written here: the header and the blocks' first two bytes are
+    those of the oracle's encode of as many zeros; a RAW block holds its samples zig-zagged, three bytes each, big-endian, behind
+    the size field (bytes 2..5: what follows them), the CRC16 over what follows it (bytes 6..7), the type and the sample count"""
+    x = carry_signal()
+    quiet = bytes(oracle.encode_whole(np.zeros_like(x), 24, 44100, CARRY_BLOCK, 0, False))
+    out = bytearray(quiet[:30])
+    for at in range(0, CARRY_NS, CARRY_BLOCK):
+        v = x[0, at:at + CARRY_BLOCK].astype(np.int64)
+        zz = np.where(v >= 0, 2 * v, -2 * v - 1)
+        payload = b"".join(int(u).to_bytes(3, "big") for u in zz)
+        body = bytes([2]) + len(v).to_bytes(2, "big") + payload
+        out += quiet[30:32] + (len(body) + 2).to_bytes(4, "big") + crc16(body).to_bytes(2, "big") + body
+    return bytes(out)

@@ -16,7 +16,8 @@ import linne_amd
 from linne_amd import PCM_F32, PCM_S16, PCM_S24, PCM_S32
 from signals import music
 from test_gpu_stream_encode import alternating
-from test_gpu_stream_windows import blocks, crc_damaged, mixed_signal, to_device
+from stream_consumers import crc_damaged, to_device
+from stream_refs import blocks, mixed_signal
 
 pytestmark = pytest.mark.gpu
 

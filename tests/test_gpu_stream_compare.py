@@ -14,8 +14,8 @@ from linne_amd import PCM_F32, PCM_S16, PCM_S24, PCM_S32
 from signals import music
 from test_cli_cpu import CLI, wav_bytes
 from test_gpu_pcm_layouts import device_pcm
-from stream_refs import expected_compare as expected
-from test_gpu_stream_windows import blocks, crc16, crc_damaged, mixed_signal, to_device
+from stream_consumers import Stream, crc_damaged, encoded, to_device
+from stream_refs import blocks, crc16, expected_compare as expected, mixed_signal
 
 pytestmark = pytest.mark.gpu
 
@@ -23,26 +23,6 @@ OK, INVALID_ARGUMENT, CORRUPTION, NG = 0, 1, 6, 7
 COMPRESS, SILENT, RAW = 0, 1, 2
 S = 1024
 TAIL = 300                                                       # (longer than 128 samples: presets 5-7 analyse it like any block)
-
-
-class Stream:
-    """a stream, the oracle's decode of its bytes, its device copy and index"""
-
-    def __init__(self, ctx, oracle, data, name=""):
-        self.name, self.stream = name, bytes(data)
-        ret, full, _ = oracle.decode_whole(self.stream)
-        assert ret == OK, name
-        self.full = np.ascontiguousarray(full, dtype=np.int32)
-        self.nch, self.ns = self.full.shape
-        self.bl = blocks(self.stream)
-        self.dev = to_device(self.stream)
-        self.index = ctx.index_stream(self.dev)
-
-
-def encoded(ctx, oracle, x, bits, preset, ms, name=""):
-    t = Stream(ctx, oracle, oracle.encode_whole(x, bits, 44100, S, preset, ms), name)
-    assert np.array_equal(t.full, x), name
-    return t
 
 
 def storage_bytes(t):

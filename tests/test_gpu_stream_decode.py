@@ -5,27 +5,12 @@ import numpy as np
 import pytest
 
 import linne_amd
-from signals import music
+from stream_refs import blocks, mixed_signal
 
 pytestmark = pytest.mark.gpu
 
 OK, INVALID_ARGUMENT, NG = 0, 1, 7
 COMPRESS, SILENT, RAW = 0, 1, 2
-
-
-def be(b):
-    return int.from_bytes(bytes(b), "big")
-
-
-def blocks(stream):
-    """(offset, bytes, type, samples, first sample) of the blocks DecodeWhole walks in a well-formed stream"""
-    ns, off, prog, out = be(stream[14:18]), 30, 0, []
-    while prog < ns and off + 11 <= len(stream):
-        size, typ, n = be(stream[off + 2:off + 6]), stream[off + 8], be(stream[off + 9:off + 11])
-        out.append((off, size + 6, typ, n, prog))
-        prog += n
-        off += size + 6
-    return out
 
 
 def decode(ctx, stream, first=0, n=None, index=None):
@@ -35,17 +20,6 @@ def decode(ctx, stream, first=0, n=None, index=None):
     except linne_amd.LinneAmdError as e:
         assert e.code is not None, str(e)
         return e.code, None
-
-
-def mixed_signal(nch, bits, ns, seed, block=4096):
-    """music with a silent stretch (SILENT blocks) and a stretch of full-scale noise (RAW blocks), each two blocks long"""
-    ns = max(ns, 7 * block)
-    x = music(nch, ns, bits, seed=seed).astype(np.int64)
-    x[:, block:3 * block] = 0
-    rng = np.random.default_rng(seed)
-    lim = 1 << (bits - 1)
-    x[:, 4 * block:6 * block] = rng.integers(-lim, lim, size=(nch, 2 * block))
-    return np.ascontiguousarray(x, dtype=np.int32)
 
 
 @pytest.fixture(scope="module")

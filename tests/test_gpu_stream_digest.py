@@ -13,11 +13,11 @@ import pytest
 
 import linne_amd
 from signals import music
+import stream_consumers as sc
+from stream_consumers import Stream, crc_damaged, encoded, to_device
+from stream_refs import CARRY_NS, carry_stream, digest_table as table, expected_digest, mixed_signal
 from test_cli_cpu import CLI
-from test_gpu_stream_compare import Stream, encoded
-from test_gpu_stream_windows import crc_damaged, mixed_signal, to_device
-from test_stream_digest_cpu import expected_digest, table, wav_data
-from test_stream_measure_cpu import CARRY_NS, carry_stream
+from test_stream_digest_cpu import wav_data
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +26,7 @@ COMPRESS, SILENT, RAW = 0, 1, 2
 S = 1024
 TAIL = 300
 BUCKETS = [0, 1, 7, 255, 256, 257, 441, 1024, 1025, 100000]
+DIGEST = sc.CONSUMERS["digest"]
 SHAPES = [(8, 1, False), (8, 2, False), (16, 1, False), (16, 2, True), (16, 8, False), (24, 1, False), (24, 2, True)]   # bits, channels, mid/side
 
 
@@ -140,109 +141,29 @@ def test_many_windows_of_mixed_shapes_in_one_call(ctx, streams):
 
 
 # 5 ------------------------------------------------------------------------------------------------------------------------------
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-
-
-def test_failures_stay_in_their_window_and_nothing_else_is_written(ctx, streams):
-    import torch
+def test_failures_stay_in_their_window_and_nothing_else_is_written(ctx, product, streams):
+    """64 windows of five stream shapes with mixed bucket lengths, failing ones among them; the buffer byte for byte"""
     t, u = streams[(16, 2)], streams[(8, 1)]
-    bad, k = crc_damaged(t)
-    assert 0 < k < len(t.bl) - 1
-    d_bad = to_device(bad)
-    bad_index = ctx.index_stream(d_bad)
-    at_k = t.bl[k][4]
-    # (stream, index, first, n, bucket, track, expected code, what is wrong with its spec)
-    cases = [(t.dev, t.index, 100, 2000, 300, t, OK, None),
-             (d_bad, bad_index, 0, at_k - 24, 64, t, OK, None),                      # before the damaged block
-             (d_bad, bad_index, at_k + 3, 600, 100, t, CORRUPTION, None),
-             (d_bad, bad_index, t.bl[k + 1][4], 200, 0, t, CORRUPTION, None),        # behind it
-             (t.dev, t.index, 0, 1000, 256, t, INVALID_ARGUMENT, "misaligned"),
-             (t.dev, t.index, 0, 1000, 0, t, INVALID_ARGUMENT, "null"),
-             (t.dev, t.index, 1, t.ns, 500, t, INVALID_ARGUMENT, None),              # a range beyond num_samples
-             (u.dev, u.index, 517, 1500, 0, u, OK, None),
-             (u.dev, u.index, 0, u.ns, 1000, u, OK, None)]
-    W = len(cases)
-    nbs = [1 if b == 0 else -(-n // b) for _, _, _, n, b, *_ in cases]
-    offs, at = [], 1
-    for nb in nbs:
-        offs.append(at)                                          # (a sentinel record in front of, between and behind the tables)
-        at += nb + 1
-    total = at
-
-    def call(which):
-        buf = torch.full((total, 2), SENTINEL, dtype=torch.int64, device="cuda")
-        w, sp = (linne_amd.Window * len(which))(), (linne_amd.DigestSpec * len(which))()
-        for j, i in enumerate(which):
-            dev, index, first, n, b, _, _, wrong = cases[i]
-            w[j].index, w[j].d_stream, w[j].first_sample, w[j].num_samples, w[j].d_pcm, w[j].pcm_stride, w[j].result = index.h, dev.data_ptr(), first, n, None, 0, -1
-            sp[j].bucket_samples, sp[j].d_out = b, buf.data_ptr() + 16 * offs[i]
-            if wrong == "misaligned":
-                sp[j].d_out = buf.data_ptr() + 16 * offs[i] + 4
-            elif wrong == "null":
-                sp[j].d_out = None
-        torch.cuda.synchronize()
-        ret = linne_amd.lib.LINNEAmd_DigestWindowsDevice(ctx.h, w, sp, len(which), 0)
-        return ret, [w[j].result for j in range(len(which))], buf.cpu().numpy().view(linne_amd.DIGEST_DTYPE).reshape(total)
-
-    def want_buffer(which):
-        """every record of the buffer: sentinels but the OK windows' buckets"""
-        buf = np.full((total, 2), SENTINEL, dtype=np.int64).view(linne_amd.DIGEST_DTYPE).reshape(total)
-        for i in which:
-            _, _, first, n, b, tr, code, _ = cases[i]
-            if code != OK:
-                continue
-            for j, (crc, size) in enumerate(expected_digest(tr.full, tr.bits, first, n, b)):
-                buf[offs[i] + j] = (crc, 0, size)
-        return buf
-
-    ret, codes, buf = call(range(W))
-    assert codes == [c[6] for c in cases]
-    assert ret == CORRUPTION                                     # the lowest failing window's
-    assert linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode().startswith(f"window 2: block {k} ")
-    assert buf.tobytes() == want_buffer(range(W)).tobytes()      # byte for byte: the tables, and sentinels everywhere else
-    for i in range(W):                                           # and every window alone: the same code, the same bytes
-        ret1, codes1, buf1 = call([i])
-        assert (ret1, codes1) == (cases[i][6], [cases[i][6]]), i
-        assert buf1.tobytes() == want_buffer([i]).tobytes(), i
-    # the Python form: codes, None for a failing window
-    four = [c[:4] for c in cases[:4]]
-    got, pcodes = ctx.digest_windows(four, bucket_samples=[c[4] for c in cases[:4]], return_codes=True)
-    assert pcodes == [OK, OK, CORRUPTION, CORRUPTION] and got[2] is None and got[3] is None
-    for i in (0, 1):
-        assert table(got[i]) == expected_digest(t.full, 16, cases[i][2], cases[i][3], cases[i][4])
-    with pytest.raises(linne_amd.LinneAmdError) as e:
-        ctx.digest_windows(four, bucket_samples=7)
-    assert e.value.code == CORRUPTION and e.value.codes == pcodes and "window 2:" in str(e.value)
-    bad_index.close()
+    crc, rice = sc.damaged(ctx, product, t)
+    (d_bad, bad_index, k), good = crc, (t.dev, t.index, 0, 1000, 2)
+    special = {**sc.rice_windows(t, rice, [(100,), (7,), (441,)]),
+               9: (d_bad, bad_index, t.bl[k][4] + 3, 600, 2, 100, None, CORRUPTION),
+               10: (d_bad, bad_index, 0, t.bl[k][4] - 24, 2, 64, None, OK),                        # before the damaged block
+               11: (d_bad, bad_index, t.bl[k + 1][4], 200, 2, 0, None, CORRUPTION),                # behind it
+               20: good + (256, "misaligned", INVALID_ARGUMENT),
+               22: good + (0, "null", INVALID_ARGUMENT),
+               40: (t.dev, t.index, 1, t.ns, 2, 500, None, INVALID_ARGUMENT),                      # a range beyond num_samples
+               41: (t.dev, t.index, 100, 2000, 2, 300, None, OK)}                                  # a good one, alone too
+    ts = [streams[key] for key in ((8, 1), (16, 2), (24, 2), (16, 8), (8, 2))]
+    items, tracks, codes = sc.many_windows(DIGEST, ctx, ts, t, lambda i: ([0, 1, 7, 64, 255, 256, 257, 441, 1024, 1025, 100000][(i * 3 + i // 16) % 11],), special, crc, rice)
+    for i in (2, 3, 43, 62):                                     # good windows of other shapes alone: the same code, the same bytes
+        ret1, codes1, buf1, offs1, nbs1 = sc.raw_call(DIGEST, ctx, [items[i]])
+        assert (ret1, codes1) == (OK, [OK]) and buf1.tobytes() == sc.want_buffer(DIGEST, len(buf1), [items[i]], [tracks[i]], [OK], offs1, nbs1).tobytes(), i
 
 
 # 6 ------------------------------------------------------------------------------------------------------------------------------
 def test_launch_counts(streams):
-    c = linne_amd.Context(0, use_torch_stream=False)
-    try:
-        c.enable_timing(True)
-        counts = {}
-        for t in (streams[(16, 2)], streams[(8, 1)]):
-            index = c.index_stream(t.dev)
-            for nw in (1, 64):
-                spans = [(0, t.ns)] + [(37 * i, t.ns - 53 * i) for i in range(1, nw)]
-                for gf in (0, 2):
-                    c.decode_windows([(t.dev, index, a, n) for a, n in spans], group_frames=gf)
-                    dec = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59)}
-                    got = c.digest_windows([(t.dev, index, a, n) for a, n in spans], bucket_samples=441, group_frames=gf)
-                    dig = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59, 79, 80, 81, 82, 83, 84, 85)}
-                    assert table(got[-1]) == expected_digest(t.full, t.bits, spans[-1][0], spans[-1][1], 441)
-                    assert dig[59] == dig[79] == dig[80] == dig[81] == dig[82] == 0 and dig[83] == dec[59] >= 1, (t.name, nw, gf, dec, dig)   # a launch per placing pass
-                    assert all(dig[k] == dec[k] for k in (28, 56, 57, 58)), (t.name, nw, gf, dec, dig)
-                    assert dig[84] == 1 and dig[85] == 1, (t.name, nw, gf, dig)                                   # the two launches per call
-                    assert c.last_ms(83) > 0
-                    counts[(t.name, nw, gf)] = dig
-                assert counts[(t.name, nw, 0)][83] == 1
-            assert counts[(t.name, 1, 0)] == counts[(t.name, 64, 0)]          # not a launch more for 64 windows than for one
-            assert counts[(t.name, 1, 2)][83] > 1                             # the window spans passes
-            index.close()
-    finally:
-        c.close()
+    sc.launch_counts(DIGEST, streams[(16, 2)], streams[(8, 1)], ((), {"bucket_samples": 441}), lambda t, w, d: check(t, [w], [441], [d]))
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------

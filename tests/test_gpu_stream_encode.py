@@ -10,7 +10,7 @@ import pytest
 import linne_amd
 from refs import _planar_ptrs
 from signals import music
-from test_gpu_stream_decode import blocks, mixed_signal
+from stream_refs import blocks, mixed_signal
 
 pytestmark = pytest.mark.gpu
 

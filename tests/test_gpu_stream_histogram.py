@@ -11,21 +11,19 @@ import pytest
 
 import linne_amd
 from signals import music
-from stream_refs import expected_quiet
+import stream_consumers as sc
+from stream_consumers import Stream, crc_damaged, encoded
+from stream_refs import CARRY_NS, bins_of, carry_stream, expected_histogram, expected_quiet, mixed_signal
 from test_cli_cpu import CLI
-from test_gpu_stream_compare import Stream, encoded
-from test_gpu_stream_windows import crc_damaged, to_device
-from test_stream_histogram_cpu import CONSTANT, S, TAIL, bins_of, constant_signal, expected_histogram
-from test_stream_measure_cpu import CARRY_NS, carry_stream
-from test_stream_quiet_cpu import mixed_signal, planted_signal
+from test_stream_histogram_cpu import CONSTANT, S, TAIL, constant_signal
+from test_stream_quiet_cpu import planted_signal
 
 pytestmark = pytest.mark.gpu
 
 OK, INVALID_ARGUMENT, CORRUPTION = 0, 1, 6
 COMPRESS, SILENT, RAW = 0, 1, 2
 SHAPES = [(nch, preset) for nch in (1, 2, 3) for preset in (0, 5)]
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HISTOGRAM = sc.CONSUMERS["histogram"]
 # (num_bins, shift, log2, bucket_samples): every bin count of {1, 2, 33, 64, 65, 1024}, every shift of {0, 4, 15, 31}, both scales, every
 # bucket length of {0, 1, 7, 255, 256, 257, 441, 1024, 5000}; a bucket of one sample goes with few bins, so that a table stays small
 SPECS = [(1, 0, False, 0), (2, 0, True, 255), (33, 0, True, 441), (64, 4, False, 256), (65, 4, True, 257), (1024, 0, False, 0), (1024, 4, False, 7), (1024, 15, False, 1024),
@@ -203,73 +201,13 @@ def test_long_buckets(ctx, oracle):
 
 
 # 6 ------------------------------------------------------------------------------------------------------------------------------
-PAD = 1                                                          # buckets a padded channel_stride leaves between the channels' rows
-GAP = 3                                                          # sentinel words in front of, between and behind the tables
-
-
-def raw_call(ctx, items, group_frames=0):
-    """LINNEAmd_HistogramWindowsDevice itself.  items: (stream, index, first, n, channels, num_bins, shift, scale, bucket_samples, what
-    is wrong with the spec); every window's table lies in one buffer of sentinels, its channels' rows PAD buckets apart -> (ret, codes,
-    the buffer as numpy, the tables' first words, the bucket counts, the bins a table has room for)"""
-    import torch
-    offs, nbs, rooms, at = [], [], [], GAP
-    for dev, index, first, n, nch, bins, shift, scale, b, wrong in items:
-        nb = 0 if n == 0 else (1 if b == 0 else -(-n // b))
-        room = bins if 1 <= bins <= 1024 else 4
-        offs.append(at)
-        nbs.append(nb)
-        rooms.append(room)
-        at += nch * (nb + PAD) * room + GAP
-    buf = torch.full((at,), SENTINEL, dtype=torch.int64, device="cuda")
-    W = len(items)
-    w, sp = (linne_amd.Window * W)(), (linne_amd.HistogramSpec * W)()
-    for j, (dev, index, first, n, nch, bins, shift, scale, b, wrong) in enumerate(items):
-        w[j].index, w[j].d_stream, w[j].first_sample, w[j].num_samples, w[j].d_pcm, w[j].pcm_stride, w[j].result = index.h, dev.data_ptr(), first, n, None, 0, -1
-        sp[j].bucket_samples, sp[j].num_bins, sp[j].shift, sp[j].scale, sp[j].reserved = b, bins, shift, scale, 1 if wrong == "reserved" else 0
-        sp[j].d_out, sp[j].channel_stride = buf.data_ptr() + 8 * offs[j] + (4 if wrong == "misaligned" else 0), nbs[j] + PAD
-        if wrong == "null":
-            sp[j].d_out = None
-        elif wrong == "stride":
-            sp[j].channel_stride = nbs[j] - 1
-    torch.cuda.synchronize()
-    ret = linne_amd.lib.LINNEAmd_HistogramWindowsDevice(ctx.h, w, sp, W, group_frames)
-    return ret, [w[j].result for j in range(W)], buf.cpu().numpy(), offs, nbs, rooms
-
-
-def want_buffer(words, items, fulls, codes, offs, nbs):
-    """sentinels but the OK windows' counts"""
-    buf = np.full(words, SENTINEL, dtype=np.int64)
-    for it, full, code, off, nb in zip(items, fulls, codes, offs, nbs):
-        if code != OK or it[3] == 0:
-            continue
-        _, _, first, n, nch, bins, shift, scale, b, _ = it
-        want = expected_histogram(full, first, n, bins, shift, bool(scale), b)
-        for ch in range(nch):
-            at = off + ch * (nb + PAD) * bins
-            buf[at:at + nb * bins] = want[ch].reshape(-1)
-    return buf
-
-
-def test_many_windows_and_failures_stay_in_their_window(ctx, streams, mixed):
-    """64 windows of four stream shapes and of specs that differ in every field, failing ones among them.  (Of the argument errors of a
-    window, nb > 2^32 - 1 cannot be reached: a stream's header holds a 32-bit sample count and a bucket has a sample or more.)"""
-    ts = [streams[(1, 0)], streams[(2, 5)], streams[(3, 0)], mixed]
+def test_many_windows_and_failures_stay_in_their_window(ctx, product, streams, mixed):
+    """64 windows of four stream shapes and of specs that differ in every field, failing ones among them"""
     t = streams[(2, 5)]
-    bad, k = crc_damaged(t)
-    assert 0 < k < len(t.bl) - 1
-    d_bad = to_device(bad)
-    bad_index = ctx.index_stream(d_bad)
-    rng = np.random.default_rng(4)
-    items, fulls = [], []
-    for i in range(64):
-        u = ts[i % 4]
-        first = int(rng.integers(0, u.ns))
-        n = int(rng.integers(1, u.ns - first + 1)) if i % 7 else 0
-        bins, shift, log2, b = SPECS[(i * 5 + i // 16) % len(SPECS)]
-        items.append((u.dev, u.index, first, n, u.nch, bins, shift, int(log2), b if b != 1 else 3, None))
-        fulls.append(u.full)
-    good = (t.dev, t.index, 0, 1000, 2)
-    special = {9: (d_bad, bad_index, t.bl[k][4] + 3, 600, 2, 64, 4, 0, 100, None, CORRUPTION),     # a failing window between good ones
+    crc, rice = sc.damaged(ctx, product, t)
+    (d_bad, bad_index, k), good = crc, (t.dev, t.index, 0, 1000, 2)
+    special = {**sc.rice_windows(t, rice, [(64, 4, 0, 100), (33, 0, 1, 7), (1024, 2, 0, 441)]),
+               9: (d_bad, bad_index, t.bl[k][4] + 3, 600, 2, 64, 4, 0, 100, None, CORRUPTION),     # a failing window between good ones
                10: (d_bad, bad_index, 0, t.bl[k][4] - 24, 2, 1024, 2, 0, 64, None, OK),            # in front of the damaged block
                11: (d_bad, bad_index, t.bl[k + 1][4], 200, 2, 33, 0, 1, 0, None, CORRUPTION),      # behind it
                20: good + (64, 0, 0, 256, "misaligned", INVALID_ARGUMENT),
@@ -282,72 +220,20 @@ def test_many_windows_and_failures_stay_in_their_window(ctx, streams, mixed):
                34: good + (64, 0, 0, 0, "reserved", INVALID_ARGUMENT),
                40: (t.dev, t.index, 1, t.ns, 2, 64, 0, 0, 500, None, INVALID_ARGUMENT),             # a range beyond num_samples
                41: good + (1024, 31, 1, 1000, None, OK), 42: good + (1, 0, 0, 1, None, OK)}         # the specs' extremes
-    want_codes = [OK] * 64
-    for i, sp in special.items():
-        items[i], fulls[i], want_codes[i] = sp[:10], t.full, sp[10]
-    ret, codes, buf, offs, nbs, _ = raw_call(ctx, items)
-    assert codes == want_codes and ret == CORRUPTION             # the lowest failing window's
-    text = linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode()
-    assert text.startswith(f"window 9: block {k} ")
-    assert np.array_equal(buf, want_buffer(len(buf), items, fulls, want_codes, offs, nbs))          # the tables, and sentinels everywhere else
-    ret2, codes2, buf2, *_ = raw_call(ctx, items, group_frames=2)
-    assert (ret2, codes2) == (ret, codes) and np.array_equal(buf2, buf)
-    # codes and text are the decode call's
-    _, dcodes = ctx.decode_windows([it[:4] for it in items[8:12]], return_codes=True)
-    assert dcodes == want_codes[8:12] and linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode() == text.replace("window 9:", "window 1:")
-    for i in sorted(special):                                    # alone: the same code, nothing written by a failing one
-        ret1, codes1, buf1, offs1, nbs1, _ = raw_call(ctx, [items[i]])
-        assert (ret1, codes1) == (want_codes[i], [want_codes[i]]), i
-        assert np.array_equal(buf1, want_buffer(len(buf1), [items[i]], [fulls[i]], [want_codes[i]], offs1, nbs1)), i
-        if want_codes[i] == INVALID_ARGUMENT and i != 40:
-            assert linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode().startswith("window 0: HistogramWindowsDevice: "), i
-    # the Python form
-    four = [it[:4] for it in items[8:12]]
-    spec4 = [[it[j] for it in items[8:12]] for j in (5, 6, 7, 8)]
-    got, pcodes = ctx.histogram_windows(four, *spec4, return_codes=True)
-    assert pcodes == want_codes[8:12] and got[1] is None and got[3] is None
-    for j in (0, 2):
-        it = items[8 + j]
-        assert np.array_equal(got[j].cpu(), expected_histogram(fulls[8 + j], it[2], it[3], it[5], it[6], bool(it[7]), it[8]))
-    with pytest.raises(linne_amd.LinneAmdError) as e:
-        ctx.histogram_windows(four, 64)
-    assert e.value.code == CORRUPTION and e.value.codes == pcodes and "window 1:" in str(e.value)
+
+    def fields(i):
+        bins, shift, log2, b = SPECS[(i * 5 + i // 16) % len(SPECS)]
+        return bins, shift, int(log2), b if b != 1 else 3
+
+    sc.many_windows(HISTOGRAM, ctx, [streams[(1, 0)], streams[(2, 5)], streams[(3, 0)], mixed], t, fields, special, crc, rice,
+                    faults={"reserved": lambda sp: setattr(sp, "reserved", 1)})
     _, pcodes = ctx.histogram_windows([good[:4]] * 3, [64, 1025, 0], return_codes=True)             # a refused num_bins gets no table
     assert pcodes == [OK, INVALID_ARGUMENT, INVALID_ARGUMENT]
-    assert ctx.histogram_windows([], 64) == [] and ctx.histogram_windows([], 64, return_codes=True) == ([], [])
-    empty = ctx.histogram_windows([(ts[2].dev, ts[2].index, 100, 0)], 64, bucket_samples=5)[0]      # no samples: no buckets
-    assert tuple(empty.counts.shape) == (3, 0, 64)
-    bad_index.close()
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------
 def test_launch_counts(mixed, streams):
-    three = streams[(3, 0)]
-    c = linne_amd.Context(0, use_torch_stream=False)
-    try:
-        c.enable_timing(True)
-        counts = {}
-        for t in (mixed, three):
-            index = c.index_stream(t.dev)
-            for nw in (1, 64):
-                spans = [(0, t.ns)] + [(37 * i, t.ns - 53 * i) for i in range(1, nw)]
-                for gf in (0, 2):
-                    c.decode_windows([(t.dev, index, a, n) for a, n in spans], group_frames=gf)
-                    dec = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59)}
-                    got = c.histogram_windows([(t.dev, index, a, n) for a, n in spans], 65, 3, False, 441, group_frames=gf)
-                    his = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59, 79, 80, 81, 82, 83, 86, 87, 92, 93, 94)}
-                    assert np.array_equal(got[-1].cpu(), expected_histogram(t.full, spans[-1][0], spans[-1][1], 65, 3, False, 441))
-                    assert his[59] == 0 and all(his[k] == 0 for k in (79, 80, 81, 82, 83, 86, 87)) and his[92] == dec[59] >= 1, (t.name, nw, gf, dec, his)
-                    assert all(his[k] == dec[k] for k in (28, 56, 57, 58)), (t.name, nw, gf, dec, his)
-                    assert his[93] == 1 and his[94] == 1, (t.name, nw, gf, his)                  # the two launches per call
-                    assert c.last_ms(92) > 0
-                    counts[(t.name, nw, gf)] = his
-                assert counts[(t.name, nw, 0)][92] == 1
-            assert counts[(t.name, 1, 0)] == counts[(t.name, 64, 0)]          # not a launch more for 64 windows than for one
-            assert counts[(t.name, 1, 2)][92] > 1                             # the window spans passes
-            index.close()
-    finally:
-        c.close()
+    sc.launch_counts(HISTOGRAM, mixed, streams[(3, 0)], ((65, 3, False, 441), {}), lambda t, w, h: check(t, [w], [(65, 3, False, 441)], [h]))
 
 
 # 8 ------------------------------------------------------------------------------------------------------------------------------

@@ -10,17 +10,21 @@ scratch with the consumers' accumulators behind it, the scan's and the splice's 
 
 When a step differs from its reference, the same call is made once more, alone, on a second fresh context, and the failure says
 whether that one agrees with the reference: if it does, the history is to blame."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
 import linne_amd
+import stream_consumers as sc
 import stream_history as sh
+from stream_consumers import last_error, to_device
 
 pytestmark = pytest.mark.gpu
 
 SENT32 = -123456789
 SENT64 = 0x5A5A5A5A5A5A5A5A
-KINDS = range(96)                       # every kernel kind of include/linne_amd.h (the last is 91)
+KINDS = range(max(sc.KIND.values()) + 1)     # every kernel kind of include/linne_amd.h
 
 
 @pytest.fixture(scope="module")
@@ -28,17 +32,8 @@ def mat(oracle):
     return sh.material(oracle)
 
 
-def to_device(data):
-    import torch
-    return torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
-
-
 def as_bytes(t):
     return bytes(t.cpu().numpy())
-
-
-def last_error(c):
-    return linne_amd.lib.LINNEAmd_GetLastError(c.h).decode()
 
 
 class Dev:
@@ -77,8 +72,13 @@ def channels(dev, name):
 def run_windows(c, dev, s, mat):
     """the step's call through its C entry point; asserts its codes, its answers and every byte of the buffer its tables lie in"""
     import torch
-    want = sh.expected(s, mat) if "raises" not in s else [None] * len(s["wins"])
     codes = s.get("codes") or [sh.OK] * len(s["wins"])
+    if "raises" in s:
+        want = [None] * len(s["wins"])
+    elif s["call"] in sh.LATER:                                  # (their references are the consumer table's, in want_buffer)
+        want = [True if code == sh.OK else None for code in codes]
+    else:
+        want = sh.expected(s, mat)
     W, gf, lib = len(s["wins"]), s["gf"], linne_amd.lib
     w = windows_array(dev, s)
     nch = [channels(dev, name) for name, _, _ in s["wins"]]
@@ -138,6 +138,15 @@ def run_windows(c, dev, s, mat):
                 for k, (crc, nbytes) in enumerate(want[j]):
                     wbuf[offs[j] + k] = (crc, 0, nbytes)
         got = buf.cpu().numpy().view(dtype).reshape(at)
+    elif s["call"] in sh.LATER:
+        # the bucket consumers' scaffold (stream_consumers.raw_call), the rows of a table adjacent and two sentinel words around it
+        c_, fields = sc.CONSUMERS[s["call"]], [(f[0], f[1], int(f[2]), f[3]) if s["call"] == "histogram" else (f,) for f in s["specs"]]
+        items = [(dev.t[name], dev.x[name], first, n, C, *f, None) for (name, first, n), C, f in zip(s["wins"], nch, fields)]
+        tracks = [SimpleNamespace(full=mat.full[name]) for name, _, _ in s["wins"]]
+        ret, results, got, offs, nbs = sc.raw_call(c_, c, items, gf, pad=0, gap=2)
+        for j in range(W):
+            w[j].result = results[j]
+        wbuf = sc.want_buffer(c_, len(got), items, tracks, codes, offs, nbs, pad=0)
     else:
         offs, at = [], 1
         for cap in s["caps"]:
@@ -264,6 +273,37 @@ def test_large_then_small_then_large_again(ctx_env, mat, name):
     """scenario (b): a whole stream, 64 samples through another consumer, the whole stream in one-block passes, the 64 samples again;
     64 windows of every shape, then one window"""
     run_list(ctx_env, mat, sh.scenario_b(mat)[name], name)
+
+
+@pytest.mark.parametrize("call", sh.LATER)
+def test_before_and_after_every_other_consumer(ctx_env, mat, call):
+    """histogram, then relate: before and after every consumer that came before it, on one context"""
+    with ctx_env({}) as c:
+        dev = Dev(c, mat)
+        for i, s in enumerate(sh.scenario_between(call)):
+            hold(ctx_env, mat, c, dev, s, f"{call} between the siblings, step {i}")
+            assert last_error(c) == ""
+        dev.close()
+
+
+@pytest.mark.parametrize("call", sh.LATER)
+def test_large_then_small_then_large_again_later(ctx_env, mat, call):
+    with ctx_env({}) as c:
+        dev = Dev(c, mat)
+        for i, s in enumerate(sh.scenario_large_small_large(mat, call)):
+            hold(ctx_env, mat, c, dev, s, f"{call} large, small, large, step {i}")
+            assert last_error(c) == ""
+        dev.close()
+
+
+@pytest.mark.parametrize("call", sh.LATER)
+def test_a_good_call_behind_a_failing_one(ctx_env, mat, call):
+    with ctx_env({}) as c:
+        dev = Dev(c, mat).need(mat.tiny)
+        for i, s in enumerate(sh.scenario_behind_failures(mat, call)):
+            hold(ctx_env, mat, c, dev, s, f"{call} behind failures, step {i}")
+        assert last_error(c) == ""
+        dev.close()
 
 
 def test_after_failures(ctx_env, mat):

@@ -10,7 +10,9 @@ import pytest
 
 import linne_amd
 from index_cases import SILENT_BLOCKS, build_corpus, index_walk
-from test_gpu_stream_windows import SHAPES, blocks, mixed_signal, to_device
+from stream_consumers import to_device
+from stream_refs import blocks, mixed_signal
+from test_gpu_stream_windows import SHAPES
 
 pytestmark = pytest.mark.gpu
 

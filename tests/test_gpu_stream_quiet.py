@@ -11,9 +11,9 @@ import pytest
 
 import linne_amd
 from signals import music
+import stream_consumers as sc
+from stream_consumers import Stream, crc_damaged, encoded, to_device
 from test_cli_cpu import CLI
-from test_gpu_stream_compare import Stream, encoded
-from test_gpu_stream_windows import crc_damaged, to_device
 from test_stream_quiet_cpu import (BASE_B, LONG_BLOCKS, MIXED_PLANTS, NS, S, TAIL, answer, expected_quiet, long_signal, made_loud, mixed_planted,
                                    planted_runs, planted_signal)
 
@@ -243,34 +243,9 @@ def test_many_windows_and_failures_stay_in_their_window(ctx, streams, mixed):
 def test_launch_counts(mixed, streams):
     header = open(os.path.join(ROOT, "include", "linne_amd.h")).read()
     extra = int(re.search(r"#define\s+LINNE_AMD_QUIET_EXTRA_LAUNCHES\s+(\d+)", header).group(1))
-    further = [87, 88, 89, 90, 91]
-    assert extra == len(further)
-    three = streams[(3, 0)]
-    c = linne_amd.Context(0, use_torch_stream=False)
-    try:
-        c.enable_timing(True)
-        counts = {}
-        for t in (mixed, three):
-            index = c.index_stream(t.dev)
-            for nw in (1, 64):
-                spans = [(0, t.ns)] + [(37 * i, t.ns - 53 * i) for i in range(1, nw)]
-                for gf in (0, 2):
-                    c.decode_windows([(t.dev, index, a, n) for a, n in spans], group_frames=gf)
-                    dec = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59)}
-                    got = c.quiet_windows([(t.dev, index, a, n) for a, n in spans], 0, 2, capacity=64, group_frames=gf)
-                    qui = {k: c.last_launches(k) for k in [28, 56, 57, 58, 59, 79, 80, 83, 86] + further}
-                    assert answer(got[-1]) == expected_quiet(t.full, spans[-1][0], spans[-1][1], 0, 2)
-                    assert qui[59] == 0 and qui[79] == qui[80] == qui[83] == 0 and qui[86] == dec[59] >= 1, (t.name, nw, gf, dec, qui)  # a launch per placing pass
-                    assert all(qui[k] == dec[k] for k in (28, 56, 57, 58)), (t.name, nw, gf, dec, qui)
-                    assert all(qui[k] == 1 for k in further) and sum(qui[k] for k in further) == extra, (t.name, nw, gf, qui)
-                    assert c.last_ms(86) > 0
-                    counts[(t.name, nw, gf)] = qui
-                assert counts[(t.name, nw, 0)][86] == 1
-            assert counts[(t.name, 1, 0)] == counts[(t.name, 64, 0)]          # not a launch more for 64 windows than for one
-            assert counts[(t.name, 1, 2)][86] > 1                             # the window spans passes
-            index.close()
-    finally:
-        c.close()
+    quiet = sc.CONSUMERS["quiet"]
+    assert extra == len(quiet.kinds) - 1
+    sc.launch_counts(quiet, mixed, streams[(3, 0)], ((0, 2), {"capacity": 64}), lambda t, w, q: check(t, [w], [0], [2], [q]))
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------

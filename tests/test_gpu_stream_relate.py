@@ -14,11 +14,10 @@ import linne_amd
 import synth_records as sr
 from relate_refs import CARRY_NS, CARRY_PEAK, bucket_lengths, carry_stereo_stream, dots, expected_relate, pairs
 from signals import music
-from stream_refs import crc16
+import stream_consumers as sc
+from stream_consumers import Stream, crc_damaged, encoded
+from stream_refs import mixed_signal
 from test_cli_cpu import CLI
-from test_gpu_stream_compare import Stream, encoded
-from test_gpu_stream_windows import crc_damaged, to_device
-from test_stream_quiet_cpu import mixed_signal
 from test_stream_relate_cpu import WIDE_SHAPE, first_wide_frame, wide_cases
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +28,7 @@ S = 1024
 TAIL = 300
 SHAPES = [(nch, preset) for nch in (1, 2, 3) for preset in (0, 5)]
 BUCKETS = [0, 1, 7, 64, 255, 256, 257, 1000, 1024, 5000]
-SENTINEL = 0x5A5A5A5A5A5A5A5A
+RELATE = sc.CONSUMERS["relate"]
 
 
 @pytest.fixture(scope="module")
@@ -192,90 +191,12 @@ def test_slots(ctx, oracle):
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------
-PAD = 1                                                          # buckets a padded pair_stride leaves between the pairs' rows
-GAP = 3                                                          # sentinel words in front of, between and behind the tables
-
-
-def raw_call(ctx, items, group_frames=0):
-    """LINNEAmd_RelateWindowsDevice itself.  items: (stream, index, first, n, channels, bucket_samples, what is wrong with the spec);
-    every window's table lies in one buffer of sentinels, its pairs' rows PAD buckets apart -> (ret, codes, the buffer as numpy, the
-    tables' first words, the bucket counts)"""
-    import torch
-    offs, nbs, at = [], [], GAP
-    for dev, index, first, n, nch, b, wrong in items:
-        nb = 0 if n == 0 else (1 if b == 0 else -(-n // b))
-        offs.append(at)
-        nbs.append(nb)
-        at += 4 * (nch * (nch + 1) // 2) * (nb + PAD) + GAP
-    buf = torch.full((at,), SENTINEL, dtype=torch.int64, device="cuda")
-    W = len(items)
-    w, sp = (linne_amd.Window * W)(), (linne_amd.RelateSpec * W)()
-    for j, (dev, index, first, n, nch, b, wrong) in enumerate(items):
-        w[j].index, w[j].d_stream, w[j].first_sample, w[j].num_samples, w[j].d_pcm, w[j].pcm_stride, w[j].result = index.h, dev.data_ptr(), first, n, None, 0, -1
-        sp[j].bucket_samples, sp[j].d_out, sp[j].pair_stride = b, buf.data_ptr() + 8 * offs[j] + (4 if wrong == "misaligned" else 0), nbs[j] + PAD
-        if wrong == "null":
-            sp[j].d_out = None
-        elif wrong == "stride":
-            sp[j].pair_stride = nbs[j] - 1
-    torch.cuda.synchronize()
-    ret = linne_amd.lib.LINNEAmd_RelateWindowsDevice(ctx.h, w, sp, W, group_frames)
-    return ret, [w[j].result for j in range(W)], buf.cpu().numpy(), offs, nbs
-
-
-def want_buffer(words, items, fulls, codes, offs, nbs):
-    """sentinels but the OK windows' records"""
-    buf = np.full(words, SENTINEL, dtype=np.int64)
-    for it, full, code, off, nb in zip(items, fulls, codes, offs, nbs):
-        if code != OK or it[3] == 0:
-            continue
-        want = expected_relate(full, it[2], it[3], it[5])
-        for p in range(want.shape[0]):
-            at = off + 4 * p * (nb + PAD)
-            buf[at:at + 4 * nb] = np.ascontiguousarray(want[p]).view(np.int64)
-    return buf
-
-
-def rice_damaged(product, t):
-    """(t's stream with a bit in the Rice codes of COMPRESS block k flipped and the block's CRC16 made right again, such that the whole
-    decode fails; k): the index finds nothing wrong with it, the device's Rice check does, and sets the window's fail word there"""
-    k = max(i for i, b in enumerate(t.bl[:-1]) if b[2] == COMPRESS and i > 0)
-    off, size = t.bl[k][:2]
-    rng = np.random.default_rng(77)
-    for _ in range(64):
-        bad = bytearray(t.stream)
-        p = off + 11 + (size - 11) // 2 + int(rng.integers(0, (size - 11) // 2))       # the later half of the payload: Rice codes
-        bad[p] ^= 1 << int(rng.integers(0, 8))
-        bad[off + 6:off + 8] = crc16(bad[off + 8:off + size]).to_bytes(2, "big")
-        if product.decode_whole(bytes(bad))[0] != OK:
-            return bytes(bad), k
-    raise AssertionError("no flip in 64 made the whole decode fail")
-
-
 def test_many_windows_and_failures_stay_in_their_window(ctx, product, streams, mixed):
-    """64 windows over three streams (and a damaged copy of one) with mixed bucket lengths, failing ones among them.  (Of the argument
-    errors of a window, nb > 2^32 - 1 cannot be reached: a stream's header holds a 32-bit sample count and a bucket has a sample or
-    more.)"""
-    ts = [streams[(1, 0)], streams[(2, 5)], streams[(3, 0)], mixed][1:]
+    """64 windows over three streams (and damaged copies of one) with mixed bucket lengths, failing ones among them"""
     t = streams[(2, 5)]
-    bad, k = crc_damaged(t)
-    assert 0 < k < len(t.bl) - 1
-    d_bad = to_device(bad)
-    bad_index = ctx.index_stream(d_bad)
-    riced, kr = rice_damaged(product, t)
-    d_rice = to_device(riced)
-    rice_index = ctx.index_stream(d_rice)                        # (the index takes the stream: its block heads and CRCs are right)
-    rng = np.random.default_rng(4)
-    items, fulls = [], []
-    for i in range(64):
-        u = ts[i % 3]
-        first = int(rng.integers(0, u.ns))
-        n = int(rng.integers(1, u.ns - first + 1)) if i % 7 else 0
-        items.append((u.dev, u.index, first, n, u.nch, (0, 3, 7, 64, 255, 256, 257, 441, 1000, 5000)[(i * 3 + i // 16) % 10], None))
-        fulls.append(u.full)
-    good = (t.dev, t.index, 0, 1000, 2)
-    special = {5: (d_rice, rice_index, t.bl[kr][4] + 10, 600, 2, 100, None, NG),                   # Rice damage: the fail word is set on the device,
-               6: (d_rice, rice_index, t.bl[kr - 1][4] + 10, 600, 2, 7, None, OK),                 # ... the commit skips that window alone; in front of it
-               7: (d_rice, rice_index, 0, t.ns, 2, 441, None, NG),                                 # the whole damaged stream
+    crc, rice = sc.damaged(ctx, product, t)
+    (d_bad, bad_index, k), good = crc, (t.dev, t.index, 0, 1000, 2)
+    special = {**sc.rice_windows(t, rice, [(100,), (7,), (441,)]),
                9: (d_bad, bad_index, t.bl[k][4] + 3, 600, 2, 100, None, CORRUPTION),               # CRC damage between good windows: refused on the host
                10: (d_bad, bad_index, 0, t.bl[k][4] - 24, 2, 64, None, OK),                        # in front of the damaged block
                11: (d_bad, bad_index, t.bl[k + 1][4], 200, 2, 0, None, CORRUPTION),                # behind it
@@ -284,72 +205,13 @@ def test_many_windows_and_failures_stay_in_their_window(ctx, product, streams, m
                22: good + (0, "null", INVALID_ARGUMENT),
                40: (t.dev, t.index, 1, t.ns, 2, 500, None, INVALID_ARGUMENT),                      # a range beyond the stream
                41: good + (1, None, OK)}
-    want_codes = [OK] * 64
-    for i, sp in special.items():
-        items[i], fulls[i], want_codes[i] = sp[:7], t.full, sp[7]
-    ret, codes, buf, offs, nbs = raw_call(ctx, items)
-    assert codes == want_codes and ret == NG                     # the lowest failing window's
-    text = linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode()
-    assert text.startswith(f"window 5: block {kr} ")
-    assert np.array_equal(buf, want_buffer(len(buf), items, fulls, want_codes, offs, nbs))          # the tables, and sentinels everywhere else
-    ret2, codes2, buf2, *_ = raw_call(ctx, items, group_frames=2)
-    assert (ret2, codes2) == (ret, codes) and np.array_equal(buf2, buf)
-    # codes and text are the decode call's
-    _, dcodes = ctx.decode_windows([it[:4] for it in items[8:12]], return_codes=True)
-    assert dcodes == want_codes[8:12] and linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode().startswith(f"window 1: block {k} ")
-    _, dcodes = ctx.decode_windows([it[:4] for it in items[4:8]], return_codes=True)
-    assert dcodes == want_codes[4:8] and linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode() == text.replace("window 5:", "window 1:")
-    for i in sorted(special):                                    # alone: the same code, nothing written by a failing one
-        ret1, codes1, buf1, offs1, nbs1 = raw_call(ctx, [items[i]])
-        assert (ret1, codes1) == (want_codes[i], [want_codes[i]]), i
-        assert np.array_equal(buf1, want_buffer(len(buf1), [items[i]], [fulls[i]], [want_codes[i]], offs1, nbs1)), i
-        if want_codes[i] == INVALID_ARGUMENT and i != 40:
-            assert linne_amd.lib.LINNEAmd_GetLastError(ctx.h).decode().startswith("window 0: RelateWindowsDevice: "), i
-    # the Python form
-    four = [it[:4] for it in items[8:12]]
-    got, pcodes = ctx.relate_windows(four, [it[5] for it in items[8:12]], return_codes=True)
-    assert pcodes == want_codes[8:12] and got[1] is None and got[3] is None
-    for j in (0, 2):
-        it = items[8 + j]
-        assert np.array_equal(got[j].cpu(), expected_relate(fulls[8 + j], it[2], it[3], it[5]))
-    with pytest.raises(linne_amd.LinneAmdError) as e:
-        ctx.relate_windows(four, 64)
-    assert e.value.code == CORRUPTION and e.value.codes == pcodes and "window 1:" in str(e.value)
-    assert ctx.relate_windows([]) == [] and ctx.relate_windows([], return_codes=True) == ([], [])
-    empty = ctx.relate_windows([(ts[1].dev, ts[1].index, 100, 0)], bucket_samples=5)[0]             # no samples: no buckets
-    assert tuple(empty.records.shape) == (6, 0, 4) and empty.cpu().shape == (6, 0)
-    bad_index.close()
-    rice_index.close()
+    sc.many_windows(RELATE, ctx, [streams[(2, 5)], streams[(3, 0)], mixed], t, lambda i: ((0, 3, 7, 64, 255, 256, 257, 441, 1000, 5000)[(i * 3 + i // 16) % 10],),
+                    special, crc, rice)
 
 
 # 8 ------------------------------------------------------------------------------------------------------------------------------
 def test_launch_counts(mixed, streams):
-    three = streams[(3, 0)]
-    c = linne_amd.Context(0, use_torch_stream=False)
-    try:
-        c.enable_timing(True)
-        counts = {}
-        for t in (mixed, three):
-            index = c.index_stream(t.dev)
-            for nw in (1, 64):
-                spans = [(0, t.ns)] + [(37 * i, t.ns - 53 * i) for i in range(1, nw)]
-                for gf in (0, 2):
-                    c.decode_windows([(t.dev, index, a, n) for a, n in spans], group_frames=gf)
-                    dec = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59)}
-                    got = c.relate_windows([(t.dev, index, a, n) for a, n in spans], 441, group_frames=gf)
-                    rel = {k: c.last_launches(k) for k in (28, 56, 57, 58, 59, 79, 80, 81, 82, 83, 86, 87, 92, 93, 94, 95, 96, 97)}
-                    assert np.array_equal(got[-1].cpu(), expected_relate(t.full, spans[-1][0], spans[-1][1], 441))
-                    assert rel[59] == 0 and all(rel[k] == 0 for k in (79, 80, 81, 82, 83, 86, 87, 92, 93, 94)) and rel[95] == dec[59] >= 1, (t.name, nw, gf, dec, rel)
-                    assert all(rel[k] == dec[k] for k in (28, 56, 57, 58)), (t.name, nw, gf, dec, rel)
-                    assert rel[96] == 1 and rel[97] == 1, (t.name, nw, gf, rel)                  # the two launches per call
-                    assert c.last_ms(95) > 0
-                    counts[(t.name, nw, gf)] = rel
-                assert counts[(t.name, nw, 0)][95] == 1
-            assert counts[(t.name, 1, 0)] == counts[(t.name, 64, 0)]          # not a launch more for 64 windows than for one
-            assert counts[(t.name, 1, 2)][95] > 1                             # the window spans passes
-            index.close()
-    finally:
-        c.close()
+    sc.launch_counts(RELATE, mixed, streams[(3, 0)], ((441,), {}), lambda t, w, r: check(t, [w], [441], [r]))
 
 
 # 9 ------------------------------------------------------------------------------------------------------------------------------

@@ -7,18 +7,14 @@ import numpy as np
 import pytest
 
 import linne_amd
-from stream_refs import be, blocks, crc16, mixed_signal  # noqa: F401  (other test modules import them from here)
+from stream_consumers import crc_damaged, to_device
+from stream_refs import blocks, crc16, mixed_signal
 
 pytestmark = pytest.mark.gpu
 
 OK, INVALID_ARGUMENT, CORRUPTION, NG = 0, 1, 6, 7
 COMPRESS, SILENT, RAW = 0, 1, 2
 NEW_KINDS = (56, 57, 58, 59)
-
-
-def to_device(stream):
-    import torch
-    return torch.from_numpy(np.frombuffer(stream, dtype=np.uint8).copy()).cuda()
 
 
 class Track:
@@ -184,15 +180,6 @@ def codes_alone(ctx, wins):
         except linne_amd.LinneAmdError as e:
             out.append(e.code)
     return out
-
-
-def crc_damaged(t):
-    """(the track's stream with a payload byte of block k flipped, so that the block's CRC fails; k)"""
-    k = len(t.bl) // 2
-    off, size = t.bl[k][:2]
-    bad = bytearray(t.stream)
-    bad[off + size - 2] ^= 0x10
-    return bytes(bad), k
 
 
 def test_damage_stays_in_its_window(ctx, corpus):

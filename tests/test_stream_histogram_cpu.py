@@ -17,7 +17,7 @@ import pytest
 
 import linne_amd
 from signals import music
-from stream_refs import blocks, mixed_signal
+from stream_refs import bins_of, blocks, expected_histogram, mixed_signal  # noqa: F401
 from test_cli_cpu import CLI
 from test_windows_plan_cpu import slots, stream as plan_stream
 
@@ -29,27 +29,6 @@ S = 1024
 TAIL = 300
 CONSTANT = 1000                             # the constant track's value
 LO, HI = -(1 << 31), (1 << 31) - 1
-
-
-def bins_of(v, num_bins, shift, log2):
-    """the bin of every sample of v (any shape): m = |v| >> shift in 64 bits, x = m or m's bit length, min(x, num_bins - 1)"""
-    m = np.abs(np.asarray(v).astype(np.int64)) >> int(shift)
-    x = np.searchsorted(np.int64(1) << np.arange(33, dtype=np.int64), m, side="right") if log2 else m       # powers of two <= m: the bit length
-    return np.minimum(x, num_bins - 1)
-
-
-def expected_histogram(full, first, n, num_bins, shift=0, log2=False, b=0):
-    """the table LINNEAmd_HistogramWindowsDevice must write for window [first, first + n) of a stream that decodes to `full` (C, N),
-    with bucket length b (0: one bucket): int64 (C, nb, num_bins)"""
-    full = np.asarray(full)
-    step = b if b > 0 else max(n, 1)
-    nb = -(-n // step)
-    out = np.zeros((full.shape[0], nb, num_bins), dtype=np.int64)
-    for ch, row in enumerate(full[:, first:first + n]):
-        x = bins_of(row, num_bins, shift, log2)
-        for k in range(nb):
-            out[ch, k] = np.bincount(x[k * step:(k + 1) * step], minlength=num_bins)
-    return out
 
 
 def constant_signal(nch, ns, value=CONSTANT):

@@ -9,7 +9,7 @@ on the device: that comparison needs the GPU and is marked so."""
 import pytest
 
 import index_cases as ic
-from test_gpu_stream_windows import blocks
+from stream_refs import blocks
 
 
 def agree(name, data, product):

@@ -14,37 +14,13 @@ import pytest
 import linne_amd
 from signals import music
 from test_cli_cpu import CLI
-from stream_refs import blocks, crc16, expected_measure, measure_table as table, mixed_signal  # noqa: F401  (the GPU tests import them from here)
+from stream_refs import CARRY_NS, CARRY_PEAK, blocks, carry_signal, carry_stream, crc16, expected_measure, measure_table as table, mixed_signal  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, INVALID_ARGUMENT = 0, 1
 COMPRESS, SILENT, RAW = 0, 1, 2
 S = 1024
 TAIL = 300
-CARRY_NS = (1 << 18) + 1024
-CARRY_PEAK = (1 << 23) - 1
-
-
-def carry_signal():
-    """mono: a square wave between +-(2^23 - 1), 2^18 + 1024 samples -- its sum of squares is above 2^64"""
-    i = np.arange(CARRY_NS)
-    return np.where((i // 100) % 2 == 0, CARRY_PEAK, -CARRY_PEAK).astype(np.int32)[None, :]
-
-
-def carry_stream(oracle):
-    """carry_signal() as a 24-bit stream of RAW blocks of 1024 samples, written here: the header and the blocks' first two bytes are
-    those of the oracle's encode of as many zeros; a RAW block holds its samples zig-zagged, three bytes each, big-endian, behind
-    the size field (bytes 2..5: what follows them), the CRC16 over what follows it (bytes 6..7), the type and the sample count"""
-    x = carry_signal()
-    quiet = bytes(oracle.encode_whole(np.zeros_like(x), 24, 44100, S, 0, False))
-    out = bytearray(quiet[:30])
-    for at in range(0, CARRY_NS, S):
-        v = x[0, at:at + S].astype(np.int64)
-        zz = np.where(v >= 0, 2 * v, -2 * v - 1)
-        payload = b"".join(int(u).to_bytes(3, "big") for u in zz)
-        body = bytes([RAW]) + len(v).to_bytes(2, "big") + payload
-        out += quiet[30:32] + (len(body) + 2).to_bytes(4, "big") + crc16(body).to_bytes(2, "big") + body
-    return bytes(out)
 
 
 def run(*args):

@@ -12,37 +12,13 @@ Peak device memory of a call = torch's peak allocation during it plus what the c
 and after, on a fresh context, less what torch's allocator reserved).  Kinds 79 and 59 are HIP events around k_wx_compare and
 k_wx_place in a compare_windows and a decode_windows call over the same windows (one pass each).  Prints one JSON line
 (profiles/stream_compare.json holds the MI355X's)."""
-import argparse, json, os, statistics, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import json
+import stream_timing as st                     # (first: it puts the repository's root on the path)
 import torch
 import linne_amd
-from bench import synth_track
+from stream_timing import bits, block, dev, preset, rate, verdict
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--minutes", type=float, default=60.0)
-ap.add_argument("--clips", type=int, default=256)
-ap.add_argument("--clip-seconds", type=float, default=5.0)
-ap.add_argument("--reps", type=int, default=9)
-args = ap.parse_args()
-nch, bits, rate, block, preset = 2, 16, 44100, 10240, 7
-dev = torch.device("cuda", 0)
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def stats(ts):
-    return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "spread_ms": round(max(ts) - min(ts), 3)}
-
-
-def verdict(ok, text):
-    return ("met: " if ok else "MISSED: ") + text
+args = st.arguments()
 
 
 def case(streams, pcms):
@@ -79,46 +55,23 @@ def case(streams, pcms):
 
     forms = {"verify_streams": new, "recipe_equal_per_stream": recipe, "recipe_one_equal": recipe_one_equal}
     out = {"streams": len(streams), "decoded_pcm_bytes": decoded_bytes, "pcm": f"{str(pcms[0].dtype).split('.')[-1]}, strides {tuple(pcms[0].stride())}"}
-    # answers, and the peak memory of each form on a context of its own
-    answers, peaks = {}, {}
-    for name, fn in forms.items():
-        torch.cuda.synchronize(); torch.cuda.empty_cache()
-        c = linne_amd.Context(0, use_torch_stream=True)
-        free0, res0, alloc0 = torch.cuda.mem_get_info(dev)[0], torch.cuda.memory_reserved(dev), torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        answers[name] = fn(c)
-        torch.cuda.synchronize()
-        torch_peak = torch.cuda.max_memory_allocated(dev) - alloc0
-        scratch = (free0 - torch.cuda.mem_get_info(dev)[0]) - (torch.cuda.memory_reserved(dev) - res0)
-        peaks[name] = {"torch_peak_bytes": int(torch_peak), "context_scratch_bytes": int(max(scratch, 0)), "peak_bytes": int(torch_peak + max(scratch, 0))}
-        c.close()
+    answers, peaks = st.peak_memory(forms)
     out["answers"] = {"verify_streams_all_identical": all(a == (0, 0, 0, None) for a in answers["verify_streams"]),
                       "recipe_equal_per_stream": bool(answers["recipe_equal_per_stream"]), "recipe_one_equal": bool(answers["recipe_one_equal"])}
     out["peak_memory"] = peaks
-    # times, the three forms in turn
     ctx = linne_amd.Context(0, use_torch_stream=True)
-    for fn in forms.values():
-        fn(ctx)
-    ts = {name: [] for name in forms}
-    for _ in range(args.reps):
-        for name, fn in forms.items():
-            ts[name].append(timed(lambda: fn(ctx)))
-    for name in forms:
-        out[name] = stats(ts[name])
+    out.update(st.repetitions(ctx, forms, args.reps))
     # kinds 79 and 59 over the same windows, one pass each
     idx = ctx.index_streams(streams)
+    wins = st.whole(streams, idx)
+
+    def check(n):
+        assert n(79) == 1 and n(59) == 0
+    held = [w + (p,) for w, p in zip(wins, pcms)]
+    mine = (lambda: ctx.compare_windows(held), check, [(79, "kind_79_k_wx_compare"), (0, "compare_windows_device_ms")])
     ctx.enable_timing(True)
-    k79, k59, calls = [], [], {}
-    for _ in range(args.reps + 1):
-        ctx.compare_windows([(s, x, 0, None, p) for s, x, p in zip(streams, idx, pcms)])
-        assert ctx.last_launches(79) == 1 and ctx.last_launches(59) == 0
-        k79.append(ctx.last_ms(79)); calls.setdefault("compare_windows_device_ms", []).append(ctx.last_ms(0))
-        ctx.decode_windows([(s, x, 0, None) for s, x in zip(streams, idx)])
-        assert ctx.last_launches(59) == 1 and ctx.last_launches(79) == 0
-        k59.append(ctx.last_ms(59)); calls.setdefault("decode_windows_device_ms", []).append(ctx.last_ms(0))
+    out.update(st.kind_timings(ctx, [mine, st.decode_step(ctx, wins, 79)], args.reps))
     ctx.enable_timing(False)
-    out["kind_79_k_wx_compare"], out["kind_59_k_wx_place"] = stats(k79[1:]), stats(k59[1:])
-    out.update({k: stats(v[1:]) for k, v in calls.items()})
     for x in idx:
         x.close()
     ctx.close()
@@ -138,20 +91,18 @@ def case(streams, pcms):
     return out
 
 
-result = {"config": f"44.1 kHz int16 stereo, -m {preset}, block {block}, MS", "reps": args.reps,
-          "statistic": "median (min, max, spread = max - min) ms of the runs, warm-up excluded, each run ends in a device synchronise; the forms of a case alternate within a repetition",
-          "recipe_library": "this build: its decode path is the parent commit's, launch for launch"}
+result = st.preamble(args)
 enc = linne_amd.Context(0, use_torch_stream=True)
-x = synth_track(int(args.minutes * 60 * rate), nch, bits, 3, dev, rate=float(rate))
+x = st.track(int(args.minutes * 60 * rate), 3)
 s = enc.encode_stream(x, bits, rate, block, preset, True).clone()
-result["one_stream"] = dict(case([s], [x]), stream=f"{args.minutes:g} min (BASELINE configs[1]), int32 planar PCM")
+result["one_stream"] = dict(case([s], [x]), stream=st.one_stream_label(args) + ", int32 planar PCM")
 del x, s
 n = int(args.clip_seconds * rate)
 clips = []
 for t in range(args.clips):
-    y = synth_track(n, nch, bits, 100 + t, dev, rate=float(rate))
+    y = st.track(n, 100 + t)
     clips.append(y.to(torch.int16).T.contiguous().T)               # interleaved int16: channel stride 1, sample stride 2
 streams = [t.clone() for t in enc.encode_streams([(p, bits, rate, block, preset, True) for p in clips])]
 enc.close()
-result["clips"] = dict(case(streams, clips), stream=f"{args.clips} x {args.clip_seconds:g} s, interleaved int16 PCM")
+result["clips"] = dict(case(streams, clips), stream=st.clips_label(args) + ", interleaved int16 PCM")
 print(json.dumps(result))

@@ -11,37 +11,11 @@ min.  Peak device memory of a call = torch's peak allocation during it plus what
 before and after, on a fresh context, less what torch's allocator reserved).  Kinds 80, 59 and 79 are HIP events around k_wx_measure,
 k_wx_place and k_wx_compare in a measure_windows, a decode_windows and a compare_windows call over the same windows (one pass
 each).  Prints one JSON line (profiles/stream_measure.json holds the MI355X's)."""
-import argparse, json, os, statistics, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
-import linne_amd
-from bench import synth_track
+import stream_timing as st
+from stream_timing import verdict
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--minutes", type=float, default=60.0)
-ap.add_argument("--clips", type=int, default=256)
-ap.add_argument("--clip-seconds", type=float, default=5.0)
-ap.add_argument("--reps", type=int, default=9)
-args = ap.parse_args()
-nch, bits, rate, block, preset = 2, 16, 44100, 10240, 7
-dev = torch.device("cuda", 0)
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def stats(ts):
-    return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "spread_ms": round(max(ts) - min(ts), 3)}
-
-
-def verdict(ok, text):
-    return ("met: " if ok else "MISSED: ") + text
+args = st.arguments()
 
 
 def reduce4(x):
@@ -69,97 +43,32 @@ def same(m, r):
 
 
 def case(streams, b):
-    decoded_bytes = 0
+    forms = {"measure_streams": lambda c: c.measure_streams(streams, bucket_samples=b), "recipe": st.recipe_of(streams, lambda g: torch_measure(g, b))}
 
-    def new(c):
-        return c.measure_streams(streams, bucket_samples=b)
+    def head(answers):
+        return {"streams": len(streams), "bucket_samples": b, "buckets_per_stream": int(answers[0].min.shape[1])}
 
-    def recipe(c):
-        idx = c.index_streams(streams)
-        got = c.decode_windows([(s, x, 0, None) for s, x in zip(streams, idx)])
-        out = [torch_measure(g, b) for g in got]
-        for x in idx:
-            x.close()
-        return out
+    def loops(ctx, wins, out):
+        """kinds 80, 59 and 79 over the same windows, one pass each"""
+        def check(n):
+            assert n(80) == 1 and n(59) == 0 and n(81) == 1 and n(82) == 1
+        mine = (lambda: ctx.measure_windows(wins, bucket_samples=b), check,
+                [(80, "kind_80_k_wx_measure"), (0, "measure_windows_device_ms"), (81, "kind_81_preset"), (82, "kind_82_commit")])
+        return [[mine, st.decode_step(ctx, wins, 80), st.compare_step(ctx, wins, ctx.decode_windows(wins))]]
 
-    forms = {"measure_streams": new, "recipe": recipe}
-    answers, peaks = {}, {}
-    for name, fn in forms.items():
-        torch.cuda.synchronize(); torch.cuda.empty_cache()
-        c = linne_amd.Context(0, use_torch_stream=True)
-        free0, res0, alloc0 = torch.cuda.mem_get_info(dev)[0], torch.cuda.memory_reserved(dev), torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        answers[name] = fn(c)
-        torch.cuda.synchronize()
-        torch_peak = torch.cuda.max_memory_allocated(dev) - alloc0
-        scratch = (free0 - torch.cuda.mem_get_info(dev)[0]) - (torch.cuda.memory_reserved(dev) - res0)
-        peaks[name] = {"torch_peak_bytes": int(torch_peak), "context_scratch_bytes": int(max(scratch, 0)), "peak_bytes": int(torch_peak + max(scratch, 0))}
-        c.close()
-    out = {"streams": len(streams), "bucket_samples": b, "buckets_per_stream": int(answers["measure_streams"][0].min.shape[1])}
-    out["answers_equal"] = all(same(m, r) for m, r in zip(answers["measure_streams"], answers["recipe"]))
-    out["peak_memory"] = peaks
-    ctx = linne_amd.Context(0, use_torch_stream=True)
-    idx = ctx.index_streams(streams)
-    decoded_bytes = sum(4 * x.header["num_channels"] * x.header["num_samples"] for x in idx)
-    out["decoded_pcm_bytes"] = decoded_bytes
-    for fn in forms.values():
-        fn(ctx)
-    ts = {name: [] for name in forms}
-    for _ in range(args.reps):
-        for name, fn in forms.items():
-            ts[name].append(timed(lambda: fn(ctx)))
-    for name in forms:
-        out[name] = stats(ts[name])
-    # kinds 80, 59 and 79 over the same windows, one pass each
-    wins = [(s, x, 0, None) for s, x in zip(streams, idx)]
-    pcms = ctx.decode_windows(wins)
-    ctx.enable_timing(True)
-    k80, k59, k79, calls = [], [], [], {}
-    for _ in range(args.reps + 1):
-        ctx.measure_windows(wins, bucket_samples=b)
-        assert ctx.last_launches(80) == 1 and ctx.last_launches(59) == 0 and ctx.last_launches(81) == 1 and ctx.last_launches(82) == 1
-        k80.append(ctx.last_ms(80)); calls.setdefault("measure_windows_device_ms", []).append(ctx.last_ms(0))
-        calls.setdefault("kind_81_preset", []).append(ctx.last_ms(81)); calls.setdefault("kind_82_commit", []).append(ctx.last_ms(82))
-        ctx.decode_windows(wins)
-        assert ctx.last_launches(59) == 1 and ctx.last_launches(80) == 0
-        k59.append(ctx.last_ms(59)); calls.setdefault("decode_windows_device_ms", []).append(ctx.last_ms(0))
-        ctx.compare_windows([w + (p,) for w, p in zip(wins, pcms)])
-        assert ctx.last_launches(79) == 1
-        k79.append(ctx.last_ms(79))
-    ctx.enable_timing(False)
-    out["kind_80_k_wx_measure"], out["kind_59_k_wx_place"], out["kind_79_k_wx_compare"] = stats(k80[1:]), stats(k59[1:]), stats(k79[1:])
-    out.update({k: stats(v[1:]) for k, v in calls.items()})
-    del pcms
-    for x in idx:
-        x.close()
-    ctx.close()
-    slack = max(out["measure_streams"]["spread_ms"], out["recipe"]["spread_ms"])
-    saved = peaks["recipe"]["peak_bytes"] - peaks["measure_streams"]["peak_bytes"]
-    slack80 = max(out["kind_80_k_wx_measure"]["spread_ms"], out["kind_59_k_wx_place"]["spread_ms"])
-    out["criteria"] = {
-        "faster_than_the_recipe_beyond_the_spread": verdict(out["measure_streams"]["median_ms"] + slack < out["recipe"]["median_ms"],
-                                                            f"measure_streams {out['measure_streams']['median_ms']} ms against the recipe's {out['recipe']['median_ms']} ms (spread {slack} ms)"),
-        "peak_memory_lower_by_about_the_decoded_pcm": verdict(saved >= 0.9 * decoded_bytes,
-                                                              f"{peaks['measure_streams']['peak_bytes']} bytes against {peaks['recipe']['peak_bytes']}: {saved} fewer, the decoded PCM is {decoded_bytes}"),
-        "kind_80_not_slower_than_kind_59": verdict(out["kind_80_k_wx_measure"]["median_ms"] <= out["kind_59_k_wx_place"]["median_ms"] + slack80,
-                                                   f"{out['kind_80_k_wx_measure']['median_ms']} ms against {out['kind_59_k_wx_place']['median_ms']} ms (spread {slack80} ms); k_wx_compare {out['kind_79_k_wx_compare']['median_ms']} ms"),
-    }
-    return out
+    def criteria(out, peaks):
+        saved = peaks["recipe"]["peak_bytes"] - peaks["measure_streams"]["peak_bytes"]
+        decoded_bytes = out["decoded_pcm_bytes"]
+        slack80 = max(out["kind_80_k_wx_measure"]["spread_ms"], out["kind_59_k_wx_place"]["spread_ms"])
+        return {
+            "faster_than_the_recipe_beyond_the_spread": st.faster_than(out, "measure_streams"),
+            "peak_memory_lower_by_about_the_decoded_pcm": verdict(saved >= 0.9 * decoded_bytes,
+                                                                  f"{peaks['measure_streams']['peak_bytes']} bytes against {peaks['recipe']['peak_bytes']}: {saved} fewer, the decoded PCM is {decoded_bytes}"),
+            "kind_80_not_slower_than_kind_59": verdict(out["kind_80_k_wx_measure"]["median_ms"] <= out["kind_59_k_wx_place"]["median_ms"] + slack80,
+                                                       f"{out['kind_80_k_wx_measure']['median_ms']} ms against {out['kind_59_k_wx_place']['median_ms']} ms (spread {slack80} ms); k_wx_compare {out['kind_79_k_wx_compare']['median_ms']} ms"),
+        }
+
+    return st.case(streams, forms, head, same, loops, criteria, args.reps)
 
 
-result = {"config": f"44.1 kHz int16 stereo, -m {preset}, block {block}, MS", "reps": args.reps,
-          "statistic": "median (min, max, spread = max - min) ms of the runs, warm-up excluded, each run ends in a device synchronise; the forms of a case alternate within a repetition",
-          "recipe_library": "this build: its decode path is the parent commit's, launch for launch"}
-enc = linne_amd.Context(0, use_torch_stream=True)
-x = synth_track(int(args.minutes * 60 * rate), nch, bits, 3, dev, rate=float(rate))
-s = enc.encode_stream(x, bits, rate, block, preset, True).clone()
-del x
-result["one_stream"] = {"stream": f"{args.minutes:g} min (BASELINE configs[1])", "bucket_0": case([s], 0), "bucket_441": case([s], 441)}
-del s
-n = int(args.clip_seconds * rate)
-clips = [synth_track(n, nch, bits, 100 + t, dev, rate=float(rate)) for t in range(args.clips)]
-streams = [t.clone() for t in enc.encode_streams([(p, bits, rate, block, preset, True) for p in clips])]
-del clips
-enc.close()
-result["clips"] = {"stream": f"{args.clips} x {args.clip_seconds:g} s", "bucket_0": case(streams, 0), "bucket_441": case(streams, 441)}
-print(json.dumps(result))
+st.bucketed(args, case)
