@@ -413,6 +413,11 @@ enum LINNEAmdRelateTimingKind {
     LINNE_AMD_RELATE_T_PRESET = 96,         /* the call's accumulators zeroed, once, in front of the first pass (k_wx_relate_preset) */
     LINNE_AMD_RELATE_T_COMMIT = 97          /* the tables of the windows that did not fail written to their d_out, once, behind the last pass (k_wx_relate_commit) */
 };
+/* mixing the channels of windows (LINNEAmd_MixWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice, with a launch of this one wherever
+ * that call has one of kind 59, and nothing else) */
+enum LINNEAmdMixTimingKind {
+    LINNE_AMD_MIX_T_MIX = 98                /* every window's sample frames through its channel matrix into its output (k_wx_mix) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -883,6 +888,40 @@ struct LINNEAmdRelateSpec {
 };
 int LINNEAmd_RelateWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
         const struct LINNEAmdRelateSpec *specs /* [num_windows] */, uint32_t num_windows, uint32_t group_frames);
+
+/* ---- mixing the channels of windows of resident streams: a downmix, a channel swap, a polarity fix, on decode ----
+ * LINNEAmd_MixWindowsDevice takes the windows and layouts of LINNEAmd_DecodeWindowsDeviceLayout and writes, instead of every window's C
+ * channels, the Co = specs[i].out_channels channels its exact integer matrix makes of them.  With v[c] the values
+ * LINNEAmd_DecodeStreamDevice gives for a sample frame, output channel o of that frame is
+ *   1. the sum    acc = sum over c < C of (int64)coef[o][c] * v[c]   (a product is at most 2^46 in magnitude, eight of them 2^49:
+ *                 nothing wraps);
+ *   2. the shift  y = shift ? (acc + (1 << (shift - 1))) >> shift : acc, the shift arithmetic: halves round towards plus infinity;
+ *   3. the clip   y clipped to [-2^(B - 1), 2^(B - 1) - 1], B = clip_bits, or 32 where clip_bits is 0;
+ *   4. the layout's conversion of the clipped value, as LINNEAmd_DecodeWindowsDeviceLayout converts: S32 as it is, S16 and S24 saturated
+ *      to the format's range, F32 (float)y * 2^-(Bf - 1), Bf = clip_bits, or the stream's bits_per_sample where clip_bits is 0.
+ * layouts[i].saturated is 1 when step 3 or step 4 clipped an element of window i, otherwise 0; a failing window's stays as it was.
+ * coef[o][c] with o >= Co or c >= C is never read into the result.  The identity matrix with shift 0 and clip_bits 0 writes what
+ * LINNEAmd_DecodeWindowsDeviceLayout writes.
+ * The rest of the contract is LINNEAmd_DecodeWindowsDeviceLayout's, word for word, with Co where that has the stream's channel count
+ * in what it says of the output (the elements written, the layout's checks -- injectivity, alignment --, pcm_stride >= num_samples
+ * when Co > 1 and layouts is NULL): per-window results ("window <i>: MixWindowsDevice: ..." for this call's own checks), a failing
+ * window's memory never written and the others undisturbed, the lowest failing window's code returned, shape groups (the stream's
+ * shape: windows of different C, Co and matrices share a pass), passes, group_frames, scratch, copies, the one host synchronisation
+ * and whole-call failures.  For window i alone INVALID_ARGUMENT when out_channels is outside 1 .. 8, shift > 31, clip_bits is 1 or
+ * above 32, or reserved is not 0.  A pass has the decode call's launches with kind 98 in place of kind 59 and nothing more, whatever
+ * num_windows is.  num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.
+ * Enqueued on the context's stream and synchronous. */
+struct LINNEAmdMixSpec {
+    uint32_t out_channels;              /* Co, 1 .. 8 */
+    uint32_t shift;                     /* 0 .. 31 */
+    uint32_t clip_bits;                 /* 0 (32), or 2 .. 32 */
+    uint32_t reserved;                  /* 0 */
+    int16_t coef[LINNE_MAX_NUM_CHANNELS][LINNE_MAX_NUM_CHANNELS];       /* [o][c] */
+};
+int LINNEAmd_MixWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdMixSpec *specs /* [num_windows] */,
+        struct LINNEAmdPcmLayout *layouts /* [num_windows] in/out; NULL: int32 planar, pcm_stride */,
+        uint32_t num_windows, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

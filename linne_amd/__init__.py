@@ -60,6 +60,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_MeasureWindowsDevice",
     "LINNEAmd_DigestWindowsDevice",
     "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice", "LINNEAmd_RelateWindowsDevice",
+    "LINNEAmd_MixWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -267,6 +268,12 @@ class RelateSpec(C.Structure):
     _fields_ = [("bucket_samples", C.c_uint64), ("d_out", C.c_void_p), ("pair_stride", C.c_uint64)]
 
 
+class MixSpec(C.Structure):
+    """struct LINNEAmdMixSpec (include/linne_amd.h)"""
+    _fields_ = [("out_channels", C.c_uint32), ("shift", C.c_uint32), ("clip_bits", C.c_uint32), ("reserved", C.c_uint32),
+                ("coef", (C.c_int16 * 8) * 8)]
+
+
 RELATION_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("num_equal", "<u8"), ("num_opposite", "<u8")])
 
 
@@ -275,6 +282,40 @@ def pair_index(C, i, j):
     C, i, j = int(C), int(i), int(j)
     assert 0 <= i <= j < C, "a pair is i <= j < C"
     return i * C - i * (i - 1) // 2 + (j - i)
+
+
+def downmix_matrix(C):
+    """the matrix and shift that make one channel, the mean, of C -> (matrix, shift) as mix_windows takes them: a row of ones and
+    shift log2(C) where C is a power of two (the shift's rounding is the mean's: halves towards plus infinity), otherwise a row of
+    round(2^15 / C) in Q15 and shift 15.  Pure host code"""
+    C = int(C)
+    assert 1 <= C <= 8, "1 .. 8 channels"
+    if C & (C - 1) == 0:
+        return ((1,) * C,), C.bit_length() - 1
+    return ((int(round(32768 / C)),) * C,), 15
+
+
+def select_matrix(C, channels):
+    """the matrix that keeps the given channels of C, in the given order (a channel may repeat) -> a tuple of rows of 0 and 1"""
+    C, channels = int(C), [int(c) for c in channels]
+    assert 1 <= C <= 8 and 1 <= len(channels) <= 8 and all(0 <= c < C for c in channels), "1 .. 8 channels out of C <= 8"
+    return tuple(tuple(int(c == k) for c in range(C)) for k in channels)
+
+
+def fix_matrix(findings):
+    """one bucket of channel_findings -> the matrix that acts on it: of an "identical" pair (i, j) channel j is dropped, of an
+    "inverted" pair channel j is negated; every other channel is kept as it is.  A pair with a channel already dropped changes
+    nothing further.  Pure host code"""
+    C = len(findings["channels"])
+    keep, sign = [True] * C, [1] * C
+    for (i, j), what in sorted(findings["pairs"].items()):
+        if not (keep[i] and keep[j]):
+            continue
+        if what == "identical":
+            keep[j] = False
+        elif what == "inverted":
+            sign[j] = -1
+    return tuple(tuple(sign[k] * int(c == k) for c in range(C)) for k in range(C) if keep[k])
 
 
 def _pair_channels(P):
@@ -469,6 +510,7 @@ def _load():
     L.LINNEAmd_QuietWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(QuietSpec), C.POINTER(Quiet), C.c_uint32, C.c_uint32]
     L.LINNEAmd_HistogramWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(HistogramSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_RelateWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(RelateSpec), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_MixWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MixSpec), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -869,10 +911,15 @@ class Context:
         or torch.int32 (the default); s24=True gives packed 3-byte little-endian samples (saturating) as uint8 tensors with a trailing
         dimension of 3; channels_last=True gives (n_w, C_w) windows, and says that `out` is (W, n, C).  `out` then has that dtype and
         any strides.  return_saturated appends the list of the windows' flags "a sample was clipped" to the result"""
+        return self._place_windows(windows, None, out, group_frames, return_codes, dtype, channels_last, s24, return_saturated)
+
+    def _place_windows(self, windows, specs, out, group_frames, return_codes, dtype, channels_last, s24, return_saturated):
+        """decode_windows (specs None) and mix_windows (specs: the windows' MixSpec array, whose out_channels are the windows' channel
+        counts): the outputs, the layouts, the call and what it returns"""
         import torch
         W = len(windows)
         arr, keep, ranges = self._windows_array(windows)
-        shapes = [(x.header["num_channels"], max(n, 0)) for x, _, n in ranges]
+        shapes = [(x.header["num_channels"] if specs is None else int(specs[i].out_channels), max(n, 0)) for i, (x, _, n) in enumerate(ranges)]
         dev = f"cuda:{self.device}"
         if s24:
             assert dtype in (None, torch.uint8), "s24 samples are uint8 triples"
@@ -881,7 +928,7 @@ class Context:
             tdtype = torch.int32 if dtype is None else dtype
             assert tdtype in (torch.int32, torch.int16, torch.float32), "dtype is torch.int32, torch.int16 or torch.float32"
             fmt, esize = {torch.int32: (PCM_S32, 4), torch.int16: (PCM_S16, 2), torch.float32: (PCM_F32, 4)}[tdtype]
-        plain = fmt == PCM_S32 and not channels_last and not return_saturated and (out is None or out.dim() != 3 or out.stride(2) == 1 or out.shape[2] <= 1)
+        plain = specs is None and fmt == PCM_S32 and not channels_last and not return_saturated and (out is None or out.dim() != 3 or out.stride(2) == 1 or out.shape[2] <= 1)
         lays = (PcmLayout * max(W, 1))()
         cdim, sdim = (2, 1) if channels_last else (1, 2)
         if out is not None:
@@ -914,11 +961,73 @@ class Context:
         self._fence()
         if plain:
             ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
-        else:
+        elif specs is None:
             ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice", return_codes)
+        else:
+            ret = lib.LINNEAmd_MixWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice" if specs is None else "MixWindowsDevice", return_codes)
         res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
         return res[0] if len(res) == 1 else res
+
+    @staticmethod
+    def _mix_specs(indexes, matrix, shift, clip_bits):
+        """the MixSpec array of a mix call: matrix one (Co, C) integer array for all windows or a sequence of them, one per window;
+        shift and clip_bits one value or one per window.  Values outside int16 raise ValueError"""
+        W = len(indexes)
+        one = isinstance(matrix, np.ndarray) and matrix.ndim == 2 or (not isinstance(matrix, np.ndarray) and len(matrix) > 0 and np.ndim(matrix[0]) == 1)
+        mats = [matrix] * W if one else list(matrix)
+        assert len(mats) == W, "matrix is one (Co, C) array, or one per window"
+        per = lambda v: [int(v)] * W if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+        shifts, clips = per(shift), per(clip_bits)
+        assert len(shifts) == W and len(clips) == W, "shift and clip_bits are one value, or one per window"
+        specs = (MixSpec * max(W, 1))()
+        for i, (x, m) in enumerate(zip(indexes, mats)):
+            m = np.asarray(m)
+            if m.ndim != 2 or m.dtype.kind not in "iu" or not 1 <= m.shape[0] <= 8 or m.shape[1] != x.header["num_channels"]:
+                raise ValueError(f"window {i}: the matrix is an integer array (Co, {x.header['num_channels']}), Co 1 .. 8; got {m.dtype} {m.shape}")
+            if m.size and (int(m.min()) < -32768 or int(m.max()) > 32767):
+                raise ValueError(f"window {i}: a coefficient outside int16")
+            if shifts[i] < 0 or clips[i] < 0 or shifts[i] >= 1 << 32 or clips[i] >= 1 << 32:
+                raise ValueError(f"window {i}: shift and clip_bits are unsigned")
+            specs[i].out_channels, specs[i].shift, specs[i].clip_bits, specs[i].reserved = m.shape[0], shifts[i], clips[i], 0
+            for o in range(m.shape[0]):
+                for c in range(m.shape[1]):
+                    specs[i].coef[o][c] = int(m[o, c])
+        return specs
+
+    def mix_windows(self, windows, matrix, shift=0, clip_bits=0, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False,
+                    s24=False, return_saturated=False):
+        """decode_windows with an exact integer channel matrix between the samples and the PCM (include/linne_amd.h
+        LINNEAmd_MixWindowsDevice states the arithmetic): output channel o of a frame is sum_c matrix[o][c] * v[c] in 64 bits, shifted
+        right by `shift` with halves rounded up, clipped to clip_bits bits (0: 32), then converted as decode_windows converts (float32:
+        times 2^-(clip_bits - 1), or 2^-(bits - 1) of the stream where clip_bits is 0).  matrix: one (Co, C) integer array for all
+        windows, or a sequence of them, one per window; shift and clip_bits likewise one value or one per window; values outside int16
+        raise ValueError before any call.  Everything else -- windows, out, dtype, channels_last, s24, return_codes, return_saturated,
+        group_frames, errors -- is decode_windows', with Co channels where that has the stream's"""
+        specs = self._mix_specs([w[1] for w in windows], matrix, shift, clip_bits)
+        return self._place_windows(windows, specs, out, group_frames, return_codes, dtype, channels_last, s24, return_saturated)
+
+    def remix_streams(self, streams, matrix, shift=0, bits=None, preset=None, block=None, ms=None, group_frames=0):
+        """new .lnn streams whose channels are a matrix of the given streams' channels, without the PCM leaving the device: one
+        index_streams call, one mix_windows call over the whole streams into one int32 allocation (clip_bits = the output's bits) and
+        one encode_streams call.  matrix and shift as mix_windows takes them (one for all streams, or one per stream).  Every header
+        field not given (bits, preset, block, ms) is the source stream's; num_channels is the matrix' row count, and an output of one
+        channel does not inherit MS, which a mono header cannot carry.  -> a list of uint8 CUDA tensors"""
+        if len(streams) == 0:
+            return []
+        ts = [self._stream_bytes(s) for s in streams]
+        indexes = self.index_streams(ts)
+        try:
+            heads = [x.header for x in indexes]
+            obits = [int(bits) if bits is not None else h["bits_per_sample"] for h in heads]
+            pcms = self.mix_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], matrix, shift=shift, clip_bits=obits, group_frames=group_frames)
+            tracks = [(pcm, b, h["sampling_rate"], int(block) if block is not None else h["num_samples_per_block"],
+                       int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else (h["ch_process_method"] if pcm.shape[0] > 1 else 0))
+                      for pcm, b, h in zip(pcms, obits, heads)]
+            return self.encode_streams(tracks, group_frames=group_frames)
+        finally:
+            for x in indexes:
+                x.close()
 
     def compare_windows(self, windows, group_frames=0, return_codes=False):
         """many sample windows of resident .lnn streams compared with resident PCM in one call, nothing decoded into memory of the

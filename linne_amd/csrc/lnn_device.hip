@@ -55,6 +55,7 @@
 #include "lnn_k_quiet.h"
 #include "lnn_k_histogram.h"
 #include "lnn_k_relate.h"
+#include "lnn_k_mix.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -72,6 +73,7 @@ static_assert(LINNE_AMD_DIGEST_T_DIGEST == 83 && LINNE_AMD_DIGEST_T_COMMIT == 85
 static_assert(LINNE_AMD_QUIET_T_QUIET == 86 && LINNE_AMD_QUIET_T_ENDS == 91 && LINNE_AMD_QUIET_EXTRA_LAUNCHES == 5, "the quiet call's timing kinds are 86 to 91: the pass kind and five launches per call");
 static_assert(LINNE_AMD_HISTOGRAM_T_HISTOGRAM == 92 && LINNE_AMD_HISTOGRAM_T_COMMIT == 94, "the histogram call's timing kinds are 92 to 94");
 static_assert(LINNE_AMD_RELATE_T_RELATE == 95 && LINNE_AMD_RELATE_T_COMMIT == 97, "the relate call's timing kinds are 95 to 97");
+static_assert(LINNE_AMD_MIX_T_MIX == 98, "the mix call's timing kind is 98");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2243,9 +2245,9 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
 struct WxCall;
 /* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
  * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
-struct WxLaunch { const WxBucket *side; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The seven calls are the
- * seven constant instances below; a launch that a consumer does not have is NULL */
+struct WxLaunch { const WxBucket *side; const WxMix *mix; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The eight calls are the
+ * eight constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2259,28 +2261,29 @@ struct WxConsumer {
     int (*commit)(LINNEAmdContext *ctx, const WxLaunch &l);
     /* an OK window's answer into the caller's arrays; words: all that came back (fail words first), NULL for a window that took no pass */
     void (*read_back)(const WxCall &c, uint32_t i, const uint32_t *words);
+    bool mixes;                         /* a WxMix beside every window record, from the windows' struct LINNEAmdMixSpec (a consumer without buckets) */
 };
 struct WxCall {
     const WxConsumer *use;
     bool single;                        /* the call is LINNEAmd_DecodeStreamDevice, which its texts then name */
     struct LINNEAmdWindow *win; uint32_t W, group_frames;
-    const void *specs;                  /* [W] of the consumer's: place and compare struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet, histogram and relate their specs */
-    void *answers;                      /* [W] of the consumer's: place the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
+    const void *specs;                  /* [W] of the consumer's: place, compare and mix struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet, histogram and relate their specs */
+    void *answers;                      /* [W] of the consumer's: place and mix the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
+    const struct LINNEAmdMixSpec *mix;  /* [W], mix alone: its specs go beside its layouts */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
     WxCall c;
-    c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers;
+    c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL;
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
 static dim3 wx_grid(uint64_t n) { const uint64_t g = (n + WXB_THREADS - 1u) / WXB_THREADS; return dim3((uint32_t)(g < 65536u ? g : 65536u)); }
 
 /* ---- place, and compare, which reads the PCM that place writes (LINNE_AMD_PCM_F32 is refused as on encode) ---- */
-static int wx_pcm_check(const WxCall &c, uint32_t i, bool writes, char *err, size_t cap)
+static int wx_pcm_check(const WxCall &c, uint32_t i, uint32_t C, bool writes, char *err, size_t cap)
 {
     const struct LINNEAmdWindow *w = &c.win[i];
-    const uint32_t C = w->index->shape.num_channels;
     if (c.specs) {
         const struct LINNEAmdPcmLayout *ly = (const struct LINNEAmdPcmLayout *)c.specs + i;
         const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)w->d_pcm, C, w->num_samples, writes);
@@ -2288,8 +2291,8 @@ static int wx_pcm_check(const WxCall &c, uint32_t i, bool writes, char *err, siz
     } else if (C > 1u && w->pcm_stride < w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: pcm_stride %llu < %llu samples", (unsigned long long)w->pcm_stride, (unsigned long long)w->num_samples); return LNN_INVALID_ARGUMENT; }
     return LNN_OK;
 }
-static int wx_place_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, true, err, cap); }
-static int wx_compare_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, false, err, cap); }
+static int wx_place_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, c.win[i].index->shape.num_channels, true, err, cap); }
+static int wx_compare_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, c.win[i].index->shape.num_channels, false, err, cap); }
 static void wx_pcm_describe(const WxCall &c, uint32_t i, WxRange &r)
 {
     const struct LINNEAmdPcmLayout *ly = (const struct LINNEAmdPcmLayout *)c.specs;
@@ -2479,13 +2482,32 @@ static int wx_relate_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlace
 }
 static int wx_relate_commit(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_RELATE_T_COMMIT, k_wx_relate_commit, wx_grid(l.nout), dim3(WXB_THREADS), 0, ctx->stream, l.side, l.nwin, (const struct LINNEAmdRelation *)l.acc, l.fail, l.nout); return LNN_OK; }
 
-static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back };
-static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back };
-static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL };
-static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL };
-static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back };
-static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL };
-static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL };
+/* ---- mix: place with the window's channel matrix between the samples and the PCM (lnn_k_mix.h); the PCM has the matrix' Co channels ---- */
+static int wx_mix_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdMixSpec &ms = c.mix[i];
+    if (ms.out_channels < 1u || ms.out_channels > LINNE_MAX_NUM_CHANNELS) { snprintf(err, cap, "%s: out_channels %u is not 1 .. %u", c.use->name, ms.out_channels, (unsigned)LINNE_MAX_NUM_CHANNELS); return LNN_INVALID_ARGUMENT; }
+    if (ms.shift > 31u) { snprintf(err, cap, "%s: shift %u > 31", c.use->name, ms.shift); return LNN_INVALID_ARGUMENT; }
+    if (ms.clip_bits == 1u || ms.clip_bits > 32u) { snprintf(err, cap, "%s: clip_bits %u is neither 0 nor 2 .. 32", c.use->name, ms.clip_bits); return LNN_INVALID_ARGUMENT; }
+    if (ms.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", c.use->name); return LNN_INVALID_ARGUMENT; }
+    return wx_pcm_check(c, i, ms.out_channels, true, err, cap);
+}
+static void wx_mix_describe(const WxCall &c, uint32_t i, WxRange &r) { wx_pcm_describe(c, i, r); r.mix = c.mix + i; }
+static int wx_mix_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArgs &la)
+{
+    WxMixArgs ma; ma.p = la; ma.mwin = l.mix;
+    SX_LAUNCH(NULL, LINNE_AMD_MIX_T_MIX, k_wx_mix, dim3(la.nrec * la.xch), dim3(SX_PLACE_THREADS), 0, ctx->stream, ma);
+    return LNN_OK;
+}
+
+static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false };
+static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false };
+static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false };
+static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL, false };
+static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back, false };
+static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL, false };
+static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL, false };
+static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_mix_check, wx_mix_describe, NULL, wx_mix_pass, NULL, wx_place_read_back, true };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2544,14 +2566,14 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory */
-    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : 0u);
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : 0u);
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
     for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
     if (u.back_preset) u.back_preset((uint32_t *)(hs_ + ls.o_back), W);
     wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
-            (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec));
+            (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL);
     for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
@@ -2561,7 +2583,7 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
     WxLaunch ln;
-    ln.side = (const WxBucket *)(wd + ls.o_side); ln.wins = d_win; ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
+    ln.side = (const WxBucket *)(wd + ls.o_side); ln.mix = (const WxMix *)(wd + ls.o_side); ln.wins = d_win; ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
     ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout; ln.nmask = pl.nmask;
     if (!ctx->outer_keep) ctx->nspans = 0;
     if (ctx->timing && !ctx->outer_keep) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
@@ -2694,6 +2716,15 @@ extern "C" int LINNEAmd_RelateWindowsDevice(struct LINNEAmdContext *ctx, struct 
         uint32_t num_windows, uint32_t group_frames)
 {
     return wx_entry(ctx, wx_call(&WX_RELATE, windows, num_windows, group_frames, specs, NULL), windows && specs);
+}
+
+/* the windows' channels through a matrix per window on their way into the PCM */
+extern "C" int LINNEAmd_MixWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdMixSpec *specs,
+        struct LINNEAmdPcmLayout *layouts, uint32_t num_windows, uint32_t group_frames)
+{
+    WxCall c = wx_call(&WX_MIX, windows, num_windows, group_frames, layouts, layouts);
+    c.mix = specs;
+    return wx_entry(ctx, c, windows && specs);
 }
 
 /* one window of one stream */

@@ -17,7 +17,7 @@
  *                             WX_TAIL is the part of a window beyond the stream's last block (zeros).  The records of a window whose
  *                             fail word is set are skipped: a failing window's output is not written
  * k_wx_place and the kernels that stand in its place in the sibling calls -- k_wx_compare (lnn_k_compare.h), k_wx_measure
- * (lnn_k_measure.h), k_wx_digest (lnn_k_digest.h) -- begin with wx_prologue and cut their record into pieces with wx_walk, below;
+ * (lnn_k_measure.h), k_wx_digest (lnn_k_digest.h), k_wx_mix (lnn_k_mix.h, which writes PCM too: wx_place_layout_from) -- begin with wx_prologue and cut their record into pieces with wx_walk, below;
  * they differ in what they do with a piece.
  * As in lnn_k_stream.h, no read of a stream leaves [0, stream_bytes): RAW samples are un-zig-zagged straight from the stream.
  */
@@ -138,37 +138,40 @@ __device__ __forceinline__ void wx_store1(uint8_t *p, uint32_t u, uint32_t es)
     else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); p[2] = (uint8_t)(u >> 16); }
 }
 
-/* The workgroup places samples [sa, sb) (at most SX_PLACE_THREADS, inside the window) of record rc, whose sample 0 is stream sample
- * f0, in a layout other than int32 with sample stride 1.  Where the elements of this piece are contiguous in memory -- every channel's
- * for sample stride 1, the whole piece's for packed interleaved (channel stride 1, sample stride C) -- they are first laid out in
- * LDS at their address modulo 4 and then stored as aligned 32-bit words; a word that reaches outside the run [A, A + len) holds
- * elements other workgroups (or nobody) write, and only its bytes inside the run are stored, one by one.  With any other strides
+/* The workgroup places sample frames [sa, sb) (at most SX_PLACE_THREADS, inside the window) of C channels in a layout other than int32
+ * with sample stride 1.  The elements come from src: src.frame(smp) names frame sa + smp, src.get(ch, sat) then gives channel ch of it
+ * in the window's format (the element's bits, as wx_convert gives them).  Where the elements of this piece are contiguous in memory --
+ * every channel's for sample stride 1, the whole piece's for packed interleaved (channel stride 1, sample stride C) -- they are first
+ * laid out in LDS at their address modulo 4 and then stored as aligned 32-bit words; a word that reaches outside the run [A, A + len)
+ * holds elements other workgroups (or nobody) write, and only its bytes inside the run are stored, one by one.  With any other strides
  * every element is stored by itself.  Returns (to every thread) whether a sample was clipped. */
-__device__ __forceinline__ int wx_place_layout(const WxPlaceArgs &a, const WxWindow &w, const WxBlock *rc, uint32_t type, uint64_t f0,
-        uint64_t sa, uint64_t sb, uint8_t *img)
+template <class Source> __device__ __forceinline__ int wx_place_layout_from(const WxWindow &w, uint32_t C, uint64_t sa, uint64_t sb, uint8_t *img, Source src)
 {
     const uint32_t fmt = w.fmt, es = fmt == LINNE_AMD_PCM_S16 ? 2u : (fmt == LINNE_AMD_PCM_S24 ? 3u : 4u);
-    const uint32_t m = (uint32_t)(sb - sa), t = threadIdx.x, C = a.C;
+    const uint32_t m = (uint32_t)(sb - sa), t = threadIdx.x;
     uint8_t *base = (uint8_t *)w.out;
     const bool packed = (w.stride == 1u && w.sstride == C), planar = (w.sstride == 1u);
     int sat = 0;
     if (!packed && !planar) {
         for (uint32_t k = t; k < m * C; k += SX_PLACE_THREADS) {
             const uint32_t smp = k / C, ch = k - smp * C;
-            const uint32_t u = wx_convert(wx_value(a, rc, type, (uint32_t)(sa + smp - f0), ch), fmt, a.scale, sat);
+            src.frame(smp);
+            const uint32_t u = src.get(ch, sat);
             wx_store1(base + ((uint64_t)ch * w.stride + (sa + smp - w.lo) * w.sstride) * es, u, es);
         }
         return __syncthreads_or(sat);
     }
     /* runs: planar C of m elements, packed one of m * C; run r starts at byte A(r) and lies in LDS at r * pitch + (A(r) & 3) */
     const uint32_t nrun = planar ? C : 1u, len = (planar ? m : m * C) * es, pitch = ((len + 3u) & ~3u) + 8u;
-    if (t < m)
+    if (t < m) {
+        src.frame(t);
         for (uint32_t ch = 0; ch < C; ch++) {
-            const uint32_t u = wx_convert(wx_value(a, rc, type, (uint32_t)(sa + t - f0), ch), fmt, a.scale, sat);
+            const uint32_t u = src.get(ch, sat);
             const uint32_t r = planar ? ch : 0u;
             const uint64_t A = (uint64_t)(uintptr_t)base + ((uint64_t)r * w.stride + (sa - w.lo) * w.sstride) * es;
             wx_store1(img + r * pitch + (uint32_t)(A & 3u) + (planar ? t : t * C + ch) * es, u, es);
         }
+    }
     sat = __syncthreads_or(sat);
     for (uint32_t r = 0; r < nrun; r++) {
         const uint64_t A = (uint64_t)(uintptr_t)base + ((uint64_t)r * w.stride + (sa - w.lo) * w.sstride) * es, E = A + len, W0 = A & ~(uint64_t)3u;
@@ -183,6 +186,18 @@ __device__ __forceinline__ int wx_place_layout(const WxPlaceArgs &a, const WxWin
     }
     __syncthreads();                    /* (the image is filled again by the next piece) */
     return sat;
+}
+/* k_wx_place's source: the record's own samples, channel for channel; sample 0 of record rc is stream sample f0 */
+struct WxPlaceSource {
+    const WxPlaceArgs &a; const WxBlock *rc; uint32_t type, fmt; uint64_t f0, sa; uint32_t smp;
+    __device__ __forceinline__ void frame(uint32_t smp_) { smp = smp_; }
+    __device__ __forceinline__ uint32_t get(uint32_t ch, int &sat) const { return wx_convert(wx_value(a, rc, type, (uint32_t)(sa + smp - f0), ch), fmt, a.scale, sat); }
+};
+__device__ __forceinline__ int wx_place_layout(const WxPlaceArgs &a, const WxWindow &w, const WxBlock *rc, uint32_t type, uint64_t f0,
+        uint64_t sa, uint64_t sb, uint8_t *img)
+{
+    WxPlaceSource src = { a, rc, type, w.fmt, f0, sa, 0u };
+    return wx_place_layout_from(w, a.C, sa, sb, img, src);
 }
 
 /* ---- the record walk k_wx_place and its siblings (lnn_k_compare.h, lnn_k_measure.h, lnn_k_digest.h) share ---- */

@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs, histogram and relate; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram, relate and mix; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -74,6 +74,18 @@ struct WxBucket {
     union { uint32_t sstride, hist, npair; };   /* per frame: units from one slot to the next (per channel: C * nb, not kept); per bin: the window's bins, shift and scale (WXH_SPEC); per pair: P = C (C + 1) / 2 */
 };
 static_assert(sizeof(WxBlock) == 64 && sizeof(WxBucket) == 64, "a block record and a bucket record are 64 bytes");
+/* one window's channel matrix (160 bytes), at its WxWindow's index: what the mixing consumer (lnn_k_mix.h) keeps per window -- struct
+ * LINNEAmdMixSpec with everything the host can work out worked out: the clip bounds -2^(B - 1) and 2^(B - 1) - 1, and the F32 format's
+ * scale 2^-(Bf - 1) as the bits of a float.  Rows >= Co and columns >= C hold zeros, whatever the caller's spec holds there */
+struct WxMix {
+    uint32_t Co, shift;                 /* output channels 1 .. 8; the shift 0 .. 31 */
+    int32_t lo, hi;                     /* the clip */
+    uint32_t scale_bits;                /* the float 2^-(Bf - 1), Bf = clip_bits or, where that is 0, the stream's bits_per_sample */
+    uint32_t fidx;                      /* its fail word */
+    uint32_t reserved[2];
+    int16_t coef[LINNE_MAX_NUM_CHANNELS][LINNE_MAX_NUM_CHANNELS];  /* [o][c] */
+};
+static_assert(sizeof(WxMix) == 160 && sizeof(WxMix) % 16 == 0, "a mix record is 160 bytes");
 
 /* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
 #define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
@@ -107,6 +119,7 @@ struct WxRange {
     uint64_t bucket_samples, bucket_cstride; void *bucket_out;  /* bucketed consumers: its spec */
     uint64_t quiet_min, quiet_capacity; uint32_t quiet_threshold;       /* the bitmask consumer: its spec beside bucket_out (quiet_min >= 1) */
     uint32_t hist;                      /* the per-bin consumer: WXH_SPEC beside bucket_samples, bucket_cstride and bucket_out */
+    const struct LINNEAmdMixSpec *mix;  /* the mixing consumer: its spec, checked (out_channels 1 .. 8, shift <= 31, clip_bits 0 or 2 .. 32) */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -204,10 +217,22 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
     return (p.nlive && p.total_rec >= 0x7FFFFFFFull) ? WXP_BLOCKS : WXP_OK;
 }
 
+/* a window's mix record from its spec and its stream's shape */
+static inline void wx_mix_record(const struct LINNEAmdMixSpec &s, const struct LINNEAmdShape &shape, uint32_t fidx, WxMix &m)
+{
+    const uint32_t B = s.clip_bits ? s.clip_bits : 32u, Bf = s.clip_bits ? s.clip_bits : shape.bits_per_sample;
+    memset(&m, 0, sizeof(m));
+    m.Co = s.out_channels; m.shift = s.shift; m.fidx = fidx;
+    m.hi = (int32_t)(((uint64_t)1 << (B - 1u)) - 1u); m.lo = -m.hi - 1;
+    m.scale_bits = (128u - Bf) << 23;   /* 2^-(Bf - 1): exponent field 127 - (Bf - 1), Bf <= 32 */
+    for (uint32_t o = 0; o < s.out_channels && o < LINNE_MAX_NUM_CHANNELS; o++)
+        for (uint32_t c = 0; c < shape.num_channels && c < LINNE_MAX_NUM_CHANNELS; c++) m.coef[o][c] = s.coef[o][c];
+}
+
 /* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
- * entries; h_side NULL for WX_NO_BUCKETS */
+ * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs */
 static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
-        WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec)
+        WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL)
 {
     for (uint32_t g = 0; g < p.ngroups; g++) {
         const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
@@ -249,6 +274,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             WxWindow &ww = h_win[wi];
             ww.lo = w.lo; ww.hi = w.lo + w.n; ww.covered = x.covered; ww.out = w.out; ww.fidx = i;
             ww.fmt = w.fmt; ww.stride = w.stride; ww.sstride = w.sstride;
+            if (h_mix) wx_mix_record(*w.mix, shape, i, h_mix[wi]);
             if (bucketing == WX_BITMASK) {
                 WxBucket &m = h_side[wi];
                 memset(&m, 0, sizeof(m));

@@ -32,7 +32,11 @@
  *     %.6f" on stdout -- the exact sum of a_i * a_j in decimal, the frames with a_i == a_j and with a_i == -a_j, and
  *     dot_ij / sqrt(dot_ii * dot_jj) ("nan" where a channel has no energy) -- followed by " identical" or " inverted" where every
  *     frame says so, and "channel %u: silent" for a channel of zeros; with BUCKET one such group per BUCKET samples, every line
- *     behind "bucket %llu ".
+ *     behind "bucket %llu ";
+ *   - -X / --remix SPEC IN.lnn OUT.lnn writes a new stream whose channels are an integer matrix of IN's, on the device
+ *     (LINNEAmd_MixWindowsDevice into device PCM, clipped to the stream's bits, then LINNEAmd_EncodeStreamsDevice with IN's header and
+ *     the matrix' row count as its channels; one channel does not inherit MS).  SPEC: the rows separated by '/', a row's coefficients (int16) by ',', then optionally
+ *     ">>SHIFT" (0 .. 31, halves round up): "1,1>>1" the mean of a stereo pair, "0,1/1,0" a channel swap.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -48,9 +52,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec, *levels_spec;
+    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec;
     const char *files[4096];
     int num_files;
 };
@@ -67,6 +71,7 @@ static void usage(const char *argv0)
     printf("       %s -S THRESHOLD[,MIN_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -L BINS[,SHIFT[,log2]] STREAM.lnn \n", argv0);
     printf("       %s -R [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
+    printf("       %s -X ROW[/ROW...][>>SHIFT] IN.lnn OUT.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -78,6 +83,7 @@ static void usage(const char *argv0)
            "  -S, --silence THRESHOLD[,MIN_SAMPLES]  List a .lnn stream's quiet runs on the device: every channel within +-THRESHOLD \n"
            "  -L, --levels BINS[,SHIFT[,log2]]       Histogram a .lnn stream's sample levels on the device: |v| >> SHIFT, or its bit length \n"
            "  -R, --relate                           Relate a .lnn stream's channels on the device: dot products, equal and opposite frames, correlation per pair (and bucket) \n"
+           "  -X, --remix ROW[/ROW...][>>SHIFT]      Write a .lnn stream whose channels are an integer matrix of the input's: rows of C coefficients \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -132,6 +138,7 @@ static void parse(int argc, char **argv, struct options *o)
             if (*end != '\0' || o->af_iterations < 0 || o->af_iterations > 255) { fprintf(stderr, "%s: auxiliary function iteration count is out of range. \n", argv[0]); exit(1); }
         } else if (take_value(argc, argv, &i, "-S", "--silence", &v)) { o->silence = 1; o->silence_spec = v; }
         else if (take_value(argc, argv, &i, "-L", "--levels", &v)) { o->levels = 1; o->levels_spec = v; }
+        else if (take_value(argc, argv, &i, "-X", "--remix", &v)) { o->remix = 1; o->remix_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -606,6 +613,85 @@ done:
     return rc;
 }
 
+/* "1,1>>1", "0,1/1,0": rows by '/', coefficients by ',', an optional ">>shift" -> spec (out_channels the rows) and *cols, the length
+ * every row has.  0, or a message in err */
+static int parse_remix(const char *text, struct LINNEAmdMixSpec *spec, uint32_t *cols, char *err, size_t cap)
+{
+    const char *p = text;
+    uint32_t o = 0, c = 0;
+    memset(spec, 0, sizeof(*spec));
+    *cols = 0;
+    for (;;) {
+        char *end;
+        long v;
+        if (!((*p >= '0' && *p <= '9') || ((*p == '-' || *p == '+') && p[1] >= '0' && p[1] <= '9'))) { snprintf(err, cap, "remix spec: a coefficient is expected at \"%s\"", p); return 1; }
+        v = strtol(p, &end, 10);
+        if (v < -32768 || v > 32767) { snprintf(err, cap, "remix spec: coefficient %ld is outside int16", v); return 1; }
+        if (o >= LINNE_MAX_NUM_CHANNELS || c >= LINNE_MAX_NUM_CHANNELS) { snprintf(err, cap, "remix spec: more than %d rows or coefficients in a row", LINNE_MAX_NUM_CHANNELS); return 1; }
+        spec->coef[o][c++] = (int16_t)v;
+        p = end;
+        if (*p == ',') { p++; continue; }
+        if (o == 0) *cols = c;
+        else if (c != *cols) { snprintf(err, cap, "remix spec: row %u has %u coefficients, row 0 has %u", o, c, *cols); return 1; }
+        o++; c = 0;
+        if (*p == '/') { p++; continue; }
+        break;
+    }
+    spec->out_channels = o;
+    if (p[0] == '>' && p[1] == '>' && p[2] >= '0' && p[2] <= '9') {
+        char *end;
+        const unsigned long sh = strtoul(p + 2, &end, 10);
+        if (sh > 31) { snprintf(err, cap, "remix spec: shift %lu > 31", sh); return 1; }
+        spec->shift = (uint32_t)sh;
+        p = end;
+    }
+    if (*p != '\0') { snprintf(err, cap, "remix spec: malformed at \"%s\"", p); return 1; }
+    return 0;
+}
+
+/* -X: the spec and the stream's header are checked on the host; then the stream goes to the device, LINNEAmd_StreamIndexCreate, one
+ * LINNEAmd_MixWindowsDevice window over the whole stream into int32 planes beside it, and LINNEAmd_EncodeStreamsDevice make the output */
+static int remix_one(const char *spec_text, const char *in_path, const char *out_path)
+{
+    uint8_t *buf = NULL, *out = NULL;
+    void *d_out = NULL;
+    uint32_t size = 0, cols = 0;
+    struct resident r;
+    struct LINNEAmdMixSpec spec;
+    struct LINNEAmdTrack tr;
+    struct LINNEHeader h;
+    char err[512];
+    uint64_t n, cap;
+    FILE *fp;
+    int ret, stage, rc = 1;
+    memset(&r, 0, sizeof(r));
+    if (parse_remix(spec_text, &spec, &cols, err, sizeof(err)) != 0) { fprintf(stderr, "%s \n", err); return 1; }
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    if (cols != h.num_channels) { fprintf(stderr, "remix spec: its rows have %u coefficients, the stream has %u channels \n", cols, (unsigned)h.num_channels); free(buf); return 1; }
+    n = h.num_samples;
+    spec.clip_bits = h.bits_per_sample;
+    if ((stage = resident_open(&r, buf, size, n, sizeof(int32_t) * n * spec.out_channels, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to remix! %s \n" : "%s \n", err); goto done; }
+    r.w.d_pcm = r.d_extra; r.w.pcm_stride = n;
+    if ((ret = LINNEAmd_MixWindowsDevice(r.ctx, &r.w, &spec, NULL, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to remix! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    memset(&tr, 0, sizeof(tr));
+    tr.header = h; tr.header.num_channels = (uint16_t)spec.out_channels;
+    if (spec.out_channels == 1) tr.header.ch_process_method = LINNE_CH_PROCESS_METHOD_NONE;    /* (one channel has no mid and side) */
+    cap = LINNEAmd_EncodeStreamBound(&tr.header);
+    if (hipMalloc(&d_out, cap ? cap : 1) != hipSuccess) { fprintf(stderr, "Failed to allocate %llu bytes on the device. \n", (unsigned long long)cap); d_out = NULL; goto done; }
+    tr.d_pcm = r.d_extra; tr.pcm_stride = n; tr.d_out = d_out; tr.capacity = cap;
+    if ((ret = LINNEAmd_EncodeStreamsDevice(r.ctx, &tr, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to encode! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(out = malloc(tr.out_bytes ? (size_t)tr.out_bytes : 1)) || hipMemcpy(out, d_out, tr.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the stream. \n"); goto done; }
+    if (!(fp = fopen(out_path, "wb")) || fwrite(out, 1, (size_t)tr.out_bytes, fp) != tr.out_bytes) { fprintf(stderr, "File output error! %s \n", out_path); if (fp) fclose(fp); goto done; }
+    fclose(fp);
+    rc = 0;
+done:
+    if (d_out) (void)hipFree(d_out);
+    resident_close(&r);
+    free(out); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -614,6 +700,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.remix) {
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -X takes a matrix, an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        return remix_one(o.remix_spec, o.files[0], o.files[1]);
+    }
     if (o.relate) {
         unsigned long long bucket = 0;
         if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.batch_dir || o.num_files < 1 || o.num_files > 2) { fprintf(stderr, "%s: -R takes an optional bucket sample count and a stream file name and no other mode. \n", argv[0]); return 1; }
