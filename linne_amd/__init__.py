@@ -11,6 +11,7 @@ only loads it and wraps its two interfaces:
 There is no CPU fallback: importing works without a GPU (so the symbol table can be checked), but any
 compute call needs a HIP device, and a missing library raises ImportError.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -562,6 +563,13 @@ class StreamIndex:
         self.num_blocks = num_blocks
         self.nbytes = nbytes
 
+    @classmethod
+    def of(cls, handle, nbytes):
+        """the StreamIndex of a handle the library gave for a stream of nbytes bytes"""
+        hd = Header()
+        lib.LINNEAmd_StreamIndexHeader(handle, C.byref(hd))
+        return cls(handle, {k: int(getattr(hd, k)) for k, _ in Header._fields_}, int(lib.LINNEAmd_StreamIndexNumBlocks(handle)), nbytes)
+
     def blocks(self):
         """the blocks a whole decode walks -> numpy copies (off, first, size, type, nsmp): byte offsets, first samples (num_blocks + 1
         entries), size fields, types (0 COMPRESS, 1 SILENT, 2 RAW) and sample counts (LINNEAmd_StreamIndexBlocks)"""
@@ -590,6 +598,41 @@ class StreamIndex:
 
     def __del__(self):
         self.close()
+
+
+def _per_window(value, W, what, lo=0, hi=None, scalars=(int, np.integer)):
+    """an argument that is one value or one per window -> a list of W integers, each >= lo (None: any) and < hi (None: any)"""
+    vs = [int(value)] * W if isinstance(value, scalars) else [int(v) for v in value]
+    rule = "" if lo is None else f" >= {lo}" if hi is None else f" in {lo} .. 2^{hi.bit_length() - 1} - 1"
+    assert len(vs) == W and all((lo is None or v >= lo) and (hi is None or v < hi) for v in vs), f"{what} is one value{rule}, or one per window"
+    return vs
+
+
+def _sample_range(index, nbytes, first, n, where, *at):
+    """the range (first, n) of a stream of nbytes bytes against its index, n None: to the stream's end -> (first, n, the num_samples
+    a C struct takes: a negative n as a count no stream has, which the call refuses).  where % at names the range in the assertion"""
+    assert index.nbytes == nbytes, f"{where % at}: the index was built for a stream of another length"
+    first = int(first)
+    n = index.header["num_samples"] - first if n is None else int(n)
+    return first, n, n if n >= 0 else (1 << 64) - 1
+
+
+def _default_room(nch, ns, bits):
+    """the bytes encode_stream and encode_streams give a track's stream at first: what the reference's command line tool allocates"""
+    return 2 * nch * ns * ((bits + 7) // 8) + 30
+
+
+# The windows calls that answer per bucket, as _bucket_windows runs them (tests/stream_consumers.py holds the same table for the tests):
+# the spec struct; the C entry point; the 64-bit words of a bucket (None: the caller's, per window); the rows of a window's table in
+# front of (buckets, words), from its channel count; the spec's stride field; the answer of a window from (its table, its bucket length,
+# its index, the spec's further fields)
+_BUCKET_CONSUMERS = {
+    "measure": (MeasureSpec, "LINNEAmd_MeasureWindowsDevice", 4, lambda c: (c,), "channel_stride", lambda t, b, x: Measurement(t, b)),
+    "digest": (DigestSpec, "LINNEAmd_DigestWindowsDevice", 2, lambda c: (), None, lambda t, b, x: DigestTable(t, b, x.header)),
+    "histogram": (HistogramSpec, "LINNEAmd_HistogramWindowsDevice", None, lambda c: (c,), "channel_stride",
+                  lambda t, b, x, bins, shift, scale: Histogram(t, bins, shift, bool(scale), b)),
+    "relate": (RelateSpec, "LINNEAmd_RelateWindowsDevice", 4, lambda c: (c * (c + 1) // 2,), "pair_stride", lambda t, b, x: Relations(t, b)),
+}
 
 
 class Context:
@@ -760,10 +803,7 @@ class Context:
         h = lib.LINNEAmd_StreamIndexCreate(self.h, C.c_void_p(t.data_ptr()), t.numel(), C.byref(res))
         if not h:
             raise LinneAmdError(f"StreamIndexCreate -> {res.value}: {lib.LINNEAmd_GetLastError(self.h).decode()}", res.value)
-        hd = Header()
-        lib.LINNEAmd_StreamIndexHeader(h, C.byref(hd))
-        header = {k: int(getattr(hd, k)) for k, _ in Header._fields_}
-        return StreamIndex(h, header, int(lib.LINNEAmd_StreamIndexNumBlocks(h)), t.numel())
+        return StreamIndex.of(h, t.numel())
 
     def index_streams(self, streams, return_codes=False):
         """the block indexes of many whole .lnn streams in one call (include/linne_amd.h LINNEAmd_StreamIndexesCreate).  streams: a
@@ -781,14 +821,7 @@ class Context:
         ret = lib.LINNEAmd_StreamIndexesCreate(self.h, ptrs, sizes, T, handles, res)
         codes = [int(res[i]) for i in range(T)]
         msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
-        out = []
-        for i in range(T):
-            if not handles[i]:
-                out.append(None)
-                continue
-            hd = Header()
-            lib.LINNEAmd_StreamIndexHeader(handles[i], C.byref(hd))
-            out.append(StreamIndex(handles[i], {k: int(getattr(hd, k)) for k, _ in Header._fields_}, int(lib.LINNEAmd_StreamIndexNumBlocks(handles[i])), keep[i].numel()))
+        out = [StreamIndex.of(handles[i], keep[i].numel()) if handles[i] else None for i in range(T)]
         whole_call = ret == 7 and all(x is None for x in out) and all(c == 7 for c in codes)      # LINNE_APIRESULT_NG everywhere, nothing built
         if ret != 0 and (not return_codes or whole_call):
             for x in out:
@@ -826,10 +859,8 @@ class Context:
             nch = index.header["num_channels"]
             out = torch.empty((nch, max(n, 0)), dtype=torch.int32, device=t.device)
             self._fence()
-            ret = lib.LINNEAmd_DecodeStreamDevice(self.h, index.h, C.c_void_p(t.data_ptr()), int(first_sample), max(n, 0) if n >= 0 else (1 << 64) - 1,
-                                                  C.c_void_p(out.data_ptr()), out.shape[1])
-            if ret != 0:
-                raise LinneAmdError(f"DecodeStreamDevice -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
+            self._check(lib.LINNEAmd_DecodeStreamDevice(self.h, index.h, C.c_void_p(t.data_ptr()), int(first_sample), n if n >= 0 else (1 << 64) - 1,
+                                                        C.c_void_p(out.data_ptr()), out.shape[1]), "DecodeStreamDevice")
             return out
         finally:
             if own:
@@ -844,14 +875,11 @@ class Context:
         for i, w in enumerate(windows):
             stream, index, first, n = w[:len(w) - extra]
             t = self._stream_bytes(stream)
-            assert index.nbytes == t.numel(), f"window {i}: the index was built for a stream of another length"
-            first = int(first)
-            n = index.header["num_samples"] - first if n is None else int(n)
+            first, n, count = _sample_range(index, t.numel(), first, n, "window %d", i)
             keep.append(t)
             ranges.append((index, first, n))
-            arr[i].index, arr[i].d_stream, arr[i].first_sample = index.h, t.data_ptr(), first
-            arr[i].num_samples = n if n >= 0 else (1 << 64) - 1
-            arr[i].d_pcm, arr[i].pcm_stride = None, 0
+            win = arr[i]
+            win.index, win.d_stream, win.first_sample, win.num_samples, win.d_pcm, win.pcm_stride = index.h, t.data_ptr(), first, count, None, 0
         return arr, keep, ranges
 
     def _windows_codes(self, ret, arr, W, what, return_codes):
@@ -864,18 +892,12 @@ class Context:
                 raise LinneAmdError(f"{what} -> {ret}: {msg}", ret, codes)
         return codes
 
-    def _bucket_tables(self, bucket_samples, ranges, words, per_channel):
-        """the tables of a call that answers per bucket: bucket_samples one value or one per window -> (the bucket length per window;
-        per window an int64 view (nb, words) -- per_channel: (C, nb, words) -- of one allocation; the views' device addresses; the
-        bucket counts nb).  words: one value, or one per window; per_channel "pairs": (P, nb, words), P the channel pairs"""
+    def _bucket_tables(self, buckets, ranges, words, rows):
+        """the tables of a call that answers per bucket, from the windows' bucket lengths and 64-bit words per bucket -> (per window an
+        int64 view rows(C) + (nb, words) of one allocation; the views' device addresses; the bucket counts nb)"""
         import torch
-        W = len(ranges)
-        buckets = [int(bucket_samples)] * W if isinstance(bucket_samples, (int, np.integer)) else [int(b) for b in bucket_samples]
-        assert len(buckets) == W and all(b >= 0 for b in buckets), "bucket_samples is one value >= 0, or one per window"
-        words = [words] * W if isinstance(words, int) else list(words)
         counts = [0 if n <= 0 else (1 if b == 0 else -(-n // b)) for (_, _, n), b in zip(ranges, buckets)]
-        lead = {False: lambda c: (), True: lambda c: (c,), "pairs": lambda c: (c * (c + 1) // 2,)}[per_channel]
-        shapes = [lead(x.header["num_channels"]) + (nb, wd) for (x, _, _), nb, wd in zip(ranges, counts, words)]
+        shapes = [rows(x.header["num_channels"]) + (nb, wd) for (x, _, _), nb, wd in zip(ranges, counts, words)]
         sizes = [math.prod(shape) for shape in shapes]
         flat = torch.empty(max(sum(sizes), max(words, default=1)), dtype=torch.int64, device=f"cuda:{self.device}")
         views, addresses, at = [], [], 0
@@ -883,19 +905,50 @@ class Context:
             views.append(flat[at:at + size].view(*shape))
             addresses.append(flat.data_ptr() + 8 * at)                 # (an empty view has no address of its own)
             at += size
-        return buckets, views, addresses, counts
+        return views, addresses, counts
+
+    def _bucket_windows(self, name, windows, bucket_samples, group_frames, return_codes, words=None, **fields):
+        """measure_, digest_, histogram_ and relate_windows: row `name` of _BUCKET_CONSUMERS over the windows.  words: the 64-bit words
+        of a bucket per window, where the row names none; fields: the spec's further fields, each a list with a value per window"""
+        spec, entry, row_words, rows, stride, answer = _BUCKET_CONSUMERS[name]
+        W = len(windows)
+        arr, keep, ranges = self._windows_array(windows)
+        buckets = _per_window(bucket_samples, W, "bucket_samples")
+        tables, addresses, counts = self._bucket_tables(buckets, ranges, [row_words] * W if words is None else words, rows)
+        specs = (spec * max(W, 1))()
+        for i in range(W):
+            sp = specs[i]
+            sp.bucket_samples, sp.d_out = buckets[i], addresses[i]
+            if stride:
+                setattr(sp, stride, counts[i])
+            for field, values in fields.items():
+                setattr(sp, field, values[i])
+        self._fence()
+        ret = getattr(lib, entry)(self.h, arr, specs, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, entry[len("LINNEAmd_"):], return_codes)
+        own = list(zip(*fields.values())) if fields else [()] * W
+        out = [answer(tables[i], buckets[i], ranges[i][0], *own[i]) if codes[i] == 0 else None for i in range(W)]
+        return (out, codes) if return_codes else out
+
+    @contextlib.contextmanager
+    def _whole_streams(self, streams, return_codes=False):
+        """one index_streams call over whole streams -> (the streams' tensors, their indexes, with return_codes the streams' codes --
+        a failed stream's index is None -- otherwise None); the indexes are closed behind the block"""
+        ts = [self._stream_bytes(s) for s in streams]
+        indexes, codes = self.index_streams(ts, return_codes=True) if return_codes else (self.index_streams(ts), None)
+        try:
+            yield ts, indexes, codes
+        finally:
+            for x in indexes:
+                if x is not None:
+                    x.close()
 
     def _over_whole_streams(self, streams, call, **kw):
         """one index_streams call and one `call` over the whole streams"""
         if len(streams) == 0:
             return []
-        ts = [self._stream_bytes(s) for s in streams]
-        indexes = self.index_streams(ts)
-        try:
+        with self._whole_streams(streams) as (ts, indexes, _):
             return call([(t, x, 0, None) for t, x in zip(ts, indexes)], **kw)
-        finally:
-            for x in indexes:
-                x.close()
 
     def decode_windows(self, windows, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False, s24=False,
                        return_saturated=False):
@@ -977,9 +1030,7 @@ class Context:
         one = isinstance(matrix, np.ndarray) and matrix.ndim == 2 or (not isinstance(matrix, np.ndarray) and len(matrix) > 0 and np.ndim(matrix[0]) == 1)
         mats = [matrix] * W if one else list(matrix)
         assert len(mats) == W, "matrix is one (Co, C) array, or one per window"
-        per = lambda v: [int(v)] * W if isinstance(v, (int, np.integer)) else [int(x) for x in v]
-        shifts, clips = per(shift), per(clip_bits)
-        assert len(shifts) == W and len(clips) == W, "shift and clip_bits are one value, or one per window"
+        shifts, clips = _per_window(shift, W, "shift", lo=None), _per_window(clip_bits, W, "clip_bits", lo=None)      # (their ranges: ValueError, below)
         specs = (MixSpec * max(W, 1))()
         for i, (x, m) in enumerate(zip(indexes, mats)):
             m = np.asarray(m)
@@ -1015,9 +1066,7 @@ class Context:
         channel does not inherit MS, which a mono header cannot carry.  -> a list of uint8 CUDA tensors"""
         if len(streams) == 0:
             return []
-        ts = [self._stream_bytes(s) for s in streams]
-        indexes = self.index_streams(ts)
-        try:
+        with self._whole_streams(streams) as (ts, indexes, _):
             heads = [x.header for x in indexes]
             obits = [int(bits) if bits is not None else h["bits_per_sample"] for h in heads]
             pcms = self.mix_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], matrix, shift=shift, clip_bits=obits, group_frames=group_frames)
@@ -1025,9 +1074,6 @@ class Context:
                        int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else (h["ch_process_method"] if pcm.shape[0] > 1 else 0))
                       for pcm, b, h in zip(pcms, obits, heads)]
             return self.encode_streams(tracks, group_frames=group_frames)
-        finally:
-            for x in indexes:
-                x.close()
 
     def compare_windows(self, windows, group_frames=0, return_codes=False):
         """many sample windows of resident .lnn streams compared with resident PCM in one call, nothing decoded into memory of the
@@ -1065,17 +1111,7 @@ class Context:
         allocation.  Every number is exact and is what numpy gives on decode_windows' int32 samples.  Errors follow
         compare_windows: LinneAmdError with .code and .codes when a window fails; with return_codes -> (answers, codes), a failing
         window's answer is None, and only a failure of the whole call raises"""
-        W = len(windows)
-        arr, keep, ranges = self._windows_array(windows)
-        buckets, recs, addresses, counts = self._bucket_tables(bucket_samples, ranges, 4, True)
-        specs = (MeasureSpec * max(W, 1))()
-        for i in range(W):
-            specs[i].bucket_samples, specs[i].d_out, specs[i].channel_stride = buckets[i], addresses[i], counts[i]
-        self._fence()
-        ret = lib.LINNEAmd_MeasureWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "MeasureWindowsDevice", return_codes)
-        out = [Measurement(recs[i], buckets[i]) if codes[i] == 0 else None for i in range(W)]
-        return (out, codes) if return_codes else out
+        return self._bucket_windows("measure", windows, bucket_samples, group_frames, return_codes)
 
     def measure_streams(self, streams, bucket_samples=0, group_frames=0):
         """min, max, sum and sum of squares of whole resident .lnn streams, per channel and bucket: one index_streams call and one
@@ -1091,17 +1127,7 @@ class Context:
         zlib.crc32 of the window's samples as a WAV file holds them (interleaved, ceil(bits / 8) bytes little-endian, 8-bit
         unsigned).  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with return_codes ->
         (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
-        W = len(windows)
-        arr, keep, ranges = self._windows_array(windows)
-        buckets, recs, addresses, _ = self._bucket_tables(bucket_samples, ranges, 2, False)
-        specs = (DigestSpec * max(W, 1))()
-        for i in range(W):
-            specs[i].bucket_samples, specs[i].d_out = buckets[i], addresses[i]
-        self._fence()
-        ret = lib.LINNEAmd_DigestWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "DigestWindowsDevice", return_codes)
-        out = [DigestTable(recs[i], buckets[i], windows[i][1].header) if codes[i] == 0 else None for i in range(W)]
-        return (out, codes) if return_codes else out
+        return self._bucket_windows("digest", windows, bucket_samples, group_frames, return_codes)
 
     def digest_streams(self, streams, bucket_samples=0, group_frames=0):
         """the CRC-32 of the decoded PCM of whole resident .lnn streams, per bucket: one index_streams call and one digest_windows
@@ -1122,13 +1148,8 @@ class Context:
         import torch
         W = len(windows)
         arr, keep, ranges = self._windows_array(windows)
-
-        def per_window(v, what):
-            vs = [int(v)] * W if isinstance(v, (int, np.integer)) else [int(e) for e in v]
-            assert len(vs) == W and all(e >= 0 for e in vs), f"{what} is one value >= 0, or one per window"
-            return vs
-        thr, mins = per_window(threshold, "threshold"), per_window(min_samples, "min_samples")
-        caps = per_window(QUIET_DEFAULT_CAPACITY if capacity is None else capacity, "capacity")
+        thr, mins = _per_window(threshold, W, "threshold"), _per_window(min_samples, W, "min_samples")
+        caps = _per_window(QUIET_DEFAULT_CAPACITY if capacity is None else capacity, W, "capacity")
         assert all(t < (1 << 32) for t in thr), "threshold is below 2^32"
 
         def call(which, caps):
@@ -1138,8 +1159,7 @@ class Context:
             flat = torch.empty((max(sum(caps), 1), 2), dtype=torch.int64, device=f"cuda:{self.device}")
             at = 0
             for j, i in enumerate(which):
-                for name, _ in Window._fields_:
-                    setattr(w[j], name, getattr(arr[i], name))
+                C.memmove(C.byref(w[j]), C.byref(arr[i]), C.sizeof(Window))
                 specs[j].threshold, specs[j].min_samples, specs[j].capacity = thr[i], mins[i], caps[j]
                 specs[j].d_out = flat.data_ptr() + 16 * at if caps[j] else None
                 at += caps[j]
@@ -1177,25 +1197,11 @@ class Context:
         Histogram, one per window, views of one allocation.  Every count is exact and is what numpy.bincount gives on
         decode_windows' int32 samples.  Errors follow measure_windows: LinneAmdError with .code and .codes when a window fails; with
         return_codes -> (answers, codes), a failing window's answer is None, and only a failure of the whole call raises"""
-        W = len(windows)
-        arr, keep, ranges = self._windows_array(windows)
-
-        def per_window(v, what):
-            vs = [int(v)] * W if isinstance(v, (bool, int, np.integer, np.bool_)) else [int(e) for e in v]
-            assert len(vs) == W and all(0 <= e < (1 << 32) for e in vs), f"{what} is one value in 0 .. 2^32 - 1, or one per window"
-            return vs
-        bins, shifts, scales = per_window(num_bins, "num_bins"), per_window(shift, "shift"), per_window(log2, "log2")
+        bins, shifts, scales = (_per_window(v, len(windows), what, hi=1 << 32, scalars=(int, np.integer, np.bool_))
+                                for v, what in ((num_bins, "num_bins"), (shift, "shift"), (log2, "log2")))
         # (a table is sized for bins the call will accept; a num_bins that it refuses gets no room)
-        buckets, tables, addresses, counts = self._bucket_tables(bucket_samples, ranges, [b if b <= HIST_MAX_BINS else 0 for b in bins], True)
-        specs = (HistogramSpec * max(W, 1))()
-        for i in range(W):
-            specs[i].bucket_samples, specs[i].num_bins, specs[i].shift, specs[i].scale = buckets[i], bins[i], shifts[i], scales[i]
-            specs[i].d_out, specs[i].channel_stride = addresses[i], counts[i]
-        self._fence()
-        ret = lib.LINNEAmd_HistogramWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "HistogramWindowsDevice", return_codes)
-        out = [Histogram(tables[i], bins[i], shifts[i], bool(scales[i]), buckets[i]) if codes[i] == 0 else None for i in range(W)]
-        return (out, codes) if return_codes else out
+        return self._bucket_windows("histogram", windows, bucket_samples, group_frames, return_codes, words=[b if b <= HIST_MAX_BINS else 0 for b in bins],
+                                    num_bins=bins, shift=shifts, scale=scales)
 
     def histogram_streams(self, streams, num_bins, shift=0, log2=False, bucket_samples=0, group_frames=0):
         """histograms of |v| of whole resident .lnn streams, per channel and bucket: one index_streams call and one histogram_windows
@@ -1215,17 +1221,7 @@ class Context:
         correlation and channel_findings read the table on the host.  Errors follow measure_windows: LinneAmdError with .code and
         .codes when a window fails; with return_codes -> (answers, codes), a failing window's answer is None, and only a failure of
         the whole call raises"""
-        W = len(windows)
-        arr, keep, ranges = self._windows_array(windows)
-        buckets, recs, addresses, counts = self._bucket_tables(bucket_samples, ranges, 4, "pairs")
-        specs = (RelateSpec * max(W, 1))()
-        for i in range(W):
-            specs[i].bucket_samples, specs[i].d_out, specs[i].pair_stride = buckets[i], addresses[i], counts[i]
-        self._fence()
-        ret = lib.LINNEAmd_RelateWindowsDevice(self.h, arr, specs, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "RelateWindowsDevice", return_codes)
-        out = [Relations(recs[i], buckets[i]) if codes[i] == 0 else None for i in range(W)]
-        return (out, codes) if return_codes else out
+        return self._bucket_windows("relate", windows, bucket_samples, group_frames, return_codes)
 
     def relate_streams(self, streams, bucket_samples=0, group_frames=0):
         """the channel relations of whole resident .lnn streams, per pair and bucket: one index_streams call and one relate_windows
@@ -1254,9 +1250,7 @@ class Context:
         T = len(pairs)
         if T == 0:
             return []
-        streams = [self._stream_bytes(s) for s, _ in pairs]
-        indexes, icodes = self.index_streams(streams, return_codes=True)
-        try:
+        with self._whole_streams([s for s, _ in pairs], return_codes=True) as (streams, indexes, icodes):
             out, wins, at = [None] * T, [], []
             for i, (x, (_, pcm)) in enumerate(zip(indexes, pairs)):
                 if x is None:
@@ -1273,10 +1267,6 @@ class Context:
                 for i, a, c in zip(at, answers, codes):
                     out[i] = a + (None,) if c == 0 else (None, 0, 0, f"the stream does not decode (LINNEApiResult {c})")
             return out
-        finally:
-            for x in indexes:
-                if x is not None:
-                    x.close()
 
     def _verified(self, streams, pcms, what):
         """set_verify(True) in encode_stream / encode_streams: raises when a stream that was encoded does not hold its track's PCM"""
@@ -1345,13 +1335,12 @@ class Context:
             assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.is_contiguous()
             buf = out
         else:
-            buf = torch.empty(2 * nch * ns * ((bits + 7) // 8) + 30, dtype=torch.uint8, device=pcm.device)
+            buf = torch.empty(_default_room(nch, ns, bits), dtype=torch.uint8, device=pcm.device)
         ret = run(buf)
         if ret == 3 and out is None and nbytes.value > 0:             # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
             buf = torch.empty(nbytes.value, dtype=torch.uint8, device=pcm.device)
             ret = run(buf)
-        if ret != 0:
-            raise LinneAmdError(f"EncodeStreamDevice -> {ret}: {lib.LINNEAmd_GetLastError(self.h).decode()}", ret)
+        self._check(ret, "EncodeStreamDevice")
         stream = buf[:nbytes.value]
         if self._verify:
             self._verified([stream], [pcm], "EncodeStreamDevice")
@@ -1360,6 +1349,49 @@ class Context:
     def last_stream_encode_count(self, which):
         """the last encode_stream or encode_streams call: 0 / 1 / 2 its COMPRESS / SILENT / RAW blocks, 3 the channel-frames whose Rice plan the host settled"""
         return int(lib.LINNEAmd_GetLastStreamEncodeCount(self.h, int(which)))
+
+    def _write_streams(self, what, noun, struct, rooms, fill, call, read):
+        """encode_streams, splice_streams and repair_streams: the C call `what`, whose error texts name an item `noun`, writes every
+        item's stream into rooms[i] bytes at a 4-byte-aligned offset of one allocation; the items that did not fit are written once
+        more, together, at their exact sizes into another one.  struct: the call's item, with d_out, capacity, out_bytes and result;
+        fill(sub[j], i) writes the rest of item i into its place of a call; call(sub, which) makes the C call over the items `which`;
+        read(i, j, sub[j], item i's stream or None) takes item i's answer, before any other library call.  -> (the items' LINNEApiResults; the
+        LinneAmdError of the lowest failing item, which the caller raises unless it returns the codes, or None).  A failure of a whole
+        call raises here, with the codes of that call's items"""
+        import torch
+        T = len(rooms)
+        codes, nbytes = [0] * T, [0] * T
+
+        def run(which, sizes):
+            offs, at = [], 0
+            for n in sizes:
+                offs.append(at)
+                at += (n + 3) & ~3
+            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=f"cuda:{self.device}")
+            sub = (struct * max(len(which), 1))()
+            for j, i in enumerate(which):
+                item = sub[j]
+                fill(item, i)
+                item.d_out, item.capacity, item.out_bytes, item.result = flat.data_ptr() + offs[j], sizes[j], 0, 0
+            self._fence()
+            ret = call(sub, which)
+            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
+            if ret != 0 and not msg.startswith(noun + " "):              # (a failing item's text starts with its noun and number)
+                raise LinneAmdError(f"{what} -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
+            for j, i in enumerate(which):
+                item = sub[j]
+                codes[i], nbytes[i] = int(item.result), int(item.out_bytes)
+                read(i, j, item, flat[offs[j]:offs[j] + nbytes[i]] if codes[i] == 0 else None)
+            return ret, msg
+
+        ret, msg = run(list(range(T)), rooms)
+        again = [i for i in range(T) if codes[i] == 3 and nbytes[i] > rooms[i]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
+        if again:
+            run(again, [nbytes[i] for i in again])
+            bad = [i for i in range(T) if codes[i] != 0]
+            ret = codes[bad[0]] if bad else 0
+            msg = f"{noun} {bad[0]} failed" if bad else ""
+        return codes, LinneAmdError(f"{what} -> {ret}: {msg}", ret, codes) if ret != 0 else None
 
     def encode_streams(self, tracks, group_frames=0, parcor_states=None, return_codes=False):
         """many tracks into their .lnn streams in one call (include/linne_amd.h LINNEAmd_EncodeStreamsDevice).  tracks: a sequence of
@@ -1394,46 +1426,24 @@ class Context:
             keep.append(pcm)
             arr[i].header = Header(1, 2, nch, ns, rate, bits, block, preset, int(bool(ms)))
             arr[i].d_pcm, arr[i].pcm_stride = pcm.data_ptr(), pcm.stride(0) if nch > 1 else ns
-            rooms.append(2 * nch * ns * ((bits + 7) // 8) + 30)
+            rooms.append(_default_room(nch, ns, bits))
+        states, streams = [0.0] * T, [None] * T
 
-        def run(which, sizes):
-            """one call over the tracks `which` with sizes[j] bytes of room each -> (result, error text, buffer views)"""
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += (n + 3) & ~3
-            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
-            sub = (Track * max(len(which), 1))()
-            sublay = None if all_plain else (PcmLayout * max(len(which), 1))()
-            for j, i in enumerate(which):
-                C.memmove(C.byref(sub[j]), C.byref(arr[i]), C.sizeof(Track))
-                if sublay is not None:
-                    C.memmove(C.byref(sublay[j]), C.byref(lays[i]), C.sizeof(PcmLayout))
-                sub[j].d_out, sub[j].capacity, sub[j].out_bytes, sub[j].result = flat.data_ptr() + offs[j], sizes[j], 0, 0
-                sub[j].parcor_state = 0.0 if parcor_states is None else float(parcor_states[i])
-            self._fence()
+        def fill(track, i):
+            C.memmove(C.byref(track), C.byref(arr[i]), C.sizeof(Track))
+            track.parcor_state = 0.0 if parcor_states is None else float(parcor_states[i])
+
+        def call(sub, which):
             if all_plain:
-                ret = lib.LINNEAmd_EncodeStreamsDevice(self.h, sub, len(which), int(group_frames))
-            else:
-                ret = lib.LINNEAmd_EncodeStreamsDeviceLayout(self.h, sub, sublay, len(which), int(group_frames))
-            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
-            if ret != 0 and not msg.startswith("track "):                # (a failing track's text starts with its number)
-                raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
-            for j, i in enumerate(which):
-                codes[i], states[i], nbytes[i] = int(sub[j].result), float(sub[j].parcor_state), int(sub[j].out_bytes)
-                streams[i] = flat[offs[j]:offs[j] + nbytes[i]] if codes[i] == 0 else None
-            return ret, msg
+                return lib.LINNEAmd_EncodeStreamsDevice(self.h, sub, len(which), int(group_frames))
+            sublay = (PcmLayout * max(len(which), 1))(*[lays[i] for i in which])
+            return lib.LINNEAmd_EncodeStreamsDeviceLayout(self.h, sub, sublay, len(which), int(group_frames))
 
-        codes, states, nbytes, streams = [0] * T, [0.0] * T, [0] * T, [None] * T
-        ret, msg = run(list(range(T)), rooms)
-        again = [i for i in range(T) if codes[i] == 3 and nbytes[i] > rooms[i]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
-        if again:
-            run(again, [nbytes[i] for i in again])
-            bad = [i for i in range(T) if codes[i] != 0]
-            ret = codes[bad[0]] if bad else 0
-            msg = f"track {bad[0]} failed" if bad else ""
-        if ret != 0 and not return_codes:
-            raise LinneAmdError(f"EncodeStreamsDevice -> {ret}: {msg}", ret, codes)
+        def read(i, j, track, stream):
+            states[i], streams[i] = float(track.parcor_state), stream
+        codes, failed = self._write_streams("EncodeStreamsDevice", "track", Track, rooms, fill, call, read)
+        if failed and not return_codes:
+            raise failed
         if self._verify:
             self._verified(streams, keep, "EncodeStreamsDevice")
         out = (streams,) if parcor_states is None else (streams, states)
@@ -1456,61 +1466,30 @@ class Context:
         LINNEApiResults when an output fails; with return_codes -> (streams, codes), and only a failure of the whole call raises.
         group_frames bounds the edge blocks decoded and encoded per pass and never changes a byte.  Afterwards self.last_splice_blocks
         holds every output's (copied, re-encoded) block counts"""
-        import torch
-        dev = f"cuda:{self.device}"
-        K = len(splices)
-        arr = (Splice * max(K, 1))()
-        keep, rooms = [], []
+        keep, cutlists, rooms = [], [], []
         for k, cuts in enumerate(splices):
             cs = (Cut * max(len(cuts), 1))()
             room = 30
             for i, (data, index, first, n) in enumerate(cuts):
                 t = self._stream_bytes(data)
-                assert index.nbytes == t.numel(), f"splice {k}, cut {i}: the index was built for a stream of another length"
-                first = int(first)
-                n = index.header["num_samples"] - first if n is None else int(n)
-                cs[i].index, cs[i].d_stream, cs[i].first_sample = index.h, t.data_ptr(), first
-                cs[i].num_samples = n if n >= 0 else (1 << 64) - 1
+                first, _, count = _sample_range(index, t.numel(), first, n, "splice %d, cut %d", k, i)
+                cs[i].index, cs[i].d_stream, cs[i].first_sample, cs[i].num_samples = index.h, t.data_ptr(), first, count
                 keep.append(t)
                 room += t.numel() + 2 * (64 + index.header["num_channels"] * index.header["num_samples_per_block"] * 8)
-            keep.append(cs)
-            arr[k].cuts, arr[k].num_cuts = cs, len(cuts)
+            cutlists.append((cs, len(cuts)))
             rooms.append(room)
+        streams, counts = [None] * len(splices), [(0, 0)] * len(splices)
 
-        codes, nbytes, streams = [0] * K, [0] * K, [None] * K
+        def fill(splice, k):
+            splice.cuts, splice.num_cuts = cutlists[k]
 
-        def run(which, sizes):
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += (n + 3) & ~3
-            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
-            sub = (Splice * max(len(which), 1))()
-            for j, k in enumerate(which):
-                sub[j].cuts, sub[j].num_cuts = arr[k].cuts, arr[k].num_cuts
-                sub[j].d_out, sub[j].capacity = flat.data_ptr() + offs[j], sizes[j]
-            self._fence()
-            ret = lib.LINNEAmd_SpliceStreamsDevice(self.h, sub, len(which), int(group_frames))
-            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
-            if ret != 0 and not msg.startswith("splice "):              # (a failing output's text starts with its number)
-                raise LinneAmdError(f"SpliceStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
-            for j, k in enumerate(which):
-                codes[k], nbytes[k] = int(sub[j].result), int(sub[j].out_bytes)
-                streams[k] = flat[offs[j]:offs[j] + nbytes[k]] if codes[k] == 0 else None
-                counts[k] = (int(sub[j].copied_blocks), int(sub[j].encoded_blocks))
-            return ret, msg
-
-        counts = [(0, 0)] * K
-        ret, msg = run(list(range(K)), rooms)
-        again = [k for k in range(K) if codes[k] == 3 and nbytes[k] > rooms[k]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
-        if again:
-            run(again, [nbytes[k] for k in again])
-            bad = [k for k in range(K) if codes[k] != 0]
-            ret = codes[bad[0]] if bad else 0
-            msg = f"splice {bad[0]} failed" if bad else ""
+        def read(k, j, splice, stream):
+            streams[k], counts[k] = stream, (int(splice.copied_blocks), int(splice.encoded_blocks))
+        codes, failed = self._write_streams("SpliceStreamsDevice", "splice", Splice, rooms, fill,
+                                            lambda sub, which: lib.LINNEAmd_SpliceStreamsDevice(self.h, sub, len(which), int(group_frames)), read)
         self.last_splice_blocks = counts
-        if ret != 0 and not return_codes:
-            raise LinneAmdError(f"SpliceStreamsDevice -> {ret}: {msg}", ret, codes)
+        if failed and not return_codes:
+            raise failed
         return (streams, codes) if return_codes else streams
 
     def last_splice_count(self, which):
@@ -1528,7 +1507,6 @@ class Context:
         Raises LinneAmdError with .code = the call's result and .codes = the per-stream LINNEApiResults when a stream fails; with
         return_codes -> (list, codes), and only a failure of the whole call raises"""
         import torch
-        dev = f"cuda:{self.device}"
         T = len(streams)
         keep = [self._stream_bytes(s) for s in streams]
         whole = [k for k in range(T) if keep[k].numel() >= 30]              # the headers' sample counts and block sizes: one copy
@@ -1538,42 +1516,20 @@ class Context:
             n, s = int.from_bytes(bytes(row[14:18]), "big"), int.from_bytes(bytes(row[24:28]), "big")
             rooms[k] = keep[k].numel() + 11 * (n // max(min(s, 65535), 1) + 2)
         out = [(None, None)] * T
-        codes = [0] * T
 
-        def run(which, sizes):
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += (n + 3) & ~3
-            flat = torch.empty(max(at, 4), dtype=torch.uint8, device=dev)
-            sub = (Repair * max(len(which), 1))()
-            for j, k in enumerate(which):
-                sub[j].d_stream, sub[j].stream_bytes = keep[k].data_ptr(), keep[k].numel()
-                sub[j].d_out, sub[j].capacity = flat.data_ptr() + offs[j], sizes[j]
-            self._fence()
-            ret = lib.LINNEAmd_RepairStreamsDevice(self.h, sub, len(which))
-            msg = lib.LINNEAmd_GetLastError(self.h).decode() if ret != 0 else ""
-            if ret != 0 and not msg.startswith("repair "):              # (a failing stream's text starts with its number)
-                raise LinneAmdError(f"RepairStreamsDevice -> {ret}: {msg}", ret, [int(sub[j].result) for j in range(len(which))])
-            for j, k in enumerate(which):
-                r = sub[j]
-                codes[k] = int(r.result)
-                report = {f: int(getattr(r, f)) for f in ("out_bytes", "result", "kept_blocks", "fill_blocks", "num_gaps", "lost_samples", "exact")}
-                gaps, n = C.POINTER(Gap)(), C.c_uint32(0)
-                self._check(lib.LINNEAmd_GetLastRepairGaps(self.h, j, C.byref(gaps), C.byref(n)), "GetLastRepairGaps")
-                report["gaps"] = [{f: int(getattr(gaps[i], f)) for f in ("first_sample", "num_samples", "src_offset", "src_bytes", "fill_blocks")} for i in range(n.value)]
-                out[k] = (flat[offs[j]:offs[j] + report["out_bytes"]] if codes[k] == 0 else None, report)
-            return ret, msg
+        def fill(r, k):
+            r.d_stream, r.stream_bytes = keep[k].data_ptr(), keep[k].numel()
 
-        ret, msg = run(list(range(T)), rooms)
-        again = [k for k in range(T) if codes[k] == 3 and out[k][1]["out_bytes"] > rooms[k]]      # LINNE_APIRESULT_INSUFFICIENT_BUFFER: once more at the exact size
-        if again:
-            run(again, [out[k][1]["out_bytes"] for k in again])
-            bad = [k for k in range(T) if codes[k] != 0]
-            ret = codes[bad[0]] if bad else 0
-            msg = f"repair {bad[0]} failed" if bad else ""
-        if ret != 0 and not return_codes:
-            raise LinneAmdError(f"RepairStreamsDevice -> {ret}: {msg}", ret, codes)
+        def read(k, j, r, stream):
+            report = {f: int(getattr(r, f)) for f in ("out_bytes", "result", "kept_blocks", "fill_blocks", "num_gaps", "lost_samples", "exact")}
+            gaps, n = C.POINTER(Gap)(), C.c_uint32(0)
+            self._check(lib.LINNEAmd_GetLastRepairGaps(self.h, j, C.byref(gaps), C.byref(n)), "GetLastRepairGaps")      # (j: the stream's number within that call)
+            report["gaps"] = [{f: int(getattr(gaps[i], f)) for f in ("first_sample", "num_samples", "src_offset", "src_bytes", "fill_blocks")} for i in range(n.value)]
+            out[k] = (stream, report)
+        codes, failed = self._write_streams("RepairStreamsDevice", "repair", Repair, rooms, fill,
+                                            lambda sub, which: lib.LINNEAmd_RepairStreamsDevice(self.h, sub, len(which)), read)
+        if failed and not return_codes:
+            raise failed
         return (out, codes) if return_codes else out
 
     def last_repair_count(self, which):
