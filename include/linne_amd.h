@@ -418,6 +418,12 @@ enum LINNEAmdRelateTimingKind {
 enum LINNEAmdMixTimingKind {
     LINNE_AMD_MIX_T_MIX = 98                /* every window's sample frames through its channel matrix into its output (k_wx_mix) */
 };
+/* resampling windows (LINNEAmd_ResampleWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice -- its kind 59 places the windows' input
+ * samples into the call's scratch --, and one launch each of kinds 99 and 100 per call that takes a pass) */
+enum LINNEAmdResampleTimingKind {
+    LINNE_AMD_RESAMPLE_T_PRESET = 99,       /* the call's input images zeroed, once, in front of the first pass (k_wx_resample_preset) */
+    LINNE_AMD_RESAMPLE_T_RESAMPLE = 100     /* the outputs of the windows that did not fail filtered from their input images, once, behind the last pass (k_wx_resample) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -922,6 +928,60 @@ int LINNEAmd_MixWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow
         const struct LINNEAmdMixSpec *specs /* [num_windows] */,
         struct LINNEAmdPcmLayout *layouts /* [num_windows] in/out; NULL: int32 planar, pcm_stride */,
         uint32_t num_windows, uint32_t group_frames);
+
+/* ---- resampling windows of resident streams: a rational rate change L/M through an exact int16 polyphase FIR, on decode ----
+ * LINNEAmd_ResampleWindowsDevice takes the windows and layouts of LINNEAmd_DecodeWindowsDeviceLayout, but a window's first_sample and
+ * num_samples count OUTPUT samples of the resampled stream, which has LINNEAmd_ResampleLength(N, L, M) = ceil(N * L / M) samples, N the
+ * header's num_samples, L = specs[i].up, M = specs[i].down.  With x[c][i] the values LINNEAmd_DecodeStreamDevice gives for channel c,
+ * sample i of the stream, and x = 0 for i < 0 and i >= N, output sample m of channel c of the resampled stream is, with all index
+ * arithmetic in 64 bits,
+ *   1. the place  t = m * M, p = t % L, n = t / L;
+ *   2. the sum    acc = sum over k < P of (int64)coef[p * P + k] * x[c][n - before + k], P = taps   (a product is at most 2^46 in
+ *                 magnitude, 64 of them 2^52: nothing wraps);
+ *   3. the shift, the clip and the layout's conversion: steps 2 to 4 of LINNEAmd_MixWindowsDevice, word for word, and its rule for
+ *      layouts[i].saturated.
+ * Zero-stuffed samples are never formed: this is the polyphase form.  With L = M = P = 1, coef = {1} and shift 0 the call writes what
+ * LINNEAmd_DecodeWindowsDeviceLayout writes.  The output has the stream's channel count.  The rest of the contract is
+ * LINNEAmd_DecodeWindowsDeviceLayout's: per-window results ("window <i>: ResampleWindowsDevice: ..." for this call's own checks), a
+ * failing window's memory never written and the others undisturbed, the lowest failing window's code returned, shape groups, passes,
+ * group_frames (which never changes a byte), copies, the one host synchronisation and whole-call failures -- with two rules adapted:
+ * the range check uses the resampled length where that call uses N, and the index's failing block fails a window when it lies at or
+ * before the last INPUT sample the window reads (sample n - before + P - 1 of its last output, or N - 1 where that lies behind the
+ * stream).  For window i alone INVALID_ARGUMENT when up or down is outside 1 .. LINNE_AMD_RESAMPLE_MAX_RATIO, taps outside
+ * 1 .. LINNE_AMD_RESAMPLE_MAX_TAPS, up * taps > LINNE_AMD_RESAMPLE_MAX_COEFS, before > taps - 1, shift > 31, clip_bits is 1 or above
+ * 32, coef is NULL or reserved is not 0; these are checked in front of the range.  Windows with different specs, ratios and stream
+ * shapes may share a call; windows that name the same (coef, up, taps) share one device copy of the table, which is read during the
+ * call only.
+ * Scratch: beside a pass's, the call keeps an int32 image of every live window's input range, halo included --
+ * 4 * C * (n(last) - n(first) + P, rounded up to 4) bytes per window -- in the context's scratch; where that cannot be had the whole
+ * call fails with NG and nothing is written.  A pass has the decode call's launches (its kind 59 writes the images); a call that takes
+ * a pass adds one launch of kind 99 in front of the first pass and one of kind 100 behind the last, whatever num_windows, L, M and P
+ * are.  num_windows == 0 is OK; a NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the
+ * context's stream and synchronous. */
+#define LINNE_AMD_RESAMPLE_MAX_TAPS   64      /* P: taps per phase */
+#define LINNE_AMD_RESAMPLE_MAX_RATIO  1024    /* L and M */
+#define LINNE_AMD_RESAMPLE_MAX_COEFS  16384   /* L * P */
+struct LINNEAmdResampleSpec {
+    uint32_t up, down;                  /* L, M: 1 .. LINNE_AMD_RESAMPLE_MAX_RATIO; need not be coprime */
+    uint32_t taps;                      /* P: 1 .. LINNE_AMD_RESAMPLE_MAX_TAPS */
+    uint32_t before;                    /* 0 .. P - 1: input samples the filter reaches back */
+    uint32_t shift;                     /* 0 .. 31 */
+    uint32_t clip_bits;                 /* 0 (32), or 2 .. 32, as in struct LINNEAmdMixSpec */
+    uint64_t reserved;                  /* 0 */
+    const int16_t *coef;                /* HOST memory, [L][P]: coef[p * P + k] */
+};
+int LINNEAmd_ResampleWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        const struct LINNEAmdResampleSpec *specs /* [num_windows] */,
+        struct LINNEAmdPcmLayout *layouts /* [num_windows] in/out; NULL: int32 planar, pcm_stride */,
+        uint32_t num_windows, uint32_t group_frames);
+/* ceil(num_samples * up / down), 0 where down is 0; the product is formed in 128 bits, and a quotient no uint64 holds gives UINT64_MAX */
+uint64_t LINNEAmd_ResampleLength(uint64_t num_samples, uint32_t up, uint32_t down);
+/* A filter for the call above: a Kaiser-windowed sinc prototype of up * taps points (beta 8) with its cutoff at the lower of the two
+ * Nyquist rates, split into `up` phases of `taps` coefficients and quantised to int16 so that every phase sums to exactly 1 << *shift
+ * (the rounding remainder goes to the phase's largest tap): a constant input gives the same constant.  *before centres the filter:
+ * (taps - 1) / 2.  up, down and taps are checked as the spec's are (INVALID_ARGUMENT, as for a NULL pointer); otherwise OK.  Pure host
+ * code: no device is needed. */
+int LINNEAmd_ResampleDesign(uint32_t up, uint32_t down, uint32_t taps, int16_t *coef /* [up][taps] */, uint32_t *shift, uint32_t *before);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

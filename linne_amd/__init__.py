@@ -62,6 +62,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_DigestWindowsDevice",
     "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice", "LINNEAmd_RelateWindowsDevice",
     "LINNEAmd_MixWindowsDevice",
+    "LINNEAmd_ResampleWindowsDevice", "LINNEAmd_ResampleLength", "LINNEAmd_ResampleDesign",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -273,6 +274,48 @@ class MixSpec(C.Structure):
     """struct LINNEAmdMixSpec (include/linne_amd.h)"""
     _fields_ = [("out_channels", C.c_uint32), ("shift", C.c_uint32), ("clip_bits", C.c_uint32), ("reserved", C.c_uint32),
                 ("coef", (C.c_int16 * 8) * 8)]
+
+
+class ResampleSpec(C.Structure):
+    """struct LINNEAmdResampleSpec (include/linne_amd.h); coef is host memory"""
+    _fields_ = [("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32), ("before", C.c_uint32), ("shift", C.c_uint32),
+                ("clip_bits", C.c_uint32), ("reserved", C.c_uint64), ("coef", C.POINTER(C.c_int16))]
+
+
+RESAMPLE_MAX_TAPS, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_COEFS = 64, 1024, 16384     # include/linne_amd.h LINNE_AMD_RESAMPLE_MAX_*
+
+
+def resample_ratio(rate_in, rate_out):
+    """the rate change rate_in -> rate_out as (up, down), reduced by their greatest common divisor; ValueError when a rate is not
+    positive or either of the two exceeds RESAMPLE_MAX_RATIO.  Pure host code"""
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in < 1 or rate_out < 1:
+        raise ValueError(f"sampling rates are positive: {rate_in} -> {rate_out}")
+    g = math.gcd(rate_in, rate_out)
+    up, down = rate_out // g, rate_in // g
+    if up > RESAMPLE_MAX_RATIO or down > RESAMPLE_MAX_RATIO:
+        raise ValueError(f"{rate_in} -> {rate_out} is {up}/{down}: beyond {RESAMPLE_MAX_RATIO}")
+    return up, down
+
+
+def resample_length(num_samples, up, down):
+    """LINNEAmd_ResampleLength: ceil(num_samples * up / down)"""
+    return int(lib.LINNEAmd_ResampleLength(int(num_samples), int(up), int(down)))
+
+
+def resample_design(up, down, taps=32):
+    """LINNEAmd_ResampleDesign, the one designer there is -> (coef int16 (up, taps), shift, before); ValueError for arguments outside
+    the call's bounds.  Pure host code: no device is needed"""
+    up, down, taps = int(up), int(down), int(taps)
+    if not (0 <= up < 1 << 32 and 0 <= down < 1 << 32 and 0 <= taps < 1 << 32):
+        raise ValueError("up, down and taps are unsigned")
+    fits = up * taps <= RESAMPLE_MAX_COEFS
+    coef = np.zeros((max(up, 1), max(taps, 1)) if fits else (1, 1), dtype=np.int16)
+    shift, before = C.c_uint32(0), C.c_uint32(0)
+    ret = lib.LINNEAmd_ResampleDesign(up, down, taps, coef.ctypes.data_as(C.POINTER(C.c_int16)), C.byref(shift), C.byref(before))
+    if ret != 0:
+        raise ValueError(f"resample_design({up}, {down}, {taps}) -> {ret}: up and down are 1 .. {RESAMPLE_MAX_RATIO}, taps 1 .. {RESAMPLE_MAX_TAPS}, up * taps <= {RESAMPLE_MAX_COEFS}")
+    return coef, int(shift.value), int(before.value)
 
 
 RELATION_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("num_equal", "<u8"), ("num_opposite", "<u8")])
@@ -512,6 +555,10 @@ def _load():
     L.LINNEAmd_HistogramWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(HistogramSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_RelateWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(RelateSpec), C.c_uint32, C.c_uint32]
     L.LINNEAmd_MixWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(MixSpec), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_ResampleWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(ResampleSpec), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_ResampleLength.restype = C.c_uint64
+    L.LINNEAmd_ResampleLength.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    L.LINNEAmd_ResampleDesign.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -972,7 +1019,8 @@ class Context:
         import torch
         W = len(windows)
         arr, keep, ranges = self._windows_array(windows)
-        shapes = [(x.header["num_channels"] if specs is None else int(specs[i].out_channels), max(n, 0)) for i, (x, _, n) in enumerate(ranges)]
+        mixes = specs is not None and specs._type_ is MixSpec      # (otherwise the specs are ResampleSpec: the stream's channels, ranges of output samples)
+        shapes = [(int(specs[i].out_channels) if mixes else x.header["num_channels"], max(n, 0)) for i, (x, _, n) in enumerate(ranges)]
         dev = f"cuda:{self.device}"
         if s24:
             assert dtype in (None, torch.uint8), "s24 samples are uint8 triples"
@@ -1016,9 +1064,11 @@ class Context:
             ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
         elif specs is None:
             ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
-        else:
+        elif mixes:
             ret = lib.LINNEAmd_MixWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice" if specs is None else "MixWindowsDevice", return_codes)
+        else:
+            ret = lib.LINNEAmd_ResampleWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice" if specs is None else "MixWindowsDevice" if mixes else "ResampleWindowsDevice", return_codes)
         res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
         return res[0] if len(res) == 1 else res
 
@@ -1072,6 +1122,81 @@ class Context:
             pcms = self.mix_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], matrix, shift=shift, clip_bits=obits, group_frames=group_frames)
             tracks = [(pcm, b, h["sampling_rate"], int(block) if block is not None else h["num_samples_per_block"],
                        int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else (h["ch_process_method"] if pcm.shape[0] > 1 else 0))
+                      for pcm, b, h in zip(pcms, obits, heads)]
+            return self.encode_streams(tracks, group_frames=group_frames)
+
+    def resample_windows(self, windows, up, down, coef=None, taps=32, before=None, shift=None, clip_bits=0, out=None, group_frames=0,
+                         return_codes=False, dtype=None, channels_last=False, s24=False, return_saturated=False):
+        """decode_windows at another sampling rate: a rational rate change up/down through an exact int16 polyphase FIR between the
+        samples and the PCM (include/linne_amd.h LINNEAmd_ResampleWindowsDevice states the arithmetic).  A window's first_sample and
+        num_samples count OUTPUT samples of the resampled stream, which has resample_length(N, up, down) of them; num_samples None: to
+        its end.  up, down: one value for all windows or one per window.  coef: an int16 array (up, taps) for all windows, or a
+        sequence of them, one per window, with `before` (default (taps - 1) // 2 of the array) and `shift` (default 0) one value or one
+        per window; coef None designs the filter of `taps` coefficients per phase (resample_design) and takes its shift and before.
+        clip_bits as mix_windows has it.  Values outside the call's bounds raise ValueError before any call.  Everything else --
+        out, dtype, channels_last, s24, return_codes, return_saturated, group_frames, errors -- is decode_windows'"""
+        W = len(windows)
+        ups, downs = _per_window(up, W, "up", lo=None), _per_window(down, W, "down", lo=None)
+        clips = _per_window(clip_bits, W, "clip_bits", lo=None)
+        if coef is None:
+            made = {}
+            for u, d in zip(ups, downs):
+                if (u, d) not in made:
+                    made[(u, d)] = resample_design(u, d, taps)
+            tables = [made[(u, d)][0] for u, d in zip(ups, downs)]
+            shifts = [made[(u, d)][1] for u, d in zip(ups, downs)] if shift is None else _per_window(shift, W, "shift", lo=None)
+            befores = [made[(u, d)][2] for u, d in zip(ups, downs)] if before is None else _per_window(before, W, "before", lo=None)
+        else:
+            one = isinstance(coef, np.ndarray) and coef.ndim == 2
+            given = [coef] * W if one else list(coef)
+            assert len(given) == W, "coef is one (up, taps) array, or one per window"
+            tables, same = [], {}
+            for i, m in enumerate(given):
+                if id(m) not in same:                                # (windows that share an array share its device copy)
+                    a = np.asarray(m)
+                    if a.ndim != 2 or a.dtype.kind not in "iu" or a.size == 0:
+                        raise ValueError(f"window {i}: coef is an integer array (up, taps); got {a.dtype} {a.shape}")
+                    if int(a.min()) < -32768 or int(a.max()) > 32767:
+                        raise ValueError(f"window {i}: a coefficient outside int16")
+                    same[id(m)] = np.ascontiguousarray(a, dtype=np.int16)
+                tables.append(same[id(m)])
+            shifts = _per_window(0 if shift is None else shift, W, "shift", lo=None)
+            befores = [(t.shape[1] - 1) // 2 for t in tables] if before is None else _per_window(before, W, "before", lo=None)
+        specs = (ResampleSpec * max(W, 1))()
+        ranged = []
+        for i, w in enumerate(windows):
+            t = tables[i]
+            if t.shape[0] != ups[i]:
+                raise ValueError(f"window {i}: coef has {t.shape[0]} phases, up is {ups[i]}")
+            if not (1 <= ups[i] <= RESAMPLE_MAX_RATIO and 1 <= downs[i] <= RESAMPLE_MAX_RATIO and 1 <= t.shape[1] <= RESAMPLE_MAX_TAPS and t.size <= RESAMPLE_MAX_COEFS):
+                raise ValueError(f"window {i}: up and down are 1 .. {RESAMPLE_MAX_RATIO}, taps 1 .. {RESAMPLE_MAX_TAPS}, up * taps <= {RESAMPLE_MAX_COEFS}")
+            if not (0 <= befores[i] < t.shape[1] and 0 <= shifts[i] <= 31 and (clips[i] == 0 or 2 <= clips[i] <= 32)):
+                raise ValueError(f"window {i}: before is 0 .. taps - 1, shift 0 .. 31, clip_bits 0 or 2 .. 32")
+            sp = specs[i]
+            sp.up, sp.down, sp.taps, sp.before, sp.shift, sp.clip_bits, sp.reserved = ups[i], downs[i], t.shape[1], befores[i], shifts[i], clips[i], 0
+            sp.coef = t.ctypes.data_as(C.POINTER(C.c_int16))
+            stream, index, first, n = w
+            if n is None:
+                n = resample_length(index.header["num_samples"], ups[i], downs[i]) - int(first)
+            ranged.append((stream, index, first, n))
+        return self._place_windows(ranged, specs, out, group_frames, return_codes, dtype, channels_last, s24, return_saturated)
+
+    def resample_streams(self, streams, rate, taps=32, bits=None, preset=None, block=None, ms=None, group_frames=0):
+        """new .lnn streams at the sampling rate `rate`, without the PCM leaving the device: one index_streams call, one
+        resample_windows call over the whole streams into one int32 allocation (the designed filter of `taps` coefficients per phase,
+        clip_bits = the output's bits) and one encode_streams call.  A stream already at `rate` goes the same way, with 1/1.  Every
+        header field not given (bits, preset, block, ms) is the source stream's; sampling_rate is `rate`.  -> a list of uint8 CUDA
+        tensors"""
+        if len(streams) == 0:
+            return []
+        with self._whole_streams(streams) as (ts, indexes, _):
+            heads = [x.header for x in indexes]
+            obits = [int(bits) if bits is not None else h["bits_per_sample"] for h in heads]
+            ratios = [resample_ratio(h["sampling_rate"], rate) for h in heads]
+            pcms = self.resample_windows([(t, x, 0, None) for t, x in zip(ts, indexes)], [r[0] for r in ratios], [r[1] for r in ratios], taps=taps,
+                                         clip_bits=obits, group_frames=group_frames)
+            tracks = [(pcm, b, int(rate), int(block) if block is not None else h["num_samples_per_block"],
+                       int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else h["ch_process_method"])
                       for pcm, b, h in zip(pcms, obits, heads)]
             return self.encode_streams(tracks, group_frames=group_frames)
 

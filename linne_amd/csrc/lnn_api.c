@@ -893,3 +893,77 @@ done:
     for (i = 0; i < ngalloc; i++) dgroup_free(&grp[i]);
     return (LINNEApiResult)ret;
 }
+
+/* ================================================================================================
+ * the filter of LINNEAmd_ResampleWindowsDevice (include/linne_amd.h LINNEAmd_ResampleDesign): host code, no device
+ * ============================================================================================== */
+#include <math.h>
+#include "linne_amd.h"
+
+#define LNN_RESAMPLE_KAISER_BETA 8.0
+/* the modified Bessel function of the first kind, order 0: its power series, whose terms fall below 1e-17 of the sum long before 64 */
+static double resample_bessel_i0(double x)
+{
+    double sum = 1.0, term = 1.0;
+    int k;
+    for (k = 1; k < 64; k++) {
+        term *= (x / (2.0 * k)) * (x / (2.0 * k));
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+/* point j of the prototype of n points: a sinc with its first zeros max(up, down) points from the centre (n - 1) / 2, under a Kaiser window */
+static double resample_prototype(uint32_t j, uint32_t n, uint32_t up, uint32_t down)
+{
+    const double pi = 3.14159265358979323846, centre = 0.5 * ((double)n - 1.0);
+    const double d = fabs((double)j - centre), x = d / (double)(up > down ? up : down);
+    const double r = (n > 1u) ? d / centre : 0.0;
+    const double s = (x == 0.0) ? 1.0 : sin(pi * x) / (pi * x);
+    return s * resample_bessel_i0(LNN_RESAMPLE_KAISER_BETA * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / resample_bessel_i0(LNN_RESAMPLE_KAISER_BETA);
+}
+/* Coefficient k of phase p is point p + (taps - 1 - k) * up of the prototype: the prototype is what the zero-stuffed stream would be
+ * convolved with.  Every phase is scaled to the sum 1 and quantised with 15 fraction bits, or with 14 where a coefficient of some
+ * phase would not fit int16 */
+int LINNEAmd_ResampleDesign(uint32_t up, uint32_t down, uint32_t taps, int16_t *coef, uint32_t *shift, uint32_t *before)
+{
+    uint32_t sh, p, k;
+    if (!coef || !shift || !before) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    if (up < 1u || up > LINNE_AMD_RESAMPLE_MAX_RATIO || down < 1u || down > LINNE_AMD_RESAMPLE_MAX_RATIO) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    if (taps < 1u || taps > LINNE_AMD_RESAMPLE_MAX_TAPS || (uint64_t)up * taps > LINNE_AMD_RESAMPLE_MAX_COEFS) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    for (sh = 15u; sh >= 14u; sh--) {
+        int fits = 1;
+        for (p = 0; p < up && fits; p++) {
+            double h[LINNE_AMD_RESAMPLE_MAX_TAPS], sum = 0.0;
+            int32_t q[LINNE_AMD_RESAMPLE_MAX_TAPS], total = 0;
+            uint32_t big = 0;
+            /* (summed from the ends of the phase towards its middle: the mirrored phase L - 1 - p then has the same sum to the bit) */
+            for (k = 0; k < taps; k++) h[k] = resample_prototype(p + (taps - 1u - k) * up, up * taps, up, down);
+            { uint32_t a = 0, b = taps - 1u;
+              const double ca = 0.5 * ((double)(up * taps) - 1.0);
+              while (a < b) {
+                  const double da = fabs((double)(p + (taps - 1u - a) * up) - ca), db = fabs((double)(p + (taps - 1u - b) * up) - ca);
+                  if (da >= db) sum += h[a++]; else sum += h[b--];
+              }
+              sum += h[a]; }
+            if (!(sum > 0.0)) { fits = 0; break; }
+            for (k = 0; k < taps; k++) {
+                const double v = h[k] / sum * (double)(1u << sh);
+                if (!(v > -40000.0 && v < 40000.0)) { fits = 0; break; }    /* (in front of the narrowing; the exact test is below) */
+                q[k] = (int32_t)lrint(v);
+                total += q[k];
+                if (q[k] > q[big]) big = k;
+            }
+            if (!fits) break;
+            q[big] += (int32_t)(1u << sh) - total;
+            for (k = 0; k < taps; k++) {
+                if (q[k] < -32768 || q[k] > 32767) { fits = 0; break; }
+                coef[(size_t)p * taps + k] = (int16_t)q[k];
+            }
+        }
+        if (fits) break;
+    }
+    if (sh < 14u) return LINNE_APIRESULT_NG;        /* a phase whose coefficients nearly cancel: no such design in int16 */
+    *shift = sh; *before = (taps - 1u) / 2u;
+    return LINNE_APIRESULT_OK;
+}

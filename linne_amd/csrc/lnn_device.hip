@@ -56,6 +56,7 @@
 #include "lnn_k_histogram.h"
 #include "lnn_k_relate.h"
 #include "lnn_k_mix.h"
+#include "lnn_k_resample.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -74,6 +75,7 @@ static_assert(LINNE_AMD_QUIET_T_QUIET == 86 && LINNE_AMD_QUIET_T_ENDS == 91 && L
 static_assert(LINNE_AMD_HISTOGRAM_T_HISTOGRAM == 92 && LINNE_AMD_HISTOGRAM_T_COMMIT == 94, "the histogram call's timing kinds are 92 to 94");
 static_assert(LINNE_AMD_RELATE_T_RELATE == 95 && LINNE_AMD_RELATE_T_COMMIT == 97, "the relate call's timing kinds are 95 to 97");
 static_assert(LINNE_AMD_MIX_T_MIX == 98, "the mix call's timing kind is 98");
+static_assert(LINNE_AMD_RESAMPLE_T_PRESET == 99 && LINNE_AMD_RESAMPLE_T_RESAMPLE == 100, "the resample call's timing kinds are 99 and 100");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2245,9 +2247,12 @@ extern "C" struct LINNEAmdStreamIndex *LINNEAmd_StreamIndexCreate(struct LINNEAm
 struct WxCall;
 /* what a consumer's launches read beside a pass's WxPlaceArgs: its per-window records, its accumulators (behind every pass's scratch,
  * acc_prefix units of its own in front of them) and its words behind the fail and saturation words */
-struct WxLaunch { const WxBucket *side; const WxMix *mix; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask; };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The eight calls are the
- * eight constant instances below; a launch that a consumer does not have is NULL */
+struct WxLaunch {
+    const WxBucket *side; const WxMix *mix; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask;
+    const WxResample *rs; const WxTile *tiles; const uint32_t *coef; uint64_t ntile; uint32_t *sat;        /* the resampling consumer's */
+};
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The nine calls are the
+ * nine constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2262,6 +2267,8 @@ struct WxConsumer {
     /* an OK window's answer into the caller's arrays; words: all that came back (fail words first), NULL for a window that took no pass */
     void (*read_back)(const WxCall &c, uint32_t i, const uint32_t *words);
     bool mixes;                         /* a WxMix beside every window record, from the windows' struct LINNEAmdMixSpec (a consumer without buckets) */
+    bool resamples;                     /* a WxResample beside every window record, from the windows' struct LINNEAmdResampleSpec: the passes place the
+                                         * windows' input ranges into images among the accumulators, the commit filters them (a consumer without buckets) */
 };
 struct WxCall {
     const WxConsumer *use;
@@ -2270,11 +2277,12 @@ struct WxCall {
     const void *specs;                  /* [W] of the consumer's: place, compare and mix struct LINNEAmdPcmLayout (NULL: int32 planar, pcm_stride), measure, digest, quiet, histogram and relate their specs */
     void *answers;                      /* [W] of the consumer's: place and mix the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
     const struct LINNEAmdMixSpec *mix;  /* [W], mix alone: its specs go beside its layouts */
+    const struct LINNEAmdResampleSpec *rs;      /* [W], resample alone, likewise */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
     WxCall c;
-    c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL;
+    c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL; c.rs = NULL;
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
@@ -2500,14 +2508,49 @@ static int wx_mix_pass(LINNEAmdContext *ctx, const WxLaunch &l, const WxPlaceArg
     return LNN_OK;
 }
 
-static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false };
-static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false };
-static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false };
-static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL, false };
-static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back, false };
-static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL, false };
-static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL, false };
-static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_mix_check, wx_mix_describe, NULL, wx_mix_pass, NULL, wx_place_read_back, true };
+/* ---- resample: the passes place the windows' input ranges into images; the commit filters the outputs from them (lnn_k_resample.h) ---- */
+/* the spec's own bounds, which the range check needs in front of it */
+static int wx_resample_spec_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdResampleSpec &s = c.rs[i];
+    const char *who = c.use->name;
+    if (s.up < 1u || s.up > LINNE_AMD_RESAMPLE_MAX_RATIO || s.down < 1u || s.down > LINNE_AMD_RESAMPLE_MAX_RATIO) { snprintf(err, cap, "%s: up %u / down %u is not 1 .. %u", who, s.up, s.down, (unsigned)LINNE_AMD_RESAMPLE_MAX_RATIO); return LNN_INVALID_ARGUMENT; }
+    if (s.taps < 1u || s.taps > LINNE_AMD_RESAMPLE_MAX_TAPS) { snprintf(err, cap, "%s: taps %u is not 1 .. %u", who, s.taps, (unsigned)LINNE_AMD_RESAMPLE_MAX_TAPS); return LNN_INVALID_ARGUMENT; }
+    if ((uint64_t)s.up * s.taps > LINNE_AMD_RESAMPLE_MAX_COEFS) { snprintf(err, cap, "%s: up %u * taps %u > %u coefficients", who, s.up, s.taps, (unsigned)LINNE_AMD_RESAMPLE_MAX_COEFS); return LNN_INVALID_ARGUMENT; }
+    if (s.before > s.taps - 1u) { snprintf(err, cap, "%s: before %u > taps - 1", who, s.before); return LNN_INVALID_ARGUMENT; }
+    if (s.shift > 31u) { snprintf(err, cap, "%s: shift %u > 31", who, s.shift); return LNN_INVALID_ARGUMENT; }
+    if (s.clip_bits == 1u || s.clip_bits > 32u) { snprintf(err, cap, "%s: clip_bits %u is neither 0 nor 2 .. 32", who, s.clip_bits); return LNN_INVALID_ARGUMENT; }
+    if (s.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", who); return LNN_INVALID_ARGUMENT; }
+    if (!s.coef) { snprintf(err, cap, "%s: null coef", who); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static int wx_resample_check(const WxCall &c, uint32_t i, char *err, size_t cap) { return wx_pcm_check(c, i, c.win[i].index->shape.num_channels, true, err, cap); }
+/* (behind wx_decode's own: the planned range becomes the window's input range) */
+static void wx_resample_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    wx_pcm_describe(c, i, r);
+    r.rs = c.rs + i; r.m_lo = r.lo; r.m_n = r.n;
+    const WxrInput in = wxr_input(r.m_lo, r.m_n, c.rs[i], c.win[i].index->header.num_samples);
+    r.lo = in.lo; r.n = in.hi - in.lo;
+}
+static int wx_resample_preset(LINNEAmdContext *ctx, const WxLaunch &l) { SX_LAUNCH(NULL, LINNE_AMD_RESAMPLE_T_PRESET, k_wx_resample_preset, wx_grid(l.nacc / 4u), dim3(WXB_THREADS), 0, ctx->stream, (uint4 *)l.acc, l.nacc / 4u); return LNN_OK; }
+static int wx_resample_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxResampleArgs ra;
+    ra.tiles = l.tiles; ra.ntiles = (uint32_t)l.ntile; ra.rwin = l.rs; ra.fail = l.fail; ra.sat = l.sat; ra.acc = (const int32_t *)l.acc; ra.coef = l.coef;
+    SX_LAUNCH(NULL, LINNE_AMD_RESAMPLE_T_RESAMPLE, k_wx_resample, dim3(ra.ntiles), dim3(WXR_TILE), 0, ctx->stream, ra);
+    return LNN_OK;
+}
+
+static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false, false };
+static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false, false };
+static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false, false };
+static const WxConsumer WX_DIGEST = { "DigestWindowsDevice", 0u, NULL, WX_BUCKETS_PER_FRAME, sizeof(uint32_t), WXD_POW_WORDS, wx_digest_check, wx_digest_describe, wx_digest_preset, wx_digest_pass, wx_digest_commit, NULL, false, false };
+static const WxConsumer WX_QUIET = { "QuietWindowsDevice", WXQ_BACK_WORDS, wx_quiet_back_preset, WX_BITMASK, sizeof(uint64_t), 0u, wx_quiet_check, wx_quiet_describe, wx_quiet_preset, wx_quiet_pass, wx_quiet_commit, wx_quiet_read_back, false, false };
+static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_BUCKETS_PER_BIN, sizeof(uint32_t), 0u, wx_histogram_check, wx_histogram_describe, wx_histogram_preset, wx_histogram_pass, wx_histogram_commit, NULL, false, false };
+static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL, false, false };
+static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_mix_check, wx_mix_describe, NULL, wx_mix_pass, NULL, wx_place_read_back, true, false };
+static const WxConsumer WX_RESAMPLE = { "ResampleWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_resample_check, wx_resample_describe, wx_resample_preset, wx_place_pass, wx_resample_commit, wx_place_read_back, false, true };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2517,14 +2560,16 @@ static int wx_check_window(const LINNEAmdContext *ctx, const WxCall &c, uint32_t
     const struct LINNEAmdWindow *w = &c.win[i];
     const LINNEAmdStreamIndex *x = w->index;
     err[0] = 0;
+    if (c.rs) SX_TRY(wx_resample_spec_check(c, i, err, cap));      /* (in front of everything: the range check needs the ratio) */
     if (!x || !w->d_stream) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (c.use->bucketing == WX_NO_BUCKETS && !w->d_pcm && w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
-    const uint64_t total = x->header.num_samples;
+    uint64_t total = x->header.num_samples;
+    if (c.rs) total = wxr_length(total, c.rs[i].up, c.rs[i].down);         /* the range is one of the resampled stream */
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
     SX_TRY(c.use->check(c, i, err, cap));
     if (w->num_samples == 0) return LNN_OK;
-    const uint64_t hi = w->first_sample + w->num_samples;
+    const uint64_t hi = c.rs ? wxr_input(w->first_sample, w->num_samples, c.rs[i], x->header.num_samples).hi : w->first_sample + w->num_samples;
     *r1 = (hi - 1u < x->covered) ? wx_block_of(x->h_first, x->nb, hi - 1u) : x->nb;
     if (x->fail_block >= 0 && (uint64_t)x->fail_block <= *r1) {
         snprintf(err, cap, "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
@@ -2563,28 +2608,38 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     default: break;
     }
     if (!pl.nlive) return LNN_OK;
+    if (u.resamples) {
+        wx_resample_count(rg.data(), W, pl);
+        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory */
-    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : 0u);
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples);
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
     for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
     if (u.back_preset) u.back_preset((uint32_t *)(hs_ + ls.o_back), W);
     wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
-            (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL);
+            (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL,
+            u.resamples ? (WxResample *)(hs_ + ls.o_side) : NULL, u.resamples ? (WxTile *)(hs_ + ls.o_tile) : NULL, u.resamples ? (uint32_t *)(hs_ + ls.o_coef) : NULL);
     for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
     const uint64_t o_acc = align_up(pl.scratch_bytes);             /* (the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
     WxLaunch ln;
     ln.side = (const WxBucket *)(wd + ls.o_side); ln.mix = (const WxMix *)(wd + ls.o_side); ln.wins = d_win; ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
     ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout; ln.nmask = pl.nmask;
+    ln.rs = (const WxResample *)(wd + ls.o_side); ln.tiles = (const WxTile *)(wd + ls.o_tile); ln.coef = (const uint32_t *)(wd + ls.o_coef); ln.ntile = pl.ntile; ln.sat = d_fail + W;
+    if (u.resamples) {                  /* the plan named the images by their offsets: now they have an address */
+        WxWindow *h_win = (WxWindow *)(hs_ + ls.o_win);
+        for (uint32_t k = 0; k < pl.nwin; k++) h_win[k].out = ln.acc + (uintptr_t)h_win[k].out;
+    }
     if (!ctx->outer_keep) ctx->nspans = 0;
     if (ctx->timing && !ctx->outer_keep) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(wd, hs_, ls.bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -2726,6 +2781,16 @@ extern "C" int LINNEAmd_MixWindowsDevice(struct LINNEAmdContext *ctx, struct LIN
     c.mix = specs;
     return wx_entry(ctx, c, windows && specs);
 }
+
+/* the windows are ranges of the stream resampled by a ratio per window, through a polyphase FIR per window, on their way into the PCM */
+extern "C" int LINNEAmd_ResampleWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, const struct LINNEAmdResampleSpec *specs,
+        struct LINNEAmdPcmLayout *layouts, uint32_t num_windows, uint32_t group_frames)
+{
+    WxCall c = wx_call(&WX_RESAMPLE, windows, num_windows, group_frames, layouts, layouts);
+    c.rs = specs;
+    return wx_entry(ctx, c, windows && specs);
+}
+extern "C" uint64_t LINNEAmd_ResampleLength(uint64_t num_samples, uint32_t up, uint32_t down) { return wxr_length(num_samples, up, down); }
 
 /* one window of one stream */
 extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *x, const uint8_t *d_stream,

@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs, histogram, relate and mix; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram, relate, mix and resample; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -21,6 +21,8 @@
 #include <assert.h>
 #include <stdint.h>
 #include <string.h>
+#include <map>
+#include <tuple>
 #include <vector>
 
 #include "linne_amd.h"
@@ -87,6 +89,27 @@ struct WxMix {
 };
 static_assert(sizeof(WxMix) == 160 && sizeof(WxMix) % 16 == 0, "a mix record is 160 bytes");
 
+/* one window's resampling (128 bytes), at its WxWindow's index: what the resampling consumer (lnn_k_resample.h) keeps per window.  That
+ * consumer's WxWindow names the window's INPUT range and, as its output, the window's int32 planar image in the accumulators; the
+ * PCM the caller named is here */
+struct WxResample {
+    void *out; uint64_t stride, sstride;        /* the caller's PCM: element (ch, i) at out + (ch * stride + i * sstride) elements of fmt */
+    uint64_t m_lo, m_hi;                /* the output samples [m_lo, m_hi) of the resampled stream */
+    uint64_t n_first;                   /* n of output m_lo: word j of a channel of the image is stream sample n_first - before + j */
+    uint64_t img, istride;              /* the image's first word among the accumulators; words from one channel to the next */
+    uint64_t coef;                      /* its table's first word in the call's coefficient area */
+    uint32_t up, down, taps, shift;
+    int32_t lo, hi;                     /* the clip */
+    uint32_t scale_bits;                /* the float 2^-(Bf - 1), as in WxMix */
+    uint32_t fidx, fmt, C;              /* its fail word; LINNE_AMD_PCM_*; the stream's channels */
+    uint32_t prow;                      /* 32-bit words of a phase's row in the table: (taps + 1) / 2, a pair of coefficients each */
+    uint32_t reserved[3];
+};
+/* 256 outputs of one window: output m0 reads from stream sample n0 - before on, through phase p0 (m0 * down = n0 * up + p0) */
+struct WxTile { uint32_t win, p0; uint64_t m0, n0; };
+static_assert(sizeof(WxResample) == 128 && sizeof(WxTile) == 24, "a resample record is 128 bytes, a tile 24");
+#define WXR_TILE 256u
+
 /* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
 #define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
 #define WXH_BINS(h) ((h) & 0xFFFFu)
@@ -120,6 +143,8 @@ struct WxRange {
     uint64_t quiet_min, quiet_capacity; uint32_t quiet_threshold;       /* the bitmask consumer: its spec beside bucket_out (quiet_min >= 1) */
     uint32_t hist;                      /* the per-bin consumer: WXH_SPEC beside bucket_samples, bucket_cstride and bucket_out */
     const struct LINNEAmdMixSpec *mix;  /* the mixing consumer: its spec, checked (out_channels 1 .. 8, shift <= 31, clip_bits 0 or 2 .. 32) */
+    const struct LINNEAmdResampleSpec *rs;      /* the resampling consumer: its spec, checked; [lo, lo + n) above is the window's INPUT range */
+    uint64_t m_lo, m_n;                 /* ... and these its output samples, of the resampled stream */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -132,6 +157,9 @@ struct WxPlanned {
     uint64_t scratch_bytes;             /* the largest pass's */
     uint64_t nacc, nout;                /* bucketed consumers: accumulator units, output records */
     uint64_t nmask;                     /* the bitmask consumer: the mask words among nacc; behind them the commit's units per chunk (wxq_chunk_units) */
+    /* the resampling consumer (wx_resample_count): every window's table in the coefficient area (windows of one (coef, up, taps) share
+     * one), the area's words, the tiles of all live windows; ntile: the tiles written */
+    std::vector<uint64_t> rs_coef; std::vector<uint8_t> rs_owner; uint64_t rs_words, rs_tiles, ntile;
 };
 enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
 
@@ -175,8 +203,8 @@ static inline WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t
 /* the lists, in pinned memory and at the same offsets on the device: the words that come back (fail words, saturation words and
  * back_words 32-bit words per window of the consumer's own) | window records | the consumer's per-window records | block records |
  * the passes' COMPRESS records */
-struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes; };
-static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes)
+struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef; };
+static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false)
 {
     WxLists l;
     l.o_fail = 0; l.o_back = 2u * sizeof(uint32_t) * W; l.back_bytes = l.o_back + sizeof(uint32_t) * back_words * W;
@@ -185,6 +213,11 @@ static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_wor
     l.o_rec = wx_align(l.o_side + side_bytes * p.nlive);
     l.o_crec = wx_align(l.o_rec + sizeof(WxBlock) * p.total_rec);
     l.bytes = wx_align(l.o_crec + sizeof(uint32_t) * (p.total_crec + 1u));
+    l.o_tile = l.o_coef = l.bytes;
+    if (resamples) {                    /* behind everything the other consumers have: the tiles | the coefficient tables */
+        l.o_coef = wx_align(l.o_tile + sizeof(WxTile) * p.rs_tiles);
+        l.bytes = wx_align(l.o_coef + sizeof(uint32_t) * p.rs_words);
+    }
     return l;
 }
 
@@ -194,6 +227,7 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
     p.win.resize(W);
     p.ngroups = 0; p.nlive = p.total_rec = p.total_crec = 0;
     p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = p.nmask = 0;
+    p.rs_coef.clear(); p.rs_owner.clear(); p.rs_words = p.rs_tiles = p.ntile = 0;
     for (uint32_t i = 0; i < W; i++) {
         WxPlan &pl = p.win[i];
         pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
@@ -229,10 +263,79 @@ static inline void wx_mix_record(const struct LINNEAmdMixSpec &s, const struct L
         for (uint32_t c = 0; c < shape.num_channels && c < LINNE_MAX_NUM_CHANNELS; c++) m.coef[o][c] = s.coef[o][c];
 }
 
+/* ---- the resampling consumer ---- */
+static inline uint64_t wxr_length(uint64_t N, uint32_t L, uint32_t M)
+{
+    if (M == 0) return 0;
+    const unsigned __int128 q = ((unsigned __int128)N * L + (M - 1u)) / M;
+    return q > (unsigned __int128)~(uint64_t)0 ? ~(uint64_t)0 : (uint64_t)q;
+}
+/* what outputs [first, first + n), n >= 1, of a stream of N samples read: n(first), and the input range [lo, hi) inside the stream */
+struct WxrInput { uint64_t n_first, n_last, lo, hi, istride; };
+static inline WxrInput wxr_input(uint64_t first, uint64_t n, const struct LINNEAmdResampleSpec &s, uint64_t N)
+{
+    WxrInput r;
+    r.n_first = (uint64_t)((unsigned __int128)first * s.down / s.up);
+    r.n_last = (uint64_t)((unsigned __int128)(first + n - 1u) * s.down / s.up);
+    r.lo = r.n_first > s.before ? r.n_first - s.before : 0u;
+    r.hi = r.n_last + s.taps - s.before;                    /* (before <= taps - 1: at least n_last + 1) */
+    if (r.hi > N) r.hi = N;
+    r.istride = (r.n_last - r.n_first + s.taps + 3u) & ~(uint64_t)3u;
+    return r;
+}
+/* between wx_plan_count and wx_lists: the tables and the tiles the lists must have room for */
+static inline void wx_resample_count(const WxRange *rg, uint32_t W, WxPlanned &p)
+{
+    std::map<std::tuple<const int16_t *, uint32_t, uint32_t>, uint64_t> seen;
+    p.rs_coef.assign(W, 0u); p.rs_owner.assign(W, 0u);
+    for (uint32_t i = 0; i < W; i++) {
+        if (p.win[i].group < 0) continue;
+        const struct LINNEAmdResampleSpec &s = *rg[i].rs;
+        p.rs_tiles += (rg[i].m_n + WXR_TILE - 1u) / WXR_TILE;
+        const auto at = seen.emplace(std::make_tuple(s.coef, s.up, s.taps), p.rs_words);
+        if (at.second) { p.rs_owner[i] = 1u; p.rs_words += (uint64_t)s.up * ((s.taps + 1u) / 2u); }
+        p.rs_coef[i] = at.first->second;
+    }
+}
+/* a window's resample record, its tiles and (where it is the first to name it) its table; the window record names the image */
+static inline void wx_resample_record(const WxRange &w, const struct LINNEAmdShape &shape, uint32_t i, uint32_t wi, WxPlanned &p,
+        WxWindow &ww, WxResample &m, WxTile *h_tile, uint32_t *h_coef)
+{
+    const struct LINNEAmdResampleSpec &s = *w.rs;
+    const uint32_t B = s.clip_bits ? s.clip_bits : 32u, Bf = s.clip_bits ? s.clip_bits : shape.bits_per_sample;
+    const uint64_t n_first = (uint64_t)((unsigned __int128)w.m_lo * s.down / s.up);
+    const uint64_t n_last = (uint64_t)((unsigned __int128)(w.m_lo + w.m_n - 1u) * s.down / s.up);
+    memset(&m, 0, sizeof(m));
+    m.out = w.out; m.stride = w.stride; m.sstride = w.sstride; m.fmt = w.fmt;
+    m.m_lo = w.m_lo; m.m_hi = w.m_lo + w.m_n; m.n_first = n_first;
+    m.img = p.nacc; m.istride = (n_last - n_first + s.taps + 3u) & ~(uint64_t)3u;
+    m.coef = p.rs_coef[i]; m.up = s.up; m.down = s.down; m.taps = s.taps; m.shift = s.shift; m.prow = (s.taps + 1u) / 2u;
+    m.hi = (int32_t)(((uint64_t)1 << (B - 1u)) - 1u); m.lo = -m.hi - 1;
+    m.scale_bits = (128u - Bf) << 23;
+    m.fidx = i; m.C = shape.num_channels;
+    p.nacc += m.istride * shape.num_channels;
+    /* the passes place the input range into the image: the window record's output is the image, as an offset in bytes from the
+     * accumulators' first byte (the caller of the plan adds their address) */
+    ww.out = (void *)(uintptr_t)(sizeof(int32_t) * (m.img + (w.lo + s.before - n_first)));
+    ww.fmt = LINNE_AMD_PCM_S32; ww.stride = m.istride; ww.sstride = 1u;
+    for (uint64_t m0 = m.m_lo; m0 < m.m_hi; m0 += WXR_TILE) {
+        assert(p.ntile < p.rs_tiles);
+        WxTile &t = h_tile[p.ntile++];
+        const unsigned __int128 at = (unsigned __int128)m0 * s.down;
+        t.win = wi; t.m0 = m0; t.n0 = (uint64_t)(at / s.up); t.p0 = (uint32_t)(at % s.up);
+    }
+    if (p.rs_owner[i]) for (uint32_t ph = 0; ph < s.up; ph++)
+        for (uint32_t k = 0; k < m.prow; k++) {
+            const uint32_t a = (uint16_t)s.coef[(uint64_t)ph * s.taps + 2u * k], b = (2u * k + 1u < s.taps) ? (uint16_t)s.coef[(uint64_t)ph * s.taps + 2u * k + 1u] : 0u;
+            h_coef[m.coef + (uint64_t)ph * m.prow + k] = a | b << 16;
+        }
+}
+
 /* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
  * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs */
 static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
-        WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL)
+        WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL,
+        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL)
 {
     for (uint32_t g = 0; g < p.ngroups; g++) {
         const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
@@ -275,6 +378,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             ww.lo = w.lo; ww.hi = w.lo + w.n; ww.covered = x.covered; ww.out = w.out; ww.fidx = i;
             ww.fmt = w.fmt; ww.stride = w.stride; ww.sstride = w.sstride;
             if (h_mix) wx_mix_record(*w.mix, shape, i, h_mix[wi]);
+            if (h_rs) wx_resample_record(w, shape, i, wi, p, ww, h_rs[wi], h_tile, h_coef);
             if (bucketing == WX_BITMASK) {
                 WxBucket &m = h_side[wi];
                 memset(&m, 0, sizeof(m));

@@ -37,6 +37,9 @@
  *     (LINNEAmd_MixWindowsDevice into device PCM, clipped to the stream's bits, then LINNEAmd_EncodeStreamsDevice with IN's header and
  *     the matrix' row count as its channels; one channel does not inherit MS).  SPEC: the rows separated by '/', a row's coefficients (int16) by ',', then optionally
  *     ">>SHIFT" (0 .. 31, halves round up): "1,1>>1" the mean of a stereo pair, "0,1/1,0" a channel swap.
+ *   - -Z / --resample RATE[,TAPS] IN.lnn OUT.lnn writes IN at the sampling rate RATE, on the device (LINNEAmd_ResampleDesign's filter of
+ *     TAPS coefficients per phase, 32 unless given; LINNEAmd_ResampleWindowsDevice into device PCM, clipped to the stream's bits; then
+ *     LINNEAmd_EncodeStreamsDevice with IN's header but for the rate and the sample count): what Context.resample_streams writes.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -52,9 +55,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec;
+    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec;
     const char *files[4096];
     int num_files;
 };
@@ -72,6 +75,7 @@ static void usage(const char *argv0)
     printf("       %s -L BINS[,SHIFT[,log2]] STREAM.lnn \n", argv0);
     printf("       %s -R [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -X ROW[/ROW...][>>SHIFT] IN.lnn OUT.lnn \n", argv0);
+    printf("       %s -Z RATE[,TAPS] IN.lnn OUT.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -84,6 +88,7 @@ static void usage(const char *argv0)
            "  -L, --levels BINS[,SHIFT[,log2]]       Histogram a .lnn stream's sample levels on the device: |v| >> SHIFT, or its bit length \n"
            "  -R, --relate                           Relate a .lnn stream's channels on the device: dot products, equal and opposite frames, correlation per pair (and bucket) \n"
            "  -X, --remix ROW[/ROW...][>>SHIFT]      Write a .lnn stream whose channels are an integer matrix of the input's: rows of C coefficients \n"
+           "  -Z, --resample RATE[,TAPS]             Write a .lnn stream at the sampling rate RATE: an exact polyphase FIR of TAPS (32) coefficients per phase \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -139,6 +144,7 @@ static void parse(int argc, char **argv, struct options *o)
         } else if (take_value(argc, argv, &i, "-S", "--silence", &v)) { o->silence = 1; o->silence_spec = v; }
         else if (take_value(argc, argv, &i, "-L", "--levels", &v)) { o->levels = 1; o->levels_spec = v; }
         else if (take_value(argc, argv, &i, "-X", "--remix", &v)) { o->remix = 1; o->remix_spec = v; }
+        else if (take_value(argc, argv, &i, "-Z", "--resample", &v)) { o->resample = 1; o->resample_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -692,6 +698,85 @@ done:
     return rc;
 }
 
+/* "16000", "48000,64": the rate, then optionally the taps per phase -> *rate, *taps (32 unless given).  0, or a message in err */
+static int parse_resample(const char *text, uint32_t *rate, uint32_t *taps, char *err, size_t cap)
+{
+    const char *p = text;
+    char *end;
+    unsigned long v;
+    *taps = 32;
+    if (!(*p >= '0' && *p <= '9')) { snprintf(err, cap, "resample spec: a sampling rate is expected at \"%s\"", p); return 1; }
+    v = strtoul(p, &end, 10);
+    if (v < 1 || v > 0xFFFFFFFFul) { snprintf(err, cap, "resample spec: sampling rate %lu is outside 1 .. 4294967295", v); return 1; }
+    *rate = (uint32_t)v;
+    p = end;
+    if (*p == ',') {
+        p++;
+        if (!(*p >= '0' && *p <= '9')) { snprintf(err, cap, "resample spec: a tap count is expected at \"%s\"", p); return 1; }
+        v = strtoul(p, &end, 10);
+        if (v < 1 || v > LINNE_AMD_RESAMPLE_MAX_TAPS) { snprintf(err, cap, "resample spec: %lu taps are outside 1 .. %d", v, LINNE_AMD_RESAMPLE_MAX_TAPS); return 1; }
+        *taps = (uint32_t)v;
+        p = end;
+    }
+    if (*p != '\0') { snprintf(err, cap, "resample spec: malformed at \"%s\"", p); return 1; }
+    return 0;
+}
+static uint32_t gcd32(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
+
+/* -Z: the spec and the stream's header are checked on the host and the filter designed there; then the stream goes to the device,
+ * LINNEAmd_StreamIndexCreate, one LINNEAmd_ResampleWindowsDevice window over the whole resampled stream into int32 planes beside it, and
+ * LINNEAmd_EncodeStreamsDevice make the output */
+static int resample_one(const char *spec_text, const char *in_path, const char *out_path)
+{
+    uint8_t *buf = NULL, *out = NULL;
+    int16_t *coef = NULL;
+    void *d_out = NULL;
+    uint32_t size = 0, rate = 0, taps = 0, g;
+    struct resident r;
+    struct LINNEAmdResampleSpec spec;
+    struct LINNEAmdTrack tr;
+    struct LINNEHeader h;
+    char err[512];
+    uint64_t n, cap, up, down;
+    FILE *fp;
+    int ret, stage, rc = 1;
+    memset(&r, 0, sizeof(r));
+    if (parse_resample(spec_text, &rate, &taps, err, sizeof(err)) != 0) { fprintf(stderr, "%s \n", err); return 1; }
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); free(buf); return 1; }
+    if (h.sampling_rate == 0) { fprintf(stderr, "resample spec: the stream names no sampling rate \n"); free(buf); return 1; }
+    g = gcd32(h.sampling_rate, rate); up = rate / g; down = h.sampling_rate / g;
+    memset(&spec, 0, sizeof(spec));
+    if (up > LINNE_AMD_RESAMPLE_MAX_RATIO || down > LINNE_AMD_RESAMPLE_MAX_RATIO || up * taps > LINNE_AMD_RESAMPLE_MAX_COEFS) {
+        fprintf(stderr, "resample spec: %u -> %u Hz is %llu/%llu with %u taps: beyond %d/%d or %d coefficients \n", (unsigned)h.sampling_rate, rate, (unsigned long long)up, (unsigned long long)down, taps,
+                LINNE_AMD_RESAMPLE_MAX_RATIO, LINNE_AMD_RESAMPLE_MAX_RATIO, LINNE_AMD_RESAMPLE_MAX_COEFS);
+        free(buf); return 1;
+    }
+    spec.up = (uint32_t)up; spec.down = (uint32_t)down; spec.taps = taps; spec.clip_bits = h.bits_per_sample;
+    if (!(coef = malloc(sizeof(*coef) * up * taps)) || (ret = LINNEAmd_ResampleDesign(spec.up, spec.down, taps, coef, &spec.shift, &spec.before)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to design the filter: %d \n", coef ? ret : -1); goto done; }
+    spec.coef = coef;
+    n = LINNEAmd_ResampleLength(h.num_samples, spec.up, spec.down);
+    if (n > 0xFFFFFFFFull) { fprintf(stderr, "resample spec: %llu samples are more than a header names \n", (unsigned long long)n); goto done; }
+    if ((stage = resident_open(&r, buf, size, n, sizeof(int32_t) * n * h.num_channels, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to resample! %s \n" : "%s \n", err); goto done; }
+    r.w.d_pcm = r.d_extra; r.w.pcm_stride = n;
+    if ((ret = LINNEAmd_ResampleWindowsDevice(r.ctx, &r.w, &spec, NULL, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to resample! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    memset(&tr, 0, sizeof(tr));
+    tr.header = h; tr.header.sampling_rate = rate; tr.header.num_samples = (uint32_t)n;
+    cap = LINNEAmd_EncodeStreamBound(&tr.header);
+    if (hipMalloc(&d_out, cap ? cap : 1) != hipSuccess) { fprintf(stderr, "Failed to allocate %llu bytes on the device. \n", (unsigned long long)cap); d_out = NULL; goto done; }
+    tr.d_pcm = r.d_extra; tr.pcm_stride = n; tr.d_out = d_out; tr.capacity = cap;
+    if ((ret = LINNEAmd_EncodeStreamsDevice(r.ctx, &tr, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to encode! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(out = malloc(tr.out_bytes ? (size_t)tr.out_bytes : 1)) || hipMemcpy(out, d_out, tr.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the stream. \n"); goto done; }
+    if (!(fp = fopen(out_path, "wb")) || fwrite(out, 1, (size_t)tr.out_bytes, fp) != tr.out_bytes) { fprintf(stderr, "File output error! %s \n", out_path); if (fp) fclose(fp); goto done; }
+    fclose(fp);
+    rc = 0;
+done:
+    if (d_out) (void)hipFree(d_out);
+    resident_close(&r);
+    free(out); free(coef); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -700,6 +785,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.resample) {
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -Z takes a sampling rate, an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        return resample_one(o.resample_spec, o.files[0], o.files[1]);
+    }
     if (o.remix) {
         if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -X takes a matrix, an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return remix_one(o.remix_spec, o.files[0], o.files[1]);

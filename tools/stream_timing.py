@@ -1,5 +1,5 @@
 """What the stream timing tools (tools/stream_measure.py, stream_digest.py, stream_quiet.py, stream_histogram.py, stream_relate.py,
-stream_compare.py, stream_mix.py) share, so that the figures under profiles/stream_*.json are taken in one way: the arguments, the material (BASELINE
+stream_compare.py, stream_mix.py, stream_resample.py) share, so that the figures under profiles/stream_*.json are taken in one way: the arguments, the material (BASELINE
 configs[1]'s stream and the clips of that shape, encoded once on the device), the timing of one call, the statistic, the peak-memory
 probe of every form on a context of its own, the repetitions in which the forms of a case alternate, the loops that read the HIP
 events of single kernel kinds, and the head of the result.  A tool keeps what is its own: its docstring, its torch recipe, its
