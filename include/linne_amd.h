@@ -424,6 +424,11 @@ enum LINNEAmdResampleTimingKind {
     LINNE_AMD_RESAMPLE_T_PRESET = 99,       /* the call's input images zeroed, once, in front of the first pass (k_wx_resample_preset) */
     LINNE_AMD_RESAMPLE_T_RESAMPLE = 100     /* the outputs of the windows that did not fail filtered from their input images, once, behind the last pass (k_wx_resample) */
 };
+/* overlaying windows (LINNEAmd_OverlayWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice -- its kind 59 places the sources'
+ * samples into the call's scratch --, and one launch of kind 101 per call that takes a pass) */
+enum LINNEAmdOverlayTimingKind {
+    LINNE_AMD_OVERLAY_T_OVERLAY = 101       /* the outputs whose sources did not fail summed from their sources' images, once, behind the last pass (k_wx_overlay) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -982,6 +987,59 @@ uint64_t LINNEAmd_ResampleLength(uint64_t num_samples, uint32_t up, uint32_t dow
  * (taps - 1) / 2.  up, down and taps are checked as the spec's are (INVALID_ARGUMENT, as for a NULL pointer); otherwise OK.  Pure host
  * code: no device is needed. */
 int LINNEAmd_ResampleDesign(uint32_t up, uint32_t down, uint32_t taps, int16_t *coef /* [up][taps] */, uint32_t *shift, uint32_t *before);
+
+/* ---- overlaying windows of several resident streams: a mix-down, a fade, a crossfade at a join, on decode ----
+ * LINNEAmd_OverlayWindowsDevice writes num_outputs outputs, each the sum of up to LINNE_AMD_OVERLAY_MAX_SOURCES sources: ranges of
+ * indexed streams, each laid at an output sample of its own under a gain that moves linearly over its samples.  For source s, sample
+ * i of its range (0 <= i < n_s = num_samples), the gain is
+ *   g_s(i) = (gain_q32 + step_q32 * i) >> 32, the sum formed in 64 bits and the shift arithmetic: the floor.
+ * g_s(0) and g_s(n_s - 1) must lie in [-32768, 32767]; the host checks both in 128 bits, and the ramp being linear every gain between
+ * them lies there too: nothing in the kernel can wrap.  With x_s[c][j] the values LINNEAmd_DecodeStreamDevice gives for channel c,
+ * sample j of source s's stream, output sample t of channel c is
+ *   1. the sum    acc = sum over the sources with at_s <= t < at_s + n_s of (int64)g_s(t - at_s) * x_s[c][first_s + t - at_s]   (a
+ *                 product is at most 2^46 in magnitude, 64 of them 2^52: nothing wraps); a sample no source covers has acc = 0;
+ *   2. the shift, the clip and the layout's conversion: steps 2 to 4 of LINNEAmd_MixWindowsDevice, word for word, and its rule for
+ *      layouts[i].saturated.  For F32 with clip_bits 0, Bf is the bits_per_sample of the stream of the output's first source.
+ * One source with at = 0, gain_q32 = 1 << 32, step_q32 = 0, shift 0 and clip_bits 0 writes what LINNEAmd_DecodeWindowsDeviceLayout
+ * writes.  The output has the channel count C its sources' streams share; the streams may differ in everything else (bits, block
+ * size, preset, MS, rate), and two sources may name the same stream and overlap.  An output's d_pcm, pcm_stride and layouts[i] are
+ * what a window's are in LINNEAmd_DecodeWindowsDeviceLayout, for num_samples samples of C channels: all of them are written, zeros
+ * where no source lies.
+ * Results: outputs[i].result.  For output i alone INVALID_ARGUMENT ("output <i>: OverlayWindowsDevice: ..." in GetLastError) when
+ * num_sources is outside 1 .. LINNE_AMD_OVERLAY_MAX_SOURCES or sources is NULL, shift > 31, clip_bits is 1 or above 32, reserved (the
+ * output's or a source's) is not 0, a source is NULL in index or d_stream or has num_samples 0, at + num_samples lies beyond the
+ * output's num_samples (or wraps), a gain end lies outside int16, the sources' streams differ in channel count, d_pcm is NULL, or the
+ * layout's checks (with C) fail.  These come first; every source is then checked as a struct LINNEAmdWindow of
+ * LINNEAmd_DecodeWindowsDevice is ("output <i>: source <j>: ..."): its range, its index's failing block at or before its range, and,
+ * on the device, its Rice codes.  An output fails with the code of its lowest-numbered failing source; a failing output's memory is
+ * never written and the others are undisturbed; the call returns the lowest failing output's code.  Whole-call failures are the decode
+ * call's.
+ * Every source is a window of the decode call's plan: shape groups, passes, group_frames (which never changes a byte), copies and the
+ * one host synchronisation are that call's, over all sources of all outputs.  The passes place every source's samples into an int32
+ * image in the context's scratch -- 4 * C * (n_s rounded up to 4) bytes per source --; where that cannot be had the whole call fails
+ * with NG and nothing is written.  A pass has the decode call's launches (its kind 59 writes the images); a call that takes a pass
+ * adds one launch of kind 101 behind the last pass and nothing else, whatever the numbers of outputs and sources are.
+ * num_outputs == 0 is OK; a NULL ctx, or NULL outputs with num_outputs > 0, INVALID_ARGUMENT.  Enqueued on the context's stream and
+ * synchronous. */
+#define LINNE_AMD_OVERLAY_MAX_SOURCES 64
+struct LINNEAmdOverlaySource {          /* 64 bytes */
+    const struct LINNEAmdStreamIndex *index;    /* as in struct LINNEAmdWindow */
+    const uint8_t *d_stream;
+    uint64_t first_sample, num_samples; /* the source's range in ITS stream; num_samples >= 1 */
+    uint64_t at;                        /* the output sample its first sample lands on */
+    int64_t gain_q32, step_q32;         /* the gain at its first sample and its change per sample, in units of 2^-32 */
+    uint64_t reserved;                  /* 0 */
+};
+struct LINNEAmdOverlay {
+    const struct LINNEAmdOverlaySource *sources; uint32_t num_sources;  /* HOST memory; 1 .. LINNE_AMD_OVERLAY_MAX_SOURCES */
+    uint32_t shift, clip_bits, reserved;        /* as in struct LINNEAmdMixSpec */
+    uint64_t num_samples;               /* of the output */
+    int32_t *d_pcm; uint64_t pcm_stride;        /* as in struct LINNEAmdWindow, when layouts is NULL */
+    int32_t result;                     /* out */
+};
+int LINNEAmd_OverlayWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdOverlay *outputs,
+        struct LINNEAmdPcmLayout *layouts /* [num_outputs] in/out; NULL: int32 planar, pcm_stride */,
+        uint32_t num_outputs, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

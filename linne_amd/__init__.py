@@ -63,6 +63,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_QuietWindowsDevice", "LINNEAmd_HistogramWindowsDevice", "LINNEAmd_RelateWindowsDevice",
     "LINNEAmd_MixWindowsDevice",
     "LINNEAmd_ResampleWindowsDevice", "LINNEAmd_ResampleLength", "LINNEAmd_ResampleDesign",
+    "LINNEAmd_OverlayWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -318,6 +319,50 @@ def resample_design(up, down, taps=32):
     return coef, int(shift.value), int(before.value)
 
 
+class OverlaySource(C.Structure):
+    """struct LINNEAmdOverlaySource (include/linne_amd.h)"""
+    _fields_ = [("index", C.c_void_p), ("d_stream", C.c_void_p), ("first_sample", C.c_uint64), ("num_samples", C.c_uint64),
+                ("at", C.c_uint64), ("gain_q32", C.c_int64), ("step_q32", C.c_int64), ("reserved", C.c_uint64)]
+
+
+class Overlay(C.Structure):
+    """struct LINNEAmdOverlay (include/linne_amd.h); sources is host memory"""
+    _fields_ = [("sources", C.POINTER(OverlaySource)), ("num_sources", C.c_uint32), ("shift", C.c_uint32), ("clip_bits", C.c_uint32),
+                ("reserved", C.c_uint32), ("num_samples", C.c_uint64), ("d_pcm", C.c_void_p), ("pcm_stride", C.c_uint64), ("result", C.c_int32)]
+
+
+OVERLAY_MAX_SOURCES = 64                # include/linne_amd.h LINNE_AMD_OVERLAY_MAX_SOURCES
+
+
+def overlay_gain(gain_q32, step_q32, i):
+    """the gain LINNEAmd_OverlayWindowsDevice gives sample i of a source: (gain_q32 + step_q32 * i) >> 32, the floor"""
+    return (int(gain_q32) + int(step_q32) * int(i)) >> 32
+
+
+def fade(g0, g1, n):
+    """a linear ramp for overlay_windows -> (gain_q32, step_q32): exactly g0 at sample 0, and g1 reached at sample n, one past the last
+    of the n samples it is for (the step is rounded towards g0, and half a unit of 2^-32 keeps the floor of sample 0 at g0 when the
+    ramp falls); g0 and g1 are int16 gains and n is 1 .. 2^31 -- beyond that the rounded step could miss g1 by one --, anything else
+    raises ValueError.  Pure host code"""
+    g0, g1, n = int(g0), int(g1), int(n)
+    if not 1 <= n <= 1 << 31 or not (-32768 <= g0 <= 32767 and -32768 <= g1 <= 32767):
+        raise ValueError(f"fade({g0}, {g1}, {n}): the gains are int16, n is 1 .. 2^31")
+    span = (g1 - g0) << 32
+    step = span // n if span >= 0 else -((-span) // n)
+    return (g0 << 32) + (1 << 31), step
+
+
+def crossfade(n, unity):
+    """the two ramps of a linear crossfade over n samples -> ((gain_q32, step_q32) of the stream that leaves, of the stream that
+    comes): the first falls from `unity` towards 0, the second is (unity << 32) + (1 << 32) - 1 - the first with the negated step, so
+    that the two gains add up to exactly `unity` at every one of the n samples.  Pure host code"""
+    n, unity = int(n), int(unity)
+    if not 1 <= n <= 1 << 31 or not 1 <= unity <= 32767:
+        raise ValueError(f"crossfade({n}, {unity}): n is 1 .. 2^31, unity 1 .. 32767")
+    a, step = fade(unity, 0, n)
+    return (a, step), ((unity << 32) + (1 << 32) - 1 - a, -step)
+
+
 RELATION_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("num_equal", "<u8"), ("num_opposite", "<u8")])
 
 
@@ -559,6 +604,7 @@ def _load():
     L.LINNEAmd_ResampleLength.restype = C.c_uint64
     L.LINNEAmd_ResampleLength.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
     L.LINNEAmd_ResampleDesign.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.LINNEAmd_OverlayWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Overlay), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -1021,6 +1067,26 @@ class Context:
         arr, keep, ranges = self._windows_array(windows)
         mixes = specs is not None and specs._type_ is MixSpec      # (otherwise the specs are ResampleSpec: the stream's channels, ranges of output samples)
         shapes = [(int(specs[i].out_channels) if mixes else x.header["num_channels"], max(n, 0)) for i, (x, _, n) in enumerate(ranges)]
+        pcm, lays, plain = self._pcm_targets(arr, shapes, specs is None, out, dtype, channels_last, s24, return_saturated)
+        self._fence()
+        if plain:
+            ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
+        elif specs is None:
+            ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
+        elif mixes:
+            ret = lib.LINNEAmd_MixWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
+        else:
+            ret = lib.LINNEAmd_ResampleWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice" if specs is None else "MixWindowsDevice" if mixes else "ResampleWindowsDevice", return_codes)
+        res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
+        return res[0] if len(res) == 1 else res
+
+    def _pcm_targets(self, arr, shapes, bare, out, dtype, channels_last, s24, return_saturated, noun="window"):
+        """where a batch writer's PCM goes: arr's elements (Window, or Overlay) get their d_pcm and pcm_stride for the (C, n) of
+        `shapes`, in `out` or in one new allocation -> (the PCM as the call returns it, the PcmLayout array, whether the call may be
+        the one without layouts: `bare`, int32 planar, and nobody asks for `saturated`)"""
+        import torch
+        W = len(shapes)
         dev = f"cuda:{self.device}"
         if s24:
             assert dtype in (None, torch.uint8), "s24 samples are uint8 triples"
@@ -1029,7 +1095,7 @@ class Context:
             tdtype = torch.int32 if dtype is None else dtype
             assert tdtype in (torch.int32, torch.int16, torch.float32), "dtype is torch.int32, torch.int16 or torch.float32"
             fmt, esize = {torch.int32: (PCM_S32, 4), torch.int16: (PCM_S16, 2), torch.float32: (PCM_F32, 4)}[tdtype]
-        plain = specs is None and fmt == PCM_S32 and not channels_last and not return_saturated and (out is None or out.dim() != 3 or out.stride(2) == 1 or out.shape[2] <= 1)
+        plain = bare and fmt == PCM_S32 and not channels_last and not return_saturated and (out is None or out.dim() != 3 or out.stride(2) == 1 or out.shape[2] <= 1)
         lays = (PcmLayout * max(W, 1))()
         cdim, sdim = (2, 1) if channels_last else (1, 2)
         if out is not None:
@@ -1044,7 +1110,7 @@ class Context:
             assert out.device.index == self.device, f"out is on {out.device}, the context on cuda:{self.device}"
             unit = 3 if s24 else 1
             for i, (c, n) in enumerate(shapes):
-                assert (c, n) == (out.shape[cdim], out.shape[sdim]), f"window {i} is {(c, n)}, out holds {tuple(out.shape[1:])} per window"
+                assert (c, n) == (out.shape[cdim], out.shape[sdim]), f"{noun} {i} is {(c, n)}, out holds {tuple(out.shape[1:])} per {noun}"
                 arr[i].d_pcm, arr[i].pcm_stride = out.data_ptr() + out.element_size() * i * out.stride(0), out.stride(1) if c > 1 else n
                 lays[i].format, lays[i].channel_stride = fmt, out.stride(cdim) // unit if c > 1 else 0
                 lays[i].sample_stride = out.stride(sdim) // unit if n > 1 else 1
@@ -1059,18 +1125,7 @@ class Context:
                 arr[i].d_pcm, arr[i].pcm_stride = v.data_ptr(), n
                 lays[i].format = fmt
                 lays[i].channel_stride, lays[i].sample_stride = (1, c) if channels_last else (n, 1)
-        self._fence()
-        if plain:
-            ret = lib.LINNEAmd_DecodeWindowsDevice(self.h, arr, W, int(group_frames))
-        elif specs is None:
-            ret = lib.LINNEAmd_DecodeWindowsDeviceLayout(self.h, arr, lays, W, int(group_frames))
-        elif mixes:
-            ret = lib.LINNEAmd_MixWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
-        else:
-            ret = lib.LINNEAmd_ResampleWindowsDevice(self.h, arr, specs, lays, W, int(group_frames))
-        codes = self._windows_codes(ret, arr, W, "DecodeWindowsDevice" if specs is None else "MixWindowsDevice" if mixes else "ResampleWindowsDevice", return_codes)
-        res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[i].saturated) for i in range(W)],) if return_saturated else ())
-        return res[0] if len(res) == 1 else res
+        return pcm, lays, plain
 
     @staticmethod
     def _mix_specs(indexes, matrix, shift, clip_bits):
@@ -1199,6 +1254,128 @@ class Context:
                        int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else h["ch_process_method"])
                       for pcm, b, h in zip(pcms, obits, heads)]
             return self.encode_streams(tracks, group_frames=group_frames)
+
+    def overlay_windows(self, outputs, shift=0, clip_bits=0, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False,
+                        s24=False, return_saturated=False):
+        """windows of several resident streams summed into each output under gains that move linearly over a source: a mix-down, a
+        fade, a crossfade (include/linne_amd.h LINNEAmd_OverlayWindowsDevice states the arithmetic).  outputs: a sequence of
+        (num_samples, sources), sources a sequence of (stream, index, first_sample, num_samples, at, gain): the range of the source in
+        its stream (num_samples None: to the stream's end), the output sample its first sample lands on, and its gain -- an int, a
+        constant gain, or a (gain_q32, step_q32) pair as fade and crossfade make them.  The sum is shifted right by `shift` with
+        halves rounded up and clipped to clip_bits bits (0: 32), as mix_windows has it; shift and clip_bits are one value or one per
+        output.  An output has the channel count its sources share.  Values outside the call's bounds raise ValueError before any
+        call.  Everything else -- out, dtype, channels_last, s24, return_codes, return_saturated, group_frames, errors -- is
+        decode_windows', with an output where that has a window"""
+        O = len(outputs)
+        shifts, clips = _per_window(shift, O, "shift", lo=None), _per_window(clip_bits, O, "clip_bits", lo=None)
+        arr = (Overlay * max(O, 1))()
+        keep, shapes = [], []
+        for k, (n_out, sources) in enumerate(outputs):
+            n_out, K = int(n_out), len(sources)
+            if not 1 <= K <= OVERLAY_MAX_SOURCES:
+                raise ValueError(f"output {k}: {K} sources: 1 .. {OVERLAY_MAX_SOURCES}")
+            if not (0 <= shifts[k] <= 31 and (clips[k] == 0 or 2 <= clips[k] <= 32) and 0 <= n_out < 1 << 64):
+                raise ValueError(f"output {k}: shift is 0 .. 31, clip_bits 0 or 2 .. 32, num_samples unsigned")
+            srcs = (OverlaySource * K)()
+            keep.append(srcs)
+            for j, (stream, index, first, n, at, gain) in enumerate(sources):
+                t = self._stream_bytes(stream)
+                first, n, count = _sample_range(index, t.numel(), first, n, "output %d: source %d", k, j)
+                q, step = (int(gain) << 32, 0) if isinstance(gain, (int, np.integer)) else (int(gain[0]), int(gain[1]))
+                at = int(at)
+                if n < 1 or at < 0 or at + n > n_out:
+                    raise ValueError(f"output {k}: source {j}: {n} samples at {at} of an output of {n_out}")
+                if not (-32768 <= overlay_gain(q, step, 0) <= 32767 and -32768 <= overlay_gain(q, step, n - 1) <= 32767):
+                    raise ValueError(f"output {k}: source {j}: a gain outside int16")
+                if index.header["num_channels"] != sources[0][1].header["num_channels"]:
+                    raise ValueError(f"output {k}: source {j} has {index.header['num_channels']} channels, source 0 {sources[0][1].header['num_channels']}")
+                keep.append(t)
+                sc = srcs[j]
+                sc.index, sc.d_stream, sc.first_sample, sc.num_samples, sc.at, sc.gain_q32, sc.step_q32, sc.reserved = index.h, t.data_ptr(), first, count, at, q, step, 0
+            o = arr[k]
+            o.sources, o.num_sources, o.shift, o.clip_bits, o.reserved, o.num_samples = srcs, K, shifts[k], clips[k], 0, n_out
+            shapes.append((sources[0][1].header["num_channels"], n_out))
+        pcm, lays, _ = self._pcm_targets(arr, shapes, False, out, dtype, channels_last, s24, return_saturated, noun="output")
+        self._fence()
+        ret = lib.LINNEAmd_OverlayWindowsDevice(self.h, arr, lays, O, int(group_frames))
+        codes = [int(arr[k].result) for k in range(O)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("output ")):       # (a failing output's text starts with its number)
+                raise LinneAmdError(f"OverlayWindowsDevice -> {ret}: {msg}", ret, codes)
+        res = (pcm,) + ((codes,) if return_codes else ()) + (([bool(lays[k].saturated) for k in range(O)],) if return_saturated else ())
+        return res[0] if len(res) == 1 else res
+
+    def overlay_streams(self, jobs, shift, bits=None, preset=None, block=None, ms=None, group_frames=0):
+        """new .lnn streams that are overlays of resident streams, without the PCM leaving the device: one index_streams call over the
+        distinct streams named, one overlay_windows call into one int32 allocation (clip_bits = the output's bits) and one
+        encode_streams call.  jobs: a sequence of (num_samples, sources), sources a sequence of (stream, first_sample, num_samples, at,
+        gain) as overlay_windows takes them without the index; shift one value or one per job.  Every header field not given (bits,
+        preset, block, ms) is the job's first source's, the sampling rate too: sources of one job with different rates raise
+        ValueError.  -> a list of uint8 CUDA tensors"""
+        if len(jobs) == 0:
+            return []
+        order, ts = {}, []
+        for _, sources in jobs:
+            for src in sources:
+                if id(src[0]) not in order:                      # (a stream named twice is indexed once)
+                    order[id(src[0])] = len(ts)
+                    ts.append(self._stream_bytes(src[0]))
+        with self._whole_streams(ts) as (ts, xs, _):
+            paired = [(n_out, [(ts[order[id(src[0])]], xs[order[id(src[0])]]) + tuple(src[1:]) for src in sources]) for n_out, sources in jobs]
+            return self._overlay_indexed(paired, shift, bits, preset, block, ms, group_frames)
+
+    def _overlay_indexed(self, jobs, shift, bits, preset, block, ms, group_frames):
+        """overlay_streams and crossfade_streams behind their index_streams call: jobs of (num_samples, sources), a source (stream, its
+        index, first_sample, num_samples, at, gain) as overlay_windows takes it -- every source carries its own index, so nothing
+        depends on the order in which streams were named -> the encoded streams"""
+        heads = []
+        for k, (_, sources) in enumerate(jobs):
+            if len(sources) == 0:
+                raise ValueError(f"job {k}: no sources")
+            rates = sorted({src[1].header["sampling_rate"] for src in sources})
+            if len(rates) > 1:
+                raise ValueError(f"job {k}: its sources have the sampling rates {rates}")
+            heads.append(sources[0][1].header)
+        obits = [int(bits) if bits is not None else h["bits_per_sample"] for h in heads]
+        pcms = self.overlay_windows(jobs, shift=shift, clip_bits=obits, group_frames=group_frames)
+        tracks = [(pcm, b, h["sampling_rate"], int(block) if block is not None else h["num_samples_per_block"],
+                   int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else h["ch_process_method"])
+                  for pcm, b, h in zip(pcms, obits, heads)]
+        return self.encode_streams(tracks, group_frames=group_frames)
+
+    def crossfade_streams(self, streams, overlap, bits=None, preset=None, block=None, ms=None, group_frames=0):
+        """one new .lnn stream: the given streams in order, each join a linear crossfade over `overlap` samples -- the last `overlap`
+        samples of a stream under the falling ramp of crossfade(overlap, 16384), the first `overlap` of the next under the rising one,
+        everything else at 16384, shift 14.  overlap 0 is a hard cut: the PCM of a splice_streams join.  One index_streams call (a
+        stream given twice is indexed twice: an index per position), then what overlay_streams does behind its own: one
+        overlay_windows call of one output and one encode_streams call.  A stream is a source at overlap 0 and otherwise up to three,
+        two at the ends (one where it lies wholly under a ramp), and an output takes OVERLAY_MAX_SOURCES = 64: 64 streams at overlap 0,
+        22 with crossfades, or ValueError.  A stream shorter than the overlaps it takes part in raises ValueError too.  -> a uint8
+        CUDA tensor"""
+        overlap = int(overlap)
+        if len(streams) == 0 or overlap < 0:
+            raise ValueError("crossfade_streams: at least one stream, overlap >= 0")
+        unity = 16384
+        down, up = crossfade(overlap, unity) if overlap else (None, None)
+        ts = [self._stream_bytes(s) for s in streams]
+        with self._whole_streams(ts) as (ts, indexes, _):
+            sources, at = [], 0
+            for i, (t, x) in enumerate(zip(ts, indexes)):
+                n = x.header["num_samples"]
+                head, tail = overlap if i > 0 else 0, overlap if i + 1 < len(ts) else 0
+                if n < head + tail or n < 1:
+                    raise ValueError(f"stream {i}: {n} samples under crossfades of {overlap}")
+                if head:
+                    sources.append((t, x, 0, head, at, up))
+                if n - head - tail:
+                    sources.append((t, x, head, n - head - tail, at + head, unity))
+                if tail:
+                    sources.append((t, x, n - tail, tail, at + n - tail, down))
+                at += n - tail
+            if len(sources) > OVERLAY_MAX_SOURCES:
+                raise ValueError(f"crossfade_streams: {len(sources)} sources in one output: at most {OVERLAY_MAX_SOURCES}")
+            return self._overlay_indexed([(at, sources)], 14, bits, preset, block, ms, group_frames)[0]
 
     def compare_windows(self, windows, group_frames=0, return_codes=False):
         """many sample windows of resident .lnn streams compared with resident PCM in one call, nothing decoded into memory of the

@@ -57,6 +57,7 @@
 #include "lnn_k_relate.h"
 #include "lnn_k_mix.h"
 #include "lnn_k_resample.h"
+#include "lnn_k_overlay.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -76,6 +77,7 @@ static_assert(LINNE_AMD_HISTOGRAM_T_HISTOGRAM == 92 && LINNE_AMD_HISTOGRAM_T_COM
 static_assert(LINNE_AMD_RELATE_T_RELATE == 95 && LINNE_AMD_RELATE_T_COMMIT == 97, "the relate call's timing kinds are 95 to 97");
 static_assert(LINNE_AMD_MIX_T_MIX == 98, "the mix call's timing kind is 98");
 static_assert(LINNE_AMD_RESAMPLE_T_PRESET == 99 && LINNE_AMD_RESAMPLE_T_RESAMPLE == 100, "the resample call's timing kinds are 99 and 100");
+static_assert(LINNE_AMD_OVERLAY_T_OVERLAY == 101, "the overlay call's timing kind is 101");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2250,9 +2252,10 @@ struct WxCall;
 struct WxLaunch {
     const WxBucket *side; const WxMix *mix; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask;
     const WxResample *rs; const WxTile *tiles; const uint32_t *coef; uint64_t ntile; uint32_t *sat;        /* the resampling consumer's */
+    const WxOvOutput *ov_outs; const WxOvSource *ov_srcs;          /* the overlaying consumer's, beside tiles, ntile and sat */
 };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The nine calls are the
- * nine constant instances below; a launch that a consumer does not have is NULL */
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The ten calls are the
+ * ten constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2269,6 +2272,8 @@ struct WxConsumer {
     bool mixes;                         /* a WxMix beside every window record, from the windows' struct LINNEAmdMixSpec (a consumer without buckets) */
     bool resamples;                     /* a WxResample beside every window record, from the windows' struct LINNEAmdResampleSpec: the passes place the
                                          * windows' input ranges into images among the accumulators, the commit filters them (a consumer without buckets) */
+    bool overlays;                      /* the windows are the sources of the call's outputs (WxCall.ov_*): the passes place them into images among the
+                                         * accumulators, the commit sums the outputs from them (a consumer without buckets) */
 };
 struct WxCall {
     const WxConsumer *use;
@@ -2278,11 +2283,13 @@ struct WxCall {
     void *answers;                      /* [W] of the consumer's: place and mix the layouts again (`saturated`; NULL: not reported), compare struct LINNEAmdDiff, quiet struct LINNEAmdQuiet */
     const struct LINNEAmdMixSpec *mix;  /* [W], mix alone: its specs go beside its layouts */
     const struct LINNEAmdResampleSpec *rs;      /* [W], resample alone, likewise */
+    const struct LINNEAmdOverlaySource *const *ov_src; const WxOvOut *ov_outs; uint32_t ov_O;      /* overlay alone: window i's source [W]; the outputs [ov_O] */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
     WxCall c;
     c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL; c.rs = NULL;
+    c.ov_src = NULL; c.ov_outs = NULL; c.ov_O = 0;
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
@@ -2542,6 +2549,18 @@ static int wx_resample_commit(LINNEAmdContext *ctx, const WxLaunch &l)
     return LNN_OK;
 }
 
+/* ---- overlay: the passes place the sources' ranges into images; the commit sums the outputs from them (lnn_k_overlay.h) ---- */
+static int wx_overlay_check(const WxCall &, uint32_t, char *, size_t) { return LNN_OK; }   /* (the outputs' checks came in front of the windows') */
+static void wx_overlay_describe(const WxCall &c, uint32_t i, WxRange &r) { r.ov = c.ov_src[i]; }
+static int wx_overlay_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxOverlayArgs oa;
+    oa.tiles = l.tiles; oa.ntiles = (uint32_t)l.ntile; oa.outs = l.ov_outs; oa.srcs = l.ov_srcs; oa.fail = l.fail; oa.sat = l.sat; oa.acc = (const int32_t *)l.acc;
+    /* (a call whose live sources all belong to outputs with a failing source has no tile: its one workgroup returns at once) */
+    SX_LAUNCH(NULL, LINNE_AMD_OVERLAY_T_OVERLAY, k_wx_overlay, dim3(oa.ntiles ? oa.ntiles : 1u), dim3(WXR_TILE), 0, ctx->stream, oa);
+    return LNN_OK;
+}
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false, false };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false, false };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false, false };
@@ -2551,6 +2570,7 @@ static const WxConsumer WX_HISTOGRAM = { "HistogramWindowsDevice", 0u, NULL, WX_
 static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKETS_PER_PAIR, sizeof(struct LINNEAmdRelation), 0u, wx_relate_check, wx_relate_describe, wx_relate_preset, wx_relate_pass, wx_relate_commit, NULL, false, false };
 static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_mix_check, wx_mix_describe, NULL, wx_mix_pass, NULL, wx_place_read_back, true, false };
 static const WxConsumer WX_RESAMPLE = { "ResampleWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_resample_check, wx_resample_describe, wx_resample_preset, wx_place_pass, wx_resample_commit, wx_place_read_back, false, true };
+static const WxConsumer WX_OVERLAY = { "OverlayWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_overlay_check, wx_overlay_describe, NULL, wx_place_pass, wx_overlay_commit, NULL, false, false, true };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2612,10 +2632,14 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
         wx_resample_count(rg.data(), W, pl);
         if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
+    if (u.overlays) {
+        wx_overlay_count(c.ov_outs, c.ov_O, pl);
+        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory */
-    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples);
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples, u.overlays);
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
@@ -2623,12 +2647,14 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     if (u.back_preset) u.back_preset((uint32_t *)(hs_ + ls.o_back), W);
     wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
             (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL,
-            u.resamples ? (WxResample *)(hs_ + ls.o_side) : NULL, u.resamples ? (WxTile *)(hs_ + ls.o_tile) : NULL, u.resamples ? (uint32_t *)(hs_ + ls.o_coef) : NULL);
+            u.resamples ? (WxResample *)(hs_ + ls.o_side) : NULL, u.resamples ? (WxTile *)(hs_ + ls.o_tile) : NULL, u.resamples ? (uint32_t *)(hs_ + ls.o_coef) : NULL,
+            u.overlays ? (WxOvSource *)memset(hs_ + ls.o_ovsrc, 0, sizeof(WxOvSource) * W) : NULL);
+    if (u.overlays) wx_overlay_fill(c.ov_outs, c.ov_O, rg.data(), pl, (WxOvOutput *)(hs_ + ls.o_ovout), (WxTile *)(hs_ + ls.o_tile));
     for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
     const uint64_t o_acc = align_up(pl.scratch_bytes);             /* (the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples || u.overlays ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
@@ -2636,7 +2662,8 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     ln.side = (const WxBucket *)(wd + ls.o_side); ln.mix = (const WxMix *)(wd + ls.o_side); ln.wins = d_win; ln.acc = sd + o_acc; ln.back = (uint32_t *)(wd + ls.o_back); ln.fail = d_fail;
     ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout; ln.nmask = pl.nmask;
     ln.rs = (const WxResample *)(wd + ls.o_side); ln.tiles = (const WxTile *)(wd + ls.o_tile); ln.coef = (const uint32_t *)(wd + ls.o_coef); ln.ntile = pl.ntile; ln.sat = d_fail + W;
-    if (u.resamples) {                  /* the plan named the images by their offsets: now they have an address */
+    ln.ov_outs = (const WxOvOutput *)(wd + ls.o_ovout); ln.ov_srcs = (const WxOvSource *)(wd + ls.o_ovsrc);
+    if (u.resamples || u.overlays) {                  /* the plan named the images by their offsets: now they have an address */
         WxWindow *h_win = (WxWindow *)(hs_ + ls.o_win);
         for (uint32_t k = 0; k < pl.nwin; k++) h_win[k].out = ln.acc + (uintptr_t)h_win[k].out;
     }
@@ -2791,6 +2818,118 @@ extern "C" int LINNEAmd_ResampleWindowsDevice(struct LINNEAmdContext *ctx, struc
     return wx_entry(ctx, c, windows && specs);
 }
 extern "C" uint64_t LINNEAmd_ResampleLength(uint64_t num_samples, uint32_t up, uint32_t down) { return wxr_length(num_samples, up, down); }
+
+/* ---- LINNEAmd_OverlayWindowsDevice: the sources of all outputs are the windows of one windows call ---- */
+/* the gain (q + step * i) >> 32 lies in int16: in 128 bits */
+static bool ov_gain_fits(int64_t q, int64_t step, uint64_t i)
+{
+    const __int128 g = ((__int128)q + (__int128)step * (__int128)(unsigned __int128)i) >> 32;
+    return g >= -32768 && g <= 32767;
+}
+/* the checks on output o alone, in front of its sources' window checks; *C: the channel count its sources share */
+static int ov_check_output(const struct LINNEAmdOverlay &o, const struct LINNEAmdPcmLayout *ly, char *err, size_t cap, uint32_t *C)
+{
+    const char *who = "OverlayWindowsDevice";
+    err[0] = 0;
+    if (o.num_sources < 1u || o.num_sources > LINNE_AMD_OVERLAY_MAX_SOURCES) { snprintf(err, cap, "%s: num_sources %u is not 1 .. %u", who, o.num_sources, (unsigned)LINNE_AMD_OVERLAY_MAX_SOURCES); return LNN_INVALID_ARGUMENT; }
+    if (!o.sources) { snprintf(err, cap, "%s: null sources", who); return LNN_INVALID_ARGUMENT; }
+    if (o.shift > 31u) { snprintf(err, cap, "%s: shift %u > 31", who, o.shift); return LNN_INVALID_ARGUMENT; }
+    if (o.clip_bits == 1u || o.clip_bits > 32u) { snprintf(err, cap, "%s: clip_bits %u is neither 0 nor 2 .. 32", who, o.clip_bits); return LNN_INVALID_ARGUMENT; }
+    if (o.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", who); return LNN_INVALID_ARGUMENT; }
+    for (uint32_t j = 0; j < o.num_sources; j++) {
+        const struct LINNEAmdOverlaySource &s = o.sources[j];
+        if (!s.index || !s.d_stream) { snprintf(err, cap, "%s: source %u: null argument", who, j); return LNN_INVALID_ARGUMENT; }
+        if (s.reserved != 0u) { snprintf(err, cap, "%s: source %u: reserved is not 0", who, j); return LNN_INVALID_ARGUMENT; }
+        if (s.num_samples == 0u) { snprintf(err, cap, "%s: source %u: num_samples 0", who, j); return LNN_INVALID_ARGUMENT; }
+        if (s.at > o.num_samples || s.num_samples > o.num_samples - s.at) { snprintf(err, cap, "%s: source %u: at %llu + %llu samples beyond the output's %llu", who, j, (unsigned long long)s.at, (unsigned long long)s.num_samples, (unsigned long long)o.num_samples); return LNN_INVALID_ARGUMENT; }
+        if (!ov_gain_fits(s.gain_q32, s.step_q32, 0u) || !ov_gain_fits(s.gain_q32, s.step_q32, s.num_samples - 1u)) { snprintf(err, cap, "%s: source %u: a gain outside -32768 .. 32767", who, j); return LNN_INVALID_ARGUMENT; }
+    }
+    *C = o.sources[0].index->shape.num_channels;
+    for (uint32_t j = 1; j < o.num_sources; j++)
+        if (o.sources[j].index->shape.num_channels != *C) { snprintf(err, cap, "%s: source %u: %u channels, source 0 has %u", who, j, o.sources[j].index->shape.num_channels, *C); return LNN_INVALID_ARGUMENT; }
+    if (!o.d_pcm) { snprintf(err, cap, "%s: null d_pcm", who); return LNN_INVALID_ARGUMENT; }
+    if (ly) {
+        const int why = sb_layout_check(ly->format, ly->channel_stride, ly->sample_stride, (uint64_t)(uintptr_t)o.d_pcm, *C, o.num_samples, true);
+        if (why != SB_LY_OK) { snprintf(err, cap, "%s: %s", who, sb_layout_text(why)); return LNN_INVALID_ARGUMENT; }
+    } else if (*C > 1u && o.pcm_stride < o.num_samples) { snprintf(err, cap, "%s: pcm_stride %llu < %llu samples", who, (unsigned long long)o.pcm_stride, (unsigned long long)o.num_samples); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+
+extern "C" int LINNEAmd_OverlayWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdOverlay *outputs, struct LINNEAmdPcmLayout *layouts,
+        uint32_t num_outputs, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    const uint32_t O = num_outputs;
+    if (O == 0) return LNN_OK;
+    if (!outputs) { snprintf(ctx->err, sizeof(ctx->err), "OverlayWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    char text[sizeof(ctx->err)];
+    std::vector<WxOvOut> outs;
+    std::vector<struct LINNEAmdWindow> wins;
+    std::vector<const struct LINNEAmdOverlaySource *> srcs;
+    const uint32_t *fail = NULL;
+    WxPlanned pl;
+    WxCall c = wx_call(&WX_OVERLAY, NULL, 0, group_frames, NULL, NULL);
+    int ret = items_try(ctx, [&] {
+        /* 1. the outputs' own checks; the sources of those that pass become the call's windows */
+        outs.resize(O);
+        for (uint32_t k = 0; k < O; k++) {
+            struct LINNEAmdOverlay &o = outputs[k];
+            WxOvOut &d = outs[k];
+            uint32_t C = 0;
+            memset(&d, 0, sizeof(d));
+            d.w0 = (uint32_t)wins.size();
+            o.result = ov_check_output(o, layouts ? layouts + k : NULL, text, sizeof(text), &C);
+            if (o.result != LNN_OK) continue;
+            d.checked = 1; d.nsrc = o.num_sources; d.n = o.num_samples; d.out = o.d_pcm; d.shift = o.shift; d.clip_bits = o.clip_bits;
+            if (layouts) { d.fmt = layouts[k].format; d.stride = layouts[k].channel_stride; d.sstride = layouts[k].sample_stride; }
+            else { d.fmt = LINNE_AMD_PCM_S32; d.stride = o.pcm_stride; d.sstride = 1u; }
+            for (uint32_t j = 0; j < o.num_sources; j++) {
+                const struct LINNEAmdOverlaySource &s = o.sources[j];
+                struct LINNEAmdWindow w;
+                w.index = s.index; w.d_stream = s.d_stream; w.first_sample = s.first_sample; w.num_samples = s.num_samples;
+                w.d_pcm = o.d_pcm; w.pcm_stride = 0u; w.result = LNN_OK;   /* (the passes write the source's image, not this) */
+                wins.push_back(w); srcs.push_back(&s);
+                /* A source the host refuses ends the output's windows: the output cannot be written any more, and only the sources in
+                 * front of this one can still change its code, by failing their Rice check */
+                const WxCall one = wx_call(&WX_OVERLAY, &w, 1, 0, NULL, NULL);
+                uint64_t r1;
+                if (wx_check_window(ctx, one, 0, text, sizeof(text), &r1) != LNN_OK) { d.nsrc = j + 1u; break; }
+            }
+        }
+        if (wins.size() >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "OverlayWindowsDevice: %llu sources in one call: too many", (unsigned long long)wins.size()); return (int)LNN_NG; }
+        c.win = wins.data(); c.W = (uint32_t)wins.size(); c.ov_src = srcs.data(); c.ov_outs = outs.data(); c.ov_O = O;
+        /* 2. the windows call over all sources */
+        return wx_decode(ctx, c, pl, &fail);
+    });
+    if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, O, [&](uint32_t k) { outputs[k].result = LNN_NG; }) != LNN_OK) return LNN_NG;
+    /* 3. an output has the result of its lowest-numbered failing source; the call that of its lowest-numbered failing output */
+    int first = LNN_OK;
+    for (uint32_t k = 0; k < O; k++) {
+        struct LINNEAmdOverlay &o = outputs[k];
+        const WxOvOut &d = outs[k];
+        uint32_t C, j = 0;
+        if (d.checked) {
+            while (j < d.nsrc && wins[d.w0 + j].result == LNN_OK) j++;
+            if (j == d.nsrc) { if (layouts) layouts[k].saturated = (fail && fail[c.W + d.w0]) ? 1u : 0u; continue; }
+            o.result = wins[d.w0 + j].result;
+        }
+        if (first != LNN_OK) continue;
+        first = o.result;
+        if (!d.checked) (void)ov_check_output(o, layouts ? layouts + k : NULL, text, sizeof(text), &C);
+        else {
+            const uint32_t i = d.w0 + j;
+            char inner[sizeof(ctx->err)]; uint64_t r1;
+            if (pl.win[i].group >= 0 && fail)
+                snprintf(inner, sizeof(inner), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
+                        fail[i], (unsigned long long)wins[i].index->h_off[fail[i]]);
+            else (void)wx_check_window(ctx, c, i, inner, sizeof(inner), &r1);
+            snprintf(text, sizeof(text), "source %u: %.*s", j, (int)sizeof(text) - 24, inner);
+        }
+        items_first_text(ctx, "output", k, false, text);
+    }
+    return first;
+}
 
 /* one window of one stream */
 extern "C" int LINNEAmd_DecodeStreamDevice(struct LINNEAmdContext *ctx, const struct LINNEAmdStreamIndex *x, const uint8_t *d_stream,

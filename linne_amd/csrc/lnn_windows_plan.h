@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs, histogram, relate, mix and resample; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram, relate, mix, resample and overlay; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -110,6 +110,31 @@ struct WxTile { uint32_t win, p0; uint64_t m0, n0; };
 static_assert(sizeof(WxResample) == 128 && sizeof(WxTile) == 24, "a resample record is 128 bytes, a tile 24");
 #define WXR_TILE 256u
 
+/* ---- the overlaying consumer (lnn_k_overlay.h): its windows are the SOURCES of its outputs, in the caller's order, output by output ----
+ * one source (48 bytes), at its window's number in the call (not at its WxWindow's): its image, the int32 planar target of the passes,
+ * and where and under which gains it lies in its output */
+struct WxOvSource {
+    uint64_t img, istride;              /* the image's first word among the accumulators; words from one channel to the next: n rounded up to 4 */
+    uint64_t at, n;                     /* it covers output samples [at, at + n) */
+    int64_t gain, step;                 /* sample i of it under (gain + step * i) >> 32 */
+};
+/* one output that none of the host's checks failed (80 bytes); its tiles are WxTile with `win` its record here and m0 the tile's
+ * first output sample (p0 and n0 are 0) */
+struct WxOvOutput {
+    void *out; uint64_t stride, sstride;        /* the caller's PCM: element (ch, t) at out + (ch * stride + t * sstride) elements of fmt */
+    uint64_t n;                         /* its samples */
+    uint32_t src0, nsrc;                /* its sources' records, and their fail words: [src0, src0 + nsrc); its saturation word is src0's */
+    uint32_t C, shift;
+    int32_t lo, hi;                     /* the clip */
+    uint32_t scale_bits;                /* the float 2^-(Bf - 1), as in WxMix */
+    uint32_t fmt;                       /* LINNE_AMD_PCM_* */
+    uint32_t reserved[4];
+};
+static_assert(sizeof(WxOvSource) == 48 && sizeof(WxOvOutput) == 80, "an overlay source record is 48 bytes, an output record 80");
+/* what the plan reads of one output: its sources are windows [w0, w0 + nsrc) of the call (the caller leaves out those behind one that its
+ * checks refuse); checked: the output's own checks passed */
+struct WxOvOut { uint32_t w0, nsrc; int checked; uint64_t n; void *out; uint64_t stride, sstride; uint32_t fmt, shift, clip_bits; };
+
 /* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
 #define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
 #define WXH_BINS(h) ((h) & 0xFFFFu)
@@ -145,6 +170,7 @@ struct WxRange {
     const struct LINNEAmdMixSpec *mix;  /* the mixing consumer: its spec, checked (out_channels 1 .. 8, shift <= 31, clip_bits 0 or 2 .. 32) */
     const struct LINNEAmdResampleSpec *rs;      /* the resampling consumer: its spec, checked; [lo, lo + n) above is the window's INPUT range */
     uint64_t m_lo, m_n;                 /* ... and these its output samples, of the resampled stream */
+    const struct LINNEAmdOverlaySource *ov;     /* the overlaying consumer: the source this window is, checked */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -160,6 +186,7 @@ struct WxPlanned {
     /* the resampling consumer (wx_resample_count): every window's table in the coefficient area (windows of one (coef, up, taps) share
      * one), the area's words, the tiles of all live windows; ntile: the tiles written */
     std::vector<uint64_t> rs_coef; std::vector<uint8_t> rs_owner; uint64_t rs_words, rs_tiles, ntile;
+    uint64_t ov_outs, nov;              /* the overlaying consumer (wx_overlay_count): the outputs that get tiles (counted in rs_tiles); nov: their records written */
 };
 enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
 
@@ -203,8 +230,8 @@ static inline WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t
 /* the lists, in pinned memory and at the same offsets on the device: the words that come back (fail words, saturation words and
  * back_words 32-bit words per window of the consumer's own) | window records | the consumer's per-window records | block records |
  * the passes' COMPRESS records */
-struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef; };
-static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false)
+struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef, o_ovout, o_ovsrc; };
+static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false, bool overlays = false)
 {
     WxLists l;
     l.o_fail = 0; l.o_back = 2u * sizeof(uint32_t) * W; l.back_bytes = l.o_back + sizeof(uint32_t) * back_words * W;
@@ -218,6 +245,12 @@ static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_wor
         l.o_coef = wx_align(l.o_tile + sizeof(WxTile) * p.rs_tiles);
         l.bytes = wx_align(l.o_coef + sizeof(uint32_t) * p.rs_words);
     }
+    l.o_ovout = l.o_ovsrc = l.bytes;
+    if (overlays) {                     /* likewise: the tiles | the output records | a source record per window of the call */
+        l.o_ovout = wx_align(l.o_tile + sizeof(WxTile) * p.rs_tiles);
+        l.o_ovsrc = wx_align(l.o_ovout + sizeof(WxOvOutput) * p.ov_outs);
+        l.bytes = wx_align(l.o_ovsrc + sizeof(WxOvSource) * W);
+    }
     return l;
 }
 
@@ -227,7 +260,7 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
     p.win.resize(W);
     p.ngroups = 0; p.nlive = p.total_rec = p.total_crec = 0;
     p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = p.nmask = 0;
-    p.rs_coef.clear(); p.rs_owner.clear(); p.rs_words = p.rs_tiles = p.ntile = 0;
+    p.rs_coef.clear(); p.rs_owner.clear(); p.rs_words = p.rs_tiles = p.ntile = 0; p.ov_outs = p.nov = 0;
     for (uint32_t i = 0; i < W; i++) {
         WxPlan &pl = p.win[i];
         pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
@@ -331,11 +364,58 @@ static inline void wx_resample_record(const WxRange &w, const struct LINNEAmdSha
         }
 }
 
+/* ---- the overlaying consumer ---- */
+/* an output gets tiles when its own checks passed and every source of it is a live window of the plan */
+static inline bool wx_overlay_live(const WxOvOut &o, const WxPlanned &p)
+{
+    if (!o.checked) return false;
+    for (uint32_t j = 0; j < o.nsrc; j++) if (p.win[o.w0 + j].group < 0) return false;
+    return true;
+}
+/* between wx_plan_count and wx_lists: the outputs and the tiles the lists must have room for */
+static inline void wx_overlay_count(const WxOvOut *outs, uint32_t O, WxPlanned &p)
+{
+    for (uint32_t k = 0; k < O; k++) if (wx_overlay_live(outs[k], p)) { p.ov_outs++; p.rs_tiles += (outs[k].n + WXR_TILE - 1u) / WXR_TILE; }
+}
+/* a source's record (at its window's number i in the call); the window record names the image, as a resampled window's does */
+static inline void wx_overlay_source(const WxRange &w, const struct LINNEAmdShape &shape, WxPlanned &p, WxWindow &ww, WxOvSource &m)
+{
+    m.img = p.nacc; m.istride = (w.n + 3u) & ~(uint64_t)3u;
+    m.at = w.ov->at; m.n = w.n; m.gain = w.ov->gain_q32; m.step = w.ov->step_q32;
+    p.nacc += m.istride * shape.num_channels;
+    ww.out = (void *)(uintptr_t)(sizeof(int32_t) * m.img);
+    ww.fmt = LINNE_AMD_PCM_S32; ww.stride = m.istride; ww.sstride = 1u;
+}
+/* behind wx_plan_fill: the records and the tiles of the outputs that get them, in the caller's order */
+static inline void wx_overlay_fill(const WxOvOut *outs, uint32_t O, const WxRange *rg, WxPlanned &p, WxOvOutput *h_out, WxTile *h_tile)
+{
+    for (uint32_t k = 0; k < O; k++) {
+        const WxOvOut &o = outs[k];
+        if (!wx_overlay_live(o, p)) continue;
+        assert(p.nov < p.ov_outs);
+        const uint32_t oi = (uint32_t)p.nov++;
+        const struct LINNEAmdShape &shape = rg[o.w0].x.shape;
+        const uint32_t B = o.clip_bits ? o.clip_bits : 32u, Bf = o.clip_bits ? o.clip_bits : shape.bits_per_sample;
+        WxOvOutput &m = h_out[oi];
+        memset(&m, 0, sizeof(m));
+        m.out = o.out; m.stride = o.stride; m.sstride = o.sstride; m.fmt = o.fmt; m.n = o.n;
+        m.src0 = o.w0; m.nsrc = o.nsrc; m.C = shape.num_channels; m.shift = o.shift;
+        m.hi = (int32_t)(((uint64_t)1 << (B - 1u)) - 1u); m.lo = -m.hi - 1;
+        m.scale_bits = (128u - Bf) << 23;
+        for (uint64_t t0 = 0; t0 < o.n; t0 += WXR_TILE) {
+            assert(p.ntile < p.rs_tiles);
+            WxTile &t = h_tile[p.ntile++];
+            t.win = oi; t.p0 = 0u; t.m0 = t0; t.n0 = 0u;
+        }
+    }
+}
+
 /* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
- * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs */
+ * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs; h_ov,
+ * where it is given, has a record per window of the CALL (W of them, zeroed by the caller) and gets those of the live ones */
 static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
         WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL,
-        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL)
+        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL, WxOvSource *h_ov = NULL)
 {
     for (uint32_t g = 0; g < p.ngroups; g++) {
         const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
@@ -379,6 +459,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             ww.fmt = w.fmt; ww.stride = w.stride; ww.sstride = w.sstride;
             if (h_mix) wx_mix_record(*w.mix, shape, i, h_mix[wi]);
             if (h_rs) wx_resample_record(w, shape, i, wi, p, ww, h_rs[wi], h_tile, h_coef);
+            if (h_ov) wx_overlay_source(w, shape, p, ww, h_ov[i]);
             if (bucketing == WX_BITMASK) {
                 WxBucket &m = h_side[wi];
                 memset(&m, 0, sizeof(m));

@@ -40,6 +40,10 @@
  *   - -Z / --resample RATE[,TAPS] IN.lnn OUT.lnn writes IN at the sampling rate RATE, on the device (LINNEAmd_ResampleDesign's filter of
  *     TAPS coefficients per phase, 32 unless given; LINNEAmd_ResampleWindowsDevice into device PCM, clipped to the stream's bits; then
  *     LINNEAmd_EncodeStreamsDevice with IN's header but for the rate and the sample count): what Context.resample_streams writes.
+ *   - -J / --join OTHER.lnn[,OVERLAP] IN.lnn OUT.lnn writes IN followed by OTHER, crossfaded over OVERLAP samples (0 unless given: a hard
+ *     cut), on the device (LINNEAmd_OverlayWindowsDevice into device PCM -- the last OVERLAP samples of IN under a gain falling from
+ *     16384, the first OVERLAP of OTHER under the one rising to it, shift 14, clipped to IN's bits --, then LINNEAmd_EncodeStreamsDevice
+ *     with IN's header but for the sample count): what Context.crossfade_streams writes.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -55,9 +59,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, join, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec;
+    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec, *join_spec;
     const char *files[4096];
     int num_files;
 };
@@ -76,6 +80,7 @@ static void usage(const char *argv0)
     printf("       %s -R [BUCKET_SAMPLES] STREAM.lnn \n", argv0);
     printf("       %s -X ROW[/ROW...][>>SHIFT] IN.lnn OUT.lnn \n", argv0);
     printf("       %s -Z RATE[,TAPS] IN.lnn OUT.lnn \n", argv0);
+    printf("       %s -J OTHER.lnn[,OVERLAP] IN.lnn OUT.lnn \n", argv0);
     printf("options: \n"
            "  -e, --encode                           Encode mode \n"
            "  -d, --decode                           Decode mode \n"
@@ -89,6 +94,7 @@ static void usage(const char *argv0)
            "  -R, --relate                           Relate a .lnn stream's channels on the device: dot products, equal and opposite frames, correlation per pair (and bucket) \n"
            "  -X, --remix ROW[/ROW...][>>SHIFT]      Write a .lnn stream whose channels are an integer matrix of the input's: rows of C coefficients \n"
            "  -Z, --resample RATE[,TAPS]             Write a .lnn stream at the sampling rate RATE: an exact polyphase FIR of TAPS (32) coefficients per phase \n"
+           "  -J, --join OTHER.lnn[,OVERLAP]         Write IN followed by OTHER.lnn, crossfaded over OVERLAP (0) samples \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -145,6 +151,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (take_value(argc, argv, &i, "-L", "--levels", &v)) { o->levels = 1; o->levels_spec = v; }
         else if (take_value(argc, argv, &i, "-X", "--remix", &v)) { o->remix = 1; o->remix_spec = v; }
         else if (take_value(argc, argv, &i, "-Z", "--resample", &v)) { o->resample = 1; o->resample_spec = v; }
+        else if (take_value(argc, argv, &i, "-J", "--join", &v)) { o->join = 1; o->join_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -777,6 +784,96 @@ done:
     return rc;
 }
 
+/* "b.lnn", "b.lnn,4410": the other stream's file name, then optionally the overlap in samples, behind the LAST comma where digits
+ * alone follow it -> path (a copy), *overlap (0 unless given).  0, or a message in err */
+static int parse_join(const char *text, char *path, size_t path_cap, uint64_t *overlap, char *err, size_t cap)
+{
+    const char *comma = strrchr(text, ',');
+    size_t len = strlen(text);
+    *overlap = 0;
+    if (comma) {
+        const char *p = comma + 1;
+        char *end;
+        unsigned long long v;
+        if (!(*p >= '0' && *p <= '9')) { snprintf(err, cap, "join spec: an overlap in samples is expected at \"%s\"", p); return 1; }
+        v = strtoull(p, &end, 10);
+        if (*end != '\0') { snprintf(err, cap, "join spec: malformed at \"%s\"", end); return 1; }
+        if (v > 0xFFFFFFFFull) { snprintf(err, cap, "join spec: overlap %s is outside 0 .. 4294967295", p); return 1; }
+        *overlap = v;
+        len = (size_t)(comma - text);
+    }
+    if (len == 0) { snprintf(err, cap, "join spec: a file name is expected"); return 1; }
+    if (len >= path_cap) { snprintf(err, cap, "join spec: the file name is too long"); return 1; }
+    memcpy(path, text, len); path[len] = '\0';
+    return 0;
+}
+
+/* -J: the spec and the two headers are checked on the host; then both streams go to the device, LINNEAmd_StreamIndexCreate each, one
+ * LINNEAmd_OverlayWindowsDevice output of up to four sources into int32 planes beside them, and LINNEAmd_EncodeStreamsDevice make
+ * the output */
+static int join_one(const char *spec_text, const char *in_path, const char *out_path)
+{
+    enum { UNITY = 16384 };
+    uint8_t *buf = NULL, *other = NULL, *out = NULL;
+    void *d_out = NULL, *d_other = NULL;
+    struct LINNEAmdStreamIndex *xo = NULL;
+    uint32_t size = 0, osize = 0, k = 0;
+    struct resident r;
+    struct LINNEAmdOverlaySource src[4];
+    struct LINNEAmdOverlay ov;
+    struct LINNEAmdTrack tr;
+    struct LINNEHeader h, ho;
+    char err[512], path[4096];
+    uint64_t n, cap, overlap, na, nb;
+    int64_t fall = 0, step = 0;
+    FILE *fp;
+    int ret, stage, rc = 1;
+    memset(&r, 0, sizeof(r));
+    if (parse_join(spec_text, path, sizeof(path), &overlap, err, sizeof(err)) != 0) { fprintf(stderr, "%s \n", err); return 1; }
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    if (read_file(path, &other, &osize) != 0) { fprintf(stderr, "Failed to open %s. \n", path); free(buf); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK || (ret = LINNEDecoder_DecodeHeader(other, osize, &ho)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); goto done; }
+    na = h.num_samples; nb = ho.num_samples;
+    if (h.num_channels != ho.num_channels || h.sampling_rate != ho.sampling_rate) { fprintf(stderr, "join spec: %u channels at %u Hz cannot be joined with %u channels at %u Hz \n", (unsigned)h.num_channels, (unsigned)h.sampling_rate, (unsigned)ho.num_channels, (unsigned)ho.sampling_rate); goto done; }
+    if (na < 1 || nb < 1 || overlap > na || overlap > nb) { fprintf(stderr, "join spec: an overlap of %llu samples between streams of %llu and %llu \n", (unsigned long long)overlap, (unsigned long long)na, (unsigned long long)nb); goto done; }
+    n = na + nb - overlap;
+    if (n > 0xFFFFFFFFull) { fprintf(stderr, "join spec: %llu samples are more than a header names \n", (unsigned long long)n); goto done; }
+    if ((stage = resident_open(&r, buf, size, na, sizeof(int32_t) * n * h.num_channels, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to join! %s \n" : "%s \n", err); goto done; }
+    if (hipMalloc(&d_other, osize ? osize : 1) != hipSuccess || hipMemcpy(d_other, other, osize, hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "Failed to copy %s to the device. \n", path); goto done; }
+    if (!(xo = LINNEAmd_StreamIndexCreate(r.ctx, d_other, osize, &ret))) { fprintf(stderr, "Failed to join! %s does not index: %d (%s) \n", path, ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    /* the falling ramp is exactly UNITY at its first sample and would reach 0 one past its last; the rising one is its complement:
+     * the two gains add up to UNITY at every sample (what linne_amd.crossfade makes) */
+    if (overlap) { fall = ((int64_t)UNITY << 32) + ((int64_t)1 << 31); step = -(int64_t)((((uint64_t)UNITY) << 32) / overlap); }
+    memset(src, 0, sizeof(src));
+    if (na > overlap) { src[k].index = r.index; src[k].d_stream = r.d_stream; src[k].first_sample = 0; src[k].num_samples = na - overlap; src[k].at = 0; src[k].gain_q32 = (int64_t)UNITY << 32; k++; }
+    if (overlap) {
+        src[k].index = r.index; src[k].d_stream = r.d_stream; src[k].first_sample = na - overlap; src[k].num_samples = overlap; src[k].at = na - overlap; src[k].gain_q32 = fall; src[k].step_q32 = step; k++;
+        src[k].index = xo; src[k].d_stream = d_other; src[k].first_sample = 0; src[k].num_samples = overlap; src[k].at = na - overlap;
+        src[k].gain_q32 = ((int64_t)UNITY << 32) + (((int64_t)1 << 32) - 1) - fall; src[k].step_q32 = -step; k++;
+    }
+    if (nb > overlap) { src[k].index = xo; src[k].d_stream = d_other; src[k].first_sample = overlap; src[k].num_samples = nb - overlap; src[k].at = na; src[k].gain_q32 = (int64_t)UNITY << 32; k++; }
+    memset(&ov, 0, sizeof(ov));
+    ov.sources = src; ov.num_sources = k; ov.shift = 14; ov.clip_bits = h.bits_per_sample; ov.num_samples = n; ov.d_pcm = r.d_extra; ov.pcm_stride = n;
+    if ((ret = LINNEAmd_OverlayWindowsDevice(r.ctx, &ov, NULL, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to join! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    memset(&tr, 0, sizeof(tr));
+    tr.header = h; tr.header.num_samples = (uint32_t)n;
+    cap = LINNEAmd_EncodeStreamBound(&tr.header);
+    if (hipMalloc(&d_out, cap ? cap : 1) != hipSuccess) { fprintf(stderr, "Failed to allocate %llu bytes on the device. \n", (unsigned long long)cap); d_out = NULL; goto done; }
+    tr.d_pcm = r.d_extra; tr.pcm_stride = n; tr.d_out = d_out; tr.capacity = cap;
+    if ((ret = LINNEAmd_EncodeStreamsDevice(r.ctx, &tr, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to encode! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(out = malloc(tr.out_bytes ? (size_t)tr.out_bytes : 1)) || hipMemcpy(out, d_out, tr.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the stream. \n"); goto done; }
+    if (!(fp = fopen(out_path, "wb")) || fwrite(out, 1, (size_t)tr.out_bytes, fp) != tr.out_bytes) { fprintf(stderr, "File output error! %s \n", out_path); if (fp) fclose(fp); goto done; }
+    fclose(fp);
+    rc = 0;
+done:
+    if (xo) LINNEAmd_StreamIndexDestroy(xo);
+    if (d_out) (void)hipFree(d_out);
+    if (d_other) (void)hipFree(d_other);
+    resident_close(&r);
+    free(out); free(other); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -785,6 +882,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.join) {
+        if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.resample || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -J takes another stream's file name, an input and an output file name and no other mode. \n", argv[0]); return 1; }
+        return join_one(o.join_spec, o.files[0], o.files[1]);
+    }
     if (o.resample) {
         if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -Z takes a sampling rate, an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return resample_one(o.resample_spec, o.files[0], o.files[1]);
