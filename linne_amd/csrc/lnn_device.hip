@@ -2293,6 +2293,8 @@ static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
+/* the most workgroups of SX_PLACE_THREADS (256) threads a launch takes: fewer than 2^32 threads in all */
+#define WX_LAUNCH_GROUPS 0xFFFFFFu
 static dim3 wx_grid(uint64_t n) { const uint64_t g = (n + WXB_THREADS - 1u) / WXB_THREADS; return dim3((uint32_t)(g < 65536u ? g : 65536u)); }
 
 /* ---- place, and compare, which reads the PCM that place writes (LINNE_AMD_PCM_F32 is refused as on encode) ---- */
@@ -2700,8 +2702,15 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
         la.recs = d_rec; la.nrec = p.nrec; la.wins = d_win; la.fail = d_fail; la.C = C; la.S = S; la.bits = x->shape.bits_per_sample; la.pcm = d_data;
         la.sat = d_fail + W; la.scale = ldexpf(1.0f, 1 - (int)x->shape.bits_per_sample);
         la.xch = (S + SX_PLACE_THREADS - 1u) / SX_PLACE_THREADS;
-        if ((uint64_t)p.nrec * la.xch >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %u blocks: %s", who, p.nrec, advice); return LNN_NG; }
-        SX_TRY(u.pass(ctx, ln, la));
+        /* A launch takes fewer than 2^32 threads: a grid beyond that is not refused, its thread count wraps and the records behind the
+         * wrap are never visited.  So the consumer takes the pass's records in runs of at most WX_LAUNCH_GROUPS / xch -- 65535 blocks
+         * of 65535 samples; a record's workgroups read nothing but their own record, the pass's synthesis and the windows' lists */
+        if (la.xch > WX_LAUNCH_GROUPS) la.xch = WX_LAUNCH_GROUPS;      /* (a record's workgroups stride over its pieces: fewer of them visit the same) */
+        const uint32_t run = WX_LAUNCH_GROUPS / la.xch;
+        for (uint32_t r0 = 0; r0 < p.nrec; r0 += run) {
+            la.recs = d_rec + r0; la.nrec = p.nrec - r0 < run ? p.nrec - r0 : run;
+            SX_TRY(u.pass(ctx, ln, la));
+        }
     }
     if (u.commit) SX_TRY(u.commit(ctx, ln));
     /* 5. the fail words and what lies behind them, with the call's one wait */
