@@ -429,6 +429,12 @@ enum LINNEAmdResampleTimingKind {
 enum LINNEAmdOverlayTimingKind {
     LINNE_AMD_OVERLAY_T_OVERLAY = 101       /* the outputs whose sources did not fail summed from their sources' images, once, behind the last pass (k_wx_overlay) */
 };
+/* lag correlation of windows (LINNEAmd_LagWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice -- its kind 59 places the needles'
+ * and the haystacks' samples into the call's scratch --, and one launch each of kinds 102 and 103 per call that takes a pass) */
+enum LINNEAmdLagsTimingKind {
+    LINNE_AMD_LAGS_T_LAGS = 102,            /* the sliding products of every tile (probe, pair, 256 lags, a chunk of the needle) into its partial sums, once, behind the last pass (k_wx_lags) */
+    LINNE_AMD_LAGS_T_COMMIT = 103           /* the partial sums added per lag and the tables of the probes that did not fail written, once, behind kind 102 (k_wx_lags_commit) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -1040,6 +1046,57 @@ struct LINNEAmdOverlay {
 int LINNEAmd_OverlayWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdOverlay *outputs,
         struct LINNEAmdPcmLayout *layouts /* [num_outputs] in/out; NULL: int32 planar, pcm_stride */,
         uint32_t num_outputs, uint32_t group_frames);
+
+/* ---- sliding one resident stream over another: the exact lag correlation, which finds the `at` an overlay needs ----
+ * LINNEAmd_LagWindowsDevice answers num_probes probes.  A probe slides n = num_samples samples of stream A, the needle, from
+ * first_a on, over stream B, the haystack, at the num_lags lags L = lag_first + l, 0 <= l < num_lags, for num_pairs channel pairs
+ * (ca, cb) = (chan_a[p], chan_b[p]).  With a[c][j] and b[c][j] the values LINNEAmd_DecodeStreamDevice gives for the two streams, and
+ * b = 0 FOR EVERY j OUTSIDE [0, N_b), N_b the sample count of B's header -- a range off the haystack's ends is no error --, record
+ * (p, l) of the table holds
+ *   dot  = sum over i < n of a[ca][first_a + i] * b[cb][first_b + L + i]       a 128-bit two's-complement sum, dot_hi * 2^64 + dot_lo;
+ *   b_sq = sum over i < n of b[cb][first_b + L + i]^2                          unsigned 128 bits;
+ * and d_a_sq, where it is given, gets a_sq = sum over i < n of a[ca][first_a + i]^2 once per pair, low word then high word: the three
+ * give the exact dot / sqrt(a_sq * b_sq) of every lag without a second decode.  Every index is formed in 128 bits on the host; A and
+ * B may be one stream (the autocorrelation), a pair may name a channel twice, and two pairs may be the same.
+ * Results: probes[i].result.  For probe i alone INVALID_ARGUMENT ("probe <i>: LagWindowsDevice: ..." in GetLastError) when a pointer
+ * (index_a, d_stream_a, index_b, d_stream_b, d_out) is NULL, reserved is not 0, num_samples is 0, num_lags is 0 or above
+ * LINNE_AMD_LAG_MAX_LAGS, num_pairs is outside 1 .. 8, num_samples * num_lags * num_pairs is above LINNE_AMD_LAG_MAX_PRODUCTS (which
+ * keeps one mistaken call from occupying a shared device for minutes: the device multiplies num_samples * num_pairs * (num_lags rounded
+ * up to 64) times, a wave of 64 lags being the least it works on, so at most 64 times the products counted), a channel is not one of its stream's, d_out or d_a_sq is not
+ * 8-byte aligned, or pair_stride < num_lags.  These come first.  A is then checked as a struct LINNEAmdWindow of
+ * LINNEAmd_DecodeWindowsDevice is ("probe <i>: needle: ..."): its range, its index's failing block at or before its range and, on the
+ * device, its Rice codes; B likewise ("probe <i>: haystack: ...") for the part of [first_b + lag_first, first_b + lag_first +
+ * num_lags - 1 + n) that lies inside [0, N_b).  A probe whose B range misses the stream entirely is valid and writes zeros; its A is
+ * still decoded, for a_sq.  A failing probe's memory is never written and the others are undisturbed; the call returns the lowest
+ * failing probe's code.  No byte outside the table elements named above is written; the streams are only read.  Whole-call failures
+ * are the decode call's.
+ * Every probe brings one or two windows into the decode call's plan -- A's range and B's clipped range --: shape groups, passes,
+ * group_frames (which never changes a byte), copies and the one host synchronisation are that call's.  The passes place the windows
+ * into int32 images in the context's scratch, 4 * C * (samples rounded up to 4) bytes each, beside 16 bytes of partial sums per lag of
+ * every tile (a probe's pair, 256 lags, 65536 needle samples) and 32 per tile; where that cannot be had the whole call fails with NG and nothing is
+ * written.  A pass has the decode call's launches (its kind 59 writes the images); a call that takes a pass adds one launch of kind
+ * 102 and one of kind 103 behind the last pass and nothing else, whatever the numbers of probes, pairs and lags are.  No atomics: a
+ * tile writes its own partial sums, and the result does not depend on scheduling.
+ * num_probes == 0 is OK; a NULL ctx, or NULL probes with num_probes > 0, INVALID_ARGUMENT.  Enqueued on the context's stream and
+ * synchronous. */
+#define LINNE_AMD_LAG_MAX_LAGS 65536u
+#define LINNE_AMD_LAG_MAX_PRODUCTS ((uint64_t)1 << 38)
+struct LINNEAmdLagSum {                 /* 32 bytes: one channel pair at one lag */
+    uint64_t dot_lo; int64_t dot_hi;    /* the sum of a * b: dot_hi * 2^64 + dot_lo */
+    uint64_t b_sq_lo; uint64_t b_sq_hi; /* the sum of b^2 under the needle at this lag */
+};
+struct LINNEAmdLagProbe {
+    const struct LINNEAmdStreamIndex *index_a; const uint8_t *d_stream_a;       /* the needle's stream, as in struct LINNEAmdWindow */
+    uint64_t first_a, num_samples;      /* the needle's range, num_samples >= 1, inside stream A */
+    const struct LINNEAmdStreamIndex *index_b; const uint8_t *d_stream_b;       /* the haystack; may be stream A */
+    uint64_t first_b; int64_t lag_first; uint32_t num_lags;     /* lags lag_first .. lag_first + num_lags - 1 */
+    uint32_t num_pairs; uint8_t chan_a[8], chan_b[8];   /* 1 .. 8 channel pairs */
+    struct LINNEAmdLagSum *d_out; uint64_t pair_stride; /* device, 8-byte aligned: pair p, lag l at d_out[p * pair_stride + l] */
+    uint64_t *d_a_sq;                   /* device, 8-byte aligned, or NULL: [num_pairs][2], low word then high word */
+    uint64_t reserved;                  /* 0 */
+    int32_t result;                     /* out */
+};
+int LINNEAmd_LagWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdLagProbe *probes, uint32_t num_probes, uint32_t group_frames);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

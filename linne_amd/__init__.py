@@ -64,6 +64,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_MixWindowsDevice",
     "LINNEAmd_ResampleWindowsDevice", "LINNEAmd_ResampleLength", "LINNEAmd_ResampleDesign",
     "LINNEAmd_OverlayWindowsDevice",
+    "LINNEAmd_LagWindowsDevice",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -363,6 +364,113 @@ def crossfade(n, unity):
     return (a, step), ((unity << 32) + (1 << 32) - 1 - a, -step)
 
 
+class LagSum(C.Structure):
+    """struct LINNEAmdLagSum (include/linne_amd.h): one channel pair at one lag"""
+    _fields_ = [("dot_lo", C.c_uint64), ("dot_hi", C.c_int64), ("b_sq_lo", C.c_uint64), ("b_sq_hi", C.c_uint64)]
+
+
+class LagProbe(C.Structure):
+    """struct LINNEAmdLagProbe (include/linne_amd.h)"""
+    _fields_ = [("index_a", C.c_void_p), ("d_stream_a", C.c_void_p), ("first_a", C.c_uint64), ("num_samples", C.c_uint64),
+                ("index_b", C.c_void_p), ("d_stream_b", C.c_void_p), ("first_b", C.c_uint64), ("lag_first", C.c_int64), ("num_lags", C.c_uint32),
+                ("num_pairs", C.c_uint32), ("chan_a", C.c_uint8 * 8), ("chan_b", C.c_uint8 * 8), ("d_out", C.c_void_p), ("pair_stride", C.c_uint64),
+                ("d_a_sq", C.c_void_p), ("reserved", C.c_uint64), ("result", C.c_int32)]
+
+
+LAG_MAX_LAGS, LAG_MAX_PRODUCTS = 65536, 1 << 38      # include/linne_amd.h LINNE_AMD_LAG_MAX_*
+LAG_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("b_sq_lo", "<u8"), ("b_sq_hi", "<u8")])
+
+
+class LagSums:
+    """one probe's table of lag_windows: `records`, an int64 CUDA tensor (P, num_lags, 4) holding a struct LINNEAmdLagSum per channel
+    pair and lag, `a_sq`, an int64 CUDA tensor (P, 2) holding the needle's sum of squares per pair (low word, high word), and what
+    the probe asked: lag_first and pairs, the (channel of a, channel of b) of every row"""
+
+    def __init__(self, records, a_sq, lag_first, pairs):
+        self.records, self.a_sq, self.lag_first, self.pairs = records, a_sq, int(lag_first), tuple(pairs)
+
+    def cpu(self):
+        """-> a numpy structured array (P, num_lags) with the fields dot_lo (unsigned), dot_hi, b_sq_lo and b_sq_hi (unsigned)"""
+        a = np.ascontiguousarray(self.records.cpu().numpy())
+        return a.view(LAG_DTYPE).reshape(a.shape[:2])
+
+    def a_squares(self):
+        """the needle's exact sums of squares: a list [P] of Python integers"""
+        return [(int(hi) << 64) + int(lo) for lo, hi in np.ascontiguousarray(self.a_sq.cpu().numpy()).view(np.uint64).reshape(-1, 2)]
+
+
+def _lag_table(table):
+    """a LagSums or its .cpu() -> the structured array (P, num_lags)"""
+    a = table.cpu() if isinstance(table, LagSums) else np.asarray(table)
+    assert a.dtype == LAG_DTYPE and a.ndim == 2, "a lag table is a LagSums or a LAG_DTYPE array (P, num_lags)"
+    return a
+
+
+def lag_dots(table):
+    """the exact sums of products of a LagSums or its .cpu(): a list [P][num_lags] of Python integers, dot_hi * 2^64 + dot_lo"""
+    return [[(int(r["dot_hi"]) << 64) + int(r["dot_lo"]) for r in row] for row in _lag_table(table)]
+
+
+def lag_energies(table):
+    """the exact sums of b^2 under the needle, likewise: a list [P][num_lags] of Python integers"""
+    return [[(int(r["b_sq_hi"]) << 64) + int(r["b_sq_lo"]) for r in row] for row in _lag_table(table)]
+
+
+def lag_correlation(table, a_sq=None):
+    """the correlation coefficients of a LagSums -> float64 (P, num_lags): dot / sqrt(a_sq * b_sq) per pair and lag, NaN where an energy
+    is 0.  a_sq: the needle's sums of squares per pair (Python integers), needed where `table` is a .cpu() array and not the LagSums.
+    The integers are divided as such, as `correlation` does.  Pure host code"""
+    from fractions import Fraction
+    if a_sq is None:
+        assert isinstance(table, LagSums), "a_sq is needed beside a bare table"
+        a_sq = table.a_squares()
+    dots, bsq = lag_dots(table), lag_energies(table)
+    out = np.full((len(dots), len(dots[0]) if dots else 0), np.nan, dtype=np.float64)
+    for p, row in enumerate(dots):
+        for l, d in enumerate(row):
+            if a_sq[p] > 0 and bsq[p][l] > 0:
+                r = math.sqrt(Fraction(d * d, int(a_sq[p]) * bsq[p][l]))
+                out[p, l] = -r if d < 0 else r
+    return out
+
+
+def best_lag(table, lag_first=None, a_sq=None):
+    """the lag at which the haystack best matches the needle -> (lag, coefficient).  The pairs' dots and energies are added per lag;
+    the lag maximises dot / sqrt(b_sq), candidates compared exactly by cross-multiplied integers (a lag whose b_sq is 0 has the
+    value 0); ties go to the smaller |lag|, then to the negative lag.  The coefficient is dot / sqrt(a_sq * b_sq) of the sums there,
+    NaN where an energy is 0 or a_sq is not known.  lag_first and a_sq default to the LagSums' own.  Pure host code"""
+    from fractions import Fraction
+    if isinstance(table, LagSums):
+        lag_first = table.lag_first if lag_first is None else lag_first
+        a_sq = table.a_squares() if a_sq is None else a_sq
+    assert lag_first is not None, "lag_first is needed beside a bare table"
+    lag_first = int(lag_first)
+    dots, bsq = lag_dots(table), lag_energies(table)
+    assert dots and dots[0], "a table of at least one pair and one lag"
+    d = [sum(row[l] for row in dots) for l in range(len(dots[0]))]
+    e = [sum(row[l] for row in bsq) for l in range(len(dots[0]))]
+
+    def above(i, j):
+        """is d_i / sqrt(e_i) > d_j / sqrt(e_j)?  (0 where e is 0)"""
+        di, dj = (d[i] if e[i] else 0), (d[j] if e[j] else 0)
+        ei, ej = (e[i] or 1), (e[j] or 1)
+        if (di > 0) != (dj > 0) or di == 0 or dj == 0:
+            return di > dj
+        lhs, rhs = di * di * ej, dj * dj * ei                      # both of one sign: compare the squares, the other way round below 0
+        return lhs > rhs if di > 0 else lhs < rhs
+
+    best = 0
+    for l in range(1, len(d)):
+        La, Lb = lag_first + l, lag_first + best
+        if above(l, best) or (not above(best, l) and (abs(La), La) < (abs(Lb), Lb)):
+            best = l
+    ea = sum(int(v) for v in a_sq) if a_sq is not None else 0
+    coef = float("nan")
+    if ea > 0 and e[best] > 0:
+        coef = math.sqrt(Fraction(d[best] * d[best], ea * e[best])) * (-1 if d[best] < 0 else 1)
+    return lag_first + best, coef
+
+
 RELATION_DTYPE = np.dtype([("dot_lo", "<u8"), ("dot_hi", "<i8"), ("num_equal", "<u8"), ("num_opposite", "<u8")])
 
 
@@ -605,6 +713,7 @@ def _load():
     L.LINNEAmd_ResampleLength.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
     L.LINNEAmd_ResampleDesign.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.LINNEAmd_OverlayWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Overlay), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_LagWindowsDevice.argtypes = [C.c_void_p, C.POINTER(LagProbe), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
     L.LINNEAmd_GetLastSpliceCount.restype = C.c_int64
     L.LINNEAmd_GetLastSpliceCount.argtypes = [C.c_void_p, C.c_int]
@@ -1376,6 +1485,85 @@ class Context:
             if len(sources) > OVERLAY_MAX_SOURCES:
                 raise ValueError(f"crossfade_streams: {len(sources)} sources in one output: at most {OVERLAY_MAX_SOURCES}")
             return self._overlay_indexed([(at, sources)], 14, bits, preset, block, ms, group_frames)[0]
+
+    def lag_windows(self, probes, group_frames=0, return_codes=False):
+        """slide ranges of resident .lnn streams over each other: per probe, channel pair and lag the exact sums of a * b and of b^2
+        under the needle, and the needle's sum of squares, no PCM written (include/linne_amd.h LINNEAmd_LagWindowsDevice states the
+        arithmetic).  probes: a sequence of (stream_a, index_a, first_a, n, stream_b, index_b, first_b, lag_first, num_lags, pairs):
+        n samples of a from first_a on (None: to the stream's end), the needle, against b at the lags lag_first .. lag_first +
+        num_lags - 1, where sample first_a + i of a meets sample first_b + lag + i of b and b is 0 outside the stream; pairs a
+        sequence of (channel of a, channel of b), None: (c, c) for every channel the two streams share.  Values outside the call's
+        bounds raise ValueError before any call.  -> a list of LagSums, views of one allocation; lag_dots, lag_correlation and
+        best_lag read a table on the host.  Errors follow measure_windows: LinneAmdError with .code and .codes when a probe fails;
+        with return_codes -> (answers, codes), a failing probe's answer is None, and only a failure of the whole call raises"""
+        import torch
+        Q = len(probes)
+        arr = (LagProbe * max(Q, 1))()
+        keep, asked, at = [], [], 0
+        for k, (sa, xa, first_a, n, sb, xb, first_b, lag_first, num_lags, pairs) in enumerate(probes):
+            ta, tb = self._stream_bytes(sa), self._stream_bytes(sb)
+            first_a, n, _ = _sample_range(xa, ta.numel(), first_a, n, "probe %d: the needle", k)
+            _sample_range(xb, tb.numel(), 0, 0, "probe %d: the haystack", k)
+            ca, cb = xa.header["num_channels"], xb.header["num_channels"]
+            pairs = [(c, c) for c in range(min(ca, cb))] if pairs is None else [(int(i), int(j)) for i, j in pairs]
+            first_b, lag_first, num_lags = int(first_b), int(lag_first), int(num_lags)
+            if not 1 <= num_lags <= LAG_MAX_LAGS or not 1 <= len(pairs) <= 8:
+                raise ValueError(f"probe {k}: num_lags is 1 .. {LAG_MAX_LAGS}, pairs are 1 .. 8")
+            if n < 1 or first_a < 0 or first_a + n > xa.header["num_samples"]:
+                raise ValueError(f"probe {k}: the needle [{first_a}, {first_a + n}) is not a range of at least one sample of its stream's {xa.header['num_samples']}")
+            if n * num_lags * len(pairs) > LAG_MAX_PRODUCTS:
+                raise ValueError(f"probe {k}: {n} samples * {num_lags} lags * {len(pairs)} pairs is more than LAG_MAX_PRODUCTS = 2^38")
+            if not (0 <= first_b < 1 << 64 and -(1 << 63) <= lag_first < 1 << 63):
+                raise ValueError(f"probe {k}: first_b is unsigned, lag_first an int64")
+            if any(not (0 <= i < ca and 0 <= j < cb) for i, j in pairs):
+                raise ValueError(f"probe {k}: a pair names a channel its stream ({ca} and {cb} channels) does not have")
+            keep += [ta, tb]
+            asked.append((at, len(pairs), num_lags, lag_first, pairs))
+            at += len(pairs) * (4 * num_lags + 2)
+            q = arr[k]
+            q.index_a, q.d_stream_a, q.first_a, q.num_samples = xa.h, ta.data_ptr(), first_a, n
+            q.index_b, q.d_stream_b, q.first_b, q.lag_first, q.num_lags, q.num_pairs = xb.h, tb.data_ptr(), first_b, lag_first, num_lags, len(pairs)
+            for p, (i, j) in enumerate(pairs):
+                q.chan_a[p], q.chan_b[p] = i, j
+            q.pair_stride, q.reserved = num_lags, 0
+        flat = torch.zeros(max(at, 1), dtype=torch.int64, device=f"cuda:{self.device}")
+        for k, (base, P, L, _, _) in enumerate(asked):
+            arr[k].d_out, arr[k].d_a_sq = flat.data_ptr() + 8 * base, flat.data_ptr() + 8 * (base + 4 * P * L)
+        self._fence()
+        ret = lib.LINNEAmd_LagWindowsDevice(self.h, arr, Q, int(group_frames))
+        codes = [int(arr[k].result) for k in range(Q)]
+        if ret != 0:
+            msg = lib.LINNEAmd_GetLastError(self.h).decode()
+            if not (return_codes and msg.startswith("probe ")):        # (a failing probe's text starts with its number)
+                raise LinneAmdError(f"LagWindowsDevice -> {ret}: {msg}", ret, codes)
+        out = [LagSums(flat[base:base + 4 * P * L].view(P, L, 4), flat[base + 4 * P * L:base + 4 * P * L + 2 * P].view(P, 2), lag_first, pairs)
+               if codes[k] == 0 else None for k, (base, P, L, lag_first, pairs) in enumerate(asked)]
+        return (out, codes) if return_codes else out
+
+    def align_streams(self, pairs_of_streams, max_lag, needle=None):
+        """where does stream b best match stream a?  pairs_of_streams: a sequence of (stream_a, stream_b); for each, a needle of a --
+        `needle` = (first, n), default the whole stream cut to what LAG_MAX_PRODUCTS allows at these lags -- is slid over b: needle sample first + i meets b's sample first + lag + i,
+        lag in -max_lag .. max_lag, over every channel the two share.
+        One index_streams call and one lag_windows call -> a list of (lag, coefficient) as best_lag gives them: b delayed by d
+        samples against a gives lag d, and laying a at output sample d of an overlay with b at 0 lines the two up.  A `needle`
+        given that with 2 * max_lag + 1 lags passes LAG_MAX_PRODUCTS raises ValueError naming the limit"""
+        max_lag = int(max_lag)
+        if not 0 <= max_lag <= (LAG_MAX_LAGS - 1) // 2:
+            raise ValueError(f"align_streams: max_lag is 0 .. {(LAG_MAX_LAGS - 1) // 2}")
+        if len(pairs_of_streams) == 0:
+            return []
+        flat = [s for pair in pairs_of_streams for s in pair]
+        with self._whole_streams(flat) as (ts, xs, _):
+            probes = []
+            for k in range(len(pairs_of_streams)):
+                ta, tb, xa, xb = ts[2 * k], ts[2 * k + 1], xs[2 * k], xs[2 * k + 1]
+                P = min(xa.header["num_channels"], xb.header["num_channels"])
+                room = LAG_MAX_PRODUCTS // ((2 * max_lag + 1) * P)
+                first, n = (0, min(xa.header["num_samples"], room)) if needle is None else (int(needle[0]), int(needle[1]))
+                if n > room:
+                    raise ValueError(f"align_streams: pair {k}: {n} samples * {2 * max_lag + 1} lags * {P} pairs is more than LAG_MAX_PRODUCTS = 2^38: give a needle of at most {LAG_MAX_PRODUCTS // ((2 * max_lag + 1) * P)} samples")
+                probes.append((ta, xa, first, n, tb, xb, first, -max_lag, 2 * max_lag + 1, None))
+            return [best_lag(t) for t in self.lag_windows(probes)]
 
     def compare_windows(self, windows, group_frames=0, return_codes=False):
         """many sample windows of resident .lnn streams compared with resident PCM in one call, nothing decoded into memory of the

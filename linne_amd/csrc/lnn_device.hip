@@ -58,6 +58,7 @@
 #include "lnn_k_mix.h"
 #include "lnn_k_resample.h"
 #include "lnn_k_overlay.h"
+#include "lnn_k_lags.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -78,6 +79,7 @@ static_assert(LINNE_AMD_RELATE_T_RELATE == 95 && LINNE_AMD_RELATE_T_COMMIT == 97
 static_assert(LINNE_AMD_MIX_T_MIX == 98, "the mix call's timing kind is 98");
 static_assert(LINNE_AMD_RESAMPLE_T_PRESET == 99 && LINNE_AMD_RESAMPLE_T_RESAMPLE == 100, "the resample call's timing kinds are 99 and 100");
 static_assert(LINNE_AMD_OVERLAY_T_OVERLAY == 101, "the overlay call's timing kind is 101");
+static_assert(LINNE_AMD_LAGS_T_LAGS == 102 && LINNE_AMD_LAGS_T_COMMIT == 103, "the lag call's timing kinds are 102 and 103");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2253,9 +2255,10 @@ struct WxLaunch {
     const WxBucket *side; const WxMix *mix; const WxWindow *wins; uint8_t *acc; uint32_t *back; const uint32_t *fail; uint32_t nwin; uint64_t nacc, nout, nmask;
     const WxResample *rs; const WxTile *tiles; const uint32_t *coef; uint64_t ntile; uint32_t *sat;        /* the resampling consumer's */
     const WxOvOutput *ov_outs; const WxOvSource *ov_srcs;          /* the overlaying consumer's, beside tiles, ntile and sat */
+    const WxLagTile *lg_tiles; const uint32_t *lg_runs; const WxLagProbe *lg_probes; const WxLagImage *lg_imgs; uint64_t nlgrun, lg_part;     /* the lag consumer's, beside ntile */
 };
-/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The ten calls are the
- * ten constant instances below; a launch that a consumer does not have is NULL */
+/* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The eleven calls are the
+ * eleven constant instances below; a launch that a consumer does not have is NULL */
 struct WxConsumer {
     const char *name;                   /* in the call's texts */
     uint32_t back_words;                /* 32-bit words per window behind the fail and saturation words, which come back with them */
@@ -2274,6 +2277,8 @@ struct WxConsumer {
                                          * windows' input ranges into images among the accumulators, the commit filters them (a consumer without buckets) */
     bool overlays;                      /* the windows are the sources of the call's outputs (WxCall.ov_*): the passes place them into images among the
                                          * accumulators, the commit sums the outputs from them (a consumer without buckets) */
+    bool lags;                          /* the windows are the needles and haystacks of the call's probes (WxCall.lag_*): the passes place them into images
+                                         * among the accumulators, the commit slides them (a consumer without buckets) */
 };
 struct WxCall {
     const WxConsumer *use;
@@ -2284,12 +2289,13 @@ struct WxCall {
     const struct LINNEAmdMixSpec *mix;  /* [W], mix alone: its specs go beside its layouts */
     const struct LINNEAmdResampleSpec *rs;      /* [W], resample alone, likewise */
     const struct LINNEAmdOverlaySource *const *ov_src; const WxOvOut *ov_outs; uint32_t ov_O;      /* overlay alone: window i's source [W]; the outputs [ov_O] */
+    const WxLagIn *lag_in; uint32_t lag_Q;      /* lags alone: the probes [lag_Q] */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
     WxCall c;
     c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL; c.rs = NULL;
-    c.ov_src = NULL; c.ov_outs = NULL; c.ov_O = 0;
+    c.ov_src = NULL; c.ov_outs = NULL; c.ov_O = 0; c.lag_in = NULL; c.lag_Q = 0;
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
@@ -2563,6 +2569,20 @@ static int wx_overlay_commit(LINNEAmdContext *ctx, const WxLaunch &l)
     return LNN_OK;
 }
 
+/* ---- lags: the passes place the needles' and the haystacks' ranges into images; two launches slide them (lnn_k_lags.h) ---- */
+static int wx_lags_check(const WxCall &, uint32_t, char *, size_t) { return LNN_OK; }      /* (the probes' checks came in front of the windows') */
+static void wx_lags_describe(const WxCall &, uint32_t, WxRange &) {}
+static int wx_lags_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxLagsArgs ga;
+    ga.tiles = l.lg_tiles; ga.ntiles = (uint32_t)l.ntile; ga.runs = l.lg_runs; ga.nruns = (uint32_t)l.nlgrun; ga.probes = l.lg_probes; ga.imgs = l.lg_imgs;
+    ga.fail = l.fail; ga.acc = (const int32_t *)l.acc; ga.part = (uint64_t *)((int32_t *)l.acc + l.lg_part);
+    /* (a call whose live windows all belong to probes with a window the host refused has no tile: the one workgroup returns at once) */
+    SX_LAUNCH(NULL, LINNE_AMD_LAGS_T_LAGS, k_wx_lags, dim3(ga.ntiles ? ga.ntiles : 1u), dim3(WXL_LAGS), 0, ctx->stream, ga);
+    SX_LAUNCH(NULL, LINNE_AMD_LAGS_T_COMMIT, k_wx_lags_commit, dim3(ga.nruns ? ga.nruns : 1u), dim3(WXL_LAGS), 0, ctx->stream, ga);
+    return LNN_OK;
+}
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false, false };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false, false };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false, false };
@@ -2573,6 +2593,7 @@ static const WxConsumer WX_RELATE = { "RelateWindowsDevice", 0u, NULL, WX_BUCKET
 static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_mix_check, wx_mix_describe, NULL, wx_mix_pass, NULL, wx_place_read_back, true, false };
 static const WxConsumer WX_RESAMPLE = { "ResampleWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_resample_check, wx_resample_describe, wx_resample_preset, wx_place_pass, wx_resample_commit, wx_place_read_back, false, true };
 static const WxConsumer WX_OVERLAY = { "OverlayWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_overlay_check, wx_overlay_describe, NULL, wx_place_pass, wx_overlay_commit, NULL, false, false, true };
+static const WxConsumer WX_LAGS = { "LagWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_lags_check, wx_lags_describe, NULL, wx_place_pass, wx_lags_commit, NULL, false, false, false, true };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2638,10 +2659,14 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
         wx_overlay_count(c.ov_outs, c.ov_O, pl);
         if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
+    if (u.lags) {
+        wx_lag_count(c.lag_in, c.lag_Q, pl);
+        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of lags in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory */
-    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples, u.overlays);
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples, u.overlays, u.lags);
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
@@ -2650,13 +2675,15 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
             (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL,
             u.resamples ? (WxResample *)(hs_ + ls.o_side) : NULL, u.resamples ? (WxTile *)(hs_ + ls.o_tile) : NULL, u.resamples ? (uint32_t *)(hs_ + ls.o_coef) : NULL,
-            u.overlays ? (WxOvSource *)memset(hs_ + ls.o_ovsrc, 0, sizeof(WxOvSource) * W) : NULL);
+            u.overlays ? (WxOvSource *)memset(hs_ + ls.o_ovsrc, 0, sizeof(WxOvSource) * W) : NULL,
+            u.lags ? (WxLagImage *)memset(hs_ + ls.o_lgimg, 0, sizeof(WxLagImage) * W) : NULL);
+    if (u.lags) wx_lag_fill(c.lag_in, c.lag_Q, pl, (WxLagProbe *)(hs_ + ls.o_lgprobe), (WxLagTile *)(hs_ + ls.o_tile), (uint32_t *)(hs_ + ls.o_lgrun));
     if (u.overlays) wx_overlay_fill(c.ov_outs, c.ov_O, rg.data(), pl, (WxOvOutput *)(hs_ + ls.o_ovout), (WxTile *)(hs_ + ls.o_tile));
     for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
     const uint64_t o_acc = align_up(pl.scratch_bytes);             /* (the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples || u.overlays ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples || u.overlays || u.lags ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
@@ -2665,7 +2692,9 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     ln.nwin = pl.nwin; ln.nacc = pl.nacc; ln.nout = pl.nout; ln.nmask = pl.nmask;
     ln.rs = (const WxResample *)(wd + ls.o_side); ln.tiles = (const WxTile *)(wd + ls.o_tile); ln.coef = (const uint32_t *)(wd + ls.o_coef); ln.ntile = pl.ntile; ln.sat = d_fail + W;
     ln.ov_outs = (const WxOvOutput *)(wd + ls.o_ovout); ln.ov_srcs = (const WxOvSource *)(wd + ls.o_ovsrc);
-    if (u.resamples || u.overlays) {                  /* the plan named the images by their offsets: now they have an address */
+    ln.lg_tiles = (const WxLagTile *)(wd + ls.o_tile); ln.lg_runs = (const uint32_t *)(wd + ls.o_lgrun); ln.lg_probes = (const WxLagProbe *)(wd + ls.o_lgprobe);
+    ln.lg_imgs = (const WxLagImage *)(wd + ls.o_lgimg); ln.nlgrun = pl.nlgrun; ln.lg_part = pl.lg_part;
+    if (u.resamples || u.overlays || u.lags) {        /* the plan named the images by their offsets: now they have an address */
         WxWindow *h_win = (WxWindow *)(hs_ + ls.o_win);
         for (uint32_t k = 0; k < pl.nwin; k++) h_win[k].out = ln.acc + (uintptr_t)h_win[k].out;
     }
@@ -2936,6 +2965,115 @@ extern "C" int LINNEAmd_OverlayWindowsDevice(struct LINNEAmdContext *ctx, struct
             snprintf(text, sizeof(text), "source %u: %.*s", j, (int)sizeof(text) - 24, inner);
         }
         items_first_text(ctx, "output", k, false, text);
+    }
+    return first;
+}
+
+/* ---- LINNEAmd_LagWindowsDevice: the needles and the clipped haystacks of all probes are the windows of one windows call ---- */
+/* the checks on probe q alone, in front of its windows' checks */
+static int lg_check_probe(const struct LINNEAmdLagProbe &q, char *err, size_t cap)
+{
+    const char *who = "LagWindowsDevice";
+    err[0] = 0;
+    if (!q.index_a || !q.d_stream_a || !q.index_b || !q.d_stream_b) { snprintf(err, cap, "%s: null argument", who); return LNN_INVALID_ARGUMENT; }
+    if (!q.d_out) { snprintf(err, cap, "%s: null d_out", who); return LNN_INVALID_ARGUMENT; }
+    if (q.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", who); return LNN_INVALID_ARGUMENT; }
+    if (q.num_samples == 0u) { snprintf(err, cap, "%s: num_samples 0", who); return LNN_INVALID_ARGUMENT; }
+    if (q.num_lags < 1u || q.num_lags > LINNE_AMD_LAG_MAX_LAGS) { snprintf(err, cap, "%s: num_lags %u is not 1 .. %u", who, q.num_lags, (unsigned)LINNE_AMD_LAG_MAX_LAGS); return LNN_INVALID_ARGUMENT; }
+    if (q.num_pairs < 1u || q.num_pairs > LINNE_MAX_NUM_CHANNELS) { snprintf(err, cap, "%s: num_pairs %u is not 1 .. %u", who, q.num_pairs, (unsigned)LINNE_MAX_NUM_CHANNELS); return LNN_INVALID_ARGUMENT; }
+    if ((unsigned __int128)q.num_samples * q.num_lags * q.num_pairs > (unsigned __int128)LINNE_AMD_LAG_MAX_PRODUCTS) {
+        snprintf(err, cap, "%s: %llu samples * %u lags * %u pairs > 2^38 products", who, (unsigned long long)q.num_samples, q.num_lags, q.num_pairs);
+        return LNN_INVALID_ARGUMENT;
+    }
+    for (uint32_t p = 0; p < q.num_pairs; p++) {
+        if (q.chan_a[p] >= q.index_a->shape.num_channels) { snprintf(err, cap, "%s: pair %u: channel %u of a needle of %u", who, p, q.chan_a[p], q.index_a->shape.num_channels); return LNN_INVALID_ARGUMENT; }
+        if (q.chan_b[p] >= q.index_b->shape.num_channels) { snprintf(err, cap, "%s: pair %u: channel %u of a haystack of %u", who, p, q.chan_b[p], q.index_b->shape.num_channels); return LNN_INVALID_ARGUMENT; }
+    }
+    if ((uint64_t)(uintptr_t)q.d_out & 7u) { snprintf(err, cap, "%s: d_out is not 8-byte aligned", who); return LNN_INVALID_ARGUMENT; }
+    if ((uint64_t)(uintptr_t)q.d_a_sq & 7u) { snprintf(err, cap, "%s: d_a_sq is not 8-byte aligned", who); return LNN_INVALID_ARGUMENT; }
+    if (q.pair_stride < q.num_lags) { snprintf(err, cap, "%s: pair_stride %llu < %u lags", who, (unsigned long long)q.pair_stride, q.num_lags); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+/* the haystack samples probe q reads, clipped to the stream's [0, N_b): [*lo, *lo + *n), *n 0 when the range misses the stream; *b0:
+ * first_b + lag_first relative to *lo, never positive.  In 128 bits */
+static void lg_haystack(const struct LINNEAmdLagProbe &q, uint64_t *lo, uint64_t *n, int64_t *b0)
+{
+    const __int128 S = (__int128)(unsigned __int128)q.first_b + q.lag_first, E = S + (q.num_lags - 1u) + (__int128)(unsigned __int128)q.num_samples;
+    const __int128 N = (__int128)(unsigned __int128)q.index_b->header.num_samples;
+    const __int128 a = S < 0 ? (__int128)0 : S, b = E > N ? N : E;
+    *b0 = S < 0 ? (int64_t)S : 0;       /* (>= -2^63: first_b is not negative) */
+    *lo = 0u; *n = 0u;
+    if (a < b) { *lo = (uint64_t)a; *n = (uint64_t)(b - a); }
+}
+
+extern "C" int LINNEAmd_LagWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdLagProbe *probes, uint32_t num_probes, uint32_t group_frames)
+{
+    if (!ctx) return LNN_INVALID_ARGUMENT;
+    ctx->err[0] = 0;
+    const uint32_t Q = num_probes;
+    if (Q == 0) return LNN_OK;
+    if (!probes) { snprintf(ctx->err, sizeof(ctx->err), "LagWindowsDevice: null argument"); return LNN_INVALID_ARGUMENT; }
+    char text[sizeof(ctx->err)];
+    std::vector<WxLagIn> in;
+    std::vector<struct LINNEAmdWindow> wins;
+    const uint32_t *fail = NULL;
+    WxPlanned pl;
+    WxCall c = wx_call(&WX_LAGS, NULL, 0, group_frames, NULL, NULL);
+    int ret = items_try(ctx, [&] {
+        /* 1. the probes' own checks; the needle and the clipped haystack of those that pass become the call's windows */
+        in.resize(Q);
+        for (uint32_t k = 0; k < Q; k++) {
+            struct LINNEAmdLagProbe &q = probes[k];
+            WxLagIn &d = in[k];
+            memset(&d, 0, sizeof(d));
+            d.wa = (uint32_t)wins.size(); d.wb = WXL_NOWIN;
+            q.result = lg_check_probe(q, text, sizeof(text));
+            if (q.result != LNN_OK) continue;
+            d.checked = 1; d.n = q.num_samples; d.nlags = q.num_lags; d.npair = q.num_pairs; d.out = q.d_out; d.pstride = q.pair_stride; d.a_sq = q.d_a_sq;
+            memcpy(d.ca, q.chan_a, sizeof(d.ca)); memcpy(d.cb, q.chan_b, sizeof(d.cb));
+            struct LINNEAmdWindow w;
+            w.index = q.index_a; w.d_stream = q.d_stream_a; w.first_sample = q.first_a; w.num_samples = q.num_samples;
+            w.d_pcm = (int32_t *)q.d_out; w.pcm_stride = 0u; w.result = LNN_OK;    /* (the passes write the window's image, not this) */
+            wins.push_back(w);
+            /* a needle the host refuses ends the probe's windows: the probe cannot be answered any more */
+            const WxCall one = wx_call(&WX_LAGS, &w, 1, 0, NULL, NULL);
+            uint64_t r1, lo, n;
+            if (wx_check_window(ctx, one, 0, text, sizeof(text), &r1) != LNN_OK) continue;
+            lg_haystack(q, &lo, &n, &d.b0);
+            if (n == 0) continue;
+            d.wb = (uint32_t)wins.size();
+            w.index = q.index_b; w.d_stream = q.d_stream_b; w.first_sample = lo; w.num_samples = n;
+            wins.push_back(w);
+        }
+        if (wins.size() >= 0xFFFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "LagWindowsDevice: %llu windows in one call: too many", (unsigned long long)wins.size()); return (int)LNN_NG; }
+        c.win = wins.data(); c.W = (uint32_t)wins.size(); c.lag_in = in.data(); c.lag_Q = Q;
+        /* 2. the windows call over all needles and haystacks */
+        return wx_decode(ctx, c, pl, &fail);
+    });
+    if (items_end(ctx, NULL, ret, false, ret != LNN_OK, NULL, Q, [&](uint32_t k) { probes[k].result = LNN_NG; }) != LNN_OK) return LNN_NG;
+    /* 3. a probe has the result of its needle, then of its haystack; the call that of its lowest-numbered failing probe */
+    int first = LNN_OK;
+    for (uint32_t k = 0; k < Q; k++) {
+        struct LINNEAmdLagProbe &q = probes[k];
+        const WxLagIn &d = in[k];
+        uint32_t i = d.wa; const char *what = "needle";
+        if (d.checked) {
+            if (wins[i].result == LNN_OK && d.wb != WXL_NOWIN) { i = d.wb; what = "haystack"; }
+            if (wins[i].result == LNN_OK) continue;
+            q.result = wins[i].result;
+        }
+        if (first != LNN_OK) continue;
+        first = q.result;
+        if (!d.checked) (void)lg_check_probe(q, text, sizeof(text));
+        else {
+            char inner[sizeof(ctx->err)]; uint64_t r1;
+            if (pl.win[i].group >= 0 && fail)
+                snprintf(inner, sizeof(inner), "block %u (byte %llu of the stream): its Rice codes do not end where its size field says (a block no encoder writes)",
+                        fail[i], (unsigned long long)wins[i].index->h_off[fail[i]]);
+            else (void)wx_check_window(ctx, c, i, inner, sizeof(inner), &r1);
+            snprintf(text, sizeof(text), "%s: %.*s", what, (int)sizeof(text) - 24, inner);
+        }
+        items_first_text(ctx, "probe", k, false, text);
     }
     return first;
 }

@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs, histogram, relate, mix, resample and overlay; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram, relate, mix, resample, overlay and slide; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -135,6 +135,39 @@ static_assert(sizeof(WxOvSource) == 48 && sizeof(WxOvOutput) == 80, "an overlay 
  * checks refuse); checked: the output's own checks passed */
 struct WxOvOut { uint32_t w0, nsrc; int checked; uint64_t n; void *out; uint64_t stride, sstride; uint32_t fmt, shift, clip_bits; };
 
+/* ---- the lag consumer (lnn_k_lags.h): its windows are the needles and the clipped haystacks of its probes, in the caller's order ----
+ * one window's image (32 bytes), at its window's number in the call: the int32 planar target of the passes, as an overlay source's */
+struct WxLagImage {
+    uint64_t img, istride;              /* the image's first word among the accumulators; words from one channel to the next: n rounded up to 4 */
+    uint64_t lo, n;                     /* it holds stream samples [lo, lo + n) */
+};
+/* one probe that none of the host's checks failed (80 bytes) */
+struct WxLagProbe {
+    void *out; uint64_t pstride;        /* the caller's table: pair p, lag l at out[p * pstride + l] (struct LINNEAmdLagSum) */
+    uint64_t *a_sq;                     /* the caller's [npair][2], or NULL */
+    uint64_t n;                         /* the needle's samples */
+    int64_t b0;                         /* word b0 + l + i of the haystack's image meets needle sample i at lag number l; <= 0, and words outside the image are 0 */
+    uint32_t wa, wb;                    /* the needle's and the haystack's windows in the call: their images and fail words; wb WXL_NOWIN: the haystack is all zeros */
+    uint32_t nlags, npair, nchunk, ntl; /* lags, pairs, chunks of WXL_CHUNK needle samples, tiles of WXL_LAGS lags */
+    uint8_t ca[LINNE_MAX_NUM_CHANNELS], cb[LINNE_MAX_NUM_CHANNELS];
+};
+/* a tile: WXL_LAGS lags from l0 on of one pair of one probe, over chunk `chunk` of the needle; the chunks of one (probe, pair, l0) follow
+ * each other in the list, and the commit's list names the first of each such run */
+struct WxLagTile { uint32_t probe, pair, l0, chunk; };
+static_assert(sizeof(WxLagImage) == 32 && sizeof(WxLagProbe) == 80 && sizeof(WxLagTile) == 16, "a lag image is 32 bytes, a probe record 80, a tile 16");
+#define WXL_LAGS 256u
+#define WXL_CHUNK 65536u
+#define WXL_NOWIN 0xFFFFFFFFu
+/* a tile's partial sums among the accumulators, in 64-bit words: (lo, hi) of the dot per lag, then the chunk's sum of b^2 at the tile's
+ * first lag and its sum of a^2, (lo, hi) each */
+#define WXL_PART_WORDS (2u * WXL_LAGS + 4u)
+/* what the plan reads of one probe: checked: its own checks and its windows' host checks passed; its needle is window wa of the call, its
+ * clipped haystack window wb (WXL_NOWIN: the range misses the stream) */
+struct WxLagIn {
+    int checked; uint32_t wa, wb; uint64_t n; int64_t b0; uint32_t nlags, npair;
+    void *out; uint64_t pstride; uint64_t *a_sq; uint8_t ca[LINNE_MAX_NUM_CHANNELS], cb[LINNE_MAX_NUM_CHANNELS];
+};
+
 /* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
 #define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
 #define WXH_BINS(h) ((h) & 0xFFFFu)
@@ -187,6 +220,9 @@ struct WxPlanned {
      * one), the area's words, the tiles of all live windows; ntile: the tiles written */
     std::vector<uint64_t> rs_coef; std::vector<uint8_t> rs_owner; uint64_t rs_words, rs_tiles, ntile;
     uint64_t ov_outs, nov;              /* the overlaying consumer (wx_overlay_count): the outputs that get tiles (counted in rs_tiles); nov: their records written */
+    /* the lag consumer (wx_lag_count): the probes that get tiles (counted in rs_tiles) and the runs of tiles the commit takes; nlg and
+     * nlgrun: those written; lg_part: the partial sums' first word among the accumulators (wx_lag_fill) */
+    uint64_t lg_probes, lg_runs, nlg, nlgrun, lg_part;
 };
 enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
 
@@ -230,8 +266,8 @@ static inline WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t
 /* the lists, in pinned memory and at the same offsets on the device: the words that come back (fail words, saturation words and
  * back_words 32-bit words per window of the consumer's own) | window records | the consumer's per-window records | block records |
  * the passes' COMPRESS records */
-struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef, o_ovout, o_ovsrc; };
-static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false, bool overlays = false)
+struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef, o_ovout, o_ovsrc, o_lgrun, o_lgprobe, o_lgimg; };
+static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false, bool overlays = false, bool lags = false)
 {
     WxLists l;
     l.o_fail = 0; l.o_back = 2u * sizeof(uint32_t) * W; l.back_bytes = l.o_back + sizeof(uint32_t) * back_words * W;
@@ -251,6 +287,13 @@ static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_wor
         l.o_ovsrc = wx_align(l.o_ovout + sizeof(WxOvOutput) * p.ov_outs);
         l.bytes = wx_align(l.o_ovsrc + sizeof(WxOvSource) * W);
     }
+    l.o_lgrun = l.o_lgprobe = l.o_lgimg = l.bytes;
+    if (lags) {                         /* likewise: the tiles | the commit's runs | the probe records | an image record per window of the call */
+        l.o_lgrun = wx_align(l.o_tile + sizeof(WxLagTile) * p.rs_tiles);
+        l.o_lgprobe = wx_align(l.o_lgrun + sizeof(uint32_t) * p.lg_runs);
+        l.o_lgimg = wx_align(l.o_lgprobe + sizeof(WxLagProbe) * p.lg_probes);
+        l.bytes = wx_align(l.o_lgimg + sizeof(WxLagImage) * W);
+    }
     return l;
 }
 
@@ -261,6 +304,7 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
     p.ngroups = 0; p.nlive = p.total_rec = p.total_crec = 0;
     p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = p.nmask = 0;
     p.rs_coef.clear(); p.rs_owner.clear(); p.rs_words = p.rs_tiles = p.ntile = 0; p.ov_outs = p.nov = 0;
+    p.lg_probes = p.lg_runs = p.nlg = p.nlgrun = p.lg_part = 0;
     for (uint32_t i = 0; i < W; i++) {
         WxPlan &pl = p.win[i];
         pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
@@ -410,12 +454,66 @@ static inline void wx_overlay_fill(const WxOvOut *outs, uint32_t O, const WxRang
     }
 }
 
+/* ---- the lag consumer ---- */
+/* a probe gets tiles when its checks passed and its windows are live windows of the plan */
+static inline bool wx_lag_live(const WxLagIn &q, const WxPlanned &p)
+{
+    return q.checked && p.win[q.wa].group >= 0 && (q.wb == WXL_NOWIN || p.win[q.wb].group >= 0);
+}
+static inline uint64_t wxl_lag_tiles(uint32_t nlags) { return ((uint64_t)nlags + WXL_LAGS - 1u) / WXL_LAGS; }
+static inline uint64_t wxl_chunks(uint64_t n) { return (n + WXL_CHUNK - 1u) / WXL_CHUNK; }
+/* between wx_plan_count and wx_lists: the probes, the runs and the tiles the lists must have room for */
+static inline void wx_lag_count(const WxLagIn *in, uint32_t Q, WxPlanned &p)
+{
+    for (uint32_t k = 0; k < Q; k++) if (wx_lag_live(in[k], p)) {
+        const uint64_t runs = in[k].npair * wxl_lag_tiles(in[k].nlags);
+        p.lg_probes++; p.lg_runs += runs; p.rs_tiles += runs * wxl_chunks(in[k].n);
+    }
+}
+/* a window's image (at its window's number i in the call); the window record names the image, as an overlay source's does */
+static inline void wx_lag_image(const WxRange &w, const struct LINNEAmdShape &shape, WxPlanned &p, WxWindow &ww, WxLagImage &m)
+{
+    m.img = p.nacc; m.istride = (w.n + 3u) & ~(uint64_t)3u; m.lo = w.lo; m.n = w.n;
+    p.nacc += m.istride * shape.num_channels;
+    ww.out = (void *)(uintptr_t)(sizeof(int32_t) * m.img);
+    ww.fmt = LINNE_AMD_PCM_S32; ww.stride = m.istride; ww.sstride = 1u;
+}
+/* behind wx_plan_fill: the records, the tiles and the runs of the probes that get them, in the caller's order; the partial sums lie
+ * behind the images, WXL_PART_WORDS 64-bit words per tile */
+static inline void wx_lag_fill(const WxLagIn *in, uint32_t Q, WxPlanned &p, WxLagProbe *h_probe, WxLagTile *h_tile, uint32_t *h_run)
+{
+    for (uint32_t k = 0; k < Q; k++) {
+        const WxLagIn &q = in[k];
+        if (!wx_lag_live(q, p)) continue;
+        assert(p.nlg < p.lg_probes);
+        const uint32_t pi = (uint32_t)p.nlg++;
+        WxLagProbe &m = h_probe[pi];
+        memset(&m, 0, sizeof(m));
+        m.out = q.out; m.pstride = q.pstride; m.a_sq = q.a_sq; m.n = q.n; m.b0 = q.b0; m.wa = q.wa; m.wb = q.wb;
+        m.nlags = q.nlags; m.npair = q.npair; m.nchunk = (uint32_t)wxl_chunks(q.n); m.ntl = (uint32_t)wxl_lag_tiles(q.nlags);
+        memcpy(m.ca, q.ca, sizeof(m.ca)); memcpy(m.cb, q.cb, sizeof(m.cb));
+        for (uint32_t pr = 0; pr < m.npair; pr++)
+            for (uint32_t lt = 0; lt < m.ntl; lt++) {
+                assert(p.nlgrun < p.lg_runs);
+                h_run[p.nlgrun++] = (uint32_t)p.ntile;
+                for (uint32_t c = 0; c < m.nchunk; c++) {
+                    assert(p.ntile < p.rs_tiles);
+                    WxLagTile &t = h_tile[p.ntile++];
+                    t.probe = pi; t.pair = pr; t.l0 = lt * WXL_LAGS; t.chunk = c;
+                }
+            }
+    }
+    p.lg_part = (p.nacc + 3u) & ~(uint64_t)3u;  /* (in the images' 32-bit words: 16-byte aligned) */
+    p.nacc = p.lg_part + 2u * WXL_PART_WORDS * p.ntile;
+}
+
 /* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
  * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs; h_ov,
- * where it is given, has a record per window of the CALL (W of them, zeroed by the caller) and gets those of the live ones */
+ * where it is given, has a record per window of the CALL (W of them, zeroed by the caller) and gets those of the live ones; h_lag
+ * likewise */
 static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
         WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL,
-        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL, WxOvSource *h_ov = NULL)
+        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL, WxOvSource *h_ov = NULL, WxLagImage *h_lag = NULL)
 {
     for (uint32_t g = 0; g < p.ngroups; g++) {
         const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
@@ -460,6 +558,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             if (h_mix) wx_mix_record(*w.mix, shape, i, h_mix[wi]);
             if (h_rs) wx_resample_record(w, shape, i, wi, p, ww, h_rs[wi], h_tile, h_coef);
             if (h_ov) wx_overlay_source(w, shape, p, ww, h_ov[i]);
+            if (h_lag) wx_lag_image(w, shape, p, ww, h_lag[i]);
             if (bucketing == WX_BITMASK) {
                 WxBucket &m = h_side[wi];
                 memset(&m, 0, sizeof(m));

@@ -44,6 +44,10 @@
  *     cut), on the device (LINNEAmd_OverlayWindowsDevice into device PCM -- the last OVERLAP samples of IN under a gain falling from
  *     16384, the first OVERLAP of OTHER under the one rising to it, shift 14, clipped to IN's bits --, then LINNEAmd_EncodeStreamsDevice
  *     with IN's header but for the sample count): what Context.crossfade_streams writes.
+ *   - -A / --align OTHER.lnn[,MAX_LAG[,FIRST,N]] IN.lnn prints the lag at which OTHER best matches IN, per channel the two share and for
+ *     all of them together, on the device (one LINNEAmd_LagWindowsDevice probe at the lags -MAX_LAG .. MAX_LAG, 4096 unless given; the
+ *     needle N samples of IN from FIRST on, unless given the whole stream cut to the call's products limit): what Context.align_streams
+ *     returns, compared as exactly.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -52,6 +56,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,9 +64,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, join, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, join, align, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec, *join_spec;
+    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec, *join_spec, *align_spec;
     const char *files[4096];
     int num_files;
 };
@@ -95,6 +100,8 @@ static void usage(const char *argv0)
            "  -X, --remix ROW[/ROW...][>>SHIFT]      Write a .lnn stream whose channels are an integer matrix of the input's: rows of C coefficients \n"
            "  -Z, --resample RATE[,TAPS]             Write a .lnn stream at the sampling rate RATE: an exact polyphase FIR of TAPS (32) coefficients per phase \n"
            "  -J, --join OTHER.lnn[,OVERLAP]         Write IN followed by OTHER.lnn, crossfaded over OVERLAP (0) samples \n"
+           "  -A, --align OTHER.lnn[,MAX_LAG[,FIRST,N]]  Print the lag at which OTHER.lnn best matches IN (-A OTHER.lnn[,MAX_LAG[,FIRST,N]] IN.lnn): \n"
+           "                                         lags -MAX_LAG .. MAX_LAG (4096), the needle N samples of IN from FIRST on \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -152,6 +159,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (take_value(argc, argv, &i, "-X", "--remix", &v)) { o->remix = 1; o->remix_spec = v; }
         else if (take_value(argc, argv, &i, "-Z", "--resample", &v)) { o->resample = 1; o->resample_spec = v; }
         else if (take_value(argc, argv, &i, "-J", "--join", &v)) { o->join = 1; o->join_spec = v; }
+        else if (take_value(argc, argv, &i, "-A", "--align", &v)) { o->align = 1; o->align_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -874,6 +882,155 @@ done:
     return rc;
 }
 
+/* "b.lnn", "b.lnn,4096", "b.lnn,4096,0,220500": the other stream's file name, then optionally the largest lag, then optionally the
+ * needle's first sample and its length, which come together; numbers are the trailing fields that begin with a digit -> path (a
+ * copy), *max_lag (4096 unless given), *has_needle, *first, *n.  0, or a message in err */
+static int parse_align(const char *text, char *path, size_t path_cap, uint64_t *max_lag, int *has_needle, uint64_t *first, uint64_t *n, char *err, size_t cap)
+{
+    size_t len = strlen(text);
+    unsigned long long v[3];
+    int count = 0;
+    *max_lag = 4096; *has_needle = 0; *first = *n = 0;
+    if (memchr(text, ',', len)) {
+        while (count < 3) {
+            size_t at = len;
+            const char *p;
+            char *end;
+            while (at > 0 && text[at - 1] != ',') at--;
+            if (at == 0) break;                                 /* no comma in front: the file name */
+            p = text + at;
+            if (!(*p >= '0' && *p <= '9')) {
+                if (count == 0) { snprintf(err, cap, "lag spec: a largest lag in samples is expected at \"%s\"", p); return 1; }
+                break;
+            }
+            errno = 0;
+            v[count] = strtoull(p, &end, 10);
+            if (end != text + len) { snprintf(err, cap, "lag spec: malformed at \"%.*s\"", (int)(text + len - end), end); return 1; }
+            if (errno != 0) { snprintf(err, cap, "lag spec: %.*s is outside 64 bits", (int)(len - at), p); return 1; }
+            count++;
+            len = at - 1;
+        }
+        if (count == 2) { snprintf(err, cap, "lag spec: the needle's first sample and its length come together, behind the largest lag"); return 1; }
+        if (count == 1) *max_lag = v[0];
+        if (count == 3) { *max_lag = v[2]; *first = v[1]; *n = v[0]; *has_needle = 1; }
+    }
+    if (*max_lag > (LINNE_AMD_LAG_MAX_LAGS - 1u) / 2u) { snprintf(err, cap, "lag spec: a largest lag of %llu is outside 0 .. %u", (unsigned long long)*max_lag, (unsigned)((LINNE_AMD_LAG_MAX_LAGS - 1u) / 2u)); return 1; }
+    if (len == 0) { snprintf(err, cap, "lag spec: a file name is expected"); return 1; }
+    if (len >= path_cap) { snprintf(err, cap, "lag spec: the file name is too long"); return 1; }
+    memcpy(path, text, len); path[len] = '\0';
+    return 0;
+}
+
+/* a * b * c in 384 bits, least significant limb first */
+static void mul3(unsigned __int128 a, unsigned __int128 b, unsigned __int128 c, uint64_t out[6])
+{
+    const uint64_t x[3][2] = { { (uint64_t)a, (uint64_t)(a >> 64) }, { (uint64_t)b, (uint64_t)(b >> 64) }, { (uint64_t)c, (uint64_t)(c >> 64) } };
+    uint64_t acc[6] = { x[0][0], x[0][1], 0, 0, 0, 0 }, next[6];
+    int f, i, j;
+    for (f = 1; f < 3; f++) {
+        memset(next, 0, sizeof(next));
+        for (i = 0; i < 6; i++)
+            for (j = 0; j < 2 && i + j < 6; j++) {
+                unsigned __int128 t = (unsigned __int128)acc[i] * x[f][j];
+                int k = i + j;
+                while (t != 0 && k < 6) { t += next[k]; next[k] = (uint64_t)t; t >>= 64; k++; }
+            }
+        memcpy(acc, next, sizeof(acc));
+    }
+    memcpy(out, acc, sizeof(acc));
+}
+/* is d_i / sqrt(e_i) above d_j / sqrt(e_j)?  (a lag without energy has the value 0.)  Exact: the squares cross-multiplied */
+static int lag_above(__int128 di, unsigned __int128 ei, __int128 dj, unsigned __int128 ej)
+{
+    uint64_t l[6], r[6];
+    int k;
+    if (ei == 0) di = 0;
+    if (ej == 0) dj = 0;
+    if ((di > 0) != (dj > 0) || di == 0 || dj == 0) return di > dj;
+    mul3((unsigned __int128)(di < 0 ? -di : di), (unsigned __int128)(di < 0 ? -di : di), ej, l);
+    mul3((unsigned __int128)(dj < 0 ? -dj : dj), (unsigned __int128)(dj < 0 ? -dj : dj), ei, r);
+    for (k = 5; k >= 0; k--) if (l[k] != r[k]) return di > 0 ? l[k] > r[k] : l[k] < r[k];
+    return 0;
+}
+/* linne_amd.best_lag over pairs [p0, p1) of a table [pairs][lags]: the pairs' dots and energies added per lag; ties go to the smaller
+ * |lag|, then to the negative lag -> the lag, *r = dot / sqrt(a_sq * b_sq) there (NaN where an energy is 0) */
+static int64_t best_lag(const struct LINNEAmdLagSum *t, const uint64_t *a_sq, uint32_t p0, uint32_t p1, uint32_t lags, int64_t lag_first, double *r)
+{
+    __int128 bd = 0; unsigned __int128 be = 0, ea = 0;
+    uint32_t best = 0, l, p;
+    for (p = p0; p < p1; p++) ea += ((unsigned __int128)a_sq[2u * p + 1u] << 64) | a_sq[2u * p];
+    for (l = 0; l < lags; l++) {
+        __int128 d = 0; unsigned __int128 e = 0;
+        for (p = p0; p < p1; p++) {
+            const struct LINNEAmdLagSum *s = t + (size_t)p * lags + l;
+            d += (__int128)(((unsigned __int128)(uint64_t)s->dot_hi << 64) | s->dot_lo);
+            e += ((unsigned __int128)s->b_sq_hi << 64) | s->b_sq_lo;
+        }
+        if (l > 0) {
+            const int64_t la = lag_first + l, lb = lag_first + best, ma = la < 0 ? -la : la, mb = lb < 0 ? -lb : lb;
+            if (!(lag_above(d, e, bd, be) || (!lag_above(bd, be, d, e) && (ma < mb || (ma == mb && la < lb))))) continue;
+        }
+        best = l; bd = d; be = e;
+    }
+    *r = (ea > 0 && be > 0) ? (double)((long double)bd / sqrtl((long double)ea * (long double)be)) : NAN;
+    return lag_first + best;
+}
+
+/* -A: the spec and the two headers are checked on the host; then both streams go to the device, LINNEAmd_StreamIndexCreate each and
+ * one LINNEAmd_LagWindowsDevice probe over the channels the two share; the host reads the table as linne_amd.best_lag does */
+static int align_one(const char *spec_text, const char *in_path)
+{
+    uint8_t *buf = NULL, *other = NULL;
+    void *d_other = NULL;
+    struct LINNEAmdStreamIndex *xo = NULL;
+    struct LINNEAmdLagSum *table = NULL;
+    uint64_t a_sq[16];
+    uint32_t size = 0, osize = 0, P, L, p;
+    struct resident r;
+    struct LINNEAmdLagProbe q;
+    struct LINNEHeader h, ho;
+    char err[512], path[4096];
+    uint64_t max_lag, first, n, room;
+    int has_needle, ret, stage, rc = 1;
+    double coef;
+    int64_t lag;
+    memset(&r, 0, sizeof(r));
+    if (parse_align(spec_text, path, sizeof(path), &max_lag, &has_needle, &first, &n, err, sizeof(err)) != 0) { fprintf(stderr, "%s \n", err); return 1; }
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    if (read_file(path, &other, &osize) != 0) { fprintf(stderr, "Failed to open %s. \n", path); free(buf); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK || (ret = LINNEDecoder_DecodeHeader(other, osize, &ho)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); goto done; }
+    P = h.num_channels < ho.num_channels ? h.num_channels : ho.num_channels;
+    L = (uint32_t)(2u * max_lag + 1u);
+    room = LINNE_AMD_LAG_MAX_PRODUCTS / ((uint64_t)L * P);
+    if (!has_needle) { first = 0; n = h.num_samples < room ? h.num_samples : room; }     /* the whole stream, cut to the products limit */
+    if (n < 1 || first > h.num_samples || n > h.num_samples - first) { fprintf(stderr, "lag spec: a needle of %llu samples from %llu on in a stream of %llu \n", (unsigned long long)n, (unsigned long long)first, (unsigned long long)h.num_samples); goto done; }
+    if (n > room) { fprintf(stderr, "lag spec: %llu samples * %u lags * %u pairs are more than LINNE_AMD_LAG_MAX_PRODUCTS = 2^38: a needle of at most %llu samples \n", (unsigned long long)n, L, P, (unsigned long long)room); goto done; }
+    if ((stage = resident_open(&r, buf, size, h.num_samples, sizeof(struct LINNEAmdLagSum) * (uint64_t)L * P + sizeof(a_sq), "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to align! %s \n" : "%s \n", err); goto done; }
+    if (hipMalloc(&d_other, osize ? osize : 1) != hipSuccess || hipMemcpy(d_other, other, osize, hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "Failed to copy %s to the device. \n", path); goto done; }
+    if (!(xo = LINNEAmd_StreamIndexCreate(r.ctx, d_other, osize, &ret))) { fprintf(stderr, "Failed to align! %s does not index: %d (%s) \n", path, ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    memset(&q, 0, sizeof(q));
+    q.index_a = r.index; q.d_stream_a = r.d_stream; q.first_a = first; q.num_samples = n;
+    q.index_b = xo; q.d_stream_b = d_other; q.first_b = first; q.lag_first = -(int64_t)max_lag; q.num_lags = L; q.num_pairs = P;
+    for (p = 0; p < P; p++) q.chan_a[p] = q.chan_b[p] = (uint8_t)p;
+    q.d_out = r.d_extra; q.pair_stride = L; q.d_a_sq = (uint64_t *)((struct LINNEAmdLagSum *)r.d_extra + (size_t)L * P);
+    if ((ret = LINNEAmd_LagWindowsDevice(r.ctx, &q, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to align! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+    if (!(table = malloc(sizeof(*table) * (size_t)L * P)) || hipMemcpy(table, q.d_out, sizeof(*table) * (size_t)L * P, hipMemcpyDeviceToHost) != hipSuccess
+            || hipMemcpy(a_sq, q.d_a_sq, sizeof(uint64_t) * 2u * P, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+    for (p = 0; p < P; p++) {
+        lag = best_lag(table, a_sq, p, p + 1u, L, q.lag_first, &coef);
+        printf("channel %u: lag %lld correlation %.9f \n", p, (long long)lag, coef);
+    }
+    lag = best_lag(table, a_sq, 0, P, L, q.lag_first, &coef);
+    printf("all %u channels: lag %lld correlation %.9f \n", P, (long long)lag, coef);
+    rc = 0;
+done:
+    if (xo) LINNEAmd_StreamIndexDestroy(xo);
+    if (d_other) (void)hipFree(d_other);
+    resident_close(&r);
+    free(table); free(other); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -882,6 +1039,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.align) {
+        if (o.join || o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.resample || o.batch_dir || o.num_files != 1) { fprintf(stderr, "%s: -A takes another stream's file name and an input file name and no other mode. \n", argv[0]); return 1; }
+        return align_one(o.align_spec, o.files[0]);
+    }
     if (o.join) {
         if (o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.resample || o.batch_dir || o.num_files != 2) { fprintf(stderr, "%s: -J takes another stream's file name, an input and an output file name and no other mode. \n", argv[0]); return 1; }
         return join_one(o.join_spec, o.files[0], o.files[1]);
