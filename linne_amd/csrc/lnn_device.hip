@@ -2437,7 +2437,7 @@ static int wx_quiet_commit(LINNEAmdContext *ctx, const WxLaunch &l)
     uint64_t *ofs = (uint64_t *)l.acc + l.nmask;
     a.qwin = l.side; a.wins = l.wins; a.nwin = l.nwin; a.mask = (const unsigned long long *)l.acc; a.fail = l.fail; a.nchunks = l.nout;
     a.counts = (uint32_t *)(ofs + 2u * l.nout + 1u); a.ofs = ofs; a.back = (unsigned long long *)l.back;
-    const dim3 grid((uint32_t)(l.nout < 0x7FFFFFFFull ? l.nout : 0x7FFFFFFFull));
+    const dim3 grid((uint32_t)(l.nout < WX_MAX_TILES ? l.nout : WX_MAX_TILES));      /* (the kernels walk the chunks in steps of the grid) */
     SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_COUNT, k_wx_quiet_runs<WXQ_COUNT>, grid, dim3(WXB_THREADS), 0, ctx->stream, a);
     SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_SCAN, k_sx_scan, dim3(1), dim3(SX_SCAN_THREADS), 0, ctx->stream, (const uint32_t *)a.counts, 2u * l.nout, ofs);
     SX_LAUNCH(NULL, LINNE_AMD_QUIET_T_STARTS, k_wx_quiet_runs<WXQ_STARTS>, grid, dim3(WXB_THREADS), 0, ctx->stream, a);
@@ -2653,15 +2653,15 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     if (!pl.nlive) return LNN_OK;
     if (u.resamples) {
         wx_resample_count(rg.data(), W, pl);
-        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+        if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
     if (u.overlays) {
         wx_overlay_count(c.ov_outs, c.ov_O, pl);
-        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+        if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
     if (u.lags) {
         wx_lag_count(c.lag_in, c.lag_Q, pl);
-        if (pl.rs_tiles >= 0x7FFFFFFFull) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of lags in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+        if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of lags in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);

@@ -158,6 +158,10 @@ static_assert(sizeof(WxLagImage) == 32 && sizeof(WxLagProbe) == 80 && sizeof(WxL
 #define WXL_LAGS 256u
 #define WXL_CHUNK 65536u
 #define WXL_NOWIN 0xFFFFFFFFu
+/* the most tiles of outputs or of lags one call takes: every tile is a workgroup of 256 threads of one launch, and a launch of 2^32
+ * threads or more is not refused -- the count wraps and the tiles behind the wrap are never visited */
+#define WX_MAX_TILES 0xFFFFFFull
+static_assert(WXL_LAGS == 256u && WXR_TILE == 256u && (WX_MAX_TILES + 1u) * 256u == (1ull << 32), "WX_MAX_TILES workgroups of a tile's threads stay below 2^32 threads");
 /* a tile's partial sums among the accumulators, in 64-bit words: (lo, hi) of the dot per lag, then the chunk's sum of b^2 at the tile's
  * first lag and its sum of a^2, (lo, hi) each */
 #define WXL_PART_WORDS (2u * WXL_LAGS + 4u)

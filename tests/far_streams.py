@@ -320,6 +320,67 @@ def resample_view(pcm, first, n, up, down, before, taps):
     return pcm.slice(lo, hi - lo), first - lo // down * up
 
 
+# ---- lags: a needle's runs of PCM against dense pieces of the haystack ----
+def padded(pcm, ch, start, m):
+    """row ch of the m <= 2^24 samples from `start` on -- any Python integer -- as int64, zeros where the stream has none"""
+    start, m = int(start), int(m)
+    assert 0 <= m <= SLICE_LIMIT, "a dense window of more than 2^24 samples"
+    out = np.zeros(m, dtype=np.int64)
+    lo, hi = max(start, 0), min(start + m, pcm.total)
+    if lo < hi:
+        out[lo - start:hi - start] = pcm.slice(lo, hi - lo)[ch]
+    return out
+
+
+def far_lags(pcm_a, ca, first_a, n, pcm_b, cb, first_b, lag_first, num_lags):
+    """lag_refs.lag_sums for a needle of any length at any position: channel ca of pcm_a's [first_a, first_a + n) slid over channel cb of
+    pcm_b from first_b + lag_first on -> (dots [num_lags], b_sq [num_lags], a_sq), Python integers.  The needle's zeros add nothing: per
+    run of PCM at needle offset r, np.correlate against the haystack's dense piece [S + r, S + r + length + num_lags - 1) -- a run has
+    fewer than 2^13 samples of at most 2^23 in magnitude, asserted, so that int64 holds every sum.  b_sq at the first lag from the
+    haystack's runs over [S, S + n); from there on the square that enters less the square that leaves"""
+    first_a, n, num_lags = int(first_a), int(n), int(num_lags)
+    S = int(first_b) + int(lag_first)
+    dots, a_sq, r = [0] * num_lags, 0, 0
+    for kind, v in pcm_a.segments(first_a, n):
+        if kind == "zeros":
+            r += v
+            continue
+        x = v[ca].astype(np.int64)
+        h = padded(pcm_b, cb, S + r, x.shape[0] + num_lags - 1)
+        assert x.shape[0] < 1 << 13 and int(np.abs(x).max()) <= 1 << 23 and int(np.abs(h).max()) <= 1 << 23
+        dots = [d + int(c) for d, c in zip(dots, np.correlate(h, x, mode="valid"))]
+        a_sq += exact_dot(x, x)
+        r += x.shape[0]
+    assert r == n
+    lo, hi = max(S, 0), min(S + n, pcm_b.total)
+    first = 0
+    if lo < hi:
+        for kind, v in pcm_b.segments(lo, hi - lo):
+            if kind == "pcm":
+                first += exact_dot(v[cb], v[cb])
+    b_sq = [first]
+    if num_lags > 1:
+        leave, enter = padded(pcm_b, cb, S, num_lags - 1), padded(pcm_b, cb, S + n, num_lags - 1)
+        for e, l in zip((enter * enter).tolist(), (leave * leave).tolist()):
+            b_sq.append(b_sq[-1] + e - l)
+    assert min(b_sq) >= 0
+    return dots, b_sq, a_sq
+
+
+def far_lag_table(pcm_a, first_a, n, pcm_b, first_b, lag_first, num_lags, pairs):
+    """lag_refs.expected_lags from far_lags: (lag_refs.table_of's table (P, num_lags), a_sq as uint64 (P, 2): low word, high word)"""
+    import linne_amd
+    once = {pair: far_lags(pcm_a, pair[0], first_a, n, pcm_b, pair[1], first_b, lag_first, num_lags) for pair in set(pairs)}
+    t = np.zeros((len(pairs), num_lags), dtype=linne_amd.LAG_DTYPE)
+    a_sq = np.zeros((len(pairs), 2), dtype=np.uint64)
+    word = lambda vals, shift: np.array([(v >> shift) & MASK64 for v in vals], dtype=np.uint64)    # (two's complement: Python's >> and & do it)
+    for p, pair in enumerate(pairs):
+        dots, b_sq, e = once[tuple(pair)]
+        t["dot_lo"][p], t["dot_hi"][p], t["b_sq_lo"][p], t["b_sq_hi"][p] = word(dots, 0), word(dots, 64).view(np.int64), word(b_sq, 0), word(b_sq, 64)
+        a_sq[p] = (e & MASK64, e >> 64)
+    return t, a_sq
+
+
 # ---- the streams of the far tests ----
 ISLAND = ((1024, COMPRESS), (777, COMPRESS), (300, RAW), (33, COMPRESS), (1024, COMPRESS))
 ISLAND_SAMPLES = sum(n for n, _ in ISLAND)

@@ -1,6 +1,7 @@
 """The reference of the lag tests (include/linne_amd.h LINNEAmd_LagWindowsDevice): the sliding sums of a needle over a haystack that is
 zero outside its stream, from decoded PCM alone.  np.correlate on int64 where n * 2^(2 * bits - 2) fits int64 -- bits the width the
-values really have --, Python integers otherwise."""
+values really have --; otherwise Python integers for short needles and, for long ones, numpy on 16-bit limbs put together in Python
+integers (limb_sums), which tests/test_stream_lags_cpu.py holds to the Python integers."""
 import numpy as np
 
 import linne_amd
@@ -33,6 +34,8 @@ def lag_sums(a, first_a, n, b, first_b, lag_first, num_lags):
         cs = np.concatenate(([0], np.cumsum(h * h)))
         b_sq = [int(cs[l + n] - cs[l]) for l in range(num_lags)]
         return dots, b_sq, int(np.dot(x, x))
+    if n > 4096:
+        return limb_sums(x, h, n, num_lags)
     xs, hs = [int(v) for v in x], [int(v) for v in h]
     dots = [sum(p * q for p, q in zip(xs, hs[l:l + n])) for l in range(num_lags)]
     sq = [v * v for v in hs]
@@ -40,6 +43,19 @@ def lag_sums(a, first_a, n, b, first_b, lag_first, num_lags):
     for l in range(1, num_lags):
         b_sq.append(b_sq[-1] + sq[l - 1 + n] - sq[l - 1])
     return dots, b_sq, sum(v * v for v in xs)
+
+
+def limb_sums(x, h, n, num_lags):
+    """lag_sums for int32 values of any width and long needles, exact: every value is v1 * 2^16 + v0 with 0 <= v0 < 2^16 and
+    |v1| <= 2^15, a product of two limbs lies below 2^32, and np.correlate's int64 holds n < 2^31 of them; the four limb correlations
+    are put together in Python integers.  The squares are Python integers"""
+    assert n < 1 << 31 and int(np.abs(x).max()) <= 1 << 31 and int(np.abs(h).max()) <= 1 << 31
+    x0, x1, h0, h1 = x & 0xFFFF, x >> 16, h & 0xFFFF, h >> 16
+    c = [[np.correlate(p, q, mode="valid") for q in (x0, x1)] for p in (h0, h1)]
+    dots = [(int(hh) << 32) + ((int(hl) + int(lh)) << 16) + int(ll) for ll, lh, hl, hh in zip(c[0][0], c[0][1], c[1][0], c[1][1])]
+    sq = h.astype(object) ** 2
+    cs = np.concatenate(([0], np.cumsum(sq)))
+    return dots, [int(cs[l + n] - cs[l]) for l in range(num_lags)], int((x.astype(object) ** 2).sum())
 
 
 def expected_lags(full_a, first_a, n, full_b, first_b, lag_first, num_lags, pairs):

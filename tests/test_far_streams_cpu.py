@@ -107,6 +107,45 @@ def test_resample_view_is_the_window_of_the_whole(reduced, name):
             assert view.shape[1] <= taps + n * down // up + 2 * down + 2
 
 
+def lag_cases(reduced):
+    """(needle stream, first_a, n, haystack stream, first_b, lag_first, num_lags, pairs).  lag_refs.lag_sums is numpy while n * 2^(2 bits - 2)
+    fits int64: needles of more than 2^17 samples go with the 16-bit stream alone"""
+    d16, d24 = reduced["far16"][1], reduced["far24"][1]
+    (a, _, _, pa), (b, _, _, pb) = d16.islands
+    la, T = pa.shape[1], d16.total
+    assert d24.total == T and [s for s, _, _, _ in d24.islands] == [a, b]
+    both = b + la + 100 - (a - 50)
+    return [("far16", a - 100, la + 300, "far16", a - 100, -300, 601, [(0, 0), (1, 1), (0, 1)]),          # a needle over an island, against itself
+            ("far24", a - 7, la + 20, "far16", b, -100, 400, [(0, 1), (2, 0)]),                           # ... over the other stream's other island
+            ("far16", a + 100, 2000, "far24", a, 0, 300, [(1, 2)]),                                       # a needle of PCM alone
+            ("far16", a - 50, both, "far16", a - 50, -40, 81, [(0, 1), (1, 0)]),                          # a needle holding two islands
+            ("far16", 0, T, "far16", 0, -30, 61, [(1, 1)]),                                               # a haystack range off both ends
+            ("far24", b - 50, 5000, "far24", b, 0, 20000, [(2, 1)]),                                      # ... off the end, lags in the thousands
+            ("far16", a, la, "far24", a, -a - 100, 300, [(0, 0)]),                                        # ... that starts at -100
+            ("far16", a, la, "far24", T + 5, -(T + 5 - a) + 17, 200, [(0, 2), (1, 1)]),                    # first_b beyond the stream, the range inside it
+            ("far16", a, la, "far24", (1 << 64) - 1, 5, 9, [(0, 0)]),                                     # a range that misses the stream
+            ("far16", a, la, "far24", 0, -(1 << 63), 9, [(0, 0)]),
+            ("far24", T - 40, 40, "far16", b + la - 10, -20, 50, [(0, 0)]), ("far24", T - 1, 1, "far24", a, 0, la, [(1, 1)]),
+            ("far16", b + la - 1, 1, "far24", a, 0, la, [(1, 1)]), ("far24", a + 5, 1, "far16", a, -3, 1, [(2, 0)])]
+
+
+def test_far_lags_equal_the_dense_reference(reduced):
+    """far_streams.far_lags and far_lag_table against lag_refs.lag_sums and expected_lags on the oracle's whole decode"""
+    from lag_refs import expected_lags, lag_sums
+    nonzero = 0
+    for key in lag_cases(reduced):
+        na, first_a, n, nb, first_b, lag_first, num_lags, pairs = key
+        (_, da, fa), (_, db, fb) = reduced[na], reduced[nb]
+        for ca, cb in pairs:
+            got = fs.far_lags(da.pcm, ca, first_a, n, db.pcm, cb, first_b, lag_first, num_lags)
+            assert got == lag_sums(fa[ca], first_a, n, fb[cb], first_b, lag_first, num_lags), key[:7] + (ca, cb)
+            nonzero += any(got[0])
+        table, a_sq = fs.far_lag_table(da.pcm, first_a, n, db.pcm, first_b, lag_first, num_lags, pairs)
+        want, want_sq = expected_lags(fa, first_a, n, fb, first_b, lag_first, num_lags, pairs)
+        assert table.dtype == want.dtype and table.tobytes() == want.tobytes() and a_sq.dtype == want_sq.dtype and np.array_equal(a_sq, want_sq), key
+    assert nonzero >= 12
+
+
 def test_crc32_zeros_against_zlib():
     starts = (0, 1, 0xFFFFFFFF, 0xDEADBEEF, zlib.crc32(b"far streams"))
     for n in (0, 1, 255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 24) + 1):

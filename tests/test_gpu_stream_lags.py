@@ -2,18 +2,20 @@
 LINNEAmd_LagWindowsDevice).  Every element of every table is computed with numpy int64 or Python integers (lag_refs.expected_lags) from
 the oracle's decode of the same bytes, never from the library under test, and everything must be equal: integers, no tolerance.  The
 tables of a call lie in one buffer of sentinels, which must come back untouched around them.  Streams hold 3 blocks of 1024 samples and
-a tail, or 21 blocks of 33; one mono stream holds 65537 + 300 samples for the needles at the chunk's edge."""
+a tail, or 21 blocks of 33; one mono stream holds 65537 + 300 samples for the needles at the chunk's edge, and one of 24-bit RAW blocks
+written by hand holds 66 blocks of full-scale values.  Where a test is about which of the kernel's two summing paths a sub-tile takes,
+it works that out from the reference's data under the kernel's staging rule (sub_tiles) and asserts its premise."""
 import numpy as np
 import pytest
 
 import linne_amd
 import synth_records as sr
-from lag_refs import expected_lags
+from lag_refs import expected_lags, haystack
 from relate_refs import CARRY_NS, CARRY_PEAK, carry_stereo_stream
 from signals import music
 import stream_consumers as sc
 from stream_consumers import KIND, Stream, encoded, last_error
-from stream_refs import mixed_signal
+from stream_refs import crc16, mixed_signal
 from test_stream_lags_cpu import BAD
 from test_stream_relate_cpu import WIDE_SHAPE, wide_cases
 
@@ -169,6 +171,132 @@ def test_wide_values(ctx, oracle):
         check(ctx, [probe(w, 20, n, w, 20, -20, 41, [(0, 0), (0, 1), (1, 0)]), probe(w, 0, 300, w, 0, 0, 1, [(1, 1)])])
     finally:
         w.index.close()
+
+
+# ---- the two summing paths: sub-tiles within +-2^23 in one int64, the others in (lo, hi) ----
+CHUNK, SUB, LAGS, NARROW = 65536, 1024, 256, 1 << 23
+
+
+def is_wide(v):
+    """the kernel's rule (lnn_k_lags.h wxl_wide): -2^23 and 2^23 are narrow, -2^23 - 1 and 2^23 + 1 are wide"""
+    return (v < -NARROW) | (v > NARROW)
+
+
+def sub_tiles(x, h, l0, chunk):
+    """what tile (chunk, l0) stages, from the reference's data: x the needle's samples, h = lag_refs.haystack(...), which is zero where the
+    haystack's image has no word -> per sub-tile (its 1024 or fewer needle words, the 1279 haystack words under them at the tile's 256
+    lags, whether one of them is wide)"""
+    i0 = chunk * CHUNK
+    length = min(x.shape[0] - i0, CHUNK)
+    out = []
+    for s0 in range(0, length, SUB):
+        a = x[i0 + s0:i0 + min(s0 + SUB, length)]
+        b = np.zeros(SUB + LAGS - 1, dtype=np.int64)
+        piece = h[l0 + i0 + s0:l0 + i0 + s0 + SUB + LAGS - 1]
+        b[:piece.shape[0]] = piece
+        out.append((a, b, bool(is_wide(a).any() or is_wide(b).any())))
+    return out
+
+
+def raw24_stream(oracle, x):
+    """x (2, a multiple of 1024 samples) as a 24-bit stream of RAW blocks, written as relate_refs.carry_stereo_stream writes its one: header
+    and block heads from the oracle's encode of as many zeros; a RAW block holds its samples zig-zagged, three bytes each, big-endian,
+    frame by frame"""
+    assert x.shape[0] == 2 and x.shape[1] % S == 0 and np.abs(x.astype(np.int64) * 2 + 1).max() < 1 << 24
+    quiet = bytes(oracle.encode_whole(np.zeros_like(x), 24, 44100, S, 0, False))
+    out = bytearray(quiet[:30])
+    for at in range(0, x.shape[1], S):
+        v = x[:, at:at + S].T.reshape(-1).astype(np.int64)
+        zz = np.where(v >= 0, 2 * v, -2 * v - 1)
+        body = bytes([2]) + S.to_bytes(2, "big") + b"".join(int(u).to_bytes(3, "big") for u in zz)
+        out += quiet[30:32] + (len(body) + 2).to_bytes(4, "big") + crc16(body).to_bytes(2, "big") + body
+    return bytes(out)
+
+
+@pytest.fixture(scope="module")
+def wide(ctx, oracle):
+    w = Stream(ctx, oracle, sr.case_stream(WIDE_SHAPE, wide_cases()), "wide values")
+    yield w
+    w.index.close()
+
+
+@pytest.fixture(scope="module")
+def full24(ctx, oracle):
+    """66 RAW blocks of 24 bits: L alternates between -2^23 and 2^23 - 1, R is -2^23 throughout -- all of it narrow, by one"""
+    n = 66 * S
+    x = np.empty((2, n), dtype=np.int32)
+    x[0, 0::2], x[0, 1::2], x[1] = -NARROW, NARROW - 1, -NARROW
+    t = Stream(ctx, oracle, raw24_stream(oracle, x), "66 RAW blocks of 24 bits")
+    assert np.array_equal(t.full, x) and not is_wide(t.full.astype(np.int64)).any()
+    yield t
+    t.index.close()
+
+
+def test_wide_values_among_narrow_in_one_tile(ctx, long_mono, wide):
+    """a 16-bit needle of 65537 samples (2 chunks) over the wide-value stream, 600 lags (3 lag tiles): tile (chunk 0, l0 256) sums some of
+    its sub-tiles in one int64 and some in (lo, hi), and the int64 part, which the tile's end merges into (lo, hi) with its sign, is
+    negative at some lag.  Probe 0 has the wide stream under needle samples 28000 to 34000, so no square enters or leaves its b^2: probe
+    1 has it under the needle's first samples, where wide squares leave at every lag of the second and third lag tile.  Probe 2: the
+    wide stream as the needle"""
+    m, w, L, n = long_mono, wide, 600, 65537
+    assert w.ns == 6115 and m.ns >= n and not is_wide(m.full.astype(np.int64)).any()
+    x = m.full[0, :n].astype(np.int64)
+    for S0, squares in ((-28300, False), (800, True)):
+        for cb in (0, 1):
+            h = haystack(w.full[cb], S0, 0, L, n)
+            tiles = sub_tiles(x, h, 256, 0)
+            kinds = [wd for _, _, wd in tiles]
+            assert len(tiles) == 64 and any(kinds) and not all(kinds), (S0, cb)
+            share = sum(np.correlate(b[:a.shape[0] + LAGS - 1], a, mode="valid") for a, b, wd in tiles if not wd)
+            assert share.shape == (LAGS,) and share.min() < 0, (S0, cb)
+            for l0 in (256, 512):
+                lanes = np.arange(1, min(LAGS, L - l0))
+                leave, enter = h[l0 + lanes - 1], h[l0 + lanes - 1 + n]
+                assert (max(int((leave * leave).max()), int((enter * enter).max())) > 1 << 48) == squares, (S0, cb, l0)
+    check(ctx, [probe(m, 0, n, w, 0, -28300, L, [(0, 0), (0, 1)]), probe(m, 0, n, w, 800, 0, L, [(0, 0), (0, 1)]),
+                probe(w, 0, w.ns, m, 1000, -300, L, [(0, 0), (1, 0)])])
+
+
+def test_wide_values_across_chunks(ctx, wide, full24):
+    """a full-scale 24-bit needle of 66 blocks (2 chunks) over the wide-value stream, 300 lags (2 lag tiles): the wide values under chunk 0,
+    under both chunks and under chunk 1 alone, so that the commit adds (lo, hi) parts of both kinds with carries; and the narrow path at
+    its documented worst case, 65536 products of 2^46 in one int64: R against R is 2^62 per chunk, L against L nearly, at lags -1 .. 1"""
+    r, w, L = full24, wide, 300
+    n = r.ns
+    assert n == CHUNK + 2 * S
+    x = r.full[0].astype(np.int64)
+    met = []
+    for S0 in (-20000, -64000, -66000):
+        h = haystack(w.full[0], S0, 0, L, n)
+        met.append([any(wd for _, _, wd in sub_tiles(x, h, l0, c)) for c in (0, 1) for l0 in (0, 256)])
+    assert met == [[True, True, False, False], [True, True, True, True], [False, False, True, True]]
+    edge = CHUNK + S
+    y = r.full[1, :edge].astype(np.int64)
+    assert int(np.dot(y[:CHUNK], y[:CHUNK])) == 1 << 62 and (y == -NARROW).all()           # a chunk's share: all that one int64 is documented to hold
+    assert -(1 << 62) < int(np.dot(x[:CHUNK], x[1:CHUNK + 1])) < -(1 << 62) + (1 << 41)
+    check(ctx, [probe(r, 0, n, w, 0, S0, L, [(0, 0), (1, 1), (0, 1)]) for S0 in (-20000, -64000, -66000)] +
+               [probe(r, 0, edge, r, 0, -1, 3, [(0, 0), (0, 1), (1, 1)])])
+
+
+def test_boundary_of_the_narrow_rule(ctx, wide, full24):
+    """-2^23, the least a 24-bit RAW block holds, is narrow; the wide-value stream's channel 0 grows through 2^23 between samples 1034 and
+    1035, and its wide value of smallest magnitude is sample 2417, among wide neighbours.  A needle of 16 samples of -2^23 against
+    haystack ranges that end just before and just behind each of the two: by the rule the first range is summed in one int64 and the
+    other three in (lo, hi); the reference decides all four"""
+    r, w = full24, wide
+    v = w.full.astype(np.int64)
+    beyond = np.where(is_wide(v), np.abs(v), 1 << 40)
+    ch, at = np.unravel_index(np.argmin(beyond), beyond.shape)
+    assert is_wide(v).any() and (int(ch), int(at), int(v[ch, at])) == (0, 2417, -8391482) and NARROW < 8391482 < NARROW + 3000
+    assert int(v[0, 1034]) == 8212517 <= NARROW < int(v[0, 1035]) == 8816126 and not is_wide(v[0, :1035]).any()
+    needle = r.full[1, :16].astype(np.int64)
+    assert (needle == -NARROW).all() and not is_wide(needle).any() and is_wide(needle - 1).all() and not is_wide(-needle).any() and is_wide(1 - needle).all()
+    ranges = [(1000, 20), (1000, 21), (2400, 2), (2400, 3)]           # (first_b, num_lags): the range ends at first_b + 16 + num_lags - 1
+    assert [first + 16 + lags - 1 for first, lags in ranges] == [1035, 1036, 2417, 2418]
+    paths = [sub_tiles(needle, haystack(v[0], first, 0, lags, 16), 0, 0) for first, lags in ranges]
+    assert [[wd for _, _, wd in p] for p in paths] == [[False], [True], [True], [True]]
+    assert int(paths[0][0][1].max()) == 8212517                  # (the narrow range's largest value lies 2 % below the bound)
+    check(ctx, [probe(r, 0, 16, w, first, 0, lags, [(1, 0), (0, 0)]) for first, lags in ranges])
 
 
 # ---- the call ----

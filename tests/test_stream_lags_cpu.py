@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import linne_amd
-from lag_refs import expected_lags, haystack, lag_sums, table_of
+from lag_refs import expected_lags, haystack, lag_sums, limb_sums, table_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "linne_amd", "csrc")
@@ -47,6 +47,11 @@ def test_the_reference_against_hand_written_values():
     fast = lag_sums(x, 3, 30, y, 5, -20, 60)
     xs, hs = [int(q) for q in x[3:33]], [int(q) for q in haystack(y, 5, -20, 60, 30)]
     assert fast[0] == [sum(p * q for p, q in zip(xs, hs[l:l + 30])) for l in range(60)] and fast[1] == [sum(q * q for q in hs[l:l + 30]) for l in range(60)]
+    # ... and the third, on limbs, for long needles of values over all of int32: the extremes of both signs among them
+    x, y = rng.integers(-1 << 31, 1 << 31, 70), rng.integers(-1 << 31, 1 << 31, 90)
+    x[:4], y[5:9] = [-(1 << 31), (1 << 31) - 1, -1, 65536], [(1 << 31) - 1, -(1 << 31), -65536, -1]
+    slow = lag_sums(x, 3, 60, y, 5, -20, 80)
+    assert slow == limb_sums(x[3:63], haystack(y, 5, -20, 80, 60), 60, 80) and max(abs(v) for v in slow[0]) > 1 << 64
 
 
 # ---- the boundary --------------------------------------------------------------------------------------------------------------
@@ -215,8 +220,9 @@ PROGRAM = r"""
 /* stdin: group_frames nblocks S N nprobes, then per probe: checked first_a n hay_lo hay_n b0 nlags npair live_a live_b (hay_n 0: the
  * range misses the stream and there is no haystack window).  One stream of two channels, nblocks SILENT blocks of S samples, N samples
  * in its header.  Out come the counts, the window records, the image records of all windows, the probe records, the tiles and the runs
- * -- and whether the same ranges planned for the placing call give the same block records, byte for byte */
-int main(void)
+ * -- and whether the same ranges planned for the placing call give the same block records, byte for byte.  With the argument `count`:
+ * the counts of wx_lag_count alone, no list is written */
+int main(int argc, char **argv)
 {
     unsigned gf, nb, S, nq; unsigned long long N;
     if (scanf("%u %u %u %llu %u", &gf, &nb, &S, &N, &nq) != 5) return 2;
@@ -248,6 +254,10 @@ int main(void)
     WxPlanned p;
     if (wx_plan_count(rg.data(), W, gf, p) != WXP_OK) return 3;
     wx_lag_count(in.data(), nq, p);
+    if (argc > 1 && strcmp(argv[1], "count") == 0) {           /* the counts alone: what the call's guard reads, and the guard's bound */
+        printf("count %llu %llu %llu %llu\n", (unsigned long long)p.rs_tiles, (unsigned long long)p.lg_runs, (unsigned long long)p.lg_probes, (unsigned long long)WX_MAX_TILES);
+        return 0;
+    }
     /* exactly the reserved sizes, from the heap: the sanitizer build sees a record written past them */
     std::vector<WxWindow> win(p.nlive); std::vector<WxBlock> rec(p.total_rec); std::vector<uint32_t> crec(p.total_crec);
     std::vector<WxLagTile> tile(p.rs_tiles); std::vector<uint32_t> run(p.lg_runs); std::vector<WxLagProbe> prec(p.lg_probes); std::vector<WxLagImage> img(W);
@@ -354,3 +364,18 @@ def test_plan_images_probes_tiles_and_runs(programs, gf):
     assert plain == o_tile and o_run >= o_tile + 16 * len(tiles) and o_probe >= o_run + 4 * len(runs) and o_img >= o_probe + 80 * len(probes) and total >= o_img + 32 * W
     assert o_run % 256 == 0 and o_probe % 256 == 0 and o_img % 256 == 0 and total % 256 == 0
     assert take("same") == [[1]]                                    # the older kinds' records: unchanged byte for byte
+
+
+def test_tiles_of_whole_stream_probes_reach_the_launch_bound(programs):
+    """wx_lag_count over probes of 2^32 - 1 needle samples, 1 lag and 8 pairs, 2^35 products each: 32 of them are 2^24 tiles, one more
+    than WX_MAX_TILES, the most workgroups of 256 threads whose launch stays below 2^32 threads; 31 stay below"""
+    n = (1 << 32) - 1
+    counts = {}
+    for nq in (31, 32):
+        text = "0 1 8192 %d %d\n" % (n, nq) + "1 0 %d 0 %d 0 1 8 1 1\n" % (n, n) * nq
+        outs = [subprocess.run([exe, "count"], input=text, capture_output=True, text=True) for exe in programs]
+        assert all(r.returncode == 0 for r in outs) and outs[0].stdout == outs[1].stdout, [r.stderr for r in outs]
+        word, tiles, runs, probes, most = outs[0].stdout.split()
+        assert word == "count" and (int(runs), int(probes), int(most)) == (8 * nq, nq, 0xFFFFFF)
+        counts[nq] = int(tiles)
+    assert counts == {31: 31 * 8 * 65536, 32: 1 << 24} and counts[31] <= 0xFFFFFF < counts[32] and (0xFFFFFF + 1) * 256 == 1 << 32
