@@ -435,6 +435,12 @@ enum LINNEAmdLagsTimingKind {
     LINNE_AMD_LAGS_T_LAGS = 102,            /* the sliding products of every tile (probe, pair, 256 lags, a chunk of the needle) into its partial sums, once, behind the last pass (k_wx_lags) */
     LINNE_AMD_LAGS_T_COMMIT = 103           /* the partial sums added per lag and the tables of the probes that did not fail written, once, behind kind 102 (k_wx_lags_commit) */
 };
+/* projecting frames of windows (LINNEAmd_ProjectWindowsDevice: the kinds of LINNEAmd_DecodeWindowsDevice -- its kind 59 places the windows'
+ * input samples into the call's scratch --, and one launch each of kinds 104 and 105 per call that takes a pass) */
+enum LINNEAmdProjectTimingKind {
+    LINNE_AMD_PROJECT_T_PRESET = 104,       /* the call's input images zeroed and its basis tables cut into digit planes, once, in front of the first pass (k_wx_project_preset) */
+    LINNE_AMD_PROJECT_T_PROJECT = 105       /* the frames of the windows that did not fail projected from their input images, once, behind the last pass (k_wx_project) */
+};
 double LINNEAmd_GetLastTimingMs(struct LINNEAmdContext *ctx, int which);
 int LINNEAmd_GetLastTimingLaunches(struct LINNEAmdContext *ctx, int which);
 /* The grid form of the last k_search_long launch (kind 25) of the most recent encode call: 0 a block per (job, tile), 1 one block
@@ -1097,6 +1103,67 @@ struct LINNEAmdLagProbe {
     int32_t result;                     /* out */
 };
 int LINNEAmd_LagWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdLagProbe *probes, uint32_t num_probes, uint32_t group_frames);
+
+/* ---- projecting frames of windows of resident streams on int16 basis rows: an exact STFT, a filter bank, a band-energy front end ----
+ * LINNEAmd_ProjectWindowsDevice cuts a stream into overlapping frames of N = frame_len samples, H = hop samples apart, and writes every
+ * frame's inner product with each of K = num_rows rows of an int16 basis: a frames x rows table per channel.  A window's first_sample
+ * and num_samples count output FRAMES of its stream, which has LINNEAmd_ProjectLength(N_s, H) = ceil(N_s / H) of them, N_s the header's
+ * num_samples (this is how LINNEAmd_ResampleWindowsDevice counts outputs); d_pcm is the output's base, an int32_t* or a float*, and
+ * pcm_stride is ignored.  With x[c][i] the values LINNEAmd_DecodeStreamDevice gives for channel c, sample i of the stream, and x = 0 for
+ * i < 0 and i >= N_s, element (c, f, k) -- channel c, frame f of the stream, row k -- is
+ *   1. the sum    acc = sum over n < N of (int64)basis[k * N + n] * x[c][f * H - before + n], the index arithmetic in 64 bits   (a
+ *                 product is at most 2^46 in magnitude, 4096 of them 2^58: nothing wraps);
+ *   2. the shift  y = shift ? (acc + (1 << (shift - 1))) >> shift : acc, the shift arithmetic: halves round towards plus infinity;
+ *   3. the clip   y clipped to [-2^(B - 1), 2^(B - 1) - 1], B = clip_bits, or 32 where clip_bits is 0
+ *                 (steps 2 and 3 of LINNEAmd_MixWindowsDevice, word for word);
+ *   4. the store  LINNE_AMD_PCM_S32 stores y; LINNE_AMD_PCM_F32 stores (float)y, rounded to nearest-even, times 2^-float_exp, which is
+ *                 exact scaling;
+ * at d_pcm[c * channel_stride + (f - first_sample) * frame_stride + k * row_stride], in elements.  specs[i].saturated is 1 when step 3
+ * changed an element of window i, otherwise 0; a failing window's stays as it was.
+ * For window i alone INVALID_ARGUMENT ("window <i>: ProjectWindowsDevice: ...") when frame_len, hop or num_rows is outside 1 .. its
+ * LINNE_AMD_PROJECT_MAX_*, before > frame_len - 1, shift > 31, clip_bits is 1 or above 32, format is neither S32 nor F32, float_exp > 63
+ * or nonzero with S32, reserved is not 0, basis is NULL, d_pcm is NULL or not 4-byte aligned, frames * K * N * C (formed in 128 bits) is
+ * above LINNE_AMD_PROJECT_MAX_PRODUCTS, or the output map is not injective: with the three (stride, extent) pairs -- extents C,
+ * num_samples and K -- sorted by stride and pairs of extent 1 left out, the smallest stride must be at least 1 and each later one at
+ * least the one before it times that one's extent.  These come in front of the range check, which uses LINNEAmd_ProjectLength; the
+ * index's failing block fails a window when it lies at or before the last INPUT sample the window reads,
+ * min(N_s - 1, (first_sample + num_samples - 1) * H - before + N - 1).  Halo samples off either end of the stream are zeros, not errors.
+ * The rest of the contract is LINNEAmd_DecodeWindowsDeviceLayout's: per-window results, a failing window's memory never written and the
+ * others undisturbed, the lowest failing window's code returned, shape groups, passes, group_frames (which never changes a byte), the
+ * one host synchronisation and whole-call failures.  Windows with different specs and stream shapes may share a call; windows that name
+ * the same (basis, K, N) share one device copy of the table, which is read during the call only.
+ * Scratch: beside a pass's, the call keeps an int32 planar image of every live window's input range, halo included -- 4 * C * (span
+ * rounded up to 4) bytes, span = (num_samples - 1) * H + N -- and its tables as digit planes (2 * (K rounded up to 16) * (N rounded up
+ * to 64) bytes each) in the context's scratch; where that cannot be had the whole call fails with NG and nothing is written.  A pass has
+ * the decode call's launches (its kind 59 writes the images); a call that takes a pass adds one launch of kind 104 in front of the
+ * first pass and one of kind 105 behind the last, whatever the numbers of windows, frames, rows and taps are.  num_windows == 0 is OK; a
+ * NULL ctx, or NULL windows or NULL specs with num_windows > 0, INVALID_ARGUMENT.  Enqueued on the context's stream and synchronous. */
+#define LINNE_AMD_PROJECT_MAX_FRAME   4096u                   /* N */
+#define LINNE_AMD_PROJECT_MAX_ROWS    2048u                   /* K */
+#define LINNE_AMD_PROJECT_MAX_HOP     65536u                  /* H */
+#define LINNE_AMD_PROJECT_MAX_PRODUCTS ((uint64_t)1 << 40)    /* frames * K * N * C of one window */
+struct LINNEAmdProjectSpec {
+    uint32_t frame_len, hop, num_rows;  /* N, H, K */
+    uint32_t before;                    /* 0 .. N - 1: samples a frame reaches back from f * H */
+    uint32_t shift, clip_bits;          /* as in struct LINNEAmdMixSpec */
+    uint32_t format;                    /* LINNE_AMD_PCM_S32 or LINNE_AMD_PCM_F32 only */
+    uint32_t float_exp;                 /* 0 .. 63: F32 = (float)y * 2^-float_exp */
+    uint64_t channel_stride, frame_stride, row_stride;   /* elements: (c, f, k) -> d_pcm[c*cs + (f - first)*fs + k*rs] */
+    uint32_t saturated;                 /* out */
+    uint32_t reserved;                  /* 0 */
+    const int16_t *basis;               /* HOST memory, [K][N] */
+};
+int LINNEAmd_ProjectWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows,
+        struct LINNEAmdProjectSpec *specs /* [num_windows], in/out */, uint32_t num_windows, uint32_t group_frames);
+/* ceil(num_samples / hop), 0 where hop is 0 */
+uint64_t LINNEAmd_ProjectLength(uint64_t num_samples, uint32_t hop);
+/* A DFT basis for the call above: row 2 j is round_half_even(32767 * w[n] * cos(2 pi j n / N)), row 2 j + 1 is
+ * round_half_even(-32767 * w[n] * sin(2 pi j n / N)), j < bins, n < N = frame_len; window 0: w = 1 (rectangular), 1: the periodic Hann
+ * window w[n] = 0.5 - 0.5 cos(2 pi n / N).  Needs 1 <= frame_len <= LINNE_AMD_PROJECT_MAX_FRAME, 1 <= bins <= N / 2 + 1,
+ * 2 * bins <= LINNE_AMD_PROJECT_MAX_ROWS and window 0 or 1; INVALID_ARGUMENT otherwise, and for a NULL pointer.  Pure host code: no
+ * device is needed. */
+int LINNEAmd_ProjectDesign(uint32_t frame_len, uint32_t bins, uint32_t window /* 0 rectangular, 1 periodic Hann */,
+        int16_t *basis /* [2*bins][frame_len] */);
 
 /* ---- cutting and joining resident streams, re-encoding only the blocks a cut goes through ----
  * LINNEAmd_SpliceStreamsDevice writes num_splices output streams, each made of the cuts of indexed streams it names.  The decoder

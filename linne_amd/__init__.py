@@ -65,6 +65,7 @@ AMD_SYMBOLS = [
     "LINNEAmd_ResampleWindowsDevice", "LINNEAmd_ResampleLength", "LINNEAmd_ResampleDesign",
     "LINNEAmd_OverlayWindowsDevice",
     "LINNEAmd_LagWindowsDevice",
+    "LINNEAmd_ProjectWindowsDevice", "LINNEAmd_ProjectLength", "LINNEAmd_ProjectDesign",
 ]
 PCM_S32, PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2, 3          # include/linne_amd.h LINNE_AMD_PCM_*
 
@@ -318,6 +319,41 @@ def resample_design(up, down, taps=32):
     if ret != 0:
         raise ValueError(f"resample_design({up}, {down}, {taps}) -> {ret}: up and down are 1 .. {RESAMPLE_MAX_RATIO}, taps 1 .. {RESAMPLE_MAX_TAPS}, up * taps <= {RESAMPLE_MAX_COEFS}")
     return coef, int(shift.value), int(before.value)
+
+
+class ProjectSpec(C.Structure):
+    """struct LINNEAmdProjectSpec (include/linne_amd.h); basis is host memory"""
+    _fields_ = [("frame_len", C.c_uint32), ("hop", C.c_uint32), ("num_rows", C.c_uint32), ("before", C.c_uint32), ("shift", C.c_uint32),
+                ("clip_bits", C.c_uint32), ("format", C.c_uint32), ("float_exp", C.c_uint32), ("channel_stride", C.c_uint64),
+                ("frame_stride", C.c_uint64), ("row_stride", C.c_uint64), ("saturated", C.c_uint32), ("reserved", C.c_uint32),
+                ("basis", C.POINTER(C.c_int16))]
+
+
+PROJECT_MAX_FRAME, PROJECT_MAX_ROWS, PROJECT_MAX_HOP, PROJECT_MAX_PRODUCTS = 4096, 2048, 65536, 1 << 40     # include/linne_amd.h LINNE_AMD_PROJECT_MAX_*
+PROJECT_WINDOWS = {"rect": 0, "rectangular": 0, "hann": 1}
+
+
+def project_length(num_samples, hop):
+    """LINNEAmd_ProjectLength: the frames of a stream of num_samples samples, ceil(num_samples / hop)"""
+    return int(lib.LINNEAmd_ProjectLength(int(num_samples), int(hop)))
+
+
+def project_design(n_fft, bins=None, window="hann"):
+    """LINNEAmd_ProjectDesign -> the DFT basis as int16 (2 * bins, n_fft): row 2 j the cosine of bin j, row 2 j + 1 its negated sine,
+    under the periodic Hann window or none ("rect"), scaled by 32767.  bins None: n_fft // 2 + 1.  ValueError for arguments outside the
+    call's bounds.  Pure host code: no device is needed"""
+    n_fft = int(n_fft)
+    bins = n_fft // 2 + 1 if bins is None else int(bins)
+    if window not in PROJECT_WINDOWS:
+        raise ValueError(f"window is one of {sorted(PROJECT_WINDOWS)}")
+    if not (0 <= n_fft < 1 << 32 and 0 <= bins < 1 << 32):
+        raise ValueError("n_fft and bins are unsigned")
+    fits = 1 <= n_fft <= PROJECT_MAX_FRAME and 2 * bins <= PROJECT_MAX_ROWS
+    basis = np.zeros((2 * max(bins, 1), n_fft) if fits else (1, 1), dtype=np.int16)
+    ret = lib.LINNEAmd_ProjectDesign(n_fft, bins, PROJECT_WINDOWS[window], basis.ctypes.data_as(C.POINTER(C.c_int16)))
+    if ret != 0:
+        raise ValueError(f"project_design({n_fft}, {bins}) -> {ret}: n_fft is 1 .. {PROJECT_MAX_FRAME}, bins 1 .. n_fft // 2 + 1, 2 * bins <= {PROJECT_MAX_ROWS}")
+    return basis
 
 
 class OverlaySource(C.Structure):
@@ -712,6 +748,10 @@ def _load():
     L.LINNEAmd_ResampleLength.restype = C.c_uint64
     L.LINNEAmd_ResampleLength.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
     L.LINNEAmd_ResampleDesign.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.LINNEAmd_ProjectWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Window), C.POINTER(ProjectSpec), C.c_uint32, C.c_uint32]
+    L.LINNEAmd_ProjectLength.restype = C.c_uint64
+    L.LINNEAmd_ProjectLength.argtypes = [C.c_uint64, C.c_uint32]
+    L.LINNEAmd_ProjectDesign.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int16)]
     L.LINNEAmd_OverlayWindowsDevice.argtypes = [C.c_void_p, C.POINTER(Overlay), C.POINTER(PcmLayout), C.c_uint32, C.c_uint32]
     L.LINNEAmd_LagWindowsDevice.argtypes = [C.c_void_p, C.POINTER(LagProbe), C.c_uint32, C.c_uint32]
     L.LINNEAmd_SpliceStreamsDevice.argtypes = [C.c_void_p, C.POINTER(Splice), C.c_uint32, C.c_uint32]
@@ -1363,6 +1403,114 @@ class Context:
                        int(preset) if preset is not None else h["preset"], int(ms) if ms is not None else h["ch_process_method"])
                       for pcm, b, h in zip(pcms, obits, heads)]
             return self.encode_streams(tracks, group_frames=group_frames)
+
+    def project_windows(self, windows, basis, hop, before=0, shift=0, clip_bits=0, dtype=None, float_exp=0, rows_first=False, out=None,
+                        group_frames=0, return_codes=False, return_saturated=False):
+        """the frames of windows of resident streams projected on the rows of an int16 basis: an exact STFT, a filter bank (include/linne_amd.h
+        LINNEAmd_ProjectWindowsDevice states the arithmetic).  windows: (stream, index, first_frame, num_frames) -- a window counts
+        FRAMES of its stream, which has project_length(N, hop) of them; num_frames None: to the last.  Frame f holds the n_fft =
+        basis.shape[1] samples from f * hop - before on, zeros off either end of the stream; element (c, f, k) is the 64-bit sum of
+        basis[k][n] * x[c][f * hop - before + n], shifted right by `shift` with halves rounded up and clipped to clip_bits bits (0: 32)
+        as mix_windows has it.  basis: an integer array (K, n_fft) with values in int16.  dtype torch.int32 (the default) or torch.float32,
+        which stores (float)y * 2^-float_exp.  -> one tensor (W, C, frames, K), or (W, C, K, frames) with rows_first: all windows then
+        have one channel count and one frame count; `out` is such a tensor of any strides that keep its elements apart.  Values
+        outside the call's bounds raise ValueError before any call.  return_codes, return_saturated, group_frames and errors are
+        decode_windows'"""
+        import torch
+        W = len(windows)
+        b = np.asarray(basis)
+        if b.ndim != 2 or b.dtype.kind not in "iu" or b.size == 0:
+            raise ValueError(f"basis is an integer array (K, n_fft); got {b.dtype} {b.shape}")
+        if int(b.min()) < -32768 or int(b.max()) > 32767:
+            raise ValueError("a basis value outside int16")
+        b = np.ascontiguousarray(b, dtype=np.int16)
+        K, N = b.shape
+        hop, before, shift, clip_bits, float_exp = int(hop), int(before), int(shift), int(clip_bits), int(float_exp)
+        tdtype = torch.int32 if dtype is None else dtype
+        if tdtype not in (torch.int32, torch.float32):
+            raise ValueError("dtype is torch.int32 or torch.float32")
+        if not (1 <= N <= PROJECT_MAX_FRAME and 1 <= K <= PROJECT_MAX_ROWS and 1 <= hop <= PROJECT_MAX_HOP):
+            raise ValueError(f"n_fft is 1 .. {PROJECT_MAX_FRAME}, the rows 1 .. {PROJECT_MAX_ROWS}, hop 1 .. {PROJECT_MAX_HOP}")
+        if not (0 <= before < N and 0 <= shift <= 31 and (clip_bits == 0 or 2 <= clip_bits <= 32) and 0 <= float_exp <= 63 and (float_exp == 0 or tdtype is torch.float32)):
+            raise ValueError("before is 0 .. n_fft - 1, shift 0 .. 31, clip_bits 0 or 2 .. 32, float_exp 0 .. 63 and 0 with torch.int32")
+        ranged = []
+        for stream, index, first, n in windows:
+            if n is None:
+                n = project_length(index.header["num_samples"], hop) - int(first)
+            ranged.append((stream, index, first, n))
+        arr, keep, ranges = self._windows_array(ranged)
+        shapes = [(x.header["num_channels"], max(n, 0)) for x, _, n in ranges]
+        assert len(set(shapes)) <= 1, f"the windows of one call have one channel count and one frame count; got {sorted(set(shapes))}"
+        Cn, F = shapes[0] if shapes else (0, 0)
+        fdim, kdim = (3, 2) if rows_first else (2, 3)
+        if out is None:
+            out = torch.empty((W, Cn, K, F) if rows_first else (W, Cn, F, K), dtype=tdtype, device=f"cuda:{self.device}")
+        else:
+            assert out.dtype == tdtype and out.is_cuda and out.dim() == 4 and out.device.index == self.device, f"out is a {tdtype} CUDA tensor of the context's device"
+            assert tuple(out.shape) == ((W, Cn, K, F) if rows_first else (W, Cn, F, K)), f"out is {tuple(out.shape)}, the call gives {(W, Cn, K, F) if rows_first else (W, Cn, F, K)}"
+        specs = (ProjectSpec * max(W, 1))()
+        for i in range(W):
+            sp = specs[i]
+            sp.frame_len, sp.hop, sp.num_rows, sp.before, sp.shift, sp.clip_bits = N, hop, K, before, shift, clip_bits
+            sp.format, sp.float_exp, sp.reserved = (PCM_F32 if tdtype is torch.float32 else PCM_S32), float_exp, 0
+            sp.channel_stride, sp.frame_stride, sp.row_stride = out.stride(1), out.stride(fdim), out.stride(kdim)
+            sp.basis = b.ctypes.data_as(C.POINTER(C.c_int16))
+            arr[i].d_pcm, arr[i].pcm_stride = out.data_ptr() + out.element_size() * i * out.stride(0), 0
+        self._fence()
+        ret = lib.LINNEAmd_ProjectWindowsDevice(self.h, arr, specs, W, int(group_frames))
+        codes = self._windows_codes(ret, arr, W, "ProjectWindowsDevice", return_codes)
+        res = (out,) + ((codes,) if return_codes else ()) + (([bool(specs[i].saturated) for i in range(W)],) if return_saturated else ())
+        return res[0] if len(res) == 1 else res
+
+    def stft_windows(self, windows, n_fft, hop, window="hann", center=True, shift=15, dtype=None, float_exp=0, bins=None, clip_bits=0,
+                     rows_first=False, group_frames=0, return_codes=False, return_saturated=False):
+        """the exact integer short-time Fourier transform of windows of resident streams: project_windows on project_design(n_fft, bins,
+        window).  windows: (stream, index, first_sample, num_samples) in SAMPLES (num_samples None: to the stream's end); they map to
+        the frames f with first_sample <= f * hop < first_sample + num_samples.  center: frame f is centred on sample f * hop (before =
+        n_fft // 2), otherwise it starts there.  The basis is scaled by 32767: shift 15 (the default) gives the transform in the
+        samples' own units.  -> (W, C, frames, bins, 2), real and imaginary part last, or (W, C, bins, 2, frames) with rows_first"""
+        basis = project_design(n_fft, bins, window)
+        hop = int(hop)
+        if not 1 <= hop <= PROJECT_MAX_HOP:
+            raise ValueError(f"hop is 1 .. {PROJECT_MAX_HOP}")
+        framed = []
+        for stream, index, first, n in windows:
+            first = int(first)
+            n = index.header["num_samples"] - first if n is None else int(n)
+            f0 = -(-first // hop)
+            framed.append((stream, index, f0, -(-(first + n) // hop) - f0 if n >= 0 else n))
+        res = self.project_windows(framed, basis, hop, before=n_fft // 2 if center else 0, shift=shift, clip_bits=clip_bits, dtype=dtype,
+                                   float_exp=float_exp, rows_first=rows_first, group_frames=group_frames, return_codes=return_codes,
+                                   return_saturated=return_saturated)
+        many = isinstance(res, tuple)
+        t = res[0] if many else res
+        t = t.view(t.shape[0], t.shape[1], t.shape[2] // 2, 2, t.shape[3]) if rows_first else t.view(t.shape[0], t.shape[1], t.shape[2], t.shape[3] // 2, 2)
+        return (t,) + tuple(res[1:]) if many else t
+
+    def spectrum_streams(self, streams, n_fft, hop):
+        """the exact power spectrum of whole resident streams: one index_streams call, one stft_windows call (its defaults: Hann, centred,
+        shift 15, int32) per group of streams of one shape, and per stream, channel and bin the sum over all frames of re^2 + im^2 as
+        a Python integer -> a list per stream of [channel][bin] integers.  A bin that does not fit int32 at shift 15 (a 24-bit stream
+        under a long frame) would make the sums those of clipped values: OverflowError, naming the streams"""
+        import torch
+        if len(streams) == 0:
+            return []
+        with self._whole_streams(streams) as (ts, indexes, _):
+            groups = {}
+            for i, x in enumerate(indexes):
+                groups.setdefault((x.header["num_channels"], project_length(x.header["num_samples"], hop)), []).append(i)
+            out = [None] * len(streams)
+            for members in groups.values():
+                z, clipped = self.stft_windows([(ts[i], indexes[i], 0, None) for i in members], n_fft, hop, return_saturated=True)    # (W, C, frames, bins, 2)
+                if any(clipped):
+                    raise OverflowError(f"spectrum_streams: a bin of stream(s) {[i for i, c in zip(members, clipped) if c]} does not fit 32 bits at shift 15")
+                z = z.to(torch.int64)
+                # v = a * 2^16 + b, 0 <= b < 2^16: the three sums stay inside int64 and recombine exactly
+                a, b = z >> 16, z & 0xFFFF
+                saa, sab, sbb = ((u * v).sum(dim=(2, 4)).cpu().tolist() for u, v in ((a, a), (a, b), (b, b)))
+                for w, i in enumerate(members):
+                    out[i] = [[(int(p) << 32) + (int(q) << 17) + int(r) for p, q, r in zip(*rows)] for rows in zip(saa[w], sab[w], sbb[w])]
+            return out
 
     def overlay_windows(self, outputs, shift=0, clip_bits=0, out=None, group_frames=0, return_codes=False, dtype=None, channels_last=False,
                         s24=False, return_saturated=False):

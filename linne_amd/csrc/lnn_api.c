@@ -967,3 +967,36 @@ int LINNEAmd_ResampleDesign(uint32_t up, uint32_t down, uint32_t taps, int16_t *
     *shift = sh; *before = (taps - 1u) / 2u;
     return LINNE_APIRESULT_OK;
 }
+
+/* ================================================================================================
+ * the DFT basis of LINNEAmd_ProjectWindowsDevice (include/linne_amd.h LINNEAmd_ProjectDesign): host code, no device
+ * ============================================================================================== */
+/* cos and sin of 2 pi m / n, m < n, from the angle folded into the first half turn: point n - m is point m mirrored to the bit */
+static double project_cos(uint32_t m, uint32_t n)
+{
+    const double pi = 3.14159265358979323846;
+    if (2u * (uint64_t)m > n) m = n - m;
+    return cos(2.0 * pi * (double)m / (double)n);
+}
+static double project_sin(uint32_t m, uint32_t n)
+{
+    const double pi = 3.14159265358979323846;
+    if (2u * (uint64_t)m > n) return -sin(2.0 * pi * (double)(n - m) / (double)n);
+    return sin(2.0 * pi * (double)m / (double)n);
+}
+int LINNEAmd_ProjectDesign(uint32_t frame_len, uint32_t bins, uint32_t window, int16_t *basis)
+{
+    uint32_t j, n;
+    if (!basis || window > 1u) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    if (frame_len < 1u || frame_len > LINNE_AMD_PROJECT_MAX_FRAME) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    if (bins < 1u || bins > frame_len / 2u + 1u || 2u * bins > LINNE_AMD_PROJECT_MAX_ROWS) return LINNE_APIRESULT_INVALID_ARGUMENT;
+    for (j = 0; j < bins; j++)
+        for (n = 0; n < frame_len; n++) {
+            const double w = window ? 0.5 - 0.5 * project_cos(n, frame_len) : 1.0;
+            const uint32_t m = (uint32_t)(((uint64_t)j * n) % frame_len);
+            /* (rint: to nearest, halves to even, in the default rounding mode; |value| <= 32767) */
+            basis[(size_t)(2u * j) * frame_len + n] = (int16_t)rint(32767.0 * w * project_cos(m, frame_len));
+            basis[(size_t)(2u * j + 1u) * frame_len + n] = (int16_t)rint(-32767.0 * w * project_sin(m, frame_len));
+        }
+    return LINNE_APIRESULT_OK;
+}

@@ -59,6 +59,7 @@
 #include "lnn_k_resample.h"
 #include "lnn_k_overlay.h"
 #include "lnn_k_lags.h"
+#include "lnn_k_project.h"
 #include "lnn_k_stream_enc.h"
 #include "lnn_stream_batch.h"
 #include "lnn_block_scan.h"             /* where the lists of the index's and the repair call's block-head scan lie */
@@ -80,6 +81,7 @@ static_assert(LINNE_AMD_MIX_T_MIX == 98, "the mix call's timing kind is 98");
 static_assert(LINNE_AMD_RESAMPLE_T_PRESET == 99 && LINNE_AMD_RESAMPLE_T_RESAMPLE == 100, "the resample call's timing kinds are 99 and 100");
 static_assert(LINNE_AMD_OVERLAY_T_OVERLAY == 101, "the overlay call's timing kind is 101");
 static_assert(LINNE_AMD_LAGS_T_LAGS == 102 && LINNE_AMD_LAGS_T_COMMIT == 103, "the lag call's timing kinds are 102 and 103");
+static_assert(LINNE_AMD_PROJECT_T_PRESET == 104 && LINNE_AMD_PROJECT_T_PROJECT == 105, "the project call's timing kinds are 104 and 105");
 static_assert(LNN_FIR_TILE == FIR_TILE && LNN_FIR_WAVES == FIR_THREADS / 64 && LNN_SELW_MAXPART == SELW_MAXPART && LNN_SEARCH_JOB_MIN == SEARCH_JOB_MIN && LNN_LEV_MAXRIDE == LEV_MAXRIDE, "lnn_forms.h and the kernels disagree");
 
 /* ================================================================================================
@@ -2256,6 +2258,7 @@ struct WxLaunch {
     const WxResample *rs; const WxTile *tiles; const uint32_t *coef; uint64_t ntile; uint32_t *sat;        /* the resampling consumer's */
     const WxOvOutput *ov_outs; const WxOvSource *ov_srcs;          /* the overlaying consumer's, beside tiles, ntile and sat */
     const WxLagTile *lg_tiles; const uint32_t *lg_runs; const WxLagProbe *lg_probes; const WxLagImage *lg_imgs; uint64_t nlgrun, lg_part;     /* the lag consumer's, beside ntile */
+    const WxProject *pj; const WxProjTile *pj_tiles; const WxProjTable *pj_tabs; const int32_t *pj_rsum; const int16_t *pj_raw; uint32_t pj_ntab; uint64_t pj_plane0, pj_cells;   /* the projecting consumer's, beside ntile and sat */
 };
 /* What a windows call does with its windows' samples: k_wx_place's place in a pass, and what goes with it.  The eleven calls are the
  * eleven constant instances below; a launch that a consumer does not have is NULL */
@@ -2279,6 +2282,8 @@ struct WxConsumer {
                                          * accumulators, the commit sums the outputs from them (a consumer without buckets) */
     bool lags;                          /* the windows are the needles and haystacks of the call's probes (WxCall.lag_*): the passes place them into images
                                          * among the accumulators, the commit slides them (a consumer without buckets) */
+    bool projects;                      /* a WxProject beside every window record, from the windows' struct LINNEAmdProjectSpec: the passes place the
+                                         * windows' input ranges into images among the accumulators, the commit projects their frames (a consumer without buckets) */
 };
 struct WxCall {
     const WxConsumer *use;
@@ -2290,12 +2295,13 @@ struct WxCall {
     const struct LINNEAmdResampleSpec *rs;      /* [W], resample alone, likewise */
     const struct LINNEAmdOverlaySource *const *ov_src; const WxOvOut *ov_outs; uint32_t ov_O;      /* overlay alone: window i's source [W]; the outputs [ov_O] */
     const WxLagIn *lag_in; uint32_t lag_Q;      /* lags alone: the probes [lag_Q] */
+    struct LINNEAmdProjectSpec *pj;     /* [W], project alone: in (the spec) and out (`saturated`) */
 };
 static WxCall wx_call(const WxConsumer *use, struct LINNEAmdWindow *win, uint32_t W, uint32_t group_frames, const void *specs, void *answers)
 {
     WxCall c;
     c.use = use; c.single = false; c.win = win; c.W = W; c.group_frames = group_frames; c.specs = specs; c.answers = answers; c.mix = NULL; c.rs = NULL;
-    c.ov_src = NULL; c.ov_outs = NULL; c.ov_O = 0; c.lag_in = NULL; c.lag_Q = 0;
+    c.ov_src = NULL; c.ov_outs = NULL; c.ov_O = 0; c.lag_in = NULL; c.lag_Q = 0; c.pj = NULL;
     return c;
 }
 /* a lane per unit, in a grid-stride kernel */
@@ -2583,6 +2589,63 @@ static int wx_lags_commit(LINNEAmdContext *ctx, const WxLaunch &l)
     return LNN_OK;
 }
 
+/* ---- project: the passes place the windows' input ranges into images; the commit projects their frames on the basis rows (lnn_k_project.h) ---- */
+/* the spec's own bounds, which the range check needs in front of it */
+static int wx_project_spec_check(const WxCall &c, uint32_t i, char *err, size_t cap)
+{
+    const struct LINNEAmdProjectSpec &s = c.pj[i];
+    const char *who = c.use->name;
+    if (s.frame_len < 1u || s.frame_len > LINNE_AMD_PROJECT_MAX_FRAME) { snprintf(err, cap, "%s: frame_len %u is not 1 .. %u", who, s.frame_len, (unsigned)LINNE_AMD_PROJECT_MAX_FRAME); return LNN_INVALID_ARGUMENT; }
+    if (s.hop < 1u || s.hop > LINNE_AMD_PROJECT_MAX_HOP) { snprintf(err, cap, "%s: hop %u is not 1 .. %u", who, s.hop, (unsigned)LINNE_AMD_PROJECT_MAX_HOP); return LNN_INVALID_ARGUMENT; }
+    if (s.num_rows < 1u || s.num_rows > LINNE_AMD_PROJECT_MAX_ROWS) { snprintf(err, cap, "%s: num_rows %u is not 1 .. %u", who, s.num_rows, (unsigned)LINNE_AMD_PROJECT_MAX_ROWS); return LNN_INVALID_ARGUMENT; }
+    if (s.before > s.frame_len - 1u) { snprintf(err, cap, "%s: before %u > frame_len - 1", who, s.before); return LNN_INVALID_ARGUMENT; }
+    if (s.shift > 31u) { snprintf(err, cap, "%s: shift %u > 31", who, s.shift); return LNN_INVALID_ARGUMENT; }
+    if (s.clip_bits == 1u || s.clip_bits > 32u) { snprintf(err, cap, "%s: clip_bits %u is neither 0 nor 2 .. 32", who, s.clip_bits); return LNN_INVALID_ARGUMENT; }
+    if (s.format != LINNE_AMD_PCM_S32 && s.format != LINNE_AMD_PCM_F32) { snprintf(err, cap, "%s: format %u is neither S32 nor F32", who, s.format); return LNN_INVALID_ARGUMENT; }
+    if (s.float_exp > 63u || (s.float_exp != 0u && s.format == LINNE_AMD_PCM_S32)) { snprintf(err, cap, "%s: float_exp %u is not 0 .. 63, or not 0 with S32", who, s.float_exp); return LNN_INVALID_ARGUMENT; }
+    if (s.reserved != 0u) { snprintf(err, cap, "%s: reserved is not 0", who); return LNN_INVALID_ARGUMENT; }
+    if (!s.basis) { snprintf(err, cap, "%s: null basis", who); return LNN_INVALID_ARGUMENT; }
+    if (!c.win[i].d_pcm) { snprintf(err, cap, "%s: null d_pcm", who); return LNN_INVALID_ARGUMENT; }
+    if ((uint64_t)(uintptr_t)c.win[i].d_pcm & 3u) { snprintf(err, cap, "%s: d_pcm is not 4-byte aligned", who); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+/* what needs the stream's channel count, still in front of the range check: the products' cap and the injective output map */
+static int wx_project_shape_check(const WxCall &c, uint32_t i, uint32_t C, char *err, size_t cap)
+{
+    const struct LINNEAmdProjectSpec &s = c.pj[i];
+    const char *who = c.use->name;
+    const uint64_t n = c.win[i].num_samples;
+    if (!wxp_products_fit(n, s.num_rows, s.frame_len, C)) { snprintf(err, cap, "%s: %llu frames * %u rows * %u samples * %u channels > 2^40 products", who, (unsigned long long)n, s.num_rows, s.frame_len, C); return LNN_INVALID_ARGUMENT; }
+    if (!wxp_injective(s.channel_stride, C, s.frame_stride, n, s.row_stride, s.num_rows)) { snprintf(err, cap, "%s: channel_stride %llu, frame_stride %llu and row_stride %llu do not keep %u channels, %llu frames and %u rows apart", who, (unsigned long long)s.channel_stride, (unsigned long long)s.frame_stride, (unsigned long long)s.row_stride, C, (unsigned long long)n, s.num_rows); return LNN_INVALID_ARGUMENT; }
+    return LNN_OK;
+}
+static int wx_project_check(const WxCall &, uint32_t, char *, size_t) { return LNN_OK; }   /* (the window's own checks came in front of the range check) */
+/* (behind wx_decode's own: the planned range becomes the window's input range) */
+static void wx_project_describe(const WxCall &c, uint32_t i, WxRange &r)
+{
+    r.out = c.win[i].d_pcm; r.fmt = c.pj[i].format; r.stride = c.pj[i].channel_stride; r.sstride = c.pj[i].frame_stride;
+    r.pj = c.pj + i; r.m_lo = r.lo; r.m_n = r.n;
+    const WxpInput in = wxp_input(r.m_lo, r.m_n, c.pj[i], c.win[i].index->header.num_samples);
+    r.lo = in.lo; r.n = in.hi - in.lo;
+}
+static int wx_project_preset(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxProjectPresetArgs pa;
+    pa.acc = (uint4 *)l.acc; pa.n16 = l.pj_plane0 / 4u; pa.tabs = l.pj_tabs; pa.ntab = l.pj_ntab; pa.raw = l.pj_raw; pa.planes = (int8_t *)((int32_t *)l.acc + l.pj_plane0);
+    SX_LAUNCH(NULL, LINNE_AMD_PROJECT_T_PRESET, k_wx_project_preset, wx_grid(pa.n16 > l.pj_cells ? pa.n16 : l.pj_cells), dim3(WXB_THREADS), 0, ctx->stream, pa);
+    return LNN_OK;
+}
+static int wx_project_commit(LINNEAmdContext *ctx, const WxLaunch &l)
+{
+    WxProjectArgs pa;
+    pa.tiles = l.pj_tiles; pa.ntiles = (uint32_t)l.ntile; pa.pwin = l.pj; pa.fail = l.fail; pa.sat = l.sat; pa.acc = (const int32_t *)l.acc;
+    pa.planes = (const int8_t *)((const int32_t *)l.acc + l.pj_plane0); pa.raw = l.pj_raw; pa.rsum = l.pj_rsum;
+    SX_LAUNCH(NULL, LINNE_AMD_PROJECT_T_PROJECT, k_wx_project, dim3(pa.ntiles ? pa.ntiles : 1u), dim3(WXP_THREADS), 0, ctx->stream, pa);
+    return LNN_OK;
+}
+/* (a failing window's `saturated` stays as the caller left it) */
+static void wx_project_read_back(const WxCall &c, uint32_t i, const uint32_t *words) { c.pj[i].saturated = (words && words[c.W + i]) ? 1u : 0u; }
+
 static const WxConsumer WX_PLACE = { "DecodeWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 0u, 0u, wx_place_check, wx_pcm_describe, NULL, wx_place_pass, NULL, wx_place_read_back, false, false };
 static const WxConsumer WX_COMPARE = { "CompareWindowsDevice", 4u, wx_compare_back_preset, WX_NO_BUCKETS, 0u, 0u, wx_compare_check, wx_pcm_describe, NULL, wx_compare_pass, NULL, wx_compare_read_back, false, false };
 static const WxConsumer WX_MEASURE = { "MeasureWindowsDevice", 0u, NULL, WX_BUCKETS_PER_CHANNEL, sizeof(struct LINNEAmdMeasure), 0u, wx_measure_check, wx_measure_describe, wx_measure_preset, wx_measure_pass, wx_measure_commit, NULL, false, false };
@@ -2594,6 +2657,7 @@ static const WxConsumer WX_MIX = { "MixWindowsDevice", 0u, NULL, WX_NO_BUCKETS, 
 static const WxConsumer WX_RESAMPLE = { "ResampleWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_resample_check, wx_resample_describe, wx_resample_preset, wx_place_pass, wx_resample_commit, wx_place_read_back, false, true };
 static const WxConsumer WX_OVERLAY = { "OverlayWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_overlay_check, wx_overlay_describe, NULL, wx_place_pass, wx_overlay_commit, NULL, false, false, true };
 static const WxConsumer WX_LAGS = { "LagWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_lags_check, wx_lags_describe, NULL, wx_place_pass, wx_lags_commit, NULL, false, false, false, true };
+static const WxConsumer WX_PROJECT = { "ProjectWindowsDevice", 0u, NULL, WX_NO_BUCKETS, sizeof(int32_t), 0u, wx_project_check, wx_project_describe, wx_project_preset, wx_place_pass, wx_project_commit, wx_project_read_back, false, false, false, false, true };
 
 /* the argument and index checks on window i, with their codes and texts (they name LINNEAmd_DecodeStreamDevice, whose arguments a
  * window's fields are; the consumer's own name its call).  *r1 = the last block the window overlaps (nb: it reaches behind the last
@@ -2604,15 +2668,18 @@ static int wx_check_window(const LINNEAmdContext *ctx, const WxCall &c, uint32_t
     const LINNEAmdStreamIndex *x = w->index;
     err[0] = 0;
     if (c.rs) SX_TRY(wx_resample_spec_check(c, i, err, cap));      /* (in front of everything: the range check needs the ratio) */
+    if (c.pj) SX_TRY(wx_project_spec_check(c, i, err, cap));       /* (likewise: the range check needs the hop) */
     if (!x || !w->d_stream) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (c.use->bucketing == WX_NO_BUCKETS && !w->d_pcm && w->num_samples) { snprintf(err, cap, "DecodeStreamDevice: null argument"); return LNN_INVALID_ARGUMENT; }
     if (x->device != ctx->device) { snprintf(err, cap, "DecodeStreamDevice: the index belongs to device %d, the context to %d", x->device, ctx->device); return LNN_INVALID_ARGUMENT; }
     uint64_t total = x->header.num_samples;
     if (c.rs) total = wxr_length(total, c.rs[i].up, c.rs[i].down);         /* the range is one of the resampled stream */
+    if (c.pj) { SX_TRY(wx_project_shape_check(c, i, x->shape.num_channels, err, cap)); total = wxp_length(total, c.pj[i].hop); }   /* the range is one of the stream's frames */
     if (w->first_sample > total || w->num_samples > total - w->first_sample) { snprintf(err, cap, "DecodeStreamDevice: samples [%llu, %llu) beyond the stream's %llu", (unsigned long long)w->first_sample, (unsigned long long)(w->first_sample + w->num_samples), (unsigned long long)total); return LNN_INVALID_ARGUMENT; }
     SX_TRY(c.use->check(c, i, err, cap));
     if (w->num_samples == 0) return LNN_OK;
-    const uint64_t hi = c.rs ? wxr_input(w->first_sample, w->num_samples, c.rs[i], x->header.num_samples).hi : w->first_sample + w->num_samples;
+    const uint64_t hi = c.rs ? wxr_input(w->first_sample, w->num_samples, c.rs[i], x->header.num_samples).hi
+                      : c.pj ? wxp_input(w->first_sample, w->num_samples, c.pj[i], x->header.num_samples).hi : w->first_sample + w->num_samples;
     *r1 = (hi - 1u < x->covered) ? wx_block_of(x->h_first, x->nb, hi - 1u) : x->nb;
     if (x->fail_block >= 0 && (uint64_t)x->fail_block <= *r1) {
         snprintf(err, cap, "block %lld (byte %llu of the stream): %s", (long long)x->fail_block, (unsigned long long)x->fail_off,
@@ -2659,6 +2726,10 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
         wx_overlay_count(c.ov_outs, c.ov_O, pl);
         if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
     }
+    if (u.projects) {
+        wx_project_count(rg.data(), W, pl);
+        if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of outputs in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
+    }
     if (u.lags) {
         wx_lag_count(c.lag_in, c.lag_Q, pl);
         if (pl.rs_tiles > WX_MAX_TILES) { snprintf(ctx->err, sizeof(ctx->err), "%s: %llu tiles of lags in one call: too many", who, (unsigned long long)pl.rs_tiles); return LNN_NG; }
@@ -2666,24 +2737,25 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     HIPCHK(ctx, hipSetDevice(ctx->device));
     lnn_knobs_read_call(&ctx->knob);
     /* 2. the lists, in pinned memory */
-    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : 0u, u.resamples, u.overlays, u.lags);
+    const WxLists ls = wx_lists(pl, W, u.back_words, u.bucketing != WX_NO_BUCKETS ? sizeof(WxBucket) : u.mixes ? sizeof(WxMix) : u.resamples ? sizeof(WxResample) : u.projects ? sizeof(WxProject) : 0u, u.resamples, u.overlays, u.lags, u.projects);
     SX_TRY(ensure_buf(ctx, &ctx->wstage, &ctx->wstage_cap, ls.bytes, true));
     uint8_t *hs_ = (uint8_t *)ctx->wstage;
     uint32_t *h_fail = (uint32_t *)(hs_ + ls.o_fail);
     for (uint32_t i = 0; i < W; i++) { h_fail[i] = WX_NOFAIL; h_fail[W + i] = 0u; }
     if (u.back_preset) u.back_preset((uint32_t *)(hs_ + ls.o_back), W);
+    const WxProjLists pjl = { (WxProject *)(hs_ + ls.o_side), (WxProjTile *)(hs_ + ls.o_tile), (WxProjTable *)(hs_ + ls.o_pjtab), (int32_t *)(hs_ + ls.o_pjrsum), (int16_t *)(hs_ + ls.o_pjraw) };
     wx_plan_fill(rg.data(), W, c.group_frames, u.bucketing, pl, (WxWindow *)(hs_ + ls.o_win), u.bucketing != WX_NO_BUCKETS ? (WxBucket *)(hs_ + ls.o_side) : NULL,
             (WxBlock *)(hs_ + ls.o_rec), (uint32_t *)(hs_ + ls.o_crec), u.mixes ? (WxMix *)(hs_ + ls.o_side) : NULL,
             u.resamples ? (WxResample *)(hs_ + ls.o_side) : NULL, u.resamples ? (WxTile *)(hs_ + ls.o_tile) : NULL, u.resamples ? (uint32_t *)(hs_ + ls.o_coef) : NULL,
             u.overlays ? (WxOvSource *)memset(hs_ + ls.o_ovsrc, 0, sizeof(WxOvSource) * W) : NULL,
-            u.lags ? (WxLagImage *)memset(hs_ + ls.o_lgimg, 0, sizeof(WxLagImage) * W) : NULL);
+            u.lags ? (WxLagImage *)memset(hs_ + ls.o_lgimg, 0, sizeof(WxLagImage) * W) : NULL, u.projects ? &pjl : NULL);
     if (u.lags) wx_lag_fill(c.lag_in, c.lag_Q, pl, (WxLagProbe *)(hs_ + ls.o_lgprobe), (WxLagTile *)(hs_ + ls.o_tile), (uint32_t *)(hs_ + ls.o_lgrun));
     if (u.overlays) wx_overlay_fill(c.ov_outs, c.ov_O, rg.data(), pl, (WxOvOutput *)(hs_ + ls.o_ovout), (WxTile *)(hs_ + ls.o_tile));
     for (const WxPass &p : pl.passes) if (p.seg_bytes >= ((uint64_t)1 << 33)) { snprintf(ctx->err, sizeof(ctx->err), "%s: a pass of %llu stream bytes: %s", who, (unsigned long long)p.seg_bytes, advice); return LNN_NG; }
     /* 3. device memory (a buffer that grows waits for the stream first), then the one upload */
     SX_TRY(ensure_buf(ctx, &ctx->wdec, &ctx->wdec_cap, ls.bytes));
     const uint64_t o_acc = align_up(pl.scratch_bytes);             /* (the accumulators lie behind every pass's scratch) */
-    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples || u.overlays || u.lags ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
+    SX_TRY(ensure_buf(ctx, &ctx->sdec, &ctx->sdec_cap, o_acc + (u.bucketing != WX_NO_BUCKETS || u.resamples || u.overlays || u.lags || u.projects ? u.acc_unit * (u.acc_prefix + pl.nacc) : 0u)));
     uint8_t *wd = (uint8_t *)ctx->wdec, *sd = (uint8_t *)ctx->sdec;
     uint32_t *d_fail = (uint32_t *)(wd + ls.o_fail);
     const WxWindow *d_win = (const WxWindow *)(wd + ls.o_win);
@@ -2694,7 +2766,10 @@ static int wx_decode(LINNEAmdContext *ctx, const WxCall &c, WxPlanned &pl, const
     ln.ov_outs = (const WxOvOutput *)(wd + ls.o_ovout); ln.ov_srcs = (const WxOvSource *)(wd + ls.o_ovsrc);
     ln.lg_tiles = (const WxLagTile *)(wd + ls.o_tile); ln.lg_runs = (const uint32_t *)(wd + ls.o_lgrun); ln.lg_probes = (const WxLagProbe *)(wd + ls.o_lgprobe);
     ln.lg_imgs = (const WxLagImage *)(wd + ls.o_lgimg); ln.nlgrun = pl.nlgrun; ln.lg_part = pl.lg_part;
-    if (u.resamples || u.overlays || u.lags) {        /* the plan named the images by their offsets: now they have an address */
+    ln.pj = (const WxProject *)(wd + ls.o_side); ln.pj_tiles = (const WxProjTile *)(wd + ls.o_tile); ln.pj_tabs = (const WxProjTable *)(wd + ls.o_pjtab);
+    ln.pj_rsum = (const int32_t *)(wd + ls.o_pjrsum); ln.pj_raw = (const int16_t *)(wd + ls.o_pjraw); ln.pj_ntab = (uint32_t)pl.pj_tabs.size(); ln.pj_plane0 = pl.pj_plane0; ln.pj_cells = 0;
+    for (const WxProjTable &tb : pl.pj_tabs) { const uint64_t cells = (uint64_t)tb.Kpad * tb.Npad; if (cells > ln.pj_cells) ln.pj_cells = cells; }
+    if (u.resamples || u.overlays || u.lags || u.projects) {        /* the plan named the images by their offsets: now they have an address */
         WxWindow *h_win = (WxWindow *)(hs_ + ls.o_win);
         for (uint32_t k = 0; k < pl.nwin; k++) h_win[k].out = ln.acc + (uintptr_t)h_win[k].out;
     }
@@ -2856,6 +2931,16 @@ extern "C" int LINNEAmd_ResampleWindowsDevice(struct LINNEAmdContext *ctx, struc
     return wx_entry(ctx, c, windows && specs);
 }
 extern "C" uint64_t LINNEAmd_ResampleLength(uint64_t num_samples, uint32_t up, uint32_t down) { return wxr_length(num_samples, up, down); }
+
+/* the windows are ranges of the stream's frames, every frame projected on the rows of the window's int16 basis, into a table per window */
+extern "C" int LINNEAmd_ProjectWindowsDevice(struct LINNEAmdContext *ctx, struct LINNEAmdWindow *windows, struct LINNEAmdProjectSpec *specs,
+        uint32_t num_windows, uint32_t group_frames)
+{
+    WxCall c = wx_call(&WX_PROJECT, windows, num_windows, group_frames, NULL, NULL);
+    c.pj = specs;
+    return wx_entry(ctx, c, windows && specs);
+}
+extern "C" uint64_t LINNEAmd_ProjectLength(uint64_t num_samples, uint32_t hop) { return wxp_length(num_samples, hop); }
 
 /* ---- LINNEAmd_OverlayWindowsDevice: the sources of all outputs are the windows of one windows call ---- */
 /* the gain (q + step * i) >> 32 lies in int16: in 128 bits */

@@ -1,5 +1,5 @@
 /* lnn_windows_plan.h -- the host's planning for the windows calls (LINNEAmd_DecodeWindowsDevice and its siblings that compare, measure,
- * digest, find quiet runs, histogram, relate, mix, resample, overlay and slide; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
+ * digest, find quiet runs, histogram, relate, mix, resample, overlay, slide and project; DESIGN.md section 5, "Many windows in one call"): from the windows' ranges and their streams' block indexes, the groups
  * by stream shape, the passes under group_frames, the block, window and bucket records the kernels of lnn_k_windows.h read, and the
  * sizes of the lists and of a pass's scratch.  Plain host C++ with no HIP call and no context in it, so a small stand-alone program
  * (tests/test_windows_plan_cpu.py) can drive it.  The records' structs are here because the plan fills them.
@@ -172,6 +172,31 @@ struct WxLagIn {
     void *out; uint64_t pstride; uint64_t *a_sq; uint8_t ca[LINNE_MAX_NUM_CHANNELS], cb[LINNE_MAX_NUM_CHANNELS];
 };
 
+/* ---- the projecting consumer (lnn_k_project.h): its WxWindow names the window's INPUT range and, as its output, the window's int32
+ * planar image in the accumulators, as a resampled window's does; the table the caller named is here (144 bytes) */
+struct WxProject {
+    void *out; uint64_t cstride, fstride, rstride;      /* the caller's table: element (c, f, k) at out + c * cstride + (f - f_lo) * fstride + k * rstride elements */
+    uint64_t f_lo, nframes;             /* the frames [f_lo, f_lo + nframes) of the stream */
+    uint64_t img, istride;              /* the image's first word among the accumulators; words from one channel to the next; word j of a channel is stream sample f_lo * H - before + j */
+    uint64_t planes;                    /* its basis' digit planes: their first byte in the call's plane area (behind the images) */
+    uint64_t raw;                       /* its basis as the caller gave it: its first int16 in the lists' table area */
+    uint64_t rsum;                      /* its rows' sums: their first word in the lists' sums area */
+    uint32_t N, H, K, Npad, Kpad, shift;        /* Npad: N rounded up to 64; Kpad: K rounded up to 16 */
+    int32_t lo, hi;                     /* the clip */
+    uint32_t fmt, scale_bits;           /* LINNE_AMD_PCM_S32 / _F32; the float 2^-float_exp */
+    uint32_t fidx, C;                   /* its fail word; the stream's channels */
+    uint32_t reserved[2];
+};
+/* one basis of the call (32 bytes): K rows of N int16 at `raw`, to become two planes of Kpad rows of Npad bytes at `planes` */
+struct WxProjTable { uint64_t raw, planes; uint32_t K, N, Kpad, Npad; };
+/* WXP_FRAMES frames from f0 on (counted from the window's first) by WXP_ROWS rows from k0 on, of channel ch of one window */
+struct WxProjTile { uint64_t f0; uint32_t win, ch, k0, reserved; };
+static_assert(sizeof(WxProject) == 144 && sizeof(WxProjTable) == 32 && sizeof(WxProjTile) == 24, "a project record is 144 bytes, a table record 32, a tile 24");
+#define WXP_FRAMES 64u
+#define WXP_ROWS 64u
+/* where wx_plan_fill writes the projecting consumer's lists */
+struct WxProjLists { WxProject *rec; WxProjTile *tile; WxProjTable *tab; int32_t *rsum; int16_t *raw; };
+
 /* the histogram's spec in one word: num_bins (1 .. 1024) | shift (0 .. 31) << 16 | scale (0 linear, 1 log2) << 24 */
 #define WXH_SPEC(bins, shift, scale) ((uint32_t)(bins) | (uint32_t)(shift) << 16 | (uint32_t)(scale) << 24)
 #define WXH_BINS(h) ((h) & 0xFFFFu)
@@ -208,6 +233,7 @@ struct WxRange {
     const struct LINNEAmdResampleSpec *rs;      /* the resampling consumer: its spec, checked; [lo, lo + n) above is the window's INPUT range */
     uint64_t m_lo, m_n;                 /* ... and these its output samples, of the resampled stream */
     const struct LINNEAmdOverlaySource *ov;     /* the overlaying consumer: the source this window is, checked */
+    const struct LINNEAmdProjectSpec *pj;       /* the projecting consumer: its spec, checked; [lo, lo + n) is the window's INPUT range, m_lo and m_n its frames */
 };
 struct WxPlan { uint32_t r0, nr, ncomp; int32_t group; };               /* a window's blocks [r0, r0 + nr), the COMPRESS ones among them; group -1: it takes no pass */
 struct WxPass { uint32_t group, rec0, nrec, c0, nc; uint64_t seg_bytes; int check_only; };
@@ -227,6 +253,11 @@ struct WxPlanned {
     /* the lag consumer (wx_lag_count): the probes that get tiles (counted in rs_tiles) and the runs of tiles the commit takes; nlg and
      * nlgrun: those written; lg_part: the partial sums' first word among the accumulators (wx_lag_fill) */
     uint64_t lg_probes, lg_runs, nlg, nlgrun, lg_part;
+    /* the projecting consumer (wx_project_count): every window's table among the call's (windows of one (basis, K, N) share one), the
+     * tables' records, int16 elements, row sums and plane bytes the lists and the scratch must have room for (the tiles are counted in
+     * rs_tiles); pj_plane0: the planes' first word among the accumulators (wx_plan_fill) */
+    std::vector<uint32_t> pj_tab; std::vector<uint8_t> pj_owner; std::vector<WxProjTable> pj_tabs;
+    uint64_t pj_raw, pj_rsum, pj_plane_bytes, pj_plane0;
 };
 enum { WXP_OK = 0, WXP_SHAPES = 1, WXP_BLOCKS = 2 };    /* wx_plan_count: more than WX_MAXGROUPS shapes; total_rec blocks are too many */
 
@@ -270,8 +301,8 @@ static inline WxScratch wx_scratch(uint32_t nc, uint32_t C, uint32_t S, uint64_t
 /* the lists, in pinned memory and at the same offsets on the device: the words that come back (fail words, saturation words and
  * back_words 32-bit words per window of the consumer's own) | window records | the consumer's per-window records | block records |
  * the passes' COMPRESS records */
-struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef, o_ovout, o_ovsrc, o_lgrun, o_lgprobe, o_lgimg; };
-static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false, bool overlays = false, bool lags = false)
+struct WxLists { uint64_t o_fail, o_back, back_bytes, o_win, o_side, o_rec, o_crec, bytes, o_tile, o_coef, o_ovout, o_ovsrc, o_lgrun, o_lgprobe, o_lgimg, o_pjtab, o_pjrsum, o_pjraw; };
+static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_words, uint64_t side_bytes, bool resamples = false, bool overlays = false, bool lags = false, bool projects = false)
 {
     WxLists l;
     l.o_fail = 0; l.o_back = 2u * sizeof(uint32_t) * W; l.back_bytes = l.o_back + sizeof(uint32_t) * back_words * W;
@@ -298,6 +329,13 @@ static inline WxLists wx_lists(const WxPlanned &p, uint64_t W, uint64_t back_wor
         l.o_lgimg = wx_align(l.o_lgprobe + sizeof(WxLagProbe) * p.lg_probes);
         l.bytes = wx_align(l.o_lgimg + sizeof(WxLagImage) * W);
     }
+    l.o_pjtab = l.o_pjrsum = l.o_pjraw = l.bytes;
+    if (projects) {                     /* likewise: the tiles | the table records | the rows' sums | the tables as the caller gave them */
+        l.o_pjtab = wx_align(l.o_tile + sizeof(WxProjTile) * p.rs_tiles);
+        l.o_pjrsum = wx_align(l.o_pjtab + sizeof(WxProjTable) * p.pj_tabs.size());
+        l.o_pjraw = wx_align(l.o_pjrsum + sizeof(int32_t) * p.pj_rsum);
+        l.bytes = wx_align(l.o_pjraw + sizeof(int16_t) * p.pj_raw);
+    }
     return l;
 }
 
@@ -309,6 +347,7 @@ static inline int wx_plan_count(const WxRange *rg, uint32_t W, uint32_t group_fr
     p.passes.clear(); p.nwin = p.nrec = p.ncrec = 0; p.scratch_bytes = p.nacc = p.nout = p.nmask = 0;
     p.rs_coef.clear(); p.rs_owner.clear(); p.rs_words = p.rs_tiles = p.ntile = 0; p.ov_outs = p.nov = 0;
     p.lg_probes = p.lg_runs = p.nlg = p.nlgrun = p.lg_part = 0;
+    p.pj_tab.clear(); p.pj_owner.clear(); p.pj_tabs.clear(); p.pj_raw = p.pj_rsum = p.pj_plane_bytes = p.pj_plane0 = 0;
     for (uint32_t i = 0; i < W; i++) {
         WxPlan &pl = p.win[i];
         pl.group = -1; pl.r0 = pl.nr = pl.ncomp = 0;
@@ -511,13 +550,112 @@ static inline void wx_lag_fill(const WxLagIn *in, uint32_t Q, WxPlanned &p, WxLa
     p.nacc = p.lg_part + 2u * WXL_PART_WORDS * p.ntile;
 }
 
+/* ---- the projecting consumer ---- */
+static inline uint64_t wxp_length(uint64_t N, uint32_t H) { return H == 0 ? 0u : N / H + (N % H != 0); }
+/* frames * K * N * C of one window stays inside LINNE_AMD_PROJECT_MAX_PRODUCTS: formed in 128 bits */
+static inline bool wxp_products_fit(uint64_t frames, uint32_t K, uint32_t N, uint32_t C)
+{
+    return (unsigned __int128)frames * K * N * C <= (unsigned __int128)LINNE_AMD_PROJECT_MAX_PRODUCTS;
+}
+/* the output map (c, f, k) -> c * cs + f * fs + k * rs is injective by the header's rule: the three (stride, extent) pairs sorted by
+ * stride, pairs of extent 1 (or 0) left out, the smallest stride at least 1 and each later one at least the one before it times that
+ * one's extent */
+static inline bool wxp_injective(uint64_t cs, uint64_t C, uint64_t fs, uint64_t frames, uint64_t rs, uint64_t K)
+{
+    uint64_t st[3] = { cs, fs, rs }, ex[3] = { C, frames, K };
+    for (int a = 0; a < 3; a++) for (int b = a + 1; b < 3; b++) if (st[b] < st[a]) { const uint64_t s = st[a], e = ex[a]; st[a] = st[b]; ex[a] = ex[b]; st[b] = s; ex[b] = e; }
+    bool first = true; uint64_t ps = 0, pe = 0;
+    for (int a = 0; a < 3; a++) {
+        if (ex[a] <= 1u) continue;
+        if (first ? st[a] < 1u : (unsigned __int128)st[a] < (unsigned __int128)ps * pe) return false;
+        first = false; ps = st[a]; pe = ex[a];
+    }
+    return true;
+}
+/* what frames [first, first + n), n >= 1 and (first + n - 1) * H < N_s, of a stream of N_s samples read: the input range [lo, hi) inside
+ * the stream (hi > lo), and the words of a channel of the image, which holds the halos off either end too */
+struct WxpInput { uint64_t lo, hi, istride; };
+static inline WxpInput wxp_input(uint64_t first, uint64_t n, const struct LINNEAmdProjectSpec &s, uint64_t N_s)
+{
+    WxpInput r;
+    const uint64_t at = first * s.hop;                      /* (< N_s) */
+    r.lo = at > s.before ? at - s.before : 0u;
+    const unsigned __int128 hi = (unsigned __int128)(first + n - 1u) * s.hop + s.frame_len - s.before;
+    r.hi = hi > N_s ? N_s : (uint64_t)hi;
+    r.istride = ((n - 1u) * s.hop + s.frame_len + 3u) & ~(uint64_t)3u;
+    return r;
+}
+/* between wx_plan_count and wx_lists: the tables and the tiles the lists must have room for */
+static inline void wx_project_count(const WxRange *rg, uint32_t W, WxPlanned &p)
+{
+    std::map<std::tuple<const int16_t *, uint32_t, uint32_t>, uint32_t> seen;
+    p.pj_tab.assign(W, 0u); p.pj_owner.assign(W, 0u);
+    for (uint32_t i = 0; i < W; i++) {
+        if (p.win[i].group < 0) continue;
+        const struct LINNEAmdProjectSpec &s = *rg[i].pj;
+        p.rs_tiles += rg[i].x.shape.num_channels * ((rg[i].m_n + WXP_FRAMES - 1u) / WXP_FRAMES) * ((s.num_rows + WXP_ROWS - 1u) / WXP_ROWS);
+        const auto at = seen.emplace(std::make_tuple(s.basis, s.num_rows, s.frame_len), (uint32_t)p.pj_tabs.size());
+        if (at.second) {
+            WxProjTable t;
+            t.K = s.num_rows; t.N = s.frame_len; t.Kpad = (t.K + 15u) & ~15u; t.Npad = (t.N + 63u) & ~63u;
+            t.raw = p.pj_raw; t.planes = p.pj_plane_bytes;
+            p.pj_owner[i] = 1u; p.pj_tabs.push_back(t);
+            p.pj_raw += ((uint64_t)t.K * t.N + 7u) & ~(uint64_t)7u;         /* (every table 16-byte aligned) */
+            p.pj_rsum += t.Kpad;
+            p.pj_plane_bytes += 2u * (uint64_t)t.Kpad * t.Npad;
+        }
+        p.pj_tab[i] = at.first->second;
+    }
+}
+/* a window's project record, its tiles and (where it is the first to name it) its table and its rows' sums; the window record names
+ * the image.  Row k's sum is that of basis[k][n] - 128 over n < N: what the kernel's offset digits need (lnn_k_project.h) */
+static inline void wx_project_record(const WxRange &w, const struct LINNEAmdShape &shape, uint32_t i, uint32_t wi, WxPlanned &p,
+        WxWindow &ww, const WxProjLists &h)
+{
+    const struct LINNEAmdProjectSpec &s = *w.pj;
+    const uint32_t B = s.clip_bits ? s.clip_bits : 32u;
+    const WxProjTable &t = p.pj_tabs[p.pj_tab[i]];
+    WxProject &m = h.rec[wi];
+    memset(&m, 0, sizeof(m));
+    m.out = w.out; m.cstride = s.channel_stride; m.fstride = s.frame_stride; m.rstride = s.row_stride; m.fmt = s.format;
+    m.f_lo = w.m_lo; m.nframes = w.m_n;
+    m.img = p.nacc; m.istride = ((w.m_n - 1u) * s.hop + s.frame_len + 3u) & ~(uint64_t)3u;
+    m.planes = t.planes; m.raw = t.raw; m.rsum = 0;
+    for (uint32_t j = 0; j < p.pj_tab[i]; j++) m.rsum += p.pj_tabs[j].Kpad;
+    m.N = s.frame_len; m.H = s.hop; m.K = s.num_rows; m.Npad = t.Npad; m.Kpad = t.Kpad; m.shift = s.shift;
+    m.hi = (int32_t)(((uint64_t)1 << (B - 1u)) - 1u); m.lo = -m.hi - 1;
+    m.scale_bits = (127u - s.float_exp) << 23;            /* 2^-float_exp, float_exp <= 63 */
+    m.fidx = i; m.C = shape.num_channels;
+    p.nacc += m.istride * shape.num_channels;
+    /* the passes place the input range into the image: word j of a channel is stream sample f_lo * H - before + j */
+    ww.out = (void *)(uintptr_t)(sizeof(int32_t) * (m.img + (w.lo + s.before - w.m_lo * s.hop)));
+    ww.fmt = LINNE_AMD_PCM_S32; ww.stride = m.istride; ww.sstride = 1u;
+    for (uint32_t c = 0; c < shape.num_channels; c++)
+        for (uint64_t f0 = 0; f0 < w.m_n; f0 += WXP_FRAMES)
+            for (uint32_t k0 = 0; k0 < s.num_rows; k0 += WXP_ROWS) {
+                assert(p.ntile < p.rs_tiles);
+                WxProjTile &tl = h.tile[p.ntile++];
+                tl.f0 = f0; tl.win = wi; tl.ch = c; tl.k0 = k0; tl.reserved = 0u;
+            }
+    if (p.pj_owner[i]) {
+        h.tab[p.pj_tab[i]] = t;
+        memcpy(h.raw + t.raw, s.basis, sizeof(int16_t) * (size_t)t.K * t.N);
+        for (uint32_t k = 0; k < t.Kpad; k++) {
+            int32_t sum = 0;
+            if (k < t.K) for (uint32_t n = 0; n < t.N; n++) sum += (int32_t)s.basis[(size_t)k * t.N + n] - 128;
+            h.rsum[m.rsum + k] = sum;
+        }
+    }
+}
+
 /* step 2: the records, into lists with room for nlive window (and bucket) records, total_rec block records and total_crec COMPRESS
  * entries; h_side NULL for WX_NO_BUCKETS; h_mix, where it is given, gets a mix record per window from the windows' mix specs; h_ov,
  * where it is given, has a record per window of the CALL (W of them, zeroed by the caller) and gets those of the live ones; h_lag
  * likewise */
 static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_frames, WxBucketing bucketing, WxPlanned &p,
         WxWindow *h_win, WxBucket *h_side, WxBlock *h_rec, uint32_t *h_crec, WxMix *h_mix = NULL,
-        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL, WxOvSource *h_ov = NULL, WxLagImage *h_lag = NULL)
+        WxResample *h_rs = NULL, WxTile *h_tile = NULL, uint32_t *h_coef = NULL, WxOvSource *h_ov = NULL, WxLagImage *h_lag = NULL,
+        const WxProjLists *h_pj = NULL)
 {
     for (uint32_t g = 0; g < p.ngroups; g++) {
         const struct LINNEAmdShape &shape = rg[p.gwin[g]].x.shape;
@@ -563,6 +701,7 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
             if (h_rs) wx_resample_record(w, shape, i, wi, p, ww, h_rs[wi], h_tile, h_coef);
             if (h_ov) wx_overlay_source(w, shape, p, ww, h_ov[i]);
             if (h_lag) wx_lag_image(w, shape, p, ww, h_lag[i]);
+            if (h_pj) wx_project_record(w, shape, i, wi, p, ww, *h_pj);
             if (bucketing == WX_BITMASK) {
                 WxBucket &m = h_side[wi];
                 memset(&m, 0, sizeof(m));
@@ -614,6 +753,10 @@ static inline void wx_plan_fill(const WxRange *rg, uint32_t W, uint32_t group_fr
         close(0);
     }
     if (bucketing == WX_BITMASK) { p.nmask = p.nacc; p.nacc += wxq_chunk_units(p.nout); }
+    if (h_pj) {                         /* the digit planes lie behind the images, 16-byte aligned, in the images' 32-bit words */
+        p.pj_plane0 = (p.nacc + 3u) & ~(uint64_t)3u;
+        p.nacc = p.pj_plane0 + (p.pj_plane_bytes + 3u) / 4u;
+    }
 }
 
 #endif

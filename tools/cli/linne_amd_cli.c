@@ -48,6 +48,10 @@
  *     all of them together, on the device (one LINNEAmd_LagWindowsDevice probe at the lags -MAX_LAG .. MAX_LAG, 4096 unless given; the
  *     needle N samples of IN from FIRST on, unless given the whole stream cut to the call's products limit): what Context.align_streams
  *     returns, compared as exactly.
+ *   - -F / --spectrum N_FFT[,HOP[,FIRST,N]] IN.lnn prints the exact power spectrum of IN, a line per bin: the bin, its frequency in Hz and
+ *     per channel the sum over the frames of re^2 + im^2 as an unsigned 128-bit decimal (LINNEAmd_ProjectDesign's Hann basis of all
+ *     N_FFT / 2 + 1 bins, LINNEAmd_ProjectWindowsDevice on frames centred HOP apart -- N_FFT / 4 unless given --, shift 15, over the
+ *     frames that begin in the N samples from FIRST on, the whole stream unless given): what Context.spectrum_streams returns.
  */
 #include "linne_decoder.h"
 #include "linne_encoder.h"
@@ -64,9 +68,9 @@
 #include <time.h>
 
 struct options {
-    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, join, align, no_crc, learning, block_at_a_time, help, version, quiet;
+    int encode, decode, repair, verify, compare, measure, digest, silence, levels, relate, remix, resample, join, align, spectrum, no_crc, learning, block_at_a_time, help, version, quiet;
     long mode, af_iterations;
-    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec, *join_spec, *align_spec;
+    const char *batch_dir, *silence_spec, *levels_spec, *remix_spec, *resample_spec, *join_spec, *align_spec, *spectrum_spec;
     const char *files[4096];
     int num_files;
 };
@@ -102,6 +106,8 @@ static void usage(const char *argv0)
            "  -J, --join OTHER.lnn[,OVERLAP]         Write IN followed by OTHER.lnn, crossfaded over OVERLAP (0) samples \n"
            "  -A, --align OTHER.lnn[,MAX_LAG[,FIRST,N]]  Print the lag at which OTHER.lnn best matches IN (-A OTHER.lnn[,MAX_LAG[,FIRST,N]] IN.lnn): \n"
            "                                         lags -MAX_LAG .. MAX_LAG (4096), the needle N samples of IN from FIRST on \n"
+           "  -F, --spectrum N_FFT[,HOP[,FIRST,N]]   Print the exact power spectrum of IN (-F N_FFT[,HOP[,FIRST,N]] IN.lnn): per bin its frequency and, per channel, \n"
+           "                                         the sum of re^2 + im^2 over the Hann frames HOP (N_FFT / 4) apart that begin in N samples from FIRST on \n"
            "  -m, --mode N                           Specify compress mode: 0(fast), ..., 7(high compression) (default:0) \n"
            "  -l, --enable-learning                  (not offered by the MI355X path) \n"
            "  -a, --auxiliary-function-iteration N   (not offered by the MI355X path unless N is 0) \n"
@@ -160,6 +166,7 @@ static void parse(int argc, char **argv, struct options *o)
         else if (take_value(argc, argv, &i, "-Z", "--resample", &v)) { o->resample = 1; o->resample_spec = v; }
         else if (take_value(argc, argv, &i, "-J", "--join", &v)) { o->join = 1; o->join_spec = v; }
         else if (take_value(argc, argv, &i, "-A", "--align", &v)) { o->align = 1; o->align_spec = v; }
+        else if (take_value(argc, argv, &i, "-F", "--spectrum", &v)) { o->spectrum = 1; o->spectrum_spec = v; }
         else if (take_value(argc, argv, &i, "", "--batch", &v)) o->batch_dir = v;
         else if (a[0] == '-' && a[1] != '\0') { fprintf(stderr, "%s: unknown option %s \n", argv[0], a); exit(1); }
         else if (o->num_files < (int)(sizeof(o->files) / sizeof(o->files[0]))) o->files[o->num_files++] = a;
@@ -1031,6 +1038,115 @@ done:
     return rc;
 }
 
+/* "512", "512,128", "512,128,0,220500": the frame length, then optionally the hop (a quarter of the frame unless given), then optionally
+ * the first sample and the sample count, which come together -> *n_fft, *hop, *has_range, *first, *n.  0, or a message in err */
+static int parse_spectrum(const char *text, uint32_t *n_fft, uint32_t *hop, int *has_range, uint64_t *first, uint64_t *n, char *err, size_t cap)
+{
+    unsigned long long v[4];
+    int count = 0;
+    const char *p = text;
+    *has_range = 0; *first = *n = 0;
+    for (;;) {
+        char *end;
+        if (!(*p >= '0' && *p <= '9')) {
+            snprintf(err, cap, "spectrum spec: %s is expected at \"%s\"", count == 0 ? "a frame length in samples" : count == 1 ? "a hop in samples" : "a sample number", p);
+            return 1;
+        }
+        errno = 0;
+        v[count] = strtoull(p, &end, 10);
+        if (errno != 0) { snprintf(err, cap, "spectrum spec: %.*s is outside 64 bits", (int)(end - p), p); return 1; }
+        count++;
+        if (*end == '\0') break;
+        if (*end != ',' || count == 4) { snprintf(err, cap, "spectrum spec: malformed at \"%s\"", end); return 1; }
+        p = end + 1;
+    }
+    if (count == 3) { snprintf(err, cap, "spectrum spec: the first sample and the sample count come together, behind the hop"); return 1; }
+    /* every bin of the frame is printed: 2 * (N_FFT / 2 + 1) rows within LINNE_AMD_PROJECT_MAX_ROWS */
+    if (v[0] < 1u || v[0] > LINNE_AMD_PROJECT_MAX_ROWS - 1u) { snprintf(err, cap, "spectrum spec: a frame length of %llu is outside 1 .. %u", v[0], (unsigned)(LINNE_AMD_PROJECT_MAX_ROWS - 1u)); return 1; }
+    *n_fft = (uint32_t)v[0];
+    *hop = *n_fft / 4u ? *n_fft / 4u : 1u;
+    if (count >= 2) {
+        if (v[1] < 1u || v[1] > LINNE_AMD_PROJECT_MAX_HOP) { snprintf(err, cap, "spectrum spec: a hop of %llu is outside 1 .. %u", v[1], (unsigned)LINNE_AMD_PROJECT_MAX_HOP); return 1; }
+        *hop = (uint32_t)v[1];
+    }
+    if (count == 4) { *first = v[2]; *n = v[3]; *has_range = 1; }
+    return 0;
+}
+
+/* an unsigned 128-bit integer in decimal */
+static void print_u128(unsigned __int128 v)
+{
+    char text[40];
+    int at = 39;
+    text[at] = '\0';
+    do { text[--at] = (char)('0' + (int)(v % 10u)); v /= 10u; } while (v != 0);
+    fputs(text + at, stdout);
+}
+
+/* -F: the spec and the header are checked on the host; then the stream goes to the device, LINNEAmd_StreamIndexCreate, and
+ * LINNEAmd_ProjectWindowsDevice on the designed basis, in runs of frames that fit the call's products limit and a table of 256 MiB;
+ * the host adds re^2 + im^2 per bin in 128 bits */
+static int spectrum_one(const char *spec_text, const char *in_path)
+{
+    uint8_t *buf = NULL;
+    int16_t *basis = NULL;
+    int32_t *table = NULL;
+    unsigned __int128 *sums = NULL;
+    uint32_t size = 0, n_fft, hop, bins, K, C, c, j;
+    struct resident r;
+    struct LINNEAmdWindow w;
+    struct LINNEAmdProjectSpec sp;
+    struct LINNEHeader h;
+    char err[512];
+    uint64_t first, n, f0, f1, run, f, most;
+    int has_range, ret, stage, rc = 1;
+    memset(&r, 0, sizeof(r));
+    if (parse_spectrum(spec_text, &n_fft, &hop, &has_range, &first, &n, err, sizeof(err)) != 0) { fprintf(stderr, "%s \n", err); return 1; }
+    if (read_file(in_path, &buf, &size) != 0) { fprintf(stderr, "Failed to open %s. \n", in_path); return 1; }
+    if ((ret = LINNEDecoder_DecodeHeader(buf, size, &h)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to get header information: %d \n", ret); goto done; }
+    if (!has_range) { first = 0; n = h.num_samples; }
+    if (first > h.num_samples || n > h.num_samples - first) { fprintf(stderr, "spectrum spec: %llu samples from %llu on in a stream of %llu \n", (unsigned long long)n, (unsigned long long)first, (unsigned long long)h.num_samples); goto done; }
+    bins = n_fft / 2u + 1u; K = 2u * bins; C = h.num_channels;
+    f0 = (first + hop - 1u) / hop; f1 = (first + n + hop - 1u) / hop;       /* the frames f with first <= f * hop < first + n */
+    most = LINNE_AMD_PROJECT_MAX_PRODUCTS / ((uint64_t)K * n_fft * C);
+    if (most > ((uint64_t)1 << 26) / ((uint64_t)K * C)) most = ((uint64_t)1 << 26) / ((uint64_t)K * C);
+    if (most < 1u) most = 1u;
+    run = f1 - f0 < most ? f1 - f0 : most;
+    if (!(basis = malloc(sizeof(*basis) * (size_t)K * n_fft)) || !(sums = calloc((size_t)C * bins, sizeof(*sums))) || !(table = malloc(sizeof(*table) * (size_t)(C * (run ? run : 1u) * K)))) { fprintf(stderr, "Failed to allocate the tables. \n"); goto done; }
+    if ((ret = LINNEAmd_ProjectDesign(n_fft, bins, 1, basis)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to design the basis: %d \n", ret); goto done; }
+    if ((stage = resident_open(&r, buf, size, h.num_samples, sizeof(int32_t) * C * (run ? run : 1u) * K, "the stream", err, sizeof(err))) != 0) { fprintf(stderr, stage == 3 ? "Failed to project! %s \n" : "%s \n", err); goto done; }
+    for (f = f0; f < f1; f += run) {
+        const uint64_t cnt = f1 - f < run ? f1 - f : run;
+        memset(&sp, 0, sizeof(sp));
+        sp.frame_len = n_fft; sp.hop = hop; sp.num_rows = K; sp.before = n_fft / 2u; sp.shift = 15; sp.format = LINNE_AMD_PCM_S32;
+        sp.channel_stride = cnt * K; sp.frame_stride = K; sp.row_stride = 1; sp.basis = basis;
+        w = r.w; w.first_sample = f; w.num_samples = cnt; w.d_pcm = r.d_extra; w.pcm_stride = 0;
+        if ((ret = LINNEAmd_ProjectWindowsDevice(r.ctx, &w, &sp, 1, 0)) != LINNE_APIRESULT_OK) { fprintf(stderr, "Failed to project! ret:%d (%s) \n", ret, LINNEAmd_GetLastError(r.ctx)); goto done; }
+        if (sp.saturated) { fprintf(stderr, "Failed to project! a bin does not fit 32 bits at shift 15: the sums would not be exact \n"); goto done; }
+        if (hipMemcpy(table, r.d_extra, sizeof(*table) * (size_t)(C * cnt * K), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "Failed to fetch the table. \n"); goto done; }
+        for (c = 0; c < C; c++) {
+            uint64_t g;
+            for (g = 0; g < cnt; g++) {
+                const int32_t *row = table + ((size_t)c * cnt + g) * K;
+                for (j = 0; j < bins; j++) {
+                    const int64_t re = row[2u * j], im = row[2u * j + 1u];
+                    sums[(size_t)c * bins + j] += (unsigned __int128)(uint64_t)(re * re) + (unsigned __int128)(uint64_t)(im * im);
+                }
+            }
+        }
+    }
+    for (j = 0; j < bins; j++) {
+        printf("bin %u %.6f Hz:", j, (double)j * (double)h.sampling_rate / (double)n_fft);
+        for (c = 0; c < C; c++) { putchar(' '); print_u128(sums[(size_t)c * bins + j]); }
+        printf(" \n");
+    }
+    rc = 0;
+done:
+    resident_close(&r);
+    free(table); free(sums); free(basis); free(buf);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     struct options o;
@@ -1039,6 +1155,10 @@ int main(int argc, char **argv)
     parse(argc, argv, &o);
     if (o.help) { usage(argv[0]); return 0; }
     if (o.version) { printf("LINNE -- LInear-predictive Neural Net Encoder Version.%d (liblinne_amd, MI355X) \n", LINNE_CODEC_VERSION); return 0; }
+    if (o.spectrum) {
+        if (o.align || o.join || o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.resample || o.batch_dir || o.num_files != 1) { fprintf(stderr, "%s: -F takes a frame length and an input file name and no other mode. \n", argv[0]); return 1; }
+        return spectrum_one(o.spectrum_spec, o.files[0]);
+    }
     if (o.align) {
         if (o.join || o.encode || o.decode || o.repair || o.verify || o.compare || o.measure || o.digest || o.silence || o.levels || o.relate || o.remix || o.resample || o.batch_dir || o.num_files != 1) { fprintf(stderr, "%s: -A takes another stream's file name and an input file name and no other mode. \n", argv[0]); return 1; }
         return align_one(o.align_spec, o.files[0]);
