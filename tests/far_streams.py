@@ -381,6 +381,48 @@ def far_lag_table(pcm_a, first_a, n, pcm_b, first_b, lag_first, num_lags, pairs)
     return t, a_sq
 
 
+# ---- project: the frames that touch an island, cut densely ----
+def far_project(pcm, first, n, basis, hop, before=0, shift=0, clip_bits=0, f32=False, float_exp=0):
+    """project_refs.expected_project for frames [first, first + n) of a stream of any length -> (idx, rows, saturated): idx the frames,
+    counted from `first` and ascending, that read a sample of an island; rows what the call stores for them, (C, len(idx), K) int32 or
+    float32.  Every other frame of the window reads zeros alone, and its row is zeros: a sum of 0 stays 0 under the rounding shift (the
+    half that is added is shifted out again) and under any clip, and never saturates.  Frame f reads samples f * hop - before + (0 .. N);
+    the frames that touch an island are runs of consecutive ones, and every run is cut from `padded` in pieces of at most 256 frames
+    and goes through project_refs.projected_values as a stream of its own that begins at the piece's first sample"""
+    from project_refs import projected_values
+    first, n, hop, before = int(first), int(n), int(hop), int(before)
+    basis = np.asarray(basis, dtype=np.int64)
+    K, N = basis.shape
+    touched = set()
+    for s, p in pcm.islands:
+        e = s + p.shape[1]
+        lo = max((s - N + before) // hop + 1, first)                    # f * hop - before + N > s
+        hi = min(-(-(e + before) // hop), first + n)                    # f * hop - before < e
+        touched.update(range(lo, hi))
+    idx = np.array(sorted(touched), dtype=np.int64)
+    rows = np.zeros((pcm.nch, idx.shape[0], K), dtype=np.int64)
+    sat, at = False, 0
+    while at < idx.shape[0]:
+        cnt = 1
+        while at + cnt < idx.shape[0] and cnt < 256 and idx[at + cnt] == idx[at] + cnt and cnt * hop + N <= SLICE_LIMIT:
+            cnt += 1
+        start = int(idx[at]) * hop - before
+        x = np.stack([padded(pcm, ch, start, (cnt - 1) * hop + N) for ch in range(pcm.nch)])
+        rows[:, at:at + cnt], s = projected_values(x, 0, cnt, basis, hop, 0, shift, clip_bits)
+        sat, at = sat or s, at + cnt
+    idx -= first
+    if not f32:
+        return idx, rows.astype(np.int32), sat
+    return idx, (rows.astype(np.int32).astype(np.float32) * np.float32(2.0 ** -float_exp)).astype(np.float32), sat
+
+
+def dense_project(nch, n, K, idx, rows):
+    """far_project's answer as the table (C, n, K) of a window small enough to hold"""
+    out = np.zeros((nch, n, K), dtype=rows.dtype)
+    out[:, idx] = rows
+    return out
+
+
 # ---- the streams of the far tests ----
 ISLAND = ((1024, COMPRESS), (777, COMPRESS), (300, RAW), (33, COMPRESS), (1024, COMPRESS))
 ISLAND_SAMPLES = sum(n for n, _ in ISLAND)

@@ -146,6 +146,39 @@ def test_far_lags_equal_the_dense_reference(reduced):
     assert nonzero >= 12
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_far_project_equals_the_dense_reference(reduced, name):
+    """far_streams.far_project against project_refs.expected_project on the oracle's whole decode: hops from 1 to beyond the frame and
+    65536, `before` at 0 and N - 1, windows that start before an island, that hold both, that end behind the stream's last block and in
+    the header's tail, and one of silence alone; every frame outside the returned indexes is zeros in the dense reference"""
+    from project_refs import expected_project, project_length
+    _, d, full = reduced[name]
+    (a, _, _, pa), (b, _, _, pb) = d.islands
+    la, T = pa.shape[1], d.total
+    rng = np.random.default_rng(77)
+    loud, k = 0, 0
+    for N, K in ((70, 5), (1, 2), (512, 3)):
+        basis = rng.integers(-32768, 32768, (K, N)).astype(np.int16)
+        basis[0] = 32767
+        for H in (1, 3, N, N + 5, 1000, 65536):
+            F = project_length(T, H)
+            spans = [(max((a - 300) // H, 0), min(-(-(la + 600) // H), 900)), ((a + la - 100) // H, min(40, F - (a + la - 100) // H)), (max(F - 50, 0), min(F, 50)),
+                     ((d.covered - 200) // H, min(-(-400 // H), F - (d.covered - 200) // H)), (b // H, min(-(-(la + 3100) // H), 700, F - b // H)), (0, min(F, 30))]
+            if H >= 1000:
+                spans.append((0, F))                            # both islands and all the silence in one window
+            for first, n in spans:
+                for before in (0, N - 1):
+                    shift, clip, f32 = (0, 15, 31, 7)[k % 4], (0, 16, 24)[k % 3], k % 5 == 1
+                    idx, rows, sat = fs.far_project(d.pcm, first, n, basis, H, before, shift, clip, f32, 31 if f32 else 0)
+                    want, wsat = expected_project(full, first, n, basis, H, before, shift, clip, f32, 31 if f32 else 0)
+                    got = fs.dense_project(d.nch, n, K, idx, rows)
+                    assert got.dtype == want.dtype and got.tobytes() == want.tobytes() and sat == wsat, (name, N, K, H, first, n, before)
+                    assert idx.shape[0] <= n and (np.diff(idx) > 0).all() and (idx.shape[0] == 0 or (0 <= idx[0] and idx[-1] < n))
+                    loud += bool(rows.any())
+                    k += 1
+    assert loud >= 60
+
+
 def test_crc32_zeros_against_zlib():
     starts = (0, 1, 0xFFFFFFFF, 0xDEADBEEF, zlib.crc32(b"far streams"))
     for n in (0, 1, 255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 24) + 1):

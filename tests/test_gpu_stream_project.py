@@ -2,7 +2,8 @@
 include/linne_amd.h LINNEAmd_ProjectWindowsDevice).  Every expected element is computed with numpy int64 (project_refs.expected_project)
 from the oracle's decode of the same bytes, never from the library under test, and everything must be equal: words between sentinels, no
 tolerance -- the float32 path is a conversion and a multiplication by a power of two.  Streams hold 3 to 6 blocks of 1024 samples, or 21
-blocks of 33."""
+blocks of 33; the tests from 7 on build streams whose decode is chosen: planted values at the edges of the kernel's 2, 3 and 4 sample
+planes, constant full scale under 4096-sample rows of full scale, and a sparse mono stream long enough for 17 frames at hop 65536."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,9 @@ import pytest
 
 import linne_amd
 import synth_records as sr
-from project_refs import expected_project, project_length, projected_values
+import far_streams as fs
+import project_edges as pe
+from project_refs import basis_digits, expected_project, project_length, projected_values, sample_digits, sample_planes
 from signals import music
 import stream_consumers as sc
 from stream_consumers import DECODE_KINDS, KIND, Stream, encoded, last_error
@@ -408,3 +411,133 @@ def test_python_forms(ctx, streams):
         want = [[sum(int(y[c, f, 2 * j]) ** 2 + int(y[c, f, 2 * j + 1]) ** 2 for f in range(y.shape[1])) for j in range(n_fft // 2 + 1)] for c in range(x.nch)]
         assert g == want and all(isinstance(v, int) for row in g for v in row)
     assert ctx.spectrum_streams([], 64, 16) == []
+
+
+# 7 ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def edge_streams(ctx, oracle, wide):
+    """the streams of tests/project_edges.py on the device: two whose chosen signal the oracle encodes -- the codec is lossless, and
+    encoded() asserts that the decode is the signal --, one written block by block with synth_records, whose decode under the oracle is
+    asserted to be zeros but for the four 4-plane edge values; and the "wide values" stream"""
+    out = {}
+    for name in pe.PLANTS:
+        bits, x = pe.planted_signal(name)
+        out[name] = encoded(ctx, oracle, x, bits, 5, bits == 16, name)
+        assert out[name].bl[-1][2] == RAW
+    data, x = pe.crafted_stream()
+    out["crafted"] = Stream(ctx, oracle, data, "crafted")
+    assert np.array_equal(out["crafted"].full, x) and np.count_nonzero(x) == 4
+    yield dict(out, wide=wide)
+    for t in out.values():
+        t.index.close()
+
+
+def test_plane_counts_at_their_edges(ctx, edge_streams):
+    """values at the edges of the plane rule -- 32767, -32768 (2 planes), 32768, -32769, 2^23 - 1, -2^23 (3), 2^23, -2^23 - 1, INT32_MAX,
+    INT32_MIN (4) --, each the only one of its width among the values its tile reads: at the tile's first frame's first sample, at its
+    last frame's last sample, in a ragged last tile, and -- where the hop is beyond the frame -- in the gap between two frames, where
+    it must neither widen the tile nor change an output.  The library does not report the plane count it chose: the check is that every
+    element equals the reference's, which a tile cut into too few planes, or a scan that misses the value, cannot give.  The premises --
+    which count each tile must choose, under which of the kernel's two scans, where its widest value lies -- are project_edges.py's,
+    computed from the oracle's decode with project_refs.sample_planes, asserted here and, without a GPU, in test_stream_project_cpu.py"""
+    t = edge_streams
+    windows, counts = pe.edge_windows({name: x.full for name, x in t.items()}, found=[("wide", ch, p) for ch, p in pe.WIDE_AT])
+    pe.assert_coverage(windows, counts)
+    bases = {"one": np.array([[1], [-1], [32767], [-32768]], dtype=np.int16), "b70": random_basis(np.random.default_rng(12), 19, 70)}
+    items = [item(t[w["stream"]], w["first"], w["n"], bases[w["basis"]], w["hop"], before=w["before"], shift=w["shift"], order=("fk", "kf")[k % 2], pad=k % 3) for k, w in enumerate(windows)]
+    assert all(it["basis"].shape[1] == w["N"] for it, w in zip(items, windows))
+    held(ctx, items, group_frames=(0, 2))
+
+
+# 8 ------------------------------------------------------------------------------------------------------------------------------
+FULL = {"min16": (16, -32768), "max16": (16, 32767), "min24": (24, -(1 << 23)), "max24": (24, (1 << 23) - 1)}
+
+
+@pytest.fixture(scope="module")
+def constant(ctx, oracle):
+    """mono streams of 5 blocks whose every sample is one end of their width's range (encoded() asserts the decode)"""
+    out = {name: encoded(ctx, oracle, np.full((1, 5 * S), v, dtype=np.int32), bits, 0, False, name) for name, (bits, v) in FULL.items()}
+    yield out
+    for t in out.values():
+        t.index.close()
+
+
+def test_accumulators_at_their_worst_case(ctx, constant):
+    """frames of 4096 samples of constant full scale under rows of constant and alternating full scale: the largest sums a pair of
+    digit planes can have.  A digit product is at most (-128) * (-128) = 2^14, and 4096 of them are 2^26 -- reached here exactly, by
+    the low and by the high planes of -32768 (and of -2^23) under a row of -32768; no pair goes beyond it, so every pair's int32
+    accumulator holds.  The bound is per pair of planes and the same whatever the plane count, so streams of 2 and of 3 planes
+    suffice.  At shift 0 every sum leaves int32 and `saturated` is set; at shift 31 the values themselves show"""
+    rows = [[-32768] * 4096, [32767] * 4096, [-129] * 4096, [127] * 4096, [128] * 4096, [32767, -32768] * 2048, [-32768, 32767] * 2048]
+    basis = np.array(rows, dtype=np.int16)
+    worst = 0
+    for name, (bits, v) in FULL.items():
+        assert (constant[name].full == v).all() and constant[name].ns >= 4096 + 63
+        P = sample_planes(v)
+        assert P == (2 if bits == 16 else 3)
+        xd = sample_digits(v, P)
+        for row in rows:
+            sums = [sum(basis_digits(c)[a] for c in row) * xd[b] for a in range(2) for b in range(P)]      # (the frame is constant: the sum over n factors)
+            assert all(abs(q) <= 1 << 26 for q in sums)
+            worst = max(worst, max(abs(q) for q in sums))
+            if v < 0 and row[0] == row[1] == -32768:
+                assert sums.count(1 << 26) == 2 * P                  # every pair of planes: all digits are -128
+            assert abs(sum(row) * v) > 1 << 31 or row[0] != row[1]                  # a constant row's result leaves int32 (an alternating row's is -+2048 v)
+    assert worst == 1 << 26
+    items = [item(constant[name], first, n, basis, H, shift=shift, order=order) for name in FULL for shift in (0, 31)
+             for first, n, H, order in ((0, 65, 1, "fk"), (3, 17, 64, "kf"))]
+    held(ctx, items, group_frames=(0, 2))
+    assert all(reference(it)[1] == (it["shift"] == 0) for it in items)
+
+
+# 9 ------------------------------------------------------------------------------------------------------------------------------
+def test_tables_are_told_apart_by_pointer_rows_and_frame_length(ctx, streams):
+    """windows of one call share one int16 array's pointer under three shapes -- (K, N), its first K - 3 rows, and the same words as
+    rows of M -- beside an array of equal content at another address: each window's values are those of its own table"""
+    rng = np.random.default_rng(21)
+    K, N, M = 12, 40, 30
+    base = random_basis(rng, K, N)
+    views = [base, base[:K - 3], base.reshape(K * N // M, M), base.copy()]
+    items = []
+    for k in range(12):
+        t, b = streams[(2, 3)[k % 2]], views[(k + k // 4) % 4]
+        H = (1, 7, 45)[k % 3]
+        items.append(item(t, 5 * k, min(70 - k, project_length(t.ns, H) - 5 * k), b, H, before=k % min(b.shape[1], 29), shift=12, clip_bits=(0, 24)[k % 2], order=("fk", "kf")[(k // 2) % 2], pad=k % 2))
+    ptr = lambda it: it["basis"].ctypes.data
+    assert {(ptr(it), it["basis"].shape) for it in items} == {(base.ctypes.data, (12, 40)), (base.ctypes.data, (9, 40)), (base.ctypes.data, (16, 30)), (views[3].ctypes.data, (12, 40))}
+    assert views[3].ctypes.data != base.ctypes.data and np.array_equal(views[3], base)
+    # the premise: a window read with the table of another shape at the same pointer has other values -- the first window of the
+    # reshaped view against the whole array's first 30 columns, and the row the shorter view lacks is no row of zeros
+    j = next(i for i, it in enumerate(items) if it["basis"] is views[2])
+    it = items[j]
+    other = expected_project(it["t"].full, it["first"], it["n"], base[:, :M], it["hop"], it["before"], it["shift"], it["clip"])[0]
+    assert not np.array_equal(reference(it)[0][:, :, :K], other) and base[K - 3:].any()
+    held(ctx, items, group_frames=(0, 3))
+
+
+# 10 -----------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sparse(ctx, oracle):
+    """a mono stream of 17 * 65536 - 100 samples -- 17 frames at hop 65536 -- as tests/far_streams.py builds them: SILENT blocks and two
+    islands of sound, one under frame 3 and one under frame 9 of that hop; its decode is small enough to hold whole"""
+    stream, d = fs.far_stream(oracle, 1, 16, 0, False, [(3 * 65536 - 1000, list(fs.ISLAND), 801), (9 * 65536 - 2000, list(fs.ISLAND), 802)], 17 * 65536 - 100)
+    dev = sc.to_device(stream)
+
+    class Track:
+        name, nch, ns, full = "sparse mono", 1, d.total, d.pcm.dense()
+    Track.dev, Track.index = dev, ctx.index_stream(dev)
+    assert Track.full.shape == (1, 17 * 65536 - 100) and Track.full[0, 3 * 65536:3 * 65536 + 2000].any() and Track.full[0, 9 * 65536:9 * 65536 + 1000].any()
+    yield Track
+    Track.index.close()
+
+
+def test_the_largest_frame_with_the_most_rows(ctx, sparse):
+    """frame_len 4096 with num_rows 2048 -- each runs elsewhere with a small partner only --: 17 frames of one channel, at the largest
+    hop, where every frame is an image region of its own, and at hop 1"""
+    basis = random_basis(np.random.default_rng(31), 2048, 4096)
+    assert basis.shape == (linne_amd.PROJECT_MAX_ROWS, linne_amd.PROJECT_MAX_FRAME) and project_length(sparse.ns, 65536) == 17
+    items = [item(sparse, 0, 17, basis, 65536, before=1000, shift=14), item(sparse, 3 * 65536 - 3000, 17, basis, 1, before=4095, shift=14, order="kf", pad=1),
+             item(sparse, 9 * 65536 - 2000 + fs.ISLAND_SAMPLES - 10, 17, basis, 1, before=0, shift=0, clip_bits=16)]
+    held(ctx, items, group_frames=(0, 2))
+    y = reference(items[0])[0]
+    assert [bool(y[0, f].any()) for f in range(17)] == [f in (3, 9) for f in range(17)]       # the two islands' frames, silence between

@@ -17,7 +17,7 @@ import linne_amd
 from signals import music
 from test_cli_cpu import CLI
 from project_refs import (INT32_MAX, INT32_MIN, basis_digits, dot_by_digits, expected_project, frames_of, project_length, projected_values,
-                          sample_digits, sample_mask, sample_planes)
+                          s8, sample_digits, sample_mask, sample_planes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "linne_amd", "csrc")
@@ -243,6 +243,53 @@ def test_digits_recombine_exactly_and_fit_int8():
             assert dot_by_digits(row, xs, P) == sum(a * b for a, b in zip(row, xs)), (P, row[:3])
 
 
+def test_digit_sums_at_the_plane_edges_and_at_full_scale():
+    """what tests/test_gpu_stream_project.py plants and what it fills frames with: at every edge of the plane rule the digits of the
+    value's own plane count, and of every larger one, give the exact product with the rows of the one-sample basis, and one plane
+    fewer cannot hold the value; frames of 4096 samples of constant full scale under rows of full scale sum exactly"""
+    edges = [32767, -32768, 32768, -32769, (1 << 23) - 1, -(1 << 23), 1 << 23, -(1 << 23) - 1, INT32_MAX, INT32_MIN]
+    assert [sample_planes(v) for v in edges] == [2, 2, 3, 3, 3, 3, 4, 4, 4, 4]
+    for v in edges:
+        need = sample_planes(v)
+        for P in range(need, 5):
+            for c in (1, -1, 32767, -32768):
+                assert dot_by_digits([c], [v], P) == c * v, (v, P, c)
+        if need > 2:                                            # cut into one plane fewer, the digits are another value's
+            d = (v & 0xFFFFFFFF) ^ sample_mask(need - 1)
+            low = sum(s8((d >> (8 * b)) & 255) << (8 * b) for b in range(need - 1)) + sample_mask(need - 1)
+            assert low != v and (low - v) % (1 << (8 * (need - 1))) == 0, (v, low)
+    rows = [[-32768] * 4096, [32767] * 4096, [-129] * 4096, [127] * 4096, [128] * 4096, [32767, -32768] * 2048, [-32768, 32767] * 2048]
+    for v in (-32768, 32767, -(1 << 23), (1 << 23) - 1):
+        P = sample_planes(v)
+        for row in rows:
+            assert dot_by_digits(row, [v] * 4096, P) == sum(row) * v, (v, row[:2])
+            pairs = [sum(basis_digits(c)[a] * sample_digits(v, P)[b] for c in row) for a in range(2) for b in range(P)]
+            assert max(abs(q) for q in pairs) <= 1 << 26 and (max(pairs) == 1 << 26) == (v < 0 and row[0] == row[1] == -32768), (v, row[:2], pairs)
+
+
+def test_plane_edge_windows_and_their_premises(oracle):
+    """tests/project_edges.py without a GPU: the chosen signals survive the oracle's encoder and decoder, the crafted stream decodes to
+    zeros but for the four 4-plane edge values, and the windows of the GPU test have the premises it rests on"""
+    import project_edges as pe
+    import synth_records as sr
+    from test_stream_relate_cpu import WIDE_SHAPE, wide_cases
+    decodes = {}
+    for name in pe.PLANTS:
+        bits, x = pe.planted_signal(name)
+        ret, full, _ = oracle.decode_whole(bytes(oracle.encode_whole(x, bits, 44100, 1024, 5, bits == 16)))
+        assert ret == OK and np.array_equal(full, x)
+        decodes[name] = x
+    data, x = pe.crafted_stream()
+    ret, full, _ = oracle.decode_whole(bytes(data))
+    assert ret == OK and np.array_equal(full, x) and sorted(int(v) for v in x[x != 0]) == [INT32_MIN, -(1 << 23) - 1, 1 << 23, INT32_MAX]
+    ret, full, _ = oracle.decode_whole(bytes(sr.case_stream(WIDE_SHAPE, wide_cases())))
+    assert ret == OK
+    decodes["crafted"], decodes["wide"] = x, np.ascontiguousarray(full, dtype=np.int32)
+    windows, counts = pe.edge_windows(decodes, found=[("wide", ch, p) for ch, p in pe.WIDE_AT])
+    pe.assert_coverage(windows, counts)
+    assert len(windows) >= 200 and all(w["first"] + w["n"] <= project_length(decodes[w["stream"]].shape[1], w["hop"]) for w in windows)
+
+
 # ---- the plan ------------------------------------------------------------------------------------------------------------------
 PROGRAM = r"""
 #include <stdio.h>
@@ -423,18 +470,62 @@ def test_plan_input_ranges_images_tables_and_tiles(programs, gf):
         assert mine and min(b[2] for b in mine) <= row[1] < min(b[2] for b in mine) + 64 and max(b[2] for b in mine) < row[2], k
 
 
+# ---- the plan at the positions and bounds of tests/test_gpu_stream_project_far.py ----
+N32, HALF, A_START = (1 << 32) - 1, 1 << 31, (1 << 31) - 1500
+# (first frame, frames, frame_len, hop, rows, before, table) on a stream of 65537 SILENT blocks of 65535 samples, 2^32 - 1 in all: the
+# stream's last frame at hop 1; a first frame above 2^31; 2^15 frames at hop 65536; the frames at the products' bound (one row here:
+# the program prints its tables); then the two windows of the images test, whose second image begins behind word 2^32
+FAR_SPECS = [(N32 - 1, 1, 70, 1, 19, 69, 0), (N32 - 40, 40, 70, 1, 19, 0, 0), (HALF + 5, 150, 70, 1, 19, 0, 0), (0, 1 << 15, 8, 65536, 3, 0, 1), (65536 - 70, 70, 70, 65536, 19, 69, 0),
+             (HALF // 64 - (1 << 15), 1 << 16, 4096, 64, 1, 2048, 2), (0, 32769, 8, 65536, 3, 0, 1), (A_START - 100, 400, 70, 1, 19, 69, 0)]
+
+
+def test_plan_at_far_positions(programs):
+    """wxp_input's lo, hi and istride, and the image offsets of wx_project_record, against Python integers where first * hop, the input
+    range and the images pass 2^31 and 2^32"""
+    assert 65537 * 65535 == N32 and FAR_SPECS[0][0] == project_length(N32, 1) - 1
+    text = "0 65537 65535 %d %d\n" % (N32, len(FAR_SPECS)) + "".join(" ".join(str(v) for v in s) + "\n" for s in FAR_SPECS)
+    outs = []
+    for exe in programs:
+        r = subprocess.run([exe], input=text, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        outs.append(r.stdout)
+    assert outs[0] == outs[1]
+    got = [[int(v) for v in x.replace("|", " ").split()[1:16]] for x in outs[0].splitlines() if x.startswith("window ")]
+    want, img = [], 0
+    for i, (f0, n, N, H, K, before, table) in enumerate(FAR_SPECS):
+        assert f0 + n <= project_length(N32, H)
+        lo, hi = max(f0 * H - before, 0), min((f0 + n - 1) * H - before + N, N32)
+        istride = ((n - 1) * H + N + 3) // 4 * 4
+        want.append([i, lo, hi, 4 * (img + lo + before - f0 * H), istride, 0, 1, 0x1000 * (i + 1), 100000, K, 1, f0, n, img, istride])
+        img += 2 * istride
+    assert got == want
+    assert want[0][1:3] == [N32 - 70, N32] and want[1][2] == N32 and want[2][1] > HALF                 # the last frames end with the stream; a range above 2^31
+    assert want[3][4] == ((1 << 15) - 1) * 65536 + 8 and want[3][2] == want[3][4] and want[5][4] == 65535 * 64 + 4096      # 2^15 frames at the largest hop; the bound's frames
+    assert want[6][4] == HALF + 8 and want[7][13] == want[6][13] + (1 << 32) + 16 and want[7][13] > 1 << 32 and want[7][3] > 1 << 34   # the image behind word 2^32, its byte offset behind 2^34
+    tiles = sum(1 for x in outs[0].splitlines() if x.startswith("tile "))
+    assert tiles == sum(2 * -(-n // 64) * -(-K // 64) for _, n, _, _, K, _, _ in FAR_SPECS)
+
+
+# the rules at the far tests' shapes: the products' bound and one frame beyond it; the strides of the far tables and of the refused tiles
+FAR_INJECTIVE = [(((1 << 32) + 5, 2, 2, 3, 1, 2), True), ((7, 2, HALF + 3, 3, 1, 2), True), ((6, 2, HALF + 3, 3, 1, 2), True), ((7, 2, 13, 3, 1, 2), False),
+                 ((64 * 0xFFFFFF // 2 + 1, 2, 1, 64 * 0xFFFFFF // 2 + 1, 1, 1), True), ((64 * 0xFFFFFF // 2, 2, 1, 64 * 0xFFFFFF // 2 + 1, 1, 1), False),
+                 (((1 << 16) * 2048, 2, 2048, 1 << 16, 1, 2048), True), ((((1 << 16) + 1) * 2048, 2, 2048, (1 << 16) + 1, 1, 2048), True)]
+FAR_FITS = [((1 << 16, 2048, 4096, 2), True), (((1 << 16) + 1, 2048, 4096, 2), False), ((64 * 0xFFFFFF // 2 + 1, 1, 1, 2), True), ((32769, 3, 8, 2), True)]
+
+
 # (channel_stride, C, frame_stride, frames, row_stride, K) -> injective: both orders, padded strides, extents of 1, and the failures
-INJECTIVE = [((1000, 2, 5, 200, 1, 5), True), ((1000, 2, 1, 200, 200, 5), True), ((1400, 2, 7, 200, 1, 5), True), ((1, 2, 2, 200, 400, 5), True),
+INJECTIVE_NEAR = [((1000, 2, 5, 200, 1, 5), True), ((1000, 2, 1, 200, 200, 5), True), ((1400, 2, 7, 200, 1, 5), True), ((1, 2, 2, 200, 400, 5), True),
              ((999, 2, 5, 200, 1, 5), False), ((1000, 2, 4, 200, 1, 5), False), ((1000, 2, 1, 200, 199, 5), False), ((1000, 2, 5, 200, 0, 5), False),
              ((0, 1, 5, 200, 1, 5), True), ((0, 1, 0, 1, 0, 1), True), ((0, 1, 0, 1, 1, 5), True), ((0, 1, 0, 1, 0, 5), False), ((7, 2, 7, 1, 1, 5), True),
              ((5, 2, 0, 1, 1, 5), True), ((4, 2, 0, 1, 1, 5), False), ((1, 2, 2, 3, 6, 1), True), ((1 << 63, 2, 1 << 62, 2, 1 << 61, 2), True),
              (((1 << 64) - 1, 2, (1 << 63) + 1, 2, 1, 1 << 20), False), ((2, 8, 16, 3, 1, 2), True), ((2, 8, 15, 3, 1, 2), False)]
-FITS = [((1 << 40, 1, 1, 1), True), (((1 << 40) + 1, 1, 1, 1), False), ((1 << 17, 2048, 4096, 1), True), (((1 << 17) + 1, 2048, 4096, 1), False),
+FITS_NEAR = [((1 << 40, 1, 1, 1), True), (((1 << 40) + 1, 1, 1, 1), False), ((1 << 17, 2048, 4096, 1), True), (((1 << 17) + 1, 2048, 4096, 1), False),
         ((1 << 14, 2048, 4096, 8), True), (((1 << 14) + 1, 2048, 4096, 8), False), (((1 << 64) - 1, 2048, 4096, 8), False), ((1 << 41, 2048, 4096, 8), False),
         ((0, 2048, 4096, 8), True)]
 
 
 def test_the_injectivity_rule_and_the_products_cap(programs):
+    INJECTIVE, FITS = INJECTIVE_NEAR + FAR_INJECTIVE, FITS_NEAR + FAR_FITS
     text = "99\n" + "".join(" ".join(str(v) for v in a) + "\n" for a, _ in INJECTIVE) + "0 0 0 0 0 0\n" + "".join(" ".join(str(v) for v in a) + "\n" for a, _ in FITS)
     for exe in programs:
         r = subprocess.run([exe], input=text, capture_output=True, text=True)
